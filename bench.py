@@ -9,6 +9,11 @@ One step = zero_grad + CENet forward (video side native; text heads on the synth
 + global-batch similarity + MaxMarginRankingLoss + backward + Adam step, inputs resident in HBM.
 The text tower (HF bert-base, third party, out of scope) is replaced by synthetic (B,768) vectors.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what needs runs of its own: HIP-event
+probes of the leading kernel families (`roofline`, `roofline_top3`, live-row / executed-FLOP figures), the unpacked
+(`dense`) timing of the same step, the CPU baseline and, for --config 4, the similarity / loss row block.
+--dump-outputs DIR writes what the last timed step computed (its loss, a fixed sample of the updated weights) as .npy.
 """
 import argparse
 import json
@@ -349,6 +354,24 @@ def spawn_ranks(n):
   return rc
 
 
+DUMP_WEIGHTS_MAX = 8 * 1024 * 1024  # float32 values of the weight sample (32 MB): with the loss, well under 64 MB
+
+
+def dump_outputs(out_dir, loss, model):
+  """What a caller of the timed step receives from its last step: the loss (float64) and the weights the Adam update left
+  (float32, every floating-point entry of the state dict in its order, concatenated; a fixed seeded sample of
+  DUMP_WEIGHTS_MAX positions when there are more)."""
+  import numpy as np
+  os.makedirs(out_dir, exist_ok=True)
+  np.save(os.path.join(out_dir, 'loss.npy'), np.asarray([float(loss.item())], dtype=np.float64))
+  with torch.no_grad():
+    flat = torch.cat([v.detach().reshape(-1).float().cpu() for v in model.state_dict().values() if v.dtype.is_floating_point])
+  w = flat.numpy()
+  if w.size > DUMP_WEIGHTS_MAX:
+    w = w[np.sort(np.random.default_rng(0).integers(0, w.size, DUMP_WEIGHTS_MAX))]
+  np.save(os.path.join(out_dir, 'weights.npy'), np.ascontiguousarray(w, dtype=np.float32))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--gpus', type=int, default=1)
@@ -358,6 +381,11 @@ def main():
   ap.add_argument('--steps', type=int, default=50)
   ap.add_argument('--warmup', type=int, default=10)
   ap.add_argument('--dense', action='store_true', help='keep padded tokens (no variable-length packing)')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure what takes runs of its own: kernel probes and roofline, the unpacked step (unless '
+                       '--no-dense), the CPU baseline (unless --no-cpu-baseline), the configs[4] row block')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write the last timed step\'s outputs (loss, sampled weights) to DIR/<name>.npy (rank 0)')
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--grad-sync', choices=['auto', 'staged', 'single'], default='auto',
                   help='auto: staged backward with per-stage all-reduce when N > 1; staged/single force either')
@@ -409,6 +437,8 @@ def main():
                   help='N > 1: NCCL_DEBUG=INFO (RCCL prints the rings/trees and the algorithm + protocol of every collective)')
   args = ap.parse_args()
   select_config(args.config, args.dense)
+  if not args.full:
+    args.no_cpu_baseline = args.no_dense = True  # a plain run times the headline step only
   if args.config != 1:
     args.no_cpu_baseline = True  # the CPU port is timed on the headline shape only (a bounded sample of THAT workload)
   if args.ragged_inputs:
@@ -598,21 +628,23 @@ def main():
     exposed = runner.exposed_collective_ms()
     runner._exposed = []
     return dict(model=model, runner=runner, elapsed=elapsed, first_loss=first, final_loss=float(loss.item()), it=it,
-                exposed_ms=exposed)
+                exposed_ms=exposed, loss=loss)
 
   main_run = timed_run(not args.dense, args.steps, args.warmup)
   model, runner, elapsed, it = main_run['model'], main_run['runner'], main_run['elapsed'], main_run['it']
   main_first, main_final, exposed_ms = main_run['first_loss'], main_run['final_loss'], main_run['exposed_ms']
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, main_run['loss'], model)
 
-  # Kernel-family durations: HIP events around one launch per step of the three kernel families that lead the rocprof
-  # time table, recorded by the engine on the launch stream in eager steps of the same workload right after the timed
-  # region (events cannot be read back from inside a graph replay).
-  probe_steps = 8
+  # Kernel-family durations (--full): HIP events around one launch per step of the three kernel families that lead the
+  # rocprof time table, recorded by the engine on the launch stream in eager steps of the same workload right after the
+  # timed region (events cannot be read back from inside a graph replay).
+  probe_steps = 8 if args.full else 0
   towers = 2 if args.text_tower == 'native' else 1
   sites = [0, 1, 2, 3, 4] if towers == 1 else [0]
-  probes = {st: KernelProbe(probe_steps * towers, st) for st in sites} if rank == 0 else {}
+  probes = {st: KernelProbe(probe_steps * towers, st) for st in sites} if rank == 0 and args.full else {}
   live_rows, sq_sums = [], []
-  plan0 = model._plans[next(iter(model._plans))]
+  plan0 = model._plans[next(iter(model._plans))] if probe_steps else None
   for _ in range(probe_steps):
     runner.load(batches[it % NBATCH]); it += 1
     runner.eager_step()
@@ -650,12 +682,14 @@ def main():
   if world > 1:
     dist.barrier()
   if rank == 0:
-    live = int(round(sum(live_rows) / len(live_rows)))  # mean live token rows per launch over the probe steps
+    # (--full) mean live token rows per launch over the probe steps, and the FLOPs they execute
+    live = int(round(sum(live_rows) / len(live_rows))) if live_rows else None
     dense_rows = BATCH * seq
     pairs_per_s = world * BATCH * args.steps / elapsed
     flops = encoder_flops_per_step(BATCH, seq)
     rows = live if not args.dense else dense_rows
-    executed = executed_flops_per_step(BATCH, rows, sum(sq_sums) / len(sq_sums), len(synthetic.MSRVTT_MODALITIES))
+    executed = (executed_flops_per_step(BATCH, rows, sum(sq_sums) / len(sq_sums), len(synthetic.MSRVTT_MODALITIES))
+                if live_rows else None)
     out = {
         'metric': 'video-text pairs/sec (fwd+bwd+Adam), MSRVTT 7-expert d%d L%d' % (HIDDEN, LAYERS), 'value': pairs_per_s,
         'unit': 'pairs/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -683,16 +717,16 @@ def main():
                    'exposed_collective_ms_rank0': exposed_ms,
                    'comm_backend': (backend if world > 1 else None), 'comm_log': bool(args.comm_log),
                    'collectives_captured': bool(args.capture_collectives and (world > 1 or args.force_collectives)),
-                   'live_rows_rank0': live, 'dense_rows': dense_rows},
+                   'live_rows_rank0': live, 'dense_rows': dense_rows, 'full': bool(args.full)},
         # fraction of the (B, S) token grid that holds a real token in the synthetic batches (valid length ~ U{0..30}
         # per expert); the packed step computes only those, the dense step all of them.  The fill of real
         # MSRVTT features is unknown here (no dataset): `dense` below is the fill-independent number.
-        'fill_fraction': live / dense_rows,
+        'fill_fraction': live / dense_rows if live is not None else None,
         'dense': dense_run,
         'encoder_dense_tflops': pairs_per_s / BATCH * flops / 1e12 / world,
         'encoder_dense_mfma_frac': pairs_per_s / BATCH * flops / 1e12 / world / BF16_DENSE_PEAK_TFLOPS,
-        'executed_tflops': pairs_per_s / BATCH * executed / 1e12 / world,
-        'executed_mfma_frac': pairs_per_s / BATCH * executed / 1e12 / world / BF16_DENSE_PEAK_TFLOPS,
+        'executed_tflops': pairs_per_s / BATCH * executed / 1e12 / world if executed else None,
+        'executed_mfma_frac': pairs_per_s / BATCH * executed / 1e12 / world / BF16_DENSE_PEAK_TFLOPS if executed else None,
         'first_loss': main_first, 'final_loss': main_final,
     }
     tops = [site_roofline(st, rows, sec, used, sum(sq_sums) / len(sq_sums)) for st, (sec, used) in sorted(site_times.items()) if used]
@@ -735,7 +769,7 @@ def main():
                                                       frac=tb / tsec / 8e12, hbm_floor_ms=tb / 6.3e12 * 1e3)
     if world == 1 and not args.no_cpu_baseline:
       out['cpu_baseline'] = cpu_baseline()
-    if args.config == 4:
+    if args.config == 4 and args.full:
       out['similarity_loss_row_block'] = row_block_timing()
     # RCCL prints its version banner through C stdio, which is block-buffered on a pipe and would otherwise come out at
     # exit, AFTER the result: flush it first so that the JSON line is the last line of stdout

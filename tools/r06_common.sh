@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r06
 P=$R/profiles
 mkdir -p $O
-BENCH="--no-cpu-baseline --no-dense"
+BENCH="--full --no-cpu-baseline --no-dense"
 prof() {  # name, bench args [, env assignments]: rocprofv3 kernel trace of the bench command -> by-grid summary (txt + csv) + the replayed step's sequence
   rm -rf /tmp/prof && (cd /tmp && env $3 timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof -o step -- python $R/bench.py $2 $BENCH > $O/prof_$1.log 2>&1)
   DB=$(find /tmp/prof -name "*.db" | head -1)

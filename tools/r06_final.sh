@@ -20,9 +20,9 @@ pmc dense "--dense --steps 10 --warmup 3"; cp $O/pmc_dense.csv $P/r06_pmc_dense.
 pmc config3 "--config 3 --steps 6 --warmup 2"; cp $O/pmc_config3.csv $P/r06_pmc_config3.csv
 pmc config4 "--config 4 --steps 4 --warmup 2"; cp $O/pmc_config4.csv $P/r06_pmc_config4.csv
 pmc native_text_tower "--text-tower native --steps 6 --warmup 2"
-BENCH="--no-dense"
-(cd $R && timeout 900 python bench.py --steps 400 --warmup 20 > $O/bench_default_head.log 2>&1; tail -1 $O/bench_default_head.log > $O/bench_default_head.json; line $O/bench_default_head.json)
-BENCH="--no-cpu-baseline --no-dense"
+BENCH="--full --no-dense"
+(cd $R && timeout 900 python bench.py --full --steps 400 --warmup 20 > $O/bench_default_head.log 2>&1; tail -1 $O/bench_default_head.log > $O/bench_default_head.json; line $O/bench_default_head.json)
+BENCH="--full --no-cpu-baseline --no-dense"
 for i in 1 2; do fb bench_packed_$i "--steps 400 --warmup 20" "MMT_X=0"; done
 fb bench_dense "--dense --steps 200 --warmup 20" "MMT_X=0"
 fb bench_config3 "--config 3 --steps 100 --warmup 10" "MMT_X=0"
