@@ -515,6 +515,27 @@ int mmt_sims_eval(const float* txt, const float* vid, const float* tw, const flo
 int mmt_retrieval_ranks(const float* sims, const uint8_t* qmask, int NQ, int NV, float* t2v_rank, float* v2t_rank,
                         float* scratch, void* stream);
 
+/* ---- top-k retrieval (search.hip, fold in retrieval.hip) -------------------------------------------------------
+ * score(q, g) = sum_m qw[q][m] gw[g][m] <Q_m[q], G_m[g]> / sum_m qw[q][m] gw[g][m] (0 -> 1e-5), the 'indep' similarity
+ * of model/model.py:789-837.  Per query the min(k, NV) best (score, gallery index) pairs, score descending, equal scores
+ * by ascending index (a stable argsort; the reference's np.argsort leaves the order of exact ties unspecified).
+ * 1 <= k <= 128.  Deterministic (no atomics).  Never forms the NQ x NV matrix.
+ * mmt_search_fold: out = w (.) x for x [N][M][d] (d % 4 == 0, 16-byte aligned), w [N][M] -> out [N][M*d].
+ * mmt_topk_workspace_keys: uint64 workspace of mmt_search_topk / mmt_rows_topk, NQ * ceil(NV / chunk) * k with a
+ *   gallery chunk of 4096 columns (smaller only when the launch would not fill the chip); MMT_ERR_ARG if k or a size is
+ *   out of range.
+ * mmt_search_topk: qf = fold(Q, qw) [NQ][M*d], gf = fold(G, gw) [NV][M*d] (16-byte aligned), qw [NQ][M], gw [NV][M];
+ *   scores (nullable) fp32 / index int64 [NQ][min(k, NV)].  Fused fp32-MFMA scoring + selection, then a merge launch.
+ * mmt_rows_topk: the same selection on a given fp32 matrix (row stride ld), rows r = rows[i] for output row i (nullable:
+ *   i itself) -- utils/util.py:38-68 compress_predictions (trainer/trainer.py:411-437 'final_eval'; the visualiser's
+ *   ranking, utils/visualizer.py:74-92). */
+int mmt_search_fold(const float* x, const float* w, int N, int M, int d, float* out, void* stream);
+int64_t mmt_topk_workspace_keys(int NQ, int NV, int k);
+int mmt_search_topk(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                    int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
+int mmt_rows_topk(const float* sims, int64_t ld, const int32_t* rows, int NR, int NV, int k, uint64_t* ws, float* scores,
+                  int64_t* index, void* stream);
+
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as
  * model.py:789-837 + loss.py:38-65 without the [n,n,M] weight tensor or the 2n^2 index vectors.  The two big GEMMs

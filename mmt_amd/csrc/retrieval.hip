@@ -34,6 +34,16 @@ __global__ __launch_bounds__(256) void sims_normalise_kernel(float* __restrict__
   sims[(int64_t)t * NV + v] /= den;
 }
 
+// Folded operand of the top-k search (search.hip): out[r] = w[r][m] * x[r][m][:] over [N][M][d].
+extern "C" int mmt_search_fold(const float* x, const float* w, int N, int M, int d, float* out, void* stream) {
+  if (!x || !w || !out || N <= 0 || M <= 0 || M > MMT_MAX_EXPERTS || d <= 0 || (d & 3)) return MMT_ERR_ARG;
+  if (((uintptr_t)x | (uintptr_t)out) & 15) return MMT_ERR_ALIGN;
+  const int64_t n4 = (int64_t)N * M * d / 4;
+  hipLaunchKernelGGL(scale_rows_kernel, dim3((int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096)), dim3(256), 0,
+                     (hipStream_t)stream, x, w, n4, M, d, out);
+  return (int)hipGetLastError();
+}
+
 extern "C" int64_t mmt_sims_eval_workspace_floats(int NT, int NV, int M, int d) { return (int64_t)(NT + NV) * M * d; }
 
 extern "C" int mmt_sims_eval(const float* txt, const float* vid, const float* tw, const float* vw, int NT, int NV, int M,

@@ -1,0 +1,336 @@
+// Top-k retrieval without the N_query x N_gallery matrix (reference: utils/util.py:38-68 compress_predictions,
+// trainer/trainer.py:411-437, utils/visualizer.py:74-92; similarity of model/model.py:789-837 in 'indep' mode).
+//
+//   score(q, g) = sum_m qw[q][m] gw[g][m] <Q_m[q], G_m[g]> / sum_m qw[q][m] gw[g][m]     (0 -> 1e-5)
+//
+// Both operands arrive folded (Q' = qw * Q, G' = gw * G: mmt_search_fold), so the numerator is ONE fp32 GEMM with
+// K = M*d on v_mfma_f32_32x32x2_f32, like mmt_sims_eval.  Two launches:
+//   topk_chunk_kernel<true>  : block = 64 queries x one gallery chunk.  Per 128-column tile the K loop streams
+//                              through LDS in 32-wide slabs (register-staged: the next slab's global loads are in flight
+//                              during the current slab's MFMAs), the epilogue divides by the gated denominator and the
+//                              tile's 64 x 128 scores land in LDS, where each wave keeps a running top-k for its 16 rows
+//                              (threshold = k-th best so far; candidates above it are appended, the list is compacted
+//                              back to k when full).  The chunk's sorted k best go to the workspace.
+//   topk_chunk_kernel<false> : the same selection stage reading the scores from a given matrix (compress_predictions).
+//   topk_merge_kernel        : per query, the chunk lists merged by rank (each list is sorted: binary search).
+// Order: score descending, ties by ascending gallery index (= a stable argsort of -score).  A (score, index) pair is one
+// uint64 key -- order-preserving score bits above, ~index below -- so "better" is one unsigned compare and every key is
+// distinct; 0 is "no candidate".  No atomics: every output slot has exactly one writer, results are bit-reproducible.
+#include "mmt_common.h"
+#include "../../include/mmt_hip.h"
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+#define TK_Q 64                  // query rows per block (4 waves: 2 x 2 of 32 rows x 64 columns)
+#define TK_G 128                 // gallery columns per tile
+#define TK_BK 32                 // contraction slab
+#define TK_LD (TK_BK + 4)        // slab row pitch (floats): conflict-free ds_read_b128 across 16 consecutive rows
+#define TK_SLD (TK_G + 4)        // score tile row pitch
+#define TK_MAXK 128
+#define TK_CHUNK 4096            // gallery columns per block at full occupancy
+#define TK_FILL 512              // blocks wanted per launch before the chunk is allowed to shrink (2 per CU)
+#define TK_SLAB_BYTES ((TK_Q + TK_G) * TK_LD * 4)
+#define TK_TILE_BYTES (TK_Q * TK_SLD * 4)
+#define TK_UNION_BYTES (TK_TILE_BYTES > TK_SLAB_BYTES ? TK_TILE_BYTES : TK_SLAB_BYTES)
+#define TK_QW_BYTES (TK_Q * MMT_MAX_EXPERTS * 4)
+
+struct TkArgs {
+  const float* q;       // fused: Q' [NQ][K]        select: sims (row stride ld)
+  const float* qw;      // fused: query weights [NQ][M]
+  const float* g;       // fused: G' [NV][K]
+  const float* gw;      // fused: gallery weights [NV][M]
+  const int32_t* rows;  // select: source row of output row r (nullable = identity)
+  int64_t ld;
+  uint64_t* ws;         // [NQ][n_chunks][k]
+  int NQ, NV, M, K, k, chunk, n_qt, n_chunks;
+};
+
+__device__ __forceinline__ uint64_t tk_key(float s, int idx) {
+  unsigned u = __float_as_uint(s);
+  if (!(u & 0x7fffffffu)) u = 0;  // -0 ranks as +0 (numpy compares them equal)
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((uint64_t)u << 32) | (uint64_t)(~(unsigned)idx);
+}
+__device__ __forceinline__ float tk_score(uint64_t key) {
+  const unsigned u = (unsigned)(key >> 32);
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+__device__ __forceinline__ int tk_index(uint64_t key) { return (int)~(unsigned)key; }
+
+// One wave, one row: rank-sort the n (<= k + 64 <= 192) candidates c[0..n) and keep the best min(n, k) in c[0..) in
+// descending order.
+__device__ __forceinline__ void tk_compact(uint64_t* c, int n, int k, int lane) {
+  uint64_t v[3];
+  int rk[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int i = lane + 64 * j;
+    v[j] = i < n ? c[i] : 0;
+    rk[j] = 0;
+  }
+  for (int i = 0; i < n; ++i) {
+    const uint64_t x = c[i];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) rk[j] += x > v[j];
+  }
+  __builtin_amdgcn_wave_barrier();  // every lane's reads above precede any rewrite (one wave: LDS ops stay in order)
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    if (lane + 64 * j < n && rk[j] < k) c[rk[j]] = v[j];
+  __builtin_amdgcn_wave_barrier();
+}
+
+// One wave, one row: offers one key per lane (0 = none).  Keys at or below the threshold (the k-th best so far) cannot
+// enter the top k; the others are appended.  Capacity k + 64: the list is compacted first whenever it holds more than k.
+__device__ __forceinline__ void tk_push(uint64_t* c, int& n, uint64_t& thr, int k, uint64_t key, int lane) {
+  if (n > k) {
+    tk_compact(c, n, k, lane);
+    n = k;
+    thr = c[k - 1];
+  }
+  const bool take = key > thr;
+  const uint64_t mask = __ballot(take);
+  if (take) c[n + __popcll(mask & ((1ull << lane) - 1ull))] = key;
+  n += __popcll(mask);
+}
+
+// The chunk's best min(n, k) keys of one row, sorted, padded with 0 to k.
+__device__ __forceinline__ void tk_flush(uint64_t* c, int n, int k, int lane, uint64_t* dst) {
+  if (n > 0) tk_compact(c, n, k, lane);
+  const int have = n < k ? n : k;
+  for (int j = lane; j < k; j += 64) dst[j] = j < have ? c[j] : 0ull;
+}
+
+template <bool FUSED>
+__global__ __launch_bounds__(256) void topk_chunk_kernel(TkArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);  // gallery-chunk-major: an XCD's blocks share their chunk in L2
+  const int chunk = bid / a.n_qt, q0 = (bid % a.n_qt) * TK_Q;
+  const int g_begin = chunk * a.chunk, g_end = min(a.NV, g_begin + a.chunk);
+  const int cap = a.k + 64;
+  uint64_t* ws = a.ws + chunk * (int64_t)a.k;
+  const int64_t ws_row = (int64_t)a.n_chunks * a.k;
+
+  if constexpr (!FUSED) {
+    uint64_t* cand = (uint64_t*)smem + (int64_t)wave * cap;
+    for (int rr = 0; rr < TK_Q / 4; ++rr) {
+      const int q = q0 + wave * (TK_Q / 4) + rr;
+      if (q >= a.NQ) break;
+      const float* row = a.q + (a.rows ? (int64_t)a.rows[q] : (int64_t)q) * a.ld;
+      int n = 0;
+      uint64_t thr = 0;
+      for (int g0 = g_begin; g0 < g_end; g0 += 64) {
+        const int g = g0 + lane;
+        tk_push(cand, n, thr, a.k, g < g_end ? tk_key(row[g], g) : 0ull, lane);
+      }
+      tk_flush(cand, n, a.k, lane, ws + q * ws_row);
+    }
+    return;
+  } else {
+    float* sA = (float*)smem;                                  // [TK_Q][TK_LD]   slab of Q'
+    float* sB = sA + TK_Q * TK_LD;                             // [TK_G][TK_LD]   slab of G'
+    float* sS = (float*)smem;                                  // [TK_Q][TK_SLD]  scores (after the K loop)
+    float* sQw = (float*)(smem + TK_UNION_BYTES);              // [TK_Q][MMT_MAX_EXPERTS]
+    int* sN = (int*)(smem + TK_UNION_BYTES + TK_QW_BYTES);     // [TK_Q] candidates held
+    uint64_t* sT = (uint64_t*)(sN + TK_Q);                     // [TK_Q] thresholds
+    uint64_t* sC = sT + TK_Q;                                  // [TK_Q][cap] candidates
+    const int l31 = lane & 31, h = lane >> 5, wq = wave >> 1, wg = wave & 1;
+    const int K = a.K, M = a.M;
+    if (tid < TK_Q) { sN[tid] = 0; sT[tid] = 0; }
+    for (int i = tid; i < TK_Q * MMT_MAX_EXPERTS; i += 256) {
+      const int r = i / MMT_MAX_EXPERTS, m = i % MMT_MAX_EXPERTS;
+      sQw[i] = (q0 + r < a.NQ && m < M) ? a.qw[(int64_t)(q0 + r) * M + m] : 0.f;
+    }
+    for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
+      f32x16 acc[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+      // staging: Q' slab = 64 rows x 8 f32x4 (2 per thread), G' slab = 128 rows x 8 f32x4 (4 per thread)
+      f32x4 ra[2], rb[4];
+      auto load = [&](int kb) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 4;
+          ra[j] = (q0 + r < a.NQ && c < K) ? *(const f32x4*)(a.q + (int64_t)(q0 + r) * K + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 4;
+          rb[j] = (g0 + r < g_end && c < K) ? *(const f32x4*)(a.g + (int64_t)(g0 + r) * K + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      };
+      load(0);
+      for (int kb = 0; kb < K; kb += TK_BK) {
+        __syncthreads();  // previous slab (or the previous tile's scores) consumed
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { const int i = tid + 256 * j; *(f32x4*)(sA + (i >> 3) * TK_LD + (i & 7) * 4) = ra[j]; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int i = tid + 256 * j; *(f32x4*)(sB + (i >> 3) * TK_LD + (i & 7) * 4) = rb[j]; }
+        __syncthreads();
+        if (kb + TK_BK < K) load(kb + TK_BK);
+        // 8 contraction values per step = 4 MFMAs per accumulator; lane half h feeds k = kk + 4h + u to MFMA u
+#pragma unroll
+        for (int kk = 0; kk < TK_BK; kk += 8) {
+          const f32x4 av = *(const f32x4*)(sA + (wq * 32 + l31) * TK_LD + kk + 4 * h);
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            const f32x4 bv = *(const f32x4*)(sB + (wg * 64 + t * 32 + l31) * TK_LD + kk + 4 * h);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc[t], 0, 0, 0);
+          }
+        }
+      }
+      __syncthreads();  // the slabs become the score tile
+      // epilogue: lane holds column wg*64 + t*32 + l31, rows wq*32 + (r&3) + 8*(r>>2) + 4h
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int col = wg * 64 + t * 32 + l31, g = g0 + col;
+        float den[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) den[r] = 0.f;
+        for (int m = 0; m < M; ++m) {
+          const float gwm = g < g_end ? a.gw[(int64_t)g * M + m] : 0.f;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) den[r] += sQw[(wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * MMT_MAX_EXPERTS + m] * gwm;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+          sS[row * TK_SLD + col] = acc[t][r] / (den[r] == 0.f ? 1e-5f : den[r]);
+        }
+      }
+      __syncthreads();
+      // selection: wave w owns rows 16w .. 16w + 15; columns in increasing index order
+      for (int rr = 0; rr < TK_Q / 4; ++rr) {
+        const int row = wave * (TK_Q / 4) + rr;
+        if (q0 + row >= a.NQ) break;
+        int n = sN[row];
+        uint64_t thr = sT[row];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          const int col = half * 64 + lane, g = g0 + col;
+          tk_push(sC + row * cap, n, thr, a.k, g < g_end ? tk_key(sS[row * TK_SLD + col], g) : 0ull, lane);
+        }
+        if (lane == 0) { sN[row] = n; sT[row] = thr; }
+      }
+    }
+    __syncthreads();
+    for (int rr = 0; rr < TK_Q / 4; ++rr) {
+      const int row = wave * (TK_Q / 4) + rr, q = q0 + row;
+      if (q >= a.NQ) break;
+      tk_flush(sC + row * cap, sN[row], a.k, lane, ws + q * ws_row);
+    }
+  }
+}
+
+// One block per query: the n_chunks sorted lists of k keys -> the best kout, by rank.  A key at position j of its list
+// has rank j + (number of keys above it in every other list); only the first kout of a list can matter.
+__global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restrict__ ws, int n_chunks, int k, int kout,
+                                                         int stage, float* __restrict__ scores, int64_t* __restrict__ index) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int q = blockIdx.x, n = n_chunks * k;
+  const uint64_t* L = ws + (int64_t)q * n;
+  if (stage) {  // the lists fit in LDS
+    uint64_t* s = (uint64_t*)smem;
+    for (int i = threadIdx.x; i < n; i += 256) s[i] = L[i];
+    __syncthreads();
+    L = s;
+  }
+  const int lim = min(k, kout);
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int c = i / k, j = i - c * k;
+    if (j >= kout) continue;
+    const uint64_t key = L[i];
+    if (!key) continue;
+    int rank = j;
+    for (int c2 = 0; c2 < n_chunks && rank < kout; ++c2) {
+      if (c2 == c) continue;
+      const uint64_t* l = L + (int64_t)c2 * k;
+      int lo = 0, hi = lim;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (l[mid] > key) lo = mid + 1;
+        else hi = mid;
+      }
+      rank += lo;
+    }
+    if (rank < kout) {
+      if (scores) scores[(int64_t)q * kout + rank] = tk_score(key);
+      index[(int64_t)q * kout + rank] = tk_index(key);
+    }
+  }
+}
+
+namespace {
+constexpr int kMergeLdsMax = 64 * 1024;
+
+// Gallery columns per block: TK_CHUNK, halved (down to one tile) while the launch would not fill the chip.  A smaller
+// chunk only happens when n_qt * n_chunks < TK_FILL, so the workspace stays below TK_FILL * TK_Q * k keys then.
+int tk_chunk(int NQ, int NV) {
+  const int64_t n_qt = (NQ + TK_Q - 1) / TK_Q;
+  int chunk = TK_CHUNK;
+  while (chunk > TK_G && n_qt * ((NV + chunk - 1) / chunk) < TK_FILL) chunk >>= 1;
+  return chunk;
+}
+
+size_t tk_fused_lds(int k) { return TK_UNION_BYTES + TK_QW_BYTES + TK_Q * (4 + 8) + (size_t)TK_Q * (k + 64) * 8; }
+size_t tk_select_lds(int k) { return (size_t)4 * (k + 64) * 8; }
+
+bool tk_args_ok(int NQ, int NV, int k) { return NQ > 0 && NV > 0 && k >= 1 && k <= TK_MAXK; }
+
+int tk_launch(TkArgs a, bool fused, int kout, float* scores, int64_t* index, hipStream_t s) {
+  static const bool attrs = [] {  // allow the k = 128 footprint (over the 64 KiB default)
+    (void)hipFuncSetAttribute((const void*)topk_chunk_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                        (int)tk_fused_lds(TK_MAXK));
+    return true;
+  }();
+  (void)attrs;
+  const int blocks = a.n_qt * a.n_chunks;
+  if (fused)
+    hipLaunchKernelGGL(topk_chunk_kernel<true>, dim3(blocks), dim3(256), tk_fused_lds(a.k), s, a);
+  else
+    hipLaunchKernelGGL(topk_chunk_kernel<false>, dim3(blocks), dim3(256), tk_select_lds(a.k), s, a);
+  const int64_t list_bytes = (int64_t)a.n_chunks * a.k * 8;
+  const int stage = list_bytes <= kMergeLdsMax;
+  hipLaunchKernelGGL(topk_merge_kernel, dim3(a.NQ), dim3(256), stage ? (size_t)list_bytes : 0, s, a.ws, a.n_chunks,
+                     a.k, kout, stage, scores, index);
+  return (int)hipGetLastError();
+}
+
+TkArgs tk_args(int NQ, int NV, int k, uint64_t* ws) {
+  TkArgs a = {};
+  a.NQ = NQ; a.NV = NV; a.k = k; a.ws = ws;
+  a.chunk = tk_chunk(NQ, NV);
+  a.n_qt = (NQ + TK_Q - 1) / TK_Q;
+  a.n_chunks = (NV + a.chunk - 1) / a.chunk;
+  return a;
+}
+}  // namespace
+
+extern "C" int64_t mmt_topk_workspace_keys(int NQ, int NV, int k) {
+  if (!tk_args_ok(NQ, NV, k)) return MMT_ERR_ARG;
+  const int chunk = tk_chunk(NQ, NV);
+  return (int64_t)NQ * ((NV + chunk - 1) / chunk) * k;
+}
+
+extern "C" int mmt_search_topk(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
+                               int d, int k, uint64_t* ws, float* scores, int64_t* index, void* stream) {
+  if (!qf || !qw || !gf || !gw || !ws || !index || !tk_args_ok(NQ, NV, k) || M <= 0 || M > MMT_MAX_EXPERTS || d <= 0 ||
+      (d & 3))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)qf | (uintptr_t)gf) & 15) return MMT_ERR_ALIGN;
+  TkArgs a = tk_args(NQ, NV, k, ws);
+  a.q = qf; a.qw = qw; a.g = gf; a.gw = gw; a.M = M; a.K = M * d;
+  return tk_launch(a, true, k < NV ? k : NV, scores, index, (hipStream_t)stream);
+}
+
+extern "C" int mmt_rows_topk(const float* sims, int64_t ld, const int32_t* rows, int NR, int NV, int k, uint64_t* ws,
+                             float* scores, int64_t* index, void* stream) {
+  if (!sims || !ws || !index || !tk_args_ok(NR, NV, k) || ld < NV) return MMT_ERR_ARG;
+  TkArgs a = tk_args(NR, NV, k, ws);
+  a.q = sims; a.ld = ld; a.rows = rows;
+  return tk_launch(a, false, k < NV ? k : NV, scores, index, (hipStream_t)stream);
+}

@@ -95,3 +95,36 @@ def retrieval_metrics(vid_embds, text_embds, vid_weights, text_weights, query_ma
   """Embeddings of the whole eval set -> {'t2v_metrics': {...}, 'v2t_metrics': {...}} without an n^2 host copy."""
   sims = eval_similarity(vid_embds, text_embds, vid_weights, text_weights)
   return {'t2v_metrics': t2v_metrics(sims, query_masks), 'v2t_metrics': v2t_metrics(sims, query_masks)}
+
+
+def compress_predictions(query_masks, sims, topk=10):
+  """Drop-in for utils/util.py:38-68 (trainer/trainer.py:411-437, sets == 'final_eval'): the masked query rows are dropped
+  and each remaining row of `sims` keeps the indices of its `topk` highest columns, best first -> numpy int64
+  [n_valid, min(topk, N_video)].  The selection runs on the device (mmt_rows_topk): a numpy `sims` is uploaded once, a
+  CUDA tensor never leaves HBM; only the index rows come back.  Equal scores come out by ascending column index (a stable
+  argsort); the reference's quicksort argsort leaves their order unspecified, the one place the two can differ."""
+  qm = np.asarray(query_masks.cpu() if torch.is_tensor(query_masks) else query_masks)
+  assert qm.ndim == 2, 'Expected query_masks to be a matrix'
+  query_num_videos, query_max_per_video = qm.shape
+  sims_queries, sims_num_videos = tuple(sims.shape)
+  msg = (f'Expected sims and query masks to represent the same number of videos '
+         f'(found {sims_num_videos} v {query_num_videos}')
+  assert query_num_videos == sims_num_videos, msg
+  msg = (f'Expected sims and query masks to represent the same number of queries '
+         f'(found {sims_queries} v {query_num_videos * query_max_per_video}')
+  assert query_max_per_video * query_num_videos == sims_queries, msg
+  kout = min(int(topk), sims_num_videos)
+  if kout < 1 or kout > 128:
+    raise ValueError('compress_predictions: topk must give 1..128 columns, got topk=%r for %d videos' % (topk, sims_num_videos))
+  rows = np.flatnonzero(qm.reshape(-1).astype(bool)).astype(np.int32)
+  if rows.size == 0:
+    return np.zeros((0, kout), dtype=np.int64)
+  sims = _as_cuda_f32(sims)
+  dev = sims.device
+  rows_d = torch.from_numpy(rows).to(dev)
+  L = _lib.lib()
+  ws = torch.empty(L.mmt_topk_workspace_keys(rows.size, sims_num_videos, kout), device=dev, dtype=torch.int64)
+  index = torch.empty(rows.size, kout, device=dev, dtype=torch.int64)
+  check(L.mmt_rows_topk(ops._p(sims), sims.stride(0), ops._p(rows_d), rows.size, sims_num_videos, kout, ops._p(ws), None,
+                        ops._p(index), ops._stream()), 'mmt_rows_topk')
+  return index.cpu().numpy()

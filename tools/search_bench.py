@@ -1,0 +1,120 @@
+"""Top-k text-to-video search: fused score + select (search.VideoIndex.search) against the materialised path (the
+N_query x N_video similarity of metric.eval_similarity, then the device compress_predictions), M = 7, d = 512, k = 10.
+
+  S1  1 000 x 1 000      MSRVTT 1k-A size
+  S2  4 917 x 4 917      ActivityNet val1 size
+  S3  4 096 x 262 144    gallery search
+
+Times with device events after warm-up, over >= --min-seconds of work per point; reports peak allocator growth,
+FLOP/s from 2 NQ NV M d and the fraction of the 157.3 TF fp32 matrix peak.  At S1 / S2 (one caption per video) the
+materialised path is the public eval_similarity + compress_predictions; at S3 (NQ != NV * captions, which those
+functions require) it is their kernels, mmt_sims_eval + mmt_rows_topk.
+   python tools/search_bench.py [--shapes S1,S2,S3] [--out profiles/search_bench.json] [--min-seconds 0.5]"""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mmt_amd import _lib, metric, ops  # noqa: E402
+from mmt_amd.search import VideoIndex  # noqa: E402
+
+SHAPES = {'S1': (1000, 1000), 'S2': (4917, 4917), 'S3': (4096, 262144)}
+PEAK = 157.3e12
+M, D, K = 7, 512, 10
+
+
+def materialised_kernels(q, qw, g, gw, k):
+  nq, nv = q.shape[0], g.shape[0]
+  L = _lib.lib()
+  ws = torch.empty(L.mmt_sims_eval_workspace_floats(nq, nv, M, D), device=q.device)
+  sims = torch.empty(nq, nv, device=q.device)
+  _lib.check(L.mmt_sims_eval(ops._p(q), ops._p(g), ops._p(qw), ops._p(gw), nq, nv, M, D, ops._p(ws), ops._p(sims),
+                             ops._stream()), 'mmt_sims_eval')
+  del ws
+  tk = torch.empty(L.mmt_topk_workspace_keys(nq, nv, k), device=q.device, dtype=torch.int64)
+  idx = torch.empty(nq, k, device=q.device, dtype=torch.int64)
+  _lib.check(L.mmt_rows_topk(ops._p(sims), nv, None, nq, nv, k, ops._p(tk), None, ops._p(idx), ops._stream()),
+             'mmt_rows_topk')
+  return idx.cpu().numpy()
+
+
+def materialised_public(q, qw, g, gw, k):
+  nv = g.shape[0]
+  sims = metric.eval_similarity(g, q.unsqueeze(2), gw, qw.unsqueeze(1))
+  return metric.compress_predictions(np.ones((nv, 1), np.float32), sims, topk=k)
+
+
+def timed(fn, min_seconds):
+  fn()
+  torch.cuda.synchronize()
+  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  e0.record()
+  fn()
+  e1.record()
+  torch.cuda.synchronize()
+  once = e0.elapsed_time(e1) / 1e3
+  iters = max(3, math.ceil(min_seconds / max(once, 1e-6)))
+  base = torch.cuda.memory_allocated()
+  torch.cuda.reset_peak_memory_stats()
+  e0.record()
+  for _ in range(iters):
+    out = fn()
+  e1.record()
+  torch.cuda.synchronize()
+  return e0.elapsed_time(e1) / 1e3 / iters, iters, torch.cuda.max_memory_allocated() - base, out
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--shapes', default='S1,S2,S3')
+  ap.add_argument('--out', default=None)
+  ap.add_argument('--min-seconds', type=float, default=0.5)
+  ap.add_argument('--skip-materialised', action='store_true', help='fused path only (kernel-trace runs)')
+  a = ap.parse_args()
+  if not torch.cuda.is_available():
+    raise SystemExit('search_bench needs the GPU')
+  dev = torch.device('cuda', 0)
+  res = {'M': M, 'd': D, 'k': K, 'peak_fp32_matrix_flops': PEAK, 'device': torch.cuda.get_device_name(0), 'shapes': {}}
+  for name in a.shapes.split(','):
+    nq, nv = SHAPES[name]
+    gen = torch.Generator(device=dev).manual_seed(0)
+    nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
+    g = nrm(torch.randn(nv, M, D, device=dev, generator=gen))
+    gw = torch.softmax(torch.randn(nv, M, device=dev, generator=gen), -1)
+    q = nrm(torch.randn(nq, M, D, device=dev, generator=gen) + 0.3 * g[torch.arange(nq, device=dev) % nv])
+    qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
+    flop = 2.0 * nq * nv * M * D
+    row = {'NQ': nq, 'NV': nv, 'flop': flop}
+    index = VideoIndex(g, gw)
+    t, it, mem, (s, i) = timed(lambda: index.search(q, qw, k=K), a.min_seconds)
+    row['fused'] = dict(seconds=t, iters=it, peak_mem_growth_bytes=mem, tflops=flop / t / 1e12,
+                        fraction_of_peak=flop / t / PEAK)
+    fused_idx = i.cpu().numpy()
+    del index
+    if not a.skip_materialised:
+      fn = materialised_public if nq == nv else materialised_kernels
+      t, it, mem, idx = timed(lambda: fn(q, qw, g, gw, K), a.min_seconds)
+      row['materialised'] = dict(path='eval_similarity + compress_predictions' if nq == nv else
+                                 'mmt_sims_eval + mmt_rows_topk', seconds=t, iters=it, peak_mem_growth_bytes=mem,
+                                 tflops=flop / t / 1e12, fraction_of_peak=flop / t / PEAK)
+      row['fused_speedup'] = row['materialised']['seconds'] / row['fused']['seconds']
+      row['memory_ratio'] = row['fused']['peak_mem_growth_bytes'] / max(1, row['materialised']['peak_mem_growth_bytes'])
+      row['rows_identical'] = float((fused_idx == idx).all(1).mean())
+    res['shapes'][name] = row
+    print(name, json.dumps(row), flush=True)
+    del g, gw, q, qw
+    torch.cuda.empty_cache()
+  if a.out:
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+      json.dump(res, f, indent=1)
+  print(json.dumps(res))
+
+
+if __name__ == '__main__':
+  main()
