@@ -515,7 +515,7 @@ int mmt_sims_eval(const float* txt, const float* vid, const float* tw, const flo
 int mmt_retrieval_ranks(const float* sims, const uint8_t* qmask, int NQ, int NV, float* t2v_rank, float* v2t_rank,
                         float* scratch, void* stream);
 
-/* ---- top-k retrieval (search.hip, fold in retrieval.hip) -------------------------------------------------------
+/* ---- top-k retrieval (search.hip, search_bf16.hip, fold in retrieval.hip) --------------------------------------
  * score(q, g) = sum_m qw[q][m] gw[g][m] <Q_m[q], G_m[g]> / sum_m qw[q][m] gw[g][m] (0 -> 1e-5), the 'indep' similarity
  * of model/model.py:789-837.  Per query the min(k, NV) best (score, gallery index) pairs, score descending, equal scores
  * by ascending index (a stable argsort; the reference's np.argsort leaves the order of exact ties unspecified).
@@ -535,6 +535,22 @@ int mmt_search_topk(const float* qf, const float* qw, const float* gf, const flo
                     int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
 int mmt_rows_topk(const float* sims, int64_t ld, const int32_t* rows, int NR, int NV, int k, uint64_t* ws, float* scores,
                   int64_t* index, void* stream);
+/* bf16-stored gallery (search_bf16.hip).  The index keeps bf16(gw (.) G): the fp32 fold rounded once, round-to-nearest-
+ * even.  Only storage is lossy; the score is defined on the stored value,
+ *   score(q, g) = < fold_fp32(Q, qw)[q], dequant(stored[g]) > / sum_m qw[q][m] gw[g][m] (0 -> 1e-5),
+ * with the fp32 query carried as hi = bf16(qf), lo = bf16(qf - hi) (two bf16 MFMAs per gallery fragment, fp32
+ * accumulation; residual < 2^-16 relative per query element).  Against the fp32 index a score moves by at most
+ * 2^-8 * sum_m qw gw <|Q_m|, |G_m|> / sum_m qw gw.  Order, ties, k range, determinism and workspace
+ * (mmt_topk_workspace_keys) as for mmt_search_topk.  d % 8 == 0 (16-byte bf16 rows), pointers 16-byte aligned.
+ * mmt_search_fold_bf16: out = bf16(w (.) x) [N][M*d]; out may point at a row of a larger preallocated buffer.
+ * mmt_search_fold_split_bf16: the query pair hi, lo [N][M*d] in one launch.
+ * mmt_search_topk_bf16: q_hi / q_lo [NQ][M*d], gf [NV][M*d] bf16 bits; qw [NQ][M], gw [NV][M] fp32; outputs as
+ *   mmt_search_topk. */
+int mmt_search_fold_bf16(const float* x, const float* w, int N, int M, int d, uint16_t* out, void* stream);
+int mmt_search_fold_split_bf16(const float* x, const float* w, int N, int M, int d, uint16_t* hi, uint16_t* lo,
+                               void* stream);
+int mmt_search_topk_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
+                         int NQ, int NV, int M, int d, int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

@@ -16,23 +16,14 @@
 // Order: score descending, ties by ascending gallery index (= a stable argsort of -score).  A (score, index) pair is one
 // uint64 key -- order-preserving score bits above, ~index below -- so "better" is one unsigned compare and every key is
 // distinct; 0 is "no candidate".  No atomics: every output slot has exactly one writer, results are bit-reproducible.
-#include "mmt_common.h"
-#include "../../include/mmt_hip.h"
+// The key, the running top-k and the tile epilogue live in search_topk.h, shared with the bf16-gallery kernel
+// (search_bf16.hip).
+#include "search_topk.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-#define TK_Q 64                  // query rows per block (4 waves: 2 x 2 of 32 rows x 64 columns)
-#define TK_G 128                 // gallery columns per tile
 #define TK_BK 32                 // contraction slab
 #define TK_LD (TK_BK + 4)        // slab row pitch (floats): conflict-free ds_read_b128 across 16 consecutive rows
-#define TK_SLD (TK_G + 4)        // score tile row pitch
-#define TK_MAXK 128
-#define TK_CHUNK 4096            // gallery columns per block at full occupancy
-#define TK_FILL 512              // blocks wanted per launch before the chunk is allowed to shrink (2 per CU)
 #define TK_SLAB_BYTES ((TK_Q + TK_G) * TK_LD * 4)
-#define TK_TILE_BYTES (TK_Q * TK_SLD * 4)
 #define TK_UNION_BYTES (TK_TILE_BYTES > TK_SLAB_BYTES ? TK_TILE_BYTES : TK_SLAB_BYTES)
-#define TK_QW_BYTES (TK_Q * MMT_MAX_EXPERTS * 4)
 
 struct TkArgs {
   const float* q;       // fused: Q' [NQ][K]        select: sims (row stride ld)
@@ -44,62 +35,6 @@ struct TkArgs {
   uint64_t* ws;         // [NQ][n_chunks][k]
   int NQ, NV, M, K, k, chunk, n_qt, n_chunks;
 };
-
-__device__ __forceinline__ uint64_t tk_key(float s, int idx) {
-  unsigned u = __float_as_uint(s);
-  if (!(u & 0x7fffffffu)) u = 0;  // -0 ranks as +0 (numpy compares them equal)
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | (uint64_t)(~(unsigned)idx);
-}
-__device__ __forceinline__ float tk_score(uint64_t key) {
-  const unsigned u = (unsigned)(key >> 32);
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-__device__ __forceinline__ int tk_index(uint64_t key) { return (int)~(unsigned)key; }
-
-// One wave, one row: rank-sort the n (<= k + 64 <= 192) candidates c[0..n) and keep the best min(n, k) in c[0..) in
-// descending order.
-__device__ __forceinline__ void tk_compact(uint64_t* c, int n, int k, int lane) {
-  uint64_t v[3];
-  int rk[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int i = lane + 64 * j;
-    v[j] = i < n ? c[i] : 0;
-    rk[j] = 0;
-  }
-  for (int i = 0; i < n; ++i) {
-    const uint64_t x = c[i];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) rk[j] += x > v[j];
-  }
-  __builtin_amdgcn_wave_barrier();  // every lane's reads above precede any rewrite (one wave: LDS ops stay in order)
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-    if (lane + 64 * j < n && rk[j] < k) c[rk[j]] = v[j];
-  __builtin_amdgcn_wave_barrier();
-}
-
-// One wave, one row: offers one key per lane (0 = none).  Keys at or below the threshold (the k-th best so far) cannot
-// enter the top k; the others are appended.  Capacity k + 64: the list is compacted first whenever it holds more than k.
-__device__ __forceinline__ void tk_push(uint64_t* c, int& n, uint64_t& thr, int k, uint64_t key, int lane) {
-  if (n > k) {
-    tk_compact(c, n, k, lane);
-    n = k;
-    thr = c[k - 1];
-  }
-  const bool take = key > thr;
-  const uint64_t mask = __ballot(take);
-  if (take) c[n + __popcll(mask & ((1ull << lane) - 1ull))] = key;
-  n += __popcll(mask);
-}
-
-// The chunk's best min(n, k) keys of one row, sorted, padded with 0 to k.
-__device__ __forceinline__ void tk_flush(uint64_t* c, int n, int k, int lane, uint64_t* dst) {
-  if (n > 0) tk_compact(c, n, k, lane);
-  const int have = n < k ? n : k;
-  for (int j = lane; j < k; j += 64) dst[j] = j < have ? c[j] : 0ull;
-}
 
 template <bool FUSED>
 __global__ __launch_bounds__(256) void topk_chunk_kernel(TkArgs a) {
@@ -184,38 +119,9 @@ __global__ __launch_bounds__(256) void topk_chunk_kernel(TkArgs a) {
         }
       }
       __syncthreads();  // the slabs become the score tile
-      // epilogue: lane holds column wg*64 + t*32 + l31, rows wq*32 + (r&3) + 8*(r>>2) + 4h
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int col = wg * 64 + t * 32 + l31, g = g0 + col;
-        float den[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) den[r] = 0.f;
-        for (int m = 0; m < M; ++m) {
-          const float gwm = g < g_end ? a.gw[(int64_t)g * M + m] : 0.f;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) den[r] += sQw[(wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * MMT_MAX_EXPERTS + m] * gwm;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          sS[row * TK_SLD + col] = acc[t][r] / (den[r] == 0.f ? 1e-5f : den[r]);
-        }
-      }
+      tk_tile_scores(acc, sS, sQw, a.gw, M, g0, g_end, wq, wg, l31, h);
       __syncthreads();
-      // selection: wave w owns rows 16w .. 16w + 15; columns in increasing index order
-      for (int rr = 0; rr < TK_Q / 4; ++rr) {
-        const int row = wave * (TK_Q / 4) + rr;
-        if (q0 + row >= a.NQ) break;
-        int n = sN[row];
-        uint64_t thr = sT[row];
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          const int col = half * 64 + lane, g = g0 + col;
-          tk_push(sC + row * cap, n, thr, a.k, g < g_end ? tk_key(sS[row * TK_SLD + col], g) : 0ull, lane);
-        }
-        if (lane == 0) { sN[row] = n; sT[row] = thr; }
-      }
+      tk_tile_select(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane);
     }
     __syncthreads();
     for (int rr = 0; rr < TK_Q / 4; ++rr) {
@@ -264,9 +170,6 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restr
   }
 }
 
-namespace {
-constexpr int kMergeLdsMax = 64 * 1024;
-
 // Gallery columns per block: TK_CHUNK, halved (down to one tile) while the launch would not fill the chip.  A smaller
 // chunk only happens when n_qt * n_chunks < TK_FILL, so the workspace stays below TK_FILL * TK_Q * k keys then.
 int tk_chunk(int NQ, int NV) {
@@ -276,10 +179,23 @@ int tk_chunk(int NQ, int NV) {
   return chunk;
 }
 
-size_t tk_fused_lds(int k) { return TK_UNION_BYTES + TK_QW_BYTES + TK_Q * (4 + 8) + (size_t)TK_Q * (k + 64) * 8; }
-size_t tk_select_lds(int k) { return (size_t)4 * (k + 64) * 8; }
-
 bool tk_args_ok(int NQ, int NV, int k) { return NQ > 0 && NV > 0 && k >= 1 && k <= TK_MAXK; }
+
+size_t tk_state_lds(int k) { return TK_QW_BYTES + TK_Q * (4 + 8) + (size_t)TK_Q * (k + 64) * 8; }
+
+int tk_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, float* scores, int64_t* index,
+                    hipStream_t s) {
+  constexpr int kMergeLdsMax = 64 * 1024;
+  const int64_t list_bytes = (int64_t)n_chunks * k * 8;
+  const int stage = list_bytes <= kMergeLdsMax;
+  hipLaunchKernelGGL(topk_merge_kernel, dim3(NQ), dim3(256), stage ? (size_t)list_bytes : 0, s, ws, n_chunks, k, kout,
+                     stage, scores, index);
+  return (int)hipGetLastError();
+}
+
+namespace {
+size_t tk_fused_lds(int k) { return TK_UNION_BYTES + tk_state_lds(k); }
+size_t tk_select_lds(int k) { return (size_t)4 * (k + 64) * 8; }
 
 int tk_launch(TkArgs a, bool fused, int kout, float* scores, int64_t* index, hipStream_t s) {
   static const bool attrs = [] {  // allow the k = 128 footprint (over the 64 KiB default)
@@ -293,11 +209,7 @@ int tk_launch(TkArgs a, bool fused, int kout, float* scores, int64_t* index, hip
     hipLaunchKernelGGL(topk_chunk_kernel<true>, dim3(blocks), dim3(256), tk_fused_lds(a.k), s, a);
   else
     hipLaunchKernelGGL(topk_chunk_kernel<false>, dim3(blocks), dim3(256), tk_select_lds(a.k), s, a);
-  const int64_t list_bytes = (int64_t)a.n_chunks * a.k * 8;
-  const int stage = list_bytes <= kMergeLdsMax;
-  hipLaunchKernelGGL(topk_merge_kernel, dim3(a.NQ), dim3(256), stage ? (size_t)list_bytes : 0, s, a.ws, a.n_chunks,
-                     a.k, kout, stage, scores, index);
-  return (int)hipGetLastError();
+  return tk_merge_launch(a.ws, a.NQ, a.n_chunks, a.k, kout, scores, index, s);
 }
 
 TkArgs tk_args(int NQ, int NV, int k, uint64_t* ws) {

@@ -1,0 +1,202 @@
+// Top-k search over a gallery stored in bf16 (search.py: VideoIndex(dtype=torch.bfloat16)).
+//
+// Only the storage is lossy: the index keeps bf16_rne(gw (.) G) -- the fp32 fold of mmt_search_fold rounded once by a
+// plain cast -- and the score is DEFINED on that stored value,
+//
+//   score(q, g) = < fold_fp32(Q, qw)[q], dequant(stored[g]) > / sum_m qw[q][m] gw[g][m]     (0 -> 1e-5)
+//
+// The fp32 query runs on the bf16 matrix cores as two terms, hi = bf16(qf) and lo = bf16(qf - hi): bf16 x bf16 products
+// are exact in fp32, the accumulator is fp32, and what the split drops is below 2^-16 relative per query element.
+//
+//   fold_bf16_kernel<false> : x [N][M][d] fp32, w [N][M] -> bf16 [N][M*d], 8 elements (one 16-byte store) per thread
+//   fold_bf16_kernel<true>  : the same fold written as the hi / lo pair (queries)
+//   topk_chunk_bf16_kernel  : topk_chunk_kernel<true> of search.hip with the K loop on v_mfma_f32_32x32x16_bf16.  Same
+//                             block (64 queries x one gallery chunk, 4 waves of 32 rows x 64 columns), same 128-column
+//                             tile, same accumulator layout, hence the same epilogue, selection, workspace and merge
+//                             (search_topk.h).  Per 64-wide K slab the block stages hi, lo (64 rows each) and the
+//                             gallery (128 rows) in LDS; a wave reads each gallery fragment ONCE and feeds it to the hi
+//                             and the lo MFMA.  A 64-query tile is below the bf16 ridge for a gallery streamed from
+//                             HBM; the blocks of one gallery chunk are consecutive ids on one XCD (xcd_remap), so the
+//                             chunk is fetched from HBM once per XCD and served to the other query tiles from L2.
+//                             Rows past NQ / NV and the K tail are zero-filled in registers, never read.
+#include "search_topk.h"
+
+#define TKB_BK 64                 // contraction slab (bf16 elements): 128 bytes of a folded row
+#define TKB_LD (TKB_BK + 8)       // slab row pitch (bf16): 36 dwords, the fp32 kernel's conflict-free pitch
+#define TKB_SLAB_BYTES ((2 * TK_Q + TK_G) * TKB_LD * 2)
+#define TKB_UNION_BYTES (TK_TILE_BYTES > TKB_SLAB_BYTES ? TK_TILE_BYTES : TKB_SLAB_BYTES)
+
+struct TkBf16Args {
+  const bf16_t* q_hi;   // [NQ][K]
+  const bf16_t* q_lo;   // [NQ][K]
+  const float* qw;      // [NQ][M]
+  const bf16_t* g;      // [NV][K]
+  const float* gw;      // [NV][M]
+  uint64_t* ws;         // [NQ][n_chunks][k]
+  int NQ, NV, M, K, k, chunk, n_qt, n_chunks;
+};
+
+// out[r][m*d + c] = bf16(w[r][m] * x[r][m][c]); SPLIT: hi = bf16(v), lo = bf16(v - hi).  i8 counts groups of 8 elements,
+// which never straddle an (r, m) row because d % 8 == 0.
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void fold_bf16_kernel(const float* __restrict__ x, const float* __restrict__ w, int64_t n8,
+                                                        int d, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo) {
+  const int d8 = d >> 3;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
+    const float wv = w[i / d8];  // r*M + m
+    const f32x4 v0 = ((const f32x4*)x)[2 * i] * wv, v1 = ((const f32x4*)x)[2 * i + 1] * wv;
+    u16x8 h, l;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      h[j] = f2bf(v0[j]);
+      h[4 + j] = f2bf(v1[j]);
+      if constexpr (SPLIT) {
+        l[j] = f2bf(v0[j] - bf2f(h[j]));
+        l[4 + j] = f2bf(v1[j] - bf2f(h[4 + j]));
+      }
+    }
+    ((u16x8*)hi)[i] = h;
+    if constexpr (SPLIT) ((u16x8*)lo)[i] = l;
+  }
+}
+
+__global__ __launch_bounds__(256) void topk_chunk_bf16_kernel(TkBf16Args a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);  // gallery-chunk-major: an XCD's blocks share their chunk in L2
+  const int chunk = bid / a.n_qt, q0 = (bid % a.n_qt) * TK_Q;
+  const int g_begin = chunk * a.chunk, g_end = min(a.NV, g_begin + a.chunk);
+  const int cap = a.k + 64;
+  uint64_t* ws = a.ws + chunk * (int64_t)a.k;
+  const int64_t ws_row = (int64_t)a.n_chunks * a.k;
+
+  bf16_t* sAh = (bf16_t*)smem;                                // [TK_Q][TKB_LD]  slab of hi(Q')
+  bf16_t* sAl = sAh + TK_Q * TKB_LD;                          // [TK_Q][TKB_LD]  slab of lo(Q')
+  bf16_t* sB = sAl + TK_Q * TKB_LD;                           // [TK_G][TKB_LD]  slab of the stored gallery
+  float* sS = (float*)smem;                                   // [TK_Q][TK_SLD]  scores (after the K loop)
+  float* sQw = (float*)(smem + TKB_UNION_BYTES);              // [TK_Q][MMT_MAX_EXPERTS]
+  int* sN = (int*)(smem + TKB_UNION_BYTES + TK_QW_BYTES);     // [TK_Q] candidates held
+  uint64_t* sT = (uint64_t*)(sN + TK_Q);                      // [TK_Q] thresholds
+  uint64_t* sC = sT + TK_Q;                                   // [TK_Q][cap] candidates
+  const int l31 = lane & 31, h = lane >> 5, wq = wave >> 1, wg = wave & 1;
+  const int K = a.K, M = a.M;
+  if (tid < TK_Q) { sN[tid] = 0; sT[tid] = 0; }
+  for (int i = tid; i < TK_Q * MMT_MAX_EXPERTS; i += 256) {
+    const int r = i / MMT_MAX_EXPERTS, m = i % MMT_MAX_EXPERTS;
+    sQw[i] = (q0 + r < a.NQ && m < M) ? a.qw[(int64_t)(q0 + r) * M + m] : 0.f;
+  }
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+  for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    // staging, 16 bytes = 8 bf16 per load: hi and lo slabs = 64 rows x 8 (2 per thread each), gallery slab = 128 rows x 8
+    // (4 per thread).  K % 8 == 0, so a load is inside the row or past its end as a whole.
+    u32x4 rh[2], rl[2], rb[4];
+    auto load = [&](int kb) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 8;
+        const bool in = q0 + r < a.NQ && c < K;
+        const int64_t off = (int64_t)(q0 + r) * K + c;
+        rh[j] = in ? *(const u32x4*)(a.q_hi + off) : zero;
+        rl[j] = in ? *(const u32x4*)(a.q_lo + off) : zero;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 8;
+        rb[j] = (g0 + r < g_end && c < K) ? *(const u32x4*)(a.g + (int64_t)(g0 + r) * K + c) : zero;
+      }
+    };
+    load(0);
+    for (int kb = 0; kb < K; kb += TKB_BK) {
+      __syncthreads();  // previous slab (or the previous tile's scores) consumed
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int i = tid + 256 * j, o = (i >> 3) * TKB_LD + (i & 7) * 8;
+        *(u32x4*)(sAh + o) = rh[j];
+        *(u32x4*)(sAl + o) = rl[j];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { const int i = tid + 256 * j; *(u32x4*)(sB + (i >> 3) * TKB_LD + (i & 7) * 8) = rb[j]; }
+      __syncthreads();
+      if (kb + TKB_BK < K) load(kb + TKB_BK);
+      // 16 contraction values per MFMA; lane half h holds k = kk + 8h .. + 7 of its row (A) / column (B)
+#pragma unroll
+      for (int kk = 0; kk < TKB_BK; kk += 16) {
+        const int ao = (wq * 32 + l31) * TKB_LD + kk + 8 * h;
+        const bf16x8_t ah = *(const bf16x8_t*)(sAh + ao), al = *(const bf16x8_t*)(sAl + ao);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const bf16x8_t bv = *(const bf16x8_t*)(sB + (wg * 64 + t * 32 + l31) * TKB_LD + kk + 8 * h);
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bv, acc[t], 0, 0, 0);
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bv, acc[t], 0, 0, 0);
+        }
+      }
+    }
+    __syncthreads();  // the slabs become the score tile
+    tk_tile_scores(acc, sS, sQw, a.gw, M, g0, g_end, wq, wg, l31, h);
+    __syncthreads();
+    tk_tile_select(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane);
+  }
+  __syncthreads();
+  for (int rr = 0; rr < TK_Q / 4; ++rr) {
+    const int row = wave * (TK_Q / 4) + rr, q = q0 + row;
+    if (q >= a.NQ) break;
+    tk_flush(sC + row * cap, sN[row], a.k, lane, ws + q * ws_row);
+  }
+}
+
+namespace {
+size_t tkb_lds(int k) { return TKB_UNION_BYTES + tk_state_lds(k); }
+
+bool fold_args_ok(const void* x, const void* w, int N, int M, int d) {
+  return x && w && N > 0 && M > 0 && M <= MMT_MAX_EXPERTS && d > 0 && !(d & 7);
+}
+
+int fold_blocks(int64_t n8) { return (int)((n8 + 255) / 256 < 4096 ? (n8 + 255) / 256 : 4096); }
+}  // namespace
+
+extern "C" int mmt_search_fold_bf16(const float* x, const float* w, int N, int M, int d, uint16_t* out, void* stream) {
+  if (!fold_args_ok(x, w, N, M, d) || !out) return MMT_ERR_ARG;
+  if (((uintptr_t)x | (uintptr_t)out) & 15) return MMT_ERR_ALIGN;
+  const int64_t n8 = (int64_t)N * M * d / 8;
+  hipLaunchKernelGGL(fold_bf16_kernel<false>, dim3(fold_blocks(n8)), dim3(256), 0, (hipStream_t)stream, x, w, n8, d, out,
+                     (bf16_t*)nullptr);
+  return (int)hipGetLastError();
+}
+
+extern "C" int mmt_search_fold_split_bf16(const float* x, const float* w, int N, int M, int d, uint16_t* hi, uint16_t* lo,
+                                          void* stream) {
+  if (!fold_args_ok(x, w, N, M, d) || !hi || !lo) return MMT_ERR_ARG;
+  if (((uintptr_t)x | (uintptr_t)hi | (uintptr_t)lo) & 15) return MMT_ERR_ALIGN;
+  const int64_t n8 = (int64_t)N * M * d / 8;
+  hipLaunchKernelGGL(fold_bf16_kernel<true>, dim3(fold_blocks(n8)), dim3(256), 0, (hipStream_t)stream, x, w, n8, d, hi, lo);
+  return (int)hipGetLastError();
+}
+
+extern "C" int mmt_search_topk_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                    const float* gw, int NQ, int NV, int M, int d, int k, uint64_t* ws, float* scores,
+                                    int64_t* index, void* stream) {
+  if (!q_hi || !q_lo || !qw || !gf || !gw || !ws || !index || !tk_args_ok(NQ, NV, k) || M <= 0 || M > MMT_MAX_EXPERTS ||
+      d <= 0 || (d & 7))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)q_hi | (uintptr_t)q_lo | (uintptr_t)gf) & 15) return MMT_ERR_ALIGN;
+  static const bool attrs = [] {  // allow the k = 128 footprint (over the 64 KiB default)
+    (void)hipFuncSetAttribute((const void*)topk_chunk_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)tkb_lds(TK_MAXK));
+    return true;
+  }();
+  (void)attrs;
+  TkBf16Args a = {};
+  a.q_hi = q_hi; a.q_lo = q_lo; a.qw = qw; a.g = gf; a.gw = gw; a.ws = ws;
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.k = k;
+  a.chunk = tk_chunk(NQ, NV);
+  a.n_qt = (NQ + TK_Q - 1) / TK_Q;
+  a.n_chunks = (NV + a.chunk - 1) / a.chunk;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(topk_chunk_bf16_kernel, dim3(a.n_qt * a.n_chunks), dim3(256), tkb_lds(k), s, a);
+  return tk_merge_launch(ws, NQ, a.n_chunks, k, k < NV ? k : NV, scores, index, s);
+}

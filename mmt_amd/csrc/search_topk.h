@@ -1,0 +1,122 @@
+// Selection machinery of the top-k search, shared by the fp32 kernels (search.hip) and the bf16-gallery kernel
+// (search_bf16.hip): the (score, index) key, the per-row running top-k in LDS, the tile epilogue and the chunk rule.
+// See search.hip for the algorithm.
+#pragma once
+#include "mmt_common.h"
+#include "../../include/mmt_hip.h"
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+#define TK_Q 64                  // query rows per block (4 waves: 2 x 2 of 32 rows x 64 columns)
+#define TK_G 128                 // gallery columns per tile
+#define TK_SLD (TK_G + 4)        // score tile row pitch
+#define TK_MAXK 128
+#define TK_CHUNK 4096            // gallery columns per block at full occupancy
+#define TK_FILL 512              // blocks wanted per launch before the chunk is allowed to shrink (2 per CU)
+#define TK_TILE_BYTES (TK_Q * TK_SLD * 4)
+#define TK_QW_BYTES (TK_Q * MMT_MAX_EXPERTS * 4)
+
+__device__ __forceinline__ uint64_t tk_key(float s, int idx) {
+  unsigned u = __float_as_uint(s);
+  if (!(u & 0x7fffffffu)) u = 0;  // -0 ranks as +0 (numpy compares them equal)
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((uint64_t)u << 32) | (uint64_t)(~(unsigned)idx);
+}
+__device__ __forceinline__ float tk_score(uint64_t key) {
+  const unsigned u = (unsigned)(key >> 32);
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+__device__ __forceinline__ int tk_index(uint64_t key) { return (int)~(unsigned)key; }
+
+// One wave, one row: rank-sort the n (<= k + 64 <= 192) candidates c[0..n) and keep the best min(n, k) in c[0..) in
+// descending order.
+__device__ __forceinline__ void tk_compact(uint64_t* c, int n, int k, int lane) {
+  uint64_t v[3];
+  int rk[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int i = lane + 64 * j;
+    v[j] = i < n ? c[i] : 0;
+    rk[j] = 0;
+  }
+  for (int i = 0; i < n; ++i) {
+    const uint64_t x = c[i];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) rk[j] += x > v[j];
+  }
+  __builtin_amdgcn_wave_barrier();  // every lane's reads above precede any rewrite (one wave: LDS ops stay in order)
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    if (lane + 64 * j < n && rk[j] < k) c[rk[j]] = v[j];
+  __builtin_amdgcn_wave_barrier();
+}
+
+// One wave, one row: offers one key per lane (0 = none).  Keys at or below the threshold (the k-th best so far) cannot
+// enter the top k; the others are appended.  Capacity k + 64: the list is compacted first whenever it holds more than k.
+__device__ __forceinline__ void tk_push(uint64_t* c, int& n, uint64_t& thr, int k, uint64_t key, int lane) {
+  if (n > k) {
+    tk_compact(c, n, k, lane);
+    n = k;
+    thr = c[k - 1];
+  }
+  const bool take = key > thr;
+  const uint64_t mask = __ballot(take);
+  if (take) c[n + __popcll(mask & ((1ull << lane) - 1ull))] = key;
+  n += __popcll(mask);
+}
+
+// The chunk's best min(n, k) keys of one row, sorted, padded with 0 to k.
+__device__ __forceinline__ void tk_flush(uint64_t* c, int n, int k, int lane, uint64_t* dst) {
+  if (n > 0) tk_compact(c, n, k, lane);
+  const int have = n < k ? n : k;
+  for (int j = lane; j < k; j += 64) dst[j] = j < have ? c[j] : 0ull;
+}
+
+// Epilogue of one 64 x 128 tile held as 32x32 MFMA accumulators (lane: column wg*64 + t*32 + l31, rows
+// wq*32 + (r&3) + 8*(r>>2) + 4h -- the layout of v_mfma_f32_32x32x2_f32 and v_mfma_f32_32x32x16_bf16 alike): divides by
+// the gated denominator and leaves the scores in sS [TK_Q][TK_SLD].
+__device__ __forceinline__ void tk_tile_scores(const f32x16 (&acc)[2], float* sS, const float* sQw, const float* gw, int M,
+                                               int g0, int g_end, int wq, int wg, int l31, int h) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int col = wg * 64 + t * 32 + l31, g = g0 + col;
+    float den[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) den[r] = 0.f;
+    for (int m = 0; m < M; ++m) {
+      const float gwm = g < g_end ? gw[(int64_t)g * M + m] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) den[r] += sQw[(wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * MMT_MAX_EXPERTS + m] * gwm;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      sS[row * TK_SLD + col] = acc[t][r] / (den[r] == 0.f ? 1e-5f : den[r]);
+    }
+  }
+}
+
+// Selection over the score tile: wave w owns rows 16w .. 16w + 15; columns in increasing index order.
+__device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, int* sN, uint64_t* sT, int k, int rows_live,
+                                               int g0, int g_end, int wave, int lane) {
+  const int cap = k + 64;
+  for (int rr = 0; rr < TK_Q / 4; ++rr) {
+    const int row = wave * (TK_Q / 4) + rr;
+    if (row >= rows_live) break;
+    int n = sN[row];
+    uint64_t thr = sT[row];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int col = half * 64 + lane, g = g0 + col;
+      tk_push(sC + row * cap, n, thr, k, g < g_end ? tk_key(sS[row * TK_SLD + col], g) : 0ull, lane);
+    }
+    if (lane == 0) { sN[row] = n; sT[row] = thr; }
+  }
+}
+
+// Host side (search.hip): the chunk rule, the argument gate and the merge launch, shared by the fp32 and bf16 paths.
+int tk_chunk(int NQ, int NV);
+bool tk_args_ok(int NQ, int NV, int k);
+size_t tk_state_lds(int k);  // LDS behind the slab / score-tile union: query weights, counts, thresholds, candidates
+int tk_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, float* scores, int64_t* index,
+                    hipStream_t s);

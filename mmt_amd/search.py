@@ -8,8 +8,19 @@ The score is the 'indep' similarity of model/model.py:789-837 (the matrix `metri
     score(q, g) = sum_m qw[q][m] gw[g][m] <Q_m[q], G_m[g]> / sum_m qw[q][m] gw[g][m]     (0 -> 1e-5)
 It is symmetric, so video-to-text search is an index of captions queried with videos.  Each query gets min(k, NV)
 (score, index) pairs, best first, equal scores by ascending gallery index.  One launch scores 64-query x 4096-video
-blocks on the fp32 matrix cores and keeps a running top-k per query; a second merges the chunk lists (mmt_search_topk).
+blocks on the matrix cores and keeps a running top-k per query; a second merges the chunk lists (mmt_search_topk).
 Results are bit-reproducible.
+
+    index = VideoIndex(vid_embds, vid_weights, dtype=torch.bfloat16)    # half the bytes per item (d % 8 == 0)
+    index = VideoIndex.empty(capacity, M, d, device, dtype=...)         # preallocated, filled in pieces:
+    first, last = index.add(chunk_embds, chunk_weights)                 # items first .. last - 1
+    index.num_items, index.capacity, index.dtype, index.nbytes
+
+A bfloat16 index stores bf16(gw (.) G), the fp32 fold rounded once to nearest-even; the weights stay fp32 and the queries
+are NOT rounded to 8 bits: score(q, g) = <fold_fp32(Q, qw)[q], dequant(stored[g])> / sum_m qw gw, computed on the bf16
+matrix cores with the query split into hi = bf16(qf) and lo = bf16(qf - hi) (mmt_search_topk_bf16; within 1e-5 of the
+fp64 value of that definition).  Against the float32 index a score moves by at most
+2^-8 * sum_m qw gw <|Q_m|, |G_m|> / sum_m qw gw, i.e. 2^-8 for unit-norm rows.
 """
 import torch
 
@@ -17,7 +28,8 @@ from . import _lib, ops
 from ._lib import check
 
 MAX_K = 128
-_BATCH_BYTES = 48 << 20  # folded queries + chunk lists per launch
+_BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 bytes per element either way) + chunk lists
+_DTYPES = {torch.float32: 4, torch.bfloat16: 8}  # storage dtype -> multiple d must have (16-byte folded rows)
 
 
 def _cuda_f32(x, name):
@@ -33,23 +45,88 @@ def _fold(x, w):
   return out
 
 
-class VideoIndex:
-  """A gallery of NV items with M expert embeddings of width d (d % 4 == 0, M <= 16), weighted per item and expert."""
+def _check_dtype(dtype):
+  if dtype not in _DTYPES:
+    raise ValueError('VideoIndex: dtype must be torch.float32 or torch.bfloat16, got %r' % (dtype,))
 
-  def __init__(self, embds, weights):
+
+class VideoIndex:
+  """A gallery of up to `capacity` items with M expert embeddings of width d (M <= 16), weighted per item and expert.
+  dtype=torch.float32 (d % 4 == 0) stores the fold gw (.) G as it is; dtype=torch.bfloat16 (d % 8 == 0) stores it rounded
+  once to bf16 -- half the bytes, scored on the bf16 matrix cores against the unrounded fp32 queries (module docstring)."""
+
+  def __init__(self, embds, weights, dtype=torch.float32):
+    _check_dtype(dtype)
+    g, gw = self._items(embds, weights, 'VideoIndex')
+    self._allocate(g.shape[0], g.shape[1], g.shape[2], g.device, dtype)
+    self.add(g, gw)
+
+  @classmethod
+  def empty(cls, capacity, num_experts, dim, device, dtype=torch.float32):
+    """An index with room for `capacity` items and none stored: [capacity, M*d] of `dtype` and [capacity, M] fp32 are
+    allocated here, `add` fills them chunk by chunk (the unfolded gallery is never needed in one piece)."""
+    _check_dtype(dtype)
+    device = torch.device(device)
+    if device.type != 'cuda':
+      raise ValueError('VideoIndex.empty: device must be a CUDA device, got %s' % device)
+    if device.index is None:
+      device = torch.device('cuda', torch.cuda.current_device())
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (capacity, num_experts, dim)):
+      raise ValueError('VideoIndex.empty: capacity, num_experts and dim must be ints')
+    self = cls.__new__(cls)
+    self._allocate(capacity, num_experts, dim, device, dtype)
+    return self
+
+  def _allocate(self, capacity, m, d, device, dtype):
+    mult = _DTYPES[dtype]
+    if capacity < 1 or not 1 <= m <= 16 or d < mult or d % mult:
+      raise ValueError('VideoIndex: need capacity >= 1, 1 <= M <= 16 and d %% %d == 0 for %s, got (%d, %d, %d)' % (
+          mult, dtype, capacity, m, d))
+    self.capacity, self.num_experts, self.dim = capacity, m, d
+    self.num_items = 0
+    self.device, self.dtype = device, dtype
+    self.folded = torch.empty(capacity, m * d, device=device, dtype=dtype)   # gw (.) G; rows < num_items are valid
+    self.weights = torch.empty(capacity, m, device=device, dtype=torch.float32)
+
+  @staticmethod
+  def _items(embds, weights, who):
     g = _cuda_f32(embds, 'embds')
     gw = _cuda_f32(weights, 'weights')
     if g.dim() != 3 or gw.shape != g.shape[:2]:
-      raise ValueError('VideoIndex expects embds (NV, M, d) and weights (NV, M), got %s and %s' % (
-          tuple(g.shape), tuple(gw.shape)))
-    nv, m, d = g.shape
-    if nv < 1 or not 1 <= m <= 16 or d < 4 or d % 4:
-      raise ValueError('VideoIndex: need NV >= 1, 1 <= M <= 16 and d % 4 == 0, got %s' % (tuple(g.shape),))
-    self.num_items, self.num_experts, self.dim = nv, m, d
-    self.device = g.device
+      raise ValueError('%s expects embds (NV, M, d) and weights (NV, M), got %s and %s' % (
+          who, tuple(g.shape), tuple(gw.shape)))
+    if g.shape[0] < 1:
+      raise ValueError('%s: need NV >= 1, got %s' % (who, tuple(g.shape)))
+    return g, gw
+
+  @property
+  def nbytes(self):
+    """Bytes held by the index: the folded storage plus the weights, at full capacity."""
+    return self.folded.numel() * self.folded.element_size() + self.weights.numel() * 4
+
+  def add(self, embds, weights):
+    """Appends items (n, M, d) / (n, M): folded (and for bfloat16 rounded) straight into the preallocated rows.  Returns
+    (first, last): the new items are numbers first .. last - 1.  Raises ValueError, leaving the index as it was, if they
+    do not fit."""
+    g, gw = self._items(embds, weights, 'VideoIndex.add')
+    n, m, d = g.shape
+    if (m, d) != (self.num_experts, self.dim):
+      raise ValueError('VideoIndex.add: items (n, %d, %d) expected, got %s' % (self.num_experts, self.dim, tuple(g.shape)))
+    if g.device != self.device or gw.device != self.device:
+      raise ValueError('VideoIndex.add: items must be on the index device %s' % self.device)
+    first, last = self.num_items, self.num_items + n
+    if last > self.capacity:
+      raise ValueError('VideoIndex.add: %d items do not fit (%d of %d in use)' % (n, first, self.capacity))
+    L = _lib.lib()
     with torch.cuda.device(self.device):
-      self.folded = _fold(g, gw)  # gw (.) G: [NV, M*d]
-    self.weights = gw
+      out = self.folded[first:last]
+      if self.dtype == torch.bfloat16:
+        check(L.mmt_search_fold_bf16(ops._p(g), ops._p(gw), n, m, d, ops._p(out), ops._stream()), 'mmt_search_fold_bf16')
+      else:
+        check(L.mmt_search_fold(ops._p(g), ops._p(gw), n, m, d, ops._p(out), ops._stream()), 'mmt_search_fold')
+      self.weights[first:last].copy_(gw)
+    self.num_items = last
+    return first, last
 
   def _queries(self, embds, weights):
     q = _cuda_f32(embds, 'embds')
@@ -74,6 +151,8 @@ class VideoIndex:
     indices [NQ, k'] int64) on the device, k' = min(k, NV), best first."""
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
       raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
+    if self.num_items == 0:
+      raise ValueError('search: the index holds no items')
     q, qw = self._queries(embds, weights)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     kout = min(k, nv)
@@ -87,9 +166,17 @@ class VideoIndex:
       batch = max(64, (_BATCH_BYTES // per_row) // 64 * 64)
       for r0 in range(0, nq, batch):
         r1 = min(nq, r0 + batch)
-        qf = _fold(q[r0:r1], qw[r0:r1])
-        ws = torch.empty(L.mmt_topk_workspace_keys(r1 - r0, nv, k), device=self.device, dtype=torch.int64)
-        check(L.mmt_search_topk(ops._p(qf), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights), r1 - r0, nv, m,
-                                d, k, ops._p(ws), ops._p(scores[r0:r1]), ops._p(indices[r0:r1]), ops._stream()),
-              'mmt_search_topk')
+        n = r1 - r0
+        ws = torch.empty(L.mmt_topk_workspace_keys(n, nv, k), device=self.device, dtype=torch.int64)
+        out = (n, nv, m, d, k, ops._p(ws), ops._p(scores[r0:r1]), ops._p(indices[r0:r1]), ops._stream())
+        if self.dtype == torch.bfloat16:
+          hl = torch.empty(2, n, m * d, device=self.device, dtype=torch.bfloat16)  # hi = bf16(qf), lo = bf16(qf - hi)
+          check(L.mmt_search_fold_split_bf16(ops._p(q[r0:r1]), ops._p(qw[r0:r1]), n, m, d, ops._p(hl[0]), ops._p(hl[1]),
+                                             ops._stream()), 'mmt_search_fold_split_bf16')
+          check(L.mmt_search_topk_bf16(ops._p(hl[0]), ops._p(hl[1]), ops._p(qw[r0:r1]), ops._p(self.folded),
+                                       ops._p(self.weights), *out), 'mmt_search_topk_bf16')
+        else:
+          qf = _fold(q[r0:r1], qw[r0:r1])
+          check(L.mmt_search_topk(ops._p(qf), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights), *out),
+                'mmt_search_topk')
     return scores, indices

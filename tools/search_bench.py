@@ -9,7 +9,12 @@ Times with device events after warm-up, over >= --min-seconds of work per point;
 FLOP/s from 2 NQ NV M d and the fraction of the 157.3 TF fp32 matrix peak.  At S1 / S2 (one caption per video) the
 materialised path is the public eval_similarity + compress_predictions; at S3 (NQ != NV * captions, which those
 functions require) it is their kernels, mmt_sims_eval + mmt_rows_topk.
-   python tools/search_bench.py [--shapes S1,S2,S3] [--out profiles/search_bench.json] [--min-seconds 0.5]"""
+   python tools/search_bench.py [--shapes S1,S2,S3] [--out profiles/search_bench.json] [--min-seconds 0.5]
+
+--gallery-dtype bfloat16 times the bf16-stored index instead; --gallery-dtype both times the two indexes side by side on
+the same data (--runs timed runs each, interleaved; median and spread = max - min) and reports per shape the index bytes,
+peak memory, TF (2 NQ NV M d counted once: the hi / lo query split is overhead, not work) and the share of rows whose
+index lists agree.  The bf16 index is built in chunks (VideoIndex.empty + add)."""
 import argparse
 import json
 import math
@@ -69,17 +74,51 @@ def timed(fn, min_seconds):
   return e0.elapsed_time(e1) / 1e3 / iters, iters, torch.cuda.max_memory_allocated() - base, out
 
 
+def both_dtypes(q, qw, g, gw, flop, a):
+  """fp32 and bf16 indexes over the same gallery, timed alternately so drift hits both alike."""
+  nv = g.shape[0]
+  idx = {'float32': VideoIndex(g, gw)}
+  idx['bfloat16'] = VideoIndex.empty(nv, M, D, g.device, dtype=torch.bfloat16)
+  for at in range(0, nv, 8192):
+    idx['bfloat16'].add(g[at:at + 8192], gw[at:at + 8192])
+  ts = {n: [] for n in idx}
+  mem = {n: 0 for n in idx}
+  out = {}
+  for _ in range(a.runs):
+    for n in idx:
+      t, _, m, out[n] = timed(lambda: idx[n].search(q, qw, k=K), a.min_seconds)
+      ts[n].append(t)
+      mem[n] = max(mem[n], m)
+  row = {}
+  for n in idx:
+    med = float(np.median(ts[n]))
+    row[n] = dict(seconds_median=med, seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n], tflops=flop / med / 1e12,
+                  index_bytes=idx[n].nbytes, peak_mem_growth_bytes=mem[n])
+  row['bf16_speedup'] = row['float32']['seconds_median'] / row['bfloat16']['seconds_median']
+  row['margin_seconds'] = max(row['float32']['seconds_spread'], row['bfloat16']['seconds_spread'])
+  row['bf16_faster_beyond_margin'] = bool(row['float32']['seconds_median'] - row['bfloat16']['seconds_median'] >
+                                          row['margin_seconds'])
+  row['bf16_not_slower_beyond_margin'] = bool(row['bfloat16']['seconds_median'] - row['float32']['seconds_median'] <=
+                                              row['margin_seconds'])
+  row['index_rows_identical'] = float((out['float32'][1] == out['bfloat16'][1]).all(1).float().mean())
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--shapes', default='S1,S2,S3')
   ap.add_argument('--out', default=None)
   ap.add_argument('--min-seconds', type=float, default=0.5)
   ap.add_argument('--skip-materialised', action='store_true', help='fused path only (kernel-trace runs)')
+  ap.add_argument('--gallery-dtype', choices=('float32', 'bfloat16', 'both'), default='float32')
+  ap.add_argument('--runs', type=int, default=5, help='timed runs per index with --gallery-dtype both')
   a = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
   res = {'M': M, 'd': D, 'k': K, 'peak_fp32_matrix_flops': PEAK, 'device': torch.cuda.get_device_name(0), 'shapes': {}}
+  if a.gallery_dtype != 'float32':  # the default invocation keeps its JSON layout
+    res['gallery_dtype'] = a.gallery_dtype
   for name in a.shapes.split(','):
     nq, nv = SHAPES[name]
     gen = torch.Generator(device=dev).manual_seed(0)
@@ -90,7 +129,14 @@ def main():
     qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
     flop = 2.0 * nq * nv * M * D
     row = {'NQ': nq, 'NV': nv, 'flop': flop}
-    index = VideoIndex(g, gw)
+    if a.gallery_dtype == 'both':
+      row.update(both_dtypes(q, qw, g, gw, flop, a))
+      res['shapes'][name] = row
+      print(name, json.dumps(row), flush=True)
+      del g, gw, q, qw
+      torch.cuda.empty_cache()
+      continue
+    index = VideoIndex(g, gw, dtype=getattr(torch, a.gallery_dtype))
     t, it, mem, (s, i) = timed(lambda: index.search(q, qw, k=K), a.min_seconds)
     row['fused'] = dict(seconds=t, iters=it, peak_mem_growth_bytes=mem, tflops=flop / t / 1e12,
                         fraction_of_peak=flop / t / PEAK)
