@@ -53,17 +53,6 @@ from .model import cross_view_similarity
 from .optim import FlatAdam
 
 
-def _layer_stage(name, n_layers, first):
-  """Optimizer-queue stage of an encoder parameter: `first` + k for the matrices and biases of layer n_layers-1-k (final
-  after that layer's weight-gradient launch); None (final only when the backward ends) for LayerNorm parameters --
-  their gradients come out of the batched reduction at the end of the backward --, embeddings and everything else."""
-  import re
-  z = re.search(r'encoder\.layer\.(\d+)\.', name)
-  if z is None or '.layer_norm.' in name or '.LayerNorm.' in name:
-    return None
-  return first + (n_layers - 1 - int(z.group(1)))
-
-
 _QUIESCE_WARNED = False
 
 
@@ -167,6 +156,7 @@ FORK_DEFAULT = 0
 
 
 class GraphedTrainStep:
+  _rider_on = False  # bench.py reads it (the Adam riders are gone: never on)
 
   def __init__(self, model, loss_fn, minibatch, lr=5e-5, group=None, use_graphs=True, warmup_steps=3,
                overlap_grad_sync=None, force_collectives=False, grad_dtype=None, capture_collectives=False, fork=None,
@@ -204,26 +194,18 @@ class GraphedTrainStep:
     when a minibatch's count would select other tiles -- on ONE rank; with several ranks the constructor's count stands (a
     re-capture contains collectives that all ranks would have to enter); without any count a packed batch is priced at its
     allocated rows.
-    adam_riders (one rank only; None = OFF unless MMT_ADAM_RIDERS=1): the optimizer inside the backward -- the step's Adam
-    update is a queue of 4096-element units ordered by when their gradients are final, the GEMM launches of the
-    backward carry it (blocks without a tile of their own -- idle CUs, the last partial round -- stream Adam's bytes beside
-    the tiles) and the optimizer launch at the end only runs what is left.  Bit-identical to the serial fused step
-    (tests/test_optim_gpu.py); needs the stage-by-stage backward (native text heads and losses).  MEASURED SLOWER on
-    MI355X in every configuration (r06, DESIGN section 7: the hosting GEMMs are bound by memory latency, every unit a rider
-    streams costs 2-3x what it costs in the optimizer's own launch -- headline 1.31-1.58 ms against 1.28 ms), hence opt-in.
-    Reference: train.py:100, trainer/trainer.py:203-204.
+    adam_riders: removed in ABI 4 (the optimizer riding in the backward's GEMM launches measured slower in every
+    configuration); a true value raises ValueError.
     The warm-up steps only allocate buffers and optimizer state: weights, Adam moments and step count, BatchNorm
     statistics and the dropout seed are restored afterwards, so the first `step()` IS the first optimisation step."""
+    if adam_riders:
+      raise ValueError('adam_riders: removed; measured slower, see DESIGN §7')
     self.model, self.loss_fn, self.group = model, loss_fn, group
     if fork is None:
       fork = int(os.environ.get('MMT_FORK', FORK_DEFAULT))
     self.fork = int(fork)
     self._side = None
     self._fork_on = False  # decided after the first warm-up step (needs the model's stage handles)
-    if adam_riders is None:
-      adam_riders = os.environ.get('MMT_ADAM_RIDERS', '0') == '1'
-    self._want_riders = bool(adam_riders)
-    self._rider_on = False  # decided after the first warm-up step as well
     self._keep = []
     self.world = dist.get_world_size(group) if dist.is_initialized() else 1
     self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -298,9 +280,6 @@ class GraphedTrainStep:
       snap = self._snapshot() if warmup_steps > 0 else None
       for i in range(warmup_steps):  # allocates every lazily created buffer / optimizer state
         self._eager_step()
-        if i == 0 and self._want_riders and not self._multi and not self.fork and not self._want_stages:
-          self._rider_on = self._stageable([p for p in rest if p.grad is not None]) and \
-              all(not o._frozen_spans() for o in self.opt_flats)
         if i == 0 and (self._want_stages or self.fork):
           ok = self._stageable([p for p in rest if p.grad is not None])  # e.g. the unused pooler: no grad
           self.staged = ok and self._want_stages
@@ -312,9 +291,6 @@ class GraphedTrainStep:
               model.overlap_text_heads = True
               model._side_streams[next(model.parameters()).device] = self._side
             self._fork_on = True
-      if self._rider_on:  # the queues exist before anything is captured (building them copies tables to the device)
-        self._arm_riders()
-        self._disarm_riders()
       if snap is not None:
         self._restore(snap)
     torch.cuda.current_stream().wait_stream(self._stream)
@@ -421,8 +397,6 @@ class GraphedTrainStep:
         o.exp_avg.zero_()
         o.exp_avg_sq.zero_()
         o.step_dev.zero_()
-      if o._queue is not None:
-        o._queue['state'].zero_()
     if self.opt_rest is not None:
       for st in self.opt_rest.state.values():
         for v in st.values():
@@ -610,10 +584,8 @@ class GraphedTrainStep:
       return False
     return all(p.requires_grad for p in m._flat.params)
 
-  def _stage_list(self, e, g, single_range=False):
-    """[(callable, [names of the flat-gradient regions that are final once it has run])], in execution order.
-    single_range: ONE stage -- loss, text heads, read-out, then the whole encoder as one engine call (one batched
-    LayerNorm / table reduction at its end instead of one per stage) and the video tokens."""
+  def _stage_list(self, e, g):
+    """[(callable, [names of the flat-gradient regions that are final once it has run])], in execution order."""
     model, vb = self.model, self.model.vid_bert
     st = {}
 
@@ -653,12 +625,6 @@ class GraphedTrainStep:
         st['run'](n_layers - 1, n_layers - 1)
 
     names = dict(self._grad_regions())
-    if single_range:
-      def whole():
-        head()
-        st['run'](n_layers - 1, 0)
-        model._video_tokens_backward(model._stages['plan'], st['run'].dfeat)
-      return [(whole, list(names) + ['flat%d' % (i + 1) for i in range(len(self._extra_flats))])]
     stages = [(top, (['top'] if 'top' in names else []) + ['flat%d' % (i + 1) for i in range(len(self._extra_flats))])]
     for l in range(n_layers - 2, 0, -1):
       stages.append((lambda l=l: st['run'](l, l), ['layer%d' % l]))
@@ -883,73 +849,7 @@ class GraphedTrainStep:
     if not self.fork & FORK_ADAM:
       self._opt()
 
-  # ---- the optimizer riding in the backward's GEMM launches (one rank) ------------------------------------------------
-  def _arm_riders(self):
-    """Build (once) the optimizer queues of the flat buffers and attach them to the encoders whose backward launches
-    carry them.  Stages of the video side's queue: 0 = text heads (their backward runs first), 1 + k = the matrices and
-    biases of encoder layer L-1-k (final after that layer's weight-gradient launch); LayerNorm parameters, embedding tables
-    and the expert projections are only final when the backward ends and stay for the optimizer launch.  The native text
-    tower's queue: stage k = its layer Lt-1-k; what its own backward leaves (embeddings, its bottom layer) rides in the
-    video side's launches (chain)."""
-    m = self.model
-    opt_v = self.opt_flats[0]
-    opt_t = self.opt_flats[1] if len(self.opt_flats) > 1 else None
-    vb = m.vid_bert
-    Lv = vb.config.num_hidden_layers
-    built = False
-    if opt_t is not None and not opt_t._queue_ok():
-      tb = m.txt_bert
-      Lt = tb.config.num_hidden_layers
-      names = dict((id(p), n) for n, p in zip(opt_t.flat.names, opt_t.flat.params))
-      opt_t.build_queue(lambda p: _layer_stage(names[id(p)], Lt, 0))
-      built = True
-    if built or not opt_v._queue_ok():
-      names = dict((id(p), n) for n, p in zip(opt_v.flat.names, opt_v.flat.params))
-
-      def stage_v(p):
-        n = names[id(p)]
-        if n.startswith('text_GU.') or n.startswith('moe_fc_txt.'):
-          return 0
-        return _layer_stage(n, Lv, 1)
-      opt_v.build_queue(stage_v, chain=opt_t)
-    for o in self.opt_flats:
-      o.arm_queue(True)
-    # stages of the queue that are final while layer l's backward runs: text heads + the layers above (video side), the
-    # layers above (text tower)
-    # (lab: MMT_RIDER_CAP = rider blocks at work per launch, MMT_RIDER_PASSES = passes a rider block makes, 0 = until the
-    # host launch is in its tail; both travel in the upper half of rider_slot0 -> MmtEpilogue.rider_cap)
-    cap = max(0, min(0xfff, int(os.environ.get('MMT_RIDER_CAP', '0'))))
-    cap = (cap | (max(0, min(15, int(os.environ.get('MMT_RIDER_PASSES', '0')))) << 12)) << 16
-    vb.set_rider(opt_v.queue_ptr(), [Lv - l for l in range(Lv)], cap)
-    if opt_t is not None:
-      tb = m.txt_bert
-      Lt = tb.config.num_hidden_layers
-      tb.set_rider(opt_t.queue_ptr(), [Lt - 1 - l for l in range(Lt)], cap)
-
-  def _disarm_riders(self):
-    self.model.vid_bert.set_rider(None)
-    if len(self.opt_flats) > 1:
-      self.model.txt_bert.set_rider(None)
-
-  def _rider_step(self):
-    """One rank: forward, the backward stage by stage (text heads first, then the encoder from the top layer down) with
-    the optimizer queues riding in its GEMM launches, then the optimizer launches for what is left.  ONE serial chain of
-    kernels, captured as one graph."""
-    self._zero()
-    e = self._forward()
-    g = self._gather(e)
-    self._regions = self._region_table()
-    self._arm_riders()
-    try:
-      for fn, _ in self._stage_list(e, g, single_range=True):
-        fn()
-    finally:
-      self._disarm_riders()
-    self._opt()
-
   def _eager_step(self):
-    if self._rider_on and not self._multi:
-      return self._rider_step()
     if self._fork_on and not self._multi:
       return self._fork_step()
     self._zero()
@@ -999,13 +899,10 @@ class GraphedTrainStep:
   def _capture(self):
     torch.cuda.synchronize()
     self._zero()
-    if not self._multi and (self._fork_on or self._rider_on):
+    if not self._multi and self._fork_on:
       ga = torch.cuda.CUDAGraph()
       with torch.cuda.graph(ga, pool=self._pool, stream=self._stream, capture_error_mode=self._cap_mode):
-        if self._rider_on:
-          self._rider_step()  # ONE serial chain; the optimizer rides in the backward's GEMM launches
-        else:
-          self._fork_step()  # ONE graph whose branches are the main and the side stream
+        self._fork_step()  # ONE graph whose branches are the main and the side stream
         self._upload_branch_end()
       self._graphs, self._e = (ga, None, None), None
       torch.cuda.synchronize()

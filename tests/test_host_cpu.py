@@ -22,11 +22,6 @@ def _header_functions():
   return out
 
 
-def _header_define(name):
-  src = open(os.path.join(ROOT, 'include', 'mmt_hip.h')).read()
-  return int(re.search(r'#define\s+%s\s+(\d+)' % name, src).group(1))
-
-
 def test_library_exports_every_declared_symbol_and_bindings_match():
   from mmt_amd import _lib
   decl = _header_functions()
@@ -37,17 +32,23 @@ def test_library_exports_every_declared_symbol_and_bindings_match():
     assert name in _lib.SIGNATURES, 'no ctypes signature for ' + name
     assert len(_lib.SIGNATURES[name][1]) == nargs, 'arity mismatch for ' + name
   assert set(_lib.SIGNATURES) == set(decl)
-  assert _lib.lib().mmt_abi_version() == 3
+  assert _lib.lib().mmt_abi_version() == 4
   # struct layouts agree with the C side (sizes are what the kernels are compiled against)
-  assert ctypes.sizeof(_lib.MmtEpilogue) == 144  # + dot_src / lddot / dot_out (r04), rider / rider_limit / rider_slot / live_rows_hint (r06)
+  assert ctypes.sizeof(_lib.MmtEpilogue) == 128  # + dot_src / lddot / dot_out (r04), live_rows_hint (r06)
   assert ctypes.sizeof(_lib.MmtPackItem) == 48
   assert ctypes.sizeof(_lib.MmtExpertIO) == 96
   assert ctypes.sizeof(_lib.MmtBertLayer) == 28 * 8
-  assert ctypes.sizeof(_lib.MmtBertBatch) == 128  # + side_stream (r03), rider / rider_limits / rider_slot0 / live_rows_hint (r06)
-  assert ctypes.sizeof(_lib.MmtAdamQueue) == 416 and _header_define('MMT_RIDER_SLOTS') == _lib.RIDER_SLOTS
-  assert _header_define('MMT_RIDER_STAGES') == _lib.RIDER_STAGES and _lib.RIDER_STATE_WORDS == 72 + 1 + 1024 + 64 + 4096
+  assert ctypes.sizeof(_lib.MmtBertBatch) == 112  # + side_stream (r03), live_rows_hint (r06)
   assert ctypes.sizeof(_lib.MmtVideoFront) == 8 + 6 * 4 + 11 * 8  # experts | M B T pack max_pos do_cast | 11 pointers
   assert ctypes.sizeof(_lib.MmtTextHeadsOpts) == 16 + 4 * 8          # + video_front (r03)
+
+
+def test_graphed_step_refuses_the_removed_adam_riders():
+  """The Adam riders were removed in ABI 4: asking for them fails before any device work instead of measuring the
+  default step under another name."""
+  from mmt_amd.train_step import GraphedTrainStep
+  with pytest.raises(ValueError):
+    GraphedTrainStep(None, None, None, adam_riders=True)
 
 
 def test_gemm_tile_policy_is_a_function_of_shape_and_live_rows():
