@@ -61,7 +61,9 @@ typedef struct MmtEpilogue {
   uint32_t drop_key;        /* dropout stream key (seed, site, layer mixed by the host)         */
   uint32_t drop_thr16;      /* keep iff u16 >= thr16; 0 disables dropout                        */
   float drop_scale;         /* 1 / (1 - thr16/65536)                                            */
-  int32_t reserved;         /* 0 = auto tile; 1 = force 128x128; 2 = force 128x64 (tests/tuning)       */
+  int32_t reserved;         /* 0 = auto tile; forced tile id (tests/tuning): 1 / 2 = the 4-wave 128x128 / 128x64 kernel
+                             * of gemm.hip, 13 / 14 / 18 = gemm2.hip, 21 = gemm3.hip, 24 / 25 = gemm5.hip; any other
+                             * id >= 3 is MMT_ERR_ARG                                                    */
   /* MMT_EPI_BF16 only, nullable: dot_out[row, n / 64] = sum over the 64 output columns of group n / 64 of
    * out(bf16)[row, n] * dot_src(bf16)[row, n] -- with out = dO = dA . Wo and dot_src = O (the attention context) these are
    * the "delta" sums of the attention backward (rowsum(dO * O) per head = DH / 64 groups), formed while dO is still in

@@ -13,7 +13,6 @@
 //       ds_read_b64_tr_b16 (hardware 4x16 transpose) because the contraction index is the ROW.
 // MFMA operands are swapped (a = B-side fragment) so each lane ends up with 4 consecutive output
 // columns of one row: 8/16-byte stores instead of 2-byte scatters.
-#include <stdlib.h>
 #include "mmt_common.h"
 #include "../../include/mmt_hip.h"
 
@@ -295,11 +294,35 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(
 // 48 + 16 + 96 + 96 = 256 tiles = one per CU.  Tiles in the first tile-column also produce the bias gradient
 // (column sums of the bf16 dY operand) with one extra MFMA per fragment against an all-ones operand.
 // ------------------------------------------------------------------------------------------------
-// 8 waves per tile: wave group kg = wave >> 2 contracts the even / odd 64-row units of the token dimension with its
-// own LDS ring (intra-block split-K), so a CU that owns ONE tile still has two independent load/MFMA streams in
-// flight; the two partial tiles are summed through LDS at the end (fixed order => deterministic).
+// Transpose reads issued from inline asm.  The compiler cannot tell an LDS-DMA write from the LDS location a transpose
+// read touches and drains vmcnt to ZERO in front of every builtin ds_read_tr that follows a global_load_lds -- i.e. it
+// waits for the prefetches of later units as well.  Issued this way the reads are invisible to that analysis; the price
+// is that their completion has to be waited for by hand (TR_WAIT ties the loaded registers to the s_waitcnt so that no
+// consumer can be scheduled above it).
+// Both halves of one fragment (rows r0 and r0 + 16 of the same 16-byte chunk: the swizzle repeats every 8 rows, so the
+// second read is the first one's address + 16 rows = 4096 bytes, an instruction immediate).
+__device__ __forceinline__ void tr_frag_issue(u32x2& lo, u32x2& hi, unsigned addr) {
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(addr));
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:4096" : "=v"(hi) : "v"(addr));
+}
+// LDS byte offset (inside a [64][128] bf16 tile) of the first half of the fragment for columns colbase .. colbase + 15,
+// k-sub-step ks.  Fragments 16 columns further on are this offset XOR 32 per step (two 16-byte chunks: the chunk index is
+// XOR-swizzled, and colbase only sets bits the swizzle leaves alone in a multiple of 64).
+__device__ __forceinline__ unsigned tr_frag_offset(int ks, int colbase, int lane) {
+  const int t = lane & 15, g = lane >> 4;
+  const int col = colbase + 4 * (t & 3);
+  const int r0 = ks * 32 + 4 * g + (t >> 2);
+  const int ch = col >> 3, w = col & 7;
+  return (unsigned)((r0 * 128 + ((ch ^ ((r0 & 7) << 1)) << 3) + w) * 2);
+}
+#define TR_TIE4(x) "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3])
+__device__ __forceinline__ bf16x8_t tr_join(const u32x2& lo, const u32x2& hi) {
+  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
+  return __builtin_bit_cast(bf16x8_t, v);
+}
+
 #ifdef MMT_GEMM2_INSTR
-__device__ long long* g_wgrad_dbg = nullptr;  // lab build only: per-block cycle counters
+__device__ long long* g_wgrad_dbg = nullptr;  // instrumented build only: per-block cycle counters
 extern "C" int mmt_debug_set_wgrad_buffer(void* p) {
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_wgrad_dbg), &p, sizeof(p));
 }
@@ -307,9 +330,27 @@ extern "C" int mmt_debug_set_wgrad_buffer(void* p) {
 #else
 #define WTICK(acc) do {} while (0)
 #endif
-__global__ __launch_bounds__(512) void wgrad_grouped_kernel(MmtWgradGroup g) {
+
+// ------------------------------------------------------------------------------------------------
+// Eight waves per tile, as two groups of four in OPPOSITE phase, with 64 x 128 wave tiles.
+//   * The 64-row units of the contraction alternate between the groups: unit u belongs to group u & 1 and lives in stage
+//     u & 3 of ONE four-deep ring.  In half-step h, group h & 1 runs the transpose reads + MFMAs of unit h while the other
+//     group issues the LDS-DMA loads of unit h + 3 (its own next but one): the ~90 cycles a global_load_lds stalls its wave
+//     at issue hide under the other group's MFMAs, loads have two half-steps to land (counted vmcnt: a group waits for
+//     its OWN loads), and one workgroup barrier per half-step orders both hazards (unit h has landed; the stage of unit
+//     h - 1 is free).
+//   * What then bounds a half-step is LDS read bandwidth: ds_read_b64_tr_b16 delivers ~64 B/clk/CU, and four 64 x 64 wave
+//     tiles read 64 KiB per unit (measured on r02's lock-step kernel: 1620 cycles per unit against 544 cycles of MFMA).  The
+//     four waves of a group therefore split the unit 2 (32-row halves = the two k-sub-steps) x 2 (halves of the tile's
+//     128 dW rows): a wave computes 64 x 128 outputs over 32 rows from 4 + 8 fragments (48 KiB per unit, -25 %), at the
+//     price of four partial tiles per output (2 groups x 2 row halves) summed through LDS at the end, in a fixed order.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512) void wgrad_phased_kernel(MmtWgradGroup g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char wg_smem[];
-  bf16_t* smem = (bf16_t*)wg_smem;  // [2 stages][2 groups][A 64x128 | B 64x128]
+#ifdef MMT_GEMM2_INSTR
+  const long long t_entry = clock64();
+#endif
+  bf16_t* smem = (bf16_t*)wg_smem;  // ring: 4 units x [A 64x128 | B 64x128]
   const int id = xcd_remap(blockIdx.x, gridDim.x);
   int p = 0;
 #pragma unroll 1
@@ -345,224 +386,6 @@ __global__ __launch_bounds__(512) void wgrad_grouped_kernel(MmtWgradGroup g) {
                                     : (g.n_rows_dev ? min(*g.n_rows_dev, g.rows) : g.rows);
   const int units_all = (nrows + 63) / 64;  // 64-row units of the contraction
   // item.splits > 1: the units are divided among `splits` blocks per tile, each writing its own partial slab
-  const int per_split = (units_all + nsplit - 1) / nsplit;
-  const int u0 = split * per_split;
-  const int units = max(0, min(units_all, u0 + per_split) - u0);
-  const int steps = (units + 1) / 2;       // each step: group 0 takes unit 2s, group 1 unit 2s+1
-
-  const int tid = threadIdx.x, lane = tid & 63, wave8 = tid >> 6;
-  const int kg = wave8 >> 2, wave = wave8 & 3;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 15, lg = lane >> 4;
-  // bias gradient (column sums of the A operand) in the first tile column: the two waves that hold the same A fragments
-  // (wn = 0 / 1) take two of the four each, so no wave of the tile carries 25 % more MFMAs than its neighbours
-  const bool want_bias = it.bias_out != nullptr && tk == 0;
-  f32x4 acc[4][4], accb[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    accb[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  bf16x8_t ones;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
-  constexpr int GSTAGE = 2 * 64 * 128;      // one group's [A | B] tiles
-  constexpr int TSTAGE = 2 * GSTAGE;        // both groups
-
-  auto stage = [&](int step, int st) {
-    const int unit = 2 * step + kg;
-    if (unit < units) {
-      bf16_t* base = smem + st * TSTAGE + kg * GSTAGE;
-      stage_tn(A, lda, (u0 + unit) * 64, n0, base, wave, lane);
-      stage_tn(B, ldb, (u0 + unit) * 64, k0, base + 64 * 128, wave, lane);
-    }
-  };
-#ifdef MMT_GEMM2_INSTR
-  long long t_wait = 0, t_bar = 0, t_issue = 0, t_comp = 0, t0 = clock64(), tp = t0;
-#endif
-  if (steps > 0) stage(0, 0);
-  for (int s = 0; s < steps; ++s) {
-    const int cur = s & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    WTICK(t_wait);
-    __syncthreads();
-    WTICK(t_bar);
-    if (s + 1 < steps) stage(s + 1, cur ^ 1);
-    WTICK(t_issue);
-    const int unit = 2 * s + kg;
-    bf16_t* at = smem + cur * TSTAGE + kg * GSTAGE;
-    bf16_t* bt = at + 64 * 128;
-    const int live = unit < units ? nrows - (u0 + unit) * 64 : 0;  // rows of this unit that exist (<= 0: nothing to do)
-    if (2 * s + 1 >= units || nrows - (u0 + 2 * s + 1) * 64 < 64) {  // last step: ragged tails (block-uniform condition)
-      if (live > 0 && live < 64) {
-        for (int e = wave * 64 + lane; e < (64 - live) * 32; e += 256) {
-          const int r = live + e / 32, q = e % 32;
-          u32x4 z = {0, 0, 0, 0};
-          if (q < 16) *(u32x4*)(at + r * 128 + q * 8) = z;
-          else *(u32x4*)(bt + r * 128 + (q - 16) * 8) = z;
-        }
-      }
-      __syncthreads();
-    }
-    if (live > 0) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8_t af[4], bfr[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) af[i] = tr_frag(at, ks, wm * 64 + i * 16, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bfr[j] = tr_frag(bt, ks, wn * 64 + j * 16, lane);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-        if (want_bias) {
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {  // (two static branches: a dynamic index would send af[] to scratch)
-            if (wn == 0) accb[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, af[i], accb[i], 0, 0, 0);
-            else accb[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, af[2 + i], accb[i], 0, 0, 0);
-          }
-        }
-      }
-    }
-#ifdef MMT_GEMM2_INSTR
-    asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[3][3][3]));
-#endif
-    WTICK(t_comp);
-  }
-#ifdef MMT_GEMM2_INSTR
-  if (g_wgrad_dbg && tid == 0) {
-    long long* d = g_wgrad_dbg + (int64_t)blockIdx.x * 8;
-    d[0] = t_wait; d[1] = t_bar; d[2] = t_issue; d[3] = t_comp; d[4] = clock64() - t0; d[5] = steps; d[6] = p; d[7] = t0;
-  }
-#endif
-  // ---- sum the two wave groups through LDS (group 1 -> group 0), then store ----
-  __syncthreads();
-  f32x4* xch = (f32x4*)wg_smem;  // [20][256] f32x4 = 80 KiB
-  const int t4 = wave * 64 + lane;
-  if (kg == 1) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) xch[(i * 4 + j) * 256 + t4] = acc[i][j];
-      xch[(16 + i) * 256 + t4] = accb[i];
-    }
-  }
-  __syncthreads();
-  if (kg == 1) return;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] += xch[(i * 4 + j) * 256 + t4];
-    accb[i] += xch[(16 + i) * 256 + t4];
-  }
-  float* __restrict__ out = nsplit > 1 ? it.slab + (int64_t)split * it.N_out * it.ldo : it.out;
-  float* __restrict__ bias_out = nsplit > 1 ? (it.bias_slab ? it.bias_slab + (int64_t)split * it.N_out : nullptr) : it.bias_out;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int n = n0 + wm * 64 + i * 16 + li;
-    if (n >= it.N_out) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int k2 = k0 + wn * 64 + j * 16 + lg * 4;
-      if (k2 + 3 < it.K2_out && !(it.ldo & 3)) {
-        *(f32x4*)(out + (int64_t)n * it.ldo + k2) = acc[i][j];
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (k2 + e < it.K2_out) out[(int64_t)n * it.ldo + k2 + e] = acc[i][j][e];
-      }
-    }
-    if (want_bias && lg == 0 && (i >> 1) == wn) bias_out[n] = accb[i & 1][0];
-  }
-}
-
-// Transpose reads issued from inline asm.  The compiler cannot tell an LDS-DMA write from the LDS location a transpose
-// read touches and drains vmcnt to ZERO in front of every builtin ds_read_tr that follows a global_load_lds -- i.e. it
-// waits for the prefetches of later units as well.  Issued this way the reads are invisible to that analysis; the price
-// is that their completion has to be waited for by hand (TR_WAIT ties the loaded registers to the s_waitcnt so that no
-// consumer can be scheduled above it).
-// Both halves of one fragment (rows r0 and r0 + 16 of the same 16-byte chunk: the swizzle repeats every 8 rows, so the
-// second read is the first one's address + 16 rows = 4096 bytes, an instruction immediate).
-__device__ __forceinline__ void tr_frag_issue(u32x2& lo, u32x2& hi, unsigned addr) {
-#ifndef MMT_WGRAD_LAB_NOREADS
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(addr));
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:4096" : "=v"(hi) : "v"(addr));
-#else  // lab: no LDS traffic, the MFMAs run on whatever the registers hold
-  asm volatile("v_mov_b32 %0, %1" : "=v"(lo[0]) : "v"(addr));
-  lo[1] = lo[0]; hi = lo;
-#endif
-}
-// LDS byte offset (inside a [64][128] bf16 tile) of the first half of the fragment for columns colbase .. colbase + 15,
-// k-sub-step ks.  Fragments 16 columns further on are this offset XOR 32 per step (two 16-byte chunks: the chunk index is
-// XOR-swizzled, and colbase only sets bits the swizzle leaves alone in a multiple of 64).
-__device__ __forceinline__ unsigned tr_frag_offset(int ks, int colbase, int lane) {
-  const int t = lane & 15, g = lane >> 4;
-  const int col = colbase + 4 * (t & 3);
-  const int r0 = ks * 32 + 4 * g + (t >> 2);
-  const int ch = col >> 3, w = col & 7;
-  return (unsigned)((r0 * 128 + ((ch ^ ((r0 & 7) << 1)) << 3) + w) * 2);
-}
-#define TR_TIE4(x) "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3])
-__device__ __forceinline__ bf16x8_t tr_join(const u32x2& lo, const u32x2& hi) {
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// The same grouped weight gradients with the two wave groups in OPPOSITE phase and 64 x 128 wave tiles (default; the
-// lock-step kernel above stays for same-box A/B, MMT_WGRAD_LOCKSTEP=1).
-//   * The 64-row units of the contraction alternate between the groups: unit u belongs to group u & 1 and lives in stage
-//     u & 3 of ONE four-deep ring.  In half-step h, group h & 1 runs the transpose reads + MFMAs of unit h while the other
-//     group issues the LDS-DMA loads of unit h + 3 (its own next but one): the ~90 cycles a global_load_lds stalls its wave
-//     at issue hide under the other group's MFMAs, loads have two half-steps to land (counted vmcnt: a group waits for
-//     its OWN loads), and one workgroup barrier per half-step orders both hazards (unit h has landed; the stage of unit
-//     h - 1 is free).
-//   * What then bounds a half-step is LDS read bandwidth: ds_read_b64_tr_b16 delivers ~64 B/clk/CU, and four 64 x 64 wave
-//     tiles read 64 KiB per unit (measured 1620 cycles per unit against 544 cycles of MFMA, tools/wgrad_instr.py).  The
-//     four waves of a group therefore split the unit 2 (32-row halves = the two k-sub-steps) x 2 (halves of the tile's
-//     128 dW rows): a wave computes 64 x 128 outputs over 32 rows from 4 + 8 fragments (48 KiB per unit, -25 %), at the
-//     price of four partial tiles per output (2 groups x 2 row halves) summed through LDS at the end, in a fixed order.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(512) void wgrad_phased_kernel(MmtWgradGroup g) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char wg_smem[];
-#ifdef MMT_GEMM2_INSTR
-  const long long t_entry = clock64();
-#endif
-  bf16_t* smem = (bf16_t*)wg_smem;  // ring: 4 units x [A 64x128 | B 64x128]
-  const int id = xcd_remap(blockIdx.x, gridDim.x);
-  int p = 0;
-#pragma unroll 1
-  for (int q = 1; q < g.count; ++q)
-    if (id >= g.item[q].tile_begin) p = q;
-  const MmtWgradItem& it = g.item[p];
-  const bf16_t* __restrict__ A = (const bf16_t*)it.A;
-  const bf16_t* __restrict__ B = (const bf16_t*)it.B;
-  const int64_t lda = it.lda, ldb = it.ldb;
-  const int nsplit = it.splits > 1 ? it.splits : 1;
-  const int tile = (id - it.tile_begin) / nsplit, split = (id - it.tile_begin) % nsplit;
-  const int tiles_k = it.K2 / 128;
-  int tn, tk;
-  {
-    const int PN = it.reserved2 >> 16, PK = it.reserved2 & 0xffff;  // XCD-sized patches, see the lock-step kernel
-    if (PN > 0 && PK > 0) {
-      const int per = PN * PK, patches_k = tiles_k / PK;
-      const int patch = tile / per, within = tile % per;
-      tn = (patch / patches_k) * PN + within / PK;
-      tk = (patch % patches_k) * PK + within % PK;
-    } else {
-      tn = tile / tiles_k;
-      tk = tile % tiles_k;
-    }
-  }
-  const int n0 = tn * 128, k0 = tk * 128;
-  const int nrows = it.reserved > 0 ? it.reserved
-                    : it.n_rows_dev ? min(*it.n_rows_dev, g.rows)
-                                    : (g.n_rows_dev ? min(*g.n_rows_dev, g.rows) : g.rows);
-  const int units_all = (nrows + 63) / 64;
   const int per_split = (units_all + nsplit - 1) / nsplit;
   const int u0 = split * per_split;
   const int units = max(0, min(units_all, u0 + per_split) - u0);
@@ -647,8 +470,8 @@ __global__ __launch_bounds__(512) void wgrad_phased_kernel(MmtWgradGroup g) {
     // transpose reads: the 4 A fragments and the first THREE pairs of B fragments go out at once, the fourth after the
     // first pair's MFMAs: an LDS round trip (~150-200 cycles) then hides behind two pairs of MFMAs (in-order returns:
     // "at most N outstanding" = everything issued before the last N reads has landed).  Measured with the MFMAs compiled
-    // out (tools/wgrad_instr.py, MMT_LAB_DEFINES=MMT_WGRAD_LAB_NOMFMA): the reads' latency chain alone is 1040 of the 1400
-    // cycles of a compute half-step when only one pair is in flight ahead of the MFMAs.  (r05: the opposite split -- A and
+    // out: the reads' latency chain alone is 1040 of the 1400 cycles of a compute half-step when only one pair is in flight
+    // ahead of the MFMAs.  (r05: the opposite split -- A and
     // the first B pair up front, pairs 1..3 behind the MFMAs of pairs 0 / 1, 12 instead of 20 reads in front of the first
     // MFMA -- measured identical: 46.8-47.0 vs 45.5-46.9 us per launch in the step's eager probes, same step time.)
     // One base address per operand; every fragment's address is that XOR a constant, formed right at the read (the asm
@@ -681,11 +504,7 @@ __global__ __launch_bounds__(512) void wgrad_phased_kernel(MmtWgradGroup g) {
         const int j = 2 * q + jj;
         const bf16x8_t bfr = tr_join(blo[q][jj], bhi[q][jj]);
 #pragma unroll
-#ifndef MMT_WGRAD_LAB_NOMFMA
         for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr, af[i], acc[i][j], 0, 0, 0);
-#else   // lab: the reads stay (consumed by one cheap op), the matrix pipe idles
-        for (int i = 0; i < 1; ++i) acc[i][j][0] += (float)bfr[0] + (float)af[jj][0];
-#endif
       }
       if (q == 0) {
 #pragma unroll
@@ -820,19 +639,10 @@ extern "C" int mmt_wgrad_grouped(const MmtWgradGroup* g, void* stream) {
   int tiles = 0;
   // r04: 256 x 256 tiles (wgrad3.hip) when every item is cut into such tiles without remainder, nothing is split over the
   // rows, and the launch has at least 3/4 of a tile per CU over thousands of rows (configs[4]: d = 1024, 256 tiles).
-  // MMT_WGRAD3=0 switches it off (same-box A/B).
+  constexpr int kWgrad3MinRows = 2048, kWgrad3MinTiles = 192;
   {
-    static int w3 = -1, w3_rows = 2048, w3_tiles = 192;
-    if (w3 < 0) {
-      const char* e = getenv("MMT_WGRAD3");
-      w3 = e ? atoi(e) : 1;
-      const char* r = getenv("MMT_WGRAD3_ROWS");   // (lab: the thresholds of this choice)
-      const char* t = getenv("MMT_WGRAD3_TILES");
-      if (r) w3_rows = atoi(r);
-      if (t) w3_tiles = atoi(t);
-    }
     int t3 = 0;
-    bool ok = w3 != 0 && h.rows >= w3_rows;
+    bool ok = h.rows >= kWgrad3MinRows;
     for (int q = 0; q < h.count && ok; ++q) {
       const MmtWgradItem& it = h.item[q];
       ok = it.A && it.B && it.out && it.N > 0 && it.K2 > 0 && it.N % 256 == 0 && it.K2 % 256 == 0 && it.splits <= 1 &&
@@ -840,7 +650,7 @@ extern "C" int mmt_wgrad_grouped(const MmtWgradGroup* g, void* stream) {
            it.lda >= 256 && it.ldb >= 256;
       t3 += (it.N / 256) * (it.K2 / 256);
     }
-    if (ok && t3 >= w3_tiles) {
+    if (ok && t3 >= kWgrad3MinTiles) {
       int tb = 0;
       for (int q = 0; q < h.count; ++q) {
         MmtWgradItem& it = h.item[q];
@@ -875,19 +685,14 @@ extern "C" int mmt_wgrad_grouped(const MmtWgradGroup* g, void* stream) {
       it.reserved2 = (pn << 16) | pk;
     }
   }
-  constexpr int lds = 2 * 2 * 2 * 64 * 128 * 2;   // lock-step: 2 stages x 2 wave groups x (A + B) 64x128 bf16 = 128 KiB
-  constexpr int lds_phased = 36 * 256 * 16;       // phased: the same 128 KiB ring; 144 KiB for the final exchange
-  static int lockstep = -1;
-  if (lockstep < 0) {
-    hipError_t rc = hipFuncSetAttribute((const void*)wgrad_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (rc == hipSuccess)
-      rc = hipFuncSetAttribute((const void*)wgrad_phased_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_phased);
+  constexpr int lds = 36 * 256 * 16;  // a 128 KiB ring of 4 units x (A + B) 64x128 bf16; 144 KiB for the final exchange
+  static bool configured = false;
+  if (!configured) {
+    hipError_t rc = hipFuncSetAttribute((const void*)wgrad_phased_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (rc != hipSuccess) return (int)rc;
-    const char* e = getenv("MMT_WGRAD_LOCKSTEP");
-    lockstep = e ? atoi(e) : 0;
+    configured = true;
   }
-  if (lockstep) hipLaunchKernelGGL(wgrad_grouped_kernel, dim3(tiles), dim3(512), lds, (hipStream_t)stream, h);
-  else hipLaunchKernelGGL(wgrad_phased_kernel, dim3(tiles), dim3(512), lds_phased, (hipStream_t)stream, h);
+  hipLaunchKernelGGL(wgrad_phased_kernel, dim3(tiles), dim3(512), lds, (hipStream_t)stream, h);
   return (int)hipGetLastError();
 }
 
@@ -917,78 +722,20 @@ int mmt_gemm2_dispatch(int tile, int epilogue, const void* A, int64_t lda, const
 
 // ---- tile policy ---------------------------------------------------------------------------------------------------
 // Which kernel runs a GEMM is a pure function of its shape, its epilogue and the number of LIVE rows (token packing: the
-// tiles past the live row count exit, so the launch's real size is the live one).  The live count is on the device; the
-// host's figure is MmtEpilogue.live_rows_hint -- what the collator counted before the upload (MmtBertBatch.live_rows_hint)
-// -- and WITHOUT a hint a packed batch is priced at its allocated rows (every tile live).  r01-r05 guessed
-// M x MMT_LIVE_FRACTION with a default of 0.52 = the fill of the benchmark's synthetic generator: no default of this file
-// is tied to a dataset's fill any more; MMT_LIVE_FRACTION survives as a LAB override only (it replaces the hint).
-// The switches below are read from the environment ONCE (lab / same-box A-B use); mmt_gemm_select_tile exposes the policy
-// to tests (tests/test_host_cpu.py asserts the tile of every shipped (shape, live rows) class).
-struct TilePolicy {
-  int big = 1;      // MMT_TILE_BIG   : 256x256 eight-phase kernel (gemm3.hip, tile 21) where it fills the chip
-  int big_kmin = 1024;  // MMT_TILE_BIG_KMIN: ... from this K on (with >= 220 such tiles; K >= 3072: >= 160)
-  int narrow = 18;  // MMT_TILE_NARROW: tile of the packed N < 1024 GEMMs (18 = phased 128x64 while one round covers them; 13)
-  int wide = 0;     // MMT_TILE_WIDE  : lab, tile for N >= 1024
-  int longk = 0;    // MMT_TILE_LONGK : lab (23 = gemm4.hip), packed narrow GEMMs with K >= 1536
-  int ppn = 1;      // MMT_TILE_PPN   : gemm5.hip on the narrow GEMMs: 0 off, 1 tile 24 on long K once 128x128 tiles fill a round,
-                    //                  2 / 3 force 24 / 25 there, 4 = 24 or else 25, 5 = tile 25 for every packed narrow GEMM,
-                    //                  6 = 1 + tile 25 for the packed K < 1536 ones
-  int pp = 1;       // MMT_TILE_PP    : gemm5.hip (tile 24) on the wide K = hidden GEMMs: 0 off, 1 from 1024 live tiles, 2 from 512
-  int t192 = 0, forced3072 = 0, forced1536 = 0;  // MMT_TILE_192 / _N3072 / _N1536: lab (192-wide tiles)
-  double live_fraction = 0.0;                    // MMT_LIVE_FRACTION: lab override of the live-row estimate (0 = unset)
-};
-static const TilePolicy& tile_policy() {
-  static const TilePolicy pol = [] {
-    TilePolicy p;
-    auto geti = [](const char* name, int def) { const char* v = getenv(name); return v ? atoi(v) : def; };
-    p.big = geti("MMT_TILE_BIG", p.big);
-    p.big_kmin = geti("MMT_TILE_BIG_KMIN", p.big_kmin);
-    p.narrow = geti("MMT_TILE_NARROW", p.narrow);
-    p.wide = geti("MMT_TILE_WIDE", p.wide);
-    p.ppn = geti("MMT_TILE_PPN", p.ppn);
-    p.pp = geti("MMT_TILE_PP", p.pp);
-    const char* f = getenv("MMT_LIVE_FRACTION");
-    if (f && atof(f) > 0.0) p.live_fraction = atof(f);
-#ifdef MMT_LAB_TILES  // (tile 23 = gemm4.hip and the 192-wide tiles exist in the lab library only)
-    p.longk = geti("MMT_TILE_LONGK", 0);
-    p.t192 = geti("MMT_TILE_192", 0);
-    p.forced3072 = geti("MMT_TILE_N3072", 0);
-    p.forced1536 = geti("MMT_TILE_N1536", 0);
-#endif
-    return p;
-  }();
-  return pol;
-}
+// tiles past the live row count exit, so the launch's real size is the live one): no environment variable and no build
+// flag enters it.  The live count is on the device; the host's figure is MmtEpilogue.live_rows_hint -- what the collator
+// counted before the upload (MmtBertBatch.live_rows_hint) -- and WITHOUT a hint a packed batch is priced at its allocated
+// rows (every tile live); no default of this file is tied to a dataset's fill.  mmt_gemm_select_tile exposes the policy to
+// tests (tests/test_host_cpu.py asserts the tile of every shipped (shape, live rows) class).
 
 // rows of the problem that hold live tokens, as far as the host knows
-static int live_rows_of(const TilePolicy& pol, int M, bool packed, int hint) {
+static int live_rows_of(int M, bool packed, int hint) {
   if (!packed) return M;
-  if (pol.live_fraction > 0.0) return (int)(M * pol.live_fraction);
   return hint > 0 && hint < M ? hint : M;
 }
 
-// Wide outputs whose width is a multiple of 192 (QKV: 1536, FFN: 3072), LAB library only: a 192-column tile can cover the live
-// rows in ONE round of <= 256 blocks where the 128x128 tile needs 1.3 rounds at 2 blocks per CU (measured: whole-step A/B
-// 1.473 ms off vs 1.485 ms on; tile 20 = a two-deep 128x192 ring: step 1.302 -> 1.339 ms -- opt-in).
-static int wide192_tile(const TilePolicy& pol, int live, int N) {
-  if (N == 3072 && pol.forced3072) return pol.forced3072;
-  if (N == 1536 && pol.forced1536) return pol.forced1536;
-  const int cols = N / 192;
-  const int big = ((live + 255) / 256) * cols, mid = ((live + 127) / 128) * cols;
-  if (pol.t192 == 1) {
-    if (big > 128 && big <= 256) return 15;   // 256x192, one block per CU, one round
-    if (mid > 128 && mid <= 256) return 16;   // 128x192
-    return 0;
-  }
-  if (pol.t192 == 3) {
-    const int sq = ((live + 127) / 128) * (N / 128);
-    if (sq > 512 && mid <= 512) return 20;
-  }
-  return 0;
-}
-
-// -> tile id: 13 / 14 / 18 (gemm2.hip), 21 (gemm3.hip), 24 / 25 (gemm5.hip), lab tiles, or 1 / 2 = this file's 4-wave
-// 128x128 / 128x64 kernel.  Measured on MI355X (tools/gemm_lab.py, tools/gemm_instr.py, profiles/r01_gemm_lab.txt):
+// -> tile id: 13 / 14 / 18 (gemm2.hip), 21 (gemm3.hip), 24 / 25 (gemm5.hip), or 1 / 2 = this file's 4-wave 128x128 / 128x64
+// kernel.  Measured on MI355X (tools/gemm_lab.py, tools/gemm_instr.py, profiles/r01_gemm_lab.txt):
 //   * wide outputs (N >= 1024: QKV, FFN up-projection, dGELU) run best on gemm2's 128x128 tile with 8 waves (wave tile 64x32)
 //     at 2 blocks/CU -- from 1024 live tiles on (>= 4 per CU) on the persistent wave-specialised kernel (tile 24: its first
 //     K-loop and last epilogue are not overlapped with anything: headline, 696 live tiles: 1.2934 vs 1.2816 ms with it; dense
@@ -1001,34 +748,29 @@ static int wide192_tile(const TilePolicy& pol, int live, int N) {
 //     (at K = 512 prologue and epilogue eat the gain: configs[3] 3.00 -> 3.26 ms with it);
 //   * short batches (M <= 1024: the text tower's ~560..960 token rows) and few-row problems: the 128x64 8-wave tile (13);
 //   * the dense N = 512 GEMMs stay on this file's 128x64 4-wave tile (both saturate the CU's LDS ingest).
+constexpr int kRoundBlocks = 256;       // one block per CU: what "one round" of the chip holds
+constexpr int kBigTiles = 220;          // 256x256 tiles from which tile 21 fills the chip, K >= kBigK ...
+constexpr int kBigK = 1024;
+constexpr int kBigTilesLongK = 160;     // ... or this many with K >= kBigLongK
+constexpr int kBigLongK = 3072;
+constexpr int kNarrowLongK = 1536;      // "long K" of the narrow GEMMs (tile 24 ...
+constexpr int kNarrowLongKTiles = 200;  // ... from this many live 128x128 tiles)
+constexpr int kWideLiveTiles = 1024;    // live 128x128 tiles (>= 4 per CU) from which the wide K = hidden GEMMs take tile 24
 static int select_tile(int EPI, int M, int N, int K, bool packed, int live_hint, bool colsum, bool dot_out, int reserved) {
-  const TilePolicy& pol = tile_policy();
   if ((reserved & 0xff) >= 3) return reserved & 0xff;  // forced (tests / tuning)
   const bool dgelu_sums = EPI == MMT_EPI_DGELU && colsum;
-  const int live = live_rows_of(pol, M, packed, live_hint);
+  const int live = live_rows_of(M, packed, live_hint);
   const long rt128 = (live + 127) / 128;  // live row tiles of 128
-  if (pol.big && reserved == 0 && N % 256 == 0 && M > 1024) {
+  if (reserved == 0 && N % 256 == 0 && M > 1024) {
     const long t21 = (long)((live + 255) / 256) * (N / 256);
-    if ((t21 >= 220 && K >= pol.big_kmin) || (t21 >= 160 && K >= 48 * 64 && K >= pol.big_kmin)) return 21;
+    if ((t21 >= kBigTiles && K >= kBigK) || (t21 >= kBigTilesLongK && K >= kBigLongK)) return 21;
   }
   if (reserved == 0 && M > 1024 && !dgelu_sums) {
-    const bool one_round = rt128 * (N / 64) <= 256;
+    const long t128 = rt128 * (N / 128);
     const bool plain_epi = EPI != MMT_EPI_BIAS_GELU && EPI != MMT_EPI_DGELU && !dot_out;
-    if (pol.ppn >= 5 && N < 1024 && N % 64 == 0 && K >= 128 && K % 64 == 0 && packed && plain_epi && (pol.ppn == 5 || K < 1536))
-      return 25;
-    if (pol.ppn && N < 1024 && N % 128 == 0 && K >= 1536 && plain_epi) {
-      const long t128 = rt128 * (N / 128);
-      const int t = pol.ppn == 2 ? 24 : pol.ppn == 3 ? 25 : t128 >= 200 ? 24 : pol.ppn == 4 ? 25 : 0;
-      if (t) return t;
-    }
-    if (pol.narrow && N < 1024 && packed && (pol.narrow != 18 || one_round))
-      return pol.longk && K >= 1536 && one_round ? pol.longk : pol.narrow;
-    if (pol.wide && N >= 1024) return pol.wide;
-    if (pol.pp && N >= 1024 && N % 128 == 0 && K >= 128 && K <= 1024 && rt128 * (N / 128) >= (pol.pp >= 2 ? 512 : 1024)) return 24;
-  }
-  if (reserved == 0 && M >= 512 && N >= 1024 && N % 192 == 0 && !dgelu_sums && (pol.t192 || pol.forced3072 || pol.forced1536)) {
-    const int t = wide192_tile(pol, live, N);
-    if (t) return t;
+    if (N < 1024 && N % 128 == 0 && K >= kNarrowLongK && plain_epi && t128 >= kNarrowLongKTiles) return 24;
+    if (N < 1024 && packed && rt128 * (N / 64) <= kRoundBlocks) return 18;
+    if (N >= 1024 && N % 128 == 0 && K >= 128 && K <= 1024 && t128 >= kWideLiveTiles) return 24;
   }
   if (reserved == 0 && M <= 1024 && !dgelu_sums) return 13;
   if (reserved == 0 && M >= 512) {

@@ -86,7 +86,7 @@ __device__ __forceinline__ void gemm2_body(
     const int32_t* __restrict__ n_rows_dev, const int bid, const int nblk) {
   constexpr int GW = WGM * WGN;  // waves that tile the output once
   constexpr int NW = PH ? 2 * GW : GW, NT = NW * 64, WTM = BM / WGM, WTN = BN / WGN, MI = WTM / 32, NJ = WTN / 32;
-  static_assert(!PH || NS == 4 || NS == 6, "the phased loop runs on a four- or six-deep ring");
+  static_assert(!PH || NS == 4, "the phased loop runs on a four-deep ring");
   // 8-wave blocks run as two groups in opposite phase (waves w and w+4 share a SIMD): group 0 issues the next
   // stage's LDS-DMA and THEN computes, group 1 computes and THEN issues.  An LDS-DMA instruction stalls its wave for
   // ~100 cycles at issue (measured, tools/gemm_instr.py); staggered, that stall hides under the partner wave's MFMAs.
@@ -155,15 +155,15 @@ __device__ __forceinline__ void gemm2_body(
   // drained inside the loop (raw s_barrier -- __syncthreads() would add vmcnt(0), cdna guide section 5).
   auto issue_ph = [&](int kt) {  // phased mode: the four waves of group kt & 1 load K-step kt
     if (kt < KT) {
-      bf16_t* base = smem + (kt % NS) * STAGE;  // (phased mode: NS = ring depth, 4 or 6)
+      bf16_t* base = smem + (kt % NS) * STAGE;
       stage2<BM, GW>(A, lda, m0, amax, kt * BK, base, wave, lane);
       if constexpr (BKN) stage2_kn<BN, GW>(B, ldb, kt * BK, n0, base + BM * BK, wave, lane);
       else stage2<BN, GW>(B, ldb, n0, bmax, kt * BK, base + BM * BK, wave, lane);
     }
   };
   if constexpr (PH) {
-    // group g has requested its first NS / 2 own K-steps (g, g + 2, ..) but the last, which goes out in the first half-step
-    if (kg == 0) { issue_ph(0); issue_ph(2); if (NS >= 6) issue_ph(4); } else { issue_ph(1); if (NS >= 6) issue_ph(3); }
+    // group g has requested its first two own K-steps (g, g + 2) but the last, which goes out in the first half-step
+    if (kg == 0) { issue_ph(0); issue_ph(2); } else { issue_ph(1); }
   } else {
 #pragma unroll
   for (int s0 = 0; s0 < NS - 1; ++s0)
@@ -197,9 +197,8 @@ __device__ __forceinline__ void gemm2_body(
     int nxt = 0;
     if constexpr (PH) {
       const bool mine = (kt & 1) == kg;
-      if (mine) {  // outstanding loads of this wave: K-steps kt, kt + 2 (and kt + 4 in the six-deep ring), L instructions each
-        if (NS >= 6 && kt + 4 < KT) wait_vmcnt<2 * L>();
-        else if (kt + 2 < KT) wait_vmcnt<L>();
+      if (mine) {  // outstanding loads of this wave: K-steps kt and kt + 2, L instructions each
+        if (kt + 2 < KT) wait_vmcnt<L>();
         else wait_vmcnt<0>();
       }
       TICK(t_wait);
@@ -616,37 +615,15 @@ static int pick2(int tile, const void* A, int64_t lda, const void* B, int64_t ld
                  int K, const MmtEpilogue& e, const int32_t* nr, hipStream_t s) {
 #define G2(BM_, BN_, WGM_, WGN_, NS_) \
   return launch2<BM_, BN_, WGM_, WGN_, NS_, EPI>(A, lda, B, ldb, C, ldc, M, N, K, e, nr, s)
-  if (EPI == MMT_EPI_DGELU && e.colsum && (tile & 0xff) == 12) return MMT_ERR_ARG;  // 64-row tiles: no column sums
-  // The tiles the dispatcher selects on its own (gemm.hip: dispatch_tile): 13, 14, 18 (+ 21 = gemm3.hip, 24 = gemm5.hip).
-  // Everything else was measured and lost and is compiled into the LAB library only
-  // (python -m mmt_amd.build --lab: -DMMT_LAB_TILES), where tools/gemm_lab.py and the MMT_TILE_* switches reach it.
+  // The tiles of this file that the dispatcher selects (gemm.hip: select_tile); 21 = gemm3.hip and 24 / 25 = gemm5.hip are
+  // routed in mmt_gemm2_dispatch.  Any other id is an argument error: the shapes that were measured and lost (DESIGN
+  // section 7) are gone from the source.
   switch (tile & 0xff) {
     case 13: if (N % 64 == 0) G2(128, 64, 4, 2, 3); break;    // 8 waves on 128x64 (wave 32x32), staggered, 2 blocks/CU
     case 14: if (N % 128 == 0) G2(128, 128, 2, 4, 2); break;  // 8 waves on 128x128, in phase, 2 blocks/CU
     case 18:  // 2 x 4 waves on 128x64, PHASED: the groups take alternate K-steps (wave tile 64x32), 1-2 blocks/CU
       if (N % 64 == 0) return launch2<128, 64, 2, 2, 4, EPI, false, true>(A, lda, B, ldb, C, ldc, M, N, K, e, nr, s);
       break;
-#ifdef MMT_LAB_TILES
-    case 3: if (N % 128 == 0) G2(256, 128, 4, 2, 3); break;   // 8 waves, staggered
-    case 4: if (N % 256 == 0) G2(256, 256, 4, 2, 2); break;   // 8 waves
-    case 5: if (N % 128 == 0) G2(128, 128, 2, 2, 2); break;   // 4 waves, 2 blocks/CU
-    case 7: if (N % 64 == 0) G2(128, 64, 2, 2, 3); break;     // 4 waves
-    case 10: if (N % 128 == 0) G2(256, 128, 4, 2, 2); break;  // 8 waves, in phase
-    case 11: if (N % 128 == 0) G2(128, 128, 2, 4, 3); break;  // 8 waves on 128x128 (wave 64x32), staggered
-    case 12: if (N % 128 == 0) G2(64, 128, 2, 4, 3); break;   // 8 waves on 64x128 (wave 32x32), staggered, 2 blocks/CU
-    case 15: if (N % 192 == 0) G2(256, 192, 4, 2, 2); break;  // 8 waves on 256x192 (wave 64x96), 1 block/CU: N = 3072 at
-                                                              // <= 4096 live rows is ONE round of <= 256 tiles
-    case 16: if (N % 192 == 0) G2(128, 192, 4, 2, 3); break;  // 8 waves on 128x192 (wave 32x96), staggered
-    case 17: if (N % 192 == 0) G2(128, 192, 2, 2, 3); break;  // 4 waves on 128x192 (wave 64x96)
-    case 22:  // tile 18 with a SIX-deep ring (144 KiB): every group keeps two of its own K-steps in flight beside the one it waits for
-      if (N % 64 == 0) return launch2<128, 64, 2, 2, 6, EPI, false, true>(A, lda, B, ldb, C, ldc, M, N, K, e, nr, s);
-      break;
-    case 20: if (N % 192 == 0) G2(128, 192, 4, 2, 2); break;  // 8 waves on 128x192 (wave 32x96), in phase, TWO-deep ring:
-                                                              // 80 KiB of LDS = two blocks per CU (tile 16's three stages allow one)
-    case 19:  // 2 x 4 waves on 128x128, PHASED (wave tile 64x64)
-      if (N % 128 == 0) return launch2<128, 128, 2, 2, 4, EPI, false, true>(A, lda, B, ldb, C, ldc, M, N, K, e, nr, s);
-      break;
-#endif
   }
 #undef G2
   return MMT_ERR_ARG;
@@ -654,13 +631,11 @@ static int pick2(int tile, const void* A, int64_t lda, const void* B, int64_t ld
 
 int mmt_gemm3_dispatch(int epilogue, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int M, int N,
                        int K, const MmtEpilogue& e, const int32_t* nr, hipStream_t s);
-int mmt_gemm4_dispatch(int epilogue, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int M, int N,
-                       int K, const MmtEpilogue& e, const int32_t* nr, hipStream_t s);
 int mmt_gemm5_dispatch(int epilogue, int bn, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int M,
                        int N, int K, const MmtEpilogue& e, const int32_t* nr, hipStream_t s);
 
-// tile: 3 = 256x128, 4 = 256x256, 5 = 128x128, 6 = 128x256 (see MmtEpilogue.reserved); 21 = the 256x256 eight-phase kernel
-// of gemm3.hip
+// tile (see MmtEpilogue.reserved): 13 = 128x64 staggered, 14 = 128x128, 18 = 128x64 phased (this file); 21 = the 256x256
+// eight-phase kernel of gemm3.hip; 24 / 25 = the persistent 128x128 / 128x64 kernel of gemm5.hip.  Anything else: MMT_ERR_ARG.
 int mmt_gemm2_dispatch(int tile, int epilogue, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
                        int64_t ldc, int M, int N, int K, const MmtEpilogue& e, const int32_t* nr, hipStream_t s) {
   if ((tile & 0xff) == 21) return mmt_gemm3_dispatch(epilogue, A, lda, B, ldb, C, ldc, M, N, K, e, nr, s);
@@ -674,9 +649,6 @@ int mmt_gemm2_dispatch(int tile, int epilogue, const void* A, int64_t lda, const
     if (rc != MMT_ERR_ARG) return rc;
     tile = 13;
   }
-#ifdef MMT_LAB_TILES
-  if ((tile & 0xff) == 23) return mmt_gemm4_dispatch(epilogue, A, lda, B, ldb, C, ldc, M, N, K, e, nr, s);  // producer / consumer 128 x 64 (gemm4.hip)
-#endif
   switch (epilogue) {
     case MMT_EPI_BF16: return pick2<MMT_EPI_BF16>(tile, A, lda, B, ldb, C, ldc, M, N, K, e, nr, s);
     case MMT_EPI_BIAS_BF16: return pick2<MMT_EPI_BIAS_BF16>(tile, A, lda, B, ldb, C, ldc, M, N, K, e, nr, s);

@@ -3,6 +3,8 @@ import ctypes
 import json
 import os
 import re
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -57,11 +59,15 @@ def test_gemm_tile_policy_is_a_function_of_shape_and_live_rows():
   from >= 4 tiles per CU (wide) / >= 200 tiles of 128x128 (long K, narrow), 21: 256x256 from a chip's worth of such tiles, 2:
   the 4-wave dense N = 512 kernel -- as a function of (epilogue, M, N, K, packed, live rows): the live count the HOST passes
   (MmtBertBatch.live_rows_hint) decides, no constant tied to the benchmark generator's fill (VERDICT r05 item 4 / weak 8, 11);
-  without a hint a packed batch is priced at its allocated rows."""
+  without a hint a packed batch is priced at its allocated rows.  Nothing in the environment moves it: a fresh process with
+  the names of the removed policy switches set answers the same on every tuple asked here."""
   from mmt_amd import _lib
-  if any(k.startswith('MMT_TILE_') or k == 'MMT_LIVE_FRACTION' for k in os.environ):
-    pytest.skip('tile policy switches set in the environment')
-  f = ctypes.CDLL(_lib.LIB_PATH).mmt_gemm_select_tile
+  select = ctypes.CDLL(_lib.LIB_PATH).mmt_gemm_select_tile
+  asked = []
+
+  def f(*args):
+    asked.append(list(args))
+    return select(*args)
   E = _lib.EPI
   shapes = [('BIAS_BF16', 1536, 512, 0), ('BIAS_DROP_RES', 512, 512, 0), ('BIAS_GELU', 3072, 512, 0), ('BIAS_DROP_RES', 512, 3072, 0),
             ('DGELU', 3072, 512, 0), ('ADD_F32', 512, 3072, 0), ('BF16', 512, 512, 1), ('ADD_F32', 512, 1536, 0)]
@@ -83,6 +89,13 @@ def test_gemm_tile_policy_is_a_function_of_shape_and_live_rows():
   assert f(E['BIAS_DROP_RES'], 6976, 512, 3072, 1, 10 ** 6, 0, 0, 0) == f(E['BIAS_DROP_RES'], 6976, 512, 3072, 1, -5, 0, 0, 0) == 24
   assert f(E['BIAS_GELU'], 6976, 3072, 512, 1, 3639, 0, 0, 13) == 13 and f(E['BIAS_GELU'], 6976, 3072, 512, 0, 0, 0, 0, 1) == 1
   assert f(99, 1, 1, 1, 0, 0, 0, 0, 0) < 0
+  child = ('import ctypes, json, sys\n'
+           'f = ctypes.CDLL(sys.argv[1]).mmt_gemm_select_tile\n'
+           'print(json.dumps([f(*a) for a in json.loads(sys.argv[2])]))')
+  env = dict(os.environ, MMT_TILE_NARROW='13', MMT_TILE_PPN='5', MMT_LIVE_FRACTION='0.5')
+  out = subprocess.run([sys.executable, '-c', child, _lib.LIB_PATH, json.dumps(asked)], env=env, check=True,
+                       stdout=subprocess.PIPE, text=True).stdout
+  assert json.loads(out) == [select(*a) for a in asked]
 
 
 def test_product_path_refuses_cpu_tensors():

@@ -98,18 +98,15 @@ def test_gemm_nt_fused_epilogues(tile):
 
 
 # The product library holds the tiles the dispatcher selects on its own: 13 / 14 / 18 (gemm2.hip), 21 (gemm3.hip), 24 / 25
-# (gemm5.hip: 128x128 / 128x64).  The tiles that were measured and lost live in the LAB library (python -m mmt_amd.build --lab, loaded through
-# MMT_HIP_LIB=mmt_amd/lib/libmmt_hip_lab.so); their parity cases run when that library is the one under test.
-_LAB = 'lab' in os.path.basename(os.environ.get('MMT_HIP_LIB', '')) or 'instr' in os.path.basename(os.environ.get('MMT_HIP_LIB', ''))
+# (gemm5.hip: 128x128 / 128x64).  The tiles that were measured and lost are gone from the source.
 _PRODUCT_TILES = [13, 14, 18, 24, 25]
-_LAB_TILES = [3, 4, 5, 7, 10, 11, 12, 19, 22, 23]
 
 
-@pytest.mark.parametrize('tile', _PRODUCT_TILES + (_LAB_TILES if _LAB else []))
+@pytest.mark.parametrize('tile', _PRODUCT_TILES)
 @pytest.mark.parametrize('M,N,K', [(300, 256, 128), (777, 512, 192), (7168, 1536, 512), (3583, 512, 3072), (640, 512, 64)])
 def test_gemm_nt_wide_tiles(tile, M, N, K):
-  """gemm2.hip (128x128 / 128x64 tiles, 32x32x16 MFMA, LDS-staged epilogue; lab: 256x128 / 256x256 / ...) and gemm5.hip
-  (tile 24: persistent, wave-specialised 128x128): every epilogue."""
+  """gemm2.hip (128x128 / 128x64 tiles, 32x32x16 MFMA, LDS-staged epilogue) and gemm5.hip (tiles 24 / 25: persistent,
+  wave-specialised 128x128 / 128x64): every epilogue."""
   _wide_tile_case(tile, M, N, K)
 
 
@@ -143,26 +140,33 @@ def test_persistent_gemm_on_packed_rows(tile, M, N, K, live):
       _close('add_f32 vs fp32 reference', got[:live], ref + res[:live], 2e-3, 2e-4)
 
 
-def test_lab_tiles_are_not_in_the_product_library():
-  """A lab tile id asked of the product library is an argument error, not a silent fallback."""
-  if _LAB:
-    pytest.skip('lab library under test')
+def test_a_removed_tile_id_is_an_argument_error():
+  """A tile id that no kernel answers to (the removed lab tiles among them) is an argument error, not a silent fallback."""
   from mmt_amd import ops
   a = _rand((256, 64), seed=1, dtype=torch.bfloat16)
   b = _rand((128, 64), seed=2, dtype=torch.bfloat16)
   out = torch.zeros(256, 128, device=_dev(), dtype=torch.bfloat16)
-  for tile in (3, 16, 19, 23):
+  for tile in (3, 4, 5, 7, 10, 11, 12, 15, 16, 17, 19, 20, 22, 23):
     with pytest.raises(RuntimeError):
       ops.gemm_nt(a, b, out, 'BF16', tile=tile)
 
 
-@pytest.mark.skipif(not _LAB, reason='192-wide tiles: lab library only')
 @pytest.mark.parametrize('tile', [15, 16, 17])
 @pytest.mark.parametrize('M,N,K', [(300, 384, 128), (777, 576, 192), (3583, 3072, 512), (7168, 1536, 512)])
 def test_gemm_nt_192_wide_tiles(tile, M, N, K):
-  """gemm2.hip tiles with 192 output columns (256x192 / 128x192: N = 3072 and 1536 in ONE round of <= 256 tiles at
-  ~3600 live rows); the epilogue sweeps them as three 64-column blocks."""
-  _wide_tile_case(tile, M, N, K)
+  """The tiles with 192 output columns (256x192 / 128x192) are gone: on the shapes they served (N a multiple of 192), asking
+  for one is an argument error for every epilogue family, raised before any launch -- the output is not touched."""
+  from mmt_amd import ops
+  R = ops.pad_rows(M)
+  a = _rand((R, K), seed=21, dtype=torch.bfloat16)
+  b = _rand((N, K), 0.1, seed=22, dtype=torch.bfloat16)
+  bias, res = _rand((N,), seed=23), _rand((R, N), seed=24)
+  for epi, kw, dt in (('BF16', {}, torch.bfloat16), ('BIAS_BF16', dict(bias=bias), torch.bfloat16),
+                      ('BIAS_DROP_RES', dict(bias=bias, res=res), torch.float32), ('ADD_F32', dict(res=res), torch.float32)):
+    out = torch.full((R, N), 7.0, device=_dev(), dtype=dt)
+    with pytest.raises(RuntimeError):
+      ops.gemm_nt(a, b, out, epi, m=M, tile=tile, **kw)
+    assert bool((out == 7.0).all()), epi
 
 
 @pytest.mark.parametrize('M,N,K', [(300, 256, 64), (777, 512, 128), (640, 256, 192), (3583, 3072, 512), (7168, 1536, 512),
@@ -201,13 +205,12 @@ def _wide_tile_case(tile, M, N, K):
   _close('bf16', pre[:M], ref, 2e-2, 1e-2)
   aux = _rand((R, N), seed=25, dtype=torch.bfloat16)
   live = torch.tensor([M - 37], device=_dev(), dtype=torch.int32)
-  colsum = torch.zeros((M + 127) // 128, N, device=_dev(), dtype=torch.float32) if tile != 12 else None  # 64-row tiles: none
+  colsum = torch.zeros((M + 127) // 128, N, device=_dev(), dtype=torch.float32)
   ops.gemm_nt(a, b, pre, 'DGELU', m=M, aux=aux, colsum=colsum, n_rows_dev=live, tile=tile)
   x = aux[:M].float().requires_grad_(True)
   _gelu(x).sum().backward()
   _close('dgelu', pre[:M - 37], (ref * x.grad)[:M - 37], 3e-2, 1.5e-2)
-  if colsum is not None:
-    _close('dgelu.colsum (live rows only)', colsum.sum(0), pre[:M - 37].float().sum(0), 2e-2, 2e-4)
+  _close('dgelu.colsum (live rows only)', colsum.sum(0), pre[:M - 37].float().sum(0), 2e-2, 2e-4)
 
 
 @pytest.mark.parametrize('batch,M,N,K,trans', [(3, 6, 256, 768, False), (7, 32, 512, 512, False), (2, 300, 130, 6, True),

@@ -1,4 +1,4 @@
-"""Cycle budget of the FFN-sized GEMMs of the headline step, per phase.  Needs the lab build:
+"""Cycle budget of the FFN-sized GEMMs of the headline step, per phase.  Needs the instrumented build:
    python -m mmt_amd.build --instr
    MMT_HIP_LIB=mmt_amd/lib/libmmt_hip_instr.so python tools/gemm2_budget.py [rows]
 For each of the four shapes (FFN-up + GELU, its dGELU input gradient, FFN-down + dropout + residual, its input gradient)
@@ -102,13 +102,13 @@ def budget(name, live, dense, N, K, epi, tile=0, **kw):
 nums = [a for a in sys.argv[1:] if a.isdigit()]
 rows = int(nums[0]) if nums else 3639
 dense = 6976
-print('# gemm2 cycle budget, lab build (s_memtime ticks of wave 0; the ticks themselves inflate a loop by ~10-20 %)')
+print('# gemm2 cycle budget, instrumented build (s_memtime ticks of wave 0; the ticks themselves inflate a loop by ~10-20 %)')
 budget('FFN-up   + bias + erf-GELU (2 outputs) ', rows, dense, 3072, 512, 'BIAS_GELU')
 budget('dGELU input gradient (reads pre-act)   ', rows, dense, 3072, 512, 'DGELU')
 budget('FFN-down + bias + dropout + residual   ', rows, dense, 512, 3072, 'BIAS_DROP_RES')
 budget('FFN-up input gradient + residual grad  ', rows, dense, 512, 3072, 'ADD_F32')
 if '--alt' in sys.argv:
-  for t in (11, 3, 15, 16):
+  for t in (14, 24):
     budget('FFN-up on tile %d' % t, rows, dense, 3072, 512, 'BIAS_GELU', tile=t)
   for t in (13, 18):
     budget('FFN-down on tile %d' % t, rows, dense, 512, 3072, 'BIAS_DROP_RES', tile=t)

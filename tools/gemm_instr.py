@@ -1,4 +1,4 @@
-"""Where do the cycles of gemm2's K-loop go?  Needs the lab build:  python -m mmt_amd.build --instr
+"""Where do the cycles of gemm2's K-loop go?  Needs the instrumented build:  python -m mmt_amd.build --instr
    MMT_HIP_LIB=mmt_amd/lib/libmmt_hip_instr.so python tools/gemm_instr.py
 Per block, wave 0 accumulates s_memtime deltas for: counted-vmcnt wait, barrier, LDS-DMA issue, LDS-read+MFMA."""
 import os
@@ -32,7 +32,7 @@ def run(rows, N, K, tile, epi='F32'):
         (rows, N, K, tile, d.shape[0], kt, m[0] / kt, m[1] / kt, m[2] / kt, m[3] / kt, m[4], m[5], span))
 
 
-tiles = [int(t) for t in sys.argv[1:]] or [5, 7, 3, 11, 12, 13, 18]
+tiles = [int(t) for t in sys.argv[1:]] or [13, 14, 18]
 for rows in (3596, 6976):
   for (N, K) in ((512, 3072), (512, 512), (3072, 512)):
     for tile in tiles:
