@@ -465,7 +465,7 @@ int mmt_sims_eval(const float* txt, const float* vid, const float* tw, const flo
 int mmt_retrieval_ranks(const float* sims, const uint8_t* qmask, int NQ, int NV, float* t2v_rank, float* v2t_rank,
                         float* scratch, void* stream);
 
-/* ---- top-k retrieval (search.hip, search_bf16.hip, fold in retrieval.hip) --------------------------------------
+/* ---- top-k retrieval (search.hip, search_bf16.hip, search_rank.hip, fold in retrieval.hip) --------------------------------------
  * score(q, g) = sum_m qw[q][m] gw[g][m] <Q_m[q], G_m[g]> / sum_m qw[q][m] gw[g][m] (0 -> 1e-5), the 'indep' similarity
  * of model/model.py:789-837.  Per query the min(k, NV) best (score, gallery index) pairs, score descending, equal scores
  * by ascending index (a stable argsort; the reference's np.argsort leaves the order of exact ties unspecified).
@@ -501,6 +501,24 @@ int mmt_search_fold_split_bf16(const float* x, const float* w, int N, int M, int
                                void* stream);
 int mmt_search_topk_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
                          int NQ, int NV, int M, int d, int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
+/* Exact rank counts over the same scan (search_rank.hip), replacing the ranking of a materialised sims matrix in
+ * model/metric.py:90-121 (t2v_metrics) and 153-243 (v2t_metrics): for every query q and each of its T targets
+ * (gallery items, int64 [NQ][T], 1 <= T <= 32)
+ *   greater[q][t] = #{g < NV : score(q, g) > score(q, targets[q][t])},  equal[q][t] = #{g < NV : score(q, g) == ...}
+ * as int32 [NQ][T]; the reference's tie-averaged 0-based rank is greater + (equal - 1) / 2.  The threshold is the very
+ * value the scan computes for the target, so equal >= 1 for a target with a non-NaN score.  Plain float compares
+ * (-0 == +0, NaN counts for nothing).  A target outside 0 .. NV - 1 (-1 = none) is checked on the device, never
+ * dereferenced, and gets 0 / 0.  Deterministic (integer sums, no atomics).  Never forms the NQ x NV matrix.
+ * mmt_rank_workspace_ints: int32 workspace, NQ * T * (1 + 2 * ceil(NV / chunk)) with the chunk of mmt_search_topk;
+ *   MMT_ERR_ARG if T or a size is out of range.
+ * mmt_search_rank / mmt_search_rank_bf16: operands, gates (MMT_ERR_ARG, MMT_ERR_ALIGN) and score definition as
+ *   mmt_search_topk / mmt_search_topk_bf16. */
+int64_t mmt_rank_workspace_ints(int NQ, int NV, int T);
+int mmt_search_rank(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                    const int64_t* targets, int T, int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
+int mmt_search_rank_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
+                         int NQ, int NV, int M, int d, const int64_t* targets, int T, int32_t* ws, int32_t* greater,
+                         int32_t* equal, void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

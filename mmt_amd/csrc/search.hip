@@ -16,14 +16,9 @@
 // Order: score descending, ties by ascending gallery index (= a stable argsort of -score).  A (score, index) pair is one
 // uint64 key -- order-preserving score bits above, ~index below -- so "better" is one unsigned compare and every key is
 // distinct; 0 is "no candidate".  No atomics: every output slot has exactly one writer, results are bit-reproducible.
-// The key, the running top-k and the tile epilogue live in search_topk.h, shared with the bf16-gallery kernel
-// (search_bf16.hip).
+// The key and the running top-k live in search_topk.h, shared with the bf16-gallery kernel (search_bf16.hip); the K loop
+// and the score epilogue in search_scan.h, shared with the rank-count kernels as well (search_rank.hip).
 #include "search_topk.h"
-
-#define TK_BK 32                 // contraction slab
-#define TK_LD (TK_BK + 4)        // slab row pitch (floats): conflict-free ds_read_b128 across 16 consecutive rows
-#define TK_SLAB_BYTES ((TK_Q + TK_G) * TK_LD * 4)
-#define TK_UNION_BYTES (TK_TILE_BYTES > TK_SLAB_BYTES ? TK_TILE_BYTES : TK_SLAB_BYTES)
 
 struct TkArgs {
   const float* q;       // fused: Q' [NQ][K]        select: sims (row stride ld)
@@ -63,9 +58,7 @@ __global__ __launch_bounds__(256) void topk_chunk_kernel(TkArgs a) {
     }
     return;
   } else {
-    float* sA = (float*)smem;                                  // [TK_Q][TK_LD]   slab of Q'
-    float* sB = sA + TK_Q * TK_LD;                             // [TK_G][TK_LD]   slab of G'
-    float* sS = (float*)smem;                                  // [TK_Q][TK_SLD]  scores (after the K loop)
+    float* sS = (float*)smem;                                  // [TK_Q][TK_SLD]  scores (after the K loop: tk_scan_f32)
     float* sQw = (float*)(smem + TK_UNION_BYTES);              // [TK_Q][MMT_MAX_EXPERTS]
     int* sN = (int*)(smem + TK_UNION_BYTES + TK_QW_BYTES);     // [TK_Q] candidates held
     uint64_t* sT = (uint64_t*)(sN + TK_Q);                     // [TK_Q] thresholds
@@ -73,53 +66,13 @@ __global__ __launch_bounds__(256) void topk_chunk_kernel(TkArgs a) {
     const int l31 = lane & 31, h = lane >> 5, wq = wave >> 1, wg = wave & 1;
     const int K = a.K, M = a.M;
     if (tid < TK_Q) { sN[tid] = 0; sT[tid] = 0; }
-    for (int i = tid; i < TK_Q * MMT_MAX_EXPERTS; i += 256) {
-      const int r = i / MMT_MAX_EXPERTS, m = i % MMT_MAX_EXPERTS;
-      sQw[i] = (q0 + r < a.NQ && m < M) ? a.qw[(int64_t)(q0 + r) * M + m] : 0.f;
-    }
+    tk_load_qw(sQw, a.qw, a.NQ, M, q0, tid);
     for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
+      const auto grow = [=](int r) { return g0 + r < g_end ? g0 + r : -1; };
       f32x16 acc[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-      // staging: Q' slab = 64 rows x 8 f32x4 (2 per thread), G' slab = 128 rows x 8 f32x4 (4 per thread)
-      f32x4 ra[2], rb[4];
-      auto load = [&](int kb) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 4;
-          ra[j] = (q0 + r < a.NQ && c < K) ? *(const f32x4*)(a.q + (int64_t)(q0 + r) * K + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 4;
-          rb[j] = (g0 + r < g_end && c < K) ? *(const f32x4*)(a.g + (int64_t)(g0 + r) * K + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-      };
-      load(0);
-      for (int kb = 0; kb < K; kb += TK_BK) {
-        __syncthreads();  // previous slab (or the previous tile's scores) consumed
-#pragma unroll
-        for (int j = 0; j < 2; ++j) { const int i = tid + 256 * j; *(f32x4*)(sA + (i >> 3) * TK_LD + (i & 7) * 4) = ra[j]; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const int i = tid + 256 * j; *(f32x4*)(sB + (i >> 3) * TK_LD + (i & 7) * 4) = rb[j]; }
-        __syncthreads();
-        if (kb + TK_BK < K) load(kb + TK_BK);
-        // 8 contraction values per step = 4 MFMAs per accumulator; lane half h feeds k = kk + 4h + u to MFMA u
-#pragma unroll
-        for (int kk = 0; kk < TK_BK; kk += 8) {
-          const f32x4 av = *(const f32x4*)(sA + (wq * 32 + l31) * TK_LD + kk + 4 * h);
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            const f32x4 bv = *(const f32x4*)(sB + (wg * 64 + t * 32 + l31) * TK_LD + kk + 4 * h);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc[t], 0, 0, 0);
-          }
-        }
-      }
+      tk_scan_f32(acc, smem, a.q, a.g, a.NQ, K, q0, grow, tid, wq, wg, l31, h);
       __syncthreads();  // the slabs become the score tile
-      tk_tile_scores(acc, sS, sQw, a.gw, M, g0, g_end, wq, wg, l31, h);
+      tk_tile_scores(acc, sS, sQw, a.gw, M, grow, wq, wg, l31, h);
       __syncthreads();
       tk_tile_select(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane);
     }

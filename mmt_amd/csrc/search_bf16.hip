@@ -21,11 +21,6 @@
 //                             Rows past NQ / NV and the K tail are zero-filled in registers, never read.
 #include "search_topk.h"
 
-#define TKB_BK 64                 // contraction slab (bf16 elements): 128 bytes of a folded row
-#define TKB_LD (TKB_BK + 8)       // slab row pitch (bf16): 36 dwords, the fp32 kernel's conflict-free pitch
-#define TKB_SLAB_BYTES ((2 * TK_Q + TK_G) * TKB_LD * 2)
-#define TKB_UNION_BYTES (TK_TILE_BYTES > TKB_SLAB_BYTES ? TK_TILE_BYTES : TKB_SLAB_BYTES)
-
 struct TkBf16Args {
   const bf16_t* q_hi;   // [NQ][K]
   const bf16_t* q_lo;   // [NQ][K]
@@ -70,10 +65,7 @@ __global__ __launch_bounds__(256) void topk_chunk_bf16_kernel(TkBf16Args a) {
   uint64_t* ws = a.ws + chunk * (int64_t)a.k;
   const int64_t ws_row = (int64_t)a.n_chunks * a.k;
 
-  bf16_t* sAh = (bf16_t*)smem;                                // [TK_Q][TKB_LD]  slab of hi(Q')
-  bf16_t* sAl = sAh + TK_Q * TKB_LD;                          // [TK_Q][TKB_LD]  slab of lo(Q')
-  bf16_t* sB = sAl + TK_Q * TKB_LD;                           // [TK_G][TKB_LD]  slab of the stored gallery
-  float* sS = (float*)smem;                                   // [TK_Q][TK_SLD]  scores (after the K loop)
+  float* sS = (float*)smem;                                   // [TK_Q][TK_SLD]  scores (after the K loop: tk_scan_bf16)
   float* sQw = (float*)(smem + TKB_UNION_BYTES);              // [TK_Q][MMT_MAX_EXPERTS]
   int* sN = (int*)(smem + TKB_UNION_BYTES + TK_QW_BYTES);     // [TK_Q] candidates held
   uint64_t* sT = (uint64_t*)(sN + TK_Q);                      // [TK_Q] thresholds
@@ -81,63 +73,13 @@ __global__ __launch_bounds__(256) void topk_chunk_bf16_kernel(TkBf16Args a) {
   const int l31 = lane & 31, h = lane >> 5, wq = wave >> 1, wg = wave & 1;
   const int K = a.K, M = a.M;
   if (tid < TK_Q) { sN[tid] = 0; sT[tid] = 0; }
-  for (int i = tid; i < TK_Q * MMT_MAX_EXPERTS; i += 256) {
-    const int r = i / MMT_MAX_EXPERTS, m = i % MMT_MAX_EXPERTS;
-    sQw[i] = (q0 + r < a.NQ && m < M) ? a.qw[(int64_t)(q0 + r) * M + m] : 0.f;
-  }
-  const u32x4 zero = {0u, 0u, 0u, 0u};
+  tk_load_qw(sQw, a.qw, a.NQ, M, q0, tid);
   for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
+    const auto grow = [=](int r) { return g0 + r < g_end ? g0 + r : -1; };
     f32x16 acc[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    // staging, 16 bytes = 8 bf16 per load: hi and lo slabs = 64 rows x 8 (2 per thread each), gallery slab = 128 rows x 8
-    // (4 per thread).  K % 8 == 0, so a load is inside the row or past its end as a whole.
-    u32x4 rh[2], rl[2], rb[4];
-    auto load = [&](int kb) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 8;
-        const bool in = q0 + r < a.NQ && c < K;
-        const int64_t off = (int64_t)(q0 + r) * K + c;
-        rh[j] = in ? *(const u32x4*)(a.q_hi + off) : zero;
-        rl[j] = in ? *(const u32x4*)(a.q_lo + off) : zero;
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 8;
-        rb[j] = (g0 + r < g_end && c < K) ? *(const u32x4*)(a.g + (int64_t)(g0 + r) * K + c) : zero;
-      }
-    };
-    load(0);
-    for (int kb = 0; kb < K; kb += TKB_BK) {
-      __syncthreads();  // previous slab (or the previous tile's scores) consumed
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int i = tid + 256 * j, o = (i >> 3) * TKB_LD + (i & 7) * 8;
-        *(u32x4*)(sAh + o) = rh[j];
-        *(u32x4*)(sAl + o) = rl[j];
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { const int i = tid + 256 * j; *(u32x4*)(sB + (i >> 3) * TKB_LD + (i & 7) * 8) = rb[j]; }
-      __syncthreads();
-      if (kb + TKB_BK < K) load(kb + TKB_BK);
-      // 16 contraction values per MFMA; lane half h holds k = kk + 8h .. + 7 of its row (A) / column (B)
-#pragma unroll
-      for (int kk = 0; kk < TKB_BK; kk += 16) {
-        const int ao = (wq * 32 + l31) * TKB_LD + kk + 8 * h;
-        const bf16x8_t ah = *(const bf16x8_t*)(sAh + ao), al = *(const bf16x8_t*)(sAl + ao);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const bf16x8_t bv = *(const bf16x8_t*)(sB + (wg * 64 + t * 32 + l31) * TKB_LD + kk + 8 * h);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bv, acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bv, acc[t], 0, 0, 0);
-        }
-      }
-    }
+    tk_scan_bf16(acc, smem, a.q_hi, a.q_lo, a.g, a.NQ, K, q0, grow, tid, wq, wg, l31, h);
     __syncthreads();  // the slabs become the score tile
-    tk_tile_scores(acc, sS, sQw, a.gw, M, g0, g_end, wq, wg, l31, h);
+    tk_tile_scores(acc, sS, sQw, a.gw, M, grow, wq, wg, l31, h);
     __syncthreads();
     tk_tile_select(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane);
   }

@@ -1,0 +1,184 @@
+// The scoring tile of the gallery scans, shared by the top-k kernels (search.hip, search_bf16.hip: a running top-k per
+// query) and the rank-count kernels (search_rank.hip: a counter per query and target): block shape, the two K loops (fp32
+// gallery on v_mfma_f32_32x32x2_f32, bf16 gallery on v_mfma_f32_32x32x16_bf16), the gated-denominator epilogue and the
+// chunk rule.  One copy, so every kernel that scores a (query, item) pair computes the same bits for it.
+//
+// Which gallery row a tile row / column holds is a functor `grow(r)`, r in 0 .. TK_G - 1 -> gallery row, or -1 for "none"
+// (zero-filled in registers, never read): g0 + r for a scan, a table lookup for the rank kernels' threshold pass.
+#pragma once
+#include "mmt_common.h"
+#include "../../include/mmt_hip.h"
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+#define TK_Q 64                  // query rows per block (4 waves: 2 x 2 of 32 rows x 64 columns)
+#define TK_G 128                 // gallery columns per tile
+#define TK_SLD (TK_G + 4)        // score tile row pitch
+#define TK_CHUNK 4096            // gallery columns per block at full occupancy
+#define TK_FILL 512              // blocks wanted per launch before the chunk is allowed to shrink (2 per CU)
+#define TK_TILE_BYTES (TK_Q * TK_SLD * 4)
+#define TK_QW_BYTES (TK_Q * MMT_MAX_EXPERTS * 4)
+
+#define TK_BK 32                 // fp32 contraction slab
+#define TK_LD (TK_BK + 4)        // slab row pitch (floats): conflict-free ds_read_b128 across 16 consecutive rows
+#define TK_SLAB_BYTES ((TK_Q + TK_G) * TK_LD * 4)
+#define TK_UNION_BYTES (TK_TILE_BYTES > TK_SLAB_BYTES ? TK_TILE_BYTES : TK_SLAB_BYTES)
+
+#define TKB_BK 64                 // bf16 contraction slab (bf16 elements): 128 bytes of a folded row
+#define TKB_LD (TKB_BK + 8)       // slab row pitch (bf16): 36 dwords, the fp32 kernel's conflict-free pitch
+#define TKB_SLAB_BYTES ((2 * TK_Q + TK_G) * TKB_LD * 2)
+#define TKB_UNION_BYTES (TK_TILE_BYTES > TKB_SLAB_BYTES ? TK_TILE_BYTES : TKB_SLAB_BYTES)
+
+// Query weights of the block's rows -> sQw [TK_Q][MMT_MAX_EXPERTS], zero past NQ / M.
+__device__ __forceinline__ void tk_load_qw(float* sQw, const float* qw, int NQ, int M, int q0, int tid) {
+  for (int i = tid; i < TK_Q * MMT_MAX_EXPERTS; i += 256) {
+    const int r = i / MMT_MAX_EXPERTS, m = i % MMT_MAX_EXPERTS;
+    sQw[i] = (q0 + r < NQ && m < M) ? qw[(int64_t)(q0 + r) * M + m] : 0.f;
+  }
+}
+
+// fp32 K loop of one 64 x 128 tile: acc = Q'[q0 .. q0 + 63] . G'[grow(.)]^T.  The K dimension streams through LDS
+// (smem: TK_SLAB_BYTES) in 32-wide slabs, register-staged: the next slab's global loads are in flight during the
+// current slab's MFMAs.  Opens with a barrier (the previous tile's scores, which share smem, are consumed) and leaves
+// the last slab's reads unfenced: the caller syncs before it reuses smem.
+template <class GRow>
+__device__ __forceinline__ void tk_scan_f32(f32x16 (&acc)[2], unsigned char* smem, const float* q, const float* g, int NQ,
+                                            int K, int q0, GRow grow, int tid, int wq, int wg, int l31, int h) {
+  float* sA = (float*)smem;        // [TK_Q][TK_LD]   slab of Q'
+  float* sB = sA + TK_Q * TK_LD;   // [TK_G][TK_LD]   slab of G'
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  // staging: Q' slab = 64 rows x 8 f32x4 (2 per thread), G' slab = 128 rows x 8 f32x4 (4 per thread)
+  int gr[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) gr[j] = grow((tid + 256 * j) >> 3);
+  f32x4 ra[2], rb[4];
+  auto load = [&](int kb) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 4;
+      ra[j] = (q0 + r < NQ && c < K) ? *(const f32x4*)(q + (int64_t)(q0 + r) * K + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = kb + ((tid + 256 * j) & 7) * 4;
+      rb[j] = (gr[j] >= 0 && c < K) ? *(const f32x4*)(g + (int64_t)gr[j] * K + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  load(0);
+  for (int kb = 0; kb < K; kb += TK_BK) {
+    __syncthreads();  // previous slab (or the previous tile's scores) consumed
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { const int i = tid + 256 * j; *(f32x4*)(sA + (i >> 3) * TK_LD + (i & 7) * 4) = ra[j]; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const int i = tid + 256 * j; *(f32x4*)(sB + (i >> 3) * TK_LD + (i & 7) * 4) = rb[j]; }
+    __syncthreads();
+    if (kb + TK_BK < K) load(kb + TK_BK);
+    // 8 contraction values per step = 4 MFMAs per accumulator; lane half h feeds k = kk + 4h + u to MFMA u
+#pragma unroll
+    for (int kk = 0; kk < TK_BK; kk += 8) {
+      const f32x4 av = *(const f32x4*)(sA + (wq * 32 + l31) * TK_LD + kk + 4 * h);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const f32x4 bv = *(const f32x4*)(sB + (wg * 64 + t * 32 + l31) * TK_LD + kk + 4 * h);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc[t], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// bf16-gallery K loop of one tile (smem: TKB_SLAB_BYTES): per 64-wide slab the block stages hi(Q'), lo(Q') (64 rows each)
+// and the gallery (128 rows); a wave reads each gallery fragment ONCE and feeds it to the hi and the lo MFMA.  Barriers as
+// tk_scan_f32.  K % 8 == 0, so a 16-byte load is inside the row or past its end as a whole.
+template <class GRow>
+__device__ __forceinline__ void tk_scan_bf16(f32x16 (&acc)[2], unsigned char* smem, const bf16_t* q_hi, const bf16_t* q_lo,
+                                             const bf16_t* g, int NQ, int K, int q0, GRow grow, int tid, int wq, int wg,
+                                             int l31, int h) {
+  bf16_t* sAh = (bf16_t*)smem;          // [TK_Q][TKB_LD]  slab of hi(Q')
+  bf16_t* sAl = sAh + TK_Q * TKB_LD;    // [TK_Q][TKB_LD]  slab of lo(Q')
+  bf16_t* sB = sAl + TK_Q * TKB_LD;     // [TK_G][TKB_LD]  slab of the stored gallery
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  // staging, 16 bytes = 8 bf16 per load: hi and lo slabs = 64 rows x 8 (2 per thread each), gallery slab = 128 rows x 8
+  // (4 per thread)
+  int gr[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) gr[j] = grow((tid + 256 * j) >> 3);
+  u32x4 rh[2], rl[2], rb[4];
+  auto load = [&](int kb) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 8;
+      const bool in = q0 + r < NQ && c < K;
+      const int64_t off = (int64_t)(q0 + r) * K + c;
+      rh[j] = in ? *(const u32x4*)(q_hi + off) : zero;
+      rl[j] = in ? *(const u32x4*)(q_lo + off) : zero;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = kb + ((tid + 256 * j) & 7) * 8;
+      rb[j] = (gr[j] >= 0 && c < K) ? *(const u32x4*)(g + (int64_t)gr[j] * K + c) : zero;
+    }
+  };
+  load(0);
+  for (int kb = 0; kb < K; kb += TKB_BK) {
+    __syncthreads();  // previous slab (or the previous tile's scores) consumed
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int i = tid + 256 * j, o = (i >> 3) * TKB_LD + (i & 7) * 8;
+      *(u32x4*)(sAh + o) = rh[j];
+      *(u32x4*)(sAl + o) = rl[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const int i = tid + 256 * j; *(u32x4*)(sB + (i >> 3) * TKB_LD + (i & 7) * 8) = rb[j]; }
+    __syncthreads();
+    if (kb + TKB_BK < K) load(kb + TKB_BK);
+    // 16 contraction values per MFMA; lane half h holds k = kk + 8h .. + 7 of its row (A) / column (B)
+#pragma unroll
+    for (int kk = 0; kk < TKB_BK; kk += 16) {
+      const int ao = (wq * 32 + l31) * TKB_LD + kk + 8 * h;
+      const bf16x8_t ah = *(const bf16x8_t*)(sAh + ao), al = *(const bf16x8_t*)(sAl + ao);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const bf16x8_t bv = *(const bf16x8_t*)(sB + (wg * 64 + t * 32 + l31) * TKB_LD + kk + 8 * h);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bv, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bv, acc[t], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// Epilogue of one 64 x 128 tile held as 32x32 MFMA accumulators (lane: column wg*64 + t*32 + l31, rows
+// wq*32 + (r&3) + 8*(r>>2) + 4h -- the layout of v_mfma_f32_32x32x2_f32 and v_mfma_f32_32x32x16_bf16 alike): divides by
+// the gated denominator and leaves the scores in sS [TK_Q][TK_SLD].
+template <class GRow>
+__device__ __forceinline__ void tk_tile_scores(const f32x16 (&acc)[2], float* sS, const float* sQw, const float* gw, int M,
+                                               GRow grow, int wq, int wg, int l31, int h) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int col = wg * 64 + t * 32 + l31, g = grow(col);
+    float den[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) den[r] = 0.f;
+    for (int m = 0; m < M; ++m) {
+      const float gwm = g >= 0 ? gw[(int64_t)g * M + m] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) den[r] += sQw[(wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * MMT_MAX_EXPERTS + m] * gwm;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      sS[row * TK_SLD + col] = acc[t][r] / (den[r] == 0.f ? 1e-5f : den[r]);
+    }
+  }
+}
+
+// Host side (search.hip): gallery columns per block, TK_CHUNK halved (down to one tile) while the launch would not fill
+// the chip.
+int tk_chunk(int NQ, int NV);

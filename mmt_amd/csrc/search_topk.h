@@ -1,20 +1,10 @@
 // Selection machinery of the top-k search, shared by the fp32 kernels (search.hip) and the bf16-gallery kernel
-// (search_bf16.hip): the (score, index) key, the per-row running top-k in LDS, the tile epilogue and the chunk rule.
-// See search.hip for the algorithm.
+// (search_bf16.hip): the (score, index) key and the per-row running top-k in LDS.  The scoring tile itself (K loops, score
+// epilogue, chunk rule) is search_scan.h.  See search.hip for the algorithm.
 #pragma once
-#include "mmt_common.h"
-#include "../../include/mmt_hip.h"
+#include "search_scan.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-#define TK_Q 64                  // query rows per block (4 waves: 2 x 2 of 32 rows x 64 columns)
-#define TK_G 128                 // gallery columns per tile
-#define TK_SLD (TK_G + 4)        // score tile row pitch
 #define TK_MAXK 128
-#define TK_CHUNK 4096            // gallery columns per block at full occupancy
-#define TK_FILL 512              // blocks wanted per launch before the chunk is allowed to shrink (2 per CU)
-#define TK_TILE_BYTES (TK_Q * TK_SLD * 4)
-#define TK_QW_BYTES (TK_Q * MMT_MAX_EXPERTS * 4)
 
 __device__ __forceinline__ uint64_t tk_key(float s, int idx) {
   unsigned u = __float_as_uint(s);
@@ -72,30 +62,6 @@ __device__ __forceinline__ void tk_flush(uint64_t* c, int n, int k, int lane, ui
   for (int j = lane; j < k; j += 64) dst[j] = j < have ? c[j] : 0ull;
 }
 
-// Epilogue of one 64 x 128 tile held as 32x32 MFMA accumulators (lane: column wg*64 + t*32 + l31, rows
-// wq*32 + (r&3) + 8*(r>>2) + 4h -- the layout of v_mfma_f32_32x32x2_f32 and v_mfma_f32_32x32x16_bf16 alike): divides by
-// the gated denominator and leaves the scores in sS [TK_Q][TK_SLD].
-__device__ __forceinline__ void tk_tile_scores(const f32x16 (&acc)[2], float* sS, const float* sQw, const float* gw, int M,
-                                               int g0, int g_end, int wq, int wg, int l31, int h) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int col = wg * 64 + t * 32 + l31, g = g0 + col;
-    float den[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) den[r] = 0.f;
-    for (int m = 0; m < M; ++m) {
-      const float gwm = g < g_end ? gw[(int64_t)g * M + m] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) den[r] += sQw[(wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * MMT_MAX_EXPERTS + m] * gwm;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      sS[row * TK_SLD + col] = acc[t][r] / (den[r] == 0.f ? 1e-5f : den[r]);
-    }
-  }
-}
-
 // Selection over the score tile: wave w owns rows 16w .. 16w + 15; columns in increasing index order.
 __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, int* sN, uint64_t* sT, int k, int rows_live,
                                                int g0, int g_end, int wave, int lane) {
@@ -114,8 +80,7 @@ __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, in
   }
 }
 
-// Host side (search.hip): the chunk rule, the argument gate and the merge launch, shared by the fp32 and bf16 paths.
-int tk_chunk(int NQ, int NV);
+// Host side (search.hip): the argument gate and the merge launch, shared by the fp32 and bf16 paths.
 bool tk_args_ok(int NQ, int NV, int k);
 size_t tk_state_lds(int k);  // LDS behind the slab / score-tile union: query weights, counts, thresholds, candidates
 int tk_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, float* scores, int64_t* index,

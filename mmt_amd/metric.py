@@ -5,6 +5,8 @@ result keys (model/metric.py:26-150, 153-243, 246-258) but rank on the device: `
 never leaves HBM -- only the n rank values are copied to the host) or a numpy array (uploaded once).
 `retrieval_metrics(...)` goes one step further and also builds the N_text x N_video similarity on the device from
 the gathered embeddings (the reference does both on the CPU: trainer/trainer.py:396-447).  SURVEY.md section 8f.1.
+`retrieval_metrics_indexed(...)` gives the same metrics from exact rank counts over a search.VideoIndex, without the
+matrix: for eval sets whose N_text x N_video similarity does not fit.
 """
 import numpy as np
 import torch
@@ -95,6 +97,49 @@ def retrieval_metrics(vid_embds, text_embds, vid_weights, text_weights, query_ma
   """Embeddings of the whole eval set -> {'t2v_metrics': {...}, 'v2t_metrics': {...}} without an n^2 host copy."""
   sims = eval_similarity(vid_embds, text_embds, vid_weights, text_weights)
   return {'t2v_metrics': t2v_metrics(sims, query_masks), 'v2t_metrics': v2t_metrics(sims, query_masks)}
+
+
+def v2t_targets(query_masks, num_videos, captions_per_video):
+  """query_masks (None = every caption real; else anything of num_videos * captions_per_video entries, nonzero = real)
+  -> (valid bool [B*C], targets int64 [B, C]): targets[b, c] is the position of caption (b, c) in the gallery of the real
+  captions only (rows b*C + c with valid set, in order), -1 where it is masked.  Pure numpy: the renumbering behind
+  retrieval_metrics_indexed's video-to-text half."""
+  n = num_videos * captions_per_video
+  if query_masks is None:
+    valid = np.ones(n, dtype=bool)
+  else:
+    qm = np.asarray(query_masks.cpu() if torch.is_tensor(query_masks) else query_masks).reshape(-1)
+    if qm.size != n:
+      raise ValueError('query_masks has %d entries, %d videos x %d captions expected' % (qm.size, num_videos, captions_per_video))
+    valid = qm != 0
+  targets = np.where(valid, np.cumsum(valid) - 1, -1).astype(np.int64)
+  return valid, targets.reshape(num_videos, captions_per_video)
+
+
+def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, query_masks=None, dtype=torch.float32):
+  """`retrieval_metrics` (same arguments, same result dict and keys) without the N_text x N_video matrix: the rank of every
+  ground truth comes from search.VideoIndex.ranks, so no buffer grows with N_text * N_video.  t2v: an index of the videos
+  queried with the real captions, the target of caption row b*C + c being video b.  v2t: an index of the real captions
+  queried with the videos, each video's targets its own captions (`v2t_targets`), the best of their ranks kept (+inf for a
+  video without a real caption, as mmt_retrieval_ranks).  dtype: the index storage, torch.float32 or torch.bfloat16."""
+  from .search import VideoIndex
+  b, m, d = vid_embds.shape
+  c = text_embds.shape[2]
+  valid, targets = v2t_targets(query_masks, b, c)
+  if not valid.any():
+    raise ValueError('retrieval_metrics_indexed: query_masks leaves no caption to rank')
+  vid = _as_cuda_f32(vid_embds)
+  txt4 = _as_cuda_f32(text_embds)
+  vw = _as_cuda_f32(vid_weights).reshape(b, m).contiguous()
+  rows = torch.from_numpy(np.flatnonzero(valid)).to(vid.device)
+  txt = txt4.permute(0, 2, 1, 3).reshape(b * c, m, d)[rows].contiguous()      # the real captions, rows b*C + c in order
+  tw = _as_cuda_f32(text_weights).reshape(b * c, m)[rows].contiguous()
+  cols = VideoIndex(vid, vw, dtype=dtype).ranks(txt, tw, rows // c).cpu().numpy()
+  out = {'t2v_metrics': dict(cols2metrics(cols, cols.size), cols=cols)}
+  ranks = VideoIndex(txt, tw, dtype=dtype).ranks(vid, vw, torch.from_numpy(targets).to(vid.device))
+  cols = ranks.min(dim=1).values.cpu().numpy()
+  out['v2t_metrics'] = dict(cols2metrics(cols, cols.size), cols=cols)
+  return out
 
 
 def compress_predictions(query_masks, sims, topk=10):

@@ -21,6 +21,16 @@ are NOT rounded to 8 bits: score(q, g) = <fold_fp32(Q, qw)[q], dequant(stored[g]
 matrix cores with the query split into hi = bf16(qf) and lo = bf16(qf - hi) (mmt_search_topk_bf16; within 1e-5 of the
 fp64 value of that definition).  Against the float32 index a score moves by at most
 2^-8 * sum_m qw gw <|Q_m|, |G_m|> / sum_m qw gw, i.e. 2^-8 for unit-norm rows.
+
+    greater, equal = index.rank_counts(embds, weights, targets)   # int32, shape of targets ([NQ] or [NQ, T], int64)
+    ranks = index.ranks(embds, weights, targets)                  # float64: greater + (equal - 1) / 2
+
+The other half of evaluation (R@k, MedR, MeanR: model/metric.py:90-121, 153-243) needs the exact rank of each query's
+ground truth wherever it falls: for every target item, how many of the index's items score above it and how many score
+equal to it -- the same scan with a counter per (query, target) in place of the top-k list (mmt_search_rank), so again
+no N_query x N_video matrix.  The target's own score is taken from the same scoring tile, bit for bit, so it always
+counts itself (equal >= 1) and `ranks` is the reference's tie-averaged 0-based rank; a target of -1 means "none" and
+gives 0 / 0 and rank +inf.  metric.retrieval_metrics_indexed builds the t2v / v2t metrics on it.
 """
 import torch
 
@@ -28,6 +38,7 @@ from . import _lib, ops
 from ._lib import check
 
 MAX_K = 128
+MAX_T = 32  # targets per query and launch of the rank kernels; wider target lists are sliced
 _BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 bytes per element either way) + chunk lists
 _DTYPES = {torch.float32: 4, torch.bfloat16: 8}  # storage dtype -> multiple d must have (16-byte folded rows)
 
@@ -180,3 +191,73 @@ class VideoIndex:
           check(L.mmt_search_topk(ops._p(qf), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights), *out),
                 'mmt_search_topk')
     return scores, indices
+
+  def _targets(self, targets):
+    """Type, device and rank of `targets`: all that can be said about them before the queries are known."""
+    if not torch.is_tensor(targets) or targets.dtype != torch.int64:
+      raise ValueError('ranks: targets must be an int64 tensor, got %s' % (
+          targets.dtype if torch.is_tensor(targets) else type(targets).__name__))
+    if targets.device != self.device:
+      raise ValueError('ranks: targets must be on the index device %s, got %s' % (self.device, targets.device))
+    if targets.dim() not in (1, 2) or targets.dim() == 2 and targets.shape[1] < 1:
+      raise ValueError('ranks: targets [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(targets.shape),))
+
+  def rank_counts(self, embds, weights, targets):
+    """Queries as for `search`; targets [NQ] or [NQ, T] int64 on the index device, values -1 .. num_items - 1 ->
+    (greater, equal), int32 of targets' shape: how many of the num_items stored items score above / exactly equal to item
+    targets[q, t] for query q (the item itself is one of the equal ones); 0 / 0 where the target is -1.  The range of the
+    targets is checked here (one small reduction and a host sync); nothing is scored before it passes."""
+    if self.num_items == 0:
+      raise ValueError('ranks: the index holds no items')
+    self._targets(targets)
+    q, qw = self._queries(embds, weights)
+    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    if targets.shape[0] != nq:
+      raise ValueError('ranks: %d queries but targets %s' % (nq, tuple(targets.shape)))
+    shape = targets.shape
+    if nq == 0:
+      return tuple(torch.empty(shape, device=self.device, dtype=torch.int32) for _ in range(2))
+    tg = targets.reshape(nq, -1).contiguous()
+    greater = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
+    equal = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
+    lo, hi = (int(v) for v in torch.aminmax(tg))
+    if lo < -1 or hi >= nv:
+      raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (nv - 1, lo, hi))
+    L = _lib.lib()
+    bf16 = self.dtype == torch.bfloat16
+    with torch.cuda.device(self.device):
+      t_max = min(MAX_T, tg.shape[1])
+      per_row = m * d * 4 + 4 * t_max * (1 + 2 * -(-nv // 4096))  # folded row + its thresholds and chunk counters
+      batch = max(64, (_BATCH_BYTES // per_row) // 64 * 64)
+      for r0 in range(0, nq, batch):
+        r1 = min(nq, r0 + batch)
+        n = r1 - r0
+        if bf16:
+          hl = torch.empty(2, n, m * d, device=self.device, dtype=torch.bfloat16)  # hi = bf16(qf), lo = bf16(qf - hi)
+          check(L.mmt_search_fold_split_bf16(ops._p(q[r0:r1]), ops._p(qw[r0:r1]), n, m, d, ops._p(hl[0]), ops._p(hl[1]),
+                                             ops._stream()), 'mmt_search_fold_split_bf16')
+          operands = (ops._p(hl[0]), ops._p(hl[1]), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights))
+        else:
+          qf = _fold(q[r0:r1], qw[r0:r1])
+          operands = (ops._p(qf), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights))
+        ws = torch.empty(L.mmt_rank_workspace_ints(n, nv, t_max), device=self.device, dtype=torch.int32)
+        for t0 in range(0, tg.shape[1], MAX_T):
+          t1 = min(tg.shape[1], t0 + MAX_T)
+          whole = t0 == 0 and t1 == tg.shape[1]  # a column slice of a wider list is not contiguous: copy in and out
+          tgs = tg[r0:r1] if whole else tg[r0:r1, t0:t1].contiguous()
+          gs = greater[r0:r1] if whole else torch.empty(n, t1 - t0, device=self.device, dtype=torch.int32)
+          es = equal[r0:r1] if whole else torch.empty_like(gs)
+          fn, name = (L.mmt_search_rank_bf16, 'mmt_search_rank_bf16') if bf16 else (L.mmt_search_rank, 'mmt_search_rank')
+          check(fn(*operands, n, nv, m, d, ops._p(tgs), t1 - t0, ops._p(ws), ops._p(gs), ops._p(es), ops._stream()), name)
+          if not whole:
+            greater[r0:r1, t0:t1] = gs
+            equal[r0:r1, t0:t1] = es
+    return greater.reshape(shape), equal.reshape(shape)
+
+  def ranks(self, embds, weights, targets):
+    """The reference's tie-averaged 0-based rank (model/metric.py:90-121) of item targets[q, t] among the stored items for
+    query q: greater + (equal - 1) / 2 from `rank_counts`, +inf where the target is -1.  float64 on the device, of
+    targets' shape (float32 would not hold counts above 2^24)."""
+    greater, equal = self.rank_counts(embds, weights, targets)
+    ranks = greater.double() + (equal.double() - 1) / 2
+    return torch.where(targets < 0, torch.full_like(ranks, float('inf')), ranks)

@@ -14,7 +14,13 @@ functions require) it is their kernels, mmt_sims_eval + mmt_rows_topk.
 --gallery-dtype bfloat16 times the bf16-stored index instead; --gallery-dtype both times the two indexes side by side on
 the same data (--runs timed runs each, interleaved; median and spread = max - min) and reports per shape the index bytes,
 peak memory, TF (2 NQ NV M d counted once: the hi / lo query split is overhead, not work) and the share of rows whose
-index lists agree.  The bf16 index is built in chunks (VideoIndex.empty + add)."""
+index lists agree.  The bf16 index is built in chunks (VideoIndex.empty + add).
+
+--ranks times the exact rank of one ground-truth item per query (VideoIndex.ranks, T = 1) on both indexes, beside
+search(k = 1) and search(k = 10) on the same index -- the same scan with the top-k epilogue, the yardstick -- and beside
+the materialised path (mmt_sims_eval + mmt_retrieval_ranks: the N_query x N_video matrix, then its ranking) where that
+path applies (it wants NQ = NV x captions, so S1 and S2).  --runs rounds, every variant once per round, interleaved;
+median and spread.  Default output profiles/search_ranks_bench.json."""
 import argparse
 import json
 import math
@@ -104,6 +110,69 @@ def both_dtypes(q, qw, g, gw, flop, a):
   return row
 
 
+def materialised_ranks(q, qw, g, gw):
+  """The eval path of metric.retrieval_metrics: the whole similarity matrix, then the rank of the diagonal."""
+  nq, nv = q.shape[0], g.shape[0]
+  L = _lib.lib()
+  ws = torch.empty(L.mmt_sims_eval_workspace_floats(nq, nv, M, D), device=q.device)
+  sims = torch.empty(nq, nv, device=q.device)
+  _lib.check(L.mmt_sims_eval(ops._p(q), ops._p(g), ops._p(qw), ops._p(gw), nq, nv, M, D, ops._p(ws), ops._p(sims),
+                             ops._stream()), 'mmt_sims_eval')
+  del ws
+  t2v, v2t, scratch = (torch.empty(n, device=q.device) for n in (nq, nv, nq))
+  _lib.check(L.mmt_retrieval_ranks(ops._p(sims), None, nq, nv, ops._p(t2v), ops._p(v2t), ops._p(scratch), ops._stream()),
+             'mmt_retrieval_ranks')
+  return t2v
+
+
+def ranks_mode(q, qw, g, gw, flop, a):
+  """ranks() with one target per query against search(k = 1), search(k = 10) and the materialised ranking, per index."""
+  nq, nv = q.shape[0], g.shape[0]
+  tg = torch.arange(nq, device=q.device) % nv   # the item each query was drawn around (main)
+  idx = {'float32': VideoIndex(g, gw)}
+  idx['bfloat16'] = VideoIndex.empty(nv, M, D, g.device, dtype=torch.bfloat16)
+  for at in range(0, nv, 8192):
+    idx['bfloat16'].add(g[at:at + 8192], gw[at:at + 8192])
+  fns = {}
+  for n in idx:
+    fns[n + '/ranks'] = lambda n=n: idx[n].ranks(q, qw, tg)
+    fns[n + '/search_k1'] = lambda n=n: idx[n].search(q, qw, k=1)
+    fns[n + '/search_k10'] = lambda n=n: idx[n].search(q, qw, k=K)
+  if nq % nv == 0:
+    fns['materialised/ranks'] = lambda: materialised_ranks(q, qw, g, gw)
+  ts = {n: [] for n in fns}
+  mem = {n: 0 for n in fns}
+  out = {}
+  for _ in range(a.runs):
+    for n, fn in fns.items():
+      t, _, m, out[n] = timed(fn, a.min_seconds)
+      ts[n].append(t)
+      mem[n] = max(mem[n], m)
+  row = {}
+  for n in fns:
+    med = float(np.median(ts[n]))
+    row[n] = dict(seconds_median=med, seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n], tflops=flop / med / 1e12,
+                  peak_mem_growth_bytes=mem[n])
+  if 'materialised/ranks' not in fns:
+    row['materialised/ranks'] = 'not applicable: mmt_retrieval_ranks wants NQ = NV x captions'
+  for n in idx:
+    r, k1, k10 = (row['%s/%s' % (n, v)] for v in ('ranks', 'search_k1', 'search_k10'))
+    margin = max(r['seconds_spread'], k1['seconds_spread'], k10['seconds_spread'])
+    ranks = out[n + '/ranks']
+    row[n + '/summary'] = dict(
+        ranks_over_search_k1=r['seconds_median'] / k1['seconds_median'],
+        ranks_over_search_k10=r['seconds_median'] / k10['seconds_median'], margin_seconds=margin,
+        ranks_within_margin_of_search_k1=bool(r['seconds_median'] - k1['seconds_median'] <= margin),
+        ranks_slower_than_search_k10_beyond_margin=bool(r['seconds_median'] - k10['seconds_median'] > margin),
+        # R@1 two ways: rank 0 from ranks(), and the first item of search(k = 1) being the target (they can differ on ties)
+        r_at_1_from_ranks=float((ranks == 0).double().mean()),
+        r_at_1_from_search=float((out[n + '/search_k1'][1][:, 0] == tg).double().mean()),
+        median_rank=float(ranks.median()), mean_rank=float(ranks.mean()))
+    if 'materialised/ranks' in fns:
+      row[n + '/summary']['ranks_equal_materialised'] = float((ranks == out['materialised/ranks'].double()).double().mean())
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--shapes', default='S1,S2,S3')
@@ -112,13 +181,19 @@ def main():
   ap.add_argument('--skip-materialised', action='store_true', help='fused path only (kernel-trace runs)')
   ap.add_argument('--gallery-dtype', choices=('float32', 'bfloat16', 'both'), default='float32')
   ap.add_argument('--runs', type=int, default=5, help='timed runs per index with --gallery-dtype both')
+  ap.add_argument('--ranks', action='store_true', help='time VideoIndex.ranks (T = 1) against search(k = 1) and the '
+                  'materialised ranking, both gallery dtypes')
   a = ap.parse_args()
+  if a.ranks and a.out is None:
+    a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_ranks_bench.json')
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
   res = {'M': M, 'd': D, 'k': K, 'peak_fp32_matrix_flops': PEAK, 'device': torch.cuda.get_device_name(0), 'shapes': {}}
   if a.gallery_dtype != 'float32':  # the default invocation keeps its JSON layout
     res['gallery_dtype'] = a.gallery_dtype
+  if a.ranks:
+    res.update(mode='ranks', T=1, runs=a.runs, min_seconds=a.min_seconds)
   for name in a.shapes.split(','):
     nq, nv = SHAPES[name]
     gen = torch.Generator(device=dev).manual_seed(0)
@@ -129,8 +204,8 @@ def main():
     qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
     flop = 2.0 * nq * nv * M * D
     row = {'NQ': nq, 'NV': nv, 'flop': flop}
-    if a.gallery_dtype == 'both':
-      row.update(both_dtypes(q, qw, g, gw, flop, a))
+    if a.ranks or a.gallery_dtype == 'both':
+      row.update(ranks_mode(q, qw, g, gw, flop, a) if a.ranks else both_dtypes(q, qw, g, gw, flop, a))
       res['shapes'][name] = row
       print(name, json.dumps(row), flush=True)
       del g, gw, q, qw
