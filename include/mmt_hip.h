@@ -559,6 +559,25 @@ int mmt_ls_grad_ex(const float* S, int64_t ld, const float* diag, const float* t
 int mmt_ls_unfold(const float* P, int64_t ldp, const float* x, const float* w, const float* gsub, int R, int M, int d,
                   float* dx, float* dw, void* stream);
 
+/* ---- row-sharded InfoNCE over the same row block (largesim.hip; model/loss.py:68-81) ---------------------------------
+ * loss = CE(z, diag) + CE(z^T, diag), z = scale * S (scale = 1 is the reference), with rank r owning rows r0..r0+b:
+ *   loss = (1/n) sum_t (row_lse[t] + col_lse[r0+t] - 2 z[t, r0+t]),  dL/dS = scale/n (exp(z - row_lse[t]) + exp(z - col_lse[v]) - 2 [v == r0+t]).
+ * Both passes read the RAW numerators of the similarity GEMM and divide on the fly (S is never written); vw_t as above.
+ *   mmt_ls_nce_stats: online-softmax partials, (max, sum of exp relative to that max), planar: plane 0 = max, plane 1 = sum.
+ *                     row_part[2, b, ncb]   per local row and column block, ncb = mmt_ls_nce_col_blocks(n);
+ *                     col_part[nrg, 2, n]   per column and group of rows,  nrg = mmt_ls_nce_row_groups(b), 16-byte aligned.
+ *                     No atomics: the caller combines the partials in a fixed order (and the columns across ranks).
+ *   mmt_ls_nce_grad : G16[t,v] = bf16((dL/dS)/den) and gs_part[t,cb,m] in the layout of mmt_ls_grad_ex (cb < mmt_ls_col_blocks(n))
+ *                     from row_lse[b] and the GLOBAL col_lse[n] (16-byte aligned); inv_n = 1/n.
+ * n, ld, ldg multiples of 4; r0 + b <= n; 1 <= M <= 16; scale finite and > 0. */
+int mmt_ls_nce_col_blocks(int n);
+int mmt_ls_nce_row_groups(int b);
+int mmt_ls_nce_stats(const float* S, int64_t ld, const float* tw, const float* vw, const float* vw_t, int b, int n, int M, int r0,
+                     float scale, float* row_part, float* col_part, void* stream);
+int mmt_ls_nce_grad(const float* S, int64_t ld, const float* tw, const float* vw, const float* vw_t, const float* row_lse,
+                    const float* col_lse, int b, int n, int M, int r0, float scale, float inv_n, void* G16, int64_t ldg,
+                    float* gs_part, void* stream);
+
 /* ---- text heads (texthead.hip), fp32 ------------------------------------------------------------------
  * GatedEmbeddingUnit per expert (model.py:683-702, 736-750) + text MoE weights (model.py:262-283,618),
  * batched over the M experts. */

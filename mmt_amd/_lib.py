@@ -240,6 +240,11 @@ SIGNATURES = {
     'mmt_ls_grad_ex': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f32, c_f32, c_vp, c_i64,
                             c_vp, c_int, c_vp]),
     'mmt_ls_unfold': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    'mmt_ls_nce_col_blocks': (c_int, [c_int]),
+    'mmt_ls_nce_row_groups': (c_int, [c_int]),
+    'mmt_ls_nce_stats': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f32, c_vp, c_vp, c_vp]),
+    'mmt_ls_nce_grad': (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f32, c_f32, c_vp, c_i64,
+                                c_vp, c_vp]),
     'mmt_simloss_small_max_n': (c_int, []),
     'mmt_simloss_bwd_small': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f32, c_int, c_vp, c_vp,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

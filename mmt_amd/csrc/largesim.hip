@@ -390,6 +390,264 @@ extern "C" int mmt_ls_grad_ex(const float* S, int64_t ld, const float* diag, con
   return (int)hipGetLastError();
 }
 
+// ---- row-sharded InfoNCE (model/loss.py:68-81) over the same row block ----------------------------------------------------
+//   z = scale * S,  loss = (1/n) sum_t (row_lse[t] + col_lse[r0 + t] - 2 z[t][r0 + t]),
+//   dL/dS[t][v] = scale / n * (exp(z - row_lse[t]) + exp(z - col_lse[v]) - 2 [v == r0 + t])
+// Two passes over the RAW numerators (both divide on the fly with ls_den / ls_rcp / ls_quot, as ls_sweep_kernel<.., 7> and
+// ls_grad2_kernel<.., true> do; S is never rewritten).  Between them the host combines the partials below and, across
+// ranks, the column statistics.  Everything is (max, sum of exp relative to that max) pairs: safe for any finite logits.
+//
+// Statistics pass.  One block = NCE_RG = 128 rows x NCE_CPB = 4096 columns, walked as row tiles of TR rows (16 at M <= 8,
+// 8 above) times 4 chunks of 1024 columns; a thread owns the same 4 columns of every chunk for the whole block.
+//   per (tile, chunk): z for TR x 4 elements in registers; the 4 columns' (max, sum) over the tile's rows are thread-local
+//     (TR - 1 max, TR exp per column) and merged into the block's running column pair, which lives in the thread's own LDS
+//     slot (no other thread touches it: no barrier, no atomics); the TR rows' running (max, sum) stay in registers across
+//     the 4 chunks (one rescale + 4 exp per row and chunk).
+//   per tile: rows reduced over the wave (max, then sum relative to it), over the 4 waves through LDS in wave order.
+//   per block: the thread's column pairs go out once.
+// Workspace (floats; both planar, plane 0 = max, plane 1 = sum):
+//   row_part[2][b][ncb]   ncb = mmt_ls_nce_col_blocks(n) = ceil(n / 4096)
+//   col_part[nrg][2][n]   nrg = mmt_ls_nce_row_groups(b) = ceil(b / 128)
+// At b = 8192, n = 65536: row_part 1 MiB, col_part 64 * 2 * 65536 * 4 B = 32 MiB = 1/64 of the 2 GiB row block.
+// Every partial is combined downstream in a fixed order, so the results are bit-reproducible.
+#define NCE_CPB 4096
+#define NCE_RG 128
+#define NCE_NCHUNK (NCE_CPB / LS_CHUNK)
+#define NCE_NEG (-3.402823466e+38f)  // "no element yet": exp(NCE_NEG - finite) == 0, and no inf - inf anywhere
+static inline int nce_col_blocks(int n) { return (n + NCE_CPB - 1) / NCE_CPB; }
+static inline int nce_row_groups(int b) { return (b + NCE_RG - 1) / NCE_RG; }
+extern "C" int mmt_ls_nce_col_blocks(int n) { return n > 0 ? nce_col_blocks(n) : MMT_ERR_ARG; }
+extern "C" int mmt_ls_nce_row_groups(int b) { return b > 0 ? nce_row_groups(b) : MMT_ERR_ARG; }
+
+template <int TR, int MM>
+__global__ __launch_bounds__(256, 2) void ls_nce_stats_kernel(const float* __restrict__ S, int64_t ld, const float* __restrict__ tw,
+                                                              const float* __restrict__ vw, const float* __restrict__ vwt, int b,
+                                                              int n, int M, float scale, float* __restrict__ row_part,
+                                                              float* __restrict__ col_part) {
+  __shared__ float tws[TR][MM];
+  __shared__ f32x4 colm_s[NCE_NCHUNK][256], cols_s[NCE_NCHUNK][256];  // the thread's own running column pairs
+  __shared__ float redm[4][TR], reds[4][TR];
+  const int cb = blockIdx.x, ncb = gridDim.x, rg = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c_beg = cb * NCE_CPB + tid * 4, c_end = min(n, (cb + 1) * NCE_CPB);
+  const int t_beg = rg * NCE_RG, t_end = min(b, t_beg + NCE_RG);
+  for (int t0 = t_beg; t0 < t_end; t0 += TR) {
+    __syncthreads();  // (the previous tile's readers of tws / redm / reds are done)
+    for (int e = tid; e < TR * MM; e += 256) {
+      const int r = e / MM, m = e % MM;
+      tws[r][m] = (t0 + r < b && m < M) ? tw[(int64_t)(t0 + r) * M + m] : 0.f;
+    }
+    __syncthreads();
+    float rm[TR], rs[TR];
+#pragma unroll
+    for (int r = 0; r < TR; ++r) { rm[r] = NCE_NEG; rs[r] = 0.f; }
+    const bool full = t0 + TR <= b;
+    int k = 0;
+    for (int c0 = c_beg; c0 < c_end; c0 += LS_CHUNK, ++k) {
+      // (the row data in LDS is loop-invariant: without this the compiler hoists all TR x MM of it into VGPRs and spills)
+      asm volatile("" ::: "memory");
+      float vwc[4][MM];
+      f32x4 dg;
+      ls_load_cols<MM>(vw, vwt, nullptr, c0, n, M, vwc, dg);
+      f32x4 z[TR];
+#pragma unroll
+      for (int r = 0; r < TR; ++r)  // (rows beyond b re-read row b - 1 and are masked below)
+        z[r] = *(const f32x4*)(S + (int64_t)min(t0 + r, b - 1) * ld + c0);
+#pragma unroll
+      for (int r = 0; r < TR; ++r) {
+        float twr[MM];
+#pragma unroll
+        for (int m = 0; m < MM; ++m) twr[m] = tws[r][m];
+        const bool live = full || t0 + r < b;  // (block-uniform)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          bool zero;
+          const float den = ls_den<MM>(twr, vwc[j], &zero);
+          const float zj = scale * ls_quot(z[r][j], ls_rcp(den));
+          z[r][j] = live ? zj : NCE_NEG;
+        }
+      }
+      // the tile's column pairs: thread-local
+      f32x4 cm = z[0], cs = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int r = 1; r < TR; ++r)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cm[j] = fmaxf(cm[j], z[r][j]);
+#pragma unroll
+      for (int r = 0; r < TR; ++r)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cs[j] += __expf(z[r][j] - cm[j]);
+      // the rows' running pairs
+#pragma unroll
+      for (int r = 0; r < TR; ++r) {
+        const float nm = fmaxf(rm[r], fmaxf(fmaxf(z[r][0], z[r][1]), fmaxf(z[r][2], z[r][3])));
+        rs[r] = rs[r] * __expf(rm[r] - nm) +
+                ((__expf(z[r][0] - nm) + __expf(z[r][1] - nm)) + (__expf(z[r][2] - nm) + __expf(z[r][3] - nm)));
+        rm[r] = nm;
+      }
+      if (t0 != t_beg) {  // merge with the pairs of the tiles above (one exp per column: the smaller side is rescaled)
+        const f32x4 om = colm_s[k][tid], os = cols_s[k][tid];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float e = __expf(-fabsf(om[j] - cm[j]));
+          cs[j] = om[j] >= cm[j] ? os[j] + cs[j] * e : os[j] * e + cs[j];
+          cm[j] = fmaxf(om[j], cm[j]);
+        }
+      }
+      colm_s[k][tid] = cm;
+      cols_s[k][tid] = cs;
+    }
+#pragma unroll
+    for (int r = 0; r < TR; ++r) {
+      const float wm = wave_max(rm[r]);
+      const float ws = wave_sum(rs[r] * __expf(rm[r] - wm));
+      if (lane == 0) { redm[wave][r] = wm; reds[wave][r] = ws; }
+    }
+    __syncthreads();
+    if (tid < TR && t0 + tid < b) {
+      const float mx = fmaxf(fmaxf(redm[0][tid], redm[1][tid]), fmaxf(redm[2][tid], redm[3][tid]));
+      const float sm = (reds[0][tid] * __expf(redm[0][tid] - mx) + reds[1][tid] * __expf(redm[1][tid] - mx)) +
+                       (reds[2][tid] * __expf(redm[2][tid] - mx) + reds[3][tid] * __expf(redm[3][tid] - mx));
+      const int64_t o = (int64_t)(t0 + tid) * ncb + cb;
+      row_part[o] = mx;
+      row_part[(int64_t)b * ncb + o] = sm;
+    }
+  }
+  int k = 0;
+  for (int c0 = c_beg; c0 < c_end; c0 += LS_CHUNK, ++k) {  // (own slots only: program order suffices)
+    float* o = col_part + (int64_t)rg * 2 * n + c0;
+    *(f32x4*)o = colm_s[k][tid];
+    *(f32x4*)(o + n) = cols_s[k][tid];
+  }
+}
+
+// Gradient pass: ls_grad2_kernel<.., RAW = true> with the hinge decision replaced by the two exponentials.
+//   G'[t][v] = bf16(g / den),  g = scale / n * (exp(z - row_lse[t]) + exp(z - col_lse[v]) - 2 [v == r0 + t]),
+//   gs_part[t][cb][m] = sum over column block cb (LS_CPB columns, as mmt_ls_grad_ex) of G' S vw[v][m], zero where den took
+//   the 1e-5 branch.  Checked / plain copies of the chunk body as above (the diagonal term and rows beyond b).
+template <int TR, int MM>
+__global__ __launch_bounds__(256, 2) void ls_nce_grad_kernel(const float* __restrict__ S, int64_t ld, const float* __restrict__ tw,
+                                                             const float* __restrict__ vw, const float* __restrict__ vwt,
+                                                             const float* __restrict__ row_lse, const float* __restrict__ col_lse,
+                                                             int b, int n, int M, int r0, float scale, float inv_n,
+                                                             bf16_t* __restrict__ G16, int64_t ldg, float* __restrict__ gs_part) {
+  __shared__ float tws[TR][MM];
+  __shared__ float rl_s[TR];
+  __shared__ float red[4][TR][MM];
+  const int cb = blockIdx.x, ncb = gridDim.x, t0 = blockIdx.y * TR, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int e = tid; e < TR * MM; e += 256) {
+    const int r = e / MM, m = e % MM;
+    tws[r][m] = (t0 + r < b && m < M) ? tw[(int64_t)(t0 + r) * M + m] : 0.f;
+  }
+  if (tid < TR) rl_s[tid] = t0 + tid < b ? row_lse[t0 + tid] : 0.f;
+  __syncthreads();
+  float acc[TR][MM];
+#pragma unroll
+  for (int r = 0; r < TR; ++r)
+#pragma unroll
+    for (int m = 0; m < MM; ++m) acc[r][m] = 0.f;
+  const bool full = t0 + TR <= b;
+  const int rg0 = r0 + t0;
+  const int c_end = min(n, (cb + 1) * LS_CPB);
+  const float w = scale * inv_n;
+  for (int c0 = cb * LS_CPB + tid * 4; c0 < c_end; c0 += LS_CHUNK) {
+    // (the row data in LDS is loop-invariant: without this the compiler hoists all TR x MM of it into VGPRs and spills)
+    asm volatile("" ::: "memory");
+    float vwc[4][MM];
+    f32x4 cl;
+    ls_load_cols<MM>(vw, vwt, col_lse, c0, n, M, vwc, cl);
+    f32x4 sv[TR];
+#pragma unroll
+    for (int r = 0; r < TR; ++r) sv[r] = *(const f32x4*)(S + (int64_t)min(t0 + r, b - 1) * ld + c0);
+    auto rows = [&](auto checked_t) {
+      constexpr bool CHECKED = decltype(checked_t)::value;
+#pragma unroll
+      for (int r = 0; r < TR; ++r) {
+        if (CHECKED && t0 + r >= b) continue;  // (block-uniform)
+        const float rl = rl_s[r];
+        float twr[MM];
+#pragma unroll
+        for (int m = 0; m < MM; ++m) twr[m] = tws[r][m];
+        float gq[4], gpb[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          bool zero;
+          const float rden = ls_rcp(ls_den<MM>(twr, vwc[j], &zero));
+          const float sj = ls_quot(sv[r][j], rden);
+          const float zj = scale * sj;
+          float p = __expf(zj - rl) + __expf(zj - cl[j]);
+          if (CHECKED && c0 + j == rg0 + r) p -= 2.f;
+          gq[j] = ls_quot(w * p, rden);
+          // the 1e-5 branch carries no normaliser gradient (model.py:816)
+          gpb[j] = zero ? 0.f : sj;
+        }
+        const u32x2 o = {pack_bf2(gq[0], gq[1]), pack_bf2(gq[2], gq[3])};
+        *(u32x2*)(G16 + (int64_t)(t0 + r) * ldg + c0) = o;
+        gpb[0] *= __uint_as_float(o[0] << 16); gpb[1] *= __uint_as_float(o[0] & 0xffff0000u);
+        gpb[2] *= __uint_as_float(o[1] << 16); gpb[3] *= __uint_as_float(o[1] & 0xffff0000u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int m = 0; m < MM; ++m) acc[r][m] += gpb[j] * vwc[j][m];
+      }
+    };
+    if (full && !__ballot(c0 < rg0 + TR && c0 + 4 > rg0)) rows(std::false_type{});
+    else rows(std::true_type{});
+  }
+#pragma unroll
+  for (int r = 0; r < TR; ++r)
+#pragma unroll
+    for (int m = 0; m < MM; ++m) {
+      const float v = wave_sum(acc[r][m]);
+      if (lane == 0) red[wave][r][m] = v;
+    }
+  __syncthreads();
+  for (int e = tid; e < TR * MM; e += 256) {
+    const int r = e / MM, m = e % MM;
+    if (t0 + r < b && m < M)
+      gs_part[((int64_t)(t0 + r) * ncb + cb) * M + m] = (red[0][r][m] + red[1][r][m]) + (red[2][r][m] + red[3][r][m]);
+  }
+}
+
+static bool nce_scale_ok(float scale) { return scale > 0.f && scale <= 3.402823466e+38f; }  // (false for NaN)
+
+// r0 places the block in the n x n matrix (r0 + b <= n); the statistics themselves do not depend on it.
+extern "C" int mmt_ls_nce_stats(const float* S, int64_t ld, const float* tw, const float* vw, const float* vw_t, int b, int n, int M,
+                                int r0, float scale, float* row_part, float* col_part, void* stream) {
+  if (!S || !tw || !vw || !row_part || !col_part || b <= 0 || n <= 0 || r0 < 0 || (int64_t)r0 + b > n || M <= 0 || M > LS_MAXM ||
+      ld < n || !nce_scale_ok(scale))
+    return MMT_ERR_ARG;
+  if ((n & 3) || (ld & 3) || ((uintptr_t)S & 15) || ((uintptr_t)vw_t & 15) || ((uintptr_t)col_part & 15)) return MMT_ERR_ALIGN;
+  const dim3 grid(nce_col_blocks(n), nce_row_groups(b));
+  if (M <= 8)
+    hipLaunchKernelGGL((ls_nce_stats_kernel<16, 8>), grid, dim3(256), 0, (hipStream_t)stream, S, ld, tw, vw, vw_t, b, n, M, scale,
+                       row_part, col_part);
+  else
+    hipLaunchKernelGGL((ls_nce_stats_kernel<8, 16>), grid, dim3(256), 0, (hipStream_t)stream, S, ld, tw, vw, vw_t, b, n, M, scale,
+                       row_part, col_part);
+  return (int)hipGetLastError();
+}
+
+// row_lse [b]: logsumexp over all n columns of the local rows; col_lse [n]: over all n rows (every rank's), 16-byte aligned.
+// gs_part: [b, mmt_ls_col_blocks(n), M], the layout of mmt_ls_grad_ex.
+extern "C" int mmt_ls_nce_grad(const float* S, int64_t ld, const float* tw, const float* vw, const float* vw_t, const float* row_lse,
+                               const float* col_lse, int b, int n, int M, int r0, float scale, float inv_n, void* G16, int64_t ldg,
+                               float* gs_part, void* stream) {
+  if (!S || !tw || !vw || !row_lse || !col_lse || !G16 || !gs_part || b <= 0 || n <= 0 || r0 < 0 || (int64_t)r0 + b > n || M <= 0 ||
+      M > LS_MAXM || ld < n || ldg < n || !nce_scale_ok(scale) || !(inv_n > 0.f))
+    return MMT_ERR_ARG;
+  if ((n & 3) || (ld & 3) || (ldg & 3) || ((uintptr_t)S & 15) || ((uintptr_t)vw_t & 15) || ((uintptr_t)col_lse & 15) ||
+      ((uintptr_t)G16 & 7))
+    return MMT_ERR_ALIGN;
+#define NCE_GRAD(TRR, MMM)                                                                                                        \
+  hipLaunchKernelGGL((ls_nce_grad_kernel<TRR, MMM>), dim3(ls_col_blocks(n), (b + TRR - 1) / TRR), dim3(256), 0, (hipStream_t)stream, \
+                     S, ld, tw, vw, vw_t, row_lse, col_lse, b, n, M, r0, scale, inv_n, (bf16_t*)G16, ldg, gs_part)
+  // (TR x MM gs accumulators per thread: 8 rows x 8 experts; 2 x 16 above -- 4 x 16 spills 23 registers to scratch)
+  if (M <= 8) NCE_GRAD(8, 8);
+  else NCE_GRAD(2, 16);
+#undef NCE_GRAD
+  return (int)hipGetLastError();
+}
+
 // dst[c][r] = src[r][c] for bf16 matrices (rows, cols multiples of 128): the backward GEMMs of the row block are NT GEMMs
 // on the 256x256 eight-phase kernel (gemm3.hip), which wants both operands K-contiguous -- V'^T for P = G' V', and G'^T,
 // T'^T for Q = G'^T T'.  128 x 128 tiles; a thread transposes 2 x 8 patches in registers (dword = two rows of one column),

@@ -10,6 +10,10 @@ owns the text ROWS r0..r0+b: its b texts against all n (all-gathered) videos,
     dT, dtw   from P = G' V'               one GEMM
     dV        from Q = G'^T T'             one GEMM + a reduce-scatter over ranks
 
+The same row block carries the reference's second loss, InfoNCE (model/loss.py:68-81): `phase_nce_stats` /
+`phase_nce_loss` / `phase_nce_backward` replace the two hinge passes by a statistics pass (online-softmax partials of the
+rows and the columns) and a gradient pass; the cross-rank quantity is the column logsumexp instead of the column counts.
+
 The maths is phase-structured (`phase_*`) so that the collectives sit between plain function calls; `ShardedSimLoss`
 wires the phases to torch.distributed (RCCL) and degenerates to a single row block without a process group.
 """
@@ -98,8 +102,8 @@ class RowBlock:
 
   # ---- phase C: gradients of the local texts, contribution to every video ----------------------------
   def phase_backward(self, colcnt_total):
-    L, b, n, m, d = self.L, self.b, self.n, self.m, self.d
-    md, bp = m * d, self.t16.shape[0]
+    L, b, n, m = self.L, self.b, self.n, self.m
+    bp = self.t16.shape[0]
     colcnt_total = colcnt_total.to(device=self.dev, dtype=torch.int32).contiguous()
     g16 = torch.empty(bp, n, device=self.dev, dtype=torch.bfloat16)
     g16[b:].zero_()                                        # (pad rows: K of the Q product)
@@ -107,6 +111,12 @@ class RowBlock:
     check(L.mmt_ls_grad_ex(ops._p(self.S), self.ld, ops._p(self.diag_all), ops._p(self.tw), ops._p(self.vw_all), ops._p(self.vw_t),
                            ops._p(self.rowcnt), ops._p(colcnt_total), b, n, m, self.r0, self.margin, 1.0 / self.norm, ops._p(g16), n, ops._p(gs_part),
                            0 if self.keep_similarity else 1, ops._stream()), 'mmt_ls_grad_ex')
+    return self._backward_tail(g16, gs_part)
+
+  def _backward_tail(self, g16, gs_part):
+    """(dtxt, dtw, q) from G' [bp, n] (bf16, pad rows zero) and its gs partials [b, ncb, M]: the same for every loss."""
+    L, b, n, m, d = self.L, self.b, self.n, self.m, self.d
+    md, bp = m * d, self.t16.shape[0]
     gs = gs_part.sum(1)
     v16t = _transposed(L, self.v16)                        # [M*d, n]: B operand of P = G' V'
     p = torch.empty(bp, md, device=self.dev, dtype=torch.float32)
@@ -119,6 +129,53 @@ class RowBlock:
     ops.gemm_nt(_transposed(L, g16), _transposed(L, self.t16), q, 'F32')   # K = the (zero-padded) local rows
     return dtxt, dtw, q
 
+  # ---- InfoNCE on the same block (model/loss.py:68-81): phases B' and C' -----------------------------------
+  @staticmethod
+  def nce_merge(mx, sm, dim):
+    """(max, sum of exp relative to it) partials along `dim` -> one pair, in fp64 and in index order."""
+    mx, sm = mx.double(), sm.double()
+    top = mx.amax(dim, keepdim=True)
+    return top.squeeze(dim), (sm * torch.exp(mx - top)).sum(dim)
+
+  def phase_nce_stats(self, scale=1.0):
+    """One sweep over the raw numerators: returns (col_stat [2, n], row_lse [b]) -- this rank's (max, sum-exp) of every
+    column of z = scale * S over its b rows (to be all-gathered and combined by `nce_col_lse`), and the finished
+    logsumexp of its rows."""
+    L, b, n = self.L, self.b, self.n
+    self.scale = float(scale)
+    ncb, nrg = L.mmt_ls_nce_col_blocks(n), L.mmt_ls_nce_row_groups(b)
+    row_part = torch.empty(2, b, ncb, device=self.dev, dtype=torch.float32)
+    col_part = torch.empty(nrg, 2, n, device=self.dev, dtype=torch.float32)
+    check(L.mmt_ls_nce_stats(ops._p(self.S), self.ld, ops._p(self.tw), ops._p(self.vw_all), ops._p(self.vw_t), b, n, self.m,
+                             self.r0, self.scale, ops._p(row_part), ops._p(col_part), ops._stream()), 'mmt_ls_nce_stats')
+    top, sm = self.nce_merge(row_part[0], row_part[1], 1)
+    self.row_lse = (top + torch.log(sm)).float()
+    top, sm = self.nce_merge(col_part[:, 0], col_part[:, 1], 0)
+    return torch.stack([top, sm]).float(), self.row_lse
+
+  @classmethod
+  def nce_col_lse(cls, col_stat_all):
+    """[world, 2, n] all-gathered column statistics -> col_lse [n], combined in rank order (bit-identical on every rank)."""
+    top, sm = cls.nce_merge(col_stat_all[:, 0], col_stat_all[:, 1], 0)
+    return (top + torch.log(sm)).float()
+
+  def phase_nce_loss(self, col_lse_all):
+    """This rank's share of the loss: (1/n) sum_t (row_lse[t] + col_lse[r0 + t] - 2 z[t][r0 + t]); the shares add up."""
+    own = col_lse_all[self.r0:self.r0 + self.b].double()
+    terms = self.row_lse.double() + own - 2.0 * self.scale * self.diag_local.double()
+    return (terms.sum() / self.n).float()
+
+  def phase_nce_backward(self, col_lse_all):
+    L, b, n, m = self.L, self.b, self.n, self.m
+    col_lse_all = _f32(col_lse_all)
+    g16 = torch.empty(self.t16.shape[0], n, device=self.dev, dtype=torch.bfloat16)
+    g16[b:].zero_()                                        # (pad rows: K of the Q product)
+    gs_part = torch.empty(b, L.mmt_ls_col_blocks(n), m, device=self.dev, dtype=torch.float32)
+    check(L.mmt_ls_nce_grad(ops._p(self.S), self.ld, ops._p(self.tw), ops._p(self.vw_all), ops._p(self.vw_t), ops._p(self.row_lse),
+                            ops._p(col_lse_all), b, n, m, self.r0, self.scale, 1.0 / n, ops._p(g16), n, ops._p(gs_part),
+                            ops._stream()), 'mmt_ls_nce_grad')
+    return self._backward_tail(g16, gs_part)
+
   # ---- phase D: gradient of the local videos from the reduce-scattered Q rows ---------------------------
   def phase_video_grad(self, q_rows, vid_local, vw_local):
     vid_local, vw_local = _f32(vid_local), _f32(vw_local)
@@ -130,6 +187,15 @@ class RowBlock:
     return dvid
 
 
+def _gather(x, world, group):
+  """All-gather along dim 0, rank order."""
+  if world == 1:
+    return x.detach().contiguous()
+  out = torch.empty((world * x.shape[0],) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype)
+  dist.all_gather_into_tensor(out, x.detach().contiguous(), group=group)
+  return out
+
+
 class _ShardedSimLossFn(torch.autograd.Function):
 
   @staticmethod
@@ -137,14 +203,7 @@ class _ShardedSimLossFn(torch.autograd.Function):
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     b = vid.shape[0]
-
-    def gather(x):
-      if world == 1:
-        return x.detach().contiguous()
-      out = torch.empty((world * x.shape[0],) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype)
-      dist.all_gather_into_tensor(out, x.detach().contiguous(), group=group)
-      return out
-
+    gather = lambda x: _gather(x, world, group)
     blk = RowBlock(txt, tw, gather(vid), gather(vw), rank * b, margin, fix_norm)
     diag_all = gather(blk.phase_similarity())
     colcnt, loss = blk.phase_counts(diag_all)
@@ -169,6 +228,68 @@ class _ShardedSimLossFn(torch.autograd.Function):
     return dvid * gout, dtxt * gout, None, dtw * gout, None, None, None
 
 
+class _ShardedInfoNceLossFn(torch.autograd.Function):
+
+  @staticmethod
+  def forward(ctx, vid, txt, vw, tw, scale, group):
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    b = vid.shape[0]
+    blk = RowBlock(txt, tw, _gather(vid, world, group), _gather(vw, world, group), rank * b, 0.0)
+    blk.phase_similarity()  # (the diagonal stays local: this loss needs each rank's own part of it only)
+    col_stat, _ = blk.phase_nce_stats(scale)
+    col_lse = RowBlock.nce_col_lse(_gather(col_stat[None], world, group))
+    loss = blk.phase_nce_loss(col_lse)
+    if world > 1:
+      dist.all_reduce(loss, group=group)
+    dtxt, dtw, q = blk.phase_nce_backward(col_lse)
+    if world > 1:
+      q_rows = torch.empty(b, q.shape[1], device=q.device, dtype=q.dtype)
+      dist.reduce_scatter_tensor(q_rows, q, group=group)
+    else:
+      q_rows = q
+    dvid = blk.phase_video_grad(q_rows, vid, vw)
+    ctx.save_for_backward(dvid, dtxt, dtw)
+    return loss
+
+  @staticmethod
+  def backward(ctx, gout):
+    dvid, dtxt, dtw = ctx.saved_tensors
+    return dvid * gout, dtxt * gout, None, dtw * gout, None, None
+
+
+def _check_sharded_inputs(vid_embds, text_embds, vid_weights, text_weights):
+  if text_embds.dim() == 4:  # (B, M, C=1, d) as CENet returns it
+    if text_embds.shape[2] != 1:
+      raise NotImplementedError('row-sharded loss: one caption per video (training layout)')
+    text_embds = text_embds[:, :, 0]
+  if text_weights.dim() == 3:
+    text_weights = text_weights[:, 0]
+  if not vid_embds.is_cuda:
+    raise RuntimeError('mmt_amd.large_sim runs on the GPU only (no CPU fallback)')
+  if vid_weights.requires_grad:
+    raise NotImplementedError('row-sharded loss: video mixture weights are constants (vid_wgh="none")')
+  return text_embds, text_weights
+
+
+class ShardedInfoNceLoss(torch.nn.Module):
+  """loss = InfoNceLoss()(scale * sharded_cross_view_inner_product(...)) over the GLOBAL batch (model/loss.py:68-81;
+  scale = 1 is the reference), with the n x n matrix sharded by text rows over the ranks of `group`.  Same inputs as
+  `ShardedSimLoss`.  Collectives per step: the all-gathers of videos and weights, one all-gather of the per-rank column
+  (max, sum-exp), one all-reduce of the scalar loss, the reduce-scatter of the video gradients (no diagonal all-gather:
+  every rank needs its own diagonal entries only)."""
+
+  def __init__(self, scale=1.0, group=None):
+    super().__init__()
+    if not (scale > 0.0 and scale < float('inf')):
+      raise ValueError('ShardedInfoNceLoss: scale must be finite and positive')
+    self.scale, self.group = float(scale), group
+
+  def forward(self, vid_embds, text_embds, vid_weights, text_weights):
+    text_embds, text_weights = _check_sharded_inputs(vid_embds, text_embds, vid_weights, text_weights)
+    return _ShardedInfoNceLossFn.apply(vid_embds, text_embds, vid_weights, text_weights, self.scale, self.group)
+
+
 class ShardedSimLoss(torch.nn.Module):
   """loss = MaxMarginRankingLoss(margin, fix_norm)(sharded_cross_view_inner_product(...)) over the GLOBAL batch,
   with the n x n matrix sharded by text rows over the ranks of `group`.  Inputs are this rank's (b, M, d) expert
@@ -180,14 +301,5 @@ class ShardedSimLoss(torch.nn.Module):
     self.margin, self.fix_norm, self.group = margin, fix_norm, group
 
   def forward(self, vid_embds, text_embds, vid_weights, text_weights):
-    if text_embds.dim() == 4:  # (B, M, C=1, d) as CENet returns it
-      if text_embds.shape[2] != 1:
-        raise NotImplementedError('row-sharded loss: one caption per video (training layout)')
-      text_embds = text_embds[:, :, 0]
-    if text_weights.dim() == 3:
-      text_weights = text_weights[:, 0]
-    if not vid_embds.is_cuda:
-      raise RuntimeError('mmt_amd.large_sim runs on the GPU only (no CPU fallback)')
-    if vid_weights.requires_grad:
-      raise NotImplementedError('row-sharded loss: video mixture weights are constants (vid_wgh="none")')
+    text_embds, text_weights = _check_sharded_inputs(vid_embds, text_embds, vid_weights, text_weights)
     return _ShardedSimLossFn.apply(vid_embds, text_embds, vid_weights, text_weights, self.margin, self.fix_norm, self.group)
