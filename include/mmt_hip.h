@@ -465,7 +465,7 @@ int mmt_sims_eval(const float* txt, const float* vid, const float* tw, const flo
 int mmt_retrieval_ranks(const float* sims, const uint8_t* qmask, int NQ, int NV, float* t2v_rank, float* v2t_rank,
                         float* scratch, void* stream);
 
-/* ---- top-k retrieval (search.hip, search_bf16.hip, search_rank.hip, fold in retrieval.hip) --------------------------------------
+/* ---- top-k retrieval (search.hip, search_bf16.hip, search_rank.hip, search_subset.hip, fold in retrieval.hip) --------------------------------------
  * score(q, g) = sum_m qw[q][m] gw[g][m] <Q_m[q], G_m[g]> / sum_m qw[q][m] gw[g][m] (0 -> 1e-5), the 'indep' similarity
  * of model/model.py:789-837.  Per query the min(k, NV) best (score, gallery index) pairs, score descending, equal scores
  * by ascending index (a stable argsort; the reference's np.argsort leaves the order of exact ties unspecified).
@@ -519,6 +519,38 @@ int mmt_search_rank(const float* qf, const float* qw, const float* gf, const flo
 int mmt_search_rank_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
                          int NQ, int NV, int M, int d, const int64_t* targets, int T, int32_t* ws, int32_t* greater,
                          int32_t* equal, void* stream);
+/* The same scans restricted to a subset of the stored items (search_subset.hip and the masked instantiations of the
+ * kernels above): the test cuts of one corpus ("full", "jsfusion", "miech": data_loader/msrvtt_dataset.py:27-47)
+ * and the padded captions of a multi-caption set (query_masks, model/metric.py:90-121, 153-243) without a second,
+ * gathered index per cut; and "the k best items, not counting the query's own" for the negatives of the max-margin
+ * loss (model/loss.py:29-65).
+ * subset: uint32 words, bit i & 31 of word i >> 5 = item i allowed; 4 * ceil(NV / 128) words (one 128-item scan tile =
+ *   one aligned 16-byte load), bits at or past NV zero, 16-byte aligned (else MMT_ERR_ALIGN).  A tile with no bit set is
+ *   skipped before its K loop.  Null = every item (the unmasked kernels run unless exclusions are given).
+ * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> those words, padding included: one ballot per 64 items,
+ *   one writer per word.
+ * mmt_search_topk_ex / mmt_search_topk_bf16_ex: mmt_search_topk / mmt_search_topk_bf16 over the allowed items less, per
+ *   query, the E items exclude[q][0 .. E - 1] (int64, -1 .. NV - 1, -1 = none; duplicates and items outside the subset
+ *   are fine).  0 <= E <= 32, and exclude non-null when E > 0, else MMT_ERR_ARG.  The score of a returned item has the
+ *   bits the unmasked search gives it: the mask acts at selection only.  Outputs [NQ][min(k, NV)] as before, but ONLY
+ *   the slots that have a candidate are written -- a query with fewer allowed items than that leaves the rest of its
+ *   row untouched (the caller prefills).  Workspace: mmt_topk_workspace_keys.
+ * mmt_search_rank_ex / mmt_search_rank_bf16_ex: greater / equal count allowed items only.  Thresholds come from the
+ *   unmasked threshold pass, so a target outside the subset is scored but does not count itself (equal may be 0).
+ *   Workspace: mmt_rank_workspace_ints. */
+int mmt_search_subset_pack(const uint8_t* mask, int NV, uint32_t* words, void* stream);
+int mmt_search_topk_ex(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                       int k, const uint32_t* subset, const int64_t* exclude, int E, uint64_t* ws, float* scores,
+                       int64_t* index, void* stream);
+int mmt_search_topk_bf16_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
+                            int NQ, int NV, int M, int d, int k, const uint32_t* subset, const int64_t* exclude, int E,
+                            uint64_t* ws, float* scores, int64_t* index, void* stream);
+int mmt_search_rank_ex(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                       const int64_t* targets, int T, const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal,
+                       void* stream);
+int mmt_search_rank_bf16_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
+                            int NQ, int NV, int M, int d, const int64_t* targets, int T, const uint32_t* subset, int32_t* ws,
+                            int32_t* greater, int32_t* equal, void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

@@ -22,6 +22,13 @@
 // No atomics, integer sums only, every slot has one writer: bit-reproducible.  LDS at T = 32: score tile / slab union +
 // 4 KiB query weights + 24 KiB thresholds and counters, against the 97 KiB of candidate lists of the top-k kernel at
 // k = 128; registers: the top-k kernel's K loop plus four counters.
+//
+// rank_kernel<BF16, false, true> is the masked count pass (mmt_search_rank_ex): only items whose bit is set in a packed
+// bitmap (search_subset.hip) are counted -- the live-column predicate ANDed with the tile's 128 bits, one block-uniform
+// 16-byte load per tile, and a tile without a set bit skipped before its K loop.  Thresholds and the reduce are the
+// unmasked ones, so a target outside the subset is still scored; it just does not count itself.
+#include <type_traits>
+
 #include "search_scan.h"
 
 #define RK_MAXT 32
@@ -38,6 +45,12 @@ struct RkArgs {
   int NQ, NV, M, K, T, chunk, n_qt, n_chunks;
 };
 
+// The masked count pass takes an argument type of its own, so the unmasked kernels keep their argument block (and with
+// it their code) byte for byte.
+struct RkMaskedArgs : RkArgs {
+  const uint32_t* subset;  // bit g & 31 of word g >> 5 allows item g (16-byte aligned)
+};
+
 template <bool BF16, class GRow>
 __device__ __forceinline__ void rk_tile(const RkArgs& a, unsigned char* smem, float* sS, const float* sQw, int q0, GRow grow,
                                         int tid, int wq, int wg, int l31, int h) {
@@ -52,8 +65,8 @@ __device__ __forceinline__ void rk_tile(const RkArgs& a, unsigned char* smem, fl
   __syncthreads();
 }
 
-template <bool BF16, bool THR>
-__global__ __launch_bounds__(256) void rank_kernel(RkArgs a) {
+template <bool BF16, bool THR, bool MASKED = false>
+__global__ __launch_bounds__(256) void rank_kernel(std::conditional_t<MASKED, RkMaskedArgs, RkArgs> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int kUnion = BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -87,10 +100,19 @@ __global__ __launch_bounds__(256) void rank_kernel(RkArgs a) {
       sCnt[2 * i] = 0;
       sCnt[2 * i + 1] = 0;
     }
+    if constexpr (MASKED) __syncthreads();  // every tile may be skipped: the counters are read below all the same
     for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
+      uint64_t m0 = ~0ull, m1 = ~0ull;
+      if constexpr (MASKED) {
+        const u32x4 w = *(const u32x4*)(a.subset + (g0 >> 5));
+        m0 = w[0] | (uint64_t)w[1] << 32;
+        m1 = w[2] | (uint64_t)w[3] << 32;
+        if (!(m0 | m1)) continue;  // block-uniform: nothing of this tile is counted
+      }
       rk_tile<BF16>(a, smem, sS, sQw, q0, [=](int r) { return g0 + r < g_end ? g0 + r : -1; }, tid, wq, wg, l31, h);
       // wave w owns rows 16w .. 16w + 15 for the whole block, so its counters need no barrier
-      const bool live0 = g0 + lane < g_end, live1 = g0 + 64 + lane < g_end;
+      const bool live0 = g0 + lane < g_end && (!MASKED || ((m0 >> lane) & 1ull));
+      const bool live1 = g0 + 64 + lane < g_end && (!MASKED || ((m1 >> lane) & 1ull));
       for (int rr = 0; rr < TK_Q / 4; ++rr) {
         const int row = wave * (TK_Q / 4) + rr;
         if (row >= rows_live) break;
@@ -145,10 +167,12 @@ int rk_chunks(int NQ, int NV) {
 
 // workspace (int32 units): thresholds [NQ][T] fp32, then (greater, equal) [NQ][T][n_chunks][2]
 template <bool BF16>
-int rk_launch(RkArgs a, int32_t* ws, int32_t* greater, int32_t* equal, hipStream_t s) {
+int rk_launch(RkMaskedArgs a, int32_t* ws, int32_t* greater, int32_t* equal, hipStream_t s) {
   constexpr size_t base = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + TK_QW_BYTES;
   static const bool attrs = [] {  // the T = 32 footprint of the bf16 kernel is exactly the 64 KiB default limit
     (void)hipFuncSetAttribute((const void*)rank_kernel<BF16, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(base + (size_t)TK_Q * RK_MAXT * 12));
+    (void)hipFuncSetAttribute((const void*)rank_kernel<BF16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)(base + (size_t)TK_Q * RK_MAXT * 12));
     return true;
   }();
@@ -159,8 +183,13 @@ int rk_launch(RkArgs a, int32_t* ws, int32_t* greater, int32_t* equal, hipStream
   a.thr = (float*)ws;
   a.cnt = ws + (int64_t)a.NQ * a.T;
   const int n_pt = (TK_Q * a.T + TK_G - 1) / TK_G;  // threshold tiles per query tile
-  hipLaunchKernelGGL((rank_kernel<BF16, true>), dim3(a.n_qt * n_pt), dim3(256), base + TK_G * 4, s, a);
-  hipLaunchKernelGGL((rank_kernel<BF16, false>), dim3(a.n_qt * a.n_chunks), dim3(256), base + (size_t)TK_Q * a.T * 12, s, a);
+  hipLaunchKernelGGL((rank_kernel<BF16, true>), dim3(a.n_qt * n_pt), dim3(256), base + TK_G * 4, s, (RkArgs)a);
+  if (a.subset)
+    hipLaunchKernelGGL((rank_kernel<BF16, false, true>), dim3(a.n_qt * a.n_chunks), dim3(256),
+                       base + (size_t)TK_Q * a.T * 12, s, a);
+  else
+    hipLaunchKernelGGL((rank_kernel<BF16, false>), dim3(a.n_qt * a.n_chunks), dim3(256), base + (size_t)TK_Q * a.T * 12, s,
+                       (RkArgs)a);
   const int64_t n = (int64_t)a.NQ * a.T;
   hipLaunchKernelGGL(rank_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.cnt, n, a.n_chunks, greater,
                      equal);
@@ -173,28 +202,41 @@ extern "C" int64_t mmt_rank_workspace_ints(int NQ, int NV, int T) {
   return (int64_t)NQ * T * (1 + 2 * (int64_t)rk_chunks(NQ, NV));
 }
 
-extern "C" int mmt_search_rank(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
-                               int d, const int64_t* targets, int T, int32_t* ws, int32_t* greater, int32_t* equal,
-                               void* stream) {
+extern "C" int mmt_search_rank_ex(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
+                                  int d, const int64_t* targets, int T, const uint32_t* subset, int32_t* ws,
+                                  int32_t* greater, int32_t* equal, void* stream) {
   if (!qf || !qw || !gf || !gw || !targets || !ws || !greater || !equal || !rk_args_ok(NQ, NV, T) || M <= 0 ||
       M > MMT_MAX_EXPERTS || d <= 0 || (d & 3))
     return MMT_ERR_ARG;
-  if (((uintptr_t)qf | (uintptr_t)gf) & 15) return MMT_ERR_ALIGN;
-  RkArgs a = {};
-  a.q = qf; a.qw = qw; a.g = gf; a.gw = gw; a.targets = targets;
+  if (((uintptr_t)qf | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  RkMaskedArgs a = {};
+  a.q = qf; a.qw = qw; a.g = gf; a.gw = gw; a.targets = targets; a.subset = subset;
   a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.T = T;
   return rk_launch<false>(a, ws, greater, equal, (hipStream_t)stream);
+}
+
+extern "C" int mmt_search_rank(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
+                               int d, const int64_t* targets, int T, int32_t* ws, int32_t* greater, int32_t* equal,
+                               void* stream) {
+  return mmt_search_rank_ex(qf, qw, gf, gw, NQ, NV, M, d, targets, T, nullptr, ws, greater, equal, stream);
+}
+
+extern "C" int mmt_search_rank_bf16_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                       const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T,
+                                       const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal,
+                                       void* stream) {
+  if (!q_hi || !q_lo || !qw || !gf || !gw || !targets || !ws || !greater || !equal || !rk_args_ok(NQ, NV, T) || M <= 0 ||
+      M > MMT_MAX_EXPERTS || d <= 0 || (d & 7))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)q_hi | (uintptr_t)q_lo | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  RkMaskedArgs a = {};
+  a.q = q_hi; a.q_lo = q_lo; a.qw = qw; a.g = gf; a.gw = gw; a.targets = targets; a.subset = subset;
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.T = T;
+  return rk_launch<true>(a, ws, greater, equal, (hipStream_t)stream);
 }
 
 extern "C" int mmt_search_rank_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
                                     const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T,
                                     int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
-  if (!q_hi || !q_lo || !qw || !gf || !gw || !targets || !ws || !greater || !equal || !rk_args_ok(NQ, NV, T) || M <= 0 ||
-      M > MMT_MAX_EXPERTS || d <= 0 || (d & 7))
-    return MMT_ERR_ARG;
-  if (((uintptr_t)q_hi | (uintptr_t)q_lo | (uintptr_t)gf) & 15) return MMT_ERR_ALIGN;
-  RkArgs a = {};
-  a.q = q_hi; a.q_lo = q_lo; a.qw = qw; a.g = gf; a.gw = gw; a.targets = targets;
-  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.T = T;
-  return rk_launch<true>(a, ws, greater, equal, (hipStream_t)stream);
+  return mmt_search_rank_bf16_ex(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, nullptr, ws, greater, equal, stream);
 }

@@ -5,6 +5,7 @@
 #include "search_scan.h"
 
 #define TK_MAXK 128
+#define TK_MAXE 32  // per-query exclusions of the masked instantiations
 
 __device__ __forceinline__ uint64_t tk_key(float s, int idx) {
   unsigned u = __float_as_uint(s);
@@ -62,19 +63,39 @@ __device__ __forceinline__ void tk_flush(uint64_t* c, int n, int k, int lane, ui
   for (int j = lane; j < k; j += 64) dst[j] = j < have ? c[j] : 0ull;
 }
 
-// Selection over the score tile: wave w owns rows 16w .. 16w + 15; columns in increasing index order.
+// Selection over the score tile: wave w owns rows 16w .. 16w + 15; columns in increasing index order.  MASKED: only the
+// columns whose bit is set in m0 (columns 0 .. 63) / m1 (64 .. 127) are candidates, less the row's exclusions sEx[row][E]
+// (item numbers, -1 = none; lane e holds exclusion e, and the few that fall into this tile clear their bit).  The score
+// tile is the unmasked kernel's, so a returned score has the bits the unmasked search gives that item.
+template <bool MASKED = false>
 __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, int* sN, uint64_t* sT, int k, int rows_live,
-                                               int g0, int g_end, int wave, int lane) {
+                                               int g0, int g_end, int wave, int lane, uint64_t m0 = 0, uint64_t m1 = 0,
+                                               const int* sEx = nullptr, int E = 0) {
   const int cap = k + 64;
   for (int rr = 0; rr < TK_Q / 4; ++rr) {
     const int row = wave * (TK_Q / 4) + rr;
     if (row >= rows_live) break;
     int n = sN[row];
     uint64_t thr = sT[row];
+    uint64_t a0 = m0, a1 = m1;
+    if constexpr (MASKED) {
+      if (E) {
+        const int mine = lane < E ? sEx[row * E + lane] : -1;
+        uint64_t hit = __ballot(mine >= g0 && mine < g0 + TK_G);
+        while (hit) {  // wave-uniform: one pass per exclusion inside this tile
+          const int c = __builtin_amdgcn_readlane(mine, __ffsll((unsigned long long)hit) - 1) - g0;
+          hit &= hit - 1;
+          if (c < 64) a0 &= ~(1ull << c);
+          else a1 &= ~(1ull << (c - 64));
+        }
+      }
+    }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       const int col = half * 64 + lane, g = g0 + col;
-      tk_push(sC + row * cap, n, thr, k, g < g_end ? tk_key(sS[row * TK_SLD + col], g) : 0ull, lane);
+      bool live = g < g_end;
+      if constexpr (MASKED) live = live && (((half ? a1 : a0) >> lane) & 1ull);
+      tk_push(sC + row * cap, n, thr, k, live ? tk_key(sS[row * TK_SLD + col], g) : 0ull, lane);
     }
     if (lane == 0) { sN[row] = n; sT[row] = thr; }
   }
@@ -83,5 +104,9 @@ __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, in
 // Host side (search.hip): the argument gate and the merge launch, shared by the fp32 and bf16 paths.
 bool tk_args_ok(int NQ, int NV, int k);
 size_t tk_state_lds(int k);  // LDS behind the slab / score-tile union: query weights, counts, thresholds, candidates
+size_t tk_exclude_lds(int E);  // ... and behind those, the masked kernels' exclusions [TK_Q][E]
+// The gate of the masked entry points: false with *rc = MMT_ERR_ARG (E outside 0 .. TK_MAXE, E > 0 without a list) or
+// MMT_ERR_ALIGN (subset words not 16-byte aligned; null = every item allowed).
+bool tk_mask_args_ok(const uint32_t* subset, const int64_t* exclude, int E, int* rc);
 int tk_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, float* scores, int64_t* index,
                     hipStream_t s);

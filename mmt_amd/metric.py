@@ -116,16 +116,35 @@ def v2t_targets(query_masks, num_videos, captions_per_video):
   return valid, targets.reshape(num_videos, captions_per_video)
 
 
-def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, query_masks=None, dtype=torch.float32):
+def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, query_masks=None, dtype=torch.float32,
+                              video_subset=None):
   """`retrieval_metrics` (same arguments, same result dict and keys) without the N_text x N_video matrix: the rank of every
   ground truth comes from search.VideoIndex.ranks, so no buffer grows with N_text * N_video.  t2v: an index of the videos
   queried with the real captions, the target of caption row b*C + c being video b.  v2t: an index of the real captions
   queried with the videos, each video's targets its own captions (`v2t_targets`), the best of their ranks kept (+inf for a
-  video without a real caption, as mmt_retrieval_ranks).  dtype: the index storage, torch.float32 or torch.bfloat16."""
+  video without a real caption, as mmt_retrieval_ranks).  dtype: the index storage, torch.float32 or torch.bfloat16.
+  video_subset (bool [B], or int64 video numbers in any order): the metrics of one cut of the set -- what this function
+  gives on the arrays gathered to the cut's videos in ascending order -- from the SAME two indexes over all videos and
+  all real captions (VideoIndex.subset): t2v queries are the real captions of the cut's videos and rank among the cut's
+  videos; v2t queries are the cut's videos and rank among the real captions of the cut."""
   from .search import VideoIndex
   b, m, d = vid_embds.shape
   c = text_embds.shape[2]
   valid, targets = v2t_targets(query_masks, b, c)
+  cut = None
+  if video_subset is not None:
+    vs = np.asarray(video_subset.cpu() if torch.is_tensor(video_subset) else video_subset)
+    if vs.dtype == bool:
+      if vs.shape != (b,):
+        raise ValueError('retrieval_metrics_indexed: a bool video_subset of shape (%d,) expected, got %s' % (b, vs.shape))
+      cut = vs
+    else:
+      if vs.dtype.kind not in 'iu' or vs.size and (vs.min() < 0 or vs.max() >= b):
+        raise ValueError('retrieval_metrics_indexed: video_subset must be a bool mask or video numbers in 0 .. %d' % (b - 1))
+      cut = np.zeros(b, dtype=bool)
+      cut[vs.reshape(-1)] = True
+    if not (valid & np.repeat(cut, c)).any():
+      raise ValueError('retrieval_metrics_indexed: video_subset leaves no caption to rank')
   if not valid.any():
     raise ValueError('retrieval_metrics_indexed: query_masks leaves no caption to rank')
   vid = _as_cuda_f32(vid_embds)
@@ -134,6 +153,18 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
   rows = torch.from_numpy(np.flatnonzero(valid)).to(vid.device)
   txt = txt4.permute(0, 2, 1, 3).reshape(b * c, m, d)[rows].contiguous()      # the real captions, rows b*C + c in order
   tw = _as_cuda_f32(text_weights).reshape(b * c, m)[rows].contiguous()
+  if cut is not None:
+    dev = vid.device
+    cut_d = torch.from_numpy(cut).to(dev)
+    mine = cut_d[rows // c]                                                     # real captions of the cut's videos
+    videos = VideoIndex(vid, vw, dtype=dtype)
+    cols = videos.ranks(txt[mine], tw[mine], (rows // c)[mine], subset=videos.subset(cut_d)).cpu().numpy()
+    out = {'t2v_metrics': dict(cols2metrics(cols, cols.size), cols=cols)}
+    captions = VideoIndex(txt, tw, dtype=dtype)
+    ranks = captions.ranks(vid[cut_d], vw[cut_d], torch.from_numpy(targets).to(dev)[cut_d], subset=captions.subset(mine))
+    cols = ranks.min(dim=1).values.cpu().numpy()
+    out['v2t_metrics'] = dict(cols2metrics(cols, cols.size), cols=cols)
+    return out
   cols = VideoIndex(vid, vw, dtype=dtype).ranks(txt, tw, rows // c).cpu().numpy()
   out = {'t2v_metrics': dict(cols2metrics(cols, cols.size), cols=cols)}
   ranks = VideoIndex(txt, tw, dtype=dtype).ranks(vid, vw, torch.from_numpy(targets).to(vid.device))

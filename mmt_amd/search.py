@@ -31,6 +31,20 @@ equal to it -- the same scan with a counter per (query, target) in place of the 
 no N_query x N_video matrix.  The target's own score is taken from the same scoring tile, bit for bit, so it always
 counts itself (equal >= 1) and `ranks` is the reference's tie-averaged 0-based rank; a target of -1 means "none" and
 gives 0 / 0 and rank +inf.  metric.retrieval_metrics_indexed builds the t2v / v2t metrics on it.
+
+    sub = index.subset(items)            # items: bool [num_items] or int64 ids (any order, duplicates allowed)
+    sub.count, sub.num_items, sub.words  # allowed items; the num_items it was built for; packed uint32 bitmap
+    scores, indices = index.search(q, qw, k=10, subset=sub, exclude=ex)
+    greater, equal = index.rank_counts(q, qw, targets, subset=sub)
+    ranks = index.ranks(q, qw, targets, subset=sub)
+
+One stored corpus answers for any subset of its items -- a test cut, the real captions of a padded set -- without a
+gathered copy: the subset is packed once into a bitmap (bit i & 31 of word i >> 5 is item i; mmt_search_subset_pack) and
+reused across calls; the scan skips every 128-item tile that holds no allowed item and otherwise only declines to select
+(or count) the items whose bit is clear (mmt_search_topk_ex, mmt_search_rank_ex).  Indices stay the original item
+numbers and a returned score has the bits plain `search` gives that item.  `exclude` ([NQ] or [NQ, E <= 32] int64, -1 =
+none) bars items per query -- "the k best videos for this caption, not counting its own" -- and a query left with fewer
+than k' candidates gets (-inf, -1) in the remaining slots.  subset=None and exclude=None take the unmasked calls.
 """
 import torch
 
@@ -39,6 +53,7 @@ from ._lib import check
 
 MAX_K = 128
 MAX_T = 32  # targets per query and launch of the rank kernels; wider target lists are sliced
+MAX_E = 32  # exclusions per query of a masked search
 _BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 bytes per element either way) + chunk lists
 _DTYPES = {torch.float32: 4, torch.bfloat16: 8}  # storage dtype -> multiple d must have (16-byte folded rows)
 
@@ -59,6 +74,21 @@ def _fold(x, w):
 def _check_dtype(dtype):
   if dtype not in _DTYPES:
     raise ValueError('VideoIndex: dtype must be torch.float32 or torch.bfloat16, got %r' % (dtype,))
+
+
+class IndexSubset:
+  """A set of items of a VideoIndex, packed for the masked scans (VideoIndex.subset): `words` is the uint32 bitmap on the
+  device (bit i & 31 of word i >> 5 is item i; 4 words per 128 items, padding bits zero), `mask` the same as bool
+  [num_items], `count` the number of allowed items, `num_items` the index size it was built for."""
+
+  def __init__(self, mask, count):
+    n = mask.shape[0]
+    self.num_items, self.device, self.mask, self.count = n, mask.device, mask, count
+    words = torch.empty(4 * -(-n // 128), device=mask.device, dtype=torch.int32)
+    with torch.cuda.device(mask.device):
+      check(_lib.lib().mmt_search_subset_pack(ops._p(mask.view(torch.uint8)), n, ops._p(words), ops._stream()),
+            'mmt_search_subset_pack')
+    self.words = words.view(torch.uint32)
 
 
 class VideoIndex:
@@ -157,18 +187,91 @@ class VideoIndex:
       raise ValueError('search: queries must be on the index device %s' % self.device)
     return q, qw
 
-  def search(self, embds, weights, k=10):
+  def subset(self, items):
+    """items: bool [num_items] (True = allowed) or int64 item numbers (any shape, any order, duplicates allowed), on the
+    index device -> IndexSubset for `search`, `rank_counts` and `ranks`.  Packed here, once; the range of the numbers is
+    checked (one small reduction and a host sync).  It describes the num_items of this moment: after a further `add` it
+    is refused.  Raises ValueError for an empty subset."""
+    if self.num_items == 0:
+      raise ValueError('subset: the index holds no items')
+    if not torch.is_tensor(items) or items.dtype not in (torch.bool, torch.int64):
+      raise ValueError('subset: items must be a bool or int64 tensor, got %s' % (
+          items.dtype if torch.is_tensor(items) else type(items).__name__))
+    if items.device != self.device:
+      raise ValueError('subset: items must be on the index device %s, got %s' % (self.device, items.device))
+    nv = self.num_items
+    if items.dtype == torch.bool:
+      if tuple(items.shape) != (nv,):
+        raise ValueError('subset: a bool mask of shape (%d,) expected, got %s' % (nv, tuple(items.shape)))
+      mask = items.contiguous().clone()
+    else:
+      ids = items.reshape(-1)
+      if ids.numel() == 0:
+        raise ValueError('subset: no item allowed')
+      lo, hi = (int(v) for v in torch.aminmax(ids))
+      if lo < 0 or hi >= nv:
+        raise ValueError('subset: items must lie in 0 .. %d, got %d .. %d' % (nv - 1, lo, hi))
+      mask = torch.zeros(nv, device=self.device, dtype=torch.bool).index_fill_(0, ids, True)
+    count = int(mask.sum())
+    if count == 0:
+      raise ValueError('subset: no item allowed')
+    return IndexSubset(mask, count)
+
+  def _subset(self, subset, who):
+    if not isinstance(subset, IndexSubset):
+      raise ValueError('%s: subset must come from VideoIndex.subset, got %s' % (who, type(subset).__name__))
+    if subset.num_items != self.num_items:
+      raise ValueError('%s: the subset was built for %d items, the index holds %d' % (who, subset.num_items, self.num_items))
+    if subset.device != self.device:
+      raise ValueError('%s: the subset is on %s, the index on %s' % (who, subset.device, self.device))
+
+  def _exclude(self, exclude):
+    """Type, device and width of `exclude`: all that can be said about it before the queries are known."""
+    if not torch.is_tensor(exclude) or exclude.dtype != torch.int64:
+      raise ValueError('search: exclude must be an int64 tensor, got %s' % (
+          exclude.dtype if torch.is_tensor(exclude) else type(exclude).__name__))
+    if exclude.dim() not in (1, 2) or exclude.dim() == 2 and not 1 <= exclude.shape[1] <= MAX_E:
+      raise ValueError('search: exclude [NQ] or [NQ, 1 <= E <= %d] expected, got %s' % (MAX_E, tuple(exclude.shape)))
+    if exclude.device != self.device:
+      raise ValueError('search: exclude must be on the index device %s, got %s' % (self.device, exclude.device))
+
+  def search(self, embds, weights, k=10, subset=None, exclude=None):
     """Queries (NQ, M, d) / (NQ, M), or the text layout (B, M, C, d) / (B, C, M) -> (scores [NQ, k'] float32,
-    indices [NQ, k'] int64) on the device, k' = min(k, NV), best first."""
+    indices [NQ, k'] int64) on the device, k' = min(k, NV), best first.  subset (VideoIndex.subset): only its items are
+    candidates and k' = min(k, subset.count).  exclude: int64 [NQ] or [NQ, E <= 32] on the index device, values
+    -1 .. num_items - 1 (-1 = none; duplicates and items outside the subset are fine): items barred for that query; its
+    range is checked as that of `rank_counts`' targets, before anything is scored.  A query with fewer than k' candidates
+    left gets score -inf and index -1 in the remaining slots."""
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
       raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
     if self.num_items == 0:
       raise ValueError('search: the index holds no items')
+    if subset is not None:
+      self._subset(subset, 'search')
+    if exclude is not None:
+      self._exclude(exclude)
     q, qw = self._queries(embds, weights)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    masked = ()  # the extra arguments of the _ex entry points: subset words, exclusions of the batch, E
+    if subset is not None or exclude is not None:
+      k = min(k, nv if subset is None else subset.count)  # lists no longer than the candidates: the outputs stay dense
+      ex = None
+      if exclude is not None:
+        if exclude.shape[0] != nq:
+          raise ValueError('search: %d queries but exclude %s' % (nq, tuple(exclude.shape)))
+        ex = exclude.reshape(nq, -1).contiguous()
+        if nq:
+          lo, hi = (int(v) for v in torch.aminmax(ex))
+          if lo < -1 or hi >= nv:
+            raise ValueError('search: exclude must lie in -1 .. %d, got %d .. %d' % (nv - 1, lo, hi))
+      masked = (None if subset is None else subset.words, ex, 0 if ex is None else ex.shape[1])
     kout = min(k, nv)
-    scores = torch.empty(nq, kout, device=self.device, dtype=torch.float32)
-    indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
+    if exclude is None:
+      scores = torch.empty(nq, kout, device=self.device, dtype=torch.float32)
+      indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
+    else:  # the merge writes only the slots that have a candidate
+      scores = torch.full((nq, kout), float('-inf'), device=self.device, dtype=torch.float32)
+      indices = torch.full((nq, kout), -1, device=self.device, dtype=torch.int64)
     if nq == 0:
       return scores, indices
     L = _lib.lib()
@@ -179,17 +282,22 @@ class VideoIndex:
         r1 = min(nq, r0 + batch)
         n = r1 - r0
         ws = torch.empty(L.mmt_topk_workspace_keys(n, nv, k), device=self.device, dtype=torch.int64)
-        out = (n, nv, m, d, k, ops._p(ws), ops._p(scores[r0:r1]), ops._p(indices[r0:r1]), ops._stream())
+        out = (ops._p(ws), ops._p(scores[r0:r1]), ops._p(indices[r0:r1]), ops._stream())
+        if masked:
+          words, ex, e = masked
+          out = (ops._p(words), ops._p(None if ex is None else ex[r0:r1]), e) + out
+        out = (n, nv, m, d, k) + out
         if self.dtype == torch.bfloat16:
           hl = torch.empty(2, n, m * d, device=self.device, dtype=torch.bfloat16)  # hi = bf16(qf), lo = bf16(qf - hi)
           check(L.mmt_search_fold_split_bf16(ops._p(q[r0:r1]), ops._p(qw[r0:r1]), n, m, d, ops._p(hl[0]), ops._p(hl[1]),
                                              ops._stream()), 'mmt_search_fold_split_bf16')
-          check(L.mmt_search_topk_bf16(ops._p(hl[0]), ops._p(hl[1]), ops._p(qw[r0:r1]), ops._p(self.folded),
-                                       ops._p(self.weights), *out), 'mmt_search_topk_bf16')
+          fn = L.mmt_search_topk_bf16_ex if masked else L.mmt_search_topk_bf16
+          check(fn(ops._p(hl[0]), ops._p(hl[1]), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights), *out),
+                'mmt_search_topk_bf16')
         else:
           qf = _fold(q[r0:r1], qw[r0:r1])
-          check(L.mmt_search_topk(ops._p(qf), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights), *out),
-                'mmt_search_topk')
+          fn = L.mmt_search_topk_ex if masked else L.mmt_search_topk
+          check(fn(ops._p(qf), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights), *out), 'mmt_search_topk')
     return scores, indices
 
   def _targets(self, targets):
@@ -202,14 +310,18 @@ class VideoIndex:
     if targets.dim() not in (1, 2) or targets.dim() == 2 and targets.shape[1] < 1:
       raise ValueError('ranks: targets [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(targets.shape),))
 
-  def rank_counts(self, embds, weights, targets):
+  def rank_counts(self, embds, weights, targets, subset=None):
     """Queries as for `search`; targets [NQ] or [NQ, T] int64 on the index device, values -1 .. num_items - 1 ->
     (greater, equal), int32 of targets' shape: how many of the num_items stored items score above / exactly equal to item
     targets[q, t] for query q (the item itself is one of the equal ones); 0 / 0 where the target is -1.  The range of the
-    targets is checked here (one small reduction and a host sync); nothing is scored before it passes."""
+    targets is checked here (one small reduction and a host sync); nothing is scored before it passes.  subset
+    (VideoIndex.subset): only its items are counted; a target outside it is still scored but does not count itself, so
+    its `equal` may be 0."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
+    if subset is not None:
+      self._subset(subset, 'ranks')
     q, qw = self._queries(embds, weights)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     if targets.shape[0] != nq:
@@ -248,16 +360,25 @@ class VideoIndex:
           gs = greater[r0:r1] if whole else torch.empty(n, t1 - t0, device=self.device, dtype=torch.int32)
           es = equal[r0:r1] if whole else torch.empty_like(gs)
           fn, name = (L.mmt_search_rank_bf16, 'mmt_search_rank_bf16') if bf16 else (L.mmt_search_rank, 'mmt_search_rank')
-          check(fn(*operands, n, nv, m, d, ops._p(tgs), t1 - t0, ops._p(ws), ops._p(gs), ops._p(es), ops._stream()), name)
+          if subset is None:
+            check(fn(*operands, n, nv, m, d, ops._p(tgs), t1 - t0, ops._p(ws), ops._p(gs), ops._p(es), ops._stream()), name)
+          else:
+            fn = L.mmt_search_rank_bf16_ex if bf16 else L.mmt_search_rank_ex
+            check(fn(*operands, n, nv, m, d, ops._p(tgs), t1 - t0, ops._p(subset.words), ops._p(ws), ops._p(gs), ops._p(es),
+                     ops._stream()), name)
           if not whole:
             greater[r0:r1, t0:t1] = gs
             equal[r0:r1, t0:t1] = es
     return greater.reshape(shape), equal.reshape(shape)
 
-  def ranks(self, embds, weights, targets):
+  def ranks(self, embds, weights, targets, subset=None):
     """The reference's tie-averaged 0-based rank (model/metric.py:90-121) of item targets[q, t] among the stored items for
     query q: greater + (equal - 1) / 2 from `rank_counts`, +inf where the target is -1.  float64 on the device, of
-    targets' shape (float32 would not hold counts above 2^24)."""
-    greater, equal = self.rank_counts(embds, weights, targets)
+    targets' shape (float32 would not hold counts above 2^24).  subset: the rank among its items, +inf for a target that
+    is not one of them."""
+    greater, equal = self.rank_counts(embds, weights, targets, subset=subset)
     ranks = greater.double() + (equal.double() - 1) / 2
-    return torch.where(targets < 0, torch.full_like(ranks, float('inf')), ranks)
+    none = targets < 0
+    if subset is not None:
+      none = none | ~subset.mask[targets.clamp(min=0)]
+    return torch.where(none, torch.full_like(ranks, float('inf')), ranks)

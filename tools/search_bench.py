@@ -20,7 +20,13 @@ index lists agree.  The bf16 index is built in chunks (VideoIndex.empty + add).
 search(k = 1) and search(k = 10) on the same index -- the same scan with the top-k epilogue, the yardstick -- and beside
 the materialised path (mmt_sims_eval + mmt_retrieval_ranks: the N_query x N_video matrix, then its ranking) where that
 path applies (it wants NQ = NV x captions, so S1 and S2).  --runs rounds, every variant once per round, interleaved;
-median and spread.  Default output profiles/search_ranks_bench.json."""
+median and spread.  Default output profiles/search_ranks_bench.json.
+
+--subset FRACTION and / or --exclude E time the masked search (VideoIndex.search(subset=, exclude=)) beside the unmasked
+one on the same index (--gallery-dtype, both = the two indexes): an all-ones subset (the cost of the predicate), a
+contiguous FRACTION of the items (whole tiles skipped: the time should follow the fraction), a random FRACTION (no tile
+skips: as all-ones), and E exclusions per query without a subset (the query's own item and E - 1 random ones).  --runs
+rounds, every variant once per round, interleaved; median and spread.  Default output profiles/search_subset_bench.json."""
 import argparse
 import json
 import math
@@ -173,6 +179,42 @@ def ranks_mode(q, qw, g, gw, flop, a):
   return row
 
 
+def subset_mode(q, qw, g, gw, flop, a):
+  """Masked search against the unmasked one, per index dtype."""
+  nq, nv = q.shape[0], g.shape[0]
+  dtypes = ('float32', 'bfloat16') if a.gallery_dtype == 'both' else (a.gallery_dtype,)
+  gen = torch.Generator(device=q.device).manual_seed(1)
+  fns = {}
+  for n in dtypes:
+    index = VideoIndex.empty(nv, M, D, g.device, dtype=getattr(torch, n))
+    for at in range(0, nv, 8192):
+      index.add(g[at:at + 8192], gw[at:at + 8192])
+    fns[n + '/unmasked'] = lambda index=index: index.search(q, qw, k=K)
+    if a.subset is not None:
+      count = max(1, int(round(a.subset * nv)))
+      subs = {'all_ones': torch.ones(nv, device=q.device, dtype=torch.bool),
+              'contiguous': torch.arange(nv, device=q.device) < count,
+              'random': torch.rand(nv, device=q.device, generator=gen) < a.subset}
+      for name, mask in subs.items():
+        sub = index.subset(mask)
+        fns['%s/subset_%s' % (n, name)] = lambda index=index, sub=sub: index.search(q, qw, k=K, subset=sub)
+    if a.exclude:
+      ex = torch.randint(0, nv, (nq, a.exclude), device=q.device, generator=gen)
+      ex[:, 0] = torch.arange(nq, device=q.device) % nv   # the item each query was drawn around (main)
+      fns['%s/exclude_%d' % (n, a.exclude)] = lambda index=index, ex=ex: index.search(q, qw, k=K, exclude=ex)
+  ts = {n: [] for n in fns}
+  for _ in range(a.runs):
+    for n, fn in fns.items():
+      ts[n].append(timed(fn, a.min_seconds)[0])
+  row = {}
+  for n in fns:
+    med = float(np.median(ts[n]))
+    base = float(np.median(ts[n.split('/')[0] + '/unmasked']))
+    row[n] = dict(seconds_median=med, seconds_min=min(ts[n]), seconds_max=max(ts[n]), seconds_runs=ts[n],
+                  over_unmasked=med / base, tflops_of_the_full_scan=flop / med / 1e12)
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--shapes', default='S1,S2,S3')
@@ -183,7 +225,18 @@ def main():
   ap.add_argument('--runs', type=int, default=5, help='timed runs per index with --gallery-dtype both')
   ap.add_argument('--ranks', action='store_true', help='time VideoIndex.ranks (T = 1) against search(k = 1) and the '
                   'materialised ranking, both gallery dtypes')
+  ap.add_argument('--subset', type=float, default=None, metavar='FRACTION', help='time search(subset=) with an all-ones, '
+                  'a contiguous and a random subset of this fraction of the items against the unmasked search')
+  ap.add_argument('--exclude', type=int, default=0, metavar='E', help='time search(exclude=) with E (1..32) exclusions per '
+                  'query against the unmasked search')
   a = ap.parse_args()
+  masked = a.subset is not None or a.exclude > 0
+  if a.subset is not None and not 0 < a.subset <= 1:
+    raise SystemExit('--subset wants a fraction in (0, 1]')
+  if not 0 <= a.exclude <= 32:
+    raise SystemExit('--exclude wants 0..32')
+  if masked and a.out is None:
+    a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_subset_bench.json')
   if a.ranks and a.out is None:
     a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_ranks_bench.json')
   if not torch.cuda.is_available():
@@ -194,6 +247,8 @@ def main():
     res['gallery_dtype'] = a.gallery_dtype
   if a.ranks:
     res.update(mode='ranks', T=1, runs=a.runs, min_seconds=a.min_seconds)
+  if masked:
+    res.update(mode='subset', subset_fraction=a.subset, exclude=a.exclude, runs=a.runs, min_seconds=a.min_seconds)
   for name in a.shapes.split(','):
     nq, nv = SHAPES[name]
     gen = torch.Generator(device=dev).manual_seed(0)
@@ -204,8 +259,9 @@ def main():
     qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
     flop = 2.0 * nq * nv * M * D
     row = {'NQ': nq, 'NV': nv, 'flop': flop}
-    if a.ranks or a.gallery_dtype == 'both':
-      row.update(ranks_mode(q, qw, g, gw, flop, a) if a.ranks else both_dtypes(q, qw, g, gw, flop, a))
+    if masked or a.ranks or a.gallery_dtype == 'both':
+      mode = subset_mode if masked else ranks_mode if a.ranks else both_dtypes
+      row.update(mode(q, qw, g, gw, flop, a))
       res['shapes'][name] = row
       print(name, json.dumps(row), flush=True)
       del g, gw, q, qw
