@@ -465,7 +465,7 @@ int mmt_sims_eval(const float* txt, const float* vid, const float* tw, const flo
 int mmt_retrieval_ranks(const float* sims, const uint8_t* qmask, int NQ, int NV, float* t2v_rank, float* v2t_rank,
                         float* scratch, void* stream);
 
-/* ---- top-k retrieval (search.hip, search_bf16.hip, search_rank.hip, search_subset.hip, fold in retrieval.hip) --------------------------------------
+/* ---- top-k retrieval (search.hip, search_bf16.hip, search_rank.hip, search_subset.hip, search_shard.hip, fold in retrieval.hip) --------------------------------------
  * score(q, g) = sum_m qw[q][m] gw[g][m] <Q_m[q], G_m[g]> / sum_m qw[q][m] gw[g][m] (0 -> 1e-5), the 'indep' similarity
  * of model/model.py:789-837.  Per query the min(k, NV) best (score, gallery index) pairs, score descending, equal scores
  * by ascending index (a stable argsort; the reference's np.argsort leaves the order of exact ties unspecified).
@@ -551,6 +551,42 @@ int mmt_search_rank_ex(const float* qf, const float* qw, const float* gf, const 
 int mmt_search_rank_bf16_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
                             int NQ, int NV, int M, int d, const int64_t* targets, int T, const uint32_t* subset, int32_t* ws,
                             int32_t* greater, int32_t* equal, void* stream);
+/* One gallery cut into shards, each an index of its own with item numbers of its own (search.py: ShardedVideoIndex; the
+ * 8-GPU node of trainer/trainer.py's evaluation over a corpus that does not fit one card).  score(q, g) has the same
+ * bits wherever item g is stored and whatever NV is, so the shards' answers combine exactly:
+ * mmt_search_thresholds / mmt_search_thresholds_bf16: the threshold pass of mmt_search_rank / _bf16 alone --
+ *   thr[q][t] = score(q, targets[q][t]) as fp32 [NQ][T], NaN for a target outside 0 .. NV - 1 (-1 = none; checked on the
+ *   device, never dereferenced).  Operands and gates (MMT_ERR_ARG, MMT_ERR_ALIGN) as mmt_search_rank / _bf16.
+ * mmt_search_count / mmt_search_count_bf16: the count pass and the chunk reduce against GIVEN thresholds thr [NQ][T]:
+ *   greater / equal int32 [NQ][T] over the NV items (plain float compares; a NaN threshold counts nothing).  subset
+ *   (nullable, words as above): only allowed items count.  So a target scored on the shard that holds it is counted on
+ *   every shard and the int32 counts add up to those of one index over all items.
+ * mmt_count_workspace_ints: int32 workspace of the two, NQ * T * 2 * ceil(NV / chunk); MMT_ERR_ARG as
+ *   mmt_rank_workspace_ints.
+ * mmt_search_merge_lists (search_shard.hip): per query, S lists of kin (score, shard-local item) pairs -- scores fp32 /
+ *   index int64 [S][NQ][kin], index -1 = empty slot -- and ids, a device array of S device pointers, ids[s] the int64
+ *   local -> global item table of shard s -> the best kout of them as scores fp32 / index int64 (global) [NQ][kout]: score
+ *   descending, equal scores (-0 == +0) by ascending global item, slots without a candidate (-inf, -1).  Each list must be
+ *   best-first under that order with its empty slots last (true of a shard whose table is increasing).  1 <= S <= 32,
+ *   1 <= kin, kout <= 128 (kout may exceed S * kin), else MMT_ERR_ARG.  A returned score has the bits of the input score.
+ *   One block per query, the lists as keys in LDS, rank by binary search; no atomics, one writer per slot.  Every
+ *   pointer, the S tables behind ids included, is memory of the device the kernel is launched on (ShardedVideoIndex keeps
+ *   the tables on its primary device and copies the shards' lists there).  Trusted, not checked: every index value is
+ *   -1 or below the length of its list's table, and every global item number is below 2^31 (the key holds it as int). */
+int64_t mmt_count_workspace_ints(int NQ, int NV, int T);
+int mmt_search_thresholds(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                          const int64_t* targets, int T, float* thr, void* stream);
+int mmt_search_thresholds_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                               const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T, float* thr,
+                               void* stream);
+int mmt_search_count(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                     const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal,
+                     void* stream);
+int mmt_search_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
+                          int NQ, int NV, int M, int d, const float* thr, int T, const uint32_t* subset, int32_t* ws,
+                          int32_t* greater, int32_t* equal, void* stream);
+int mmt_search_merge_lists(const float* scores, const int64_t* index, const int64_t* const* ids, int S, int NQ, int kin,
+                           int kout, float* out_scores, int64_t* out_index, void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

@@ -27,6 +27,10 @@
 // bitmap (search_subset.hip) are counted -- the live-column predicate ANDed with the tile's 128 bits, one block-uniform
 // 16-byte load per tile, and a tile without a set bit skipped before its K loop.  Thresholds and the reduce are the
 // unmasked ones, so a target outside the subset is still scored; it just does not count itself.
+//
+// mmt_search_thresholds / mmt_search_count (and their bf16 forms) launch the threshold pass alone and the count pass +
+// reduce against given thresholds: the same instantiations with the same argument blocks.  A gallery cut into shards
+// scores a target where it is stored and counts it on every shard (search.py: ShardedVideoIndex); the int32 counts add.
 #include <type_traits>
 
 #include "search_scan.h"
@@ -165,18 +169,28 @@ int rk_chunks(int NQ, int NV) {
   return (NV + chunk - 1) / chunk;
 }
 
+// The count kernels' dynamic LDS limit, raised once on every device they are launched on (the T = 32 footprint of the bf16
+// kernel is exactly the 64 KiB default limit).  A function attribute belongs to the device that is current when it is set,
+// and a gallery cut into shards launches these kernels on several.  Two threads meeting here set the same value twice.
+template <bool BF16>
+void rk_count_attrs() {
+  constexpr size_t base = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + TK_QW_BYTES;
+  static bool done[64] = {};
+  int dev = -1;
+  const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;  // beyond the table: set every time
+  if (known && done[dev]) return;
+  (void)hipFuncSetAttribute((const void*)rank_kernel<BF16, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(base + (size_t)TK_Q * RK_MAXT * 12));
+  (void)hipFuncSetAttribute((const void*)rank_kernel<BF16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(base + (size_t)TK_Q * RK_MAXT * 12));
+  if (known) done[dev] = true;
+}
+
 // workspace (int32 units): thresholds [NQ][T] fp32, then (greater, equal) [NQ][T][n_chunks][2]
 template <bool BF16>
 int rk_launch(RkMaskedArgs a, int32_t* ws, int32_t* greater, int32_t* equal, hipStream_t s) {
   constexpr size_t base = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + TK_QW_BYTES;
-  static const bool attrs = [] {  // the T = 32 footprint of the bf16 kernel is exactly the 64 KiB default limit
-    (void)hipFuncSetAttribute((const void*)rank_kernel<BF16, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(base + (size_t)TK_Q * RK_MAXT * 12));
-    (void)hipFuncSetAttribute((const void*)rank_kernel<BF16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(base + (size_t)TK_Q * RK_MAXT * 12));
-    return true;
-  }();
-  (void)attrs;
+  rk_count_attrs<BF16>();
   a.chunk = tk_chunk(a.NQ, a.NV);
   a.n_qt = (a.NQ + TK_Q - 1) / TK_Q;
   a.n_chunks = (a.NV + a.chunk - 1) / a.chunk;
@@ -184,6 +198,41 @@ int rk_launch(RkMaskedArgs a, int32_t* ws, int32_t* greater, int32_t* equal, hip
   a.cnt = ws + (int64_t)a.NQ * a.T;
   const int n_pt = (TK_Q * a.T + TK_G - 1) / TK_G;  // threshold tiles per query tile
   hipLaunchKernelGGL((rank_kernel<BF16, true>), dim3(a.n_qt * n_pt), dim3(256), base + TK_G * 4, s, (RkArgs)a);
+  if (a.subset)
+    hipLaunchKernelGGL((rank_kernel<BF16, false, true>), dim3(a.n_qt * a.n_chunks), dim3(256),
+                       base + (size_t)TK_Q * a.T * 12, s, a);
+  else
+    hipLaunchKernelGGL((rank_kernel<BF16, false>), dim3(a.n_qt * a.n_chunks), dim3(256), base + (size_t)TK_Q * a.T * 12, s,
+                       (RkArgs)a);
+  const int64_t n = (int64_t)a.NQ * a.T;
+  hipLaunchKernelGGL(rank_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.cnt, n, a.n_chunks, greater,
+                     equal);
+  return (int)hipGetLastError();
+}
+
+// The two halves of rk_launch on their own (a gallery cut into shards scores a target on the shard that holds it and
+// counts it on every shard: search.py, ShardedVideoIndex): the same kernels, launched as above.
+template <bool BF16>
+int rk_launch_thresholds(RkMaskedArgs a, float* thr, hipStream_t s) {
+  constexpr size_t base = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + TK_QW_BYTES;
+  a.chunk = tk_chunk(a.NQ, a.NV);
+  a.n_qt = (a.NQ + TK_Q - 1) / TK_Q;
+  a.n_chunks = (a.NV + a.chunk - 1) / a.chunk;
+  a.thr = thr;
+  const int n_pt = (TK_Q * a.T + TK_G - 1) / TK_G;
+  hipLaunchKernelGGL((rank_kernel<BF16, true>), dim3(a.n_qt * n_pt), dim3(256), base + TK_G * 4, s, (RkArgs)a);
+  return (int)hipGetLastError();
+}
+
+// workspace (int32 units): (greater, equal) [NQ][T][n_chunks][2]; a.thr is the caller's
+template <bool BF16>
+int rk_launch_count(RkMaskedArgs a, int32_t* ws, int32_t* greater, int32_t* equal, hipStream_t s) {
+  constexpr size_t base = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + TK_QW_BYTES;
+  rk_count_attrs<BF16>();
+  a.chunk = tk_chunk(a.NQ, a.NV);
+  a.n_qt = (a.NQ + TK_Q - 1) / TK_Q;
+  a.n_chunks = (a.NV + a.chunk - 1) / a.chunk;
+  a.cnt = ws;
   if (a.subset)
     hipLaunchKernelGGL((rank_kernel<BF16, false, true>), dim3(a.n_qt * a.n_chunks), dim3(256),
                        base + (size_t)TK_Q * a.T * 12, s, a);
@@ -239,4 +288,60 @@ extern "C" int mmt_search_rank_bf16(const uint16_t* q_hi, const uint16_t* q_lo, 
                                     const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T,
                                     int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
   return mmt_search_rank_bf16_ex(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, nullptr, ws, greater, equal, stream);
+}
+
+extern "C" int64_t mmt_count_workspace_ints(int NQ, int NV, int T) {
+  if (!rk_args_ok(NQ, NV, T)) return MMT_ERR_ARG;
+  return (int64_t)NQ * T * 2 * (int64_t)rk_chunks(NQ, NV);
+}
+
+extern "C" int mmt_search_thresholds(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
+                                     int M, int d, const int64_t* targets, int T, float* thr, void* stream) {
+  if (!qf || !qw || !gf || !gw || !targets || !thr || !rk_args_ok(NQ, NV, T) || M <= 0 || M > MMT_MAX_EXPERTS || d <= 0 ||
+      (d & 3))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)qf | (uintptr_t)gf) & 15) return MMT_ERR_ALIGN;
+  RkMaskedArgs a = {};
+  a.q = qf; a.qw = qw; a.g = gf; a.gw = gw; a.targets = targets;
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.T = T;
+  return rk_launch_thresholds<false>(a, thr, (hipStream_t)stream);
+}
+
+extern "C" int mmt_search_thresholds_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                          const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T,
+                                          float* thr, void* stream) {
+  if (!q_hi || !q_lo || !qw || !gf || !gw || !targets || !thr || !rk_args_ok(NQ, NV, T) || M <= 0 ||
+      M > MMT_MAX_EXPERTS || d <= 0 || (d & 7))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)q_hi | (uintptr_t)q_lo | (uintptr_t)gf) & 15) return MMT_ERR_ALIGN;
+  RkMaskedArgs a = {};
+  a.q = q_hi; a.q_lo = q_lo; a.qw = qw; a.g = gf; a.gw = gw; a.targets = targets;
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.T = T;
+  return rk_launch_thresholds<true>(a, thr, (hipStream_t)stream);
+}
+
+extern "C" int mmt_search_count(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
+                                int d, const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
+                                int32_t* equal, void* stream) {
+  if (!qf || !qw || !gf || !gw || !thr || !ws || !greater || !equal || !rk_args_ok(NQ, NV, T) || M <= 0 ||
+      M > MMT_MAX_EXPERTS || d <= 0 || (d & 3))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)qf | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  RkMaskedArgs a = {};
+  a.q = qf; a.qw = qw; a.g = gf; a.gw = gw; a.thr = const_cast<float*>(thr); a.subset = subset;
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.T = T;
+  return rk_launch_count<false>(a, ws, greater, equal, (hipStream_t)stream);
+}
+
+extern "C" int mmt_search_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                     const float* gw, int NQ, int NV, int M, int d, const float* thr, int T,
+                                     const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
+  if (!q_hi || !q_lo || !qw || !gf || !gw || !thr || !ws || !greater || !equal || !rk_args_ok(NQ, NV, T) || M <= 0 ||
+      M > MMT_MAX_EXPERTS || d <= 0 || (d & 7))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)q_hi | (uintptr_t)q_lo | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  RkMaskedArgs a = {};
+  a.q = q_hi; a.q_lo = q_lo; a.qw = qw; a.g = gf; a.gw = gw; a.thr = const_cast<float*>(thr); a.subset = subset;
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.T = T;
+  return rk_launch_count<true>(a, ws, greater, equal, (hipStream_t)stream);
 }

@@ -117,7 +117,7 @@ def v2t_targets(query_masks, num_videos, captions_per_video):
 
 
 def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, query_masks=None, dtype=torch.float32,
-                              video_subset=None):
+                              video_subset=None, devices=None):
   """`retrieval_metrics` (same arguments, same result dict and keys) without the N_text x N_video matrix: the rank of every
   ground truth comes from search.VideoIndex.ranks, so no buffer grows with N_text * N_video.  t2v: an index of the videos
   queried with the real captions, the target of caption row b*C + c being video b.  v2t: an index of the real captions
@@ -126,8 +126,17 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
   video_subset (bool [B], or int64 video numbers in any order): the metrics of one cut of the set -- what this function
   gives on the arrays gathered to the cut's videos in ascending order -- from the SAME two indexes over all videos and
   all real captions (VideoIndex.subset): t2v queries are the real captions of the cut's videos and rank among the cut's
-  videos; v2t queries are the cut's videos and rank among the real captions of the cut."""
-  from .search import VideoIndex
+  videos; v2t queries are the cut's videos and rank among the real captions of the cut.
+  devices (a list of CUDA devices): both indexes are search.ShardedVideoIndex over those devices, the arrays and the
+  ranking on devices[0]; the result is the same, bit for bit."""
+  from .search import ShardedVideoIndex, VideoIndex
+  if devices is None:
+    make_index = VideoIndex
+  else:
+    devices = [torch.device(dev) for dev in devices]
+
+    def make_index(embds, weights, dtype):
+      return ShardedVideoIndex(embds, weights, devices, dtype=dtype)
   b, m, d = vid_embds.shape
   c = text_embds.shape[2]
   valid, targets = v2t_targets(query_masks, b, c)
@@ -150,24 +159,27 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
   vid = _as_cuda_f32(vid_embds)
   txt4 = _as_cuda_f32(text_embds)
   vw = _as_cuda_f32(vid_weights).reshape(b, m).contiguous()
+  tw = _as_cuda_f32(text_weights).reshape(b * c, m)
+  if devices is not None:
+    vid, txt4, vw, tw = (x.to(devices[0]) for x in (vid, txt4, vw, tw))
   rows = torch.from_numpy(np.flatnonzero(valid)).to(vid.device)
   txt = txt4.permute(0, 2, 1, 3).reshape(b * c, m, d)[rows].contiguous()      # the real captions, rows b*C + c in order
-  tw = _as_cuda_f32(text_weights).reshape(b * c, m)[rows].contiguous()
+  tw = tw[rows].contiguous()
   if cut is not None:
     dev = vid.device
     cut_d = torch.from_numpy(cut).to(dev)
     mine = cut_d[rows // c]                                                     # real captions of the cut's videos
-    videos = VideoIndex(vid, vw, dtype=dtype)
+    videos = make_index(vid, vw, dtype=dtype)
     cols = videos.ranks(txt[mine], tw[mine], (rows // c)[mine], subset=videos.subset(cut_d)).cpu().numpy()
     out = {'t2v_metrics': dict(cols2metrics(cols, cols.size), cols=cols)}
-    captions = VideoIndex(txt, tw, dtype=dtype)
+    captions = make_index(txt, tw, dtype=dtype)
     ranks = captions.ranks(vid[cut_d], vw[cut_d], torch.from_numpy(targets).to(dev)[cut_d], subset=captions.subset(mine))
     cols = ranks.min(dim=1).values.cpu().numpy()
     out['v2t_metrics'] = dict(cols2metrics(cols, cols.size), cols=cols)
     return out
-  cols = VideoIndex(vid, vw, dtype=dtype).ranks(txt, tw, rows // c).cpu().numpy()
+  cols = make_index(vid, vw, dtype=dtype).ranks(txt, tw, rows // c).cpu().numpy()
   out = {'t2v_metrics': dict(cols2metrics(cols, cols.size), cols=cols)}
-  ranks = VideoIndex(txt, tw, dtype=dtype).ranks(vid, vw, torch.from_numpy(targets).to(vid.device))
+  ranks = make_index(txt, tw, dtype=dtype).ranks(vid, vw, torch.from_numpy(targets).to(vid.device))
   cols = ranks.min(dim=1).values.cpu().numpy()
   out['v2t_metrics'] = dict(cols2metrics(cols, cols.size), cols=cols)
   return out

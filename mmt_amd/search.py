@@ -45,6 +45,21 @@ reused across calls; the scan skips every 128-item tile that holds no allowed it
 numbers and a returned score has the bits plain `search` gives that item.  `exclude` ([NQ] or [NQ, E <= 32] int64, -1 =
 none) bars items per query -- "the k best videos for this caption, not counting its own" -- and a query left with fewer
 than k' candidates gets (-inf, -1) in the remaining slots.  subset=None and exclude=None take the unmasked calls.
+
+    thr = index.target_scores(q, qw, targets)                    # float32, NaN for -1: score(q, target), the scan's bits
+    greater, equal = index.threshold_counts(q, qw, thr, subset=None)
+
+The two halves of `rank_counts` on their own (mmt_search_thresholds, mmt_search_count): what lets a gallery be cut up.
+
+    index = ShardedVideoIndex(vid_embds, vid_weights, devices=['cuda:0', 'cuda:1', ...], dtype=...)   # or .empty + add
+    index.search(...), index.rank_counts(...), index.ranks(...), index.subset(...)    # as VideoIndex, on devices[0]
+    index.num_items, index.capacity, index.dtype, index.nbytes, index.devices, index.shard_sizes
+
+One gallery held as one VideoIndex per entry of `devices` (up to 32; a device may repeat), for a corpus beyond one card's
+memory or a scan at the rate of several cards.  Item numbers are global insertion order and every result is bit-identical
+to that of one VideoIndex over the same items: a score does not depend on where its item is stored, the shards' lists are
+merged on the device under the global tie rule (mmt_search_merge_lists), and a target is scored on the shard that holds
+it and counted on all of them.
 """
 import torch
 
@@ -69,6 +84,21 @@ def _fold(x, w):
   out = torch.empty(n, m * d, device=x.device, dtype=torch.float32)
   check(_lib.lib().mmt_search_fold(ops._p(x), ops._p(w), n, m, d, ops._p(out), ops._stream()), 'mmt_search_fold')
   return out
+
+
+def _exclusions(exclude, nq, nv):
+  """exclude (type and width already checked) -> None or int64 [NQ, E], its values checked against -1 .. nv - 1 (one small
+  reduction and a host sync)."""
+  if exclude is None:
+    return None
+  if exclude.shape[0] != nq:
+    raise ValueError('search: %d queries but exclude %s' % (nq, tuple(exclude.shape)))
+  ex = exclude.reshape(nq, -1).contiguous()
+  if nq:
+    lo, hi = (int(v) for v in torch.aminmax(ex))
+    if lo < -1 or hi >= nv:
+      raise ValueError('search: exclude must lie in -1 .. %d, got %d .. %d' % (nv - 1, lo, hi))
+  return ex
 
 
 def _check_dtype(dtype):
@@ -192,6 +222,10 @@ class VideoIndex:
     index device -> IndexSubset for `search`, `rank_counts` and `ranks`.  Packed here, once; the range of the numbers is
     checked (one small reduction and a host sync).  It describes the num_items of this moment: after a further `add` it
     is refused.  Raises ValueError for an empty subset."""
+    return IndexSubset(*self._subset_mask(items))
+
+  def _subset_mask(self, items):
+    """The checks of `subset` -> (the set as a bool mask [num_items] of its own, the number of allowed items)."""
     if self.num_items == 0:
       raise ValueError('subset: the index holds no items')
     if not torch.is_tensor(items) or items.dtype not in (torch.bool, torch.int64):
@@ -215,7 +249,7 @@ class VideoIndex:
     count = int(mask.sum())
     if count == 0:
       raise ValueError('subset: no item allowed')
-    return IndexSubset(mask, count)
+    return mask, count
 
   def _subset(self, subset, who):
     if not isinstance(subset, IndexSubset):
@@ -251,22 +285,18 @@ class VideoIndex:
     if exclude is not None:
       self._exclude(exclude)
     q, qw = self._queries(embds, weights)
+    return self._search(q, qw, k, subset, _exclusions(exclude, q.shape[0], self.num_items))
+
+  def _search(self, q, qw, k, subset, ex):
+    """`search` behind its argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the index device, ex None or int64 [NQ, E]
+    there.  Nothing here waits for the device."""
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     masked = ()  # the extra arguments of the _ex entry points: subset words, exclusions of the batch, E
-    if subset is not None or exclude is not None:
+    if subset is not None or ex is not None:
       k = min(k, nv if subset is None else subset.count)  # lists no longer than the candidates: the outputs stay dense
-      ex = None
-      if exclude is not None:
-        if exclude.shape[0] != nq:
-          raise ValueError('search: %d queries but exclude %s' % (nq, tuple(exclude.shape)))
-        ex = exclude.reshape(nq, -1).contiguous()
-        if nq:
-          lo, hi = (int(v) for v in torch.aminmax(ex))
-          if lo < -1 or hi >= nv:
-            raise ValueError('search: exclude must lie in -1 .. %d, got %d .. %d' % (nv - 1, lo, hi))
       masked = (None if subset is None else subset.words, ex, 0 if ex is None else ex.shape[1])
     kout = min(k, nv)
-    if exclude is None:
+    if ex is None:
       scores = torch.empty(nq, kout, device=self.device, dtype=torch.float32)
       indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
     else:  # the merge writes only the slots that have a candidate
@@ -371,11 +401,398 @@ class VideoIndex:
             equal[r0:r1, t0:t1] = es
     return greater.reshape(shape), equal.reshape(shape)
 
+  def _operands(self, q, qw):
+    """The query operands of the rank entry points for one batch of rows: the fp32 fold, or its bf16 hi / lo pair.  Returns
+    (pointers, the tensors they point into)."""
+    n, m, d = q.shape
+    L = _lib.lib()
+    if self.dtype == torch.bfloat16:
+      hl = torch.empty(2, n, m * d, device=self.device, dtype=torch.bfloat16)  # hi = bf16(qf), lo = bf16(qf - hi)
+      check(L.mmt_search_fold_split_bf16(ops._p(q), ops._p(qw), n, m, d, ops._p(hl[0]), ops._p(hl[1]), ops._stream()),
+            'mmt_search_fold_split_bf16')
+      return (ops._p(hl[0]), ops._p(hl[1]), ops._p(qw), ops._p(self.folded), ops._p(self.weights)), hl
+    qf = _fold(q, qw)
+    return (ops._p(qf), ops._p(qw), ops._p(self.folded), ops._p(self.weights)), qf
+
+  def _batches(self, nq, t_max):
+    """Row ranges of the rank passes: a multiple of 64 rows (the query block) within _BATCH_BYTES, as `rank_counts`."""
+    per_row = self.num_experts * self.dim * 4 + 4 * t_max * (1 + 2 * -(-self.num_items // 4096))
+    batch = max(64, (_BATCH_BYTES // per_row) // 64 * 64)
+    return [(r0, min(nq, r0 + batch)) for r0 in range(0, nq, batch)]
+
+  def target_scores(self, embds, weights, targets):
+    """Queries as for `search`; targets as for `rank_counts` -> float32 of targets' shape on the device:
+    score(q, targets[q, t]) with the very bits `search` returns for that pair (the threshold pass of `rank_counts` on its
+    own: mmt_search_thresholds), NaN where the target is -1."""
+    if self.num_items == 0:
+      raise ValueError('ranks: the index holds no items')
+    self._targets(targets)
+    q, qw = self._queries(embds, weights)
+    if targets.shape[0] != q.shape[0]:
+      raise ValueError('ranks: %d queries but targets %s' % (q.shape[0], tuple(targets.shape)))
+    if q.shape[0]:
+      lo, hi = (int(v) for v in torch.aminmax(targets))
+      if lo < -1 or hi >= self.num_items:
+        raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
+    return self._target_scores(q, qw, targets)
+
+  def _target_scores(self, q, qw, targets):
+    """`target_scores` behind its checks; a target outside 0 .. num_items - 1 gives NaN.  Nothing here waits for the
+    device."""
+    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    tg = targets.reshape(nq, -1).contiguous()
+    thr = torch.empty(tg.shape, device=self.device, dtype=torch.float32)
+    if nq == 0:
+      return thr.reshape(targets.shape)
+    L = _lib.lib()
+    fn, name = ((L.mmt_search_thresholds_bf16, 'mmt_search_thresholds_bf16') if self.dtype == torch.bfloat16 else
+                (L.mmt_search_thresholds, 'mmt_search_thresholds'))
+    t_all = tg.shape[1]
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._batches(nq, min(MAX_T, t_all)):
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        for t0 in range(0, t_all, MAX_T):
+          t1 = min(t_all, t0 + MAX_T)
+          whole = t1 - t0 == t_all  # a column slice of a wider list is not contiguous: copy in and out
+          tgs = tg[r0:r1] if whole else tg[r0:r1, t0:t1].contiguous()
+          out = thr[r0:r1] if whole else torch.empty(r1 - r0, t1 - t0, device=self.device, dtype=torch.float32)
+          check(fn(*operands, r1 - r0, nv, m, d, ops._p(tgs), t1 - t0, ops._p(out), ops._stream()), name)
+          if not whole:
+            thr[r0:r1, t0:t1] = out
+    return thr.reshape(targets.shape)
+
+  def threshold_counts(self, embds, weights, thresholds, subset=None):
+    """Queries as for `search`; thresholds float32 [NQ] or [NQ, T] on the index device -> (greater, equal), int32 of
+    thresholds' shape: how many stored items score above / exactly equal to thresholds[q, t] for query q (plain float
+    compares; a NaN threshold counts nothing) -- the count pass of `rank_counts` against given values (mmt_search_count).
+    Fed with `target_scores` it gives `rank_counts`.  subset: only its items are counted."""
+    if self.num_items == 0:
+      raise ValueError('ranks: the index holds no items')
+    if not torch.is_tensor(thresholds) or thresholds.dtype != torch.float32:
+      raise ValueError('ranks: thresholds must be a float32 tensor, got %s' % (
+          thresholds.dtype if torch.is_tensor(thresholds) else type(thresholds).__name__))
+    if thresholds.device != self.device:
+      raise ValueError('ranks: thresholds must be on the index device %s, got %s' % (self.device, thresholds.device))
+    if thresholds.dim() not in (1, 2) or thresholds.dim() == 2 and thresholds.shape[1] < 1:
+      raise ValueError('ranks: thresholds [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(thresholds.shape),))
+    if subset is not None:
+      self._subset(subset, 'ranks')
+    q, qw = self._queries(embds, weights)
+    if thresholds.shape[0] != q.shape[0]:
+      raise ValueError('ranks: %d queries but thresholds %s' % (q.shape[0], tuple(thresholds.shape)))
+    return self._threshold_counts(q, qw, thresholds, subset)
+
+  def _threshold_counts(self, q, qw, thresholds, subset):
+    """`threshold_counts` behind its checks.  Nothing here waits for the device."""
+    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    thr = thresholds.reshape(nq, -1).contiguous()
+    greater = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
+    equal = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
+    if nq == 0:
+      return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
+    L = _lib.lib()
+    fn, name = ((L.mmt_search_count_bf16, 'mmt_search_count_bf16') if self.dtype == torch.bfloat16 else
+                (L.mmt_search_count, 'mmt_search_count'))
+    words = None if subset is None else subset.words
+    t_all = thr.shape[1]
+    t_max = min(MAX_T, t_all)
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._batches(nq, t_max):
+        n = r1 - r0
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        ws = torch.empty(L.mmt_count_workspace_ints(n, nv, t_max), device=self.device, dtype=torch.int32)
+        for t0 in range(0, t_all, MAX_T):
+          t1 = min(t_all, t0 + MAX_T)
+          whole = t1 - t0 == t_all
+          ts = thr[r0:r1] if whole else thr[r0:r1, t0:t1].contiguous()
+          gs = greater[r0:r1] if whole else torch.empty(n, t1 - t0, device=self.device, dtype=torch.int32)
+          es = equal[r0:r1] if whole else torch.empty_like(gs)
+          check(fn(*operands, n, nv, m, d, ops._p(ts), t1 - t0, ops._p(words), ops._p(ws), ops._p(gs), ops._p(es),
+                   ops._stream()), name)
+          if not whole:
+            greater[r0:r1, t0:t1] = gs
+            equal[r0:r1, t0:t1] = es
+    return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
+
   def ranks(self, embds, weights, targets, subset=None):
     """The reference's tie-averaged 0-based rank (model/metric.py:90-121) of item targets[q, t] among the stored items for
     query q: greater + (equal - 1) / 2 from `rank_counts`, +inf where the target is -1.  float64 on the device, of
     targets' shape (float32 would not hold counts above 2^24).  subset: the rank among its items, +inf for a target that
     is not one of them."""
+    greater, equal = self.rank_counts(embds, weights, targets, subset=subset)
+    ranks = greater.double() + (equal.double() - 1) / 2
+    none = targets < 0
+    if subset is not None:
+      none = none | ~subset.mask[targets.clamp(min=0)]
+    return torch.where(none, torch.full_like(ranks, float('inf')), ranks)
+
+
+MAX_SHARDS = 32  # lists per query of the merge kernel
+
+
+def place(capacities, fills, n):
+  """Where `add` puts n new items: (shard capacities, items held per shard, n) -> [(shard, count), ...] in item order.  The
+  chunk goes to the shard that holds the fewest items among those with room (the lowest number on a tie) and what does not
+  fit there spills to the next such shard, and so on.  Raises ValueError if the shards' free rows together are fewer than
+  n.  Pure: the arguments are not changed."""
+  fills = list(fills)
+  if n > sum(c - f for c, f in zip(capacities, fills)):
+    raise ValueError('%d items do not fit (%d of %d in use)' % (n, sum(fills), sum(capacities)))
+  segments = []
+  while n > 0:
+    s = min((i for i in range(len(fills)) if fills[i] < capacities[i]), key=lambda i: (fills[i], i))
+    take = min(n, capacities[s] - fills[s])
+    segments.append((s, take))
+    fills[s] += take
+    n -= take
+  return segments
+
+
+class ShardedSubset:
+  """A set of items of a ShardedVideoIndex (ShardedVideoIndex.subset): `parts[s]` is shard s's IndexSubset in its own item
+  numbers on its own device (None where the shard holds no allowed item), `mask` the set as bool [num_items] on the primary
+  device, `count` the number of allowed items, `num_items` the index size it was built for."""
+
+  def __init__(self, parts, mask, count):
+    self.parts, self.mask, self.count = parts, mask, count
+    self.num_items, self.device = mask.shape[0], mask.device
+
+
+class _Shard:
+  """One shard: an ordinary VideoIndex on its device (None while the shard has no room at all) and its local -> global
+  item table.  The table is kept on the primary device: it is written there by `add`, and its readers -- the merge kernel
+  and `subset` -- run there, on the stream that wrote it, so no kernel ever follows a pointer into another device."""
+
+  def __init__(self, capacity, m, d, device, dtype, primary):
+    self.device = device
+    self.capacity = capacity
+    self.index = VideoIndex.empty(capacity, m, d, device, dtype=dtype) if capacity else None
+    self.ids = torch.empty(capacity, device=primary, dtype=torch.int64)
+
+  @property
+  def num_items(self):
+    return self.index.num_items if self.index is not None else 0
+
+
+def _devices(devices):
+  if not isinstance(devices, (list, tuple)) or not 1 <= len(devices) <= MAX_SHARDS:
+    raise ValueError('ShardedVideoIndex: devices must be a list of 1..%d CUDA devices, got %r' % (MAX_SHARDS, devices))
+  out = []
+  for dev in devices:
+    dev = torch.device(dev)
+    if dev.type != 'cuda':
+      raise ValueError('ShardedVideoIndex: devices must be CUDA devices, got %s' % dev)
+    out.append(dev if dev.index is not None else torch.device('cuda', torch.cuda.current_device()))
+  return out
+
+
+class ShardedVideoIndex:
+  """One gallery held as S = len(devices) VideoIndex shards, one per entry of `devices` (the same device may appear more
+  than once), with the surface of VideoIndex.  Item numbers are global insertion order 0 .. num_items - 1; every result is
+  bit-identical to that of one VideoIndex over the same items in the same order: score(q, g) has the same bits wherever
+  item g is stored, the shards' top-k lists are merged under the global tie rule on the device (mmt_search_merge_lists),
+  and a target is scored on the shard that holds it and counted on every shard (mmt_search_thresholds,
+  mmt_search_count), the int32 counts summed.  devices[0] is the primary: items to add, queries, targets, `exclude` and
+  subset items are given on it and results are returned on it.  One host thread drives all devices; launches and
+  cross-device copies are asynchronous, so the shards scan concurrently."""
+
+  def __init__(self, embds, weights, devices, dtype=torch.float32):
+    _check_dtype(dtype)
+    devices = _devices(devices)
+    g, gw = VideoIndex._items(embds, weights, 'ShardedVideoIndex')
+    n, s = g.shape[0], len(devices)
+    sizes = [n // s + (i < n % s) for i in range(s)]   # contiguous near-equal ranges
+    self._allocate(sizes, n, g.shape[1], g.shape[2], devices, dtype)
+    self.add(g, gw)
+
+  @classmethod
+  def empty(cls, capacity, num_experts, dim, devices, dtype=torch.float32):
+    """Room for `capacity` items and none stored: every shard gets ceil(capacity / S) rows; `add` fills them."""
+    _check_dtype(dtype)
+    devices = _devices(devices)
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (capacity, num_experts, dim)):
+      raise ValueError('ShardedVideoIndex.empty: capacity, num_experts and dim must be ints')
+    self = cls.__new__(cls)
+    self._allocate([-(-capacity // len(devices))] * len(devices), capacity, num_experts, dim, devices, dtype)
+    return self
+
+  def _allocate(self, sizes, capacity, m, d, devices, dtype):
+    mult = _DTYPES[dtype]
+    if capacity < 1 or capacity >= 2 ** 31 or not 1 <= m <= 16 or d < mult or d % mult:
+      raise ValueError('ShardedVideoIndex: need 1 <= capacity < 2^31, 1 <= M <= 16 and d %% %d == 0 for %s, got (%d, %d, %d)'
+                       % (mult, dtype, capacity, m, d))
+    self.capacity, self.num_experts, self.dim = capacity, m, d
+    self.num_items = 0
+    self.devices, self.device, self.dtype = devices, devices[0], dtype
+    self.shards = [_Shard(size, m, d, dev, dtype, devices[0]) for size, dev in zip(sizes, devices)]
+    # global item -> (shard, local item), on the primary: exclusions, targets and subsets are translated there
+    self._shard_of = torch.empty(capacity, device=self.device, dtype=torch.int64)
+    self._local_of = torch.empty(capacity, device=self.device, dtype=torch.int64)
+    self._table_cache = {}
+
+  @property
+  def shard_sizes(self):
+    return [sh.num_items for sh in self.shards]
+
+  @property
+  def nbytes(self):
+    """Bytes held: the shards' storage, their item tables and the primary's item map, at full capacity."""
+    return (sum(sh.index.nbytes for sh in self.shards if sh.index is not None) + 8 * sum(sh.capacity for sh in self.shards) +
+            16 * self.capacity)
+
+  def add(self, embds, weights):
+    """Appends items (n, M, d) / (n, M) given on the primary device; they get the next n global numbers.  Placement is
+    `place`: the shard with the fewest items first, spilling when it is full.  Returns (first, last).  Raises ValueError,
+    leaving the index as it was, if they do not fit."""
+    g, gw = VideoIndex._items(embds, weights, 'ShardedVideoIndex.add')
+    n, m, d = g.shape
+    if (m, d) != (self.num_experts, self.dim):
+      raise ValueError('ShardedVideoIndex.add: items (n, %d, %d) expected, got %s' % (self.num_experts, self.dim, tuple(g.shape)))
+    if g.device != self.device or gw.device != self.device:
+      raise ValueError('ShardedVideoIndex.add: items must be on the primary device %s' % self.device)
+    first, last = self.num_items, self.num_items + n
+    if last > self.capacity:
+      raise ValueError('ShardedVideoIndex.add: %d items do not fit (%d of %d in use)' % (n, first, self.capacity))
+    segments = place([sh.capacity for sh in self.shards], self.shard_sizes, n)
+    at = 0
+    for s, count in segments:
+      sh = self.shards[s]
+      lo, hi = sh.index.add(g[at:at + count].to(sh.device), gw[at:at + count].to(sh.device))
+      sh.ids[lo:hi] = torch.arange(first + at, first + at + count, device=self.device)
+      self._shard_of[first + at:first + at + count] = s
+      self._local_of[first + at:first + at + count] = torch.arange(lo, hi, device=self.device)
+      at += count
+    self.num_items = last
+    return first, last
+
+  def _tables(self, shards):
+    """The item tables' addresses of the given shards as a device array on the primary, where the tables themselves are:
+    the `ids` of the merge kernel."""
+    if shards not in self._table_cache:
+      self._table_cache[shards] = torch.tensor([self.shards[s].ids.data_ptr() for s in shards],
+                                               dtype=torch.int64).to(self.device)
+    return self._table_cache[shards]
+
+  def _live(self):
+    return [(s, sh) for s, sh in enumerate(self.shards) if sh.num_items]
+
+  def _queries(self, embds, weights):
+    """The queries checked and flattened once, on the primary (VideoIndex._queries reads only the bookkeeping both classes
+    share: num_experts, dim, device)."""
+    return VideoIndex._queries(self, embds, weights)
+
+  def _local(self, items, s):
+    """Global item numbers (-1 = none) on the primary -> shard s's numbers, -1 for none and for items held elsewhere."""
+    at = items.clamp(min=0)
+    return torch.where((items >= 0) & (self._shard_of[at] == s), self._local_of[at], torch.full_like(items, -1))
+
+  def subset(self, items):
+    """items: bool [num_items] or int64 item numbers on the primary device, as VideoIndex.subset -> ShardedSubset: the set
+    cut into one IndexSubset per shard, in the shard's own numbers.  After a further `add` it is refused."""
+    mask, total = VideoIndex._subset_mask(self, items)   # reads only the bookkeeping both classes share
+    parts = []
+    for sh in self.shards:
+      part = None
+      if sh.num_items:
+        local = mask[sh.ids[:sh.num_items]]  # gathered on the primary, where the table is
+        with torch.cuda.device(sh.device):
+          local = local.to(sh.device)
+          count = int(local.sum())
+          if count:
+            part = IndexSubset(local, count)
+      parts.append(part)
+    return ShardedSubset(parts, mask, total)
+
+  def _subset(self, subset, who):
+    if not isinstance(subset, ShardedSubset):
+      raise ValueError('%s: subset must come from ShardedVideoIndex.subset, got %s' % (who, type(subset).__name__))
+    if subset.num_items != self.num_items:
+      raise ValueError('%s: the subset was built for %d items, the index holds %d' % (who, subset.num_items, self.num_items))
+    if subset.device != self.device or len(subset.parts) != len(self.shards):
+      raise ValueError('%s: the subset belongs to another index' % who)
+
+  def search(self, embds, weights, k=10, subset=None, exclude=None):
+    """VideoIndex.search over all shards: (scores [NQ, k'] float32, indices [NQ, k'] int64 global item numbers) on the
+    primary, k' = min(k, num_items) or min(k, subset.count).  Every shard searches its own items for its best min(k', its
+    candidates); the lists are copied to the primary and merged there in one launch."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+      raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
+    if self.num_items == 0:
+      raise ValueError('search: the index holds no items')
+    if subset is not None:
+      self._subset(subset, 'search')
+    if exclude is not None:
+      VideoIndex._exclude(self, exclude)
+    q, qw = self._queries(embds, weights)
+    nq = q.shape[0]
+    ex = _exclusions(exclude, nq, self.num_items)
+    kout = min(k, self.num_items if subset is None else subset.count)
+    scores = torch.empty(nq, kout, device=self.device, dtype=torch.float32)
+    indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
+    if nq == 0:
+      return scores, indices
+    live = [(s, sh) for s, sh in self._live() if subset is None or subset.parts[s] is not None]
+    kin = min(kout, max(sh.num_items if subset is None else subset.parts[s].count for s, sh in live))
+    with torch.cuda.device(self.device):  # the staged lists; the slots a shorter list leaves are empty
+      st_scores = torch.full((len(live), nq, kin), float('-inf'), device=self.device, dtype=torch.float32)
+      st_index = torch.full((len(live), nq, kin), -1, device=self.device, dtype=torch.int64)
+      tables = self._tables(tuple(s for s, _ in live))
+    for i, (s, sh) in enumerate(live):
+      ex_s = None if ex is None else self._local(ex, s).to(sh.device)
+      with torch.cuda.device(sh.device):
+        part = sh.index._search(q.to(sh.device), qw.to(sh.device), kout, None if subset is None else subset.parts[s], ex_s)
+      width = part[0].shape[1]
+      st_scores[i, :, :width].copy_(part[0])
+      st_index[i, :, :width].copy_(part[1])
+    with torch.cuda.device(self.device):
+      check(_lib.lib().mmt_search_merge_lists(ops._p(st_scores), ops._p(st_index), ops._p(tables), len(live), nq, kin, kout,
+                                              ops._p(scores), ops._p(indices), ops._stream()), 'mmt_search_merge_lists')
+    return scores, indices
+
+  def rank_counts(self, embds, weights, targets, subset=None):
+    """VideoIndex.rank_counts over all shards: each shard scores the targets it holds (target_scores), the primary picks
+    the owner's value per (query, target), each shard counts its items against those thresholds (threshold_counts) and
+    the int32 counts are summed on the primary."""
+    if self.num_items == 0:
+      raise ValueError('ranks: the index holds no items')
+    VideoIndex._targets(self, targets)
+    if subset is not None:
+      self._subset(subset, 'ranks')
+    q, qw = self._queries(embds, weights)
+    nq = q.shape[0]
+    if targets.shape[0] != nq:
+      raise ValueError('ranks: %d queries but targets %s' % (nq, tuple(targets.shape)))
+    shape = targets.shape
+    if nq == 0:
+      return tuple(torch.empty(shape, device=self.device, dtype=torch.int32) for _ in range(2))
+    tg = targets.reshape(nq, -1).contiguous()
+    lo, hi = (int(v) for v in torch.aminmax(tg))
+    if lo < -1 or hi >= self.num_items:
+      raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
+    live = self._live()
+    queries = {}
+    thr = torch.full(tg.shape, float('nan'), device=self.device, dtype=torch.float32)
+    for s, sh in live:
+      local = self._local(tg, s)
+      queries[s] = (q.to(sh.device), qw.to(sh.device))
+      with torch.cuda.device(sh.device):
+        mine = sh.index._target_scores(*queries[s], local.to(sh.device))
+      thr = torch.where(local >= 0, mine.to(self.device), thr)
+    greater = torch.zeros(tg.shape, device=self.device, dtype=torch.int32)
+    equal = torch.zeros(tg.shape, device=self.device, dtype=torch.int32)
+    for s, sh in live:
+      part = None if subset is None else subset.parts[s]
+      if subset is not None and part is None:
+        continue  # no allowed item here: nothing to count
+      with torch.cuda.device(sh.device):
+        gs, es = sh.index._threshold_counts(*queries[s], thr.to(sh.device), part)
+      greater += gs.to(self.device)
+      equal += es.to(self.device)
+    return greater.reshape(shape), equal.reshape(shape)
+
+  def ranks(self, embds, weights, targets, subset=None):
+    """VideoIndex.ranks: greater + (equal - 1) / 2 from `rank_counts`, float64 on the primary, +inf where the target is -1
+    or outside the subset."""
     greater, equal = self.rank_counts(embds, weights, targets, subset=subset)
     ranks = greater.double() + (equal.double() - 1) / 2
     none = targets < 0

@@ -26,7 +26,12 @@ median and spread.  Default output profiles/search_ranks_bench.json.
 one on the same index (--gallery-dtype, both = the two indexes): an all-ones subset (the cost of the predicate), a
 contiguous FRACTION of the items (whole tiles skipped: the time should follow the fraction), a random FRACTION (no tile
 skips: as all-ones), and E exclusions per query without a subset (the query's own item and E - 1 random ones).  --runs
-rounds, every variant once per round, interleaved; median and spread.  Default output profiles/search_subset_bench.json."""
+rounds, every variant once per round, interleaved; median and spread.  Default output profiles/search_subset_bench.json.
+
+--shards N times search.ShardedVideoIndex with N shards in place of the single index of the default mode: the shards go to
+the visible devices in turn (cuda:0, cuda:1, ..., again from cuda:0 when there are fewer devices than shards), queries
+and results on cuda:0.  On one device the difference to the plain run is the cost of the merge launch, the staged lists
+and of scanning N shorter galleries; with --skip-materialised only the index is timed."""
 import argparse
 import json
 import math
@@ -38,7 +43,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mmt_amd import _lib, metric, ops  # noqa: E402
-from mmt_amd.search import VideoIndex  # noqa: E402
+from mmt_amd.search import ShardedVideoIndex, VideoIndex  # noqa: E402
 
 SHAPES = {'S1': (1000, 1000), 'S2': (4917, 4917), 'S3': (4096, 262144)}
 PEAK = 157.3e12
@@ -229,12 +234,16 @@ def main():
                   'a contiguous and a random subset of this fraction of the items against the unmasked search')
   ap.add_argument('--exclude', type=int, default=0, metavar='E', help='time search(exclude=) with E (1..32) exclusions per '
                   'query against the unmasked search')
+  ap.add_argument('--shards', type=int, default=0, metavar='N', help='time a ShardedVideoIndex of N (1..32) shards over '
+                  'the visible devices, cycling, in place of the single index (default mode only)')
   a = ap.parse_args()
   masked = a.subset is not None or a.exclude > 0
   if a.subset is not None and not 0 < a.subset <= 1:
     raise SystemExit('--subset wants a fraction in (0, 1]')
   if not 0 <= a.exclude <= 32:
     raise SystemExit('--exclude wants 0..32')
+  if not 0 <= a.shards <= 32 or a.shards and (masked or a.ranks or a.gallery_dtype == 'both'):
+    raise SystemExit('--shards wants 1..32 and the default mode (no --ranks, --subset, --exclude, --gallery-dtype both)')
   if masked and a.out is None:
     a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_subset_bench.json')
   if a.ranks and a.out is None:
@@ -267,7 +276,14 @@ def main():
       del g, gw, q, qw
       torch.cuda.empty_cache()
       continue
-    index = VideoIndex(g, gw, dtype=getattr(torch, a.gallery_dtype))
+    if a.shards:
+      devices = [torch.device('cuda', i % torch.cuda.device_count()) for i in range(a.shards)]
+      index = ShardedVideoIndex.empty(nv, M, D, devices, dtype=getattr(torch, a.gallery_dtype))
+      for at in range(0, nv, 8192):
+        index.add(g[at:at + 8192], gw[at:at + 8192])
+      row.update(shards=a.shards, devices=[str(dev) for dev in devices], shard_sizes=index.shard_sizes)
+    else:
+      index = VideoIndex(g, gw, dtype=getattr(torch, a.gallery_dtype))
     t, it, mem, (s, i) = timed(lambda: index.search(q, qw, k=K), a.min_seconds)
     row['fused'] = dict(seconds=t, iters=it, peak_mem_growth_bytes=mem, tflops=flop / t / 1e12,
                         fraction_of_peak=flop / t / PEAK)
