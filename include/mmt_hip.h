@@ -465,7 +465,7 @@ int mmt_sims_eval(const float* txt, const float* vid, const float* tw, const flo
 int mmt_retrieval_ranks(const float* sims, const uint8_t* qmask, int NQ, int NV, float* t2v_rank, float* v2t_rank,
                         float* scratch, void* stream);
 
-/* ---- top-k retrieval (search.hip, search_bf16.hip, search_rank.hip, search_subset.hip, search_shard.hip, fold in retrieval.hip) --------------------------------------
+/* ---- top-k retrieval (search.hip, search_bf16.hip, search_rank.hip, search_subset.hip, search_shard.hip, search_norm.hip, fold in retrieval.hip) --------------------------------------
  * score(q, g) = sum_m qw[q][m] gw[g][m] <Q_m[q], G_m[g]> / sum_m qw[q][m] gw[g][m] (0 -> 1e-5), the 'indep' similarity
  * of model/model.py:789-837.  Per query the min(k, NV) best (score, gallery index) pairs, score descending, equal scores
  * by ascending index (a stable argsort; the reference's np.argsort leaves the order of exact ties unspecified).
@@ -587,6 +587,52 @@ int mmt_search_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const floa
                           int32_t* greater, int32_t* equal, void* stream);
 int mmt_search_merge_lists(const float* scores, const int64_t* index, const int64_t* const* ids, int S, int NQ, int kin,
                            int kout, float* out_scores, int64_t* out_index, void* stream);
+/* Querybank hubness normalisation (search_norm.hip): inverted softmax over a bank of NB queries, the static half of
+ * QB-Norm (Bogolin et al., CVPR 2022), a test-time re-scoring of the ranking model/metric.py:90-121, 153-243 evaluates.
+ * With score the plain value of the scans above, bit for bit, and 0 < beta < inf, all in fp32:
+ *   x(b, g) = fl(beta * score(b, g));  lse[g] = log sum_b exp(x(b, g));  score'(q, g) = fl(fl(beta * score(q, g)) - lse[g])
+ * (a rounded multiply, then a rounded subtract, never an fma).  lse[g] is computed blockwise: every 64-row bank block gives
+ * m = max x and p = sum exp(x - m) per item, rows in ascending order, and the blocks are folded in ascending order,
+ * M' = max(M, m), S' = S exp(M - M') + p exp(m - M'), lse = M + log S.  It depends on item g's stored row and weights, the
+ * bank in its row order and beta only -- not on NV, the item's position, the chunk rule, the batching of the bank or the
+ * shard that holds the item.  No atomics, one writer per output.
+ * mmt_col_lse_workspace_floats: fp32 workspace of one mmt_search_col_lse call, 2 * ceil(NB / 64) * NV (the (m, p) pairs of
+ *   its bank blocks); MMT_ERR_ARG if a size is out of range.
+ * mmt_search_col_lse / mmt_search_col_lse_bf16: one batch of the bank -- operands as the query operands of mmt_search_topk /
+ *   mmt_search_topk_bf16, then the gallery -- folded into the running state: state fp32 [2][NV] (M, then S).  first != 0
+ *   starts the state (it is not read), otherwise it is the state the previous batch left; every batch but the last must
+ *   hold a multiple of 64 rows.  lse (nullable) fp32 [NV]: written when given, i.e. with the last batch.  ws 16-byte
+ *   aligned.  Gates as mmt_search_topk / _bf16 (MMT_ERR_ARG, MMT_ERR_ALIGN); beta not finite or <= 0 is MMT_ERR_ARG.
+ * mmt_search_topk_norm / mmt_search_topk_bf16_norm: mmt_search_topk_ex / mmt_search_topk_bf16_ex ranking by score' (one pass
+ *   over the score tile in LDS before selection; lse of the tile's 128 items read once per tile).  subset and exclude
+ *   nullable, E = 0 allowed; selection, ties, workspace and merge as there.  The returned scores are score'.
+ * mmt_search_thresholds_norm / _bf16_norm, mmt_search_count_norm / _bf16_norm: mmt_search_thresholds and mmt_search_count on
+ *   score': thr[q][t] = score'(q, targets[q][t]) from the same tile code (NaN for a target outside 0 .. NV - 1), and the
+ *   counts of score' above / equal to given thresholds (subset nullable).  Workspace: mmt_count_workspace_ints. */
+int64_t mmt_col_lse_workspace_floats(int NB, int NV);
+int mmt_search_col_lse(const float* bf, const float* bw, const float* gf, const float* gw, int NB, int NV, int M, int d,
+                       float beta, float* ws, float* state, int first, float* lse, void* stream);
+int mmt_search_col_lse_bf16(const uint16_t* b_hi, const uint16_t* b_lo, const float* bw, const uint16_t* gf, const float* gw,
+                            int NB, int NV, int M, int d, float beta, float* ws, float* state, int first, float* lse,
+                            void* stream);
+int mmt_search_topk_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                         int k, const uint32_t* subset, const int64_t* exclude, int E, float beta, const float* lse,
+                         uint64_t* ws, float* scores, int64_t* index, void* stream);
+int mmt_search_topk_bf16_norm(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                              const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
+                              const int64_t* exclude, int E, float beta, const float* lse, uint64_t* ws, float* scores,
+                              int64_t* index, void* stream);
+int mmt_search_thresholds_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
+                               int d, const int64_t* targets, int T, float beta, const float* lse, float* thr, void* stream);
+int mmt_search_thresholds_bf16_norm(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                    const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T, float beta,
+                                    const float* lse, float* thr, void* stream);
+int mmt_search_count_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                          const float* thr, int T, const uint32_t* subset, float beta, const float* lse, int32_t* ws,
+                          int32_t* greater, int32_t* equal, void* stream);
+int mmt_search_count_bf16_norm(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                               const float* gw, int NQ, int NV, int M, int d, const float* thr, int T, const uint32_t* subset,
+                               float beta, const float* lse, int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

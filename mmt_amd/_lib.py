@@ -246,6 +246,22 @@ SIGNATURES = {
     'mmt_search_count_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
                                       c_vp, c_vp, c_vp]),
     'mmt_search_merge_lists': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    'mmt_col_lse_workspace_floats': (c_i64, [c_int, c_int]),
+    'mmt_search_col_lse': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f32, c_vp, c_vp, c_int, c_vp, c_vp]),
+    'mmt_search_col_lse_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f32, c_vp, c_vp, c_int,
+                                        c_vp, c_vp]),
+    'mmt_search_topk_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_f32,
+                                     c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_topk_bf16_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int,
+                                          c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_thresholds_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_f32, c_vp,
+                                           c_vp, c_vp]),
+    'mmt_search_thresholds_bf16_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_f32,
+                                                c_vp, c_vp, c_vp]),
+    'mmt_search_count_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_f32, c_vp,
+                                      c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_count_bf16_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_f32,
+                                           c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

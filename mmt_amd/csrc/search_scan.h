@@ -1,7 +1,8 @@
 // The scoring tile of the gallery scans, shared by the top-k kernels (search.hip, search_bf16.hip: a running top-k per
 // query) and the rank-count kernels (search_rank.hip: a counter per query and target): block shape, the two K loops (fp32
 // gallery on v_mfma_f32_32x32x2_f32, bf16 gallery on v_mfma_f32_32x32x16_bf16), the gated-denominator epilogue and the
-// chunk rule.  One copy, so every kernel that scores a (query, item) pair computes the same bits for it.
+// chunk rule.  One copy, so every kernel that scores a (query, item) pair computes the same bits for it.  The querybank
+// normalisation kernels (search_norm.hip) score with the same tile and add the two passes at the end of this file.
 //
 // Which gallery row a tile row / column holds is a functor `grow(r)`, r in 0 .. TK_G - 1 -> gallery row, or -1 for "none"
 // (zero-filled in registers, never read): g0 + r for a scan, a table lookup for the rank kernels' threshold pass.
@@ -177,6 +178,37 @@ __device__ __forceinline__ void tk_tile_scores(const f32x16 (&acc)[2], float* sS
       sS[row * TK_SLD + col] = acc[t][r] / (den[r] == 0.f ? 1e-5f : den[r]);
     }
   }
+}
+
+// fl(a * b) as an instruction of its own: the optimiser cannot contract it with a following add or subtract into an fma
+// (plain `a * b`, and __fmul_rn which is defined as that, may be under -ffast-math).
+__device__ __forceinline__ float tk_mul_rn(float a, float b) {
+  float r;
+  asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+// Querybank normalisation of one score tile in place (search_norm.hip only): sS[r][c] = fl(fl(beta * sS[r][c]) - lse[item
+// of column c]) -- a rounded multiply, then a rounded subtract, never an fma, so the value can be restated bit for bit.
+// Two threads per column (rows of one parity each); a thread reads its column's lse once per tile.  A column without an
+// item (grow = -1) keeps a plain product: it is never selected or counted.  The caller syncs before the tile is read.
+template <class GRow>
+__device__ __forceinline__ void tk_tile_norm(float* sS, const float* lse, float beta, GRow grow, int tid) {
+  const int col = tid & (TK_G - 1), g = grow(col);
+  const float l = g >= 0 ? lse[g] : 0.f;
+  for (int row = tid >> 7; row < TK_Q; row += 2)
+    sS[row * TK_SLD + col] = tk_mul_rn(beta, sS[row * TK_SLD + col]) - l;
+}
+
+// Column statistics of one score tile for the log-sum-exp over a bank of queries (search_norm.hip only): thread c < TK_G
+// takes column c and the tile's live rows 0 .. rows_live - 1 in ascending order: x = fl(beta * score), m = max x,
+// p = sum exp(x - m).  The order is fixed by the row number alone, so (m, p) is a function of the 64-row bank block, the
+// item and beta -- not of the launch geometry.
+__device__ __forceinline__ void tk_tile_col_stats(const float* sS, float beta, int rows_live, int col, float& m, float& p) {
+  m = tk_mul_rn(beta, sS[col]);
+  for (int row = 1; row < rows_live; ++row) m = fmaxf(m, tk_mul_rn(beta, sS[row * TK_SLD + col]));
+  p = 0.f;
+  for (int row = 0; row < rows_live; ++row) p += expf(tk_mul_rn(beta, sS[row * TK_SLD + col]) - m);
 }
 
 // Host side (search.hip): gallery columns per block, TK_CHUNK halved (down to one tile) while the launch would not fill

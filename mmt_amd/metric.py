@@ -117,7 +117,7 @@ def v2t_targets(query_masks, num_videos, captions_per_video):
 
 
 def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, query_masks=None, dtype=torch.float32,
-                              video_subset=None, devices=None):
+                              video_subset=None, devices=None, text_bank=None, video_bank=None, beta=None):
   """`retrieval_metrics` (same arguments, same result dict and keys) without the N_text x N_video matrix: the rank of every
   ground truth comes from search.VideoIndex.ranks, so no buffer grows with N_text * N_video.  t2v: an index of the videos
   queried with the real captions, the target of caption row b*C + c being video b.  v2t: an index of the real captions
@@ -128,8 +128,16 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
   all real captions (VideoIndex.subset): t2v queries are the real captions of the cut's videos and rank among the cut's
   videos; v2t queries are the cut's videos and rank among the real captions of the cut.
   devices (a list of CUDA devices): both indexes are search.ShardedVideoIndex over those devices, the arrays and the
-  ranking on devices[0]; the result is the same, bit for bit."""
+  ranking on devices[0]; the result is the same, bit for bit.
+  text_bank / video_bank ((embds, weights) pairs in either query layout of VideoIndex.search) with beta (a float > 0):
+  querybank hubness normalisation (VideoIndex.hub_norm) -- a bank of text queries re-scores the t2v ranking over the video
+  index, a bank of videos the v2t ranking over the caption index; either may be given alone."""
   from .search import ShardedVideoIndex, VideoIndex
+  if (text_bank is not None or video_bank is not None) and beta is None:
+    raise ValueError('retrieval_metrics_indexed: a bank needs beta')
+  for bank in (text_bank, video_bank):
+    if bank is not None and not (isinstance(bank, (tuple, list)) and len(bank) == 2):
+      raise ValueError('retrieval_metrics_indexed: a bank is an (embds, weights) pair')
   if devices is None:
     make_index = VideoIndex
   else:
@@ -162,6 +170,11 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
   tw = _as_cuda_f32(text_weights).reshape(b * c, m)
   if devices is not None:
     vid, txt4, vw, tw = (x.to(devices[0]) for x in (vid, txt4, vw, tw))
+
+  def normaliser(index, bank):
+    if bank is None:
+      return None
+    return index.hub_norm(*(_as_cuda_f32(x).to(vid.device) for x in bank), beta)
   rows = torch.from_numpy(np.flatnonzero(valid)).to(vid.device)
   txt = txt4.permute(0, 2, 1, 3).reshape(b * c, m, d)[rows].contiguous()      # the real captions, rows b*C + c in order
   tw = tw[rows].contiguous()
@@ -170,16 +183,21 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
     cut_d = torch.from_numpy(cut).to(dev)
     mine = cut_d[rows // c]                                                     # real captions of the cut's videos
     videos = make_index(vid, vw, dtype=dtype)
-    cols = videos.ranks(txt[mine], tw[mine], (rows // c)[mine], subset=videos.subset(cut_d)).cpu().numpy()
+    cols = videos.ranks(txt[mine], tw[mine], (rows // c)[mine], subset=videos.subset(cut_d),
+                        norm=normaliser(videos, text_bank)).cpu().numpy()
     out = {'t2v_metrics': dict(cols2metrics(cols, cols.size), cols=cols)}
     captions = make_index(txt, tw, dtype=dtype)
-    ranks = captions.ranks(vid[cut_d], vw[cut_d], torch.from_numpy(targets).to(dev)[cut_d], subset=captions.subset(mine))
+    ranks = captions.ranks(vid[cut_d], vw[cut_d], torch.from_numpy(targets).to(dev)[cut_d], subset=captions.subset(mine),
+                           norm=normaliser(captions, video_bank))
     cols = ranks.min(dim=1).values.cpu().numpy()
     out['v2t_metrics'] = dict(cols2metrics(cols, cols.size), cols=cols)
     return out
-  cols = make_index(vid, vw, dtype=dtype).ranks(txt, tw, rows // c).cpu().numpy()
+  videos = make_index(vid, vw, dtype=dtype)
+  cols = videos.ranks(txt, tw, rows // c, norm=normaliser(videos, text_bank)).cpu().numpy()
+  del videos
   out = {'t2v_metrics': dict(cols2metrics(cols, cols.size), cols=cols)}
-  ranks = make_index(txt, tw, dtype=dtype).ranks(vid, vw, torch.from_numpy(targets).to(vid.device))
+  captions = make_index(txt, tw, dtype=dtype)
+  ranks = captions.ranks(vid, vw, torch.from_numpy(targets).to(vid.device), norm=normaliser(captions, video_bank))
   cols = ranks.min(dim=1).values.cpu().numpy()
   out['v2t_metrics'] = dict(cols2metrics(cols, cols.size), cols=cols)
   return out

@@ -60,7 +60,27 @@ memory or a scan at the rate of several cards.  Item numbers are global insertio
 to that of one VideoIndex over the same items: a score does not depend on where its item is stored, the shards' lists are
 merged on the device under the global tie rule (mmt_search_merge_lists), and a target is scored on the shard that holds
 it and counted on all of them.
+
+    norm = index.hub_norm(bank_embds, bank_weights, beta=20.0)             # HubNorm: .lse [num_items], .beta, .bank_size
+    scores, indices = index.search(q, qw, k=10, norm=norm)                 # also with subset= and exclude=
+    ranks = index.ranks(q, qw, targets, norm=norm)                         # rank_counts, target_scores, threshold_counts too
+    norm = index.hub_norm(bank_embds, bank_weights, 20.0, dynamic=True)    # + .hubs: the plain top-1 items of the bank
+
+Querybank hubness normalisation (inverted softmax, the static half of QB-Norm: Bogolin et al., CVPR 2022): a video that is
+every query's nearest neighbour stops crowding out the right answers once each item is re-scored by how strongly a bank of
+queries already pulls on it.  In fp32, with score the plain value above:
+    lse[g] = log sum_b exp(fl(beta * score(b, g)))       over the bank, blockwise (mmt_search_col_lse)
+    score'(q, g) = fl(fl(beta * score(q, g)) - lse[g])   a rounded multiply, then a rounded subtract
+score' is the log of the inverted-softmax probability; with norm= the calls rank by it and return it, and norm=None takes
+exactly the plain calls.  The bank streams through a scan of its own in batches of whole 64-row blocks -- no bank x
+gallery matrix -- and lse[g] depends on item g, the bank in its row order and beta only: not on num_items, the item's
+position, the batching or the shard, so ShardedVideoIndex.hub_norm (one HubNorm per shard, .lse and .hubs in global order
+on the primary) gives bit-identical results.  A norm with .hubs applies QB-Norm's dynamic rule: a query is normalised only
+if its plain top-1 among its candidates (after subset / exclude) is a hub, else it keeps its plain result; dynamic=False on
+the call normalises every query.  Like a subset, a norm is refused after a further `add`.
 """
+import math
+
 import torch
 
 from . import _lib, ops
@@ -119,6 +139,40 @@ class IndexSubset:
       check(_lib.lib().mmt_search_subset_pack(ops._p(mask.view(torch.uint8)), n, ops._p(words), ops._stream()),
             'mmt_search_subset_pack')
     self.words = words.view(torch.uint32)
+
+
+class HubNorm:
+  """The querybank normaliser of a VideoIndex (VideoIndex.hub_norm): `lse` fp32 [num_items] on the index device,
+  lse[g] = log sum_b exp(beta * score(b, g)) over the `bank_size` bank queries; `beta`; `num_items` and `device` it was built
+  for; `hubs` bool [num_items] (dynamic=True, else None): the items that are the plain top-1 of at least one bank query."""
+
+  def __init__(self, lse, beta, bank_size, hubs=None):
+    self.lse, self.beta, self.bank_size, self.hubs = lse, beta, bank_size, hubs
+    self.num_items, self.device = lse.shape[0], lse.device
+
+
+def _check_beta(beta):
+  if isinstance(beta, bool) or not isinstance(beta, float) or not 0 < beta < math.inf:
+    raise ValueError('hub_norm: beta must be a float with 0 < beta < inf, got %r' % (beta,))
+
+
+def _check_dynamic(dynamic, norm, who):
+  """The `dynamic` of a call with norm= -> whether QB-Norm's per-query rule applies: None follows the norm (it applies
+  when the norm carries `hubs`), False normalises every query, True demands a norm built with dynamic=True."""
+  if dynamic is not None and not isinstance(dynamic, bool):
+    raise ValueError('%s: dynamic must be None, False or True, got %r' % (who, dynamic))
+  if norm is None:
+    if dynamic:
+      raise ValueError('%s: dynamic=True needs norm=' % who)
+    return False
+  if dynamic and norm.hubs is None:
+    raise ValueError('%s: dynamic=True needs a norm built with hub_norm(..., dynamic=True)' % who)
+  return norm.hubs is not None if dynamic is None else dynamic
+
+
+def _pick(use, normed, plain):
+  """Per query row: the normalised result where `use`, else the plain one (tensors of equal shape, rows first)."""
+  return torch.where(use.reshape((-1,) + (1,) * (normed.dim() - 1)), normed, plain)
 
 
 class VideoIndex:
@@ -269,13 +323,73 @@ class VideoIndex:
     if exclude.device != self.device:
       raise ValueError('search: exclude must be on the index device %s, got %s' % (self.device, exclude.device))
 
-  def search(self, embds, weights, k=10, subset=None, exclude=None):
+  def _norm(self, norm, who):
+    if not isinstance(norm, HubNorm):
+      raise ValueError('%s: norm must come from VideoIndex.hub_norm, got %s' % (who, type(norm).__name__))
+    if norm.num_items != self.num_items:
+      raise ValueError('%s: the norm was built for %d items, the index holds %d' % (who, norm.num_items, self.num_items))
+    if norm.device != self.device:
+      raise ValueError('%s: the norm is on %s, the index on %s' % (who, norm.device, self.device))
+
+  def hub_norm(self, bank_embds, bank_weights, beta, dynamic=False):
+    """The querybank normaliser of this index (inverted softmax, the static half of QB-Norm): bank queries in either layout
+    of `search`, NB >= 1 of them, and a temperature beta (a Python float, 0 < beta < inf) -> HubNorm with
+    lse[g] = log sum_b exp(fl(beta * score(b, g))) per stored item, in fp32 (mmt_search_col_lse).  Passed as norm= to
+    `search`, `rank_counts`, `ranks`, `target_scores` and `threshold_counts` it replaces score(q, g) by
+    score'(q, g) = fl(fl(beta * score(q, g)) - lse[g]), the log of the inverted-softmax probability.  The bank streams
+    through in batches within _BATCH_BYTES; lse[g] does not depend on the batching, on num_items or on g's position.
+    dynamic=True also records `hubs`, the items that are the plain top-1 of a bank query (one search(k=1) of the bank):
+    a call with such a norm then normalises only the queries whose own plain top-1 is a hub (QB-Norm's dynamic inverted
+    softmax).  Like a subset, a norm describes the num_items of this moment: after a further `add` it is refused."""
+    _check_beta(beta)
+    if not isinstance(dynamic, bool):
+      raise ValueError('hub_norm: dynamic must be False or True, got %r' % (dynamic,))
+    if self.num_items == 0:
+      raise ValueError('hub_norm: the index holds no items')
+    b, bw = self._queries(bank_embds, bank_weights)
+    if b.shape[0] < 1:
+      raise ValueError('hub_norm: the bank holds no queries')
+    hubs = None
+    if dynamic:
+      top1 = self._search(b, bw, 1, None, None)[1][:, 0]
+      hubs = torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
+    return HubNorm(self._col_lse(b, bw, beta), beta, b.shape[0], hubs)
+
+  def _col_lse(self, b, bw, beta):
+    """`hub_norm` behind its checks: b (NB, M, d) / bw (NB, M) fp32 on the index device -> lse fp32 [num_items].  The bank
+    goes through in batches of whole 64-row blocks; the running (M, S) pair per item carries from one to the next."""
+    nb, nv, m, d = b.shape[0], self.num_items, self.num_experts, self.dim
+    L = _lib.lib()
+    fn, name = ((L.mmt_search_col_lse_bf16, 'mmt_search_col_lse_bf16') if self.dtype == torch.bfloat16 else
+                (L.mmt_search_col_lse, 'mmt_search_col_lse'))
+    with torch.cuda.device(self.device):
+      lse = torch.empty(nv, device=self.device, dtype=torch.float32)
+      state = torch.empty(2, nv, device=self.device, dtype=torch.float32)
+      per_row = m * d * 4 + -(-nv // 8)  # folded row + its share of the block's (m, p) pairs: 8 bytes per item / 64 rows
+      batch = max(64, (_BATCH_BYTES // per_row) // 64 * 64)
+      ws = torch.empty(L.mmt_col_lse_workspace_floats(min(nb, batch), nv), device=self.device, dtype=torch.float32)
+      for r0 in range(0, nb, batch):
+        r1 = min(nb, r0 + batch)
+        operands, _keep = self._operands(b[r0:r1], bw[r0:r1])
+        check(fn(*operands, r1 - r0, nv, m, d, beta, ops._p(ws), ops._p(state), int(r0 == 0),
+                 ops._p(lse if r1 == nb else None), ops._stream()), name)
+    return lse
+
+  def _use_norm(self, q, qw, subset, ex, norm):
+    """QB-Norm's dynamic rule: bool [NQ], True where the query's plain top-1 among its candidates (after subset and
+    exclusions) is one of norm.hubs.  A query without a candidate keeps its plain result."""
+    top1 = self._search(q, qw, 1, subset, ex)[1][:, 0]
+    return (top1 >= 0) & norm.hubs[top1.clamp(min=0)]
+
+  def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None):
     """Queries (NQ, M, d) / (NQ, M), or the text layout (B, M, C, d) / (B, C, M) -> (scores [NQ, k'] float32,
     indices [NQ, k'] int64) on the device, k' = min(k, NV), best first.  subset (VideoIndex.subset): only its items are
     candidates and k' = min(k, subset.count).  exclude: int64 [NQ] or [NQ, E <= 32] on the index device, values
     -1 .. num_items - 1 (-1 = none; duplicates and items outside the subset are fine): items barred for that query; its
     range is checked as that of `rank_counts`' targets, before anything is scored.  A query with fewer than k' candidates
-    left gets score -inf and index -1 in the remaining slots."""
+    left gets score -inf and index -1 in the remaining slots.  norm (VideoIndex.hub_norm): the ranking and the returned
+    scores are those of score' (mmt_search_topk_norm); with a norm that has `hubs`, only the queries whose plain top-1
+    candidate is a hub are normalised and the others keep their plain result (dynamic=False normalises every query)."""
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
       raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
     if self.num_items == 0:
@@ -284,16 +398,28 @@ class VideoIndex:
       self._subset(subset, 'search')
     if exclude is not None:
       self._exclude(exclude)
+    if norm is not None:
+      self._norm(norm, 'search')
+    dynamic = _check_dynamic(dynamic, norm, 'search')
     q, qw = self._queries(embds, weights)
-    return self._search(q, qw, k, subset, _exclusions(exclude, q.shape[0], self.num_items))
+    ex = _exclusions(exclude, q.shape[0], self.num_items)
+    if norm is None:
+      return self._search(q, qw, k, subset, ex)
+    normed = self._search(q, qw, k, subset, ex, norm)
+    if not dynamic:
+      return normed
+    use = self._use_norm(q, qw, subset, ex, norm)
+    plain = self._search(q, qw, k, subset, ex)
+    return _pick(use, normed[0], plain[0]), _pick(use, normed[1], plain[1])
 
-  def _search(self, q, qw, k, subset, ex):
+  def _search(self, q, qw, k, subset, ex, norm=None):
     """`search` behind its argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the index device, ex None or int64 [NQ, E]
-    there.  Nothing here waits for the device."""
+    there, norm None or a HubNorm of this index (every query normalised).  Nothing here waits for the device."""
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     masked = ()  # the extra arguments of the _ex entry points: subset words, exclusions of the batch, E
-    if subset is not None or ex is not None:
-      k = min(k, nv if subset is None else subset.count)  # lists no longer than the candidates: the outputs stay dense
+    if subset is not None or ex is not None or norm is not None:
+      if subset is not None or ex is not None:
+        k = min(k, nv if subset is None else subset.count)  # lists no longer than the candidates: the outputs stay dense
       masked = (None if subset is None else subset.words, ex, 0 if ex is None else ex.shape[1])
     kout = min(k, nv)
     if ex is None:
@@ -316,17 +442,23 @@ class VideoIndex:
         if masked:
           words, ex, e = masked
           out = (ops._p(words), ops._p(None if ex is None else ex[r0:r1]), e) + out
+          if norm is not None:
+            out = out[:3] + (norm.beta, ops._p(norm.lse)) + out[3:]
         out = (n, nv, m, d, k) + out
         if self.dtype == torch.bfloat16:
           hl = torch.empty(2, n, m * d, device=self.device, dtype=torch.bfloat16)  # hi = bf16(qf), lo = bf16(qf - hi)
           check(L.mmt_search_fold_split_bf16(ops._p(q[r0:r1]), ops._p(qw[r0:r1]), n, m, d, ops._p(hl[0]), ops._p(hl[1]),
                                              ops._stream()), 'mmt_search_fold_split_bf16')
           fn = L.mmt_search_topk_bf16_ex if masked else L.mmt_search_topk_bf16
+          if norm is not None:
+            fn = L.mmt_search_topk_bf16_norm
           check(fn(ops._p(hl[0]), ops._p(hl[1]), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights), *out),
                 'mmt_search_topk_bf16')
         else:
           qf = _fold(q[r0:r1], qw[r0:r1])
           fn = L.mmt_search_topk_ex if masked else L.mmt_search_topk
+          if norm is not None:
+            fn = L.mmt_search_topk_norm
           check(fn(ops._p(qf), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights), *out), 'mmt_search_topk')
     return scores, indices
 
@@ -340,18 +472,24 @@ class VideoIndex:
     if targets.dim() not in (1, 2) or targets.dim() == 2 and targets.shape[1] < 1:
       raise ValueError('ranks: targets [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(targets.shape),))
 
-  def rank_counts(self, embds, weights, targets, subset=None):
+  def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
     """Queries as for `search`; targets [NQ] or [NQ, T] int64 on the index device, values -1 .. num_items - 1 ->
     (greater, equal), int32 of targets' shape: how many of the num_items stored items score above / exactly equal to item
     targets[q, t] for query q (the item itself is one of the equal ones); 0 / 0 where the target is -1.  The range of the
     targets is checked here (one small reduction and a host sync); nothing is scored before it passes.  subset
     (VideoIndex.subset): only its items are counted; a target outside it is still scored but does not count itself, so
-    its `equal` may be 0."""
+    its `equal` may be 0.  norm (VideoIndex.hub_norm): the counts are those of score' -- the target's score' from the
+    threshold pass, then the count pass against it (mmt_search_thresholds_norm, mmt_search_count_norm); with a norm that
+    has `hubs` only the queries whose plain top-1 candidate is a hub, the others keep their plain counts (dynamic=False
+    normalises every query)."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
     if subset is not None:
       self._subset(subset, 'ranks')
+    if norm is not None:
+      self._norm(norm, 'ranks')
+    dynamic = _check_dynamic(dynamic, norm, 'ranks')
     q, qw = self._queries(embds, weights)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     if targets.shape[0] != nq:
@@ -360,11 +498,18 @@ class VideoIndex:
     if nq == 0:
       return tuple(torch.empty(shape, device=self.device, dtype=torch.int32) for _ in range(2))
     tg = targets.reshape(nq, -1).contiguous()
-    greater = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
-    equal = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
     lo, hi = (int(v) for v in torch.aminmax(tg))
     if lo < -1 or hi >= nv:
       raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (nv - 1, lo, hi))
+    if norm is not None:
+      normed = self._threshold_counts(q, qw, self._target_scores(q, qw, tg, norm), subset, norm)
+      if dynamic:
+        use = self._use_norm(q, qw, subset, None, norm)
+        plain = self.rank_counts(q, qw, tg, subset=subset)
+        normed = tuple(_pick(use, a, b) for a, b in zip(normed, plain))
+      return normed[0].reshape(shape), normed[1].reshape(shape)
+    greater = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
+    equal = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
     L = _lib.lib()
     bf16 = self.dtype == torch.bfloat16
     with torch.cuda.device(self.device):
@@ -420,13 +565,17 @@ class VideoIndex:
     batch = max(64, (_BATCH_BYTES // per_row) // 64 * 64)
     return [(r0, min(nq, r0 + batch)) for r0 in range(0, nq, batch)]
 
-  def target_scores(self, embds, weights, targets):
+  def target_scores(self, embds, weights, targets, norm=None, dynamic=None):
     """Queries as for `search`; targets as for `rank_counts` -> float32 of targets' shape on the device:
     score(q, targets[q, t]) with the very bits `search` returns for that pair (the threshold pass of `rank_counts` on its
-    own: mmt_search_thresholds), NaN where the target is -1."""
+    own: mmt_search_thresholds), NaN where the target is -1.  norm (VideoIndex.hub_norm): score'(q, targets[q, t]), with
+    the bits `search(norm=)` returns; the dynamic rule as there, the plain top-1 taken over all items."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
+    if norm is not None:
+      self._norm(norm, 'ranks')
+    dynamic = _check_dynamic(dynamic, norm, 'ranks')
     q, qw = self._queries(embds, weights)
     if targets.shape[0] != q.shape[0]:
       raise ValueError('ranks: %d queries but targets %s' % (q.shape[0], tuple(targets.shape)))
@@ -434,11 +583,16 @@ class VideoIndex:
       lo, hi = (int(v) for v in torch.aminmax(targets))
       if lo < -1 or hi >= self.num_items:
         raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
-    return self._target_scores(q, qw, targets)
+    if norm is None:
+      return self._target_scores(q, qw, targets)
+    normed = self._target_scores(q, qw, targets, norm)
+    if not dynamic or q.shape[0] == 0:
+      return normed
+    return _pick(self._use_norm(q, qw, None, None, norm), normed, self._target_scores(q, qw, targets))
 
-  def _target_scores(self, q, qw, targets):
-    """`target_scores` behind its checks; a target outside 0 .. num_items - 1 gives NaN.  Nothing here waits for the
-    device."""
+  def _target_scores(self, q, qw, targets, norm=None):
+    """`target_scores` behind its checks; a target outside 0 .. num_items - 1 gives NaN; norm None or a HubNorm of this
+    index (every query normalised).  Nothing here waits for the device."""
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     tg = targets.reshape(nq, -1).contiguous()
     thr = torch.empty(tg.shape, device=self.device, dtype=torch.float32)
@@ -447,6 +601,11 @@ class VideoIndex:
     L = _lib.lib()
     fn, name = ((L.mmt_search_thresholds_bf16, 'mmt_search_thresholds_bf16') if self.dtype == torch.bfloat16 else
                 (L.mmt_search_thresholds, 'mmt_search_thresholds'))
+    extra = ()
+    if norm is not None:
+      fn, name = ((L.mmt_search_thresholds_bf16_norm, 'mmt_search_thresholds_bf16_norm') if self.dtype == torch.bfloat16
+                  else (L.mmt_search_thresholds_norm, 'mmt_search_thresholds_norm'))
+      extra = (norm.beta, ops._p(norm.lse))
     t_all = tg.shape[1]
     with torch.cuda.device(self.device):
       for r0, r1 in self._batches(nq, min(MAX_T, t_all)):
@@ -456,16 +615,17 @@ class VideoIndex:
           whole = t1 - t0 == t_all  # a column slice of a wider list is not contiguous: copy in and out
           tgs = tg[r0:r1] if whole else tg[r0:r1, t0:t1].contiguous()
           out = thr[r0:r1] if whole else torch.empty(r1 - r0, t1 - t0, device=self.device, dtype=torch.float32)
-          check(fn(*operands, r1 - r0, nv, m, d, ops._p(tgs), t1 - t0, ops._p(out), ops._stream()), name)
+          check(fn(*operands, r1 - r0, nv, m, d, ops._p(tgs), t1 - t0, *extra, ops._p(out), ops._stream()), name)
           if not whole:
             thr[r0:r1, t0:t1] = out
     return thr.reshape(targets.shape)
 
-  def threshold_counts(self, embds, weights, thresholds, subset=None):
+  def threshold_counts(self, embds, weights, thresholds, subset=None, norm=None, dynamic=None):
     """Queries as for `search`; thresholds float32 [NQ] or [NQ, T] on the index device -> (greater, equal), int32 of
     thresholds' shape: how many stored items score above / exactly equal to thresholds[q, t] for query q (plain float
     compares; a NaN threshold counts nothing) -- the count pass of `rank_counts` against given values (mmt_search_count).
-    Fed with `target_scores` it gives `rank_counts`.  subset: only its items are counted."""
+    Fed with `target_scores` it gives `rank_counts`.  subset: only its items are counted.  norm (VideoIndex.hub_norm): the
+    items' score' is what is compared (mmt_search_count_norm); the dynamic rule as in `rank_counts`."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     if not torch.is_tensor(thresholds) or thresholds.dtype != torch.float32:
@@ -477,13 +637,23 @@ class VideoIndex:
       raise ValueError('ranks: thresholds [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(thresholds.shape),))
     if subset is not None:
       self._subset(subset, 'ranks')
+    if norm is not None:
+      self._norm(norm, 'ranks')
+    dynamic = _check_dynamic(dynamic, norm, 'ranks')
     q, qw = self._queries(embds, weights)
     if thresholds.shape[0] != q.shape[0]:
       raise ValueError('ranks: %d queries but thresholds %s' % (q.shape[0], tuple(thresholds.shape)))
-    return self._threshold_counts(q, qw, thresholds, subset)
+    if norm is None:
+      return self._threshold_counts(q, qw, thresholds, subset)
+    normed = self._threshold_counts(q, qw, thresholds, subset, norm)
+    if not dynamic or q.shape[0] == 0:
+      return normed
+    use = self._use_norm(q, qw, subset, None, norm)
+    return tuple(_pick(use, a, b) for a, b in zip(normed, self._threshold_counts(q, qw, thresholds, subset)))
 
-  def _threshold_counts(self, q, qw, thresholds, subset):
-    """`threshold_counts` behind its checks.  Nothing here waits for the device."""
+  def _threshold_counts(self, q, qw, thresholds, subset, norm=None):
+    """`threshold_counts` behind its checks; norm None or a HubNorm of this index (every query normalised).  Nothing here
+    waits for the device."""
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     thr = thresholds.reshape(nq, -1).contiguous()
     greater = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
@@ -493,6 +663,11 @@ class VideoIndex:
     L = _lib.lib()
     fn, name = ((L.mmt_search_count_bf16, 'mmt_search_count_bf16') if self.dtype == torch.bfloat16 else
                 (L.mmt_search_count, 'mmt_search_count'))
+    extra = ()
+    if norm is not None:
+      fn, name = ((L.mmt_search_count_bf16_norm, 'mmt_search_count_bf16_norm') if self.dtype == torch.bfloat16 else
+                  (L.mmt_search_count_norm, 'mmt_search_count_norm'))
+      extra = (norm.beta, ops._p(norm.lse))
     words = None if subset is None else subset.words
     t_all = thr.shape[1]
     t_max = min(MAX_T, t_all)
@@ -507,19 +682,19 @@ class VideoIndex:
           ts = thr[r0:r1] if whole else thr[r0:r1, t0:t1].contiguous()
           gs = greater[r0:r1] if whole else torch.empty(n, t1 - t0, device=self.device, dtype=torch.int32)
           es = equal[r0:r1] if whole else torch.empty_like(gs)
-          check(fn(*operands, n, nv, m, d, ops._p(ts), t1 - t0, ops._p(words), ops._p(ws), ops._p(gs), ops._p(es),
+          check(fn(*operands, n, nv, m, d, ops._p(ts), t1 - t0, ops._p(words), *extra, ops._p(ws), ops._p(gs), ops._p(es),
                    ops._stream()), name)
           if not whole:
             greater[r0:r1, t0:t1] = gs
             equal[r0:r1, t0:t1] = es
     return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
 
-  def ranks(self, embds, weights, targets, subset=None):
+  def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
     """The reference's tie-averaged 0-based rank (model/metric.py:90-121) of item targets[q, t] among the stored items for
     query q: greater + (equal - 1) / 2 from `rank_counts`, +inf where the target is -1.  float64 on the device, of
     targets' shape (float32 would not hold counts above 2^24).  subset: the rank among its items, +inf for a target that
-    is not one of them."""
-    greater, equal = self.rank_counts(embds, weights, targets, subset=subset)
+    is not one of them.  norm, dynamic: as `rank_counts` -- the rank under the querybank-normalised score."""
+    greater, equal = self.rank_counts(embds, weights, targets, subset=subset, norm=norm, dynamic=dynamic)
     ranks = greater.double() + (equal.double() - 1) / 2
     none = targets < 0
     if subset is not None:
@@ -556,6 +731,16 @@ class ShardedSubset:
   def __init__(self, parts, mask, count):
     self.parts, self.mask, self.count = parts, mask, count
     self.num_items, self.device = mask.shape[0], mask.device
+
+
+class ShardedHubNorm:
+  """The querybank normaliser of a ShardedVideoIndex (ShardedVideoIndex.hub_norm): `parts[s]` is shard s's HubNorm in its
+  own item numbers on its own device (None for a shard without items); `lse` fp32 [num_items] and `hubs` (bool
+  [num_items], or None) in global item order on the primary device; `beta`, `bank_size`, `num_items`, `device`."""
+
+  def __init__(self, parts, lse, beta, bank_size, hubs=None):
+    self.parts, self.lse, self.beta, self.bank_size, self.hubs = parts, lse, beta, bank_size, hubs
+    self.num_items, self.device = lse.shape[0], lse.device
 
 
 class _Shard:
@@ -711,10 +896,54 @@ class ShardedVideoIndex:
     if subset.device != self.device or len(subset.parts) != len(self.shards):
       raise ValueError('%s: the subset belongs to another index' % who)
 
-  def search(self, embds, weights, k=10, subset=None, exclude=None):
+  def _norm(self, norm, who):
+    if not isinstance(norm, ShardedHubNorm):
+      raise ValueError('%s: norm must come from ShardedVideoIndex.hub_norm, got %s' % (who, type(norm).__name__))
+    if norm.num_items != self.num_items:
+      raise ValueError('%s: the norm was built for %d items, the index holds %d' % (who, norm.num_items, self.num_items))
+    if norm.device != self.device or len(norm.parts) != len(self.shards):
+      raise ValueError('%s: the norm belongs to another index' % who)
+
+  def hub_norm(self, bank_embds, bank_weights, beta, dynamic=False):
+    """VideoIndex.hub_norm over all shards -> ShardedHubNorm: the bank (given on the primary) is copied to every shard,
+    which computes the lse of its own items; lse[g] does not depend on where item g is stored, so `lse` -- and every
+    result under norm= -- is bit-identical to that of one VideoIndex.  dynamic=True: `hubs` from one sharded search(k=1)
+    of the bank."""
+    _check_beta(beta)
+    if not isinstance(dynamic, bool):
+      raise ValueError('hub_norm: dynamic must be False or True, got %r' % (dynamic,))
+    if self.num_items == 0:
+      raise ValueError('hub_norm: the index holds no items')
+    b, bw = self._queries(bank_embds, bank_weights)
+    if b.shape[0] < 1:
+      raise ValueError('hub_norm: the bank holds no queries')
+    hubs = None
+    if dynamic:
+      top1 = self._search(b, bw, 1, None, None, None)[1][:, 0]
+      hubs = torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
+    lse = torch.empty(self.num_items, device=self.device, dtype=torch.float32)
+    parts = []
+    for sh in self.shards:
+      part = None
+      if sh.num_items:
+        ids = sh.ids[:sh.num_items]
+        with torch.cuda.device(sh.device):
+          mine = sh.index._col_lse(b.to(sh.device), bw.to(sh.device), beta)
+          part = HubNorm(mine, beta, b.shape[0], None if hubs is None else hubs[ids].to(sh.device))
+        lse[ids] = mine.to(self.device)
+      parts.append(part)
+    return ShardedHubNorm(parts, lse, beta, b.shape[0], hubs)
+
+  def _use_norm(self, q, qw, subset, ex, norm):
+    """VideoIndex._use_norm on the global item numbers."""
+    top1 = self._search(q, qw, 1, subset, ex, None)[1][:, 0]
+    return (top1 >= 0) & norm.hubs[top1.clamp(min=0)]
+
+  def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None):
     """VideoIndex.search over all shards: (scores [NQ, k'] float32, indices [NQ, k'] int64 global item numbers) on the
     primary, k' = min(k, num_items) or min(k, subset.count).  Every shard searches its own items for its best min(k', its
-    candidates); the lists are copied to the primary and merged there in one launch."""
+    candidates); the lists are copied to the primary and merged there in one launch.  norm (ShardedVideoIndex.hub_norm),
+    dynamic: as VideoIndex.search; every shard ranks by score' with its own part of the norm."""
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
       raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
     if self.num_items == 0:
@@ -723,9 +952,22 @@ class ShardedVideoIndex:
       self._subset(subset, 'search')
     if exclude is not None:
       VideoIndex._exclude(self, exclude)
+    if norm is not None:
+      self._norm(norm, 'search')
+    dynamic = _check_dynamic(dynamic, norm, 'search')
     q, qw = self._queries(embds, weights)
+    ex = _exclusions(exclude, q.shape[0], self.num_items)
+    out = self._search(q, qw, k, subset, ex, norm)
+    if not dynamic or q.shape[0] == 0:
+      return out
+    use = self._use_norm(q, qw, subset, ex, norm)
+    plain = self._search(q, qw, k, subset, ex, None)
+    return _pick(use, out[0], plain[0]), _pick(use, out[1], plain[1])
+
+  def _search(self, q, qw, k, subset, ex, norm):
+    """`search` behind its checks: q, qw on the primary, ex None or int64 [NQ, E] global numbers there, norm None or a
+    ShardedHubNorm of this index (every query normalised)."""
     nq = q.shape[0]
-    ex = _exclusions(exclude, nq, self.num_items)
     kout = min(k, self.num_items if subset is None else subset.count)
     scores = torch.empty(nq, kout, device=self.device, dtype=torch.float32)
     indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
@@ -740,7 +982,8 @@ class ShardedVideoIndex:
     for i, (s, sh) in enumerate(live):
       ex_s = None if ex is None else self._local(ex, s).to(sh.device)
       with torch.cuda.device(sh.device):
-        part = sh.index._search(q.to(sh.device), qw.to(sh.device), kout, None if subset is None else subset.parts[s], ex_s)
+        part = sh.index._search(q.to(sh.device), qw.to(sh.device), kout, None if subset is None else subset.parts[s], ex_s,
+                                None if norm is None else norm.parts[s])
       width = part[0].shape[1]
       st_scores[i, :, :width].copy_(part[0])
       st_index[i, :, :width].copy_(part[1])
@@ -749,15 +992,18 @@ class ShardedVideoIndex:
                                               ops._p(scores), ops._p(indices), ops._stream()), 'mmt_search_merge_lists')
     return scores, indices
 
-  def rank_counts(self, embds, weights, targets, subset=None):
+  def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
     """VideoIndex.rank_counts over all shards: each shard scores the targets it holds (target_scores), the primary picks
     the owner's value per (query, target), each shard counts its items against those thresholds (threshold_counts) and
-    the int32 counts are summed on the primary."""
+    the int32 counts are summed on the primary.  norm (ShardedVideoIndex.hub_norm), dynamic: as VideoIndex.rank_counts."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     VideoIndex._targets(self, targets)
     if subset is not None:
       self._subset(subset, 'ranks')
+    if norm is not None:
+      self._norm(norm, 'ranks')
+    dynamic = _check_dynamic(dynamic, norm, 'ranks')
     q, qw = self._queries(embds, weights)
     nq = q.shape[0]
     if targets.shape[0] != nq:
@@ -769,6 +1015,14 @@ class ShardedVideoIndex:
     lo, hi = (int(v) for v in torch.aminmax(tg))
     if lo < -1 or hi >= self.num_items:
       raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
+    out = self._rank_counts(q, qw, tg, subset, norm)
+    if dynamic:
+      use = self._use_norm(q, qw, subset, None, norm)
+      out = tuple(_pick(use, a, b) for a, b in zip(out, self._rank_counts(q, qw, tg, subset, None)))
+    return out[0].reshape(shape), out[1].reshape(shape)
+
+  def _rank_counts(self, q, qw, tg, subset, norm):
+    """`rank_counts` behind its checks: tg int64 [NQ, T] global numbers on the primary -> (greater, equal) int32 [NQ, T]."""
     live = self._live()
     queries = {}
     thr = torch.full(tg.shape, float('nan'), device=self.device, dtype=torch.float32)
@@ -776,7 +1030,7 @@ class ShardedVideoIndex:
       local = self._local(tg, s)
       queries[s] = (q.to(sh.device), qw.to(sh.device))
       with torch.cuda.device(sh.device):
-        mine = sh.index._target_scores(*queries[s], local.to(sh.device))
+        mine = sh.index._target_scores(*queries[s], local.to(sh.device), None if norm is None else norm.parts[s])
       thr = torch.where(local >= 0, mine.to(self.device), thr)
     greater = torch.zeros(tg.shape, device=self.device, dtype=torch.int32)
     equal = torch.zeros(tg.shape, device=self.device, dtype=torch.int32)
@@ -785,15 +1039,15 @@ class ShardedVideoIndex:
       if subset is not None and part is None:
         continue  # no allowed item here: nothing to count
       with torch.cuda.device(sh.device):
-        gs, es = sh.index._threshold_counts(*queries[s], thr.to(sh.device), part)
+        gs, es = sh.index._threshold_counts(*queries[s], thr.to(sh.device), part, None if norm is None else norm.parts[s])
       greater += gs.to(self.device)
       equal += es.to(self.device)
-    return greater.reshape(shape), equal.reshape(shape)
+    return greater, equal
 
-  def ranks(self, embds, weights, targets, subset=None):
+  def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
     """VideoIndex.ranks: greater + (equal - 1) / 2 from `rank_counts`, float64 on the primary, +inf where the target is -1
-    or outside the subset."""
-    greater, equal = self.rank_counts(embds, weights, targets, subset=subset)
+    or outside the subset.  norm, dynamic: as `rank_counts`."""
+    greater, equal = self.rank_counts(embds, weights, targets, subset=subset, norm=norm, dynamic=dynamic)
     ranks = greater.double() + (equal.double() - 1) / 2
     none = targets < 0
     if subset is not None:

@@ -31,7 +31,16 @@ rounds, every variant once per round, interleaved; median and spread.  Default o
 --shards N times search.ShardedVideoIndex with N shards in place of the single index of the default mode: the shards go to
 the visible devices in turn (cuda:0, cuda:1, ..., again from cuda:0 when there are fewer devices than shards), queries
 and results on cuda:0.  On one device the difference to the plain run is the cost of the merge launch, the staged lists
-and of scanning N shorter galleries; with --skip-materialised only the index is timed."""
+and of scanning N shorter galleries; with --skip-materialised only the index is timed.
+
+--norm BETA times querybank hubness normalisation (VideoIndex.hub_norm, search(norm=)) with the queries as the bank, per
+index dtype (--gallery-dtype, both = the two indexes): the lse pass over the bank (hub_norm: mmt_search_col_lse), the
+normalised search and the plain search of the same build, which is also the plain scan of the same bank.  --runs rounds,
+every variant once per round, interleaved; median and spread, and the two costs as ratios: normalised over plain search,
+lse pass over plain scan.  --baseline-json FILE... records beside them the plain search of another build (default-mode
+outputs of its own search_bench, --skip-materialised, run in the same session) and --same-build-json FILE... such runs
+of this build, taken alternately with them.  The result goes under the key "norm" of
+--out (default profiles/search_bench.json), whose other content is kept."""
 import argparse
 import json
 import math
@@ -220,6 +229,41 @@ def subset_mode(q, qw, g, gw, flop, a):
   return row
 
 
+def norm_mode(q, qw, g, gw, flop, a):
+  """hub_norm (the lse pass), search(norm=) and the plain search, per index dtype; the bank is the queries."""
+  nv = g.shape[0]
+  dtypes = ('float32', 'bfloat16') if a.gallery_dtype == 'both' else (a.gallery_dtype,)
+  fns = {}
+  for n in dtypes:
+    index = VideoIndex.empty(nv, M, D, g.device, dtype=getattr(torch, n))
+    for at in range(0, nv, 8192):
+      index.add(g[at:at + 8192], gw[at:at + 8192])
+    norm = index.hub_norm(q, qw, a.norm)
+    fns[n + '/search'] = lambda index=index: index.search(q, qw, k=K)
+    fns[n + '/search_norm'] = lambda index=index, norm=norm: index.search(q, qw, k=K, norm=norm)
+    fns[n + '/col_lse'] = lambda index=index: index.hub_norm(q, qw, a.norm)
+  ts = {n: [] for n in fns}
+  mem = {n: 0 for n in fns}
+  out = {}
+  for _ in range(a.runs):
+    for n, fn in fns.items():
+      t, _, m, out[n] = timed(fn, a.min_seconds)
+      ts[n].append(t)
+      mem[n] = max(mem[n], m)
+  row = {'beta': a.norm, 'bank_rows': q.shape[0]}
+  for n in fns:
+    med = float(np.median(ts[n]))
+    row[n] = dict(seconds_median=med, seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n], tflops=flop / med / 1e12,
+                  peak_mem_growth_bytes=mem[n])
+  for n in dtypes:
+    plain = row[n + '/search']['seconds_median']
+    moved = (out[n + '/search'][1] != out[n + '/search_norm'][1]).any(1).float().mean()
+    row[n + '/summary'] = dict(search_norm_over_search=row[n + '/search_norm']['seconds_median'] / plain,
+                               col_lse_over_search=row[n + '/col_lse']['seconds_median'] / plain,
+                               rows_reordered_by_the_norm=float(moved))
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--shapes', default='S1,S2,S3')
@@ -236,6 +280,10 @@ def main():
                   'query against the unmasked search')
   ap.add_argument('--shards', type=int, default=0, metavar='N', help='time a ShardedVideoIndex of N (1..32) shards over '
                   'the visible devices, cycling, in place of the single index (default mode only)')
+  ap.add_argument('--norm', type=float, default=None, metavar='BETA', help='time hub_norm (the lse pass, bank = the queries) '
+                  'and search(norm=) against the plain search')
+  ap.add_argument('--baseline-json', nargs='+', default=[], help='with --norm: default-mode results of another build')
+  ap.add_argument('--same-build-json', nargs='+', default=[], help='with --norm: default-mode results of this build')
   a = ap.parse_args()
   masked = a.subset is not None or a.exclude > 0
   if a.subset is not None and not 0 < a.subset <= 1:
@@ -244,6 +292,10 @@ def main():
     raise SystemExit('--exclude wants 0..32')
   if not 0 <= a.shards <= 32 or a.shards and (masked or a.ranks or a.gallery_dtype == 'both'):
     raise SystemExit('--shards wants 1..32 and the default mode (no --ranks, --subset, --exclude, --gallery-dtype both)')
+  if a.norm is not None and (masked or a.ranks or a.shards or not 0 < a.norm < math.inf):
+    raise SystemExit('--norm wants 0 < BETA < inf and no --ranks, --subset, --exclude, --shards')
+  if a.norm is not None and a.out is None:
+    a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_bench.json')
   if masked and a.out is None:
     a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_subset_bench.json')
   if a.ranks and a.out is None:
@@ -256,6 +308,17 @@ def main():
     res['gallery_dtype'] = a.gallery_dtype
   if a.ranks:
     res.update(mode='ranks', T=1, runs=a.runs, min_seconds=a.min_seconds)
+  if a.norm is not None:
+    res.update(mode='norm', gallery_dtype=a.gallery_dtype, runs=a.runs, min_seconds=a.min_seconds)
+    for key, files in (('baseline_plain_search', a.baseline_json), ('same_build_plain_search', a.same_build_json)):
+      runs = {}
+      for path in files:
+        with open(path) as f:
+          for name, row in json.load(f)['shapes'].items():
+            runs.setdefault(name, []).append(row['fused']['seconds'])
+      if runs:
+        res[key] = {name: dict(seconds_runs=v, seconds_median=float(np.median(v)), seconds_spread=max(v) - min(v))
+                    for name, v in runs.items()}
   if masked:
     res.update(mode='subset', subset_fraction=a.subset, exclude=a.exclude, runs=a.runs, min_seconds=a.min_seconds)
   for name in a.shapes.split(','):
@@ -268,8 +331,8 @@ def main():
     qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
     flop = 2.0 * nq * nv * M * D
     row = {'NQ': nq, 'NV': nv, 'flop': flop}
-    if masked or a.ranks or a.gallery_dtype == 'both':
-      mode = subset_mode if masked else ranks_mode if a.ranks else both_dtypes
+    if masked or a.ranks or a.norm is not None or a.gallery_dtype == 'both':
+      mode = norm_mode if a.norm is not None else subset_mode if masked else ranks_mode if a.ranks else both_dtypes
       row.update(mode(q, qw, g, gw, flop, a))
       res['shapes'][name] = row
       print(name, json.dumps(row), flush=True)
@@ -304,6 +367,11 @@ def main():
     torch.cuda.empty_cache()
   if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.norm is not None and os.path.exists(a.out):  # joins the default-mode results of that file
+      with open(a.out) as f:
+        kept = json.load(f)
+      kept['norm'] = res
+      res = kept
     with open(a.out, 'w') as f:
       json.dump(res, f, indent=1)
   print(json.dumps(res))
