@@ -633,6 +633,34 @@ int mmt_search_count_norm(const float* qf, const float* qw, const float* gf, con
 int mmt_search_count_bf16_norm(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
                                const float* gw, int NQ, int NV, int M, int d, const float* thr, int T, const uint32_t* subset,
                                float beta, const float* lse, int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
+/* Range search (search_range.hip): every item g with score(q, g) >= thr[q] -- however many -- as a CSR over the queries,
+ * without the N_query x N_gallery matrix: near-duplicate joins, all matches of a query, lists deeper than k = 128.  Two
+ * passes of the scan of mmt_search_count over the same operands, the caller's prefix sum between them:
+ * mmt_range_workspace_ints: int32 workspace of the two passes, NQ * ceil(NV / chunk) (one slot per query and gallery chunk
+ *   of the launch); MMT_ERR_ARG if a size is out of range.
+ * mmt_search_range_count / mmt_search_range_count_bf16: query operands and gallery as mmt_search_count / _bf16; thr fp32
+ *   [NQ], one threshold per query (a plain float compare: NaN hits nothing, -inf every item); subset nullable, words as
+ *   above: only allowed items hit.  row_counts int64 [NQ]: the hits of each query.  ws is left holding, per query, the
+ *   exclusive prefix of its chunk counts in chunk order: the fill pass reads it as it is.
+ * mmt_search_range_fill / mmt_search_range_fill_bf16: the same operands, thr and subset; ws as the count pass of the very
+ *   same arguments left it; offsets int64 [NQ + 1], the exclusive prefix of row_counts (offsets[0] may be any base into
+ *   the outputs).  Writes query q's hits to indices (int64 item numbers) / scores (fp32, the bits mmt_search_topk gives
+ *   the pair) [offsets[q], offsets[q + 1]), by ascending item number.  No atomics, one writer per slot; a position is
+ *   clamped against the start of the row's next chunk, so the pass writes nothing outside [offsets[0], offsets[NQ]).
+ * Gates as mmt_search_count / _bf16: MMT_ERR_ARG (a null pointer other than subset, a size out of range, d % 4 / d % 8),
+ * MMT_ERR_ALIGN (query or gallery rows or subset words off a 16-byte boundary). */
+int64_t mmt_range_workspace_ints(int NQ, int NV);
+int mmt_search_range_count(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                           const float* thr, const uint32_t* subset, int32_t* ws, int64_t* row_counts, void* stream);
+int mmt_search_range_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                const float* gw, int NQ, int NV, int M, int d, const float* thr, const uint32_t* subset,
+                                int32_t* ws, int64_t* row_counts, void* stream);
+int mmt_search_range_fill(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                          const float* thr, const uint32_t* subset, const int32_t* ws, const int64_t* offsets,
+                          int64_t* indices, float* scores, void* stream);
+int mmt_search_range_fill_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                               const float* gw, int NQ, int NV, int M, int d, const float* thr, const uint32_t* subset,
+                               const int32_t* ws, const int64_t* offsets, int64_t* indices, float* scores, void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

@@ -1,0 +1,243 @@
+// Range search without the N_query x N_gallery matrix: every item g with score(q, g) >= thr[q], however many there are,
+// as a CSR over the queries (offsets, item numbers, scores).  Near-duplicate joins, all captions that match a video, all
+// negatives inside a margin, any list deeper than the top-k kernels' k <= 128.
+//
+// The scan is the one of the count kernels (search_rank.hip): block = 64 queries x one gallery chunk (tk_chunk), blocks
+// ordered by xcd_remap, tk_scan_f32 / tk_scan_bf16 + tk_tile_scores leave a 64 x 128 score tile in LDS and a wave takes
+// its 16 rows.  It runs twice over the same operands, with a host-side sum between the passes:
+//   range_kernel<BF16, false, MASKED> : counts.  Per row and tile two ballots of `live && score >= thr[row]` (the two
+//                               64-column halves; a plain float compare: a NaN threshold hits nothing, -inf every live
+//                               item); the popcounts add up in a register of the lane that holds the row (lane l < 16 of
+//                               wave w holds row 16 w + l for the whole block: no LDS, no barrier).  One int32 per (query,
+//                               chunk) goes to the workspace [NQ][n_chunks].
+//   range_offsets_kernel      : one thread per query turns the row's chunk counts into their exclusive prefix in place, in
+//                               chunk order, and writes the row total as int64.  The host sums the rows (torch cumsum)
+//                               into offsets [NQ + 1] and learns the grand total before anything of that size exists.
+//   range_kernel<BF16, true, MASKED>  : fill.  The same scan and predicate, so the same hits.  A hit at lane l of half h
+//                               of row q goes to  offsets[q] + prefix[q][chunk] + (hits of the row in the block's earlier
+//                               tiles) + (hits in lower columns of this tile): popcount of the ballot below the lane, plus
+//                               the first half's popcount for the second half.  It writes the item number (int64) and
+//                               the tile's own score bits.  A block whose 64 rows have no hit in its chunk (the prefix
+//                               says so) returns before its first K loop.
+// No atomics and one writer per slot: bit-reproducible, every row ascending by item number by construction.  Both passes
+// compute the same bits from the same code, so the counts agree; all the same a fill position is clamped against the
+// start of the row's next chunk (the next prefix, or the next row's offset), so a disagreement would show as a wrong
+// answer inside the row's own slots and never as a stray write.
+// MASKED: only items whose bit is set in the packed bitmap (search_subset.hip) are hits; a tile without a set bit is
+// skipped before its K loop, as in rank_kernel<., false, true>.
+#include <type_traits>
+
+#include "search_scan.h"
+
+struct RgArgs {
+  const void* q;           // fp32: Q' [NQ][K]; bf16: hi(Q')
+  const void* q_lo;        // bf16: lo(Q')
+  const float* qw;         // [NQ][M]
+  const void* g;           // [NV][K] fp32 or bf16 bits
+  const float* gw;         // [NV][M]
+  const float* thr;        // [NQ]
+  int32_t* ws;             // [NQ][n_chunks]: the count pass writes hit counts, the offsets kernel their prefix
+  const int64_t* offsets;  // fill: [NQ + 1]
+  int64_t* indices;        // fill: [offsets[NQ]]
+  float* scores;           // fill: [offsets[NQ]]
+  int NQ, NV, M, K, chunk, n_qt, n_chunks;
+};
+
+// The masked passes take an argument type of their own, as RkMaskedArgs: the unmasked kernels keep their argument block.
+struct RgMaskedArgs : RgArgs {
+  const uint32_t* subset;  // bit g & 31 of word g >> 5 allows item g (16-byte aligned)
+};
+
+template <bool BF16, class GRow>
+__device__ __forceinline__ void rg_tile(const RgArgs& a, unsigned char* smem, float* sS, const float* sQw, int q0, GRow grow,
+                                        int tid, int wq, int wg, int l31, int h) {
+  f32x16 acc[2];
+  if constexpr (BF16)
+    tk_scan_bf16(acc, smem, (const bf16_t*)a.q, (const bf16_t*)a.q_lo, (const bf16_t*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg,
+                 l31, h);
+  else
+    tk_scan_f32(acc, smem, (const float*)a.q, (const float*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg, l31, h);
+  __syncthreads();  // the slabs become the score tile
+  tk_tile_scores(acc, sS, sQw, a.gw, a.M, grow, wq, wg, l31, h);
+  __syncthreads();
+}
+
+template <bool BF16, bool FILL, bool MASKED>
+__global__ __launch_bounds__(256) void range_kernel(std::conditional_t<MASKED, RgMaskedArgs, RgArgs> a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int kUnion = BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES;
+  constexpr int kRows = TK_Q / 4;  // rows per wave
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, h = lane >> 5, wq = wave >> 1, wg = wave & 1;
+  float* sS = (float*)smem;              // [TK_Q][TK_SLD]  scores (after the K loop)
+  float* sQw = (float*)(smem + kUnion);  // [TK_Q][MMT_MAX_EXPERTS]
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);  // gallery-chunk-major: an XCD's blocks share their chunk in L2
+  const int chunk = bid / a.n_qt, q0 = (bid % a.n_qt) * TK_Q;
+  const int g_begin = chunk * a.chunk, g_end = min(a.NV, g_begin + a.chunk);
+  const int rows_live = min(a.NQ - q0, TK_Q);
+  // lane l < 16 of wave w holds the state of row 16 w + l for the whole block: its threshold, its hits so far and, for
+  // the fill, where its slots of this chunk begin and how many they are
+  const int my_row = wave * kRows + lane;
+  const bool holder = lane < kRows && my_row < rows_live;
+  const float my_thr = holder ? a.thr[q0 + my_row] : __builtin_nanf("");
+  int my_cnt = 0, my_cap = 0;
+  int64_t my_base = 0;
+  if constexpr (FILL) {
+    if (holder) {
+      const int64_t q = q0 + my_row, off = a.offsets[q];
+      const int32_t* pre = a.ws + q * a.n_chunks + chunk;
+      my_base = off + pre[0];
+      const int64_t next = chunk + 1 < a.n_chunks ? off + pre[1] : a.offsets[q + 1];
+      const int64_t room = next - my_base;  // never beyond the row's next chunk, nor more than the chunk has items
+      my_cap = room < 0 ? 0 : room > g_end - g_begin ? g_end - g_begin : (int)room;
+    }
+    if (!__syncthreads_or(my_cap > 0)) return;  // block-uniform: no row of this block has a hit in this chunk
+  }
+  tk_load_qw(sQw, a.qw, a.NQ, a.M, q0, tid);  // read after the barriers of the first K loop
+  for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
+    uint64_t m0 = ~0ull, m1 = ~0ull;
+    if constexpr (MASKED) {
+      const u32x4 w = *(const u32x4*)(a.subset + (g0 >> 5));
+      m0 = w[0] | (uint64_t)w[1] << 32;
+      m1 = w[2] | (uint64_t)w[3] << 32;
+      if (!(m0 | m1)) continue;  // block-uniform: nothing of this tile can hit
+    }
+    rg_tile<BF16>(a, smem, sS, sQw, q0, [=](int r) { return g0 + r < g_end ? g0 + r : -1; }, tid, wq, wg, l31, h);
+    const bool live0 = g0 + lane < g_end && (!MASKED || ((m0 >> lane) & 1ull));
+    const bool live1 = g0 + 64 + lane < g_end && (!MASKED || ((m1 >> lane) & 1ull));
+    for (int rr = 0; rr < kRows; ++rr) {
+      const int row = wave * kRows + rr;
+      if (row >= rows_live) break;
+      const float s0 = sS[row * TK_SLD + lane], s1 = sS[row * TK_SLD + 64 + lane];
+      const float thr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_thr), rr));
+      const bool hit0 = live0 && s0 >= thr, hit1 = live1 && s1 >= thr;
+      const uint64_t b0 = __ballot(hit0), b1 = __ballot(hit1);
+      const int n0 = __popcll(b0), n1 = __popcll(b1);
+      if constexpr (FILL) {
+        if (b0 | b1) {  // wave-uniform
+          const int seen = __builtin_amdgcn_readlane(my_cnt, rr), cap = __builtin_amdgcn_readlane(my_cap, rr);
+          const int64_t base = (int64_t)(((uint64_t)(unsigned)__builtin_amdgcn_readlane((int)(my_base >> 32), rr) << 32) |
+                                         (unsigned)__builtin_amdgcn_readlane((int)my_base, rr));
+          const uint64_t below = (1ull << lane) - 1;
+          const int p0 = seen + __popcll(b0 & below), p1 = seen + n0 + __popcll(b1 & below);
+          if (hit0 && p0 < cap) {
+            a.indices[base + p0] = g0 + lane;
+            a.scores[base + p0] = s0;
+          }
+          if (hit1 && p1 < cap) {
+            a.indices[base + p1] = g0 + 64 + lane;
+            a.scores[base + p1] = s1;
+          }
+        }
+      }
+      if (lane == rr) my_cnt += n0 + n1;
+    }
+  }
+  if constexpr (!FILL) {
+    if (holder) a.ws[(int64_t)(q0 + my_row) * a.n_chunks + chunk] = my_cnt;
+  }
+}
+
+// One thread per query: the chunk counts become their exclusive prefix, in chunk order; the row total as int64.
+__global__ __launch_bounds__(256) void range_offsets_kernel(int32_t* __restrict__ ws, int NQ, int n_chunks,
+                                                            int64_t* __restrict__ row_counts) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= NQ) return;
+  int32_t* row = ws + (int64_t)q * n_chunks;
+  int run = 0;
+  for (int c = 0; c < n_chunks; ++c) {
+    const int n = row[c];
+    row[c] = run;
+    run += n;
+  }
+  row_counts[q] = run;
+}
+
+namespace {
+bool rg_args_ok(int NQ, int NV, int M, int d, int mult) {
+  return NQ > 0 && NV > 0 && M > 0 && M <= MMT_MAX_EXPERTS && d > 0 && !(d & (mult - 1));
+}
+
+template <bool BF16, bool FILL>
+int rg_launch(RgMaskedArgs a, hipStream_t s) {
+  constexpr size_t lds = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + TK_QW_BYTES;
+  a.chunk = tk_chunk(a.NQ, a.NV);
+  a.n_qt = (a.NQ + TK_Q - 1) / TK_Q;
+  a.n_chunks = (a.NV + a.chunk - 1) / a.chunk;
+  if (a.subset)
+    hipLaunchKernelGGL((range_kernel<BF16, FILL, true>), dim3(a.n_qt * a.n_chunks), dim3(256), lds, s, a);
+  else
+    hipLaunchKernelGGL((range_kernel<BF16, FILL, false>), dim3(a.n_qt * a.n_chunks), dim3(256), lds, s, (RgArgs)a);
+  return a.n_chunks;
+}
+
+template <bool BF16>
+int rg_count(RgMaskedArgs a, int64_t* row_counts, hipStream_t s) {
+  const int n_chunks = rg_launch<BF16, false>(a, s);
+  hipLaunchKernelGGL(range_offsets_kernel, dim3((a.NQ + 255) / 256), dim3(256), 0, s, a.ws, a.NQ, n_chunks, row_counts);
+  return (int)hipGetLastError();
+}
+
+template <bool BF16>
+int rg_fill(RgMaskedArgs a, hipStream_t s) {
+  rg_launch<BF16, true>(a, s);
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" int64_t mmt_range_workspace_ints(int NQ, int NV) {
+  if (NQ <= 0 || NV <= 0) return MMT_ERR_ARG;
+  const int chunk = tk_chunk(NQ, NV);
+  return (int64_t)NQ * ((NV + chunk - 1) / chunk);
+}
+
+extern "C" int mmt_search_range_count(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
+                                      int M, int d, const float* thr, const uint32_t* subset, int32_t* ws,
+                                      int64_t* row_counts, void* stream) {
+  if (!qf || !qw || !gf || !gw || !thr || !ws || !row_counts || !rg_args_ok(NQ, NV, M, d, 4)) return MMT_ERR_ARG;
+  if (((uintptr_t)qf | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  RgMaskedArgs a = {};
+  a.q = qf; a.qw = qw; a.g = gf; a.gw = gw; a.thr = thr; a.ws = ws; a.subset = subset;
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d;
+  return rg_count<false>(a, row_counts, (hipStream_t)stream);
+}
+
+extern "C" int mmt_search_range_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                           const float* gw, int NQ, int NV, int M, int d, const float* thr,
+                                           const uint32_t* subset, int32_t* ws, int64_t* row_counts, void* stream) {
+  if (!q_hi || !q_lo || !qw || !gf || !gw || !thr || !ws || !row_counts || !rg_args_ok(NQ, NV, M, d, 8))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)q_hi | (uintptr_t)q_lo | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  RgMaskedArgs a = {};
+  a.q = q_hi; a.q_lo = q_lo; a.qw = qw; a.g = gf; a.gw = gw; a.thr = thr; a.ws = ws; a.subset = subset;
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d;
+  return rg_count<true>(a, row_counts, (hipStream_t)stream);
+}
+
+extern "C" int mmt_search_range_fill(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
+                                     int M, int d, const float* thr, const uint32_t* subset, const int32_t* ws,
+                                     const int64_t* offsets, int64_t* indices, float* scores, void* stream) {
+  if (!qf || !qw || !gf || !gw || !thr || !ws || !offsets || !indices || !scores || !rg_args_ok(NQ, NV, M, d, 4))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)qf | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  RgMaskedArgs a = {};
+  a.q = qf; a.qw = qw; a.g = gf; a.gw = gw; a.thr = thr; a.ws = const_cast<int32_t*>(ws); a.subset = subset;
+  a.offsets = offsets; a.indices = indices; a.scores = scores;
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d;
+  return rg_fill<false>(a, (hipStream_t)stream);
+}
+
+extern "C" int mmt_search_range_fill_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                          const float* gw, int NQ, int NV, int M, int d, const float* thr,
+                                          const uint32_t* subset, const int32_t* ws, const int64_t* offsets,
+                                          int64_t* indices, float* scores, void* stream) {
+  if (!q_hi || !q_lo || !qw || !gf || !gw || !thr || !ws || !offsets || !indices || !scores ||
+      !rg_args_ok(NQ, NV, M, d, 8))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)q_hi | (uintptr_t)q_lo | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  RgMaskedArgs a = {};
+  a.q = q_hi; a.q_lo = q_lo; a.qw = qw; a.g = gf; a.gw = gw; a.thr = thr; a.ws = const_cast<int32_t*>(ws); a.subset = subset;
+  a.offsets = offsets; a.indices = indices; a.scores = scores;
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d;
+  return rg_fill<true>(a, (hipStream_t)stream);
+}

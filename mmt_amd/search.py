@@ -78,6 +78,17 @@ position, the batching or the shard, so ShardedVideoIndex.hub_norm (one HubNorm 
 on the primary) gives bit-identical results.  A norm with .hubs applies QB-Norm's dynamic rule: a query is normalised only
 if its plain top-1 among its candidates (after subset / exclude) is a hub, else it keeps its plain result; dynamic=False on
 the call normalises every query.  Like a subset, a norm is refused after a further `add`.
+
+    res = index.range_search(q, qw, threshold, subset=None, order='index', max_hits=1 << 27)   # RangeResult, a CSR:
+    res.offsets, res.indices, res.scores, res.counts     # int64 [NQ + 1], int64 [total], float32 [total], int64 [NQ]
+
+The third question, beside "the k best" and "how many beat this one": WHICH items score at least threshold[q] (a float, or
+float32 [NQ]), however many -- near-duplicate joins of a gallery against itself, every caption that matches a video, all
+negatives inside a margin, any list deeper than MAX_K.  Query q's hits are positions offsets[q] .. offsets[q + 1] - 1, by
+ascending item (order='index') or in `search`'s order (order='score'); a score has the bits `search` gives the pair.  Two
+scans with the hit counts summed in between (mmt_search_range_count, mmt_search_range_fill): every hit has a slot of its
+own before it is written, so there are no atomics and the result is bit-reproducible; the total is known -- and held
+against max_hits -- before anything of its size is allocated.  ShardedVideoIndex.range_search is bit-identical.
 """
 import math
 
@@ -90,6 +101,7 @@ MAX_K = 128
 MAX_T = 32  # targets per query and launch of the rank kernels; wider target lists are sliced
 MAX_E = 32  # exclusions per query of a masked search
 _BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 bytes per element either way) + chunk lists
+_MAX_HITS = 1 << 27  # default cap of a range search's total: a guard against a mistyped threshold, not a tuned number
 _DTYPES = {torch.float32: 4, torch.bfloat16: 8}  # storage dtype -> multiple d must have (16-byte folded rows)
 
 
@@ -149,6 +161,33 @@ class HubNorm:
   def __init__(self, lse, beta, bank_size, hubs=None):
     self.lse, self.beta, self.bank_size, self.hubs = lse, beta, bank_size, hubs
     self.num_items, self.device = lse.shape[0], lse.device
+
+
+class RangeResult:
+  """The hits of a range search (VideoIndex.range_search) as a CSR over the queries, on the index device: query q's hits are
+  positions offsets[q] .. offsets[q + 1] - 1 of `indices` (int64 item numbers) and `scores` (float32); `offsets` int64
+  [NQ + 1] with offsets[0] = 0, `counts` int64 [NQ] = offsets[1:] - offsets[:-1]."""
+
+  def __init__(self, offsets, indices, scores):
+    self.offsets, self.indices, self.scores = offsets, indices, scores
+    self.counts = offsets[1:] - offsets[:-1]
+
+
+def _csr_rows(offsets):
+  """offsets int64 [NQ + 1] -> the row of every CSR position, int64 [offsets[-1]]."""
+  counts = offsets[1:] - offsets[:-1]
+  return torch.repeat_interleave(torch.arange(counts.shape[0], device=offsets.device), counts)
+
+
+def _range_result(offsets, indices, scores, order):
+  """A CSR whose rows ascend by item -> RangeResult in the given order.  order='score' is `search`'s order (tk_key of the
+  kernels): descending score with -0 tied to +0, equal scores by ascending item -- two stable torch sorts, by score over
+  everything (which keeps (row, item) order among equal scores), then by row."""
+  if order == 'score' and indices.numel():
+    by_score = torch.argsort(scores + 0.0, descending=True, stable=True)  # -0.0 + 0.0 = +0.0
+    perm = by_score[torch.argsort(_csr_rows(offsets)[by_score], stable=True)]
+    indices, scores = indices[perm], scores[perm]
+  return RangeResult(offsets, indices, scores)
 
 
 def _check_beta(beta):
@@ -689,6 +728,101 @@ class VideoIndex:
             equal[r0:r1, t0:t1] = es
     return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
 
+  def range_search(self, embds, weights, threshold, subset=None, order='index', max_hits=_MAX_HITS):
+    """Queries as for `search`; threshold a Python float, or float32 [NQ] on the index device (one per query) ->
+    RangeResult: for every query ALL items g with score(q, g) >= threshold[q], however many (`search` stops at MAX_K), as a
+    CSR on the device -- offsets int64 [NQ + 1], indices int64 [total], scores float32 [total], counts int64 [NQ]; query q's
+    hits are [offsets[q], offsets[q + 1]).  The compare is a plain float compare: a NaN threshold hits nothing, -inf every
+    candidate.  A score has the very bits `search` and `target_scores` give that pair.  subset (VideoIndex.subset): only
+    its items are candidates.  order='index': each row by ascending item number; order='score': by descending score, equal
+    scores (-0 == +0) by ascending item -- `search`'s order, so a row continues that query's top-k list.
+
+    Two scans (mmt_search_range_count, mmt_search_range_fill): the first counts the hits per query and gallery chunk, the
+    sum of the counts places the rows, the second writes every hit to its slot -- no atomics, bit-reproducible.  The total
+    is known after the first scan (the call's one wait for the device) and nothing of output size exists before: a total
+    above max_hits raises ValueError naming it (the default is a guard against a mistyped threshold, not a tuned number).
+    Queries run in batches of whole 64-row blocks within _BATCH_BYTES: every batch is counted first, across the whole
+    call, then comes the one allocation, then the fills.  Each batch's count workspace is KEPT for its fill rather than
+    recounted: it is 4 bytes per query and gallery chunk (at most 1 / 1024 of the score matrix, 1 MiB at 4 096 x 262 144),
+    where a recount would be a third scan; the folded queries of a batch, which are large, are folded again instead.
+    Exclusions per query are not part of this call: the caller applies them to the CSR."""
+    q, qw, thr = self._range_args(embds, weights, threshold, subset, order, max_hits)
+    nq = q.shape[0]
+    with torch.cuda.device(self.device):
+      counted = self._range_count(q, qw, thr, subset)
+      offsets = torch.zeros(nq + 1, device=self.device, dtype=torch.int64)
+      if nq:
+        torch.cumsum(counted[0], 0, out=offsets[1:])
+      total = int(offsets[-1]) if nq else 0
+      if total > max_hits:
+        raise ValueError('range_search: %d hits exceed max_hits = %d' % (total, max_hits))
+      indices = torch.empty(total, device=self.device, dtype=torch.int64)
+      scores = torch.empty(total, device=self.device, dtype=torch.float32)
+      if total:
+        self._range_fill(q, qw, thr, subset, counted[1], offsets, indices, scores)
+      return _range_result(offsets, indices, scores, order)
+
+  def _range_args(self, embds, weights, threshold, subset, order, max_hits):
+    """The checks of `range_search` (read through the bookkeeping both index classes share) -> q, qw, thr float32 [NQ]."""
+    if order not in ('index', 'score'):
+      raise ValueError("range_search: order must be 'index' or 'score', got %r" % (order,))
+    if isinstance(max_hits, bool) or not isinstance(max_hits, int) or max_hits < 0:
+      raise ValueError('range_search: max_hits must be an int >= 0, got %r' % (max_hits,))
+    if self.num_items == 0:
+      raise ValueError('range_search: the index holds no items')
+    if torch.is_tensor(threshold):
+      if threshold.dtype != torch.float32:
+        raise ValueError('range_search: threshold must be a float or a float32 tensor, got %s' % threshold.dtype)
+      if threshold.device != self.device:
+        raise ValueError('range_search: threshold must be on the index device %s, got %s' % (self.device, threshold.device))
+      if threshold.dim() != 1:
+        raise ValueError('range_search: threshold [NQ] expected, got %s' % (tuple(threshold.shape),))
+    elif isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+      raise ValueError('range_search: threshold must be a float or a float32 tensor, got %s' % type(threshold).__name__)
+    if subset is not None:
+      self._subset(subset, 'range_search')
+    q, qw = self._queries(embds, weights)
+    nq = q.shape[0]
+    if torch.is_tensor(threshold):
+      if threshold.shape[0] != nq:
+        raise ValueError('range_search: %d queries but threshold %s' % (nq, tuple(threshold.shape)))
+      thr = threshold.contiguous()
+    else:
+      thr = torch.full((nq,), float(threshold), device=self.device, dtype=torch.float32)
+    return q, qw, thr
+
+  def _range_count(self, q, qw, thr, subset):
+    """The count pass of `range_search` behind its checks, batch by batch -> (hits per query int64 [NQ], the batches'
+    workspaces as the fill pass wants them).  Nothing here waits for the device."""
+    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    L = _lib.lib()
+    fn, name = ((L.mmt_search_range_count_bf16, 'mmt_search_range_count_bf16') if self.dtype == torch.bfloat16 else
+                (L.mmt_search_range_count, 'mmt_search_range_count'))
+    words = None if subset is None else subset.words
+    counts = torch.empty(nq, device=self.device, dtype=torch.int64)
+    kept = []
+    for r0, r1 in self._batches(nq, 1):
+      n = r1 - r0
+      operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+      ws = torch.empty(L.mmt_range_workspace_ints(n, nv), device=self.device, dtype=torch.int32)
+      check(fn(*operands, n, nv, m, d, ops._p(thr[r0:r1]), ops._p(words), ops._p(ws), ops._p(counts[r0:r1]), ops._stream()),
+            name)
+      kept.append(ws)
+    return counts, kept
+
+  def _range_fill(self, q, qw, thr, subset, kept, offsets, indices, scores):
+    """The fill pass of `range_search`: `kept` from `_range_count` of the same arguments, offsets int64 [NQ + 1] into
+    indices / scores."""
+    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    L = _lib.lib()
+    fn, name = ((L.mmt_search_range_fill_bf16, 'mmt_search_range_fill_bf16') if self.dtype == torch.bfloat16 else
+                (L.mmt_search_range_fill, 'mmt_search_range_fill'))
+    words = None if subset is None else subset.words
+    for (r0, r1), ws in zip(self._batches(nq, 1), kept):
+      operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+      check(fn(*operands, r1 - r0, nv, m, d, ops._p(thr[r0:r1]), ops._p(words), ops._p(ws), ops._p(offsets[r0:r1 + 1]),
+               ops._p(indices), ops._p(scores), ops._stream()), name)
+
   def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
     """The reference's tie-averaged 0-based rank (model/metric.py:90-121) of item targets[q, t] among the stored items for
     query q: greater + (equal - 1) / 2 from `rank_counts`, +inf where the target is -1.  float64 on the device, of
@@ -1043,6 +1177,51 @@ class ShardedVideoIndex:
       greater += gs.to(self.device)
       equal += es.to(self.device)
     return greater, equal
+
+  def range_search(self, embds, weights, threshold, subset=None, order='index', max_hits=_MAX_HITS):
+    """VideoIndex.range_search over all shards -> RangeResult on the primary, in global item numbers, bit-identical to that
+    of one VideoIndex.  Every shard counts the hits among its own items (with its part of the subset); the shards' totals
+    are summed on the primary -- the call's one wait for the devices -- and held against max_hits before any shard
+    allocates its outputs; every shard then fills a CSR of its own, whose local item numbers go through the shard's table
+    to global ones; the primary concatenates the shards' hits and orders them by (query, global item) with two stable
+    torch sorts.  order='score' as VideoIndex.range_search.  Exclusions are applied to the CSR by the caller."""
+    q, qw, thr = VideoIndex._range_args(self, embds, weights, threshold, subset, order, max_hits)
+    nq = q.shape[0]
+    live = [(s, sh) for s, sh in self._live() if subset is None or subset.parts[s] is not None]
+    args, counted = {}, {}
+    for s, sh in live:
+      args[s] = (q.to(sh.device), qw.to(sh.device), thr.to(sh.device), None if subset is None else subset.parts[s])
+      with torch.cuda.device(sh.device):
+        counted[s] = sh.index._range_count(*args[s])
+    with torch.cuda.device(self.device):
+      per_shard = torch.stack([counted[s][0].to(self.device) for s, _ in live])   # [S, NQ]
+      totals = per_shard.sum(1).tolist()
+      if sum(totals) > max_hits:
+        raise ValueError('range_search: %d hits exceed max_hits = %d' % (sum(totals), max_hits))
+      offsets = torch.zeros(nq + 1, device=self.device, dtype=torch.int64)
+      if nq:
+        torch.cumsum(per_shard.sum(0), 0, out=offsets[1:])
+    rows, items, scores = [], [], []
+    for (s, sh), total in zip(live, totals):
+      if not total:
+        continue
+      with torch.cuda.device(sh.device):
+        local = torch.zeros(nq + 1, device=sh.device, dtype=torch.int64)
+        torch.cumsum(counted[s][0], 0, out=local[1:])
+        idx = torch.empty(total, device=sh.device, dtype=torch.int64)
+        sc = torch.empty(total, device=sh.device, dtype=torch.float32)
+        sh.index._range_fill(*args[s], counted[s][1], local, idx, sc)
+      rows.append(_csr_rows(local.to(self.device)))
+      items.append(sh.ids[idx.to(self.device)])
+      scores.append(sc.to(self.device))
+    with torch.cuda.device(self.device):
+      if not rows:
+        return RangeResult(offsets, torch.empty(0, device=self.device, dtype=torch.int64),
+                           torch.empty(0, device=self.device, dtype=torch.float32))
+      rows, items, scores = torch.cat(rows), torch.cat(items), torch.cat(scores)
+      by_item = torch.argsort(items, stable=True)
+      perm = by_item[torch.argsort(rows[by_item], stable=True)]
+      return _range_result(offsets, items[perm], scores[perm], order)
 
   def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
     """VideoIndex.ranks: greater + (equal - 1) / 2 from `rank_counts`, float64 on the primary, +inf where the target is -1

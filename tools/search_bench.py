@@ -40,7 +40,16 @@ every variant once per round, interleaved; median and spread, and the two costs 
 lse pass over plain scan.  --baseline-json FILE... records beside them the plain search of another build (default-mode
 outputs of its own search_bench, --skip-materialised, run in the same session) and --same-build-json FILE... such runs
 of this build, taken alternately with them.  The result goes under the key "norm" of
---out (default profiles/search_bench.json), whose other content is kept."""
+--out (default profiles/search_bench.json), whose other content is kept.
+
+--range HITS times the range search (VideoIndex.range_search: every item at or above a per-query threshold, two scans) per
+index dtype (--gallery-dtype, both = the two indexes).  The thresholds are the HITS-th best score of each query (the last
+score of search(k = HITS), 1 <= HITS <= 128), so every query has at least HITS hits.  Beside it, on the same index:
+threshold_counts against the same thresholds (T = 1: one scan, the yardstick -- a range search should cost about two) and
+search(k = 10).  --runs rounds, every variant once per round, interleaved; median and spread.  --counts-only times the
+two yardsticks alone: it calls nothing a build without range_search lacks, so the same file run inside a checkout of the
+parent commit gives the parent's numbers, and --baseline-json FILE... records such results beside this build's.  Default
+output profiles/search_range_bench.json."""
 import argparse
 import json
 import math
@@ -264,6 +273,48 @@ def norm_mode(q, qw, g, gw, flop, a):
   return row
 
 
+def range_mode(q, qw, g, gw, flop, a):
+  """range_search against threshold_counts (T = 1, one scan) and search(k = 10), per index dtype."""
+  nv = g.shape[0]
+  dtypes = ('float32', 'bfloat16') if a.gallery_dtype == 'both' else (a.gallery_dtype,)
+  hits = min(a.range, nv)
+  fns = {}
+  for n in dtypes:
+    index = VideoIndex.empty(nv, M, D, g.device, dtype=getattr(torch, n))
+    for at in range(0, nv, 8192):
+      index.add(g[at:at + 8192], gw[at:at + 8192])
+    thr = index.search(q, qw, k=hits)[0][:, -1].contiguous()
+    if not a.counts_only:
+      fns[n + '/range_search'] = lambda index=index, thr=thr: index.range_search(q, qw, thr)
+    fns[n + '/threshold_counts'] = lambda index=index, thr=thr: index.threshold_counts(q, qw, thr)
+    fns[n + '/search_k10'] = lambda index=index: index.search(q, qw, k=K)
+  ts = {n: [] for n in fns}
+  mem = {n: 0 for n in fns}
+  out = {}
+  for _ in range(a.runs):
+    for n, fn in fns.items():
+      t, _, m, out[n] = timed(fn, a.min_seconds)
+      ts[n].append(t)
+      mem[n] = max(mem[n], m)
+  row = {'hits_per_query_at_least': hits}
+  for n in fns:
+    med = float(np.median(ts[n]))
+    row[n] = dict(seconds_median=med, seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n],
+                  tflops_of_one_scan=flop / med / 1e12, peak_mem_growth_bytes=mem[n])
+  if not a.counts_only:
+    for n in dtypes:
+      r, c, s10 = (row['%s/%s' % (n, v)] for v in ('range_search', 'threshold_counts', 'search_k10'))
+      res, (greater, equal) = out[n + '/range_search'], out[n + '/threshold_counts']
+      spread = max(r['seconds_spread'], 2 * c['seconds_spread'])
+      row[n + '/summary'] = dict(
+          total_hits=int(res.offsets[-1]), counts_agree=bool(torch.equal(res.counts, greater.long() + equal.long())),
+          range_over_threshold_counts=r['seconds_median'] / c['seconds_median'],
+          range_over_search_k10=r['seconds_median'] / s10['seconds_median'],
+          seconds_above_two_scans=r['seconds_median'] - 2 * c['seconds_median'], spread_seconds=spread,
+          above_two_scans_beyond_spread=bool(r['seconds_median'] - 2 * c['seconds_median'] > spread))
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--shapes', default='S1,S2,S3')
@@ -282,7 +333,12 @@ def main():
                   'the visible devices, cycling, in place of the single index (default mode only)')
   ap.add_argument('--norm', type=float, default=None, metavar='BETA', help='time hub_norm (the lse pass, bank = the queries) '
                   'and search(norm=) against the plain search')
-  ap.add_argument('--baseline-json', nargs='+', default=[], help='with --norm: default-mode results of another build')
+  ap.add_argument('--range', type=int, default=0, metavar='HITS', help='time range_search with per-query thresholds at the '
+                  'HITS-th best score (1..128) against threshold_counts (T = 1) and search(k = 10)')
+  ap.add_argument('--counts-only', action='store_true', help='with --range: the two yardsticks alone (runs on a build '
+                  'without range_search)')
+  ap.add_argument('--baseline-json', nargs='+', default=[], help='with --norm: default-mode results of another build; '
+                  'with --range: --range --counts-only results of another build')
   ap.add_argument('--same-build-json', nargs='+', default=[], help='with --norm: default-mode results of this build')
   a = ap.parse_args()
   masked = a.subset is not None or a.exclude > 0
@@ -294,6 +350,12 @@ def main():
     raise SystemExit('--shards wants 1..32 and the default mode (no --ranks, --subset, --exclude, --gallery-dtype both)')
   if a.norm is not None and (masked or a.ranks or a.shards or not 0 < a.norm < math.inf):
     raise SystemExit('--norm wants 0 < BETA < inf and no --ranks, --subset, --exclude, --shards')
+  if not 0 <= a.range <= 128 or a.range and (masked or a.ranks or a.shards or a.norm is not None):
+    raise SystemExit('--range wants 1..128 and no --ranks, --subset, --exclude, --shards, --norm')
+  if a.counts_only and not a.range:
+    raise SystemExit('--counts-only goes with --range')
+  if a.range and a.out is None and not a.counts_only:
+    a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_range_bench.json')
   if a.norm is not None and a.out is None:
     a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_bench.json')
   if masked and a.out is None:
@@ -319,6 +381,16 @@ def main():
       if runs:
         res[key] = {name: dict(seconds_runs=v, seconds_median=float(np.median(v)), seconds_spread=max(v) - min(v))
                     for name, v in runs.items()}
+  if a.range:
+    res.update(mode='range', hits=a.range, counts_only=a.counts_only, gallery_dtype=a.gallery_dtype, runs=a.runs,
+               min_seconds=a.min_seconds)
+    if a.baseline_json:
+      res['baseline'] = []
+      for path in a.baseline_json:
+        with open(path) as f:
+          other = json.load(f)
+        res['baseline'].append({name: {n: v for n, v in row.items() if isinstance(v, dict) and 'seconds_median' in v}
+                                for name, row in other['shapes'].items()})
   if masked:
     res.update(mode='subset', subset_fraction=a.subset, exclude=a.exclude, runs=a.runs, min_seconds=a.min_seconds)
   for name in a.shapes.split(','):
@@ -331,8 +403,9 @@ def main():
     qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
     flop = 2.0 * nq * nv * M * D
     row = {'NQ': nq, 'NV': nv, 'flop': flop}
-    if masked or a.ranks or a.norm is not None or a.gallery_dtype == 'both':
-      mode = norm_mode if a.norm is not None else subset_mode if masked else ranks_mode if a.ranks else both_dtypes
+    if masked or a.ranks or a.norm is not None or a.range or a.gallery_dtype == 'both':
+      mode = (norm_mode if a.norm is not None else range_mode if a.range else subset_mode if masked else
+              ranks_mode if a.ranks else both_dtypes)
       row.update(mode(q, qw, g, gw, flop, a))
       res['shapes'][name] = row
       print(name, json.dumps(row), flush=True)
