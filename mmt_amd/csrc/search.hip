@@ -5,25 +5,37 @@
 //
 // Both operands arrive folded (Q' = qw * Q, G' = gw * G: mmt_search_fold), so the numerator is ONE fp32 GEMM with
 // K = M*d on v_mfma_f32_32x32x2_f32, like mmt_sims_eval.  Two launches:
-//   topk_chunk_kernel<true>  : block = 64 queries x one gallery chunk.  Per 128-column tile the K loop streams
+//   topk_scan_kernel         : block = 64 queries x one gallery chunk.  Per 128-column tile the K loop streams
 //                              through LDS in 32-wide slabs (register-staged: the next slab's global loads are in flight
 //                              during the current slab's MFMAs), the epilogue divides by the gated denominator and the
 //                              tile's 64 x 128 scores land in LDS, where each wave keeps a running top-k for its 16 rows
 //                              (threshold = k-th best so far; candidates above it are appended, the list is compacted
 //                              back to k when full).  The chunk's sorted k best go to the workspace.
-//   topk_chunk_kernel<false> : the same selection stage reading the scores from a given matrix (compress_predictions).
+//   topk_select_kernel       : the same selection stage reading the scores from a given matrix (compress_predictions).
 //   topk_merge_kernel        : per query, the chunk lists merged by rank (each list is sorted: binary search).
 // Order: score descending, ties by ascending gallery index (= a stable argsort of -score).  A (score, index) pair is one
 // uint64 key -- order-preserving score bits above, ~index below -- so "better" is one unsigned compare and every key is
 // distinct; 0 is "no candidate".  No atomics: every output slot has exactly one writer, results are bit-reproducible.
-// The key and the running top-k live in search_topk.h, shared with the bf16-gallery kernel (search_bf16.hip); the K loop
-// and the score epilogue in search_scan.h, shared with the rank-count kernels as well (search_rank.hip).
+// The key and the running top-k live in search_topk.h; the scoring tile (K loops, score epilogue, querybank rewrite) in
+// search_scan.h, shared with the count, range and column-pass kernels (search_rank.hip, search_range.hip, search_norm.hip).
 //
-// topk_chunk_kernel<true, true> is the masked instantiation (mmt_search_topk_ex): the candidates are the items whose bit
-// is set in a packed bitmap (search_subset.hip), less up to TK_MAXE items per query.  A tile's four mask words are one
-// block-uniform 16-byte load (g0 is a multiple of 128); a tile with no bit set is skipped before its K loop -- no gallery
-// loads, no MFMAs.  The mask acts at selection only (tk_tile_select<true>), on the score tile the unmasked kernel
-// computes.  The unmasked instantiations compile to the code they had before the mask existed.
+// topk_scan_kernel<BF16, Args> is ONE body, generic over its argument block; the block says how the subset bitmap and the
+// querybank normalisation enter (kMask, kNorm: search_scan.h):
+//   <false, TkArgs>, <false, TkMaskedArgs>       : fp32 gallery, above.
+//   <true, TkBf16Args>, <true, TkBf16MaskedArgs> : a gallery stored in bf16 (search_bf16.hip has the fold and the score
+//                                      definition): the K loop on v_mfma_f32_32x32x16_bf16 with the fp32 query as a bf16
+//                                      hi / lo pair; same block, tile, accumulator layout, epilogue, selection, workspace
+//                                      and merge.
+//   <BF16, NmTopkArgs>               : the masked kernels with tk_tile_norm between the score epilogue and the selection:
+//                                      ranks by and returns the querybank-normalised score' (search_norm.hip).
+// The argument blocks stay separate types with their layouts as they are: a field appended to TkArgs moves the hidden
+// kernel arguments behind it and changes the unmasked code (profiles/search_subset_kernel_identity.txt).
+//
+// The masked blocks (mmt_search_topk_ex and the normalised calls): the candidates are the items whose bit is set in a
+// packed bitmap (search_subset.hip; a null pointer allows every item), less up to TK_MAXE items per query.  A tile's four
+// mask words are one block-uniform 16-byte load (tk_tile_mask; g0 is a multiple of 128); a tile with no bit set is skipped
+// before its K loop -- no gallery loads, no MFMAs.  The mask acts at selection only (tk_tile_select<true>), on the score
+// tile the unmasked kernel computes.  The unmasked instantiations compile to the code they had before the mask existed.
 #include <type_traits>
 
 #include "search_topk.h"
@@ -37,6 +49,8 @@ struct TkArgs {
   int64_t ld;
   uint64_t* ws;         // [NQ][n_chunks][k]
   int NQ, NV, M, K, k, chunk, n_qt, n_chunks;
+  static constexpr TkMask kMask = TK_MASK_NONE;
+  static constexpr bool kNorm = false;
 };
 
 // The masked instantiation's arguments: a kernel argument of its own type, so the unmasked kernels keep their argument
@@ -45,11 +59,44 @@ struct TkMaskedArgs : TkArgs {
   const uint32_t* subset;   // bit g & 31 of word g >> 5 allows item g (nullable = all; 16-byte aligned)
   const int64_t* exclude;   // [NQ][E] items barred per query, -1 = none
   int E;
+  static constexpr TkMask kMask = TK_MASK_NULLABLE;
 };
 
-template <bool FUSED, bool MASKED = false>
-__global__ __launch_bounds__(256) void topk_chunk_kernel(std::conditional_t<MASKED, TkMaskedArgs, TkArgs> a) {
+struct TkBf16Args {
+  const bf16_t* q;      // hi(Q') [NQ][K]
+  const bf16_t* q_lo;   // lo(Q') [NQ][K]
+  const float* qw;      // [NQ][M]
+  const bf16_t* g;      // [NV][K]
+  const float* gw;      // [NV][M]
+  uint64_t* ws;         // [NQ][n_chunks][k]
+  int NQ, NV, M, K, k, chunk, n_qt, n_chunks;
+  static constexpr TkMask kMask = TK_MASK_NONE;
+  static constexpr bool kNorm = false;
+};
+
+struct TkBf16MaskedArgs : TkBf16Args {  // as TkMaskedArgs
+  const uint32_t* subset;
+  const int64_t* exclude;
+  int E;
+  static constexpr TkMask kMask = TK_MASK_NULLABLE;
+};
+
+struct NmTopkArgs : NmArgs {
+  uint64_t* ws;             // [NQ][n_chunks][k]
+  const uint32_t* subset;   // nullable = all
+  const int64_t* exclude;   // [NQ][E]
+  int k, E;
+};
+
+// One block of the fused scan: 64 queries x one gallery chunk -> the chunk's sorted k best per query in the workspace.
+// Args = TkArgs, TkBf16Args (kMask = TK_MASK_NONE), their masked forms or NmTopkArgs (TK_MASK_NULLABLE: subset bitmap,
+// may be null, and per-query exclusions, E = 0 allowed).
+template <bool BF16, class Args>
+__global__ __launch_bounds__(256) void topk_scan_kernel(Args a) {
+  constexpr TkMask MASK = Args::kMask;
+  constexpr bool NORM = Args::kNorm;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int kUnion = BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int bid = xcd_remap(blockIdx.x, gridDim.x);  // gallery-chunk-major: an XCD's blocks share their chunk in L2
   const int chunk = bid / a.n_qt, q0 = (bid % a.n_qt) * TK_Q;
@@ -58,61 +105,57 @@ __global__ __launch_bounds__(256) void topk_chunk_kernel(std::conditional_t<MASK
   uint64_t* ws = a.ws + chunk * (int64_t)a.k;
   const int64_t ws_row = (int64_t)a.n_chunks * a.k;
 
-  if constexpr (!FUSED) {
-    uint64_t* cand = (uint64_t*)smem + (int64_t)wave * cap;
-    for (int rr = 0; rr < TK_Q / 4; ++rr) {
-      const int q = q0 + wave * (TK_Q / 4) + rr;
-      if (q >= a.NQ) break;
-      const float* row = a.q + (a.rows ? (int64_t)a.rows[q] : (int64_t)q) * a.ld;
-      int n = 0;
-      uint64_t thr = 0;
-      for (int g0 = g_begin; g0 < g_end; g0 += 64) {
-        const int g = g0 + lane;
-        tk_push(cand, n, thr, a.k, g < g_end ? tk_key(row[g], g) : 0ull, lane);
-      }
-      tk_flush(cand, n, a.k, lane, ws + q * ws_row);
+  float* sS = (float*)smem;                                   // [TK_Q][TK_SLD]  scores (after the K loop)
+  float* sQw = (float*)(smem + kUnion);                       // [TK_Q][MMT_MAX_EXPERTS]
+  int* sN = (int*)(smem + kUnion + TK_QW_BYTES);              // [TK_Q] candidates held
+  uint64_t* sT = (uint64_t*)(sN + TK_Q);                      // [TK_Q] thresholds
+  uint64_t* sC = sT + TK_Q;                                   // [TK_Q][cap] candidates
+  const int l31 = lane & 31, h = lane >> 5, wq = wave >> 1, wg = wave & 1;
+  if (tid < TK_Q) { sN[tid] = 0; sT[tid] = 0; }
+  tk_load_qw(sQw, a.qw, a.NQ, a.M, q0, tid);
+  int* sEx = (int*)(sC + TK_Q * cap);                         // masked: [TK_Q][E] exclusions
+  if constexpr (MASK != TK_MASK_NONE)
+    for (int i = tid; i < TK_Q * a.E; i += 256) sEx[i] = q0 + i / a.E < a.NQ ? (int)a.exclude[(int64_t)q0 * a.E + i] : -1;
+  for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
+    uint64_t m0 = ~0ull, m1 = ~0ull;
+    if constexpr (MASK != TK_MASK_NONE)
+      if (a.subset && !tk_tile_mask(a.subset, g0, m0, m1)) continue;  // block-uniform: nothing of this tile is allowed
+    tk_tile<BF16, NORM>(a, smem, sS, sQw, q0, [=](int r) { return g0 + r < g_end ? g0 + r : -1; }, tid, wq, wg, l31, h);
+    if constexpr (MASK != TK_MASK_NONE)
+      tk_tile_select<true>(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane, m0, m1, sEx, a.E);
+    else
+      tk_tile_select(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane);
+  }
+  __syncthreads();
+  for (int rr = 0; rr < TK_Q / 4; ++rr) {
+    const int row = wave * (TK_Q / 4) + rr, q = q0 + row;
+    if (q >= a.NQ) break;
+    tk_flush(sC + row * cap, sN[row], a.k, lane, ws + q * ws_row);
+  }
+}
+
+// The selection stage alone, reading the scores from a given matrix (mmt_rows_topk).
+__global__ __launch_bounds__(256) void topk_select_kernel(TkArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
+  const int chunk = bid / a.n_qt, q0 = (bid % a.n_qt) * TK_Q;
+  const int g_begin = chunk * a.chunk, g_end = min(a.NV, g_begin + a.chunk);
+  const int cap = a.k + 64;
+  uint64_t* ws = a.ws + chunk * (int64_t)a.k;
+  const int64_t ws_row = (int64_t)a.n_chunks * a.k;
+  uint64_t* cand = (uint64_t*)smem + (int64_t)wave * cap;
+  for (int rr = 0; rr < TK_Q / 4; ++rr) {
+    const int q = q0 + wave * (TK_Q / 4) + rr;
+    if (q >= a.NQ) break;
+    const float* row = a.q + (a.rows ? (int64_t)a.rows[q] : (int64_t)q) * a.ld;
+    int n = 0;
+    uint64_t thr = 0;
+    for (int g0 = g_begin; g0 < g_end; g0 += 64) {
+      const int g = g0 + lane;
+      tk_push(cand, n, thr, a.k, g < g_end ? tk_key(row[g], g) : 0ull, lane);
     }
-    return;
-  } else {
-    float* sS = (float*)smem;                                  // [TK_Q][TK_SLD]  scores (after the K loop: tk_scan_f32)
-    float* sQw = (float*)(smem + TK_UNION_BYTES);              // [TK_Q][MMT_MAX_EXPERTS]
-    int* sN = (int*)(smem + TK_UNION_BYTES + TK_QW_BYTES);     // [TK_Q] candidates held
-    uint64_t* sT = (uint64_t*)(sN + TK_Q);                     // [TK_Q] thresholds
-    uint64_t* sC = sT + TK_Q;                                  // [TK_Q][cap] candidates
-    const int l31 = lane & 31, h = lane >> 5, wq = wave >> 1, wg = wave & 1;
-    const int K = a.K, M = a.M;
-    if (tid < TK_Q) { sN[tid] = 0; sT[tid] = 0; }
-    tk_load_qw(sQw, a.qw, a.NQ, M, q0, tid);
-    int* sEx = (int*)(sC + TK_Q * cap);                        // MASKED: [TK_Q][E] exclusions
-    if constexpr (MASKED)
-      for (int i = tid; i < TK_Q * a.E; i += 256) sEx[i] = q0 + i / a.E < a.NQ ? (int)a.exclude[(int64_t)q0 * a.E + i] : -1;
-    for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
-      uint64_t m0 = ~0ull, m1 = ~0ull;
-      if constexpr (MASKED) {
-        if (a.subset) {
-          const u32x4 w = *(const u32x4*)(a.subset + (g0 >> 5));
-          m0 = w[0] | (uint64_t)w[1] << 32;
-          m1 = w[2] | (uint64_t)w[3] << 32;
-          if (!(m0 | m1)) continue;  // block-uniform: nothing of this tile is allowed
-        }
-      }
-      const auto grow = [=](int r) { return g0 + r < g_end ? g0 + r : -1; };
-      f32x16 acc[2];
-      tk_scan_f32(acc, smem, a.q, a.g, a.NQ, K, q0, grow, tid, wq, wg, l31, h);
-      __syncthreads();  // the slabs become the score tile
-      tk_tile_scores(acc, sS, sQw, a.gw, M, grow, wq, wg, l31, h);
-      __syncthreads();
-      if constexpr (MASKED)
-        tk_tile_select<true>(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane, m0, m1, sEx, a.E);
-      else
-        tk_tile_select(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane);
-    }
-    __syncthreads();
-    for (int rr = 0; rr < TK_Q / 4; ++rr) {
-      const int row = wave * (TK_Q / 4) + rr, q = q0 + row;
-      if (q >= a.NQ) break;
-      tk_flush(sC + row * cap, sN[row], a.k, lane, ws + q * ws_row);
-    }
+    tk_flush(cand, n, a.k, lane, ws + q * ws_row);
   }
 }
 
@@ -163,17 +206,14 @@ int tk_chunk(int NQ, int NV) {
   return chunk;
 }
 
+namespace {
 bool tk_args_ok(int NQ, int NV, int k) { return NQ > 0 && NV > 0 && k >= 1 && k <= TK_MAXK; }
 
+// LDS behind the slab / score-tile union: query weights, counts, thresholds, candidates ...
 size_t tk_state_lds(int k) { return TK_QW_BYTES + TK_Q * (4 + 8) + (size_t)TK_Q * (k + 64) * 8; }
-
+// ... and behind those, the masked kernels' exclusions [TK_Q][E]
 size_t tk_exclude_lds(int E) { return (size_t)TK_Q * E * 4; }
-
-bool tk_mask_args_ok(const uint32_t* subset, const int64_t* exclude, int E, int* rc) {
-  if (E < 0 || E > TK_MAXE || (E > 0 && !exclude)) { *rc = MMT_ERR_ARG; return false; }
-  if ((uintptr_t)subset & 15) { *rc = MMT_ERR_ALIGN; return false; }
-  return true;
-}
+size_t tk_select_lds(int k) { return (size_t)4 * (k + 64) * 8; }
 
 int tk_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, float* scores, int64_t* index,
                     hipStream_t s) {
@@ -185,58 +225,66 @@ int tk_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, f
   return (int)hipGetLastError();
 }
 
-namespace {
-size_t tk_fused_lds(int k) { return TK_UNION_BYTES + tk_state_lds(k); }
-size_t tk_select_lds(int k) { return (size_t)4 * (k + 64) * 8; }
-
-int tk_launch(const TkMaskedArgs& a, bool fused, int kout, float* scores, int64_t* index, hipStream_t s) {
-  static const bool attrs = [] {  // allow the k = 128 footprint (over the 64 KiB default)
-    (void)hipFuncSetAttribute((const void*)topk_chunk_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)tk_fused_lds(TK_MAXK));
-    (void)hipFuncSetAttribute((const void*)topk_chunk_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(tk_fused_lds(TK_MAXK) + tk_exclude_lds(TK_MAXE)));
-    return true;
-  }();
-  (void)attrs;
-  const int blocks = a.n_qt * a.n_chunks;
-  if (fused && (a.subset || a.E))
-    hipLaunchKernelGGL((topk_chunk_kernel<true, true>), dim3(blocks), dim3(256), tk_fused_lds(a.k) + tk_exclude_lds(a.E), s, a);
-  else if (fused)
-    hipLaunchKernelGGL(topk_chunk_kernel<true>, dim3(blocks), dim3(256), tk_fused_lds(a.k), s, (TkArgs)a);
-  else
-    hipLaunchKernelGGL(topk_chunk_kernel<false>, dim3(blocks), dim3(256), tk_select_lds(a.k), s, (TkArgs)a);
-  return tk_merge_launch(a.ws, a.NQ, a.n_chunks, a.k, kout, scores, index, s);
+// The k = 128 footprint of the fused kernels is over the 64 KiB default.
+void tk_topk_lds_limits() {
+  static bool done[64] = {};
+  const size_t f32 = TK_UNION_BYTES + tk_state_lds(TK_MAXK), bf16 = TKB_UNION_BYTES + tk_state_lds(TK_MAXK);
+  const size_t ex = tk_exclude_lds(TK_MAXE);
+  tk_lds_limits(done, {{(const void*)topk_scan_kernel<false, TkArgs>, f32},
+                       {(const void*)topk_scan_kernel<false, TkMaskedArgs>, f32 + ex},
+                       {(const void*)topk_scan_kernel<true, TkBf16Args>, bf16},
+                       {(const void*)topk_scan_kernel<true, TkBf16MaskedArgs>, bf16 + ex},
+                       {(const void*)topk_scan_kernel<false, NmTopkArgs>, f32 + ex},
+                       {(const void*)topk_scan_kernel<true, NmTopkArgs>, bf16 + ex}});
 }
 
-TkMaskedArgs tk_args(int NQ, int NV, int k, uint64_t* ws) {
-  TkMaskedArgs a = {};
-  a.NQ = NQ; a.NV = NV; a.k = k; a.ws = ws;
-  a.chunk = tk_chunk(NQ, NV);
-  a.n_qt = (NQ + TK_Q - 1) / TK_Q;
-  a.n_chunks = (NV + a.chunk - 1) / a.chunk;
+// The fused search behind every top-k entry point (Args = TkMaskedArgs, TkBf16MaskedArgs or NmTopkArgs, the last with lse
+// and beta set by the caller): gate, fill, the chunk scan and the merge.  `rest`: the entry's other arguments are in
+// order.  q_lo is null where an entry has none.
+template <bool BF16, class Args>
+int tk_search(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
+              int d, int k, const uint32_t* subset, const int64_t* exclude, int E, bool rest, uint64_t* ws, float* scores,
+              int64_t* index, void* stream) {
+  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !rest || !ws || !index || !tk_args_ok(NQ, NV, k) ||
+      !tk_shape_ok(NQ, NV, M, d, BF16))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g) & 15) return MMT_ERR_ALIGN;
+  if (E < 0 || E > TK_MAXE || (E > 0 && !exclude)) return MMT_ERR_ARG;
+  if ((uintptr_t)subset & 15) return MMT_ERR_ALIGN;  // null = every item allowed
+  a.q = static_cast<decltype(a.q)>(q); a.qw = qw; a.g = static_cast<decltype(a.g)>(g); a.gw = gw; a.ws = ws;
+  if constexpr (BF16) a.q_lo = static_cast<decltype(a.q_lo)>(q_lo);
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.k = k;
+  a.subset = subset; a.exclude = exclude; a.E = E;
+  tk_geometry(a);
+  tk_topk_lds_limits();
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(a.n_qt * a.n_chunks);
+  const size_t lds = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + tk_state_lds(k);
+  using Plain = std::conditional_t<BF16, TkBf16Args, TkArgs>;
+  if (Args::kNorm || subset || E)
+    hipLaunchKernelGGL((topk_scan_kernel<BF16, Args>), grid, dim3(256), lds + tk_exclude_lds(E), s, a);
+  else if constexpr (!Args::kNorm)  // constexpr only so that the slice to Plain is not instantiated for NmTopkArgs
+    hipLaunchKernelGGL((topk_scan_kernel<BF16, Plain>), grid, dim3(256), lds, s, (Plain)a);
+  return tk_merge_launch(ws, NQ, a.n_chunks, k, k < NV ? k : NV, scores, index, s);
+}
+
+NmTopkArgs nm_topk_args(float beta, const float* lse) {
+  NmTopkArgs a = {};
+  a.beta = beta; a.lse = lse;
   return a;
 }
 }  // namespace
 
 extern "C" int64_t mmt_topk_workspace_keys(int NQ, int NV, int k) {
   if (!tk_args_ok(NQ, NV, k)) return MMT_ERR_ARG;
-  const int chunk = tk_chunk(NQ, NV);
-  return (int64_t)NQ * ((NV + chunk - 1) / chunk) * k;
+  return (int64_t)NQ * tk_n_chunks(NQ, NV) * k;
 }
 
 extern "C" int mmt_search_topk_ex(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
                                   int d, int k, const uint32_t* subset, const int64_t* exclude, int E, uint64_t* ws,
                                   float* scores, int64_t* index, void* stream) {
-  if (!qf || !qw || !gf || !gw || !ws || !index || !tk_args_ok(NQ, NV, k) || M <= 0 || M > MMT_MAX_EXPERTS || d <= 0 ||
-      (d & 3))
-    return MMT_ERR_ARG;
-  if (((uintptr_t)qf | (uintptr_t)gf) & 15) return MMT_ERR_ALIGN;
-  int rc;
-  if (!tk_mask_args_ok(subset, exclude, E, &rc)) return rc;
-  TkMaskedArgs a = tk_args(NQ, NV, k, ws);
-  a.q = qf; a.qw = qw; a.g = gf; a.gw = gw; a.M = M; a.K = M * d;
-  a.subset = subset; a.exclude = exclude; a.E = E;
-  return tk_launch(a, true, k < NV ? k : NV, scores, index, (hipStream_t)stream);
+  return tk_search<false>(TkMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, true, ws, scores,
+                          index, stream);
 }
 
 extern "C" int mmt_search_topk(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
@@ -244,10 +292,43 @@ extern "C" int mmt_search_topk(const float* qf, const float* qw, const float* gf
   return mmt_search_topk_ex(qf, qw, gf, gw, NQ, NV, M, d, k, nullptr, nullptr, 0, ws, scores, index, stream);
 }
 
+extern "C" int mmt_search_topk_bf16_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                       const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
+                                       const int64_t* exclude, int E, uint64_t* ws, float* scores, int64_t* index,
+                                       void* stream) {
+  return tk_search<true>(TkBf16MaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, true, ws, scores,
+                         index, stream);
+}
+
+extern "C" int mmt_search_topk_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                    const float* gw, int NQ, int NV, int M, int d, int k, uint64_t* ws, float* scores,
+                                    int64_t* index, void* stream) {
+  return mmt_search_topk_bf16_ex(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, nullptr, nullptr, 0, ws, scores, index, stream);
+}
+
+extern "C" int mmt_search_topk_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
+                                    int d, int k, const uint32_t* subset, const int64_t* exclude, int E, float beta,
+                                    const float* lse, uint64_t* ws, float* scores, int64_t* index, void* stream) {
+  return tk_search<false>(nm_topk_args(beta, lse), qf, nullptr, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E,
+                          lse && tk_beta_ok(beta), ws, scores, index, stream);
+}
+
+extern "C" int mmt_search_topk_bf16_norm(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                         const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
+                                         const int64_t* exclude, int E, float beta, const float* lse, uint64_t* ws,
+                                         float* scores, int64_t* index, void* stream) {
+  return tk_search<true>(nm_topk_args(beta, lse), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E,
+                         lse && tk_beta_ok(beta), ws, scores, index, stream);
+}
+
 extern "C" int mmt_rows_topk(const float* sims, int64_t ld, const int32_t* rows, int NR, int NV, int k, uint64_t* ws,
                              float* scores, int64_t* index, void* stream) {
   if (!sims || !ws || !index || !tk_args_ok(NR, NV, k) || ld < NV) return MMT_ERR_ARG;
-  TkMaskedArgs a = tk_args(NR, NV, k, ws);
-  a.q = sims; a.ld = ld; a.rows = rows;
-  return tk_launch(a, false, k < NV ? k : NV, scores, index, (hipStream_t)stream);
+  TkArgs a = {};
+  a.q = sims; a.ld = ld; a.rows = rows; a.ws = ws;
+  a.NQ = NR; a.NV = NV; a.k = k;
+  tk_geometry(a);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(topk_select_kernel, dim3(a.n_qt * a.n_chunks), dim3(256), tk_select_lds(k), s, a);
+  return tk_merge_launch(ws, NR, a.n_chunks, k, k < NV ? k : NV, scores, index, s);
 }

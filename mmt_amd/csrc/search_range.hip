@@ -2,9 +2,9 @@
 // as a CSR over the queries (offsets, item numbers, scores).  Near-duplicate joins, all captions that match a video, all
 // negatives inside a margin, any list deeper than the top-k kernels' k <= 128.
 //
-// The scan is the one of the count kernels (search_rank.hip): block = 64 queries x one gallery chunk (tk_chunk), blocks
-// ordered by xcd_remap, tk_scan_f32 / tk_scan_bf16 + tk_tile_scores leave a 64 x 128 score tile in LDS and a wave takes
-// its 16 rows.  It runs twice over the same operands, with a host-side sum between the passes:
+// The scan is the one of the count kernels (search_rank.hip): block = 64 queries x one gallery chunk (tk_geometry), blocks
+// ordered by xcd_remap, tk_tile of search_scan.h leaves a 64 x 128 score tile in LDS (tk_tile_mask gates it) and a wave
+// takes its 16 rows.  It runs twice over the same operands, with a host-side sum between the passes:
 //   range_kernel<BF16, false, MASKED> : counts.  Per row and tile two ballots of `live && score >= thr[row]` (the two
 //                               64-column halves; a plain float compare: a NaN threshold hits nothing, -inf every live
 //                               item); the popcounts add up in a register of the lane that holds the row (lane l < 16 of
@@ -48,20 +48,6 @@ struct RgMaskedArgs : RgArgs {
   const uint32_t* subset;  // bit g & 31 of word g >> 5 allows item g (16-byte aligned)
 };
 
-template <bool BF16, class GRow>
-__device__ __forceinline__ void rg_tile(const RgArgs& a, unsigned char* smem, float* sS, const float* sQw, int q0, GRow grow,
-                                        int tid, int wq, int wg, int l31, int h) {
-  f32x16 acc[2];
-  if constexpr (BF16)
-    tk_scan_bf16(acc, smem, (const bf16_t*)a.q, (const bf16_t*)a.q_lo, (const bf16_t*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg,
-                 l31, h);
-  else
-    tk_scan_f32(acc, smem, (const float*)a.q, (const float*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg, l31, h);
-  __syncthreads();  // the slabs become the score tile
-  tk_tile_scores(acc, sS, sQw, a.gw, a.M, grow, wq, wg, l31, h);
-  __syncthreads();
-}
-
 template <bool BF16, bool FILL, bool MASKED>
 __global__ __launch_bounds__(256) void range_kernel(std::conditional_t<MASKED, RgMaskedArgs, RgArgs> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -96,13 +82,9 @@ __global__ __launch_bounds__(256) void range_kernel(std::conditional_t<MASKED, R
   tk_load_qw(sQw, a.qw, a.NQ, a.M, q0, tid);  // read after the barriers of the first K loop
   for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
     uint64_t m0 = ~0ull, m1 = ~0ull;
-    if constexpr (MASKED) {
-      const u32x4 w = *(const u32x4*)(a.subset + (g0 >> 5));
-      m0 = w[0] | (uint64_t)w[1] << 32;
-      m1 = w[2] | (uint64_t)w[3] << 32;
-      if (!(m0 | m1)) continue;  // block-uniform: nothing of this tile can hit
-    }
-    rg_tile<BF16>(a, smem, sS, sQw, q0, [=](int r) { return g0 + r < g_end ? g0 + r : -1; }, tid, wq, wg, l31, h);
+    if constexpr (MASKED)
+      if (!tk_tile_mask(a.subset, g0, m0, m1)) continue;  // block-uniform: nothing of this tile can hit
+    tk_tile<BF16, false>(a, smem, sS, sQw, q0, [=](int r) { return g0 + r < g_end ? g0 + r : -1; }, tid, wq, wg, l31, h);
     const bool live0 = g0 + lane < g_end && (!MASKED || ((m0 >> lane) & 1ull));
     const bool live1 = g0 + 64 + lane < g_end && (!MASKED || ((m1 >> lane) & 1ull));
     for (int rr = 0; rr < kRows; ++rr) {
@@ -154,90 +136,78 @@ __global__ __launch_bounds__(256) void range_offsets_kernel(int32_t* __restrict_
 }
 
 namespace {
-bool rg_args_ok(int NQ, int NV, int M, int d, int mult) {
-  return NQ > 0 && NV > 0 && M > 0 && M <= MMT_MAX_EXPERTS && d > 0 && !(d & (mult - 1));
+// The gate and the fill of the four entry points: 0, or the error code.  `rest`: the entry's other pointers are all there.
+template <bool BF16>
+int rg_fill(RgMaskedArgs& a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV,
+            int M, int d, const float* thr, const uint32_t* subset, const int32_t* ws, bool rest) {
+  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !thr || !ws || !rest || !tk_shape_ok(NQ, NV, M, d, BF16))
+    return MMT_ERR_ARG;
+  if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  a.q = q; a.q_lo = q_lo; a.qw = qw; a.g = g; a.gw = gw; a.thr = thr; a.ws = const_cast<int32_t*>(ws); a.subset = subset;
+  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d;
+  tk_geometry(a);
+  return 0;
 }
 
 template <bool BF16, bool FILL>
-int rg_launch(RgMaskedArgs a, hipStream_t s) {
-  constexpr size_t lds = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + TK_QW_BYTES;
-  a.chunk = tk_chunk(a.NQ, a.NV);
-  a.n_qt = (a.NQ + TK_Q - 1) / TK_Q;
-  a.n_chunks = (a.NV + a.chunk - 1) / a.chunk;
+void rg_launch(const RgMaskedArgs& a, hipStream_t s) {
   if (a.subset)
-    hipLaunchKernelGGL((range_kernel<BF16, FILL, true>), dim3(a.n_qt * a.n_chunks), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((range_kernel<BF16, FILL, true>), dim3(a.n_qt * a.n_chunks), dim3(256), tk_base_lds<BF16>(), s, a);
   else
-    hipLaunchKernelGGL((range_kernel<BF16, FILL, false>), dim3(a.n_qt * a.n_chunks), dim3(256), lds, s, (RgArgs)a);
-  return a.n_chunks;
+    hipLaunchKernelGGL((range_kernel<BF16, FILL, false>), dim3(a.n_qt * a.n_chunks), dim3(256), tk_base_lds<BF16>(), s,
+                       (RgArgs)a);
 }
 
 template <bool BF16>
-int rg_count(RgMaskedArgs a, int64_t* row_counts, hipStream_t s) {
-  const int n_chunks = rg_launch<BF16, false>(a, s);
-  hipLaunchKernelGGL(range_offsets_kernel, dim3((a.NQ + 255) / 256), dim3(256), 0, s, a.ws, a.NQ, n_chunks, row_counts);
+int rg_count(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M, int d,
+             const float* thr, const uint32_t* subset, int32_t* ws, int64_t* row_counts, void* stream) {
+  RgMaskedArgs a = {};
+  if (const int rc = rg_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, thr, subset, ws, row_counts != nullptr)) return rc;
+  rg_launch<BF16, false>(a, (hipStream_t)stream);
+  hipLaunchKernelGGL(range_offsets_kernel, dim3((NQ + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws, NQ, a.n_chunks,
+                     row_counts);
   return (int)hipGetLastError();
 }
 
 template <bool BF16>
-int rg_fill(RgMaskedArgs a, hipStream_t s) {
-  rg_launch<BF16, true>(a, s);
+int rg_fill_hits(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
+                 int d, const float* thr, const uint32_t* subset, const int32_t* ws, const int64_t* offsets,
+                 int64_t* indices, float* scores, void* stream) {
+  RgMaskedArgs a = {};
+  if (const int rc = rg_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, thr, subset, ws, offsets && indices && scores))
+    return rc;
+  a.offsets = offsets; a.indices = indices; a.scores = scores;
+  rg_launch<BF16, true>(a, (hipStream_t)stream);
   return (int)hipGetLastError();
 }
 }  // namespace
 
 extern "C" int64_t mmt_range_workspace_ints(int NQ, int NV) {
   if (NQ <= 0 || NV <= 0) return MMT_ERR_ARG;
-  const int chunk = tk_chunk(NQ, NV);
-  return (int64_t)NQ * ((NV + chunk - 1) / chunk);
+  return (int64_t)NQ * tk_n_chunks(NQ, NV);
 }
 
 extern "C" int mmt_search_range_count(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
                                       int M, int d, const float* thr, const uint32_t* subset, int32_t* ws,
                                       int64_t* row_counts, void* stream) {
-  if (!qf || !qw || !gf || !gw || !thr || !ws || !row_counts || !rg_args_ok(NQ, NV, M, d, 4)) return MMT_ERR_ARG;
-  if (((uintptr_t)qf | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
-  RgMaskedArgs a = {};
-  a.q = qf; a.qw = qw; a.g = gf; a.gw = gw; a.thr = thr; a.ws = ws; a.subset = subset;
-  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d;
-  return rg_count<false>(a, row_counts, (hipStream_t)stream);
+  return rg_count<false>(qf, nullptr, qw, gf, gw, NQ, NV, M, d, thr, subset, ws, row_counts, stream);
 }
 
 extern "C" int mmt_search_range_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
                                            const float* gw, int NQ, int NV, int M, int d, const float* thr,
                                            const uint32_t* subset, int32_t* ws, int64_t* row_counts, void* stream) {
-  if (!q_hi || !q_lo || !qw || !gf || !gw || !thr || !ws || !row_counts || !rg_args_ok(NQ, NV, M, d, 8))
-    return MMT_ERR_ARG;
-  if (((uintptr_t)q_hi | (uintptr_t)q_lo | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
-  RgMaskedArgs a = {};
-  a.q = q_hi; a.q_lo = q_lo; a.qw = qw; a.g = gf; a.gw = gw; a.thr = thr; a.ws = ws; a.subset = subset;
-  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d;
-  return rg_count<true>(a, row_counts, (hipStream_t)stream);
+  return rg_count<true>(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, ws, row_counts, stream);
 }
 
 extern "C" int mmt_search_range_fill(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
                                      int M, int d, const float* thr, const uint32_t* subset, const int32_t* ws,
                                      const int64_t* offsets, int64_t* indices, float* scores, void* stream) {
-  if (!qf || !qw || !gf || !gw || !thr || !ws || !offsets || !indices || !scores || !rg_args_ok(NQ, NV, M, d, 4))
-    return MMT_ERR_ARG;
-  if (((uintptr_t)qf | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
-  RgMaskedArgs a = {};
-  a.q = qf; a.qw = qw; a.g = gf; a.gw = gw; a.thr = thr; a.ws = const_cast<int32_t*>(ws); a.subset = subset;
-  a.offsets = offsets; a.indices = indices; a.scores = scores;
-  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d;
-  return rg_fill<false>(a, (hipStream_t)stream);
+  return rg_fill_hits<false>(qf, nullptr, qw, gf, gw, NQ, NV, M, d, thr, subset, ws, offsets, indices, scores, stream);
 }
 
 extern "C" int mmt_search_range_fill_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
                                           const float* gw, int NQ, int NV, int M, int d, const float* thr,
                                           const uint32_t* subset, const int32_t* ws, const int64_t* offsets,
                                           int64_t* indices, float* scores, void* stream) {
-  if (!q_hi || !q_lo || !qw || !gf || !gw || !thr || !ws || !offsets || !indices || !scores ||
-      !rg_args_ok(NQ, NV, M, d, 8))
-    return MMT_ERR_ARG;
-  if (((uintptr_t)q_hi | (uintptr_t)q_lo | (uintptr_t)gf | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
-  RgMaskedArgs a = {};
-  a.q = q_hi; a.q_lo = q_lo; a.qw = qw; a.g = gf; a.gw = gw; a.thr = thr; a.ws = const_cast<int32_t*>(ws); a.subset = subset;
-  a.offsets = offsets; a.indices = indices; a.scores = scores;
-  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d;
-  return rg_fill<true>(a, (hipStream_t)stream);
+  return rg_fill_hits<true>(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, ws, offsets, indices, scores, stream);
 }

@@ -1,12 +1,17 @@
-// The scoring tile of the gallery scans, shared by the top-k kernels (search.hip, search_bf16.hip: a running top-k per
-// query) and the rank-count kernels (search_rank.hip: a counter per query and target): block shape, the two K loops (fp32
-// gallery on v_mfma_f32_32x32x2_f32, bf16 gallery on v_mfma_f32_32x32x16_bf16), the gated-denominator epilogue and the
-// chunk rule.  One copy, so every kernel that scores a (query, item) pair computes the same bits for it.  The querybank
-// normalisation kernels (search_norm.hip) score with the same tile and add the two passes at the end of this file.
+// The scoring tile of the gallery scans, shared by every kernel that scores a (query, item) pair: the top-k kernels
+// (search.hip: a running top-k per query), the count / threshold kernels (search_rank.hip: a counter per query and
+// target), the range kernels (search_range.hip: every hit) and the querybank column pass (search_norm.hip).  Block shape,
+// the two K loops (fp32 gallery on v_mfma_f32_32x32x2_f32, bf16 gallery on v_mfma_f32_32x32x16_bf16), the gated-denominator
+// epilogue and the querybank rewrite are composed in ONE place, tk_tile, so a pair has the same score bits on every path
+// by construction.  The subset gate of a tile (tk_tile_mask), the chunk rule and launch geometry (tk_chunk, tk_geometry),
+// the shape gate and the per-device dynamic-LDS limit (tk_lds_limits) are here once as well.
 //
 // Which gallery row a tile row / column holds is a functor `grow(r)`, r in 0 .. TK_G - 1 -> gallery row, or -1 for "none"
 // (zero-filled in registers, never read): g0 + r for a scan, a table lookup for the rank kernels' threshold pass.
 #pragma once
+#include <cmath>
+#include <initializer_list>
+
 #include "mmt_common.h"
 #include "../../include/mmt_hip.h"
 
@@ -188,7 +193,7 @@ __device__ __forceinline__ float tk_mul_rn(float a, float b) {
   return r;
 }
 
-// Querybank normalisation of one score tile in place (search_norm.hip only): sS[r][c] = fl(fl(beta * sS[r][c]) - lse[item
+// Querybank normalisation of one score tile in place (tk_tile<., true> only): sS[r][c] = fl(fl(beta * sS[r][c]) - lse[item
 // of column c]) -- a rounded multiply, then a rounded subtract, never an fma, so the value can be restated bit for bit.
 // Two threads per column (rows of one parity each); a thread reads its column's lse once per tile.  A column without an
 // item (grow = -1) keeps a plain product: it is never selected or counted.  The caller syncs before the tile is read.
@@ -211,6 +216,93 @@ __device__ __forceinline__ void tk_tile_col_stats(const float* sS, float beta, i
   for (int row = 0; row < rows_live; ++row) p += expf(tk_mul_rn(beta, sS[row * TK_SLD + col]) - m);
 }
 
-// Host side (search.hip): gallery columns per block, TK_CHUNK halved (down to one tile) while the launch would not fill
+// One 64 x 128 tile of scores in sS: the K loop, the gated-denominator epilogue and, with NORM, the querybank rewrite to
+// score'.  Ends fenced.  `a` is any of the scans' argument blocks (q, q_lo for BF16, g, gw, NQ, K, M; lse and beta for
+// NORM).
+template <bool BF16, bool NORM, class Args, class GRow>
+__device__ __forceinline__ void tk_tile(const Args& a, unsigned char* smem, float* sS, const float* sQw, int q0, GRow grow,
+                                        int tid, int wq, int wg, int l31, int h) {
+  f32x16 acc[2];
+  if constexpr (BF16)
+    tk_scan_bf16(acc, smem, (const bf16_t*)a.q, (const bf16_t*)a.q_lo, (const bf16_t*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg,
+                 l31, h);
+  else
+    tk_scan_f32(acc, smem, (const float*)a.q, (const float*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg, l31, h);
+  __syncthreads();  // the slabs become the score tile
+  tk_tile_scores(acc, sS, sQw, a.gw, a.M, grow, wq, wg, l31, h);
+  __syncthreads();
+  if constexpr (NORM) {
+    tk_tile_norm(sS, a.lse, a.beta, grow, tid);
+    __syncthreads();
+  }
+}
+
+// How a subset bitmap (search_subset.hip: bit g & 31 of word g >> 5 allows item g) enters a scan kernel: not at all, as a
+// compile-time fact, or as a pointer that may be null (= every item allowed).  An argument block says so itself, in
+// kMask, and in kNorm whether its kernels score the querybank-normalised score': the kernels are generic over the block.
+enum TkMask { TK_MASK_NONE, TK_MASK_SET, TK_MASK_NULLABLE };
+
+// The subset gate of the tile at g0 (a multiple of 128): its four mask words are one block-uniform 16-byte load; m0 holds
+// columns 0 .. 63, m1 columns 64 .. 127.  False = no bit set: the caller skips the tile before its K loop.
+__device__ __forceinline__ bool tk_tile_mask(const uint32_t* subset, int g0, uint64_t& m0, uint64_t& m1) {
+  const u32x4 w = *(const u32x4*)(subset + (g0 >> 5));
+  m0 = w[0] | (uint64_t)w[1] << 32;
+  m1 = w[2] | (uint64_t)w[3] << 32;
+  return m0 | m1;
+}
+
+// The operands of the querybank scans; the argument blocks of the normalised top-k (search.hip) and rank kernels
+// (search_rank.hip) extend it.
+struct NmArgs {
+  const void* q;        // fp32: Q' [NQ][K]; bf16: hi(Q')
+  const void* q_lo;     // bf16: lo(Q')
+  const float* qw;      // [NQ][M]
+  const void* g;        // [NV][K] fp32 or bf16 bits
+  const float* gw;      // [NV][M]
+  const float* lse;     // [NV] (the lse pass: unused)
+  float beta;
+  int NQ, NV, M, K, chunk, n_qt, n_chunks;
+  static constexpr TkMask kMask = TK_MASK_NULLABLE;
+  static constexpr bool kNorm = true;
+};
+
+// Host side.  Gallery columns per block (search.hip): TK_CHUNK halved (down to one tile) while the launch would not fill
 // the chip.
 int tk_chunk(int NQ, int NV);
+
+inline int tk_n_chunks(int NQ, int NV) {
+  const int chunk = tk_chunk(NQ, NV);
+  return (NV + chunk - 1) / chunk;
+}
+
+// The launch geometry of a scan over a.NQ queries and a.NV items: grid = n_qt * n_chunks blocks.
+template <class Args>
+void tk_geometry(Args& a) {
+  a.chunk = tk_chunk(a.NQ, a.NV);
+  a.n_qt = (a.NQ + TK_Q - 1) / TK_Q;
+  a.n_chunks = (a.NV + a.chunk - 1) / a.chunk;
+}
+
+// The shape gate of every scan entry point: folded rows are 16 bytes times a whole number (d % 4 fp32, d % 8 bf16).
+inline bool tk_shape_ok(int NQ, int NV, int M, int d, bool bf16) {
+  return NQ > 0 && NV > 0 && M > 0 && M <= MMT_MAX_EXPERTS && d > 0 && !(d & (bf16 ? 7 : 3));
+}
+
+inline bool tk_beta_ok(float beta) { return beta > 0.f && std::isfinite(beta); }
+
+template <bool BF16>
+constexpr size_t tk_base_lds() { return (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + TK_QW_BYTES; }
+
+// Raises the dynamic-LDS limit of kernels whose footprint can pass the 64 KiB default, once on every device they are
+// launched on: a function attribute belongs to the device that is current when it is set, and a gallery cut into shards
+// launches on several.  `done` is the caller's table (static, zeroed), one per group of kernels.  Two threads meeting here
+// set the same values twice.
+struct TkLdsLimit { const void* kernel; size_t bytes; };
+inline void tk_lds_limits(bool (&done)[64], std::initializer_list<TkLdsLimit> kernels) {
+  int dev = -1;
+  const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;  // beyond the table: set every time
+  if (known && done[dev]) return;
+  for (const TkLdsLimit& k : kernels)
+    (void)hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes);
+  if (known) done[dev] = true;
+}

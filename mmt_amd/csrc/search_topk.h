@@ -1,6 +1,6 @@
-// Selection machinery of the top-k search, shared by the fp32 kernels (search.hip) and the bf16-gallery kernel
-// (search_bf16.hip): the (score, index) key and the per-row running top-k in LDS.  The scoring tile itself (K loops, score
-// epilogue, chunk rule) is search_scan.h.  See search.hip for the algorithm.
+// Selection machinery of the top-k search (search.hip; the shard merge of search_shard.hip shares the key): the
+// (score, index) key and the per-row running top-k in LDS.  The scoring tile itself (K loops, score epilogue, chunk rule)
+// is search_scan.h.  See search.hip for the algorithm.
 #pragma once
 #include "search_scan.h"
 
@@ -100,13 +100,3 @@ __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, in
     if (lane == 0) { sN[row] = n; sT[row] = thr; }
   }
 }
-
-// Host side (search.hip): the argument gate and the merge launch, shared by the fp32 and bf16 paths.
-bool tk_args_ok(int NQ, int NV, int k);
-size_t tk_state_lds(int k);  // LDS behind the slab / score-tile union: query weights, counts, thresholds, candidates
-size_t tk_exclude_lds(int E);  // ... and behind those, the masked kernels' exclusions [TK_Q][E]
-// The gate of the masked entry points: false with *rc = MMT_ERR_ARG (E outside 0 .. TK_MAXE, E > 0 without a list) or
-// MMT_ERR_ALIGN (subset words not 16-byte aligned; null = every item allowed).
-bool tk_mask_args_ok(const uint32_t* subset, const int64_t* exclude, int E, int* rc);
-int tk_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, float* scores, int64_t* index,
-                    hipStream_t s);

@@ -214,7 +214,249 @@ def _pick(use, normed, plain):
   return torch.where(use.reshape((-1,) + (1,) * (normed.dim() - 1)), normed, plain)
 
 
-class VideoIndex:
+def _column_groups(src, outs, r0, r1):
+  """Rows r0 .. r1 - 1 of src [NQ, T] and of every tensor of outs, in column groups of at most MAX_T (the launches' limit):
+  yields (the src slice, the out slices), all contiguous.  A column slice of a wider list is not contiguous: it is copied
+  in, and the outs are copied back when the caller asks for the next group."""
+  t_all = src.shape[1]
+  for t0 in range(0, t_all, MAX_T):
+    t1 = min(t_all, t0 + MAX_T)
+    whole = t1 - t0 == t_all
+    parts = [o[r0:r1] if whole else torch.empty(r1 - r0, t1 - t0, device=o.device, dtype=o.dtype) for o in outs]
+    yield src[r0:r1] if whole else src[r0:r1, t0:t1].contiguous(), parts
+    if not whole:
+      for o, part in zip(outs, parts):
+        o[r0:r1, t0:t1] = part
+
+
+class _Index:
+  """What VideoIndex and ShardedVideoIndex share: the checks of every public call, the calls that are the same on both
+  (`search`, `rank_counts`, `ranks`, `hub_norm` up to the scan) and QB-Norm's dynamic rule.  It reads the bookkeeping both
+  have -- num_experts, dim, num_items, device (the primary of a sharded index) -- and leaves to the class what happens
+  behind the checks: _search, _rank_counts, _hub_norm and the type checks _subset / _norm."""
+
+  @staticmethod
+  def _items(embds, weights, who):
+    g = _cuda_f32(embds, 'embds')
+    gw = _cuda_f32(weights, 'weights')
+    if g.dim() != 3 or gw.shape != g.shape[:2]:
+      raise ValueError('%s expects embds (NV, M, d) and weights (NV, M), got %s and %s' % (
+          who, tuple(g.shape), tuple(gw.shape)))
+    if g.shape[0] < 1:
+      raise ValueError('%s: need NV >= 1, got %s' % (who, tuple(g.shape)))
+    return g, gw
+
+  def _queries(self, embds, weights):
+    q = _cuda_f32(embds, 'embds')
+    qw = _cuda_f32(weights, 'weights')
+    m, d = self.num_experts, self.dim
+    if q.dim() == 4:  # CENet text layout (B, M, C, d) / (B, C, M) -> rows b*C + c, as metric.eval_similarity
+      b, qm, c, qd = q.shape
+      if (qm, qd) != (m, d) or tuple(qw.shape) != (b, c, m):
+        raise ValueError('search: text embds (B, %d, C, %d) with weights (B, C, %d) expected, got %s and %s' % (
+            m, d, m, tuple(q.shape), tuple(qw.shape)))
+      q = q.permute(0, 2, 1, 3).reshape(b * c, m, d).contiguous()
+      qw = qw.reshape(b * c, m).contiguous()
+    elif q.dim() != 3 or tuple(q.shape[1:]) != (m, d) or tuple(qw.shape) != (q.shape[0], m):
+      raise ValueError('search: embds (NQ, %d, %d) with weights (NQ, %d) expected, got %s and %s' % (
+          m, d, m, tuple(q.shape), tuple(qw.shape)))
+    if q.device != self.device or qw.device != self.device:
+      raise ValueError('search: queries must be on the index device %s' % self.device)
+    return q, qw
+
+  def _subset_mask(self, items):
+    """The checks of `subset` -> (the set as a bool mask [num_items] of its own, the number of allowed items)."""
+    if self.num_items == 0:
+      raise ValueError('subset: the index holds no items')
+    if not torch.is_tensor(items) or items.dtype not in (torch.bool, torch.int64):
+      raise ValueError('subset: items must be a bool or int64 tensor, got %s' % (
+          items.dtype if torch.is_tensor(items) else type(items).__name__))
+    if items.device != self.device:
+      raise ValueError('subset: items must be on the index device %s, got %s' % (self.device, items.device))
+    nv = self.num_items
+    if items.dtype == torch.bool:
+      if tuple(items.shape) != (nv,):
+        raise ValueError('subset: a bool mask of shape (%d,) expected, got %s' % (nv, tuple(items.shape)))
+      mask = items.contiguous().clone()
+    else:
+      ids = items.reshape(-1)
+      if ids.numel() == 0:
+        raise ValueError('subset: no item allowed')
+      lo, hi = (int(v) for v in torch.aminmax(ids))
+      if lo < 0 or hi >= nv:
+        raise ValueError('subset: items must lie in 0 .. %d, got %d .. %d' % (nv - 1, lo, hi))
+      mask = torch.zeros(nv, device=self.device, dtype=torch.bool).index_fill_(0, ids, True)
+    count = int(mask.sum())
+    if count == 0:
+      raise ValueError('subset: no item allowed')
+    return mask, count
+
+  def _exclude(self, exclude):
+    """Type, device and width of `exclude`: all that can be said about it before the queries are known."""
+    if not torch.is_tensor(exclude) or exclude.dtype != torch.int64:
+      raise ValueError('search: exclude must be an int64 tensor, got %s' % (
+          exclude.dtype if torch.is_tensor(exclude) else type(exclude).__name__))
+    if exclude.dim() not in (1, 2) or exclude.dim() == 2 and not 1 <= exclude.shape[1] <= MAX_E:
+      raise ValueError('search: exclude [NQ] or [NQ, 1 <= E <= %d] expected, got %s' % (MAX_E, tuple(exclude.shape)))
+    if exclude.device != self.device:
+      raise ValueError('search: exclude must be on the index device %s, got %s' % (self.device, exclude.device))
+
+  def _targets(self, targets):
+    """Type, device and rank of `targets`: all that can be said about them before the queries are known."""
+    if not torch.is_tensor(targets) or targets.dtype != torch.int64:
+      raise ValueError('ranks: targets must be an int64 tensor, got %s' % (
+          targets.dtype if torch.is_tensor(targets) else type(targets).__name__))
+    if targets.device != self.device:
+      raise ValueError('ranks: targets must be on the index device %s, got %s' % (self.device, targets.device))
+    if targets.dim() not in (1, 2) or targets.dim() == 2 and targets.shape[1] < 1:
+      raise ValueError('ranks: targets [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(targets.shape),))
+
+  def _target_range(self, targets):
+    """The values of the (non-empty) targets against -1 .. num_items - 1: one small reduction and a host sync."""
+    lo, hi = (int(v) for v in torch.aminmax(targets))
+    if lo < -1 or hi >= self.num_items:
+      raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
+
+  def _scan_args(self, who, embds, weights, subset, norm, dynamic, exclude=None):
+    """The checks every scan shares once its own arguments have passed -> q, qw, whether the dynamic rule applies."""
+    if subset is not None:
+      self._subset(subset, who)
+    if exclude is not None:
+      self._exclude(exclude)
+    if norm is not None:
+      self._norm(norm, who)
+    dynamic = _check_dynamic(dynamic, norm, who)
+    q, qw = self._queries(embds, weights)
+    return q, qw, dynamic
+
+  def _use_norm(self, q, qw, subset, ex, norm):
+    """QB-Norm's dynamic rule: bool [NQ], True where the query's plain top-1 among its candidates (after subset and
+    exclusions) is one of norm.hubs.  A query without a candidate keeps its plain result."""
+    top1 = self._search(q, qw, 1, subset, ex)[1][:, 0]
+    return (top1 >= 0) & norm.hubs[top1.clamp(min=0)]
+
+  def _dynamic(self, dynamic, q, qw, subset, ex, norm, normed, plain):
+    """The result of a call with norm=: `normed` (a tuple of tensors, every query normalised) as it is, or under the dynamic
+    rule mixed per query with what `plain()` gives."""
+    if not dynamic or q.shape[0] == 0:
+      return normed
+    use = self._use_norm(q, qw, subset, ex, norm)
+    return tuple(_pick(use, a, b) for a, b in zip(normed, plain()))
+
+  def hub_norm(self, bank_embds, bank_weights, beta, dynamic=False):
+    """The querybank normaliser of this index (inverted softmax, the static half of QB-Norm): bank queries in either layout
+    of `search`, NB >= 1 of them, and a temperature beta (a Python float, 0 < beta < inf) -> HubNorm (ShardedVideoIndex:
+    ShardedHubNorm) with lse[g] = log sum_b exp(fl(beta * score(b, g))) per stored item, in fp32 (mmt_search_col_lse).
+    Passed as norm= to `search`, `rank_counts`, `ranks`, `target_scores` and `threshold_counts` it replaces score(q, g) by
+    score'(q, g) = fl(fl(beta * score(q, g)) - lse[g]), the log of the inverted-softmax probability.  The bank streams
+    through in batches within _BATCH_BYTES; lse[g] does not depend on the batching, on num_items, on g's position or on the
+    shard that holds g.  dynamic=True also records `hubs`, the items that are the plain top-1 of a bank query (one
+    search(k=1) of the bank): a call with such a norm then normalises only the queries whose own plain top-1 is a hub
+    (QB-Norm's dynamic inverted softmax).  Like a subset, a norm describes the num_items of this moment: after a further
+    `add` it is refused."""
+    _check_beta(beta)
+    if not isinstance(dynamic, bool):
+      raise ValueError('hub_norm: dynamic must be False or True, got %r' % (dynamic,))
+    if self.num_items == 0:
+      raise ValueError('hub_norm: the index holds no items')
+    b, bw = self._queries(bank_embds, bank_weights)
+    if b.shape[0] < 1:
+      raise ValueError('hub_norm: the bank holds no queries')
+    hubs = None
+    if dynamic:
+      top1 = self._search(b, bw, 1, None, None)[1][:, 0]
+      hubs = torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
+    return self._hub_norm(b, bw, beta, hubs)
+
+  def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None):
+    """Queries (NQ, M, d) / (NQ, M), or the text layout (B, M, C, d) / (B, C, M) -> (scores [NQ, k'] float32,
+    indices [NQ, k'] int64) on the device, k' = min(k, NV), best first.  subset (from this index's `subset`): only its
+    items are candidates and k' = min(k, subset.count).  exclude: int64 [NQ] or [NQ, E <= 32] on the index device, values
+    -1 .. num_items - 1 (-1 = none; duplicates and items outside the subset are fine): items barred for that query; its
+    range is checked as that of `rank_counts`' targets, before anything is scored.  A query with fewer than k' candidates
+    left gets score -inf and index -1 in the remaining slots.  norm (from this index's `hub_norm`): the ranking and the
+    returned scores are those of score' (mmt_search_topk_norm); with a norm that has `hubs`, only the queries whose plain
+    top-1 candidate is a hub are normalised and the others keep their plain result (dynamic=False normalises every query).
+    ShardedVideoIndex: every shard searches its own items for its best min(k', its candidates), with its part of the
+    subset and the norm; the lists are copied to the primary and merged there in one launch."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+      raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
+    if self.num_items == 0:
+      raise ValueError('search: the index holds no items')
+    q, qw, dynamic = self._scan_args('search', embds, weights, subset, norm, dynamic, exclude)
+    ex = _exclusions(exclude, q.shape[0], self.num_items)
+    out = self._search(q, qw, k, subset, ex, norm)
+    return self._dynamic(dynamic, q, qw, subset, ex, norm, out, lambda: self._search(q, qw, k, subset, ex))
+
+  def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
+    """Queries as for `search`; targets [NQ] or [NQ, T] int64 on the index device, values -1 .. num_items - 1 ->
+    (greater, equal), int32 of targets' shape: how many of the num_items stored items score above / exactly equal to item
+    targets[q, t] for query q (the item itself is one of the equal ones); 0 / 0 where the target is -1.  The range of the
+    targets is checked here (one small reduction and a host sync); nothing is scored before it passes.  subset: only its
+    items are counted; a target outside it is still scored but does not count itself, so its `equal` may be 0.  norm: the
+    counts are those of score' -- the target's score' from the threshold pass, then the count pass against it
+    (mmt_search_thresholds_norm, mmt_search_count_norm); with a norm that has `hubs` only the queries whose plain top-1
+    candidate is a hub, the others keep their plain counts (dynamic=False normalises every query).  ShardedVideoIndex: each
+    shard scores the targets it holds, the primary picks the owner's value per (query, target), each shard counts its
+    items against those thresholds and the int32 counts are summed on the primary."""
+    if self.num_items == 0:
+      raise ValueError('ranks: the index holds no items')
+    self._targets(targets)
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic)
+    nq, shape = q.shape[0], targets.shape
+    if shape[0] != nq:
+      raise ValueError('ranks: %d queries but targets %s' % (nq, tuple(shape)))
+    if nq == 0:
+      return tuple(torch.empty(shape, device=self.device, dtype=torch.int32) for _ in range(2))
+    tg = targets.reshape(nq, -1).contiguous()
+    self._target_range(tg)
+    out = self._rank_counts(q, qw, tg, subset, norm)
+    out = self._dynamic(dynamic, q, qw, subset, None, norm, out, lambda: self._rank_counts(q, qw, tg, subset))
+    return out[0].reshape(shape), out[1].reshape(shape)
+
+  def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
+    """The reference's tie-averaged 0-based rank (model/metric.py:90-121) of item targets[q, t] among the stored items for
+    query q: greater + (equal - 1) / 2 from `rank_counts`, +inf where the target is -1.  float64 on the device, of
+    targets' shape (float32 would not hold counts above 2^24).  subset: the rank among its items, +inf for a target that
+    is not one of them.  norm, dynamic: as `rank_counts` -- the rank under the querybank-normalised score."""
+    greater, equal = self.rank_counts(embds, weights, targets, subset=subset, norm=norm, dynamic=dynamic)
+    ranks = greater.double() + (equal.double() - 1) / 2
+    none = targets < 0
+    if subset is not None:
+      none = none | ~subset.mask[targets.clamp(min=0)]
+    return torch.where(none, torch.full_like(ranks, float('inf')), ranks)
+
+  def _range_args(self, embds, weights, threshold, subset, order, max_hits):
+    """The checks of `range_search` -> q, qw, thr float32 [NQ]."""
+    if order not in ('index', 'score'):
+      raise ValueError("range_search: order must be 'index' or 'score', got %r" % (order,))
+    if isinstance(max_hits, bool) or not isinstance(max_hits, int) or max_hits < 0:
+      raise ValueError('range_search: max_hits must be an int >= 0, got %r' % (max_hits,))
+    if self.num_items == 0:
+      raise ValueError('range_search: the index holds no items')
+    if torch.is_tensor(threshold):
+      if threshold.dtype != torch.float32:
+        raise ValueError('range_search: threshold must be a float or a float32 tensor, got %s' % threshold.dtype)
+      if threshold.device != self.device:
+        raise ValueError('range_search: threshold must be on the index device %s, got %s' % (self.device, threshold.device))
+      if threshold.dim() != 1:
+        raise ValueError('range_search: threshold [NQ] expected, got %s' % (tuple(threshold.shape),))
+    elif isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+      raise ValueError('range_search: threshold must be a float or a float32 tensor, got %s' % type(threshold).__name__)
+    if subset is not None:
+      self._subset(subset, 'range_search')
+    q, qw = self._queries(embds, weights)
+    nq = q.shape[0]
+    if torch.is_tensor(threshold):
+      if threshold.shape[0] != nq:
+        raise ValueError('range_search: %d queries but threshold %s' % (nq, tuple(threshold.shape)))
+      thr = threshold.contiguous()
+    else:
+      thr = torch.full((nq,), float(threshold), device=self.device, dtype=torch.float32)
+    return q, qw, thr
+
+
+class VideoIndex(_Index):
   """A gallery of up to `capacity` items with M expert embeddings of width d (M <= 16), weighted per item and expert.
   dtype=torch.float32 (d % 4 == 0) stores the fold gw (.) G as it is; dtype=torch.bfloat16 (d % 8 == 0) stores it rounded
   once to bf16 -- half the bytes, scored on the bf16 matrix cores against the unrounded fp32 queries (module docstring)."""
@@ -252,17 +494,6 @@ class VideoIndex:
     self.folded = torch.empty(capacity, m * d, device=device, dtype=dtype)   # gw (.) G; rows < num_items are valid
     self.weights = torch.empty(capacity, m, device=device, dtype=torch.float32)
 
-  @staticmethod
-  def _items(embds, weights, who):
-    g = _cuda_f32(embds, 'embds')
-    gw = _cuda_f32(weights, 'weights')
-    if g.dim() != 3 or gw.shape != g.shape[:2]:
-      raise ValueError('%s expects embds (NV, M, d) and weights (NV, M), got %s and %s' % (
-          who, tuple(g.shape), tuple(gw.shape)))
-    if g.shape[0] < 1:
-      raise ValueError('%s: need NV >= 1, got %s' % (who, tuple(g.shape)))
-    return g, gw
-
   @property
   def nbytes(self):
     """Bytes held by the index: the folded storage plus the weights, at full capacity."""
@@ -292,57 +523,12 @@ class VideoIndex:
     self.num_items = last
     return first, last
 
-  def _queries(self, embds, weights):
-    q = _cuda_f32(embds, 'embds')
-    qw = _cuda_f32(weights, 'weights')
-    m, d = self.num_experts, self.dim
-    if q.dim() == 4:  # CENet text layout (B, M, C, d) / (B, C, M) -> rows b*C + c, as metric.eval_similarity
-      b, qm, c, qd = q.shape
-      if (qm, qd) != (m, d) or tuple(qw.shape) != (b, c, m):
-        raise ValueError('search: text embds (B, %d, C, %d) with weights (B, C, %d) expected, got %s and %s' % (
-            m, d, m, tuple(q.shape), tuple(qw.shape)))
-      q = q.permute(0, 2, 1, 3).reshape(b * c, m, d).contiguous()
-      qw = qw.reshape(b * c, m).contiguous()
-    elif q.dim() != 3 or tuple(q.shape[1:]) != (m, d) or tuple(qw.shape) != (q.shape[0], m):
-      raise ValueError('search: embds (NQ, %d, %d) with weights (NQ, %d) expected, got %s and %s' % (
-          m, d, m, tuple(q.shape), tuple(qw.shape)))
-    if q.device != self.device or qw.device != self.device:
-      raise ValueError('search: queries must be on the index device %s' % self.device)
-    return q, qw
-
   def subset(self, items):
     """items: bool [num_items] (True = allowed) or int64 item numbers (any shape, any order, duplicates allowed), on the
     index device -> IndexSubset for `search`, `rank_counts` and `ranks`.  Packed here, once; the range of the numbers is
     checked (one small reduction and a host sync).  It describes the num_items of this moment: after a further `add` it
     is refused.  Raises ValueError for an empty subset."""
     return IndexSubset(*self._subset_mask(items))
-
-  def _subset_mask(self, items):
-    """The checks of `subset` -> (the set as a bool mask [num_items] of its own, the number of allowed items)."""
-    if self.num_items == 0:
-      raise ValueError('subset: the index holds no items')
-    if not torch.is_tensor(items) or items.dtype not in (torch.bool, torch.int64):
-      raise ValueError('subset: items must be a bool or int64 tensor, got %s' % (
-          items.dtype if torch.is_tensor(items) else type(items).__name__))
-    if items.device != self.device:
-      raise ValueError('subset: items must be on the index device %s, got %s' % (self.device, items.device))
-    nv = self.num_items
-    if items.dtype == torch.bool:
-      if tuple(items.shape) != (nv,):
-        raise ValueError('subset: a bool mask of shape (%d,) expected, got %s' % (nv, tuple(items.shape)))
-      mask = items.contiguous().clone()
-    else:
-      ids = items.reshape(-1)
-      if ids.numel() == 0:
-        raise ValueError('subset: no item allowed')
-      lo, hi = (int(v) for v in torch.aminmax(ids))
-      if lo < 0 or hi >= nv:
-        raise ValueError('subset: items must lie in 0 .. %d, got %d .. %d' % (nv - 1, lo, hi))
-      mask = torch.zeros(nv, device=self.device, dtype=torch.bool).index_fill_(0, ids, True)
-    count = int(mask.sum())
-    if count == 0:
-      raise ValueError('subset: no item allowed')
-    return mask, count
 
   def _subset(self, subset, who):
     if not isinstance(subset, IndexSubset):
@@ -352,16 +538,6 @@ class VideoIndex:
     if subset.device != self.device:
       raise ValueError('%s: the subset is on %s, the index on %s' % (who, subset.device, self.device))
 
-  def _exclude(self, exclude):
-    """Type, device and width of `exclude`: all that can be said about it before the queries are known."""
-    if not torch.is_tensor(exclude) or exclude.dtype != torch.int64:
-      raise ValueError('search: exclude must be an int64 tensor, got %s' % (
-          exclude.dtype if torch.is_tensor(exclude) else type(exclude).__name__))
-    if exclude.dim() not in (1, 2) or exclude.dim() == 2 and not 1 <= exclude.shape[1] <= MAX_E:
-      raise ValueError('search: exclude [NQ] or [NQ, 1 <= E <= %d] expected, got %s' % (MAX_E, tuple(exclude.shape)))
-    if exclude.device != self.device:
-      raise ValueError('search: exclude must be on the index device %s, got %s' % (self.device, exclude.device))
-
   def _norm(self, norm, who):
     if not isinstance(norm, HubNorm):
       raise ValueError('%s: norm must come from VideoIndex.hub_norm, got %s' % (who, type(norm).__name__))
@@ -370,224 +546,15 @@ class VideoIndex:
     if norm.device != self.device:
       raise ValueError('%s: the norm is on %s, the index on %s' % (who, norm.device, self.device))
 
-  def hub_norm(self, bank_embds, bank_weights, beta, dynamic=False):
-    """The querybank normaliser of this index (inverted softmax, the static half of QB-Norm): bank queries in either layout
-    of `search`, NB >= 1 of them, and a temperature beta (a Python float, 0 < beta < inf) -> HubNorm with
-    lse[g] = log sum_b exp(fl(beta * score(b, g))) per stored item, in fp32 (mmt_search_col_lse).  Passed as norm= to
-    `search`, `rank_counts`, `ranks`, `target_scores` and `threshold_counts` it replaces score(q, g) by
-    score'(q, g) = fl(fl(beta * score(q, g)) - lse[g]), the log of the inverted-softmax probability.  The bank streams
-    through in batches within _BATCH_BYTES; lse[g] does not depend on the batching, on num_items or on g's position.
-    dynamic=True also records `hubs`, the items that are the plain top-1 of a bank query (one search(k=1) of the bank):
-    a call with such a norm then normalises only the queries whose own plain top-1 is a hub (QB-Norm's dynamic inverted
-    softmax).  Like a subset, a norm describes the num_items of this moment: after a further `add` it is refused."""
-    _check_beta(beta)
-    if not isinstance(dynamic, bool):
-      raise ValueError('hub_norm: dynamic must be False or True, got %r' % (dynamic,))
-    if self.num_items == 0:
-      raise ValueError('hub_norm: the index holds no items')
-    b, bw = self._queries(bank_embds, bank_weights)
-    if b.shape[0] < 1:
-      raise ValueError('hub_norm: the bank holds no queries')
-    hubs = None
-    if dynamic:
-      top1 = self._search(b, bw, 1, None, None)[1][:, 0]
-      hubs = torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
-    return HubNorm(self._col_lse(b, bw, beta), beta, b.shape[0], hubs)
-
-  def _col_lse(self, b, bw, beta):
-    """`hub_norm` behind its checks: b (NB, M, d) / bw (NB, M) fp32 on the index device -> lse fp32 [num_items].  The bank
-    goes through in batches of whole 64-row blocks; the running (M, S) pair per item carries from one to the next."""
-    nb, nv, m, d = b.shape[0], self.num_items, self.num_experts, self.dim
-    L = _lib.lib()
-    fn, name = ((L.mmt_search_col_lse_bf16, 'mmt_search_col_lse_bf16') if self.dtype == torch.bfloat16 else
-                (L.mmt_search_col_lse, 'mmt_search_col_lse'))
-    with torch.cuda.device(self.device):
-      lse = torch.empty(nv, device=self.device, dtype=torch.float32)
-      state = torch.empty(2, nv, device=self.device, dtype=torch.float32)
-      per_row = m * d * 4 + -(-nv // 8)  # folded row + its share of the block's (m, p) pairs: 8 bytes per item / 64 rows
-      batch = max(64, (_BATCH_BYTES // per_row) // 64 * 64)
-      ws = torch.empty(L.mmt_col_lse_workspace_floats(min(nb, batch), nv), device=self.device, dtype=torch.float32)
-      for r0 in range(0, nb, batch):
-        r1 = min(nb, r0 + batch)
-        operands, _keep = self._operands(b[r0:r1], bw[r0:r1])
-        check(fn(*operands, r1 - r0, nv, m, d, beta, ops._p(ws), ops._p(state), int(r0 == 0),
-                 ops._p(lse if r1 == nb else None), ops._stream()), name)
-    return lse
-
-  def _use_norm(self, q, qw, subset, ex, norm):
-    """QB-Norm's dynamic rule: bool [NQ], True where the query's plain top-1 among its candidates (after subset and
-    exclusions) is one of norm.hubs.  A query without a candidate keeps its plain result."""
-    top1 = self._search(q, qw, 1, subset, ex)[1][:, 0]
-    return (top1 >= 0) & norm.hubs[top1.clamp(min=0)]
-
-  def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None):
-    """Queries (NQ, M, d) / (NQ, M), or the text layout (B, M, C, d) / (B, C, M) -> (scores [NQ, k'] float32,
-    indices [NQ, k'] int64) on the device, k' = min(k, NV), best first.  subset (VideoIndex.subset): only its items are
-    candidates and k' = min(k, subset.count).  exclude: int64 [NQ] or [NQ, E <= 32] on the index device, values
-    -1 .. num_items - 1 (-1 = none; duplicates and items outside the subset are fine): items barred for that query; its
-    range is checked as that of `rank_counts`' targets, before anything is scored.  A query with fewer than k' candidates
-    left gets score -inf and index -1 in the remaining slots.  norm (VideoIndex.hub_norm): the ranking and the returned
-    scores are those of score' (mmt_search_topk_norm); with a norm that has `hubs`, only the queries whose plain top-1
-    candidate is a hub are normalised and the others keep their plain result (dynamic=False normalises every query)."""
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
-      raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
-    if self.num_items == 0:
-      raise ValueError('search: the index holds no items')
-    if subset is not None:
-      self._subset(subset, 'search')
-    if exclude is not None:
-      self._exclude(exclude)
-    if norm is not None:
-      self._norm(norm, 'search')
-    dynamic = _check_dynamic(dynamic, norm, 'search')
-    q, qw = self._queries(embds, weights)
-    ex = _exclusions(exclude, q.shape[0], self.num_items)
-    if norm is None:
-      return self._search(q, qw, k, subset, ex)
-    normed = self._search(q, qw, k, subset, ex, norm)
-    if not dynamic:
-      return normed
-    use = self._use_norm(q, qw, subset, ex, norm)
-    plain = self._search(q, qw, k, subset, ex)
-    return _pick(use, normed[0], plain[0]), _pick(use, normed[1], plain[1])
-
-  def _search(self, q, qw, k, subset, ex, norm=None):
-    """`search` behind its argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the index device, ex None or int64 [NQ, E]
-    there, norm None or a HubNorm of this index (every query normalised).  Nothing here waits for the device."""
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    masked = ()  # the extra arguments of the _ex entry points: subset words, exclusions of the batch, E
-    if subset is not None or ex is not None or norm is not None:
-      if subset is not None or ex is not None:
-        k = min(k, nv if subset is None else subset.count)  # lists no longer than the candidates: the outputs stay dense
-      masked = (None if subset is None else subset.words, ex, 0 if ex is None else ex.shape[1])
-    kout = min(k, nv)
-    if ex is None:
-      scores = torch.empty(nq, kout, device=self.device, dtype=torch.float32)
-      indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
-    else:  # the merge writes only the slots that have a candidate
-      scores = torch.full((nq, kout), float('-inf'), device=self.device, dtype=torch.float32)
-      indices = torch.full((nq, kout), -1, device=self.device, dtype=torch.int64)
-    if nq == 0:
-      return scores, indices
-    L = _lib.lib()
-    with torch.cuda.device(self.device):
-      per_row = m * d * 4 + 8 * k * -(-nv // 4096)  # folded row + its chunk lists at full-size chunks
-      batch = max(64, (_BATCH_BYTES // per_row) // 64 * 64)
-      for r0 in range(0, nq, batch):
-        r1 = min(nq, r0 + batch)
-        n = r1 - r0
-        ws = torch.empty(L.mmt_topk_workspace_keys(n, nv, k), device=self.device, dtype=torch.int64)
-        out = (ops._p(ws), ops._p(scores[r0:r1]), ops._p(indices[r0:r1]), ops._stream())
-        if masked:
-          words, ex, e = masked
-          out = (ops._p(words), ops._p(None if ex is None else ex[r0:r1]), e) + out
-          if norm is not None:
-            out = out[:3] + (norm.beta, ops._p(norm.lse)) + out[3:]
-        out = (n, nv, m, d, k) + out
-        if self.dtype == torch.bfloat16:
-          hl = torch.empty(2, n, m * d, device=self.device, dtype=torch.bfloat16)  # hi = bf16(qf), lo = bf16(qf - hi)
-          check(L.mmt_search_fold_split_bf16(ops._p(q[r0:r1]), ops._p(qw[r0:r1]), n, m, d, ops._p(hl[0]), ops._p(hl[1]),
-                                             ops._stream()), 'mmt_search_fold_split_bf16')
-          fn = L.mmt_search_topk_bf16_ex if masked else L.mmt_search_topk_bf16
-          if norm is not None:
-            fn = L.mmt_search_topk_bf16_norm
-          check(fn(ops._p(hl[0]), ops._p(hl[1]), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights), *out),
-                'mmt_search_topk_bf16')
-        else:
-          qf = _fold(q[r0:r1], qw[r0:r1])
-          fn = L.mmt_search_topk_ex if masked else L.mmt_search_topk
-          if norm is not None:
-            fn = L.mmt_search_topk_norm
-          check(fn(ops._p(qf), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights), *out), 'mmt_search_topk')
-    return scores, indices
-
-  def _targets(self, targets):
-    """Type, device and rank of `targets`: all that can be said about them before the queries are known."""
-    if not torch.is_tensor(targets) or targets.dtype != torch.int64:
-      raise ValueError('ranks: targets must be an int64 tensor, got %s' % (
-          targets.dtype if torch.is_tensor(targets) else type(targets).__name__))
-    if targets.device != self.device:
-      raise ValueError('ranks: targets must be on the index device %s, got %s' % (self.device, targets.device))
-    if targets.dim() not in (1, 2) or targets.dim() == 2 and targets.shape[1] < 1:
-      raise ValueError('ranks: targets [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(targets.shape),))
-
-  def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
-    """Queries as for `search`; targets [NQ] or [NQ, T] int64 on the index device, values -1 .. num_items - 1 ->
-    (greater, equal), int32 of targets' shape: how many of the num_items stored items score above / exactly equal to item
-    targets[q, t] for query q (the item itself is one of the equal ones); 0 / 0 where the target is -1.  The range of the
-    targets is checked here (one small reduction and a host sync); nothing is scored before it passes.  subset
-    (VideoIndex.subset): only its items are counted; a target outside it is still scored but does not count itself, so
-    its `equal` may be 0.  norm (VideoIndex.hub_norm): the counts are those of score' -- the target's score' from the
-    threshold pass, then the count pass against it (mmt_search_thresholds_norm, mmt_search_count_norm); with a norm that
-    has `hubs` only the queries whose plain top-1 candidate is a hub, the others keep their plain counts (dynamic=False
-    normalises every query)."""
-    if self.num_items == 0:
-      raise ValueError('ranks: the index holds no items')
-    self._targets(targets)
-    if subset is not None:
-      self._subset(subset, 'ranks')
-    if norm is not None:
-      self._norm(norm, 'ranks')
-    dynamic = _check_dynamic(dynamic, norm, 'ranks')
-    q, qw = self._queries(embds, weights)
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    if targets.shape[0] != nq:
-      raise ValueError('ranks: %d queries but targets %s' % (nq, tuple(targets.shape)))
-    shape = targets.shape
-    if nq == 0:
-      return tuple(torch.empty(shape, device=self.device, dtype=torch.int32) for _ in range(2))
-    tg = targets.reshape(nq, -1).contiguous()
-    lo, hi = (int(v) for v in torch.aminmax(tg))
-    if lo < -1 or hi >= nv:
-      raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (nv - 1, lo, hi))
-    if norm is not None:
-      normed = self._threshold_counts(q, qw, self._target_scores(q, qw, tg, norm), subset, norm)
-      if dynamic:
-        use = self._use_norm(q, qw, subset, None, norm)
-        plain = self.rank_counts(q, qw, tg, subset=subset)
-        normed = tuple(_pick(use, a, b) for a, b in zip(normed, plain))
-      return normed[0].reshape(shape), normed[1].reshape(shape)
-    greater = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
-    equal = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
-    L = _lib.lib()
-    bf16 = self.dtype == torch.bfloat16
-    with torch.cuda.device(self.device):
-      t_max = min(MAX_T, tg.shape[1])
-      per_row = m * d * 4 + 4 * t_max * (1 + 2 * -(-nv // 4096))  # folded row + its thresholds and chunk counters
-      batch = max(64, (_BATCH_BYTES // per_row) // 64 * 64)
-      for r0 in range(0, nq, batch):
-        r1 = min(nq, r0 + batch)
-        n = r1 - r0
-        if bf16:
-          hl = torch.empty(2, n, m * d, device=self.device, dtype=torch.bfloat16)  # hi = bf16(qf), lo = bf16(qf - hi)
-          check(L.mmt_search_fold_split_bf16(ops._p(q[r0:r1]), ops._p(qw[r0:r1]), n, m, d, ops._p(hl[0]), ops._p(hl[1]),
-                                             ops._stream()), 'mmt_search_fold_split_bf16')
-          operands = (ops._p(hl[0]), ops._p(hl[1]), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights))
-        else:
-          qf = _fold(q[r0:r1], qw[r0:r1])
-          operands = (ops._p(qf), ops._p(qw[r0:r1]), ops._p(self.folded), ops._p(self.weights))
-        ws = torch.empty(L.mmt_rank_workspace_ints(n, nv, t_max), device=self.device, dtype=torch.int32)
-        for t0 in range(0, tg.shape[1], MAX_T):
-          t1 = min(tg.shape[1], t0 + MAX_T)
-          whole = t0 == 0 and t1 == tg.shape[1]  # a column slice of a wider list is not contiguous: copy in and out
-          tgs = tg[r0:r1] if whole else tg[r0:r1, t0:t1].contiguous()
-          gs = greater[r0:r1] if whole else torch.empty(n, t1 - t0, device=self.device, dtype=torch.int32)
-          es = equal[r0:r1] if whole else torch.empty_like(gs)
-          fn, name = (L.mmt_search_rank_bf16, 'mmt_search_rank_bf16') if bf16 else (L.mmt_search_rank, 'mmt_search_rank')
-          if subset is None:
-            check(fn(*operands, n, nv, m, d, ops._p(tgs), t1 - t0, ops._p(ws), ops._p(gs), ops._p(es), ops._stream()), name)
-          else:
-            fn = L.mmt_search_rank_bf16_ex if bf16 else L.mmt_search_rank_ex
-            check(fn(*operands, n, nv, m, d, ops._p(tgs), t1 - t0, ops._p(subset.words), ops._p(ws), ops._p(gs), ops._p(es),
-                     ops._stream()), name)
-          if not whole:
-            greater[r0:r1, t0:t1] = gs
-            equal[r0:r1, t0:t1] = es
-    return greater.reshape(shape), equal.reshape(shape)
+  def _entry(self, op, variant=''):
+    """The C entry point of a scan over this index's storage: op 'topk', 'rank', 'thresholds', 'count', 'range_count',
+    'range_fill' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions) or '_norm' -> (the function, its name)."""
+    name = 'mmt_search_%s%s%s' % (op, '_bf16' if self.dtype == torch.bfloat16 else '', variant)
+    return getattr(_lib.lib(), name), name
 
   def _operands(self, q, qw):
-    """The query operands of the rank entry points for one batch of rows: the fp32 fold, or its bf16 hi / lo pair.  Returns
-    (pointers, the tensors they point into)."""
+    """The query and gallery operands of the scan entry points for one batch of rows: the fp32 fold, or its bf16 hi / lo
+    pair.  Returns (pointers, the tensors they point into)."""
     n, m, d = q.shape
     L = _lib.lib()
     if self.dtype == torch.bfloat16:
@@ -598,11 +565,89 @@ class VideoIndex:
     qf = _fold(q, qw)
     return (ops._p(qf), ops._p(qw), ops._p(self.folded), ops._p(self.weights)), qf
 
-  def _batches(self, nq, t_max):
-    """Row ranges of the rank passes: a multiple of 64 rows (the query block) within _BATCH_BYTES, as `rank_counts`."""
-    per_row = self.num_experts * self.dim * 4 + 4 * t_max * (1 + 2 * -(-self.num_items // 4096))
+  def _row_batches(self, nq, extra):
+    """Row ranges of a scan: a multiple of 64 rows (the query block) whose folded rows (4 bytes per element, fp32 or the
+    bf16 hi + lo pair) and `extra` bytes of workspace per row stay within _BATCH_BYTES."""
+    per_row = self.num_experts * self.dim * 4 + extra
     batch = max(64, (_BATCH_BYTES // per_row) // 64 * 64)
     return [(r0, min(nq, r0 + batch)) for r0 in range(0, nq, batch)]
+
+  def _batches(self, nq, t_max):
+    """Row ranges of the rank and range passes: a row's thresholds and chunk counters at full-size chunks."""
+    return self._row_batches(nq, 4 * t_max * (1 + 2 * -(-self.num_items // 4096)))
+
+  def _hub_norm(self, b, bw, beta, hubs):
+    return HubNorm(self._col_lse(b, bw, beta), beta, b.shape[0], hubs)
+
+  def _col_lse(self, b, bw, beta):
+    """`hub_norm` behind its checks: b (NB, M, d) / bw (NB, M) fp32 on the index device -> lse fp32 [num_items].  The bank
+    goes through in batches of whole 64-row blocks; the running (M, S) pair per item carries from one to the next."""
+    nb, nv, m, d = b.shape[0], self.num_items, self.num_experts, self.dim
+    fn, name = self._entry('col_lse')
+    with torch.cuda.device(self.device):
+      lse = torch.empty(nv, device=self.device, dtype=torch.float32)
+      state = torch.empty(2, nv, device=self.device, dtype=torch.float32)
+      # a row's share of the block's (m, p) pairs: 8 bytes per item / 64 rows
+      batches = self._row_batches(nb, -(-nv // 8))
+      ws = torch.empty(_lib.lib().mmt_col_lse_workspace_floats(batches[0][1], nv), device=self.device, dtype=torch.float32)
+      for r0, r1 in batches:
+        operands, _keep = self._operands(b[r0:r1], bw[r0:r1])
+        check(fn(*operands, r1 - r0, nv, m, d, beta, ops._p(ws), ops._p(state), int(r0 == 0),
+                 ops._p(lse if r1 == nb else None), ops._stream()), name)
+    return lse
+
+  def _search(self, q, qw, k, subset, ex, norm=None):
+    """`search` behind its argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the index device, ex None or int64 [NQ, E]
+    there, norm None or a HubNorm of this index (every query normalised).  Nothing here waits for the device."""
+    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    masked = subset is not None or ex is not None
+    if masked:
+      k = min(k, nv if subset is None else subset.count)  # lists no longer than the candidates: the outputs stay dense
+    kout = min(k, nv)
+    if ex is None:
+      scores = torch.empty(nq, kout, device=self.device, dtype=torch.float32)
+      indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
+    else:  # the merge writes only the slots that have a candidate
+      scores = torch.full((nq, kout), float('-inf'), device=self.device, dtype=torch.float32)
+      indices = torch.full((nq, kout), -1, device=self.device, dtype=torch.int64)
+    if nq == 0:
+      return scores, indices
+    fn, name = self._entry('topk', '_norm' if norm is not None else '_ex' if masked else '')
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._row_batches(nq, 8 * k * -(-nv // 4096)):  # a row's chunk lists at full-size chunks
+        n = r1 - r0
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        extra = ()  # of the _ex and _norm entry points: subset words, exclusions of the batch, E; then beta, lse
+        if masked or norm is not None:
+          extra = (ops._p(None if subset is None else subset.words), ops._p(None if ex is None else ex[r0:r1]),
+                   0 if ex is None else ex.shape[1])
+        if norm is not None:
+          extra += (norm.beta, ops._p(norm.lse))
+        ws = torch.empty(_lib.lib().mmt_topk_workspace_keys(n, nv, k), device=self.device, dtype=torch.int64)
+        check(fn(*operands, n, nv, m, d, k, *extra, ops._p(ws), ops._p(scores[r0:r1]), ops._p(indices[r0:r1]),
+                 ops._stream()), name)
+    return scores, indices
+
+  def _rank_counts(self, q, qw, tg, subset, norm=None):
+    """`rank_counts` behind its checks: tg int64 [NQ >= 1, T] on the index device -> (greater, equal) int32 [NQ, T].  Plain:
+    the threshold and the count pass in one call per batch (mmt_search_rank); with a norm: one after the other."""
+    if norm is not None:
+      return self._threshold_counts(q, qw, self._target_scores(q, qw, tg, norm), subset, norm)
+    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    greater = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
+    equal = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
+    fn, name = self._entry('rank', '' if subset is None else '_ex')
+    words = () if subset is None else (ops._p(subset.words),)
+    t_max = min(MAX_T, tg.shape[1])
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._batches(nq, t_max):
+        n = r1 - r0
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        ws = torch.empty(_lib.lib().mmt_rank_workspace_ints(n, nv, t_max), device=self.device, dtype=torch.int32)
+        for tgs, (gs, es) in _column_groups(tg, (greater, equal), r0, r1):
+          check(fn(*operands, n, nv, m, d, ops._p(tgs), tgs.shape[1], *words, ops._p(ws), ops._p(gs), ops._p(es),
+                   ops._stream()), name)
+    return greater, equal
 
   def target_scores(self, embds, weights, targets, norm=None, dynamic=None):
     """Queries as for `search`; targets as for `rank_counts` -> float32 of targets' shape on the device:
@@ -612,22 +657,13 @@ class VideoIndex:
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
-    if norm is not None:
-      self._norm(norm, 'ranks')
-    dynamic = _check_dynamic(dynamic, norm, 'ranks')
-    q, qw = self._queries(embds, weights)
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, None, norm, dynamic)
     if targets.shape[0] != q.shape[0]:
       raise ValueError('ranks: %d queries but targets %s' % (q.shape[0], tuple(targets.shape)))
     if q.shape[0]:
-      lo, hi = (int(v) for v in torch.aminmax(targets))
-      if lo < -1 or hi >= self.num_items:
-        raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
-    if norm is None:
-      return self._target_scores(q, qw, targets)
-    normed = self._target_scores(q, qw, targets, norm)
-    if not dynamic or q.shape[0] == 0:
-      return normed
-    return _pick(self._use_norm(q, qw, None, None, norm), normed, self._target_scores(q, qw, targets))
+      self._target_range(targets)
+    out = (self._target_scores(q, qw, targets, norm),)
+    return self._dynamic(dynamic, q, qw, None, None, norm, out, lambda: (self._target_scores(q, qw, targets),))[0]
 
   def _target_scores(self, q, qw, targets, norm=None):
     """`target_scores` behind its checks; a target outside 0 .. num_items - 1 gives NaN; norm None or a HubNorm of this
@@ -637,26 +673,13 @@ class VideoIndex:
     thr = torch.empty(tg.shape, device=self.device, dtype=torch.float32)
     if nq == 0:
       return thr.reshape(targets.shape)
-    L = _lib.lib()
-    fn, name = ((L.mmt_search_thresholds_bf16, 'mmt_search_thresholds_bf16') if self.dtype == torch.bfloat16 else
-                (L.mmt_search_thresholds, 'mmt_search_thresholds'))
-    extra = ()
-    if norm is not None:
-      fn, name = ((L.mmt_search_thresholds_bf16_norm, 'mmt_search_thresholds_bf16_norm') if self.dtype == torch.bfloat16
-                  else (L.mmt_search_thresholds_norm, 'mmt_search_thresholds_norm'))
-      extra = (norm.beta, ops._p(norm.lse))
-    t_all = tg.shape[1]
+    fn, name = self._entry('thresholds', '' if norm is None else '_norm')
+    extra = () if norm is None else (norm.beta, ops._p(norm.lse))
     with torch.cuda.device(self.device):
-      for r0, r1 in self._batches(nq, min(MAX_T, t_all)):
+      for r0, r1 in self._batches(nq, min(MAX_T, tg.shape[1])):
         operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        for t0 in range(0, t_all, MAX_T):
-          t1 = min(t_all, t0 + MAX_T)
-          whole = t1 - t0 == t_all  # a column slice of a wider list is not contiguous: copy in and out
-          tgs = tg[r0:r1] if whole else tg[r0:r1, t0:t1].contiguous()
-          out = thr[r0:r1] if whole else torch.empty(r1 - r0, t1 - t0, device=self.device, dtype=torch.float32)
-          check(fn(*operands, r1 - r0, nv, m, d, ops._p(tgs), t1 - t0, *extra, ops._p(out), ops._stream()), name)
-          if not whole:
-            thr[r0:r1, t0:t1] = out
+        for tgs, (out,) in _column_groups(tg, (thr,), r0, r1):
+          check(fn(*operands, r1 - r0, nv, m, d, ops._p(tgs), tgs.shape[1], *extra, ops._p(out), ops._stream()), name)
     return thr.reshape(targets.shape)
 
   def threshold_counts(self, embds, weights, thresholds, subset=None, norm=None, dynamic=None):
@@ -674,21 +697,11 @@ class VideoIndex:
       raise ValueError('ranks: thresholds must be on the index device %s, got %s' % (self.device, thresholds.device))
     if thresholds.dim() not in (1, 2) or thresholds.dim() == 2 and thresholds.shape[1] < 1:
       raise ValueError('ranks: thresholds [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(thresholds.shape),))
-    if subset is not None:
-      self._subset(subset, 'ranks')
-    if norm is not None:
-      self._norm(norm, 'ranks')
-    dynamic = _check_dynamic(dynamic, norm, 'ranks')
-    q, qw = self._queries(embds, weights)
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic)
     if thresholds.shape[0] != q.shape[0]:
       raise ValueError('ranks: %d queries but thresholds %s' % (q.shape[0], tuple(thresholds.shape)))
-    if norm is None:
-      return self._threshold_counts(q, qw, thresholds, subset)
-    normed = self._threshold_counts(q, qw, thresholds, subset, norm)
-    if not dynamic or q.shape[0] == 0:
-      return normed
-    use = self._use_norm(q, qw, subset, None, norm)
-    return tuple(_pick(use, a, b) for a, b in zip(normed, self._threshold_counts(q, qw, thresholds, subset)))
+    out = self._threshold_counts(q, qw, thresholds, subset, norm)
+    return self._dynamic(dynamic, q, qw, subset, None, norm, out, lambda: self._threshold_counts(q, qw, thresholds, subset))
 
   def _threshold_counts(self, q, qw, thresholds, subset, norm=None):
     """`threshold_counts` behind its checks; norm None or a HubNorm of this index (every query normalised).  Nothing here
@@ -699,33 +712,18 @@ class VideoIndex:
     equal = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
     if nq == 0:
       return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
-    L = _lib.lib()
-    fn, name = ((L.mmt_search_count_bf16, 'mmt_search_count_bf16') if self.dtype == torch.bfloat16 else
-                (L.mmt_search_count, 'mmt_search_count'))
-    extra = ()
-    if norm is not None:
-      fn, name = ((L.mmt_search_count_bf16_norm, 'mmt_search_count_bf16_norm') if self.dtype == torch.bfloat16 else
-                  (L.mmt_search_count_norm, 'mmt_search_count_norm'))
-      extra = (norm.beta, ops._p(norm.lse))
+    fn, name = self._entry('count', '' if norm is None else '_norm')
+    extra = () if norm is None else (norm.beta, ops._p(norm.lse))
     words = None if subset is None else subset.words
-    t_all = thr.shape[1]
-    t_max = min(MAX_T, t_all)
+    t_max = min(MAX_T, thr.shape[1])
     with torch.cuda.device(self.device):
       for r0, r1 in self._batches(nq, t_max):
         n = r1 - r0
         operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        ws = torch.empty(L.mmt_count_workspace_ints(n, nv, t_max), device=self.device, dtype=torch.int32)
-        for t0 in range(0, t_all, MAX_T):
-          t1 = min(t_all, t0 + MAX_T)
-          whole = t1 - t0 == t_all
-          ts = thr[r0:r1] if whole else thr[r0:r1, t0:t1].contiguous()
-          gs = greater[r0:r1] if whole else torch.empty(n, t1 - t0, device=self.device, dtype=torch.int32)
-          es = equal[r0:r1] if whole else torch.empty_like(gs)
-          check(fn(*operands, n, nv, m, d, ops._p(ts), t1 - t0, ops._p(words), *extra, ops._p(ws), ops._p(gs), ops._p(es),
-                   ops._stream()), name)
-          if not whole:
-            greater[r0:r1, t0:t1] = gs
-            equal[r0:r1, t0:t1] = es
+        ws = torch.empty(_lib.lib().mmt_count_workspace_ints(n, nv, t_max), device=self.device, dtype=torch.int32)
+        for ts, (gs, es) in _column_groups(thr, (greater, equal), r0, r1):
+          check(fn(*operands, n, nv, m, d, ops._p(ts), ts.shape[1], ops._p(words), *extra, ops._p(ws), ops._p(gs),
+                   ops._p(es), ops._stream()), name)
     return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
 
   def range_search(self, embds, weights, threshold, subset=None, order='index', max_hits=_MAX_HITS):
@@ -762,49 +760,18 @@ class VideoIndex:
         self._range_fill(q, qw, thr, subset, counted[1], offsets, indices, scores)
       return _range_result(offsets, indices, scores, order)
 
-  def _range_args(self, embds, weights, threshold, subset, order, max_hits):
-    """The checks of `range_search` (read through the bookkeeping both index classes share) -> q, qw, thr float32 [NQ]."""
-    if order not in ('index', 'score'):
-      raise ValueError("range_search: order must be 'index' or 'score', got %r" % (order,))
-    if isinstance(max_hits, bool) or not isinstance(max_hits, int) or max_hits < 0:
-      raise ValueError('range_search: max_hits must be an int >= 0, got %r' % (max_hits,))
-    if self.num_items == 0:
-      raise ValueError('range_search: the index holds no items')
-    if torch.is_tensor(threshold):
-      if threshold.dtype != torch.float32:
-        raise ValueError('range_search: threshold must be a float or a float32 tensor, got %s' % threshold.dtype)
-      if threshold.device != self.device:
-        raise ValueError('range_search: threshold must be on the index device %s, got %s' % (self.device, threshold.device))
-      if threshold.dim() != 1:
-        raise ValueError('range_search: threshold [NQ] expected, got %s' % (tuple(threshold.shape),))
-    elif isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
-      raise ValueError('range_search: threshold must be a float or a float32 tensor, got %s' % type(threshold).__name__)
-    if subset is not None:
-      self._subset(subset, 'range_search')
-    q, qw = self._queries(embds, weights)
-    nq = q.shape[0]
-    if torch.is_tensor(threshold):
-      if threshold.shape[0] != nq:
-        raise ValueError('range_search: %d queries but threshold %s' % (nq, tuple(threshold.shape)))
-      thr = threshold.contiguous()
-    else:
-      thr = torch.full((nq,), float(threshold), device=self.device, dtype=torch.float32)
-    return q, qw, thr
-
   def _range_count(self, q, qw, thr, subset):
     """The count pass of `range_search` behind its checks, batch by batch -> (hits per query int64 [NQ], the batches'
     workspaces as the fill pass wants them).  Nothing here waits for the device."""
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    L = _lib.lib()
-    fn, name = ((L.mmt_search_range_count_bf16, 'mmt_search_range_count_bf16') if self.dtype == torch.bfloat16 else
-                (L.mmt_search_range_count, 'mmt_search_range_count'))
+    fn, name = self._entry('range_count')
     words = None if subset is None else subset.words
     counts = torch.empty(nq, device=self.device, dtype=torch.int64)
     kept = []
     for r0, r1 in self._batches(nq, 1):
       n = r1 - r0
       operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-      ws = torch.empty(L.mmt_range_workspace_ints(n, nv), device=self.device, dtype=torch.int32)
+      ws = torch.empty(_lib.lib().mmt_range_workspace_ints(n, nv), device=self.device, dtype=torch.int32)
       check(fn(*operands, n, nv, m, d, ops._p(thr[r0:r1]), ops._p(words), ops._p(ws), ops._p(counts[r0:r1]), ops._stream()),
             name)
       kept.append(ws)
@@ -814,26 +781,12 @@ class VideoIndex:
     """The fill pass of `range_search`: `kept` from `_range_count` of the same arguments, offsets int64 [NQ + 1] into
     indices / scores."""
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    L = _lib.lib()
-    fn, name = ((L.mmt_search_range_fill_bf16, 'mmt_search_range_fill_bf16') if self.dtype == torch.bfloat16 else
-                (L.mmt_search_range_fill, 'mmt_search_range_fill'))
+    fn, name = self._entry('range_fill')
     words = None if subset is None else subset.words
     for (r0, r1), ws in zip(self._batches(nq, 1), kept):
       operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
       check(fn(*operands, r1 - r0, nv, m, d, ops._p(thr[r0:r1]), ops._p(words), ops._p(ws), ops._p(offsets[r0:r1 + 1]),
                ops._p(indices), ops._p(scores), ops._stream()), name)
-
-  def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
-    """The reference's tie-averaged 0-based rank (model/metric.py:90-121) of item targets[q, t] among the stored items for
-    query q: greater + (equal - 1) / 2 from `rank_counts`, +inf where the target is -1.  float64 on the device, of
-    targets' shape (float32 would not hold counts above 2^24).  subset: the rank among its items, +inf for a target that
-    is not one of them.  norm, dynamic: as `rank_counts` -- the rank under the querybank-normalised score."""
-    greater, equal = self.rank_counts(embds, weights, targets, subset=subset, norm=norm, dynamic=dynamic)
-    ranks = greater.double() + (equal.double() - 1) / 2
-    none = targets < 0
-    if subset is not None:
-      none = none | ~subset.mask[targets.clamp(min=0)]
-    return torch.where(none, torch.full_like(ranks, float('inf')), ranks)
 
 
 MAX_SHARDS = 32  # lists per query of the merge kernel
@@ -905,7 +858,7 @@ def _devices(devices):
   return out
 
 
-class ShardedVideoIndex:
+class ShardedVideoIndex(_Index):
   """One gallery held as S = len(devices) VideoIndex shards, one per entry of `devices` (the same device may appear more
   than once), with the surface of VideoIndex.  Item numbers are global insertion order 0 .. num_items - 1; every result is
   bit-identical to that of one VideoIndex over the same items in the same order: score(q, g) has the same bits wherever
@@ -918,7 +871,7 @@ class ShardedVideoIndex:
   def __init__(self, embds, weights, devices, dtype=torch.float32):
     _check_dtype(dtype)
     devices = _devices(devices)
-    g, gw = VideoIndex._items(embds, weights, 'ShardedVideoIndex')
+    g, gw = self._items(embds, weights, 'ShardedVideoIndex')
     n, s = g.shape[0], len(devices)
     sizes = [n // s + (i < n % s) for i in range(s)]   # contiguous near-equal ranges
     self._allocate(sizes, n, g.shape[1], g.shape[2], devices, dtype)
@@ -963,7 +916,7 @@ class ShardedVideoIndex:
     """Appends items (n, M, d) / (n, M) given on the primary device; they get the next n global numbers.  Placement is
     `place`: the shard with the fewest items first, spilling when it is full.  Returns (first, last).  Raises ValueError,
     leaving the index as it was, if they do not fit."""
-    g, gw = VideoIndex._items(embds, weights, 'ShardedVideoIndex.add')
+    g, gw = self._items(embds, weights, 'ShardedVideoIndex.add')
     n, m, d = g.shape
     if (m, d) != (self.num_experts, self.dim):
       raise ValueError('ShardedVideoIndex.add: items (n, %d, %d) expected, got %s' % (self.num_experts, self.dim, tuple(g.shape)))
@@ -992,13 +945,9 @@ class ShardedVideoIndex:
                                                dtype=torch.int64).to(self.device)
     return self._table_cache[shards]
 
-  def _live(self):
-    return [(s, sh) for s, sh in enumerate(self.shards) if sh.num_items]
-
-  def _queries(self, embds, weights):
-    """The queries checked and flattened once, on the primary (VideoIndex._queries reads only the bookkeeping both classes
-    share: num_experts, dim, device)."""
-    return VideoIndex._queries(self, embds, weights)
+  def _live(self, subset=None):
+    """(number, shard) of the shards that hold items -- with a subset: allowed items."""
+    return [(s, sh) for s, sh in enumerate(self.shards) if sh.num_items and (subset is None or subset.parts[s] is not None)]
 
   def _local(self, items, s):
     """Global item numbers (-1 = none) on the primary -> shard s's numbers, -1 for none and for items held elsewhere."""
@@ -1008,7 +957,7 @@ class ShardedVideoIndex:
   def subset(self, items):
     """items: bool [num_items] or int64 item numbers on the primary device, as VideoIndex.subset -> ShardedSubset: the set
     cut into one IndexSubset per shard, in the shard's own numbers.  After a further `add` it is refused."""
-    mask, total = VideoIndex._subset_mask(self, items)   # reads only the bookkeeping both classes share
+    mask, total = self._subset_mask(items)
     parts = []
     for sh in self.shards:
       part = None
@@ -1038,23 +987,10 @@ class ShardedVideoIndex:
     if norm.device != self.device or len(norm.parts) != len(self.shards):
       raise ValueError('%s: the norm belongs to another index' % who)
 
-  def hub_norm(self, bank_embds, bank_weights, beta, dynamic=False):
-    """VideoIndex.hub_norm over all shards -> ShardedHubNorm: the bank (given on the primary) is copied to every shard,
-    which computes the lse of its own items; lse[g] does not depend on where item g is stored, so `lse` -- and every
-    result under norm= -- is bit-identical to that of one VideoIndex.  dynamic=True: `hubs` from one sharded search(k=1)
-    of the bank."""
-    _check_beta(beta)
-    if not isinstance(dynamic, bool):
-      raise ValueError('hub_norm: dynamic must be False or True, got %r' % (dynamic,))
-    if self.num_items == 0:
-      raise ValueError('hub_norm: the index holds no items')
-    b, bw = self._queries(bank_embds, bank_weights)
-    if b.shape[0] < 1:
-      raise ValueError('hub_norm: the bank holds no queries')
-    hubs = None
-    if dynamic:
-      top1 = self._search(b, bw, 1, None, None, None)[1][:, 0]
-      hubs = torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
+  def _hub_norm(self, b, bw, beta, hubs):
+    """`hub_norm` behind its checks -> ShardedHubNorm: the bank (given on the primary) is copied to every shard, which
+    computes the lse of its own items; lse[g] does not depend on where item g is stored, so `lse` -- and every result under
+    norm= -- is bit-identical to that of one VideoIndex."""
     lse = torch.empty(self.num_items, device=self.device, dtype=torch.float32)
     parts = []
     for sh in self.shards:
@@ -1068,37 +1004,7 @@ class ShardedVideoIndex:
       parts.append(part)
     return ShardedHubNorm(parts, lse, beta, b.shape[0], hubs)
 
-  def _use_norm(self, q, qw, subset, ex, norm):
-    """VideoIndex._use_norm on the global item numbers."""
-    top1 = self._search(q, qw, 1, subset, ex, None)[1][:, 0]
-    return (top1 >= 0) & norm.hubs[top1.clamp(min=0)]
-
-  def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None):
-    """VideoIndex.search over all shards: (scores [NQ, k'] float32, indices [NQ, k'] int64 global item numbers) on the
-    primary, k' = min(k, num_items) or min(k, subset.count).  Every shard searches its own items for its best min(k', its
-    candidates); the lists are copied to the primary and merged there in one launch.  norm (ShardedVideoIndex.hub_norm),
-    dynamic: as VideoIndex.search; every shard ranks by score' with its own part of the norm."""
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
-      raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
-    if self.num_items == 0:
-      raise ValueError('search: the index holds no items')
-    if subset is not None:
-      self._subset(subset, 'search')
-    if exclude is not None:
-      VideoIndex._exclude(self, exclude)
-    if norm is not None:
-      self._norm(norm, 'search')
-    dynamic = _check_dynamic(dynamic, norm, 'search')
-    q, qw = self._queries(embds, weights)
-    ex = _exclusions(exclude, q.shape[0], self.num_items)
-    out = self._search(q, qw, k, subset, ex, norm)
-    if not dynamic or q.shape[0] == 0:
-      return out
-    use = self._use_norm(q, qw, subset, ex, norm)
-    plain = self._search(q, qw, k, subset, ex, None)
-    return _pick(use, out[0], plain[0]), _pick(use, out[1], plain[1])
-
-  def _search(self, q, qw, k, subset, ex, norm):
+  def _search(self, q, qw, k, subset, ex, norm=None):
     """`search` behind its checks: q, qw on the primary, ex None or int64 [NQ, E] global numbers there, norm None or a
     ShardedHubNorm of this index (every query normalised)."""
     nq = q.shape[0]
@@ -1107,7 +1013,7 @@ class ShardedVideoIndex:
     indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
     if nq == 0:
       return scores, indices
-    live = [(s, sh) for s, sh in self._live() if subset is None or subset.parts[s] is not None]
+    live = self._live(subset)
     kin = min(kout, max(sh.num_items if subset is None else subset.parts[s].count for s, sh in live))
     with torch.cuda.device(self.device):  # the staged lists; the slots a shorter list leaves are empty
       st_scores = torch.full((len(live), nq, kin), float('-inf'), device=self.device, dtype=torch.float32)
@@ -1126,36 +1032,7 @@ class ShardedVideoIndex:
                                               ops._p(scores), ops._p(indices), ops._stream()), 'mmt_search_merge_lists')
     return scores, indices
 
-  def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
-    """VideoIndex.rank_counts over all shards: each shard scores the targets it holds (target_scores), the primary picks
-    the owner's value per (query, target), each shard counts its items against those thresholds (threshold_counts) and
-    the int32 counts are summed on the primary.  norm (ShardedVideoIndex.hub_norm), dynamic: as VideoIndex.rank_counts."""
-    if self.num_items == 0:
-      raise ValueError('ranks: the index holds no items')
-    VideoIndex._targets(self, targets)
-    if subset is not None:
-      self._subset(subset, 'ranks')
-    if norm is not None:
-      self._norm(norm, 'ranks')
-    dynamic = _check_dynamic(dynamic, norm, 'ranks')
-    q, qw = self._queries(embds, weights)
-    nq = q.shape[0]
-    if targets.shape[0] != nq:
-      raise ValueError('ranks: %d queries but targets %s' % (nq, tuple(targets.shape)))
-    shape = targets.shape
-    if nq == 0:
-      return tuple(torch.empty(shape, device=self.device, dtype=torch.int32) for _ in range(2))
-    tg = targets.reshape(nq, -1).contiguous()
-    lo, hi = (int(v) for v in torch.aminmax(tg))
-    if lo < -1 or hi >= self.num_items:
-      raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
-    out = self._rank_counts(q, qw, tg, subset, norm)
-    if dynamic:
-      use = self._use_norm(q, qw, subset, None, norm)
-      out = tuple(_pick(use, a, b) for a, b in zip(out, self._rank_counts(q, qw, tg, subset, None)))
-    return out[0].reshape(shape), out[1].reshape(shape)
-
-  def _rank_counts(self, q, qw, tg, subset, norm):
+  def _rank_counts(self, q, qw, tg, subset, norm=None):
     """`rank_counts` behind its checks: tg int64 [NQ, T] global numbers on the primary -> (greater, equal) int32 [NQ, T]."""
     live = self._live()
     queries = {}
@@ -1185,9 +1062,9 @@ class ShardedVideoIndex:
     allocates its outputs; every shard then fills a CSR of its own, whose local item numbers go through the shard's table
     to global ones; the primary concatenates the shards' hits and orders them by (query, global item) with two stable
     torch sorts.  order='score' as VideoIndex.range_search.  Exclusions are applied to the CSR by the caller."""
-    q, qw, thr = VideoIndex._range_args(self, embds, weights, threshold, subset, order, max_hits)
+    q, qw, thr = self._range_args(embds, weights, threshold, subset, order, max_hits)
     nq = q.shape[0]
-    live = [(s, sh) for s, sh in self._live() if subset is None or subset.parts[s] is not None]
+    live = self._live(subset)
     args, counted = {}, {}
     for s, sh in live:
       args[s] = (q.to(sh.device), qw.to(sh.device), thr.to(sh.device), None if subset is None else subset.parts[s])
@@ -1222,13 +1099,3 @@ class ShardedVideoIndex:
       by_item = torch.argsort(items, stable=True)
       perm = by_item[torch.argsort(rows[by_item], stable=True)]
       return _range_result(offsets, items[perm], scores[perm], order)
-
-  def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
-    """VideoIndex.ranks: greater + (equal - 1) / 2 from `rank_counts`, float64 on the primary, +inf where the target is -1
-    or outside the subset.  norm, dynamic: as `rank_counts`."""
-    greater, equal = self.rank_counts(embds, weights, targets, subset=subset, norm=norm, dynamic=dynamic)
-    ranks = greater.double() + (equal.double() - 1) / 2
-    none = targets < 0
-    if subset is not None:
-      none = none | ~subset.mask[targets.clamp(min=0)]
-    return torch.where(none, torch.full_like(ranks, float('inf')), ranks)
