@@ -661,6 +661,37 @@ int mmt_search_range_fill(const float* qf, const float* qw, const float* gf, con
 int mmt_search_range_fill_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
                                const float* gw, int NQ, int NV, int M, int d, const float* thr, const uint32_t* subset,
                                const int32_t* ws, const int64_t* offsets, int64_t* indices, float* scores, void* stream);
+/* Grouped search (search_group.hip): the k best GROUPS of a gallery whose items carry a group id -- the clips of a video,
+ * the captions of a video -- each with its best item, without the N_query x N_gallery matrix.  groups int32 [NV], values
+ * >= 0, any labelling (ids need not be dense, members need not be adjacent).  Per query the representative of a group is
+ * its member with the largest key under mmt_search_topk's order (score descending, -0 tied with +0, equal scores by
+ * ascending item); groups rank by their representatives under the same order.
+ * mmt_search_topk_groups / mmt_search_topk_groups_bf16: query operands and gallery as mmt_search_topk / _bf16; subset
+ *   nullable, words as above: only allowed items are candidates, a group's representative is its best allowed member and
+ *   a group without one does not appear.  1 <= k <= 128 (the caller passes min(k, number of groups): k is the width of
+ *   the outputs and of the chunk lists).  Outputs [NQ][k]: scores fp32 (the bits mmt_search_topk gives the pair),
+ *   out_groups int64, out_items int64; slots past the last group hold (-inf, -1, -1).  The scan keeps the best k distinct
+ *   groups per query and chunk (a compaction drops the lesser duplicates of a group before it rank-sorts); one wave per
+ *   query then merges the chunk lists, de-duplicating again.  Workspace: mmt_topk_workspace_keys(NQ, NV, k).  No atomics,
+ *   one writer per slot.  Gates: MMT_ERR_ARG (a null pointer other than subset -- the group table included -- a size or
+ *   k out of range, d % 4 / d % 8), MMT_ERR_ALIGN (query or gallery rows or subset words off a 16-byte boundary), before
+ *   any launch.  Trusted, not checked: 0 <= groups[g].
+ * mmt_search_merge_group_lists: per query, S lists of kin (score, group, shard-local item) triples -- scores fp32, groups
+ *   int64, index int64 [S][NQ][kin], index -1 = empty slot, each list best-first with distinct groups and its empty slots
+ *   last -- and ids as mmt_search_merge_lists -> the best kout distinct groups over all lists as out_scores fp32 /
+ *   out_groups int64 / out_items int64 (global) [NQ][kout], equal scores by ascending GLOBAL item, then (-inf, -1, -1).
+ *   1 <= S <= 32, 1 <= kin, kout <= 128, else MMT_ERR_ARG.  Pointers and trust as mmt_search_merge_lists; a group id is
+ *   below 2^31. */
+int mmt_search_topk_groups(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                           int k, const int32_t* groups, const uint32_t* subset, uint64_t* ws, float* scores,
+                           int64_t* out_groups, int64_t* out_items, void* stream);
+int mmt_search_topk_groups_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                const float* gw, int NQ, int NV, int M, int d, int k, const int32_t* groups,
+                                const uint32_t* subset, uint64_t* ws, float* scores, int64_t* out_groups, int64_t* out_items,
+                                void* stream);
+int mmt_search_merge_group_lists(const float* scores, const int64_t* groups, const int64_t* index, const int64_t* const* ids,
+                                 int S, int NQ, int kin, int kout, float* out_scores, int64_t* out_groups, int64_t* out_items,
+                                 void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

@@ -89,6 +89,21 @@ ascending item (order='index') or in `search`'s order (order='score'); a score h
 scans with the hit counts summed in between (mmt_search_range_count, mmt_search_range_fill): every hit has a slot of its
 own before it is written, so there are no atomics and the result is bit-reproducible; the total is known -- and held
 against max_hits -- before anything of its size is allocated.  ShardedVideoIndex.range_search is bit-identical.
+
+    grp = index.grouping(group_ids)      # IndexGrouping, built once like a subset: int64 [num_items], any labelling
+    grp.ids, grp.num_groups, grp.num_items, grp.device
+    scores, groups, items = index.search_groups(q, qw, grp, k=10, subset=None)      # each [NQ, min(k, num_groups)]
+
+The fourth question: the k best VIDEOS of a gallery that holds clips (windows of a long video, segments, feature crops) or
+of a caption index with several captions per video, each video reported once, with its best item -- "grouping search" /
+"search groups" / field collapsing of the serving engines.  A group's representative is its member with the largest key
+under `search`'s order (score descending, -0 tied with +0, equal scores by ascending item); groups are ranked by their
+representatives; slot j holds the j-th best group, its representative's item number and that item's score, with the bits
+`search` gives the pair.  With a subset a representative is the group's best allowed member and a group without one does not
+appear: the slots left over hold (-inf, -1, -1).  It is not `search` plus a host-side de-duplication -- one video's clips
+would push other videos' best clips out of a list before anybody could remove them: the running top-k of the scan keeps the
+best k distinct groups, and the chunk and shard merges de-duplicate again (mmt_search_topk_groups,
+mmt_search_merge_group_lists).  ShardedVideoIndex.search_groups is bit-identical; a group may have members on several shards.
 """
 import math
 
@@ -173,6 +188,33 @@ class RangeResult:
     self.counts = offsets[1:] - offsets[:-1]
 
 
+MAX_GROUP_ID = 2 ** 31 - 2
+
+
+class IndexGrouping:
+  """The groups of a VideoIndex's items (VideoIndex.grouping): `ids` int32 [num_items] on the index device, the group of
+  every item; `num_groups` the number of distinct ids; `num_items` and `device` it was built for."""
+
+  def __init__(self, ids, num_groups):
+    self.ids, self.num_groups = ids, num_groups
+    self.num_items, self.device = ids.shape[0], ids.device
+
+
+class ShardedGrouping:
+  """The groups of a ShardedVideoIndex's items (ShardedVideoIndex.grouping): `parts[s]` is shard s's IndexGrouping in its own
+  item order on its own device (None for a shard without items), with the same, global, group ids; `ids` int32 [num_items]
+  in global item order on the primary device; `num_groups`, `num_items`, `device`."""
+
+  def __init__(self, parts, ids, num_groups):
+    self.parts, self.ids, self.num_groups = parts, ids, num_groups
+    self.num_items, self.device = ids.shape[0], ids.device
+
+
+def _count_groups(ids):
+  """The number of distinct values of a non-empty id tensor: one torch.unique, whose size is the one wait for the device."""
+  return int(torch.unique(ids).numel())
+
+
 def _csr_rows(offsets):
   """offsets int64 [NQ + 1] -> the row of every CSR position, int64 [offsets[-1]]."""
   counts = offsets[1:] - offsets[:-1]
@@ -231,9 +273,9 @@ def _column_groups(src, outs, r0, r1):
 
 class _Index:
   """What VideoIndex and ShardedVideoIndex share: the checks of every public call, the calls that are the same on both
-  (`search`, `rank_counts`, `ranks`, `hub_norm` up to the scan) and QB-Norm's dynamic rule.  It reads the bookkeeping both
+  (`search`, `rank_counts`, `ranks`, `hub_norm` up to the scan, `search_groups`) and QB-Norm's dynamic rule.  It reads the bookkeeping both
   have -- num_experts, dim, num_items, device (the primary of a sharded index) -- and leaves to the class what happens
-  behind the checks: _search, _rank_counts, _hub_norm and the type checks _subset / _norm."""
+  behind the checks: _search, _rank_counts, _hub_norm, _search_groups and the type checks _subset / _norm / _grouping."""
 
   @staticmethod
   def _items(embds, weights, who):
@@ -426,6 +468,47 @@ class _Index:
       none = none | ~subset.mask[targets.clamp(min=0)]
     return torch.where(none, torch.full_like(ranks, float('inf')), ranks)
 
+  def _group_ids(self, group_ids):
+    """The checks of `grouping` -> (the ids as int32 [num_items] of their own, the number of distinct ids)."""
+    if self.num_items == 0:
+      raise ValueError('grouping: the index holds no items')
+    if not torch.is_tensor(group_ids) or group_ids.dtype != torch.int64:
+      raise ValueError('grouping: group_ids must be an int64 tensor, got %s' % (
+          group_ids.dtype if torch.is_tensor(group_ids) else type(group_ids).__name__))
+    if group_ids.device != self.device:
+      raise ValueError('grouping: group_ids must be on the index device %s, got %s' % (self.device, group_ids.device))
+    nv = self.num_items
+    if tuple(group_ids.shape) != (nv,):
+      raise ValueError('grouping: group_ids of shape (%d,) expected, got %s' % (nv, tuple(group_ids.shape)))
+    lo, hi = (int(v) for v in torch.aminmax(group_ids))
+    if lo < 0 or hi > MAX_GROUP_ID:
+      raise ValueError('grouping: group_ids must lie in 0 .. %d, got %d .. %d' % (MAX_GROUP_ID, lo, hi))
+    return group_ids.to(torch.int32).contiguous(), _count_groups(group_ids)
+
+  def search_groups(self, embds, weights, grouping, k=10, subset=None):
+    """Queries as for `search`; grouping from this index's `grouping` -> (scores [NQ, k'] float32, groups [NQ, k'] int64,
+    items [NQ, k'] int64) on the device, k' = min(k, grouping.num_groups): per query the k' best GROUPS, best first.  A
+    group's representative is its member with the largest key under `search`'s order (score descending, -0 tied with +0,
+    equal scores by ascending item number) and groups are ranked by their representatives under the same order; slot j
+    holds the j-th best group's score, id and representative item, the score with the very bits `search` and
+    `target_scores` give the pair.  subset (from this index's `subset`): only its items are candidates, a representative
+    is the group's best allowed member, a group with no allowed member does not appear and the slots left without a group
+    hold (-inf, -1, -1).  Per-query exclusions and the querybank normalisation are not part of this call.  The scan keeps
+    the best k' distinct groups per query and gallery chunk and the merge de-duplicates across chunks
+    (mmt_search_topk_groups); nothing here waits for the device.  ShardedVideoIndex: every shard searches its own items
+    with its part of the grouping (ids are global: a group may have members on several shards), the lists are copied to
+    the primary and merged there, de-duplicating across shards under the global tie rule
+    (mmt_search_merge_group_lists)."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+      raise ValueError('search_groups: k must be an int in 1..%d, got %r' % (MAX_K, k))
+    if self.num_items == 0:
+      raise ValueError('search_groups: the index holds no items')
+    self._grouping(grouping, 'search_groups')
+    if subset is not None:
+      self._subset(subset, 'search_groups')
+    q, qw = self._queries(embds, weights)
+    return self._search_groups(q, qw, min(k, grouping.num_groups), grouping, subset)
+
   def _range_args(self, embds, weights, threshold, subset, order, max_hits):
     """The checks of `range_search` -> q, qw, thr float32 [NQ]."""
     if order not in ('index', 'score'):
@@ -546,9 +629,45 @@ class VideoIndex(_Index):
     if norm.device != self.device:
       raise ValueError('%s: the norm is on %s, the index on %s' % (who, norm.device, self.device))
 
+  def grouping(self, group_ids):
+    """group_ids: int64 [num_items] on the index device, the group of every item, values 0 .. 2^31 - 2 in any labelling
+    (ids need not be dense, members need not be stored next to each other) -> IndexGrouping for `search_groups`.  Stored
+    as int32 here, once; the range is checked and the distinct ids are counted (one small reduction, one torch.unique and
+    a host sync).  It describes the num_items of this moment: after a further `add` it is refused."""
+    return IndexGrouping(*self._group_ids(group_ids))
+
+  def _grouping(self, grouping, who):
+    if not isinstance(grouping, IndexGrouping):
+      raise ValueError('%s: grouping must come from VideoIndex.grouping, got %s' % (who, type(grouping).__name__))
+    if grouping.num_items != self.num_items:
+      raise ValueError('%s: the grouping was built for %d items, the index holds %d' % (
+          who, grouping.num_items, self.num_items))
+    if grouping.device != self.device:
+      raise ValueError('%s: the grouping is on %s, the index on %s' % (who, grouping.device, self.device))
+
+  def _search_groups(self, q, qw, k, grouping, subset):
+    """`search_groups` behind its argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the index device, 1 <= k <=
+    grouping.num_groups: the width of the outputs.  Nothing here waits for the device."""
+    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    scores = torch.empty(nq, k, device=self.device, dtype=torch.float32)
+    groups = torch.empty(nq, k, device=self.device, dtype=torch.int64)
+    items = torch.empty(nq, k, device=self.device, dtype=torch.int64)
+    if nq == 0:
+      return scores, groups, items
+    fn, name = self._entry('topk_groups')
+    words = None if subset is None else subset.words
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._row_batches(nq, 8 * k * -(-nv // 4096)):  # a row's chunk lists at full-size chunks
+        n = r1 - r0
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        ws = torch.empty(_lib.lib().mmt_topk_workspace_keys(n, nv, k), device=self.device, dtype=torch.int64)
+        check(fn(*operands, n, nv, m, d, k, ops._p(grouping.ids), ops._p(words), ops._p(ws), ops._p(scores[r0:r1]),
+                 ops._p(groups[r0:r1]), ops._p(items[r0:r1]), ops._stream()), name)
+    return scores, groups, items
+
   def _entry(self, op, variant=''):
-    """The C entry point of a scan over this index's storage: op 'topk', 'rank', 'thresholds', 'count', 'range_count',
-    'range_fill' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions) or '_norm' -> (the function, its name)."""
+    """The C entry point of a scan over this index's storage: op 'topk', 'topk_groups', 'rank', 'thresholds', 'count',
+    'range_count', 'range_fill' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions) or '_norm' -> (the function, its name)."""
     name = 'mmt_search_%s%s%s' % (op, '_bf16' if self.dtype == torch.bfloat16 else '', variant)
     return getattr(_lib.lib(), name), name
 
@@ -1031,6 +1150,62 @@ class ShardedVideoIndex(_Index):
       check(_lib.lib().mmt_search_merge_lists(ops._p(st_scores), ops._p(st_index), ops._p(tables), len(live), nq, kin, kout,
                                               ops._p(scores), ops._p(indices), ops._stream()), 'mmt_search_merge_lists')
     return scores, indices
+
+  def grouping(self, group_ids):
+    """group_ids: int64 [num_items] on the primary device, as VideoIndex.grouping -> ShardedGrouping: the ids cut into one
+    IndexGrouping per shard, in the shard's item order, with the ids as given -- they are global, so a group may have
+    members on several shards.  After a further `add` it is refused."""
+    ids, num_groups = self._group_ids(group_ids)
+    parts = []
+    for sh in self.shards:
+      part = None
+      if sh.num_items:
+        local = ids[sh.ids[:sh.num_items]]  # gathered on the primary, where the table is
+        with torch.cuda.device(sh.device):
+          local = local.to(sh.device)
+          part = IndexGrouping(local, _count_groups(local))
+      parts.append(part)
+    return ShardedGrouping(parts, ids, num_groups)
+
+  def _grouping(self, grouping, who):
+    if not isinstance(grouping, ShardedGrouping):
+      raise ValueError('%s: grouping must come from ShardedVideoIndex.grouping, got %s' % (who, type(grouping).__name__))
+    if grouping.num_items != self.num_items:
+      raise ValueError('%s: the grouping was built for %d items, the index holds %d' % (
+          who, grouping.num_items, self.num_items))
+    if grouping.device != self.device or len(grouping.parts) != len(self.shards):
+      raise ValueError('%s: the grouping belongs to another index' % who)
+
+  def _search_groups(self, q, qw, k, grouping, subset):
+    """`search_groups` behind its checks: q, qw on the primary, 1 <= k <= grouping.num_groups.  Every live shard returns its
+    best min(k, its groups) groups; the merge on the primary keeps one entry per group."""
+    nq = q.shape[0]
+    scores = torch.empty(nq, k, device=self.device, dtype=torch.float32)
+    groups = torch.empty(nq, k, device=self.device, dtype=torch.int64)
+    items = torch.empty(nq, k, device=self.device, dtype=torch.int64)
+    if nq == 0:
+      return scores, groups, items
+    live = self._live(subset)
+    kin = min(k, max(grouping.parts[s].num_groups for s, _ in live))
+    with torch.cuda.device(self.device):  # the staged lists; the slots a shorter list leaves are empty
+      st_scores = torch.full((len(live), nq, kin), float('-inf'), device=self.device, dtype=torch.float32)
+      st_groups = torch.full((len(live), nq, kin), -1, device=self.device, dtype=torch.int64)
+      st_index = torch.full((len(live), nq, kin), -1, device=self.device, dtype=torch.int64)
+      tables = self._tables(tuple(s for s, _ in live))
+    for i, (s, sh) in enumerate(live):
+      part = grouping.parts[s]
+      with torch.cuda.device(sh.device):
+        out = sh.index._search_groups(q.to(sh.device), qw.to(sh.device), min(k, part.num_groups), part,
+                                      None if subset is None else subset.parts[s])
+      width = out[0].shape[1]
+      st_scores[i, :, :width].copy_(out[0])
+      st_groups[i, :, :width].copy_(out[1])
+      st_index[i, :, :width].copy_(out[2])
+    with torch.cuda.device(self.device):
+      check(_lib.lib().mmt_search_merge_group_lists(ops._p(st_scores), ops._p(st_groups), ops._p(st_index), ops._p(tables),
+                                                    len(live), nq, kin, k, ops._p(scores), ops._p(groups), ops._p(items),
+                                                    ops._stream()), 'mmt_search_merge_group_lists')
+    return scores, groups, items
 
   def _rank_counts(self, q, qw, tg, subset, norm=None):
     """`rank_counts` behind its checks: tg int64 [NQ, T] global numbers on the primary -> (greater, equal) int32 [NQ, T]."""

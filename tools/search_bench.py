@@ -49,7 +49,14 @@ threshold_counts against the same thresholds (T = 1: one scan, the yardstick -- 
 search(k = 10).  --runs rounds, every variant once per round, interleaved; median and spread.  --counts-only times the
 two yardsticks alone: it calls nothing a build without range_search lacks, so the same file run inside a checkout of the
 parent commit gives the parent's numbers, and --baseline-json FILE... records such results beside this build's.  Default
-output profiles/search_range_bench.json."""
+output profiles/search_range_bench.json.
+
+--groups SIZE times the grouped search (VideoIndex.search_groups, k = 10: the k best groups, each with its best item) per
+index dtype (--gallery-dtype, both = the two indexes) with the items in groups of SIZE: contiguous groups (item i in group
+i // SIZE: a clip gallery stored video by video) and the same groups with the item order shuffled (members anywhere: every
+chunk list can hold any group, so the merge de-duplicates), beside the plain search(k = 10) of the same index -- the same
+scan with the plain running list, the yardstick.  --runs rounds, every variant once per round, interleaved; median and
+spread.  Default output profiles/search_groups_bench.json."""
 import argparse
 import json
 import math
@@ -315,6 +322,53 @@ def range_mode(q, qw, g, gw, flop, a):
   return row
 
 
+def groups_mode(q, qw, g, gw, flop, a):
+  """search_groups with contiguous and with shuffled groups of a.groups items against search(k = 10), per index dtype."""
+  nv = g.shape[0]
+  dtypes = ('float32', 'bfloat16') if a.gallery_dtype == 'both' else (a.gallery_dtype,)
+  gen = torch.Generator(device=q.device).manual_seed(2)
+  every = torch.arange(nv, device=q.device)
+  ids = {'contiguous': every // a.groups, 'shuffled': (every // a.groups)[torch.randperm(nv, device=q.device, generator=gen)]}
+  fns = {}
+  for n in dtypes:
+    index = VideoIndex.empty(nv, M, D, g.device, dtype=getattr(torch, n))
+    for at in range(0, nv, 8192):
+      index.add(g[at:at + 8192], gw[at:at + 8192])
+    for name, gids in ids.items():
+      grp = index.grouping(gids)
+      fns['%s/search_groups_%s' % (n, name)] = lambda index=index, grp=grp: index.search_groups(q, qw, grp, k=K)
+    fns[n + '/search_k10'] = lambda index=index: index.search(q, qw, k=K)
+  ts = {n: [] for n in fns}
+  mem = {n: 0 for n in fns}
+  out = {}
+  for _ in range(a.runs):
+    for n, fn in fns.items():
+      t, _, m, out[n] = timed(fn, a.min_seconds)
+      ts[n].append(t)
+      mem[n] = max(mem[n], m)
+  row = {'group_size': a.groups, 'num_groups': -(-nv // a.groups)}
+  for n in fns:
+    med = float(np.median(ts[n]))
+    row[n] = dict(seconds_median=med, seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n],
+                  tflops_of_the_scan=flop / med / 1e12, peak_mem_growth_bytes=mem[n])
+  for n in dtypes:
+    plain = row[n + '/search_k10']
+    summary = {}
+    for name in ids:
+      r = row['%s/search_groups_%s' % (n, name)]
+      scores, groups, items = out['%s/search_groups_%s' % (n, name)]
+      spread = max(r['seconds_spread'], plain['seconds_spread'])
+      summary[name] = dict(
+          over_search_k10=r['seconds_median'] / plain['seconds_median'], spread_seconds=spread,
+          slower_than_search_k10_beyond_spread=bool(r['seconds_median'] - plain['seconds_median'] > spread),
+          # the best group is the group of the best item, and every row holds K distinct groups
+          top_group_is_that_of_the_top_item=bool(torch.equal(items[:, 0], out[n + '/search_k10'][1][:, 0])),
+          rows_with_distinct_groups=float((groups.sort(1).values.diff(dim=1) != 0).all(1).float().mean()),
+          groups_are_those_of_the_items=bool(torch.equal(groups, ids[name][items])))
+    row[n + '/summary'] = summary
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--shapes', default='S1,S2,S3')
@@ -337,6 +391,8 @@ def main():
                   'HITS-th best score (1..128) against threshold_counts (T = 1) and search(k = 10)')
   ap.add_argument('--counts-only', action='store_true', help='with --range: the two yardsticks alone (runs on a build '
                   'without range_search)')
+  ap.add_argument('--groups', type=int, default=0, metavar='SIZE', help='time search_groups(k = 10) with contiguous and with '
+                  'shuffled groups of SIZE items against search(k = 10)')
   ap.add_argument('--baseline-json', nargs='+', default=[], help='with --norm: default-mode results of another build; '
                   'with --range: --range --counts-only results of another build')
   ap.add_argument('--same-build-json', nargs='+', default=[], help='with --norm: default-mode results of this build')
@@ -352,6 +408,10 @@ def main():
     raise SystemExit('--norm wants 0 < BETA < inf and no --ranks, --subset, --exclude, --shards')
   if not 0 <= a.range <= 128 or a.range and (masked or a.ranks or a.shards or a.norm is not None):
     raise SystemExit('--range wants 1..128 and no --ranks, --subset, --exclude, --shards, --norm')
+  if a.groups < 0 or a.groups and (masked or a.ranks or a.shards or a.norm is not None or a.range):
+    raise SystemExit('--groups wants SIZE >= 1 and no --ranks, --subset, --exclude, --shards, --norm, --range')
+  if a.groups and a.out is None:
+    a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_groups_bench.json')
   if a.counts_only and not a.range:
     raise SystemExit('--counts-only goes with --range')
   if a.range and a.out is None and not a.counts_only:
@@ -391,6 +451,8 @@ def main():
           other = json.load(f)
         res['baseline'].append({name: {n: v for n, v in row.items() if isinstance(v, dict) and 'seconds_median' in v}
                                 for name, row in other['shapes'].items()})
+  if a.groups:
+    res.update(mode='groups', group_size=a.groups, gallery_dtype=a.gallery_dtype, runs=a.runs, min_seconds=a.min_seconds)
   if masked:
     res.update(mode='subset', subset_fraction=a.subset, exclude=a.exclude, runs=a.runs, min_seconds=a.min_seconds)
   for name in a.shapes.split(','):
@@ -403,9 +465,9 @@ def main():
     qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
     flop = 2.0 * nq * nv * M * D
     row = {'NQ': nq, 'NV': nv, 'flop': flop}
-    if masked or a.ranks or a.norm is not None or a.range or a.gallery_dtype == 'both':
-      mode = (norm_mode if a.norm is not None else range_mode if a.range else subset_mode if masked else
-              ranks_mode if a.ranks else both_dtypes)
+    if masked or a.ranks or a.norm is not None or a.range or a.groups or a.gallery_dtype == 'both':
+      mode = (norm_mode if a.norm is not None else range_mode if a.range else groups_mode if a.groups else
+              subset_mode if masked else ranks_mode if a.ranks else both_dtypes)
       row.update(mode(q, qw, g, gw, flop, a))
       res['shapes'][name] = row
       print(name, json.dumps(row), flush=True)
