@@ -18,7 +18,6 @@
 // Dropout mask of element (b,h,q,k): hash of (key, (b*H+h)*S4+q) then of (k>>1); q,k are the ORIGINAL positions of the
 // tokens inside the sample (row_index[row] - b*S when the rows are packed), so a packed run draws exactly the mask of
 // the dense run.  Backward regenerates it.
-#include <stdlib.h>
 #include "mmt_common.h"
 #include "attn_sched.h"
 #include "../../include/mmt_hip.h"
@@ -833,7 +832,7 @@ __device__ __forceinline__ void attn_bwd_dkv_block(const AttnArgs& a, unsigned c
 // its two halves share the CUs instead of running back to back.
 // ------------------------------------------------------------------------------------------------
 template <int DH>
-__global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnArgs a, int q_tiles, int k_tiles) {
+__global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnArgs a, int k_tiles) {
   extern __shared__ __attribute__((aligned(256))) unsigned char att_smem[];
   ATT_MARK(0);
   if (a.work) {  // scheduled order (attn_sched.h): one scalar 16-byte load tells the block what it is
@@ -845,23 +844,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnArgs a, int q_tile
       else attn_bwd_dkv_block<DH>(a, att_smem, tile, wb, h, woff, wlen);
     }
   } else {
-  const int nbh = a.H * a.B, bh = (int)blockIdx.x % nbh, slot = (int)blockIdx.x / nbh;
-  const int b = bh / a.H, h = bh % a.H;
-  const int off = a.cu ? a.cu[b] : b * a.S_dense;
-  const int Sb = a.cu ? a.cu[b + 1] - off : a.S_dense;
-  if (q_tiles < 0) {  // lab (MMT_ATTN_BWD_MERGE=1): tile i of BOTH roles in one block, one after the other
-    attn_bwd_dkv_block<DH>(a, att_smem, slot, b, h, off, Sb);
-    __syncthreads();
-    if (slot < -q_tiles) attn_bwd_dq_block<DH>(a, att_smem, slot, b, h, off, Sb);
-  } else {
-  // All dK/dV tiles first (the longer role), then the dQ tiles.  Tiles past a sample's length exit at once and hand their
-  // slot to the next block in line.  (Order without a work list: callers outside the engine, dense batches.)
-  int role, tile;  // role 0 = dK/dV, 1 = dQ
-  if (slot < k_tiles) { role = 0; tile = slot; }
-  else { role = 1; tile = slot - k_tiles; }
-  if (role) attn_bwd_dq_block<DH>(a, att_smem, tile, b, h, off, Sb);
-  else attn_bwd_dkv_block<DH>(a, att_smem, tile, b, h, off, Sb);
-  }
+    const int nbh = a.H * a.B, bh = (int)blockIdx.x % nbh, slot = (int)blockIdx.x / nbh;
+    const int b = bh / a.H, h = bh % a.H;
+    const int off = a.cu ? a.cu[b] : b * a.S_dense;
+    const int Sb = a.cu ? a.cu[b + 1] - off : a.S_dense;
+    // All dK/dV tiles first (the longer role), then the dQ tiles.  Tiles past a sample's length exit at once and hand their
+    // slot to the next block in line.  (Order without a work list: callers outside the engine, dense batches.)
+    int role, tile;  // role 0 = dK/dV, 1 = dQ
+    if (slot < k_tiles) { role = 0; tile = slot; }
+    else { role = 1; tile = slot - k_tiles; }
+    if (role) attn_bwd_dq_block<DH>(a, att_smem, tile, b, h, off, Sb);
+    else attn_bwd_dkv_block<DH>(a, att_smem, tile, b, h, off, Sb);
   }
 #ifdef MMT_GEMM2_INSTR
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -922,18 +915,12 @@ template <typename K> static int set_lds(K kernel, size_t bytes, size_t* configu
   return 0;
 }
 
-// nq queries per sample.  8-wave blocks (128 queries) when a sample has more than 64 queries; MMT_ATTN_FWD_WAVES=4 (lab:
-// same-box A/B) keeps the 4-wave blocks of r01-r02.
+// nq queries per sample.  8-wave blocks (128 queries) when a sample has more than 64 queries, 4-wave blocks otherwise.
 static int launch_fwd(const AttnArgs& a, int nq, int H, int B, bool dh128, hipStream_t s) {
-  static int waves = -1;
   static size_t conf[4] = {0, 0, 0, 0};
-  if (waves < 0) {
-    const char* e = getenv("MMT_ATTN_FWD_WAVES");
-    waves = e ? atoi(e) : 8;
-  }
   const size_t lds = attn_lds_bytes(dh128 ? 128 : 64, a.S_dense);
   if (lds > 160 * 1024) return MMT_ERR_ARG;
-  if (waves == 8 && nq > 64) {
+  if (nq > 64) {
     const dim3 grid(((nq + 127) / 128) * H * B);
     if (dh128) { if (set_lds(attn_fwd_kernel<128, 8>, lds, &conf[0])) return MMT_ERR_ARG; hipLaunchKernelGGL((attn_fwd_kernel<128, 8>), grid, dim3(512), lds, s, a); }
     else { if (set_lds(attn_fwd_kernel<64, 8>, lds, &conf[1])) return MMT_ERR_ARG; hipLaunchKernelGGL((attn_fwd_kernel<64, 8>), grid, dim3(512), lds, s, a); }
@@ -945,16 +932,10 @@ static int launch_fwd(const AttnArgs& a, int nq, int H, int B, bool dh128, hipSt
   return (int)hipGetLastError();
 }
 
-// tq query tiles (dQ role) + tk key tiles (dK/dV role) in one launch.  MMT_ATTN_BWD_SPLIT=1 (lab: same-box A/B) issues
-// the two roles as two launches of the same kernel, the r02 structure.  delta_ready = 0: the delta partials are formed
+// tq query tiles (dQ role) + tk key tiles (dK/dV role) in one launch.  delta_ready = 0: the delta partials are formed
 // here (one more launch); 1: the caller's `delta` buffer already holds them (MmtEpilogue.dot_out of the dO GEMM).
 static int launch_bwd(const AttnArgs& a, int tq, int tk, int H, int B, bool dh128, int delta_ready, int rows_c, hipStream_t s) {
-  static int split = -1;
   static size_t conf[2] = {0, 0};
-  if (split < 0) {
-    const char* e = getenv("MMT_ATTN_BWD_SPLIT");
-    split = e ? atoi(e) : 0;
-  }
   const size_t lds = attn_lds_bytes(dh128 ? 128 : 64, a.S_dense);
   if (lds > 160 * 1024) return MMT_ERR_ARG;
   if (dh128) { if (set_lds(attn_bwd_kernel<128>, lds, &conf[0])) return MMT_ERR_ARG; }
@@ -964,24 +945,22 @@ static int launch_bwd(const AttnArgs& a, int tq, int tk, int H, int B, bool dh12
     hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, a.dctx, (const bf16_t*)a.ctx, a.ldc,
                        (float*)a.dparts, rows_c, a.d, a.qsel ? nullptr : a.cu, B);
   }
-  auto go = [&](int q_tiles, int k_tiles) {
-    const int gx = (q_tiles + k_tiles) * H * B;
-    if (dh128) hipLaunchKernelGGL(attn_bwd_kernel<128>, dim3(gx), dim3(256), lds, s, a, q_tiles, k_tiles);
-    else hipLaunchKernelGGL(attn_bwd_kernel<64>, dim3(gx), dim3(256), lds, s, a, q_tiles, k_tiles);
-  };
-  if (a.work) {
-    go(tq, tk);
-  } else if (split == 2 && tq <= tk) {  // lab: merged roles (see the kernel)
-    const int gx = tk * H * B;
-    if (dh128) hipLaunchKernelGGL(attn_bwd_kernel<128>, dim3(gx), dim3(256), lds, s, a, -tq, tk);
-    else hipLaunchKernelGGL(attn_bwd_kernel<64>, dim3(gx), dim3(256), lds, s, a, -tq, tk);
-  } else if (split) {
-    go(tq, 0);
-    go(0, tk);
-  } else {
-    go(tq, tk);
-  }
+  const dim3 grid((tq + tk) * H * B);
+  if (dh128) hipLaunchKernelGGL(attn_bwd_kernel<128>, grid, dim3(256), lds, s, a, tk);
+  else hipLaunchKernelGGL(attn_bwd_kernel<64>, grid, dim3(256), lds, s, a, tk);
   return (int)hipGetLastError();
+}
+
+// what every entry point passes to the kernels; the callers add qsel / nq, the backward pointers and the work list
+static AttnArgs attn_args(const void* qkv, const int32_t* cu_seqlens, const float* mask_bias, const void* ctx, const float* lse,
+                          int B, int S, int H, int d, float scale, uint32_t drop_key, uint32_t thr16, float drop_scale,
+                          const uint32_t* seed_dev, const int32_t* row_index) {
+  AttnArgs a = {};
+  a.qkv = (const bf16_t*)qkv; a.ld = 3 * (int64_t)d; a.cu = cu_seqlens; a.S_dense = S; a.mask_bias = mask_bias;
+  a.ctx = (bf16_t*)ctx; a.ldc = d; a.lse = (float*)lse; a.H = H; a.d = d; a.B = B; a.scale = scale;
+  a.drop_key = drop_key; a.thr16 = thr16; a.drop_scale = drop_scale; a.S4 = (S + 3) & ~3; a.seed_dev = seed_dev;
+  a.row_index = row_index;
+  return a;
 }
 
 extern "C" int mmt_attn_fwd(const void* qkv, const int32_t* cu_seqlens, const float* mask_bias, void* ctx,
@@ -989,11 +968,7 @@ extern "C" int mmt_attn_fwd(const void* qkv, const int32_t* cu_seqlens, const fl
                             uint32_t thr16, float drop_scale, const uint32_t* seed_dev, const int32_t* row_index, void* stream) {
   if (int e = check_args(qkv, B, S, H, d)) return e;
   if (!mask_bias || !ctx || !lse) return MMT_ERR_ARG;
-  AttnArgs a = {};
-  a.qkv = (const bf16_t*)qkv; a.ld = 3 * (int64_t)d; a.cu = cu_seqlens; a.S_dense = S; a.mask_bias = mask_bias;
-  a.ctx = (bf16_t*)ctx; a.ldc = d; a.lse = lse; a.H = H; a.d = d; a.B = B; a.scale = scale;
-  a.drop_key = drop_key; a.thr16 = thr16; a.drop_scale = drop_scale; a.S4 = (S + 3) & ~3; a.seed_dev = seed_dev;
-  a.row_index = row_index;
+  AttnArgs a = attn_args(qkv, cu_seqlens, mask_bias, ctx, lse, B, S, H, d, scale, drop_key, thr16, drop_scale, seed_dev, row_index);
   return launch_fwd(a, S, H, B, d == H * 128, (hipStream_t)stream);
 }
 
@@ -1016,12 +991,8 @@ extern "C" int mmt_attn_bwd_ex(const void* qkv, const int32_t* cu_seqlens, const
                                const uint32_t* seed_dev, const int32_t* row_index, const int32_t* work, void* stream) {
   if (int e = check_args(qkv, B, S, H, d)) return e;
   if (!mask_bias || !ctx || !lse || !dctx || !dqkv || !delta) return MMT_ERR_ARG;
-  AttnArgs a = {};
-  a.qkv = (const bf16_t*)qkv; a.ld = 3 * (int64_t)d; a.cu = cu_seqlens; a.S_dense = S; a.mask_bias = mask_bias;
-  a.ctx = (bf16_t*)ctx; a.ldc = d; a.lse = (float*)lse; a.dctx = (const bf16_t*)dctx; a.dqkv = (bf16_t*)dqkv;
-  a.dparts = delta; a.H = H; a.d = d; a.B = B; a.scale = scale;
-  a.drop_key = drop_key; a.thr16 = thr16; a.drop_scale = drop_scale; a.S4 = (S + 3) & ~3; a.seed_dev = seed_dev;
-  a.row_index = row_index;
+  AttnArgs a = attn_args(qkv, cu_seqlens, mask_bias, ctx, lse, B, S, H, d, scale, drop_key, thr16, drop_scale, seed_dev, row_index);
+  a.dctx = (const bf16_t*)dctx; a.dqkv = (bf16_t*)dqkv; a.dparts = delta;
   if (work && (!cu_seqlens || !attn_schedulable(B, H))) return MMT_ERR_ARG;
   a.work = work;
   const int tiles = (S + 63) / 64;
@@ -1043,11 +1014,7 @@ extern "C" int mmt_attn_fwd_rows(const void* qkv, const int32_t* cu_seqlens, con
                                  uint32_t drop_key, uint32_t thr16, float drop_scale, const uint32_t* seed_dev, const int32_t* row_index, void* stream) {
   if (int e = check_args(qkv, B, S, H, d)) return e;
   if (!mask_bias || !ctx || !lse || !qsel || nq <= 0) return MMT_ERR_ARG;
-  AttnArgs a = {};
-  a.qkv = (const bf16_t*)qkv; a.ld = 3 * (int64_t)d; a.cu = cu_seqlens; a.S_dense = S; a.mask_bias = mask_bias;
-  a.ctx = (bf16_t*)ctx; a.ldc = d; a.lse = lse; a.H = H; a.d = d; a.B = B; a.scale = scale;
-  a.drop_key = drop_key; a.thr16 = thr16; a.drop_scale = drop_scale; a.S4 = (S + 3) & ~3; a.seed_dev = seed_dev;
-  a.row_index = row_index;
+  AttnArgs a = attn_args(qkv, cu_seqlens, mask_bias, ctx, lse, B, S, H, d, scale, drop_key, thr16, drop_scale, seed_dev, row_index);
   a.qsel = qsel; a.nq = nq;
   return launch_fwd(a, nq, H, B, d == H * 128, (hipStream_t)stream);
 }
@@ -1058,12 +1025,8 @@ extern "C" int mmt_attn_bwd_rows_ex(const void* qkv, const int32_t* cu_seqlens, 
                                     float drop_scale, const uint32_t* seed_dev, const int32_t* row_index, void* stream) {
   if (int e = check_args(qkv, B, S, H, d)) return e;
   if (!mask_bias || !ctx || !lse || !dctx || !dqkv || !delta || !qsel || nq <= 0) return MMT_ERR_ARG;
-  AttnArgs a = {};
-  a.qkv = (const bf16_t*)qkv; a.ld = 3 * (int64_t)d; a.cu = cu_seqlens; a.S_dense = S; a.mask_bias = mask_bias;
-  a.ctx = (bf16_t*)ctx; a.ldc = d; a.lse = (float*)lse; a.dctx = (const bf16_t*)dctx; a.dqkv = (bf16_t*)dqkv;
-  a.dparts = delta; a.H = H; a.d = d; a.B = B; a.scale = scale;
-  a.drop_key = drop_key; a.thr16 = thr16; a.drop_scale = drop_scale; a.S4 = (S + 3) & ~3; a.seed_dev = seed_dev;
-  a.row_index = row_index;
+  AttnArgs a = attn_args(qkv, cu_seqlens, mask_bias, ctx, lse, B, S, H, d, scale, drop_key, thr16, drop_scale, seed_dev, row_index);
+  a.dctx = (const bf16_t*)dctx; a.dqkv = (bf16_t*)dqkv; a.dparts = delta;
   a.qsel = qsel; a.nq = nq;
   return launch_bwd(a, (nq + 63) / 64, (S + 63) / 64, H, B, d == H * 128, delta_ready, B * nq, (hipStream_t)stream);
 }

@@ -39,7 +39,6 @@ struct Ws {
   char *dy_[2], *dy2_[2], *dhpre_[2], *dqkv_[2], *dctx;
   size_t attn_work_words;
   int32_t* attn_work;  // block order of the attention backward for the batch in flight (attn_sched.h; written by the forward)
-  float* kslab;  // split-K partial slabs of the main path's K = intermediate, N = hidden GEMMs (up to 4 x [R, d])
   size_t bytes;
 };
 
@@ -88,7 +87,6 @@ void layout(const MmtBertModel* m, int R, char* base, Ws* w) {
   // second set of the weight-gradient operands (odd layers under MMT_FORK_WGRAD), behind everything else: the buffers of
   // the serial path keep the addresses (and the cache-set relationships) they had before forking existed
   w->dy_[1] = take(R * d * 2); w->dy2_[1] = take(R * d * 2); w->dhpre_[1] = take(R * I * 2); w->dqkv_[1] = take(R * 3 * d * 2);
-  w->kslab = (float*)take((size_t)4 * R * d * 4);
   // B * ceil(S / 64) <= R / 64 + B tile slots per role and head, and a schedule is only built for B * H <= 2048
   w->attn_work_words = (size_t)2 * ((size_t)R / 64 + (R < 2048 ? (size_t)R : 2048)) * H * 4;
   w->attn_work = (int32_t*)take(w->attn_work_words * 4);
@@ -193,72 +191,28 @@ extern "C" int64_t mmt_bert_workspace_bytes(const MmtBertModel* m, int rows_allo
 
 // N = hidden GEMMs with a long K on SHORT batches (the text tower: ~1000 token rows x 768): too few output tiles for
 // 256 CUs and a 36..48-step dependent K loop per tile -> split K over 2..4 blocks per tile (partials in the tail's slab
-// workspace, which is idle outside the tail layer) and reduce in the epilogue kernel.  Measured 30 -> 17 us (K = 3072),
-// 24 -> 15.5 us (K = 2304) at 960 rows; not worth it at K = 768.  The video side (thousands of rows) never takes it.
-static int gemm_hidden(const Ws& w, int rows, int d, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
-                       int64_t ldc, int K, int epi, const MmtEpilogue* e, const int32_t* nr, void* stream) {
+// workspace, which is idle outside the tail layer).  Measured 30 -> 17 us (K = 3072), 24 -> 15.5 us (K = 2304) at 960 rows;
+// not worth it at K = 768.  The video side (thousands of rows) never takes it.  -> splits (0: not a short batch)
+static int short_batch_splits(const Ws& w, int rows, int d, int K) {
   const int tiles = ((rows + 127) / 128) * (d / 64), ksteps = K / 64;
-  if (tiles < 160 && ksteps >= 32 && rows <= 4 * w.t.cap)
-    return mmt_gemm_nt_splitk_ex(A, lda, B, ldb, C, ldc, rows, d, K, epi, e, w.t.slabs, ksteps >= 48 ? 4 : 2, 0, nr, 0, stream);
-  return mmt_gemm_nt_bf16(A, lda, B, ldb, C, ldc, rows, d, K, epi, e, nr, stream);
-}
-
-// K = intermediate, N = hidden on thousands of rows: one 128x64 tile per CU walks 48 dependent K-steps at the CU's
-// L2 -> LDS ingest limit (24 KB per step).  Lab switch MMT_SPLITK_FFN = 10 * splits + wide (0 = off, the default): the GEMM
-// split over K with the partial slabs summed by the LayerNorm pass that follows anyway (fwd: + bias, dropout, residual;
-// bwd: + residual gradient).  Same-box A/B of the whole step (3 alternations, r04): off 1.2864 ms; 2 splits of 128x64
-// tiles 1.2912; 2 splits of 128x128 tiles 1.3245; 4 splits of 256x128 tiles 1.2808 -- the slab traffic (4 x 7.3 MB written
-// and read back per GEMM) eats what the shorter K-chains win.  Parity-tested (tests/test_cenet_gpu.py under the switch).
-static int splitk_ffn_mode() {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("MMT_SPLITK_FFN");
-    mode = e ? atoi(e) : 0;
-  }
-  return mode;
-}
-static bool splitk_ffn(const Ws&, int rows, int d, int K) {
-  return splitk_ffn_mode() > 0 && rows >= 2048 && K >= 2048 && d <= 512;
-}
-
-// r06: the short-batch case of gemm_hidden (the text tower: a few hundred live rows, K = intermediate) already runs split-K;
-// its slab-summing epilogue launch and the LayerNorm launch behind it are ONE launch when the LayerNorm reads the slabs
-// itself (mmt_splitk_ln_fwd_ex / mmt_ln_bwd_slabs_ex: + bias, dropout, residual resp. + residual gradient) -- two graph
-// nodes less per layer, forward and backward.  -> splits (0: not this case).  MMT_SPLITK_LN=0 restores the r05 launches.
-static int small_splitk_ln(const Ws& w, int rows, int d, int K) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("MMT_SPLITK_LN");
-    on = e ? atoi(e) : 1;
-  }
-  const int tiles = ((rows + 127) / 128) * (d / 64), ksteps = K / 64;
-  if (!on || !(tiles < 160 && ksteps >= 32 && rows <= 4 * w.t.cap)) return 0;
+  if (!(tiles < 160 && ksteps >= 32 && rows <= 4 * w.t.cap)) return 0;
   return ksteps >= 48 ? 4 : 2;
 }
 
-// r05: BertSelfOutput's projection + LayerNorm as one launch where the hidden size is the 512 of the video BERT (a block of
-// gemm_ln.hip owns 32 whole rows of 512 columns).  OPT-IN (MMT_FUSE_OUT_LN=1): it removes three graph nodes and three reads
-// of z per step, but every block streams the whole 512 KiB weight through its CU's ~21 B/clk ingest -- same-box A/B of the
-// whole step, three alternations: 1.2718 / 1.2719 / 1.2738 ms with the GEMM + LayerNorm pair, 1.2851 / 1.2863 / 1.2871 with
-// the fused launch.
-static bool fuse_out_ln(int d) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("MMT_FUSE_OUT_LN");
-    on = e ? atoi(e) : 0;
-  }
-  return on && d == 512;
+// the N = hidden GEMM as one launch pair: on a short batch the slabs are reduced by the split-K epilogue kernel.  Where a
+// LayerNorm follows, the engine skips that epilogue and has the LayerNorm read the slabs itself (mmt_splitk_ln_fwd_ex /
+// mmt_ln_bwd_slabs_ex: + bias, dropout, residual resp. + residual gradient) -- two graph nodes less per layer.
+static int gemm_hidden(const Ws& w, int rows, int d, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
+                       int64_t ldc, int K, int epi, const MmtEpilogue* e, const int32_t* nr, void* stream) {
+  if (const int sp = short_batch_splits(w, rows, d, K))
+    return mmt_gemm_nt_splitk_ex(A, lda, B, ldb, C, ldc, rows, d, K, epi, e, w.t.slabs, sp, 0, nr, 0, stream);
+  return mmt_gemm_nt_bf16(A, lda, B, ldb, C, ldc, rows, d, K, epi, e, nr, stream);
 }
 
 // the attention backward's block order (attn_sched.h) exists for packed batches whose (sample, head) pairs split over 8 XCDs
 static const int32_t* attn_work_of(const MmtBertModel* m, const MmtBertBatch* b, const Ws& w) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("MMT_ATTN_SCHED");
-    on = e ? atoi(e) : 1;
-  }
   const long bh = (long)b->batch * m->heads;
-  if (!on || !b->cu_seqlens || bh % 8 || bh > 2048 || m->heads > 255) return nullptr;
+  if (!b->cu_seqlens || bh % 8 || bh > 2048 || m->heads > 255) return nullptr;
   if ((size_t)mmt_attn_schedule_words(b->batch, b->seq, m->heads) > w.attn_work_words) return nullptr;
   return w.attn_work;
 }
@@ -321,51 +275,41 @@ extern "C" int mmt_bert_forward(const MmtBertModel* m, const MmtBertBatch* b, vo
       TRY(mmt_attn_fwd(L.qkv, b->cu_seqlens, b->mask_bias, L.ctx, L.lse, b->batch, b->seq, m->heads, d, qk_scale,
                        site_key(l, SITE_PROBS), ta, sa, b->seed_dev, b->row_index, stream));
     }
-    if (fuse_out_ln(d)) {
-      // attention output projection + dropout + residual + LayerNorm in ONE launch (gemm_ln.hip: a block owns 32 whole rows)
-      TRY(mmt_gemm_nt_ln_fwd(L.ctx, d, P.wo, d, P.bo, hin32, d, b->row_index, site_key(l, SITE_ATTN_OUT), th, sh, b->seed_dev,
-                             L.z1, P.ln1_g, P.ln1_b, m->ln_eps, L.a32, L.a16, L.mean1, L.rstd1, rows, d, d, b->n_rows_dev, stream));
-    } else {
     e = {}; e.live_rows_hint = lh;
     e.bias = P.bo; e.res = hin32; e.ldres = d; e.row_index = b->row_index; e.seed_dev = b->seed_dev;
     e.drop_key = site_key(l, SITE_ATTN_OUT); e.drop_thr16 = th; e.drop_scale = sh;
     TRY(mmt_gemm_nt_bf16(L.ctx, d, P.wo, d, L.z1, d, rows, d, d, MMT_EPI_BIAS_DROP_RES, &e, b->n_rows_dev, stream));
     TRY(mmt_ln_fwd(L.z1, P.ln1_g, P.ln1_b, m->ln_eps, L.a32, L.a16, L.mean1, L.rstd1, rows, d, b->n_rows_dev, stream));
-    }
     e = {}; e.live_rows_hint = lh;
     e.bias = P.b1; e.out2 = L.g; e.ldout2 = I;
     {
       ProbeScope probe(0, l == 0, stream);
       TRY(mmt_gemm_nt_bf16(L.a16, d, P.w1, d, L.hpre, I, rows, I, d, MMT_EPI_BIAS_GELU, &e, b->n_rows_dev, stream));
     }
-    e = {}; e.live_rows_hint = lh;
-    e.bias = P.b2; e.res = L.a32; e.ldres = d; e.row_index = b->row_index; e.seed_dev = b->seed_dev;
-    e.drop_key = site_key(l, SITE_FFN_OUT); e.drop_thr16 = th; e.drop_scale = sh;
     float* hout32 = (l == m->layers - 1) ? out_last : L.h32;
-    const int small_sp = small_splitk_ln(w, rows, d, I);
-    if (splitk_ffn(w, rows, d, I) || small_sp) {
-      const int mode = small_sp ? 10 * small_sp : splitk_ffn_mode();
-      float* slabs = small_sp ? w.t.slabs : w.kslab;
+    if (const int splits = short_batch_splits(w, rows, d, I)) {
+      // short batch: the slabs are summed by the LayerNorm pass, which also applies bias, dropout and the residual
       int sp = 0;
       int64_t sstride = 0;
-      TRY(mmt_gemm_splitk_geometry(rows, d, I, mode / 10, &sp, &sstride));
+      TRY(mmt_gemm_splitk_geometry(rows, d, I, splits, &sp, &sstride));
       {
         ProbeScope probe(1, l == 0, stream);
-        TRY(mmt_gemm_nt_splitk_ex(L.g, I, P.w2, I, nullptr, d, rows, d, I, MMT_EPI_F32, nullptr, slabs, mode / 10, mode % 10,
+        TRY(mmt_gemm_nt_splitk_ex(L.g, I, P.w2, I, nullptr, d, rows, d, I, MMT_EPI_F32, nullptr, w.t.slabs, splits, 0,
                                   b->n_rows_dev, 1, stream));
       }
-      TRY(mmt_splitk_ln_fwd_ex(slabs, sp, sstride, P.b2, L.a32, nullptr, nullptr, b->row_index, nullptr,
+      TRY(mmt_splitk_ln_fwd_ex(w.t.slabs, sp, sstride, P.b2, L.a32, nullptr, nullptr, b->row_index, nullptr,
                                site_key(l, SITE_FFN_OUT), th, sh, b->seed_dev, L.z2, P.ln2_g, P.ln2_b, m->ln_eps, hout32, L.h16,
                                L.mean2, L.rstd2, rows, d, b->n_rows_dev, stream));
-      hin32 = hout32;
-      hin16 = L.h16;
-      continue;
+    } else {
+      e = {}; e.live_rows_hint = lh;
+      e.bias = P.b2; e.res = L.a32; e.ldres = d; e.row_index = b->row_index; e.seed_dev = b->seed_dev;
+      e.drop_key = site_key(l, SITE_FFN_OUT); e.drop_thr16 = th; e.drop_scale = sh;
+      {
+        ProbeScope probe(1, l == 0, stream);
+        TRY(gemm_hidden(w, rows, d, L.g, I, P.w2, I, L.z2, d, I, MMT_EPI_BIAS_DROP_RES, &e, b->n_rows_dev, stream));
+      }
+      TRY(mmt_ln_fwd(L.z2, P.ln2_g, P.ln2_b, m->ln_eps, hout32, L.h16, L.mean2, L.rstd2, rows, d, b->n_rows_dev, stream));
     }
-    {
-      ProbeScope probe(1, l == 0, stream);
-      TRY(gemm_hidden(w, rows, d, L.g, I, P.w2, I, L.z2, d, I, MMT_EPI_BIAS_DROP_RES, &e, b->n_rows_dev, stream));
-    }
-    TRY(mmt_ln_fwd(L.z2, P.ln2_g, P.ln2_b, m->ln_eps, hout32, L.h16, L.mean2, L.rstd2, rows, d, b->n_rows_dev, stream));
     hin32 = hout32;
     hin16 = L.h16;
   }
@@ -519,8 +463,8 @@ extern "C" int mmt_bert_backward_range(const MmtBertModel* m, const MmtBertBatch
                               rows, d, 1, nr, b->row_index, site_key(l, SITE_FFN_OUT), th, sh, b->seed_dev, stream));
       dc_slabs = nullptr;
     } else {
-    TRY(mmt_ln_bwd(dcur, L.z2, L.mean2, L.rstd2, P.ln2_g, w.dz, dy2, w.ln_partials[2 * l + 2], rows, d, 1, nr, b->row_index,
-                   site_key(l, SITE_FFN_OUT), th, sh, b->seed_dev, stream));
+      TRY(mmt_ln_bwd(dcur, L.z2, L.mean2, L.rstd2, P.ln2_g, w.dz, dy2, w.ln_partials[2 * l + 2], rows, d, 1, nr, b->row_index,
+                     site_key(l, SITE_FFN_OUT), th, sh, b->seed_dev, stream));
     }
     add_job(w.ln_partials[2 * l + 2], ln_blocks, 3, 2, d, P.g_ln2_g, P.g_ln2_b);
     MmtEpilogue e = {}; e.live_rows_hint = lh;
@@ -531,26 +475,25 @@ extern "C" int mmt_bert_backward_range(const MmtBertModel* m, const MmtBertBatch
       TRY(mmt_wgrad_grouped(&gffn, side));
     }
     // --- BertIntermediate: dense(d->I) ---
-    const int small_sp = small_splitk_ln(w, rows, d, I);
-    if (splitk_ffn(w, rows, d, I) || small_sp) {
-      const int mode = small_sp ? 10 * small_sp : splitk_ffn_mode();
-      float* slabs = small_sp ? w.t.slabs : w.kslab;
+    if (const int splits = short_batch_splits(w, rows, d, I)) {
+      // short batch: the slabs and the residual gradient are summed by the LayerNorm backward itself
       int sp = 0;
       int64_t sstride = 0;
-      TRY(mmt_gemm_splitk_geometry(rows, d, I, mode / 10, &sp, &sstride));
+      TRY(mmt_gemm_splitk_geometry(rows, d, I, splits, &sp, &sstride));
       MmtEpilogue er = {}; er.live_rows_hint = lh;
-      TRY(mmt_gemm_nt_splitk_ex(dhpre, I, P.w1_t, I, nullptr, d, rows, d, I, MMT_EPI_F32, &er, slabs, mode / 10, mode % 10,
-                                nr, 1, stream));
+      TRY(mmt_gemm_nt_splitk_ex(dhpre, I, P.w1_t, I, nullptr, d, rows, d, I, MMT_EPI_F32, &er, w.t.slabs, splits, 0, nr, 1,
+                                stream));
+      // --- BertSelfOutput: LN1 <- dropout <- dense(d->d) ---
       // w.dz is read (residual gradient) and rewritten (LN1 input gradient) by the same lanes at the same elements
-      TRY(mmt_ln_bwd_slabs_ex(slabs, sp, sstride, w.dz, L.z1, L.mean1, L.rstd1, P.ln1_g, w.dz, dy, w.ln_partials[2 * l + 1],
+      TRY(mmt_ln_bwd_slabs_ex(w.t.slabs, sp, sstride, w.dz, L.z1, L.mean1, L.rstd1, P.ln1_g, w.dz, dy, w.ln_partials[2 * l + 1],
                               rows, d, 1, nr, b->row_index, site_key(l, SITE_ATTN_OUT), th, sh, b->seed_dev, stream));
     } else {
-    e = {}; e.live_rows_hint = lh;
-    e.res = w.dz; e.ldres = d;
-    TRY(gemm_hidden(w, rows, d, dhpre, I, P.w1_t, I, w.dA, d, I, MMT_EPI_ADD_F32, &e, nr, stream));
-    // --- BertSelfOutput: LN1 <- dropout <- dense(d->d) ---
-    TRY(mmt_ln_bwd(w.dA, L.z1, L.mean1, L.rstd1, P.ln1_g, w.dz, dy, w.ln_partials[2 * l + 1], rows, d, 1, nr, b->row_index,
-                   site_key(l, SITE_ATTN_OUT), th, sh, b->seed_dev, stream));
+      e = {}; e.live_rows_hint = lh;
+      e.res = w.dz; e.ldres = d;
+      TRY(gemm_hidden(w, rows, d, dhpre, I, P.w1_t, I, w.dA, d, I, MMT_EPI_ADD_F32, &e, nr, stream));
+      // --- BertSelfOutput: LN1 <- dropout <- dense(d->d) ---
+      TRY(mmt_ln_bwd(w.dA, L.z1, L.mean1, L.rstd1, P.ln1_g, w.dz, dy, w.ln_partials[2 * l + 1], rows, d, 1, nr, b->row_index,
+                     site_key(l, SITE_ATTN_OUT), th, sh, b->seed_dev, stream));
     }
     add_job(w.ln_partials[2 * l + 1], ln_blocks, 3, 2, d, P.g_ln1_g, P.g_ln1_b);
     e = {}; e.live_rows_hint = lh;
@@ -581,17 +524,18 @@ extern "C" int mmt_bert_backward_range(const MmtBertModel* m, const MmtBertBatch
     e.res = w.dz; e.ldres = d;
     float* dnext = (dcur == dlast) ? w.dA : dlast;  // ping-pong between the caller's buffer and dA
     // dA was consumed by the LN1 backward above, so it is free again here.
-    // r06, short batches: the split-K slabs of dX = dQKV . Wqkv are summed (+ the residual gradient w.dz) by the LayerNorm
+    // short batches: the split-K slabs of dX = dQKV . Wqkv are summed (+ the residual gradient w.dz) by the LayerNorm
     // backward of the layer below instead of by a slab-reducing epilogue launch -- when that layer runs in this call and
     // nothing is forked (the weight gradients below read dqkv, not the slabs; w.dz is not written in between)
-    const int qkv_sp = (l > l_lo && !fork_w) ? small_splitk_ln(w, rows, d, 3 * d) : 0;
+    const int qkv_sp = (l > l_lo && !fork_w) ? short_batch_splits(w, rows, d, 3 * d) : 0;
     if (qkv_sp) {
       TRY(mmt_gemm_splitk_geometry(rows, d, 3 * d, qkv_sp, &dc_sp, &dc_stride));
       TRY(mmt_gemm_nt_splitk_ex(dqkv, 3 * d, P.wqkv_t, 3 * d, nullptr, d, rows, d, 3 * d, MMT_EPI_F32, &e, w.t.slabs, qkv_sp, 0, nr, 1,
                                 stream));
       dc_slabs = w.t.slabs;
-    } else
-    TRY(gemm_hidden(w, rows, d, dqkv, 3 * d, P.wqkv_t, 3 * d, dnext, d, 3 * d, MMT_EPI_ADD_F32, &e, nr, stream));
+    } else {
+      TRY(gemm_hidden(w, rows, d, dqkv, 3 * d, P.wqkv_t, 3 * d, dnext, d, 3 * d, MMT_EPI_ADD_F32, &e, nr, stream));
+    }
     // --- all four weight gradients + bias gradients of the layer: ONE grouped launch (256 tiles at d=512, I=3072) ---
     if (!fork_w) {
       MmtWgradGroup g = gffn;

@@ -7,7 +7,6 @@
 //   moe           : softmax_m(text . w_m + b_m)
 // and the matching backward kernels.  Activations are [N, M, d] (row n contiguous over experts) so that
 // the text gradient is ONE GEMM over K = M*d.  Arithmetic is fp32 like the reference (the work is ~0.3 GFLOP).
-#include <stdlib.h>
 #include "mmt_common.h"
 #include "../../include/mmt_hip.h"
 
@@ -347,9 +346,6 @@ int mmt_text_heads_fwd_small(const MmtTextHeads* h, const float* text, const flo
 int mmt_text_heads_bwd_small(const MmtTextHeads* h, const float* text, const float* text_moe, int N, int C, int M, int d,
                              int K, int use_bn, int training, float* ws, const float* dtext_embds, const float* text_weights,
                              const float* dtext_weights, float* dtext_moe, const MmtTextHeadsOpts* opts, hipStream_t s);
-static bool small_path(int N, int M, int d, int K) {
-  return mmt_text_heads_fast(N, M, d, K);  // (honours the lab switch MMT_TEXT_HEADS_V1: the one-kernel-per-op path)
-}
 static bool fused_dropout(const MmtTextHeadsOpts* o, const float* text_moe) { return o && o->moe_drop_thr16 && !text_moe; }
 
 extern "C" int mmt_text_heads_fwd(const MmtTextHeads* h, const float* text, const float* text_moe, int N, int C, int M,
@@ -360,7 +356,7 @@ extern "C" int mmt_text_heads_fwd(const MmtTextHeads* h, const float* text, cons
   if (text_weights)
     for (int m = 0; m < M; ++m)
       if (!h->moe_w[m] || !h->moe_b[m]) return MMT_ERR_ARG;
-  if (small_path(N, M, d, K))
+  if (mmt_text_heads_fast(N, M, d, K))
     return mmt_text_heads_fwd_small(h, text, text_moe, N, C, M, d, K, use_bn, training, ws, text_embds, text_weights, opts,
                                     (hipStream_t)stream);
   if (fused_dropout(opts, text_moe) || (opts && (opts->num_batches_tracked || opts->video_front))) return MMT_ERR_ARG;  // small-batch path only
@@ -404,7 +400,7 @@ extern "C" int mmt_text_heads_bwd(const MmtTextHeads* h, const float* text, cons
   float *y = ws, *x1 = ws + nmd, *mean = ws + 2 * nmd, *rstd = mean + (int64_t)M * d;
   float *dyg = rstd + (int64_t)M * d, *dz = dyg + nmd, *dlogit = dz + nmd;
   hipStream_t s = (hipStream_t)stream;
-  if (small_path(N, M, d, K)) {
+  if (mmt_text_heads_fast(N, M, d, K)) {
     // the masked MoE-input gradient needs its own buffer when the dropout is applied on the fly
     if (fused_dropout(opts, text_moe) && dtext && !dtext_moe) return MMT_ERR_ARG;
     if (dtext && !w1_all) return MMT_ERR_ARG;

@@ -37,19 +37,10 @@
 
 #define W3_TIE(x) asm volatile("" : "+v"(x))
 // one fragment = 16 columns x 32 contracted rows: two transpose reads 16 rows (4096 bytes) apart
-#if defined(MMT_W3_LAB_NOREADS)  // lab (wrong results): no fragment reads at all
-#define W3_RD(lo, hi, base, OFF) do { asm volatile("" : "=v"(lo) : "v"(base)); asm volatile("" : "=v"(hi) : "v"(base)); } while (0)
-#elif defined(MMT_W3_LAB_PLAINREADS)  // lab (wrong results): the same bytes by plain 8-byte reads
-#define W3_RD(lo, hi, base, OFF) do {                                                          \
-    asm volatile("ds_read_b64 %0, %1 offset:" #OFF : "=v"(lo) : "v"(base));                   \
-    asm volatile("ds_read_b64 %0, %1 offset:" #OFF "+4096" : "=v"(hi) : "v"(base));           \
-  } while (0)
-#else
 #define W3_RD(lo, hi, base, OFF) do {                                                          \
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #OFF : "=v"(lo) : "v"(base));            \
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #OFF "+4096" : "=v"(hi) : "v"(base));    \
   } while (0)
-#endif
 
 template <int N> __device__ __forceinline__ void w3_vmwait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void w3_vmwait_rt(int n) {  // (wave-uniform n from {0, 2, 4, 6, 8})
@@ -195,11 +186,7 @@ __global__ __launch_bounds__(512) void wgrad3_kernel(MmtWgradGroup g) {
   // fragment registers: A fragments of the current row half (4 fragments x 2 k-sub-steps), right B fragments, left B fragments
   // of the current / next unit
   u32x2 fal[4][2], fah[4][2], frl[2][2], frh[2][2], fll[2][2][2], flh[2][2][2];
-#ifdef MMT_W3_LAB_NOMFMA  // lab (wrong results): the operands are consumed by one cheap op, the matrix pipe idles
-#define W3_MFMA(I, J, BL_, BH_, AL_, AH_) acc[I][J][0] += __uint_as_float(BL_[0] ^ AH_[1])
-#else
 #define W3_MFMA(I, J, BL_, BH_, AL_, AH_) acc[I][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3_join(BL_, BH_), w3_join(AL_, AH_), acc[I][J], 0, 0, 0)
-#endif
   // lab build (python -m mmt_amd.build --instr): per-phase s_memtime ticks, as gemm3.hip -- [phase][0] reads + requests + vmcnt,
   // [1] barrier, [2] lgkm wait + 16 MFMAs, [3] barrier; read back by tools/wgrad3_budget.py through mmt_debug_set_wgrad3_buffer
 #ifdef MMT_GEMM2_INSTR

@@ -17,7 +17,6 @@ rows and the columns) and a gradient pass; the cross-rank quantity is the column
 The maths is phase-structured (`phase_*`) so that the collectives sit between plain function calls; `ShardedSimLoss`
 wires the phases to torch.distributed (RCCL) and degenerates to a single row block without a process group.
 """
-import os
 
 import torch
 import torch.distributed as dist
@@ -66,8 +65,7 @@ class RowBlock:
     check(L.mmt_ls_fold_bf16(ops._p(self.txt), ops._p(self.tw), b, bp, m, d, ops._p(self.t16), ops._stream()), 'mmt_ls_fold_bf16')
     check(L.mmt_ls_fold_bf16(ops._p(self.vid_all), ops._p(self.vw_all), n, n, m, d, ops._p(self.v16), ops._stream()),
           'mmt_ls_fold_bf16')
-    pad = int(os.environ.get('MMT_LS_PAD', '0'))  # lab: leading dimension of the row block = n + pad
-    self.S = torch.empty(bp, n + pad, device=self.dev, dtype=torch.float32)[:, :n]
+    self.S = torch.empty(bp, n, device=self.dev, dtype=torch.float32)
     self.ld = self.S.stride(0)
     ops.gemm_nt(self.t16, self.v16, self.S, 'F32', m=b)
     # S holds the raw numerators until phase_counts divides them in its own sweep; the diagonal needs b divisions now

@@ -21,7 +21,6 @@ anything else raises NotImplementedError instead of silently taking a slow path.
 """
 import collections
 import ctypes
-import os
 import re
 import types
 
@@ -723,8 +722,7 @@ class CENet(nn.Module):
   _th_key = None
   _pending_front = None  # video plan whose plan / cast launches the next text-heads forward carries along
   _th_front = None
-  # lab switch (same-box A/B): MMT_FRONT_FUSE=0 keeps the plan and the cast as launches of their own
-  front_fuse = os.environ.get('MMT_FRONT_FUSE', '1') != '0'
+  front_fuse = True  # False (set per instance) keeps the plan and the cast as launches of their own
 
   def _text_heads_forward(self, text, text_moe, caps, moe_drop_p=0.0):
     n, k = text.shape

@@ -202,7 +202,7 @@ class GraphedTrainStep:
       raise ValueError('adam_riders: removed; measured slower, see DESIGN §7')
     self.model, self.loss_fn, self.group = model, loss_fn, group
     if fork is None:
-      fork = int(os.environ.get('MMT_FORK', FORK_DEFAULT))
+      fork = FORK_DEFAULT
     self.fork = int(fork)
     self._side = None
     self._fork_on = False  # decided after the first warm-up step (needs the model's stage handles)

@@ -34,7 +34,7 @@ def test_library_exports_every_declared_symbol_and_bindings_match():
     assert name in _lib.SIGNATURES, 'no ctypes signature for ' + name
     assert len(_lib.SIGNATURES[name][1]) == nargs, 'arity mismatch for ' + name
   assert set(_lib.SIGNATURES) == set(decl)
-  assert _lib.lib().mmt_abi_version() == 4
+  assert _lib.lib().mmt_abi_version() == 5
   # struct layouts agree with the C side (sizes are what the kernels are compiled against)
   assert ctypes.sizeof(_lib.MmtEpilogue) == 128  # + dot_src / lddot / dot_out (r04), live_rows_hint (r06)
   assert ctypes.sizeof(_lib.MmtPackItem) == 48
@@ -96,6 +96,26 @@ def test_gemm_tile_policy_is_a_function_of_shape_and_live_rows():
   out = subprocess.run([sys.executable, '-c', child, _lib.LIB_PATH, json.dumps(asked)], env=env, check=True,
                        stdout=subprocess.PIPE, text=True).stdout
   assert json.loads(out) == [select(*a) for a in asked]
+
+
+def test_engine_launch_sequence_ignores_the_environment():
+  """Which kernels a training step launches depends on the model and the batch only.  The library does not import getenv at
+  all (so no kernel file can read a switch), and a fresh process with the names of two removed switches set still has the
+  fused video front end on and still routes a 32-row text batch to the three-launch text-head kernels."""
+  from mmt_amd import _lib
+  syms = subprocess.run(['nm', '-D', '--undefined-only', _lib.LIB_PATH], check=True, stdout=subprocess.PIPE, text=True).stdout
+  imported = {line.split()[-1].split('@')[0] for line in syms.splitlines() if line.strip()}
+  assert len(imported) > 10  # (the table was read)
+  assert not imported & {'getenv', 'secure_getenv'}
+  child = ('import ctypes, json, sys\n'
+           'sys.path.insert(0, sys.argv[2])\n'
+           'from mmt_amd.model import CENet\n'
+           'fast = ctypes.CDLL(sys.argv[1]).mmt_text_heads_fast(32, 7, 512, 768)\n'
+           'print(json.dumps([CENet.front_fuse, fast]))')
+  env = dict(os.environ, MMT_FRONT_FUSE='0', MMT_TEXT_HEADS_V1='1')
+  out = subprocess.run([sys.executable, '-c', child, _lib.LIB_PATH, ROOT], env=env, check=True, stdout=subprocess.PIPE,
+                       text=True).stdout
+  assert json.loads(out.strip().splitlines()[-1]) == [True, 1]
 
 
 def test_product_path_refuses_cpu_tensors():

@@ -83,7 +83,7 @@ def test_signatures_of_the_new_exports_agree_with_the_header():
     for p, a in zip(params, args):
       assert (a is ctypes.c_void_p) == ('*' in p) and (a is ctypes.c_int) == (p.startswith('int ')), (name, p)
     assert hasattr(handle, name)
-  assert handle.mmt_abi_version() == 4
+  assert handle.mmt_abi_version() == 5
 
 
 def test_new_exports_gate_their_arguments_on_the_host():

@@ -1,6 +1,5 @@
-"""wgrad3.hip on configs[4]'s shapes (four weight gradients of a d = 1024 layer, 14 393 live rows): time per launch.  Builds
-with -DMMT_W3_LAB_NOREADS | -DMMT_W3_LAB_PLAINREADS | -DMMT_W3_LAB_NOMFMA added to the flags of mmt_amd/build.py switch
-parts of the loop off; results are then wrong, only the time is read.   MMT_HIP_LIB=... python tools/wgrad3_lab.py"""
+"""wgrad3.hip on configs[4]'s shapes (four weight gradients of a d = 1024 layer, 14 393 live rows): time per launch.
+MMT_HIP_LIB=... python tools/wgrad3_lab.py"""
 import os
 import sys
 
