@@ -683,6 +683,48 @@ int mmt_search_topk_groups_bf16(const uint16_t* q_hi, const uint16_t* q_lo, cons
 int mmt_search_merge_group_lists(const float* scores, const int64_t* groups, const int64_t* index, const int64_t* const* ids,
                                  int S, int NQ, int kin, int kout, float* out_scores, int64_t* out_groups, int64_t* out_items,
                                  void* stream);
+/* Query-set pooling (search_pool.hip): the queries are NS sets of C consecutive rows (1 <= C <= 64, NS * C < 2^31) --
+ * the captions of a video, the clips of a query video, a caption and its paraphrases -- and every scan answers per SET,
+ * on the pooled score, without the N_query x N_gallery matrix.  rw fp32 [NS * C]: row weights, finite; a row with
+ * rw == 0 takes no part.  Over the participating rows r0 < r1 < ... of a set, in row order, with score(r, g) the bits
+ * mmt_search_topk gives the pair:
+ *   mode 0 (mean): v = fl(rw[r0] * score(r0, g)), then v = fl(v + fl(rw[ri] * score(ri, g))) -- a rounded multiply, then
+ *                  a rounded add, never an fma, never reassociated (rw = 1 / C: model/model.py:826-831, 'avg');
+ *   mode 1 (max) : v = score(r0, g), then v = score(ri, g) where score(ri, g) > v (a plain compare; rw is a mask).
+ * v depends on the set's rows, their weights and the item only.  Query operands [NS * C] rows and gallery as the unpooled
+ * calls (fp32, or the bf16 hi / lo pair); subset nullable, words as above.
+ * mmt_search_topk_pooled / _bf16_pooled: per set the best min(k, NV) items by v under mmt_search_topk's order, scores /
+ *   index [NS][min(k, NV)] (slots without a candidate are not written, as mmt_search_topk_ex).  1 <= k <= 128.
+ *   Workspace: mmt_topk_pooled_workspace_keys(NS, C, NV, k) keys.
+ * mmt_search_thresholds_pooled / _bf16_pooled: targets int64 [NS][T] (outside 0 .. NV - 1 = none) -> thr fp32 [NS][T],
+ *   v(set, target) with the bits the top-k and count passes compute for that pair; NaN for none.  1 <= T <= 32.
+ * mmt_search_count_pooled / _bf16_pooled: thr fp32 [NS][T] -> greater / equal int32 [NS][T]: the allowed items whose v
+ *   is above / equal to the threshold (plain compares).  Workspace: mmt_count_pooled_workspace_ints(NS, C, NV, T) int32.
+ * The workspace sizes differ from the unpooled ones: a block holds 64 / C sets and the chunk rule counts blocks.
+ * Gates: MMT_ERR_ARG (a null pointer other than subset, NS < 1, C outside 1 .. 64, a mode other than 0 / 1, a size, k or
+ * T out of range, d % 4 / d % 8), MMT_ERR_ALIGN (query or gallery rows or subset words off a 16-byte boundary), before
+ * any launch.  Trusted, not checked: rw finite, every set has a row with rw != 0 (a set without one pools to 0). */
+int64_t mmt_topk_pooled_workspace_keys(int NS, int C, int NV, int k);
+int64_t mmt_count_pooled_workspace_ints(int NS, int C, int NV, int T);
+int mmt_search_topk_pooled(const float* qf, const float* qw, const float* gf, const float* gw, const float* rw, int NS, int C,
+                           int mode, int NV, int M, int d, int k, const uint32_t* subset, uint64_t* ws, float* scores,
+                           int64_t* index, void* stream);
+int mmt_search_topk_bf16_pooled(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                const float* gw, const float* rw, int NS, int C, int mode, int NV, int M, int d, int k,
+                                const uint32_t* subset, uint64_t* ws, float* scores, int64_t* index, void* stream);
+int mmt_search_thresholds_pooled(const float* qf, const float* qw, const float* gf, const float* gw, const float* rw, int NS,
+                                 int C, int mode, int NV, int M, int d, const int64_t* targets, int T, float* thr,
+                                 void* stream);
+int mmt_search_thresholds_bf16_pooled(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                      const float* gw, const float* rw, int NS, int C, int mode, int NV, int M, int d,
+                                      const int64_t* targets, int T, float* thr, void* stream);
+int mmt_search_count_pooled(const float* qf, const float* qw, const float* gf, const float* gw, const float* rw, int NS, int C,
+                            int mode, int NV, int M, int d, const float* thr, int T, const uint32_t* subset, int32_t* ws,
+                            int32_t* greater, int32_t* equal, void* stream);
+int mmt_search_count_bf16_pooled(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                 const float* gw, const float* rw, int NS, int C, int mode, int NV, int M, int d,
+                                 const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
+                                 int32_t* equal, void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

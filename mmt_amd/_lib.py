@@ -273,6 +273,20 @@ SIGNATURES = {
     'mmt_search_topk_groups_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
                                             c_vp, c_vp, c_vp, c_vp]),
     'mmt_search_merge_group_lists': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_topk_pooled_workspace_keys': (c_i64, [c_int, c_int, c_int, c_int]),
+    'mmt_count_pooled_workspace_ints': (c_i64, [c_int, c_int, c_int, c_int]),
+    'mmt_search_topk_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                       c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_topk_bf16_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_thresholds_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                             c_int, c_vp, c_vp]),
+    'mmt_search_thresholds_bf16_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                                  c_int, c_vp, c_int, c_vp, c_vp]),
+    'mmt_search_count_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_count_bf16_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                             c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

@@ -206,15 +206,8 @@ int tk_chunk(int NQ, int NV) {
   return chunk;
 }
 
-namespace {
-bool tk_args_ok(int NQ, int NV, int k) { return NQ > 0 && NV > 0 && k >= 1 && k <= TK_MAXK; }
-
-// LDS behind the slab / score-tile union: query weights, counts, thresholds, candidates ...
-size_t tk_state_lds(int k) { return TK_QW_BYTES + TK_Q * (4 + 8) + (size_t)TK_Q * (k + 64) * 8; }
-// ... and behind those, the masked kernels' exclusions [TK_Q][E]
-size_t tk_exclude_lds(int E) { return (size_t)TK_Q * E * 4; }
-size_t tk_select_lds(int k) { return (size_t)4 * (k + 64) * 8; }
-
+// The merge of the chunk lists behind every top-k entry point (declared in search_topk.h: search_pool.hip merges the
+// lists of its sets with it).
 int tk_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, float* scores, int64_t* index,
                     hipStream_t s) {
   constexpr int kMergeLdsMax = 64 * 1024;
@@ -224,6 +217,15 @@ int tk_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, f
                      stage, scores, index);
   return (int)hipGetLastError();
 }
+
+namespace {
+bool tk_args_ok(int NQ, int NV, int k) { return NQ > 0 && NV > 0 && k >= 1 && k <= TK_MAXK; }
+
+// LDS behind the slab / score-tile union: query weights, counts, thresholds, candidates ...
+size_t tk_state_lds(int k) { return TK_QW_BYTES + TK_Q * (4 + 8) + (size_t)TK_Q * (k + 64) * 8; }
+// ... and behind those, the masked kernels' exclusions [TK_Q][E]
+size_t tk_exclude_lds(int E) { return (size_t)TK_Q * E * 4; }
+size_t tk_select_lds(int k) { return (size_t)4 * (k + 64) * 8; }
 
 // The k = 128 footprint of the fused kernels is over the 64 KiB default.
 void tk_topk_lds_limits() {

@@ -121,33 +121,9 @@ __global__ __launch_bounds__(256) void rank_kernel(Args a) {
       // wave w owns rows 16w .. 16w + 15 for the whole block, so its counters need no barrier
       const bool live0 = g0 + lane < g_end && (MASK == TK_MASK_NONE || ((m0 >> lane) & 1ull));
       const bool live1 = g0 + 64 + lane < g_end && (MASK == TK_MASK_NONE || ((m1 >> lane) & 1ull));
-      for (int rr = 0; rr < TK_Q / 4; ++rr) {
-        const int row = wave * (TK_Q / 4) + rr;
-        if (row >= rows_live) break;
-        const float s0 = sS[row * TK_SLD + lane], s1 = sS[row * TK_SLD + 64 + lane];
-        const int mine = lane < T ? __float_as_int(sThr[row * T + lane]) : 0;
-        int ng = 0, ne = 0;
-        for (int t = 0; t < T; ++t) {
-          const float thr = __int_as_float(__builtin_amdgcn_readlane(mine, t));
-          const int cg = __popcll(__ballot(live0 && s0 > thr)) + __popcll(__ballot(live1 && s1 > thr));
-          const int ce = __popcll(__ballot(live0 && s0 == thr)) + __popcll(__ballot(live1 && s1 == thr));
-          if (lane == t) { ng = cg; ne = ce; }
-        }
-        if (lane < T) {
-          sCnt[2 * (row * T + lane)] += ng;
-          sCnt[2 * (row * T + lane) + 1] += ne;
-        }
-      }
+      tk_tile_count(sS, sThr, sCnt, T, rows_live, live0, live1, wave, lane);
     }
-    for (int rr = 0; rr < TK_Q / 4; ++rr) {
-      const int row = wave * (TK_Q / 4) + rr;
-      if (row >= rows_live) break;
-      if (lane < T) {
-        int32_t* dst = a.cnt + (((int64_t)(q0 + row) * T + lane) * a.n_chunks + chunk) * 2;
-        dst[0] = sCnt[2 * (row * T + lane)];
-        dst[1] = sCnt[2 * (row * T + lane) + 1];
-      }
-    }
+    tk_count_flush(sCnt, a.cnt, T, rows_live, q0, a.n_chunks, chunk, wave, lane);
   }
 }
 
@@ -163,6 +139,13 @@ __global__ __launch_bounds__(256) void rank_reduce_kernel(const int32_t* __restr
   }
   greater[i] = g;
   equal[i] = e;
+}
+
+// The chunk reduce behind every count entry point (declared in search_scan.h: search_pool.hip sums the counters of its
+// sets with it): cnt [n][n_chunks][2] -> greater [n], equal [n].
+int rk_reduce_launch(const int32_t* cnt, int64_t n, int n_chunks, int32_t* greater, int32_t* equal, hipStream_t s) {
+  hipLaunchKernelGGL(rank_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cnt, n, n_chunks, greater, equal);
+  return (int)hipGetLastError();
 }
 
 namespace {
@@ -211,10 +194,7 @@ int rk_launch_count(const Args& a, int32_t* greater, int32_t* equal, hipStream_t
     hipLaunchKernelGGL((rank_kernel<BF16, false, Args>), grid, dim3(256), lds, s, a);
   else if constexpr (!Args::kNorm)  // constexpr only so that the slice to RkArgs is not instantiated for NmRankArgs
     hipLaunchKernelGGL((rank_kernel<BF16, false, RkArgs>), grid, dim3(256), lds, s, (RkArgs)a);
-  const int64_t n = (int64_t)a.NQ * a.T;
-  hipLaunchKernelGGL(rank_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.cnt, n, a.n_chunks, greater,
-                     equal);
-  return (int)hipGetLastError();
+  return rk_reduce_launch(a.cnt, (int64_t)a.NQ * a.T, a.n_chunks, greater, equal, s);
 }
 
 // workspace (int32 units): thresholds [NQ][T] fp32, then (greater, equal) [NQ][T][n_chunks][2]

@@ -4,7 +4,8 @@
 // the two K loops (fp32 gallery on v_mfma_f32_32x32x2_f32, bf16 gallery on v_mfma_f32_32x32x16_bf16), the gated-denominator
 // epilogue and the querybank rewrite are composed in ONE place, tk_tile, so a pair has the same score bits on every path
 // by construction.  The subset gate of a tile (tk_tile_mask), the chunk rule and launch geometry (tk_chunk, tk_geometry),
-// the shape gate and the per-device dynamic-LDS limit (tk_lds_limits) are here once as well.
+// the shape gate and the per-device dynamic-LDS limit (tk_lds_limits) are here once as well, and so are the steps that
+// follow a tile on more than one path: the count step (tk_tile_count) and the query-set pooling (tk_tile_pool).
 //
 // Which gallery row a tile row / column holds is a functor `grow(r)`, r in 0 .. TK_G - 1 -> gallery row, or -1 for "none"
 // (zero-filled in registers, never read): g0 + r for a scan, a table lookup for the rank kernels' threshold pass.
@@ -205,6 +206,107 @@ __device__ __forceinline__ void tk_tile_norm(float* sS, const float* lse, float 
     sS[row * TK_SLD + col] = tk_mul_rn(beta, sS[row * TK_SLD + col]) - l;
 }
 
+// fl(a + b) as an instruction of its own, the partner of tk_mul_rn: a sum the optimiser can neither contract with the
+// multiply that feeds it nor reassociate.
+__device__ __forceinline__ float tk_add_rn(float a, float b) {
+  float r;
+  asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+#define TK_POOL_MEAN 0
+#define TK_POOL_MAX 1
+
+// Query-set pooling of one score tile in place (search_pool.hip only): the block's query rows are `sets` sets of C
+// consecutive rows (sets * C <= TK_Q), sRw [TK_Q] their row weights; a row whose weight is 0 takes no part.  Over the
+// participating rows r0 < r1 < ... of set s, in row order:
+//   mean: v = fl(rw[r0] * s_r0), then v = fl(v + fl(rw[ri] * s_ri))  -- a rounded multiply, then a rounded add
+//   max : v = s_r0, then v = s_ri where s_ri > v                      -- a plain compare: the first of equal values stays
+// and v lands in row s of the tile.  ONE thread per column (threads 0 .. TK_G - 1) walks the sets in ascending order: set
+// s reads rows s * C .. s * C + C - 1, all >= s, and then writes row s; the rows written before, 0 .. s - 1, are below
+// every row it reads, so no thread ever reads a pooled value back and no second buffer is needed.  The caller syncs
+// before the tile is read.  A set without a participating row (refused by the host) would give 0.
+__device__ __forceinline__ void tk_tile_pool(float* sS, const float* sRw, int C, int sets, int mode, int tid) {
+  if (tid >= TK_G) return;
+  // `step(v, have, w, x)`: the value after a participating row.  Rows go four at a time: their scores are read whether or
+  // not they take part (past the set's end the last row again, with weight 0) and the update is a select, so the four LDS
+  // reads are in flight together and the loop has no branch.
+  auto walk = [&](auto step) {
+    for (int s = 0; s < sets; ++s) {
+      const float* col = sS + s * C * TK_SLD + tid;
+      const float* wr = sRw + s * C;
+      float v = 0.f;
+      bool have = false;
+      for (int c = 0; c < C; c += 4) {
+        float w[4], x[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int cc = min(c + j, C - 1);
+          w[j] = wr[cc];
+          x[j] = col[cc * TK_SLD];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool part = c + j < C && w[j] != 0.f;
+          const float nv = step(v, have, w[j], x[j]);
+          v = part ? nv : v;
+          have = have || part;
+        }
+      }
+      sS[s * TK_SLD + tid] = v;
+    }
+  };
+  if (mode == TK_POOL_MEAN)
+    walk([](float v, bool have, float w, float x) {
+      const float p = tk_mul_rn(w, x);
+      return have ? tk_add_rn(v, p) : p;
+    });
+  else  // selected as integers: a float select may become v_max_f32, which treats NaN and the zeros differently
+    walk([](float v, bool have, float, float x) {
+      return __int_as_float(!have || x > v ? __float_as_int(x) : __float_as_int(v));
+    });
+}
+
+// The count step of one score tile (the count passes of search_rank.hip and search_pool.hip): wave w owns rows 16w .. 16w + 15
+// of the tile for the whole block, so its counters need no barrier.  Per row, lane t holds threshold t of sThr [.][T]; the
+// wave broadcasts one threshold at a time and counts `score > thr` / `score == thr` over the live columns (live0: column
+// `lane`, live1: column 64 + `lane`) with two ballots each -- plain float compares: -0 == +0, NaN counts for nothing --
+// and lane t adds the sums of threshold t to sCnt [.][T][2].
+__device__ __forceinline__ void tk_tile_count(const float* sS, const float* sThr, int* sCnt, int T, int rows_live, bool live0,
+                                              bool live1, int wave, int lane) {
+  for (int rr = 0; rr < TK_Q / 4; ++rr) {
+    const int row = wave * (TK_Q / 4) + rr;
+    if (row >= rows_live) break;
+    const float s0 = sS[row * TK_SLD + lane], s1 = sS[row * TK_SLD + 64 + lane];
+    const int mine = lane < T ? __float_as_int(sThr[row * T + lane]) : 0;
+    int ng = 0, ne = 0;
+    for (int t = 0; t < T; ++t) {
+      const float thr = __int_as_float(__builtin_amdgcn_readlane(mine, t));
+      const int cg = __popcll(__ballot(live0 && s0 > thr)) + __popcll(__ballot(live1 && s1 > thr));
+      const int ce = __popcll(__ballot(live0 && s0 == thr)) + __popcll(__ballot(live1 && s1 == thr));
+      if (lane == t) { ng = cg; ne = ce; }
+    }
+    if (lane < T) {
+      sCnt[2 * (row * T + lane)] += ng;
+      sCnt[2 * (row * T + lane) + 1] += ne;
+    }
+  }
+}
+
+// The block's counters sCnt [.][T][2] -> cnt [.][T][n_chunks][2] at its chunk; row0 = the block's first output row.
+__device__ __forceinline__ void tk_count_flush(const int* sCnt, int32_t* cnt, int T, int rows_live, int row0, int n_chunks,
+                                               int chunk, int wave, int lane) {
+  for (int rr = 0; rr < TK_Q / 4; ++rr) {
+    const int row = wave * (TK_Q / 4) + rr;
+    if (row >= rows_live) break;
+    if (lane < T) {
+      int32_t* dst = cnt + (((int64_t)(row0 + row) * T + lane) * n_chunks + chunk) * 2;
+      dst[0] = sCnt[2 * (row * T + lane)];
+      dst[1] = sCnt[2 * (row * T + lane) + 1];
+    }
+  }
+}
+
 // Column statistics of one score tile for the log-sum-exp over a bank of queries (search_norm.hip only): thread c < TK_G
 // takes column c and the tile's live rows 0 .. rows_live - 1 in ascending order: x = fl(beta * score), m = max x,
 // p = sum exp(x - m).  The order is fixed by the row number alone, so (m, p) is a function of the 64-row bank block, the
@@ -269,6 +371,9 @@ struct NmArgs {
 // Host side.  Gallery columns per block (search.hip): TK_CHUNK halved (down to one tile) while the launch would not fill
 // the chip.
 int tk_chunk(int NQ, int NV);
+
+// The chunk reduce of the count passes (search_rank.hip): cnt [n][n_chunks][2] summed in chunk order.
+int rk_reduce_launch(const int32_t* cnt, int64_t n, int n_chunks, int32_t* greater, int32_t* equal, hipStream_t s);
 
 inline int tk_n_chunks(int NQ, int NV) {
   const int chunk = tk_chunk(NQ, NV);

@@ -100,3 +100,7 @@ __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, in
     if (lane == 0) { sN[row] = n; sT[row] = thr; }
   }
 }
+
+// Host side (search.hip): the merge launch over the workspace of a chunk scan -- NQ rows of n_chunks sorted lists of k
+// keys -> the best kout per row.
+int tk_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, float* scores, int64_t* index, hipStream_t s);

@@ -104,6 +104,35 @@ appear: the slots left over hold (-inf, -1, -1).  It is not `search` plus a host
 would push other videos' best clips out of a list before anybody could remove them: the running top-k of the scan keeps the
 best k distinct groups, and the chunk and shard merges de-duplicate again (mmt_search_topk_groups,
 mmt_search_merge_group_lists).  ShardedVideoIndex.search_groups is bit-identical; a group may have members on several shards.
+
+    pool = index.pooling(set_size, num_sets, row_weights=None, mode='mean')     # QueryPooling, built once like a subset
+    pool.set_size, pool.num_sets, pool.num_rows, pool.mode, pool.weights, pool.device
+    scores, indices = index.search(q, qw, k=10, pooling=pool, subset=None)      # [num_sets, k']: one row per SET
+    greater, equal = index.rank_counts(q, qw, targets, pooling=pool)            # targets [num_sets] or [num_sets, T]
+    index.ranks(...), index.target_scores(...), index.threshold_counts(...)     # likewise
+
+The fifth question: the queries are SETS of rows with one answer per set -- the captions of a video (the reference's
+merge_caption_similiarities = 'avg', model/model.py:826-831: the mean of the captions' similarities), a query video cut into
+clips (max over the clips), a caption and its paraphrases (mean), "any of these captions" (max).  The score is not linear in
+the query -- its denominator sum_m qw[q][m] gw[g][m] depends on the pair -- so the rows cannot be averaged before the scan,
+and per-row top-k lists cannot be merged exactly (a set's best item need not be in any member's list): the pooling happens
+on the score tile, inside the kernel (mmt_search_topk_pooled, mmt_search_thresholds_pooled, mmt_search_count_pooled).  The
+queries are num_sets * set_size rows (either layout of `search`; the text layout (B, M, C, d) / (B, C, M) is sets of C
+already), set s is rows s * set_size .. s * set_size + set_size - 1, 1 <= set_size <= MAX_SET = 64.  Every row has a weight
+rw[r] (float32, finite; default float32(1 / set_size)); a row with rw[r] == 0 takes no part at all -- a padded caption --
+and every set has a row that does.  With s_r = score(r, g), the bits the plain scan gives the pair, and r0 < r1 < ... the
+participating rows of the set:
+    mode='mean': v = fl(rw[r0] * s_r0), then v = fl(v + fl(rw[ri] * s_ri))    a rounded multiply, then a rounded add:
+                                                                               never an fma, never reassociated
+    mode='max' : v = s_r0, then v = s_ri where s_ri > v                        a plain compare, the first of equals stays;
+                                                                               the weights act as a mask only
+v depends on the set's rows, their weights and the item -- not on the launch geometry, the set's place in its block or the
+shard that holds the item.  Ranking, ties and k' are `search`'s; a returned score has -0 as +0, `target_scores` returns the
+pooled bits as they are, and a target counts itself.  A pooling does not describe the stored items: it stays valid after
+`add`.  ShardedVideoIndex has the same surface: every shard sees all the query rows, so results are bit-identical to one
+VideoIndex.  Out of scope: pooling= does not combine with exclude= or norm=, and `search_groups` and `range_search` take no
+pooling (the gallery-side mean that video-to-text evaluation in 'avg' mode would need is no scan here either, so
+metric.retrieval_metrics_indexed stays as it is).
 """
 import math
 
@@ -115,6 +144,8 @@ from ._lib import check
 MAX_K = 128
 MAX_T = 32  # targets per query and launch of the rank kernels; wider target lists are sliced
 MAX_E = 32  # exclusions per query of a masked search
+MAX_SET = 64  # rows per query set of a pooled scan: one 64-row query block holds whole sets
+_POOL_MODES = {'mean': 0, 'max': 1}  # the `mode` of the pooled entry points
 _BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 bytes per element either way) + chunk lists
 _MAX_HITS = 1 << 27  # default cap of a range search's total: a guard against a mistyped threshold, not a tuned number
 _DTYPES = {torch.float32: 4, torch.bfloat16: 8}  # storage dtype -> multiple d must have (16-byte folded rows)
@@ -210,6 +241,23 @@ class ShardedGrouping:
     self.num_items, self.device = ids.shape[0], ids.device
 
 
+class QueryPooling:
+  """How the query rows of a pooled scan form sets (VideoIndex.pooling / ShardedVideoIndex.pooling): `num_sets` sets of
+  `set_size` consecutive rows, `num_rows` = num_sets * set_size; `weights` float32 [num_rows] on `device`, the row weights
+  (a row with weight 0 takes no part); `mode` 'mean' or 'max'.  It does not depend on the number of stored items."""
+
+  def __init__(self, set_size, num_sets, weights, mode):
+    self.set_size, self.num_sets, self.num_rows = set_size, num_sets, set_size * num_sets
+    self.weights, self.mode, self.device = weights, mode, weights.device
+    self._copies = {weights.device: weights}
+
+  def _on(self, device):
+    """The weights on a shard's device, copied once."""
+    if device not in self._copies:
+      self._copies[device] = self.weights.to(device)
+    return self._copies[device]
+
+
 def _count_groups(ids):
   """The number of distinct values of a non-empty id tensor: one torch.unique, whose size is the one wait for the device."""
   return int(torch.unique(ids).numel())
@@ -254,6 +302,11 @@ def _check_dynamic(dynamic, norm, who):
 def _pick(use, normed, plain):
   """Per query row: the normalised result where `use`, else the plain one (tensors of equal shape, rows first)."""
   return torch.where(use.reshape((-1,) + (1,) * (normed.dim() - 1)), normed, plain)
+
+
+def _result_rows(q, pooling):
+  """The rows of a scan's outputs: one per query, or with a pooling one per query set."""
+  return q.shape[0] if pooling is None else pooling.num_sets
 
 
 def _column_groups(src, outs, r0, r1):
@@ -359,8 +412,60 @@ class _Index:
     if lo < -1 or hi >= self.num_items:
       raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
 
-  def _scan_args(self, who, embds, weights, subset, norm, dynamic, exclude=None):
-    """The checks every scan shares once its own arguments have passed -> q, qw, whether the dynamic rule applies."""
+  def pooling(self, set_size, num_sets, row_weights=None, mode='mean'):
+    """The query sets of a pooled scan -> QueryPooling, built once like a subset and passed as pooling= to `search`,
+    `rank_counts`, `ranks`, `target_scores` and `threshold_counts`: the queries of such a call are num_sets * set_size rows,
+    set s is rows s * set_size .. s * set_size + set_size - 1 (1 <= set_size <= MAX_SET = 64), and the call answers per SET.
+    row_weights: float32 [num_sets * set_size] or [num_sets, set_size] on the index device, finite; a row whose weight
+    is 0 takes no part (a padded caption), and every set needs a row that does.  None = float32(1 / set_size) on every
+    row, the reference's 'avg' (model/model.py:826-831).  mode='mean': the weighted sum over the participating rows in
+    row order, each product and each sum rounded to fp32 on its own; mode='max': the largest score, the weights acting
+    as a mask only.  The checks cost one small reduction and one host sync.  A pooling does not describe the stored
+    items: it stays valid after `add`."""
+    for name, v in (('set_size', set_size), ('num_sets', num_sets)):
+      if isinstance(v, bool) or not isinstance(v, int):
+        raise ValueError('pooling: %s must be an int, got %r' % (name, v))
+    if not 1 <= set_size <= MAX_SET:
+      raise ValueError('pooling: set_size must lie in 1..%d, got %d' % (MAX_SET, set_size))
+    if num_sets < 0 or num_sets * set_size >= 2 ** 31:
+      raise ValueError('pooling: num_sets must be >= 0 with num_sets * set_size < 2^31, got %d' % num_sets)
+    if mode not in _POOL_MODES:
+      raise ValueError("pooling: mode must be 'mean' or 'max', got %r" % (mode,))
+    if row_weights is None:
+      w = torch.full((num_sets * set_size,), 1.0 / set_size, device=self.device, dtype=torch.float32)
+      return QueryPooling(set_size, num_sets, w, mode)
+    if not torch.is_tensor(row_weights) or row_weights.dtype != torch.float32:
+      raise ValueError('pooling: row_weights must be a float32 tensor, got %s' % (
+          row_weights.dtype if torch.is_tensor(row_weights) else type(row_weights).__name__))
+    if row_weights.device != self.device:
+      raise ValueError('pooling: row_weights must be on the index device %s, got %s' % (self.device, row_weights.device))
+    if tuple(row_weights.shape) not in ((num_sets * set_size,), (num_sets, set_size)):
+      raise ValueError('pooling: row_weights of shape (%d,) or (%d, %d) expected, got %s' % (
+          num_sets * set_size, num_sets, set_size, tuple(row_weights.shape)))
+    w = row_weights.reshape(-1).contiguous().clone()
+    if num_sets:
+      sets = w.view(num_sets, set_size)
+      finite, manned = (bool(v) for v in torch.stack([torch.isfinite(w).all(), (sets != 0).any(1).all()]).tolist())
+      if not finite:
+        raise ValueError('pooling: row_weights must be finite')
+      if not manned:
+        raise ValueError('pooling: every set needs a row with a weight other than 0')
+    return QueryPooling(set_size, num_sets, w, mode)
+
+  def _pooling(self, pooling, who, exclude=None, norm=None):
+    """Type and device of `pooling`, and what it does not combine with: all that can be said before the queries are known."""
+    if not isinstance(pooling, QueryPooling):
+      raise ValueError('%s: pooling must come from pooling(), got %s' % (who, type(pooling).__name__))
+    if pooling.device != self.device:
+      raise ValueError('%s: the pooling is on %s, the index on %s' % (who, pooling.device, self.device))
+    if exclude is not None or norm is not None:
+      raise ValueError('%s: pooling= does not combine with exclude= or norm=' % who)
+
+  def _scan_args(self, who, embds, weights, subset, norm, dynamic, exclude=None, pooling=None):
+    """The checks every scan shares once its own arguments have passed -> q, qw, whether the dynamic rule applies.  With
+    a pooling the query count must be its num_rows: nothing is scored otherwise."""
+    if pooling is not None:
+      self._pooling(pooling, who, exclude, norm)
     if subset is not None:
       self._subset(subset, who)
     if exclude is not None:
@@ -369,6 +474,9 @@ class _Index:
       self._norm(norm, who)
     dynamic = _check_dynamic(dynamic, norm, who)
     q, qw = self._queries(embds, weights)
+    if pooling is not None and q.shape[0] != pooling.num_rows:
+      raise ValueError('%s: %d queries but the pooling has %d rows (%d sets of %d)' % (
+          who, q.shape[0], pooling.num_rows, pooling.num_sets, pooling.set_size))
     return q, qw, dynamic
 
   def _use_norm(self, q, qw, subset, ex, norm):
@@ -410,7 +518,7 @@ class _Index:
       hubs = torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
     return self._hub_norm(b, bw, beta, hubs)
 
-  def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None):
+  def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None, pooling=None):
     """Queries (NQ, M, d) / (NQ, M), or the text layout (B, M, C, d) / (B, C, M) -> (scores [NQ, k'] float32,
     indices [NQ, k'] int64) on the device, k' = min(k, NV), best first.  subset (from this index's `subset`): only its
     items are candidates and k' = min(k, subset.count).  exclude: int64 [NQ] or [NQ, E <= 32] on the index device, values
@@ -419,18 +527,24 @@ class _Index:
     left gets score -inf and index -1 in the remaining slots.  norm (from this index's `hub_norm`): the ranking and the
     returned scores are those of score' (mmt_search_topk_norm); with a norm that has `hubs`, only the queries whose plain
     top-1 candidate is a hub are normalised and the others keep their plain result (dynamic=False normalises every query).
+    pooling (from `pooling`): the queries are pooling.num_sets sets of pooling.set_size rows and the outputs have one row
+    per SET: the k' best items by the set's pooled score (module docstring; mmt_search_topk_pooled), ranked and tied as
+    above; a returned score is the pooled value with -0 as +0.  pooling= does not combine with exclude= or norm=.
     ShardedVideoIndex: every shard searches its own items for its best min(k', its candidates), with its part of the
-    subset and the norm; the lists are copied to the primary and merged there in one launch."""
+    subset and the norm; the lists are copied to the primary and merged there in one launch.  With a pooling every shard
+    sees all query rows, so a pooled score has the same bits wherever the item is stored."""
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
       raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
     if self.num_items == 0:
       raise ValueError('search: the index holds no items')
-    q, qw, dynamic = self._scan_args('search', embds, weights, subset, norm, dynamic, exclude)
+    q, qw, dynamic = self._scan_args('search', embds, weights, subset, norm, dynamic, exclude, pooling)
+    if pooling is not None:
+      return self._search(q, qw, k, subset, None, None, pooling)
     ex = _exclusions(exclude, q.shape[0], self.num_items)
     out = self._search(q, qw, k, subset, ex, norm)
     return self._dynamic(dynamic, q, qw, subset, ex, norm, out, lambda: self._search(q, qw, k, subset, ex))
 
-  def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
+  def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None):
     """Queries as for `search`; targets [NQ] or [NQ, T] int64 on the index device, values -1 .. num_items - 1 ->
     (greater, equal), int32 of targets' shape: how many of the num_items stored items score above / exactly equal to item
     targets[q, t] for query q (the item itself is one of the equal ones); 0 / 0 where the target is -1.  The range of the
@@ -438,30 +552,37 @@ class _Index:
     items are counted; a target outside it is still scored but does not count itself, so its `equal` may be 0.  norm: the
     counts are those of score' -- the target's score' from the threshold pass, then the count pass against it
     (mmt_search_thresholds_norm, mmt_search_count_norm); with a norm that has `hubs` only the queries whose plain top-1
-    candidate is a hub, the others keep their plain counts (dynamic=False normalises every query).  ShardedVideoIndex: each
+    candidate is a hub, the others keep their plain counts (dynamic=False normalises every query).  pooling (from
+    `pooling`): targets [NS] or [NS, T], one row per SET; the counts are those of the set's pooled score -- the target's
+    pooled value from the threshold pass, then the count pass against it (mmt_search_thresholds_pooled,
+    mmt_search_count_pooled), so a target counts itself; not with norm=.  ShardedVideoIndex: each
     shard scores the targets it holds, the primary picks the owner's value per (query, target), each shard counts its
     items against those thresholds and the int32 counts are summed on the primary."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
-    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic)
-    nq, shape = q.shape[0], targets.shape
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic, None, pooling)
+    nq, shape = _result_rows(q, pooling), targets.shape
     if shape[0] != nq:
-      raise ValueError('ranks: %d queries but targets %s' % (nq, tuple(shape)))
+      raise ValueError('ranks: %d %s but targets %s' % (nq, 'queries' if pooling is None else 'query sets', tuple(shape)))
     if nq == 0:
       return tuple(torch.empty(shape, device=self.device, dtype=torch.int32) for _ in range(2))
     tg = targets.reshape(nq, -1).contiguous()
     self._target_range(tg)
+    if pooling is not None:
+      out = self._rank_counts(q, qw, tg, subset, None, pooling)
+      return out[0].reshape(shape), out[1].reshape(shape)
     out = self._rank_counts(q, qw, tg, subset, norm)
     out = self._dynamic(dynamic, q, qw, subset, None, norm, out, lambda: self._rank_counts(q, qw, tg, subset))
     return out[0].reshape(shape), out[1].reshape(shape)
 
-  def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None):
+  def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None):
     """The reference's tie-averaged 0-based rank (model/metric.py:90-121) of item targets[q, t] among the stored items for
     query q: greater + (equal - 1) / 2 from `rank_counts`, +inf where the target is -1.  float64 on the device, of
     targets' shape (float32 would not hold counts above 2^24).  subset: the rank among its items, +inf for a target that
-    is not one of them.  norm, dynamic: as `rank_counts` -- the rank under the querybank-normalised score."""
-    greater, equal = self.rank_counts(embds, weights, targets, subset=subset, norm=norm, dynamic=dynamic)
+    is not one of them.  norm, dynamic: as `rank_counts` -- the rank under the querybank-normalised score.  pooling: as
+    `rank_counts` -- one row per query set, the rank under the set's pooled score."""
+    greater, equal = self.rank_counts(embds, weights, targets, subset=subset, norm=norm, dynamic=dynamic, pooling=pooling)
     ranks = greater.double() + (equal.double() - 1) / 2
     none = targets < 0
     if subset is not None:
@@ -667,7 +788,8 @@ class VideoIndex(_Index):
 
   def _entry(self, op, variant=''):
     """The C entry point of a scan over this index's storage: op 'topk', 'topk_groups', 'rank', 'thresholds', 'count',
-    'range_count', 'range_fill' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions) or '_norm' -> (the function, its name)."""
+    'range_count', 'range_fill' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions), '_norm' or '_pooled' -> (the
+    function, its name)."""
     name = 'mmt_search_%s%s%s' % (op, '_bf16' if self.dtype == torch.bfloat16 else '', variant)
     return getattr(_lib.lib(), name), name
 
@@ -684,16 +806,22 @@ class VideoIndex(_Index):
     qf = _fold(q, qw)
     return (ops._p(qf), ops._p(qw), ops._p(self.folded), ops._p(self.weights)), qf
 
-  def _row_batches(self, nq, extra):
+  def _row_batches(self, nq, extra, pooling=None):
     """Row ranges of a scan: a multiple of 64 rows (the query block) whose folded rows (4 bytes per element, fp32 or the
-    bf16 hi + lo pair) and `extra` bytes of workspace per row stay within _BATCH_BYTES."""
+    bf16 hi + lo pair) and `extra` bytes of workspace per row stay within _BATCH_BYTES.  With a pooling a block is
+    64 // set_size whole sets, the batches are cut at whole blocks of whole sets and `extra` is per set."""
     per_row = self.num_experts * self.dim * 4 + extra
-    batch = max(64, (_BATCH_BYTES // per_row) // 64 * 64)
+    block = 64
+    if pooling is not None:
+      block = 64 // pooling.set_size * pooling.set_size
+      per_row = self.num_experts * self.dim * 4 + -(-extra // pooling.set_size)
+    batch = max(block, (_BATCH_BYTES // per_row) // block * block)
     return [(r0, min(nq, r0 + batch)) for r0 in range(0, nq, batch)]
 
-  def _batches(self, nq, t_max):
-    """Row ranges of the rank and range passes: a row's thresholds and chunk counters at full-size chunks."""
-    return self._row_batches(nq, 4 * t_max * (1 + 2 * -(-self.num_items // 4096)))
+  def _batches(self, nq, t_max, pooling=None):
+    """Row ranges of the rank and range passes: a row's (pooled: a set's) thresholds and chunk counters at full-size
+    chunks."""
+    return self._row_batches(nq, 4 * t_max * (1 + 2 * -(-self.num_items // 4096)), pooling)
 
   def _hub_norm(self, b, bw, beta, hubs):
     return HubNorm(self._col_lse(b, bw, beta), beta, b.shape[0], hubs)
@@ -715,9 +843,37 @@ class VideoIndex(_Index):
                  ops._p(lse if r1 == nb else None), ops._stream()), name)
     return lse
 
-  def _search(self, q, qw, k, subset, ex, norm=None):
+  def _pool_args(self, pooling, r0, r1):
+    """Rows r0 .. r1 - 1 of a pooled scan (whole sets) -> the entry points' (row weights, NS, C, mode) and the sets' range."""
+    c = pooling.set_size
+    return (ops._p(pooling._on(self.device)[r0:r1]), (r1 - r0) // c, c, _POOL_MODES[pooling.mode]), r0 // c, r1 // c
+
+  def _search_pooled(self, q, qw, k, subset, pooling):
+    """`search` with a pooling behind its checks -> (scores, indices) [num_sets, k'].  Nothing here waits for the device."""
+    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    k = min(k, nv if subset is None else subset.count)
+    scores = torch.empty(pooling.num_sets, k, device=self.device, dtype=torch.float32)
+    indices = torch.empty(pooling.num_sets, k, device=self.device, dtype=torch.int64)
+    if nq == 0:
+      return scores, indices
+    fn, name = self._entry('topk', '_pooled')
+    words = None if subset is None else subset.words
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._row_batches(nq, 8 * k * -(-nv // 4096), pooling):  # a set's chunk lists at full-size chunks
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        pool, s0, s1 = self._pool_args(pooling, r0, r1)
+        ws = torch.empty(_lib.lib().mmt_topk_pooled_workspace_keys(s1 - s0, pooling.set_size, nv, k), device=self.device,
+                         dtype=torch.int64)
+        check(fn(*operands, *pool, nv, m, d, k, ops._p(words), ops._p(ws), ops._p(scores[s0:s1]), ops._p(indices[s0:s1]),
+                 ops._stream()), name)
+    return scores, indices
+
+  def _search(self, q, qw, k, subset, ex, norm=None, pooling=None):
     """`search` behind its argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the index device, ex None or int64 [NQ, E]
-    there, norm None or a HubNorm of this index (every query normalised).  Nothing here waits for the device."""
+    there, norm None or a HubNorm of this index (every query normalised), pooling None or a QueryPooling of NQ rows (then
+    ex and norm are None).  Nothing here waits for the device."""
+    if pooling is not None:
+      return self._search_pooled(q, qw, k, subset, pooling)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     masked = subset is not None or ex is not None
     if masked:
@@ -747,11 +903,12 @@ class VideoIndex(_Index):
                  ops._stream()), name)
     return scores, indices
 
-  def _rank_counts(self, q, qw, tg, subset, norm=None):
+  def _rank_counts(self, q, qw, tg, subset, norm=None, pooling=None):
     """`rank_counts` behind its checks: tg int64 [NQ >= 1, T] on the index device -> (greater, equal) int32 [NQ, T].  Plain:
-    the threshold and the count pass in one call per batch (mmt_search_rank); with a norm: one after the other."""
-    if norm is not None:
-      return self._threshold_counts(q, qw, self._target_scores(q, qw, tg, norm), subset, norm)
+    the threshold and the count pass in one call per batch (mmt_search_rank); with a norm or a pooling (tg [num_sets, T]):
+    one after the other."""
+    if norm is not None or pooling is not None:
+      return self._threshold_counts(q, qw, self._target_scores(q, qw, tg, norm, pooling), subset, norm, pooling)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     greater = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
     equal = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
@@ -768,25 +925,50 @@ class VideoIndex(_Index):
                    ops._stream()), name)
     return greater, equal
 
-  def target_scores(self, embds, weights, targets, norm=None, dynamic=None):
+  def target_scores(self, embds, weights, targets, norm=None, dynamic=None, pooling=None):
     """Queries as for `search`; targets as for `rank_counts` -> float32 of targets' shape on the device:
     score(q, targets[q, t]) with the very bits `search` returns for that pair (the threshold pass of `rank_counts` on its
     own: mmt_search_thresholds), NaN where the target is -1.  norm (VideoIndex.hub_norm): score'(q, targets[q, t]), with
-    the bits `search(norm=)` returns; the dynamic rule as there, the plain top-1 taken over all items."""
+    the bits `search(norm=)` returns; the dynamic rule as there, the plain top-1 taken over all items.  pooling (from
+    `pooling`; not with norm=): targets [NS] or [NS, T], one row per query SET -> the set's pooled score of the target with
+    the bits the pooled scans compute for the pair, as they are (a -0 stays -0; mmt_search_thresholds_pooled)."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
-    q, qw, dynamic = self._scan_args('ranks', embds, weights, None, norm, dynamic)
-    if targets.shape[0] != q.shape[0]:
-      raise ValueError('ranks: %d queries but targets %s' % (q.shape[0], tuple(targets.shape)))
-    if q.shape[0]:
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, None, norm, dynamic, None, pooling)
+    nq = _result_rows(q, pooling)
+    if targets.shape[0] != nq:
+      raise ValueError('ranks: %d %s but targets %s' % (nq, 'queries' if pooling is None else 'query sets',
+                                                        tuple(targets.shape)))
+    if nq:
       self._target_range(targets)
+    if pooling is not None:
+      return self._target_scores(q, qw, targets, None, pooling)
     out = (self._target_scores(q, qw, targets, norm),)
     return self._dynamic(dynamic, q, qw, None, None, norm, out, lambda: (self._target_scores(q, qw, targets),))[0]
 
-  def _target_scores(self, q, qw, targets, norm=None):
+  def _target_scores_pooled(self, q, qw, targets, pooling):
+    """`target_scores` with a pooling behind its checks: targets [num_sets] or [num_sets, T]."""
+    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    tg = targets.reshape(pooling.num_sets, -1).contiguous()
+    thr = torch.empty(tg.shape, device=self.device, dtype=torch.float32)
+    if nq == 0:
+      return thr.reshape(targets.shape)
+    fn, name = self._entry('thresholds', '_pooled')
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._batches(nq, min(MAX_T, tg.shape[1]), pooling):
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        pool, s0, s1 = self._pool_args(pooling, r0, r1)
+        for tgs, (out,) in _column_groups(tg, (thr,), s0, s1):
+          check(fn(*operands, *pool, nv, m, d, ops._p(tgs), tgs.shape[1], ops._p(out), ops._stream()), name)
+    return thr.reshape(targets.shape)
+
+  def _target_scores(self, q, qw, targets, norm=None, pooling=None):
     """`target_scores` behind its checks; a target outside 0 .. num_items - 1 gives NaN; norm None or a HubNorm of this
-    index (every query normalised).  Nothing here waits for the device."""
+    index (every query normalised); pooling None or a QueryPooling of NQ rows (then norm is None).  Nothing here waits
+    for the device."""
+    if pooling is not None:
+      return self._target_scores_pooled(q, qw, targets, pooling)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     tg = targets.reshape(nq, -1).contiguous()
     thr = torch.empty(tg.shape, device=self.device, dtype=torch.float32)
@@ -801,12 +983,14 @@ class VideoIndex(_Index):
           check(fn(*operands, r1 - r0, nv, m, d, ops._p(tgs), tgs.shape[1], *extra, ops._p(out), ops._stream()), name)
     return thr.reshape(targets.shape)
 
-  def threshold_counts(self, embds, weights, thresholds, subset=None, norm=None, dynamic=None):
+  def threshold_counts(self, embds, weights, thresholds, subset=None, norm=None, dynamic=None, pooling=None):
     """Queries as for `search`; thresholds float32 [NQ] or [NQ, T] on the index device -> (greater, equal), int32 of
     thresholds' shape: how many stored items score above / exactly equal to thresholds[q, t] for query q (plain float
     compares; a NaN threshold counts nothing) -- the count pass of `rank_counts` against given values (mmt_search_count).
     Fed with `target_scores` it gives `rank_counts`.  subset: only its items are counted.  norm (VideoIndex.hub_norm): the
-    items' score' is what is compared (mmt_search_count_norm); the dynamic rule as in `rank_counts`."""
+    items' score' is what is compared (mmt_search_count_norm); the dynamic rule as in `rank_counts`.  pooling (from
+    `pooling`; not with norm=): thresholds [NS] or [NS, T], one row per query SET; the items' pooled score for the set is
+    what is compared (mmt_search_count_pooled)."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     if not torch.is_tensor(thresholds) or thresholds.dtype != torch.float32:
@@ -816,15 +1000,43 @@ class VideoIndex(_Index):
       raise ValueError('ranks: thresholds must be on the index device %s, got %s' % (self.device, thresholds.device))
     if thresholds.dim() not in (1, 2) or thresholds.dim() == 2 and thresholds.shape[1] < 1:
       raise ValueError('ranks: thresholds [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(thresholds.shape),))
-    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic)
-    if thresholds.shape[0] != q.shape[0]:
-      raise ValueError('ranks: %d queries but thresholds %s' % (q.shape[0], tuple(thresholds.shape)))
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic, None, pooling)
+    nq = _result_rows(q, pooling)
+    if thresholds.shape[0] != nq:
+      raise ValueError('ranks: %d %s but thresholds %s' % (nq, 'queries' if pooling is None else 'query sets',
+                                                           tuple(thresholds.shape)))
+    if pooling is not None:
+      return self._threshold_counts(q, qw, thresholds, subset, None, pooling)
     out = self._threshold_counts(q, qw, thresholds, subset, norm)
     return self._dynamic(dynamic, q, qw, subset, None, norm, out, lambda: self._threshold_counts(q, qw, thresholds, subset))
 
-  def _threshold_counts(self, q, qw, thresholds, subset, norm=None):
-    """`threshold_counts` behind its checks; norm None or a HubNorm of this index (every query normalised).  Nothing here
-    waits for the device."""
+  def _threshold_counts_pooled(self, q, qw, thresholds, subset, pooling):
+    """`threshold_counts` with a pooling behind its checks: thresholds [num_sets] or [num_sets, T]."""
+    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    thr = thresholds.reshape(pooling.num_sets, -1).contiguous()
+    greater = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
+    equal = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
+    if nq == 0:
+      return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
+    fn, name = self._entry('count', '_pooled')
+    words = None if subset is None else subset.words
+    t_max = min(MAX_T, thr.shape[1])
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._batches(nq, t_max, pooling):
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        pool, s0, s1 = self._pool_args(pooling, r0, r1)
+        ws = torch.empty(_lib.lib().mmt_count_pooled_workspace_ints(s1 - s0, pooling.set_size, nv, t_max),
+                         device=self.device, dtype=torch.int32)
+        for ts, (gs, es) in _column_groups(thr, (greater, equal), s0, s1):
+          check(fn(*operands, *pool, nv, m, d, ops._p(ts), ts.shape[1], ops._p(words), ops._p(ws), ops._p(gs), ops._p(es),
+                   ops._stream()), name)
+    return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
+
+  def _threshold_counts(self, q, qw, thresholds, subset, norm=None, pooling=None):
+    """`threshold_counts` behind its checks; norm None or a HubNorm of this index (every query normalised); pooling None
+    or a QueryPooling of NQ rows (then norm is None).  Nothing here waits for the device."""
+    if pooling is not None:
+      return self._threshold_counts_pooled(q, qw, thresholds, subset, pooling)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     thr = thresholds.reshape(nq, -1).contiguous()
     greater = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
@@ -1123,10 +1335,11 @@ class ShardedVideoIndex(_Index):
       parts.append(part)
     return ShardedHubNorm(parts, lse, beta, b.shape[0], hubs)
 
-  def _search(self, q, qw, k, subset, ex, norm=None):
+  def _search(self, q, qw, k, subset, ex, norm=None, pooling=None):
     """`search` behind its checks: q, qw on the primary, ex None or int64 [NQ, E] global numbers there, norm None or a
-    ShardedHubNorm of this index (every query normalised)."""
-    nq = q.shape[0]
+    ShardedHubNorm of this index (every query normalised), pooling None or a QueryPooling of NQ rows (then ex and norm
+    are None): every shard gets all the rows and returns one list per set."""
+    nq = _result_rows(q, pooling)
     kout = min(k, self.num_items if subset is None else subset.count)
     scores = torch.empty(nq, kout, device=self.device, dtype=torch.float32)
     indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
@@ -1142,7 +1355,7 @@ class ShardedVideoIndex(_Index):
       ex_s = None if ex is None else self._local(ex, s).to(sh.device)
       with torch.cuda.device(sh.device):
         part = sh.index._search(q.to(sh.device), qw.to(sh.device), kout, None if subset is None else subset.parts[s], ex_s,
-                                None if norm is None else norm.parts[s])
+                                None if norm is None else norm.parts[s], pooling)
       width = part[0].shape[1]
       st_scores[i, :, :width].copy_(part[0])
       st_index[i, :, :width].copy_(part[1])
@@ -1207,8 +1420,9 @@ class ShardedVideoIndex(_Index):
                                                     ops._stream()), 'mmt_search_merge_group_lists')
     return scores, groups, items
 
-  def _rank_counts(self, q, qw, tg, subset, norm=None):
-    """`rank_counts` behind its checks: tg int64 [NQ, T] global numbers on the primary -> (greater, equal) int32 [NQ, T]."""
+  def _rank_counts(self, q, qw, tg, subset, norm=None, pooling=None):
+    """`rank_counts` behind its checks: tg int64 [NQ, T] global numbers on the primary -> (greater, equal) int32 [NQ, T];
+    with a pooling (then norm is None) tg is [num_sets, T] and every shard gets all the rows."""
     live = self._live()
     queries = {}
     thr = torch.full(tg.shape, float('nan'), device=self.device, dtype=torch.float32)
@@ -1216,7 +1430,7 @@ class ShardedVideoIndex(_Index):
       local = self._local(tg, s)
       queries[s] = (q.to(sh.device), qw.to(sh.device))
       with torch.cuda.device(sh.device):
-        mine = sh.index._target_scores(*queries[s], local.to(sh.device), None if norm is None else norm.parts[s])
+        mine = sh.index._target_scores(*queries[s], local.to(sh.device), None if norm is None else norm.parts[s], pooling)
       thr = torch.where(local >= 0, mine.to(self.device), thr)
     greater = torch.zeros(tg.shape, device=self.device, dtype=torch.int32)
     equal = torch.zeros(tg.shape, device=self.device, dtype=torch.int32)
@@ -1225,7 +1439,8 @@ class ShardedVideoIndex(_Index):
       if subset is not None and part is None:
         continue  # no allowed item here: nothing to count
       with torch.cuda.device(sh.device):
-        gs, es = sh.index._threshold_counts(*queries[s], thr.to(sh.device), part, None if norm is None else norm.parts[s])
+        gs, es = sh.index._threshold_counts(*queries[s], thr.to(sh.device), part, None if norm is None else norm.parts[s],
+                                            pooling)
       greater += gs.to(self.device)
       equal += es.to(self.device)
     return greater, equal

@@ -56,7 +56,14 @@ index dtype (--gallery-dtype, both = the two indexes) with the items in groups o
 i // SIZE: a clip gallery stored video by video) and the same groups with the item order shuffled (members anywhere: every
 chunk list can hold any group, so the merge de-duplicates), beside the plain search(k = 10) of the same index -- the same
 scan with the plain running list, the yardstick.  --runs rounds, every variant once per round, interleaved; median and
-spread.  Default output profiles/search_groups_bench.json."""
+spread.  Default output profiles/search_groups_bench.json.
+
+--pooled C times the pooled search (VideoIndex.search(pooling=), k = 10, mean with weights 1 / C and max) per index dtype
+(--gallery-dtype, both = the two indexes) with the first NQ // C * C query rows as sets of C, beside the plain search(k = 10)
+of the same rows on the same index -- the same scan without the pool step and with C times the selection rows, the
+yardstick.  At S1 and S2 the materialised path is timed too: the NQ x NV matrix (mmt_sims_eval, the kernel of
+eval_similarity, which itself wants NQ = NV x captions), its mean over the sets in torch, then mmt_rows_topk.  --runs
+rounds, every variant once per round, interleaved; median and spread.  Default output profiles/search_pooled_bench.json."""
 import argparse
 import json
 import math
@@ -369,6 +376,82 @@ def groups_mode(q, qw, g, gw, flop, a):
   return row
 
 
+def materialised_pooled(q, qw, g, gw, c, k):
+  """The matrix path of the 'avg' caption mode: every row's scores, their mean over the sets of c rows, then the top k."""
+  nq, nv = q.shape[0], g.shape[0]
+  L = _lib.lib()
+  ws = torch.empty(L.mmt_sims_eval_workspace_floats(nq, nv, M, D), device=q.device)
+  sims = torch.empty(nq, nv, device=q.device)
+  _lib.check(L.mmt_sims_eval(ops._p(q), ops._p(g), ops._p(qw), ops._p(gw), nq, nv, M, D, ops._p(ws), ops._p(sims),
+                             ops._stream()), 'mmt_sims_eval')
+  del ws
+  avg = sims.view(nq // c, c, nv).mean(1)
+  del sims
+  tk = torch.empty(L.mmt_topk_workspace_keys(nq // c, nv, k), device=q.device, dtype=torch.int64)
+  scores = torch.empty(nq // c, k, device=q.device)
+  idx = torch.empty(nq // c, k, device=q.device, dtype=torch.int64)
+  _lib.check(L.mmt_rows_topk(ops._p(avg), nv, None, nq // c, nv, k, ops._p(tk), ops._p(scores), ops._p(idx), ops._stream()),
+             'mmt_rows_topk')
+  return scores, idx
+
+
+def pooled_mode(q, qw, g, gw, flop, a):
+  """search(pooling=) in both modes against the plain search of the same rows, per index dtype; at up to 25 M scores the
+  materialised mean as well."""
+  nv, c = g.shape[0], a.pooled
+  ns = q.shape[0] // c
+  q, qw = q[:ns * c].contiguous(), qw[:ns * c].contiguous()
+  flop = 2.0 * ns * c * nv * M * D   # the rows in use
+  dtypes = ('float32', 'bfloat16') if a.gallery_dtype == 'both' else (a.gallery_dtype,)
+  fns = {}
+  for n in dtypes:
+    index = VideoIndex.empty(nv, M, D, g.device, dtype=getattr(torch, n))
+    for at in range(0, nv, 8192):
+      index.add(g[at:at + 8192], gw[at:at + 8192])
+    for mode in ('mean', 'max'):
+      pool = index.pooling(c, ns, mode=mode)
+      fns['%s/search_pooled_%s' % (n, mode)] = lambda index=index, pool=pool: index.search(q, qw, k=K, pooling=pool)
+    fns[n + '/search_k10'] = lambda index=index: index.search(q, qw, k=K)
+  if ns * c * nv <= 25e6:
+    fns['materialised_mean'] = lambda: materialised_pooled(q, qw, g, gw, c, K)
+  ts = {n: [] for n in fns}
+  mem = {n: 0 for n in fns}
+  out = {}
+  for _ in range(a.runs):
+    for n, fn in fns.items():
+      t, _, m, out[n] = timed(fn, a.min_seconds)
+      ts[n].append(t)
+      mem[n] = max(mem[n], m)
+  row = {'set_size': c, 'num_sets': ns, 'rows': ns * c, 'flop': flop}
+  for n in fns:
+    med = float(np.median(ts[n]))
+    row[n] = dict(seconds_median=med, seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n],
+                  tflops_of_the_scan=flop / med / 1e12, peak_mem_growth_bytes=mem[n])
+  for n in dtypes:
+    plain = row[n + '/search_k10']
+    summary = {}
+    for mode in ('mean', 'max'):
+      r = row['%s/search_pooled_%s' % (n, mode)]
+      spread = max(r['seconds_spread'], plain['seconds_spread'])
+      summary[mode] = dict(over_search_k10=r['seconds_median'] / plain['seconds_median'], spread_seconds=spread,
+                           slower_than_search_k10_beyond_spread=bool(r['seconds_median'] - plain['seconds_median'] > spread))
+    # the best item of a set under max is the best item of one of its rows
+    top = out[n + '/search_k10'][1][:, 0].view(ns, c)
+    summary['max']['top_item_is_a_row_top_item'] = bool((top == out[n + '/search_pooled_max'][1][:, :1]).any(1).all())
+    if 'materialised_mean' in row:
+      mat = row['materialised_mean']
+      summary['mean']['materialised_over_pooled'] = mat['seconds_median'] / row[n + '/search_pooled_mean']['seconds_median']
+      summary['mean']['memory_over_materialised'] = (row[n + '/search_pooled_mean']['peak_mem_growth_bytes'] /
+                                                     max(1, mat['peak_mem_growth_bytes']))
+      if n == 'float32':
+        summary['mean']['rows_identical_to_materialised'] = float(
+            (out['materialised_mean'][1] == out[n + '/search_pooled_mean'][1]).all(1).float().mean())
+        summary['mean']['max_score_difference_to_materialised'] = float(
+            (out['materialised_mean'][0] - out[n + '/search_pooled_mean'][0]).abs().max())
+    row[n + '/summary'] = summary
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--shapes', default='S1,S2,S3')
@@ -393,6 +476,8 @@ def main():
                   'without range_search)')
   ap.add_argument('--groups', type=int, default=0, metavar='SIZE', help='time search_groups(k = 10) with contiguous and with '
                   'shuffled groups of SIZE items against search(k = 10)')
+  ap.add_argument('--pooled', type=int, default=0, metavar='C', help='time search(pooling=) with sets of C (1..64) rows, mean '
+                  'and max, against search(k = 10) of the same rows and, at S1 / S2, the materialised mean')
   ap.add_argument('--baseline-json', nargs='+', default=[], help='with --norm: default-mode results of another build; '
                   'with --range: --range --counts-only results of another build')
   ap.add_argument('--same-build-json', nargs='+', default=[], help='with --norm: default-mode results of this build')
@@ -412,6 +497,10 @@ def main():
     raise SystemExit('--groups wants SIZE >= 1 and no --ranks, --subset, --exclude, --shards, --norm, --range')
   if a.groups and a.out is None:
     a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_groups_bench.json')
+  if not 0 <= a.pooled <= 64 or a.pooled and (masked or a.ranks or a.shards or a.norm is not None or a.range or a.groups):
+    raise SystemExit('--pooled wants C in 1..64 and no --ranks, --subset, --exclude, --shards, --norm, --range, --groups')
+  if a.pooled and a.out is None:
+    a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_pooled_bench.json')
   if a.counts_only and not a.range:
     raise SystemExit('--counts-only goes with --range')
   if a.range and a.out is None and not a.counts_only:
@@ -453,6 +542,8 @@ def main():
                                 for name, row in other['shapes'].items()})
   if a.groups:
     res.update(mode='groups', group_size=a.groups, gallery_dtype=a.gallery_dtype, runs=a.runs, min_seconds=a.min_seconds)
+  if a.pooled:
+    res.update(mode='pooled', set_size=a.pooled, gallery_dtype=a.gallery_dtype, runs=a.runs, min_seconds=a.min_seconds)
   if masked:
     res.update(mode='subset', subset_fraction=a.subset, exclude=a.exclude, runs=a.runs, min_seconds=a.min_seconds)
   for name in a.shapes.split(','):
@@ -465,8 +556,9 @@ def main():
     qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
     flop = 2.0 * nq * nv * M * D
     row = {'NQ': nq, 'NV': nv, 'flop': flop}
-    if masked or a.ranks or a.norm is not None or a.range or a.groups or a.gallery_dtype == 'both':
+    if masked or a.ranks or a.norm is not None or a.range or a.groups or a.pooled or a.gallery_dtype == 'both':
       mode = (norm_mode if a.norm is not None else range_mode if a.range else groups_mode if a.groups else
+              pooled_mode if a.pooled else
               subset_mode if masked else ranks_mode if a.ranks else both_dtypes)
       row.update(mode(q, qw, g, gw, flop, a))
       res['shapes'][name] = row
