@@ -725,6 +725,51 @@ int mmt_search_count_bf16_pooled(const uint16_t* q_hi, const uint16_t* q_lo, con
                                  const float* gw, const float* rw, int NS, int C, int mode, int NV, int M, int d,
                                  const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
                                  int32_t* equal, void* stream);
+/* Item-set pooling (search_itemset.hip): the STORED items are NT sets of C consecutive items (1 <= C <= 128,
+ * NT * C < 2^31; set t is items t * C .. t * C + C - 1) -- the captions of a video in a caption index, the clips of a video
+ * in a clip gallery -- and every scan answers per SET, on the pooled score, without the N_query x N_item matrix.  iw fp32
+ * [NT * C]: item weights, finite; an item with iw == 0 takes no part.  Over the participating items g0 < g1 < ... of a
+ * set, in item order, with score(q, g) the bits mmt_search_topk gives the pair:
+ *   mode 0 (mean): v = fl(iw[g0] * score(q, g0)), then v = fl(v + fl(iw[gi] * score(q, gi))) -- a rounded multiply, then
+ *                  a rounded add, never an fma, never reassociated (iw = 1 / C: model/model.py:826-831 on the gallery axis);
+ *   mode 1 (max) : v = score(q, g0), then v = score(q, gi) where score(q, gi) > v (a plain compare; iw is a mask).
+ * v depends on the query row, the set's items and their weights only.  Query operands [NQ] rows and gallery [NT * C] rows
+ * as the unpooled calls (fp32, or the bf16 hi / lo pair); indices, targets and the subset bitmap (nullable, words as
+ * above, 4 per 128 SETS) are in set numbers.
+ * mmt_search_topk_itemsets / _bf16_itemsets: per query the best min(k, NT) sets by v under mmt_search_topk's order, scores /
+ *   index [NQ][min(k, NT)] (slots without a candidate are not written, as mmt_search_topk_ex).  1 <= k <= 128.
+ *   Workspace: mmt_topk_itemsets_workspace_keys(NQ, NT, C, k) keys.
+ * mmt_search_thresholds_itemsets / _bf16_itemsets: targets int64 [NQ][T] (outside 0 .. NT - 1 = none) -> thr fp32 [NQ][T],
+ *   v(query, target set) with the bits the top-k and count passes compute for that pair; NaN for none.  1 <= T <= 32.
+ * mmt_search_count_itemsets / _bf16_itemsets: thr fp32 [NQ][T] -> greater / equal int32 [NQ][T]: the allowed sets whose v
+ *   is above / equal to the threshold (plain compares).  Workspace: mmt_count_itemsets_workspace_ints(NQ, NT, C, T) int32.
+ * The workspace sizes differ from the unpooled ones: a 128-column tile holds 128 / C whole sets and a chunk is a whole
+ * number of tiles (the unpooled chunk rule on 128 * ceil(NT / (128 / C)) columns); at C = 1 they are the unpooled sizes.
+ * Gates: MMT_ERR_ARG (a null pointer other than subset, NQ or NT < 1, C outside 1 .. 128, NT * C >= 2^31, a mode other
+ * than 0 / 1, a size, k or T out of range, d % 4 / d % 8), MMT_ERR_ALIGN (query or gallery rows or subset words off a
+ * 16-byte boundary), before any launch.  Trusted, not checked: iw finite, every set has an item with iw != 0 (a set
+ * without one pools to 0). */
+int64_t mmt_topk_itemsets_workspace_keys(int NQ, int NT, int C, int k);
+int64_t mmt_count_itemsets_workspace_ints(int NQ, int NT, int C, int T);
+int mmt_search_topk_itemsets(const float* qf, const float* qw, const float* gf, const float* gw, const float* iw, int NQ,
+                             int NT, int C, int mode, int M, int d, int k, const uint32_t* subset, uint64_t* ws,
+                             float* scores, int64_t* index, void* stream);
+int mmt_search_topk_bf16_itemsets(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                  const float* gw, const float* iw, int NQ, int NT, int C, int mode, int M, int d, int k,
+                                  const uint32_t* subset, uint64_t* ws, float* scores, int64_t* index, void* stream);
+int mmt_search_thresholds_itemsets(const float* qf, const float* qw, const float* gf, const float* gw, const float* iw,
+                                   int NQ, int NT, int C, int mode, int M, int d, const int64_t* targets, int T, float* thr,
+                                   void* stream);
+int mmt_search_thresholds_bf16_itemsets(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                        const float* gw, const float* iw, int NQ, int NT, int C, int mode, int M, int d,
+                                        const int64_t* targets, int T, float* thr, void* stream);
+int mmt_search_count_itemsets(const float* qf, const float* qw, const float* gf, const float* gw, const float* iw, int NQ,
+                              int NT, int C, int mode, int M, int d, const float* thr, int T, const uint32_t* subset,
+                              int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
+int mmt_search_count_bf16_itemsets(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                   const float* gw, const float* iw, int NQ, int NT, int C, int mode, int M, int d,
+                                   const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
+                                   int32_t* equal, void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

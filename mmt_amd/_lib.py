@@ -287,6 +287,20 @@ SIGNATURES = {
                                         c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_search_count_bf16_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
                                              c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_topk_itemsets_workspace_keys': (c_i64, [c_int, c_int, c_int, c_int]),
+    'mmt_count_itemsets_workspace_ints': (c_i64, [c_int, c_int, c_int, c_int]),
+    'mmt_search_topk_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                         c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_topk_bf16_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                              c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_thresholds_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                               c_int, c_vp, c_vp]),
+    'mmt_search_thresholds_bf16_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                                    c_int, c_vp, c_int, c_vp, c_vp]),
+    'mmt_search_count_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int,
+                                          c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_count_bf16_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                               c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

@@ -5,7 +5,8 @@
 // epilogue and the querybank rewrite are composed in ONE place, tk_tile, so a pair has the same score bits on every path
 // by construction.  The subset gate of a tile (tk_tile_mask), the chunk rule and launch geometry (tk_chunk, tk_geometry),
 // the shape gate and the per-device dynamic-LDS limit (tk_lds_limits) are here once as well, and so are the steps that
-// follow a tile on more than one path: the count step (tk_tile_count) and the query-set pooling (tk_tile_pool).
+// follow a tile on more than one path: the count step (tk_tile_count), the query-set pooling (tk_tile_pool) and the item-set
+// pooling (tk_tile_pool_items, with the unaligned subset window tk_tile_mask_window).
 //
 // Which gallery row a tile row / column holds is a functor `grow(r)`, r in 0 .. TK_G - 1 -> gallery row, or -1 for "none"
 // (zero-filled in registers, never read): g0 + r for a scan, a table lookup for the rank kernels' threshold pass.
@@ -267,6 +268,56 @@ __device__ __forceinline__ void tk_tile_pool(float* sS, const float* sRw, int C,
     });
 }
 
+// Item-set pooling of one score tile in place (search_itemset.hip only), tk_tile_pool along the other axis: the tile's
+// columns are `sets` sets of C consecutive columns (sets * C <= TK_G), sIw [TK_G] their item weights (16-byte aligned); a
+// column whose weight is 0 takes no part.  Over the participating columns g0 < g1 < ... of set s, in column order, the
+// value is tk_tile_pool's (mean: a rounded multiply, then a rounded add; max: a plain compare on the integer bits), and it
+// lands in column s of the row.  ONE thread per row (threads 0 .. TK_Q - 1: one wave) walks its row left to right: when it
+// has consumed n columns it has finished floor(n / C) <= n sets, so every column it has written, 0 .. floor(n / C) - 1, is
+// below every column it has yet to read, n .. sets * C - 1: no thread ever reads a pooled value back, rows do not meet, and
+// no second buffer is needed.  (A split of one row's sets over several threads would not do: set s reads columns up to
+// s * C + C - 1, into the columns a thread with higher sets writes.)  The row is read four columns at a time -- an aligned
+// 16-byte read, the whole of which is in registers before the thread writes anything at or beyond its first column: with
+// the 132-float row pitch eight rows cover the 32 banks, so the reads are conflict-free where 64 single-column reads of 64
+// rows would meet on 8 banks; the `sets` single-column writes of a row do meet there.  The caller syncs before the tile is
+// read.  A set without a participating column (refused by the host) would give 0.
+__device__ __forceinline__ void tk_tile_pool_items(float* sS, const float* sIw, int C, int sets, int mode, int tid) {
+  if (tid >= TK_Q) return;
+  float* row = sS + tid * TK_SLD;
+  const int cols = sets * C;
+  auto walk = [&](auto step) {
+    float v = 0.f;
+    bool have = false;
+    int pos = 0, s = 0;  // wave-uniform: the place inside the set, the set
+    for (int c = 0; c < cols; c += 4) {
+      const f32x4 x = *(const f32x4*)(row + c), w = *(const f32x4*)(sIw + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (c + j >= cols) break;
+        const bool part = w[j] != 0.f;
+        const float nv = step(v, have, w[j], x[j]);
+        v = part ? nv : v;
+        have = have || part;
+        if (++pos == C) {
+          row[s++] = v;
+          pos = 0;
+          v = 0.f;
+          have = false;
+        }
+      }
+    }
+  };
+  if (mode == TK_POOL_MEAN)
+    walk([](float v, bool have, float w, float x) {
+      const float p = tk_mul_rn(w, x);
+      return have ? tk_add_rn(v, p) : p;
+    });
+  else  // selected as integers, as in tk_tile_pool
+    walk([](float v, bool have, float, float x) {
+      return __int_as_float(!have || x > v ? __float_as_int(x) : __float_as_int(v));
+    });
+}
+
 // The count step of one score tile (the count passes of search_rank.hip and search_pool.hip): wave w owns rows 16w .. 16w + 15
 // of the tile for the whole block, so its counters need no barrier.  Per row, lane t holds threshold t of sThr [.][T]; the
 // wave broadcasts one threshold at a time and counts `score > thr` / `score == thr` over the live columns (live0: column
@@ -350,6 +401,26 @@ __device__ __forceinline__ bool tk_tile_mask(const uint32_t* subset, int g0, uin
   const u32x4 w = *(const u32x4*)(subset + (g0 >> 5));
   m0 = w[0] | (uint64_t)w[1] << 32;
   m1 = w[2] | (uint64_t)w[3] << 32;
+  return m0 | m1;
+}
+
+// The subset gate of a tile whose first column stands for number t0 of the bitmap, t0 any value (search_itemset.hip: a
+// tile's sets start wherever the tile before ended): bits t0 .. t0 + n - 1 of the bitmap (n <= 128 live columns) come from
+// up to five block-uniform words, funnel-shifted by t0 & 31; a word at or past n_words (the bitmap's length: 4 words per
+// 128 numbers) is not read.  m0 / m1 as tk_tile_mask, bits n .. 127 cleared, so false = none of the tile's own columns is
+// allowed.
+__device__ __forceinline__ bool tk_tile_mask_window(const uint32_t* subset, int n_words, int t0, int n, uint64_t& m0,
+                                                    uint64_t& m1) {
+  const int w0 = t0 >> 5, sh = t0 & 31;
+  uint32_t w[5], o[4];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) w[i] = w0 + i < n_words ? subset[w0 + i] : 0u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) o[i] = (uint32_t)((((uint64_t)w[i + 1] << 32) | w[i]) >> sh);
+  m0 = o[0] | (uint64_t)o[1] << 32;
+  m1 = o[2] | (uint64_t)o[3] << 32;
+  if (n < 64) { m0 &= (1ull << n) - 1ull; m1 = 0; }
+  else if (n < 128) m1 &= (1ull << (n - 64)) - 1ull;
   return m0 | m1;
 }
 

@@ -6,7 +6,8 @@ never leaves HBM -- only the n rank values are copied to the host) or a numpy ar
 `retrieval_metrics(...)` goes one step further and also builds the N_text x N_video similarity on the device from
 the gathered embeddings (the reference does both on the CPU: trainer/trainer.py:396-447).  SURVEY.md section 8f.1.
 `retrieval_metrics_indexed(...)` gives the same metrics from exact rank counts over a search.VideoIndex, without the
-matrix: for eval sets whose N_text x N_video similarity does not fit.
+matrix: for eval sets whose N_text x N_video similarity does not fit; caption_mode='avg' gives the reference's merged-caption
+evaluation the same way (query-set pooling for text-to-video, item-set pooling for video-to-text).
 """
 import numpy as np
 import torch
@@ -117,7 +118,8 @@ def v2t_targets(query_masks, num_videos, captions_per_video):
 
 
 def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, query_masks=None, dtype=torch.float32,
-                              video_subset=None, devices=None, text_bank=None, video_bank=None, beta=None):
+                              video_subset=None, devices=None, text_bank=None, video_bank=None, beta=None,
+                              caption_mode='indep'):
   """`retrieval_metrics` (same arguments, same result dict and keys) without the N_text x N_video matrix: the rank of every
   ground truth comes from search.VideoIndex.ranks, so no buffer grows with N_text * N_video.  t2v: an index of the videos
   queried with the real captions, the target of caption row b*C + c being video b.  v2t: an index of the real captions
@@ -131,8 +133,21 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
   ranking on devices[0]; the result is the same, bit for bit.
   text_bank / video_bank ((embds, weights) pairs in either query layout of VideoIndex.search) with beta (a float > 0):
   querybank hubness normalisation (VideoIndex.hub_norm) -- a bank of text queries re-scores the t2v ranking over the video
-  index, a bank of videos the v2t ranking over the caption index; either may be given alone."""
+  index, a bank of videos the v2t ranking over the caption index; either may be given alone.
+  caption_mode: 'indep' (every caption a query of its own, as above) or 'avg' (the reference's
+  merge_caption_similiarities = 'avg', model/model.py:826-831: a video's C captions answer as one, on the mean of their
+  similarities) -- then the result is what t2v_metrics / v2t_metrics give on the B x B matrix of those means.  t2v: the
+  video index is queried with the captions under VideoIndex.pooling(C, B), the target of set b being video b.  v2t: an
+  index of all B * C captions in row order b*C + c carries VideoIndex.item_pooling(C) with the default weights (the
+  reference's mean includes every caption) and is queried with the videos, the target of video b being set b.
+  video_subset and devices work as above (the sharded caption index is filled so that every set stays whole on one
+  shard); query_masks, text_bank and video_bank with 'avg' raise ValueError: the reference gives masked captions no
+  meaning in this mode, and pooling does not combine with a norm."""
   from .search import ShardedVideoIndex, VideoIndex
+  if caption_mode not in ('indep', 'avg'):
+    raise ValueError("retrieval_metrics_indexed: caption_mode must be 'indep' or 'avg', got %r" % (caption_mode,))
+  if caption_mode == 'avg' and (query_masks is not None or text_bank is not None or video_bank is not None):
+    raise ValueError("retrieval_metrics_indexed: caption_mode='avg' does not combine with query_masks, text_bank or video_bank")
   if (text_bank is not None or video_bank is not None) and beta is None:
     raise ValueError('retrieval_metrics_indexed: a bank needs beta')
   for bank in (text_bank, video_bank):
@@ -175,6 +190,9 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
     if bank is None:
       return None
     return index.hub_norm(*(_as_cuda_f32(x).to(vid.device) for x in bank), beta)
+  if caption_mode == 'avg':
+    return _metrics_avg(make_index, devices, vid, vw, txt4.permute(0, 2, 1, 3).reshape(b * c, m, d).contiguous(),
+                        tw.contiguous(), c, cut, dtype)
   rows = torch.from_numpy(np.flatnonzero(valid)).to(vid.device)
   txt = txt4.permute(0, 2, 1, 3).reshape(b * c, m, d)[rows].contiguous()      # the real captions, rows b*C + c in order
   tw = tw[rows].contiguous()
@@ -199,6 +217,38 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
   captions = make_index(txt, tw, dtype=dtype)
   ranks = captions.ranks(vid, vw, torch.from_numpy(targets).to(vid.device), norm=normaliser(captions, video_bank))
   cols = ranks.min(dim=1).values.cpu().numpy()
+  out['v2t_metrics'] = dict(cols2metrics(cols, cols.size), cols=cols)
+  return out
+
+
+def _metrics_avg(make_index, devices, vid, vw, txt, tw, c, cut, dtype):
+  """`retrieval_metrics_indexed` in 'avg' mode behind its checks: vid (B, M, d) / vw (B, M), txt (B*C, M, d) / tw (B*C, M)
+  in row order b*C + c, all on one device; cut None or a bool numpy mask [B]."""
+  from .search import ShardedVideoIndex
+  b, m, d = vid.shape
+  dev = vid.device
+  if cut is None:
+    mine = torch.arange(b, device=dev)
+  else:
+    mine = torch.from_numpy(np.flatnonzero(cut)).to(dev)
+  cut_d = None if cut is None else torch.from_numpy(cut).to(dev)
+  nb = mine.shape[0]
+  videos = make_index(vid, vw, dtype=dtype)
+  sets = txt.view(b, c, m, d)[mine].reshape(nb * c, m, d)
+  cols = videos.ranks(sets, tw.view(b, c, m)[mine].reshape(nb * c, m), mine, pooling=videos.pooling(c, nb),
+                      subset=None if cut is None else videos.subset(cut_d)).cpu().numpy()
+  del videos
+  out = {'t2v_metrics': dict(cols2metrics(cols, cols.size), cols=cols)}
+  if devices is None:
+    captions = make_index(txt, tw, dtype=dtype)
+  else:  # every shard's capacity a multiple of C, filled in pieces of whole sets that fit one shard: the sets stay whole
+    per_shard = -(-b // len(devices)) * c
+    captions = ShardedVideoIndex.empty(per_shard * len(devices), m, d, devices, dtype=dtype)
+    for r0 in range(0, b * c, per_shard):
+      captions.add(txt[r0:r0 + per_shard], tw[r0:r0 + per_shard])
+  ip = captions.item_pooling(c)
+  cols = captions.ranks(vid[mine], vw[mine], mine, item_pooling=ip,
+                        subset=None if cut is None else ip.subset(cut_d)).cpu().numpy()
   out['v2t_metrics'] = dict(cols2metrics(cols, cols.size), cols=cols)
   return out
 

@@ -131,8 +131,36 @@ shard that holds the item.  Ranking, ties and k' are `search`'s; a returned scor
 pooled bits as they are, and a target counts itself.  A pooling does not describe the stored items: it stays valid after
 `add`.  ShardedVideoIndex has the same surface: every shard sees all the query rows, so results are bit-identical to one
 VideoIndex.  Out of scope: pooling= does not combine with exclude= or norm=, and `search_groups` and `range_search` take no
-pooling (the gallery-side mean that video-to-text evaluation in 'avg' mode would need is no scan here either, so
-metric.retrieval_metrics_indexed stays as it is).
+pooling.
+
+    ip = index.item_pooling(set_size, item_weights=None, mode='mean')           # ItemPooling, built once like a subset
+    ip.set_size, ip.num_sets, ip.num_items, ip.mode, ip.weights, ip.device
+    scores, sets = index.search(q, qw, k=10, item_pooling=ip, subset=ip.subset(allowed_sets))   # [NQ, k']: SET numbers
+    index.rank_counts(...), index.ranks(...), index.target_scores(...), index.threshold_counts(...)   # likewise
+
+The sixth question, the fifth along the other axis: the STORED items are sets with one answer per set -- an index of
+captions, C per video, queried with a video for "the k videos whose captions match best on average" (video-to-text in the
+reference's 'avg' mode), a clip gallery ranked by the mean, not the best, of each video's clips.  `search_groups` collapses
+a gallery by its best member; it cannot give a mean and gives no ranks.  The denominator of the score depends on the pair,
+so the C items of a set cannot be averaged into one when the index is built, and per-item top-k lists cannot be merged into
+set means: the pooling happens on the score tile (mmt_search_topk_itemsets, mmt_search_thresholds_itemsets,
+mmt_search_count_itemsets).  The stored items are num_items / set_size sets, set t is items t * set_size .. t * set_size +
+set_size - 1, 1 <= set_size <= MAX_ITEM_SET = 128 (one 128-column tile holds whole sets), num_items % set_size == 0.
+Every item has a weight iw[g] (float32, finite; default float32(1 / set_size)); an item with iw[g] == 0 takes no part and
+every set has an item that does.  With s_g = score(q, g), the bits the plain scan gives the pair, and g0 < g1 < ... the
+participating items of the set in item order, the value v is `pooling`'s: 'mean' a rounded multiply, then a rounded add,
+never an fma, never reassociated; 'max' a plain compare, the first of equals stays, the weights a mask.  v depends on the
+query row, the set's items and their weights -- not on the launch geometry, the set's place in its tile, the chunking or
+the shard.  Indices, targets (-1 .. num_sets - 1), subset= (from ip.subset: an IndexSubset over set numbers) and k' are in
+set numbers; ranking and ties are `search`'s; a returned score has -0 as +0, `target_scores` returns the pooled bits as
+they are, and a target counts itself; a target set outside the subset is still pooled and does not count itself.  An item
+pooling describes the num_items of its moment: after a further `add` it is refused.  item_pooling= does not combine with
+pooling=, exclude= or norm=, and `search_groups` and `range_search` do not take it.  ShardedVideoIndex.item_pooling is
+accepted when every set is stored whole on one shard, in order, from a local item number that is a multiple of set_size
+(`.empty` with a per-shard capacity that is a multiple of set_size, then `add` in pieces of whole sets that fit one shard);
+each shard pools its own sets and the lists are merged through local-set -> global-set tables, bit-identical to one
+VideoIndex.  metric.retrieval_metrics_indexed(caption_mode='avg') builds the reference's 'avg' evaluation on `pooling`
+(text-to-video) and `item_pooling` (video-to-text).
 """
 import math
 
@@ -145,6 +173,7 @@ MAX_K = 128
 MAX_T = 32  # targets per query and launch of the rank kernels; wider target lists are sliced
 MAX_E = 32  # exclusions per query of a masked search
 MAX_SET = 64  # rows per query set of a pooled scan: one 64-row query block holds whole sets
+MAX_ITEM_SET = 128  # items per stored set of an item-pooled scan: one 128-column tile holds whole sets
 _POOL_MODES = {'mean': 0, 'max': 1}  # the `mode` of the pooled entry points
 _BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 bytes per element either way) + chunk lists
 _MAX_HITS = 1 << 27  # default cap of a range search's total: a guard against a mistyped threshold, not a tuned number
@@ -258,6 +287,133 @@ class QueryPooling:
     return self._copies[device]
 
 
+def _mask_of(items, n, device, what='items'):
+  """The checks of a subset of n numbered things -> (the set as a bool mask [n] of its own, the number allowed)."""
+  if not torch.is_tensor(items) or items.dtype not in (torch.bool, torch.int64):
+    raise ValueError('subset: %s must be a bool or int64 tensor, got %s' % (
+        what, items.dtype if torch.is_tensor(items) else type(items).__name__))
+  if items.device != device:
+    raise ValueError('subset: %s must be on the index device %s, got %s' % (what, device, items.device))
+  if items.dtype == torch.bool:
+    if tuple(items.shape) != (n,):
+      raise ValueError('subset: a bool mask of shape (%d,) expected, got %s' % (n, tuple(items.shape)))
+    mask = items.contiguous().clone()
+  else:
+    ids = items.reshape(-1)
+    if ids.numel() == 0:
+      raise ValueError('subset: no item allowed')
+    lo, hi = (int(v) for v in torch.aminmax(ids))
+    if lo < 0 or hi >= n:
+      raise ValueError('subset: %s must lie in 0 .. %d, got %d .. %d' % (what, n - 1, lo, hi))
+    mask = torch.zeros(n, device=device, dtype=torch.bool).index_fill_(0, ids, True)
+  count = int(mask.sum())
+  if count == 0:
+    raise ValueError('subset: no item allowed')
+  return mask, count
+
+
+class ItemPooling:
+  """How the stored items of an item-pooled scan form sets (VideoIndex.item_pooling): `num_sets` sets of `set_size`
+  consecutive items, `num_items` = num_sets * set_size, the index size it was built for; `weights` float32 [num_items] on
+  `device`, the item weights (an item with weight 0 takes no part); `mode` 'mean' or 'max'."""
+
+  def __init__(self, set_size, num_sets, weights, mode):
+    self.set_size, self.num_sets, self.num_items = set_size, num_sets, set_size * num_sets
+    self.weights, self.mode, self.device = weights, mode, weights.device
+
+  @property
+  def _columns(self):
+    """The virtual columns of the scans: 128 per tile of 128 // set_size whole sets."""
+    return 128 * -(-self.num_sets // (128 // self.set_size))
+
+  def subset(self, sets):
+    """sets: bool [num_sets] (True = allowed) or int64 set numbers (any shape, any order, duplicates allowed), on the
+    index device -> the IndexSubset over SET numbers (its num_items is num_sets) that subset= takes next to this
+    item_pooling=.  Checked and packed as VideoIndex.subset."""
+    return IndexSubset(*_mask_of(sets, self.num_sets, self.device, 'sets'))
+
+
+class ShardedItemPooling:
+  """The item sets of a ShardedVideoIndex (ShardedVideoIndex.item_pooling): `parts[s]` is shard s's ItemPooling in its own
+  set numbers on its own device (None for a shard without items); `tables[s]` int64 on the primary, shard s's local set ->
+  global set; `weights` float32 [num_items] in global item order on the primary; `set_size`, `num_sets`, `num_items`,
+  `mode`, `device`."""
+
+  def __init__(self, set_size, num_sets, weights, mode, parts, tables, set_shard_of, set_local_of):
+    self.set_size, self.num_sets, self.num_items = set_size, num_sets, set_size * num_sets
+    self.weights, self.mode, self.device = weights, mode, weights.device
+    self.parts, self.tables = parts, tables
+    self._maps = (set_shard_of, set_local_of)   # global set -> (shard, local set), on the primary
+    self._table_cache = {}
+
+  def _tables(self, shards):
+    """The set tables' addresses of the given shards as a device array on the primary: the `ids` of the merge kernel."""
+    if shards not in self._table_cache:
+      self._table_cache[shards] = torch.tensor([self.tables[s].data_ptr() for s in shards],
+                                               dtype=torch.int64).to(self.device)
+    return self._table_cache[shards]
+
+  def subset(self, sets):
+    """sets: bool [num_sets] or int64 set numbers on the primary device, as ItemPooling.subset -> ShardedSubset over SET
+    numbers: the set cut into one IndexSubset per shard, in the shard's own set numbers."""
+    mask, total = _mask_of(sets, self.num_sets, self.device, 'sets')
+    parts = []
+    for part_pool, table in zip(self.parts, self.tables):
+      part = None
+      if part_pool is not None:
+        local = mask[table]  # gathered on the primary, where the table is
+        with torch.cuda.device(part_pool.device):
+          local = local.to(part_pool.device)
+          count = int(local.sum())
+          if count:
+            part = IndexSubset(local, count)
+      parts.append(part)
+    return ShardedSubset(parts, mask, total)
+
+
+def sets_whole(shard_of, local_of, set_size):
+  """Whether sets of `set_size` consecutive global items are each stored whole on one shard, in order, starting at a local
+  item number that is a multiple of set_size: (global item -> shard, global item -> local item), int64 [num_sets *
+  set_size] -> a 0-dim bool tensor on their device (one reduction, no host sync here)."""
+  so, lo = shard_of.view(-1, set_size), local_of.view(-1, set_size)
+  steps = torch.arange(set_size, device=lo.device, dtype=lo.dtype)
+  return ((so == so[:, :1]) & (lo == lo[:, :1] + steps) & (lo[:, :1] % set_size == 0)).all()
+
+
+def _check_item_sets(who, set_size, num_items, item_weights, mode, device):
+  """The checks of `item_pooling` -> (num_sets, the weights as float32 [num_items] of their own).  One small reduction
+  and one host sync where weights are given."""
+  if isinstance(set_size, bool) or not isinstance(set_size, int):
+    raise ValueError('%s: set_size must be an int, got %r' % (who, set_size))
+  if not 1 <= set_size <= MAX_ITEM_SET:
+    raise ValueError('%s: set_size must lie in 1..%d, got %d' % (who, MAX_ITEM_SET, set_size))
+  if mode not in _POOL_MODES:
+    raise ValueError("%s: mode must be 'mean' or 'max', got %r" % (who, mode))
+  if num_items == 0:
+    raise ValueError('%s: the index holds no items' % who)
+  if num_items % set_size:
+    raise ValueError('%s: %d items are no whole number of sets of %d' % (who, num_items, set_size))
+  num_sets = num_items // set_size
+  if item_weights is None:
+    return num_sets, torch.full((num_items,), 1.0 / set_size, device=device, dtype=torch.float32)
+  if not torch.is_tensor(item_weights) or item_weights.dtype != torch.float32:
+    raise ValueError('%s: item_weights must be a float32 tensor, got %s' % (
+        who, item_weights.dtype if torch.is_tensor(item_weights) else type(item_weights).__name__))
+  if item_weights.device != device:
+    raise ValueError('%s: item_weights must be on the index device %s, got %s' % (who, device, item_weights.device))
+  if tuple(item_weights.shape) not in ((num_items,), (num_sets, set_size)):
+    raise ValueError('%s: item_weights of shape (%d,) or (%d, %d) expected, got %s' % (
+        who, num_items, num_sets, set_size, tuple(item_weights.shape)))
+  w = item_weights.reshape(-1).contiguous().clone()
+  sets = w.view(num_sets, set_size)
+  finite, manned = (bool(v) for v in torch.stack([torch.isfinite(w).all(), (sets != 0).any(1).all()]).tolist())
+  if not finite:
+    raise ValueError('%s: item_weights must be finite' % who)
+  if not manned:
+    raise ValueError('%s: every set needs an item with a weight other than 0' % who)
+  return num_sets, w
+
+
 def _count_groups(ids):
   """The number of distinct values of a non-empty id tensor: one torch.unique, whose size is the one wait for the device."""
   return int(torch.unique(ids).numel())
@@ -363,28 +519,7 @@ class _Index:
     """The checks of `subset` -> (the set as a bool mask [num_items] of its own, the number of allowed items)."""
     if self.num_items == 0:
       raise ValueError('subset: the index holds no items')
-    if not torch.is_tensor(items) or items.dtype not in (torch.bool, torch.int64):
-      raise ValueError('subset: items must be a bool or int64 tensor, got %s' % (
-          items.dtype if torch.is_tensor(items) else type(items).__name__))
-    if items.device != self.device:
-      raise ValueError('subset: items must be on the index device %s, got %s' % (self.device, items.device))
-    nv = self.num_items
-    if items.dtype == torch.bool:
-      if tuple(items.shape) != (nv,):
-        raise ValueError('subset: a bool mask of shape (%d,) expected, got %s' % (nv, tuple(items.shape)))
-      mask = items.contiguous().clone()
-    else:
-      ids = items.reshape(-1)
-      if ids.numel() == 0:
-        raise ValueError('subset: no item allowed')
-      lo, hi = (int(v) for v in torch.aminmax(ids))
-      if lo < 0 or hi >= nv:
-        raise ValueError('subset: items must lie in 0 .. %d, got %d .. %d' % (nv - 1, lo, hi))
-      mask = torch.zeros(nv, device=self.device, dtype=torch.bool).index_fill_(0, ids, True)
-    count = int(mask.sum())
-    if count == 0:
-      raise ValueError('subset: no item allowed')
-    return mask, count
+    return _mask_of(items, self.num_items, self.device)
 
   def _exclude(self, exclude):
     """Type, device and width of `exclude`: all that can be said about it before the queries are known."""
@@ -406,11 +541,13 @@ class _Index:
     if targets.dim() not in (1, 2) or targets.dim() == 2 and targets.shape[1] < 1:
       raise ValueError('ranks: targets [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(targets.shape),))
 
-  def _target_range(self, targets):
-    """The values of the (non-empty) targets against -1 .. num_items - 1: one small reduction and a host sync."""
+  def _target_range(self, targets, item_pooling=None):
+    """The values of the (non-empty) targets against -1 .. num_items - 1 (with an item pooling: num_sets - 1): one small
+    reduction and a host sync."""
+    n = self.num_items if item_pooling is None else item_pooling.num_sets
     lo, hi = (int(v) for v in torch.aminmax(targets))
-    if lo < -1 or hi >= self.num_items:
-      raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
+    if lo < -1 or hi >= n:
+      raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (n - 1, lo, hi))
 
   def pooling(self, set_size, num_sets, row_weights=None, mode='mean'):
     """The query sets of a pooled scan -> QueryPooling, built once like a subset and passed as pooling= to `search`,
@@ -461,13 +598,28 @@ class _Index:
     if exclude is not None or norm is not None:
       raise ValueError('%s: pooling= does not combine with exclude= or norm=' % who)
 
-  def _scan_args(self, who, embds, weights, subset, norm, dynamic, exclude=None, pooling=None):
+  def _item_pooling(self, item_pooling, who, pooling=None, exclude=None, norm=None):
+    """Type, device and age of `item_pooling`, and what it does not combine with."""
+    if not isinstance(item_pooling, self._item_pooling_type):
+      raise ValueError('%s: item_pooling must come from item_pooling(), got %s' % (who, type(item_pooling).__name__))
+    if item_pooling.device != self.device:
+      raise ValueError('%s: the item pooling is on %s, the index on %s' % (who, item_pooling.device, self.device))
+    if item_pooling.num_items != self.num_items:
+      raise ValueError('%s: the item pooling was built for %d items, the index holds %d' % (
+          who, item_pooling.num_items, self.num_items))
+    if pooling is not None or exclude is not None or norm is not None:
+      raise ValueError('%s: item_pooling= does not combine with pooling=, exclude= or norm=' % who)
+
+  def _scan_args(self, who, embds, weights, subset, norm, dynamic, exclude=None, pooling=None, item_pooling=None):
     """The checks every scan shares once its own arguments have passed -> q, qw, whether the dynamic rule applies.  With
-    a pooling the query count must be its num_rows: nothing is scored otherwise."""
+    a pooling the query count must be its num_rows: nothing is scored otherwise.  With an item pooling the subset is one
+    of its sets."""
+    if item_pooling is not None:
+      self._item_pooling(item_pooling, who, pooling, exclude, norm)
     if pooling is not None:
       self._pooling(pooling, who, exclude, norm)
     if subset is not None:
-      self._subset(subset, who)
+      self._subset(subset, who, item_pooling)
     if exclude is not None:
       self._exclude(exclude)
     if norm is not None:
@@ -518,7 +670,8 @@ class _Index:
       hubs = torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
     return self._hub_norm(b, bw, beta, hubs)
 
-  def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None, pooling=None):
+  def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None, pooling=None,
+             item_pooling=None):
     """Queries (NQ, M, d) / (NQ, M), or the text layout (B, M, C, d) / (B, C, M) -> (scores [NQ, k'] float32,
     indices [NQ, k'] int64) on the device, k' = min(k, NV), best first.  subset (from this index's `subset`): only its
     items are candidates and k' = min(k, subset.count).  exclude: int64 [NQ] or [NQ, E <= 32] on the index device, values
@@ -530,6 +683,9 @@ class _Index:
     pooling (from `pooling`): the queries are pooling.num_sets sets of pooling.set_size rows and the outputs have one row
     per SET: the k' best items by the set's pooled score (module docstring; mmt_search_topk_pooled), ranked and tied as
     above; a returned score is the pooled value with -0 as +0.  pooling= does not combine with exclude= or norm=.
+    item_pooling (from `item_pooling`): the STORED items are sets and the indices are set numbers: per query the k' best
+    sets by the set's pooled score (mmt_search_topk_itemsets), k' = min(k, num_sets) or min(k, subset.count) with a subset
+    from item_pooling.subset; does not combine with pooling=, exclude= or norm=.
     ShardedVideoIndex: every shard searches its own items for its best min(k', its candidates), with its part of the
     subset and the norm; the lists are copied to the primary and merged there in one launch.  With a pooling every shard
     sees all query rows, so a pooled score has the same bits wherever the item is stored."""
@@ -537,14 +693,16 @@ class _Index:
       raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
     if self.num_items == 0:
       raise ValueError('search: the index holds no items')
-    q, qw, dynamic = self._scan_args('search', embds, weights, subset, norm, dynamic, exclude, pooling)
+    q, qw, dynamic = self._scan_args('search', embds, weights, subset, norm, dynamic, exclude, pooling, item_pooling)
+    if item_pooling is not None:
+      return self._search(q, qw, k, subset, None, None, None, item_pooling)
     if pooling is not None:
       return self._search(q, qw, k, subset, None, None, pooling)
     ex = _exclusions(exclude, q.shape[0], self.num_items)
     out = self._search(q, qw, k, subset, ex, norm)
     return self._dynamic(dynamic, q, qw, subset, ex, norm, out, lambda: self._search(q, qw, k, subset, ex))
 
-  def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None):
+  def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None, item_pooling=None):
     """Queries as for `search`; targets [NQ] or [NQ, T] int64 on the index device, values -1 .. num_items - 1 ->
     (greater, equal), int32 of targets' shape: how many of the num_items stored items score above / exactly equal to item
     targets[q, t] for query q (the item itself is one of the equal ones); 0 / 0 where the target is -1.  The range of the
@@ -555,20 +713,26 @@ class _Index:
     candidate is a hub, the others keep their plain counts (dynamic=False normalises every query).  pooling (from
     `pooling`): targets [NS] or [NS, T], one row per SET; the counts are those of the set's pooled score -- the target's
     pooled value from the threshold pass, then the count pass against it (mmt_search_thresholds_pooled,
-    mmt_search_count_pooled), so a target counts itself; not with norm=.  ShardedVideoIndex: each
+    mmt_search_count_pooled), so a target counts itself; not with norm=.  item_pooling (from `item_pooling`): targets are
+    SET numbers -1 .. num_sets - 1 and the counts are over the sets, by the set's pooled score
+    (mmt_search_thresholds_itemsets, mmt_search_count_itemsets); a target counts itself; a subset is one of sets.
+    ShardedVideoIndex: each
     shard scores the targets it holds, the primary picks the owner's value per (query, target), each shard counts its
     items against those thresholds and the int32 counts are summed on the primary."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
-    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic, None, pooling)
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic, None, pooling, item_pooling)
     nq, shape = _result_rows(q, pooling), targets.shape
     if shape[0] != nq:
       raise ValueError('ranks: %d %s but targets %s' % (nq, 'queries' if pooling is None else 'query sets', tuple(shape)))
     if nq == 0:
       return tuple(torch.empty(shape, device=self.device, dtype=torch.int32) for _ in range(2))
     tg = targets.reshape(nq, -1).contiguous()
-    self._target_range(tg)
+    self._target_range(tg, item_pooling)
+    if item_pooling is not None:
+      out = self._rank_counts(q, qw, tg, subset, None, None, item_pooling)
+      return out[0].reshape(shape), out[1].reshape(shape)
     if pooling is not None:
       out = self._rank_counts(q, qw, tg, subset, None, pooling)
       return out[0].reshape(shape), out[1].reshape(shape)
@@ -576,13 +740,15 @@ class _Index:
     out = self._dynamic(dynamic, q, qw, subset, None, norm, out, lambda: self._rank_counts(q, qw, tg, subset))
     return out[0].reshape(shape), out[1].reshape(shape)
 
-  def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None):
+  def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None, item_pooling=None):
     """The reference's tie-averaged 0-based rank (model/metric.py:90-121) of item targets[q, t] among the stored items for
     query q: greater + (equal - 1) / 2 from `rank_counts`, +inf where the target is -1.  float64 on the device, of
     targets' shape (float32 would not hold counts above 2^24).  subset: the rank among its items, +inf for a target that
     is not one of them.  norm, dynamic: as `rank_counts` -- the rank under the querybank-normalised score.  pooling: as
-    `rank_counts` -- one row per query set, the rank under the set's pooled score."""
-    greater, equal = self.rank_counts(embds, weights, targets, subset=subset, norm=norm, dynamic=dynamic, pooling=pooling)
+    `rank_counts` -- one row per query set, the rank under the set's pooled score.  item_pooling: as `rank_counts` -- the
+    rank of the target SET among the sets."""
+    greater, equal = self.rank_counts(embds, weights, targets, subset=subset, norm=norm, dynamic=dynamic, pooling=pooling,
+                                      item_pooling=item_pooling)
     ranks = greater.double() + (equal.double() - 1) / 2
     none = targets < 0
     if subset is not None:
@@ -734,10 +900,27 @@ class VideoIndex(_Index):
     is refused.  Raises ValueError for an empty subset."""
     return IndexSubset(*self._subset_mask(items))
 
-  def _subset(self, subset, who):
+  _item_pooling_type = ItemPooling
+
+  def item_pooling(self, set_size, item_weights=None, mode='mean'):
+    """The item sets of an item-pooled scan -> ItemPooling, built once like a subset and passed as item_pooling= to
+    `search`, `rank_counts`, `ranks`, `target_scores` and `threshold_counts`: the stored items are num_items / set_size
+    sets of set_size consecutive items (1 <= set_size <= MAX_ITEM_SET = 128, num_items % set_size == 0) and such a call
+    answers per SET.  item_weights: float32 [num_items] or [num_sets, set_size] on the index device, finite; an item
+    whose weight is 0 takes no part, and every set needs an item that does.  None = float32(1 / set_size) on every item,
+    the reference's 'avg' on the gallery axis.  mode as `pooling`.  The checks cost one small reduction and one host
+    sync.  It describes the num_items of this moment: after a further `add` it is refused."""
+    num_sets, w = _check_item_sets('item_pooling', set_size, self.num_items, item_weights, mode, self.device)
+    return ItemPooling(set_size, num_sets, w, mode)
+
+  def _subset(self, subset, who, item_pooling=None):
     if not isinstance(subset, IndexSubset):
       raise ValueError('%s: subset must come from VideoIndex.subset, got %s' % (who, type(subset).__name__))
-    if subset.num_items != self.num_items:
+    if item_pooling is not None:
+      if subset.num_items != item_pooling.num_sets:
+        raise ValueError('%s: the subset was built for %d sets, the item pooling has %d' % (
+            who, subset.num_items, item_pooling.num_sets))
+    elif subset.num_items != self.num_items:
       raise ValueError('%s: the subset was built for %d items, the index holds %d' % (who, subset.num_items, self.num_items))
     if subset.device != self.device:
       raise ValueError('%s: the subset is on %s, the index on %s' % (who, subset.device, self.device))
@@ -788,7 +971,7 @@ class VideoIndex(_Index):
 
   def _entry(self, op, variant=''):
     """The C entry point of a scan over this index's storage: op 'topk', 'topk_groups', 'rank', 'thresholds', 'count',
-    'range_count', 'range_fill' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions), '_norm' or '_pooled' -> (the
+    'range_count', 'range_fill' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions), '_norm', '_pooled' or '_itemsets' -> (the
     function, its name)."""
     name = 'mmt_search_%s%s%s' % (op, '_bf16' if self.dtype == torch.bfloat16 else '', variant)
     return getattr(_lib.lib(), name), name
@@ -868,10 +1051,78 @@ class VideoIndex(_Index):
                  ops._stream()), name)
     return scores, indices
 
-  def _search(self, q, qw, k, subset, ex, norm=None, pooling=None):
+  def _itemset_args(self, ip, n):
+    """The entry points' (item weights, NQ, NT, C, mode) for n query rows."""
+    return ops._p(ip.weights), n, ip.num_sets, ip.set_size, _POOL_MODES[ip.mode]
+
+  def _search_itemsets(self, q, qw, k, subset, ip):
+    """`search` with an item pooling behind its checks -> (scores, set numbers) [NQ, k'].  Nothing here waits for the
+    device."""
+    nq, m, d = q.shape[0], self.num_experts, self.dim
+    k = min(k, ip.num_sets if subset is None else subset.count)
+    scores = torch.empty(nq, k, device=self.device, dtype=torch.float32)
+    indices = torch.empty(nq, k, device=self.device, dtype=torch.int64)
+    if nq == 0:
+      return scores, indices
+    fn, name = self._entry('topk', '_itemsets')
+    words = None if subset is None else subset.words
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._row_batches(nq, 8 * k * -(-ip._columns // 4096)):  # a row's chunk lists at full-size chunks
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        ws = torch.empty(_lib.lib().mmt_topk_itemsets_workspace_keys(r1 - r0, ip.num_sets, ip.set_size, k),
+                         device=self.device, dtype=torch.int64)
+        check(fn(*operands, *self._itemset_args(ip, r1 - r0), m, d, k, ops._p(words), ops._p(ws), ops._p(scores[r0:r1]),
+                 ops._p(indices[r0:r1]), ops._stream()), name)
+    return scores, indices
+
+  def _itemset_batches(self, nq, t_max, ip):
+    """Row ranges of the item-pooled rank passes: a row's thresholds and chunk counters at full-size chunks."""
+    return self._row_batches(nq, 4 * t_max * (1 + 2 * -(-ip._columns // 4096)))
+
+  def _target_scores_itemsets(self, q, qw, targets, ip):
+    """`target_scores` with an item pooling behind its checks: targets [NQ] or [NQ, T] set numbers."""
+    nq, m, d = q.shape[0], self.num_experts, self.dim
+    tg = targets.reshape(nq, -1).contiguous()
+    thr = torch.empty(tg.shape, device=self.device, dtype=torch.float32)
+    if nq == 0:
+      return thr.reshape(targets.shape)
+    fn, name = self._entry('thresholds', '_itemsets')
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._itemset_batches(nq, min(MAX_T, tg.shape[1]), ip):
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        for tgs, (out,) in _column_groups(tg, (thr,), r0, r1):
+          check(fn(*operands, *self._itemset_args(ip, r1 - r0), m, d, ops._p(tgs), tgs.shape[1], ops._p(out), ops._stream()),
+                name)
+    return thr.reshape(targets.shape)
+
+  def _threshold_counts_itemsets(self, q, qw, thresholds, subset, ip):
+    """`threshold_counts` with an item pooling behind its checks: the counts are over the sets."""
+    nq, m, d = q.shape[0], self.num_experts, self.dim
+    thr = thresholds.reshape(nq, -1).contiguous()
+    greater = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
+    equal = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
+    if nq == 0:
+      return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
+    fn, name = self._entry('count', '_itemsets')
+    words = None if subset is None else subset.words
+    t_max = min(MAX_T, thr.shape[1])
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._itemset_batches(nq, t_max, ip):
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        ws = torch.empty(_lib.lib().mmt_count_itemsets_workspace_ints(r1 - r0, ip.num_sets, ip.set_size, t_max),
+                         device=self.device, dtype=torch.int32)
+        for ts, (gs, es) in _column_groups(thr, (greater, equal), r0, r1):
+          check(fn(*operands, *self._itemset_args(ip, r1 - r0), m, d, ops._p(ts), ts.shape[1], ops._p(words), ops._p(ws),
+                   ops._p(gs), ops._p(es), ops._stream()), name)
+    return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
+
+  def _search(self, q, qw, k, subset, ex, norm=None, pooling=None, item_pooling=None):
     """`search` behind its argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the index device, ex None or int64 [NQ, E]
     there, norm None or a HubNorm of this index (every query normalised), pooling None or a QueryPooling of NQ rows (then
-    ex and norm are None).  Nothing here waits for the device."""
+    ex and norm are None), item_pooling None or an ItemPooling of this index (then the others are None).  Nothing here
+    waits for the device."""
+    if item_pooling is not None:
+      return self._search_itemsets(q, qw, k, subset, item_pooling)
     if pooling is not None:
       return self._search_pooled(q, qw, k, subset, pooling)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
@@ -903,12 +1154,13 @@ class VideoIndex(_Index):
                  ops._stream()), name)
     return scores, indices
 
-  def _rank_counts(self, q, qw, tg, subset, norm=None, pooling=None):
+  def _rank_counts(self, q, qw, tg, subset, norm=None, pooling=None, item_pooling=None):
     """`rank_counts` behind its checks: tg int64 [NQ >= 1, T] on the index device -> (greater, equal) int32 [NQ, T].  Plain:
-    the threshold and the count pass in one call per batch (mmt_search_rank); with a norm or a pooling (tg [num_sets, T]):
-    one after the other."""
-    if norm is not None or pooling is not None:
-      return self._threshold_counts(q, qw, self._target_scores(q, qw, tg, norm, pooling), subset, norm, pooling)
+    the threshold and the count pass in one call per batch (mmt_search_rank); with a norm, a pooling (tg [num_sets, T]) or
+    an item pooling (tg set numbers): one after the other."""
+    if norm is not None or pooling is not None or item_pooling is not None:
+      return self._threshold_counts(q, qw, self._target_scores(q, qw, tg, norm, pooling, item_pooling), subset, norm, pooling,
+                                    item_pooling)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     greater = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
     equal = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
@@ -925,23 +1177,27 @@ class VideoIndex(_Index):
                    ops._stream()), name)
     return greater, equal
 
-  def target_scores(self, embds, weights, targets, norm=None, dynamic=None, pooling=None):
+  def target_scores(self, embds, weights, targets, norm=None, dynamic=None, pooling=None, item_pooling=None):
     """Queries as for `search`; targets as for `rank_counts` -> float32 of targets' shape on the device:
     score(q, targets[q, t]) with the very bits `search` returns for that pair (the threshold pass of `rank_counts` on its
     own: mmt_search_thresholds), NaN where the target is -1.  norm (VideoIndex.hub_norm): score'(q, targets[q, t]), with
     the bits `search(norm=)` returns; the dynamic rule as there, the plain top-1 taken over all items.  pooling (from
     `pooling`; not with norm=): targets [NS] or [NS, T], one row per query SET -> the set's pooled score of the target with
-    the bits the pooled scans compute for the pair, as they are (a -0 stays -0; mmt_search_thresholds_pooled)."""
+    the bits the pooled scans compute for the pair, as they are (a -0 stays -0; mmt_search_thresholds_pooled).
+    item_pooling (from `item_pooling`; not with norm= or pooling=): targets are SET numbers -> the query's pooled score of
+    the target set, likewise as it is (mmt_search_thresholds_itemsets)."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
-    q, qw, dynamic = self._scan_args('ranks', embds, weights, None, norm, dynamic, None, pooling)
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, None, norm, dynamic, None, pooling, item_pooling)
     nq = _result_rows(q, pooling)
     if targets.shape[0] != nq:
       raise ValueError('ranks: %d %s but targets %s' % (nq, 'queries' if pooling is None else 'query sets',
                                                         tuple(targets.shape)))
     if nq:
-      self._target_range(targets)
+      self._target_range(targets, item_pooling)
+    if item_pooling is not None:
+      return self._target_scores(q, qw, targets, None, None, item_pooling)
     if pooling is not None:
       return self._target_scores(q, qw, targets, None, pooling)
     out = (self._target_scores(q, qw, targets, norm),)
@@ -963,10 +1219,12 @@ class VideoIndex(_Index):
           check(fn(*operands, *pool, nv, m, d, ops._p(tgs), tgs.shape[1], ops._p(out), ops._stream()), name)
     return thr.reshape(targets.shape)
 
-  def _target_scores(self, q, qw, targets, norm=None, pooling=None):
+  def _target_scores(self, q, qw, targets, norm=None, pooling=None, item_pooling=None):
     """`target_scores` behind its checks; a target outside 0 .. num_items - 1 gives NaN; norm None or a HubNorm of this
-    index (every query normalised); pooling None or a QueryPooling of NQ rows (then norm is None).  Nothing here waits
-    for the device."""
+    index (every query normalised); pooling None or a QueryPooling of NQ rows (then norm is None); item_pooling None or
+    an ItemPooling of this index (then the others are None).  Nothing here waits for the device."""
+    if item_pooling is not None:
+      return self._target_scores_itemsets(q, qw, targets, item_pooling)
     if pooling is not None:
       return self._target_scores_pooled(q, qw, targets, pooling)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
@@ -983,14 +1241,16 @@ class VideoIndex(_Index):
           check(fn(*operands, r1 - r0, nv, m, d, ops._p(tgs), tgs.shape[1], *extra, ops._p(out), ops._stream()), name)
     return thr.reshape(targets.shape)
 
-  def threshold_counts(self, embds, weights, thresholds, subset=None, norm=None, dynamic=None, pooling=None):
+  def threshold_counts(self, embds, weights, thresholds, subset=None, norm=None, dynamic=None, pooling=None,
+                       item_pooling=None):
     """Queries as for `search`; thresholds float32 [NQ] or [NQ, T] on the index device -> (greater, equal), int32 of
     thresholds' shape: how many stored items score above / exactly equal to thresholds[q, t] for query q (plain float
     compares; a NaN threshold counts nothing) -- the count pass of `rank_counts` against given values (mmt_search_count).
     Fed with `target_scores` it gives `rank_counts`.  subset: only its items are counted.  norm (VideoIndex.hub_norm): the
     items' score' is what is compared (mmt_search_count_norm); the dynamic rule as in `rank_counts`.  pooling (from
     `pooling`; not with norm=): thresholds [NS] or [NS, T], one row per query SET; the items' pooled score for the set is
-    what is compared (mmt_search_count_pooled)."""
+    what is compared (mmt_search_count_pooled).  item_pooling (from `item_pooling`; not with norm= or pooling=): the
+    SETS' pooled scores for the query are what is compared and counted (mmt_search_count_itemsets)."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     if not torch.is_tensor(thresholds) or thresholds.dtype != torch.float32:
@@ -1000,11 +1260,13 @@ class VideoIndex(_Index):
       raise ValueError('ranks: thresholds must be on the index device %s, got %s' % (self.device, thresholds.device))
     if thresholds.dim() not in (1, 2) or thresholds.dim() == 2 and thresholds.shape[1] < 1:
       raise ValueError('ranks: thresholds [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(thresholds.shape),))
-    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic, None, pooling)
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic, None, pooling, item_pooling)
     nq = _result_rows(q, pooling)
     if thresholds.shape[0] != nq:
       raise ValueError('ranks: %d %s but thresholds %s' % (nq, 'queries' if pooling is None else 'query sets',
                                                            tuple(thresholds.shape)))
+    if item_pooling is not None:
+      return self._threshold_counts(q, qw, thresholds, subset, None, None, item_pooling)
     if pooling is not None:
       return self._threshold_counts(q, qw, thresholds, subset, None, pooling)
     out = self._threshold_counts(q, qw, thresholds, subset, norm)
@@ -1032,9 +1294,12 @@ class VideoIndex(_Index):
                    ops._stream()), name)
     return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
 
-  def _threshold_counts(self, q, qw, thresholds, subset, norm=None, pooling=None):
+  def _threshold_counts(self, q, qw, thresholds, subset, norm=None, pooling=None, item_pooling=None):
     """`threshold_counts` behind its checks; norm None or a HubNorm of this index (every query normalised); pooling None
-    or a QueryPooling of NQ rows (then norm is None).  Nothing here waits for the device."""
+    or a QueryPooling of NQ rows (then norm is None); item_pooling None or an ItemPooling of this index (then the others
+    are None).  Nothing here waits for the device."""
+    if item_pooling is not None:
+      return self._threshold_counts_itemsets(q, qw, thresholds, subset, item_pooling)
     if pooling is not None:
       return self._threshold_counts_pooled(q, qw, thresholds, subset, pooling)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
@@ -1280,10 +1545,40 @@ class ShardedVideoIndex(_Index):
     """(number, shard) of the shards that hold items -- with a subset: allowed items."""
     return [(s, sh) for s, sh in enumerate(self.shards) if sh.num_items and (subset is None or subset.parts[s] is not None)]
 
-  def _local(self, items, s):
-    """Global item numbers (-1 = none) on the primary -> shard s's numbers, -1 for none and for items held elsewhere."""
+  def _local(self, items, s, maps=None):
+    """Global item numbers (-1 = none) on the primary -> shard s's numbers, -1 for none and for items held elsewhere.
+    maps: (global -> shard, global -> local) in place of the item maps: an item pooling's set maps."""
+    shard_of, local_of = (self._shard_of, self._local_of) if maps is None else maps
     at = items.clamp(min=0)
-    return torch.where((items >= 0) & (self._shard_of[at] == s), self._local_of[at], torch.full_like(items, -1))
+    return torch.where((items >= 0) & (shard_of[at] == s), local_of[at], torch.full_like(items, -1))
+
+  _item_pooling_type = ShardedItemPooling
+
+  def item_pooling(self, set_size, item_weights=None, mode='mean'):
+    """As VideoIndex.item_pooling, item_weights in global item order on the primary -> ShardedItemPooling.  Accepted when
+    every set is stored whole on one shard, in order, starting at a local item number that is a multiple of set_size
+    (checked from the item maps with one reduction; ValueError otherwise).  To fill an index so that this holds: `.empty`
+    with a capacity of len(devices) * n * set_size, so that every shard's capacity is a multiple of set_size, then `add`
+    in pieces of whole sets that fit one shard (a piece that spills is cut at the shard's free rows, a multiple of
+    set_size, so its sets stay whole too).  Each shard gets its own ItemPooling in local set numbers and a local-set ->
+    global-set table on the primary, so results are bit-identical to one VideoIndex."""
+    num_sets, w = _check_item_sets('item_pooling', set_size, self.num_items, item_weights, mode, self.device)
+    n = self.num_items
+    if not bool(sets_whole(self._shard_of[:n], self._local_of[:n], set_size)):
+      raise ValueError('item_pooling: a set of %d items is split across shards or starts off a multiple of %d there'
+                       % (set_size, set_size))
+    parts, tables = [], []
+    for sh in self.shards:
+      part, table = None, None
+      if sh.num_items:
+        ids = sh.ids[:sh.num_items]
+        table = ids[::set_size] // set_size          # on the primary, where the item table is
+        with torch.cuda.device(sh.device):
+          part = ItemPooling(set_size, sh.num_items // set_size, w[ids].to(sh.device), mode)
+      parts.append(part)
+      tables.append(table)
+    return ShardedItemPooling(set_size, num_sets, w, mode, parts, tables, self._shard_of[:n:set_size].clone(),
+                              self._local_of[:n:set_size] // set_size)
 
   def subset(self, items):
     """items: bool [num_items] or int64 item numbers on the primary device, as VideoIndex.subset -> ShardedSubset: the set
@@ -1302,10 +1597,14 @@ class ShardedVideoIndex(_Index):
       parts.append(part)
     return ShardedSubset(parts, mask, total)
 
-  def _subset(self, subset, who):
+  def _subset(self, subset, who, item_pooling=None):
     if not isinstance(subset, ShardedSubset):
       raise ValueError('%s: subset must come from ShardedVideoIndex.subset, got %s' % (who, type(subset).__name__))
-    if subset.num_items != self.num_items:
+    if item_pooling is not None:
+      if subset.num_items != item_pooling.num_sets:
+        raise ValueError('%s: the subset was built for %d sets, the item pooling has %d' % (
+            who, subset.num_items, item_pooling.num_sets))
+    elif subset.num_items != self.num_items:
       raise ValueError('%s: the subset was built for %d items, the index holds %d' % (who, subset.num_items, self.num_items))
     if subset.device != self.device or len(subset.parts) != len(self.shards):
       raise ValueError('%s: the subset belongs to another index' % who)
@@ -1335,27 +1634,30 @@ class ShardedVideoIndex(_Index):
       parts.append(part)
     return ShardedHubNorm(parts, lse, beta, b.shape[0], hubs)
 
-  def _search(self, q, qw, k, subset, ex, norm=None, pooling=None):
+  def _search(self, q, qw, k, subset, ex, norm=None, pooling=None, item_pooling=None):
     """`search` behind its checks: q, qw on the primary, ex None or int64 [NQ, E] global numbers there, norm None or a
     ShardedHubNorm of this index (every query normalised), pooling None or a QueryPooling of NQ rows (then ex and norm
-    are None): every shard gets all the rows and returns one list per set."""
+    are None): every shard gets all the rows and returns one list per set.  item_pooling None or a ShardedItemPooling of
+    this index (then the others are None): every shard searches its own sets and the merge goes through the set tables."""
+    ip = item_pooling
     nq = _result_rows(q, pooling)
-    kout = min(k, self.num_items if subset is None else subset.count)
+    kout = min(k, (self.num_items if ip is None else ip.num_sets) if subset is None else subset.count)
     scores = torch.empty(nq, kout, device=self.device, dtype=torch.float32)
     indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
     if nq == 0:
       return scores, indices
     live = self._live(subset)
-    kin = min(kout, max(sh.num_items if subset is None else subset.parts[s].count for s, sh in live))
+    kin = min(kout, max((sh.num_items if ip is None else ip.parts[s].num_sets) if subset is None else subset.parts[s].count
+                        for s, sh in live))
     with torch.cuda.device(self.device):  # the staged lists; the slots a shorter list leaves are empty
       st_scores = torch.full((len(live), nq, kin), float('-inf'), device=self.device, dtype=torch.float32)
       st_index = torch.full((len(live), nq, kin), -1, device=self.device, dtype=torch.int64)
-      tables = self._tables(tuple(s for s, _ in live))
+      tables = (self if ip is None else ip)._tables(tuple(s for s, _ in live))
     for i, (s, sh) in enumerate(live):
       ex_s = None if ex is None else self._local(ex, s).to(sh.device)
       with torch.cuda.device(sh.device):
         part = sh.index._search(q.to(sh.device), qw.to(sh.device), kout, None if subset is None else subset.parts[s], ex_s,
-                                None if norm is None else norm.parts[s], pooling)
+                                None if norm is None else norm.parts[s], pooling, None if ip is None else ip.parts[s])
       width = part[0].shape[1]
       st_scores[i, :, :width].copy_(part[0])
       st_index[i, :, :width].copy_(part[1])
@@ -1420,17 +1722,20 @@ class ShardedVideoIndex(_Index):
                                                     ops._stream()), 'mmt_search_merge_group_lists')
     return scores, groups, items
 
-  def _rank_counts(self, q, qw, tg, subset, norm=None, pooling=None):
+  def _rank_counts(self, q, qw, tg, subset, norm=None, pooling=None, item_pooling=None):
     """`rank_counts` behind its checks: tg int64 [NQ, T] global numbers on the primary -> (greater, equal) int32 [NQ, T];
-    with a pooling (then norm is None) tg is [num_sets, T] and every shard gets all the rows."""
+    with a pooling (then norm is None) tg is [num_sets, T] and every shard gets all the rows; with an item pooling (then
+    the others are None) tg holds global set numbers, translated through its set maps."""
+    ip = item_pooling
     live = self._live()
     queries = {}
     thr = torch.full(tg.shape, float('nan'), device=self.device, dtype=torch.float32)
     for s, sh in live:
-      local = self._local(tg, s)
+      local = self._local(tg, s, None if ip is None else ip._maps)
       queries[s] = (q.to(sh.device), qw.to(sh.device))
       with torch.cuda.device(sh.device):
-        mine = sh.index._target_scores(*queries[s], local.to(sh.device), None if norm is None else norm.parts[s], pooling)
+        mine = sh.index._target_scores(*queries[s], local.to(sh.device), None if norm is None else norm.parts[s], pooling,
+                                       None if ip is None else ip.parts[s])
       thr = torch.where(local >= 0, mine.to(self.device), thr)
     greater = torch.zeros(tg.shape, device=self.device, dtype=torch.int32)
     equal = torch.zeros(tg.shape, device=self.device, dtype=torch.int32)
@@ -1440,7 +1745,7 @@ class ShardedVideoIndex(_Index):
         continue  # no allowed item here: nothing to count
       with torch.cuda.device(sh.device):
         gs, es = sh.index._threshold_counts(*queries[s], thr.to(sh.device), part, None if norm is None else norm.parts[s],
-                                            pooling)
+                                            pooling, None if ip is None else ip.parts[s])
       greater += gs.to(self.device)
       equal += es.to(self.device)
     return greater, equal

@@ -63,7 +63,14 @@ spread.  Default output profiles/search_groups_bench.json.
 of the same rows on the same index -- the same scan without the pool step and with C times the selection rows, the
 yardstick.  At S1 and S2 the materialised path is timed too: the NQ x NV matrix (mmt_sims_eval, the kernel of
 eval_similarity, which itself wants NQ = NV x captions), its mean over the sets in torch, then mmt_rows_topk.  --runs
-rounds, every variant once per round, interleaved; median and spread.  Default output profiles/search_pooled_bench.json."""
+rounds, every variant once per round, interleaved; median and spread.  Default output profiles/search_pooled_bench.json.
+
+--item-pooled C times the item-pooled search (VideoIndex.search(item_pooling=), k = 10, mean with weights 1 / C and max)
+per index dtype (--gallery-dtype, both = the two indexes) with the first NV // C * C stored items as sets of C, beside the
+plain search(k = 10) over the same stored items on the same index -- the same scan without the pool step, the yardstick.
+What the code predicts is the plain scan's time, times 128 / (128 // C * C) for the idle tile columns, plus the pool step;
+the prediction's factor is reported beside the measured ratio.  --runs rounds, every variant once per round, interleaved;
+median and spread.  Default output profiles/search_itemset_bench.json."""
 import argparse
 import json
 import math
@@ -452,6 +459,53 @@ def pooled_mode(q, qw, g, gw, flop, a):
   return row
 
 
+def item_pooled_mode(q, qw, g, gw, flop, a):
+  """search(item_pooling=) in both modes against the plain search over the same stored items, per index dtype."""
+  c = a.item_pooled
+  nt = g.shape[0] // c
+  nv = nt * c
+  flop = 2.0 * q.shape[0] * nv * M * D   # the items in use
+  dtypes = ('float32', 'bfloat16') if a.gallery_dtype == 'both' else (a.gallery_dtype,)
+  fns = {}
+  for n in dtypes:
+    index = VideoIndex.empty(nv, M, D, g.device, dtype=getattr(torch, n))
+    for at in range(0, nv, 8192):
+      index.add(g[at:min(nv, at + 8192)], gw[at:min(nv, at + 8192)])
+    for mode in ('mean', 'max'):
+      ip = index.item_pooling(c, mode=mode)
+      fns['%s/search_item_pooled_%s' % (n, mode)] = lambda index=index, ip=ip: index.search(q, qw, k=K, item_pooling=ip)
+    fns[n + '/search_k10'] = lambda index=index: index.search(q, qw, k=K)
+  ts = {n: [] for n in fns}
+  mem = {n: 0 for n in fns}
+  out = {}
+  for _ in range(a.runs):
+    for n, fn in fns.items():
+      t, _, m, out[n] = timed(fn, a.min_seconds)
+      ts[n].append(t)
+      mem[n] = max(mem[n], m)
+  idle = 128.0 / (128 // c * c)
+  row = {'set_size': c, 'num_sets': nt, 'items': nv, 'flop': flop, 'idle_column_factor': idle}
+  for n in fns:
+    med = float(np.median(ts[n]))
+    row[n] = dict(seconds_median=med, seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n],
+                  tflops_of_the_scan=flop / med / 1e12, peak_mem_growth_bytes=mem[n])
+  for n in dtypes:
+    plain = row[n + '/search_k10']
+    summary = {}
+    for mode in ('mean', 'max'):
+      r = row['%s/search_item_pooled_%s' % (n, mode)]
+      spread = max(r['seconds_spread'], plain['seconds_spread'])
+      summary[mode] = dict(over_search_k10=r['seconds_median'] / plain['seconds_median'], spread_seconds=spread,
+                           predicted_without_the_pool_step=idle,
+                           beyond_prediction_by_more_than_spread=bool(
+                               r['seconds_median'] - idle * plain['seconds_median'] > spread))
+    # the best set under max is the set of the best item
+    summary['max']['top_set_is_that_of_the_top_item'] = bool(
+        torch.equal(out[n + '/search_item_pooled_max'][1][:, 0], out[n + '/search_k10'][1][:, 0] // c))
+    row[n + '/summary'] = summary
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--shapes', default='S1,S2,S3')
@@ -478,6 +532,8 @@ def main():
                   'shuffled groups of SIZE items against search(k = 10)')
   ap.add_argument('--pooled', type=int, default=0, metavar='C', help='time search(pooling=) with sets of C (1..64) rows, mean '
                   'and max, against search(k = 10) of the same rows and, at S1 / S2, the materialised mean')
+  ap.add_argument('--item-pooled', type=int, default=0, metavar='C', help='time search(item_pooling=) with stored sets of C '
+                  '(1..128) items, mean and max, against search(k = 10) over the same items')
   ap.add_argument('--baseline-json', nargs='+', default=[], help='with --norm: default-mode results of another build; '
                   'with --range: --range --counts-only results of another build')
   ap.add_argument('--same-build-json', nargs='+', default=[], help='with --norm: default-mode results of this build')
@@ -501,6 +557,12 @@ def main():
     raise SystemExit('--pooled wants C in 1..64 and no --ranks, --subset, --exclude, --shards, --norm, --range, --groups')
   if a.pooled and a.out is None:
     a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_pooled_bench.json')
+  if not 0 <= a.item_pooled <= 128 or a.item_pooled and (masked or a.ranks or a.shards or a.norm is not None or a.range or
+                                                         a.groups or a.pooled):
+    raise SystemExit('--item-pooled wants C in 1..128 and no --ranks, --subset, --exclude, --shards, --norm, --range, '
+                     '--groups, --pooled')
+  if a.item_pooled and a.out is None:
+    a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_itemset_bench.json')
   if a.counts_only and not a.range:
     raise SystemExit('--counts-only goes with --range')
   if a.range and a.out is None and not a.counts_only:
@@ -544,6 +606,9 @@ def main():
     res.update(mode='groups', group_size=a.groups, gallery_dtype=a.gallery_dtype, runs=a.runs, min_seconds=a.min_seconds)
   if a.pooled:
     res.update(mode='pooled', set_size=a.pooled, gallery_dtype=a.gallery_dtype, runs=a.runs, min_seconds=a.min_seconds)
+  if a.item_pooled:
+    res.update(mode='item_pooled', set_size=a.item_pooled, gallery_dtype=a.gallery_dtype, runs=a.runs,
+               min_seconds=a.min_seconds)
   if masked:
     res.update(mode='subset', subset_fraction=a.subset, exclude=a.exclude, runs=a.runs, min_seconds=a.min_seconds)
   for name in a.shapes.split(','):
@@ -556,9 +621,10 @@ def main():
     qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
     flop = 2.0 * nq * nv * M * D
     row = {'NQ': nq, 'NV': nv, 'flop': flop}
-    if masked or a.ranks or a.norm is not None or a.range or a.groups or a.pooled or a.gallery_dtype == 'both':
+    if (masked or a.ranks or a.norm is not None or a.range or a.groups or a.pooled or a.item_pooled or
+        a.gallery_dtype == 'both'):
       mode = (norm_mode if a.norm is not None else range_mode if a.range else groups_mode if a.groups else
-              pooled_mode if a.pooled else
+              pooled_mode if a.pooled else item_pooled_mode if a.item_pooled else
               subset_mode if masked else ranks_mode if a.ranks else both_dtypes)
       row.update(mode(q, qw, g, gw, flop, a))
       res['shapes'][name] = row
