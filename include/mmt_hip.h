@@ -456,7 +456,7 @@ int mmt_sims_eval(const float* txt, const float* vid, const float* tw, const flo
 int mmt_retrieval_ranks(const float* sims, const uint8_t* qmask, int NQ, int NV, float* t2v_rank, float* v2t_rank,
                         float* scratch, void* stream);
 
-/* ---- top-k retrieval (search.hip, search_bf16.hip, search_rank.hip, search_subset.hip, search_shard.hip, search_norm.hip, fold in retrieval.hip) --------------------------------------
+/* ---- top-k retrieval (search.hip, search_bf16.hip, search_fp8.hip, search_rank.hip, search_subset.hip, search_shard.hip, search_norm.hip, fold in retrieval.hip) --------------------------------------
  * score(q, g) = sum_m qw[q][m] gw[g][m] <Q_m[q], G_m[g]> / sum_m qw[q][m] gw[g][m] (0 -> 1e-5), the 'indep' similarity
  * of model/model.py:789-837.  Per query the min(k, NV) best (score, gallery index) pairs, score descending, equal scores
  * by ascending index (a stable argsort; the reference's np.argsort leaves the order of exact ties unspecified).
@@ -652,6 +652,45 @@ int mmt_search_range_fill(const float* qf, const float* qw, const float* gf, con
 int mmt_search_range_fill_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
                                const float* gw, int NQ, int NV, int M, int d, const float* thr, const uint32_t* subset,
                                const int32_t* ws, const int64_t* offsets, int64_t* indices, float* scores, void* stream);
+/* fp8-stored gallery (search_fp8.hip; the scans are instantiations of the kernels above).  With f = the row mmt_search_fold
+ * gives an item, the index keeps scale = 2^e, the smallest power of two with max_k |f[k]| / 2^e <= 448 (e clamped to
+ * -120 .. 120; an all-zero row: 1), and stored = e4m3fn_rne(f / scale): OCP e4m3fn codes, round-to-nearest-even with
+ * subnormals, never saturating.  Inputs are taken to be finite (a NaN or Inf spoils its own item only).  Only storage is
+ * lossy; the score is defined on the stored value,
+ *   score(q, g) = fl( fl(acc * scale[g]) / den ),  acc = < fold_fp32(Q, qw)[q], dequant(stored[g]) >,
+ *   den = sum_m qw[q][m] gw[g][m] (0 -> 1e-5),
+ * acc as mmt_search_topk_bf16 computes it (hi = bf16(qf), lo = bf16(qf - hi), bf16 MFMAs, fp32 accumulation; every
+ * e4m3fn value is a bf16 value), the scale multiply rounded on its own.  Against the fp32 index a score moves by at most
+ *   ( 2^-4 * <|qf|, |f|> + 2^-10 * scale[g] * sum_k |qf[k]| ) / |den|.
+ * d % 16 == 0 (16-byte fp8 rows), pointers 16-byte aligned.
+ * mmt_search_fold_fp8: out = the codes [N][M*d], scale fp32 [N]; both may point into larger preallocated buffers.
+ * The scans: query operands from mmt_search_fold_split_bf16; gf [NV][M*d] e4m3fn codes; gscale fp32 [NV] after gw; every
+ *   other argument, gate, order, workspace and output as the _bf16 call of the same name. */
+int mmt_search_fold_fp8(const float* x, const float* w, int N, int M, int d, uint8_t* out, float* scale, void* stream);
+int mmt_search_topk_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
+                        const float* gscale, int NQ, int NV, int M, int d, int k, uint64_t* ws, float* scores, int64_t* index,
+                        void* stream);
+int mmt_search_topk_fp8_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
+                           const float* gscale, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
+                           const int64_t* exclude, int E, uint64_t* ws, float* scores, int64_t* index, void* stream);
+int mmt_search_rank_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
+                        const float* gscale, int NQ, int NV, int M, int d, const int64_t* targets, int T, int32_t* ws,
+                        int32_t* greater, int32_t* equal, void* stream);
+int mmt_search_rank_fp8_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
+                           const float* gscale, int NQ, int NV, int M, int d, const int64_t* targets, int T,
+                           const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
+int mmt_search_thresholds_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
+                              const float* gscale, int NQ, int NV, int M, int d, const int64_t* targets, int T, float* thr,
+                              void* stream);
+int mmt_search_count_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
+                         const float* gscale, int NQ, int NV, int M, int d, const float* thr, int T, const uint32_t* subset,
+                         int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
+int mmt_search_range_count_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
+                               const float* gw, const float* gscale, int NQ, int NV, int M, int d, const float* thr,
+                               const uint32_t* subset, int32_t* ws, int64_t* row_counts, void* stream);
+int mmt_search_range_fill_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
+                              const float* gscale, int NQ, int NV, int M, int d, const float* thr, const uint32_t* subset,
+                              const int32_t* ws, const int64_t* offsets, int64_t* indices, float* scores, void* stream);
 /* Grouped search (search_group.hip): the k best GROUPS of a gallery whose items carry a group id -- the clips of a video,
  * the captions of a video -- each with its best item, without the N_query x N_gallery matrix.  groups int32 [NV], values
  * >= 0, any labelling (ids need not be dense, members need not be adjacent).  Per query the representative of a group is

@@ -268,6 +268,24 @@ SIGNATURES = {
                                       c_vp]),
     'mmt_search_range_fill_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
                                            c_vp, c_vp, c_vp]),
+    # fp8 gallery: the _bf16 signatures with gscale after gw
+    'mmt_search_fold_fp8': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    'mmt_search_topk_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
+                                    c_vp]),
+    'mmt_search_topk_fp8_ex': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                       c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_rank_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
+                                    c_vp, c_vp]),
+    'mmt_search_rank_fp8_ex': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp,
+                                       c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_thresholds_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp,
+                                          c_vp]),
+    'mmt_search_count_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_range_count_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
+                                           c_vp, c_vp]),
+    'mmt_search_range_fill_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp, c_vp, c_vp]),
     'mmt_search_topk_groups': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        c_vp, c_vp]),
     'mmt_search_topk_groups_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,

@@ -26,6 +26,9 @@
 //                                      definition): the K loop on v_mfma_f32_32x32x16_bf16 with the fp32 query as a bf16
 //                                      hi / lo pair; same block, tile, accumulator layout, epilogue, selection, workspace
 //                                      and merge.
+//   <true, TkFp8Args>, <true, TkFp8MaskedArgs>   : a gallery stored in fp8 with a scale per item (search_fp8.hip): the
+//                                      bf16 kernels with the gallery widened to bf16 on its way into LDS and the scale in
+//                                      the epilogue (tk_tile reads kFp8 off the block).
 //   <BF16, NmTopkArgs>               : the masked kernels with tk_tile_norm between the score epilogue and the selection:
 //                                      ranks by and returns the querybank-normalised score' (search_norm.hip).
 // The argument blocks stay separate types with their layouts as they are: a field appended to TkArgs moves the hidden
@@ -75,6 +78,20 @@ struct TkBf16Args {
 };
 
 struct TkBf16MaskedArgs : TkBf16Args {  // as TkMaskedArgs
+  const uint32_t* subset;
+  const int64_t* exclude;
+  int E;
+  static constexpr TkMask kMask = TK_MASK_NULLABLE;
+};
+
+// A gallery stored in fp8 (search_fp8.hip): e4m3fn codes behind g, one power-of-two scale per item.  The block says so in
+// kFp8 (search_scan.h: TkFp8); the bf16 blocks keep their layout.
+struct TkFp8Args : TkBf16Args {
+  const float* gscale;  // [NV]
+  static constexpr bool kFp8 = true;
+};
+
+struct TkFp8MaskedArgs : TkFp8Args {  // as TkMaskedArgs
   const uint32_t* subset;
   const int64_t* exclude;
   int E;
@@ -236,6 +253,8 @@ void tk_topk_lds_limits() {
                        {(const void*)topk_scan_kernel<false, TkMaskedArgs>, f32 + ex},
                        {(const void*)topk_scan_kernel<true, TkBf16Args>, bf16},
                        {(const void*)topk_scan_kernel<true, TkBf16MaskedArgs>, bf16 + ex},
+                       {(const void*)topk_scan_kernel<true, TkFp8Args>, bf16},
+                       {(const void*)topk_scan_kernel<true, TkFp8MaskedArgs>, bf16 + ex},
                        {(const void*)topk_scan_kernel<false, NmTopkArgs>, f32 + ex},
                        {(const void*)topk_scan_kernel<true, NmTopkArgs>, bf16 + ex}});
 }
@@ -248,7 +267,7 @@ int tk_search(Args a, const void* q, const void* q_lo, const float* qw, const vo
               int d, int k, const uint32_t* subset, const int64_t* exclude, int E, bool rest, uint64_t* ws, float* scores,
               int64_t* index, void* stream) {
   if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !rest || !ws || !index || !tk_args_ok(NQ, NV, k) ||
-      !tk_shape_ok(NQ, NV, M, d, BF16))
+      !tk_shape_ok(NQ, NV, M, d, BF16, TkFp8<Args>::value))
     return MMT_ERR_ARG;
   if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g) & 15) return MMT_ERR_ALIGN;
   if (E < 0 || E > TK_MAXE || (E > 0 && !exclude)) return MMT_ERR_ARG;
@@ -262,7 +281,7 @@ int tk_search(Args a, const void* q, const void* q_lo, const float* qw, const vo
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(a.n_qt * a.n_chunks);
   const size_t lds = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + tk_state_lds(k);
-  using Plain = std::conditional_t<BF16, TkBf16Args, TkArgs>;
+  using Plain = std::conditional_t<TkFp8<Args>::value, TkFp8Args, std::conditional_t<BF16, TkBf16Args, TkArgs>>;
   if (Args::kNorm || subset || E)
     hipLaunchKernelGGL((topk_scan_kernel<BF16, Args>), grid, dim3(256), lds + tk_exclude_lds(E), s, a);
   else if constexpr (!Args::kNorm)  // constexpr only so that the slice to Plain is not instantiated for NmTopkArgs
@@ -306,6 +325,23 @@ extern "C" int mmt_search_topk_bf16(const uint16_t* q_hi, const uint16_t* q_lo, 
                                     const float* gw, int NQ, int NV, int M, int d, int k, uint64_t* ws, float* scores,
                                     int64_t* index, void* stream) {
   return mmt_search_topk_bf16_ex(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, nullptr, nullptr, 0, ws, scores, index, stream);
+}
+
+extern "C" int mmt_search_topk_fp8_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
+                                      const float* gw, const float* gscale, int NQ, int NV, int M, int d, int k,
+                                      const uint32_t* subset, const int64_t* exclude, int E, uint64_t* ws, float* scores,
+                                      int64_t* index, void* stream) {
+  TkFp8MaskedArgs a = {};
+  a.gscale = gscale;
+  return tk_search<true>(a, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, gscale != nullptr, ws, scores, index,
+                         stream);
+}
+
+extern "C" int mmt_search_topk_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
+                                   const float* gw, const float* gscale, int NQ, int NV, int M, int d, int k, uint64_t* ws,
+                                   float* scores, int64_t* index, void* stream) {
+  return mmt_search_topk_fp8_ex(q_hi, q_lo, qw, gf, gw, gscale, NQ, NV, M, d, k, nullptr, nullptr, 0, ws, scores, index,
+                                stream);
 }
 
 extern "C" int mmt_search_topk_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,

@@ -48,8 +48,24 @@ struct RgMaskedArgs : RgArgs {
   const uint32_t* subset;  // bit g & 31 of word g >> 5 allows item g (16-byte aligned)
 };
 
-template <bool BF16, bool FILL, bool MASKED>
-__global__ __launch_bounds__(256) void range_kernel(std::conditional_t<MASKED, RgMaskedArgs, RgArgs> a) {
+// A gallery stored in fp8 (search_fp8.hip): e4m3fn codes behind g, one power-of-two scale per item; the block says so in
+// kFp8 (search_scan.h: TkFp8).
+struct RgFp8Args : RgArgs {
+  const float* gscale;     // [NV]
+  static constexpr bool kFp8 = true;
+};
+
+struct RgFp8MaskedArgs : RgFp8Args {  // as RgMaskedArgs
+  const uint32_t* subset;
+};
+
+// The unmasked block of a masked one.
+template <class Args>
+using RgPlain = std::conditional_t<TkFp8<Args>::value, RgFp8Args, RgArgs>;
+
+// Args: RgArgs / RgMaskedArgs unless given (the fp8 blocks).
+template <bool BF16, bool FILL, bool MASKED, class Args = std::conditional_t<MASKED, RgMaskedArgs, RgArgs>>
+__global__ __launch_bounds__(256) void range_kernel(Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int kUnion = BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES;
   constexpr int kRows = TK_Q / 4;  // rows per wave
@@ -137,10 +153,11 @@ __global__ __launch_bounds__(256) void range_offsets_kernel(int32_t* __restrict_
 
 namespace {
 // The gate and the fill of the four entry points: 0, or the error code.  `rest`: the entry's other pointers are all there.
-template <bool BF16>
-int rg_fill(RgMaskedArgs& a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV,
+template <bool BF16, class Args>
+int rg_fill(Args& a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV,
             int M, int d, const float* thr, const uint32_t* subset, const int32_t* ws, bool rest) {
-  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !thr || !ws || !rest || !tk_shape_ok(NQ, NV, M, d, BF16))
+  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !thr || !ws || !rest ||
+      !tk_shape_ok(NQ, NV, M, d, BF16, TkFp8<Args>::value))
     return MMT_ERR_ARG;
   if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
   a.q = q; a.q_lo = q_lo; a.qw = qw; a.g = g; a.gw = gw; a.thr = thr; a.ws = const_cast<int32_t*>(ws); a.subset = subset;
@@ -149,36 +166,44 @@ int rg_fill(RgMaskedArgs& a, const void* q, const void* q_lo, const float* qw, c
   return 0;
 }
 
-template <bool BF16, bool FILL>
-void rg_launch(const RgMaskedArgs& a, hipStream_t s) {
+template <bool BF16, bool FILL, class Args>
+void rg_launch(const Args& a, hipStream_t s) {
   if (a.subset)
-    hipLaunchKernelGGL((range_kernel<BF16, FILL, true>), dim3(a.n_qt * a.n_chunks), dim3(256), tk_base_lds<BF16>(), s, a);
+    hipLaunchKernelGGL((range_kernel<BF16, FILL, true, Args>), dim3(a.n_qt * a.n_chunks), dim3(256), tk_base_lds<BF16>(), s,
+                       a);
   else
-    hipLaunchKernelGGL((range_kernel<BF16, FILL, false>), dim3(a.n_qt * a.n_chunks), dim3(256), tk_base_lds<BF16>(), s,
-                       (RgArgs)a);
+    hipLaunchKernelGGL((range_kernel<BF16, FILL, false, RgPlain<Args>>), dim3(a.n_qt * a.n_chunks), dim3(256),
+                       tk_base_lds<BF16>(), s, (RgPlain<Args>)a);
 }
 
-template <bool BF16>
-int rg_count(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M, int d,
-             const float* thr, const uint32_t* subset, int32_t* ws, int64_t* row_counts, void* stream) {
-  RgMaskedArgs a = {};
-  if (const int rc = rg_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, thr, subset, ws, row_counts != nullptr)) return rc;
+// (Args = RgMaskedArgs, or RgFp8MaskedArgs with gscale set by the caller; `rest`: the entry's other pointers are there)
+template <bool BF16, class Args>
+int rg_count(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
+             int d, const float* thr, const uint32_t* subset, bool rest, int32_t* ws, int64_t* row_counts, void* stream) {
+  if (const int rc = rg_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, thr, subset, ws, rest && row_counts != nullptr))
+    return rc;
   rg_launch<BF16, false>(a, (hipStream_t)stream);
   hipLaunchKernelGGL(range_offsets_kernel, dim3((NQ + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws, NQ, a.n_chunks,
                      row_counts);
   return (int)hipGetLastError();
 }
 
-template <bool BF16>
-int rg_fill_hits(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
-                 int d, const float* thr, const uint32_t* subset, const int32_t* ws, const int64_t* offsets,
-                 int64_t* indices, float* scores, void* stream) {
-  RgMaskedArgs a = {};
-  if (const int rc = rg_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, thr, subset, ws, offsets && indices && scores))
+template <bool BF16, class Args>
+int rg_fill_hits(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV,
+                 int M, int d, const float* thr, const uint32_t* subset, bool rest, const int32_t* ws,
+                 const int64_t* offsets, int64_t* indices, float* scores, void* stream) {
+  if (const int rc =
+          rg_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, thr, subset, ws, rest && offsets && indices && scores))
     return rc;
   a.offsets = offsets; a.indices = indices; a.scores = scores;
   rg_launch<BF16, true>(a, (hipStream_t)stream);
   return (int)hipGetLastError();
+}
+
+RgFp8MaskedArgs rg_fp8_args(const float* gscale) {
+  RgFp8MaskedArgs a = {};
+  a.gscale = gscale;
+  return a;
 }
 }  // namespace
 
@@ -190,24 +215,40 @@ extern "C" int64_t mmt_range_workspace_ints(int NQ, int NV) {
 extern "C" int mmt_search_range_count(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
                                       int M, int d, const float* thr, const uint32_t* subset, int32_t* ws,
                                       int64_t* row_counts, void* stream) {
-  return rg_count<false>(qf, nullptr, qw, gf, gw, NQ, NV, M, d, thr, subset, ws, row_counts, stream);
+  return rg_count<false>(RgMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, thr, subset, true, ws, row_counts, stream);
 }
 
 extern "C" int mmt_search_range_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
                                            const float* gw, int NQ, int NV, int M, int d, const float* thr,
                                            const uint32_t* subset, int32_t* ws, int64_t* row_counts, void* stream) {
-  return rg_count<true>(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, ws, row_counts, stream);
+  return rg_count<true>(RgMaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, true, ws, row_counts, stream);
 }
 
 extern "C" int mmt_search_range_fill(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
                                      int M, int d, const float* thr, const uint32_t* subset, const int32_t* ws,
                                      const int64_t* offsets, int64_t* indices, float* scores, void* stream) {
-  return rg_fill_hits<false>(qf, nullptr, qw, gf, gw, NQ, NV, M, d, thr, subset, ws, offsets, indices, scores, stream);
+  return rg_fill_hits<false>(RgMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, thr, subset, true, ws, offsets, indices, scores, stream);
 }
 
 extern "C" int mmt_search_range_fill_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
                                           const float* gw, int NQ, int NV, int M, int d, const float* thr,
                                           const uint32_t* subset, const int32_t* ws, const int64_t* offsets,
                                           int64_t* indices, float* scores, void* stream) {
-  return rg_fill_hits<true>(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, ws, offsets, indices, scores, stream);
+  return rg_fill_hits<true>(RgMaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, true, ws, offsets, indices, scores, stream);
+}
+
+extern "C" int mmt_search_range_count_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
+                                          const float* gw, const float* gscale, int NQ, int NV, int M, int d,
+                                          const float* thr, const uint32_t* subset, int32_t* ws, int64_t* row_counts,
+                                          void* stream) {
+  return rg_count<true>(rg_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, gscale != nullptr, ws,
+                        row_counts, stream);
+}
+
+extern "C" int mmt_search_range_fill_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
+                                         const float* gw, const float* gscale, int NQ, int NV, int M, int d, const float* thr,
+                                         const uint32_t* subset, const int32_t* ws, const int64_t* offsets, int64_t* indices,
+                                         float* scores, void* stream) {
+  return rg_fill_hits<true>(rg_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, gscale != nullptr, ws,
+                            offsets, indices, scores, stream);
 }

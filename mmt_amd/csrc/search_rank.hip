@@ -65,6 +65,22 @@ struct RkMaskedArgs : RkArgs {
   static constexpr TkMask kMask = TK_MASK_SET;
 };
 
+// A gallery stored in fp8 (search_fp8.hip): e4m3fn codes behind g, one power-of-two scale per item; the block says so in
+// kFp8 (search_scan.h: TkFp8).
+struct RkFp8Args : RkArgs {
+  const float* gscale;     // [NV]
+  static constexpr bool kFp8 = true;
+};
+
+struct RkFp8MaskedArgs : RkFp8Args {  // as RkMaskedArgs
+  const uint32_t* subset;
+  static constexpr TkMask kMask = TK_MASK_SET;
+};
+
+// The unmasked block of a masked one: what the threshold pass and a count pass without a subset are launched with.
+template <class Args>
+using RkPlain = std::conditional_t<TkFp8<Args>::value, RkFp8Args, RkArgs>;
+
 struct NmRankArgs : NmArgs {
   const int64_t* targets;   // THR: [NQ][T]
   float* thr;               // [NQ][T]
@@ -74,7 +90,7 @@ struct NmRankArgs : NmArgs {
 };
 
 // The threshold pass (THR) or the count pass of one block, on the plain score or (Args::kNorm) on score'; Args = RkArgs,
-// RkMaskedArgs or NmRankArgs.
+// RkMaskedArgs, their fp8 forms or NmRankArgs.
 template <bool BF16, bool THR, class Args>
 __global__ __launch_bounds__(256) void rank_kernel(Args a) {
   constexpr TkMask MASK = Args::kMask;
@@ -157,7 +173,8 @@ bool rk_args_ok(int NQ, int NV, int T) { return NQ > 0 && NV > 0 && T >= 1 && T 
 template <bool BF16, class Args>
 int rk_fill(Args& a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
             int d, int T, const uint32_t* subset, bool rest) {
-  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !rest || !rk_args_ok(NQ, NV, T) || !tk_shape_ok(NQ, NV, M, d, BF16))
+  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !rest || !rk_args_ok(NQ, NV, T) ||
+      !tk_shape_ok(NQ, NV, M, d, BF16, TkFp8<Args>::value))
     return MMT_ERR_ARG;
   if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
   a.q = q; a.q_lo = q_lo; a.qw = qw; a.g = g; a.gw = gw; a.subset = subset;
@@ -170,40 +187,44 @@ template <bool BF16, class Args>
 void rk_launch_thresholds(const Args& a, hipStream_t s) {
   const int n_pt = (TK_Q * a.T + TK_G - 1) / TK_G;  // threshold tiles per query tile
   const dim3 grid(a.n_qt * n_pt);
-  using Plain = std::conditional_t<Args::kNorm, Args, RkArgs>;  // the threshold pass has no subset
+  using Plain = std::conditional_t<Args::kNorm, Args, RkPlain<Args>>;  // the threshold pass has no subset
   hipLaunchKernelGGL((rank_kernel<BF16, true, Plain>), grid, dim3(256), tk_base_lds<BF16>() + TK_G * 4, s, (Plain)a);
 }
 
 // The count kernels' T = 32 footprint reaches the 64 KiB default limit (bf16: exactly).
-template <bool BF16>
+template <bool BF16, bool FP8>
 void rk_lds_limits() {
   static bool done[64] = {};
   constexpr size_t bytes = tk_base_lds<BF16>() + (size_t)TK_Q * RK_MAXT * 12;
-  tk_lds_limits(done, {{(const void*)rank_kernel<BF16, false, RkArgs>, bytes},
-                       {(const void*)rank_kernel<BF16, false, RkMaskedArgs>, bytes},
-                       {(const void*)rank_kernel<BF16, false, NmRankArgs>, bytes}});
+  if constexpr (FP8)
+    tk_lds_limits(done, {{(const void*)rank_kernel<BF16, false, RkFp8Args>, bytes},
+                         {(const void*)rank_kernel<BF16, false, RkFp8MaskedArgs>, bytes}});
+  else
+    tk_lds_limits(done, {{(const void*)rank_kernel<BF16, false, RkArgs>, bytes},
+                         {(const void*)rank_kernel<BF16, false, RkMaskedArgs>, bytes},
+                         {(const void*)rank_kernel<BF16, false, NmRankArgs>, bytes}});
 }
 
 // The count pass and the reduce.
 template <bool BF16, class Args>
 int rk_launch_count(const Args& a, int32_t* greater, int32_t* equal, hipStream_t s) {
-  rk_lds_limits<BF16>();
+  rk_lds_limits<BF16, TkFp8<Args>::value>();
   const dim3 grid(a.n_qt * a.n_chunks);
   const size_t lds = tk_base_lds<BF16>() + (size_t)TK_Q * a.T * 12;
   if (Args::kNorm || a.subset)
     hipLaunchKernelGGL((rank_kernel<BF16, false, Args>), grid, dim3(256), lds, s, a);
   else if constexpr (!Args::kNorm)  // constexpr only so that the slice to RkArgs is not instantiated for NmRankArgs
-    hipLaunchKernelGGL((rank_kernel<BF16, false, RkArgs>), grid, dim3(256), lds, s, (RkArgs)a);
+    hipLaunchKernelGGL((rank_kernel<BF16, false, RkPlain<Args>>), grid, dim3(256), lds, s, (RkPlain<Args>)a);
   return rk_reduce_launch(a.cnt, (int64_t)a.NQ * a.T, a.n_chunks, greater, equal, s);
 }
 
 // workspace (int32 units): thresholds [NQ][T] fp32, then (greater, equal) [NQ][T][n_chunks][2]
-template <bool BF16>
-int rk_rank(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M, int d,
-            const int64_t* targets, int T, const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal,
-            void* stream) {
-  RkMaskedArgs a = {};
-  if (const int rc = rk_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, T, subset, targets && ws && greater && equal))
+// (Args = RkMaskedArgs, or RkFp8MaskedArgs with gscale set by the caller)
+template <bool BF16, class Args>
+int rk_rank(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
+            int d, const int64_t* targets, int T, const uint32_t* subset, bool rest, int32_t* ws, int32_t* greater,
+            int32_t* equal, void* stream) {
+  if (const int rc = rk_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, T, subset, rest && targets && ws && greater && equal))
     return rc;
   a.targets = targets; a.thr = (float*)ws; a.cnt = ws + (int64_t)NQ * T;
   rk_launch_thresholds<BF16>(a, (hipStream_t)stream);
@@ -238,6 +259,12 @@ NmRankArgs nm_rank_args(float beta, const float* lse) {
   a.beta = beta; a.lse = lse;
   return a;
 }
+
+RkFp8MaskedArgs rk_fp8_args(const float* gscale) {
+  RkFp8MaskedArgs a = {};
+  a.gscale = gscale;
+  return a;
+}
 }  // namespace
 
 extern "C" int64_t mmt_rank_workspace_ints(int NQ, int NV, int T) {
@@ -248,26 +275,41 @@ extern "C" int64_t mmt_rank_workspace_ints(int NQ, int NV, int T) {
 extern "C" int mmt_search_rank_ex(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
                                   int d, const int64_t* targets, int T, const uint32_t* subset, int32_t* ws,
                                   int32_t* greater, int32_t* equal, void* stream) {
-  return rk_rank<false>(qf, nullptr, qw, gf, gw, NQ, NV, M, d, targets, T, subset, ws, greater, equal, stream);
+  return rk_rank<false>(RkMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, targets, T, subset, true, ws, greater, equal, stream);
 }
 
 extern "C" int mmt_search_rank(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
                                int d, const int64_t* targets, int T, int32_t* ws, int32_t* greater, int32_t* equal,
                                void* stream) {
-  return rk_rank<false>(qf, nullptr, qw, gf, gw, NQ, NV, M, d, targets, T, nullptr, ws, greater, equal, stream);
+  return rk_rank<false>(RkMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, targets, T, nullptr, true, ws, greater, equal, stream);
 }
 
 extern "C" int mmt_search_rank_bf16_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
                                        const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T,
                                        const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal,
                                        void* stream) {
-  return rk_rank<true>(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, subset, ws, greater, equal, stream);
+  return rk_rank<true>(RkMaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, subset, true, ws, greater, equal, stream);
 }
 
 extern "C" int mmt_search_rank_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
                                     const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T,
                                     int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
-  return rk_rank<true>(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, nullptr, ws, greater, equal, stream);
+  return rk_rank<true>(RkMaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, nullptr, true, ws, greater, equal, stream);
+}
+
+extern "C" int mmt_search_rank_fp8_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
+                                      const float* gw, const float* gscale, int NQ, int NV, int M, int d,
+                                      const int64_t* targets, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
+                                      int32_t* equal, void* stream) {
+  return rk_rank<true>(rk_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, subset, gscale != nullptr, ws,
+                       greater, equal, stream);
+}
+
+extern "C" int mmt_search_rank_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
+                                   const float* gw, const float* gscale, int NQ, int NV, int M, int d, const int64_t* targets,
+                                   int T, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
+  return rk_rank<true>(rk_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, nullptr, gscale != nullptr, ws,
+                       greater, equal, stream);
 }
 
 extern "C" int64_t mmt_count_workspace_ints(int NQ, int NV, int T) {
@@ -298,6 +340,21 @@ extern "C" int mmt_search_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo,
                                      const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
   return rk_count<true>(RkMaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, T, subset, true, ws, greater, equal,
                         stream);
+}
+
+extern "C" int mmt_search_thresholds_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
+                                         const float* gw, const float* gscale, int NQ, int NV, int M, int d,
+                                         const int64_t* targets, int T, float* thr, void* stream) {
+  return rk_thresholds<true>(rk_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, gscale != nullptr, thr,
+                             stream);
+}
+
+extern "C" int mmt_search_count_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
+                                    const float* gw, const float* gscale, int NQ, int NV, int M, int d, const float* thr,
+                                    int T, const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal,
+                                    void* stream) {
+  return rk_count<true>(rk_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, T, subset, gscale != nullptr, ws,
+                        greater, equal, stream);
 }
 
 extern "C" int mmt_search_thresholds_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,

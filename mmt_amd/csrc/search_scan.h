@@ -1,9 +1,10 @@
 // The scoring tile of the gallery scans, shared by every kernel that scores a (query, item) pair: the top-k kernels
 // (search.hip: a running top-k per query), the count / threshold kernels (search_rank.hip: a counter per query and
 // target), the range kernels (search_range.hip: every hit) and the querybank column pass (search_norm.hip).  Block shape,
-// the two K loops (fp32 gallery on v_mfma_f32_32x32x2_f32, bf16 gallery on v_mfma_f32_32x32x16_bf16), the gated-denominator
-// epilogue and the querybank rewrite are composed in ONE place, tk_tile, so a pair has the same score bits on every path
-// by construction.  The subset gate of a tile (tk_tile_mask), the chunk rule and launch geometry (tk_chunk, tk_geometry),
+// the two K loops (fp32 gallery on v_mfma_f32_32x32x2_f32, bf16 gallery on v_mfma_f32_32x32x16_bf16 -- an fp8 gallery is
+// widened to bf16 on its way into LDS and runs the bf16 loop), the gated-denominator epilogue (with an fp8 gallery: the
+// item's scale first) and the querybank rewrite are composed in ONE place, tk_tile, so a pair has the same score bits on
+// every path by construction.  The subset gate of a tile (tk_tile_mask), the chunk rule and launch geometry (tk_chunk, tk_geometry),
 // the shape gate and the per-device dynamic-LDS limit (tk_lds_limits) are here once as well, and so are the steps that
 // follow a tile on more than one path: the count step (tk_tile_count), the query-set pooling (tk_tile_pool) and the item-set
 // pooling (tk_tile_pool_items, with the unaligned subset window tk_tile_mask_window).
@@ -13,6 +14,7 @@
 #pragma once
 #include <cmath>
 #include <initializer_list>
+#include <type_traits>
 
 #include "mmt_common.h"
 #include "../../include/mmt_hip.h"
@@ -98,27 +100,49 @@ __device__ __forceinline__ void tk_scan_f32(f32x16 (&acc)[2], unsigned char* sme
   }
 }
 
-// bf16-gallery K loop of one tile (smem: TKB_SLAB_BYTES): per 64-wide slab the block stages hi(Q'), lo(Q') (64 rows each)
-// and the gallery (128 rows); a wave reads each gallery fragment ONCE and feeds it to the hi and the lo MFMA.  Barriers as
-// tk_scan_f32.  K % 8 == 0, so a 16-byte load is inside the row or past its end as a whole.
-template <class GRow>
-__device__ __forceinline__ void tk_scan_bf16(f32x16 (&acc)[2], unsigned char* smem, const bf16_t* q_hi, const bf16_t* q_lo,
-                                             const bf16_t* g, int NQ, int K, int q0, GRow grow, int tid, int wq, int wg,
-                                             int l31, int h) {
+// 16 fp8 values (OCP e4m3fn, one 16-byte load) -> 16 bf16 as two 16-byte halves, exactly: every e4m3fn value is a bf16
+// value (3 mantissa bits against 7, and the range fits), so the upper half of v_cvt_pk_f32_fp8's fp32 IS the bf16.
+__device__ __forceinline__ void tk_widen_fp8(const u32x4& v, u32x4& lo, u32x4& hi) {
+  uint32_t o[8];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[w], false);  // bytes 0, 1 of dword w
+    const f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[w], true);   // bytes 2, 3
+    o[2 * w] = (__float_as_uint(a[0]) >> 16) | (__float_as_uint(a[1]) & 0xffff0000u);
+    o[2 * w + 1] = (__float_as_uint(b[0]) >> 16) | (__float_as_uint(b[1]) & 0xffff0000u);
+  }
+  lo = u32x4{o[0], o[1], o[2], o[3]};
+  hi = u32x4{o[4], o[5], o[6], o[7]};
+}
+
+// K loop of one tile over a gallery stored in 16 bits or fewer (smem: TKB_SLAB_BYTES): per 64-wide slab the block stages
+// hi(Q'), lo(Q') (64 rows each) and the gallery (128 rows) as bf16; a wave reads each gallery fragment ONCE and feeds it to
+// the hi and the lo MFMA.  Barriers as tk_scan_f32.  The gallery slab is 128 rows x 64 elements:
+//   bf16 (FP8 = false): 128 bytes of a row = 8 sixteen-byte loads, 4 per thread, stored to LDS as they are (K % 8 == 0);
+//   fp8  (FP8 = true) :  64 bytes of a row = 4 sixteen-byte loads, 2 per thread, each widened in registers to 16 bf16
+//                        (tk_widen_fp8) and stored as two 16-byte halves to the same place of the same slab (K % 16 == 0).
+// Either way a 16-byte load is inside the row or past its end as a whole, and LDS layout, pitch and MFMA loop are one.
+template <bool FP8, class GRow>
+__device__ __forceinline__ void tk_scan_b16(f32x16 (&acc)[2], unsigned char* smem, const bf16_t* q_hi, const bf16_t* q_lo,
+                                            const void* g, int NQ, int K, int q0, GRow grow, int tid, int wq, int wg, int l31,
+                                            int h) {
+  constexpr int NB = FP8 ? 2 : 4;    // gallery loads per thread and slab
+  constexpr int SH = FP8 ? 2 : 3;    // log2 of the loads per gallery row and slab
+  constexpr int EL = FP8 ? 16 : 8;   // elements per load
   bf16_t* sAh = (bf16_t*)smem;          // [TK_Q][TKB_LD]  slab of hi(Q')
   bf16_t* sAl = sAh + TK_Q * TKB_LD;    // [TK_Q][TKB_LD]  slab of lo(Q')
-  bf16_t* sB = sAl + TK_Q * TKB_LD;     // [TK_G][TKB_LD]  slab of the stored gallery
+  bf16_t* sB = sAl + TK_Q * TKB_LD;     // [TK_G][TKB_LD]  slab of the stored gallery, as bf16
   const u32x4 zero = {0u, 0u, 0u, 0u};
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  // staging, 16 bytes = 8 bf16 per load: hi and lo slabs = 64 rows x 8 (2 per thread each), gallery slab = 128 rows x 8
-  // (4 per thread)
-  int gr[4];
+  // staging, 16 bytes per load: hi and lo slabs = 64 rows x 8 (2 per thread each), gallery slab = 128 rows x 8 (bf16) or
+  // x 4 (fp8)
+  int gr[NB];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) gr[j] = grow((tid + 256 * j) >> 3);
-  u32x4 rh[2], rl[2], rb[4];
+  for (int j = 0; j < NB; ++j) gr[j] = grow((tid + 256 * j) >> SH);
+  u32x4 rh[2], rl[2], rb[NB];
   auto load = [&](int kb) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -129,9 +153,13 @@ __device__ __forceinline__ void tk_scan_bf16(f32x16 (&acc)[2], unsigned char* sm
       rl[j] = in ? *(const u32x4*)(q_lo + off) : zero;
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = kb + ((tid + 256 * j) & 7) * 8;
-      rb[j] = (gr[j] >= 0 && c < K) ? *(const u32x4*)(g + (int64_t)gr[j] * K + c) : zero;
+    for (int j = 0; j < NB; ++j) {
+      const int c = kb + ((tid + 256 * j) & ((1 << SH) - 1)) * EL;
+      const int64_t off = (int64_t)gr[j] * K + c;
+      if constexpr (FP8)
+        rb[j] = (gr[j] >= 0 && c < K) ? *(const u32x4*)((const uint8_t*)g + off) : zero;
+      else
+        rb[j] = (gr[j] >= 0 && c < K) ? *(const u32x4*)((const bf16_t*)g + off) : zero;
     }
   };
   load(0);
@@ -144,7 +172,18 @@ __device__ __forceinline__ void tk_scan_bf16(f32x16 (&acc)[2], unsigned char* sm
       *(u32x4*)(sAl + o) = rl[j];
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { const int i = tid + 256 * j; *(u32x4*)(sB + (i >> 3) * TKB_LD + (i & 7) * 8) = rb[j]; }
+    for (int j = 0; j < NB; ++j) {
+      const int i = tid + 256 * j;
+      bf16_t* dst = sB + (i >> SH) * TKB_LD + (i & ((1 << SH) - 1)) * EL;
+      if constexpr (FP8) {
+        u32x4 lo, hi;
+        tk_widen_fp8(rb[j], lo, hi);
+        *(u32x4*)dst = lo;
+        *(u32x4*)(dst + 8) = hi;
+      } else {
+        *(u32x4*)dst = rb[j];
+      }
+    }
     __syncthreads();
     if (kb + TKB_BK < K) load(kb + TKB_BK);
     // 16 contraction values per MFMA; lane half h holds k = kk + 8h .. + 7 of its row (A) / column (B)
@@ -162,15 +201,43 @@ __device__ __forceinline__ void tk_scan_bf16(f32x16 (&acc)[2], unsigned char* sm
   }
 }
 
+// bf16-gallery K loop of one tile: g [.][K] bf16 bits.
+template <class GRow>
+__device__ __forceinline__ void tk_scan_bf16(f32x16 (&acc)[2], unsigned char* smem, const bf16_t* q_hi, const bf16_t* q_lo,
+                                             const bf16_t* g, int NQ, int K, int q0, GRow grow, int tid, int wq, int wg,
+                                             int l31, int h) {
+  tk_scan_b16<false>(acc, smem, q_hi, q_lo, g, NQ, K, q0, grow, tid, wq, wg, l31, h);
+}
+
+// fp8-gallery K loop of one tile: g [.][K] e4m3fn codes, half the gallery bytes of tk_scan_bf16 and the same arithmetic.
+template <class GRow>
+__device__ __forceinline__ void tk_scan_fp8(f32x16 (&acc)[2], unsigned char* smem, const bf16_t* q_hi, const bf16_t* q_lo,
+                                            const uint8_t* g, int NQ, int K, int q0, GRow grow, int tid, int wq, int wg,
+                                            int l31, int h) {
+  tk_scan_b16<true>(acc, smem, q_hi, q_lo, g, NQ, K, q0, grow, tid, wq, wg, l31, h);
+}
+
+// fl(a * b) as an instruction of its own: the optimiser cannot contract it with a following add or subtract into an fma
+// (plain `a * b`, and __fmul_rn which is defined as that, may be under -ffast-math).
+__device__ __forceinline__ float tk_mul_rn(float a, float b) {
+  float r;
+  asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
 // Epilogue of one 64 x 128 tile held as 32x32 MFMA accumulators (lane: column wg*64 + t*32 + l31, rows
 // wq*32 + (r&3) + 8*(r>>2) + 4h -- the layout of v_mfma_f32_32x32x2_f32 and v_mfma_f32_32x32x16_bf16 alike): divides by
-// the gated denominator and leaves the scores in sS [TK_Q][TK_SLD].
-template <class GRow>
+// the gated denominator and leaves the scores in sS [TK_Q][TK_SLD].  SCALE (an fp8 gallery): the accumulator is first
+// multiplied by the item's scale gscale[grow(col)], a power of two, as a rounded multiply of its own (tk_mul_rn):
+// score = fl(fl(acc * scale) / den); a column without an item gets the scale 0.
+template <bool SCALE = false, class GRow>
 __device__ __forceinline__ void tk_tile_scores(const f32x16 (&acc)[2], float* sS, const float* sQw, const float* gw, int M,
-                                               GRow grow, int wq, int wg, int l31, int h) {
+                                               GRow grow, int wq, int wg, int l31, int h, const float* gscale = nullptr) {
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const int col = wg * 64 + t * 32 + l31, g = grow(col);
+    float sc = 1.f;
+    if constexpr (SCALE) sc = g >= 0 ? gscale[g] : 0.f;
     float den[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) den[r] = 0.f;
@@ -182,17 +249,11 @@ __device__ __forceinline__ void tk_tile_scores(const f32x16 (&acc)[2], float* sS
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      sS[row * TK_SLD + col] = acc[t][r] / (den[r] == 0.f ? 1e-5f : den[r]);
+      float num = acc[t][r];
+      if constexpr (SCALE) num = tk_mul_rn(num, sc);
+      sS[row * TK_SLD + col] = num / (den[r] == 0.f ? 1e-5f : den[r]);
     }
   }
-}
-
-// fl(a * b) as an instruction of its own: the optimiser cannot contract it with a following add or subtract into an fma
-// (plain `a * b`, and __fmul_rn which is defined as that, may be under -ffast-math).
-__device__ __forceinline__ float tk_mul_rn(float a, float b) {
-  float r;
-  asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
 }
 
 // Querybank normalisation of one score tile in place (tk_tile<., true> only): sS[r][c] = fl(fl(beta * sS[r][c]) - lse[item
@@ -369,20 +430,35 @@ __device__ __forceinline__ void tk_tile_col_stats(const float* sS, float beta, i
   for (int row = 0; row < rows_live; ++row) p += expf(tk_mul_rn(beta, sS[row * TK_SLD + col]) - m);
 }
 
+// Whether an argument block's gallery is stored in fp8 (e4m3fn codes in g, one fp32 scale per item in gscale): a block
+// says so itself with `static constexpr bool kFp8 = true`, as it says kMask and kNorm; a block that says nothing is not.
+template <class Args, class = void>
+struct TkFp8 { static constexpr bool value = false; };
+template <class Args>
+struct TkFp8<Args, std::void_t<decltype(Args::kFp8)>> { static constexpr bool value = Args::kFp8; };
+
 // One 64 x 128 tile of scores in sS: the K loop, the gated-denominator epilogue and, with NORM, the querybank rewrite to
 // score'.  Ends fenced.  `a` is any of the scans' argument blocks (q, q_lo for BF16, g, gw, NQ, K, M; lse and beta for
-// NORM).
+// NORM; gscale for an fp8 gallery, which takes the BF16 query operands, LDS footprint and MFMA loop).
 template <bool BF16, bool NORM, class Args, class GRow>
 __device__ __forceinline__ void tk_tile(const Args& a, unsigned char* smem, float* sS, const float* sQw, int q0, GRow grow,
                                         int tid, int wq, int wg, int l31, int h) {
+  constexpr bool FP8 = TkFp8<Args>::value;
+  static_assert(!FP8 || BF16, "an fp8 gallery is scanned with the bf16 query pair");
   f32x16 acc[2];
-  if constexpr (BF16)
+  if constexpr (FP8)
+    tk_scan_fp8(acc, smem, (const bf16_t*)a.q, (const bf16_t*)a.q_lo, (const uint8_t*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg,
+                l31, h);
+  else if constexpr (BF16)
     tk_scan_bf16(acc, smem, (const bf16_t*)a.q, (const bf16_t*)a.q_lo, (const bf16_t*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg,
                  l31, h);
   else
     tk_scan_f32(acc, smem, (const float*)a.q, (const float*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg, l31, h);
   __syncthreads();  // the slabs become the score tile
-  tk_tile_scores(acc, sS, sQw, a.gw, a.M, grow, wq, wg, l31, h);
+  if constexpr (FP8)
+    tk_tile_scores<true>(acc, sS, sQw, a.gw, a.M, grow, wq, wg, l31, h, a.gscale);
+  else
+    tk_tile_scores(acc, sS, sQw, a.gw, a.M, grow, wq, wg, l31, h);
   __syncthreads();
   if constexpr (NORM) {
     tk_tile_norm(sS, a.lse, a.beta, grow, tid);
@@ -459,9 +535,10 @@ void tk_geometry(Args& a) {
   a.n_chunks = (a.NV + a.chunk - 1) / a.chunk;
 }
 
-// The shape gate of every scan entry point: folded rows are 16 bytes times a whole number (d % 4 fp32, d % 8 bf16).
-inline bool tk_shape_ok(int NQ, int NV, int M, int d, bool bf16) {
-  return NQ > 0 && NV > 0 && M > 0 && M <= MMT_MAX_EXPERTS && d > 0 && !(d & (bf16 ? 7 : 3));
+// The shape gate of every scan entry point: folded rows are 16 bytes times a whole number (d % 4 fp32, d % 8 bf16,
+// d % 16 fp8).
+inline bool tk_shape_ok(int NQ, int NV, int M, int d, bool bf16, bool fp8 = false) {
+  return NQ > 0 && NV > 0 && M > 0 && M <= MMT_MAX_EXPERTS && d > 0 && !(d & (fp8 ? 15 : bf16 ? 7 : 3));
 }
 
 inline bool tk_beta_ok(float beta) { return beta > 0.f && std::isfinite(beta); }

@@ -22,6 +22,29 @@ matrix cores with the query split into hi = bf16(qf) and lo = bf16(qf - hi) (mmt
 fp64 value of that definition).  Against the float32 index a score moves by at most
 2^-8 * sum_m qw gw <|Q_m|, |G_m|> / sum_m qw gw, i.e. 2^-8 for unit-norm rows.
 
+    index = VideoIndex(vid_embds, vid_weights, dtype=torch.float8_e4m3fn)   # a quarter of the bytes per item (d % 16 == 0)
+    index.folded, index.scales, index.weights     # float8_e4m3fn [capacity, M*d], float32 [capacity], float32 [capacity, M]
+
+A float8_e4m3fn index stores, with f = fold_fp32(G, gw)[g] (the row the float32 index keeps), one power of two per item and
+the row divided by it, rounded once: scale[g] = 2^e, the smallest power of two with max_k |f[k]| / 2^e <= 448 (e clamped to
+-120 .. 120; an all-zero row has scale 1), and stored[g][k] = e4m3fn_rne(f[k] / scale[g]) -- the division is exact, the cast
+is round-to-nearest-even with e4m3's subnormals and never saturates.  The scale depends on the item alone, so the stored
+bytes do not depend on how `add` was chunked or which shard holds the item.  nbytes = capacity * (M*d + 4*M + 4).  The
+values are taken to be finite and `add` does not check them: a NaN or Inf spoils the scale and the row of its own item,
+whose scores then mean nothing, and no other item.  As for bfloat16 only the storage is lossy and the score is defined on
+the stored value:
+    score(q, g) = fl(fl(acc * scale[g]) / den),   acc = <fold_fp32(Q, qw)[q], dequant(stored[g])>,   den = sum_m qw gw
+(0 -> 1e-5), acc computed as on a bfloat16 index -- every e4m3 value is a bf16 value, so the gallery is widened exactly on
+its way to the bf16 matrix cores and the query is the same hi / lo pair (mmt_search_topk_fp8; within 1e-5 of the fp64 value
+of that definition); the scale being a power of two, where it is multiplied in cannot change the bits.  Against the float32
+index only the gallery rounding differs:
+    |score_fp8 - score_fp32| <= (2^-4 * <|qf|, |f|> + 2^-10 * scale[g] * sum_k |qf[k]|) / |den|  + 1e-5
+-- e4m3's unit roundoff for normal values, and the subnormal range below 2^-6 * scale[g].  `search` (plain, subset=,
+exclude=), `rank_counts`, `ranks`, `target_scores`, `threshold_counts` and `range_search` work on it, on both index classes,
+with the same score bits on every path.  That is the coarse stage of a two-stage search as it stands: search(k=128) on the
+float8_e4m3fn index, then `target_scores` of the shortlist on a float32 or bfloat16 index of the same items.  Not yet:
+`hub_norm` / norm=, `search_groups`, pooling= and item_pooling= raise ValueError naming the dtype before anything is scored.
+
     greater, equal = index.rank_counts(embds, weights, targets)   # int32, shape of targets ([NQ] or [NQ, T], int64)
     ranks = index.ranks(embds, weights, targets)                  # float64: greater + (equal - 1) / 2
 
@@ -177,7 +200,9 @@ MAX_ITEM_SET = 128  # items per stored set of an item-pooled scan: one 128-colum
 _POOL_MODES = {'mean': 0, 'max': 1}  # the `mode` of the pooled entry points
 _BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 bytes per element either way) + chunk lists
 _MAX_HITS = 1 << 27  # default cap of a range search's total: a guard against a mistyped threshold, not a tuned number
-_DTYPES = {torch.float32: 4, torch.bfloat16: 8}  # storage dtype -> multiple d must have (16-byte folded rows)
+FP8 = torch.float8_e4m3fn
+_DTYPES = {torch.float32: 4, torch.bfloat16: 8, FP8: 16}  # storage dtype -> multiple d must have (16-byte folded rows)
+_ENTRY_TAGS = {torch.float32: '', torch.bfloat16: '_bf16', FP8: '_fp8'}  # storage dtype -> its part of an entry point's name
 
 
 def _cuda_f32(x, name):
@@ -208,9 +233,18 @@ def _exclusions(exclude, nq, nv):
   return ex
 
 
-def _check_dtype(dtype):
+def _width(embds):
+  """d of an (NV, M, d) argument, read off its shape alone; None for anything else (the later checks say what)."""
+  shape = getattr(embds, 'shape', None)
+  return shape[-1] if shape is not None and len(shape) == 3 else None
+
+
+def _check_dtype(dtype, dim=None):
+  """The storage dtype and, where it is known as a plain int already, the width d it allows: no tensor is looked at."""
   if dtype not in _DTYPES:
-    raise ValueError('VideoIndex: dtype must be torch.float32 or torch.bfloat16, got %r' % (dtype,))
+    raise ValueError('VideoIndex: dtype must be torch.float32, torch.bfloat16 or torch.float8_e4m3fn, got %r' % (dtype,))
+  if dtype == FP8 and isinstance(dim, int) and not isinstance(dim, bool) and (dim < 16 or dim % 16):
+    raise ValueError('VideoIndex: need d %% 16 == 0 for %s (16-byte folded rows), got d = %d' % (dtype, dim))
 
 
 class IndexSubset:
@@ -515,6 +549,11 @@ class _Index:
       raise ValueError('search: queries must be on the index device %s' % self.device)
     return q, qw
 
+  def _no_fp8(self, who, what):
+    """What an fp8 index does not answer yet is refused by name, before anything is scored."""
+    if getattr(self, 'dtype', None) == FP8:
+      raise ValueError('%s: %s is not available on a %s index' % (who, what, FP8))
+
   def _subset_mask(self, items):
     """The checks of `subset` -> (the set as a bool mask [num_items] of its own, the number of allowed items)."""
     if self.num_items == 0:
@@ -614,6 +653,9 @@ class _Index:
     """The checks every scan shares once its own arguments have passed -> q, qw, whether the dynamic rule applies.  With
     a pooling the query count must be its num_rows: nothing is scored otherwise.  With an item pooling the subset is one
     of its sets."""
+    for what, given in (('item_pooling=', item_pooling), ('pooling=', pooling), ('norm=', norm)):
+      if given is not None:
+        self._no_fp8(who, what)
     if item_pooling is not None:
       self._item_pooling(item_pooling, who, pooling, exclude, norm)
     if pooling is not None:
@@ -656,6 +698,7 @@ class _Index:
     search(k=1) of the bank): a call with such a norm then normalises only the queries whose own plain top-1 is a hub
     (QB-Norm's dynamic inverted softmax).  Like a subset, a norm describes the num_items of this moment: after a further
     `add` it is refused."""
+    self._no_fp8('hub_norm', 'the querybank normalisation')
     _check_beta(beta)
     if not isinstance(dynamic, bool):
       raise ValueError('hub_norm: dynamic must be False or True, got %r' % (dynamic,))
@@ -786,6 +829,7 @@ class _Index:
     with its part of the grouping (ids are global: a group may have members on several shards), the lists are copied to
     the primary and merged there, de-duplicating across shards under the global tie rule
     (mmt_search_merge_group_lists)."""
+    self._no_fp8('search_groups', 'grouped search')
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
       raise ValueError('search_groups: k must be an int in 1..%d, got %r' % (MAX_K, k))
     if self.num_items == 0:
@@ -829,10 +873,12 @@ class _Index:
 class VideoIndex(_Index):
   """A gallery of up to `capacity` items with M expert embeddings of width d (M <= 16), weighted per item and expert.
   dtype=torch.float32 (d % 4 == 0) stores the fold gw (.) G as it is; dtype=torch.bfloat16 (d % 8 == 0) stores it rounded
-  once to bf16 -- half the bytes, scored on the bf16 matrix cores against the unrounded fp32 queries (module docstring)."""
+  once to bf16 -- half the bytes, scored on the bf16 matrix cores against the unrounded fp32 queries (module docstring);
+  dtype=torch.float8_e4m3fn (d % 16 == 0) stores it divided by a power of two per item (`scales`) and rounded once to e4m3
+  -- a quarter of the bytes, widened exactly to bf16 inside the same scan."""
 
   def __init__(self, embds, weights, dtype=torch.float32):
-    _check_dtype(dtype)
+    _check_dtype(dtype, _width(embds))
     g, gw = self._items(embds, weights, 'VideoIndex')
     self._allocate(g.shape[0], g.shape[1], g.shape[2], g.device, dtype)
     self.add(g, gw)
@@ -840,8 +886,9 @@ class VideoIndex(_Index):
   @classmethod
   def empty(cls, capacity, num_experts, dim, device, dtype=torch.float32):
     """An index with room for `capacity` items and none stored: [capacity, M*d] of `dtype` and [capacity, M] fp32 are
-    allocated here, `add` fills them chunk by chunk (the unfolded gallery is never needed in one piece)."""
-    _check_dtype(dtype)
+    allocated here (float8_e4m3fn: and the fp32 scales [capacity]), `add` fills them chunk by chunk (the unfolded gallery
+    is never needed in one piece)."""
+    _check_dtype(dtype, dim)
     device = torch.device(device)
     if device.type != 'cuda':
       raise ValueError('VideoIndex.empty: device must be a CUDA device, got %s' % device)
@@ -863,16 +910,21 @@ class VideoIndex(_Index):
     self.device, self.dtype = device, dtype
     self.folded = torch.empty(capacity, m * d, device=device, dtype=dtype)   # gw (.) G; rows < num_items are valid
     self.weights = torch.empty(capacity, m, device=device, dtype=torch.float32)
+    # float8_e4m3fn: the power of two each stored row was divided by
+    self.scales = torch.empty(capacity, device=device, dtype=torch.float32) if dtype == FP8 else None
 
   @property
   def nbytes(self):
-    """Bytes held by the index: the folded storage plus the weights, at full capacity."""
-    return self.folded.numel() * self.folded.element_size() + self.weights.numel() * 4
+    """Bytes held by the index: the folded storage plus the weights (float8_e4m3fn: and the scales), at full capacity."""
+    return (self.folded.numel() * self.folded.element_size() + self.weights.numel() * 4 +
+            (0 if self.scales is None else self.scales.numel() * 4))
 
   def add(self, embds, weights):
-    """Appends items (n, M, d) / (n, M): folded (and for bfloat16 rounded) straight into the preallocated rows.  Returns
-    (first, last): the new items are numbers first .. last - 1.  Raises ValueError, leaving the index as it was, if they
-    do not fit."""
+    """Appends items (n, M, d) / (n, M): folded (and for bfloat16 rounded, for float8_e4m3fn scaled per item and rounded)
+    straight into the preallocated rows.  Returns (first, last): the new items are numbers first .. last - 1.  Raises
+    ValueError, leaving the index as it was, if they do not fit.  The values are taken to be finite and are not checked:
+    on a float8_e4m3fn index a NaN or Inf spoils the stored row and the scale of its own item, whose scores then mean
+    nothing, and no other item."""
     g, gw = self._items(embds, weights, 'VideoIndex.add')
     n, m, d = g.shape
     if (m, d) != (self.num_experts, self.dim):
@@ -885,7 +937,10 @@ class VideoIndex(_Index):
     L = _lib.lib()
     with torch.cuda.device(self.device):
       out = self.folded[first:last]
-      if self.dtype == torch.bfloat16:
+      if self.dtype == FP8:
+        check(L.mmt_search_fold_fp8(ops._p(g), ops._p(gw), n, m, d, ops._p(out), ops._p(self.scales[first:last]),
+                                    ops._stream()), 'mmt_search_fold_fp8')
+      elif self.dtype == torch.bfloat16:
         check(L.mmt_search_fold_bf16(ops._p(g), ops._p(gw), n, m, d, ops._p(out), ops._stream()), 'mmt_search_fold_bf16')
       else:
         check(L.mmt_search_fold(ops._p(g), ops._p(gw), n, m, d, ops._p(out), ops._stream()), 'mmt_search_fold')
@@ -973,19 +1028,21 @@ class VideoIndex(_Index):
     """The C entry point of a scan over this index's storage: op 'topk', 'topk_groups', 'rank', 'thresholds', 'count',
     'range_count', 'range_fill' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions), '_norm', '_pooled' or '_itemsets' -> (the
     function, its name)."""
-    name = 'mmt_search_%s%s%s' % (op, '_bf16' if self.dtype == torch.bfloat16 else '', variant)
+    name = 'mmt_search_%s%s%s' % (op, _ENTRY_TAGS[self.dtype], variant)
     return getattr(_lib.lib(), name), name
 
   def _operands(self, q, qw):
     """The query and gallery operands of the scan entry points for one batch of rows: the fp32 fold, or its bf16 hi / lo
-    pair.  Returns (pointers, the tensors they point into)."""
+    pair (a bfloat16 or float8_e4m3fn index; the latter's gallery operands end with the scales).  Returns (pointers, the
+    tensors they point into)."""
     n, m, d = q.shape
     L = _lib.lib()
-    if self.dtype == torch.bfloat16:
+    if self.dtype != torch.float32:
       hl = torch.empty(2, n, m * d, device=self.device, dtype=torch.bfloat16)  # hi = bf16(qf), lo = bf16(qf - hi)
       check(L.mmt_search_fold_split_bf16(ops._p(q), ops._p(qw), n, m, d, ops._p(hl[0]), ops._p(hl[1]), ops._stream()),
             'mmt_search_fold_split_bf16')
-      return (ops._p(hl[0]), ops._p(hl[1]), ops._p(qw), ops._p(self.folded), ops._p(self.weights)), hl
+      scales = () if self.scales is None else (ops._p(self.scales),)
+      return (ops._p(hl[0]), ops._p(hl[1]), ops._p(qw), ops._p(self.folded), ops._p(self.weights)) + scales, hl
     qf = _fold(q, qw)
     return (ops._p(qf), ops._p(qw), ops._p(self.folded), ops._p(self.weights)), qf
 
@@ -1465,7 +1522,7 @@ class ShardedVideoIndex(_Index):
   cross-device copies are asynchronous, so the shards scan concurrently."""
 
   def __init__(self, embds, weights, devices, dtype=torch.float32):
-    _check_dtype(dtype)
+    _check_dtype(dtype, _width(embds))
     devices = _devices(devices)
     g, gw = self._items(embds, weights, 'ShardedVideoIndex')
     n, s = g.shape[0], len(devices)
@@ -1476,7 +1533,7 @@ class ShardedVideoIndex(_Index):
   @classmethod
   def empty(cls, capacity, num_experts, dim, devices, dtype=torch.float32):
     """Room for `capacity` items and none stored: every shard gets ceil(capacity / S) rows; `add` fills them."""
-    _check_dtype(dtype)
+    _check_dtype(dtype, dim)
     devices = _devices(devices)
     if any(isinstance(v, bool) or not isinstance(v, int) for v in (capacity, num_experts, dim)):
       raise ValueError('ShardedVideoIndex.empty: capacity, num_experts and dim must be ints')

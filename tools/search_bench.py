@@ -70,7 +70,13 @@ per index dtype (--gallery-dtype, both = the two indexes) with the first NV // C
 plain search(k = 10) over the same stored items on the same index -- the same scan without the pool step, the yardstick.
 What the code predicts is the plain scan's time, times 128 / (128 // C * C) for the idle tile columns, plus the pool step;
 the prediction's factor is reported beside the measured ratio.  --runs rounds, every variant once per round, interleaved;
-median and spread.  Default output profiles/search_itemset_bench.json."""
+median and spread.  Default output profiles/search_itemset_bench.json.
+
+--fp8 times the fp8-stored index (dtype=torch.float8_e4m3fn) against the bf16-stored one over 262 144 items built in chunks
+from the same data: search(k = 10) with 64 queries (one query tile per gallery chunk: the gallery streams from HBM) and with
+4 096 (the chunk's query tiles share it in L2), and `add` of 8 192 items into a preallocated index.  --runs rounds, every
+variant once per round, interleaved; median and spread; the share of rows whose index lists agree.  Default output
+profiles/search_fp8_bench.json."""
 import argparse
 import json
 import math
@@ -506,8 +512,58 @@ def item_pooled_mode(q, qw, g, gw, flop, a):
   return row
 
 
+def fp8_mode(a, dev):
+  """The fp8-stored index against the bf16-stored one: search(k = 10) at NQ = 64 (the gallery streams from HBM) and
+  NQ = 4096 (L2 serves it) over NV = 262 144 items, and `add` of 8 192 items into a preallocated index."""
+  nv, chunk = SHAPES['S3'][1], 8192
+  gen = torch.Generator(device=dev).manual_seed(0)
+  nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
+  dtypes = {'bfloat16': torch.bfloat16, 'float8_e4m3fn': torch.float8_e4m3fn}
+  idx = {n: VideoIndex.empty(nv, M, D, dev, dtype=t) for n, t in dtypes.items()}
+  small = {n: VideoIndex.empty(chunk, M, D, dev, dtype=t) for n, t in dtypes.items()}
+  for at in range(0, nv, chunk):
+    g = nrm(torch.randn(chunk, M, D, device=dev, generator=gen))
+    gw = torch.softmax(torch.randn(chunk, M, device=dev, generator=gen), -1)
+    for index in idx.values():
+      index.add(g, gw)
+  q = nrm(torch.randn(4096, M, D, device=dev, generator=gen) + 0.3 * g[torch.arange(4096, device=dev) % chunk])
+  qw = torch.softmax(torch.randn(4096, M, device=dev, generator=gen), -1)
+
+  def add(index):
+    index.num_items = 0
+    return index.add(g, gw)
+
+  fns = {}
+  for n in dtypes:
+    fns[n + '/search_nq64'] = lambda n=n: idx[n].search(q[:64], qw[:64], k=K)
+    fns[n + '/search_nq4096'] = lambda n=n: idx[n].search(q, qw, k=K)
+    fns[n + '/add_8192'] = lambda n=n: add(small[n])
+  ts = {n: [] for n in fns}
+  out = {}
+  for _ in range(a.runs):
+    for n, fn in fns.items():
+      t, _, _, out[n] = timed(fn, a.min_seconds)
+      ts[n].append(t)
+  row = {'NV': nv, 'index_bytes': {n: idx[n].nbytes for n in idx}}
+  for n in fns:
+    med = float(np.median(ts[n]))
+    row[n] = dict(seconds_median=med, seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n])
+  for what, rows in (('search_nq64', 64), ('search_nq4096', 4096), ('add_8192', 0)):
+    b, f = row['bfloat16/' + what], row['float8_e4m3fn/' + what]
+    row[what + '/summary'] = dict(bf16_over_fp8=b['seconds_median'] / f['seconds_median'],
+                                  spread_seconds=max(b['seconds_spread'], f['seconds_spread']))
+    if rows:
+      row[what + '/summary'].update(
+          gallery_gbytes_per_second_fp8=nv * M * D / f['seconds_median'] / 1e9,
+          gallery_gbytes_per_second_bf16=2 * nv * M * D / b['seconds_median'] / 1e9,
+          rows_identical=float((out['bfloat16/' + what][1] == out['float8_e4m3fn/' + what][1]).all(1).float().mean()))
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
+  ap.add_argument('--fp8', action='store_true', help='time the fp8-stored index against the bf16-stored one: search(k = 10) '
+                  'at NQ = 64 and 4096 over 262 144 items, and add of 8 192 items (no other mode flag)')
   ap.add_argument('--shapes', default='S1,S2,S3')
   ap.add_argument('--out', default=None)
   ap.add_argument('--min-seconds', type=float, default=0.5)
@@ -576,6 +632,16 @@ def main():
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
+  if a.fp8:
+    res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'fp8', 'runs': a.runs,
+           'min_seconds': a.min_seconds}
+    res.update(fp8_mode(a, dev))
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                'search_fp8_bench.json')
+    with open(out, 'w') as f:
+      json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return
   res = {'M': M, 'd': D, 'k': K, 'peak_fp32_matrix_flops': PEAK, 'device': torch.cuda.get_device_name(0), 'shapes': {}}
   if a.gallery_dtype != 'float32':  # the default invocation keeps its JSON layout
     res['gallery_dtype'] = a.gallery_dtype
