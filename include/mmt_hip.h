@@ -67,7 +67,9 @@ typedef struct MmtEpilogue {
   /* MMT_EPI_BF16 only, nullable: dot_out[row, n / 64] = sum over the 64 output columns of group n / 64 of
    * out(bf16)[row, n] * dot_src(bf16)[row, n] -- with out = dO = dA . Wo and dot_src = O (the attention context) these are
    * the "delta" sums of the attention backward (rowsum(dO * O) per head = DH / 64 groups), formed while dO is still in
-   * registers instead of by re-reading dO and O (model/bert.py:141-168 backward).  dot_out: fp32 [M, N / 64]. */
+   * registers instead of by re-reading dO and O (model/bert.py:141-168 backward).  dot_out: fp32 [M, N / 64], rows at or past M or
+   * *n_rows_dev are not written.  Every tile forms them but the forced tile 25 (MMT_ERR_ARG); forced
+   * tiles 1 / 2 run as tile 13. */
   const void* dot_src;
   int64_t lddot;
   float* dot_out;
@@ -308,8 +310,10 @@ int mmt_attn_bwd(const void* qkv, const int32_t* cu_seqlens, const float* mask_b
                  const uint32_t* seed_dev,
                  const int32_t* row_index, void* stream);
 /* Query-subset attention (last encoder layer: only the rows that are read out need a context vector): queries are the
- * rows qsel[b*nq + i]; ctx / lse / dctx / delta are compact [B*nq, .] (delta: [B*nq, d/64]); qkv / dqkv keep the full layout.  dqkv must be
- * zero on entry in the Q section of the non-selected rows. */
+ * rows qsel[b*nq + i] (distinct rows of sample b); ctx / lse / dctx / delta are compact [B*nq, .] (delta: [B*nq, d/64]);
+ * qkv / dqkv keep the full layout.  The backward needs nothing of dqkv on entry: it writes dK / dV of every live row, dQ of
+ * the selected rows and zero in the Q section of every other live row.  The backward takes nq <= 64 (MMT_ERR_ARG above that:
+ * the kernel that clears the Q section is ordered against one dQ block per (sample, head) only); the forward takes any nq. */
 int mmt_attn_fwd_rows(const void* qkv, const int32_t* cu_seqlens, const float* mask_bias, const int32_t* qsel, int nq,
                       void* ctx, float* lse, int B, int S, int H, int d, float scale, uint32_t drop_key, uint32_t thr16,
                       float drop_scale, const uint32_t* seed_dev,

@@ -1007,8 +1007,12 @@ extern "C" int mmt_attn_bwd(const void* qkv, const int32_t* cu_seqlens, const fl
 }
 
 // Query-subset variants: only the rows qsel[b*nq + i] act as queries (all rows of a sample remain keys/values).
-// ctx / lse / dctx / delta are compact [B*nq, .]; dqkv is the full [rows, 3d] buffer and must be ZERO on entry for the
-// Q section of non-selected rows (the kernels write dQ of the selected rows and dK / dV of every row).
+// ctx / lse / dctx / delta are compact [B*nq, .]; dqkv is the full [rows, 3d] buffer.  The backward writes all of it for
+// the live rows and needs nothing of it on entry: dK / dV of every row, dQ of the selected rows, and ZERO in the Q section
+// of every other row of a sample (attn_bwd_dq_block: the first dQ block of a (sample, head) clears the head's columns of
+// the whole sample before it stores its own rows; tests/test_engine_paths_gpu.py runs it on a sentinel-filled dqkv).
+// That clear is ordered against the dQ stores of ITS block only, so the backward takes nq <= 64 (one dQ block per
+// (sample, head)); a larger nq is MMT_ERR_ARG.  The forward takes any nq.
 extern "C" int mmt_attn_fwd_rows(const void* qkv, const int32_t* cu_seqlens, const float* mask_bias, const int32_t* qsel,
                                  int nq, void* ctx, float* lse, int B, int S, int H, int d, float scale,
                                  uint32_t drop_key, uint32_t thr16, float drop_scale, const uint32_t* seed_dev, const int32_t* row_index, void* stream) {
@@ -1025,6 +1029,7 @@ extern "C" int mmt_attn_bwd_rows_ex(const void* qkv, const int32_t* cu_seqlens, 
                                     float drop_scale, const uint32_t* seed_dev, const int32_t* row_index, void* stream) {
   if (int e = check_args(qkv, B, S, H, d)) return e;
   if (!mask_bias || !ctx || !lse || !dctx || !dqkv || !delta || !qsel || nq <= 0) return MMT_ERR_ARG;
+  if (nq > 64) return MMT_ERR_ARG;  // a second dQ block would race with the first one's clear of the Q section (above)
   AttnArgs a = attn_args(qkv, cu_seqlens, mask_bias, ctx, lse, B, S, H, d, scale, drop_key, thr16, drop_scale, seed_dev, row_index);
   a.dctx = (const bf16_t*)dctx; a.dqkv = (bf16_t*)dqkv; a.dparts = delta;
   a.qsel = qsel; a.nq = nq;

@@ -645,6 +645,7 @@ int mmt_gemm2_dispatch(int tile, int epilogue, const void* A, int64_t lda, const
     tile = (N % 128 == 0 && !(epilogue == MMT_EPI_DGELU && e.colsum && M < 128)) ? 14 : 13;
   }
   if ((tile & 0xff) == 25) {  // the same kernel on 128 x 64 tiles (long K, narrow outputs), else tile 13
+    if (e.dot_out) return MMT_ERR_ARG;  // no row dots on this tile at any shape: an error, not a quiet change of tile
     const int rc = mmt_gemm5_dispatch(epilogue, 64, A, lda, B, ldb, C, ldc, M, N, K, e, nr, s);
     if (rc != MMT_ERR_ARG) return rc;
     tile = 13;
@@ -684,7 +685,9 @@ extern "C" int mmt_gemm_nn_bf16(const void* A, int64_t lda, const void* B, int64
   if (epi) e = *epi;
   hipStream_t s = (hipStream_t)stream;
   switch (epilogue) {
-    case MMT_EPI_BF16: return pick_nn<MMT_EPI_BF16>(A, lda, B, ldb, C, ldc, M, N, K, e, n_rows_dev, s);
+    case MMT_EPI_BF16:
+      if (e.dot_out && !e.dot_src) return MMT_ERR_ARG;
+      return pick_nn<MMT_EPI_BF16>(A, lda, B, ldb, C, ldc, M, N, K, e, n_rows_dev, s);
     case MMT_EPI_F32: return pick_nn<MMT_EPI_F32>(A, lda, B, ldb, C, ldc, M, N, K, e, n_rows_dev, s);
     case MMT_EPI_ADD_F32:
       if (!e.res) return MMT_ERR_ARG;

@@ -236,7 +236,7 @@ __device__ __forceinline__ void g5_epilogue(f32x16 (&acc)[2][NJ], unsigned char*
                              bf2f((bf16_t)(o[1] & 0xffff)) * bf2f((bf16_t)(c[1] & 0xffff)) + bf2f((bf16_t)(o[1] >> 16)) * bf2f((bf16_t)(c[1] >> 16));
                 part += __shfl_xor(part, 1, 64); part += __shfl_xor(part, 2, 64); part += __shfl_xor(part, 4, 64);
                 if (j == 0) dotp[t] = part;
-                else if (row < M && (lane & 7) == 0) epi.dot_out[(int64_t)row * (N >> 6) + (col0 >> 6)] = dotp[t] + part;
+                else if (row < nrows && (lane & 7) == 0) epi.dot_out[(int64_t)row * (N >> 6) + (col0 >> 6)] = dotp[t] + part;
               }
             }
           } else if constexpr (EPI == MMT_EPI_BIAS_GELU) {

@@ -217,7 +217,7 @@ __device__ __forceinline__ void gemm_tile_epilogue(f32x16 (&acc)[BM / WGM / 32][
                              bf2f((bf16_t)(o[1] & 0xffff)) * bf2f((bf16_t)(c[1] & 0xffff)) + bf2f((bf16_t)(o[1] >> 16)) * bf2f((bf16_t)(c[1] >> 16));
                 part += __shfl_xor(part, 1, 64); part += __shfl_xor(part, 2, 64);
                 part += __shfl_xor(part, 4, 64); part += __shfl_xor(part, 8, 64);
-                if ((cg & 15) == 0) epi.dot_out[(int64_t)row * (N >> 6) + (col >> 6)] = part;
+                if ((cg & 15) == 0 && row < nrows) epi.dot_out[(int64_t)row * (N >> 6) + (col >> 6)] = part;
               }
             }
           } else if constexpr (EPI == MMT_EPI_BIAS_GELU) {
