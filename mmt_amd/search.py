@@ -380,29 +380,29 @@ class ShardedItemPooling:
     self._maps = (set_shard_of, set_local_of)   # global set -> (shard, local set), on the primary
     self._table_cache = {}
 
-  def _tables(self, shards):
-    """The set tables' addresses of the given shards as a device array on the primary: the `ids` of the merge kernel."""
-    if shards not in self._table_cache:
-      self._table_cache[shards] = torch.tensor([self.tables[s].data_ptr() for s in shards],
-                                               dtype=torch.int64).to(self.device)
-    return self._table_cache[shards]
-
   def subset(self, sets):
     """sets: bool [num_sets] or int64 set numbers on the primary device, as ItemPooling.subset -> ShardedSubset over SET
     numbers: the set cut into one IndexSubset per shard, in the shard's own set numbers."""
-    mask, total = _mask_of(sets, self.num_sets, self.device, 'sets')
-    parts = []
-    for part_pool, table in zip(self.parts, self.tables):
-      part = None
-      if part_pool is not None:
-        local = mask[table]  # gathered on the primary, where the table is
-        with torch.cuda.device(part_pool.device):
-          local = local.to(part_pool.device)
-          count = int(local.sum())
-          if count:
-            part = IndexSubset(local, count)
-      parts.append(part)
-    return ShardedSubset(parts, mask, total)
+    return _cut_subset(*_mask_of(sets, self.num_sets, self.device, 'sets'),
+                       [(table, part and part.device) for table, part in zip(self.tables, self.parts)])
+
+
+def _cut_subset(mask, count, tables):
+  """A set as a bool mask on the primary and the number allowed -> ShardedSubset: the mask cut into one IndexSubset per
+  shard through tables, one (the shard's local -> global table on the primary, the shard's device) per shard -- the table
+  None for a shard that holds nothing, which like a shard without an allowed member gets no part."""
+  parts = []
+  for table, device in tables:
+    part = None
+    if table is not None:
+      local = mask[table]  # gathered on the primary, where the table is
+      with torch.cuda.device(device):
+        local = local.to(device)
+        allowed = int(local.sum())
+        if allowed:
+          part = IndexSubset(local, allowed)
+    parts.append(part)
+  return ShardedSubset(parts, mask, count)
 
 
 def sets_whole(shard_of, local_of, set_size):
@@ -414,38 +414,55 @@ def sets_whole(shard_of, local_of, set_size):
   return ((so == so[:, :1]) & (lo == lo[:, :1] + steps) & (lo[:, :1] % set_size == 0)).all()
 
 
-def _check_item_sets(who, set_size, num_items, item_weights, mode, device):
-  """The checks of `item_pooling` -> (num_sets, the weights as float32 [num_items] of their own).  One small reduction
-  and one host sync where weights are given."""
-  if isinstance(set_size, bool) or not isinstance(set_size, int):
-    raise ValueError('%s: set_size must be an int, got %r' % (who, set_size))
-  if not 1 <= set_size <= MAX_ITEM_SET:
-    raise ValueError('%s: set_size must lie in 1..%d, got %d' % (who, MAX_ITEM_SET, set_size))
+def _check_sets(who, member, ints, max_size, count, count_first, mode, weights, device):
+  """The checks of `pooling` (member 'a row') and `item_pooling` ('an item'): sets of set_size members with a mode and a
+  weight per member -> (num_sets, the weights as float32 [num_sets * set_size] of their own).  ints: the (name, value)
+  pairs that must be ints, set_size first; count(): the caller's own limits on the number of sets, which returns it --
+  asked before the mode is looked at (count_first) or after it.  One small reduction and one host sync where weights are
+  given."""
+  for name, v in ints:
+    if isinstance(v, bool) or not isinstance(v, int):
+      raise ValueError('%s: %s must be an int, got %r' % (who, name, v))
+  set_size, noun = ints[0][1], member.split()[1] + '_weights'
+  if not 1 <= set_size <= max_size:
+    raise ValueError('%s: set_size must lie in 1..%d, got %d' % (who, max_size, set_size))
+  if count_first:
+    num_sets = count()
   if mode not in _POOL_MODES:
     raise ValueError("%s: mode must be 'mean' or 'max', got %r" % (who, mode))
-  if num_items == 0:
-    raise ValueError('%s: the index holds no items' % who)
-  if num_items % set_size:
-    raise ValueError('%s: %d items are no whole number of sets of %d' % (who, num_items, set_size))
-  num_sets = num_items // set_size
-  if item_weights is None:
-    return num_sets, torch.full((num_items,), 1.0 / set_size, device=device, dtype=torch.float32)
-  if not torch.is_tensor(item_weights) or item_weights.dtype != torch.float32:
-    raise ValueError('%s: item_weights must be a float32 tensor, got %s' % (
-        who, item_weights.dtype if torch.is_tensor(item_weights) else type(item_weights).__name__))
-  if item_weights.device != device:
-    raise ValueError('%s: item_weights must be on the index device %s, got %s' % (who, device, item_weights.device))
-  if tuple(item_weights.shape) not in ((num_items,), (num_sets, set_size)):
-    raise ValueError('%s: item_weights of shape (%d,) or (%d, %d) expected, got %s' % (
-        who, num_items, num_sets, set_size, tuple(item_weights.shape)))
-  w = item_weights.reshape(-1).contiguous().clone()
-  sets = w.view(num_sets, set_size)
-  finite, manned = (bool(v) for v in torch.stack([torch.isfinite(w).all(), (sets != 0).any(1).all()]).tolist())
-  if not finite:
-    raise ValueError('%s: item_weights must be finite' % who)
-  if not manned:
-    raise ValueError('%s: every set needs an item with a weight other than 0' % who)
+  if not count_first:
+    num_sets = count()
+  n = num_sets * set_size
+  if weights is None:
+    return num_sets, torch.full((n,), 1.0 / set_size, device=device, dtype=torch.float32)
+  if not torch.is_tensor(weights) or weights.dtype != torch.float32:
+    raise ValueError('%s: %s must be a float32 tensor, got %s' % (
+        who, noun, weights.dtype if torch.is_tensor(weights) else type(weights).__name__))
+  if weights.device != device:
+    raise ValueError('%s: %s must be on the index device %s, got %s' % (who, noun, device, weights.device))
+  if tuple(weights.shape) not in ((n,), (num_sets, set_size)):
+    raise ValueError('%s: %s of shape (%d,) or (%d, %d) expected, got %s' % (
+        who, noun, n, num_sets, set_size, tuple(weights.shape)))
+  w = weights.reshape(-1).contiguous().clone()
+  if num_sets:
+    sets = w.view(num_sets, set_size)
+    finite, manned = (bool(v) for v in torch.stack([torch.isfinite(w).all(), (sets != 0).any(1).all()]).tolist())
+    if not finite:
+      raise ValueError('%s: %s must be finite' % (who, noun))
+    if not manned:
+      raise ValueError('%s: every set needs %s with a weight other than 0' % (who, member))
   return num_sets, w
+
+
+def _check_item_sets(who, set_size, num_items, item_weights, mode, device):
+  """The checks of `item_pooling` on either index class -> (num_sets, the weights as float32 [num_items] of their own)."""
+  def count():
+    if num_items == 0:
+      raise ValueError('%s: the index holds no items' % who)
+    if num_items % set_size:
+      raise ValueError('%s: %d items are no whole number of sets of %d' % (who, num_items, set_size))
+    return num_items // set_size
+  return _check_sets(who, 'an item', (('set_size', set_size),), MAX_ITEM_SET, count, False, mode, item_weights, device)
 
 
 def _count_groups(ids):
@@ -494,9 +511,51 @@ def _pick(use, normed, plain):
   return torch.where(use.reshape((-1,) + (1,) * (normed.dim() - 1)), normed, plain)
 
 
-def _result_rows(q, pooling):
-  """The rows of a scan's outputs: one per query, or with a pooling one per query set."""
-  return q.shape[0] if pooling is None else pooling.num_sets
+class _Scan:
+  """What a scan is asked to do beside its queries: subset (an IndexSubset, on a sharded index a ShardedSubset), ex (int64
+  [NQ, E] exclusions, checked), norm (a HubNorm / ShardedHubNorm: every query normalised), pooling (a QueryPooling) and
+  item_pooling (an ItemPooling / ShardedItemPooling), each None unless given and already checked against the index.  A
+  public call builds it once and every internal call takes it whole; the sizes that depend on which options are there
+  are answered here."""
+
+  def __init__(self, subset=None, ex=None, norm=None, pooling=None, item_pooling=None):
+    self.subset, self.ex, self.norm, self.pooling, self.item_pooling = subset, ex, norm, pooling, item_pooling
+    # which family of entry points scans it: '' stands for the plain, _ex and _norm forms
+    self.kind = '_itemsets' if item_pooling is not None else '_pooled' if pooling is not None else ''
+
+  def plain(self):
+    """The same candidates without the norm: what the dynamic rule falls back to."""
+    return _Scan(self.subset, self.ex)
+
+  def rows(self, q):
+    """The rows of the outputs: one per query, or with a pooling one per query set."""
+    return q.shape[0] if self.pooling is None else self.pooling.num_sets
+
+  def numbered(self, index):
+    """How many things the indices, targets and subset of the scan number: the index's items, or the item pooling's sets."""
+    return index.num_items if self.item_pooling is None else self.item_pooling.num_sets
+
+  def candidates(self, index):
+    """The bound of k': the allowed ones among them."""
+    return self.numbered(index) if self.subset is None else self.subset.count
+
+  def columns(self, index):
+    """The gallery columns the chunk estimates of the batches count."""
+    return index.num_items if self.item_pooling is None else self.item_pooling._columns
+
+  def words(self):
+    return ops._p(None if self.subset is None else self.subset.words)
+
+  def norm_args(self):
+    """The trailing (beta, lse) of the _norm entry points."""
+    return () if self.norm is None else (self.norm.beta, ops._p(self.norm.lse))
+
+  def shard(self, s, index):
+    """Shard s's view of it on the ShardedVideoIndex `index`: its part of the subset, the norm and the item pooling (None
+    where the shard has none), the pooling as it is, the exclusions in the shard's item numbers on its device."""
+    part = lambda whole: None if whole is None else whole.parts[s]
+    ex = None if self.ex is None else index._local(self.ex, s).to(index.shards[s].device)
+    return _Scan(part(self.subset), ex, part(self.norm), self.pooling, part(self.item_pooling))
 
 
 def _column_groups(src, outs, r0, r1):
@@ -514,11 +573,23 @@ def _column_groups(src, outs, r0, r1):
         o[r0:r1, t0:t1] = part
 
 
+def _lists(count, device, *shape, vacant=False):
+  """`count` result lists of `shape`: float32 scores, then int64 numbers -- unwritten, or (vacant) holding (-inf, -1), a
+  slot without a candidate."""
+  if vacant:
+    return tuple([torch.full(shape, float('-inf'), device=device, dtype=torch.float32)] +
+                 [torch.full(shape, -1, device=device, dtype=torch.int64) for _ in range(count - 1)])
+  return tuple([torch.empty(*shape, device=device, dtype=torch.float32)] +
+               [torch.empty(*shape, device=device, dtype=torch.int64) for _ in range(count - 1)])
+
+
 class _Index:
   """What VideoIndex and ShardedVideoIndex share: the checks of every public call, the calls that are the same on both
-  (`search`, `rank_counts`, `ranks`, `hub_norm` up to the scan, `search_groups`) and QB-Norm's dynamic rule.  It reads the bookkeeping both
-  have -- num_experts, dim, num_items, device (the primary of a sharded index) -- and leaves to the class what happens
-  behind the checks: _search, _rank_counts, _hub_norm, _search_groups and the type checks _subset / _norm / _grouping."""
+  (`search`, `rank_counts`, `ranks`, `hub_norm` up to the scan, `search_groups`) and QB-Norm's dynamic rule.  It reads the
+  bookkeeping both have -- num_experts, dim, num_items, device (the primary of a sharded index).  Behind its checks a
+  public call puts its options into one _Scan and makes one call with it, wrapped in `_dynamic`; the class supplies
+  what happens there -- _search(q, qw, k, scan), _rank_counts(q, qw, tg, scan), _hub_norm, _search_groups -- and names
+  its own kinds of subset, norm and grouping for `_made_here` (_subset / _norm / _grouping)."""
 
   @staticmethod
   def _items(embds, weights, who):
@@ -554,6 +625,24 @@ class _Index:
     if getattr(self, 'dtype', None) == FP8:
       raise ValueError('%s: %s is not available on a %s index' % (who, what, FP8))
 
+  def _made_here(self, thing, who, noun, kind, maker, item_pooling=None):
+    """`thing` (a `noun`: subset, norm or grouping) was built by this index -- it is a `kind`, which `maker` returns --
+    for this many items (a subset beside an item pooling: for its sets) and on this device; a sharded kind (it has
+    `parts`) also for this many shards."""
+    if not isinstance(thing, kind):
+      raise ValueError('%s: %s must come from %s, got %s' % (who, noun, maker, type(thing).__name__))
+    if item_pooling is not None:
+      if thing.num_items != item_pooling.num_sets:
+        raise ValueError('%s: the %s was built for %d sets, the item pooling has %d' % (
+            who, noun, thing.num_items, item_pooling.num_sets))
+    elif thing.num_items != self.num_items:
+      raise ValueError('%s: the %s was built for %d items, the index holds %d' % (who, noun, thing.num_items, self.num_items))
+    if not hasattr(thing, 'parts'):
+      if thing.device != self.device:
+        raise ValueError('%s: the %s is on %s, the index on %s' % (who, noun, thing.device, self.device))
+    elif thing.device != self.device or len(thing.parts) != len(self.shards):
+      raise ValueError('%s: the %s belongs to another index' % (who, noun))
+
   def _subset_mask(self, items):
     """The checks of `subset` -> (the set as a bool mask [num_items] of its own, the number of allowed items)."""
     if self.num_items == 0:
@@ -580,10 +669,10 @@ class _Index:
     if targets.dim() not in (1, 2) or targets.dim() == 2 and targets.shape[1] < 1:
       raise ValueError('ranks: targets [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(targets.shape),))
 
-  def _target_range(self, targets, item_pooling=None):
+  def _target_range(self, targets, scan):
     """The values of the (non-empty) targets against -1 .. num_items - 1 (with an item pooling: num_sets - 1): one small
     reduction and a host sync."""
-    n = self.num_items if item_pooling is None else item_pooling.num_sets
+    n = scan.numbered(self)
     lo, hi = (int(v) for v in torch.aminmax(targets))
     if lo < -1 or hi >= n:
       raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (n - 1, lo, hi))
@@ -598,34 +687,12 @@ class _Index:
     row order, each product and each sum rounded to fp32 on its own; mode='max': the largest score, the weights acting
     as a mask only.  The checks cost one small reduction and one host sync.  A pooling does not describe the stored
     items: it stays valid after `add`."""
-    for name, v in (('set_size', set_size), ('num_sets', num_sets)):
-      if isinstance(v, bool) or not isinstance(v, int):
-        raise ValueError('pooling: %s must be an int, got %r' % (name, v))
-    if not 1 <= set_size <= MAX_SET:
-      raise ValueError('pooling: set_size must lie in 1..%d, got %d' % (MAX_SET, set_size))
-    if num_sets < 0 or num_sets * set_size >= 2 ** 31:
-      raise ValueError('pooling: num_sets must be >= 0 with num_sets * set_size < 2^31, got %d' % num_sets)
-    if mode not in _POOL_MODES:
-      raise ValueError("pooling: mode must be 'mean' or 'max', got %r" % (mode,))
-    if row_weights is None:
-      w = torch.full((num_sets * set_size,), 1.0 / set_size, device=self.device, dtype=torch.float32)
-      return QueryPooling(set_size, num_sets, w, mode)
-    if not torch.is_tensor(row_weights) or row_weights.dtype != torch.float32:
-      raise ValueError('pooling: row_weights must be a float32 tensor, got %s' % (
-          row_weights.dtype if torch.is_tensor(row_weights) else type(row_weights).__name__))
-    if row_weights.device != self.device:
-      raise ValueError('pooling: row_weights must be on the index device %s, got %s' % (self.device, row_weights.device))
-    if tuple(row_weights.shape) not in ((num_sets * set_size,), (num_sets, set_size)):
-      raise ValueError('pooling: row_weights of shape (%d,) or (%d, %d) expected, got %s' % (
-          num_sets * set_size, num_sets, set_size, tuple(row_weights.shape)))
-    w = row_weights.reshape(-1).contiguous().clone()
-    if num_sets:
-      sets = w.view(num_sets, set_size)
-      finite, manned = (bool(v) for v in torch.stack([torch.isfinite(w).all(), (sets != 0).any(1).all()]).tolist())
-      if not finite:
-        raise ValueError('pooling: row_weights must be finite')
-      if not manned:
-        raise ValueError('pooling: every set needs a row with a weight other than 0')
+    def count():
+      if num_sets < 0 or num_sets * set_size >= 2 ** 31:
+        raise ValueError('pooling: num_sets must be >= 0 with num_sets * set_size < 2^31, got %d' % num_sets)
+      return num_sets
+    _, w = _check_sets('pooling', 'a row', (('set_size', set_size), ('num_sets', num_sets)), MAX_SET, count, True, mode,
+                       row_weights, self.device)
     return QueryPooling(set_size, num_sets, w, mode)
 
   def _pooling(self, pooling, who, exclude=None, norm=None):
@@ -649,7 +716,7 @@ class _Index:
     if pooling is not None or exclude is not None or norm is not None:
       raise ValueError('%s: item_pooling= does not combine with pooling=, exclude= or norm=' % who)
 
-  def _scan_args(self, who, embds, weights, subset, norm, dynamic, exclude=None, pooling=None, item_pooling=None):
+  def _scan_args(self, who, embds, weights, norm, dynamic, subset=None, exclude=None, pooling=None, item_pooling=None):
     """The checks every scan shares once its own arguments have passed -> q, qw, whether the dynamic rule applies.  With
     a pooling the query count must be its num_rows: nothing is scored otherwise.  With an item pooling the subset is one
     of its sets."""
@@ -673,19 +740,20 @@ class _Index:
           who, q.shape[0], pooling.num_rows, pooling.num_sets, pooling.set_size))
     return q, qw, dynamic
 
-  def _use_norm(self, q, qw, subset, ex, norm):
+  def _use_norm(self, q, qw, scan):
     """QB-Norm's dynamic rule: bool [NQ], True where the query's plain top-1 among its candidates (after subset and
-    exclusions) is one of norm.hubs.  A query without a candidate keeps its plain result."""
-    top1 = self._search(q, qw, 1, subset, ex)[1][:, 0]
-    return (top1 >= 0) & norm.hubs[top1.clamp(min=0)]
+    exclusions) is one of the norm's hubs.  A query without a candidate keeps its plain result."""
+    top1 = self._search(q, qw, 1, scan.plain())[1][:, 0]
+    return (top1 >= 0) & scan.norm.hubs[top1.clamp(min=0)]
 
-  def _dynamic(self, dynamic, q, qw, subset, ex, norm, normed, plain):
-    """The result of a call with norm=: `normed` (a tuple of tensors, every query normalised) as it is, or under the dynamic
-    rule mixed per query with what `plain()` gives."""
+  def _dynamic(self, dynamic, q, qw, scan, run):
+    """The result of a public call: run(scan), a tuple of tensors -- with a norm every query normalised -- as it is, or
+    under the dynamic rule (which takes a norm) mixed per query with what run gives without the norm."""
+    out = run(scan)
     if not dynamic or q.shape[0] == 0:
-      return normed
-    use = self._use_norm(q, qw, subset, ex, norm)
-    return tuple(_pick(use, a, b) for a, b in zip(normed, plain()))
+      return out
+    use = self._use_norm(q, qw, scan)
+    return tuple(_pick(use, a, b) for a, b in zip(out, run(scan.plain())))
 
   def hub_norm(self, bank_embds, bank_weights, beta, dynamic=False):
     """The querybank normaliser of this index (inverted softmax, the static half of QB-Norm): bank queries in either layout
@@ -709,7 +777,7 @@ class _Index:
       raise ValueError('hub_norm: the bank holds no queries')
     hubs = None
     if dynamic:
-      top1 = self._search(b, bw, 1, None, None)[1][:, 0]
+      top1 = self._search(b, bw, 1, _Scan())[1][:, 0]
       hubs = torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
     return self._hub_norm(b, bw, beta, hubs)
 
@@ -736,14 +804,9 @@ class _Index:
       raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
     if self.num_items == 0:
       raise ValueError('search: the index holds no items')
-    q, qw, dynamic = self._scan_args('search', embds, weights, subset, norm, dynamic, exclude, pooling, item_pooling)
-    if item_pooling is not None:
-      return self._search(q, qw, k, subset, None, None, None, item_pooling)
-    if pooling is not None:
-      return self._search(q, qw, k, subset, None, None, pooling)
-    ex = _exclusions(exclude, q.shape[0], self.num_items)
-    out = self._search(q, qw, k, subset, ex, norm)
-    return self._dynamic(dynamic, q, qw, subset, ex, norm, out, lambda: self._search(q, qw, k, subset, ex))
+    q, qw, dynamic = self._scan_args('search', embds, weights, norm, dynamic, subset, exclude, pooling, item_pooling)
+    scan = _Scan(subset, _exclusions(exclude, q.shape[0], self.num_items), norm, pooling, item_pooling)
+    return self._dynamic(dynamic, q, qw, scan, lambda scan: self._search(q, qw, k, scan))
 
   def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None, item_pooling=None):
     """Queries as for `search`; targets [NQ] or [NQ, T] int64 on the index device, values -1 .. num_items - 1 ->
@@ -765,22 +828,16 @@ class _Index:
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
-    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic, None, pooling, item_pooling)
-    nq, shape = _result_rows(q, pooling), targets.shape
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, norm, dynamic, subset, pooling=pooling, item_pooling=item_pooling)
+    scan = _Scan(subset=subset, norm=norm, pooling=pooling, item_pooling=item_pooling)
+    nq, shape = scan.rows(q), targets.shape
     if shape[0] != nq:
       raise ValueError('ranks: %d %s but targets %s' % (nq, 'queries' if pooling is None else 'query sets', tuple(shape)))
     if nq == 0:
       return tuple(torch.empty(shape, device=self.device, dtype=torch.int32) for _ in range(2))
     tg = targets.reshape(nq, -1).contiguous()
-    self._target_range(tg, item_pooling)
-    if item_pooling is not None:
-      out = self._rank_counts(q, qw, tg, subset, None, None, item_pooling)
-      return out[0].reshape(shape), out[1].reshape(shape)
-    if pooling is not None:
-      out = self._rank_counts(q, qw, tg, subset, None, pooling)
-      return out[0].reshape(shape), out[1].reshape(shape)
-    out = self._rank_counts(q, qw, tg, subset, norm)
-    out = self._dynamic(dynamic, q, qw, subset, None, norm, out, lambda: self._rank_counts(q, qw, tg, subset))
+    self._target_range(tg, scan)
+    out = self._dynamic(dynamic, q, qw, scan, lambda scan: self._rank_counts(q, qw, tg, scan))
     return out[0].reshape(shape), out[1].reshape(shape)
 
   def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None, item_pooling=None):
@@ -969,24 +1026,10 @@ class VideoIndex(_Index):
     return ItemPooling(set_size, num_sets, w, mode)
 
   def _subset(self, subset, who, item_pooling=None):
-    if not isinstance(subset, IndexSubset):
-      raise ValueError('%s: subset must come from VideoIndex.subset, got %s' % (who, type(subset).__name__))
-    if item_pooling is not None:
-      if subset.num_items != item_pooling.num_sets:
-        raise ValueError('%s: the subset was built for %d sets, the item pooling has %d' % (
-            who, subset.num_items, item_pooling.num_sets))
-    elif subset.num_items != self.num_items:
-      raise ValueError('%s: the subset was built for %d items, the index holds %d' % (who, subset.num_items, self.num_items))
-    if subset.device != self.device:
-      raise ValueError('%s: the subset is on %s, the index on %s' % (who, subset.device, self.device))
+    self._made_here(subset, who, 'subset', IndexSubset, 'VideoIndex.subset', item_pooling)
 
   def _norm(self, norm, who):
-    if not isinstance(norm, HubNorm):
-      raise ValueError('%s: norm must come from VideoIndex.hub_norm, got %s' % (who, type(norm).__name__))
-    if norm.num_items != self.num_items:
-      raise ValueError('%s: the norm was built for %d items, the index holds %d' % (who, norm.num_items, self.num_items))
-    if norm.device != self.device:
-      raise ValueError('%s: the norm is on %s, the index on %s' % (who, norm.device, self.device))
+    self._made_here(norm, who, 'norm', HubNorm, 'VideoIndex.hub_norm')
 
   def grouping(self, group_ids):
     """group_ids: int64 [num_items] on the index device, the group of every item, values 0 .. 2^31 - 2 in any labelling
@@ -996,33 +1039,12 @@ class VideoIndex(_Index):
     return IndexGrouping(*self._group_ids(group_ids))
 
   def _grouping(self, grouping, who):
-    if not isinstance(grouping, IndexGrouping):
-      raise ValueError('%s: grouping must come from VideoIndex.grouping, got %s' % (who, type(grouping).__name__))
-    if grouping.num_items != self.num_items:
-      raise ValueError('%s: the grouping was built for %d items, the index holds %d' % (
-          who, grouping.num_items, self.num_items))
-    if grouping.device != self.device:
-      raise ValueError('%s: the grouping is on %s, the index on %s' % (who, grouping.device, self.device))
+    self._made_here(grouping, who, 'grouping', IndexGrouping, 'VideoIndex.grouping')
 
   def _search_groups(self, q, qw, k, grouping, subset):
     """`search_groups` behind its argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the index device, 1 <= k <=
-    grouping.num_groups: the width of the outputs.  Nothing here waits for the device."""
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    scores = torch.empty(nq, k, device=self.device, dtype=torch.float32)
-    groups = torch.empty(nq, k, device=self.device, dtype=torch.int64)
-    items = torch.empty(nq, k, device=self.device, dtype=torch.int64)
-    if nq == 0:
-      return scores, groups, items
-    fn, name = self._entry('topk_groups')
-    words = None if subset is None else subset.words
-    with torch.cuda.device(self.device):
-      for r0, r1 in self._row_batches(nq, 8 * k * -(-nv // 4096)):  # a row's chunk lists at full-size chunks
-        n = r1 - r0
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        ws = torch.empty(_lib.lib().mmt_topk_workspace_keys(n, nv, k), device=self.device, dtype=torch.int64)
-        check(fn(*operands, n, nv, m, d, k, ops._p(grouping.ids), ops._p(words), ops._p(ws), ops._p(scores[r0:r1]),
-                 ops._p(groups[r0:r1]), ops._p(items[r0:r1]), ops._stream()), name)
-    return scores, groups, items
+    grouping.num_groups: the width of the three outputs.  Nothing here waits for the device."""
+    return self._search(q, qw, k, _Scan(subset), grouping)
 
   def _entry(self, op, variant=''):
     """The C entry point of a scan over this index's storage: op 'topk', 'topk_groups', 'rank', 'thresholds', 'count',
@@ -1058,10 +1080,10 @@ class VideoIndex(_Index):
     batch = max(block, (_BATCH_BYTES // per_row) // block * block)
     return [(r0, min(nq, r0 + batch)) for r0 in range(0, nq, batch)]
 
-  def _batches(self, nq, t_max, pooling=None):
+  def _batches(self, nq, t_max, pooling=None, columns=None):
     """Row ranges of the rank and range passes: a row's (pooled: a set's) thresholds and chunk counters at full-size
-    chunks."""
-    return self._row_batches(nq, 4 * t_max * (1 + 2 * -(-self.num_items // 4096)), pooling)
+    chunks of the items (item-pooled: of the given virtual columns)."""
+    return self._row_batches(nq, 4 * t_max * (1 + 2 * -(-(self.num_items if columns is None else columns) // 4096)), pooling)
 
   def _hub_norm(self, b, bw, beta, hubs):
     return HubNorm(self._col_lse(b, bw, beta), beta, b.shape[0], hubs)
@@ -1083,146 +1105,68 @@ class VideoIndex(_Index):
                  ops._p(lse if r1 == nb else None), ops._stream()), name)
     return lse
 
-  def _pool_args(self, pooling, r0, r1):
-    """Rows r0 .. r1 - 1 of a pooled scan (whole sets) -> the entry points' (row weights, NS, C, mode) and the sets' range."""
-    c = pooling.set_size
-    return (ops._p(pooling._on(self.device)[r0:r1]), (r1 - r0) // c, c, _POOL_MODES[pooling.mode]), r0 // c, r1 // c
+  def _sizes(self, scan, r0, r1):
+    """What differs between the entry points of the three kinds for query rows r0 .. r1 - 1 (with a pooling: whole sets) ->
+    (their size arguments in their order, a pooled kind's led by its weights; those of them its workspace-size functions
+    take; the range of result rows the batch writes: its rows, or its sets)."""
+    n, nv = r1 - r0, self.num_items
+    if scan.item_pooling is not None:
+      ip = scan.item_pooling
+      dims = (n, ip.num_sets, ip.set_size)
+      return (ops._p(ip.weights),) + dims + (_POOL_MODES[ip.mode],), dims, (r0, r1)
+    if scan.pooling is not None:
+      pool, c = scan.pooling, scan.pooling.set_size
+      return ((ops._p(pool._on(self.device)[r0:r1]), n // c, c, _POOL_MODES[pool.mode], nv), (n // c, c, nv),
+              (r0 // c, r1 // c))
+    return (n, nv), (n, nv), (r0, r1)
 
-  def _search_pooled(self, q, qw, k, subset, pooling):
-    """`search` with a pooling behind its checks -> (scores, indices) [num_sets, k'].  Nothing here waits for the device."""
+  def _search(self, q, qw, k, scan, grouping=None):
+    """The top-k pass of `search` and `search_groups` behind their argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the
+    index device, the scan's parts this index's own -> (scores, indices), with a grouping (scores, groups, items), one
+    row per query or query set, min(k, the candidates) wide (a grouping: k).  The unmasked plain scan is handed k as it
+    is and writes min(k, NV) columns; only with exclusions can a slot stay without a candidate, so only then are the
+    outputs filled beforehand.  Nothing here waits for the device."""
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    k = min(k, nv if subset is None else subset.count)
-    scores = torch.empty(pooling.num_sets, k, device=self.device, dtype=torch.float32)
-    indices = torch.empty(pooling.num_sets, k, device=self.device, dtype=torch.int64)
+    masked = scan.subset is not None or scan.ex is not None
+    if grouping is None and (masked or scan.kind):
+      k = min(k, scan.candidates(self))  # lists no longer than the candidates: the outputs stay dense
+    outs = _lists(2 if grouping is None else 3, self.device, scan.rows(q), min(k, nv), vacant=scan.ex is not None)
     if nq == 0:
-      return scores, indices
-    fn, name = self._entry('topk', '_pooled')
-    words = None if subset is None else subset.words
+      return outs
+    if grouping is not None:
+      fn, name = self._entry('topk_groups')
+    else:
+      fn, name = self._entry('topk', scan.kind or ('_norm' if scan.norm is not None else '_ex' if masked else ''))
+    workspace = getattr(_lib.lib(), 'mmt_topk%s_workspace_keys' % scan.kind)
     with torch.cuda.device(self.device):
-      for r0, r1 in self._row_batches(nq, 8 * k * -(-nv // 4096), pooling):  # a set's chunk lists at full-size chunks
+      # a row's (pooled: a set's) chunk lists at full-size chunks
+      for r0, r1 in self._row_batches(nq, 8 * k * -(-scan.columns(self) // 4096), scan.pooling):
         operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        pool, s0, s1 = self._pool_args(pooling, r0, r1)
-        ws = torch.empty(_lib.lib().mmt_topk_pooled_workspace_keys(s1 - s0, pooling.set_size, nv, k), device=self.device,
-                         dtype=torch.int64)
-        check(fn(*operands, *pool, nv, m, d, k, ops._p(words), ops._p(ws), ops._p(scores[s0:s1]), ops._p(indices[s0:s1]),
-                 ops._stream()), name)
-    return scores, indices
+        sizes, dims, (o0, o1) = self._sizes(scan, r0, r1)
+        if grouping is not None:
+          extra = (ops._p(grouping.ids), scan.words())
+        elif scan.kind:
+          extra = (scan.words(),)
+        elif masked or scan.norm is not None:  # _ex and _norm: subset words, the batch's exclusions, E; then beta, lse
+          extra = (scan.words(), ops._p(None if scan.ex is None else scan.ex[r0:r1]),
+                   0 if scan.ex is None else scan.ex.shape[1]) + scan.norm_args()
+        else:
+          extra = ()
+        ws = torch.empty(workspace(*dims, k), device=self.device, dtype=torch.int64)
+        check(fn(*operands, *sizes, m, d, k, *extra, ops._p(ws), *[ops._p(o[o0:o1]) for o in outs], ops._stream()), name)
+    return outs
 
-  def _itemset_args(self, ip, n):
-    """The entry points' (item weights, NQ, NT, C, mode) for n query rows."""
-    return ops._p(ip.weights), n, ip.num_sets, ip.set_size, _POOL_MODES[ip.mode]
-
-  def _search_itemsets(self, q, qw, k, subset, ip):
-    """`search` with an item pooling behind its checks -> (scores, set numbers) [NQ, k'].  Nothing here waits for the
-    device."""
-    nq, m, d = q.shape[0], self.num_experts, self.dim
-    k = min(k, ip.num_sets if subset is None else subset.count)
-    scores = torch.empty(nq, k, device=self.device, dtype=torch.float32)
-    indices = torch.empty(nq, k, device=self.device, dtype=torch.int64)
-    if nq == 0:
-      return scores, indices
-    fn, name = self._entry('topk', '_itemsets')
-    words = None if subset is None else subset.words
-    with torch.cuda.device(self.device):
-      for r0, r1 in self._row_batches(nq, 8 * k * -(-ip._columns // 4096)):  # a row's chunk lists at full-size chunks
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        ws = torch.empty(_lib.lib().mmt_topk_itemsets_workspace_keys(r1 - r0, ip.num_sets, ip.set_size, k),
-                         device=self.device, dtype=torch.int64)
-        check(fn(*operands, *self._itemset_args(ip, r1 - r0), m, d, k, ops._p(words), ops._p(ws), ops._p(scores[r0:r1]),
-                 ops._p(indices[r0:r1]), ops._stream()), name)
-    return scores, indices
-
-  def _itemset_batches(self, nq, t_max, ip):
-    """Row ranges of the item-pooled rank passes: a row's thresholds and chunk counters at full-size chunks."""
-    return self._row_batches(nq, 4 * t_max * (1 + 2 * -(-ip._columns // 4096)))
-
-  def _target_scores_itemsets(self, q, qw, targets, ip):
-    """`target_scores` with an item pooling behind its checks: targets [NQ] or [NQ, T] set numbers."""
-    nq, m, d = q.shape[0], self.num_experts, self.dim
-    tg = targets.reshape(nq, -1).contiguous()
-    thr = torch.empty(tg.shape, device=self.device, dtype=torch.float32)
-    if nq == 0:
-      return thr.reshape(targets.shape)
-    fn, name = self._entry('thresholds', '_itemsets')
-    with torch.cuda.device(self.device):
-      for r0, r1 in self._itemset_batches(nq, min(MAX_T, tg.shape[1]), ip):
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        for tgs, (out,) in _column_groups(tg, (thr,), r0, r1):
-          check(fn(*operands, *self._itemset_args(ip, r1 - r0), m, d, ops._p(tgs), tgs.shape[1], ops._p(out), ops._stream()),
-                name)
-    return thr.reshape(targets.shape)
-
-  def _threshold_counts_itemsets(self, q, qw, thresholds, subset, ip):
-    """`threshold_counts` with an item pooling behind its checks: the counts are over the sets."""
-    nq, m, d = q.shape[0], self.num_experts, self.dim
-    thr = thresholds.reshape(nq, -1).contiguous()
-    greater = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
-    equal = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
-    if nq == 0:
-      return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
-    fn, name = self._entry('count', '_itemsets')
-    words = None if subset is None else subset.words
-    t_max = min(MAX_T, thr.shape[1])
-    with torch.cuda.device(self.device):
-      for r0, r1 in self._itemset_batches(nq, t_max, ip):
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        ws = torch.empty(_lib.lib().mmt_count_itemsets_workspace_ints(r1 - r0, ip.num_sets, ip.set_size, t_max),
-                         device=self.device, dtype=torch.int32)
-        for ts, (gs, es) in _column_groups(thr, (greater, equal), r0, r1):
-          check(fn(*operands, *self._itemset_args(ip, r1 - r0), m, d, ops._p(ts), ts.shape[1], ops._p(words), ops._p(ws),
-                   ops._p(gs), ops._p(es), ops._stream()), name)
-    return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
-
-  def _search(self, q, qw, k, subset, ex, norm=None, pooling=None, item_pooling=None):
-    """`search` behind its argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the index device, ex None or int64 [NQ, E]
-    there, norm None or a HubNorm of this index (every query normalised), pooling None or a QueryPooling of NQ rows (then
-    ex and norm are None), item_pooling None or an ItemPooling of this index (then the others are None).  Nothing here
-    waits for the device."""
-    if item_pooling is not None:
-      return self._search_itemsets(q, qw, k, subset, item_pooling)
-    if pooling is not None:
-      return self._search_pooled(q, qw, k, subset, pooling)
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    masked = subset is not None or ex is not None
-    if masked:
-      k = min(k, nv if subset is None else subset.count)  # lists no longer than the candidates: the outputs stay dense
-    kout = min(k, nv)
-    if ex is None:
-      scores = torch.empty(nq, kout, device=self.device, dtype=torch.float32)
-      indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
-    else:  # the merge writes only the slots that have a candidate
-      scores = torch.full((nq, kout), float('-inf'), device=self.device, dtype=torch.float32)
-      indices = torch.full((nq, kout), -1, device=self.device, dtype=torch.int64)
-    if nq == 0:
-      return scores, indices
-    fn, name = self._entry('topk', '_norm' if norm is not None else '_ex' if masked else '')
-    with torch.cuda.device(self.device):
-      for r0, r1 in self._row_batches(nq, 8 * k * -(-nv // 4096)):  # a row's chunk lists at full-size chunks
-        n = r1 - r0
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        extra = ()  # of the _ex and _norm entry points: subset words, exclusions of the batch, E; then beta, lse
-        if masked or norm is not None:
-          extra = (ops._p(None if subset is None else subset.words), ops._p(None if ex is None else ex[r0:r1]),
-                   0 if ex is None else ex.shape[1])
-        if norm is not None:
-          extra += (norm.beta, ops._p(norm.lse))
-        ws = torch.empty(_lib.lib().mmt_topk_workspace_keys(n, nv, k), device=self.device, dtype=torch.int64)
-        check(fn(*operands, n, nv, m, d, k, *extra, ops._p(ws), ops._p(scores[r0:r1]), ops._p(indices[r0:r1]),
-                 ops._stream()), name)
-    return scores, indices
-
-  def _rank_counts(self, q, qw, tg, subset, norm=None, pooling=None, item_pooling=None):
-    """`rank_counts` behind its checks: tg int64 [NQ >= 1, T] on the index device -> (greater, equal) int32 [NQ, T].  Plain:
-    the threshold and the count pass in one call per batch (mmt_search_rank); with a norm, a pooling (tg [num_sets, T]) or
-    an item pooling (tg set numbers): one after the other."""
-    if norm is not None or pooling is not None or item_pooling is not None:
-      return self._threshold_counts(q, qw, self._target_scores(q, qw, tg, norm, pooling, item_pooling), subset, norm, pooling,
-                                    item_pooling)
+  def _rank_counts(self, q, qw, tg, scan):
+    """`rank_counts` behind its checks: tg int64 [NQ >= 1, T] on the index device (with a pooling [num_sets, T], with an
+    item pooling set numbers) -> (greater, equal) int32 of its shape.  Plain: the threshold and the count pass in one
+    call per batch (mmt_search_rank); with a norm, a pooling or an item pooling: one after the other."""
+    if scan.norm is not None or scan.kind:
+      return self._threshold_counts(q, qw, self._target_scores(q, qw, tg, scan), scan)
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
     greater = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
     equal = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
-    fn, name = self._entry('rank', '' if subset is None else '_ex')
-    words = () if subset is None else (ops._p(subset.words),)
+    fn, name = self._entry('rank', '' if scan.subset is None else '_ex')
+    words = () if scan.subset is None else (scan.words(),)
     t_max = min(MAX_T, tg.shape[1])
     with torch.cuda.device(self.device):
       for r0, r1 in self._batches(nq, t_max):
@@ -1246,56 +1190,32 @@ class VideoIndex(_Index):
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
-    q, qw, dynamic = self._scan_args('ranks', embds, weights, None, norm, dynamic, None, pooling, item_pooling)
-    nq = _result_rows(q, pooling)
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, norm, dynamic, pooling=pooling, item_pooling=item_pooling)
+    scan = _Scan(norm=norm, pooling=pooling, item_pooling=item_pooling)
+    nq = scan.rows(q)
     if targets.shape[0] != nq:
       raise ValueError('ranks: %d %s but targets %s' % (nq, 'queries' if pooling is None else 'query sets',
                                                         tuple(targets.shape)))
     if nq:
-      self._target_range(targets, item_pooling)
-    if item_pooling is not None:
-      return self._target_scores(q, qw, targets, None, None, item_pooling)
-    if pooling is not None:
-      return self._target_scores(q, qw, targets, None, pooling)
-    out = (self._target_scores(q, qw, targets, norm),)
-    return self._dynamic(dynamic, q, qw, None, None, norm, out, lambda: (self._target_scores(q, qw, targets),))[0]
+      self._target_range(targets, scan)
+    return self._dynamic(dynamic, q, qw, scan, lambda scan: (self._target_scores(q, qw, targets, scan),))[0]
 
-  def _target_scores_pooled(self, q, qw, targets, pooling):
-    """`target_scores` with a pooling behind its checks: targets [num_sets] or [num_sets, T]."""
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    tg = targets.reshape(pooling.num_sets, -1).contiguous()
+  def _target_scores(self, q, qw, targets, scan):
+    """The threshold pass behind the checks: targets int64 [R] or [R, T] on the index device, R the scan's result rows,
+    item numbers (with an item pooling: set numbers); one outside 0 .. the last of them gives NaN.  The scan's subset
+    plays no part: a target is scored wherever it lies.  Nothing here waits for the device."""
+    nq, m, d = q.shape[0], self.num_experts, self.dim
+    tg = targets.reshape(scan.rows(q), -1).contiguous()
     thr = torch.empty(tg.shape, device=self.device, dtype=torch.float32)
     if nq == 0:
       return thr.reshape(targets.shape)
-    fn, name = self._entry('thresholds', '_pooled')
+    fn, name = self._entry('thresholds', scan.kind or ('' if scan.norm is None else '_norm'))
     with torch.cuda.device(self.device):
-      for r0, r1 in self._batches(nq, min(MAX_T, tg.shape[1]), pooling):
+      for r0, r1 in self._batches(nq, min(MAX_T, tg.shape[1]), scan.pooling, scan.columns(self)):
         operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        pool, s0, s1 = self._pool_args(pooling, r0, r1)
-        for tgs, (out,) in _column_groups(tg, (thr,), s0, s1):
-          check(fn(*operands, *pool, nv, m, d, ops._p(tgs), tgs.shape[1], ops._p(out), ops._stream()), name)
-    return thr.reshape(targets.shape)
-
-  def _target_scores(self, q, qw, targets, norm=None, pooling=None, item_pooling=None):
-    """`target_scores` behind its checks; a target outside 0 .. num_items - 1 gives NaN; norm None or a HubNorm of this
-    index (every query normalised); pooling None or a QueryPooling of NQ rows (then norm is None); item_pooling None or
-    an ItemPooling of this index (then the others are None).  Nothing here waits for the device."""
-    if item_pooling is not None:
-      return self._target_scores_itemsets(q, qw, targets, item_pooling)
-    if pooling is not None:
-      return self._target_scores_pooled(q, qw, targets, pooling)
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    tg = targets.reshape(nq, -1).contiguous()
-    thr = torch.empty(tg.shape, device=self.device, dtype=torch.float32)
-    if nq == 0:
-      return thr.reshape(targets.shape)
-    fn, name = self._entry('thresholds', '' if norm is None else '_norm')
-    extra = () if norm is None else (norm.beta, ops._p(norm.lse))
-    with torch.cuda.device(self.device):
-      for r0, r1 in self._batches(nq, min(MAX_T, tg.shape[1])):
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        for tgs, (out,) in _column_groups(tg, (thr,), r0, r1):
-          check(fn(*operands, r1 - r0, nv, m, d, ops._p(tgs), tgs.shape[1], *extra, ops._p(out), ops._stream()), name)
+        sizes, _, (o0, o1) = self._sizes(scan, r0, r1)
+        for tgs, (out,) in _column_groups(tg, (thr,), o0, o1):
+          check(fn(*operands, *sizes, m, d, ops._p(tgs), tgs.shape[1], *scan.norm_args(), ops._p(out), ops._stream()), name)
     return thr.reshape(targets.shape)
 
   def threshold_counts(self, embds, weights, thresholds, subset=None, norm=None, dynamic=None, pooling=None,
@@ -1317,65 +1237,33 @@ class VideoIndex(_Index):
       raise ValueError('ranks: thresholds must be on the index device %s, got %s' % (self.device, thresholds.device))
     if thresholds.dim() not in (1, 2) or thresholds.dim() == 2 and thresholds.shape[1] < 1:
       raise ValueError('ranks: thresholds [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(thresholds.shape),))
-    q, qw, dynamic = self._scan_args('ranks', embds, weights, subset, norm, dynamic, None, pooling, item_pooling)
-    nq = _result_rows(q, pooling)
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, norm, dynamic, subset, pooling=pooling, item_pooling=item_pooling)
+    scan = _Scan(subset=subset, norm=norm, pooling=pooling, item_pooling=item_pooling)
+    nq = scan.rows(q)
     if thresholds.shape[0] != nq:
       raise ValueError('ranks: %d %s but thresholds %s' % (nq, 'queries' if pooling is None else 'query sets',
                                                            tuple(thresholds.shape)))
-    if item_pooling is not None:
-      return self._threshold_counts(q, qw, thresholds, subset, None, None, item_pooling)
-    if pooling is not None:
-      return self._threshold_counts(q, qw, thresholds, subset, None, pooling)
-    out = self._threshold_counts(q, qw, thresholds, subset, norm)
-    return self._dynamic(dynamic, q, qw, subset, None, norm, out, lambda: self._threshold_counts(q, qw, thresholds, subset))
+    return self._dynamic(dynamic, q, qw, scan, lambda scan: self._threshold_counts(q, qw, thresholds, scan))
 
-  def _threshold_counts_pooled(self, q, qw, thresholds, subset, pooling):
-    """`threshold_counts` with a pooling behind its checks: thresholds [num_sets] or [num_sets, T]."""
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    thr = thresholds.reshape(pooling.num_sets, -1).contiguous()
+  def _threshold_counts(self, q, qw, thresholds, scan):
+    """The count pass behind the checks: thresholds float32 [R] or [R, T] on the index device, R the scan's result rows ->
+    (greater, equal) int32 of their shape, over the scan's candidates.  Nothing here waits for the device."""
+    nq, m, d = q.shape[0], self.num_experts, self.dim
+    thr = thresholds.reshape(scan.rows(q), -1).contiguous()
     greater = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
     equal = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
     if nq == 0:
       return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
-    fn, name = self._entry('count', '_pooled')
-    words = None if subset is None else subset.words
+    fn, name = self._entry('count', scan.kind or ('' if scan.norm is None else '_norm'))
+    workspace = getattr(_lib.lib(), 'mmt_count%s_workspace_ints' % scan.kind)
     t_max = min(MAX_T, thr.shape[1])
     with torch.cuda.device(self.device):
-      for r0, r1 in self._batches(nq, t_max, pooling):
+      for r0, r1 in self._batches(nq, t_max, scan.pooling, scan.columns(self)):
         operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        pool, s0, s1 = self._pool_args(pooling, r0, r1)
-        ws = torch.empty(_lib.lib().mmt_count_pooled_workspace_ints(s1 - s0, pooling.set_size, nv, t_max),
-                         device=self.device, dtype=torch.int32)
-        for ts, (gs, es) in _column_groups(thr, (greater, equal), s0, s1):
-          check(fn(*operands, *pool, nv, m, d, ops._p(ts), ts.shape[1], ops._p(words), ops._p(ws), ops._p(gs), ops._p(es),
-                   ops._stream()), name)
-    return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
-
-  def _threshold_counts(self, q, qw, thresholds, subset, norm=None, pooling=None, item_pooling=None):
-    """`threshold_counts` behind its checks; norm None or a HubNorm of this index (every query normalised); pooling None
-    or a QueryPooling of NQ rows (then norm is None); item_pooling None or an ItemPooling of this index (then the others
-    are None).  Nothing here waits for the device."""
-    if item_pooling is not None:
-      return self._threshold_counts_itemsets(q, qw, thresholds, subset, item_pooling)
-    if pooling is not None:
-      return self._threshold_counts_pooled(q, qw, thresholds, subset, pooling)
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    thr = thresholds.reshape(nq, -1).contiguous()
-    greater = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
-    equal = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
-    if nq == 0:
-      return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
-    fn, name = self._entry('count', '' if norm is None else '_norm')
-    extra = () if norm is None else (norm.beta, ops._p(norm.lse))
-    words = None if subset is None else subset.words
-    t_max = min(MAX_T, thr.shape[1])
-    with torch.cuda.device(self.device):
-      for r0, r1 in self._batches(nq, t_max):
-        n = r1 - r0
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        ws = torch.empty(_lib.lib().mmt_count_workspace_ints(n, nv, t_max), device=self.device, dtype=torch.int32)
-        for ts, (gs, es) in _column_groups(thr, (greater, equal), r0, r1):
-          check(fn(*operands, n, nv, m, d, ops._p(ts), ts.shape[1], ops._p(words), *extra, ops._p(ws), ops._p(gs),
+        sizes, dims, (o0, o1) = self._sizes(scan, r0, r1)
+        ws = torch.empty(workspace(*dims, t_max), device=self.device, dtype=torch.int32)
+        for ts, (gs, es) in _column_groups(thr, (greater, equal), o0, o1):
+          check(fn(*operands, *sizes, m, d, ops._p(ts), ts.shape[1], scan.words(), *scan.norm_args(), ops._p(ws), ops._p(gs),
                    ops._p(es), ops._stream()), name)
     return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
 
@@ -1590,13 +1478,14 @@ class ShardedVideoIndex(_Index):
     self.num_items = last
     return first, last
 
-  def _tables(self, shards):
-    """The item tables' addresses of the given shards as a device array on the primary, where the tables themselves are:
-    the `ids` of the merge kernel."""
-    if shards not in self._table_cache:
-      self._table_cache[shards] = torch.tensor([self.shards[s].ids.data_ptr() for s in shards],
-                                               dtype=torch.int64).to(self.device)
-    return self._table_cache[shards]
+  def _tables(self, shards, item_pooling=None):
+    """The addresses of the given shards' item tables -- with an item pooling: of its set tables -- as a device array on
+    the primary, where the tables themselves are: the `ids` of the merge kernels.  Built once per owner and shard tuple."""
+    cache = (self if item_pooling is None else item_pooling)._table_cache
+    if shards not in cache:
+      tables = [sh.ids for sh in self.shards] if item_pooling is None else item_pooling.tables
+      cache[shards] = torch.tensor([tables[s].data_ptr() for s in shards], dtype=torch.int64).to(self.device)
+    return cache[shards]
 
   def _live(self, subset=None):
     """(number, shard) of the shards that hold items -- with a subset: allowed items."""
@@ -1640,39 +1529,14 @@ class ShardedVideoIndex(_Index):
   def subset(self, items):
     """items: bool [num_items] or int64 item numbers on the primary device, as VideoIndex.subset -> ShardedSubset: the set
     cut into one IndexSubset per shard, in the shard's own numbers.  After a further `add` it is refused."""
-    mask, total = self._subset_mask(items)
-    parts = []
-    for sh in self.shards:
-      part = None
-      if sh.num_items:
-        local = mask[sh.ids[:sh.num_items]]  # gathered on the primary, where the table is
-        with torch.cuda.device(sh.device):
-          local = local.to(sh.device)
-          count = int(local.sum())
-          if count:
-            part = IndexSubset(local, count)
-      parts.append(part)
-    return ShardedSubset(parts, mask, total)
+    return _cut_subset(*self._subset_mask(items),
+                       [(sh.ids[:sh.num_items] if sh.num_items else None, sh.device) for sh in self.shards])
 
   def _subset(self, subset, who, item_pooling=None):
-    if not isinstance(subset, ShardedSubset):
-      raise ValueError('%s: subset must come from ShardedVideoIndex.subset, got %s' % (who, type(subset).__name__))
-    if item_pooling is not None:
-      if subset.num_items != item_pooling.num_sets:
-        raise ValueError('%s: the subset was built for %d sets, the item pooling has %d' % (
-            who, subset.num_items, item_pooling.num_sets))
-    elif subset.num_items != self.num_items:
-      raise ValueError('%s: the subset was built for %d items, the index holds %d' % (who, subset.num_items, self.num_items))
-    if subset.device != self.device or len(subset.parts) != len(self.shards):
-      raise ValueError('%s: the subset belongs to another index' % who)
+    self._made_here(subset, who, 'subset', ShardedSubset, 'ShardedVideoIndex.subset', item_pooling)
 
   def _norm(self, norm, who):
-    if not isinstance(norm, ShardedHubNorm):
-      raise ValueError('%s: norm must come from ShardedVideoIndex.hub_norm, got %s' % (who, type(norm).__name__))
-    if norm.num_items != self.num_items:
-      raise ValueError('%s: the norm was built for %d items, the index holds %d' % (who, norm.num_items, self.num_items))
-    if norm.device != self.device or len(norm.parts) != len(self.shards):
-      raise ValueError('%s: the norm belongs to another index' % who)
+    self._made_here(norm, who, 'norm', ShardedHubNorm, 'ShardedVideoIndex.hub_norm')
 
   def _hub_norm(self, b, bw, beta, hubs):
     """`hub_norm` behind its checks -> ShardedHubNorm: the bank (given on the primary) is copied to every shard, which
@@ -1691,37 +1555,36 @@ class ShardedVideoIndex(_Index):
       parts.append(part)
     return ShardedHubNorm(parts, lse, beta, b.shape[0], hubs)
 
-  def _search(self, q, qw, k, subset, ex, norm=None, pooling=None, item_pooling=None):
-    """`search` behind its checks: q, qw on the primary, ex None or int64 [NQ, E] global numbers there, norm None or a
-    ShardedHubNorm of this index (every query normalised), pooling None or a QueryPooling of NQ rows (then ex and norm
-    are None): every shard gets all the rows and returns one list per set.  item_pooling None or a ShardedItemPooling of
-    this index (then the others are None): every shard searches its own sets and the merge goes through the set tables."""
-    ip = item_pooling
-    nq = _result_rows(q, pooling)
-    kout = min(k, (self.num_items if ip is None else ip.num_sets) if subset is None else subset.count)
-    scores = torch.empty(nq, kout, device=self.device, dtype=torch.float32)
-    indices = torch.empty(nq, kout, device=self.device, dtype=torch.int64)
-    if nq == 0:
-      return scores, indices
-    live = self._live(subset)
-    kin = min(kout, max((sh.num_items if ip is None else ip.parts[s].num_sets) if subset is None else subset.parts[s].count
-                        for s, sh in live))
-    with torch.cuda.device(self.device):  # the staged lists; the slots a shorter list leaves are empty
-      st_scores = torch.full((len(live), nq, kin), float('-inf'), device=self.device, dtype=torch.float32)
-      st_index = torch.full((len(live), nq, kin), -1, device=self.device, dtype=torch.int64)
-      tables = (self if ip is None else ip)._tables(tuple(s for s, _ in live))
-    for i, (s, sh) in enumerate(live):
-      ex_s = None if ex is None else self._local(ex, s).to(sh.device)
-      with torch.cuda.device(sh.device):
-        part = sh.index._search(q.to(sh.device), qw.to(sh.device), kout, None if subset is None else subset.parts[s], ex_s,
-                                None if norm is None else norm.parts[s], pooling, None if ip is None else ip.parts[s])
-      width = part[0].shape[1]
-      st_scores[i, :, :width].copy_(part[0])
-      st_index[i, :, :width].copy_(part[1])
+  def _merged(self, outs, live, kin, merge, tables, lists):
+    """Fills outs -- result lists [NQ, kout] on the primary -- from the live shards: lists(s, sh), called under shard s's
+    device, gives its lists, at most kin wide, in its own numbers; they are staged on the primary (the slots a shorter
+    list leaves are empty) and merged there in one launch of `merge` through `tables`, the shards' local -> global tables."""
+    nq, kout = outs[0].shape
     with torch.cuda.device(self.device):
-      check(_lib.lib().mmt_search_merge_lists(ops._p(st_scores), ops._p(st_index), ops._p(tables), len(live), nq, kin, kout,
-                                              ops._p(scores), ops._p(indices), ops._stream()), 'mmt_search_merge_lists')
-    return scores, indices
+      staged = _lists(len(outs), self.device, len(live), nq, kin, vacant=True)
+    for i, (s, sh) in enumerate(live):
+      with torch.cuda.device(sh.device):
+        part = lists(s, sh)
+      for st, mine in zip(staged, part):
+        st[i, :, :mine.shape[1]].copy_(mine)
+    with torch.cuda.device(self.device):
+      check(getattr(_lib.lib(), merge)(*[ops._p(st) for st in staged], ops._p(tables), len(live), nq, kin, kout,
+                                       *[ops._p(o) for o in outs], ops._stream()), merge)
+    return outs
+
+  def _search(self, q, qw, k, scan):
+    """`search` behind its checks: q, qw and the scan's exclusions (global numbers) on the primary, its parts this index's
+    own.  Every live shard searches with its view of the scan -- with a pooling it gets all the rows and returns one list
+    per set, with an item pooling it searches its own sets and the merge goes through the set tables."""
+    kout = min(k, scan.candidates(self))
+    outs = _lists(2, self.device, scan.rows(q), kout)
+    if q.shape[0] == 0:
+      return outs
+    live = self._live(scan.subset)
+    views = {s: scan.shard(s, self) for s, _ in live}
+    kin = min(kout, max(views[s].candidates(sh.index) for s, sh in live))
+    return self._merged(outs, live, kin, 'mmt_search_merge_lists', self._tables(tuple(views), scan.item_pooling),
+                        lambda s, sh: sh.index._search(q.to(sh.device), qw.to(sh.device), kout, views[s]))
 
   def grouping(self, group_ids):
     """group_ids: int64 [num_items] on the primary device, as VideoIndex.grouping -> ShardedGrouping: the ids cut into one
@@ -1740,69 +1603,45 @@ class ShardedVideoIndex(_Index):
     return ShardedGrouping(parts, ids, num_groups)
 
   def _grouping(self, grouping, who):
-    if not isinstance(grouping, ShardedGrouping):
-      raise ValueError('%s: grouping must come from ShardedVideoIndex.grouping, got %s' % (who, type(grouping).__name__))
-    if grouping.num_items != self.num_items:
-      raise ValueError('%s: the grouping was built for %d items, the index holds %d' % (
-          who, grouping.num_items, self.num_items))
-    if grouping.device != self.device or len(grouping.parts) != len(self.shards):
-      raise ValueError('%s: the grouping belongs to another index' % who)
+    self._made_here(grouping, who, 'grouping', ShardedGrouping, 'ShardedVideoIndex.grouping')
 
   def _search_groups(self, q, qw, k, grouping, subset):
     """`search_groups` behind its checks: q, qw on the primary, 1 <= k <= grouping.num_groups.  Every live shard returns its
     best min(k, its groups) groups; the merge on the primary keeps one entry per group."""
-    nq = q.shape[0]
-    scores = torch.empty(nq, k, device=self.device, dtype=torch.float32)
-    groups = torch.empty(nq, k, device=self.device, dtype=torch.int64)
-    items = torch.empty(nq, k, device=self.device, dtype=torch.int64)
-    if nq == 0:
-      return scores, groups, items
-    live = self._live(subset)
+    outs = _lists(3, self.device, q.shape[0], k)
+    if q.shape[0] == 0:
+      return outs
+    scan, live = _Scan(subset), self._live(subset)
     kin = min(k, max(grouping.parts[s].num_groups for s, _ in live))
-    with torch.cuda.device(self.device):  # the staged lists; the slots a shorter list leaves are empty
-      st_scores = torch.full((len(live), nq, kin), float('-inf'), device=self.device, dtype=torch.float32)
-      st_groups = torch.full((len(live), nq, kin), -1, device=self.device, dtype=torch.int64)
-      st_index = torch.full((len(live), nq, kin), -1, device=self.device, dtype=torch.int64)
-      tables = self._tables(tuple(s for s, _ in live))
-    for i, (s, sh) in enumerate(live):
-      part = grouping.parts[s]
-      with torch.cuda.device(sh.device):
-        out = sh.index._search_groups(q.to(sh.device), qw.to(sh.device), min(k, part.num_groups), part,
-                                      None if subset is None else subset.parts[s])
-      width = out[0].shape[1]
-      st_scores[i, :, :width].copy_(out[0])
-      st_groups[i, :, :width].copy_(out[1])
-      st_index[i, :, :width].copy_(out[2])
-    with torch.cuda.device(self.device):
-      check(_lib.lib().mmt_search_merge_group_lists(ops._p(st_scores), ops._p(st_groups), ops._p(st_index), ops._p(tables),
-                                                    len(live), nq, kin, k, ops._p(scores), ops._p(groups), ops._p(items),
-                                                    ops._stream()), 'mmt_search_merge_group_lists')
-    return scores, groups, items
 
-  def _rank_counts(self, q, qw, tg, subset, norm=None, pooling=None, item_pooling=None):
+    def lists(s, sh):
+      part = grouping.parts[s]
+      return sh.index._search_groups(q.to(sh.device), qw.to(sh.device), min(k, part.num_groups), part,
+                                     scan.shard(s, self).subset)
+    return self._merged(outs, live, kin, 'mmt_search_merge_group_lists', self._tables(tuple(s for s, _ in live)), lists)
+
+  def _rank_counts(self, q, qw, tg, scan):
     """`rank_counts` behind its checks: tg int64 [NQ, T] global numbers on the primary -> (greater, equal) int32 [NQ, T];
-    with a pooling (then norm is None) tg is [num_sets, T] and every shard gets all the rows; with an item pooling (then
-    the others are None) tg holds global set numbers, translated through its set maps."""
-    ip = item_pooling
+    with a pooling tg is [num_sets, T] and every shard gets all the rows; with an item pooling tg holds global set
+    numbers, translated through its set maps.  A target is scored by the shard that holds it and counted by every shard
+    that has candidates."""
     live = self._live()
-    queries = {}
+    maps = None if scan.item_pooling is None else scan.item_pooling._maps
+    queries, views = {}, {}
     thr = torch.full(tg.shape, float('nan'), device=self.device, dtype=torch.float32)
     for s, sh in live:
-      local = self._local(tg, s, None if ip is None else ip._maps)
-      queries[s] = (q.to(sh.device), qw.to(sh.device))
+      local = self._local(tg, s, maps)
+      queries[s], views[s] = (q.to(sh.device), qw.to(sh.device)), scan.shard(s, self)
       with torch.cuda.device(sh.device):
-        mine = sh.index._target_scores(*queries[s], local.to(sh.device), None if norm is None else norm.parts[s], pooling,
-                                       None if ip is None else ip.parts[s])
+        mine = sh.index._target_scores(*queries[s], local.to(sh.device), views[s])
       thr = torch.where(local >= 0, mine.to(self.device), thr)
     greater = torch.zeros(tg.shape, device=self.device, dtype=torch.int32)
     equal = torch.zeros(tg.shape, device=self.device, dtype=torch.int32)
     for s, sh in live:
-      part = None if subset is None else subset.parts[s]
-      if subset is not None and part is None:
+      if scan.subset is not None and views[s].subset is None:
         continue  # no allowed item here: nothing to count
       with torch.cuda.device(sh.device):
-        gs, es = sh.index._threshold_counts(*queries[s], thr.to(sh.device), part, None if norm is None else norm.parts[s],
-                                            pooling, None if ip is None else ip.parts[s])
+        gs, es = sh.index._threshold_counts(*queries[s], thr.to(sh.device), views[s])
       greater += gs.to(self.device)
       equal += es.to(self.device)
     return greater, equal
@@ -1816,10 +1655,10 @@ class ShardedVideoIndex(_Index):
     torch sorts.  order='score' as VideoIndex.range_search.  Exclusions are applied to the CSR by the caller."""
     q, qw, thr = self._range_args(embds, weights, threshold, subset, order, max_hits)
     nq = q.shape[0]
-    live = self._live(subset)
+    scan, live = _Scan(subset), self._live(subset)
     args, counted = {}, {}
     for s, sh in live:
-      args[s] = (q.to(sh.device), qw.to(sh.device), thr.to(sh.device), None if subset is None else subset.parts[s])
+      args[s] = (q.to(sh.device), qw.to(sh.device), thr.to(sh.device), scan.shard(s, self).subset)
       with torch.cuda.device(sh.device):
         counted[s] = sh.index._range_count(*args[s])
     with torch.cuda.device(self.device):
