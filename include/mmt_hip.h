@@ -813,6 +813,31 @@ int mmt_search_count_bf16_itemsets(const uint16_t* q_hi, const uint16_t* q_lo, c
                                    const float* gw, const float* iw, int NQ, int NT, int C, int mode, int M, int d,
                                    const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
                                    int32_t* equal, void* stream);
+/* Re-scoring of per-query shortlists (search_rescore.hip): "the k best among THESE items", the second stage of a two-stage
+ * search (a wide list from an fp8 index, a range search or another model, re-ranked on the index that holds the items at
+ * full precision).  It replaces a composition of mmt_search_thresholds (at most 32 targets per launch, unsorted, NaN for
+ * none) with a host-side sort, tie rule and de-duplication.  candidates int64 [NQ][C], 1 <= C <= 1024: any order, an
+ * item may repeat, a value outside 0 .. NV - 1 (-1 = none) is checked on the device, never dereferenced, and ignored.
+ * mmt_rescore_workspace_keys: uint64 workspace of one call, NQ * C (one key per pair); MMT_ERR_ARG if NQ < 1 or C is
+ *   outside 1 .. 1024.
+ * mmt_search_rescore / _bf16 / _fp8: operands as mmt_search_thresholds / _bf16 / _fp8 -> scores fp32 / index int64
+ *   [NQ][min(k, C)], 1 <= k <= 128: per query its best distinct candidates under mmt_search_topk's order (score
+ *   descending, -0 tied with +0, equal scores by ascending item), each item once however often it was listed, then
+ *   (-inf, -1).  A score has the bits mmt_search_topk and mmt_search_thresholds give the pair (the same scoring tile
+ *   through a gallery-row indirection), decoded from the key as mmt_search_topk does: a -0 comes back as +0.  Two launches:
+ *   the pairs' keys to the workspace, then per query a bitonic sort in LDS that drops a key equal to its predecessor.  The
+ *   result does not depend on the order of a query's candidates.  No atomics, one writer per slot.  Gates: MMT_ERR_ARG (a
+ *   null pointer, a size, C or k out of range, d % 4 / d % 8 / d % 16), MMT_ERR_ALIGN (query or gallery rows off a 16-byte
+ *   boundary), before any launch. */
+int64_t mmt_rescore_workspace_keys(int NQ, int C);
+int mmt_search_rescore(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                       const int64_t* candidates, int C, int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
+int mmt_search_rescore_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
+                            int NQ, int NV, int M, int d, const int64_t* candidates, int C, int k, uint64_t* ws, float* scores,
+                            int64_t* index, void* stream);
+int mmt_search_rescore_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
+                           const float* gscale, int NQ, int NV, int M, int d, const int64_t* candidates, int C, int k,
+                           uint64_t* ws, float* scores, int64_t* index, void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

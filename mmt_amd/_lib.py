@@ -319,6 +319,14 @@ SIGNATURES = {
                                           c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_search_count_bf16_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
                                                c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # re-scoring of shortlists: the thresholds signatures with (candidates, C, k), a workspace and the two output lists
+    'mmt_rescore_workspace_keys': (c_i64, [c_int, c_int]),
+    'mmt_search_rescore': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp,
+                                   c_vp]),
+    'mmt_search_rescore_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp,
+                                        c_vp, c_vp, c_vp]),
+    'mmt_search_rescore_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int,
+                                       c_vp, c_vp, c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

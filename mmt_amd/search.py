@@ -41,9 +41,10 @@ index only the gallery rounding differs:
     |score_fp8 - score_fp32| <= (2^-4 * <|qf|, |f|> + 2^-10 * scale[g] * sum_k |qf[k]|) / |den|  + 1e-5
 -- e4m3's unit roundoff for normal values, and the subnormal range below 2^-6 * scale[g].  `search` (plain, subset=,
 exclude=), `rank_counts`, `ranks`, `target_scores`, `threshold_counts` and `range_search` work on it, on both index classes,
-with the same score bits on every path.  That is the coarse stage of a two-stage search as it stands: search(k=128) on the
-float8_e4m3fn index, then `target_scores` of the shortlist on a float32 or bfloat16 index of the same items.  Not yet:
-`hub_norm` / norm=, `search_groups`, pooling= and item_pooling= raise ValueError naming the dtype before anything is scored.
+with the same score bits on every path.  That is the coarse stage of a two-stage search: search(k=128) on the
+float8_e4m3fn index, then `rescore` of the shortlist on a float32 or bfloat16 index of the same items -- `search_refined`
+below is the two in one call.  Not yet: `hub_norm` / norm=, `search_groups`, pooling= and item_pooling= raise ValueError
+naming the dtype before anything is scored.
 
     greater, equal = index.rank_counts(embds, weights, targets)   # int32, shape of targets ([NQ] or [NQ, T], int64)
     ranks = index.ranks(embds, weights, targets)                  # float64: greater + (equal - 1) / 2
@@ -184,6 +185,24 @@ accepted when every set is stored whole on one shard, in order, from a local ite
 each shard pools its own sets and the lists are merged through local-set -> global-set tables, bit-identical to one
 VideoIndex.  metric.retrieval_metrics_indexed(caption_mode='avg') builds the reference's 'avg' evaluation on `pooling`
 (text-to-video) and `item_pooling` (video-to-text).
+
+    scores, indices = index.rescore(q, qw, candidates, k=None)        # candidates int64 [NQ, C <= MAX_C = 1024], -1 = none
+    scores, indices = fine.search_refined(q, qw, coarse, k=10, shortlist=MAX_K, subset=None, exclude=None)
+
+The seventh question: the k best among THESE items, per query -- the second stage of a two-stage search, whose shortlist
+comes from a float8_e4m3fn index of the same items, a `range_search`, another model's list, or several of them
+concatenated.  The candidates of a query come in any order, -1 is "none" and an item may be listed more than once: row q
+of the result is the min(k, C) best of the distinct candidates S_q under `search`'s order (score descending, -0 tied with
++0, equal scores by ascending item), each item once, then (-inf, -1) -- what search(q, k, subset=subset(S_q)) returns,
+padded -- and a score has the bits `search` and `target_scores` give the pair on this index, a -0 as +0; k=None is
+min(C, MAX_K).  It is the threshold pass of `rank_counts` for any C with `search`'s order on top: the pairs are scored
+on the scans' own tile through a gallery-row indirection and leave it as keys, 0 for none; one block per query then sorts
+the keys in LDS and drops a key equal to its predecessor -- a repeated item has the same score bits and the same number,
+hence the same key (mmt_search_rescore).  No atomics; the result depends on the candidates of a query as a set, not on
+their order, the row batching or the launch geometry.  ShardedVideoIndex.rescore is bit-identical: every shard re-scores
+the candidates it holds and the lists are merged on the primary.  `search_refined` is host code: coarse.search(k=shortlist,
+subset=, exclude=) on an index TAKEN to hold the same items under the same numbers (same num_items, num_experts, dim and
+device is all that can be checked), then `rescore` on this one.  Out of scope: norm=, pooling=, item_pooling= and groupings.
 """
 import math
 
@@ -195,6 +214,7 @@ from ._lib import check
 MAX_K = 128
 MAX_T = 32  # targets per query and launch of the rank kernels; wider target lists are sliced
 MAX_E = 32  # exclusions per query of a masked search
+MAX_C = 1024  # candidates per query of `rescore`: one query's keys are sorted in LDS
 MAX_SET = 64  # rows per query set of a pooled scan: one 64-row query block holds whole sets
 MAX_ITEM_SET = 128  # items per stored set of an item-pooled scan: one 128-column tile holds whole sets
 _POOL_MODES = {'mean': 0, 'max': 1}  # the `mode` of the pooled entry points
@@ -588,7 +608,8 @@ class _Index:
   (`search`, `rank_counts`, `ranks`, `hub_norm` up to the scan, `search_groups`) and QB-Norm's dynamic rule.  It reads the
   bookkeeping both have -- num_experts, dim, num_items, device (the primary of a sharded index).  Behind its checks a
   public call puts its options into one _Scan and makes one call with it, wrapped in `_dynamic`; the class supplies
-  what happens there -- _search(q, qw, k, scan), _rank_counts(q, qw, tg, scan), _hub_norm, _search_groups -- and names
+  what happens there -- _search(q, qw, k, scan), _rank_counts(q, qw, tg, scan), _hub_norm, _search_groups, and
+  _rescore(q, qw, cand, k) for `rescore`, which takes no scan options -- and names
   its own kinds of subset, norm and grouping for `_made_here` (_subset / _norm / _grouping)."""
 
   @staticmethod
@@ -855,6 +876,70 @@ class _Index:
       none = none | ~subset.mask[targets.clamp(min=0)]
     return torch.where(none, torch.full_like(ranks, float('inf')), ranks)
 
+  def rescore(self, embds, weights, candidates, k=None):
+    """Queries as for `search`; candidates int64 [NQ, C] on the index device, 1 <= C <= MAX_C = 1024, values
+    -1 .. num_items - 1 (-1 = none), in any order, an item as often as it comes -> (scores [NQ, k'] float32, indices
+    [NQ, k'] int64) on the device, k' = min(k, C); k an int in 1 .. MAX_K, None = min(C, MAX_K).  With S_q the distinct
+    non-negative entries of candidates[q], row q holds the min(k', |S_q|) best items of S_q under `search`'s order -- score
+    descending, -0 tied with +0, equal scores by ascending item number -- each once, and (-inf, -1) in the slots left: row q
+    is search(q, k', subset=subset(S_q)), padded.  A score has the very bits `search` and `target_scores` give the pair on
+    THIS index, whatever its dtype (float8_e4m3fn: the scaled score), decoded as `search` decodes it, so a -0 comes back as
+    +0.  The result does not depend on the order of a query's candidates, the row batching or the launch geometry, and on
+    a ShardedVideoIndex not on where an item is stored: it is bit-identical to one VideoIndex's.  The type, device and
+    shape of the candidates are checked before the queries are looked at, their range like the targets of `rank_counts`
+    (one small reduction and a host sync) before anything is scored; nothing after that waits for the device.  Two
+    launches per row batch (mmt_search_rescore): the pairs' keys from the scoring tile of the scans, then a sort per
+    query that drops repeated keys.  ShardedVideoIndex: every shard re-scores the candidates it holds, in its own
+    numbers, and the lists are merged on the primary (mmt_search_merge_lists).  Out of scope: norm=, pooling=,
+    item_pooling= and groupings are not part of this call; they would be further instantiations of the same kernels."""
+    if not torch.is_tensor(candidates) or candidates.dtype != torch.int64:
+      raise ValueError('rescore: candidates must be an int64 tensor, got %s' % (
+          candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__))
+    if candidates.device != self.device:
+      raise ValueError('rescore: candidates must be on the index device %s, got %s' % (self.device, candidates.device))
+    if candidates.dim() != 2 or not 1 <= candidates.shape[1] <= MAX_C:
+      raise ValueError('rescore: candidates [NQ, 1 <= C <= %d] expected, got %s' % (MAX_C, tuple(candidates.shape)))
+    c = candidates.shape[1]
+    if k is None:
+      k = min(c, MAX_K)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+      raise ValueError('rescore: k must be None or an int in 1..%d, got %r' % (MAX_K, k))
+    if self.num_items == 0:
+      raise ValueError('rescore: the index holds no items')
+    q, qw = self._queries(embds, weights)
+    nq = q.shape[0]
+    if candidates.shape[0] != nq:
+      raise ValueError('rescore: %d queries but candidates %s' % (nq, tuple(candidates.shape)))
+    if nq == 0:
+      return _lists(2, self.device, 0, min(k, c))
+    cand = candidates.contiguous()
+    lo, hi = (int(v) for v in torch.aminmax(cand))
+    if lo < -1 or hi >= self.num_items:
+      raise ValueError('rescore: candidates must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
+    return self._rescore(q, qw, cand, min(k, c))
+
+  def search_refined(self, embds, weights, coarse, k=10, shortlist=MAX_K, subset=None, exclude=None):
+    """The two-stage search as one call: coarse.search(embds, weights, k=shortlist, subset=subset, exclude=exclude) on a
+    cheap index of the same items -- typically a float8_e4m3fn one -- then self.rescore(embds, weights, that list, k) on
+    this one -> (scores, indices) [NQ, min(k, shortlist, the coarse list's width)], scores with this index's bits.
+    coarse: a VideoIndex or ShardedVideoIndex with this index's num_items, num_experts and dim on this index's (primary)
+    device; shortlist an int in 1 .. MAX_K; subset and exclude are `coarse`'s (a subset from ITS `subset`) and are checked
+    by it.  The two indexes are TAKEN to hold the same items under the same numbers: that cannot be checked here.  Host
+    code only."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+      raise ValueError('search_refined: k must be an int in 1..%d, got %r' % (MAX_K, k))
+    if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not 1 <= shortlist <= MAX_K:
+      raise ValueError('search_refined: shortlist must be an int in 1..%d, got %r' % (MAX_K, shortlist))
+    if not isinstance(coarse, _Index):
+      raise ValueError('search_refined: coarse must be a VideoIndex or ShardedVideoIndex, got %s' % type(coarse).__name__)
+    mine, theirs = ((i.num_items, i.num_experts, i.dim) for i in (self, coarse))
+    if mine != theirs:
+      raise ValueError('search_refined: the coarse index holds (num_items, num_experts, dim) = %s, this one %s' % (theirs, mine))
+    if coarse.device != self.device:
+      raise ValueError('search_refined: the coarse index is on %s, this one on %s' % (coarse.device, self.device))
+    _, shortlisted = coarse.search(embds, weights, k=shortlist, subset=subset, exclude=exclude)
+    return self.rescore(embds, weights, shortlisted, k)
+
   def _group_ids(self, group_ids):
     """The checks of `grouping` -> (the ids as int32 [num_items] of their own, the number of distinct ids)."""
     if self.num_items == 0:
@@ -1048,7 +1133,7 @@ class VideoIndex(_Index):
 
   def _entry(self, op, variant=''):
     """The C entry point of a scan over this index's storage: op 'topk', 'topk_groups', 'rank', 'thresholds', 'count',
-    'range_count', 'range_fill' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions), '_norm', '_pooled' or '_itemsets' -> (the
+    'range_count', 'range_fill', 'rescore' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions), '_norm', '_pooled' or '_itemsets' -> (the
     function, its name)."""
     name = 'mmt_search_%s%s%s' % (op, _ENTRY_TAGS[self.dtype], variant)
     return getattr(_lib.lib(), name), name
@@ -1154,6 +1239,21 @@ class VideoIndex(_Index):
           extra = ()
         ws = torch.empty(workspace(*dims, k), device=self.device, dtype=torch.int64)
         check(fn(*operands, *sizes, m, d, k, *extra, ops._p(ws), *[ops._p(o[o0:o1]) for o in outs], ops._stream()), name)
+    return outs
+
+  def _rescore(self, q, qw, cand, k):
+    """`rescore` behind its checks: q (NQ >= 1, M, d) / qw (NQ, M) fp32 and cand int64 [NQ, C] (contiguous, item numbers,
+    one outside 0 .. num_items - 1 = none) on the index device, 1 <= k <= min(C, MAX_K): the width of the outputs.  One
+    call and one workspace of C keys per row for every row batch.  Nothing here waits for the device."""
+    nq, nv, m, d, c = q.shape[0], self.num_items, self.num_experts, self.dim, cand.shape[1]
+    outs = _lists(2, self.device, nq, k)
+    fn, name = self._entry('rescore')
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._row_batches(nq, 8 * c):
+        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
+        ws = torch.empty(_lib.lib().mmt_rescore_workspace_keys(r1 - r0, c), device=self.device, dtype=torch.int64)
+        check(fn(*operands, r1 - r0, nv, m, d, ops._p(cand[r0:r1]), c, k, ops._p(ws), *[ops._p(o[r0:r1]) for o in outs],
+                 ops._stream()), name)
     return outs
 
   def _rank_counts(self, q, qw, tg, scan):
@@ -1585,6 +1685,17 @@ class ShardedVideoIndex(_Index):
     kin = min(kout, max(views[s].candidates(sh.index) for s, sh in live))
     return self._merged(outs, live, kin, 'mmt_search_merge_lists', self._tables(tuple(views), scan.item_pooling),
                         lambda s, sh: sh.index._search(q.to(sh.device), qw.to(sh.device), kout, views[s]))
+
+  def _rescore(self, q, qw, cand, k):
+    """`rescore` behind its checks: q, qw and cand (global numbers) on the primary.  Every shard that holds items re-scores
+    the candidates it holds -- the others are -1, none, in its view -- and returns them best first in its own numbers;
+    an item lives on one shard, so the merge has nothing to de-duplicate, and it keeps a slot without a candidate vacant
+    (an index of -1 is an empty slot of its input lists)."""
+    outs = _lists(2, self.device, q.shape[0], k)
+    live = self._live()
+    local = {s: self._local(cand, s) for s, _ in live}  # translated on the primary, where the item maps are
+    lists = lambda s, sh: sh.index._rescore(q.to(sh.device), qw.to(sh.device), local[s].to(sh.device), k)
+    return self._merged(outs, live, k, 'mmt_search_merge_lists', self._tables(tuple(s for s, _ in live)), lists)
 
   def grouping(self, group_ids):
     """group_ids: int64 [num_items] on the primary device, as VideoIndex.grouping -> ShardedGrouping: the ids cut into one

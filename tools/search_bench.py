@@ -76,7 +76,14 @@ median and spread.  Default output profiles/search_itemset_bench.json.
 from the same data: search(k = 10) with 64 queries (one query tile per gallery chunk: the gallery streams from HBM) and with
 4 096 (the chunk's query tiles share it in L2), and `add` of 8 192 items into a preallocated index.  --runs rounds, every
 variant once per round, interleaved; median and spread; the share of rows whose index lists agree.  Default output
-profiles/search_fp8_bench.json."""
+profiles/search_fp8_bench.json.
+
+--rescore times the second stage of a two-stage search over 262 144 items: 4 096 queries, 128 candidates each from the fp8
+index's search(k = 128), k = 10, on a bf16 and on a float32 index of the same items -- `rescore`, the composition it
+replaces (`target_scores` of the candidates, then `search`'s order as two stable torch sorts) and the index's own full
+search(k = 10) for scale; the coarse search(k = 128) is timed beside them.  --runs rounds, every variant once per round,
+interleaved; median and spread; the share of rows on which `rescore` and the composition agree bit for bit and on which
+`search_refined` returns the fine index's own top 10.  Default output profiles/search_rescore_bench.json."""
 import argparse
 import json
 import math
@@ -560,8 +567,68 @@ def fp8_mode(a, dev):
   return row
 
 
+def composed_rescore(index, q, qw, cand, k):
+  """What `rescore` replaces, from the public calls: `target_scores` of the candidates (MAX_T columns per launch), then
+  `search`'s order in torch -- two stable sorts, by item and then by descending score with -0 as +0 and none last.
+  Candidates that repeat would need a de-duplication on top; a list from `search` has none."""
+  s = index.target_scores(q, qw, cand)
+  s = torch.where(cand < 0, torch.full_like(s, float('-inf')), s) + 0.0
+  by_item = torch.argsort(cand, dim=1, stable=True)
+  perm = torch.gather(by_item, 1, torch.argsort(torch.gather(s, 1, by_item), dim=1, descending=True, stable=True))[:, :k]
+  return torch.gather(s, 1, perm), torch.gather(cand, 1, perm)
+
+
+def rescore_mode(a, dev):
+  """The second stage of a two-stage search over NV = 262 144 items, NQ = 4 096, C = 128 candidates per query from the fp8
+  index's search(k = 128), k = 10, on a bf16 and on a float32 fine index: `rescore`, the composition it replaces
+  (composed_rescore) and the fine index's full search(k = 10) for scale."""
+  nq, nv = SHAPES['S3']
+  chunk, c = 8192, 128
+  gen = torch.Generator(device=dev).manual_seed(0)
+  nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
+  dtypes = {'bfloat16': torch.bfloat16, 'float32': torch.float32}
+  coarse = VideoIndex.empty(nv, M, D, dev, dtype=torch.float8_e4m3fn)
+  fine = {n: VideoIndex.empty(nv, M, D, dev, dtype=t) for n, t in dtypes.items()}
+  for at in range(0, nv, chunk):
+    g = nrm(torch.randn(chunk, M, D, device=dev, generator=gen))
+    gw = torch.softmax(torch.randn(chunk, M, device=dev, generator=gen), -1)
+    for index in [coarse] + list(fine.values()):
+      index.add(g, gw)
+  q = nrm(torch.randn(nq, M, D, device=dev, generator=gen) + 0.3 * g[torch.arange(nq, device=dev) % chunk])
+  qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
+  cand = coarse.search(q, qw, k=c)[1]
+  fns = {'float8_e4m3fn/search_k128': lambda: coarse.search(q, qw, k=c)}
+  for n in dtypes:
+    fns[n + '/rescore'] = lambda n=n: fine[n].rescore(q, qw, cand, k=K)
+    fns[n + '/target_scores_torch_sort'] = lambda n=n: composed_rescore(fine[n], q, qw, cand, K)
+    fns[n + '/search_k10'] = lambda n=n: fine[n].search(q, qw, k=K)
+  ts = {n: [] for n in fns}
+  out = {}
+  for _ in range(a.runs):
+    for n, fn in fns.items():
+      t, _, _, out[n] = timed(fn, a.min_seconds)
+      ts[n].append(t)
+  row = {'NQ': nq, 'NV': nv, 'C': c}
+  for n in fns:
+    row[n] = dict(seconds_median=float(np.median(ts[n])), seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n])
+  same = lambda x, y: float(((x[1] == y[1]) & (x[0].view(torch.int32) == y[0].view(torch.int32))).all(1).float().mean())
+  for n in dtypes:
+    r, b, s = (row[n + '/' + what] for what in ('rescore', 'target_scores_torch_sort', 'search_k10'))
+    refined = fine[n].search_refined(q, qw, coarse, k=K, shortlist=c)
+    row[n + '/summary'] = dict(
+        composition_over_rescore=b['seconds_median'] / r['seconds_median'],
+        search_over_rescore=s['seconds_median'] / r['seconds_median'],
+        spread_seconds=max(r['seconds_spread'], b['seconds_spread']),
+        rows_identical_to_composition=same(out[n + '/rescore'], out[n + '/target_scores_torch_sort']),
+        refined_rows_with_the_fine_top10=float((refined[1] == out[n + '/search_k10'][1]).all(1).float().mean()))
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
+  ap.add_argument('--rescore', action='store_true', help='time rescore (C = 128 candidates from the fp8 index, k = 10) on a '
+                  'bf16 and a float32 index of 262 144 items against target_scores + a torch sort and the full '
+                  'search(k = 10) (no other mode flag)')
   ap.add_argument('--fp8', action='store_true', help='time the fp8-stored index against the bf16-stored one: search(k = 10) '
                   'at NQ = 64 and 4096 over 262 144 items, and add of 8 192 items (no other mode flag)')
   ap.add_argument('--shapes', default='S1,S2,S3')
@@ -632,6 +699,16 @@ def main():
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
+  if a.rescore:
+    res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'rescore', 'runs': a.runs,
+           'min_seconds': a.min_seconds}
+    res.update(rescore_mode(a, dev))
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                'search_rescore_bench.json')
+    with open(out, 'w') as f:
+      json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return
   if a.fp8:
     res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'fp8', 'runs': a.runs,
            'min_seconds': a.min_seconds}
