@@ -838,6 +838,42 @@ int mmt_search_rescore_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const fl
 int mmt_search_rescore_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
                            const float* gscale, int NQ, int NV, int M, int d, const int64_t* candidates, int C, int k,
                            uint64_t* ws, float* scores, int64_t* index, void* stream);
+/* Cursor paging (search.hip): "the k best items that come AFTER a given position in mmt_search_topk's order" -- page 2 of
+ * a result list, and through it sorted lists deeper than k = 128.  The order (score descending, -0 tied with +0, equal
+ * scores by ascending item) is the order of the uint64 keys of the scans, so a position is one key and a row's candidates
+ * are the items whose key is strictly below its bound after[q], on top of subset and exclusions:
+ *   2^64 - 1 = no cursor (no score gives that key: the row is what the parent call returns); 0 = exhausted (no candidate);
+ *   key(a, first) + 1 = every item scoring below a, and at score a the items numbered first or higher.  first is the
+ *   lowest item number still admitted at the cursor's score: a_item + 1 on one index, and on a shard the count of its
+ *   items numbered <= a_item, which may be 0 or the shard's item count -- so the shards' lists merge exactly.
+ * mmt_search_after_keys: scores fp32 [NQ] (non-NaN), first int64 [NQ] -> keys uint64 [NQ], the bounds above; first < 0
+ *   selects a sentinel by the sign of the (then infinite) score: + no cursor, - exhausted.  0 <= first < 2^31 otherwise.
+ *   MMT_ERR_ARG for a null pointer or NQ < 1.
+ * mmt_search_topk_after / _bf16_after / _fp8_after: mmt_search_topk_ex / _bf16_ex / _fp8_ex with the bounds in front of the
+ *   workspace.  mmt_search_topk_norm_after / _bf16_norm_after: mmt_search_topk_norm / _bf16_norm likewise; the keys
+ *   compared are those of score'.  A returned score has the bits the parent call gives the pair; only the slots that have
+ *   a candidate are written (the caller prefills).  Workspace: mmt_topk_workspace_keys.  A block whose 64 rows are all
+ *   exhausted scores nothing.  Gates before any launch: a null `after` is MMT_ERR_ARG, every other gate is the parent's. */
+int mmt_search_after_keys(const float* scores, const int64_t* first, int NQ, uint64_t* keys, void* stream);
+int mmt_search_topk_after(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
+                          int k, const uint32_t* subset, const int64_t* exclude, int E, const uint64_t* after, uint64_t* ws,
+                          float* scores, int64_t* index, void* stream);
+int mmt_search_topk_bf16_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                               const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
+                               const int64_t* exclude, int E, const uint64_t* after, uint64_t* ws, float* scores,
+                               int64_t* index, void* stream);
+int mmt_search_topk_fp8_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
+                              const float* gscale, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
+                              const int64_t* exclude, int E, const uint64_t* after, uint64_t* ws, float* scores,
+                              int64_t* index, void* stream);
+int mmt_search_topk_norm_after(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
+                               int d, int k, const uint32_t* subset, const int64_t* exclude, int E, float beta,
+                               const float* lse, const uint64_t* after, uint64_t* ws, float* scores, int64_t* index,
+                               void* stream);
+int mmt_search_topk_bf16_norm_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                    const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
+                                    const int64_t* exclude, int E, float beta, const float* lse, const uint64_t* after,
+                                    uint64_t* ws, float* scores, int64_t* index, void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

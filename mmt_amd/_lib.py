@@ -327,6 +327,18 @@ SIGNATURES = {
                                         c_vp, c_vp, c_vp]),
     'mmt_search_rescore_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int,
                                        c_vp, c_vp, c_vp, c_vp]),
+    # cursor paging: the bound builder, then the _ex / _norm signatures with the bounds in front of the workspace
+    'mmt_search_after_keys': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp]),
+    'mmt_search_topk_after': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp,
+                                      c_vp, c_vp, c_vp]),
+    'mmt_search_topk_bf16_after': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int,
+                                           c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_topk_fp8_after': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                          c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_topk_norm_after': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_f32,
+                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_topk_bf16_norm_after': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                                c_int, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

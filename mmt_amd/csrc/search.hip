@@ -31,6 +31,9 @@
 //                                      the epilogue (tk_tile reads kFp8 off the block).
 //   <BF16, NmTopkArgs>               : the masked kernels with tk_tile_norm between the score epilogue and the selection:
 //                                      ranks by and returns the querybank-normalised score' (search_norm.hip).
+//   <., Tk*AfterArgs>, <., NmTopkAfterArgs> : the masked and normalised kernels with a cursor per query row (the paged search,
+//                                      mmt_search_topk_after): the selection also declines every key at or above the row's
+//                                      bound (tk_tile_select<true, true>), one more compare on the same score tile.
 // The argument blocks stay separate types with their layouts as they are: a field appended to TkArgs moves the hidden
 // kernel arguments behind it and changes the unmasked code (profiles/search_subset_kernel_identity.txt).
 //
@@ -105,13 +108,38 @@ struct NmTopkArgs : NmArgs {
   int k, E;
 };
 
+// The paged search (mmt_search_topk_after and its kin): the masked blocks with one bound per query row behind them, in
+// types of their own, so the blocks above keep their layout and their kernels their code.  after[q] is a position in the
+// search's order as a key: only keys strictly below it are candidates (tk_tile_select<true, true>).
+struct TkAfterArgs : TkMaskedArgs {
+  const uint64_t* after;    // [NQ]: 2^64 - 1 = no cursor, 0 = exhausted, tk_key(a, first) + 1 = a position
+  static constexpr bool kAfter = true;
+};
+
+struct TkBf16AfterArgs : TkBf16MaskedArgs {  // as TkAfterArgs
+  const uint64_t* after;
+  static constexpr bool kAfter = true;
+};
+
+struct TkFp8AfterArgs : TkFp8MaskedArgs {  // as TkAfterArgs
+  const uint64_t* after;
+  static constexpr bool kAfter = true;
+};
+
+struct NmTopkAfterArgs : NmTopkArgs {  // as TkAfterArgs
+  const uint64_t* after;
+  static constexpr bool kAfter = true;
+};
+
 // One block of the fused scan: 64 queries x one gallery chunk -> the chunk's sorted k best per query in the workspace.
 // Args = TkArgs, TkBf16Args (kMask = TK_MASK_NONE), their masked forms or NmTopkArgs (TK_MASK_NULLABLE: subset bitmap,
-// may be null, and per-query exclusions, E = 0 allowed).
+// may be null, and per-query exclusions, E = 0 allowed), or one of those with a cursor per row (kAfter).
 template <bool BF16, class Args>
 __global__ __launch_bounds__(256) void topk_scan_kernel(Args a) {
   constexpr TkMask MASK = Args::kMask;
   constexpr bool NORM = Args::kNorm;
+  constexpr bool AFTER = TkAfter<Args>::value;
+  static_assert(!AFTER || MASK != TK_MASK_NONE, "the blocks with a cursor extend the masked ones");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int kUnion = BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -133,12 +161,24 @@ __global__ __launch_bounds__(256) void topk_scan_kernel(Args a) {
   int* sEx = (int*)(sC + TK_Q * cap);                         // masked: [TK_Q][E] exclusions
   if constexpr (MASK != TK_MASK_NONE)
     for (int i = tid; i < TK_Q * a.E; i += 256) sEx[i] = q0 + i / a.E < a.NQ ? (int)a.exclude[(int64_t)q0 * a.E + i] : -1;
-  for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
+  int g_stop = g_end;
+  uint64_t* sB = nullptr;                                     // paged: [TK_Q] bounds, behind the exclusions
+  if constexpr (AFTER) {
+    sB = (uint64_t*)(sEx + TK_Q * a.E);
+    const uint64_t mine = q0 + lane < a.NQ ? a.after[q0 + lane] : 0ull;  // every wave reads the block's 64 bounds
+    if (wave == 0) sB[lane] = mine;                                       // read behind the barriers of tk_tile
+    // block-uniform (the four waves hold the same 64 values), before any barrier: every row of the block is exhausted --
+    // no tile is scored, and the flush below writes the empty lists
+    if (!__ballot(mine != 0ull)) g_stop = g_begin;
+  }
+  for (int g0 = g_begin; g0 < g_stop; g0 += TK_G) {
     uint64_t m0 = ~0ull, m1 = ~0ull;
     if constexpr (MASK != TK_MASK_NONE)
       if (a.subset && !tk_tile_mask(a.subset, g0, m0, m1)) continue;  // block-uniform: nothing of this tile is allowed
     tk_tile<BF16, NORM>(a, smem, sS, sQw, q0, [=](int r) { return g0 + r < g_end ? g0 + r : -1; }, tid, wq, wg, l31, h);
-    if constexpr (MASK != TK_MASK_NONE)
+    if constexpr (AFTER)
+      tk_tile_select<true, true>(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane, m0, m1, sEx, a.E, sB);
+    else if constexpr (MASK != TK_MASK_NONE)
       tk_tile_select<true>(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane, m0, m1, sEx, a.E);
     else
       tk_tile_select(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane);
@@ -242,6 +282,8 @@ bool tk_args_ok(int NQ, int NV, int k) { return NQ > 0 && NV > 0 && k >= 1 && k 
 size_t tk_state_lds(int k) { return TK_QW_BYTES + TK_Q * (4 + 8) + (size_t)TK_Q * (k + 64) * 8; }
 // ... and behind those, the masked kernels' exclusions [TK_Q][E]
 size_t tk_exclude_lds(int E) { return (size_t)TK_Q * E * 4; }
+// ... and behind those, the paged kernels' bounds [TK_Q]
+constexpr size_t kAfterLds = (size_t)TK_Q * 8;
 size_t tk_select_lds(int k) { return (size_t)4 * (k + 64) * 8; }
 
 // The k = 128 footprint of the fused kernels is over the 64 KiB default.
@@ -256,17 +298,23 @@ void tk_topk_lds_limits() {
                        {(const void*)topk_scan_kernel<true, TkFp8Args>, bf16},
                        {(const void*)topk_scan_kernel<true, TkFp8MaskedArgs>, bf16 + ex},
                        {(const void*)topk_scan_kernel<false, NmTopkArgs>, f32 + ex},
-                       {(const void*)topk_scan_kernel<true, NmTopkArgs>, bf16 + ex}});
+                       {(const void*)topk_scan_kernel<true, NmTopkArgs>, bf16 + ex},
+                       {(const void*)topk_scan_kernel<false, TkAfterArgs>, f32 + ex + kAfterLds},
+                       {(const void*)topk_scan_kernel<true, TkBf16AfterArgs>, bf16 + ex + kAfterLds},
+                       {(const void*)topk_scan_kernel<true, TkFp8AfterArgs>, bf16 + ex + kAfterLds},
+                       {(const void*)topk_scan_kernel<false, NmTopkAfterArgs>, f32 + ex + kAfterLds},
+                       {(const void*)topk_scan_kernel<true, NmTopkAfterArgs>, bf16 + ex + kAfterLds}});
 }
 
 // The fused search behind every top-k entry point (Args = TkMaskedArgs, TkBf16MaskedArgs or NmTopkArgs, the last with lse
-// and beta set by the caller): gate, fill, the chunk scan and the merge.  `rest`: the entry's other arguments are in
-// order.  q_lo is null where an entry has none.
+// and beta set by the caller, or one of those with a cursor: `after`, the bounds [NQ], must then be given): gate, fill, the
+// chunk scan and the merge.  `rest`: the entry's other arguments are in order.  q_lo is null where an entry has none.
 template <bool BF16, class Args>
 int tk_search(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
               int d, int k, const uint32_t* subset, const int64_t* exclude, int E, bool rest, uint64_t* ws, float* scores,
-              int64_t* index, void* stream) {
-  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !rest || !ws || !index || !tk_args_ok(NQ, NV, k) ||
+              int64_t* index, void* stream, const uint64_t* after = nullptr) {
+  constexpr bool AFTER = TkAfter<Args>::value;
+  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !rest || (AFTER && !after) || !ws || !index || !tk_args_ok(NQ, NV, k) ||
       !tk_shape_ok(NQ, NV, M, d, BF16, TkFp8<Args>::value))
     return MMT_ERR_ARG;
   if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g) & 15) return MMT_ERR_ALIGN;
@@ -276,25 +324,47 @@ int tk_search(Args a, const void* q, const void* q_lo, const float* qw, const vo
   if constexpr (BF16) a.q_lo = static_cast<decltype(a.q_lo)>(q_lo);
   a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.k = k;
   a.subset = subset; a.exclude = exclude; a.E = E;
+  if constexpr (AFTER) a.after = after;
   tk_geometry(a);
   tk_topk_lds_limits();
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(a.n_qt * a.n_chunks);
   const size_t lds = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + tk_state_lds(k);
   using Plain = std::conditional_t<TkFp8<Args>::value, TkFp8Args, std::conditional_t<BF16, TkBf16Args, TkArgs>>;
-  if (Args::kNorm || subset || E)
-    hipLaunchKernelGGL((topk_scan_kernel<BF16, Args>), grid, dim3(256), lds + tk_exclude_lds(E), s, a);
-  else if constexpr (!Args::kNorm)  // constexpr only so that the slice to Plain is not instantiated for NmTopkArgs
+  if (AFTER || Args::kNorm || subset || E)
+    hipLaunchKernelGGL((topk_scan_kernel<BF16, Args>), grid, dim3(256), lds + tk_exclude_lds(E) + (AFTER ? kAfterLds : 0), s,
+                       a);
+  else if constexpr (!Args::kNorm && !AFTER)  // constexpr only so that the slice to Plain is not instantiated for NmTopkArgs
     hipLaunchKernelGGL((topk_scan_kernel<BF16, Plain>), grid, dim3(256), lds, s, (Plain)a);
   return tk_merge_launch(ws, NQ, a.n_chunks, k, k < NV ? k : NV, scores, index, s);
 }
 
-NmTopkArgs nm_topk_args(float beta, const float* lse) {
-  NmTopkArgs a = {};
+template <class Args = NmTopkArgs>
+Args nm_topk_args(float beta, const float* lse) {
+  Args a = {};
   a.beta = beta; a.lse = lse;
   return a;
 }
 }  // namespace
+
+// The bounds of the paged search from positions: keys[q] = tk_key(scores[q], first[q]) + 1, where first[q] >= 0 is the
+// lowest item number still admitted at that score (the low word of a key is ~item, so the + 1 carries into the score word
+// exactly when first is 0: "every item at this score"); first[q] < 0 selects a sentinel by the sign of the score, which is
+// then infinite: + = no cursor (2^64 - 1, above every key), - = exhausted (0).
+__global__ __launch_bounds__(256) void after_keys_kernel(const float* __restrict__ scores, const int64_t* __restrict__ first,
+                                                         int NQ, uint64_t* __restrict__ keys) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= NQ) return;
+  const float s = scores[q];
+  const int64_t f = first[q];
+  keys[q] = f < 0 ? (s > 0.f ? ~0ull : 0ull) : tk_key(s, (int)f) + 1ull;
+}
+
+extern "C" int mmt_search_after_keys(const float* scores, const int64_t* first, int NQ, uint64_t* keys, void* stream) {
+  if (!scores || !first || !keys || NQ < 1) return MMT_ERR_ARG;
+  hipLaunchKernelGGL(after_keys_kernel, dim3((NQ + 255) / 256), dim3(256), 0, (hipStream_t)stream, scores, first, NQ, keys);
+  return (int)hipGetLastError();
+}
 
 extern "C" int64_t mmt_topk_workspace_keys(int NQ, int NV, int k) {
   if (!tk_args_ok(NQ, NV, k)) return MMT_ERR_ARG;
@@ -357,6 +427,49 @@ extern "C" int mmt_search_topk_bf16_norm(const uint16_t* q_hi, const uint16_t* q
                                          float* scores, int64_t* index, void* stream) {
   return tk_search<true>(nm_topk_args(beta, lse), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E,
                          lse && tk_beta_ok(beta), ws, scores, index, stream);
+}
+
+// The paged forms: the _ex and _norm entries with the bounds of mmt_search_after_keys in front of the workspace.
+extern "C" int mmt_search_topk_after(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
+                                     int M, int d, int k, const uint32_t* subset, const int64_t* exclude, int E,
+                                     const uint64_t* after, uint64_t* ws, float* scores, int64_t* index, void* stream) {
+  return tk_search<false>(TkAfterArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, true, ws, scores,
+                          index, stream, after);
+}
+
+extern "C" int mmt_search_topk_bf16_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
+                                          const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
+                                          const int64_t* exclude, int E, const uint64_t* after, uint64_t* ws, float* scores,
+                                          int64_t* index, void* stream) {
+  return tk_search<true>(TkBf16AfterArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, true, ws, scores,
+                         index, stream, after);
+}
+
+extern "C" int mmt_search_topk_fp8_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
+                                         const float* gw, const float* gscale, int NQ, int NV, int M, int d, int k,
+                                         const uint32_t* subset, const int64_t* exclude, int E, const uint64_t* after,
+                                         uint64_t* ws, float* scores, int64_t* index, void* stream) {
+  TkFp8AfterArgs a = {};
+  a.gscale = gscale;
+  return tk_search<true>(a, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, gscale != nullptr, ws, scores, index,
+                         stream, after);
+}
+
+extern "C" int mmt_search_topk_norm_after(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
+                                          int M, int d, int k, const uint32_t* subset, const int64_t* exclude, int E,
+                                          float beta, const float* lse, const uint64_t* after, uint64_t* ws, float* scores,
+                                          int64_t* index, void* stream) {
+  return tk_search<false>(nm_topk_args<NmTopkAfterArgs>(beta, lse), qf, nullptr, qw, gf, gw, NQ, NV, M, d, k, subset, exclude,
+                          E, lse && tk_beta_ok(beta), ws, scores, index, stream, after);
+}
+
+extern "C" int mmt_search_topk_bf16_norm_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw,
+                                               const uint16_t* gf, const float* gw, int NQ, int NV, int M, int d, int k,
+                                               const uint32_t* subset, const int64_t* exclude, int E, float beta,
+                                               const float* lse, const uint64_t* after, uint64_t* ws, float* scores,
+                                               int64_t* index, void* stream) {
+  return tk_search<true>(nm_topk_args<NmTopkAfterArgs>(beta, lse), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E,
+                         lse && tk_beta_ok(beta), ws, scores, index, stream, after);
 }
 
 extern "C" int mmt_rows_topk(const float* sims, int64_t ld, const int32_t* rows, int NR, int NV, int k, uint64_t* ws,

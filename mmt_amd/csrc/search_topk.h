@@ -19,6 +19,13 @@ __device__ __forceinline__ float tk_score(uint64_t key) {
 }
 __device__ __forceinline__ int tk_index(uint64_t key) { return (int)~(unsigned)key; }
 
+// Whether an argument block carries a cursor per query row (`after`: uint64 bounds [NQ], tk_tile_select<., true>): a block
+// says so itself with `static constexpr bool kAfter = true`, as TkFp8; a block that says nothing does not.
+template <class Args, class = void>
+struct TkAfter { static constexpr bool value = false; };
+template <class Args>
+struct TkAfter<Args, std::void_t<decltype(Args::kAfter)>> { static constexpr bool value = Args::kAfter; };
+
 // One wave, one row: rank-sort the n (<= k + 64 <= 192) candidates c[0..n) and keep the best min(n, k) in c[0..) in
 // descending order.
 __device__ __forceinline__ void tk_compact(uint64_t* c, int n, int k, int lane) {
@@ -44,13 +51,17 @@ __device__ __forceinline__ void tk_compact(uint64_t* c, int n, int k, int lane) 
 
 // One wave, one row: offers one key per lane (0 = none).  Keys at or below the threshold (the k-th best so far) cannot
 // enter the top k; the others are appended.  Capacity k + 64: the list is compacted first whenever it holds more than k.
-__device__ __forceinline__ void tk_push(uint64_t* c, int& n, uint64_t& thr, int k, uint64_t key, int lane) {
+// AFTER: keys at or above `bound` (the row's cursor, tk_tile_select) are declined as well.
+template <bool AFTER = false>
+__device__ __forceinline__ void tk_push(uint64_t* c, int& n, uint64_t& thr, int k, uint64_t key, int lane,
+                                        uint64_t bound = ~0ull) {
   if (n > k) {
     tk_compact(c, n, k, lane);
     n = k;
     thr = c[k - 1];
   }
-  const bool take = key > thr;
+  bool take = key > thr;
+  if constexpr (AFTER) take = take && key < bound;
   const uint64_t mask = __ballot(take);
   if (take) c[n + __popcll(mask & ((1ull << lane) - 1ull))] = key;
   n += __popcll(mask);
@@ -66,17 +77,22 @@ __device__ __forceinline__ void tk_flush(uint64_t* c, int n, int k, int lane, ui
 // Selection over the score tile: wave w owns rows 16w .. 16w + 15; columns in increasing index order.  MASKED: only the
 // columns whose bit is set in m0 (columns 0 .. 63) / m1 (64 .. 127) are candidates, less the row's exclusions sEx[row][E]
 // (item numbers, -1 = none; lane e holds exclusion e, and the few that fall into this tile clear their bit).  The score
-// tile is the unmasked kernel's, so a returned score has the bits the unmasked search gives that item.
-template <bool MASKED = false>
+// tile is the unmasked kernel's, so a returned score has the bits the unmasked search gives that item.  AFTER (the paged
+// search: the argument blocks with kAfter): sB [TK_Q] holds one bound per row, a position in the search's order, and only
+// keys strictly below it are candidates: 2^64 - 1 = no cursor (no score gives that key), 0 = the row is exhausted, and
+// tk_key(a, first) + 1 = everything that scores below a, and at score a the items from number `first` on.
+template <bool MASKED = false, bool AFTER = false>
 __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, int* sN, uint64_t* sT, int k, int rows_live,
                                                int g0, int g_end, int wave, int lane, uint64_t m0 = 0, uint64_t m1 = 0,
-                                               const int* sEx = nullptr, int E = 0) {
+                                               const int* sEx = nullptr, int E = 0, const uint64_t* sB = nullptr) {
   const int cap = k + 64;
   for (int rr = 0; rr < TK_Q / 4; ++rr) {
     const int row = wave * (TK_Q / 4) + rr;
     if (row >= rows_live) break;
     int n = sN[row];
     uint64_t thr = sT[row];
+    uint64_t bound = ~0ull;
+    if constexpr (AFTER) bound = sB[row];
     uint64_t a0 = m0, a1 = m1;
     if constexpr (MASKED) {
       if (E) {
@@ -95,7 +111,7 @@ __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, in
       const int col = half * 64 + lane, g = g0 + col;
       bool live = g < g_end;
       if constexpr (MASKED) live = live && (((half ? a1 : a0) >> lane) & 1ull);
-      tk_push(sC + row * cap, n, thr, k, live ? tk_key(sS[row * TK_SLD + col], g) : 0ull, lane);
+      tk_push<AFTER>(sC + row * cap, n, thr, k, live ? tk_key(sS[row * TK_SLD + col], g) : 0ull, lane, bound);
     }
     if (lane == 0) { sN[row] = n; sT[row] = thr; }
   }

@@ -203,6 +203,24 @@ their order, the row batching or the launch geometry.  ShardedVideoIndex.rescore
 the candidates it holds and the lists are merged on the primary.  `search_refined` is host code: coarse.search(k=shortlist,
 subset=, exclude=) on an index TAKEN to hold the same items under the same numbers (same num_items, num_experts, dim and
 device is all that can be checked), then `rescore` on this one.  Out of scope: norm=, pooling=, item_pooling= and groupings.
+
+    scores, indices = index.search(q, qw, k=10, after=(page1_scores[:, -1], page1_indices[:, -1]), subset=..., exclude=..., norm=...)
+    scores, indices = index.search_deep(q, qw, depth, page=DEEP_PAGE, subset=None, exclude=None, norm=None, dynamic=None)
+
+The eighth question: the k best items that come AFTER a given position in `search`'s order -- "the next ten results", and
+through it a sorted list deeper than MAX_K.  `search`'s order (score descending, -0 tied with +0, equal scores by ascending
+item) totally orders a query's candidates, so a position is a (score, item) pair -- one key of the scans -- and "everything
+strictly after it" is one more compare at selection time, on the score tile the scan computes anyway
+(mmt_search_topk_after; exclude= holds 32 items and range_search needs a threshold nobody knows in advance).  A cursor row
+(a_scores[q], a_items[q]) with a_items[q] >= 0 admits the items g with score(q, g) < a_scores[q], or an equal score (-0 as
++0) and g > a_items[q]; it need not be the position of a stored or allowed item.  (+inf, -1) is no cursor, (-inf, -1) is
+exhausted -- the vacant slot of an earlier page -- so after=(scores[:, -1], indices[:, -1]) of the page before is always
+valid.  Exact and bit-reproducible like the other seven: a score has the bits plain `search` gives the pair, the rows are
+slices of the one complete ordered list, on all three storage dtypes and both index classes (a shard gets the cursor
+restated in its own item numbers).  Combines with subset=, exclude=, norm= and dynamic= (the dynamic rule's plain top-1 is
+taken without the cursor, so every page of a query makes the same choice); not with pooling= or item_pooling=, and
+`search_groups` has no cursor.  `search_deep` is host code: ceil(w / page) pages of `search`, w = min(depth, candidates),
+each continuing from the last column of the one before, concatenated to [NQ, w].
 """
 import math
 
@@ -212,6 +230,7 @@ from . import _lib, ops
 from ._lib import check
 
 MAX_K = 128
+DEEP_PAGE = 64  # default page of `search_deep`: the width at which a scan costs least per column
 MAX_T = 32  # targets per query and launch of the rank kernels; wider target lists are sliced
 MAX_E = 32  # exclusions per query of a masked search
 MAX_C = 1024  # candidates per query of `rescore`: one query's keys are sorted in LDS
@@ -238,19 +257,41 @@ def _fold(x, w):
   return out
 
 
-def _exclusions(exclude, nq, nv):
-  """exclude (type and width already checked) -> None or int64 [NQ, E], its values checked against -1 .. nv - 1 (one small
-  reduction and a host sync)."""
-  if exclude is None:
-    return None
-  if exclude.shape[0] != nq:
-    raise ValueError('search: %d queries but exclude %s' % (nq, tuple(exclude.shape)))
-  ex = exclude.reshape(nq, -1).contiguous()
-  if nq:
-    lo, hi = (int(v) for v in torch.aminmax(ex))
-    if lo < -1 or hi >= nv:
-      raise ValueError('search: exclude must lie in -1 .. %d, got %d .. %d' % (nv - 1, lo, hi))
-  return ex
+def _limits(exclude, after, nq, nv):
+  """The checks of `search` that look at values, together: exclude and after (types, devices and ranks already checked) ->
+  (None or int64 [NQ, E]; None or the cursor as (scores float32 [NQ], first int64 [NQ])).  The exclusions are held against
+  -1 .. nv - 1; a cursor row is a position (item 0 .. nv - 1, any score but NaN), (+inf, -1) = no cursor or (-inf, -1) =
+  exhausted.  `first` is the lowest item number still admitted at the cursor's score, item + 1, and -1 where the row is a
+  sentinel (tk_tile_select of search_topk.h; mmt_search_after_keys).  One small reduction each and ONE host sync for both."""
+  ex, cursor, facts = None, None, []
+  if exclude is not None:
+    if exclude.shape[0] != nq:
+      raise ValueError('search: %d queries but exclude %s' % (nq, tuple(exclude.shape)))
+    ex = exclude.reshape(nq, -1).contiguous()
+    if nq:
+      facts += list(torch.aminmax(ex))
+  if after is not None:
+    a_scores, a_items = after
+    if a_scores.shape[0] != nq:
+      raise ValueError('search: %d queries but after holds %d rows' % (nq, a_scores.shape[0]))
+    a_scores, a_items = a_scores.contiguous(), a_items.contiguous()
+    if nq:
+      facts += [torch.isnan(a_scores).any().long(), ((a_items == -1) & ~torch.isinf(a_scores)).any().long()]
+      facts += list(torch.aminmax(a_items))
+    cursor = (a_scores, torch.where(a_items >= 0, a_items + 1, a_items))
+  if facts:
+    facts = [int(v) for v in torch.stack(facts).tolist()]
+    if ex is not None and (facts[0] < -1 or facts[1] >= nv):
+      raise ValueError('search: exclude must lie in -1 .. %d, got %d .. %d' % (nv - 1, facts[0], facts[1]))
+    if cursor is not None:
+      nan, loose, lo, hi = facts[-4:]
+      if nan:
+        raise ValueError('search: the scores of after must not be NaN')
+      if lo < -1 or hi >= nv:
+        raise ValueError('search: the items of after must lie in -1 .. %d, got %d .. %d' % (nv - 1, lo, hi))
+      if loose:
+        raise ValueError('search: an item of -1 in after goes with a score of +inf (no cursor) or -inf (exhausted)')
+  return ex, cursor
 
 
 def _width(embds):
@@ -534,18 +575,29 @@ def _pick(use, normed, plain):
 class _Scan:
   """What a scan is asked to do beside its queries: subset (an IndexSubset, on a sharded index a ShardedSubset), ex (int64
   [NQ, E] exclusions, checked), norm (a HubNorm / ShardedHubNorm: every query normalised), pooling (a QueryPooling) and
-  item_pooling (an ItemPooling / ShardedItemPooling), each None unless given and already checked against the index.  A
-  public call builds it once and every internal call takes it whole; the sizes that depend on which options are there
-  are answered here."""
+  item_pooling (an ItemPooling / ShardedItemPooling), each None unless given and already checked against the index, and
+  after (the cursor of a paged `search`, checked: scores float32 [NQ] and first int64 [NQ], the lowest item number still
+  admitted at that score in the index's own numbers, -1 where the score is a sentinel: _limits).  A public call builds it
+  once and every internal call takes it whole; the sizes that depend on which options are there are answered here."""
 
-  def __init__(self, subset=None, ex=None, norm=None, pooling=None, item_pooling=None):
+  def __init__(self, subset=None, ex=None, norm=None, pooling=None, item_pooling=None, after=None):
     self.subset, self.ex, self.norm, self.pooling, self.item_pooling = subset, ex, norm, pooling, item_pooling
+    self.after = after
     # which family of entry points scans it: '' stands for the plain, _ex and _norm forms
     self.kind = '_itemsets' if item_pooling is not None else '_pooled' if pooling is not None else ''
 
   def plain(self):
-    """The same candidates without the norm: what the dynamic rule falls back to."""
+    """The same candidates without the norm, the cursor kept: the result the dynamic rule falls back to."""
+    return _Scan(self.subset, self.ex, after=self.after)
+
+  def uncursored(self):
+    """The candidates of the whole list, without norm or cursor: what the dynamic rule DECIDES on -- a query's plain top-1,
+    which is then the same on every page of that query."""
     return _Scan(self.subset, self.ex)
+
+  def at(self, after):
+    """The same scan from another cursor (None = from the top): the pages of `search_deep`."""
+    return _Scan(self.subset, self.ex, self.norm, self.pooling, self.item_pooling, after)
 
   def rows(self, q):
     """The rows of the outputs: one per query, or with a pooling one per query set."""
@@ -572,10 +624,14 @@ class _Scan:
 
   def shard(self, s, index):
     """Shard s's view of it on the ShardedVideoIndex `index`: its part of the subset, the norm and the item pooling (None
-    where the shard has none), the pooling as it is, the exclusions in the shard's item numbers on its device."""
+    where the shard has none), the pooling as it is, the exclusions in the shard's item numbers on its device, and the
+    cursor with `first` in the shard's numbers: the count of its items numbered at or below the cursor's item
+    (ShardedVideoIndex._first), which restates the global tie rule locally."""
     part = lambda whole: None if whole is None else whole.parts[s]
-    ex = None if self.ex is None else index._local(self.ex, s).to(index.shards[s].device)
-    return _Scan(part(self.subset), ex, part(self.norm), self.pooling, part(self.item_pooling))
+    device = index.shards[s].device
+    ex = None if self.ex is None else index._local(self.ex, s).to(device)
+    after = None if self.after is None else (self.after[0].to(device), index._first(self.after[1], s).to(device))
+    return _Scan(part(self.subset), ex, part(self.norm), self.pooling, part(self.item_pooling), after)
 
 
 def _column_groups(src, outs, r0, r1):
@@ -763,17 +819,20 @@ class _Index:
 
   def _use_norm(self, q, qw, scan):
     """QB-Norm's dynamic rule: bool [NQ], True where the query's plain top-1 among its candidates (after subset and
-    exclusions) is one of the norm's hubs.  A query without a candidate keeps its plain result."""
-    top1 = self._search(q, qw, 1, scan.plain())[1][:, 0]
+    exclusions) is one of the norm's hubs.  A query without a candidate keeps its plain result.  A cursor plays no part:
+    the decision belongs to the query, not to the page."""
+    top1 = self._search(q, qw, 1, scan.uncursored())[1][:, 0]
     return (top1 >= 0) & scan.norm.hubs[top1.clamp(min=0)]
 
-  def _dynamic(self, dynamic, q, qw, scan, run):
+  def _dynamic(self, dynamic, q, qw, scan, run, use=None):
     """The result of a public call: run(scan), a tuple of tensors -- with a norm every query normalised -- as it is, or
-    under the dynamic rule (which takes a norm) mixed per query with what run gives without the norm."""
+    under the dynamic rule (which takes a norm) mixed per query with what run gives without the norm.  use: `_use_norm`
+    of the scan where the caller has it already (the pages of `search_deep`)."""
     out = run(scan)
     if not dynamic or q.shape[0] == 0:
       return out
-    use = self._use_norm(q, qw, scan)
+    if use is None:
+      use = self._use_norm(q, qw, scan)
     return tuple(_pick(use, a, b) for a, b in zip(out, run(scan.plain())))
 
   def hub_norm(self, bank_embds, bank_weights, beta, dynamic=False):
@@ -802,8 +861,25 @@ class _Index:
       hubs = torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
     return self._hub_norm(b, bw, beta, hubs)
 
+  def _after(self, after, pooling=None, item_pooling=None):
+    """Type, device and rank of `after`, and what it does not combine with: all that can be said before the queries are
+    known."""
+    if pooling is not None or item_pooling is not None:
+      raise ValueError('search: after= does not combine with pooling= or item_pooling=')
+    if (not isinstance(after, (tuple, list)) or len(after) != 2 or not all(torch.is_tensor(t) for t in after) or
+        after[0].dtype != torch.float32 or after[1].dtype != torch.int64):
+      raise ValueError('search: after must be None or a pair (scores float32 [NQ], items int64 [NQ]), got %s' % (
+          '(%s)' % ', '.join(str(t.dtype) if torch.is_tensor(t) else type(t).__name__ for t in after)
+          if isinstance(after, (tuple, list)) else type(after).__name__))
+    for t in after:
+      if t.device != self.device:
+        raise ValueError('search: after must be on the index device %s, got %s' % (self.device, t.device))
+    if after[0].dim() != 1 or after[0].shape != after[1].shape:
+      raise ValueError('search: after (scores [NQ], items [NQ]) expected, got %s and %s' % (
+          tuple(after[0].shape), tuple(after[1].shape)))
+
   def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None, pooling=None,
-             item_pooling=None):
+             item_pooling=None, after=None):
     """Queries (NQ, M, d) / (NQ, M), or the text layout (B, M, C, d) / (B, C, M) -> (scores [NQ, k'] float32,
     indices [NQ, k'] int64) on the device, k' = min(k, NV), best first.  subset (from this index's `subset`): only its
     items are candidates and k' = min(k, subset.count).  exclude: int64 [NQ] or [NQ, E <= 32] on the index device, values
@@ -820,14 +896,66 @@ class _Index:
     from item_pooling.subset; does not combine with pooling=, exclude= or norm=.
     ShardedVideoIndex: every shard searches its own items for its best min(k', its candidates), with its part of the
     subset and the norm; the lists are copied to the primary and merged there in one launch.  With a pooling every shard
-    sees all query rows, so a pooled score has the same bits wherever the item is stored."""
+    sees all query rows, so a pooled score has the same bits wherever the item is stored.
+    after: None, or a cursor (a_scores float32 [NQ], a_items int64 [NQ]) on the index device (the primary of a sharded
+    index): the k' best items that come AFTER a position in this call's own order -- page 2 of a list is
+    search(..., after=(scores[:, -1], indices[:, -1])) of page 1, with every other argument the same.  Row q with
+    a_items[q] >= 0 is a position: the candidates are the items g with score(q, g) < a_scores[q], or score(q, g) ==
+    a_scores[q] and g > a_items[q] (-0 compares as +0, as in the order itself; with norm= the scores compared are score',
+    the values the call returns).  The position need not be that of a stored or allowed item: a_scores[q] is any float
+    but NaN, a_items[q] any number in 0 .. num_items - 1.  (+inf, -1) is "no cursor": the row is what the call returns
+    without after.  (-inf, -1) is "exhausted": the row has no candidates -- it is the vacant slot of an earlier page, so
+    the last column of a page is always a valid cursor and a row that came back short gets nothing more.  Anything else
+    (-1 with a finite score, a NaN, an item out of range) is a ValueError naming `after`, raised before anything is
+    scored: one small reduction and one host sync, shared with the check of `exclude` where both are given; type, device
+    and shape are checked before the queries are looked at.  The shape stays [NQ, k'] with k' as without a cursor, and a
+    row with fewer than k' items left holds (-inf, -1) in the remaining slots.  A score has the bits the call without
+    `after` gives the pair, and for every k and cursor the row is the slice that starts right behind the position in the
+    complete ordered list of the query's candidates -- whatever the row batching, the launch geometry or the shards (the
+    cursor is one more compare at selection time, on the keys the scan orders by: mmt_search_topk_after).  Combines
+    with subset=, exclude=, norm= and dynamic=; under the dynamic rule a query's plain top-1 is taken WITHOUT the cursor,
+    so the choice is the same on every page.  after= with pooling= or item_pooling= is a ValueError; `search_groups` has
+    no cursor (a group's representative may lie before a position while other members lie after it).  after=None takes
+    exactly the calls above."""
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
       raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
     if self.num_items == 0:
       raise ValueError('search: the index holds no items')
+    if after is not None:
+      self._after(after, pooling, item_pooling)
     q, qw, dynamic = self._scan_args('search', embds, weights, norm, dynamic, subset, exclude, pooling, item_pooling)
-    scan = _Scan(subset, _exclusions(exclude, q.shape[0], self.num_items), norm, pooling, item_pooling)
+    ex, cursor = _limits(exclude, after, q.shape[0], self.num_items)
+    scan = _Scan(subset, ex, norm, pooling, item_pooling, cursor)
     return self._dynamic(dynamic, q, qw, scan, lambda scan: self._search(q, qw, k, scan))
+
+  def search_deep(self, embds, weights, depth, page=DEEP_PAGE, subset=None, exclude=None, norm=None, dynamic=None):
+    """The sorted list deeper than MAX_K: queries, subset, exclude, norm and dynamic as for `search`; depth an int >= 1, page
+    an int in 1 .. MAX_K -> (scores [NQ, w] float32, indices [NQ, w] int64), w = min(depth, the candidates after subset):
+    column for column the complete ordered candidate list of each query, cut at w, a row with fewer candidates left
+    (exclusions) ending in (-inf, -1).  Host code: the concatenation of ceil(w / page) pages, each a search(k = min(page,
+    what is left), after = the last column of the page before); the arguments are checked once and under the dynamic rule
+    the per-query choice is taken once.  The number of pages is known on the host and nothing waits for the device
+    between them, so there is no early stop.  A page costs one scan of the gallery and a wide page costs more than a
+    narrow one, so `page` trades the number of scans against the cost of each: the default, DEEP_PAGE = 64, is the width
+    at which a scan cost least per column where it was measured (depth 256 took 404 ms at page 64, 568 ms at
+    32 and 625 ms at 128 on a bf16 index of 262 144 items with 4 096 queries)."""
+    if isinstance(depth, bool) or not isinstance(depth, int) or depth < 1:
+      raise ValueError('search_deep: depth must be an int >= 1, got %r' % (depth,))
+    if isinstance(page, bool) or not isinstance(page, int) or not 1 <= page <= MAX_K:
+      raise ValueError('search_deep: page must be an int in 1..%d, got %r' % (MAX_K, page))
+    if self.num_items == 0:
+      raise ValueError('search: the index holds no items')
+    q, qw, dynamic = self._scan_args('search', embds, weights, norm, dynamic, subset, exclude)
+    scan = _Scan(subset, _limits(exclude, None, q.shape[0], self.num_items)[0], norm)
+    width = min(depth, scan.candidates(self))
+    use = self._use_norm(q, qw, scan) if dynamic and q.shape[0] else None
+    pages, cursor = [], None
+    for c0 in range(0, width, page):
+      k = min(page, width - c0)
+      pages.append(self._dynamic(dynamic, q, qw, scan.at(cursor), lambda scan: self._search(q, qw, k, scan), use))
+      scores, items = (t[:, -1] for t in pages[-1])
+      cursor = (scores, torch.where(items >= 0, items + 1, items))   # a vacant slot (-inf, -1) is "exhausted" as it is
+    return tuple(torch.cat(parts, 1) for parts in zip(*pages))
 
   def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None, item_pooling=None):
     """Queries as for `search`; targets [NQ] or [NQ, T] int64 on the index device, values -1 .. num_items - 1 ->
@@ -1133,7 +1261,7 @@ class VideoIndex(_Index):
 
   def _entry(self, op, variant=''):
     """The C entry point of a scan over this index's storage: op 'topk', 'topk_groups', 'rank', 'thresholds', 'count',
-    'range_count', 'range_fill', 'rescore' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions), '_norm', '_pooled' or '_itemsets' -> (the
+    'range_count', 'range_fill', 'rescore' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions), '_norm', '_after' / '_norm_after' (a cursor), '_pooled' or '_itemsets' -> (the
     function, its name)."""
     name = 'mmt_search_%s%s%s' % (op, _ENTRY_TAGS[self.dtype], variant)
     return getattr(_lib.lib(), name), name
@@ -1209,21 +1337,30 @@ class VideoIndex(_Index):
     """The top-k pass of `search` and `search_groups` behind their argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the
     index device, the scan's parts this index's own -> (scores, indices), with a grouping (scores, groups, items), one
     row per query or query set, min(k, the candidates) wide (a grouping: k).  The unmasked plain scan is handed k as it
-    is and writes min(k, NV) columns; only with exclusions can a slot stay without a candidate, so only then are the
-    outputs filled beforehand.  Nothing here waits for the device."""
+    is and writes min(k, NV) columns; only with exclusions or a cursor can a slot stay without a candidate, so only
+    then are the outputs filled beforehand.  A cursor goes through the _after / _norm_after entries: its bounds are built
+    once, on the device (mmt_search_after_keys), and sliced per row batch next to the exclusions.  Nothing here waits
+    for the device."""
     nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    masked = scan.subset is not None or scan.ex is not None
+    paged = scan.after is not None
+    masked = scan.subset is not None or scan.ex is not None or paged
     if grouping is None and (masked or scan.kind):
       k = min(k, scan.candidates(self))  # lists no longer than the candidates: the outputs stay dense
-    outs = _lists(2 if grouping is None else 3, self.device, scan.rows(q), min(k, nv), vacant=scan.ex is not None)
+    outs = _lists(2 if grouping is None else 3, self.device, scan.rows(q), min(k, nv), vacant=scan.ex is not None or paged)
     if nq == 0:
       return outs
     if grouping is not None:
       fn, name = self._entry('topk_groups')
     else:
-      fn, name = self._entry('topk', scan.kind or ('_norm' if scan.norm is not None else '_ex' if masked else ''))
+      variant = scan.kind or ('_norm' if scan.norm is not None else '_after' if paged else '_ex' if masked else '')
+      fn, name = self._entry('topk', variant + ('_after' if paged and scan.norm is not None else ''))
     workspace = getattr(_lib.lib(), 'mmt_topk%s_workspace_keys' % scan.kind)
     with torch.cuda.device(self.device):
+      if paged:
+        a_scores, first = (t.contiguous() for t in scan.after)
+        bounds = torch.empty(nq, device=self.device, dtype=torch.int64)   # uint64 keys
+        check(_lib.lib().mmt_search_after_keys(ops._p(a_scores), ops._p(first), nq, ops._p(bounds), ops._stream()),
+              'mmt_search_after_keys')
       # a row's (pooled: a set's) chunk lists at full-size chunks
       for r0, r1 in self._row_batches(nq, 8 * k * -(-scan.columns(self) // 4096), scan.pooling):
         operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
@@ -1235,6 +1372,8 @@ class VideoIndex(_Index):
         elif masked or scan.norm is not None:  # _ex and _norm: subset words, the batch's exclusions, E; then beta, lse
           extra = (scan.words(), ops._p(None if scan.ex is None else scan.ex[r0:r1]),
                    0 if scan.ex is None else scan.ex.shape[1]) + scan.norm_args()
+          if paged:
+            extra += (ops._p(bounds[r0:r1]),)
         else:
           extra = ()
         ws = torch.empty(workspace(*dims, k), device=self.device, dtype=torch.int64)
@@ -1597,6 +1736,13 @@ class ShardedVideoIndex(_Index):
     shard_of, local_of = (self._shard_of, self._local_of) if maps is None else maps
     at = items.clamp(min=0)
     return torch.where((items >= 0) & (shard_of[at] == s), local_of[at], torch.full_like(items, -1))
+
+  def _first(self, first, s):
+    """The cursor's `first` (the lowest GLOBAL item number still admitted at the cursor's score, -1 = a sentinel) on the
+    primary -> shard s's: the count of its items numbered below it -- searchsorted(ids_s, cursor item, right=True) on the
+    shard's increasing local -> global table -- which may be 0 or the shard's item count.  -1 stays -1."""
+    ids = self.shards[s].ids[:self.shards[s].num_items]
+    return torch.where(first >= 0, torch.searchsorted(ids, (first - 1).clamp(min=0), right=True), first)
 
   _item_pooling_type = ShardedItemPooling
 

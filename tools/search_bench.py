@@ -83,7 +83,13 @@ index's search(k = 128), k = 10, on a bf16 and on a float32 index of the same it
 replaces (`target_scores` of the candidates, then `search`'s order as two stable torch sorts) and the index's own full
 search(k = 10) for scale; the coarse search(k = 128) is timed beside them.  --runs rounds, every variant once per round,
 interleaved; median and spread; the share of rows on which `rescore` and the composition agree bit for bit and on which
-`search_refined` returns the fine index's own top 10.  Default output profiles/search_rescore_bench.json."""
+`search_refined` returns the fine index's own top 10.  Default output profiles/search_rescore_bench.json.
+
+--after times cursor paging over 262 144 items with 4 096 queries on a bf16 and an fp8 index of the same items: page 2 at
+k = 10 (search(after=) from the last column of page 1) beside the plain search(k = 10) of the same build, the plain search at
+k = 32, 64 and 128 (how the cost of a page grows with its width) and search_deep(depth = 256) at page = 32, 64 and 128.
+--runs rounds, every variant once per round, interleaved; median and spread; whether page 2 and the deep lists are the
+slices of the plain k = 128 list they must be.  Default output profiles/search_after_bench.json."""
 import argparse
 import json
 import math
@@ -624,8 +630,63 @@ def rescore_mode(a, dev):
   return row
 
 
+def after_mode(a, dev):
+  """Cursor paging over NV = 262 144 items, NQ = 4 096, on a bf16 and an fp8 index: page 2 at k = 10 against the plain
+  search(k = 10), the plain search at k = 32 / 64 / 128, and search_deep(256) at page 32 / 64 / 128."""
+  nq, nv = SHAPES['S3']
+  chunk, depth = 8192, 256
+  gen = torch.Generator(device=dev).manual_seed(0)
+  nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
+  dtypes = {'bfloat16': torch.bfloat16, 'float8_e4m3fn': torch.float8_e4m3fn}
+  idx = {n: VideoIndex.empty(nv, M, D, dev, dtype=t) for n, t in dtypes.items()}
+  for at in range(0, nv, chunk):
+    g = nrm(torch.randn(chunk, M, D, device=dev, generator=gen))
+    gw = torch.softmax(torch.randn(chunk, M, device=dev, generator=gen), -1)
+    for index in idx.values():
+      index.add(g, gw)
+  q = nrm(torch.randn(nq, M, D, device=dev, generator=gen) + 0.3 * g[torch.arange(nq, device=dev) % chunk])
+  qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
+  fns, cursor = {}, {}
+  for n in dtypes:
+    page1 = idx[n].search(q, qw, k=K)
+    cursor[n] = (page1[0][:, -1].contiguous(), page1[1][:, -1].contiguous())
+    fns[n + '/search_k10'] = lambda n=n: idx[n].search(q, qw, k=K)
+    fns[n + '/page2_k10'] = lambda n=n: idx[n].search(q, qw, k=K, after=cursor[n])
+    for k in (32, 64, 128):
+      fns[n + '/search_k%d' % k] = lambda n=n, k=k: idx[n].search(q, qw, k=k)
+    for page in (32, 64, 128):
+      fns[n + '/deep256_page%d' % page] = lambda n=n, page=page: idx[n].search_deep(q, qw, depth, page=page)
+  ts = {n: [] for n in fns}
+  out = {}
+  for r in range(a.runs):
+    for n, fn in fns.items():
+      t, _, _, out[n] = timed(fn, a.min_seconds)
+      ts[n].append(t)
+    print('round %d of %d' % (r + 1, a.runs), file=sys.stderr, flush=True)
+  row = {'NQ': nq, 'NV': nv, 'depth': depth}
+  for n in fns:
+    row[n] = dict(seconds_median=float(np.median(ts[n])), seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n])
+  same = lambda x, y: float(((x[1] == y[1]) & (x[0].view(torch.int32) == y[0].view(torch.int32))).all(1).float().mean())
+  for n in dtypes:
+    top = out[n + '/search_k128']
+    deep = idx[n].search_deep(q, qw, 128, page=32)
+    plain, page2 = row[n + '/search_k10'], row[n + '/page2_k10']
+    row[n + '/summary'] = dict(
+        page2_over_plain=page2['seconds_median'] / plain['seconds_median'],
+        spread_seconds=max(plain['seconds_spread'], page2['seconds_spread']),
+        page2_rows_identical_to_the_k128_list=same(out[n + '/page2_k10'], (top[0][:, K:2 * K], top[1][:, K:2 * K])),
+        deep128_rows_identical_to_the_k128_list=same(deep, top),
+        deep256_rows_identical_across_pages=min(same(out[n + '/deep256_page32'], out[n + '/deep256_page%d' % p])
+                                                 for p in (64, 128)),
+        seconds_per_page_column={'k%d' % k: row[n + '/search_k%d' % k]['seconds_median'] / k for k in (10, 32, 64, 128)})
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
+  ap.add_argument('--after', action='store_true', help='time cursor paging on a bf16 and an fp8 index of 262 144 items: page 2 '
+                  'at k = 10 against search(k = 10), the plain search at k = 32 / 64 / 128 and search_deep(256) at page '
+                  '32 / 64 / 128 (no other mode flag)')
   ap.add_argument('--rescore', action='store_true', help='time rescore (C = 128 candidates from the fp8 index, k = 10) on a '
                   'bf16 and a float32 index of 262 144 items against target_scores + a torch sort and the full '
                   'search(k = 10) (no other mode flag)')
@@ -699,6 +760,16 @@ def main():
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
+  if a.after:
+    res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'after', 'runs': a.runs,
+           'min_seconds': a.min_seconds}
+    res.update(after_mode(a, dev))
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                'search_after_bench.json')
+    with open(out, 'w') as f:
+      json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return
   if a.rescore:
     res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'rescore', 'runs': a.runs,
            'min_seconds': a.min_seconds}
