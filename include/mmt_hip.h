@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MMT_ABI_VERSION 5  /* mmt_gemm_nt_ln_fwd removed (4: MmtEpilogue.rider*, MmtBertBatch.rider*, MmtAdamQueue and the Adam rider exports removed; r06: live_rows_hint; r04: MmtEpilogue.dot_*, mmt_attn_bwd*_ex) */
+#define MMT_ABI_VERSION 6  /* 6: the 54 per-variant scan entries became nine over MmtSearchScan; 5: mmt_gemm_nt_ln_fwd removed (4: MmtEpilogue.rider*, MmtBertBatch.rider*, MmtAdamQueue and the Adam rider exports removed; r06: live_rows_hint; r04: MmtEpilogue.dot_*, mmt_attn_bwd*_ex) */
 #define MMT_ROW_ALIGN 256
 
 #define MMT_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -460,420 +460,225 @@ int mmt_sims_eval(const float* txt, const float* vid, const float* tw, const flo
 int mmt_retrieval_ranks(const float* sims, const uint8_t* qmask, int NQ, int NV, float* t2v_rank, float* v2t_rank,
                         float* scratch, void* stream);
 
-/* ---- top-k retrieval (search.hip, search_bf16.hip, search_fp8.hip, search_rank.hip, search_subset.hip, search_shard.hip, search_norm.hip, fold in retrieval.hip) --------------------------------------
+/* ---- gallery search (search.hip, search_bf16.hip, search_fp8.hip, search_rank.hip, search_subset.hip, search_shard.hip,
+ * search_norm.hip, search_range.hip, search_group.hip, search_pool.hip, search_itemset.hip, search_rescore.hip; fold in
+ * retrieval.hip) ------------------------------------------------------------------------------------------------
  * score(q, g) = sum_m qw[q][m] gw[g][m] <Q_m[q], G_m[g]> / sum_m qw[q][m] gw[g][m] (0 -> 1e-5), the 'indep' similarity
- * of model/model.py:789-837.  Per query the min(k, NV) best (score, gallery index) pairs, score descending, equal scores
- * by ascending index (a stable argsort; the reference's np.argsort leaves the order of exact ties unspecified).
- * 1 <= k <= 128.  Deterministic (no atomics).  Never forms the NQ x NV matrix.
+ * of model/model.py:789-837, computed tile by tile: no scan forms the NQ x NV matrix, none uses atomics, every output
+ * slot has one writer, so every result is bit-reproducible.  The ORDER of every list is score descending, -0 tied with
+ * +0, equal scores by ascending item number (a stable argsort; the reference's np.argsort leaves exact ties unspecified).
+ *
+ * Storage.  The index keeps the folded rows gf = gw (.) G [NV][M*d] in one of three forms; a scan is told which by
+ * MmtSearchScan.storage:
+ *   MMT_SEARCH_FP32: fp32 rows, fp32 query rows qf = fold(Q, qw) (mmt_search_fold), fp32 MFMAs.  d % 4 == 0.
+ *   MMT_SEARCH_BF16: bf16(gf), rounded once, round-to-nearest-even.  Only storage is lossy; the score is defined on the
+ *     stored value, with the fp32 query carried as q = hi = bf16(qf), q_lo = lo = bf16(qf - hi) (mmt_search_fold_split_bf16;
+ *     two bf16 MFMAs per gallery fragment, fp32 accumulation; residual < 2^-16 relative per query element).  Against fp32
+ *     storage a score moves by at most 2^-8 * sum_m qw gw <|Q_m|, |G_m|> / sum_m qw gw.  d % 8 == 0.
+ *   MMT_SEARCH_FP8: with f the fp32 folded row, scale = 2^e, the smallest power of two with max_k |f[k]| / 2^e <= 448 (e
+ *     clamped to -120 .. 120; an all-zero row: 1), and stored = e4m3fn_rne(f / scale): OCP e4m3fn codes, round-to-nearest-
+ *     even with subnormals, never saturating (mmt_search_fold_fp8; inputs are taken to be finite).  The score is
+ *     fl( fl(acc * gscale[g]) / den ), acc as the bf16 scan computes it from the hi / lo pair (every e4m3fn value is a
+ *     bf16 value), the scale multiply rounded on its own.  Against fp32 storage a score moves by at most
+ *     ( 2^-4 * <|qf|, |f|> + 2^-10 * scale[g] * sum_k |qf[k]| ) / |den|.  d % 16 == 0.
+ * Folded rows are 16-byte aligned in every form.
+ *
  * mmt_search_fold: out = w (.) x for x [N][M][d] (d % 4 == 0, 16-byte aligned), w [N][M] -> out [N][M*d].
- * mmt_topk_workspace_keys: uint64 workspace of mmt_search_topk / mmt_rows_topk, NQ * ceil(NV / chunk) * k with a
- *   gallery chunk of 4096 columns (smaller only when the launch would not fill the chip); MMT_ERR_ARG if k or a size is
- *   out of range.
- * mmt_search_topk: qf = fold(Q, qw) [NQ][M*d], gf = fold(G, gw) [NV][M*d] (16-byte aligned), qw [NQ][M], gw [NV][M];
- *   scores (nullable) fp32 / index int64 [NQ][min(k, NV)].  Fused fp32-MFMA scoring + selection, then a merge launch.
- * mmt_rows_topk: the same selection on a given fp32 matrix (row stride ld), rows r = rows[i] for output row i (nullable:
- *   i itself) -- utils/util.py:38-68 compress_predictions (trainer/trainer.py:411-437 'final_eval'; the visualiser's
- *   ranking, utils/visualizer.py:74-92). */
-int mmt_search_fold(const float* x, const float* w, int N, int M, int d, float* out, void* stream);
-int64_t mmt_topk_workspace_keys(int NQ, int NV, int k);
-int mmt_search_topk(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                    int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
-int mmt_rows_topk(const float* sims, int64_t ld, const int32_t* rows, int NR, int NV, int k, uint64_t* ws, float* scores,
-                  int64_t* index, void* stream);
-/* bf16-stored gallery (search_bf16.hip).  The index keeps bf16(gw (.) G): the fp32 fold rounded once, round-to-nearest-
- * even.  Only storage is lossy; the score is defined on the stored value,
- *   score(q, g) = < fold_fp32(Q, qw)[q], dequant(stored[g]) > / sum_m qw[q][m] gw[g][m] (0 -> 1e-5),
- * with the fp32 query carried as hi = bf16(qf), lo = bf16(qf - hi) (two bf16 MFMAs per gallery fragment, fp32
- * accumulation; residual < 2^-16 relative per query element).  Against the fp32 index a score moves by at most
- * 2^-8 * sum_m qw gw <|Q_m|, |G_m|> / sum_m qw gw.  Order, ties, k range, determinism and workspace
- * (mmt_topk_workspace_keys) as for mmt_search_topk.  d % 8 == 0 (16-byte bf16 rows), pointers 16-byte aligned.
- * mmt_search_fold_bf16: out = bf16(w (.) x) [N][M*d]; out may point at a row of a larger preallocated buffer.
+ * mmt_search_fold_bf16: out = bf16(w (.) x); out may point at a row of a larger preallocated buffer.
  * mmt_search_fold_split_bf16: the query pair hi, lo [N][M*d] in one launch.
- * mmt_search_topk_bf16: q_hi / q_lo [NQ][M*d], gf [NV][M*d] bf16 bits; qw [NQ][M], gw [NV][M] fp32; outputs as
- *   mmt_search_topk. */
+ * mmt_search_fold_fp8: out = the codes [N][M*d], scale fp32 [N]; both may point into larger preallocated buffers.
+ * mmt_rows_topk: the selection of mmt_search_topk on a given fp32 matrix (row stride ld), rows r = rows[i] for output row
+ *   i (nullable: i itself) -- utils/util.py:38-68 compress_predictions (trainer/trainer.py:411-437 'final_eval'; the
+ *   visualiser's ranking, utils/visualizer.py:74-92).  Workspace: mmt_topk_workspace_keys. */
+int mmt_search_fold(const float* x, const float* w, int N, int M, int d, float* out, void* stream);
 int mmt_search_fold_bf16(const float* x, const float* w, int N, int M, int d, uint16_t* out, void* stream);
 int mmt_search_fold_split_bf16(const float* x, const float* w, int N, int M, int d, uint16_t* hi, uint16_t* lo,
                                void* stream);
-int mmt_search_topk_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
-                         int NQ, int NV, int M, int d, int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
-/* Exact rank counts over the same scan (search_rank.hip), replacing the ranking of a materialised sims matrix in
- * model/metric.py:90-121 (t2v_metrics) and 153-243 (v2t_metrics): for every query q and each of its T targets
- * (gallery items, int64 [NQ][T], 1 <= T <= 32)
- *   greater[q][t] = #{g < NV : score(q, g) > score(q, targets[q][t])},  equal[q][t] = #{g < NV : score(q, g) == ...}
- * as int32 [NQ][T]; the reference's tie-averaged 0-based rank is greater + (equal - 1) / 2.  The threshold is the very
- * value the scan computes for the target, so equal >= 1 for a target with a non-NaN score.  Plain float compares
- * (-0 == +0, NaN counts for nothing).  A target outside 0 .. NV - 1 (-1 = none) is checked on the device, never
- * dereferenced, and gets 0 / 0.  Deterministic (integer sums, no atomics).  Never forms the NQ x NV matrix.
- * mmt_rank_workspace_ints: int32 workspace, NQ * T * (1 + 2 * ceil(NV / chunk)) with the chunk of mmt_search_topk;
- *   MMT_ERR_ARG if T or a size is out of range.
- * mmt_search_rank / mmt_search_rank_bf16: operands, gates (MMT_ERR_ARG, MMT_ERR_ALIGN) and score definition as
- *   mmt_search_topk / mmt_search_topk_bf16. */
-int64_t mmt_rank_workspace_ints(int NQ, int NV, int T);
-int mmt_search_rank(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                    const int64_t* targets, int T, int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
-int mmt_search_rank_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
-                         int NQ, int NV, int M, int d, const int64_t* targets, int T, int32_t* ws, int32_t* greater,
-                         int32_t* equal, void* stream);
-/* The same scans restricted to a subset of the stored items (search_subset.hip and the masked instantiations of the
- * kernels above): the test cuts of one corpus ("full", "jsfusion", "miech": data_loader/msrvtt_dataset.py:27-47)
- * and the padded captions of a multi-caption set (query_masks, model/metric.py:90-121, 153-243) without a second,
- * gathered index per cut; and "the k best items, not counting the query's own" for the negatives of the max-margin
- * loss (model/loss.py:29-65).
- * subset: uint32 words, bit i & 31 of word i >> 5 = item i allowed; 4 * ceil(NV / 128) words (one 128-item scan tile =
- *   one aligned 16-byte load), bits at or past NV zero, 16-byte aligned (else MMT_ERR_ALIGN).  A tile with no bit set is
- *   skipped before its K loop.  Null = every item (the unmasked kernels run unless exclusions are given).
- * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> those words, padding included: one ballot per 64 items,
- *   one writer per word.
- * mmt_search_topk_ex / mmt_search_topk_bf16_ex: mmt_search_topk / mmt_search_topk_bf16 over the allowed items less, per
- *   query, the E items exclude[q][0 .. E - 1] (int64, -1 .. NV - 1, -1 = none; duplicates and items outside the subset
- *   are fine).  0 <= E <= 32, and exclude non-null when E > 0, else MMT_ERR_ARG.  The score of a returned item has the
- *   bits the unmasked search gives it: the mask acts at selection only.  Outputs [NQ][min(k, NV)] as before, but ONLY
- *   the slots that have a candidate are written -- a query with fewer allowed items than that leaves the rest of its
- *   row untouched (the caller prefills).  Workspace: mmt_topk_workspace_keys.
- * mmt_search_rank_ex / mmt_search_rank_bf16_ex: greater / equal count allowed items only.  Thresholds come from the
- *   unmasked threshold pass, so a target outside the subset is scored but does not count itself (equal may be 0).
- *   Workspace: mmt_rank_workspace_ints. */
-int mmt_search_subset_pack(const uint8_t* mask, int NV, uint32_t* words, void* stream);
-int mmt_search_topk_ex(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                       int k, const uint32_t* subset, const int64_t* exclude, int E, uint64_t* ws, float* scores,
-                       int64_t* index, void* stream);
-int mmt_search_topk_bf16_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
-                            int NQ, int NV, int M, int d, int k, const uint32_t* subset, const int64_t* exclude, int E,
-                            uint64_t* ws, float* scores, int64_t* index, void* stream);
-int mmt_search_rank_ex(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                       const int64_t* targets, int T, const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal,
-                       void* stream);
-int mmt_search_rank_bf16_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
-                            int NQ, int NV, int M, int d, const int64_t* targets, int T, const uint32_t* subset, int32_t* ws,
-                            int32_t* greater, int32_t* equal, void* stream);
-/* One gallery cut into shards, each an index of its own with item numbers of its own (search.py: ShardedVideoIndex; the
- * 8-GPU node of trainer/trainer.py's evaluation over a corpus that does not fit one card).  score(q, g) has the same
- * bits wherever item g is stored and whatever NV is, so the shards' answers combine exactly:
- * mmt_search_thresholds / mmt_search_thresholds_bf16: the threshold pass of mmt_search_rank / _bf16 alone --
- *   thr[q][t] = score(q, targets[q][t]) as fp32 [NQ][T], NaN for a target outside 0 .. NV - 1 (-1 = none; checked on the
- *   device, never dereferenced).  Operands and gates (MMT_ERR_ARG, MMT_ERR_ALIGN) as mmt_search_rank / _bf16.
- * mmt_search_count / mmt_search_count_bf16: the count pass and the chunk reduce against GIVEN thresholds thr [NQ][T]:
- *   greater / equal int32 [NQ][T] over the NV items (plain float compares; a NaN threshold counts nothing).  subset
- *   (nullable, words as above): only allowed items count.  So a target scored on the shard that holds it is counted on
- *   every shard and the int32 counts add up to those of one index over all items.
- * mmt_count_workspace_ints: int32 workspace of the two, NQ * T * 2 * ceil(NV / chunk); MMT_ERR_ARG as
- *   mmt_rank_workspace_ints.
- * mmt_search_merge_lists (search_shard.hip): per query, S lists of kin (score, shard-local item) pairs -- scores fp32 /
- *   index int64 [S][NQ][kin], index -1 = empty slot -- and ids, a device array of S device pointers, ids[s] the int64
- *   local -> global item table of shard s -> the best kout of them as scores fp32 / index int64 (global) [NQ][kout]: score
- *   descending, equal scores (-0 == +0) by ascending global item, slots without a candidate (-inf, -1).  Each list must be
- *   best-first under that order with its empty slots last (true of a shard whose table is increasing).  1 <= S <= 32,
- *   1 <= kin, kout <= 128 (kout may exceed S * kin), else MMT_ERR_ARG.  A returned score has the bits of the input score.
- *   One block per query, the lists as keys in LDS, rank by binary search; no atomics, one writer per slot.  Every
- *   pointer, the S tables behind ids included, is memory of the device the kernel is launched on (ShardedVideoIndex keeps
- *   the tables on its primary device and copies the shards' lists there).  Trusted, not checked: every index value is
- *   -1 or below the length of its list's table, and every global item number is below 2^31 (the key holds it as int). */
-int64_t mmt_count_workspace_ints(int NQ, int NV, int T);
-int mmt_search_thresholds(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                          const int64_t* targets, int T, float* thr, void* stream);
-int mmt_search_thresholds_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                               const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T, float* thr,
-                               void* stream);
-int mmt_search_count(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                     const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal,
-                     void* stream);
-int mmt_search_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
-                          int NQ, int NV, int M, int d, const float* thr, int T, const uint32_t* subset, int32_t* ws,
-                          int32_t* greater, int32_t* equal, void* stream);
-int mmt_search_merge_lists(const float* scores, const int64_t* index, const int64_t* const* ids, int S, int NQ, int kin,
-                           int kout, float* out_scores, int64_t* out_index, void* stream);
-/* Querybank hubness normalisation (search_norm.hip): inverted softmax over a bank of NB queries, the static half of
- * QB-Norm (Bogolin et al., CVPR 2022), a test-time re-scoring of the ranking model/metric.py:90-121, 153-243 evaluates.
- * With score the plain value of the scans above, bit for bit, and 0 < beta < inf, all in fp32:
- *   x(b, g) = fl(beta * score(b, g));  lse[g] = log sum_b exp(x(b, g));  score'(q, g) = fl(fl(beta * score(q, g)) - lse[g])
- * (a rounded multiply, then a rounded subtract, never an fma).  lse[g] is computed blockwise: every 64-row bank block gives
- * m = max x and p = sum exp(x - m) per item, rows in ascending order, and the blocks are folded in ascending order,
- * M' = max(M, m), S' = S exp(M - M') + p exp(m - M'), lse = M + log S.  It depends on item g's stored row and weights, the
- * bank in its row order and beta only -- not on NV, the item's position, the chunk rule, the batching of the bank or the
- * shard that holds the item.  No atomics, one writer per output.
- * mmt_col_lse_workspace_floats: fp32 workspace of one mmt_search_col_lse call, 2 * ceil(NB / 64) * NV (the (m, p) pairs of
- *   its bank blocks); MMT_ERR_ARG if a size is out of range.
- * mmt_search_col_lse / mmt_search_col_lse_bf16: one batch of the bank -- operands as the query operands of mmt_search_topk /
- *   mmt_search_topk_bf16, then the gallery -- folded into the running state: state fp32 [2][NV] (M, then S).  first != 0
- *   starts the state (it is not read), otherwise it is the state the previous batch left; every batch but the last must
- *   hold a multiple of 64 rows.  lse (nullable) fp32 [NV]: written when given, i.e. with the last batch.  ws 16-byte
- *   aligned.  Gates as mmt_search_topk / _bf16 (MMT_ERR_ARG, MMT_ERR_ALIGN); beta not finite or <= 0 is MMT_ERR_ARG.
- * mmt_search_topk_norm / mmt_search_topk_bf16_norm: mmt_search_topk_ex / mmt_search_topk_bf16_ex ranking by score' (one pass
- *   over the score tile in LDS before selection; lse of the tile's 128 items read once per tile).  subset and exclude
- *   nullable, E = 0 allowed; selection, ties, workspace and merge as there.  The returned scores are score'.
- * mmt_search_thresholds_norm / _bf16_norm, mmt_search_count_norm / _bf16_norm: mmt_search_thresholds and mmt_search_count on
- *   score': thr[q][t] = score'(q, targets[q][t]) from the same tile code (NaN for a target outside 0 .. NV - 1), and the
- *   counts of score' above / equal to given thresholds (subset nullable).  Workspace: mmt_count_workspace_ints. */
-int64_t mmt_col_lse_workspace_floats(int NB, int NV);
-int mmt_search_col_lse(const float* bf, const float* bw, const float* gf, const float* gw, int NB, int NV, int M, int d,
-                       float beta, float* ws, float* state, int first, float* lse, void* stream);
-int mmt_search_col_lse_bf16(const uint16_t* b_hi, const uint16_t* b_lo, const float* bw, const uint16_t* gf, const float* gw,
-                            int NB, int NV, int M, int d, float beta, float* ws, float* state, int first, float* lse,
-                            void* stream);
-int mmt_search_topk_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                         int k, const uint32_t* subset, const int64_t* exclude, int E, float beta, const float* lse,
-                         uint64_t* ws, float* scores, int64_t* index, void* stream);
-int mmt_search_topk_bf16_norm(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                              const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
-                              const int64_t* exclude, int E, float beta, const float* lse, uint64_t* ws, float* scores,
-                              int64_t* index, void* stream);
-int mmt_search_thresholds_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
-                               int d, const int64_t* targets, int T, float beta, const float* lse, float* thr, void* stream);
-int mmt_search_thresholds_bf16_norm(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                    const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T, float beta,
-                                    const float* lse, float* thr, void* stream);
-int mmt_search_count_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                          const float* thr, int T, const uint32_t* subset, float beta, const float* lse, int32_t* ws,
-                          int32_t* greater, int32_t* equal, void* stream);
-int mmt_search_count_bf16_norm(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                               const float* gw, int NQ, int NV, int M, int d, const float* thr, int T, const uint32_t* subset,
-                               float beta, const float* lse, int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
-/* Range search (search_range.hip): every item g with score(q, g) >= thr[q] -- however many -- as a CSR over the queries,
- * without the N_query x N_gallery matrix: near-duplicate joins, all matches of a query, lists deeper than k = 128.  Two
- * passes of the scan of mmt_search_count over the same operands, the caller's prefix sum between them:
- * mmt_range_workspace_ints: int32 workspace of the two passes, NQ * ceil(NV / chunk) (one slot per query and gallery chunk
- *   of the launch); MMT_ERR_ARG if a size is out of range.
- * mmt_search_range_count / mmt_search_range_count_bf16: query operands and gallery as mmt_search_count / _bf16; thr fp32
- *   [NQ], one threshold per query (a plain float compare: NaN hits nothing, -inf every item); subset nullable, words as
- *   above: only allowed items hit.  row_counts int64 [NQ]: the hits of each query.  ws is left holding, per query, the
- *   exclusive prefix of its chunk counts in chunk order: the fill pass reads it as it is.
- * mmt_search_range_fill / mmt_search_range_fill_bf16: the same operands, thr and subset; ws as the count pass of the very
- *   same arguments left it; offsets int64 [NQ + 1], the exclusive prefix of row_counts (offsets[0] may be any base into
- *   the outputs).  Writes query q's hits to indices (int64 item numbers) / scores (fp32, the bits mmt_search_topk gives
- *   the pair) [offsets[q], offsets[q + 1]), by ascending item number.  No atomics, one writer per slot; a position is
- *   clamped against the start of the row's next chunk, so the pass writes nothing outside [offsets[0], offsets[NQ]).
- * Gates as mmt_search_count / _bf16: MMT_ERR_ARG (a null pointer other than subset, a size out of range, d % 4 / d % 8),
- * MMT_ERR_ALIGN (query or gallery rows or subset words off a 16-byte boundary). */
-int64_t mmt_range_workspace_ints(int NQ, int NV);
-int mmt_search_range_count(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                           const float* thr, const uint32_t* subset, int32_t* ws, int64_t* row_counts, void* stream);
-int mmt_search_range_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                const float* gw, int NQ, int NV, int M, int d, const float* thr, const uint32_t* subset,
-                                int32_t* ws, int64_t* row_counts, void* stream);
-int mmt_search_range_fill(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                          const float* thr, const uint32_t* subset, const int32_t* ws, const int64_t* offsets,
-                          int64_t* indices, float* scores, void* stream);
-int mmt_search_range_fill_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                               const float* gw, int NQ, int NV, int M, int d, const float* thr, const uint32_t* subset,
-                               const int32_t* ws, const int64_t* offsets, int64_t* indices, float* scores, void* stream);
-/* fp8-stored gallery (search_fp8.hip; the scans are instantiations of the kernels above).  With f = the row mmt_search_fold
- * gives an item, the index keeps scale = 2^e, the smallest power of two with max_k |f[k]| / 2^e <= 448 (e clamped to
- * -120 .. 120; an all-zero row: 1), and stored = e4m3fn_rne(f / scale): OCP e4m3fn codes, round-to-nearest-even with
- * subnormals, never saturating.  Inputs are taken to be finite (a NaN or Inf spoils its own item only).  Only storage is
- * lossy; the score is defined on the stored value,
- *   score(q, g) = fl( fl(acc * scale[g]) / den ),  acc = < fold_fp32(Q, qw)[q], dequant(stored[g]) >,
- *   den = sum_m qw[q][m] gw[g][m] (0 -> 1e-5),
- * acc as mmt_search_topk_bf16 computes it (hi = bf16(qf), lo = bf16(qf - hi), bf16 MFMAs, fp32 accumulation; every
- * e4m3fn value is a bf16 value), the scale multiply rounded on its own.  Against the fp32 index a score moves by at most
- *   ( 2^-4 * <|qf|, |f|> + 2^-10 * scale[g] * sum_k |qf[k]| ) / |den|.
- * d % 16 == 0 (16-byte fp8 rows), pointers 16-byte aligned.
- * mmt_search_fold_fp8: out = the codes [N][M*d], scale fp32 [N]; both may point into larger preallocated buffers.
- * The scans: query operands from mmt_search_fold_split_bf16; gf [NV][M*d] e4m3fn codes; gscale fp32 [NV] after gw; every
- *   other argument, gate, order, workspace and output as the _bf16 call of the same name. */
 int mmt_search_fold_fp8(const float* x, const float* w, int N, int M, int d, uint8_t* out, float* scale, void* stream);
-int mmt_search_topk_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
-                        const float* gscale, int NQ, int NV, int M, int d, int k, uint64_t* ws, float* scores, int64_t* index,
-                        void* stream);
-int mmt_search_topk_fp8_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
-                           const float* gscale, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
-                           const int64_t* exclude, int E, uint64_t* ws, float* scores, int64_t* index, void* stream);
-int mmt_search_rank_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
-                        const float* gscale, int NQ, int NV, int M, int d, const int64_t* targets, int T, int32_t* ws,
-                        int32_t* greater, int32_t* equal, void* stream);
-int mmt_search_rank_fp8_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
-                           const float* gscale, int NQ, int NV, int M, int d, const int64_t* targets, int T,
-                           const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
-int mmt_search_thresholds_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
-                              const float* gscale, int NQ, int NV, int M, int d, const int64_t* targets, int T, float* thr,
-                              void* stream);
-int mmt_search_count_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
-                         const float* gscale, int NQ, int NV, int M, int d, const float* thr, int T, const uint32_t* subset,
-                         int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
-int mmt_search_range_count_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
-                               const float* gw, const float* gscale, int NQ, int NV, int M, int d, const float* thr,
-                               const uint32_t* subset, int32_t* ws, int64_t* row_counts, void* stream);
-int mmt_search_range_fill_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
-                              const float* gscale, int NQ, int NV, int M, int d, const float* thr, const uint32_t* subset,
-                              const int32_t* ws, const int64_t* offsets, int64_t* indices, float* scores, void* stream);
-/* Grouped search (search_group.hip): the k best GROUPS of a gallery whose items carry a group id -- the clips of a video,
- * the captions of a video -- each with its best item, without the N_query x N_gallery matrix.  groups int32 [NV], values
- * >= 0, any labelling (ids need not be dense, members need not be adjacent).  Per query the representative of a group is
- * its member with the largest key under mmt_search_topk's order (score descending, -0 tied with +0, equal scores by
- * ascending item); groups rank by their representatives under the same order.
- * mmt_search_topk_groups / mmt_search_topk_groups_bf16: query operands and gallery as mmt_search_topk / _bf16; subset
- *   nullable, words as above: only allowed items are candidates, a group's representative is its best allowed member and
- *   a group without one does not appear.  1 <= k <= 128 (the caller passes min(k, number of groups): k is the width of
- *   the outputs and of the chunk lists).  Outputs [NQ][k]: scores fp32 (the bits mmt_search_topk gives the pair),
- *   out_groups int64, out_items int64; slots past the last group hold (-inf, -1, -1).  The scan keeps the best k distinct
- *   groups per query and chunk (a compaction drops the lesser duplicates of a group before it rank-sorts); one wave per
- *   query then merges the chunk lists, de-duplicating again.  Workspace: mmt_topk_workspace_keys(NQ, NV, k).  No atomics,
- *   one writer per slot.  Gates: MMT_ERR_ARG (a null pointer other than subset -- the group table included -- a size or
- *   k out of range, d % 4 / d % 8), MMT_ERR_ALIGN (query or gallery rows or subset words off a 16-byte boundary), before
- *   any launch.  Trusted, not checked: 0 <= groups[g].
+int mmt_rows_topk(const float* sims, int64_t ld, const int32_t* rows, int NR, int NV, int k, uint64_t* ws, float* scores,
+                  int64_t* index, void* stream);
+
+/* One scan, described: everything about it except what the operation itself consumes and produces.  Every mmt_search_*
+ * scan below takes one.  A part that is not wanted is null / 0; a part the operation, the storage or another part has no
+ * kernel for is REFUSED (MMT_ERR_ARG before any launch), never ignored -- the supported combinations are listed with the
+ * entries and in DESIGN 9.15.
+ *   q, q_lo, qw : query rows [NQ][M*d] -- fp32: q = qf, q_lo null; bf16 / fp8: the hi / lo pair -- and weights [NQ][M].
+ *   g, gw, gscale: stored rows [NV][M*d] in `storage`, weights [NV][M]; gscale fp32 [NV] with fp8 and only then.
+ *   subset  : nullable = every item.  uint32 words, bit i & 31 of word i >> 5 = item i allowed; 4 * ceil(NV / 128) words
+ *             (one 128-item scan tile = one aligned 16-byte load), bits at or past NV zero, 16-byte aligned
+ *             (mmt_search_subset_pack: mask [NV] bytes, nonzero = allowed, -> those words).  A tile with no bit set is
+ *             skipped before its K loop.  With item sets the bits number SETS.
+ *   exclude, E: per query the E items exclude[q][0 .. E - 1] (int64, -1 .. NV - 1, -1 = none; duplicates and items outside
+ *             the subset are fine) are no candidates.  0 <= E <= 32; exclude non-null exactly when E > 0.
+ *   after   : nullable = no cursor.  uint64 [NQ] bounds of mmt_search_after_keys: a row's candidates are the items whose
+ *             key is strictly below its bound (see there).
+ *   lse, beta: nullable / 0 = no norm.  Querybank normalisation: lse fp32 [NV] of mmt_search_col_lse and 0 < beta < inf;
+ *             the scan works on score'(q, g) = fl(fl(beta * score(q, g)) - lse[g]).  One of the two without the other is
+ *             MMT_ERR_ARG.
+ *   sets, set_size, mode, set_weights: MMT_SEARCH_SETS_NONE (the other three 0 / null), or
+ *             MMT_SEARCH_SETS_QUERY: the queries are NQ / set_size sets of set_size consecutive rows (1 .. 64), or
+ *             MMT_SEARCH_SETS_ITEM : the stored items are NV / set_size sets of set_size consecutive items (1 .. 128);
+ *             every scan then answers per SET on the pooled score (below).  set_weights fp32 [NQ] resp. [NV]; mode 0 =
+ *             mean, 1 = max.  NQ resp. NV must be a whole number of sets.
+ *   NQ, NV, M, d: query rows, stored items, experts (1 .. 16), width per expert (a multiple of 4 / 8 / 16 by storage).
+ * Pooled score of a set over its participating members r0 < r1 < ... (weight != 0), in member order, with s(r) the score
+ * of the member's pair:  mode 0: v = fl(w[r0] * s(r0)), then v = fl(v + fl(w[ri] * s(ri))) -- a rounded multiply, then a
+ * rounded add, never an fma, never reassociated (w = 1 / C: model/model.py:826-831 'avg');  mode 1: v = s(r0), then
+ * v = s(ri) where s(ri) > v (a plain compare; the weights are a mask).  Trusted, not checked: weights finite, every set
+ * has a member with weight != 0 (a set without one pools to 0). */
+#define MMT_SEARCH_FP32 0
+#define MMT_SEARCH_BF16 1
+#define MMT_SEARCH_FP8 2
+#define MMT_SEARCH_SETS_NONE 0
+#define MMT_SEARCH_SETS_QUERY 1
+#define MMT_SEARCH_SETS_ITEM 2
+typedef struct MmtSearchScan {
+  const void* q;
+  const void* q_lo;
+  const float* qw;
+  const void* g;
+  const float* gw;
+  const float* gscale;
+  const uint32_t* subset;
+  const int64_t* exclude;
+  const uint64_t* after;
+  const float* lse;
+  const float* set_weights;
+  int32_t storage;
+  int32_t NQ;
+  int32_t NV;
+  int32_t M;
+  int32_t d;
+  int32_t E;
+  float beta;
+  int32_t sets;
+  int32_t set_size;
+  int32_t mode;
+} MmtSearchScan;
+#ifdef __cplusplus
+static_assert(sizeof(MmtSearchScan) == 128, "MmtSearchScan: 11 pointers, then 10 four-byte fields");
+#else
+_Static_assert(sizeof(MmtSearchScan) == 128, "MmtSearchScan: 11 pointers, then 10 four-byte fields");
+#endif
+
+/* The scans.  Common gates, before any launch: MMT_ERR_ARG -- a null descriptor, an unknown storage or sets tag, a null
+ * operand, output or workspace (scores of mmt_search_topk may be null), NQ / NV < 1, M outside 1 .. 16, d < 1 or off the
+ * storage's multiple, an unsupported combination; MMT_ERR_ALIGN -- q, q_lo, g or subset off a 16-byte boundary.  "R" is
+ * the number of result rows: NQ, with query sets NQ / set_size.  "N" is what indices, targets and subset bits number:
+ * the NV items, with item sets the NV / set_size sets.
+ * Supported everywhere: fp32 and bf16.  fp8: with subset, exclude and after only (no norm, no sets).  Sets: fp32 and bf16,
+ * with subset only (no norm, exclude or after), never both kinds.
+ *
+ * mmt_search_topk (subset, exclude, after, norm, sets): per result row the best min(k, N) candidates, scores (nullable)
+ *   fp32 / index int64 [R][min(k, N)], 1 <= k <= 128.  Fused scoring + selection per gallery chunk, then a merge launch.
+ *   Without subset, exclude, after, norm and sets the unmasked kernel runs and every slot is written; otherwise ONLY the
+ *   slots that have a candidate are written (the caller prefills).  The score of a returned item has the bits the
+ *   unmasked search gives it: masks act at selection only.  With norm the scores are score'.
+ * mmt_search_topk_groups (subset): the k best GROUPS of a gallery whose items carry a group id (the clips of a video), each
+ *   with its best item.  group_ids int32 [NV], values >= 0 (trusted), any labelling.  Per query the representative of a
+ *   group is its best allowed member; groups rank by their representatives.  1 <= k <= 128 (the caller passes min(k,
+ *   number of groups)).  Outputs [NQ][k]: scores fp32, groups int64, items int64; slots past the last group hold
+ *   (-inf, -1, -1).  Workspace as mmt_search_topk.
+ * mmt_search_rank (subset): for every query and each of its T targets (int64 [NQ][T], 1 <= T <= 32)
+ *     greater[q][t] = #{allowed g : score(q, g) > score(q, targets[q][t])},  equal[q][t] = #{allowed g : score(q, g) == ...}
+ *   as int32 [NQ][T]; the reference's tie-averaged 0-based rank (model/metric.py:90-121, 153-243) is greater +
+ *   (equal - 1) / 2.  The threshold is the very value the scan computes for the target (scored whether allowed or not),
+ *   plain float compares (-0 == +0, NaN counts for nothing).  A target outside 0 .. NV - 1 (-1 = none) is checked on the
+ *   device, never dereferenced, and gets 0 / 0.  = mmt_search_thresholds, then mmt_search_count, in one call.
+ * mmt_search_thresholds (norm, sets): the threshold pass alone: thr[r][t] = score (norm: score', sets: pooled score) of
+ *   (r, targets[r][t]) as fp32 [R][T] with the bits the other passes compute for the pair, NaN for a target outside
+ *   0 .. N - 1.  The same value wherever the item is stored and whatever NV is, so a gallery cut into shards scores a
+ *   target on the shard that holds it.
+ * mmt_search_count (subset, norm, sets): thr fp32 [R][T] -> greater / equal int32 [R][T] over the allowed candidates
+ *   (a NaN threshold counts nothing).  The int32 counts of shards add up to those of one index.
+ * mmt_search_range_count, mmt_search_range_fill (subset): every allowed item with score(q, g) >= thr[q] (fp32 [NQ]; NaN
+ *   hits nothing, -inf everything), however many, as a CSR.  The count pass writes row_counts int64 [NQ] and leaves ws
+ *   holding, per query, the exclusive prefix of its chunk counts; the fill pass of the very same descriptor and thr reads
+ *   it, with offsets int64 [NQ + 1] the exclusive prefix of row_counts (offsets[0] may be any base), and writes query q's
+ *   hits to indices int64 / scores fp32 [offsets[q], offsets[q + 1]) by ascending item.  A position is clamped against
+ *   the start of the row's next chunk, so the pass writes nothing outside [offsets[0], offsets[NQ]).
+ * mmt_search_rescore (no options; fp32, bf16, fp8): "the k best among THESE items".  candidates int64 [NQ][C],
+ *   1 <= C <= 1024, any order, an item may repeat, a value outside 0 .. NV - 1 is ignored -> scores fp32 / index int64
+ *   [NQ][min(k, C)], 1 <= k <= 128: the best distinct candidates in the search's order, then (-inf, -1).  A score has the
+ *   bits mmt_search_topk gives the pair, decoded from the key (a -0 comes back as +0).
+ * mmt_search_col_lse (no options; fp32, bf16; the descriptor's lse and beta stay null / 0: the operation writes lse): the
+ *   inverted softmax over a bank of queries, the static half of QB-Norm (Bogolin et al., CVPR 2022).  The descriptor's
+ *   query rows are one batch of the bank; with x(b, g) = fl(beta * score(b, g)), lse[g] = log sum_b exp(x(b, g)), computed
+ *   blockwise: every 64-row bank block gives m = max x and p = sum exp(x - m) per item, rows ascending, and the blocks
+ *   are folded in ascending order, M' = max(M, m), S' = S exp(M - M') + p exp(m - M'), lse = M + log S -- a function of the
+ *   item's stored row and weights, the bank in its row order and beta only.  state fp32 [2][NV] (M, then S): first != 0
+ *   starts it, otherwise it is what the previous batch left; every batch but the last holds a multiple of 64 rows.  lse
+ *   (nullable) fp32 [NV]: written when given, i.e. with the last batch.  ws 16-byte aligned (else MMT_ERR_ALIGN); beta not
+ *   finite or <= 0 is MMT_ERR_ARG.
+ *
+ * Workspaces (MMT_ERR_ARG if a size is out of range): a gallery chunk is 4096 columns, smaller only when the launch would
+ * not fill the chip.  mmt_topk_workspace_keys: uint64, NQ * ceil(NV / chunk) * k (mmt_search_topk, _topk_groups,
+ * mmt_rows_topk).  mmt_rank_workspace_ints: int32, NQ * T * (1 + 2 * ceil(NV / chunk)).  mmt_count_workspace_ints: int32,
+ * NQ * T * 2 * ceil(NV / chunk).  mmt_range_workspace_ints: int32, NQ * ceil(NV / chunk).  mmt_col_lse_workspace_floats:
+ * fp32, 2 * ceil(NB / 64) * NV.  mmt_rescore_workspace_keys: uint64, NQ * C.  With query sets (NS sets of C rows: a block
+ * holds 64 / C sets and the chunk rule counts blocks) mmt_topk_pooled_workspace_keys / mmt_count_pooled_workspace_ints;
+ * with item sets (NT sets of C items: a 128-column tile holds 128 / C whole sets and a chunk is a whole number of tiles)
+ * mmt_topk_itemsets_workspace_keys / mmt_count_itemsets_workspace_ints. */
+int64_t mmt_topk_workspace_keys(int NQ, int NV, int k);
+int64_t mmt_rank_workspace_ints(int NQ, int NV, int T);
+int64_t mmt_count_workspace_ints(int NQ, int NV, int T);
+int64_t mmt_range_workspace_ints(int NQ, int NV);
+int64_t mmt_col_lse_workspace_floats(int NB, int NV);
+int64_t mmt_rescore_workspace_keys(int NQ, int C);
+int64_t mmt_topk_pooled_workspace_keys(int NS, int C, int NV, int k);
+int64_t mmt_count_pooled_workspace_ints(int NS, int C, int NV, int T);
+int64_t mmt_topk_itemsets_workspace_keys(int NQ, int NT, int C, int k);
+int64_t mmt_count_itemsets_workspace_ints(int NQ, int NT, int C, int T);
+int mmt_search_topk(const MmtSearchScan* scan, int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
+int mmt_search_topk_groups(const MmtSearchScan* scan, int k, const int32_t* group_ids, uint64_t* ws, float* scores,
+                           int64_t* groups, int64_t* items, void* stream);
+int mmt_search_rank(const MmtSearchScan* scan, const int64_t* targets, int T, int32_t* ws, int32_t* greater,
+                    int32_t* equal, void* stream);
+int mmt_search_thresholds(const MmtSearchScan* scan, const int64_t* targets, int T, float* thr, void* stream);
+int mmt_search_count(const MmtSearchScan* scan, const float* thr, int T, int32_t* ws, int32_t* greater, int32_t* equal,
+                     void* stream);
+int mmt_search_range_count(const MmtSearchScan* scan, const float* thr, int32_t* ws, int64_t* row_counts, void* stream);
+int mmt_search_range_fill(const MmtSearchScan* scan, const float* thr, const int32_t* ws, const int64_t* offsets,
+                          int64_t* indices, float* scores, void* stream);
+int mmt_search_rescore(const MmtSearchScan* scan, const int64_t* candidates, int C, int k, uint64_t* ws, float* scores,
+                       int64_t* index, void* stream);
+int mmt_search_col_lse(const MmtSearchScan* scan, float beta, float* ws, float* state, int first, float* lse,
+                       void* stream);
+
+/* Beside the scans.
+ * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> the subset words, padding included: one ballot per 64
+ *   items, one writer per word.
+ * mmt_search_after_keys: cursor paging -- "the k best items that come AFTER a given position in the search's order", page 2
+ *   of a result list, and through it sorted lists deeper than k = 128.  The order is the order of the uint64 keys of the
+ *   scans, so a position is one key: 2^64 - 1 = no cursor (no score gives that key); 0 = exhausted (no candidate);
+ *   key(a, first) + 1 = every item scoring below a, and at score a the items numbered first or higher.  first is the
+ *   lowest item number still admitted at the cursor's score: a_item + 1 on one index, and on a shard the count of its
+ *   items numbered <= a_item, which may be 0 or the shard's item count -- so the shards' lists merge exactly.  scores fp32
+ *   [NQ] (non-NaN), first int64 [NQ] -> keys uint64 [NQ]; first < 0 selects a sentinel by the sign of the (then infinite)
+ *   score: + no cursor, - exhausted.  0 <= first < 2^31 otherwise.  MMT_ERR_ARG for a null pointer or NQ < 1.  With norm
+ *   the keys compared are those of score'.  A block whose 64 rows are all exhausted scores nothing.
+ * mmt_search_merge_lists (search_shard.hip; one gallery cut into shards, each an index with item numbers of its own:
+ *   search.py ShardedVideoIndex): per query, S lists of kin (score, shard-local item) pairs -- scores fp32 / index int64
+ *   [S][NQ][kin], index -1 = empty slot -- and ids, a device array of S device pointers, ids[s] the int64 local -> global
+ *   item table of shard s -> the best kout of them as scores fp32 / index int64 (global) [NQ][kout] in the search's order
+ *   by GLOBAL item, slots without a candidate (-inf, -1).  Each list must be best-first with its empty slots last (true
+ *   of a shard whose table is increasing).  1 <= S <= 32, 1 <= kin, kout <= 128 (kout may exceed S * kin), else
+ *   MMT_ERR_ARG.  A returned score has the bits of the input score.  One block per query, the lists as keys in LDS, rank
+ *   by binary search.  Every pointer, the S tables behind ids included, is memory of the device the kernel is launched
+ *   on.  Trusted, not checked: every index value is -1 or below the length of its list's table, and every global item
+ *   number is below 2^31 (the key holds it as int).
  * mmt_search_merge_group_lists: per query, S lists of kin (score, group, shard-local item) triples -- scores fp32, groups
  *   int64, index int64 [S][NQ][kin], index -1 = empty slot, each list best-first with distinct groups and its empty slots
- *   last -- and ids as mmt_search_merge_lists -> the best kout distinct groups over all lists as out_scores fp32 /
- *   out_groups int64 / out_items int64 (global) [NQ][kout], equal scores by ascending GLOBAL item, then (-inf, -1, -1).
- *   1 <= S <= 32, 1 <= kin, kout <= 128, else MMT_ERR_ARG.  Pointers and trust as mmt_search_merge_lists; a group id is
- *   below 2^31. */
-int mmt_search_topk_groups(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                           int k, const int32_t* groups, const uint32_t* subset, uint64_t* ws, float* scores,
-                           int64_t* out_groups, int64_t* out_items, void* stream);
-int mmt_search_topk_groups_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                const float* gw, int NQ, int NV, int M, int d, int k, const int32_t* groups,
-                                const uint32_t* subset, uint64_t* ws, float* scores, int64_t* out_groups, int64_t* out_items,
-                                void* stream);
+ *   last -- and ids as above -> the best kout distinct groups over all lists as out_scores fp32 / out_groups int64 /
+ *   out_items int64 (global) [NQ][kout], equal scores by ascending GLOBAL item, then (-inf, -1, -1).  Limits, pointers
+ *   and trust as mmt_search_merge_lists; a group id is below 2^31. */
+int mmt_search_subset_pack(const uint8_t* mask, int NV, uint32_t* words, void* stream);
+int mmt_search_after_keys(const float* scores, const int64_t* first, int NQ, uint64_t* keys, void* stream);
+int mmt_search_merge_lists(const float* scores, const int64_t* index, const int64_t* const* ids, int S, int NQ, int kin,
+                           int kout, float* out_scores, int64_t* out_index, void* stream);
 int mmt_search_merge_group_lists(const float* scores, const int64_t* groups, const int64_t* index, const int64_t* const* ids,
                                  int S, int NQ, int kin, int kout, float* out_scores, int64_t* out_groups, int64_t* out_items,
                                  void* stream);
-/* Query-set pooling (search_pool.hip): the queries are NS sets of C consecutive rows (1 <= C <= 64, NS * C < 2^31) --
- * the captions of a video, the clips of a query video, a caption and its paraphrases -- and every scan answers per SET,
- * on the pooled score, without the N_query x N_gallery matrix.  rw fp32 [NS * C]: row weights, finite; a row with
- * rw == 0 takes no part.  Over the participating rows r0 < r1 < ... of a set, in row order, with score(r, g) the bits
- * mmt_search_topk gives the pair:
- *   mode 0 (mean): v = fl(rw[r0] * score(r0, g)), then v = fl(v + fl(rw[ri] * score(ri, g))) -- a rounded multiply, then
- *                  a rounded add, never an fma, never reassociated (rw = 1 / C: model/model.py:826-831, 'avg');
- *   mode 1 (max) : v = score(r0, g), then v = score(ri, g) where score(ri, g) > v (a plain compare; rw is a mask).
- * v depends on the set's rows, their weights and the item only.  Query operands [NS * C] rows and gallery as the unpooled
- * calls (fp32, or the bf16 hi / lo pair); subset nullable, words as above.
- * mmt_search_topk_pooled / _bf16_pooled: per set the best min(k, NV) items by v under mmt_search_topk's order, scores /
- *   index [NS][min(k, NV)] (slots without a candidate are not written, as mmt_search_topk_ex).  1 <= k <= 128.
- *   Workspace: mmt_topk_pooled_workspace_keys(NS, C, NV, k) keys.
- * mmt_search_thresholds_pooled / _bf16_pooled: targets int64 [NS][T] (outside 0 .. NV - 1 = none) -> thr fp32 [NS][T],
- *   v(set, target) with the bits the top-k and count passes compute for that pair; NaN for none.  1 <= T <= 32.
- * mmt_search_count_pooled / _bf16_pooled: thr fp32 [NS][T] -> greater / equal int32 [NS][T]: the allowed items whose v
- *   is above / equal to the threshold (plain compares).  Workspace: mmt_count_pooled_workspace_ints(NS, C, NV, T) int32.
- * The workspace sizes differ from the unpooled ones: a block holds 64 / C sets and the chunk rule counts blocks.
- * Gates: MMT_ERR_ARG (a null pointer other than subset, NS < 1, C outside 1 .. 64, a mode other than 0 / 1, a size, k or
- * T out of range, d % 4 / d % 8), MMT_ERR_ALIGN (query or gallery rows or subset words off a 16-byte boundary), before
- * any launch.  Trusted, not checked: rw finite, every set has a row with rw != 0 (a set without one pools to 0). */
-int64_t mmt_topk_pooled_workspace_keys(int NS, int C, int NV, int k);
-int64_t mmt_count_pooled_workspace_ints(int NS, int C, int NV, int T);
-int mmt_search_topk_pooled(const float* qf, const float* qw, const float* gf, const float* gw, const float* rw, int NS, int C,
-                           int mode, int NV, int M, int d, int k, const uint32_t* subset, uint64_t* ws, float* scores,
-                           int64_t* index, void* stream);
-int mmt_search_topk_bf16_pooled(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                const float* gw, const float* rw, int NS, int C, int mode, int NV, int M, int d, int k,
-                                const uint32_t* subset, uint64_t* ws, float* scores, int64_t* index, void* stream);
-int mmt_search_thresholds_pooled(const float* qf, const float* qw, const float* gf, const float* gw, const float* rw, int NS,
-                                 int C, int mode, int NV, int M, int d, const int64_t* targets, int T, float* thr,
-                                 void* stream);
-int mmt_search_thresholds_bf16_pooled(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                      const float* gw, const float* rw, int NS, int C, int mode, int NV, int M, int d,
-                                      const int64_t* targets, int T, float* thr, void* stream);
-int mmt_search_count_pooled(const float* qf, const float* qw, const float* gf, const float* gw, const float* rw, int NS, int C,
-                            int mode, int NV, int M, int d, const float* thr, int T, const uint32_t* subset, int32_t* ws,
-                            int32_t* greater, int32_t* equal, void* stream);
-int mmt_search_count_bf16_pooled(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                 const float* gw, const float* rw, int NS, int C, int mode, int NV, int M, int d,
-                                 const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
-                                 int32_t* equal, void* stream);
-/* Item-set pooling (search_itemset.hip): the STORED items are NT sets of C consecutive items (1 <= C <= 128,
- * NT * C < 2^31; set t is items t * C .. t * C + C - 1) -- the captions of a video in a caption index, the clips of a video
- * in a clip gallery -- and every scan answers per SET, on the pooled score, without the N_query x N_item matrix.  iw fp32
- * [NT * C]: item weights, finite; an item with iw == 0 takes no part.  Over the participating items g0 < g1 < ... of a
- * set, in item order, with score(q, g) the bits mmt_search_topk gives the pair:
- *   mode 0 (mean): v = fl(iw[g0] * score(q, g0)), then v = fl(v + fl(iw[gi] * score(q, gi))) -- a rounded multiply, then
- *                  a rounded add, never an fma, never reassociated (iw = 1 / C: model/model.py:826-831 on the gallery axis);
- *   mode 1 (max) : v = score(q, g0), then v = score(q, gi) where score(q, gi) > v (a plain compare; iw is a mask).
- * v depends on the query row, the set's items and their weights only.  Query operands [NQ] rows and gallery [NT * C] rows
- * as the unpooled calls (fp32, or the bf16 hi / lo pair); indices, targets and the subset bitmap (nullable, words as
- * above, 4 per 128 SETS) are in set numbers.
- * mmt_search_topk_itemsets / _bf16_itemsets: per query the best min(k, NT) sets by v under mmt_search_topk's order, scores /
- *   index [NQ][min(k, NT)] (slots without a candidate are not written, as mmt_search_topk_ex).  1 <= k <= 128.
- *   Workspace: mmt_topk_itemsets_workspace_keys(NQ, NT, C, k) keys.
- * mmt_search_thresholds_itemsets / _bf16_itemsets: targets int64 [NQ][T] (outside 0 .. NT - 1 = none) -> thr fp32 [NQ][T],
- *   v(query, target set) with the bits the top-k and count passes compute for that pair; NaN for none.  1 <= T <= 32.
- * mmt_search_count_itemsets / _bf16_itemsets: thr fp32 [NQ][T] -> greater / equal int32 [NQ][T]: the allowed sets whose v
- *   is above / equal to the threshold (plain compares).  Workspace: mmt_count_itemsets_workspace_ints(NQ, NT, C, T) int32.
- * The workspace sizes differ from the unpooled ones: a 128-column tile holds 128 / C whole sets and a chunk is a whole
- * number of tiles (the unpooled chunk rule on 128 * ceil(NT / (128 / C)) columns); at C = 1 they are the unpooled sizes.
- * Gates: MMT_ERR_ARG (a null pointer other than subset, NQ or NT < 1, C outside 1 .. 128, NT * C >= 2^31, a mode other
- * than 0 / 1, a size, k or T out of range, d % 4 / d % 8), MMT_ERR_ALIGN (query or gallery rows or subset words off a
- * 16-byte boundary), before any launch.  Trusted, not checked: iw finite, every set has an item with iw != 0 (a set
- * without one pools to 0). */
-int64_t mmt_topk_itemsets_workspace_keys(int NQ, int NT, int C, int k);
-int64_t mmt_count_itemsets_workspace_ints(int NQ, int NT, int C, int T);
-int mmt_search_topk_itemsets(const float* qf, const float* qw, const float* gf, const float* gw, const float* iw, int NQ,
-                             int NT, int C, int mode, int M, int d, int k, const uint32_t* subset, uint64_t* ws,
-                             float* scores, int64_t* index, void* stream);
-int mmt_search_topk_bf16_itemsets(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                  const float* gw, const float* iw, int NQ, int NT, int C, int mode, int M, int d, int k,
-                                  const uint32_t* subset, uint64_t* ws, float* scores, int64_t* index, void* stream);
-int mmt_search_thresholds_itemsets(const float* qf, const float* qw, const float* gf, const float* gw, const float* iw,
-                                   int NQ, int NT, int C, int mode, int M, int d, const int64_t* targets, int T, float* thr,
-                                   void* stream);
-int mmt_search_thresholds_bf16_itemsets(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                        const float* gw, const float* iw, int NQ, int NT, int C, int mode, int M, int d,
-                                        const int64_t* targets, int T, float* thr, void* stream);
-int mmt_search_count_itemsets(const float* qf, const float* qw, const float* gf, const float* gw, const float* iw, int NQ,
-                              int NT, int C, int mode, int M, int d, const float* thr, int T, const uint32_t* subset,
-                              int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
-int mmt_search_count_bf16_itemsets(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                   const float* gw, const float* iw, int NQ, int NT, int C, int mode, int M, int d,
-                                   const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
-                                   int32_t* equal, void* stream);
-/* Re-scoring of per-query shortlists (search_rescore.hip): "the k best among THESE items", the second stage of a two-stage
- * search (a wide list from an fp8 index, a range search or another model, re-ranked on the index that holds the items at
- * full precision).  It replaces a composition of mmt_search_thresholds (at most 32 targets per launch, unsorted, NaN for
- * none) with a host-side sort, tie rule and de-duplication.  candidates int64 [NQ][C], 1 <= C <= 1024: any order, an
- * item may repeat, a value outside 0 .. NV - 1 (-1 = none) is checked on the device, never dereferenced, and ignored.
- * mmt_rescore_workspace_keys: uint64 workspace of one call, NQ * C (one key per pair); MMT_ERR_ARG if NQ < 1 or C is
- *   outside 1 .. 1024.
- * mmt_search_rescore / _bf16 / _fp8: operands as mmt_search_thresholds / _bf16 / _fp8 -> scores fp32 / index int64
- *   [NQ][min(k, C)], 1 <= k <= 128: per query its best distinct candidates under mmt_search_topk's order (score
- *   descending, -0 tied with +0, equal scores by ascending item), each item once however often it was listed, then
- *   (-inf, -1).  A score has the bits mmt_search_topk and mmt_search_thresholds give the pair (the same scoring tile
- *   through a gallery-row indirection), decoded from the key as mmt_search_topk does: a -0 comes back as +0.  Two launches:
- *   the pairs' keys to the workspace, then per query a bitonic sort in LDS that drops a key equal to its predecessor.  The
- *   result does not depend on the order of a query's candidates.  No atomics, one writer per slot.  Gates: MMT_ERR_ARG (a
- *   null pointer, a size, C or k out of range, d % 4 / d % 8 / d % 16), MMT_ERR_ALIGN (query or gallery rows off a 16-byte
- *   boundary), before any launch. */
-int64_t mmt_rescore_workspace_keys(int NQ, int C);
-int mmt_search_rescore(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                       const int64_t* candidates, int C, int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
-int mmt_search_rescore_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf, const float* gw,
-                            int NQ, int NV, int M, int d, const int64_t* candidates, int C, int k, uint64_t* ws, float* scores,
-                            int64_t* index, void* stream);
-int mmt_search_rescore_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
-                           const float* gscale, int NQ, int NV, int M, int d, const int64_t* candidates, int C, int k,
-                           uint64_t* ws, float* scores, int64_t* index, void* stream);
-/* Cursor paging (search.hip): "the k best items that come AFTER a given position in mmt_search_topk's order" -- page 2 of
- * a result list, and through it sorted lists deeper than k = 128.  The order (score descending, -0 tied with +0, equal
- * scores by ascending item) is the order of the uint64 keys of the scans, so a position is one key and a row's candidates
- * are the items whose key is strictly below its bound after[q], on top of subset and exclusions:
- *   2^64 - 1 = no cursor (no score gives that key: the row is what the parent call returns); 0 = exhausted (no candidate);
- *   key(a, first) + 1 = every item scoring below a, and at score a the items numbered first or higher.  first is the
- *   lowest item number still admitted at the cursor's score: a_item + 1 on one index, and on a shard the count of its
- *   items numbered <= a_item, which may be 0 or the shard's item count -- so the shards' lists merge exactly.
- * mmt_search_after_keys: scores fp32 [NQ] (non-NaN), first int64 [NQ] -> keys uint64 [NQ], the bounds above; first < 0
- *   selects a sentinel by the sign of the (then infinite) score: + no cursor, - exhausted.  0 <= first < 2^31 otherwise.
- *   MMT_ERR_ARG for a null pointer or NQ < 1.
- * mmt_search_topk_after / _bf16_after / _fp8_after: mmt_search_topk_ex / _bf16_ex / _fp8_ex with the bounds in front of the
- *   workspace.  mmt_search_topk_norm_after / _bf16_norm_after: mmt_search_topk_norm / _bf16_norm likewise; the keys
- *   compared are those of score'.  A returned score has the bits the parent call gives the pair; only the slots that have
- *   a candidate are written (the caller prefills).  Workspace: mmt_topk_workspace_keys.  A block whose 64 rows are all
- *   exhausted scores nothing.  Gates before any launch: a null `after` is MMT_ERR_ARG, every other gate is the parent's. */
-int mmt_search_after_keys(const float* scores, const int64_t* first, int NQ, uint64_t* keys, void* stream);
-int mmt_search_topk_after(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M, int d,
-                          int k, const uint32_t* subset, const int64_t* exclude, int E, const uint64_t* after, uint64_t* ws,
-                          float* scores, int64_t* index, void* stream);
-int mmt_search_topk_bf16_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                               const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
-                               const int64_t* exclude, int E, const uint64_t* after, uint64_t* ws, float* scores,
-                               int64_t* index, void* stream);
-int mmt_search_topk_fp8_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf, const float* gw,
-                              const float* gscale, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
-                              const int64_t* exclude, int E, const uint64_t* after, uint64_t* ws, float* scores,
-                              int64_t* index, void* stream);
-int mmt_search_topk_norm_after(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
-                               int d, int k, const uint32_t* subset, const int64_t* exclude, int E, float beta,
-                               const float* lse, const uint64_t* after, uint64_t* ws, float* scores, int64_t* index,
-                               void* stream);
-int mmt_search_topk_bf16_norm_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                    const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
-                                    const int64_t* exclude, int E, float beta, const float* lse, const uint64_t* after,
-                                    uint64_t* ws, float* scores, int64_t* index, void* stream);
 
 /* ---- row-sharded similarity + max-margin loss for very large global batches (largesim.hip) --------------------
  * BASELINE.json configs[4] / SURVEY.md 8e: rank r owns the text rows r0..r0+b of the n x n similarity; same maths as

@@ -122,6 +122,18 @@ class MmtTextHeadsOpts(ctypes.Structure):
               ('seed_dev', c_vp), ('key_dev', c_vp), ('num_batches_tracked', c_vp), ('video_front', c_vp)]
 
 
+class MmtSearchScan(ctypes.Structure):
+  """One gallery scan, described (mmt_hip.h): everything but what the operation itself consumes and produces."""
+  _fields_ = ([(n, c_vp) for n in ('q', 'q_lo', 'qw', 'g', 'gw', 'gscale', 'subset', 'exclude', 'after', 'lse',
+                                   'set_weights')] +
+              [(n, ctypes.c_int32) for n in ('storage', 'NQ', 'NV', 'M', 'd', 'E')] + [('beta', c_f32)] +
+              [(n, ctypes.c_int32) for n in ('sets', 'set_size', 'mode')])
+
+
+SEARCH_FP32, SEARCH_BF16, SEARCH_FP8 = 0, 1, 2             # MmtSearchScan.storage
+SEARCH_SETS_NONE, SEARCH_SETS_QUERY, SEARCH_SETS_ITEM = 0, 1, 2   # MmtSearchScan.sets
+_SCAN = ctypes.POINTER(MmtSearchScan)
+
 EPI = dict(BF16=0, BIAS_BF16=1, BIAS_GELU=2, BIAS_DROP_RES=3, DGELU=4, ADD_F32=5, F32=6, BIAS_F32=7)
 
 # name -> (restype, argtypes); must list every symbol declared in include/mmt_hip.h
@@ -216,129 +228,33 @@ SIGNATURES = {
     'mmt_retrieval_ranks': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mmt_search_fold': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_topk_workspace_keys': (c_i64, [c_int, c_int, c_int]),
-    'mmt_search_topk': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mmt_rows_topk': (c_int, [c_vp, c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mmt_search_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_search_fold_split_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
-    'mmt_search_topk_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
-                                     c_vp]),
     'mmt_rank_workspace_ints': (c_i64, [c_int, c_int, c_int]),
-    'mmt_search_rank': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_rank_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
-                                     c_vp, c_vp]),
     'mmt_search_subset_pack': (c_int, [c_vp, c_int, c_vp, c_vp]),
-    'mmt_search_topk_ex': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp,
-                                   c_vp, c_vp]),
-    'mmt_search_topk_bf16_ex': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int,
-                                        c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_rank_ex': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
-                                   c_vp]),
-    'mmt_search_rank_bf16_ex': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
-                                        c_vp, c_vp, c_vp]),
     'mmt_count_workspace_ints': (c_i64, [c_int, c_int, c_int]),
-    'mmt_search_thresholds': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
-    'mmt_search_thresholds_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp,
-                                           c_vp]),
-    'mmt_search_count': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
-                                 c_vp]),
-    'mmt_search_count_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
-                                      c_vp, c_vp, c_vp]),
     'mmt_search_merge_lists': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     'mmt_col_lse_workspace_floats': (c_i64, [c_int, c_int]),
-    'mmt_search_col_lse': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f32, c_vp, c_vp, c_int, c_vp, c_vp]),
-    'mmt_search_col_lse_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f32, c_vp, c_vp, c_int,
-                                        c_vp, c_vp]),
-    'mmt_search_topk_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_f32,
-                                     c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_topk_bf16_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int,
-                                          c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_thresholds_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_f32, c_vp,
-                                           c_vp, c_vp]),
-    'mmt_search_thresholds_bf16_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_f32,
-                                                c_vp, c_vp, c_vp]),
-    'mmt_search_count_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_f32, c_vp,
-                                      c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_count_bf16_norm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_f32,
-                                           c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_range_workspace_ints': (c_i64, [c_int, c_int]),
-    'mmt_search_range_count': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_range_count_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
-                                            c_vp]),
-    'mmt_search_range_fill': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                      c_vp]),
-    'mmt_search_range_fill_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
-                                           c_vp, c_vp, c_vp]),
-    # fp8 gallery: the _bf16 signatures with gscale after gw
     'mmt_search_fold_fp8': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
-    'mmt_search_topk_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
-                                    c_vp]),
-    'mmt_search_topk_fp8_ex': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
-                                       c_int, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_rank_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp,
-                                    c_vp, c_vp]),
-    'mmt_search_rank_fp8_ex': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp,
-                                       c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_thresholds_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp,
-                                          c_vp]),
-    'mmt_search_count_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp,
-                                     c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_range_count_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
-                                           c_vp, c_vp]),
-    'mmt_search_range_fill_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
-                                          c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_topk_groups': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                       c_vp, c_vp]),
-    'mmt_search_topk_groups_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
-                                            c_vp, c_vp, c_vp, c_vp]),
     'mmt_search_merge_group_lists': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mmt_topk_pooled_workspace_keys': (c_i64, [c_int, c_int, c_int, c_int]),
     'mmt_count_pooled_workspace_ints': (c_i64, [c_int, c_int, c_int, c_int]),
-    'mmt_search_topk_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
-                                       c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_topk_bf16_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                                            c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_thresholds_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
-                                             c_int, c_vp, c_vp]),
-    'mmt_search_thresholds_bf16_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
-                                                  c_int, c_vp, c_int, c_vp, c_vp]),
-    'mmt_search_count_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int,
-                                        c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_count_bf16_pooled': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                                             c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_topk_itemsets_workspace_keys': (c_i64, [c_int, c_int, c_int, c_int]),
     'mmt_count_itemsets_workspace_ints': (c_i64, [c_int, c_int, c_int, c_int]),
-    'mmt_search_topk_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
-                                         c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_topk_bf16_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                                              c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_thresholds_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
-                                               c_int, c_vp, c_vp]),
-    'mmt_search_thresholds_bf16_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
-                                                    c_int, c_vp, c_int, c_vp, c_vp]),
-    'mmt_search_count_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int,
-                                          c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_count_bf16_itemsets': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                                               c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    # re-scoring of shortlists: the thresholds signatures with (candidates, C, k), a workspace and the two output lists
     'mmt_rescore_workspace_keys': (c_i64, [c_int, c_int]),
-    'mmt_search_rescore': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp,
-                                   c_vp]),
-    'mmt_search_rescore_bf16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp,
-                                        c_vp, c_vp, c_vp]),
-    'mmt_search_rescore_fp8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int,
-                                       c_vp, c_vp, c_vp, c_vp]),
-    # cursor paging: the bound builder, then the _ex / _norm signatures with the bounds in front of the workspace
     'mmt_search_after_keys': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp]),
-    'mmt_search_topk_after': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp,
-                                      c_vp, c_vp, c_vp]),
-    'mmt_search_topk_bf16_after': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int,
-                                           c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_topk_fp8_after': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
-                                          c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_topk_norm_after': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_f32,
-                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'mmt_search_topk_bf16_norm_after': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
-                                                c_int, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # the nine scans: the descriptor, what the operation consumes and produces, the stream
+    'mmt_search_topk': (c_int, [_SCAN, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_topk_groups': (c_int, [_SCAN, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_rank': (c_int, [_SCAN, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_thresholds': (c_int, [_SCAN, c_vp, c_int, c_vp, c_vp]),
+    'mmt_search_count': (c_int, [_SCAN, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_range_count': (c_int, [_SCAN, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_range_fill': (c_int, [_SCAN, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_rescore': (c_int, [_SCAN, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_col_lse': (c_int, [_SCAN, c_f32, c_vp, c_vp, c_int, c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
@@ -399,7 +315,7 @@ def lib():
       fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
       fn.restype = res
       fn.argtypes = args
-    if handle.mmt_abi_version() != 5:
+    if handle.mmt_abi_version() != 6:
       raise RuntimeError('libmmt_hip.so ABI mismatch')
     _lib = handle
   return _lib

@@ -32,12 +32,12 @@
 //   <BF16, NmTopkArgs>               : the masked kernels with tk_tile_norm between the score epilogue and the selection:
 //                                      ranks by and returns the querybank-normalised score' (search_norm.hip).
 //   <., Tk*AfterArgs>, <., NmTopkAfterArgs> : the masked and normalised kernels with a cursor per query row (the paged search,
-//                                      mmt_search_topk_after): the selection also declines every key at or above the row's
+//                                      mmt_search_topk [after]): the selection also declines every key at or above the row's
 //                                      bound (tk_tile_select<true, true>), one more compare on the same score tile.
 // The argument blocks stay separate types with their layouts as they are: a field appended to TkArgs moves the hidden
 // kernel arguments behind it and changes the unmasked code (profiles/search_subset_kernel_identity.txt).
 //
-// The masked blocks (mmt_search_topk_ex and the normalised calls): the candidates are the items whose bit is set in a
+// The masked blocks (mmt_search_topk [subset, exclude] and the normalised calls): the candidates are the items whose bit is set in a
 // packed bitmap (search_subset.hip; a null pointer allows every item), less up to TK_MAXE items per query.  A tile's four
 // mask words are one block-uniform 16-byte load (tk_tile_mask; g0 is a multiple of 128); a tile with no bit set is skipped
 // before its K loop -- no gallery loads, no MFMAs.  The mask acts at selection only (tk_tile_select<true>), on the score
@@ -108,7 +108,7 @@ struct NmTopkArgs : NmArgs {
   int k, E;
 };
 
-// The paged search (mmt_search_topk_after and its kin): the masked blocks with one bound per query row behind them, in
+// The paged search (mmt_search_topk [after] and its kin): the masked blocks with one bound per query row behind them, in
 // types of their own, so the blocks above keep their layout and their kernels their code.  after[q] is a position in the
 // search's order as a key: only keys strictly below it are candidates (tk_tile_select<true, true>).
 struct TkAfterArgs : TkMaskedArgs {
@@ -306,44 +306,38 @@ void tk_topk_lds_limits() {
                        {(const void*)topk_scan_kernel<true, NmTopkAfterArgs>, bf16 + ex + kAfterLds}});
 }
 
-// The fused search behind every top-k entry point (Args = TkMaskedArgs, TkBf16MaskedArgs or NmTopkArgs, the last with lse
-// and beta set by the caller, or one of those with a cursor: `after`, the bounds [NQ], must then be given): gate, fill, the
-// chunk scan and the merge.  `rest`: the entry's other arguments are in order.  q_lo is null where an entry has none.
+// The fused search behind mmt_search_topk (Args = TkMaskedArgs, TkBf16MaskedArgs, TkFp8MaskedArgs or NmTopkArgs, or one of
+// those with a cursor; the descriptor has passed tk_scan_gate and carries the parts Args stands for): gate, fill, the
+// chunk scan and the merge.  Without subset, exclusions, norm and cursor the unmasked instantiation runs.
 template <bool BF16, class Args>
-int tk_search(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
-              int d, int k, const uint32_t* subset, const int64_t* exclude, int E, bool rest, uint64_t* ws, float* scores,
-              int64_t* index, void* stream, const uint64_t* after = nullptr) {
-  constexpr bool AFTER = TkAfter<Args>::value;
-  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !rest || (AFTER && !after) || !ws || !index || !tk_args_ok(NQ, NV, k) ||
-      !tk_shape_ok(NQ, NV, M, d, BF16, TkFp8<Args>::value))
+int tk_search(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_t* index, void* stream) {
+  constexpr bool AFTER = TkAfter<Args>::value, FP8 = TkFp8<Args>::value;
+  if (!tk_scan_operands<BF16, FP8, Args::kNorm>(s) || !ws || !index || !tk_args_ok(s.NQ, s.NV, k) ||
+      !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16, FP8))
     return MMT_ERR_ARG;
-  if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g) & 15) return MMT_ERR_ALIGN;
-  if (E < 0 || E > TK_MAXE || (E > 0 && !exclude)) return MMT_ERR_ARG;
-  if ((uintptr_t)subset & 15) return MMT_ERR_ALIGN;  // null = every item allowed
-  a.q = static_cast<decltype(a.q)>(q); a.qw = qw; a.g = static_cast<decltype(a.g)>(g); a.gw = gw; a.ws = ws;
-  if constexpr (BF16) a.q_lo = static_cast<decltype(a.q_lo)>(q_lo);
-  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.k = k;
-  a.subset = subset; a.exclude = exclude; a.E = E;
-  if constexpr (AFTER) a.after = after;
+  if (((uintptr_t)s.q | (uintptr_t)s.q_lo | (uintptr_t)s.g) & 15) return MMT_ERR_ALIGN;
+  if (s.E < 0 || s.E > TK_MAXE || (s.E > 0 && !s.exclude)) return MMT_ERR_ARG;
+  if ((uintptr_t)s.subset & 15) return MMT_ERR_ALIGN;  // null = every item allowed
+  Args a = {};
+  a.q = static_cast<decltype(a.q)>(s.q); a.qw = s.qw; a.g = static_cast<decltype(a.g)>(s.g); a.gw = s.gw; a.ws = ws;
+  if constexpr (BF16) a.q_lo = static_cast<decltype(a.q_lo)>(s.q_lo);
+  if constexpr (FP8) a.gscale = s.gscale;
+  if constexpr (Args::kNorm) { a.beta = s.beta; a.lse = s.lse; }
+  a.NQ = s.NQ; a.NV = s.NV; a.M = s.M; a.K = s.M * s.d; a.k = k;
+  a.subset = s.subset; a.exclude = s.exclude; a.E = s.E;
+  if constexpr (AFTER) a.after = s.after;
   tk_geometry(a);
   tk_topk_lds_limits();
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)stream;
   const dim3 grid(a.n_qt * a.n_chunks);
   const size_t lds = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + tk_state_lds(k);
-  using Plain = std::conditional_t<TkFp8<Args>::value, TkFp8Args, std::conditional_t<BF16, TkBf16Args, TkArgs>>;
-  if (AFTER || Args::kNorm || subset || E)
-    hipLaunchKernelGGL((topk_scan_kernel<BF16, Args>), grid, dim3(256), lds + tk_exclude_lds(E) + (AFTER ? kAfterLds : 0), s,
-                       a);
+  using Plain = std::conditional_t<FP8, TkFp8Args, std::conditional_t<BF16, TkBf16Args, TkArgs>>;
+  if (AFTER || Args::kNorm || s.subset || s.E)
+    hipLaunchKernelGGL((topk_scan_kernel<BF16, Args>), grid, dim3(256), lds + tk_exclude_lds(s.E) + (AFTER ? kAfterLds : 0),
+                       st, a);
   else if constexpr (!Args::kNorm && !AFTER)  // constexpr only so that the slice to Plain is not instantiated for NmTopkArgs
-    hipLaunchKernelGGL((topk_scan_kernel<BF16, Plain>), grid, dim3(256), lds, s, (Plain)a);
-  return tk_merge_launch(ws, NQ, a.n_chunks, k, k < NV ? k : NV, scores, index, s);
-}
-
-template <class Args = NmTopkArgs>
-Args nm_topk_args(float beta, const float* lse) {
-  Args a = {};
-  a.beta = beta; a.lse = lse;
-  return a;
+    hipLaunchKernelGGL((topk_scan_kernel<BF16, Plain>), grid, dim3(256), lds, st, (Plain)a);
+  return tk_merge_launch(ws, s.NQ, a.n_chunks, k, k < s.NV ? k : s.NV, scores, index, st);
 }
 }  // namespace
 
@@ -371,105 +365,30 @@ extern "C" int64_t mmt_topk_workspace_keys(int NQ, int NV, int k) {
   return (int64_t)NQ * tk_n_chunks(NQ, NV) * k;
 }
 
-extern "C" int mmt_search_topk_ex(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
-                                  int d, int k, const uint32_t* subset, const int64_t* exclude, int E, uint64_t* ws,
-                                  float* scores, int64_t* index, void* stream) {
-  return tk_search<false>(TkMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, true, ws, scores,
-                          index, stream);
-}
-
-extern "C" int mmt_search_topk(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
-                               int d, int k, uint64_t* ws, float* scores, int64_t* index, void* stream) {
-  return mmt_search_topk_ex(qf, qw, gf, gw, NQ, NV, M, d, k, nullptr, nullptr, 0, ws, scores, index, stream);
-}
-
-extern "C" int mmt_search_topk_bf16_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                       const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
-                                       const int64_t* exclude, int E, uint64_t* ws, float* scores, int64_t* index,
-                                       void* stream) {
-  return tk_search<true>(TkBf16MaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, true, ws, scores,
-                         index, stream);
-}
-
-extern "C" int mmt_search_topk_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                    const float* gw, int NQ, int NV, int M, int d, int k, uint64_t* ws, float* scores,
-                                    int64_t* index, void* stream) {
-  return mmt_search_topk_bf16_ex(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, nullptr, nullptr, 0, ws, scores, index, stream);
-}
-
-extern "C" int mmt_search_topk_fp8_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
-                                      const float* gw, const float* gscale, int NQ, int NV, int M, int d, int k,
-                                      const uint32_t* subset, const int64_t* exclude, int E, uint64_t* ws, float* scores,
-                                      int64_t* index, void* stream) {
-  TkFp8MaskedArgs a = {};
-  a.gscale = gscale;
-  return tk_search<true>(a, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, gscale != nullptr, ws, scores, index,
-                         stream);
-}
-
-extern "C" int mmt_search_topk_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
-                                   const float* gw, const float* gscale, int NQ, int NV, int M, int d, int k, uint64_t* ws,
-                                   float* scores, int64_t* index, void* stream) {
-  return mmt_search_topk_fp8_ex(q_hi, q_lo, qw, gf, gw, gscale, NQ, NV, M, d, k, nullptr, nullptr, 0, ws, scores, index,
-                                stream);
-}
-
-extern "C" int mmt_search_topk_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
-                                    int d, int k, const uint32_t* subset, const int64_t* exclude, int E, float beta,
-                                    const float* lse, uint64_t* ws, float* scores, int64_t* index, void* stream) {
-  return tk_search<false>(nm_topk_args(beta, lse), qf, nullptr, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E,
-                          lse && tk_beta_ok(beta), ws, scores, index, stream);
-}
-
-extern "C" int mmt_search_topk_bf16_norm(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                         const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
-                                         const int64_t* exclude, int E, float beta, const float* lse, uint64_t* ws,
-                                         float* scores, int64_t* index, void* stream) {
-  return tk_search<true>(nm_topk_args(beta, lse), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E,
-                         lse && tk_beta_ok(beta), ws, scores, index, stream);
-}
-
-// The paged forms: the _ex and _norm entries with the bounds of mmt_search_after_keys in front of the workspace.
-extern "C" int mmt_search_topk_after(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
-                                     int M, int d, int k, const uint32_t* subset, const int64_t* exclude, int E,
-                                     const uint64_t* after, uint64_t* ws, float* scores, int64_t* index, void* stream) {
-  return tk_search<false>(TkAfterArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, true, ws, scores,
-                          index, stream, after);
-}
-
-extern "C" int mmt_search_topk_bf16_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                          const float* gw, int NQ, int NV, int M, int d, int k, const uint32_t* subset,
-                                          const int64_t* exclude, int E, const uint64_t* after, uint64_t* ws, float* scores,
-                                          int64_t* index, void* stream) {
-  return tk_search<true>(TkBf16AfterArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, true, ws, scores,
-                         index, stream, after);
-}
-
-extern "C" int mmt_search_topk_fp8_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
-                                         const float* gw, const float* gscale, int NQ, int NV, int M, int d, int k,
-                                         const uint32_t* subset, const int64_t* exclude, int E, const uint64_t* after,
-                                         uint64_t* ws, float* scores, int64_t* index, void* stream) {
-  TkFp8AfterArgs a = {};
-  a.gscale = gscale;
-  return tk_search<true>(a, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E, gscale != nullptr, ws, scores, index,
-                         stream, after);
-}
-
-extern "C" int mmt_search_topk_norm_after(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
-                                          int M, int d, int k, const uint32_t* subset, const int64_t* exclude, int E,
-                                          float beta, const float* lse, const uint64_t* after, uint64_t* ws, float* scores,
-                                          int64_t* index, void* stream) {
-  return tk_search<false>(nm_topk_args<NmTopkAfterArgs>(beta, lse), qf, nullptr, qw, gf, gw, NQ, NV, M, d, k, subset, exclude,
-                          E, lse && tk_beta_ok(beta), ws, scores, index, stream, after);
-}
-
-extern "C" int mmt_search_topk_bf16_norm_after(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw,
-                                               const uint16_t* gf, const float* gw, int NQ, int NV, int M, int d, int k,
-                                               const uint32_t* subset, const int64_t* exclude, int E, float beta,
-                                               const float* lse, const uint64_t* after, uint64_t* ws, float* scores,
-                                               int64_t* index, void* stream) {
-  return tk_search<true>(nm_topk_args<NmTopkAfterArgs>(beta, lse), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, subset, exclude, E,
-                         lse && tk_beta_ok(beta), ws, scores, index, stream, after);
+// (storage, norm, cursor, sets) -> the body and its argument block.
+extern "C" int mmt_search_topk(const MmtSearchScan* scan, int k, uint64_t* ws, float* scores, int64_t* index,
+                               void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_SUBSET | SC_EXCLUDE | SC_AFTER | SC_NORM | SC_QSETS | SC_ISETS | SC_FP8)) return rc;
+  const MmtSearchScan& s = *scan;
+  const unsigned p = tk_scan_parts(s);
+  if (p & SC_QSETS) return pl_topk(s, k, ws, scores, index, stream);
+  if (p & SC_ISETS) return is_topk(s, k, ws, scores, index, stream);
+  const bool after = p & SC_AFTER;
+  if (p & SC_FP8)
+    return after ? tk_search<true, TkFp8AfterArgs>(s, k, ws, scores, index, stream)
+                 : tk_search<true, TkFp8MaskedArgs>(s, k, ws, scores, index, stream);
+  if (s.storage == MMT_SEARCH_BF16) {
+    if (p & SC_NORM)
+      return after ? tk_search<true, NmTopkAfterArgs>(s, k, ws, scores, index, stream)
+                   : tk_search<true, NmTopkArgs>(s, k, ws, scores, index, stream);
+    return after ? tk_search<true, TkBf16AfterArgs>(s, k, ws, scores, index, stream)
+                 : tk_search<true, TkBf16MaskedArgs>(s, k, ws, scores, index, stream);
+  }
+  if (p & SC_NORM)
+    return after ? tk_search<false, NmTopkAfterArgs>(s, k, ws, scores, index, stream)
+                 : tk_search<false, NmTopkArgs>(s, k, ws, scores, index, stream);
+  return after ? tk_search<false, TkAfterArgs>(s, k, ws, scores, index, stream)
+               : tk_search<false, TkMaskedArgs>(s, k, ws, scores, index, stream);
 }
 
 extern "C" int mmt_rows_topk(const float* sims, int64_t ld, const int32_t* rows, int NR, int NV, int k, uint64_t* ws,

@@ -339,42 +339,34 @@ void gp_lds_limits() {
 }
 
 template <bool BF16>
-int gp_search(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M, int d,
-              int k, const int32_t* groups, const uint32_t* subset, uint64_t* ws, float* scores, int64_t* out_groups,
+int gp_search(const MmtSearchScan& s, int k, const int32_t* groups, uint64_t* ws, float* scores, int64_t* out_groups,
               int64_t* out_items, void* stream) {
-  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !groups || !ws || !scores || !out_groups || !out_items || k < 1 ||
-      k > TK_MAXK || !tk_shape_ok(NQ, NV, M, d, BF16))
+  if (!tk_scan_operands<BF16>(s) || !groups || !ws || !scores || !out_groups || !out_items || k < 1 || k > TK_MAXK ||
+      !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16))
     return MMT_ERR_ARG;
-  if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  if (!tk_scan_aligned(s)) return MMT_ERR_ALIGN;
   GpArgs a = {};
-  a.q = q; a.q_lo = q_lo; a.qw = qw; a.g = g; a.gw = gw; a.groups = groups; a.subset = subset; a.ws = ws;
-  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.k = k;
+  a.q = s.q; a.q_lo = s.q_lo; a.qw = s.qw; a.g = s.g; a.gw = s.gw; a.groups = groups; a.subset = s.subset; a.ws = ws;
+  a.NQ = s.NQ; a.NV = s.NV; a.M = s.M; a.K = s.M * s.d; a.k = k;
   tk_geometry(a);
   gp_lds_limits();
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL((group_scan_kernel<BF16>), dim3(a.n_qt * a.n_chunks), dim3(256),
-                     (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + gp_state_lds(k), s, a);
+                     (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + gp_state_lds(k), st, a);
   constexpr int64_t kMergeLdsMax = 64 * 1024;
   const int64_t list_bytes = (int64_t)a.n_chunks * k * 12;
   const int stage = list_bytes <= kMergeLdsMax;
-  hipLaunchKernelGGL(group_merge_kernel, dim3(NQ), dim3(64), stage ? (size_t)list_bytes : 0, s, ws, groups, a.n_chunks, k, k,
-                     stage, scores, out_groups, out_items);
+  hipLaunchKernelGGL(group_merge_kernel, dim3(s.NQ), dim3(64), stage ? (size_t)list_bytes : 0, st, ws, groups, a.n_chunks, k,
+                     k, stage, scores, out_groups, out_items);
   return (int)hipGetLastError();
 }
 }  // namespace
 
-extern "C" int mmt_search_topk_groups(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
-                                      int M, int d, int k, const int32_t* groups, const uint32_t* subset, uint64_t* ws,
-                                      float* scores, int64_t* out_groups, int64_t* out_items, void* stream) {
-  return gp_search<false>(qf, nullptr, qw, gf, gw, NQ, NV, M, d, k, groups, subset, ws, scores, out_groups, out_items,
-                          stream);
-}
-
-extern "C" int mmt_search_topk_groups_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                           const float* gw, int NQ, int NV, int M, int d, int k, const int32_t* groups,
-                                           const uint32_t* subset, uint64_t* ws, float* scores, int64_t* out_groups,
-                                           int64_t* out_items, void* stream) {
-  return gp_search<true>(q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, k, groups, subset, ws, scores, out_groups, out_items, stream);
+extern "C" int mmt_search_topk_groups(const MmtSearchScan* scan, int k, const int32_t* group_ids, uint64_t* ws, float* scores,
+                                      int64_t* groups, int64_t* items, void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_SUBSET)) return rc;
+  return scan->storage == MMT_SEARCH_FP32 ? gp_search<false>(*scan, k, group_ids, ws, scores, groups, items, stream)
+                                          : gp_search<true>(*scan, k, group_ids, ws, scores, groups, items, stream);
 }
 
 extern "C" int mmt_search_merge_group_lists(const float* scores, const int64_t* groups, const int64_t* index,

@@ -192,20 +192,20 @@ constexpr size_t is_base_lds() { return tk_base_lds<BF16>() + TK_G * 4; }
 size_t is_topk_lds(int k) { return TK_Q * (4 + 8) + (size_t)TK_Q * (k + 64) * 8; }
 size_t is_count_lds(int T) { return (size_t)TK_Q * T * 12; }
 
-// The gate and the fill every entry point shares: 0, or the error code.  `rest`: the entry's other pointers are all
-// there.  q_lo and subset are null where an entry has none.
+// The gate and the fill every entry point shares: 0, or the error code.  `own`: the entry's own pointers are all there.
+// `subset`: the descriptor's, or null for a pass that has none.  The descriptor's NV items are NT = NV / C whole sets.
 template <bool BF16>
-int is_fill(IsArgs& a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, const float* iw,
-            int NQ, int NT, int C, int mode, int M, int d, const uint32_t* subset, bool rest) {
-  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !iw || !rest || !is_sets_ok(NT, C, mode) ||
-      !tk_shape_ok(NQ, NT * C, M, d, BF16))
+int is_fill(IsArgs& a, const MmtSearchScan& s, const uint32_t* subset, bool own) {
+  const int C = s.set_size, NT = C >= 1 ? s.NV / C : 0;
+  if (!tk_scan_operands<BF16>(s) || !s.set_weights || !own || !is_sets_ok(NT, C, s.mode) || s.NV != NT * C ||
+      !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16))
     return MMT_ERR_ARG;
-  if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
-  a.q = q; a.q_lo = q_lo; a.qw = qw; a.g = g; a.gw = gw; a.iw = iw; a.subset = subset;
-  a.NQ = NQ; a.NT = NT; a.M = M; a.K = M * d; a.C = C; a.SG = TK_G / C; a.mode = mode;
+  if (((uintptr_t)s.q | (uintptr_t)s.q_lo | (uintptr_t)s.g | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  a.q = s.q; a.q_lo = s.q_lo; a.qw = s.qw; a.g = s.g; a.gw = s.gw; a.iw = s.set_weights; a.subset = subset;
+  a.NQ = s.NQ; a.NT = NT; a.M = s.M; a.K = s.M * s.d; a.C = C; a.SG = TK_G / C; a.mode = s.mode;
   a.n_tiles = is_tiles(NT, C);
-  a.tpc = is_tiles_per_chunk(NQ, NT, C);
-  a.n_qt = (NQ + TK_Q - 1) / TK_Q;
+  a.tpc = is_tiles_per_chunk(s.NQ, NT, C);
+  a.n_qt = (s.NQ + TK_Q - 1) / TK_Q;
   a.n_chunks = (a.n_tiles + a.tpc - 1) / a.tpc;
   a.n_words = 4 * ((NT + 127) / 128);
   return 0;
@@ -226,26 +226,23 @@ void is_count_lds_limits() {
 }
 
 template <bool BF16>
-int is_topk(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, const float* iw, int NQ, int NT,
-            int C, int mode, int M, int d, int k, const uint32_t* subset, uint64_t* ws, float* scores, int64_t* index,
-            void* stream) {
+int is_topk_body(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_t* index, void* stream) {
   IsArgs a = {};
   if (k < 1 || k > TK_MAXK) return MMT_ERR_ARG;
-  if (const int rc = is_fill<BF16>(a, q, q_lo, qw, g, gw, iw, NQ, NT, C, mode, M, d, subset, ws && index)) return rc;
+  if (const int rc = is_fill<BF16>(a, s, s.subset, ws && index)) return rc;
   a.ws = ws; a.k = k;
   is_topk_lds_limits();
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((iset_topk_kernel<BF16>), dim3(a.n_qt * a.n_chunks), dim3(256), is_base_lds<BF16>() + is_topk_lds(k), s,
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((iset_topk_kernel<BF16>), dim3(a.n_qt * a.n_chunks), dim3(256), is_base_lds<BF16>() + is_topk_lds(k), st,
                      a);
-  return tk_merge_launch(ws, NQ, a.n_chunks, k, k < NT ? k : NT, scores, index, s);
+  return tk_merge_launch(ws, s.NQ, a.n_chunks, k, k < a.NT ? k : a.NT, scores, index, st);
 }
 
 template <bool BF16>
-int is_thresholds(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, const float* iw, int NQ,
-                  int NT, int C, int mode, int M, int d, const int64_t* targets, int T, float* thr, void* stream) {
+int is_thresholds_body(const MmtSearchScan& s, const int64_t* targets, int T, float* thr, void* stream) {
   IsArgs a = {};
   if (T < 1 || T > IS_MAXT) return MMT_ERR_ARG;
-  if (const int rc = is_fill<BF16>(a, q, q_lo, qw, g, gw, iw, NQ, NT, C, mode, M, d, nullptr, targets && thr)) return rc;
+  if (const int rc = is_fill<BF16>(a, s, nullptr, targets && thr)) return rc;
   a.targets = targets; a.thr = thr; a.T = T;
   const int n_pt = (TK_Q * T + a.SG - 1) / a.SG;  // threshold tiles per query block
   hipLaunchKernelGGL((iset_rank_kernel<BF16, true>), dim3(a.n_qt * n_pt), dim3(256), is_base_lds<BF16>() + TK_G * 4,
@@ -255,19 +252,17 @@ int is_thresholds(const void* q, const void* q_lo, const float* qw, const void* 
 
 // workspace (int32 units): (greater, equal) [NQ][T][n_chunks][2]
 template <bool BF16>
-int is_count(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, const float* iw, int NQ, int NT,
-             int C, int mode, int M, int d, const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
-             int32_t* equal, void* stream) {
+int is_count_body(const MmtSearchScan& s, const float* thr, int T, int32_t* ws, int32_t* greater, int32_t* equal,
+                  void* stream) {
   IsArgs a = {};
   if (T < 1 || T > IS_MAXT) return MMT_ERR_ARG;
-  if (const int rc = is_fill<BF16>(a, q, q_lo, qw, g, gw, iw, NQ, NT, C, mode, M, d, subset, thr && ws && greater && equal))
-    return rc;
+  if (const int rc = is_fill<BF16>(a, s, s.subset, thr && ws && greater && equal)) return rc;
   a.thr = const_cast<float*>(thr); a.cnt = ws; a.T = T;
   is_count_lds_limits<BF16>();
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL((iset_rank_kernel<BF16, false>), dim3(a.n_qt * a.n_chunks), dim3(256),
-                     is_base_lds<BF16>() + is_count_lds(T), s, a);
-  return rk_reduce_launch(a.cnt, (int64_t)NQ * T, a.n_chunks, greater, equal, s);
+                     is_base_lds<BF16>() + is_count_lds(T), st, a);
+  return rk_reduce_launch(a.cnt, (int64_t)s.NQ * T, a.n_chunks, greater, equal, st);
 }
 }  // namespace
 
@@ -281,41 +276,19 @@ extern "C" int64_t mmt_count_itemsets_workspace_ints(int NQ, int NT, int C, int 
   return (int64_t)NQ * T * 2 * (int64_t)is_n_chunks(NQ, NT, C);
 }
 
-extern "C" int mmt_search_topk_itemsets(const float* qf, const float* qw, const float* gf, const float* gw, const float* iw,
-                                        int NQ, int NT, int C, int mode, int M, int d, int k, const uint32_t* subset,
-                                        uint64_t* ws, float* scores, int64_t* index, void* stream) {
-  return is_topk<false>(qf, nullptr, qw, gf, gw, iw, NQ, NT, C, mode, M, d, k, subset, ws, scores, index, stream);
+// The item-set halves of mmt_search_topk, mmt_search_thresholds and mmt_search_count (search.hip, search_rank.hip: the
+// descriptor has passed their gate, so the storage is fp32 or bf16).
+int is_topk(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_t* index, void* stream) {
+  return s.storage == MMT_SEARCH_FP32 ? is_topk_body<false>(s, k, ws, scores, index, stream)
+                                      : is_topk_body<true>(s, k, ws, scores, index, stream);
 }
 
-extern "C" int mmt_search_topk_bf16_itemsets(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                             const float* gw, const float* iw, int NQ, int NT, int C, int mode, int M, int d,
-                                             int k, const uint32_t* subset, uint64_t* ws, float* scores, int64_t* index,
-                                             void* stream) {
-  return is_topk<true>(q_hi, q_lo, qw, gf, gw, iw, NQ, NT, C, mode, M, d, k, subset, ws, scores, index, stream);
+int is_thresholds(const MmtSearchScan& s, const int64_t* targets, int T, float* thr, void* stream) {
+  return s.storage == MMT_SEARCH_FP32 ? is_thresholds_body<false>(s, targets, T, thr, stream)
+                                      : is_thresholds_body<true>(s, targets, T, thr, stream);
 }
 
-extern "C" int mmt_search_thresholds_itemsets(const float* qf, const float* qw, const float* gf, const float* gw,
-                                              const float* iw, int NQ, int NT, int C, int mode, int M, int d,
-                                              const int64_t* targets, int T, float* thr, void* stream) {
-  return is_thresholds<false>(qf, nullptr, qw, gf, gw, iw, NQ, NT, C, mode, M, d, targets, T, thr, stream);
-}
-
-extern "C" int mmt_search_thresholds_bf16_itemsets(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw,
-                                                   const uint16_t* gf, const float* gw, const float* iw, int NQ, int NT, int C,
-                                                   int mode, int M, int d, const int64_t* targets, int T, float* thr,
-                                                   void* stream) {
-  return is_thresholds<true>(q_hi, q_lo, qw, gf, gw, iw, NQ, NT, C, mode, M, d, targets, T, thr, stream);
-}
-
-extern "C" int mmt_search_count_itemsets(const float* qf, const float* qw, const float* gf, const float* gw, const float* iw,
-                                         int NQ, int NT, int C, int mode, int M, int d, const float* thr, int T,
-                                         const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
-  return is_count<false>(qf, nullptr, qw, gf, gw, iw, NQ, NT, C, mode, M, d, thr, T, subset, ws, greater, equal, stream);
-}
-
-extern "C" int mmt_search_count_bf16_itemsets(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                              const float* gw, const float* iw, int NQ, int NT, int C, int mode, int M, int d,
-                                              const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
-                                              int32_t* equal, void* stream) {
-  return is_count<true>(q_hi, q_lo, qw, gf, gw, iw, NQ, NT, C, mode, M, d, thr, T, subset, ws, greater, equal, stream);
+int is_count(const MmtSearchScan& s, const float* thr, int T, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
+  return s.storage == MMT_SEARCH_FP32 ? is_count_body<false>(s, thr, T, ws, greater, equal, stream)
+                                      : is_count_body<true>(s, thr, T, ws, greater, equal, stream);
 }

@@ -81,19 +81,18 @@ __global__ __launch_bounds__(256) void col_lse_fold_kernel(const float2* __restr
 
 namespace {
 template <bool BF16>
-int nm_col_lse(const void* b, const void* b_lo, const float* bw, const void* g, const float* gw, int NB, int NV, int M, int d,
-               float beta, float* ws, float* state, int first, float* lse, void* stream) {
-  if (!b || (BF16 && !b_lo) || !bw || !g || !gw || !ws || !state || !tk_shape_ok(NB, NV, M, d, BF16) || !tk_beta_ok(beta))
+int nm_col_lse(const MmtSearchScan& s, float beta, float* ws, float* state, int first, float* lse, void* stream) {
+  if (!tk_scan_operands<BF16>(s) || !ws || !state || !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16) || !tk_beta_ok(beta))
     return MMT_ERR_ARG;
-  if (((uintptr_t)b | (uintptr_t)b_lo | (uintptr_t)g | (uintptr_t)ws) & 15) return MMT_ERR_ALIGN;
+  if (!tk_scan_aligned(s) || ((uintptr_t)ws & 15)) return MMT_ERR_ALIGN;
   NmArgs a = {};
-  a.q = b; a.q_lo = b_lo; a.qw = bw; a.g = g; a.gw = gw; a.beta = beta;
-  a.NQ = NB; a.NV = NV; a.M = M; a.K = M * d;
+  a.q = s.q; a.q_lo = s.q_lo; a.qw = s.qw; a.g = s.g; a.gw = s.gw; a.beta = beta;
+  a.NQ = s.NQ; a.NV = s.NV; a.M = s.M; a.K = s.M * s.d;
   tk_geometry(a);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(col_lse_kernel<BF16>, dim3(a.n_qt * a.n_chunks), dim3(256), tk_base_lds<BF16>(), s, a, (float2*)ws);
-  hipLaunchKernelGGL(col_lse_fold_kernel, dim3((NV + 255) / 256), dim3(256), 0, s, (const float2*)ws, a.n_qt, NV, state, first,
-                     lse);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(col_lse_kernel<BF16>, dim3(a.n_qt * a.n_chunks), dim3(256), tk_base_lds<BF16>(), st, a, (float2*)ws);
+  hipLaunchKernelGGL(col_lse_fold_kernel, dim3((s.NV + 255) / 256), dim3(256), 0, st, (const float2*)ws, a.n_qt, s.NV, state,
+                     first, lse);
   return (int)hipGetLastError();
 }
 }  // namespace
@@ -103,13 +102,10 @@ extern "C" int64_t mmt_col_lse_workspace_floats(int NB, int NV) {
   return 2 * (int64_t)((NB + TK_Q - 1) / TK_Q) * NV;
 }
 
-extern "C" int mmt_search_col_lse(const float* bf, const float* bw, const float* gf, const float* gw, int NB, int NV, int M,
-                                  int d, float beta, float* ws, float* state, int first, float* lse, void* stream) {
-  return nm_col_lse<false>(bf, nullptr, bw, gf, gw, NB, NV, M, d, beta, ws, state, first, lse, stream);
-}
-
-extern "C" int mmt_search_col_lse_bf16(const uint16_t* b_hi, const uint16_t* b_lo, const float* bw, const uint16_t* gf,
-                                       const float* gw, int NB, int NV, int M, int d, float beta, float* ws, float* state,
-                                       int first, float* lse, void* stream) {
-  return nm_col_lse<true>(b_hi, b_lo, bw, gf, gw, NB, NV, M, d, beta, ws, state, first, lse, stream);
+// The descriptor's own lse and beta stay null / 0 (the gate takes no norm): this operation writes the lse.
+extern "C" int mmt_search_col_lse(const MmtSearchScan* scan, float beta, float* ws, float* state, int first, float* lse,
+                                  void* stream) {
+  if (const int rc = tk_scan_gate(scan, 0)) return rc;
+  return scan->storage == MMT_SEARCH_FP32 ? nm_col_lse<false>(*scan, beta, ws, state, first, lse, stream)
+                                          : nm_col_lse<true>(*scan, beta, ws, state, first, lse, stream);
 }

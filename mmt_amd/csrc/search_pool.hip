@@ -179,20 +179,20 @@ constexpr size_t pl_base_lds() { return tk_base_lds<BF16>() + TK_Q * 4; }
 size_t pl_topk_lds(int sb, int k) { return TK_Q * (4 + 8) + (size_t)sb * (k + 64) * 8; }
 size_t pl_count_lds(int sb, int T) { return (size_t)sb * T * 12; }
 
-// The gate and the fill every entry point shares: 0, or the error code.  `rest`: the entry's other pointers are all
-// there.  q_lo and subset are null where an entry has none.
+// The gate and the fill every entry point shares: 0, or the error code.  `own`: the entry's own pointers are all there.
+// `subset`: the descriptor's, or null for a pass that has none.  The descriptor's NQ rows are NS = NQ / C whole sets.
 template <bool BF16>
-int pl_fill(PlArgs& a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, const float* rw,
-            int NS, int C, int mode, int NV, int M, int d, const uint32_t* subset, bool rest) {
-  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !rw || !rest || !pl_sets_ok(NS, C, mode) ||
-      !tk_shape_ok(NS * C, NV, M, d, BF16))
+int pl_fill(PlArgs& a, const MmtSearchScan& s, const uint32_t* subset, bool own) {
+  const int C = s.set_size, NS = C >= 1 ? s.NQ / C : 0;
+  if (!tk_scan_operands<BF16>(s) || !s.set_weights || !own || !pl_sets_ok(NS, C, s.mode) || s.NQ != NS * C ||
+      !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16))
     return MMT_ERR_ARG;
-  if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
-  a.q = q; a.q_lo = q_lo; a.qw = qw; a.g = g; a.gw = gw; a.rw = rw; a.subset = subset;
-  a.NQ = NS * C; a.NV = NV; a.M = M; a.K = M * d; a.NS = NS; a.C = C; a.SB = TK_Q / C; a.mode = mode;
-  a.chunk = pl_chunk(NS, C, NV);
+  if (((uintptr_t)s.q | (uintptr_t)s.q_lo | (uintptr_t)s.g | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  a.q = s.q; a.q_lo = s.q_lo; a.qw = s.qw; a.g = s.g; a.gw = s.gw; a.rw = s.set_weights; a.subset = subset;
+  a.NQ = s.NQ; a.NV = s.NV; a.M = s.M; a.K = s.M * s.d; a.NS = NS; a.C = C; a.SB = TK_Q / C; a.mode = s.mode;
+  a.chunk = pl_chunk(NS, C, s.NV);
   a.n_qt = pl_blocks(NS, C);
-  a.n_chunks = (NV + a.chunk - 1) / a.chunk;
+  a.n_chunks = (s.NV + a.chunk - 1) / a.chunk;
   return 0;
 }
 
@@ -211,26 +211,23 @@ void pl_count_lds_limits() {
 }
 
 template <bool BF16>
-int pl_topk(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, const float* rw, int NS, int C,
-            int mode, int NV, int M, int d, int k, const uint32_t* subset, uint64_t* ws, float* scores, int64_t* index,
-            void* stream) {
+int pl_topk_body(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_t* index, void* stream) {
   PlArgs a = {};
   if (k < 1 || k > TK_MAXK) return MMT_ERR_ARG;
-  if (const int rc = pl_fill<BF16>(a, q, q_lo, qw, g, gw, rw, NS, C, mode, NV, M, d, subset, ws && index)) return rc;
+  if (const int rc = pl_fill<BF16>(a, s, s.subset, ws && index)) return rc;
   a.ws = ws; a.k = k;
   pl_topk_lds_limits();
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL((pool_topk_kernel<BF16>), dim3(a.n_qt * a.n_chunks), dim3(256),
-                     pl_base_lds<BF16>() + pl_topk_lds(a.SB, k), s, a);
-  return tk_merge_launch(ws, NS, a.n_chunks, k, k < NV ? k : NV, scores, index, s);
+                     pl_base_lds<BF16>() + pl_topk_lds(a.SB, k), st, a);
+  return tk_merge_launch(ws, a.NS, a.n_chunks, k, k < s.NV ? k : s.NV, scores, index, st);
 }
 
 template <bool BF16>
-int pl_thresholds(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, const float* rw, int NS,
-                  int C, int mode, int NV, int M, int d, const int64_t* targets, int T, float* thr, void* stream) {
+int pl_thresholds_body(const MmtSearchScan& s, const int64_t* targets, int T, float* thr, void* stream) {
   PlArgs a = {};
   if (T < 1 || T > PL_MAXT) return MMT_ERR_ARG;
-  if (const int rc = pl_fill<BF16>(a, q, q_lo, qw, g, gw, rw, NS, C, mode, NV, M, d, nullptr, targets && thr)) return rc;
+  if (const int rc = pl_fill<BF16>(a, s, nullptr, targets && thr)) return rc;
   a.targets = targets; a.thr = thr; a.T = T;
   const int n_pt = (a.SB * T + TK_G - 1) / TK_G;  // threshold tiles per query block
   hipLaunchKernelGGL((pool_rank_kernel<BF16, true>), dim3(a.n_qt * n_pt), dim3(256), pl_base_lds<BF16>() + TK_G * 4,
@@ -240,19 +237,17 @@ int pl_thresholds(const void* q, const void* q_lo, const float* qw, const void* 
 
 // workspace (int32 units): (greater, equal) [NS][T][n_chunks][2]
 template <bool BF16>
-int pl_count(const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, const float* rw, int NS, int C,
-             int mode, int NV, int M, int d, const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
-             int32_t* equal, void* stream) {
+int pl_count_body(const MmtSearchScan& s, const float* thr, int T, int32_t* ws, int32_t* greater, int32_t* equal,
+                  void* stream) {
   PlArgs a = {};
   if (T < 1 || T > PL_MAXT) return MMT_ERR_ARG;
-  if (const int rc = pl_fill<BF16>(a, q, q_lo, qw, g, gw, rw, NS, C, mode, NV, M, d, subset, thr && ws && greater && equal))
-    return rc;
+  if (const int rc = pl_fill<BF16>(a, s, s.subset, thr && ws && greater && equal)) return rc;
   a.thr = const_cast<float*>(thr); a.cnt = ws; a.T = T;
   pl_count_lds_limits<BF16>();
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL((pool_rank_kernel<BF16, false>), dim3(a.n_qt * a.n_chunks), dim3(256),
-                     pl_base_lds<BF16>() + pl_count_lds(a.SB, T), s, a);
-  return rk_reduce_launch(a.cnt, (int64_t)NS * T, a.n_chunks, greater, equal, s);
+                     pl_base_lds<BF16>() + pl_count_lds(a.SB, T), st, a);
+  return rk_reduce_launch(a.cnt, (int64_t)a.NS * T, a.n_chunks, greater, equal, st);
 }
 }  // namespace
 
@@ -266,41 +261,19 @@ extern "C" int64_t mmt_count_pooled_workspace_ints(int NS, int C, int NV, int T)
   return (int64_t)NS * T * 2 * (int64_t)pl_n_chunks(NS, C, NV);
 }
 
-extern "C" int mmt_search_topk_pooled(const float* qf, const float* qw, const float* gf, const float* gw, const float* rw,
-                                      int NS, int C, int mode, int NV, int M, int d, int k, const uint32_t* subset,
-                                      uint64_t* ws, float* scores, int64_t* index, void* stream) {
-  return pl_topk<false>(qf, nullptr, qw, gf, gw, rw, NS, C, mode, NV, M, d, k, subset, ws, scores, index, stream);
+// The query-set halves of mmt_search_topk, mmt_search_thresholds and mmt_search_count (search.hip, search_rank.hip: the
+// descriptor has passed their gate, so the storage is fp32 or bf16).
+int pl_topk(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_t* index, void* stream) {
+  return s.storage == MMT_SEARCH_FP32 ? pl_topk_body<false>(s, k, ws, scores, index, stream)
+                                      : pl_topk_body<true>(s, k, ws, scores, index, stream);
 }
 
-extern "C" int mmt_search_topk_bf16_pooled(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                           const float* gw, const float* rw, int NS, int C, int mode, int NV, int M, int d,
-                                           int k, const uint32_t* subset, uint64_t* ws, float* scores, int64_t* index,
-                                           void* stream) {
-  return pl_topk<true>(q_hi, q_lo, qw, gf, gw, rw, NS, C, mode, NV, M, d, k, subset, ws, scores, index, stream);
+int pl_thresholds(const MmtSearchScan& s, const int64_t* targets, int T, float* thr, void* stream) {
+  return s.storage == MMT_SEARCH_FP32 ? pl_thresholds_body<false>(s, targets, T, thr, stream)
+                                      : pl_thresholds_body<true>(s, targets, T, thr, stream);
 }
 
-extern "C" int mmt_search_thresholds_pooled(const float* qf, const float* qw, const float* gf, const float* gw,
-                                            const float* rw, int NS, int C, int mode, int NV, int M, int d,
-                                            const int64_t* targets, int T, float* thr, void* stream) {
-  return pl_thresholds<false>(qf, nullptr, qw, gf, gw, rw, NS, C, mode, NV, M, d, targets, T, thr, stream);
-}
-
-extern "C" int mmt_search_thresholds_bf16_pooled(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw,
-                                                 const uint16_t* gf, const float* gw, const float* rw, int NS, int C, int mode,
-                                                 int NV, int M, int d, const int64_t* targets, int T, float* thr,
-                                                 void* stream) {
-  return pl_thresholds<true>(q_hi, q_lo, qw, gf, gw, rw, NS, C, mode, NV, M, d, targets, T, thr, stream);
-}
-
-extern "C" int mmt_search_count_pooled(const float* qf, const float* qw, const float* gf, const float* gw, const float* rw,
-                                       int NS, int C, int mode, int NV, int M, int d, const float* thr, int T,
-                                       const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
-  return pl_count<false>(qf, nullptr, qw, gf, gw, rw, NS, C, mode, NV, M, d, thr, T, subset, ws, greater, equal, stream);
-}
-
-extern "C" int mmt_search_count_bf16_pooled(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                            const float* gw, const float* rw, int NS, int C, int mode, int NV, int M, int d,
-                                            const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
-                                            int32_t* equal, void* stream) {
-  return pl_count<true>(q_hi, q_lo, qw, gf, gw, rw, NS, C, mode, NV, M, d, thr, T, subset, ws, greater, equal, stream);
+int pl_count(const MmtSearchScan& s, const float* thr, int T, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
+  return s.storage == MMT_SEARCH_FP32 ? pl_count_body<false>(s, thr, T, ws, greater, equal, stream)
+                                      : pl_count_body<true>(s, thr, T, ws, greater, equal, stream);
 }

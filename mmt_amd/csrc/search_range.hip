@@ -152,16 +152,18 @@ __global__ __launch_bounds__(256) void range_offsets_kernel(int32_t* __restrict_
 }
 
 namespace {
-// The gate and the fill of the four entry points: 0, or the error code.  `rest`: the entry's other pointers are all there.
+// The gate and the fill of the two entry points (Args = RgMaskedArgs or RgFp8MaskedArgs): 0, or the error code.  `own`:
+// the entry's other pointers are all there.
 template <bool BF16, class Args>
-int rg_fill(Args& a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV,
-            int M, int d, const float* thr, const uint32_t* subset, const int32_t* ws, bool rest) {
-  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !thr || !ws || !rest ||
-      !tk_shape_ok(NQ, NV, M, d, BF16, TkFp8<Args>::value))
+int rg_fill(Args& a, const MmtSearchScan& s, const float* thr, const int32_t* ws, bool own) {
+  constexpr bool FP8 = TkFp8<Args>::value;
+  if (!tk_scan_operands<BF16, FP8>(s) || !thr || !ws || !own || !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16, FP8))
     return MMT_ERR_ARG;
-  if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
-  a.q = q; a.q_lo = q_lo; a.qw = qw; a.g = g; a.gw = gw; a.thr = thr; a.ws = const_cast<int32_t*>(ws); a.subset = subset;
-  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d;
+  if (!tk_scan_aligned(s)) return MMT_ERR_ALIGN;
+  a.q = s.q; a.q_lo = s.q_lo; a.qw = s.qw; a.g = s.g; a.gw = s.gw; a.thr = thr; a.ws = const_cast<int32_t*>(ws);
+  a.subset = s.subset;
+  if constexpr (FP8) a.gscale = s.gscale;
+  a.NQ = s.NQ; a.NV = s.NV; a.M = s.M; a.K = s.M * s.d;
   tk_geometry(a);
   return 0;
 }
@@ -176,34 +178,24 @@ void rg_launch(const Args& a, hipStream_t s) {
                        tk_base_lds<BF16>(), s, (RgPlain<Args>)a);
 }
 
-// (Args = RgMaskedArgs, or RgFp8MaskedArgs with gscale set by the caller; `rest`: the entry's other pointers are there)
 template <bool BF16, class Args>
-int rg_count(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
-             int d, const float* thr, const uint32_t* subset, bool rest, int32_t* ws, int64_t* row_counts, void* stream) {
-  if (const int rc = rg_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, thr, subset, ws, rest && row_counts != nullptr))
-    return rc;
+int rg_count(const MmtSearchScan& s, const float* thr, int32_t* ws, int64_t* row_counts, void* stream) {
+  Args a = {};
+  if (const int rc = rg_fill<BF16>(a, s, thr, ws, row_counts != nullptr)) return rc;
   rg_launch<BF16, false>(a, (hipStream_t)stream);
-  hipLaunchKernelGGL(range_offsets_kernel, dim3((NQ + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws, NQ, a.n_chunks,
+  hipLaunchKernelGGL(range_offsets_kernel, dim3((s.NQ + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws, s.NQ, a.n_chunks,
                      row_counts);
   return (int)hipGetLastError();
 }
 
 template <bool BF16, class Args>
-int rg_fill_hits(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV,
-                 int M, int d, const float* thr, const uint32_t* subset, bool rest, const int32_t* ws,
-                 const int64_t* offsets, int64_t* indices, float* scores, void* stream) {
-  if (const int rc =
-          rg_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, thr, subset, ws, rest && offsets && indices && scores))
-    return rc;
+int rg_fill_hits(const MmtSearchScan& s, const float* thr, const int32_t* ws, const int64_t* offsets, int64_t* indices,
+                 float* scores, void* stream) {
+  Args a = {};
+  if (const int rc = rg_fill<BF16>(a, s, thr, ws, offsets && indices && scores)) return rc;
   a.offsets = offsets; a.indices = indices; a.scores = scores;
   rg_launch<BF16, true>(a, (hipStream_t)stream);
   return (int)hipGetLastError();
-}
-
-RgFp8MaskedArgs rg_fp8_args(const float* gscale) {
-  RgFp8MaskedArgs a = {};
-  a.gscale = gscale;
-  return a;
 }
 }  // namespace
 
@@ -212,43 +204,33 @@ extern "C" int64_t mmt_range_workspace_ints(int NQ, int NV) {
   return (int64_t)NQ * tk_n_chunks(NQ, NV);
 }
 
-extern "C" int mmt_search_range_count(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
-                                      int M, int d, const float* thr, const uint32_t* subset, int32_t* ws,
-                                      int64_t* row_counts, void* stream) {
-  return rg_count<false>(RgMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, thr, subset, true, ws, row_counts, stream);
+// storage -> the body and its argument block.  The fp8 pair is named last: the kernels lie in the code object in the order
+// of their first use here, and that order stays what it has been (profiles/search_abi_kernel_identity.txt).
+namespace {
+struct RgBodies {
+  int (*count[3])(const MmtSearchScan&, const float*, int32_t*, int64_t*, void*);
+  int (*fill[3])(const MmtSearchScan&, const float*, const int32_t*, const int64_t*, int64_t*, float*, void*);
+};
+const RgBodies kRgBodies = [] {
+  RgBodies b = {};
+  b.count[MMT_SEARCH_FP32] = rg_count<false, RgMaskedArgs>;
+  b.count[MMT_SEARCH_BF16] = rg_count<true, RgMaskedArgs>;
+  b.fill[MMT_SEARCH_FP32] = rg_fill_hits<false, RgMaskedArgs>;
+  b.fill[MMT_SEARCH_BF16] = rg_fill_hits<true, RgMaskedArgs>;
+  b.count[MMT_SEARCH_FP8] = rg_count<true, RgFp8MaskedArgs>;
+  b.fill[MMT_SEARCH_FP8] = rg_fill_hits<true, RgFp8MaskedArgs>;
+  return b;
+}();
+}  // namespace
+
+extern "C" int mmt_search_range_count(const MmtSearchScan* scan, const float* thr, int32_t* ws, int64_t* row_counts,
+                                      void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_SUBSET | SC_FP8)) return rc;
+  return kRgBodies.count[scan->storage](*scan, thr, ws, row_counts, stream);
 }
 
-extern "C" int mmt_search_range_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                           const float* gw, int NQ, int NV, int M, int d, const float* thr,
-                                           const uint32_t* subset, int32_t* ws, int64_t* row_counts, void* stream) {
-  return rg_count<true>(RgMaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, true, ws, row_counts, stream);
-}
-
-extern "C" int mmt_search_range_fill(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
-                                     int M, int d, const float* thr, const uint32_t* subset, const int32_t* ws,
-                                     const int64_t* offsets, int64_t* indices, float* scores, void* stream) {
-  return rg_fill_hits<false>(RgMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, thr, subset, true, ws, offsets, indices, scores, stream);
-}
-
-extern "C" int mmt_search_range_fill_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                          const float* gw, int NQ, int NV, int M, int d, const float* thr,
-                                          const uint32_t* subset, const int32_t* ws, const int64_t* offsets,
-                                          int64_t* indices, float* scores, void* stream) {
-  return rg_fill_hits<true>(RgMaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, true, ws, offsets, indices, scores, stream);
-}
-
-extern "C" int mmt_search_range_count_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
-                                          const float* gw, const float* gscale, int NQ, int NV, int M, int d,
-                                          const float* thr, const uint32_t* subset, int32_t* ws, int64_t* row_counts,
-                                          void* stream) {
-  return rg_count<true>(rg_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, gscale != nullptr, ws,
-                        row_counts, stream);
-}
-
-extern "C" int mmt_search_range_fill_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
-                                         const float* gw, const float* gscale, int NQ, int NV, int M, int d, const float* thr,
-                                         const uint32_t* subset, const int32_t* ws, const int64_t* offsets, int64_t* indices,
-                                         float* scores, void* stream) {
-  return rg_fill_hits<true>(rg_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, subset, gscale != nullptr, ws,
-                            offsets, indices, scores, stream);
+extern "C" int mmt_search_range_fill(const MmtSearchScan* scan, const float* thr, const int32_t* ws, const int64_t* offsets,
+                                     int64_t* indices, float* scores, void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_SUBSET | SC_FP8)) return rc;
+  return kRgBodies.fill[scan->storage](*scan, thr, ws, offsets, indices, scores, stream);
 }

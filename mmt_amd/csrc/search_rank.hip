@@ -23,7 +23,7 @@
 // 4 KiB query weights + 24 KiB thresholds and counters, against the 97 KiB of candidate lists of the top-k kernel at
 // k = 128; registers: the top-k kernel's K loop plus four counters.
 //
-// rank_kernel<BF16, false, RkMaskedArgs> is the masked count pass (mmt_search_rank_ex): only items whose bit is set in a packed
+// rank_kernel<BF16, false, RkMaskedArgs> is the masked count pass (mmt_search_rank [subset]): only items whose bit is set in a packed
 // bitmap (search_subset.hip) are counted -- the live-column predicate ANDed with the tile's 128 bits, one block-uniform
 // 16-byte load per tile, and a tile without a set bit skipped before its K loop.  Thresholds and the reduce are the
 // unmasked ones, so a target outside the subset is still scored; it just does not count itself.
@@ -32,7 +32,7 @@
 // reduce against given thresholds: the same instantiations with the same argument blocks.  A gallery cut into shards
 // scores a target where it is stored and counts it on every shard (search.py: ShardedVideoIndex); the int32 counts add.
 //
-// rank_kernel<BF16, THR, NmRankArgs> (mmt_search_thresholds_norm / mmt_search_count_norm) is the same pair of passes on
+// rank_kernel<BF16, THR, NmRankArgs> (mmt_search_thresholds [lse] / mmt_search_count [lse]) is the same pair of passes on
 // the querybank-normalised score' (search_norm.hip): the tile is rewritten by tk_tile_norm before it is read, the subset
 // of the count pass is a pointer that may be null.  rank_kernel is ONE body, generic over its argument block, which says
 // how the subset and the normalisation enter (kMask, kNorm: search_scan.h); the blocks stay separate types because a
@@ -167,18 +167,19 @@ int rk_reduce_launch(const int32_t* cnt, int64_t n, int n_chunks, int32_t* great
 namespace {
 bool rk_args_ok(int NQ, int NV, int T) { return NQ > 0 && NV > 0 && T >= 1 && T <= RK_MAXT; }
 
-// The gate and the fill every entry point shares (Args = RkMaskedArgs or NmRankArgs): 0, or the error code.  `rest`: the
-// entry's other pointers are all there (and, normalised, its beta is in range).  q_lo and subset are null where an entry
-// has none.
+// The gate and the fill every entry point shares (Args = RkMaskedArgs, RkFp8MaskedArgs or NmRankArgs): 0, or the error
+// code.  `own`: the entry's own pointers are all there.  `subset`: the descriptor's, or null for a pass that has none.
 template <bool BF16, class Args>
-int rk_fill(Args& a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
-            int d, int T, const uint32_t* subset, bool rest) {
-  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !rest || !rk_args_ok(NQ, NV, T) ||
-      !tk_shape_ok(NQ, NV, M, d, BF16, TkFp8<Args>::value))
+int rk_fill(Args& a, const MmtSearchScan& s, int T, const uint32_t* subset, bool own) {
+  constexpr bool FP8 = TkFp8<Args>::value;
+  if (!tk_scan_operands<BF16, FP8, Args::kNorm>(s) || !own || !rk_args_ok(s.NQ, s.NV, T) ||
+      !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16, FP8))
     return MMT_ERR_ARG;
-  if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
-  a.q = q; a.q_lo = q_lo; a.qw = qw; a.g = g; a.gw = gw; a.subset = subset;
-  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.T = T;
+  if (((uintptr_t)s.q | (uintptr_t)s.q_lo | (uintptr_t)s.g | (uintptr_t)subset) & 15) return MMT_ERR_ALIGN;
+  a.q = s.q; a.q_lo = s.q_lo; a.qw = s.qw; a.g = s.g; a.gw = s.gw; a.subset = subset;
+  if constexpr (FP8) a.gscale = s.gscale;
+  if constexpr (Args::kNorm) { a.beta = s.beta; a.lse = s.lse; }
+  a.NQ = s.NQ; a.NV = s.NV; a.M = s.M; a.K = s.M * s.d; a.T = T;
   tk_geometry(a);
   return 0;
 }
@@ -219,25 +220,24 @@ int rk_launch_count(const Args& a, int32_t* greater, int32_t* equal, hipStream_t
 }
 
 // workspace (int32 units): thresholds [NQ][T] fp32, then (greater, equal) [NQ][T][n_chunks][2]
-// (Args = RkMaskedArgs, or RkFp8MaskedArgs with gscale set by the caller)
+// (Args = RkMaskedArgs or RkFp8MaskedArgs)
 template <bool BF16, class Args>
-int rk_rank(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
-            int d, const int64_t* targets, int T, const uint32_t* subset, bool rest, int32_t* ws, int32_t* greater,
-            int32_t* equal, void* stream) {
-  if (const int rc = rk_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, T, subset, rest && targets && ws && greater && equal))
-    return rc;
-  a.targets = targets; a.thr = (float*)ws; a.cnt = ws + (int64_t)NQ * T;
+int rk_rank(const MmtSearchScan& s, const int64_t* targets, int T, int32_t* ws, int32_t* greater, int32_t* equal,
+            void* stream) {
+  Args a = {};
+  if (const int rc = rk_fill<BF16>(a, s, T, s.subset, targets && ws && greater && equal)) return rc;
+  a.targets = targets; a.thr = (float*)ws; a.cnt = ws + (int64_t)s.NQ * T;
   rk_launch_thresholds<BF16>(a, (hipStream_t)stream);
   return rk_launch_count<BF16>(a, greater, equal, (hipStream_t)stream);
 }
 
 // The two halves on their own (a gallery cut into shards scores a target on the shard that holds it and counts it on every
-// shard: search.py, ShardedVideoIndex), plain (Args = RkMaskedArgs) or normalised (NmRankArgs, lse and beta set by the
-// caller): the same kernels, launched as above.
+// shard: search.py, ShardedVideoIndex), plain (Args = RkMaskedArgs, RkFp8MaskedArgs) or normalised (NmRankArgs): the same
+// kernels, launched as above.
 template <bool BF16, class Args>
-int rk_thresholds(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV,
-                  int M, int d, const int64_t* targets, int T, bool rest, float* thr, void* stream) {
-  if (const int rc = rk_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, T, nullptr, rest && targets && thr)) return rc;
+int rk_thresholds(const MmtSearchScan& s, const int64_t* targets, int T, float* thr, void* stream) {
+  Args a = {};
+  if (const int rc = rk_fill<BF16>(a, s, T, nullptr, targets && thr)) return rc;
   a.targets = targets; a.thr = thr;
   rk_launch_thresholds<BF16>(a, (hipStream_t)stream);
   return (int)hipGetLastError();
@@ -245,25 +245,11 @@ int rk_thresholds(Args a, const void* q, const void* q_lo, const float* qw, cons
 
 // workspace (int32 units): (greater, equal) [NQ][T][n_chunks][2]
 template <bool BF16, class Args>
-int rk_count(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
-             int d, const float* thr, int T, const uint32_t* subset, bool rest, int32_t* ws, int32_t* greater,
-             int32_t* equal, void* stream) {
-  if (const int rc = rk_fill<BF16>(a, q, q_lo, qw, g, gw, NQ, NV, M, d, T, subset, rest && thr && ws && greater && equal))
-    return rc;
+int rk_count(const MmtSearchScan& s, const float* thr, int T, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
+  Args a = {};
+  if (const int rc = rk_fill<BF16>(a, s, T, s.subset, thr && ws && greater && equal)) return rc;
   a.thr = const_cast<float*>(thr); a.cnt = ws;
   return rk_launch_count<BF16>(a, greater, equal, (hipStream_t)stream);
-}
-
-NmRankArgs nm_rank_args(float beta, const float* lse) {
-  NmRankArgs a = {};
-  a.beta = beta; a.lse = lse;
-  return a;
-}
-
-RkFp8MaskedArgs rk_fp8_args(const float* gscale) {
-  RkFp8MaskedArgs a = {};
-  a.gscale = gscale;
-  return a;
 }
 }  // namespace
 
@@ -272,117 +258,47 @@ extern "C" int64_t mmt_rank_workspace_ints(int NQ, int NV, int T) {
   return (int64_t)NQ * T * (1 + 2 * (int64_t)tk_n_chunks(NQ, NV));
 }
 
-extern "C" int mmt_search_rank_ex(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
-                                  int d, const int64_t* targets, int T, const uint32_t* subset, int32_t* ws,
-                                  int32_t* greater, int32_t* equal, void* stream) {
-  return rk_rank<false>(RkMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, targets, T, subset, true, ws, greater, equal, stream);
-}
-
-extern "C" int mmt_search_rank(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
-                               int d, const int64_t* targets, int T, int32_t* ws, int32_t* greater, int32_t* equal,
-                               void* stream) {
-  return rk_rank<false>(RkMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, targets, T, nullptr, true, ws, greater, equal, stream);
-}
-
-extern "C" int mmt_search_rank_bf16_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                       const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T,
-                                       const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal,
-                                       void* stream) {
-  return rk_rank<true>(RkMaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, subset, true, ws, greater, equal, stream);
-}
-
-extern "C" int mmt_search_rank_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                    const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T,
-                                    int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
-  return rk_rank<true>(RkMaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, nullptr, true, ws, greater, equal, stream);
-}
-
-extern "C" int mmt_search_rank_fp8_ex(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
-                                      const float* gw, const float* gscale, int NQ, int NV, int M, int d,
-                                      const int64_t* targets, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
-                                      int32_t* equal, void* stream) {
-  return rk_rank<true>(rk_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, subset, gscale != nullptr, ws,
-                       greater, equal, stream);
-}
-
-extern "C" int mmt_search_rank_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
-                                   const float* gw, const float* gscale, int NQ, int NV, int M, int d, const int64_t* targets,
-                                   int T, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
-  return rk_rank<true>(rk_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, nullptr, gscale != nullptr, ws,
-                       greater, equal, stream);
-}
-
 extern "C" int64_t mmt_count_workspace_ints(int NQ, int NV, int T) {
   if (!rk_args_ok(NQ, NV, T)) return MMT_ERR_ARG;
   return (int64_t)NQ * T * 2 * (int64_t)tk_n_chunks(NQ, NV);
 }
 
-extern "C" int mmt_search_thresholds(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
-                                     int M, int d, const int64_t* targets, int T, float* thr, void* stream) {
-  return rk_thresholds<false>(RkMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, targets, T, true, thr, stream);
+// (storage, norm, sets) -> the body and its argument block, for each of the three entries.
+extern "C" int mmt_search_rank(const MmtSearchScan* scan, const int64_t* targets, int T, int32_t* ws, int32_t* greater,
+                               int32_t* equal, void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_SUBSET | SC_FP8)) return rc;
+  switch (scan->storage) {
+    case MMT_SEARCH_FP32: return rk_rank<false, RkMaskedArgs>(*scan, targets, T, ws, greater, equal, stream);
+    case MMT_SEARCH_BF16: return rk_rank<true, RkMaskedArgs>(*scan, targets, T, ws, greater, equal, stream);
+    default: return rk_rank<true, RkFp8MaskedArgs>(*scan, targets, T, ws, greater, equal, stream);
+  }
 }
 
-extern "C" int mmt_search_thresholds_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                          const float* gw, int NQ, int NV, int M, int d, const int64_t* targets, int T,
-                                          float* thr, void* stream) {
-  return rk_thresholds<true>(RkMaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, true, thr, stream);
+extern "C" int mmt_search_thresholds(const MmtSearchScan* scan, const int64_t* targets, int T, float* thr, void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_NORM | SC_QSETS | SC_ISETS | SC_FP8)) return rc;
+  const MmtSearchScan& s = *scan;
+  const unsigned p = tk_scan_parts(s);
+  if (p & SC_QSETS) return pl_thresholds(s, targets, T, thr, stream);
+  if (p & SC_ISETS) return is_thresholds(s, targets, T, thr, stream);
+  if (p & SC_FP8) return rk_thresholds<true, RkFp8MaskedArgs>(s, targets, T, thr, stream);
+  if (s.storage == MMT_SEARCH_FP32)
+    return p & SC_NORM ? rk_thresholds<false, NmRankArgs>(s, targets, T, thr, stream)
+                       : rk_thresholds<false, RkMaskedArgs>(s, targets, T, thr, stream);
+  return p & SC_NORM ? rk_thresholds<true, NmRankArgs>(s, targets, T, thr, stream)
+                     : rk_thresholds<true, RkMaskedArgs>(s, targets, T, thr, stream);
 }
 
-extern "C" int mmt_search_count(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
-                                int d, const float* thr, int T, const uint32_t* subset, int32_t* ws, int32_t* greater,
+extern "C" int mmt_search_count(const MmtSearchScan* scan, const float* thr, int T, int32_t* ws, int32_t* greater,
                                 int32_t* equal, void* stream) {
-  return rk_count<false>(RkMaskedArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, thr, T, subset, true, ws, greater, equal,
-                         stream);
-}
-
-extern "C" int mmt_search_count_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                     const float* gw, int NQ, int NV, int M, int d, const float* thr, int T,
-                                     const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
-  return rk_count<true>(RkMaskedArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, T, subset, true, ws, greater, equal,
-                        stream);
-}
-
-extern "C" int mmt_search_thresholds_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
-                                         const float* gw, const float* gscale, int NQ, int NV, int M, int d,
-                                         const int64_t* targets, int T, float* thr, void* stream) {
-  return rk_thresholds<true>(rk_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T, gscale != nullptr, thr,
-                             stream);
-}
-
-extern "C" int mmt_search_count_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
-                                    const float* gw, const float* gscale, int NQ, int NV, int M, int d, const float* thr,
-                                    int T, const uint32_t* subset, int32_t* ws, int32_t* greater, int32_t* equal,
-                                    void* stream) {
-  return rk_count<true>(rk_fp8_args(gscale), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, T, subset, gscale != nullptr, ws,
-                        greater, equal, stream);
-}
-
-extern "C" int mmt_search_thresholds_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
-                                          int M, int d, const int64_t* targets, int T, float beta, const float* lse,
-                                          float* thr, void* stream) {
-  return rk_thresholds<false>(nm_rank_args(beta, lse), qf, nullptr, qw, gf, gw, NQ, NV, M, d, targets, T,
-                              lse && tk_beta_ok(beta), thr, stream);
-}
-
-extern "C" int mmt_search_thresholds_bf16_norm(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw,
-                                               const uint16_t* gf, const float* gw, int NQ, int NV, int M, int d,
-                                               const int64_t* targets, int T, float beta, const float* lse, float* thr,
-                                               void* stream) {
-  return rk_thresholds<true>(nm_rank_args(beta, lse), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, targets, T,
-                             lse && tk_beta_ok(beta), thr, stream);
-}
-
-extern "C" int mmt_search_count_norm(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV,
-                                     int M, int d, const float* thr, int T, const uint32_t* subset, float beta,
-                                     const float* lse, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
-  return rk_count<false>(nm_rank_args(beta, lse), qf, nullptr, qw, gf, gw, NQ, NV, M, d, thr, T, subset,
-                         lse && tk_beta_ok(beta), ws, greater, equal, stream);
-}
-
-extern "C" int mmt_search_count_bf16_norm(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                          const float* gw, int NQ, int NV, int M, int d, const float* thr, int T,
-                                          const uint32_t* subset, float beta, const float* lse, int32_t* ws,
-                                          int32_t* greater, int32_t* equal, void* stream) {
-  return rk_count<true>(nm_rank_args(beta, lse), q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, thr, T, subset,
-                        lse && tk_beta_ok(beta), ws, greater, equal, stream);
+  if (const int rc = tk_scan_gate(scan, SC_SUBSET | SC_NORM | SC_QSETS | SC_ISETS | SC_FP8)) return rc;
+  const MmtSearchScan& s = *scan;
+  const unsigned p = tk_scan_parts(s);
+  if (p & SC_QSETS) return pl_count(s, thr, T, ws, greater, equal, stream);
+  if (p & SC_ISETS) return is_count(s, thr, T, ws, greater, equal, stream);
+  if (p & SC_FP8) return rk_count<true, RkFp8MaskedArgs>(s, thr, T, ws, greater, equal, stream);
+  if (s.storage == MMT_SEARCH_FP32)
+    return p & SC_NORM ? rk_count<false, NmRankArgs>(s, thr, T, ws, greater, equal, stream)
+                       : rk_count<false, RkMaskedArgs>(s, thr, T, ws, greater, equal, stream);
+  return p & SC_NORM ? rk_count<true, NmRankArgs>(s, thr, T, ws, greater, equal, stream)
+                     : rk_count<true, RkMaskedArgs>(s, thr, T, ws, greater, equal, stream);
 }

@@ -120,23 +120,26 @@ bool rs_sizes_ok(int NQ, int C) {
 }
 
 template <bool BF16, class Args>
-int rs_rescore(Args a, const void* q, const void* q_lo, const float* qw, const void* g, const float* gw, int NQ, int NV, int M,
-               int d, const int64_t* candidates, int C, int k, bool rest, uint64_t* ws, float* scores, int64_t* index,
+int rs_rescore(const MmtSearchScan& s, const int64_t* candidates, int C, int k, uint64_t* ws, float* scores, int64_t* index,
                void* stream) {
-  if (!q || (BF16 && !q_lo) || !qw || !g || !gw || !rest || !candidates || !ws || !scores || !index || !rs_sizes_ok(NQ, C) ||
-      k < 1 || k > TK_MAXK || !tk_shape_ok(NQ, NV, M, d, BF16, TkFp8<Args>::value))
+  constexpr bool FP8 = TkFp8<Args>::value;
+  if (!tk_scan_operands<BF16, FP8>(s) || !candidates || !ws || !scores || !index || !rs_sizes_ok(s.NQ, C) || k < 1 ||
+      k > TK_MAXK || !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16, FP8))
     return MMT_ERR_ARG;
-  if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)g) & 15) return MMT_ERR_ALIGN;
-  a.q = q; a.q_lo = q_lo; a.qw = qw; a.g = g; a.gw = gw; a.candidates = candidates; a.keys = ws;
-  a.NQ = NQ; a.NV = NV; a.M = M; a.K = M * d; a.C = C; a.n_qt = (NQ + TK_Q - 1) / TK_Q;
-  const hipStream_t s = (hipStream_t)stream;
+  if (!tk_scan_aligned(s)) return MMT_ERR_ALIGN;  // (no subset here: the gate of the entry refused one)
+  Args a = {};
+  a.q = s.q; a.q_lo = s.q_lo; a.qw = s.qw; a.g = s.g; a.gw = s.gw; a.candidates = candidates; a.keys = ws;
+  if constexpr (FP8) a.gscale = s.gscale;
+  a.NQ = s.NQ; a.NV = s.NV; a.M = s.M; a.K = s.M * s.d; a.C = C; a.n_qt = (s.NQ + TK_Q - 1) / TK_Q;
+  const hipStream_t st = (hipStream_t)stream;
   const int n_pt = (TK_Q * C + TK_G - 1) / TK_G;  // pair tiles per query tile
-  hipLaunchKernelGGL((rescore_score_kernel<BF16, Args>), dim3(a.n_qt * n_pt), dim3(256), tk_base_lds<BF16>() + TK_G * 4, s, a);
+  hipLaunchKernelGGL((rescore_score_kernel<BF16, Args>), dim3(a.n_qt * n_pt), dim3(256), tk_base_lds<BF16>() + TK_G * 4, st, a);
   if (const int rc = (int)hipGetLastError()) return rc;
   int P = 1;
   while (P < C) P <<= 1;
   const int threads = P / 2 < 64 ? 64 : P / 2 > 256 ? 256 : P / 2;
-  hipLaunchKernelGGL(rescore_select_kernel, dim3(NQ), dim3(threads), (size_t)P * 8, s, ws, C, P, k < C ? k : C, scores, index);
+  hipLaunchKernelGGL(rescore_select_kernel, dim3(s.NQ), dim3(threads), (size_t)P * 8, st, ws, C, P, k < C ? k : C, scores,
+                     index);
   return (int)hipGetLastError();
 }
 }  // namespace
@@ -146,24 +149,12 @@ extern "C" int64_t mmt_rescore_workspace_keys(int NQ, int C) {
   return (int64_t)NQ * C;
 }
 
-extern "C" int mmt_search_rescore(const float* qf, const float* qw, const float* gf, const float* gw, int NQ, int NV, int M,
-                                  int d, const int64_t* candidates, int C, int k, uint64_t* ws, float* scores,
-                                  int64_t* index, void* stream) {
-  return rs_rescore<false>(RsArgs{}, qf, nullptr, qw, gf, gw, NQ, NV, M, d, candidates, C, k, true, ws, scores, index, stream);
-}
-
-extern "C" int mmt_search_rescore_bf16(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint16_t* gf,
-                                       const float* gw, int NQ, int NV, int M, int d, const int64_t* candidates, int C, int k,
-                                       uint64_t* ws, float* scores, int64_t* index, void* stream) {
-  return rs_rescore<true>(RsArgs{}, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, candidates, C, k, true, ws, scores, index, stream);
-}
-
-extern "C" int mmt_search_rescore_fp8(const uint16_t* q_hi, const uint16_t* q_lo, const float* qw, const uint8_t* gf,
-                                      const float* gw, const float* gscale, int NQ, int NV, int M, int d,
-                                      const int64_t* candidates, int C, int k, uint64_t* ws, float* scores, int64_t* index,
-                                      void* stream) {
-  RsFp8Args a = {};
-  a.gscale = gscale;
-  return rs_rescore<true>(a, q_hi, q_lo, qw, gf, gw, NQ, NV, M, d, candidates, C, k, gscale != nullptr, ws, scores, index,
-                          stream);
+extern "C" int mmt_search_rescore(const MmtSearchScan* scan, const int64_t* candidates, int C, int k, uint64_t* ws,
+                                  float* scores, int64_t* index, void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_FP8)) return rc;
+  switch (scan->storage) {
+    case MMT_SEARCH_FP32: return rs_rescore<false, RsArgs>(*scan, candidates, C, k, ws, scores, index, stream);
+    case MMT_SEARCH_BF16: return rs_rescore<true, RsArgs>(*scan, candidates, C, k, ws, scores, index, stream);
+    default: return rs_rescore<true, RsFp8Args>(*scan, candidates, C, k, ws, scores, index, stream);
+  }
 }

@@ -559,3 +559,46 @@ inline void tk_lds_limits(bool (&done)[64], std::initializer_list<TkLdsLimit> ke
     (void)hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes);
   if (known) done[dev] = true;
 }
+
+// The descriptor of a scan (mmt_hip.h: MmtSearchScan) on the host.  Its optional parts as bits: what an entry point says
+// it has kernels for, and what its dispatch to a body's template arguments switches on.
+enum : unsigned { SC_SUBSET = 1, SC_EXCLUDE = 2, SC_AFTER = 4, SC_NORM = 8, SC_QSETS = 16, SC_ISETS = 32, SC_FP8 = 64 };
+
+inline unsigned tk_scan_parts(const MmtSearchScan& s) {
+  return (s.subset ? SC_SUBSET : 0) | (s.exclude || s.E ? SC_EXCLUDE : 0) | (s.after ? SC_AFTER : 0) |
+         (s.lse || s.beta != 0.f ? SC_NORM : 0) | (s.sets == MMT_SEARCH_SETS_QUERY ? SC_QSETS : 0) |
+         (s.sets == MMT_SEARCH_SETS_ITEM ? SC_ISETS : 0) | (s.storage == MMT_SEARCH_FP8 ? SC_FP8 : 0);
+}
+
+// The gate every scan entry point opens with: 0, or MMT_ERR_ARG for a null descriptor, an unknown tag, a part outside
+// `takes` (what the operation has kernels for), a combination no kernel exists for, or a field set whose part is absent.
+inline int tk_scan_gate(const MmtSearchScan* s, unsigned takes) {
+  if (!s || (unsigned)s->storage > MMT_SEARCH_FP8 || (unsigned)s->sets > MMT_SEARCH_SETS_ITEM) return MMT_ERR_ARG;
+  const unsigned p = tk_scan_parts(*s), sets = p & (SC_QSETS | SC_ISETS);
+  if (p & ~takes) return MMT_ERR_ARG;
+  if ((p & SC_FP8) && (p & SC_NORM || sets)) return MMT_ERR_ARG;
+  if (sets && (p & (SC_NORM | SC_EXCLUDE | SC_AFTER))) return MMT_ERR_ARG;
+  if ((s->storage == MMT_SEARCH_FP32 && s->q_lo) || (!(p & SC_FP8) && s->gscale)) return MMT_ERR_ARG;
+  if (!sets && (s->set_size || s->mode || s->set_weights)) return MMT_ERR_ARG;
+  return 0;
+}
+
+// The operands a body with these template arguments reads are all there (the norm's beta in range).
+template <bool BF16, bool FP8 = false, bool NORM = false>
+bool tk_scan_operands(const MmtSearchScan& s) {
+  return s.q && (!BF16 || s.q_lo) && s.qw && s.g && s.gw && (!FP8 || s.gscale) && (!NORM || (s.lse && tk_beta_ok(s.beta)));
+}
+
+// Query rows, gallery rows and subset words on 16-byte boundaries (null is aligned).
+inline bool tk_scan_aligned(const MmtSearchScan& s) {
+  return !(((uintptr_t)s.q | (uintptr_t)s.q_lo | (uintptr_t)s.g | (uintptr_t)s.subset) & 15);
+}
+
+// The scans of a gallery or of queries in sets (search_pool.hip, search_itemset.hip) behind mmt_search_topk,
+// mmt_search_thresholds and mmt_search_count: the descriptor has passed tk_scan_gate and carries that kind of sets.
+int pl_topk(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
+int pl_thresholds(const MmtSearchScan& s, const int64_t* targets, int T, float* thr, void* stream);
+int pl_count(const MmtSearchScan& s, const float* thr, int T, int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
+int is_topk(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
+int is_thresholds(const MmtSearchScan& s, const int64_t* targets, int T, float* thr, void* stream);
+int is_count(const MmtSearchScan& s, const float* thr, int T, int32_t* ws, int32_t* greater, int32_t* equal, void* stream);

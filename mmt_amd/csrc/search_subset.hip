@@ -1,4 +1,4 @@
-// The item bitmap of the masked scans (search.py: VideoIndex.subset; mmt_search_topk_ex, mmt_search_rank_ex and their
+// The item bitmap of the masked scans (search.py: VideoIndex.subset; mmt_search_topk [subset, exclude], mmt_search_rank [subset] and their
 // bf16 forms): bit i & 31 of word i >> 5 is item i.  The word count is padded to a multiple of 4, so the 128 bits of one
 // scan tile (TK_G = 128 columns, tiles start at multiples of 128) are one aligned 16-byte load; bits at or past NV are 0.
 //

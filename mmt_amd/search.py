@@ -9,7 +9,10 @@ The score is the 'indep' similarity of model/model.py:789-837 (the matrix `metri
 It is symmetric, so video-to-text search is an index of captions queried with videos.  Each query gets min(k, NV)
 (score, index) pairs, best first, equal scores by ascending gallery index.  One launch scores 64-query x 4096-video
 blocks on the matrix cores and keeps a running top-k per query; a second merges the chunk lists (mmt_search_topk).
-Results are bit-reproducible.
+Results are bit-reproducible.  Every scan goes to one of nine C entry points with one descriptor, MmtSearchScan
+(include/mmt_hip.h; built per row batch by VideoIndex._describe): the storage, the operands and whatever of subset,
+exclusions, cursor, norm and sets the call has.  Below, `mmt_search_topk [lse, after]` stands for "that entry with those
+parts of the descriptor set".
 
     index = VideoIndex(vid_embds, vid_weights, dtype=torch.bfloat16)    # half the bytes per item (d % 8 == 0)
     index = VideoIndex.empty(capacity, M, d, device, dtype=...)         # preallocated, filled in pieces:
@@ -18,7 +21,7 @@ Results are bit-reproducible.
 
 A bfloat16 index stores bf16(gw (.) G), the fp32 fold rounded once to nearest-even; the weights stay fp32 and the queries
 are NOT rounded to 8 bits: score(q, g) = <fold_fp32(Q, qw)[q], dequant(stored[g])> / sum_m qw gw, computed on the bf16
-matrix cores with the query split into hi = bf16(qf) and lo = bf16(qf - hi) (mmt_search_topk_bf16; within 1e-5 of the
+matrix cores with the query split into hi = bf16(qf) and lo = bf16(qf - hi) (mmt_search_topk [bf16]; within 1e-5 of the
 fp64 value of that definition).  Against the float32 index a score moves by at most
 2^-8 * sum_m qw gw <|Q_m|, |G_m|> / sum_m qw gw, i.e. 2^-8 for unit-norm rows.
 
@@ -35,7 +38,7 @@ whose scores then mean nothing, and no other item.  As for bfloat16 only the sto
 the stored value:
     score(q, g) = fl(fl(acc * scale[g]) / den),   acc = <fold_fp32(Q, qw)[q], dequant(stored[g])>,   den = sum_m qw gw
 (0 -> 1e-5), acc computed as on a bfloat16 index -- every e4m3 value is a bf16 value, so the gallery is widened exactly on
-its way to the bf16 matrix cores and the query is the same hi / lo pair (mmt_search_topk_fp8; within 1e-5 of the fp64 value
+its way to the bf16 matrix cores and the query is the same hi / lo pair (mmt_search_topk [fp8]; within 1e-5 of the fp64 value
 of that definition); the scale being a power of two, where it is multiplied in cannot change the bits.  Against the float32
 index only the gallery rounding differs:
     |score_fp8 - score_fp32| <= (2^-4 * <|qf|, |f|> + 2^-10 * scale[g] * sum_k |qf[k]|) / |den|  + 1e-5
@@ -65,7 +68,7 @@ gives 0 / 0 and rank +inf.  metric.retrieval_metrics_indexed builds the t2v / v2
 One stored corpus answers for any subset of its items -- a test cut, the real captions of a padded set -- without a
 gathered copy: the subset is packed once into a bitmap (bit i & 31 of word i >> 5 is item i; mmt_search_subset_pack) and
 reused across calls; the scan skips every 128-item tile that holds no allowed item and otherwise only declines to select
-(or count) the items whose bit is clear (mmt_search_topk_ex, mmt_search_rank_ex).  Indices stay the original item
+(or count) the items whose bit is clear (mmt_search_topk [subset, exclude], mmt_search_rank [subset]).  Indices stay the original item
 numbers and a returned score has the bits plain `search` gives that item.  `exclude` ([NQ] or [NQ, E <= 32] int64, -1 =
 none) bars items per query -- "the k best videos for this caption, not counting its own" -- and a query left with fewer
 than k' candidates gets (-inf, -1) in the remaining slots.  subset=None and exclude=None take the unmasked calls.
@@ -140,7 +143,7 @@ merge_caption_similiarities = 'avg', model/model.py:826-831: the mean of the cap
 clips (max over the clips), a caption and its paraphrases (mean), "any of these captions" (max).  The score is not linear in
 the query -- its denominator sum_m qw[q][m] gw[g][m] depends on the pair -- so the rows cannot be averaged before the scan,
 and per-row top-k lists cannot be merged exactly (a set's best item need not be in any member's list): the pooling happens
-on the score tile, inside the kernel (mmt_search_topk_pooled, mmt_search_thresholds_pooled, mmt_search_count_pooled).  The
+on the score tile, inside the kernel (mmt_search_topk [query sets], mmt_search_thresholds [query sets], mmt_search_count [query sets]).  The
 queries are num_sets * set_size rows (either layout of `search`; the text layout (B, M, C, d) / (B, C, M) is sets of C
 already), set s is rows s * set_size .. s * set_size + set_size - 1, 1 <= set_size <= MAX_SET = 64.  Every row has a weight
 rw[r] (float32, finite; default float32(1 / set_size)); a row with rw[r] == 0 takes no part at all -- a padded caption --
@@ -167,8 +170,8 @@ captions, C per video, queried with a video for "the k videos whose captions mat
 reference's 'avg' mode), a clip gallery ranked by the mean, not the best, of each video's clips.  `search_groups` collapses
 a gallery by its best member; it cannot give a mean and gives no ranks.  The denominator of the score depends on the pair,
 so the C items of a set cannot be averaged into one when the index is built, and per-item top-k lists cannot be merged into
-set means: the pooling happens on the score tile (mmt_search_topk_itemsets, mmt_search_thresholds_itemsets,
-mmt_search_count_itemsets).  The stored items are num_items / set_size sets, set t is items t * set_size .. t * set_size +
+set means: the pooling happens on the score tile (mmt_search_topk [item sets], mmt_search_thresholds [item sets],
+mmt_search_count [item sets]).  The stored items are num_items / set_size sets, set t is items t * set_size .. t * set_size +
 set_size - 1, 1 <= set_size <= MAX_ITEM_SET = 128 (one 128-column tile holds whole sets), num_items % set_size == 0.
 Every item has a weight iw[g] (float32, finite; default float32(1 / set_size)); an item with iw[g] == 0 takes no part and
 every set has an item that does.  With s_g = score(q, g), the bits the plain scan gives the pair, and g0 < g1 < ... the
@@ -211,7 +214,7 @@ The eighth question: the k best items that come AFTER a given position in `searc
 through it a sorted list deeper than MAX_K.  `search`'s order (score descending, -0 tied with +0, equal scores by ascending
 item) totally orders a query's candidates, so a position is a (score, item) pair -- one key of the scans -- and "everything
 strictly after it" is one more compare at selection time, on the score tile the scan computes anyway
-(mmt_search_topk_after; exclude= holds 32 items and range_search needs a threshold nobody knows in advance).  A cursor row
+(mmt_search_topk [after]; exclude= holds 32 items and range_search needs a threshold nobody knows in advance).  A cursor row
 (a_scores[q], a_items[q]) with a_items[q] >= 0 admits the items g with score(q, g) < a_scores[q], or an equal score (-0 as
 +0) and g > a_items[q]; it need not be the position of a stored or allowed item.  (+inf, -1) is no cursor, (-inf, -1) is
 exhausted -- the vacant slot of an earlier page -- so after=(scores[:, -1], indices[:, -1]) of the page before is always
@@ -222,6 +225,7 @@ taken without the cursor, so every page of a query makes the same choice); not w
 `search_groups` has no cursor.  `search_deep` is host code: ceil(w / page) pages of `search`, w = min(depth, candidates),
 each continuing from the last column of the one before, concatenated to [NQ, w].
 """
+import ctypes
 import math
 
 import torch
@@ -241,7 +245,11 @@ _BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 byt
 _MAX_HITS = 1 << 27  # default cap of a range search's total: a guard against a mistyped threshold, not a tuned number
 FP8 = torch.float8_e4m3fn
 _DTYPES = {torch.float32: 4, torch.bfloat16: 8, FP8: 16}  # storage dtype -> multiple d must have (16-byte folded rows)
-_ENTRY_TAGS = {torch.float32: '', torch.bfloat16: '_bf16', FP8: '_fp8'}  # storage dtype -> its part of an entry point's name
+_STORAGE = {torch.float32: _lib.SEARCH_FP32, torch.bfloat16: _lib.SEARCH_BF16, FP8: _lib.SEARCH_FP8}  # MmtSearchScan.storage
+# sets tag of a scan -> the workspace-size functions of its top-k and its count pass
+_WORKSPACES = {_lib.SEARCH_SETS_NONE: ('mmt_topk_workspace_keys', 'mmt_count_workspace_ints'),
+               _lib.SEARCH_SETS_QUERY: ('mmt_topk_pooled_workspace_keys', 'mmt_count_pooled_workspace_ints'),
+               _lib.SEARCH_SETS_ITEM: ('mmt_topk_itemsets_workspace_keys', 'mmt_count_itemsets_workspace_ints')}
 
 
 def _cuda_f32(x, name):
@@ -583,8 +591,9 @@ class _Scan:
   def __init__(self, subset=None, ex=None, norm=None, pooling=None, item_pooling=None, after=None):
     self.subset, self.ex, self.norm, self.pooling, self.item_pooling = subset, ex, norm, pooling, item_pooling
     self.after = after
-    # which family of entry points scans it: '' stands for the plain, _ex and _norm forms
-    self.kind = '_itemsets' if item_pooling is not None else '_pooled' if pooling is not None else ''
+    # MmtSearchScan.sets: whose rows come in sets
+    self.sets = (_lib.SEARCH_SETS_ITEM if item_pooling is not None else
+                 _lib.SEARCH_SETS_QUERY if pooling is not None else _lib.SEARCH_SETS_NONE)
 
   def plain(self):
     """The same candidates without the norm, the cursor kept: the result the dynamic rule falls back to."""
@@ -615,12 +624,9 @@ class _Scan:
     """The gallery columns the chunk estimates of the batches count."""
     return index.num_items if self.item_pooling is None else self.item_pooling._columns
 
-  def words(self):
-    return ops._p(None if self.subset is None else self.subset.words)
-
-  def norm_args(self):
-    """The trailing (beta, lse) of the _norm entry points."""
-    return () if self.norm is None else (self.norm.beta, ops._p(self.norm.lse))
+  def scored(self):
+    """What a threshold pass takes of it: how a pair is scored, not which items are candidates."""
+    return _Scan(norm=self.norm, pooling=self.pooling, item_pooling=self.item_pooling)
 
   def shard(self, s, index):
     """Shard s's view of it on the ShardedVideoIndex `index`: its part of the subset, the norm and the item pooling (None
@@ -886,13 +892,13 @@ class _Index:
     -1 .. num_items - 1 (-1 = none; duplicates and items outside the subset are fine): items barred for that query; its
     range is checked as that of `rank_counts`' targets, before anything is scored.  A query with fewer than k' candidates
     left gets score -inf and index -1 in the remaining slots.  norm (from this index's `hub_norm`): the ranking and the
-    returned scores are those of score' (mmt_search_topk_norm); with a norm that has `hubs`, only the queries whose plain
+    returned scores are those of score' (mmt_search_topk [lse]); with a norm that has `hubs`, only the queries whose plain
     top-1 candidate is a hub are normalised and the others keep their plain result (dynamic=False normalises every query).
     pooling (from `pooling`): the queries are pooling.num_sets sets of pooling.set_size rows and the outputs have one row
-    per SET: the k' best items by the set's pooled score (module docstring; mmt_search_topk_pooled), ranked and tied as
+    per SET: the k' best items by the set's pooled score (module docstring; mmt_search_topk [query sets]), ranked and tied as
     above; a returned score is the pooled value with -0 as +0.  pooling= does not combine with exclude= or norm=.
     item_pooling (from `item_pooling`): the STORED items are sets and the indices are set numbers: per query the k' best
-    sets by the set's pooled score (mmt_search_topk_itemsets), k' = min(k, num_sets) or min(k, subset.count) with a subset
+    sets by the set's pooled score (mmt_search_topk [item sets]), k' = min(k, num_sets) or min(k, subset.count) with a subset
     from item_pooling.subset; does not combine with pooling=, exclude= or norm=.
     ShardedVideoIndex: every shard searches its own items for its best min(k', its candidates), with its part of the
     subset and the norm; the lists are copied to the primary and merged there in one launch.  With a pooling every shard
@@ -912,7 +918,7 @@ class _Index:
     row with fewer than k' items left holds (-inf, -1) in the remaining slots.  A score has the bits the call without
     `after` gives the pair, and for every k and cursor the row is the slice that starts right behind the position in the
     complete ordered list of the query's candidates -- whatever the row batching, the launch geometry or the shards (the
-    cursor is one more compare at selection time, on the keys the scan orders by: mmt_search_topk_after).  Combines
+    cursor is one more compare at selection time, on the keys the scan orders by: mmt_search_topk [after]).  Combines
     with subset=, exclude=, norm= and dynamic=; under the dynamic rule a query's plain top-1 is taken WITHOUT the cursor,
     so the choice is the same on every page.  after= with pooling= or item_pooling= is a ValueError; `search_groups` has
     no cursor (a group's representative may lie before a position while other members lie after it).  after=None takes
@@ -964,13 +970,13 @@ class _Index:
     targets is checked here (one small reduction and a host sync); nothing is scored before it passes.  subset: only its
     items are counted; a target outside it is still scored but does not count itself, so its `equal` may be 0.  norm: the
     counts are those of score' -- the target's score' from the threshold pass, then the count pass against it
-    (mmt_search_thresholds_norm, mmt_search_count_norm); with a norm that has `hubs` only the queries whose plain top-1
+    (mmt_search_thresholds [lse], mmt_search_count [lse]); with a norm that has `hubs` only the queries whose plain top-1
     candidate is a hub, the others keep their plain counts (dynamic=False normalises every query).  pooling (from
     `pooling`): targets [NS] or [NS, T], one row per SET; the counts are those of the set's pooled score -- the target's
-    pooled value from the threshold pass, then the count pass against it (mmt_search_thresholds_pooled,
-    mmt_search_count_pooled), so a target counts itself; not with norm=.  item_pooling (from `item_pooling`): targets are
+    pooled value from the threshold pass, then the count pass against it (mmt_search_thresholds [query sets],
+    mmt_search_count [query sets]), so a target counts itself; not with norm=.  item_pooling (from `item_pooling`): targets are
     SET numbers -1 .. num_sets - 1 and the counts are over the sets, by the set's pooled score
-    (mmt_search_thresholds_itemsets, mmt_search_count_itemsets); a target counts itself; a subset is one of sets.
+    (mmt_search_thresholds [item sets], mmt_search_count [item sets]); a target counts itself; a subset is one of sets.
     ShardedVideoIndex: each
     shard scores the targets it holds, the primary picks the owner's value per (query, target), each shard counts its
     items against those thresholds and the int32 counts are summed on the primary."""
@@ -1259,27 +1265,43 @@ class VideoIndex(_Index):
     grouping.num_groups: the width of the three outputs.  Nothing here waits for the device."""
     return self._search(q, qw, k, _Scan(subset), grouping)
 
-  def _entry(self, op, variant=''):
-    """The C entry point of a scan over this index's storage: op 'topk', 'topk_groups', 'rank', 'thresholds', 'count',
-    'range_count', 'range_fill', 'rescore' or 'col_lse'; variant '' (plain), '_ex' (subset / exclusions), '_norm', '_after' / '_norm_after' (a cursor), '_pooled' or '_itemsets' -> (the
-    function, its name)."""
-    name = 'mmt_search_%s%s%s' % (op, _ENTRY_TAGS[self.dtype], variant)
-    return getattr(_lib.lib(), name), name
-
-  def _operands(self, q, qw):
-    """The query and gallery operands of the scan entry points for one batch of rows: the fp32 fold, or its bf16 hi / lo
-    pair (a bfloat16 or float8_e4m3fn index; the latter's gallery operands end with the scales).  Returns (pointers, the
-    tensors they point into)."""
-    n, m, d = q.shape
-    L = _lib.lib()
+  def _describe(self, scan, q, qw, r0, r1, bounds=None):
+    """The MmtSearchScan of `scan` over this index for query rows r0 .. r1 - 1 (with a pooling: whole sets): the rows
+    folded -- fp32, or the bf16 hi / lo pair of a bfloat16 or float8_e4m3fn index -- the stored rows, and every part the
+    scan has, so a caller hands over a _Scan holding only what its operation takes.  bounds: the cursor's keys [NQ] of
+    the whole call.  -> (the descriptor, by reference; the sizes its workspace-size function takes; the range of result
+    rows the batch writes -- its rows, or its sets; the tensors the descriptor points into, to be kept until the call
+    is made).  Fields are given in the struct's order: the cheapest way to fill a ctypes.Structure."""
+    qb, wb = q[r0:r1], qw[r0:r1]
+    n, m, d = qb.shape
+    nv, c, mode, sw, dims, rows = self.num_items, 0, 0, None, None, (r0, r1)
     if self.dtype != torch.float32:
-      hl = torch.empty(2, n, m * d, device=self.device, dtype=torch.bfloat16)  # hi = bf16(qf), lo = bf16(qf - hi)
-      check(L.mmt_search_fold_split_bf16(ops._p(q), ops._p(qw), n, m, d, ops._p(hl[0]), ops._p(hl[1]), ops._stream()),
-            'mmt_search_fold_split_bf16')
-      scales = () if self.scales is None else (ops._p(self.scales),)
-      return (ops._p(hl[0]), ops._p(hl[1]), ops._p(qw), ops._p(self.folded), ops._p(self.weights)) + scales, hl
-    qf = _fold(q, qw)
-    return (ops._p(qf), ops._p(qw), ops._p(self.folded), ops._p(self.weights)), qf
+      keep = torch.empty(2, n, m * d, device=self.device, dtype=torch.bfloat16)  # hi = bf16(qf), lo = bf16(qf - hi)
+      check(_lib.lib().mmt_search_fold_split_bf16(ops._p(qb), ops._p(wb), n, m, d, ops._p(keep[0]), ops._p(keep[1]),
+                                                  ops._stream()), 'mmt_search_fold_split_bf16')
+      q_hi, q_lo = keep[0].data_ptr(), keep[1].data_ptr()
+    else:
+      keep = _fold(qb, wb)
+      q_hi, q_lo = keep.data_ptr(), None
+    if scan.item_pooling is not None:
+      ip = scan.item_pooling
+      nv, c, mode, sw, dims = ip.num_sets * ip.set_size, ip.set_size, _POOL_MODES[ip.mode], ip.weights, (n, ip.num_sets, ip.set_size)
+    elif scan.pooling is not None:
+      pool, c = scan.pooling, scan.pooling.set_size
+      n = n // c * c
+      mode, sw, dims, rows = _POOL_MODES[pool.mode], pool._on(self.device)[r0:r1], (n // c, c, nv), (r0 // c, r1 // c)
+    ex, norm = scan.ex, scan.norm
+    desc = _lib.MmtSearchScan(
+        q_hi, q_lo, wb.data_ptr(), self.folded.data_ptr(), self.weights.data_ptr(),
+        None if self.scales is None else self.scales.data_ptr(),
+        None if scan.subset is None else scan.subset.words.data_ptr(),
+        None if ex is None else ex[r0:r1].data_ptr(),
+        None if bounds is None else bounds[r0:r1].data_ptr(),
+        None if norm is None else norm.lse.data_ptr(),
+        None if sw is None else sw.data_ptr(),
+        _STORAGE[self.dtype], n, nv, m, d, 0 if ex is None else ex.shape[1], 0.0 if norm is None else norm.beta,
+        scan.sets, c, mode)
+    return ctypes.byref(desc), dims or (n, nv), rows, (desc, keep, wb, sw)
 
   def _row_batches(self, nq, extra, pooling=None):
     """Row ranges of a scan: a multiple of 64 rows (the query block) whose folded rows (4 bytes per element, fp32 or the
@@ -1304,117 +1326,87 @@ class VideoIndex(_Index):
   def _col_lse(self, b, bw, beta):
     """`hub_norm` behind its checks: b (NB, M, d) / bw (NB, M) fp32 on the index device -> lse fp32 [num_items].  The bank
     goes through in batches of whole 64-row blocks; the running (M, S) pair per item carries from one to the next."""
-    nb, nv, m, d = b.shape[0], self.num_items, self.num_experts, self.dim
-    fn, name = self._entry('col_lse')
+    nb, nv = b.shape[0], self.num_items
+    L, nothing = _lib.lib(), _Scan()
     with torch.cuda.device(self.device):
       lse = torch.empty(nv, device=self.device, dtype=torch.float32)
       state = torch.empty(2, nv, device=self.device, dtype=torch.float32)
       # a row's share of the block's (m, p) pairs: 8 bytes per item / 64 rows
       batches = self._row_batches(nb, -(-nv // 8))
-      ws = torch.empty(_lib.lib().mmt_col_lse_workspace_floats(batches[0][1], nv), device=self.device, dtype=torch.float32)
+      ws = torch.empty(L.mmt_col_lse_workspace_floats(batches[0][1], nv), device=self.device, dtype=torch.float32)
       for r0, r1 in batches:
-        operands, _keep = self._operands(b[r0:r1], bw[r0:r1])
-        check(fn(*operands, r1 - r0, nv, m, d, beta, ops._p(ws), ops._p(state), int(r0 == 0),
-                 ops._p(lse if r1 == nb else None), ops._stream()), name)
+        desc, _, _, _keep = self._describe(nothing, b, bw, r0, r1)
+        check(L.mmt_search_col_lse(desc, beta, ops._p(ws), ops._p(state), int(r0 == 0), ops._p(lse if r1 == nb else None),
+                                   ops._stream()), 'mmt_search_col_lse')
     return lse
-
-  def _sizes(self, scan, r0, r1):
-    """What differs between the entry points of the three kinds for query rows r0 .. r1 - 1 (with a pooling: whole sets) ->
-    (their size arguments in their order, a pooled kind's led by its weights; those of them its workspace-size functions
-    take; the range of result rows the batch writes: its rows, or its sets)."""
-    n, nv = r1 - r0, self.num_items
-    if scan.item_pooling is not None:
-      ip = scan.item_pooling
-      dims = (n, ip.num_sets, ip.set_size)
-      return (ops._p(ip.weights),) + dims + (_POOL_MODES[ip.mode],), dims, (r0, r1)
-    if scan.pooling is not None:
-      pool, c = scan.pooling, scan.pooling.set_size
-      return ((ops._p(pool._on(self.device)[r0:r1]), n // c, c, _POOL_MODES[pool.mode], nv), (n // c, c, nv),
-              (r0 // c, r1 // c))
-    return (n, nv), (n, nv), (r0, r1)
 
   def _search(self, q, qw, k, scan, grouping=None):
     """The top-k pass of `search` and `search_groups` behind their argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the
     index device, the scan's parts this index's own -> (scores, indices), with a grouping (scores, groups, items), one
     row per query or query set, min(k, the candidates) wide (a grouping: k).  The unmasked plain scan is handed k as it
     is and writes min(k, NV) columns; only with exclusions or a cursor can a slot stay without a candidate, so only
-    then are the outputs filled beforehand.  A cursor goes through the _after / _norm_after entries: its bounds are built
-    once, on the device (mmt_search_after_keys), and sliced per row batch next to the exclusions.  Nothing here waits
-    for the device."""
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    then are the outputs filled beforehand.  A cursor's bounds are built once, on the device (mmt_search_after_keys),
+    and sliced per row batch next to the exclusions.  Nothing here waits for the device."""
+    nq, nv, L = q.shape[0], self.num_items, _lib.lib()
     paged = scan.after is not None
     masked = scan.subset is not None or scan.ex is not None or paged
-    if grouping is None and (masked or scan.kind):
+    if grouping is None and (masked or scan.sets):
       k = min(k, scan.candidates(self))  # lists no longer than the candidates: the outputs stay dense
     outs = _lists(2 if grouping is None else 3, self.device, scan.rows(q), min(k, nv), vacant=scan.ex is not None or paged)
     if nq == 0:
       return outs
-    if grouping is not None:
-      fn, name = self._entry('topk_groups')
-    else:
-      variant = scan.kind or ('_norm' if scan.norm is not None else '_after' if paged else '_ex' if masked else '')
-      fn, name = self._entry('topk', variant + ('_after' if paged and scan.norm is not None else ''))
-    workspace = getattr(_lib.lib(), 'mmt_topk%s_workspace_keys' % scan.kind)
+    workspace = getattr(L, _WORKSPACES[scan.sets][0])
+    bounds = None
     with torch.cuda.device(self.device):
       if paged:
         a_scores, first = (t.contiguous() for t in scan.after)
         bounds = torch.empty(nq, device=self.device, dtype=torch.int64)   # uint64 keys
-        check(_lib.lib().mmt_search_after_keys(ops._p(a_scores), ops._p(first), nq, ops._p(bounds), ops._stream()),
+        check(L.mmt_search_after_keys(ops._p(a_scores), ops._p(first), nq, ops._p(bounds), ops._stream()),
               'mmt_search_after_keys')
       # a row's (pooled: a set's) chunk lists at full-size chunks
       for r0, r1 in self._row_batches(nq, 8 * k * -(-scan.columns(self) // 4096), scan.pooling):
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        sizes, dims, (o0, o1) = self._sizes(scan, r0, r1)
-        if grouping is not None:
-          extra = (ops._p(grouping.ids), scan.words())
-        elif scan.kind:
-          extra = (scan.words(),)
-        elif masked or scan.norm is not None:  # _ex and _norm: subset words, the batch's exclusions, E; then beta, lse
-          extra = (scan.words(), ops._p(None if scan.ex is None else scan.ex[r0:r1]),
-                   0 if scan.ex is None else scan.ex.shape[1]) + scan.norm_args()
-          if paged:
-            extra += (ops._p(bounds[r0:r1]),)
-        else:
-          extra = ()
+        desc, dims, (o0, o1), _keep = self._describe(scan, q, qw, r0, r1, bounds)
         ws = torch.empty(workspace(*dims, k), device=self.device, dtype=torch.int64)
-        check(fn(*operands, *sizes, m, d, k, *extra, ops._p(ws), *[ops._p(o[o0:o1]) for o in outs], ops._stream()), name)
+        if grouping is None:
+          check(L.mmt_search_topk(desc, k, ops._p(ws), ops._p(outs[0][o0:o1]), ops._p(outs[1][o0:o1]), ops._stream()),
+                'mmt_search_topk')
+        else:
+          check(L.mmt_search_topk_groups(desc, k, ops._p(grouping.ids), ops._p(ws), ops._p(outs[0][o0:o1]),
+                                         ops._p(outs[1][o0:o1]), ops._p(outs[2][o0:o1]), ops._stream()),
+                'mmt_search_topk_groups')
     return outs
 
   def _rescore(self, q, qw, cand, k):
     """`rescore` behind its checks: q (NQ >= 1, M, d) / qw (NQ, M) fp32 and cand int64 [NQ, C] (contiguous, item numbers,
     one outside 0 .. num_items - 1 = none) on the index device, 1 <= k <= min(C, MAX_K): the width of the outputs.  One
     call and one workspace of C keys per row for every row batch.  Nothing here waits for the device."""
-    nq, nv, m, d, c = q.shape[0], self.num_items, self.num_experts, self.dim, cand.shape[1]
+    nq, c, L, nothing = q.shape[0], cand.shape[1], _lib.lib(), _Scan()
     outs = _lists(2, self.device, nq, k)
-    fn, name = self._entry('rescore')
     with torch.cuda.device(self.device):
       for r0, r1 in self._row_batches(nq, 8 * c):
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        ws = torch.empty(_lib.lib().mmt_rescore_workspace_keys(r1 - r0, c), device=self.device, dtype=torch.int64)
-        check(fn(*operands, r1 - r0, nv, m, d, ops._p(cand[r0:r1]), c, k, ops._p(ws), *[ops._p(o[r0:r1]) for o in outs],
-                 ops._stream()), name)
+        desc, _, _, _keep = self._describe(nothing, q, qw, r0, r1)
+        ws = torch.empty(L.mmt_rescore_workspace_keys(r1 - r0, c), device=self.device, dtype=torch.int64)
+        check(L.mmt_search_rescore(desc, ops._p(cand[r0:r1]), c, k, ops._p(ws), ops._p(outs[0][r0:r1]),
+                                   ops._p(outs[1][r0:r1]), ops._stream()), 'mmt_search_rescore')
     return outs
 
   def _rank_counts(self, q, qw, tg, scan):
     """`rank_counts` behind its checks: tg int64 [NQ >= 1, T] on the index device (with a pooling [num_sets, T], with an
     item pooling set numbers) -> (greater, equal) int32 of its shape.  Plain: the threshold and the count pass in one
     call per batch (mmt_search_rank); with a norm, a pooling or an item pooling: one after the other."""
-    if scan.norm is not None or scan.kind:
+    if scan.norm is not None or scan.sets:
       return self._threshold_counts(q, qw, self._target_scores(q, qw, tg, scan), scan)
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
+    nq, nv, L = q.shape[0], self.num_items, _lib.lib()
     greater = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
     equal = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
-    fn, name = self._entry('rank', '' if scan.subset is None else '_ex')
-    words = () if scan.subset is None else (scan.words(),)
     t_max = min(MAX_T, tg.shape[1])
     with torch.cuda.device(self.device):
       for r0, r1 in self._batches(nq, t_max):
-        n = r1 - r0
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        ws = torch.empty(_lib.lib().mmt_rank_workspace_ints(n, nv, t_max), device=self.device, dtype=torch.int32)
+        desc, _, _, _keep = self._describe(scan, q, qw, r0, r1)
+        ws = torch.empty(L.mmt_rank_workspace_ints(r1 - r0, nv, t_max), device=self.device, dtype=torch.int32)
         for tgs, (gs, es) in _column_groups(tg, (greater, equal), r0, r1):
-          check(fn(*operands, n, nv, m, d, ops._p(tgs), tgs.shape[1], *words, ops._p(ws), ops._p(gs), ops._p(es),
-                   ops._stream()), name)
+          check(L.mmt_search_rank(desc, ops._p(tgs), tgs.shape[1], ops._p(ws), ops._p(gs), ops._p(es), ops._stream()),
+                'mmt_search_rank')
     return greater, equal
 
   def target_scores(self, embds, weights, targets, norm=None, dynamic=None, pooling=None, item_pooling=None):
@@ -1423,9 +1415,9 @@ class VideoIndex(_Index):
     own: mmt_search_thresholds), NaN where the target is -1.  norm (VideoIndex.hub_norm): score'(q, targets[q, t]), with
     the bits `search(norm=)` returns; the dynamic rule as there, the plain top-1 taken over all items.  pooling (from
     `pooling`; not with norm=): targets [NS] or [NS, T], one row per query SET -> the set's pooled score of the target with
-    the bits the pooled scans compute for the pair, as they are (a -0 stays -0; mmt_search_thresholds_pooled).
+    the bits the pooled scans compute for the pair, as they are (a -0 stays -0; mmt_search_thresholds [query sets]).
     item_pooling (from `item_pooling`; not with norm= or pooling=): targets are SET numbers -> the query's pooled score of
-    the target set, likewise as it is (mmt_search_thresholds_itemsets)."""
+    the target set, likewise as it is (mmt_search_thresholds [item sets])."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
@@ -1443,18 +1435,16 @@ class VideoIndex(_Index):
     """The threshold pass behind the checks: targets int64 [R] or [R, T] on the index device, R the scan's result rows,
     item numbers (with an item pooling: set numbers); one outside 0 .. the last of them gives NaN.  The scan's subset
     plays no part: a target is scored wherever it lies.  Nothing here waits for the device."""
-    nq, m, d = q.shape[0], self.num_experts, self.dim
+    nq, L, scored = q.shape[0], _lib.lib(), scan.scored()
     tg = targets.reshape(scan.rows(q), -1).contiguous()
     thr = torch.empty(tg.shape, device=self.device, dtype=torch.float32)
     if nq == 0:
       return thr.reshape(targets.shape)
-    fn, name = self._entry('thresholds', scan.kind or ('' if scan.norm is None else '_norm'))
     with torch.cuda.device(self.device):
       for r0, r1 in self._batches(nq, min(MAX_T, tg.shape[1]), scan.pooling, scan.columns(self)):
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        sizes, _, (o0, o1) = self._sizes(scan, r0, r1)
+        desc, _, (o0, o1), _keep = self._describe(scored, q, qw, r0, r1)
         for tgs, (out,) in _column_groups(tg, (thr,), o0, o1):
-          check(fn(*operands, *sizes, m, d, ops._p(tgs), tgs.shape[1], *scan.norm_args(), ops._p(out), ops._stream()), name)
+          check(L.mmt_search_thresholds(desc, ops._p(tgs), tgs.shape[1], ops._p(out), ops._stream()), 'mmt_search_thresholds')
     return thr.reshape(targets.shape)
 
   def threshold_counts(self, embds, weights, thresholds, subset=None, norm=None, dynamic=None, pooling=None,
@@ -1463,10 +1453,10 @@ class VideoIndex(_Index):
     thresholds' shape: how many stored items score above / exactly equal to thresholds[q, t] for query q (plain float
     compares; a NaN threshold counts nothing) -- the count pass of `rank_counts` against given values (mmt_search_count).
     Fed with `target_scores` it gives `rank_counts`.  subset: only its items are counted.  norm (VideoIndex.hub_norm): the
-    items' score' is what is compared (mmt_search_count_norm); the dynamic rule as in `rank_counts`.  pooling (from
+    items' score' is what is compared (mmt_search_count [lse]); the dynamic rule as in `rank_counts`.  pooling (from
     `pooling`; not with norm=): thresholds [NS] or [NS, T], one row per query SET; the items' pooled score for the set is
-    what is compared (mmt_search_count_pooled).  item_pooling (from `item_pooling`; not with norm= or pooling=): the
-    SETS' pooled scores for the query are what is compared and counted (mmt_search_count_itemsets)."""
+    what is compared (mmt_search_count [query sets]).  item_pooling (from `item_pooling`; not with norm= or pooling=): the
+    SETS' pooled scores for the query are what is compared and counted (mmt_search_count [item sets])."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     if not torch.is_tensor(thresholds) or thresholds.dtype != torch.float32:
@@ -1487,23 +1477,21 @@ class VideoIndex(_Index):
   def _threshold_counts(self, q, qw, thresholds, scan):
     """The count pass behind the checks: thresholds float32 [R] or [R, T] on the index device, R the scan's result rows ->
     (greater, equal) int32 of their shape, over the scan's candidates.  Nothing here waits for the device."""
-    nq, m, d = q.shape[0], self.num_experts, self.dim
+    nq, L = q.shape[0], _lib.lib()
     thr = thresholds.reshape(scan.rows(q), -1).contiguous()
     greater = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
     equal = torch.empty(thr.shape, device=self.device, dtype=torch.int32)
     if nq == 0:
       return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
-    fn, name = self._entry('count', scan.kind or ('' if scan.norm is None else '_norm'))
-    workspace = getattr(_lib.lib(), 'mmt_count%s_workspace_ints' % scan.kind)
+    workspace = getattr(L, _WORKSPACES[scan.sets][1])
     t_max = min(MAX_T, thr.shape[1])
     with torch.cuda.device(self.device):
       for r0, r1 in self._batches(nq, t_max, scan.pooling, scan.columns(self)):
-        operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-        sizes, dims, (o0, o1) = self._sizes(scan, r0, r1)
+        desc, dims, (o0, o1), _keep = self._describe(scan, q, qw, r0, r1)
         ws = torch.empty(workspace(*dims, t_max), device=self.device, dtype=torch.int32)
         for ts, (gs, es) in _column_groups(thr, (greater, equal), o0, o1):
-          check(fn(*operands, *sizes, m, d, ops._p(ts), ts.shape[1], scan.words(), *scan.norm_args(), ops._p(ws), ops._p(gs),
-                   ops._p(es), ops._stream()), name)
+          check(L.mmt_search_count(desc, ops._p(ts), ts.shape[1], ops._p(ws), ops._p(gs), ops._p(es), ops._stream()),
+                'mmt_search_count')
     return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
 
   def range_search(self, embds, weights, threshold, subset=None, order='index', max_hits=_MAX_HITS):
@@ -1543,30 +1531,25 @@ class VideoIndex(_Index):
   def _range_count(self, q, qw, thr, subset):
     """The count pass of `range_search` behind its checks, batch by batch -> (hits per query int64 [NQ], the batches'
     workspaces as the fill pass wants them).  Nothing here waits for the device."""
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    fn, name = self._entry('range_count')
-    words = None if subset is None else subset.words
+    nq, nv, L, scan = q.shape[0], self.num_items, _lib.lib(), _Scan(subset)
     counts = torch.empty(nq, device=self.device, dtype=torch.int64)
     kept = []
     for r0, r1 in self._batches(nq, 1):
-      n = r1 - r0
-      operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-      ws = torch.empty(_lib.lib().mmt_range_workspace_ints(n, nv), device=self.device, dtype=torch.int32)
-      check(fn(*operands, n, nv, m, d, ops._p(thr[r0:r1]), ops._p(words), ops._p(ws), ops._p(counts[r0:r1]), ops._stream()),
-            name)
+      desc, _, _, _keep = self._describe(scan, q, qw, r0, r1)
+      ws = torch.empty(L.mmt_range_workspace_ints(r1 - r0, nv), device=self.device, dtype=torch.int32)
+      check(L.mmt_search_range_count(desc, ops._p(thr[r0:r1]), ops._p(ws), ops._p(counts[r0:r1]), ops._stream()),
+            'mmt_search_range_count')
       kept.append(ws)
     return counts, kept
 
   def _range_fill(self, q, qw, thr, subset, kept, offsets, indices, scores):
     """The fill pass of `range_search`: `kept` from `_range_count` of the same arguments, offsets int64 [NQ + 1] into
     indices / scores."""
-    nq, nv, m, d = q.shape[0], self.num_items, self.num_experts, self.dim
-    fn, name = self._entry('range_fill')
-    words = None if subset is None else subset.words
-    for (r0, r1), ws in zip(self._batches(nq, 1), kept):
-      operands, _keep = self._operands(q[r0:r1], qw[r0:r1])
-      check(fn(*operands, r1 - r0, nv, m, d, ops._p(thr[r0:r1]), ops._p(words), ops._p(ws), ops._p(offsets[r0:r1 + 1]),
-               ops._p(indices), ops._p(scores), ops._stream()), name)
+    L, scan = _lib.lib(), _Scan(subset)
+    for (r0, r1), ws in zip(self._batches(q.shape[0], 1), kept):
+      desc, _, _, _keep = self._describe(scan, q, qw, r0, r1)
+      check(L.mmt_search_range_fill(desc, ops._p(thr[r0:r1]), ops._p(ws), ops._p(offsets[r0:r1 + 1]), ops._p(indices),
+                                    ops._p(scores), ops._stream()), 'mmt_search_range_fill')
 
 
 MAX_SHARDS = 32  # lists per query of the merge kernel

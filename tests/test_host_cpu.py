@@ -34,7 +34,7 @@ def test_library_exports_every_declared_symbol_and_bindings_match():
     assert name in _lib.SIGNATURES, 'no ctypes signature for ' + name
     assert len(_lib.SIGNATURES[name][1]) == nargs, 'arity mismatch for ' + name
   assert set(_lib.SIGNATURES) == set(decl)
-  assert _lib.lib().mmt_abi_version() == 5
+  assert _lib.lib().mmt_abi_version() == 6
   # struct layouts agree with the C side (sizes are what the kernels are compiled against)
   assert ctypes.sizeof(_lib.MmtEpilogue) == 128  # + dot_src / lddot / dot_out (r04), live_rows_hint (r06)
   assert ctypes.sizeof(_lib.MmtPackItem) == 48
@@ -43,6 +43,7 @@ def test_library_exports_every_declared_symbol_and_bindings_match():
   assert ctypes.sizeof(_lib.MmtBertBatch) == 112  # + side_stream (r03), live_rows_hint (r06)
   assert ctypes.sizeof(_lib.MmtVideoFront) == 8 + 6 * 4 + 11 * 8  # experts | M B T pack max_pos do_cast | 11 pointers
   assert ctypes.sizeof(_lib.MmtTextHeadsOpts) == 16 + 4 * 8          # + video_front (r03)
+  assert ctypes.sizeof(_lib.MmtSearchScan) == 11 * 8 + 10 * 4        # the descriptor of the gallery scans (ABI 6)
 
 
 def test_graphed_step_refuses_the_removed_adam_riders():

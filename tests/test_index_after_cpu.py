@@ -14,11 +14,7 @@ import torch
 from tests.test_index_groups_cpu import _hollow_index, _hollow_sharded, _key, best_first
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_EXPORTS = {'mmt_search_after_keys': 5, 'mmt_search_topk_after': 17, 'mmt_search_topk_bf16_after': 18,
-               'mmt_search_topk_fp8_after': 19, 'mmt_search_topk_norm_after': 19, 'mmt_search_topk_bf16_norm_after': 20}
-PARENTS = {'mmt_search_topk_after': 'mmt_search_topk_ex', 'mmt_search_topk_bf16_after': 'mmt_search_topk_bf16_ex',
-           'mmt_search_topk_fp8_after': 'mmt_search_topk_fp8_ex', 'mmt_search_topk_norm_after': 'mmt_search_topk_norm',
-           'mmt_search_topk_bf16_norm_after': 'mmt_search_topk_bf16_norm'}
+NEW_EXPORTS = {'mmt_search_after_keys': 5}  # the scan that takes the bounds: tests/test_search_abi_cpu.py
 INF = float('inf')
 NO_CURSOR, EXHAUSTED = (INF, -1), (-INF, -1)
 
@@ -200,13 +196,7 @@ def test_signatures_of_the_new_exports_agree_with_the_header():
     assert hasattr(handle, name)
   assert _params(src, 'mmt_search_after_keys')[1] == ['const float* scores', 'const int64_t* first', 'int NQ', 'uint64_t* keys',
                                                       'void* stream']
-  for name, parent in PARENTS.items():                   # the parent's signature with the bounds in front of the workspace
-    mine, theirs = _params(src, name)[1], _params(src, parent)[1]
-    at = theirs.index('uint64_t* ws')
-    assert mine == theirs[:at] + ['const uint64_t* after'] + theirs[at:], name
-    assert _lib.SIGNATURES[name][1] == _lib.SIGNATURES[parent][1][:at] + [ctypes.c_void_p] + _lib.SIGNATURES[parent][1][at:]
-  assert 'mmt_search_topk_fp8_norm_after' not in src     # an fp8 index has no normalised form
-  assert handle.mmt_abi_version() == 5
+  assert handle.mmt_abi_version() == 6
 
 
 def test_new_exports_gate_their_arguments_on_the_host():
@@ -220,45 +210,10 @@ def test_new_exports_gate_their_arguments_on_the_host():
   buf = (ctypes.c_char * 256)()
   base = ctypes.addressof(buf)
   base += -base % 16
-  p, off4, off8 = ctypes.c_void_p(base), ctypes.c_void_p(base + 4), ctypes.c_void_p(base + 8)
+  p = ctypes.c_void_p(base)
   keys = fns['mmt_search_after_keys']
   for args in ((None, p, 1, p, None), (p, None, 1, p, None), (p, p, 1, None, None), (p, p, 0, p, None), (p, p, -1, p, None)):
     assert keys(*args) == -1, args
-  # pointers, then NQ NV M d k, subset exclude E, [beta lse,] after, ws scores index, stream; d = 16 suits every storage
-  for name, lead, norm in (('mmt_search_topk_after', 4, False), ('mmt_search_topk_bf16_after', 5, False),
-                           ('mmt_search_topk_fp8_after', 6, False), ('mmt_search_topk_norm_after', 4, True),
-                           ('mmt_search_topk_bf16_norm_after', 5, True)):
-    fn = fns[name]
-    good = [p] * lead + [1, 1, 1, 16, 1, None, None, 0] + ([1.0, p] if norm else []) + [p, p, p, p, None]
-    nq, nv, m, d, k, subset, exclude, e = (lead + j for j in range(8))
-    after = e + (3 if norm else 1)
-    ws, scores, index = after + 1, after + 2, after + 3
-    args = list(good)
-    args[after] = None
-    assert fn(*args) == -1, (name, 'after')                                    # the gate of its own
-    for missing in list(range(lead)) + [ws, index] + ([e + 2] if norm else []):  # the parents' gates
-      args = list(good)
-      args[missing] = None
-      assert fn(*args) == -1, (name, missing)
-    off_d = {4: 18, 5: 20, 6: 24}[lead]
-    for at, value in ((nq, 0), (nv, 0), (m, 0), (m, 17), (d, 0), (d, off_d), (k, 0), (k, 129), (k, -1), (e, -1), (e, 33),
-                      (e, 1)):                                                 # E = 1 without an exclude pointer
-      args = list(good)
-      args[at] = value
-      assert fn(*args) == -1, (name, at, value)
-    if norm:
-      for beta in (0.0, -1.0, INF, float('nan')):
-        args = list(good)
-        args[e + 1] = beta
-        assert fn(*args) == -1, (name, beta)
-    if lead == 6:
-      args = list(good)
-      args[d] = 8                                                              # a bf16 width, not an fp8 one
-      assert fn(*args) == -1
-    for at in (0, 2 if lead == 4 else 3, subset):                              # query rows, gallery rows, subset words
-      args = list(good)
-      args[at] = off8 if lead > 4 or at == subset else off4
-      assert fn(*args) == -2, (name, at)
 
 
 @pytest.mark.parametrize('hollow', [_hollow_index, _hollow_sharded], ids=['VideoIndex', 'ShardedVideoIndex'])

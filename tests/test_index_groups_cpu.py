@@ -11,7 +11,7 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_EXPORTS = ('mmt_search_topk_groups', 'mmt_search_topk_groups_bf16', 'mmt_search_merge_group_lists')
+NEW_EXPORTS = ('mmt_search_merge_group_lists',)  # the grouped scan: tests/test_search_abi_cpu.py
 INF = float('inf')
 
 
@@ -190,7 +190,7 @@ def test_signatures_of_the_new_exports_agree_with_the_header():
   from mmt_amd import _lib
   src = open(os.path.join(ROOT, 'include', 'mmt_hip.h')).read()
   handle = ctypes.CDLL(_lib.LIB_PATH)
-  arity = {'mmt_search_topk_groups': 16, 'mmt_search_topk_groups_bf16': 17, 'mmt_search_merge_group_lists': 12}
+  arity = {'mmt_search_merge_group_lists': 12}
   for name in NEW_EXPORTS:
     m = re.search(r'\b(int|int64_t) %s\(([^;]*?)\);' % name, src)
     assert m, name + ' is not declared in mmt_hip.h'
@@ -201,7 +201,7 @@ def test_signatures_of_the_new_exports_agree_with_the_header():
     for p, a in zip(params, args):
       assert (a is ctypes.c_void_p) == ('*' in p) and (a is ctypes.c_int) == (p.startswith('int ')), (name, p)
     assert hasattr(handle, name)
-  assert handle.mmt_abi_version() == 5
+  assert handle.mmt_abi_version() == 6
 
 
 def test_new_exports_gate_their_arguments_on_the_host():
@@ -215,35 +215,7 @@ def test_new_exports_gate_their_arguments_on_the_host():
   buf = (ctypes.c_char * 256)()
   base = ctypes.addressof(buf)
   base += -base % 16
-  p, off4, off8 = ctypes.c_void_p(base), ctypes.c_void_p(base + 4), ctypes.c_void_p(base + 8)
-  topk = fns['mmt_search_topk_groups']      # qf qw gf gw NQ NV M d k groups subset ws scores out_groups out_items stream
-  good = [p, p, p, p, 1, 1, 1, 8, 1, p, None, p, p, p, p, None]
-  for missing in (0, 1, 2, 3, 9, 11, 12, 13, 14):                            # the group table is 9; subset may be null
-    args = list(good)
-    args[missing] = None
-    assert topk(*args) == -1, missing
-  for at, value in ((4, 0), (5, 0), (6, 0), (6, 17), (7, 0), (7, 6), (8, 0), (8, 129), (8, -1)):   # NQ NV M d k
-    args = list(good)
-    args[at] = value
-    assert topk(*args) == -1, (at, value)
-  for at, value in ((0, off4), (2, off8), (10, off4)):                       # query rows, gallery rows, subset words
-    args = list(good)
-    args[at] = value
-    assert topk(*args) == -2, at
-  topk16 = fns['mmt_search_topk_groups_bf16']   # q_hi q_lo qw gf gw NQ NV M d k groups subset ws scores groups items stream
-  good = [p, p, p, p, p, 1, 1, 1, 8, 1, p, None, p, p, p, p, None]
-  for missing in (0, 1, 2, 3, 4, 10, 12, 13, 14, 15):
-    args = list(good)
-    args[missing] = None
-    assert topk16(*args) == -1, missing
-  for at, value in ((5, 0), (6, 0), (7, 17), (8, 12), (8, 4), (9, 0), (9, 129)):   # d % 8
-    args = list(good)
-    args[at] = value
-    assert topk16(*args) == -1, (at, value)
-  for at, value in ((0, off8), (1, off8), (3, off4), (11, off8)):
-    args = list(good)
-    args[at] = value
-    assert topk16(*args) == -2, at
+  p = ctypes.c_void_p(base)
   merge = fns['mmt_search_merge_group_lists']   # scores groups index ids S NQ kin kout out_scores out_groups out_items stream
   good = [p, p, p, p, 1, 1, 1, 1, p, p, p, None]
   for missing in (0, 1, 2, 3, 8, 9, 10):

@@ -14,8 +14,6 @@ import torch
 from tests.fixtures import load_npz
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_EXPORTS = ('mmt_search_topk_pooled', 'mmt_search_topk_bf16_pooled', 'mmt_search_thresholds_pooled',
-               'mmt_search_thresholds_bf16_pooled', 'mmt_search_count_pooled', 'mmt_search_count_bf16_pooled')
 SIZES = ('mmt_topk_pooled_workspace_keys', 'mmt_count_pooled_workspace_ints')
 F32 = np.float32
 
@@ -90,8 +88,8 @@ def test_signatures_of_the_new_exports_agree_with_the_header():
   from mmt_amd import _lib
   src = open(os.path.join(ROOT, 'include', 'mmt_hip.h')).read()
   handle = ctypes.CDLL(_lib.LIB_PATH)
-  arity = dict(zip(NEW_EXPORTS + SIZES, (17, 18, 15, 16, 18, 19, 4, 4)))
-  for name in NEW_EXPORTS + SIZES:
+  arity = dict(zip(SIZES, (4, 4)))
+  for name in SIZES:
     res_name, params = _params(src, name)
     res, args = _lib.SIGNATURES[name]
     assert res is (ctypes.c_int if res_name == 'int' else ctypes.c_int64), name
@@ -100,19 +98,15 @@ def test_signatures_of_the_new_exports_agree_with_the_header():
     for p, a in zip(params, args):
       assert (a is ctypes.c_void_p) == ('*' in p) and (a is ctypes.c_int) == (p.startswith('int ')), (name, p)
     assert hasattr(handle, name)
-  # the bf16 form is the fp32 form with the query as a hi / lo pair
-  for name in NEW_EXPORTS[::2]:
-    fp32, bf16 = _params(src, name)[1], _params(src, name.replace('_pooled', '_bf16_pooled'))[1]
-    assert [p.split()[-1] for p in bf16[2:]] == [p.split()[-1] for p in fp32[1:]], name
-  assert handle.mmt_abi_version() == 5
-  assert _lib.lib().mmt_abi_version() == 5                  # and every declared symbol binds
+  assert handle.mmt_abi_version() == 6
+  assert _lib.lib().mmt_abi_version() == 6                  # and every declared symbol binds
 
 
 def _fns():
   from mmt_amd import _lib
   handle = ctypes.CDLL(_lib.LIB_PATH)
   fns = {}
-  for name in NEW_EXPORTS + SIZES:
+  for name in SIZES:
     fns[name] = getattr(handle, name)
     fns[name].restype, fns[name].argtypes = _lib.SIGNATURES[name]
   return fns
@@ -139,55 +133,6 @@ def test_workspace_sizes_follow_the_query_blocks():
   for bad in ((0, 1, 1, 1), (1, 0, 1, 1), (1, 65, 1, 1), (1, -1, 1, 1), (1, 1, 0, 1), (1, 1, 1, 0), (2 ** 26, 64, 1, 1)):
     assert keys(*bad) == -1 and ints(*bad) == -1, bad
   assert keys(1, 1, 1, 129) == -1 and ints(1, 1, 1, 33) == -1
-
-
-def test_new_exports_gate_their_arguments_on_the_host():
-  """Every refusal below returns before any launch: MMT_ERR_ARG = -1, MMT_ERR_ALIGN = -2."""
-  fns = _fns()
-  buf = (ctypes.c_char * 256)()
-  base = ctypes.addressof(buf)
-  base += -base % 16
-  p, off4, off8 = ctypes.c_void_p(base), ctypes.c_void_p(base + 4), ctypes.c_void_p(base + 8)
-
-  def refuse(fn, good, missing, sizes, unaligned):
-    for at in missing:
-      args = list(good)
-      args[at] = None
-      assert fn(*args) == -1, at
-    for at, value in sizes:
-      args = list(good)
-      args[at] = value
-      assert fn(*args) == -1, (at, value)
-    for at, value in unaligned:
-      args = list(good)
-      args[at] = value
-      assert fn(*args) == -2, at
-
-  # NS C mode NV M d at 5 .. 10 (fp32) / 6 .. 11 (bf16): NS < 1, C < 1, C > 64, NS * C >= 2^31, mode, NV, M, d
-  def sizes(o, d_bad):
-    return [(o, 0), (o, -1), (o + 1, 0), (o + 1, -3), (o + 1, 65), (o, 2 ** 30), (o + 2, 2), (o + 2, -1), (o + 3, 0),
-            (o + 4, 0), (o + 4, 17), (o + 5, 0), (o + 5, d_bad)]
-  # qf qw gf gw rw NS C mode NV M d k subset ws scores index stream
-  good = [p, p, p, p, p, 1, 2, 0, 1, 1, 8, 1, None, p, p, p, None]
-  refuse(fns['mmt_search_topk_pooled'], good, (0, 1, 2, 3, 4, 13, 15), sizes(5, 6) + [(11, 0), (11, 129), (11, -1)],
-         ((0, off4), (2, off8), (12, off4)))
-  good = [p, p, p, p, p, p, 1, 2, 1, 1, 1, 8, 1, None, p, p, p, None]
-  refuse(fns['mmt_search_topk_bf16_pooled'], good, (0, 1, 2, 3, 4, 5, 14, 16), sizes(6, 12) + [(11, 4), (12, 0), (12, 129)],
-         ((0, off8), (1, off8), (3, off4), (13, off8)))
-  # qf qw gf gw rw NS C mode NV M d targets T thr stream
-  good = [p, p, p, p, p, 1, 64, 1, 1, 1, 8, p, 1, p, None]
-  refuse(fns['mmt_search_thresholds_pooled'], good, (0, 1, 2, 3, 4, 11, 13), sizes(5, 6) + [(12, 0), (12, 33)],
-         ((0, off4), (2, off8)))
-  good = [p, p, p, p, p, p, 1, 64, 1, 1, 1, 8, p, 1, p, None]
-  refuse(fns['mmt_search_thresholds_bf16_pooled'], good, (0, 1, 2, 3, 4, 5, 12, 14), sizes(6, 12) + [(13, 0), (13, 33)],
-         ((0, off8), (1, off4), (3, off8)))
-  # qf qw gf gw rw NS C mode NV M d thr T subset ws greater equal stream
-  good = [p, p, p, p, p, 3, 5, 0, 1, 1, 8, p, 1, None, p, p, p, None]
-  refuse(fns['mmt_search_count_pooled'], good, (0, 1, 2, 3, 4, 11, 14, 15, 16), sizes(5, 6) + [(12, 0), (12, 33)],
-         ((0, off4), (2, off8), (13, off4)))
-  good = [p, p, p, p, p, p, 3, 5, 0, 1, 1, 8, p, 1, None, p, p, p, None]
-  refuse(fns['mmt_search_count_bf16_pooled'], good, (0, 1, 2, 3, 4, 5, 12, 15, 16, 17), sizes(6, 12) + [(13, 0), (13, 33)],
-         ((0, off8), (1, off8), (3, off4), (14, off8)))
 
 
 def _hollow_index(num_items, dtype=torch.float32):

@@ -113,7 +113,7 @@ def test_argument_errors_are_raised_without_a_device():
 
 
 def test_rank_exports_gate_their_arguments_on_the_host():
-  """mmt_rank_workspace_ints is pure host code; the launchers return MMT_ERR_ARG / MMT_ERR_ALIGN before any launch."""
+  """mmt_rank_workspace_ints is pure host code (the gates of mmt_search_rank: tests/test_search_abi_cpu.py)."""
   from mmt_amd import _lib
   handle = ctypes.CDLL(_lib.LIB_PATH)
   f = handle.mmt_rank_workspace_ints
@@ -123,19 +123,5 @@ def test_rank_exports_gate_their_arguments_on_the_host():
   assert f(257, 4097, 32) == 257 * 32 * (1 + 2 * 33)                # 128-column chunks while the chip is not full
   for bad in ((0, 5, 1), (5, 0, 1), (5, 5, 0), (5, 5, 33)):
     assert f(*bad) == -1
-  buf = (ctypes.c_char * 256)()
-  base = ctypes.addressof(buf)
-  base += -base % 16
-  p = ctypes.c_void_p(base)
-  rank = handle.mmt_search_rank
-  rank.argtypes = _lib.SIGNATURES['mmt_search_rank'][1]
-  rank16 = handle.mmt_search_rank_bf16
-  rank16.argtypes = _lib.SIGNATURES['mmt_search_rank_bf16'][1]
-  assert rank(p, p, p, p, 1, 1, 1, 8, p, 0, p, p, p, None) == -1     # T = 0
-  assert rank(p, p, p, p, 1, 1, 1, 8, p, 33, p, p, p, None) == -1    # T = 33
-  assert rank(p, p, p, p, 1, 1, 1, 8, None, 1, p, p, p, None) == -1  # no targets
-  assert rank(p, p, p, p, 1, 1, 1, 6, p, 1, p, p, p, None) == -1     # d % 4
-  assert rank(p, p, p, p, 1, 1, 17, 8, p, 1, p, p, p, None) == -1    # M > 16
-  assert rank(ctypes.c_void_p(base + 4), p, p, p, 1, 1, 1, 8, p, 1, p, p, p, None) == -2
-  assert rank16(p, p, p, p, p, 1, 1, 1, 12, p, 1, p, p, p, None) == -1  # d % 8
-  assert rank16(p, ctypes.c_void_p(base + 8), p, p, p, 1, 1, 1, 8, p, 1, p, p, p, None) == -2
+
+

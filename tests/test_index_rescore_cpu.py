@@ -13,8 +13,7 @@ import torch
 from tests.test_index_groups_cpu import _hollow_index, _hollow_sharded, _item, _key, best_first
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_EXPORTS = {'mmt_rescore_workspace_keys': 2, 'mmt_search_rescore': 15, 'mmt_search_rescore_bf16': 16,
-               'mmt_search_rescore_fp8': 17}
+NEW_EXPORTS = {'mmt_rescore_workspace_keys': 2}  # mmt_search_rescore itself: tests/test_search_abi_cpu.py
 INF = float('inf')
 
 
@@ -119,28 +118,18 @@ def test_signatures_of_the_new_exports_agree_with_the_header():
   from mmt_amd import _lib
   src = open(os.path.join(ROOT, 'include', 'mmt_hip.h')).read()
   handle = ctypes.CDLL(_lib.LIB_PATH)
-  params_of = {}
   for name, arity in NEW_EXPORTS.items():
     m = re.search(r'\b(int|int64_t) %s\(([^;]*?)\);' % name, src)
     assert m, name + ' is not declared in mmt_hip.h'
-    params = params_of[name] = [p.strip() for p in m.group(2).replace('\n', ' ').split(',')]
+    params = [p.strip() for p in m.group(2).replace('\n', ' ').split(',')]
     res, args = _lib.SIGNATURES[name]
     assert res is (ctypes.c_int if m.group(1) == 'int' else ctypes.c_int64), name
     assert len(args) == len(params) == arity, name
     for p, a in zip(params, args):
       assert (a is ctypes.c_void_p) == ('*' in p) and (a is ctypes.c_int) == (p.startswith('int ')), (name, p)
     assert hasattr(handle, name)
-  # the thresholds signatures with (candidates, C, k), a workspace and the two lists in place of (targets, T) and thr
-  for tag in ('', '_bf16', '_fp8'):
-    theirs = re.search(r'\bint mmt_search_thresholds%s\(([^;]*?)\);' % tag, src)
-    theirs = [p.strip() for p in theirs.group(1).replace('\n', ' ').split(',')]
-    mine = params_of['mmt_search_rescore' + tag]
-    n = len(theirs) - 4                                                          # up to d
-    assert mine[:n] == theirs[:n] and theirs[n:] == ['const int64_t* targets', 'int T', 'float* thr', 'void* stream']
-    assert mine[n:] == ['const int64_t* candidates', 'int C', 'int k', 'uint64_t* ws', 'float* scores', 'int64_t* index',
-                        'void* stream']
   assert 'search_rescore.hip' in src
-  assert handle.mmt_abi_version() == 5
+  assert handle.mmt_abi_version() == 6
 
 
 def test_new_exports_gate_their_arguments_on_the_host():
@@ -155,33 +144,6 @@ def test_new_exports_gate_their_arguments_on_the_host():
   assert size(1, 1) == 1 and size(130, 1000) == 130000 and size(4096, 1024) == 4096 * 1024
   for bad in ((0, 1), (-1, 1), (1, 0), (1, 1025), (1, -1)):
     assert size(*bad) == -1, bad
-  buf = (ctypes.c_char * 256)()
-  base = ctypes.addressof(buf)
-  base += -base % 16
-  p, off4, off8 = ctypes.c_void_p(base), ctypes.c_void_p(base + 4), ctypes.c_void_p(base + 8)
-  # pointers, then NQ NV M d, candidates, C k, ws scores index, stream; d = 16 suits every storage
-  for name, lead in (('mmt_search_rescore', 4), ('mmt_search_rescore_bf16', 5), ('mmt_search_rescore_fp8', 6)):
-    fn = fns[name]
-    good = [p] * lead + [1, 1, 1, 16, p, 1, 1, p, p, p, None]
-    nq, nv, m, d, cand, c, k = (lead + j for j in range(7))
-    for missing in list(range(lead)) + [cand, k + 1, k + 2, k + 3]:
-      args = list(good)
-      args[missing] = None
-      assert fn(*args) == -1, (name, missing)
-    off_d = {4: 18, 5: 20, 6: 24}[lead]                                          # d off its multiple: d % 4, d % 8, d % 16
-    for at, value in ((nq, 0), (nv, 0), (m, 0), (m, 17), (d, 0), (d, off_d), (c, 0), (c, 1025), (c, -1), (k, 0), (k, 129),
-                      (k, -1)):
-      args = list(good)
-      args[at] = value
-      assert fn(*args) == -1, (name, at, value)
-    if lead == 6:
-      args = list(good)
-      args[d] = 8                                                                # a bf16 width, not an fp8 one
-      assert fn(*args) == -1
-    for at in (0, 2 if lead == 4 else 3):                                        # query rows, gallery rows
-      args = list(good)
-      args[at] = off8 if lead > 4 else off4
-      assert fn(*args) == -2, (name, at)
 
 
 @pytest.mark.parametrize('hollow', [_hollow_index, _hollow_sharded], ids=['VideoIndex', 'ShardedVideoIndex'])

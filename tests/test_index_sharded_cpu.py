@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_EXPORTS = ('mmt_count_workspace_ints', 'mmt_search_thresholds', 'mmt_search_thresholds_bf16', 'mmt_search_count',
-               'mmt_search_count_bf16', 'mmt_search_merge_lists')
+NEW_EXPORTS = ('mmt_count_workspace_ints', 'mmt_search_merge_lists')  # the two scans: tests/test_search_abi_cpu.py
 
 
 def merge_reference(scores, index, ids, kout):
@@ -97,7 +96,7 @@ def test_signatures_of_the_new_exports_agree_with_the_header():
     for p, a in zip(params, args):
       assert (a is ctypes.c_void_p) == ('*' in p) and (a is ctypes.c_int) == (p.startswith('int ')), (name, p)
     assert hasattr(handle, name)
-  assert handle.mmt_abi_version() == 5
+  assert handle.mmt_abi_version() == 6
 
 
 def test_new_exports_gate_their_arguments_on_the_host():
@@ -121,42 +120,7 @@ def test_new_exports_gate_their_arguments_on_the_host():
   buf = (ctypes.c_char * 256)()
   base = ctypes.addressof(buf)
   base += -base % 16
-  p, off4, off8 = ctypes.c_void_p(base), ctypes.c_void_p(base + 4), ctypes.c_void_p(base + 8)
-  thr = fns['mmt_search_thresholds']          # qf qw gf gw NQ NV M d targets T thr stream
-  assert thr(p, p, p, p, 1, 1, 1, 8, p, 0, p, None) == -1            # T = 0
-  assert thr(p, p, p, p, 1, 1, 1, 8, p, 33, p, None) == -1
-  assert thr(p, p, p, p, 1, 1, 1, 8, None, 1, p, None) == -1         # no targets
-  assert thr(p, p, p, p, 1, 1, 1, 8, p, 1, None, None) == -1         # no output
-  assert thr(p, None, p, p, 1, 1, 1, 8, p, 1, p, None) == -1
-  assert thr(p, p, p, p, 0, 1, 1, 8, p, 1, p, None) == -1
-  assert thr(p, p, p, p, 1, 1, 17, 8, p, 1, p, None) == -1           # M > 16
-  assert thr(p, p, p, p, 1, 1, 1, 6, p, 1, p, None) == -1            # d % 4
-  assert thr(off4, p, p, p, 1, 1, 1, 8, p, 1, p, None) == -2
-  assert thr(p, p, off8, p, 1, 1, 1, 8, p, 1, p, None) == -2
-  thr16 = fns['mmt_search_thresholds_bf16']   # q_hi q_lo qw gf gw NQ NV M d targets T thr stream
-  assert thr16(p, p, p, p, p, 1, 1, 1, 8, p, 33, p, None) == -1
-  assert thr16(p, p, p, p, p, 1, 1, 1, 12, p, 1, p, None) == -1      # d % 8
-  assert thr16(p, None, p, p, p, 1, 1, 1, 8, p, 1, p, None) == -1
-  assert thr16(p, p, p, p, p, 1, 1, 1, 8, p, 1, None, None) == -1
-  assert thr16(p, off8, p, p, p, 1, 1, 1, 8, p, 1, p, None) == -2
-  assert thr16(p, p, p, off4, p, 1, 1, 1, 8, p, 1, p, None) == -2
-  count = fns['mmt_search_count']             # qf qw gf gw NQ NV M d thr T subset ws greater equal stream
-  assert count(p, p, p, p, 1, 1, 1, 8, p, 0, None, p, p, p, None) == -1
-  assert count(p, p, p, p, 1, 1, 1, 8, p, 33, None, p, p, p, None) == -1
-  assert count(p, p, p, p, 1, 1, 1, 8, None, 1, None, p, p, p, None) == -1   # no thresholds
-  assert count(p, p, p, p, 1, 1, 1, 8, p, 1, None, None, p, p, None) == -1   # no workspace
-  assert count(p, p, p, p, 1, 1, 1, 8, p, 1, p, p, None, p, None) == -1
-  assert count(p, p, p, p, 1, 1, 1, 8, p, 1, p, p, p, None, None) == -1
-  assert count(p, p, p, p, 1, 0, 1, 8, p, 1, p, p, p, p, None) == -1
-  assert count(p, p, p, p, 1, 1, 1, 6, p, 1, p, p, p, p, None) == -1         # d % 4
-  assert count(p, p, p, p, 1, 1, 1, 8, p, 1, off4, p, p, p, None) == -2      # subset words off a 16-byte boundary
-  assert count(off8, p, p, p, 1, 1, 1, 8, p, 1, None, p, p, p, None) == -2
-  count16 = fns['mmt_search_count_bf16']      # q_hi q_lo qw gf gw NQ NV M d thr T subset ws greater equal stream
-  assert count16(p, p, p, p, p, 1, 1, 1, 8, p, 33, p, p, p, p, None) == -1
-  assert count16(p, p, p, p, p, 1, 1, 1, 12, p, 1, p, p, p, p, None) == -1   # d % 8
-  assert count16(p, p, p, p, p, 1, 1, 1, 8, None, 1, p, p, p, p, None) == -1
-  assert count16(p, p, p, p, p, 1, 1, 1, 8, p, 1, off8, p, p, p, None) == -2
-  assert count16(p, off8, p, p, p, 1, 1, 1, 8, p, 1, None, p, p, p, None) == -2
+  p = ctypes.c_void_p(base)
   merge = fns['mmt_search_merge_lists']       # scores index ids S NQ kin kout out_scores out_index stream
   assert merge(p, p, p, 0, 1, 1, 1, p, p, None) == -1                # S = 0
   assert merge(p, p, p, 33, 1, 1, 1, p, p, None) == -1
