@@ -645,6 +645,28 @@ int mmt_search_rescore(const MmtSearchScan* scan, const int64_t* candidates, int
 int mmt_search_col_lse(const MmtSearchScan* scan, float beta, float* ws, float* state, int first, float* lse,
                        void* stream);
 
+/* The tenth scan, additive: no existing entry, field or cell changes and mmt_abi_version() stays 6.  It serves
+ * search.py's `reverse_search` (the lists) and `csls_norm` (the mean, which takes the place of lse in the norm slot with
+ * beta = 2: Cross-domain Similarity Local Scaling, Conneau et al., ICLR 2018).
+ * mmt_search_col_topk (no options; fp32, bf16, fp8): the running top-k per ITEM over a stream of query rows -- for every
+ *   stored item the k best query rows, 1 <= k <= MMT_SEARCH_MAX_RK.  The descriptor's query rows are one batch; row0 >= 0
+ *   is the global number of its first row (row0 + NQ <= 2^31), and every batch but the last holds a multiple of 64 rows.
+ *   Every 64-row block gives, per item, its best min(k, live rows) keys -- (score, global row) in the search's key, so
+ *   score descending, -0 tied with +0, equal scores by ascending row -- and a fold launch merges them with the carried
+ *   lists.  Keys of distinct rows are distinct, so the k best of a union do not depend on the batching, the chunk rule,
+ *   NV, the item's position or the shard.  state uint64 [NV][k]: first != 0 starts it, otherwise it is what the previous
+ *   batch left.  scores fp32 / rows int64 [NV][k] and mean fp32 [NV], each nullable, are written when given, i.e. with the
+ *   last batch: slot j of item g holds its j-th best row and the score with the bits mmt_search_topk gives the pair (a -0
+ *   comes back as +0); a slot past the number of rows seen holds (-inf, -1).  mean[g] = fl(fl(.. fl(s_0 + s_1) .. +
+ *   s_{k'-1}) * mean_weight) over the item's k' = min(k, rows seen) scores in list order -- rounded adds, then one rounded
+ *   multiply, never an fma (the caller passes mean_weight = float32(1 / k')).  ws and state 16-byte aligned (else
+ *   MMT_ERR_ALIGN).  mmt_col_topk_workspace_keys: uint64, ceil(NB / 64) * NV * k; MMT_ERR_ARG for a size < 1 or k out of
+ *   range. */
+#define MMT_SEARCH_MAX_RK 32
+int64_t mmt_col_topk_workspace_keys(int NB, int NV, int k);
+int mmt_search_col_topk(const MmtSearchScan* scan, int k, int row0, uint64_t* ws, uint64_t* state, int first,
+                        float* scores, int64_t* rows, float* mean, float mean_weight, void* stream);
+
 /* Beside the scans.
  * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> the subset words, padding included: one ballot per 64
  *   items, one writer per word.

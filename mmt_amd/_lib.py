@@ -255,6 +255,9 @@ SIGNATURES = {
     'mmt_search_range_fill': (c_int, [_SCAN, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_search_rescore': (c_int, [_SCAN, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mmt_search_col_lse': (c_int, [_SCAN, c_f32, c_vp, c_vp, c_int, c_vp, c_vp]),
+    # the tenth, additive: the running top-k per item over a stream of query rows (reverse_search, csls_norm)
+    'mmt_col_topk_workspace_keys': (c_i64, [c_int, c_int, c_int]),
+    'mmt_search_col_topk': (c_int, [_SCAN, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_f32, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

@@ -119,7 +119,7 @@ def v2t_targets(query_masks, num_videos, captions_per_video):
 
 def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, query_masks=None, dtype=torch.float32,
                               video_subset=None, devices=None, text_bank=None, video_bank=None, beta=None,
-                              caption_mode='indep'):
+                              caption_mode='indep', bank_norm='softmax', bank_k=10):
   """`retrieval_metrics` (same arguments, same result dict and keys) without the N_text x N_video matrix: the rank of every
   ground truth comes from search.VideoIndex.ranks, so no buffer grows with N_text * N_video.  t2v: an index of the videos
   queried with the real captions, the target of caption row b*C + c being video b.  v2t: an index of the real captions
@@ -134,6 +134,9 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
   text_bank / video_bank ((embds, weights) pairs in either query layout of VideoIndex.search) with beta (a float > 0):
   querybank hubness normalisation (VideoIndex.hub_norm) -- a bank of text queries re-scores the t2v ranking over the video
   index, a bank of videos the v2t ranking over the caption index; either may be given alone.
+  bank_norm: 'softmax' (that, the default) or 'csls': the banks build VideoIndex.csls_norm(k=bank_k) instead -- CSLS, the
+  mean of each item's bank_k best bank scores in the same norm slot with beta = 2 -- and beta, which it has no use for,
+  must be None.
   caption_mode: 'indep' (every caption a query of its own, as above) or 'avg' (the reference's
   merge_caption_similiarities = 'avg', model/model.py:826-831: a video's C captions answer as one, on the mean of their
   similarities) -- then the result is what t2v_metrics / v2t_metrics give on the B x B matrix of those means.  t2v: the
@@ -148,7 +151,11 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
     raise ValueError("retrieval_metrics_indexed: caption_mode must be 'indep' or 'avg', got %r" % (caption_mode,))
   if caption_mode == 'avg' and (query_masks is not None or text_bank is not None or video_bank is not None):
     raise ValueError("retrieval_metrics_indexed: caption_mode='avg' does not combine with query_masks, text_bank or video_bank")
-  if (text_bank is not None or video_bank is not None) and beta is None:
+  if bank_norm not in ('softmax', 'csls'):
+    raise ValueError("retrieval_metrics_indexed: bank_norm must be 'softmax' or 'csls', got %r" % (bank_norm,))
+  if bank_norm == 'csls' and beta is not None:
+    raise ValueError("retrieval_metrics_indexed: bank_norm='csls' takes no beta (it is 2 by definition), got %r" % (beta,))
+  if bank_norm == 'softmax' and (text_bank is not None or video_bank is not None) and beta is None:
     raise ValueError('retrieval_metrics_indexed: a bank needs beta')
   for bank in (text_bank, video_bank):
     if bank is not None and not (isinstance(bank, (tuple, list)) and len(bank) == 2):
@@ -189,7 +196,8 @@ def retrieval_metrics_indexed(vid_embds, text_embds, vid_weights, text_weights, 
   def normaliser(index, bank):
     if bank is None:
       return None
-    return index.hub_norm(*(_as_cuda_f32(x).to(vid.device) for x in bank), beta)
+    bank = tuple(_as_cuda_f32(x).to(vid.device) for x in bank)
+    return index.csls_norm(*bank, k=bank_k) if bank_norm == 'csls' else index.hub_norm(*bank, beta)
   if caption_mode == 'avg':
     return _metrics_avg(make_index, devices, vid, vw, txt4.permute(0, 2, 1, 3).reshape(b * c, m, d).contiguous(),
                         tw.contiguous(), c, cut, dtype)

@@ -11,7 +11,8 @@ It is symmetric, so video-to-text search is an index of captions queried with vi
 blocks on the matrix cores and keeps a running top-k per query; a second merges the chunk lists (mmt_search_topk).
 Results are bit-reproducible.  Every scan goes to one of nine C entry points with one descriptor, MmtSearchScan
 (include/mmt_hip.h; built per row batch by VideoIndex._describe): the storage, the operands and whatever of subset,
-exclusions, cursor, norm and sets the call has.  Below, `mmt_search_topk [lse, after]` stands for "that entry with those
+exclusions, cursor, norm and sets the call has (a tenth entry over the same descriptor, mmt_search_col_topk, serves the
+ninth question at the end).  Below, `mmt_search_topk [lse, after]` stands for "that entry with those
 parts of the descriptor set".
 
     index = VideoIndex(vid_embds, vid_weights, dtype=torch.bfloat16)    # half the bytes per item (d % 8 == 0)
@@ -224,6 +225,31 @@ restated in its own item numbers).  Combines with subset=, exclude=, norm= and d
 taken without the cursor, so every page of a query makes the same choice); not with pooling= or item_pooling=, and
 `search_groups` has no cursor.  `search_deep` is host code: ceil(w / page) pages of `search`, w = min(depth, candidates),
 each continuing from the last column of the one before, concatenated to [NQ, w].
+
+    scores, rows = index.reverse_search(q, qw, k=10)                       # [num_items, k'], k' = min(k, NQ), k <= MAX_RK = 32
+    norm = index.csls_norm(bank_embds, bank_weights, k=10, dynamic=False)  # HubNorm: kind='csls', .k, .beta == 2.0, .lse = r
+    scores, indices = index.search(q, qw, k=10, norm=norm)                 # every norm= consumer, unchanged
+
+The ninth question runs the other way: per stored ITEM, the k best QUERY rows -- which captions pull on a video (hubness
+diagnosis, reciprocal-neighbour checks, mining the captions that wrongly land on it).  The eight above answer per query and
+the lse pass of `hub_norm` collapses an item's column to one number; the only other route is the NQ x num_items matrix this
+module exists to avoid, or a second index of the queries searched with the items, which doubles the storage and, on a
+bfloat16 or float8_e4m3fn index, rounds the other operand, so its scores are not the bits `search` gives the pair.  The
+order is `search`'s with the row number in the item's place -- score descending, -0 tied with +0, equal scores by ascending
+query row (the text layout numbers its rows b * C + c) -- and a score has the bits `search` returns for the pair on this
+index, on all three storage dtypes.  The rows stream through the scan in batches of whole 64-row blocks; every block
+leaves its best k rows per item, and a fold keeps a running list per item across blocks and batches
+(mmt_search_col_topk, the tenth entry: additive, no option of the descriptor).  Keys of distinct rows are distinct, so
+the k best of a union do not depend on the batching, the launch geometry, num_items, the item's position or the shard:
+ShardedVideoIndex.reverse_search -- every shard takes all the rows and answers for its own items -- is bit-identical.
+It takes no options.  `csls_norm` puts the second standard hubness correction on it, Cross-domain Similarity Local Scaling
+(Conneau et al., ICLR 2018; the other bank normaliser of QB-Norm): r[g] = the mean of item g's k' = min(k, NB) best bank
+scores, in fp32 as v = s_0, v = fl(v + s_i) in list order, r[g] = fl(v * float32(1 / k')) -- no fma, no division, restated
+bit for bit by numpy.  CSLS ranks by 2 score(q, g) - r_q - r[g]; r_q is constant within a query's row, so the ranking is
+that of fl(fl(2 * score(q, g)) - r[g]): the norm slot above with beta = 2 and r in place of lse.  Hence no scoring kernel
+of its own, and `search`, `rank_counts`, `ranks`, `target_scores`, `threshold_counts`, the dynamic rule, after=, subset=,
+exclude=, both index classes and metric.retrieval_metrics_indexed(bank_norm='csls', bank_k=) take it as they take a
+`hub_norm`.  Like `hub_norm` it is refused on a float8_e4m3fn index, because norm= is.
 """
 import ctypes
 import math
@@ -237,6 +263,7 @@ MAX_K = 128
 DEEP_PAGE = 64  # default page of `search_deep`: the width at which a scan costs least per column
 MAX_T = 32  # targets per query and launch of the rank kernels; wider target lists are sliced
 MAX_E = 32  # exclusions per query of a masked search
+MAX_RK = 32  # query rows per item of `reverse_search` and `csls_norm`: a wave's list of the fold is k + 64 keys of LDS
 MAX_C = 1024  # candidates per query of `rescore`: one query's keys are sorted in LDS
 MAX_SET = 64  # rows per query set of a pooled scan: one 64-row query block holds whole sets
 MAX_ITEM_SET = 128  # items per stored set of an item-pooled scan: one 128-column tile holds whole sets
@@ -334,11 +361,14 @@ class IndexSubset:
 class HubNorm:
   """The querybank normaliser of a VideoIndex (VideoIndex.hub_norm): `lse` fp32 [num_items] on the index device,
   lse[g] = log sum_b exp(beta * score(b, g)) over the `bank_size` bank queries; `beta`; `num_items` and `device` it was built
-  for; `hubs` bool [num_items] (dynamic=True, else None): the items that are the plain top-1 of at least one bank query."""
+  for; `hubs` bool [num_items] (dynamic=True, else None): the items that are the plain top-1 of at least one bank query.
+  `kind` is 'softmax' for that, or 'csls' (VideoIndex.csls_norm): `lse` then holds r[g], the mean of item g's `k` best bank
+  scores, and `beta` is 2.0 -- the same slot of every scan, fl(fl(beta * score) - lse[g]); `k` is None for 'softmax'."""
 
-  def __init__(self, lse, beta, bank_size, hubs=None):
+  def __init__(self, lse, beta, bank_size, hubs=None, *, kind='softmax', k=None):
     self.lse, self.beta, self.bank_size, self.hubs = lse, beta, bank_size, hubs
     self.num_items, self.device = lse.shape[0], lse.device
+    self.kind, self.k = kind, k
 
 
 class RangeResult:
@@ -559,6 +589,11 @@ def _range_result(offsets, indices, scores, order):
 def _check_beta(beta):
   if isinstance(beta, bool) or not isinstance(beta, float) or not 0 < beta < math.inf:
     raise ValueError('hub_norm: beta must be a float with 0 < beta < inf, got %r' % (beta,))
+
+
+def _check_rk(who, k):
+  if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_RK:
+    raise ValueError('%s: k must be an int in 1..%d, got %r' % (who, MAX_RK, k))
 
 
 def _check_dynamic(dynamic, norm, who):
@@ -861,11 +896,55 @@ class _Index:
     b, bw = self._queries(bank_embds, bank_weights)
     if b.shape[0] < 1:
       raise ValueError('hub_norm: the bank holds no queries')
-    hubs = None
-    if dynamic:
-      top1 = self._search(b, bw, 1, _Scan())[1][:, 0]
-      hubs = torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
-    return self._hub_norm(b, bw, beta, hubs)
+    return self._hub_norm(b, bw, beta, self._bank_hubs(b, bw, dynamic))
+
+  def _bank_hubs(self, b, bw, dynamic):
+    """`hubs` of a norm built with dynamic=True: the items that are the plain top-1 of a bank query; else None."""
+    if not dynamic:
+      return None
+    top1 = self._search(b, bw, 1, _Scan())[1][:, 0]
+    return torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
+
+  def reverse_search(self, embds, weights, k=10):
+    """The search run the other way: queries in either layout of `search` (the text layout numbers its rows b * C + c),
+    NQ >= 1 of them -> (scores float32 [num_items, k'], rows int64 [num_items, k']) on the device, k' = min(k, NQ), k an
+    int in 1 .. MAX_RK = 32: for every stored item the k' query rows that score best on it, best first, equal scores
+    (-0 tied with +0) by ascending row.  A score has the bits `search` returns for the pair on this index, whatever its
+    dtype (all three are supported), so a -0 comes back as +0.  The rows stream through in batches of whole 64-row blocks
+    within _BATCH_BYTES and a running list per item is carried between them (mmt_search_col_topk): no NQ x num_items
+    matrix, and the result does not depend on the batching, on num_items, on an item's position or on the shard that
+    holds it -- ShardedVideoIndex.reverse_search (every shard takes all the rows and answers for its own items) is
+    bit-identical.  It takes no options: subset=, exclude=, norm= and the poolings are not part of this call."""
+    _check_rk('reverse_search', k)
+    if self.num_items == 0:
+      raise ValueError('reverse_search: the index holds no items')
+    q, qw = self._queries(embds, weights)
+    if q.shape[0] < 1:
+      raise ValueError('reverse_search: need NQ >= 1 query rows, got %s' % (tuple(q.shape),))
+    return self._reverse_search(q, qw, min(k, q.shape[0]))
+
+  def csls_norm(self, bank_embds, bank_weights, k=10, dynamic=False):
+    """The CSLS normaliser of this index (Cross-domain Similarity Local Scaling, Conneau et al., ICLR 2018; the other bank
+    normaliser of QB-Norm): bank queries in either layout of `search`, NB >= 1 of them, and k, an int in 1 .. MAX_RK ->
+    HubNorm (ShardedVideoIndex: ShardedHubNorm) with kind='csls', k=k, beta=2.0 and, in `lse`, r[g] = the mean of item
+    g's k' = min(k, NB) best bank scores: with s_0 .. s_{k'-1} the scores `reverse_search(bank, k)` lists for the item, in
+    list order, v = s_0, v = fl(v + s_i), r[g] = fl(v * float32(1 / k')) (mmt_search_col_topk).  CSLS ranks a query's
+    items by 2 score(q, g) - r_q - r[g]; the query's own term r_q is constant within its row, so ranking by
+    fl(fl(2 * score(q, g)) - r[g]) is ranking by CSLS, and that is the norm slot as it is: passed as norm= to `search`,
+    `rank_counts`, `ranks`, `target_scores` and `threshold_counts` -- with subset=, exclude=, after= and the dynamic rule
+    -- it needs no kernel of its own.  r[g] does not depend on the batching, on num_items, on g's position or on the
+    shard.  dynamic=True records `hubs` as `hub_norm` does.  Like `hub_norm` it is refused on a float8_e4m3fn index,
+    because norm= is."""
+    self._no_fp8('csls_norm', 'the querybank normalisation')
+    _check_rk('csls_norm', k)
+    if not isinstance(dynamic, bool):
+      raise ValueError('csls_norm: dynamic must be False or True, got %r' % (dynamic,))
+    if self.num_items == 0:
+      raise ValueError('csls_norm: the index holds no items')
+    b, bw = self._queries(bank_embds, bank_weights)
+    if b.shape[0] < 1:
+      raise ValueError('csls_norm: the bank holds no queries')
+    return self._csls_norm(b, bw, k, self._bank_hubs(b, bw, dynamic))
 
   def _after(self, after, pooling=None, item_pooling=None):
     """Type, device and rank of `after`, and what it does not combine with: all that can be said before the queries are
@@ -1340,6 +1419,40 @@ class VideoIndex(_Index):
                                    ops._stream()), 'mmt_search_col_lse')
     return lse
 
+  def _reverse_search(self, q, qw, k):
+    return self._col_topk(q, qw, k, False)[:2]
+
+  def _csls_norm(self, b, bw, k, hubs):
+    return HubNorm(self._col_topk(b, bw, min(k, b.shape[0]), True)[2], 2.0, b.shape[0], hubs, kind='csls', k=k)
+
+  def _col_topk(self, q, qw, k, want_mean):
+    """`reverse_search` and `csls_norm` behind their checks: q (NQ >= 1, M, d) / qw (NQ, M) fp32 on the index device,
+    1 <= k <= min(MAX_RK, NQ) -> (scores fp32 [num_items, k], rows int64 [num_items, k], mean fp32 [num_items]); with
+    want_mean only the mean is made, without it only the lists.  The rows go through in batches of whole 64-row blocks;
+    the running list per item (`state`) carries from one to the next and the outputs are asked for with the last.  Beyond
+    state and outputs nothing grows with NQ * num_items: a batch's partial lists are within _BATCH_BYTES, or one 64-row
+    block's where that alone is more.  Nothing here waits for the device."""
+    nq, nv = q.shape[0], self.num_items
+    L, nothing = _lib.lib(), _Scan()
+    scores = rows = mean = None
+    with torch.cuda.device(self.device):
+      if want_mean:
+        mean = torch.empty(nv, device=self.device, dtype=torch.float32)
+      else:
+        scores, rows = _lists(2, self.device, nv, k)
+      state = torch.empty(nv, k, device=self.device, dtype=torch.int64)   # uint64 keys
+      # a row's share of its block's partial lists: 8 k bytes per item / 64 rows
+      batches = self._row_batches(nq, -(-8 * k * nv // 64))
+      ws = torch.empty(L.mmt_col_topk_workspace_keys(batches[0][1], nv, k), device=self.device, dtype=torch.int64)
+      weight = float(torch.tensor(1.0 / k, dtype=torch.float32))
+      for r0, r1 in batches:
+        desc, _, _, _keep = self._describe(nothing, q, qw, r0, r1)
+        last = r1 == nq
+        check(L.mmt_search_col_topk(desc, k, r0, ops._p(ws), ops._p(state), int(r0 == 0), ops._p(scores if last else None),
+                                    ops._p(rows if last else None), ops._p(mean if last else None), weight,
+                                    ops._stream()), 'mmt_search_col_topk')
+    return scores, rows, mean
+
   def _search(self, q, qw, k, scan, grouping=None):
     """The top-k pass of `search` and `search_groups` behind their argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the
     index device, the scan's parts this index's own -> (scores, indices), with a grouping (scores, groups, items), one
@@ -1586,11 +1699,13 @@ class ShardedSubset:
 class ShardedHubNorm:
   """The querybank normaliser of a ShardedVideoIndex (ShardedVideoIndex.hub_norm): `parts[s]` is shard s's HubNorm in its
   own item numbers on its own device (None for a shard without items); `lse` fp32 [num_items] and `hubs` (bool
-  [num_items], or None) in global item order on the primary device; `beta`, `bank_size`, `num_items`, `device`."""
+  [num_items], or None) in global item order on the primary device; `beta`, `bank_size`, `num_items`, `device`; `kind`
+  and `k` as HubNorm's ('csls' from ShardedVideoIndex.csls_norm)."""
 
-  def __init__(self, parts, lse, beta, bank_size, hubs=None):
+  def __init__(self, parts, lse, beta, bank_size, hubs=None, *, kind='softmax', k=None):
     self.parts, self.lse, self.beta, self.bank_size, self.hubs = parts, lse, beta, bank_size, hubs
     self.num_items, self.device = lse.shape[0], lse.device
+    self.kind, self.k = kind, k
 
 
 class _Shard:
@@ -1783,6 +1898,46 @@ class ShardedVideoIndex(_Index):
         lse[ids] = mine.to(self.device)
       parts.append(part)
     return ShardedHubNorm(parts, lse, beta, b.shape[0], hubs)
+
+  def _per_item(self, run, outs):
+    """Fills outs -- per-item tensors [num_items, ...] on the primary -- from the shards: run(sh), called under the device
+    of every shard that holds items, gives that shard's tensors in its own item order; they are scattered to global item
+    order through sh.ids[:sh.num_items], as `_hub_norm` does with lse.  -> the shards' own results, None for an empty
+    shard."""
+    parts = []
+    for sh in self.shards:
+      part = None
+      if sh.num_items:
+        ids = sh.ids[:sh.num_items]
+        with torch.cuda.device(sh.device):
+          part = run(sh)
+        for out, mine in zip(outs, part):
+          out[ids] = mine.to(self.device)
+      parts.append(part)
+    return parts
+
+  def _reverse_search(self, q, qw, k):
+    """`reverse_search` behind its checks: every shard reverse-searches its own items with all the query rows, copied to
+    its device; a list depends on its item and the rows only, so the lists, scattered to global item order on the
+    primary, are bit-identical to those of one VideoIndex."""
+    outs = _lists(2, self.device, self.num_items, k)
+    self._per_item(lambda sh: sh.index._reverse_search(q.to(sh.device), qw.to(sh.device), k), outs)
+    return outs
+
+  def _csls_norm(self, b, bw, k, hubs):
+    """`csls_norm` behind its checks -> ShardedHubNorm, as `_hub_norm`: one 'csls' HubNorm per shard, r in global order."""
+    r = torch.empty(self.num_items, device=self.device, dtype=torch.float32)
+    kk = min(k, b.shape[0])
+    means = self._per_item(lambda sh: (sh.index._col_topk(b.to(sh.device), bw.to(sh.device), kk, True)[2],), (r,))
+    parts = []
+    for sh, mine in zip(self.shards, means):
+      part = None
+      if mine is not None:
+        with torch.cuda.device(sh.device):
+          part = HubNorm(mine[0], 2.0, b.shape[0], None if hubs is None else hubs[sh.ids[:sh.num_items]].to(sh.device),
+                         kind='csls', k=k)
+      parts.append(part)
+    return ShardedHubNorm(parts, r, 2.0, b.shape[0], hubs, kind='csls', k=k)
 
   def _merged(self, outs, live, kin, merge, tables, lists):
     """Fills outs -- result lists [NQ, kout] on the primary -- from the live shards: lists(s, sh), called under shard s's

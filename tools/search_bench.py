@@ -42,6 +42,14 @@ outputs of its own search_bench, --skip-materialised, run in the same session) a
 of this build, taken alternately with them.  The result goes under the key "norm" of
 --out (default profiles/search_bench.json), whose other content is kept.
 
+--reverse K times the reverse search (VideoIndex.reverse_search: for every stored item the K best query rows, 1 <= K <= 32)
+and the CSLS normaliser on top of it (VideoIndex.csls_norm) with the queries as the rows / the bank, per index dtype
+(--gallery-dtype, both = the two indexes): reverse_search(k = K), reverse_search(k = 32) and csls_norm(k = K), beside the
+lse pass of hub_norm over the same bank on the same index -- the same scan with the cheapest column pass, existing code,
+the yardstick -- and the plain search(k = 10).  --runs rounds, every variant once per round, interleaved; median and
+spread, and each cost as a ratio over the lse pass.  The result goes under the key "reverse" of --out (default
+profiles/search_bench.json), whose other content is kept.
+
 --range HITS times the range search (VideoIndex.range_search: every item at or above a per-query threshold, two scans) per
 index dtype (--gallery-dtype, both = the two indexes).  The thresholds are the HITS-th best score of each query (the last
 score of search(k = HITS), 1 <= HITS <= 128), so every query has at least HITS hits.  Beside it, on the same index:
@@ -310,6 +318,39 @@ def norm_mode(q, qw, g, gw, flop, a):
     row[n + '/summary'] = dict(search_norm_over_search=row[n + '/search_norm']['seconds_median'] / plain,
                                col_lse_over_search=row[n + '/col_lse']['seconds_median'] / plain,
                                rows_reordered_by_the_norm=float(moved))
+  return row
+
+
+def reverse_mode(q, qw, g, gw, flop, a):
+  """reverse_search at k = --reverse and k = 32, csls_norm, the lse pass of hub_norm (the yardstick) and the plain search,
+  per index dtype; the rows and the bank are the queries."""
+  nv = g.shape[0]
+  dtypes = ('float32', 'bfloat16') if a.gallery_dtype == 'both' else (a.gallery_dtype,)
+  names = ('col_lse', 'reverse_k%d' % a.reverse, 'reverse_k32', 'csls_norm_k%d' % a.reverse, 'search')
+  fns = {}
+  for n in dtypes:
+    index = VideoIndex.empty(nv, M, D, g.device, dtype=getattr(torch, n))
+    for at in range(0, nv, 8192):
+      index.add(g[at:at + 8192], gw[at:at + 8192])
+    calls = (lambda index=index: index.hub_norm(q, qw, 20.0), lambda index=index: index.reverse_search(q, qw, k=a.reverse),
+             lambda index=index: index.reverse_search(q, qw, k=32), lambda index=index: index.csls_norm(q, qw, k=a.reverse),
+             lambda index=index: index.search(q, qw, k=K))
+    fns.update({n + '/' + name: call for name, call in zip(names, calls)})
+  ts = {n: [] for n in fns}
+  mem = {n: 0 for n in fns}
+  for _ in range(a.runs):
+    for n, fn in fns.items():
+      t, _, m, _ = timed(fn, a.min_seconds)
+      ts[n].append(t)
+      mem[n] = max(mem[n], m)
+  row = {'k': a.reverse, 'rows': q.shape[0]}
+  for n in fns:
+    med = float(np.median(ts[n]))
+    row[n] = dict(seconds_median=med, seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n], tflops=flop / med / 1e12,
+                  peak_mem_growth_bytes=mem[n])
+  for n in dtypes:
+    lse = row[n + '/col_lse']['seconds_median']
+    row[n + '/summary'] = {name + '_over_col_lse': row[n + '/' + name]['seconds_median'] / lse for name in names[1:]}
   return row
 
 
@@ -708,6 +749,8 @@ def main():
                   'the visible devices, cycling, in place of the single index (default mode only)')
   ap.add_argument('--norm', type=float, default=None, metavar='BETA', help='time hub_norm (the lse pass, bank = the queries) '
                   'and search(norm=) against the plain search')
+  ap.add_argument('--reverse', type=int, default=0, metavar='K', help='time reverse_search (k = K and k = 32) and csls_norm '
+                  '(k = K), rows and bank = the queries, against the lse pass of hub_norm and search(k = 10)')
   ap.add_argument('--range', type=int, default=0, metavar='HITS', help='time range_search with per-query thresholds at the '
                   'HITS-th best score (1..128) against threshold_counts (T = 1) and search(k = 10)')
   ap.add_argument('--counts-only', action='store_true', help='with --range: the two yardsticks alone (runs on a build '
@@ -731,6 +774,11 @@ def main():
     raise SystemExit('--shards wants 1..32 and the default mode (no --ranks, --subset, --exclude, --gallery-dtype both)')
   if a.norm is not None and (masked or a.ranks or a.shards or not 0 < a.norm < math.inf):
     raise SystemExit('--norm wants 0 < BETA < inf and no --ranks, --subset, --exclude, --shards')
+  if not 0 <= a.reverse <= 32 or a.reverse and (masked or a.ranks or a.shards or a.norm is not None or a.range or a.groups or
+                                                a.pooled or a.item_pooled):
+    raise SystemExit('--reverse wants K in 1..32 and no other mode')
+  if a.reverse and a.out is None:
+    a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_bench.json')
   if not 0 <= a.range <= 128 or a.range and (masked or a.ranks or a.shards or a.norm is not None):
     raise SystemExit('--range wants 1..128 and no --ranks, --subset, --exclude, --shards, --norm')
   if a.groups < 0 or a.groups and (masked or a.ranks or a.shards or a.norm is not None or a.range):
@@ -806,6 +854,8 @@ def main():
       if runs:
         res[key] = {name: dict(seconds_runs=v, seconds_median=float(np.median(v)), seconds_spread=max(v) - min(v))
                     for name, v in runs.items()}
+  if a.reverse:
+    res.update(mode='reverse', gallery_dtype=a.gallery_dtype, runs=a.runs, min_seconds=a.min_seconds)
   if a.range:
     res.update(mode='range', hits=a.range, counts_only=a.counts_only, gallery_dtype=a.gallery_dtype, runs=a.runs,
                min_seconds=a.min_seconds)
@@ -835,9 +885,9 @@ def main():
     qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
     flop = 2.0 * nq * nv * M * D
     row = {'NQ': nq, 'NV': nv, 'flop': flop}
-    if (masked or a.ranks or a.norm is not None or a.range or a.groups or a.pooled or a.item_pooled or
+    if (masked or a.ranks or a.norm is not None or a.range or a.groups or a.pooled or a.item_pooled or a.reverse or
         a.gallery_dtype == 'both'):
-      mode = (norm_mode if a.norm is not None else range_mode if a.range else groups_mode if a.groups else
+      mode = (reverse_mode if a.reverse else norm_mode if a.norm is not None else range_mode if a.range else groups_mode if a.groups else
               pooled_mode if a.pooled else item_pooled_mode if a.item_pooled else
               subset_mode if masked else ranks_mode if a.ranks else both_dtypes)
       row.update(mode(q, qw, g, gw, flop, a))
@@ -874,10 +924,10 @@ def main():
     torch.cuda.empty_cache()
   if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    if a.norm is not None and os.path.exists(a.out):  # joins the default-mode results of that file
+    if (a.norm is not None or a.reverse) and os.path.exists(a.out):  # joins the default-mode results of that file
       with open(a.out) as f:
         kept = json.load(f)
-      kept['norm'] = res
+      kept['reverse' if a.reverse else 'norm'] = res
       res = kept
     with open(a.out, 'w') as f:
       json.dump(res, f, indent=1)
