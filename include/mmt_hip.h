@@ -667,6 +667,37 @@ int64_t mmt_col_topk_workspace_keys(int NB, int NV, int k);
 int mmt_search_col_topk(const MmtSearchScan* scan, int k, int row0, uint64_t* ws, uint64_t* state, int first,
                         float* scores, int64_t* rows, float* mean, float mean_weight, void* stream);
 
+/* Diversified search (search_diverse.hip), additive like the tenth scan: two entries without a descriptor, nothing that
+ * exists changes and mmt_abi_version() stays 6.  They serve search.py's `pair_scores`, `diversify` and `search_diverse`:
+ * max marginal relevance (Carbonell & Goldstein, SIGIR 1998) over a shortlist.
+ * mmt_search_pair_scores (fp32, bf16, fp8): the similarity of STORED items to each other.  g [NV][M * d] in `storage`
+ *   (MMT_SEARCH_FP32 / _BF16 / _FP8), gw fp32 [NV][M], gscale fp32 [NV] with fp8 and null otherwise; items int64 [R][C],
+ *   1 <= C <= MMT_SEARCH_MAX_DC, a value outside 0 .. NV - 1 is "none": checked on the device, never dereferenced -> sims
+ *   fp32 [R][C][C], sims[r][i][j] = sim(items[r][i], items[r][j]), NaN where either is none:
+ *     sim(g, h) = <f_g, f_h> / sum_m gw[g][m] gw[h][m]   (0 -> 1e-5),  f_g the dequantised stored row
+ *   the score of the scans with item g in the query's place.  fp32 accumulation on the matrix cores (fp32 rows:
+ *   v_mfma_f32_32x32x2_f32; bf16 rows and fp8 codes, which are exact bf16 values: one v_mfma_f32_32x32x16_bf16 per fragment);
+ *   the denominator is fma(gw[g][m], gw[h][m], den) for m ascending; with fp8 the accumulator is multiplied by
+ *   fl(gscale[g] * gscale[h]) -- powers of two -- as one rounded multiply before the division.  sim(g, h) has the bits of
+ *   sim(h, g) and is a function of the two stored rows, their weights and scales only: not of their places in the list, the
+ *   other candidates, R, NV or the shard.  One block per list; no workspace.  MMT_ERR_ARG: a null g, gw, items or sims, an
+ *   unknown storage, gscale given without fp8 or missing with it, C out of range, R / NV < 1, M outside 1 .. 16, d < 1 or
+ *   off the storage's multiple; MMT_ERR_ALIGN: g off a 16-byte boundary.
+ * mmt_search_mmr: the selection.  items int64 / rel fp32 [R][C]: per row a list of distinct candidates in the search's order
+ *   with its relevances, padded with (-1, -inf) -- what mmt_search_rescore with k = C returns; sims fp32 [R][C][C] the Gram of
+ *   exactly that list (mmt_search_pair_scores).  With n the number of items >= 0 (taken to be positions 0 .. n - 1), in fp32:
+ *   slot 0 is position 0 with value fl(a * rel[0]); for slot t >= 1 every unselected position p has pen_p, the largest
+ *   sim(p, s) over the selected s (a plain compare, the first of equals stays) and v_p = fl(fl(a * rel[p]) - fl(b * pen_p)) --
+ *   two rounded multiplies and a rounded subtract, never an fma -- and the position with the largest v_p is selected, -0
+ *   tied with +0, equal values to the lowest p (the order of the search's key over (v_p, p)).  Slot t of scores fp32 / index
+ *   int64 / values fp32 [R][k] holds (rel[p], items[p], v_p); slots from min(k, n) on hold (-inf, -1, -inf).  1 <= k <= C
+ *   <= MMT_SEARCH_MAX_DC, R >= 1 and no null pointer, else MMT_ERR_ARG.  One wave per row; no atomics in either entry. */
+#define MMT_SEARCH_MAX_DC 128
+int mmt_search_pair_scores(const void* g, const float* gw, const float* gscale, int storage, int NV, int M, int d,
+                           const int64_t* items, int R, int C, float* sims, void* stream);
+int mmt_search_mmr(const int64_t* items, const float* rel, const float* sims, int R, int C, int k, float a, float b,
+                   float* scores, int64_t* index, float* values, void* stream);
+
 /* Beside the scans.
  * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> the subset words, padding included: one ballot per 64
  *   items, one writer per word.

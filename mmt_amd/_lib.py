@@ -258,6 +258,9 @@ SIGNATURES = {
     # the tenth, additive: the running top-k per item over a stream of query rows (reverse_search, csls_norm)
     'mmt_col_topk_workspace_keys': (c_i64, [c_int, c_int, c_int]),
     'mmt_search_col_topk': (c_int, [_SCAN, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_f32, c_vp]),
+    # diversified search, additive and without a descriptor: the Gram of stored items, the MMR selection
+    'mmt_search_pair_scores': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp]),
+    'mmt_search_mmr': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

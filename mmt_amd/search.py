@@ -250,6 +250,36 @@ that of fl(fl(2 * score(q, g)) - r[g]): the norm slot above with beta = 2 and r 
 of its own, and `search`, `rank_counts`, `ranks`, `target_scores`, `threshold_counts`, the dynamic rule, after=, subset=,
 exclude=, both index classes and metric.retrieval_metrics_indexed(bank_norm='csls', bank_k=) take it as they take a
 `hub_norm`.  Like `hub_norm` it is refused on a float8_e4m3fn index, because norm= is.
+
+    sims = index.pair_scores(candidates)                                   # int64 [R, C <= MAX_DC = 128] -> float32 [R, C, C]
+    scores, indices, values = index.diversify(q, qw, candidates, k=10, lam=0.5)
+    scores, indices, values = index.search_diverse(q, qw, k=10, lam=0.5, shortlist=MAX_K, subset=None, exclude=None, coarse=None)
+
+The tenth question: the k best items that are not copies of one another.  The nine above rank by relevance alone, and on a
+gallery of clips cut from long videos, re-uploads and crops the top of a list is often one thing several times;
+`search_groups` removes such copies only where somebody has labelled them.  Max marginal relevance (Carbonell & Goldstein,
+SIGIR 1998) repeatedly picks the item most relevant to the query and least similar to the items already picked.  That
+needs the one quantity nothing above computes, the similarity of two STORED items to each other, defined on the stored
+values like every score here: with f_g the dequantised stored row (float32: the row; bfloat16: widened; float8_e4m3fn:
+code * scales[g]),
+    sim(g, h) = <f_g, f_h> / sum_m gw[g][m] gw[h][m]      (0 -> 1e-5)
+the 'indep' similarity with item g in the query's place, in fp32 on the matrix cores: one block per shortlist gathers its
+rows through a row indirection on BOTH operands and computes the C x C Gram in place (mmt_search_pair_scores), where the
+torch route -- index_select of the shortlist rows, then torch.bmm -- materialises 7.5 GB of gathered operands for 4 096
+shortlists of 128 rows of 3 584.  sim(g, h) has the bits of sim(h, g) and depends on the two stored rows, their weights and
+scales only.  `diversify` is rescore(q, qw, candidates, k=None) -- the distinct candidates in `search`'s order with
+`search`'s score bits, rel -- followed by the Gram of that list and the selection (mmt_search_mmr), in fp32 with
+a = float32(lam) and b = float32(1.0 - lam): slot 0 is the most relevant item with value fl(a * rel); then every unselected
+p has pen_p = the largest sim(p, s) over the selected s and
+    v_p = fl(fl(a * rel_p) - fl(b * pen_p))        two rounded multiplies and a rounded subtract, never an fma
+and the largest v_p is selected, -0 tied with +0, equal values to the item earlier in `search`'s order; numpy restates it
+bit for bit.  Slot t returns the item's relevance, its number and v_p, and a row that runs out of candidates ends in
+(-inf, -1, -inf).  lam=1 is `rescore` bit for bit; the result depends on a row's candidates as a set.  `search_diverse` is
+host code like `search_refined`: (coarse or self).search(k=shortlist, subset=, exclude=), then `diversify` on this index.
+ShardedVideoIndex has the three calls, bit-identical: per row batch every shard copies the stored bytes, weights and scales
+of the batch's distinct candidates into a staging index on the primary, the candidates are renumbered into it and the same
+kernel runs there -- exact, because sim depends on the two stored rows alone.  Out of scope: norm=, pooling=, item_pooling=,
+grouping= and after= raise ValueError naming the option.
 """
 import ctypes
 import math
@@ -265,6 +295,8 @@ MAX_T = 32  # targets per query and launch of the rank kernels; wider target lis
 MAX_E = 32  # exclusions per query of a masked search
 MAX_RK = 32  # query rows per item of `reverse_search` and `csls_norm`: a wave's list of the fold is k + 64 keys of LDS
 MAX_C = 1024  # candidates per query of `rescore`: one query's keys are sorted in LDS
+MAX_DC = 128  # candidates per query of `pair_scores` and `diversify`: one block computes a list's C x C Gram
+_NOT_DIVERSE = ('norm', 'dynamic', 'pooling', 'item_pooling', 'grouping', 'after')  # options `diversify` refuses by name
 MAX_SET = 64  # rows per query set of a pooled scan: one 64-row query block holds whole sets
 MAX_ITEM_SET = 128  # items per stored set of an item-pooled scan: one 128-column tile holds whole sets
 _POOL_MODES = {'mean': 0, 'max': 1}  # the `mode` of the pooled entry points
@@ -1153,6 +1185,131 @@ class _Index:
     _, shortlisted = coarse.search(embds, weights, k=shortlist, subset=subset, exclude=exclude)
     return self.rescore(embds, weights, shortlisted, k)
 
+  def _candidate_lists(self, who, candidates):
+    """Type, device and shape of the candidate lists of `pair_scores` and `diversify`, in the words of `rescore`'s checks."""
+    if not torch.is_tensor(candidates) or candidates.dtype != torch.int64:
+      raise ValueError('%s: candidates must be an int64 tensor, got %s' % (
+          who, candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__))
+    if candidates.device != self.device:
+      raise ValueError('%s: candidates must be on the index device %s, got %s' % (who, self.device, candidates.device))
+    if candidates.dim() != 2 or not 1 <= candidates.shape[1] <= MAX_DC:
+      raise ValueError('%s: candidates [R, 1 <= C <= %d] expected, got %s' % (who, MAX_DC, tuple(candidates.shape)))
+
+  def _candidate_range(self, who, cand):
+    """The values of the (non-empty) candidates against -1 .. num_items - 1: one small reduction and a host sync."""
+    lo, hi = (int(v) for v in torch.aminmax(cand))
+    if lo < -1 or hi >= self.num_items:
+      raise ValueError('%s: candidates must lie in -1 .. %d, got %d .. %d' % (who, self.num_items - 1, lo, hi))
+
+  @staticmethod
+  def _diverse_args(who, k, lam, unsupported):
+    """The checks `diversify` and `search_diverse` share: the options that are out of scope by name, k and lam."""
+    for name in unsupported:
+      if name not in _NOT_DIVERSE:
+        raise TypeError('%s() got an unexpected keyword argument %r' % (who, name))
+      raise ValueError('%s: %s= is out of scope: the relevance of a diversified list is the plain score' % (who, name))
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+      raise ValueError('%s: k must be an int in 1..%d, got %r' % (who, MAX_K, k))
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0 <= lam <= 1:
+      raise ValueError('%s: lam must be a number with 0 <= lam <= 1, got %r' % (who, lam))
+
+  @staticmethod
+  def _list_batches(rows, c):
+    """Row ranges of the Gram launches: the [rows, C, C] fp32 workspace of a batch stays within _BATCH_BYTES."""
+    batch = max(1, _BATCH_BYTES // (4 * c * c))
+    return [(r0, min(rows, r0 + batch)) for r0 in range(0, rows, batch)]
+
+  def pair_scores(self, candidates):
+    """candidates int64 [R, C] on the index device, 1 <= C <= MAX_DC = 128, values -1 .. num_items - 1 (-1 = none), in any
+    order, an item as often as it comes -> sims float32 [R, C, C] on the device: sims[r, i, j] = sim(candidates[r, i],
+    candidates[r, j]), NaN where either is none, with
+        sim(g, h) = <f_g, f_h> / sum_m gw[g][m] gw[h][m]     (0 -> 1e-5)
+    f_g the dequantised stored row of item g (float32: the row; bfloat16: widened; float8_e4m3fn: code * scales[g]): the
+    'indep' similarity with item g in the query's place, in fp32 on the matrix cores (mmt_search_pair_scores).  sim(g, h)
+    has the bits of sim(h, g) and is a function of the two stored rows, their weights and scales only -- not of their
+    places in the list, the other candidates, the row batching, num_items or the shard: ShardedVideoIndex.pair_scores is
+    bit-identical.  No gathered copy of the rows is made on one index; one block per list reads them in place.  The range
+    of the candidates is checked (one small reduction and a host sync) before anything is scored."""
+    self._candidate_lists('pair_scores', candidates)
+    if self.num_items == 0:
+      raise ValueError('pair_scores: the index holds no items')
+    r, c = candidates.shape
+    sims = torch.empty(r, c, c, device=self.device, dtype=torch.float32)
+    if r == 0:
+      return sims
+    cand = candidates.contiguous()
+    self._candidate_range('pair_scores', cand)
+    for r0, r1 in self._list_batches(r, c):
+      self._pair_scores(cand[r0:r1], sims[r0:r1])
+    return sims
+
+  def diversify(self, embds, weights, candidates, k=10, lam=0.5, **unsupported):
+    """Max marginal relevance over per-query shortlists (Carbonell & Goldstein, SIGIR 1998).  Queries as for `search`;
+    candidates int64 [NQ, C <= MAX_DC = 128] as for `rescore` (-1 = none, any order, repeats allowed); k an int in
+    1 .. MAX_K; 0 <= lam <= 1 -> (scores float32, indices int64, values float32), each [NQ, k'], k' = min(k, C).  First
+    rescore(embds, weights, candidates, k=None): the distinct candidates of a row in `search`'s order with `search`'s score
+    bits, rel -- nothing about relevance is new.  Then, with a = float32(lam), b = float32(1.0 - lam) and sim the
+    `pair_scores` of that list, in fp32: slot 0 is the most relevant item, with value fl(a * rel); for every further slot
+    each unselected item p has pen_p, the largest sim(p, s) over the selected s, and
+        v_p = fl(fl(a * rel_p) - fl(b * pen_p))           two rounded multiplies and a rounded subtract, never an fma
+    and the item with the largest v_p is selected: -0 ties with +0, equal values go to the item earlier in `search`'s
+    order (mmt_search_mmr).  Slot t holds the item's relevance (the `search` bits), its number and v_p; a row with fewer
+    than k' distinct candidates ends in (-inf, -1, -inf).  lam=1 is `rescore`, bit for bit, with values == scores; lam=0
+    picks, after the most relevant item, whatever is least like the ones picked.  The result depends on a row's
+    candidates as a set, not on their order, the row batching (the [rows, C, C] Gram workspace stays within
+    _BATCH_BYTES) or the launch geometry, and ShardedVideoIndex.diversify is bit-identical.  Out of scope: norm=, pooling=,
+    item_pooling=, grouping= and after= raise ValueError naming the option."""
+    self._diverse_args('diversify', k, lam, unsupported)
+    self._candidate_lists('diversify', candidates)
+    shape = tuple(getattr(embds, 'shape', ()))  # the query rows as the shape alone says them (text layout: b * C + c)
+    rows = shape[0] if len(shape) == 3 else shape[0] * shape[2] if len(shape) == 4 else None
+    if rows is not None and candidates.shape[0] != rows:
+      raise ValueError('diversify: %d queries but candidates %s' % (rows, tuple(candidates.shape)))
+    if self.num_items == 0:
+      raise ValueError('diversify: the index holds no items')
+    q, qw = self._queries(embds, weights)   # (any other shape is refused here)
+    nq, c = q.shape[0], candidates.shape[1]
+    k = min(k, c)
+    if nq == 0:
+      return _lists(2, self.device, 0, k) + (torch.empty(0, k, device=self.device, dtype=torch.float32),)
+    cand = candidates.contiguous()
+    self._candidate_range('diversify', cand)
+    rel, items = self._rescore(q, qw, cand, c)
+    scores, indices = _lists(2, self.device, nq, k)
+    values = torch.empty(nq, k, device=self.device, dtype=torch.float32)
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._list_batches(nq, c):
+        sims = torch.empty(r1 - r0, c, c, device=self.device, dtype=torch.float32)
+        self._pair_scores(items[r0:r1], sims)
+        check(_lib.lib().mmt_search_mmr(ops._p(items[r0:r1]), ops._p(rel[r0:r1]), ops._p(sims), r1 - r0, c, k, lam, 1.0 - lam,
+                                        ops._p(scores[r0:r1]), ops._p(indices[r0:r1]), ops._p(values[r0:r1]), ops._stream()),
+              'mmt_search_mmr')
+    return scores, indices, values
+
+  def search_diverse(self, embds, weights, k=10, lam=0.5, shortlist=MAX_K, subset=None, exclude=None, coarse=None,
+                     **unsupported):
+    """The diversified search as one call, host code in the manner of `search_refined`: (coarse or self).search(embds,
+    weights, k=shortlist, subset=subset, exclude=exclude), then self.diversify(embds, weights, that list, k, lam) ->
+    (scores, indices, values) [NQ, min(k, the list's width)].  shortlist an int in 1 .. MAX_K; coarse: None, or a
+    VideoIndex / ShardedVideoIndex TAKEN to hold the same items under the same numbers (same num_items, num_experts, dim
+    and device is all that can be checked) -- typically a float8_e4m3fn one; subset and exclude are the searching
+    index's and are checked by it.  Relevance and item-item similarity are this index's.  Out of scope as `diversify`."""
+    self._diverse_args('search_diverse', k, lam, unsupported)
+    if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not 1 <= shortlist <= MAX_K:
+      raise ValueError('search_diverse: shortlist must be an int in 1..%d, got %r' % (MAX_K, shortlist))
+    if coarse is not None:
+      if not isinstance(coarse, _Index):
+        raise ValueError('search_diverse: coarse must be a VideoIndex or ShardedVideoIndex, got %s' % type(coarse).__name__)
+      mine, theirs = ((i.num_items, i.num_experts, i.dim) for i in (self, coarse))
+      if mine != theirs:
+        raise ValueError('search_diverse: the coarse index holds (num_items, num_experts, dim) = %s, this one %s' % (theirs, mine))
+      if coarse.device != self.device:
+        raise ValueError('search_diverse: the coarse index is on %s, this one on %s' % (coarse.device, self.device))
+    if self.num_items == 0:
+      raise ValueError('search_diverse: the index holds no items')
+    _, shortlisted = (self if coarse is None else coarse).search(embds, weights, k=shortlist, subset=subset, exclude=exclude)
+    return self.diversify(embds, weights, shortlisted, k, lam)
+
   def _group_ids(self, group_ids):
     """The checks of `grouping` -> (the ids as int32 [num_items] of their own, the number of distinct ids)."""
     if self.num_items == 0:
@@ -1502,6 +1659,16 @@ class VideoIndex(_Index):
         check(L.mmt_search_rescore(desc, ops._p(cand[r0:r1]), c, k, ops._p(ws), ops._p(outs[0][r0:r1]),
                                    ops._p(outs[1][r0:r1]), ops._stream()), 'mmt_search_rescore')
     return outs
+
+  def _pair_scores(self, cand, sims):
+    """`pair_scores` behind its checks, one row batch: cand int64 [R >= 1, C] (contiguous, item numbers, one outside
+    0 .. num_items - 1 = none) -> sims float32 [R, C, C] (contiguous), both on the index device.  One launch; nothing here
+    waits for the device."""
+    r, c = cand.shape
+    with torch.cuda.device(self.device):
+      check(_lib.lib().mmt_search_pair_scores(ops._p(self.folded), ops._p(self.weights), ops._p(self.scales),
+                                              _STORAGE[self.dtype], self.num_items, self.num_experts, self.dim, ops._p(cand),
+                                              r, c, ops._p(sims), ops._stream()), 'mmt_search_pair_scores')
 
   def _rank_counts(self, q, qw, tg, scan):
     """`rank_counts` behind its checks: tg int64 [NQ >= 1, T] on the index device (with a pooling [num_sets, T], with an
@@ -1980,6 +2147,39 @@ class ShardedVideoIndex(_Index):
     local = {s: self._local(cand, s) for s, _ in live}  # translated on the primary, where the item maps are
     lists = lambda s, sh: sh.index._rescore(q.to(sh.device), qw.to(sh.device), local[s].to(sh.device), k)
     return self._merged(outs, live, k, 'mmt_search_merge_lists', self._tables(tuple(s for s, _ in live)), lists)
+
+  def _pair_scores(self, cand, sims):
+    """`pair_scores` behind its checks, one row batch: cand (global numbers) and sims on the primary.  The stored rows of
+    two candidates may lie on different shards, so every shard copies the stored bytes, weights and scales of the batch's
+    distinct candidates it holds into a staging VideoIndex on the primary (item j of it is the j-th smallest distinct
+    candidate); the candidates are renumbered into it and the one kernel runs there.  sim depends on the two stored rows,
+    their weights and scales alone, so the bits are those of one VideoIndex.  The staging's size is the one wait for the
+    device."""
+    live = cand >= 0
+    distinct = torch.unique(cand[live])   # ascending
+    n = distinct.numel()
+    if n == 0:
+      sims.fill_(float('nan'))
+      return
+    with torch.cuda.device(self.device):
+      staging = VideoIndex.empty(n, self.num_experts, self.dim, self.device, dtype=self.dtype)
+    stored = staging.folded.view(torch.uint8)   # bytes: a copy, whatever the dtype
+    where, local = self._shard_of[distinct], self._local_of[distinct]
+    for s, sh in self._live():
+      at = torch.nonzero(where == s).reshape(-1)
+      if at.numel() == 0:
+        continue
+      with torch.cuda.device(sh.device):
+        rows = local[at].to(sh.device)
+        parts = [sh.index.folded.view(torch.uint8)[rows], sh.index.weights[rows],
+                 None if sh.index.scales is None else sh.index.scales[rows]]
+      stored[at] = parts[0].to(self.device)
+      staging.weights[at] = parts[1].to(self.device)
+      if parts[2] is not None:
+        staging.scales[at] = parts[2].to(self.device)
+    staging.num_items = n
+    renumbered = torch.where(live, torch.searchsorted(distinct, cand.clamp(min=0)), torch.full_like(cand, -1))
+    staging._pair_scores(renumbered, sims)
 
   def grouping(self, group_ids):
     """group_ids: int64 [num_items] on the primary device, as VideoIndex.grouping -> ShardedGrouping: the ids cut into one

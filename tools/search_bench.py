@@ -97,7 +97,14 @@ interleaved; median and spread; the share of rows on which `rescore` and the com
 k = 10 (search(after=) from the last column of page 1) beside the plain search(k = 10) of the same build, the plain search at
 k = 32, 64 and 128 (how the cost of a page grows with its width) and search_deep(depth = 256) at page = 32, 64 and 128.
 --runs rounds, every variant once per round, interleaved; median and spread; whether page 2 and the deep lists are the
-slices of the plain k = 128 list they must be.  Default output profiles/search_after_bench.json."""
+slices of the plain k = 128 list they must be.  Default output profiles/search_after_bench.json.
+
+--diverse times the stages of `search_diverse` over 262 144 items with 4 096 queries, shortlist 128, k = 10, on a float32, a
+bf16 and an fp8 index: search(k = 128) alone, `rescore`, the Gram launches (mmt_search_pair_scores, in diversify's row
+batches), the selection launch (mmt_search_mmr), the whole call, and the torch route to the Gram (index_select of the
+shortlist rows + torch.bmm, in row batches under the same _BATCH_BYTES budget); the Gram launch's share of the fp32 or bf16
+matrix peak.  --runs rounds, every variant once per round, interleaved; median and spread.  Joins --out (default
+profiles/search_bench.json) under 'diverse'."""
 import argparse
 import json
 import math
@@ -723,8 +730,106 @@ def after_mode(a, dev):
   return row
 
 
+PEAK_BF16 = 2.5e15  # dense bf16 matrix peak
+
+
+def torch_gram(index, items, budget):
+  """The torch route to the Gram of `pair_scores`: index_select of the shortlist rows, widened to a dtype torch.bmm takes
+  (an fp8 row to bf16, exactly), one batched matmul, the same for the weights, and the division -- in row batches whose
+  gathered operand stays within `budget` bytes.  -> float32 [R, C, C]."""
+  r, c = items.shape
+  wide = torch.float32 if index.dtype is torch.float32 else torch.bfloat16
+  kk = index.folded.shape[1]
+  rows = max(1, budget // (c * kk * (4 if wide is torch.float32 else 2)))
+  out = torch.empty(r, c, c, device=items.device, dtype=torch.float32)
+  stored = index.folded.view(torch.uint8)
+  for r0 in range(0, r, rows):
+    at = items[r0:r0 + rows].clamp(min=0).reshape(-1)
+    f = stored.index_select(0, at).view(index.dtype).to(wide).view(-1, c, kk)
+    w = index.weights.index_select(0, at).view(-1, c, index.num_experts)
+    num = torch.bmm(f, f.transpose(1, 2)).float()
+    if index.scales is not None:
+      s = index.scales.index_select(0, at).view(-1, c)
+      num = num * (s[:, :, None] * s[:, None, :])
+    den = torch.bmm(w, w.transpose(1, 2))
+    out[r0:r0 + rows] = num / torch.where(den == 0, torch.full_like(den, 1e-5), den)
+  return out
+
+
+def diverse_mode(a, dev):
+  """The stages of `search_diverse` over NV = 262 144 items, NQ = 4 096, shortlist C = 128, k = 10, per storage dtype:
+  search(k = 128) alone, `rescore` of that list, the Gram launches (mmt_search_pair_scores in diversify's row batches), the
+  selection launch (mmt_search_mmr) and the torch route to the same Gram under the same byte budget."""
+  from mmt_amd import search
+  nq, nv = SHAPES['S3']
+  chunk, c = 8192, 128
+  gen = torch.Generator(device=dev).manual_seed(0)
+  nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
+  dtypes = {'float32': torch.float32, 'bfloat16': torch.bfloat16, 'float8_e4m3fn': torch.float8_e4m3fn}
+  idx = {n: VideoIndex.empty(nv, M, D, dev, dtype=t) for n, t in dtypes.items()}
+  for at in range(0, nv, chunk):
+    g = nrm(torch.randn(chunk, M, D, device=dev, generator=gen))
+    gw = torch.softmax(torch.randn(chunk, M, device=dev, generator=gen), -1)
+    for index in idx.values():
+      index.add(g, gw)
+  q = nrm(torch.randn(nq, M, D, device=dev, generator=gen) + 0.3 * g[torch.arange(nq, device=dev) % chunk])
+  qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
+  L = _lib.lib()
+
+  def gram(index, items):
+    for r0, r1 in index._list_batches(nq, c):
+      sims = torch.empty(r1 - r0, c, c, device=dev, dtype=torch.float32)
+      index._pair_scores(items[r0:r1], sims)
+    return sims
+
+  def mmr(rel, items, sims):
+    outs = (torch.empty(nq, K, device=dev), torch.empty(nq, K, device=dev, dtype=torch.int64), torch.empty(nq, K, device=dev))
+    _lib.check(L.mmt_search_mmr(ops._p(items), ops._p(rel), ops._p(sims), nq, c, K, 0.5, 0.5, *[ops._p(o) for o in outs],
+                                ops._stream()), 'mmt_search_mmr')
+    return outs
+
+  fns, kept = {}, {}
+  for n, index in idx.items():
+    cand = index.search(q, qw, k=c)[1]
+    rel, items = index.rescore(q, qw, cand)
+    kept[n] = (rel, items, index.pair_scores(items))
+    fns[n + '/search_k128'] = lambda index=index: index.search(q, qw, k=c)
+    fns[n + '/rescore'] = lambda index=index, cand=cand: index.rescore(q, qw, cand)
+    fns[n + '/gram'] = lambda index=index, items=items: gram(index, items)
+    fns[n + '/mmr'] = lambda n=n: mmr(*kept[n])
+    fns[n + '/gram_torch'] = lambda index=index, items=items: torch_gram(index, items, search._BATCH_BYTES)
+    fns[n + '/search_diverse'] = lambda index=index: index.search_diverse(q, qw, k=K, lam=0.5, shortlist=c)
+  ts = {n: [] for n in fns}
+  for r in range(a.runs):
+    for n, fn in fns.items():
+      t, _, _, _ = timed(fn, a.min_seconds)
+      ts[n].append(t)
+    print('round %d of %d' % (r + 1, a.runs), file=sys.stderr, flush=True)
+  flop = 2.0 * nq * c * c * M * D
+  row = {'NQ': nq, 'NV': nv, 'C': c, 'gram_flop': flop, 'torch_gather_bytes_fp32': nq * c * M * D * 4}
+  for n in fns:
+    row[n] = dict(seconds_median=float(np.median(ts[n])), seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n])
+  for n, index in idx.items():
+    ours, theirs = row[n + '/gram'], row[n + '/gram_torch']
+    peak = PEAK if n == 'float32' else PEAK_BF16
+    ref = torch_gram(index, kept[n][1], search._BATCH_BYTES)
+    live = ~torch.isnan(kept[n][2])
+    row[n + '/summary'] = dict(
+        torch_over_gram=theirs['seconds_median'] / ours['seconds_median'],
+        spread_seconds=max(ours['seconds_spread'], theirs['seconds_spread']),
+        gram_tflops=flop / ours['seconds_median'] / 1e12, gram_fraction_of_matrix_peak=flop / ours['seconds_median'] / peak,
+        matrix_peak_flops=peak,
+        max_abs_difference_to_torch=float((kept[n][2] - ref)[live].abs().max()),
+        stages_over_search_k128={s: row[n + '/' + s]['seconds_median'] / row[n + '/search_k128']['seconds_median']
+                                 for s in ('rescore', 'gram', 'mmr')})
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
+  ap.add_argument('--diverse', action='store_true', help='time the stages of search_diverse (shortlist 128, k = 10) on a '
+                  'float32, a bf16 and an fp8 index of 262 144 items: search(k = 128), rescore, the Gram launches, the '
+                  'selection launch and the torch route to the Gram (no other mode flag)')
   ap.add_argument('--after', action='store_true', help='time cursor paging on a bf16 and an fp8 index of 262 144 items: page 2 '
                   'at k = 10 against search(k = 10), the plain search at k = 32 / 64 / 128 and search_deep(256) at page '
                   '32 / 64 / 128 (no other mode flag)')
@@ -808,6 +913,21 @@ def main():
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
+  if a.diverse:
+    res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'diverse', 'runs': a.runs,
+           'min_seconds': a.min_seconds}
+    res.update(diverse_mode(a, dev))
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_bench.json')
+    kept = {}
+    if os.path.exists(out):  # joins the default-mode results of that file, as --norm and --reverse do
+      with open(out) as f:
+        kept = json.load(f)
+    kept['diverse'] = res
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+      json.dump(kept, f, indent=1)
+    print(json.dumps(res))
+    return
   if a.after:
     res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'after', 'runs': a.runs,
            'min_seconds': a.min_seconds}
