@@ -154,7 +154,8 @@ typedef struct MmtWgradItem {
   int32_t reserved; /* > 0: this item contracts over exactly `reserved` rows (overrides rows / n_rows_dev)     */
   float* slab;      /* splits > 1: partial results [splits][N_out, ldo] (summed by the caller, e.g.            */
   float* bias_slab; /*   mmt_col_reduce_multi) and partial bias gradients [splits][N_out]                       */
-  int32_t splits, reserved2; /* reserved2: set by mmt_wgrad_grouped (tile patch shape), callers leave it 0 */
+  int32_t splits, reserved2; /* reserved2: set by mmt_wgrad_grouped (tile patch shape; bit 30: longest-first launch
+                              * order, below), callers leave it 0 */
   const int32_t* n_rows_dev; /* nullable: this item contracts over *n_rows_dev rows (device; overrides the group's) */
 } MmtWgradItem;
 typedef struct MmtWgradGroup {
@@ -162,6 +163,8 @@ typedef struct MmtWgradGroup {
   const int32_t* n_rows_dev; /* nullable live row count on device                                    */
   int32_t count, rows;
 } MmtWgradGroup;
+/* A group whose blocks differ in length (an item with splits > 1 or reserved > 0 next to others; lengths from `rows` and
+ * `reserved`, the row counts the host knows) is launched longest blocks first, item by item.  Results do not depend on it. */
 int mmt_wgrad_grouped(const MmtWgradGroup* g, void* stream);
 
 /* out[i] (+)= sum_s ws[s][i] over a [rows, cols_ws] slab keeping only the first cols_out columns

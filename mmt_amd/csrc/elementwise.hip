@@ -130,6 +130,9 @@ __device__ __forceinline__ AdamHyper adam_hyper(float lr, float beta1, float bet
 // First half of a unit: loads, update, stores of p / m / v (+ the row-major bf16 shadow), and the fp32 values of a
 // matrix tile into `tile` for the transposed shadow.  tid in [0, 256).  Returns true when adam_unit_store_t must follow
 // AFTER a barrier over the 256 threads that share `tile`.
+// Cache policy: g, m and v stream through non-temporal accesses; p and the bf16 shadows keep the default policy.  p with
+// non-temporal accesses too was measured and lost (profiles/step_trims_ab.txt): the launch stayed at 118 us and the first
+// two kernels of the next step, which read fp32 weights out of p, took 2.6 us longer.
 __device__ __forceinline__ bool adam_unit_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                  float* __restrict__ v, const MmtAdamSeg& seg, int lb, int tid,
                                                  float (*tile)[65], const AdamHyper& h) {

@@ -321,6 +321,7 @@ __device__ __forceinline__ bf16x8_t tr_join(const u32x2& lo, const u32x2& hi) {
   return __builtin_bit_cast(bf16x8_t, v);
 }
 
+#define WGRAD_LISTED (1 << 30)  // MmtWgradItem.reserved2: see wgrad_phased_kernel's block order
 #ifdef MMT_GEMM2_INSTR
 __device__ long long* g_wgrad_dbg = nullptr;  // instrumented build only: per-block cycle counters
 extern "C" int mmt_debug_set_wgrad_buffer(void* p) {
@@ -351,7 +352,15 @@ __global__ __launch_bounds__(512) void wgrad_phased_kernel(MmtWgradGroup g) {
   const long long t_entry = clock64();
 #endif
   bf16_t* smem = (bf16_t*)wg_smem;  // ring: 4 units x [A 64x128 | B 64x128]
-  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  // Block -> (item, tile, split).  Launches whose blocks all run equally long take ONE XCD-aware remap over the whole grid:
+  // an XCD then works on ~32 consecutive tiles of one item.  Launches that mix long and short blocks (row splits, compact
+  // items: WGRAD_LISTED, set by the host, which has also sorted the items longest blocks first) keep the item order as the
+  // DISPATCH order and remap inside each item instead: workgroups go to the XCDs round-robin, so every XCD starts on its
+  // eighth of the long blocks and fills up with short ones as CUs come free.  One remap over the whole grid hands the
+  // first XCDs nothing but long blocks, two rounds deep, while the others run out of work (the last layer's launch:
+  // 192 blocks of 15 units + 208 of 4 on 256 CUs took what 30 units take).
+  const bool listed = (g.item[0].reserved2 & WGRAD_LISTED) != 0;
+  const int id = listed ? (int)blockIdx.x : xcd_remap(blockIdx.x, gridDim.x);
   int p = 0;
 #pragma unroll 1
   for (int q = 1; q < g.count; ++q)
@@ -361,14 +370,16 @@ __global__ __launch_bounds__(512) void wgrad_phased_kernel(MmtWgradGroup g) {
   const bf16_t* __restrict__ B = (const bf16_t*)it.B;
   const int64_t lda = it.lda, ldb = it.ldb;
   const int nsplit = it.splits > 1 ? it.splits : 1;
-  const int tile = (id - it.tile_begin) / nsplit, split = (id - it.tile_begin) % nsplit;
   const int tiles_k = it.K2 / 128;
+  // (listed: the item's blocks that share an XCD are those of one residue of the local index -- a contiguous run of its ids)
+  const int local = listed ? xcd_remap(id - it.tile_begin, (it.N / 128) * tiles_k * nsplit) : id - it.tile_begin;
+  const int tile = local / nsplit, split = local % nsplit;
   // Tile order inside an item: patches of PN x PK tiles (reserved2 = PN << 16 | PK, chosen by the host so that PN * PK is
   // about the 32 consecutive ids one XCD receives): the tiles that share an L2 then share as few distinct operand panels
   // as possible (8 x 4 or 4 x 8 tiles = 12 panels; a row-major run over a 4 x 24 grid = 34).
   int tn, tk;
   {
-    const int PN = it.reserved2 >> 16, PK = it.reserved2 & 0xffff;
+    const int PN = (it.reserved2 >> 16) & 0xff, PK = it.reserved2 & 0xffff;
     if (PN > 0 && PK > 0) {
       const int per = PN * PK, patches_k = tiles_k / PK;
       const int patch = tile / per, within = tile % per;
@@ -663,6 +674,25 @@ extern "C" int mmt_wgrad_grouped(const MmtWgradGroup* g, void* stream) {
       return mmt_wgrad3_launch(h, tb, (hipStream_t)stream);
     }
   }
+  // Blocks of different lengths in one launch (an item split over its rows, or contracting over its own row count): the
+  // items are launched longest blocks first (a stable sort of the group's copy -- items are independent of each other), a
+  // pure function of the group's shape.  The length of a block = 64-row units per split, from the rows the host knows of.
+  bool listed = false;
+  {
+    int len[MMT_WGRAD_MAX];
+    for (int q = 0; q < h.count; ++q) {
+      const MmtWgradItem& it = h.item[q];
+      const int rows_q = it.reserved > 0 ? it.reserved : h.rows, sp = it.splits > 1 ? it.splits : 1;
+      len[q] = ((rows_q + 63) / 64 + sp - 1) / sp;
+      listed = listed || len[q] != len[0];
+    }
+    if (listed)
+      for (int q = 1; q < h.count; ++q)  // insertion sort, descending, stable
+        for (int r = q; r > 0 && len[r] > len[r - 1]; --r) {
+          const MmtWgradItem ti = h.item[r]; h.item[r] = h.item[r - 1]; h.item[r - 1] = ti;
+          const int tl = len[r]; len[r] = len[r - 1]; len[r - 1] = tl;
+        }
+  }
   for (int q = 0; q < h.count; ++q) {
     MmtWgradItem& it = h.item[q];
     if (!it.A || !it.B || !it.out || it.N <= 0 || it.K2 <= 0 || it.N % 128 || it.K2 % 128) return MMT_ERR_ARG;
@@ -682,7 +712,7 @@ extern "C" int mmt_wgrad_grouped(const MmtWgradGroup* g, void* stream) {
         if (tn_all % c == 0) pn = c;
       for (int c = 1; c <= 32 / pn; ++c)
         if (tk_all % c == 0) pk = c;
-      it.reserved2 = (pn << 16) | pk;
+      it.reserved2 = (pn << 16) | pk | (listed ? WGRAD_LISTED : 0);
     }
   }
   constexpr int lds = 36 * 256 * 16;  // a 128 KiB ring of 4 units x (A + B) 64x128 bf16; 144 KiB for the final exchange

@@ -72,6 +72,23 @@ template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+// The same with `extra` (wave-uniform: EpiOperands::vm_ops, 0 .. 9) younger loads allowed to stay in flight on top of N.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt_plus(int extra) {
+  static_assert(N + 9 < 64, "vmcnt is a 6-bit counter");
+  switch (extra) {
+    case 1: wait_vmcnt<N + 1>(); break;
+    case 2: wait_vmcnt<N + 2>(); break;
+    case 3: wait_vmcnt<N + 3>(); break;
+    case 4: wait_vmcnt<N + 4>(); break;
+    case 5: wait_vmcnt<N + 5>(); break;
+    case 6: wait_vmcnt<N + 6>(); break;
+    case 7: wait_vmcnt<N + 7>(); break;
+    case 8: wait_vmcnt<N + 8>(); break;
+    case 9: wait_vmcnt<N + 9>(); break;
+    default: wait_vmcnt<N>(); break;  // (0, or a count this list does not know: waiting for more is slow, never wrong)
+  }
+}
 
 // PH ("phased"): TWO groups of WGM x WGN waves, each covering the whole BM x BN tile, take ALTERNATE K-steps (K-step kt
 // belongs to group kt & 1 and lives in stage kt % 4 of one four-deep ring): in half-step h group h & 1 runs the fragment
@@ -100,6 +117,8 @@ __device__ __forceinline__ void gemm2_body(
   const int tiles_n = N / BN;
   const int nrows = n_rows_dev ? *n_rows_dev : M;
   const int tid = threadIdx.x;
+  EpiOperands<BM, BN, NT, EPI> eops;      // (phased mode) the epilogue's second operands, requested before the loop ends
+  if constexpr (PH) eops.load_seed(epi);  // beside the row count: one round trip for both
   // Variable-length packing: only the first ceil(nrows/BM) tile rows are live.  The XCD-aware remap runs over the
   // LIVE tiles only -- remapping the whole (dense-sized) grid would hand every live tile to the first few XCDs
   // and leave the others with nothing but dead tiles.
@@ -192,14 +211,16 @@ __device__ __forceinline__ void gemm2_body(
 #else
 #define TICK(acc) do {} while (0)
 #endif
-  for (int kt = 0; kt < KT; ++kt) {
+  // One K-step.  pf_vm (wave-uniform): loads younger than every LDS-DMA load of this wave that may stay in flight across
+  // the counted waits -- the epilogue's second operands once they have gone out (below), else 0.
+  auto kstep = [&](const int kt, const int pf_vm) __attribute__((always_inline)) {
     bool do_issue = false;
     int nxt = 0;
     if constexpr (PH) {
       const bool mine = (kt & 1) == kg;
-      if (mine) {  // outstanding loads of this wave: K-steps kt and kt + 2, L instructions each
-        if (kt + 2 < KT) wait_vmcnt<L>();
-        else wait_vmcnt<0>();
+      if (mine) {  // outstanding loads of this wave: K-steps kt and kt + 2, L instructions each (+ pf_vm)
+        if (kt + 2 < KT) wait_vmcnt_plus<L>(pf_vm);
+        else wait_vmcnt_plus<0>(pf_vm);
       }
       TICK(t_wait);
       asm volatile("" ::: "memory");
@@ -210,7 +231,7 @@ __device__ __forceinline__ void gemm2_body(
       if (!mine) {
         issue_ph(kt + NS - 1);
         TICK(t_issue);
-        continue;
+        return;
       }
     } else {
     const int ahead = min(KT - kt - 1, NS - 2);  // stages issued after kt that may stay in flight
@@ -279,7 +300,7 @@ __device__ __forceinline__ void gemm2_body(
       asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[MI - 1][NJ - 1][15]));
 #endif
       TICK(t_comp);
-      continue;
+      return;
     }
     // fragment reads software-pipelined one k-substep ahead of the MFMAs that consume them
     bf16x8_t af[2][MI], bfr[2][NJ];
@@ -318,8 +339,20 @@ __device__ __forceinline__ void gemm2_body(
     asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[MI - 1][NJ - 1][15]));
 #endif
     TICK(t_comp);
+  };
+  // Phased mode runs one block per CU on the N = hidden GEMMs, so nothing covers the round trips at the head of its
+  // epilogue (seed -> dropout key, then bias / residual / aux rows: 2.3-3.1 k cycles per block after the loop,
+  // profiles/r05_gemm2_budget.txt).  There the operands go out ahead of the last NS - 1 K-steps -- the first point with
+  // no LDS-DMA left to issue, so they are the YOUNGEST loads of every wave and the counted waits of the remaining steps
+  // simply let that many more stay in flight.  KT < NS - 1: straight after the prologue's loads, by the same rule.
+  const int kt_pf = !PH ? KT : KT > NS - 1 ? KT - (NS - 1) : 0;
+  for (int kt = 0; kt < kt_pf; ++kt) kstep(kt, 0);
+  if constexpr (PH) {
+    eops.load(m0, n0, M, epi, tid);
+    const int pf_vm = EpiOperands<BM, BN, NT, EPI>::vm_ops(epi);
+    for (int kt = kt_pf; kt < KT; ++kt) kstep(kt, pf_vm);
+    wait_vmcnt<0>();
   }
-  if constexpr (PH) wait_vmcnt<0>();
 #ifdef MMT_GEMM2_INSTR
   const long long t_loop_end = clock64();
 #endif
@@ -327,10 +360,10 @@ __device__ __forceinline__ void gemm2_body(
   // ---- epilogue: 64 rows at a time through a row-major fp32 LDS image (gemm_epi.h) -----------------------------
 #ifdef MMT_GEMM2_INSTR
   long long eticks[3] = {0, 0, 0};
-  gemm_tile_epilogue<BM, BN, WGM, WGN, NT, EPI, PH>(acc, smem_raw, m0, n0, M, N, nrows, Cout, ldc, epi, wm, wn, kg, tid, eticks);
+  gemm_tile_epilogue<BM, BN, WGM, WGN, NT, EPI, PH>(acc, smem_raw, m0, n0, M, N, nrows, Cout, ldc, epi, wm, wn, kg, tid, eticks, PH ? &eops : nullptr);
   const long long e_head = eticks[2] - t_loop_end, e_stage = eticks[0], e_sweep = eticks[1];
 #else
-  gemm_tile_epilogue<BM, BN, WGM, WGN, NT, EPI, PH>(acc, smem_raw, m0, n0, M, N, nrows, Cout, ldc, epi, wm, wn, kg, tid, nullptr);
+  gemm_tile_epilogue<BM, BN, WGM, WGN, NT, EPI, PH>(acc, smem_raw, m0, n0, M, N, nrows, Cout, ldc, epi, wm, wn, kg, tid, nullptr, PH ? &eops : nullptr);
 #endif
 #ifdef MMT_GEMM2_INSTR
   if (epi.row_index == nullptr && epi.seed_dev != nullptr && tid == 0) {  // lab: seed_dev doubles as the debug buffer

@@ -31,14 +31,102 @@ __device__ __forceinline__ float gelu_grad_lut(const float* __restrict__ lut, un
   return (b & 0x8000u) ? 1.0f - t : t;
 }
 
+// Second operands of a tile's epilogue (residual rows, GELU pre-activations / dot partners, original row numbers of the
+// dropout key) for the WHOLE tile, held in registers.  load() sends all of them out at once: fetched inside the sweep,
+// each sits behind the previous row's store -- a chain of (BM / RG) global round trips per thread at the end of every tile.
+// The one-block-per-CU phased kernel calls load() itself, ahead of its last K-steps (gemm2.hip), because no co-resident
+// block hides the round trip there; everyone else lets gemm_tile_epilogue() call it.  Rows past the matrix read its last
+// row (never used).  NT = threads of the block; thread tid sweeps rows m0 + tid / CG + k RG at columns n0 + 4 (tid % CG).
+template <int BM, int BN, int NT, int EPI>
+struct EpiOperands {
+  static constexpr int CB = (NT * 4) % BN == 0 ? BN : 64, NCB = BN / CB, CG = CB / 4, RG = NT / CG, CH = BM < 64 ? BM : 64;
+  static constexpr int SW = CH / RG, NPF = (BM / CH) * SW * NCB;
+  static constexpr bool FITS = NPF <= 8;  // (256-row tiles would spend > 64 registers on it: they prefetch chunk by chunk)
+  static constexpr bool RES = FITS && (EPI == MMT_EPI_BIAS_DROP_RES || EPI == MMT_EPI_ADD_F32);
+  static constexpr bool AUX = FITS && (EPI == MMT_EPI_DGELU || EPI == MMT_EPI_BF16);  // (BF16: dot_src, when dot_out is set)
+  f32x4 res[RES ? NPF : 1];
+  u32x2 aux[AUX ? NPF : 1];
+  int orow[RES && EPI == MMT_EPI_BIAS_DROP_RES ? (BM / CH) * SW : 1];
+  static constexpr bool BIAS = EPI == MMT_EPI_BIAS_BF16 || EPI == MMT_EPI_BIAS_GELU || EPI == MMT_EPI_BIAS_DROP_RES ||
+                               EPI == MMT_EPI_BIAS_F32;
+  f32x4 bias[NCB];  // of this thread's columns (zeros where the epilogue has none)
+  unsigned seed;    // *epi.seed_dev (BIAS_DROP_RES): load_seed() first, key() once it has landed
+  __device__ __forceinline__ void load_seed(const MmtEpilogue& epi) {
+    seed = 0;
+    if constexpr (EPI == MMT_EPI_BIAS_DROP_RES)
+      if (epi.seed_dev) seed = *epi.seed_dev;
+  }
+  __device__ __forceinline__ unsigned key(const MmtEpilogue& epi) const {  // = eff_key(epi.drop_key, epi.seed_dev)
+    if constexpr (EPI != MMT_EPI_BIAS_DROP_RES) return 0;
+    return epi.seed_dev ? mix32(epi.drop_key ^ mix32(seed + 0x632be5abU)) : epi.drop_key;
+  }
+  // Vector-memory instructions load() issues per wave: wave-uniform, a function of the epilogue descriptor alone.  A caller
+  // that keeps counted vmcnt waits going after load() adds exactly this many to them.
+  static __device__ __forceinline__ int vm_ops(const MmtEpilogue& epi) {
+    int n = BIAS ? NCB : 0;
+    if constexpr (RES) n += NPF;
+    if constexpr (RES && EPI == MMT_EPI_BIAS_DROP_RES) n += (epi.drop_thr16 && epi.row_index) ? (BM / CH) * SW : 0;
+    if constexpr (AUX && EPI == MMT_EPI_DGELU) n += NPF;
+    if constexpr (AUX && EPI == MMT_EPI_BF16) n += epi.dot_out ? NPF : 0;
+    return n;
+  }
+  __device__ __forceinline__ void load_bias(int n0, const MmtEpilogue& epi, int tid) {
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) {
+      bias[cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if constexpr (BIAS) bias[cb] = *(const f32x4*)(epi.bias + n0 + cb * CB + (tid % CG) * 4);
+    }
+  }
+  __device__ __forceinline__ void load(int m0, int n0, int M, const MmtEpilogue& epi, int tid) {  // vm_ops() loads
+    load_bias(n0, epi, tid);
+    load_rows(m0, n0, M, epi, tid);
+  }
+  __device__ __forceinline__ void load_rows(int m0, int n0, int M, const MmtEpilogue& epi, int tid) {
+    if constexpr (RES || AUX) {
+      const int cg = tid % CG, rg = tid / CG;
+      const int64_t rb = m0 + rg, cb0 = n0 + cg * 4;
+      const int64_t off_res = rb * epi.ldres + cb0, off_aux = rb * epi.ldaux + cb0, off_dot = rb * epi.lddot + cb0;
+#pragma unroll
+      for (int ch = 0; ch < BM / CH; ++ch)
+#pragma unroll
+        for (int sw = 0; sw < SW; ++sw) {
+          const int dr = ch * CH + sw * RG;
+          const bool in = m0 + dr + rg < M;
+          const int row = in ? m0 + dr + rg : M - 1;
+          if constexpr (RES && EPI == MMT_EPI_BIAS_DROP_RES)
+            orow[ch * SW + sw] = (epi.drop_thr16 && epi.row_index) ? epi.row_index[row] : row;
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) {
+            if constexpr (RES) {
+              const int64_t o = in ? off_res + (int64_t)dr * epi.ldres + cb * CB : (int64_t)(M - 1) * epi.ldres + cb0 + cb * CB;
+              res[(ch * SW + sw) * NCB + cb] = *(const f32x4*)(epi.res + o);
+            }
+            if constexpr (AUX && EPI == MMT_EPI_DGELU) {
+              const int64_t o = in ? off_aux + (int64_t)dr * epi.ldaux + cb * CB : (int64_t)(M - 1) * epi.ldaux + cb0 + cb * CB;
+              aux[(ch * SW + sw) * NCB + cb] = *(const u32x2*)((const bf16_t*)epi.aux + o);
+            }
+            if constexpr (AUX && EPI == MMT_EPI_BF16) {
+              if (epi.dot_out) {
+                const int64_t o = in ? off_dot + (int64_t)dr * epi.lddot + cb * CB : (int64_t)(M - 1) * epi.lddot + cb0 + cb * CB;
+                aux[(ch * SW + sw) * NCB + cb] = *(const u32x2*)((const bf16_t*)epi.dot_src + o);
+              }
+            }
+          }
+        }
+    }
+  }
+};
+
 // acc[MI][NJ]: wave (wm, wn) of a WGM x WGN grid owns rows wm * WTM + 32 i .. and columns wn * WTN + 32 j .. of the BM x BN
 // tile at (m0, n0).  PH: two wave groups (kg = 0 / 1) hold partial tiles over alternate K-steps; group 1 adds its partial
 // onto group 0's image.  smem_raw: >= (64 (BN + 4) + RG BN) floats, no longer in use by the main loop.  ticks (lab build):
 // [0] = LDS staging, [1] = row sweep, in s_memtime cycles.
+// ops / ops_loaded: the tile's second operands when the caller has already sent them out (EpiOperands::load), else null.
 template <int BM, int BN, int WGM, int WGN, int NT, int EPI, bool PH>
 __device__ __forceinline__ void gemm_tile_epilogue(f32x16 (&acc)[BM / WGM / 32][BN / WGN / 32], unsigned char* smem_raw, int m0, int n0,
                                                    int M, int N, int nrows, void* __restrict__ Cout, int64_t ldc,
-                                                   const MmtEpilogue& epi, int wm, int wn, int kg, int tid, long long* ticks) {
+                                                   const MmtEpilogue& epi, int wm, int wn, int kg, int tid, long long* ticks,
+                                                   EpiOperands<BM, BN, NT, EPI>* ops_loaded = nullptr) {
   constexpr int WTM = BM / WGM, WTN = BN / WGN, MI = WTM / 32, NJ = WTN / 32;
   constexpr int P = BN + 4;        // fp32 pitch of the epilogue image
   // the epilogue sweeps the image in column blocks of CB columns: the whole width when the thread count divides into
@@ -54,22 +142,9 @@ __device__ __forceinline__ void gemm_tile_epilogue(f32x16 (&acc)[BM / WGM / 32][
   float* st = (float*)smem_raw;
   float* red = st + CH * P;  // [RG][BN] column-sum scratch (DGELU)
   const int cg = tid % CG, rg = tid / CG;
-  f32x4 bias4[NCB];
-#pragma unroll
-  for (int cb = 0; cb < NCB; ++cb) {
-    bias4[cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if constexpr (EPI == MMT_EPI_BIAS_BF16 || EPI == MMT_EPI_BIAS_GELU || EPI == MMT_EPI_BIAS_DROP_RES ||
-                  EPI == MMT_EPI_BIAS_F32)
-      bias4[cb] = *(const f32x4*)(epi.bias + n0 + cb * CB + cg * 4);
-  }
-  unsigned dkey = 0;
-  if constexpr (EPI == MMT_EPI_BIAS_DROP_RES) dkey = eff_key(epi.drop_key, epi.seed_dev);
   float csum[NCB][4];
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) csum[cb][0] = csum[cb][1] = csum[cb][2] = csum[cb][3] = 0.f;
-  // Second operands of the epilogue (residual rows, GELU pre-activations, original row numbers of the dropout key) for
-  // the WHOLE tile go out now, all at once: fetched inside the sweep, each sits behind the previous row's store -- a
-  // chain of (BM / RG) global round trips per thread at the end of every tile.
   // Element offsets of this thread's first swept row (m0 + rg, column n0 + 4 cg) in every matrix the epilogue touches: row
   // m0 + rg + dr is that + dr * ld with dr a compile-time constant of the unrolled sweep -- a scalar multiply and one 64-bit
   // add instead of a 64-bit row x ld product per access (two quarter-rate v_mul_lo_u32 + v_mad_u64_u32: a fifth of the
@@ -77,43 +152,24 @@ __device__ __forceinline__ void gemm_tile_epilogue(f32x16 (&acc)[BM / WGM / 32][
   const int64_t rb = m0 + rg, cb0 = n0 + cg * 4;
   const int64_t off_c = rb * ldc + cb0, off_res = rb * epi.ldres + cb0, off_aux = rb * epi.ldaux + cb0,
                 off_o2 = rb * epi.ldout2 + cb0, off_dot = rb * epi.lddot + cb0;
-  constexpr int SW = CH / RG, NPF = (BM / CH) * SW * NCB;
-  constexpr bool PF_FITS = NPF <= 8;  // (256-row tiles would spend > 64 registers on it: they prefetch chunk by chunk, below)
+  using Ops = EpiOperands<BM, BN, NT, EPI>;
+  constexpr int SW = Ops::SW;
+  constexpr bool PF_FITS = Ops::FITS, PF_RES = Ops::RES, PF_AUX = Ops::AUX;
   constexpr bool PFC = !PF_FITS && SW * NCB <= 8;  // second operands of ONE 64-row chunk, fetched before its staging pass
-  constexpr bool PF_RES = PF_FITS && (EPI == MMT_EPI_BIAS_DROP_RES || EPI == MMT_EPI_ADD_F32);
-  constexpr bool PF_AUX = PF_FITS && (EPI == MMT_EPI_DGELU || EPI == MMT_EPI_BF16);  // (BF16: dot_src, when dot_out is set)
-  f32x4 pf_res[PF_RES ? NPF : 1];
-  u32x2 pf_aux[PF_AUX ? NPF : 1];
-  int pf_orow[PF_RES && EPI == MMT_EPI_BIAS_DROP_RES ? (BM / CH) * SW : 1];
-  if constexpr (PF_RES || PF_AUX) {
-#pragma unroll
-    for (int ch = 0; ch < BM / CH; ++ch)
-#pragma unroll
-      for (int sw = 0; sw < SW; ++sw) {
-        const int dr = ch * CH + sw * RG;
-        const bool in = m0 + dr + rg < M;  // rows past the matrix read its last row (never used)
-        const int row = in ? m0 + dr + rg : M - 1;
-        if constexpr (PF_RES && EPI == MMT_EPI_BIAS_DROP_RES)
-          pf_orow[ch * SW + sw] = (epi.drop_thr16 && epi.row_index) ? epi.row_index[row] : row;
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-          if constexpr (PF_RES) {
-            const int64_t o = in ? off_res + (int64_t)dr * epi.ldres + cb * CB : (int64_t)(M - 1) * epi.ldres + cb0 + cb * CB;
-            pf_res[(ch * SW + sw) * NCB + cb] = *(const f32x4*)(epi.res + o);
-          }
-          if constexpr (PF_AUX && EPI == MMT_EPI_DGELU) {
-            const int64_t o = in ? off_aux + (int64_t)dr * epi.ldaux + cb * CB : (int64_t)(M - 1) * epi.ldaux + cb0 + cb * CB;
-            pf_aux[(ch * SW + sw) * NCB + cb] = *(const u32x2*)((const bf16_t*)epi.aux + o);
-          }
-          if constexpr (PF_AUX && EPI == MMT_EPI_BF16) {
-            if (epi.dot_out) {
-              const int64_t o = in ? off_dot + (int64_t)dr * epi.lddot + cb * CB : (int64_t)(M - 1) * epi.lddot + cb0 + cb * CB;
-              pf_aux[(ch * SW + sw) * NCB + cb] = *(const u32x2*)((const bf16_t*)epi.dot_src + o);
-            }
-          }
-        }
-      }
+  // second operands of the whole tile (see EpiOperands): go out here unless the caller sent them earlier
+  // (in the order this function always had: bias, seed -> key, then the row operands)
+  Ops ops_own;
+  if (!ops_loaded) {
+    ops_own.load_bias(n0, epi, tid);
+    ops_own.load_seed(epi);
   }
+  Ops& ops = ops_loaded ? *ops_loaded : ops_own;
+  auto& bias4 = ops.bias;
+  const unsigned dkey = ops.key(epi);
+  if (!ops_loaded) ops_own.load_rows(m0, n0, M, epi, tid);
+  auto& pf_res = ops.res;
+  auto& pf_aux = ops.aux;
+  auto& pf_orow = ops.orow;
   // GELU tables: global -> registers now (the round trip overlaps the barrier and the first staging pass), -> LDS below
   constexpr bool LUT = EPI == MMT_EPI_BIAS_GELU || EPI == MMT_EPI_DGELU;
   constexpr int LUTN = (MMT_GELU_LUT_N + NT - 1) / NT;

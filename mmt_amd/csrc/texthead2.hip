@@ -97,6 +97,21 @@ __device__ __forceinline__ float splitk_reduce(ThSmem& sm, const f32x16& acc, in
   for (int w = 0; w < TH_W; ++w) v += sm.red[w][wave][lane];
   return v;
 }
+// The same sum + one more term, in ONE fixed association: (w14 + w15) + w13 + ... + w0, then `last`.  The library is
+// built with -ffast-math, which lets the compiler associate splitk_reduce's chain as it likes, and it does so differently
+// as the code around the chain changes (with `last` on hand early it went to the FRONT; with the chain fenced off the
+// partials ran ascending): same 17 adds, other low bits in dy, and after a few Adam steps in the weights.  This is the
+// association th_bwd3 has been compiled to since it was written; spelled out and closed to reassociation it stays.
+__device__ __forceinline__ float splitk_reduce_then(ThSmem& sm, const f32x16& acc, int wave, int lane, float last) {
+#pragma clang fp reassociate(off)
+#pragma unroll
+  for (int r = 0; r < 16; ++r) sm.red[wave][r][lane] = acc[r];
+  __syncthreads();
+  float v = sm.red[TH_W - 2][wave][lane] + sm.red[TH_W - 1][wave][lane];
+#pragma unroll
+  for (int w = TH_W - 3; w >= 0; --w) v = v + sm.red[w][wave][lane];
+  return v + last;
+}
 __device__ __forceinline__ int tile_row(int wave, int lane) { return (wave & 3) + 8 * (wave >> 2) + 4 * (lane >> 5); }
 
 // Column sums of a 32x33 LDS tile over its first N rows, without a serial loop: thread t takes element
@@ -370,15 +385,18 @@ __global__ __launch_bounds__(256) void th_bwd1_kernel(ThArgs a) {
   }
 }
 
-// weight-gradient tile: C[i][c] = sum_{n < N} T[n][i] * G[n * ldg + c0 + (lane & 31)], T = a 32x33 LDS tile
-__device__ __forceinline__ f32x16 mm_tn_tile(const float (*T)[33], const float* __restrict__ G, int64_t ldg, int N, int l31,
-                                             int h) {
-  float b[16];
+// weight-gradient tile: C[i][c] = sum_{n < N} T[n][i] * G[n * ldg + c0 + (lane & 31)], T = a 32x33 LDS tile.  In two halves:
+// the G operand does not depend on T, so its loads (tn_load) go out BEFORE the barrier that publishes T and the round
+// trip runs under whatever produces T; tn_mma is the MFMA chain.
+__device__ __forceinline__ void tn_load(float (&b)[16], const float* __restrict__ G, int64_t ldg, int N, int l31, int h) {
 #pragma unroll
   for (int kk = 0; kk < 16; ++kk) {
     const int k = 2 * kk + h;
-    b[kk] = k < N ? G[(int64_t)k * ldg + l31] : 0.f;
+    const float g = G[(int64_t)min(k, N - 1) * ldg + l31];  // (rows past N re-read the last one: no branch per load)
+    b[kk] = k < N ? g : 0.f;
   }
+}
+__device__ __forceinline__ f32x16 tn_mma(const float (*T)[33], const float (&b)[16], int l31, int h) {
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -403,6 +421,11 @@ __global__ __launch_bounds__(TH_T) void th_bwd2_kernel(ThArgs a) {
   const bool live = n < a.N;
   const float dzv = live ? w.dz[p] : 0.f;
   float dx = dzv;
+  // the y operand of this wave's g_w2 tiles (column tiles wave and wave + 16: d <= 1024) is independent of dx1: requested now
+  const bool gw2 = a.h.g_w2[m] != nullptr;
+  float yb0[16], yb1[16];
+  if (gw2 && wave < ct) tn_load(yb0, w.y + (int64_t)m * a.d + wave * 32, (int64_t)a.M * a.d, a.N, l31, h);
+  if (gw2 && wave + TH_W < ct) tn_load(yb1, w.y + (int64_t)m * a.d + (wave + TH_W) * 32, (int64_t)a.M * a.d, a.N, l31, h);
   if (a.use_bn) {
     const float mu = w.mean[(int64_t)m * a.d + col], rs = w.rstd[(int64_t)m * a.d + col], ga = a.h.bn_gamma[m][col];
     const float xh = live ? (w.x1[p] - mu) * rs : 0.f;
@@ -431,11 +454,10 @@ __global__ __launch_bounds__(TH_T) void th_bwd2_kernel(ThArgs a) {
     const float sb = half_wave_sum(sm.tile[2][tid & 31][tid >> 5]);
     if ((tid & 31) == 0 && a.h.g_b2[m]) a.h.g_b2[m][j0 + (tid >> 5)] = sb;
   }
-  if (a.h.g_w2[m]) {  // g_w2[m][j0 + i][c] = sum_n dx1[n][j0 + i] * y[n][m][c]
-    for (int c_t = wave; c_t < ct; c_t += TH_W) {
-      const f32x16 acc = mm_tn_tile(sm.tile[2], w.y + (int64_t)m * a.d + c_t * 32, (int64_t)a.M * a.d, a.N, l31, h);
-      store_tile(acc, a.h.g_w2[m] + (int64_t)j0 * a.d + c_t * 32, a.d, l31, h);
-    }
+  if (gw2) {  // g_w2[m][j0 + i][c] = sum_n dx1[n][j0 + i] * y[n][m][c]
+    if (wave < ct) store_tile(tn_mma(sm.tile[2], yb0, l31, h), a.h.g_w2[m] + (int64_t)j0 * a.d + wave * 32, a.d, l31, h);
+    if (wave + TH_W < ct)
+      store_tile(tn_mma(sm.tile[2], yb1, l31, h), a.h.g_w2[m] + (int64_t)j0 * a.d + (wave + TH_W) * 32, a.d, l31, h);
   }
 }
 
@@ -466,6 +488,9 @@ __global__ __launch_bounds__(TH_T) void th_bwd3_kernel(ThArgs a) {
   const int m = blockIdx.x / ct, j0 = (blockIdx.x % ct) * 32;
   // dy[n][j0 + j] = dyg[n][j0 + j] + sum_c dx1[n][c] * W2[m][c][j0 + j]   (contraction over W2's ROW index)
   const int per = k_slice(a.d), kbeg = wave * per, kend = min(a.d, kbeg + per);
+  const bool gw1 = a.h.g_w1[m] != nullptr;
+  const int kt_n = a.K / 32;
+  float tb0[16], tb1[16];
   {
     const float* ap = w.dz + ((int64_t)min(l31, a.N - 1) * a.M + m) * a.d;
     const bool iok = l31 < a.N;
@@ -491,11 +516,16 @@ __global__ __launch_bounds__(TH_T) void th_bwd3_kernel(ThArgs a) {
         for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t][u], bv[t][u], acc, 0, 0, 0);
       }
     }
-    float v = splitk_reduce(sm, acc, wave, lane);
+    // Everything the rest of the block reads that does not depend on dy goes out before the barriers that publish it: this
+    // thread's dyg element and the text operand of this wave's g_w1 tiles (K tiles wave and wave + 16: K <= 1024).  The av /
+    // bv registers are free again by now.
     const int n = tile_row(wave, lane);
+    const int64_t p = ((int64_t)n * a.M + m) * a.d + j0 + l31;
+    const float dyg0 = n < a.N ? w.dyg[p] : 0.f;
+    if (gw1 && wave < kt_n) tn_load(tb0, a.text + wave * 32, a.K, a.N, l31, h);
+    if (gw1 && wave + TH_W < kt_n) tn_load(tb1, a.text + (wave + TH_W) * 32, a.K, a.N, l31, h);
+    float v = splitk_reduce_then(sm, acc, wave, lane, dyg0);
     if (n < a.N) {
-      const int64_t p = ((int64_t)n * a.M + m) * a.d + j0 + l31;
-      v += w.dyg[p];
       w.dyg[p] = v;  // dyg now holds dy (gradient wrt the fc output), read by the text-gradient GEMM
     } else {
       v = 0.f;
@@ -507,12 +537,10 @@ __global__ __launch_bounds__(TH_T) void th_bwd3_kernel(ThArgs a) {
     const float sb = half_wave_sum(sm.tile[2][tid & 31][tid >> 5]);
     if ((tid & 31) == 0 && a.h.g_b1[m]) a.h.g_b1[m][j0 + (tid >> 5)] = sb;
   }
-  if (a.h.g_w1[m]) {  // g_w1[m][j0 + i][k] = sum_n dy[n][j0 + i] * text[n][k]
-    const int kt_n = a.K / 32;
-    for (int kt = wave; kt < kt_n; kt += TH_W) {
-      const f32x16 acc = mm_tn_tile(sm.tile[2], a.text + kt * 32, a.K, a.N, l31, h);
-      store_tile(acc, a.h.g_w1[m] + (int64_t)j0 * a.K + kt * 32, a.K, l31, h);
-    }
+  if (gw1) {  // g_w1[m][j0 + i][k] = sum_n dy[n][j0 + i] * text[n][k]
+    if (wave < kt_n) store_tile(tn_mma(sm.tile[2], tb0, l31, h), a.h.g_w1[m] + (int64_t)j0 * a.K + wave * 32, a.K, l31, h);
+    if (wave + TH_W < kt_n)
+      store_tile(tn_mma(sm.tile[2], tb1, l31, h), a.h.g_w1[m] + (int64_t)j0 * a.K + (wave + TH_W) * 32, a.K, l31, h);
   }
 }
 
