@@ -701,6 +701,53 @@ int mmt_search_pair_scores(const void* g, const float* gw, const float* gscale, 
 int mmt_search_mmr(const int64_t* items, const float* rel, const float* sims, int R, int C, int k, float a, float b,
                    float* scores, int64_t* index, float* values, void* stream);
 
+/* The gallery self-join (search_self.hip), additive like the entries above: three entries and two size functions without
+ * a descriptor, nothing that exists changes and mmt_abi_version() stays 6.  They serve search.py's `neighbours`,
+ * `neighbour_range` and `duplicate_groups`: the stored items searched against the stored items -- near-duplicate joins over
+ * a clip gallery (re-uploads, crops, windows of one video) without the NV x NV matrix.  The quantity is
+ * mmt_search_pair_scores' sim(g, h) = <f_g, f_h> / sum_m gw[g][m] gw[h][m] (0 -> 1e-5) on the stored values ('indep'
+ * similarity, model/model.py:789-837, with a stored item in the query's place), and every score these entries return has
+ * exactly the bits mmt_search_pair_scores gives the pair: the same slab and MFMA sequence along K, one accumulator per
+ * output, the same fma chain for the denominator, the same rounded multiplies for the fp8 scales.  It does not depend on
+ * the row batching, the launch geometry, NV, the items' positions or the shard.
+ * Each entry takes TWO stored operands in one `storage` (MMT_SEARCH_FP32 / _BF16 / _FP8), M and d:
+ *   A side, the rows: a_rows [NA][M * d], a_weights fp32 [NA][M], a_scales fp32 [NA] with fp8 and null otherwise; items int64
+ *     [R] (nullable = row r of A is row r of the join, then R <= NA), a value outside 0 .. NA - 1 is "none": checked on the
+ *     device, never dereferenced; self int64 [R] (nullable = none): the B-side item number row r must not meet, -1 = none
+ *     -- the self pair is left out by NUMBER, not by score, so an exact copy of an item stays in its list.
+ *   B side, the columns: g [NV][M * d], gw fp32 [NV][M], gscale fp32 [NV] with fp8; subset (nullable = every item): the
+ *     packed bitmap of mmt_search_subset_pack, only its items are candidates.
+ *   On one index the caller passes A = B and self = items; a gallery cut into shards passes a staged block of the rows
+ *   as A to every shard, with self the row's local number there or -1.
+ * mmt_search_self_topk: per row the best candidates in the search's order (score descending, -0 tied with +0, equal scores
+ *   by ascending item) as scores fp32 / index int64 [R][k], 1 <= k <= 128.  ONLY the slots that have a candidate are
+ *   written (the caller prefills (-inf, -1)).  ws uint64 [mmt_self_topk_workspace_keys(R, NV, k)] = R * ceil(NV / chunk) * k.
+ * mmt_search_self_range_count, mmt_search_self_range_fill: every candidate with sim >= thr[r] (fp32 [R]; a plain compare:
+ *   NaN hits nothing, -inf everything) as a CSR, the two passes of mmt_search_range_count / _fill: the count pass writes
+ *   row_counts int64 [R] and leaves ws (int32 [mmt_self_range_workspace_ints(R, NV)] = R * ceil(NV / chunk)) holding per row
+ *   the exclusive prefix of its chunk counts; the fill pass of the very same arguments reads it, with offsets int64 [R + 1]
+ *   the exclusive prefix of row_counts, and writes row r's hits to indices int64 / scores fp32 [offsets[r], offsets[r + 1])
+ *   by ascending item.  A position is clamped against the start of the row's next chunk.
+ * MMT_ERR_ARG: a null a_rows, a_weights, g, gw, output or workspace, an unknown storage, a_scales / gscale given without
+ *   fp8 or missing with it, NA / R / NV < 1, items null with R > NA, M outside 1 .. 16, d < 1 or off the storage's multiple,
+ *   k outside 1 .. 128; MMT_ERR_ALIGN: a_rows, g or subset off a 16-byte boundary.  All refused before any launch.  No
+ *   atomics; one writer per slot. */
+int64_t mmt_self_topk_workspace_keys(int R, int NV, int k);
+int64_t mmt_self_range_workspace_ints(int R, int NV);
+int mmt_search_self_topk(const void* a_rows, const float* a_weights, const float* a_scales, int NA, const int64_t* items,
+                         const int64_t* self, int R, const void* g, const float* gw, const float* gscale, int NV,
+                         const uint32_t* subset, int storage, int M, int d, int k, uint64_t* ws, float* scores,
+                         int64_t* index, void* stream);
+int mmt_search_self_range_count(const void* a_rows, const float* a_weights, const float* a_scales, int NA,
+                                const int64_t* items, const int64_t* self, int R, const void* g, const float* gw,
+                                const float* gscale, int NV, const uint32_t* subset, int storage, int M, int d,
+                                const float* thr, int32_t* ws, int64_t* row_counts, void* stream);
+int mmt_search_self_range_fill(const void* a_rows, const float* a_weights, const float* a_scales, int NA,
+                               const int64_t* items, const int64_t* self, int R, const void* g, const float* gw,
+                               const float* gscale, int NV, const uint32_t* subset, int storage, int M, int d,
+                               const float* thr, const int32_t* ws, const int64_t* offsets, int64_t* indices, float* scores,
+                               void* stream);
+
 /* Beside the scans.
  * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> the subset words, padding included: one ballot per 64
  *   items, one writer per word.

@@ -261,6 +261,16 @@ SIGNATURES = {
     # diversified search, additive and without a descriptor: the Gram of stored items, the MMR selection
     'mmt_search_pair_scores': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp]),
     'mmt_search_mmr': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    # the gallery self-join, additive and without a descriptor: two stored operands (A: rows, weights, scales, NA, items,
+    # self, R; B: g, gw, gscale, NV, subset), then storage, M, d, k or thr, workspace, outputs, stream
+    'mmt_self_topk_workspace_keys': (c_i64, [c_int, c_int, c_int]),
+    'mmt_self_range_workspace_ints': (c_i64, [c_int, c_int]),
+    'mmt_search_self_topk': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int,
+                                     c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_self_range_count': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_int,
+                                            c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_self_range_fill': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_int,
+                                           c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

@@ -280,6 +280,32 @@ ShardedVideoIndex has the three calls, bit-identical: per row batch every shard 
 of the batch's distinct candidates into a staging index on the primary, the candidates are renumbered into it and the same
 kernel runs there -- exact, because sim depends on the two stored rows alone.  Out of scope: norm=, pooling=, item_pooling=,
 grouping= and after= raise ValueError naming the option.
+
+    scores, indices = index.neighbours(k=10, items=None, subset=None, source=None)          # [R, k] float32 / int64
+    result = index.neighbour_range(threshold, items=None, subset=None, source=None, order='index', max_hits=...)  # RangeResult
+    labels = index.duplicate_groups(threshold, subset=None, max_hits=...)                   # int64 [num_items]
+
+The eleventh question: the gallery searched against itself.  The ten above start from a query; a clip gallery is full of
+re-uploads, crops and windows of one video, `search_groups` removes such copies only where somebody has labelled them, and
+`diversify` works around them inside one 128-item shortlist, per query, at query time.  The quantity is `pair_scores`'
+sim(g, h), reachable there only for lists of C <= 128 as a C x C matrix; searching with dequantised rows as queries is a
+different quantity (on a bfloat16 or float8_e4m3fn index it re-rounds one operand).  The self-join is a streaming scan
+with BOTH operands stored rows (search_self.hip): blocks of 64 row items x one gallery chunk score 64 x 128 tiles with the
+slab and MFMA sequence of the Gram kernel -- fp32 rows on v_mfma_f32_32x32x2_f32, bf16 rows and exactly widened fp8 codes on
+one v_mfma_f32_32x32x16_bf16 per fragment, the same fma chain for the denominator, the same rounded multiplies for the fp8
+scales -- so every score the three calls return has exactly the bits `pair_scores` gives the pair on the same index, on
+all three storage dtypes, whatever the row batching, the launch geometry, num_items, the position or the shard.  The order
+is `search`'s; the self pair (g, g) is left out by item NUMBER, not by score, so an exact copy of g stays in g's list.
+`neighbours` keeps a running top-k per row (the selection, workspace and merge of `search`); `neighbour_range` is the two
+scans of `range_search`, no atomics, the total known after the first; `duplicate_groups` turns the threshold graph's edges,
+taken from `neighbour_range` in row batches, into connected components by minimum-label propagation with pointer jumping
+(`connected_components`, torch ops), labels[g] = the smallest item number of g's component -- which `grouping` accepts
+unchanged, so `search_groups` de-duplicates without anybody's labels and `diversify` penalises with the same bits.
+source= takes another VideoIndex's items as the rows (an upload batch against the gallery before `add`; no self pair).
+ShardedVideoIndex has the three calls, bit-identical: per row batch the rows' stored bytes, weights and scales are staged
+on the primary and copied to every shard, which joins them against its own items; lists are merged
+(mmt_search_merge_lists), CSR rows assembled as `range_search` assembles them.  Out of scope: norm=, pooling=,
+item_pooling=, grouping=, after= and exclude= raise ValueError naming the option.
 """
 import ctypes
 import math
@@ -302,6 +328,8 @@ MAX_ITEM_SET = 128  # items per stored set of an item-pooled scan: one 128-colum
 _POOL_MODES = {'mean': 0, 'max': 1}  # the `mode` of the pooled entry points
 _BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 bytes per element either way) + chunk lists
 _MAX_HITS = 1 << 27  # default cap of a range search's total: a guard against a mistyped threshold, not a tuned number
+_NOT_SELF = ('norm', 'pooling', 'item_pooling', 'grouping', 'after', 'exclude')  # options the self-join refuses by name
+_GROUP_ROWS = 1 << 16  # rows per `neighbour_range` call of `duplicate_groups`: the CSR of a batch is dropped for its edges
 FP8 = torch.float8_e4m3fn
 _DTYPES = {torch.float32: 4, torch.bfloat16: 8, FP8: 16}  # storage dtype -> multiple d must have (16-byte folded rows)
 _STORAGE = {torch.float32: _lib.SEARCH_FP32, torch.bfloat16: _lib.SEARCH_BF16, FP8: _lib.SEARCH_FP8}  # MmtSearchScan.storage
@@ -616,6 +644,39 @@ def _range_result(offsets, indices, scores, order):
     perm = by_score[torch.argsort(_csr_rows(offsets)[by_score], stable=True)]
     indices, scores = indices[perm], scores[perm]
   return RangeResult(offsets, indices, scores)
+
+
+def search_order(scores, items):
+  """The order of `search` (tk_key of the kernels) over one list: scores float32 [n] and item numbers int64 [n] (distinct)
+  -> the positions int64 [n], best first: score descending with -0 tied to +0, equal scores by ascending item number.
+  Two stable torch sorts, on CPU or device tensors; a NaN has no place in a list and is not expected here."""
+  by_item = torch.argsort(items, stable=True)
+  return by_item[torch.argsort((scores + 0.0)[by_item], descending=True, stable=True)]   # -0.0 + 0.0 = +0.0
+
+
+def connected_components(num_items, src, dst):
+  """The connected components of the undirected graph on 0 .. num_items - 1 with the edges (src[i], dst[i]) -- int64 [E]
+  each, on one device, CPU included; direction, order and repeats do not matter -> labels int64 [num_items] there:
+  labels[g] is the smallest number in g's component.  Minimum-label propagation with pointer jumping: labels start as
+  the item's own number; a round pulls the two ends of every edge down to the smaller of their labels (scatter amin) and
+  then replaces labels by labels[labels] until that changes nothing -- a label is always a member of the item's own
+  component and never above the item, so the jump is safe and roughly halves the rounds a long chain needs.  It stops when
+  a round changes nothing: then both ends of every edge carry one label, a component carries one label, and that label,
+  a member no larger than any member, is its minimum.  Each comparison is one host sync."""
+  labels = torch.arange(num_items, device=src.device, dtype=torch.int64)
+  if src.numel() == 0:
+    return labels
+  while True:
+    low = torch.minimum(labels[src], labels[dst])
+    new = labels.scatter_reduce(0, src, low, 'amin').scatter_reduce(0, dst, low, 'amin')
+    while True:
+      jumped = new[new]
+      if torch.equal(jumped, new):
+        break
+      new = jumped
+    if torch.equal(new, labels):
+      return labels
+    labels = new
 
 
 def _check_beta(beta):
@@ -1310,6 +1371,145 @@ class _Index:
     _, shortlisted = (self if coarse is None else coarse).search(embds, weights, k=shortlist, subset=subset, exclude=exclude)
     return self.diversify(embds, weights, shortlisted, k, lam)
 
+  def _self_args(self, who, items, subset, source, unsupported, k=...):
+    """The checks of the self-join calls that look at no value, before anything touches the device -> the index whose
+    items are the rows of the join: this one, or `source`."""
+    for name in unsupported:
+      if name not in _NOT_SELF:
+        raise TypeError('%s() got an unexpected keyword argument %r' % (who, name))
+      raise ValueError('%s: %s= is out of scope: the self-join scores stored items by their plain sim' % (who, name))
+    if k is not ... and (isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K):
+      raise ValueError('%s: k must be an int in 1..%d, got %r' % (who, MAX_K, k))
+    if source is not None:
+      if hasattr(self, 'shards'):
+        raise ValueError('%s: source= is not available on a ShardedVideoIndex' % who)
+      if not isinstance(source, VideoIndex):
+        raise ValueError('%s: source must be a VideoIndex, got %s' % (who, type(source).__name__))
+      mine, theirs = ((i.dtype, i.num_experts, i.dim) for i in (self, source))
+      if mine != theirs:
+        raise ValueError('%s: the source holds (dtype, num_experts, dim) = %s, this index %s' % (who, theirs, mine))
+      if source.device != self.device:
+        raise ValueError('%s: the source is on %s, this index on %s' % (who, source.device, self.device))
+    if items is not None:
+      if not torch.is_tensor(items) or items.dtype != torch.int64:
+        raise ValueError('%s: items must be an int64 tensor, got %s' % (
+            who, items.dtype if torch.is_tensor(items) else type(items).__name__))
+      if items.device != self.device:
+        raise ValueError('%s: items must be on the index device %s, got %s' % (who, self.device, items.device))
+      if items.dim() != 1:
+        raise ValueError('%s: items [R] expected, got %s' % (who, tuple(items.shape)))
+    if subset is not None:
+      self._subset(subset, who)
+    if self.num_items == 0:
+      raise ValueError('%s: the index holds no items' % who)
+    if source is not None and source.num_items == 0:
+      raise ValueError('%s: the source holds no items' % who)
+    return self if source is None else source
+
+  def _self_items(self, who, rows, items):
+    """The rows of the join as int64 [R] of `rows`' item numbers: every item in order for None, else the given ones with
+    their range checked as `rescore` checks its candidates (one small reduction and a host sync)."""
+    n = rows.num_items
+    if items is None:
+      return torch.arange(n, device=self.device, dtype=torch.int64)
+    items = items.contiguous()
+    if items.numel():
+      lo, hi = (int(v) for v in torch.aminmax(items))
+      if lo < 0 or hi >= n:
+        raise ValueError('%s: items must lie in 0 .. %d, got %d .. %d' % (who, n - 1, lo, hi))
+    return items
+
+  def neighbours(self, k=10, items=None, subset=None, source=None, **unsupported):
+    """The gallery searched against itself: per stored item its k best stored items -> (scores [R, k] float32, indices
+    [R, k] int64) on the device.  items: int64 [R] on the index device, the rows of the join, values 0 .. num_items - 1,
+    repeats allowed; None = every stored item in order.  subset (from this index's `subset`): only its items are
+    candidates; the rows are not restricted by it.  k an int in 1 .. MAX_K: the width of the outputs; the slots a row
+    cannot fill hold (-inf, -1), as `rescore` pads.  Row r holds the best candidates other than items[r] itself under
+    `search`'s order -- sim descending, -0 tied with +0, equal sims by ascending item number -- and the self pair is left
+    out by item NUMBER, not by score: an exact copy of an item stays in its list.  Every score has exactly the bits
+    `pair_scores` gives the pair on this index, on all three storage dtypes,
+        sim(g, h) = <f_g, f_h> / sum_m gw[g][m] gw[h][m]     (0 -> 1e-5)
+    whatever the row batching, the launch geometry, num_items, the items' positions or the shard:
+    ShardedVideoIndex.neighbours is bit-identical.  source: another VideoIndex with this one's dtype, num_experts and dim
+    on its device; its items are then the rows (`items` numbers them, None = all of it), the columns are this index and no
+    self pair is removed -- de-duplicating an upload batch against the gallery before `add`.  Not on a ShardedVideoIndex.
+    A streaming scan (mmt_search_self_topk): blocks of 64 rows x one gallery chunk keep a running top-k per row and a
+    merge launch joins the chunk lists; the NV x NV matrix never exists.  The range of `items` is checked with one small
+    reduction and a host sync; nothing after that waits for the device.  Out of scope: norm=, pooling=, item_pooling=,
+    grouping=, after= and exclude= raise ValueError naming the option."""
+    rows = self._self_args('neighbours', items, subset, source, unsupported, k)
+    items = self._self_items('neighbours', rows, items)
+    outs = _lists(2, self.device, items.shape[0], k, vacant=True)
+    if items.shape[0]:
+      self._neighbours(rows, items, items if source is None else None, k, subset, outs)
+    return outs
+
+  def neighbour_range(self, threshold, items=None, subset=None, source=None, order='index', max_hits=_MAX_HITS,
+                      **unsupported):
+    """Per row item EVERY candidate with sim >= threshold, however many, as a CSR over the R rows -> RangeResult.  items,
+    subset and source as `neighbours`: the self pair is left out by item number, the scores have `pair_scores`' bits.
+    threshold and order as `range_search`: a Python float, or float32 [R] on the index device; a plain `>=` compare, so
+    NaN hits nothing and -inf every candidate; order='index' by ascending item number, 'score' in `search`'s order, so a
+    row continues that item's `neighbours` list.  Two scans and no atomics (mmt_search_self_range_count,
+    mmt_search_self_range_fill); the total is known after the first -- the call's wait for the device -- and a total above
+    max_hits raises ValueError before anything of that size exists.  ShardedVideoIndex.neighbour_range is bit-identical."""
+    rows = self._self_args('neighbour_range', items, subset, source, unsupported)
+    self._range_options('neighbour_range', threshold, order, max_hits)
+    items = self._self_items('neighbour_range', rows, items)
+    r = items.shape[0]
+    if torch.is_tensor(threshold):
+      if threshold.device != self.device:
+        raise ValueError('neighbour_range: threshold must be on the index device %s, got %s' % (self.device, threshold.device))
+      if threshold.shape[0] != r:
+        raise ValueError('neighbour_range: %d rows but threshold %s' % (r, tuple(threshold.shape)))
+      thr = threshold.contiguous()
+    else:
+      thr = torch.full((r,), float(threshold), device=self.device, dtype=torch.float32)
+    return self._neighbour_range(rows, items, items if source is None else None, thr, subset, order, max_hits,
+                                 'neighbour_range')
+
+  def duplicate_groups(self, threshold, subset=None, max_hits=_MAX_HITS, **unsupported):
+    """The connected components of the threshold graph {g ~ h : sim(g, h) >= threshold, g != h} -> labels int64
+    [num_items] on the device: labels[g] is the smallest item number in g's component.  threshold a Python float.  subset:
+    both ends of an edge must be in it; items outside keep their own number.  The graph is undirected because sim is
+    symmetric to the bit.  Built from `neighbour_range` in row batches: only the edge list (each edge once) and
+    O(num_items) state are ever held, and more than max_hits hits raise ValueError.  The components come from
+    `connected_components`, minimum-label propagation with pointer jumping in torch ops.  The result goes unchanged into
+    `grouping`, so `search_groups` de-duplicates a list without anybody's labels."""
+    self._self_args('duplicate_groups', None, subset, None, unsupported)
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+      raise ValueError('duplicate_groups: threshold must be a float, got %s' % type(threshold).__name__)
+    if isinstance(max_hits, bool) or not isinstance(max_hits, int) or max_hits < 0:
+      raise ValueError('duplicate_groups: max_hits must be an int >= 0, got %r' % (max_hits,))
+    n = self.num_items
+    rows = torch.arange(n, device=self.device) if subset is None else torch.nonzero(subset.mask).reshape(-1)
+    src, dst, spent = [], [], 0
+    for r0 in range(0, rows.shape[0], _GROUP_ROWS):
+      part = rows[r0:r0 + _GROUP_ROWS]
+      thr = torch.full((part.shape[0],), float(threshold), device=self.device, dtype=torch.float32)
+      hits = self._neighbour_range(self, part, part, thr, subset, 'index', max_hits, 'duplicate_groups', spent)
+      spent += hits.indices.shape[0]
+      at = part[_csr_rows(hits.offsets)]
+      once = at < hits.indices   # an undirected edge is hit from both ends: kept from the lower one
+      src.append(at[once])
+      dst.append(hits.indices[once])
+    return connected_components(n, torch.cat(src), torch.cat(dst))
+
+  @staticmethod
+  def _range_options(who, threshold, order, max_hits):
+    """order, max_hits and the type of threshold of a range call, in the words of `range_search`."""
+    if order not in ('index', 'score'):
+      raise ValueError("%s: order must be 'index' or 'score', got %r" % (who, order))
+    if isinstance(max_hits, bool) or not isinstance(max_hits, int) or max_hits < 0:
+      raise ValueError('%s: max_hits must be an int >= 0, got %r' % (who, max_hits))
+    if torch.is_tensor(threshold):
+      if threshold.dtype != torch.float32:
+        raise ValueError('%s: threshold must be a float or a float32 tensor, got %s' % (who, threshold.dtype))
+      if threshold.dim() != 1:
+        raise ValueError('%s: threshold [R] expected, got %s' % (who, tuple(threshold.shape)))
+    elif isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+      raise ValueError('%s: threshold must be a float or a float32 tensor, got %s' % (who, type(threshold).__name__))
+
   def _group_ids(self, group_ids):
     """The checks of `grouping` -> (the ids as int32 [num_items] of their own, the number of distinct ids)."""
     if self.num_items == 0:
@@ -1669,6 +1869,79 @@ class VideoIndex(_Index):
       check(_lib.lib().mmt_search_pair_scores(ops._p(self.folded), ops._p(self.weights), ops._p(self.scales),
                                               _STORAGE[self.dtype], self.num_items, self.num_experts, self.dim, ops._p(cand),
                                               r, c, ops._p(sims), ops._stream()), 'mmt_search_pair_scores')
+
+  def _self_rows(self):
+    """This index's stored operand as the A side of the self-join entries: (rows, weights, scales or None, NA)."""
+    return self.folded, self.weights, self.scales, self.num_items
+
+  def _self_operands(self, a, items, own, r0, r1, subset):
+    """The fifteen leading arguments of the self-join entries for rows r0 .. r1 - 1: a = (rows, weights, scales or None,
+    NA), a stored operand on this device in this index's dtype; items int64 [R] or None (row r of the join is row r of a:
+    the operand is then handed over from row r0 on); own int64 [R] or None, this index's item each row must not meet;
+    then this index as the B side with the subset's words."""
+    rows, aw, asc, na = a
+    if items is None:
+      rows, aw, asc, na = rows[r0:], aw[r0:], None if asc is None else asc[r0:], na - r0
+    return (ops._p(rows), ops._p(aw), ops._p(asc), na, ops._p(None if items is None else items[r0:r1]),
+            ops._p(None if own is None else own[r0:r1]), r1 - r0, ops._p(self.folded), ops._p(self.weights),
+            ops._p(self.scales), self.num_items, ops._p(None if subset is None else subset.words), _STORAGE[self.dtype],
+            self.num_experts, self.dim)
+
+  def _neighbours(self, rows, items, own, k, subset, outs):
+    self._self_topk(rows._self_rows(), items, own, k, subset, outs)
+
+  def _self_topk(self, a, items, own, k, subset, outs):
+    """`neighbours` behind its checks: a, items, own as `_self_operands`; outs (scores, indices) [R >= 1, k] on this
+    device, prefilled with (-inf, -1): only the slots with a candidate are written.  Rows go in batches of whole 64-row
+    blocks whose chunk lists stay within _BATCH_BYTES.  Nothing here waits for the device."""
+    r, nv, L = outs[0].shape[0], self.num_items, _lib.lib()
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._row_batches(r, 8 * k * -(-nv // 4096)):
+        ws = torch.empty(L.mmt_self_topk_workspace_keys(r1 - r0, nv, k), device=self.device, dtype=torch.int64)
+        check(L.mmt_search_self_topk(*self._self_operands(a, items, own, r0, r1, subset), k, ops._p(ws),
+                                     ops._p(outs[0][r0:r1]), ops._p(outs[1][r0:r1]), ops._stream()), 'mmt_search_self_topk')
+
+  def _self_range_count(self, a, items, own, thr, subset):
+    """The count pass of `neighbour_range`, batch by batch: thr float32 [R] on this device -> (hits per row int64 [R], the
+    batches' workspaces as the fill pass wants them).  Nothing here waits for the device."""
+    r, nv, L = thr.shape[0], self.num_items, _lib.lib()
+    counts = torch.empty(r, device=self.device, dtype=torch.int64)
+    kept = []
+    for r0, r1 in self._batches(r, 1):
+      ws = torch.empty(L.mmt_self_range_workspace_ints(r1 - r0, nv), device=self.device, dtype=torch.int32)
+      check(L.mmt_search_self_range_count(*self._self_operands(a, items, own, r0, r1, subset), ops._p(thr[r0:r1]), ops._p(ws),
+                                          ops._p(counts[r0:r1]), ops._stream()), 'mmt_search_self_range_count')
+      kept.append(ws)
+    return counts, kept
+
+  def _self_range_fill(self, a, items, own, thr, subset, kept, offsets, indices, scores):
+    """The fill pass of `neighbour_range`: `kept` from `_self_range_count` of the same arguments, offsets int64 [R + 1]
+    into indices / scores."""
+    L = _lib.lib()
+    for (r0, r1), ws in zip(self._batches(thr.shape[0], 1), kept):
+      check(L.mmt_search_self_range_fill(*self._self_operands(a, items, own, r0, r1, subset), ops._p(thr[r0:r1]), ops._p(ws),
+                                         ops._p(offsets[r0:r1 + 1]), ops._p(indices), ops._p(scores), ops._stream()),
+            'mmt_search_self_range_fill')
+
+  def _neighbour_range(self, rows, items, own, thr, subset, order, max_hits, who, spent=0):
+    """`neighbour_range` behind its checks: items int64 [R] of `rows`' numbers, own as `_self_operands`, thr float32 [R].
+    Every batch is counted first, then comes the one allocation, then the fills, as `range_search`.  spent: the hits an
+    enclosing call has already used of max_hits."""
+    a, r = rows._self_rows(), items.shape[0]
+    with torch.cuda.device(self.device):
+      offsets = torch.zeros(r + 1, device=self.device, dtype=torch.int64)
+      total = 0
+      if r:
+        counted = self._self_range_count(a, items, own, thr, subset)
+        torch.cumsum(counted[0], 0, out=offsets[1:])
+        total = int(offsets[-1])
+      if spent + total > max_hits:
+        raise ValueError('%s: %d hits exceed max_hits = %d' % (who, spent + total, max_hits))
+      indices = torch.empty(total, device=self.device, dtype=torch.int64)
+      scores = torch.empty(total, device=self.device, dtype=torch.float32)
+      if total:
+        self._self_range_fill(a, items, own, thr, subset, counted[1], offsets, indices, scores)
+      return _range_result(offsets, indices, scores, order)
 
   def _rank_counts(self, q, qw, tg, scan):
     """`rank_counts` behind its checks: tg int64 [NQ >= 1, T] on the index device (with a pooling [num_sets, T], with an
@@ -2180,6 +2453,121 @@ class ShardedVideoIndex(_Index):
     staging.num_items = n
     renumbered = torch.where(live, torch.searchsorted(distinct, cand.clamp(min=0)), torch.full_like(cand, -1))
     staging._pair_scores(renumbered, sims)
+
+  def _stage_batches(self, r):
+    """Row ranges of the self-join's staging blocks: whole 64-row blocks whose stored bytes, weights and scales stay
+    within _BATCH_BYTES."""
+    per_row = self.num_experts * self.dim * torch.empty(0, dtype=self.dtype).element_size() + 4 * self.num_experts + 4
+    batch = max(64, (_BATCH_BYTES // per_row) // 64 * 64)
+    return [(r0, min(r, r0 + batch)) for r0 in range(0, r, batch)]
+
+  def _stage(self, part):
+    """The staging block of the self-join: the stored bytes, weights and scales of the items `part` (int64 [n] global
+    numbers on the primary, repeats allowed), gathered from the shards that hold them -> (bytes uint8 [n, row bytes],
+    weights float32 [n, M], scales float32 [n] or None) on the primary, row j = item part[j]."""
+    n, m = part.shape[0], self.num_experts
+    row_bytes = m * self.dim * torch.empty(0, dtype=self.dtype).element_size()
+    with torch.cuda.device(self.device):
+      stored = torch.empty(n, row_bytes, device=self.device, dtype=torch.uint8)
+      weights = torch.empty(n, m, device=self.device, dtype=torch.float32)
+      scales = torch.empty(n, device=self.device, dtype=torch.float32) if self.dtype == FP8 else None
+    where, local = self._shard_of[part], self._local_of[part]
+    for s, sh in self._live():
+      at = torch.nonzero(where == s).reshape(-1)
+      if at.numel() == 0:
+        continue
+      with torch.cuda.device(sh.device):
+        rows = local[at].to(sh.device)
+        parts = [sh.index.folded.view(torch.uint8)[rows], sh.index.weights[rows],
+                 None if scales is None else sh.index.scales[rows]]
+      stored[at] = parts[0].to(self.device)
+      weights[at] = parts[1].to(self.device)
+      if scales is not None:
+        scales[at] = parts[2].to(self.device)
+    return stored, weights, scales
+
+  def _staged(self, items, r0, r1, thr, subset, live):
+    """What every live shard runs a self-join entry with for rows r0 .. r1 - 1: {shard: (the staging block on its device
+    as the A side, the rows' local numbers there or -1, the rows' thresholds or None, its part of the subset)}."""
+    part = items[r0:r1]
+    block = self._stage(part)
+    out = {}
+    for s, sh in live:
+      with torch.cuda.device(sh.device):
+        a = tuple(None if t is None else t.to(sh.device) for t in block) + (r1 - r0,)
+        out[s] = (a, self._local(part, s).to(sh.device), None if thr is None else thr[r0:r1].to(sh.device),
+                  None if subset is None else subset.parts[s])
+    return out
+
+  def _neighbours(self, rows, items, own, k, subset, outs):
+    """`neighbours` behind its checks: items (global numbers) and outs on the primary.  Per row batch the rows' stored
+    bytes, weights and scales are gathered from their shards into a staging block, the block is copied to every shard's
+    device, every shard runs the one entry with A = the block, B = its own items and self = the row's local number there
+    or -1, and the lists are renumbered and merged on the primary (mmt_search_merge_lists).  sim depends on the two
+    stored rows alone, so the bits are those of one VideoIndex."""
+    live = self._live(subset)
+    tables = self._tables(tuple(s for s, _ in live))
+    for r0, r1 in self._stage_batches(items.shape[0]):
+      staged = self._staged(items, r0, r1, None, subset, live)
+
+      def lists(s, sh):
+        a, local, _, part = staged[s]
+        mine = _lists(2, sh.device, r1 - r0, k, vacant=True)
+        sh.index._self_topk(a, None, local, k, part, mine)
+        return mine
+      self._merged(tuple(o[r0:r1] for o in outs), live, k, 'mmt_search_merge_lists', tables, lists)
+
+  def _neighbour_range(self, rows, items, own, thr, subset, order, max_hits, who, spent=0):
+    """`neighbour_range` behind its checks, over all shards, assembled as `range_search` assembles its rows: per staging
+    batch every shard counts the hits among its own items; the totals are summed on the primary and held against max_hits
+    before any shard allocates its outputs; the batches are staged again, every shard fills a CSR of its own, whose local
+    numbers go through its table to global ones, and the primary orders the hits by (row, global item)."""
+    r = items.shape[0]
+    live, batches = self._live(subset), self._stage_batches(r)
+    counted = {}
+    for b, (r0, r1) in enumerate(batches):
+      for (s, sh), (a, local, t, part) in zip(live, self._staged(items, r0, r1, thr, subset, live).values()):
+        with torch.cuda.device(sh.device):
+          counted[b, s] = sh.index._self_range_count(a, None, local, t, part)
+    with torch.cuda.device(self.device):
+      per_shard = torch.zeros(len(live), r, device=self.device, dtype=torch.int64)
+      for b, (r0, r1) in enumerate(batches):
+        for i, (s, _) in enumerate(live):
+          per_shard[i, r0:r1] = counted[b, s][0].to(self.device)
+      cells = [per_shard[:, r0:r1].sum(1) for r0, r1 in batches]
+      cells = torch.stack(cells).tolist() if cells else []   # [batch][shard]: the call's one wait for the devices
+      total = sum(sum(c) for c in cells)
+      if spent + total > max_hits:
+        raise ValueError('%s: %d hits exceed max_hits = %d' % (who, spent + total, max_hits))
+      offsets = torch.zeros(r + 1, device=self.device, dtype=torch.int64)
+      if r:
+        torch.cumsum(per_shard.sum(0), 0, out=offsets[1:])
+    at, hit, sims = [], [], []
+    for b, (r0, r1) in enumerate(batches):
+      if not any(cells[b]):
+        continue
+      staged = self._staged(items, r0, r1, thr, subset, live)
+      for i, (s, sh) in enumerate(live):
+        if not cells[b][i]:
+          continue
+        a, own_s, t, part = staged[s]
+        with torch.cuda.device(sh.device):
+          local = torch.zeros(r1 - r0 + 1, device=sh.device, dtype=torch.int64)
+          torch.cumsum(counted[b, s][0], 0, out=local[1:])
+          idx = torch.empty(cells[b][i], device=sh.device, dtype=torch.int64)
+          sc = torch.empty(cells[b][i], device=sh.device, dtype=torch.float32)
+          sh.index._self_range_fill(a, None, own_s, t, part, counted[b, s][1], local, idx, sc)
+        at.append(_csr_rows(local.to(self.device)) + r0)
+        hit.append(sh.ids[idx.to(self.device)])
+        sims.append(sc.to(self.device))
+    with torch.cuda.device(self.device):
+      if not at:
+        return RangeResult(offsets, torch.empty(0, device=self.device, dtype=torch.int64),
+                           torch.empty(0, device=self.device, dtype=torch.float32))
+      at, hit, sims = torch.cat(at), torch.cat(hit), torch.cat(sims)
+      by_item = torch.argsort(hit, stable=True)
+      perm = by_item[torch.argsort(at[by_item], stable=True)]
+      return _range_result(offsets, hit[perm], sims[perm], order)
 
   def grouping(self, group_ids):
     """group_ids: int64 [num_items] on the primary device, as VideoIndex.grouping -> ShardedGrouping: the ids cut into one

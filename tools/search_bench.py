@@ -104,7 +104,15 @@ bf16 and an fp8 index: search(k = 128) alone, `rescore`, the Gram launches (mmt_
 batches), the selection launch (mmt_search_mmr), the whole call, and the torch route to the Gram (index_select of the
 shortlist rows + torch.bmm, in row batches under the same _BATCH_BYTES budget); the Gram launch's share of the fp32 or bf16
 matrix peak.  --runs rounds, every variant once per round, interleaved; median and spread.  Joins --out (default
-profiles/search_bench.json) under 'diverse'."""
+profiles/search_bench.json) under 'diverse'.
+
+--neighbours times the gallery self-join over 262 144 items with 4 096 row items, k = 10, on a float32, a bf16 and an fp8
+index: `neighbours`, search(k = 10) of 4 096 query rows on the same index (the same tile count), that search with one
+exclusion per query (the masked selection and prefilled outputs the join runs with), the torch route
+(dequantised rows @ chunk.T with the denominators and topk over chunks under the same _BATCH_BYTES budget) and
+`neighbour_range` at per-row thresholds that give 16 hits per row; one full self-join (items=None) per storage as a single
+run.  --runs rounds, every variant once per round, interleaved; median and spread.  Joins --out (default
+profiles/search_bench.json) under 'neighbours'."""
 import argparse
 import json
 import math
@@ -825,8 +833,103 @@ def diverse_mode(a, dev):
   return row
 
 
+def torch_neighbours(index, items, k, budget):
+  """The torch route to `neighbours`: the rows dequantised to a dtype torch.matmul takes (an fp8 row to bf16, exactly, with
+  its scale applied to the product), f_rows @ f_chunk.T with the denominators, the self pair masked by number, and topk
+  over chunks of columns whose [R, chunk] fp32 scores stay within `budget` bytes, merged by a running topk.  ->
+  (scores float32 [R, k], indices int64 [R, k])."""
+  wide = torch.float32 if index.dtype is torch.float32 else torch.bfloat16
+  r, nv, dev = items.shape[0], index.num_items, items.device
+  f_rows, w_rows = index.folded.index_select(0, items).to(wide), index.weights.index_select(0, items)
+  s_rows = None if index.scales is None else index.scales.index_select(0, items)
+  cols = max(1, budget // (4 * r))
+  best_s = torch.full((r, k), float('-inf'), device=dev)
+  best_i = torch.full((r, k), -1, device=dev, dtype=torch.int64)
+  for c0 in range(0, nv, cols):
+    c1 = min(nv, c0 + cols)
+    num = (f_rows @ index.folded[c0:c1].to(wide).T).float()
+    if s_rows is not None:
+      num = num * (s_rows[:, None] * index.scales[c0:c1][None, :])
+    den = w_rows @ index.weights[c0:c1].T
+    sims = num / torch.where(den == 0, torch.full_like(den, 1e-5), den)
+    sims.masked_fill_(torch.arange(c0, c1, device=dev)[None, :] == items[:, None], float('-inf'))
+    s, i = sims.topk(min(k, c1 - c0), dim=1)
+    s, i = torch.cat([best_s, s], 1), torch.cat([best_i, i + c0], 1)
+    best_s, at = s.topk(k, dim=1)
+    best_i = i.gather(1, at)
+  return best_s, best_i
+
+
+def neighbours_mode(a, dev):
+  """The gallery self-join over NV = 262 144 items with R = 4 096 row items, k = 10, per storage dtype: `neighbours`, beside
+  search(k = 10) of 4 096 query rows on the same index (the same tile count; on bf16 and fp8 it issues two MFMAs per fragment
+  where the join issues one) and the torch route under the same byte budget; `neighbour_range` at per-row thresholds that
+  give 16 hits per row; and one full self-join (items=None), a single run."""
+  from mmt_amd import search
+  nq, nv = SHAPES['S3']
+  chunk, hits = 8192, 16
+  gen = torch.Generator(device=dev).manual_seed(0)
+  nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
+  dtypes = {'float32': torch.float32, 'bfloat16': torch.bfloat16, 'float8_e4m3fn': torch.float8_e4m3fn}
+  idx = {n: VideoIndex.empty(nv, M, D, dev, dtype=t) for n, t in dtypes.items()}
+  for at in range(0, nv, chunk):
+    g = nrm(torch.randn(chunk, M, D, device=dev, generator=gen))
+    gw = torch.softmax(torch.randn(chunk, M, device=dev, generator=gen), -1)
+    for index in idx.values():
+      index.add(g, gw)
+  q = nrm(torch.randn(nq, M, D, device=dev, generator=gen) + 0.3 * g[torch.arange(nq, device=dev) % chunk])
+  qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
+  items = torch.arange(nq, device=dev) * (nv // nq)       # 4 096 rows spread over the gallery
+  fns, thr = {}, {}
+  for n, index in idx.items():
+    thr[n] = index.neighbours(k=hits, items=items)[0][:, hits - 1].contiguous()   # the 16th best sim of every row
+    fns[n + '/neighbours'] = lambda index=index: index.neighbours(k=K, items=items)
+    fns[n + '/search_k10'] = lambda index=index: index.search(q, qw, k=K)
+    # the same search with one exclusion per query: the masked selection and prefilled outputs the join runs with
+    fns[n + '/search_k10_exclude1'] = lambda index=index: index.search(q, qw, k=K, exclude=items[:, None])
+    fns[n + '/neighbours_torch'] = lambda index=index: torch_neighbours(index, items, K, search._BATCH_BYTES)
+    fns[n + '/neighbour_range'] = lambda index=index, n=n: index.neighbour_range(thr[n], items=items)
+  ts = {n: [] for n in fns}
+  for r in range(a.runs):
+    for n, fn in fns.items():
+      t, _, _, _ = timed(fn, a.min_seconds)
+      ts[n].append(t)
+    print('round %d of %d' % (r + 1, a.runs), file=sys.stderr, flush=True)
+  flop = 2.0 * nq * nv * M * D
+  row = {'R': nq, 'NQ': nq, 'NV': nv, 'flop': flop, 'range_hits_per_row': hits}
+  for n in fns:
+    row[n] = dict(seconds_median=float(np.median(ts[n])), seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n])
+  for n, index in idx.items():
+    ours, scan, theirs = row[n + '/neighbours'], row[n + '/search_k10'], row[n + '/neighbours_torch']
+    peak = PEAK if n == 'float32' else PEAK_BF16
+    mine, ref = index.neighbours(k=K, items=items), torch_neighbours(index, items, K, search._BATCH_BYTES)
+    ranged = index.neighbour_range(thr[n], items=items)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    full = index.neighbours(k=K)
+    e1.record()
+    torch.cuda.synchronize()
+    row[n + '/summary'] = dict(
+        neighbours_over_search=ours['seconds_median'] / scan['seconds_median'],
+        spread_seconds_of_the_two=max(ours['seconds_spread'], scan['seconds_spread']),
+        torch_over_neighbours=theirs['seconds_median'] / ours['seconds_median'],
+        neighbours_tflops=flop / ours['seconds_median'] / 1e12,
+        neighbours_fraction_of_matrix_peak=flop / ours['seconds_median'] / peak, matrix_peak_flops=peak,
+        top1_agreement_with_torch=float((mine[1][:, 0] == ref[1][:, 0]).float().mean()),
+        max_abs_score_difference_to_torch=float((mine[0] - ref[0]).abs().max()),
+        range_hits_total=int(ranged.offsets[-1]),
+        full_self_join_seconds_single_run=e0.elapsed_time(e1) / 1e3,
+        full_self_join_rows_equal_the_batch=bool(torch.equal(full[1][items], mine[1])))
+    del full
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
+  ap.add_argument('--neighbours', action='store_true', help='time the gallery self-join (R = 4 096 rows, k = 10) on a float32, '
+                  'a bf16 and an fp8 index of 262 144 items against search(k = 10) of 4 096 queries and the torch route, '
+                  'neighbour_range at 16 hits per row, and one full self-join (no other mode flag)')
   ap.add_argument('--diverse', action='store_true', help='time the stages of search_diverse (shortlist 128, k = 10) on a '
                   'float32, a bf16 and an fp8 index of 262 144 items: search(k = 128), rescore, the Gram launches, the '
                   'selection launch and the torch route to the Gram (no other mode flag)')
@@ -913,6 +1016,21 @@ def main():
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
+  if a.neighbours:
+    res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'neighbours', 'runs': a.runs,
+           'min_seconds': a.min_seconds}
+    res.update(neighbours_mode(a, dev))
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_bench.json')
+    kept = {}
+    if os.path.exists(out):  # joins the results of that file, as --diverse does
+      with open(out) as f:
+        kept = json.load(f)
+    kept['neighbours'] = res
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+      json.dump(kept, f, indent=1)
+    print(json.dumps(res))
+    return
   if a.diverse:
     res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'diverse', 'runs': a.runs,
            'min_seconds': a.min_seconds}
