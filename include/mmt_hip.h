@@ -748,6 +748,25 @@ int mmt_search_self_range_fill(const void* a_rows, const float* a_weights, const
                                const float* thr, const int32_t* ws, const int64_t* offsets, int64_t* indices, float* scores,
                                void* stream);
 
+/* Softmax over the gallery (search_lse.hip), additive: one scan over the descriptor and its size function, nothing that
+ * exists changes and mmt_abi_version() stays 6.  It serves search.py's `query_lse` and `search_softmax`: the row-wise
+ * log-partition of softmax(beta * score(q, .)) over a query's candidates, as an INTEGER sum, so that the result is one
+ * number whatever the chunking, the row batching, the launch geometry, the item order or the shard.
+ * mmt_search_row_expsum (subset; fp32, bf16, fp8): per query row, over the allowed items g, in fp32
+ *     x = fl(beta * score(q, g)),  e = expf(x - xmax[q]),  t = (int64) rint(ldexpf(e, F)),   ws[q][c] = sum of t over chunk c
+ *   score the bits mmt_search_topk gives the pair (the scans' own tile), the multiply rounded on its own, expf the
+ *   expression of mmt_search_col_lse's column pass.  xmax fp32 [NQ]: fl(beta * the row's top-1 score among the same
+ *   candidates), the caller's mmt_search_topk with k = 1, so that e <= 1 and the top-1 item gives exactly 2^F.  F: the
+ *   caller's 62 - ceil(log2(max(N, 2))) for the N items of the WHOLE gallery (all shards), 0 <= F <= 62: every term is at
+ *   most 2^F and there are at most 2^(62 - F) of them, so no int64 sum overflows.  ws int64
+ *   [mmt_row_expsum_workspace_ints64(NQ, NV)] = [NQ][ceil(NV / chunk)], every slot written (0 for a chunk without an
+ *   allowed item); the caller adds a row's slots -- and the shards' -- in any order.  MMT_ERR_ARG: a part of the descriptor
+ *   other than subset, a null operand, xmax or ws, beta not finite or <= 0, F outside 0 .. 62, and the common shape gates;
+ *   MMT_ERR_ALIGN: q, q_lo, g or subset off a 16-byte boundary.  All refused before any launch.  No atomics; one writer per
+ *   slot. */
+int64_t mmt_row_expsum_workspace_ints64(int NQ, int NV);
+int mmt_search_row_expsum(const MmtSearchScan* scan, float beta, const float* xmax, int F, int64_t* ws, void* stream);
+
 /* Beside the scans.
  * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> the subset words, padding included: one ballot per 64
  *   items, one writer per word.

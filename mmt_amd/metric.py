@@ -8,6 +8,8 @@ the gathered embeddings (the reference does both on the CPU: trainer/trainer.py:
 `retrieval_metrics_indexed(...)` gives the same metrics from exact rank counts over a search.VideoIndex, without the
 matrix: for eval sets whose N_text x N_video similarity does not fit; caption_mode='avg' gives the reference's merged-caption
 evaluation the same way (query-set pooling for text-to-video, item-set pooling for video-to-text).
+`info_nce_indexed(...)` evaluates the reference's InfoNceLoss (model/loss.py:68-81) over a whole evaluation set the same
+way: the row log-sum-exps from VideoIndex.query_lse, the column ones from hub_norm, the diagonal from target_scores.
 """
 import numpy as np
 import torch
@@ -259,6 +261,43 @@ def _metrics_avg(make_index, devices, vid, vw, txt, tw, c, cut, dtype):
                         subset=None if cut is None else ip.subset(cut_d)).cpu().numpy()
   out['v2t_metrics'] = dict(cols2metrics(cols, cols.size), cols=cols)
   return out
+
+
+def info_nce_indexed(vid_embds, text_embds, vid_weights, text_weights, scale=1.0, dtype=torch.float32):
+  """The reference's InfoNceLoss (model/loss.py:68-81: cross entropy of the rows plus cross entropy of the columns, each a
+  mean, targets on the diagonal) on scale * sims over a whole evaluation set with ONE caption per video -- vid (B, M, d) /
+  (B, M), text (B, M, 1, d) / (B, 1, M) or (B, M, d) / (B, M) -- without the B x B matrix, from three scans of one
+  search.VideoIndex of the videos queried with the captions:
+      rows     : query_lse(captions, beta=scale).lse[i] = log sum_j exp(scale * sims[i, j])
+      columns  : hub_norm(bank=captions, beta=scale).lse[j] = log sum_i exp(scale * sims[i, j])
+      diagonal : target_scores(captions, i -> video i)
+  -> {'loss': t2v + v2t, 't2v': mean_i(rows[i] - scale * sims[i, i]), 'v2t': mean_j(columns[j] - scale * sims[j, j])} as
+  Python floats, the differences and the means taken in float64.  scale: a Python float, 0 < scale < inf.  dtype: the
+  index storage, torch.float32 or torch.bfloat16 (the loss is then that of the bfloat16 index's own scores);
+  torch.float8_e4m3fn is refused, because `hub_norm` is."""
+  from .search import FP8, VideoIndex
+  if isinstance(scale, bool) or not isinstance(scale, float) or not 0 < scale < float('inf'):
+    raise ValueError('info_nce_indexed: scale must be a float with 0 < scale < inf, got %r' % (scale,))
+  if dtype == FP8:
+    raise ValueError('info_nce_indexed: %s is not supported: hub_norm is not available on such an index' % (dtype,))
+  if dtype not in (torch.float32, torch.bfloat16):
+    raise ValueError('info_nce_indexed: dtype must be torch.float32 or torch.bfloat16, got %r' % (dtype,))
+  if len(vid_embds.shape) != 3:
+    raise ValueError('info_nce_indexed: vid_embds (B, M, d) expected, got %s' % (tuple(vid_embds.shape),))
+  b, m, d = vid_embds.shape
+  if tuple(text_embds.shape) not in ((b, m, 1, d), (b, m, d)):
+    raise ValueError('info_nce_indexed: one caption per video, text_embds (%d, %d, 1, %d) expected, got %s' % (
+        b, m, d, tuple(text_embds.shape)))
+  vid = _as_cuda_f32(vid_embds)
+  vw = _as_cuda_f32(vid_weights).reshape(b, m).contiguous()
+  txt = _as_cuda_f32(text_embds).reshape(b, m, d)
+  tw = _as_cuda_f32(text_weights).reshape(b, m).contiguous()
+  videos = VideoIndex(vid, vw, dtype=dtype)
+  rows = videos.query_lse(txt, tw, scale).lse.double()
+  cols = videos.hub_norm(txt, tw, scale).lse.double()
+  diag = videos.target_scores(txt, tw, torch.arange(b, device=vid.device)).double() * scale
+  t2v, v2t = float((rows - diag).mean()), float((cols - diag).mean())
+  return {'loss': t2v + v2t, 't2v': t2v, 'v2t': v2t}
 
 
 def compress_predictions(query_masks, sims, topk=10):

@@ -306,6 +306,37 @@ ShardedVideoIndex has the three calls, bit-identical: per row batch the rows' st
 on the primary and copied to every shard, which joins them against its own items; lists are merged
 (mmt_search_merge_lists), CSR rows assembled as `range_search` assembles them.  Out of scope: norm=, pooling=,
 item_pooling=, grouping=, after= and exclude= raise ValueError naming the option.
+
+    lse = index.query_lse(q, qw, beta=20.0, subset=None)          # QueryLse: .lse [NQ], .top_scores, .top_items, .sums, .bits
+    log_p = lse.log_prob(scores)                                  # any [NQ, ...] scores of those queries; .prob = exp
+    scores, indices, log_probs = index.search_softmax(q, qw, k=10, beta=20.0, subset=None)
+
+The twelfth question: what a score is worth.  The eleven above are about order; the common first use of a dual-encoder index
+is softmax(beta * sims, dim=-1) -- the probability of each item given the query, the confidence of the top hit, a scale on
+which the scores of different queries compare -- and its row-wise log-partition is the missing half of the contrastive loss
+this project trains with (loss.InfoNceLoss, large_sim.ShardedInfoNceLoss, model/loss.py:68-81).  `hub_norm` has the column
+direction; the row direction cannot be composed from the calls above (`search` returns at most 128 scores per row,
+`threshold_counts` counts), and an index of the queries searched with the items re-rounds the other operand.  Every result
+here depends on the query and the set of candidates only, and a floating-point sum over 262 144 items cannot keep that
+rule; an integer sum can.  In fp32 unless stated, s the bits `search` gives the pair on this index (any dtype):
+    x(q, g) = fl(beta * s(q, g))                           a rounded multiply
+    xmax[q] = max_g x(q, g) = fl(beta * top-1 score)       fl(beta * .) is monotone: search(k=1, subset=)
+    e(q, g) = expf(x(q, g) - xmax[q])                      in [0, 1], exactly 1 for the top-1 item
+    t(q, g) = (int64) rint(ldexp(e(q, g), F))              F = lse_bits(num_items) = 62 - ceil(log2(max(num_items, 2)))
+    T[q]    = sum_g t(q, g)                                int64: t <= 2^F, num_items <= 2^(62 - F), so T <= 2^62
+    lse[q]  = float32(float64(xmax[q]) + log(float64(T[q])) - F ln 2)       lse_from_sums, torch float64 ops
+    log_prob(q, g) = fl(x(q, g) - lse[q]),  prob = exp(log_prob)            as the norm= slot: multiply, then subtract
+T[q] is one exact number whatever the chunking, the row batching, the block geometry, the order of the items or the shard.
+Quantising a term costs at most half a unit, so at most num_items * 2^-(F + 1) relative on T (T >= 2^F), at most 2^(2c - 63)
+for num_items <= 2^c: 2^-25 at 2^19 items, below half an fp32 ulp.  Two scans: the top-1 is `search`'s, the sum is the
+scans' own score tile with the selection replaced by the sum (mmt_search_row_expsum, search_lse.hip: four threads per
+row, an int64 register each across a chunk's tiles, one writer per (row, chunk); a tile without an allowed item is skipped
+before its K loop).  `search_softmax` is host code: `search`, `query_lse` fed the top-1 already found, `log_prob`.
+ShardedVideoIndex.query_lse takes xmax from the merged top-1 and F from the global num_items; every shard sums over its own
+items and the int64 partials are added on the primary: bit-identical in .sums and .lse.  metric.info_nce_indexed evaluates
+the reference's InfoNceLoss over a whole evaluation set on it (rows: `query_lse`; columns: `hub_norm`; diagonal:
+`target_scores`).  Out of scope: exclude=, norm= (a dual softmax), pooling=, item_pooling=, after= and grouping= raise
+ValueError naming the option; a single-pass online softmax would save a scan and lose the bit-identity across shards.
 """
 import ctypes
 import math
@@ -329,6 +360,7 @@ _POOL_MODES = {'mean': 0, 'max': 1}  # the `mode` of the pooled entry points
 _BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 bytes per element either way) + chunk lists
 _MAX_HITS = 1 << 27  # default cap of a range search's total: a guard against a mistyped threshold, not a tuned number
 _NOT_SELF = ('norm', 'pooling', 'item_pooling', 'grouping', 'after', 'exclude')  # options the self-join refuses by name
+_NOT_LSE = ('exclude', 'norm', 'pooling', 'item_pooling', 'after', 'grouping')  # options `query_lse` refuses by name
 _GROUP_ROWS = 1 << 16  # rows per `neighbour_range` call of `duplicate_groups`: the CSR of a batch is dropped for its edges
 FP8 = torch.float8_e4m3fn
 _DTYPES = {torch.float32: 4, torch.bfloat16: 8, FP8: 16}  # storage dtype -> multiple d must have (16-byte folded rows)
@@ -679,9 +711,61 @@ def connected_components(num_items, src, dst):
     labels = new
 
 
-def _check_beta(beta):
+def _check_beta(beta, who='hub_norm'):
   if isinstance(beta, bool) or not isinstance(beta, float) or not 0 < beta < math.inf:
-    raise ValueError('hub_norm: beta must be a float with 0 < beta < inf, got %r' % (beta,))
+    raise ValueError('%s: beta must be a float with 0 < beta < inf, got %r' % (who, beta))
+
+
+def lse_bits(num_items):
+  """F of `query_lse` for an index of num_items items: 62 - ceil(log2(max(num_items, 2))), the fixed-point position of the
+  terms of the integer sum.  A term is at most 2^F and there are at most num_items <= 2^(62 - F) of them, so the int64
+  sum stays at or below 2^62."""
+  if isinstance(num_items, bool) or not isinstance(num_items, int) or not 1 <= num_items < 2 ** 62:
+    raise ValueError('lse_bits: num_items must be an int in 1 .. 2^62 - 1, got %r' % (num_items,))
+  return 62 - max(1, (num_items - 1).bit_length())
+
+
+def fixed_terms(e, bits):
+  """The terms of the integer sum: float32 e in [0, 1] (any shape, any device) -> int64 rint(ldexp(e, bits)).  The scaling
+  by 2^bits is exact; the rounding is to nearest, ties to even, and changes only values below 2^24 (a float32 at or above
+  that is an integer already).  e = 1 gives 2^bits, a value below 2^-(bits + 1) gives 0."""
+  return torch.ldexp(e.to(torch.float32), torch.tensor(bits, device=e.device)).round().to(torch.int64)
+
+
+def lse_from_sums(xmax, sums, bits):
+  """The log-sum-exp of `query_lse` from its integer sums: float32 xmax [NQ] and int64 sums [NQ] (same device) ->
+  float32(float64(xmax) + log(float64(sums)) - bits * ln 2), evaluated in float64 in that order."""
+  return (xmax.to(torch.float64) + torch.log(sums.to(torch.float64)) - bits * math.log(2.0)).to(torch.float32)
+
+
+class QueryLse:
+  """The softmax normaliser of a batch of queries over an index (VideoIndex.query_lse), on the index device (the primary of
+  a sharded index): `lse` float32 [NQ], lse[q] = log sum_g exp(fl(beta * score(q, g))) over the query's `count`
+  candidates; `beta`; `top_scores` float32 [NQ] / `top_items` int64 [NQ], the search(k=1) row of each query; `sums` int64
+  [NQ], the integer sums T[q] of the terms rint(exp(x - xmax) * 2^bits); `bits` = lse_bits(num_items); `num_items` and
+  `device` it was built for.  `log_prob` and `prob` put scores of THESE queries on THIS index on the softmax's scale."""
+
+  def __init__(self, lse, beta, top_scores, top_items, sums, bits, num_items, count):
+    self.lse, self.beta, self.top_scores, self.top_items = lse, beta, top_scores, top_items
+    self.sums, self.bits, self.num_items, self.count, self.device = sums, bits, num_items, count, lse.device
+
+  def log_prob(self, scores):
+    """scores float32 [NQ, ...] of these queries on that index (`search`'s list, `target_scores`, a RangeResult row by
+    row) -> fl(fl(beta * score) - lse[q]) of their shape: a rounded multiply, then a rounded subtract, as the norm= slot.
+    A vacant slot (-inf) stays -inf."""
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32:
+      raise ValueError('log_prob: scores must be a float32 tensor, got %s' % (
+          scores.dtype if torch.is_tensor(scores) else type(scores).__name__))
+    if scores.dim() < 1 or scores.shape[0] != self.lse.shape[0]:
+      raise ValueError('log_prob: scores [%d, ...] expected, got %s' % (self.lse.shape[0], tuple(scores.shape)))
+    if scores.device != self.device:
+      raise ValueError('log_prob: scores must be on %s, got %s' % (self.device, scores.device))
+    x = scores * torch.tensor(self.beta, device=self.device, dtype=torch.float32)
+    return x - self.lse.reshape((-1,) + (1,) * (scores.dim() - 1))
+
+  def prob(self, scores):
+    """exp(log_prob(scores)): the share of the candidates' probability mass each scored item holds for its query."""
+    return torch.exp(self.log_prob(scores))
 
 
 def _check_rk(who, k):
@@ -1038,6 +1122,71 @@ class _Index:
     if b.shape[0] < 1:
       raise ValueError('csls_norm: the bank holds no queries')
     return self._csls_norm(b, bw, k, self._bank_hubs(b, bw, dynamic))
+
+  def _lse_args(self, who, beta, subset, unsupported):
+    """The checks of `query_lse` and `search_softmax` that look at no value, before anything touches the device."""
+    for name in unsupported:
+      if name not in _NOT_LSE:
+        raise TypeError('%s() got an unexpected keyword argument %r' % (who, name))
+      raise ValueError('%s: %s= is out of scope: the softmax runs over the plain scores of a subset' % (who, name))
+    _check_beta(beta, who)
+    if self.num_items == 0:
+      raise ValueError('%s: the index holds no items' % who)
+    if subset is not None:
+      self._subset(subset, who)
+
+  def query_lse(self, embds, weights, beta, subset=None, **unsupported):
+    """The twelfth question: what a score is worth.  Queries in either layout of `search`, beta a Python float with
+    0 < beta < inf, subset from this index's `subset` -> QueryLse: per query the log-partition of
+    softmax(beta * score(q, .)) over its candidates (every stored item, or the subset's), without the NQ x NV matrix.
+    All in fp32 unless stated, with s(q, g) the bits `search` gives the pair on this index (any of the three dtypes):
+        x(q, g) = fl(beta * s(q, g))                     a rounded multiply
+        xmax[q] = the largest x(q, g) = fl(beta * top-1 score): fl(beta * .) is monotone; from search(k=1, subset=)
+        e(q, g) = expf(x(q, g) - xmax[q])                in [0, 1]; the top-1 item gives exactly 1
+        t(q, g) = (int64) rint(ldexp(e(q, g), F))        F = lse_bits(num_items) = 62 - ceil(log2(max(num_items, 2)))
+        T[q]    = sum_g t(q, g)                          an int64 sum: t <= 2^F, num_items <= 2^(62 - F), so T <= 2^62
+        lse[q]  = float32(float64(xmax[q]) + log(float64(T[q])) - F ln 2)      torch float64 ops (lse_from_sums)
+    An integer sum is associative, so T[q] -- and with it lse[q] -- is ONE number whatever the chunking, the row batching,
+    the launch geometry, the order of the items or the shard: a function of the query and the set of candidates only, the
+    rule every other call here keeps and no floating-point sum over 262 144 items can.  The price is the quantisation of
+    a term, at most half a unit: at most num_items * 2^-(F + 1) relative on T (T >= 2^F: the top-1 term), which is at most
+    2^(2c - 63) for num_items <= 2^c -- 2^-25 at 2^19 items, below half an fp32 ulp; 2^-15 at 2^24.  Two scans: the
+    top-1 (`search`), then the sum (mmt_search_row_expsum: the scans' own score tile with the selection replaced by the
+    sum; a tile without an allowed item is skipped before its K loop).  Rows go in batches of whole 64-row blocks within
+    _BATCH_BYTES.  ShardedVideoIndex.query_lse takes xmax from the merged top-1 and F from the global num_items, every
+    shard sums over its own items with its part of the subset, and the int64 partials are added on the primary:
+    bit-identical to one VideoIndex over the same items, in `.sums` and `.lse` alike.  Out of scope: exclude=, norm=,
+    pooling=, item_pooling=, after= and grouping= raise ValueError naming the option."""
+    self._lse_args('query_lse', beta, subset, unsupported)
+    q, qw = self._queries(embds, weights)
+    return self._query_lse(q, qw, beta, subset)
+
+  def _query_lse(self, q, qw, beta, subset, top=None):
+    """`query_lse` behind its checks.  top: the (scores [NQ, >= 1], indices) of a `search` over the same candidates that the
+    caller has already (search_softmax), whose first column is the top-1."""
+    scan = _Scan(subset)
+    if top is None:
+      top = self._search(q, qw, 1, scan)
+    bits = lse_bits(self.num_items)
+    with torch.cuda.device(self.device):
+      top_scores, top_items = top[0][:, 0].contiguous(), top[1][:, 0].contiguous()
+      xmax = top_scores * torch.tensor(beta, device=self.device, dtype=torch.float32)
+      sums = self._row_expsum(q, qw, beta, xmax, bits, scan)
+      lse = lse_from_sums(xmax, sums, bits)
+    return QueryLse(lse, beta, top_scores, top_items, sums, bits, self.num_items, scan.candidates(self))
+
+  def search_softmax(self, embds, weights, k=10, beta=None, subset=None, **unsupported):
+    """`search` with the probabilities: queries, k and subset as there, beta as `query_lse` -> (scores [NQ, k'] float32,
+    indices [NQ, k'] int64, log_probs [NQ, k'] float32): `search`'s lists, bit for bit, and for every slot
+    fl(fl(beta * score) - lse[q]), the log of the item's share of softmax(beta * score(q, .)) over the candidates; a vacant
+    slot gets -inf.  Host code: `search`, then `query_lse` fed the top-1 that search has found already -- two scans, not
+    three -- then QueryLse.log_prob."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+      raise ValueError('search_softmax: k must be an int in 1..%d, got %r' % (MAX_K, k))
+    self._lse_args('search_softmax', beta, subset, unsupported)
+    q, qw = self._queries(embds, weights)
+    scores, indices = self._search(q, qw, k, _Scan(subset))
+    return scores, indices, self._query_lse(q, qw, beta, subset, (scores, indices)).log_prob(scores)
 
   def _after(self, after, pooling=None, item_pooling=None):
     """Type, device and rank of `after`, and what it does not combine with: all that can be said before the queries are
@@ -1776,6 +1925,26 @@ class VideoIndex(_Index):
                                    ops._stream()), 'mmt_search_col_lse')
     return lse
 
+  def _row_expsum(self, q, qw, beta, xmax, bits, scan):
+    """The sum pass of `query_lse` behind its checks: q (NQ, M, d) / qw (NQ, M) and xmax float32 [NQ] on the index device,
+    the scan holding at most a subset of this index -> the integer sums int64 [NQ] over this index's candidates.  bits is
+    the caller's: on a shard it comes from the whole gallery's item count.  Per row batch one launch and one torch.sum
+    over the chunks of its workspace.  Nothing here waits for the device."""
+    nq, nv, L = q.shape[0], self.num_items, _lib.lib()
+    with torch.cuda.device(self.device):
+      sums = torch.empty(nq, device=self.device, dtype=torch.int64)
+      # A row's chunk sums at full-size chunks of 4096 items.  A launch of few blocks cuts the items into smaller chunks, down
+      # to 128 (tk_chunk), and a row's workspace is then up to 32 times this estimate, so _BATCH_BYTES is not strictly kept
+      # there.  It cannot matter: the chunk is halved only while the launch has fewer than 512 blocks, so a launch with
+      # smaller chunks has fewer than 1024 blocks of 64 slots: a workspace below half a megabyte whatever nq and nv are.
+      for r0, r1 in self._row_batches(nq, 8 * -(-nv // 4096)):
+        desc, _, _, _keep = self._describe(scan, q, qw, r0, r1)
+        ws = torch.empty(L.mmt_row_expsum_workspace_ints64(r1 - r0, nv), device=self.device, dtype=torch.int64)
+        check(L.mmt_search_row_expsum(desc, beta, ops._p(xmax[r0:r1]), bits, ops._p(ws), ops._stream()),
+              'mmt_search_row_expsum')
+        torch.sum(ws.view(r1 - r0, -1), 1, out=sums[r0:r1])
+    return sums
+
   def _reverse_search(self, q, qw, k):
     return self._col_topk(q, qw, k, False)[:2]
 
@@ -2338,6 +2507,18 @@ class ShardedVideoIndex(_Index):
         lse[ids] = mine.to(self.device)
       parts.append(part)
     return ShardedHubNorm(parts, lse, beta, b.shape[0], hubs)
+
+  def _row_expsum(self, q, qw, beta, xmax, bits, scan):
+    """The sum pass of `query_lse` behind its checks: q, qw and xmax (the merged top-1 times beta) on the primary, bits from
+    the global item count.  Every shard that holds candidates sums over its own items with its part of the subset; the
+    int64 partials are added on the primary -- integers, so the order of the shards does not matter."""
+    with torch.cuda.device(self.device):
+      sums = torch.zeros(q.shape[0], device=self.device, dtype=torch.int64)
+    for s, sh in self._live(scan.subset):
+      with torch.cuda.device(sh.device):
+        mine = sh.index._row_expsum(q.to(sh.device), qw.to(sh.device), beta, xmax.to(sh.device), bits, scan.shard(s, self))
+      sums += mine.to(self.device)
+    return sums
 
   def _per_item(self, run, outs):
     """Fills outs -- per-item tensors [num_items, ...] on the primary -- from the shards: run(sh), called under the device

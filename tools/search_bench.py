@@ -112,7 +112,12 @@ exclusion per query (the masked selection and prefilled outputs the join runs wi
 (dequantised rows @ chunk.T with the denominators and topk over chunks under the same _BATCH_BYTES budget) and
 `neighbour_range` at per-row thresholds that give 16 hits per row; one full self-join (items=None) per storage as a single
 run.  --runs rounds, every variant once per round, interleaved; median and spread.  Joins --out (default
-profiles/search_bench.json) under 'neighbours'."""
+profiles/search_bench.json) under 'neighbours'.
+
+--lse times the softmax over 262 144 items (beta = 20) at NQ = 64 and 4 096 on a float32, a bf16 and an fp8 index: the sum
+pass alone (mmt_search_row_expsum with xmax given) and `query_lse` whole, beside search(k = 1) and search(k = 10) on the same
+index, and on float32 the route through the matrix (the similarity kernel + torch.logsumexp) with its peak memory.  --runs
+rounds, every variant once per round, interleaved; median and spread.  Default output profiles/search_lse_bench.json."""
 import argparse
 import json
 import math
@@ -925,8 +930,86 @@ def neighbours_mode(a, dev):
   return row
 
 
+def materialised_lse(q, qw, g, gw, beta):
+  """The route through the matrix: the kernel behind metric.eval_similarity (which wants NQ = NV * C) on NQ x NV, scaled in
+  place, then torch.logsumexp along the rows."""
+  nq, nv = q.shape[0], g.shape[0]
+  L = _lib.lib()
+  ws = torch.empty(L.mmt_sims_eval_workspace_floats(nq, nv, M, D), device=q.device)
+  sims = torch.empty(nq, nv, device=q.device)
+  _lib.check(L.mmt_sims_eval(ops._p(q), ops._p(g), ops._p(qw), ops._p(gw), nq, nv, M, D, ops._p(ws), ops._p(sims),
+                             ops._stream()), 'mmt_sims_eval')
+  del ws
+  return torch.logsumexp(sims.mul_(beta), 1)
+
+
+def lse_mode(a, dev):
+  """The softmax over NV = 262 144 items, beta = 20, at NQ = 64 and 4 096, per storage dtype: the sum pass alone
+  (mmt_search_row_expsum with xmax given), `query_lse` whole (top-1 scan + sum pass + the float64 closing step), beside
+  search(k = 1) and search(k = 10) on the same index in the same session; on float32 also the materialised route,
+  metric.eval_similarity + torch.logsumexp over the NQ x NV matrix, with its peak memory."""
+  from mmt_amd.search import _Scan, lse_bits
+  nv, chunk, beta = SHAPES['S3'][1], 8192, 20.0
+  gen = torch.Generator(device=dev).manual_seed(0)
+  nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
+  dtypes = {'float32': torch.float32, 'bfloat16': torch.bfloat16, 'float8_e4m3fn': torch.float8_e4m3fn}
+  idx = {n: VideoIndex.empty(nv, M, D, dev, dtype=t) for n, t in dtypes.items()}
+  g_all, gw_all = [], []
+  for at in range(0, nv, chunk):
+    g = nrm(torch.randn(chunk, M, D, device=dev, generator=gen))
+    gw = torch.softmax(torch.randn(chunk, M, device=dev, generator=gen), -1)
+    for index in idx.values():
+      index.add(g, gw)
+    g_all.append(g)
+    gw_all.append(gw)
+  g_all, gw_all = torch.cat(g_all), torch.cat(gw_all)
+  bits = lse_bits(nv)
+  row = {'NV': nv, 'beta': beta, 'bits': bits}
+  for nq in (64, 4096):
+    q = nrm(torch.randn(nq, M, D, device=dev, generator=gen) + 0.3 * g[torch.arange(nq, device=dev) % chunk])
+    qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
+    fns, peaks = {}, {}
+    for n, index in idx.items():
+      xmax = index.search(q, qw, k=1)[0][:, 0] * beta
+      fns[n + '/sum_pass'] = lambda index=index, xmax=xmax: index._row_expsum(q, qw, beta, xmax, bits, _Scan())
+      fns[n + '/query_lse'] = lambda index=index: index.query_lse(q, qw, beta).lse
+      fns[n + '/search_k1'] = lambda index=index: index.search(q, qw, k=1)
+      fns[n + '/search_k10'] = lambda index=index: index.search(q, qw, k=K)
+    if not a.skip_materialised:
+      fns['float32/materialised_logsumexp'] = lambda: materialised_lse(q, qw, g_all, gw_all, beta)
+    ts = {n: [] for n in fns}
+    for r in range(a.runs):
+      for n, fn in fns.items():
+        t, _, peak, _ = timed(fn, a.min_seconds)
+        ts[n].append(t)
+        peaks[n] = max(peaks.get(n, 0), peak)
+      print('NQ %d: round %d of %d' % (nq, r + 1, a.runs), file=sys.stderr, flush=True)
+    res = {'NQ': nq, 'flop': 2.0 * nq * nv * M * D}
+    for n in fns:
+      res[n] = dict(seconds_median=float(np.median(ts[n])), seconds_spread=max(ts[n]) - min(ts[n]), seconds_runs=ts[n],
+                    peak_bytes=int(peaks[n]))
+    for n, index in idx.items():
+      s, whole, k1, k10 = (res[n + '/' + v]['seconds_median'] for v in ('sum_pass', 'query_lse', 'search_k1', 'search_k10'))
+      summary = dict(sum_pass_over_search_k1=s / k1, sum_pass_over_search_k10=s / k10, query_lse_over_search_k1=whole / k1,
+                     spread_seconds_of_the_three=max(res[n + '/' + v]['seconds_spread'] for v in ('sum_pass', 'search_k1', 'search_k10')),
+                     sum_pass_tflops=res['flop'] / s / 1e12)
+      if n == 'float32' and not a.skip_materialised:
+        mat = res['float32/materialised_logsumexp']
+        lse, ref = index.query_lse(q, qw, beta).lse, fns['float32/materialised_logsumexp']()
+        summary.update(materialised_over_query_lse=mat['seconds_median'] / whole, materialised_peak_bytes=mat['peak_bytes'],
+                       query_lse_peak_bytes=res[n + '/query_lse']['peak_bytes'],
+                       max_abs_difference_to_materialised=float((lse - ref).abs().max()))
+        del ref
+      res[n + '/summary'] = summary
+    row['NQ%d' % nq] = res
+  return row
+
+
 def main():
   ap = argparse.ArgumentParser()
+  ap.add_argument('--lse', action='store_true', help='time the softmax over 262 144 items (beta = 20) at NQ = 64 and 4 096 on '
+                  'a float32, a bf16 and an fp8 index: the sum pass alone and query_lse whole against search(k = 1) and '
+                  'search(k = 10), and on float32 eval_similarity + torch.logsumexp with its peak memory (no other mode flag)')
   ap.add_argument('--neighbours', action='store_true', help='time the gallery self-join (R = 4 096 rows, k = 10) on a float32, '
                   'a bf16 and an fp8 index of 262 144 items against search(k = 10) of 4 096 queries and the torch route, '
                   'neighbour_range at 16 hits per row, and one full self-join (no other mode flag)')
@@ -1003,6 +1086,9 @@ def main():
                      '--groups, --pooled')
   if a.item_pooled and a.out is None:
     a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'search_itemset_bench.json')
+  if a.lse and (masked or a.ranks or a.shards or a.norm is not None or a.reverse or a.range or a.groups or a.pooled or
+                a.item_pooled or a.neighbours or a.diverse or a.after or a.rescore or a.fp8):
+    raise SystemExit('--lse wants no other mode')
   if a.counts_only and not a.range:
     raise SystemExit('--counts-only goes with --range')
   if a.range and a.out is None and not a.counts_only:
@@ -1016,6 +1102,17 @@ def main():
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
+  if a.lse:
+    res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'lse', 'runs': a.runs,
+           'min_seconds': a.min_seconds}
+    res.update(lse_mode(a, dev))
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                'search_lse_bench.json')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+      json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return
   if a.neighbours:
     res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'neighbours', 'runs': a.runs,
            'min_seconds': a.min_seconds}
