@@ -6,17 +6,18 @@
 // item g in the query's place.  Two launches, two additive entries; MmtSearchScan and the ten scans are untouched.
 //   pair_scores_kernel<ST>: one block per list of C <= 128 candidates computes its C x C Gram: the two 64 x 128 tiles of
 //                           tk_tile's shape at once, as a 2 x 2 grid of waves with 2 x 2 accumulators of 32 x 32 each, BOTH
-//                           operands read from ONE gathered slab in LDS (128 rows x 32 fp32 or x 64 bf16: 18 KiB), staged
-//                           through registers as the scans' K loops are (search_scan.h, which this file only reads).  fp32
-//                           rows go to v_mfma_f32_32x32x2_f32; bf16 rows, and fp8 codes widened exactly on their way into
-//                           LDS (tk_widen_fp8), to v_mfma_f32_32x32x16_bf16 -- the operands are exact bf16 values, so one
-//                           MFMA per fragment, no hi / lo pair.  A fragment wholly past C is neither loaded nor multiplied.
+//                           operands read from ONE gathered slab in LDS (128 rows x 32 fp32 or x 64 bf16: 18 KiB): the
+//                           128-row TkStager of search_scan.h inside tk_k_loop, both fragments of tk_step read from it -- the
+//                           pieces the scans' K loop and the self-join's are made of.  fp32 rows go to
+//                           v_mfma_f32_32x32x2_f32; bf16 rows, and fp8 codes widened exactly in the stager, to
+//                           v_mfma_f32_32x32x16_bf16 -- the operands are exact bf16 values, so one MFMA per fragment, no
+//                           hi / lo pair.  A fragment wholly past C is neither loaded nor multiplied.
 //                           Every product a[k] * b[k] is exact or rounded the same way round, and every output sums its
 //                           products in the one order the slab and MFMA sequence fix, so sim(g, h) has the bits of sim(h, g)
 //                           and depends on the two rows alone: not on their places in the list, the other candidates, the
-//                           row batching, NV or the shard.  Epilogue: den = fma(gw_g[m], gw_h[m], den) for m ascending (an
-//                           explicit fma, symmetric in its factors); fp8: num = fl(acc * fl(scale_g * scale_h)), the product
-//                           of two powers of two, one rounded multiply (tk_mul_rn); sim = num / den.  A candidate outside
+//                           row batching, NV or the shard.  Epilogue: tk_pair_sims (search_scan.h), the one definition of
+//                           sim: den = fma(gw_g[m], gw_h[m], den) for m ascending, fp8: num = fl(acc * fl(scale_g *
+//                           scale_h)), sim = num / den.  A candidate outside
 //                           0 .. NV - 1 is "none": checked on the device, never dereferenced, NaN in its row and column.
 //   mmr_kernel            : one wave per list.  items / rel are the list in the search's order (what mmt_search_rescore
 //                           with k = C returns, padded with (-1, -inf)), sims its Gram.  n = the number of items >= 0, taken
@@ -45,110 +46,21 @@ struct DvArgs {
   int NV, M, K, C;
 };
 
-// acc[s][t] += slab rows (wr*64 + s*32 ..) . slab rows (wc*64 + t*32 ..)^T over the whole K, fp32 rows.
-__device__ __forceinline__ void dv_gram_f32(f32x16 (&acc)[2][2], unsigned char* smem, const DvArgs& a, const int* sRow,
-                                            const bool (&lr)[2], const bool (&lc)[2], int tid, int wr, int wc, int l31,
-                                            int h) {
-  float* sB = (float*)smem;  // [DV_MAXC][TK_LD]
-  const float* g = (const float*)a.g;
-  const int K = a.K;
-  int gr[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) gr[j] = sRow[(tid + 256 * j) >> 3];
-  f32x4 rb[4];
-  auto load = [&](int kb) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = kb + ((tid + 256 * j) & 7) * 4;
-      rb[j] = (gr[j] >= 0 && c < K) ? *(const f32x4*)(g + (int64_t)gr[j] * K + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  };
-  load(0);
-  for (int kb = 0; kb < K; kb += TK_BK) {
-    __syncthreads();  // previous slab consumed
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const int i = tid + 256 * j; *(f32x4*)(sB + (i >> 3) * TK_LD + (i & 7) * 4) = rb[j]; }
-    __syncthreads();
-    if (kb + TK_BK < K) load(kb + TK_BK);
-    // 8 contraction values per step; lane half h feeds k = kk + 4h + u to MFMA u (as tk_scan_f32)
-#pragma unroll
-    for (int kk = 0; kk < TK_BK; kk += 8) {
-      f32x4 av[2], bv[2];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) av[s] = *(const f32x4*)(sB + (wr * 64 + s * 32 + l31) * TK_LD + kk + 4 * h);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) bv[t] = *(const f32x4*)(sB + (wc * 64 + t * 32 + l31) * TK_LD + kk + 4 * h);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-          if (lr[s] && lc[t]) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[s][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][u], bv[t][u], acc[s][t], 0, 0, 0);
-          }
-    }
-  }
-}
-
-// The same over rows stored in 16 bits or fewer: bf16 as they are, fp8 widened exactly to bf16 on the way into LDS.
-template <bool FP8>
-__device__ __forceinline__ void dv_gram_b16(f32x16 (&acc)[2][2], unsigned char* smem, const DvArgs& a, const int* sRow,
-                                            const bool (&lr)[2], const bool (&lc)[2], int tid, int wr, int wc, int l31,
-                                            int h) {
-  constexpr int NB = FP8 ? 2 : 4;    // loads per thread and slab
-  constexpr int SH = FP8 ? 2 : 3;    // log2 of the loads per row and slab
-  constexpr int EL = FP8 ? 16 : 8;   // elements per load
-  bf16_t* sB = (bf16_t*)smem;  // [DV_MAXC][TKB_LD]
-  const u32x4 zero = {0u, 0u, 0u, 0u};
-  const int K = a.K;
-  int gr[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) gr[j] = sRow[(tid + 256 * j) >> SH];
-  u32x4 rb[NB];
-  auto load = [&](int kb) {
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int c = kb + ((tid + 256 * j) & ((1 << SH) - 1)) * EL;
-      const int64_t off = (int64_t)gr[j] * K + c;
-      if constexpr (FP8)
-        rb[j] = (gr[j] >= 0 && c < K) ? *(const u32x4*)((const uint8_t*)a.g + off) : zero;
-      else
-        rb[j] = (gr[j] >= 0 && c < K) ? *(const u32x4*)((const bf16_t*)a.g + off) : zero;
-    }
-  };
-  load(0);
-  for (int kb = 0; kb < K; kb += TKB_BK) {
-    __syncthreads();  // previous slab consumed
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int i = tid + 256 * j;
-      bf16_t* dst = sB + (i >> SH) * TKB_LD + (i & ((1 << SH) - 1)) * EL;
-      if constexpr (FP8) {
-        u32x4 lo, hi;
-        tk_widen_fp8(rb[j], lo, hi);
-        *(u32x4*)dst = lo;
-        *(u32x4*)(dst + 8) = hi;
-      } else {
-        *(u32x4*)dst = rb[j];
-      }
-    }
-    __syncthreads();
-    if (kb + TKB_BK < K) load(kb + TKB_BK);
-    // 16 contraction values per MFMA; lane half h holds k = kk + 8h .. + 7 of its row (as tk_scan_b16)
-#pragma unroll
-    for (int kk = 0; kk < TKB_BK; kk += 16) {
-      bf16x8_t av[2], bv[2];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) av[s] = *(const bf16x8_t*)(sB + (wr * 64 + s * 32 + l31) * TKB_LD + kk + 8 * h);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) bv[t] = *(const bf16x8_t*)(sB + (wc * 64 + t * 32 + l31) * TKB_LD + kk + 8 * h);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-          if (lr[s] && lc[t]) acc[s][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[s], bv[t], acc[s][t], 0, 0, 0);
-    }
-  }
+// acc[s * 2 + t] += slab rows (wr*64 + s*32 ..) . slab rows (wc*64 + t*32 ..)^T over the whole K: the 128-row stager of
+// search_scan.h (T = float, bf16_t, or uint8_t for fp8 codes, widened on the way in) with BOTH fragments read from its one
+// slab, inside tk_k_loop.  lr[s] && lc[t]: the fragment pair holds a position below C.
+template <class T>
+__device__ __forceinline__ void dv_gram(f32x16 (&acc)[4], unsigned char* smem, const T* g, int K, const int* sRow,
+                                        const bool (&lr)[2], const bool (&lc)[2], int tid, int wr, int wc, int l31, int h) {
+  using St = TkStager<T, DV_MAXC>;
+  typename St::S* sB = (typename St::S*)smem;  // [DV_MAXC][LD]
+  St B;
+  B.rows([=](int r) { return sRow[r]; }, tid);
+  tk_k_loop<St::BK, St::KK>(
+      K, [&](int kb) { B.load({g}, K, kb, tid); }, [&] { B.store(sB, tid); },
+      [&](int kk) {
+        tk_step<1, 2, 2>(acc, sB, wr * 64 + l31, sB, wc * 64 + l31, kk, h, [&](int s, int t) { return lr[s] && lc[t]; });
+      });
 }
 
 template <int ST>
@@ -174,17 +86,13 @@ __global__ __launch_bounds__(256) void pair_scores_kernel(DvArgs a) {
   }
   // which of the wave's 32-row / 32-column fragments hold a position below C: wave-uniform
   const bool lr[2] = {wr * 64 < C, wr * 64 + 32 < C}, lc[2] = {wc * 64 < C, wc * 64 + 32 < C};
-  f32x16 acc[2][2];
+  using T = std::conditional_t<ST == MMT_SEARCH_FP32, float, std::conditional_t<ST == MMT_SEARCH_FP8, uint8_t, bf16_t>>;
+  f32x16 acc[4];  // [s][t]
 #pragma unroll
-  for (int s = 0; s < 2; ++s)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[s][t][r] = 0.f;
-  if constexpr (ST == MMT_SEARCH_FP32)
-    dv_gram_f32(acc, smem, a, sRow, lr, lc, tid, wr, wc, l31, h);
-  else
-    dv_gram_b16<ST == MMT_SEARCH_FP8>(acc, smem, a, sRow, lr, lc, tid, wr, wc, l31, h);
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+  dv_gram(acc, smem, (const T*)a.g, a.K, sRow, lr, lc, tid, wr, wc, l31, h);
   // the K loop's barriers fence sW.  Lane: column wc*64 + t*32 + l31, rows wr*64 + s*32 + (r&3) + 8*(r>>2) + 4h.
   float* out = a.sims + list * C * C;
 #pragma unroll
@@ -198,12 +106,13 @@ __global__ __launch_bounds__(256) void pair_scores_kernel(DvArgs a) {
       for (int r = 0; r < 16; ++r) {
         const int row = wr * 64 + s * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
         if (row >= C) continue;
-        float den = 0.f;
-        for (int m = 0; m < M; ++m) den = __builtin_fmaf(sW[row * MMT_MAX_EXPERTS + m], sW[col * MMT_MAX_EXPERTS + m], den);
-        float num = acc[s][t][r];
-        if constexpr (ST == MMT_SEARCH_FP8) num = tk_mul_rn(num, tk_mul_rn(sSc[row], sSc[col]));
-        const float sim = num / (den == 0.f ? 1e-5f : den);
-        out[row * C + col] = (col_live && sRow[row] >= 0) ? sim : __builtin_nanf("");
+        const float one[1] = {acc[s * 2 + t][r]};
+        float sim[1];
+        tk_pair_sims<ST == MMT_SEARCH_FP8>(
+            sim, one, M, [&](int, int m) { return sW[row * MMT_MAX_EXPERTS + m]; },
+            [&](int m) { return sW[col * MMT_MAX_EXPERTS + m]; }, [&](int) { return sSc[row]; },
+            ST == MMT_SEARCH_FP8 ? sSc[col] : 1.f);
+        out[row * C + col] = (col_live && sRow[row] >= 0) ? sim[0] : __builtin_nanf("");
       }
   }
 }

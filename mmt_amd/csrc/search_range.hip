@@ -68,7 +68,6 @@ template <bool BF16, bool FILL, bool MASKED, class Args = std::conditional_t<MAS
 __global__ __launch_bounds__(256) void range_kernel(Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int kUnion = BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES;
-  constexpr int kRows = TK_Q / 4;  // rows per wave
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5, wq = wave >> 1, wg = wave & 1;
   float* sS = (float*)smem;              // [TK_Q][TK_SLD]  scores (after the K loop)
@@ -77,24 +76,9 @@ __global__ __launch_bounds__(256) void range_kernel(Args a) {
   const int chunk = bid / a.n_qt, q0 = (bid % a.n_qt) * TK_Q;
   const int g_begin = chunk * a.chunk, g_end = min(a.NV, g_begin + a.chunk);
   const int rows_live = min(a.NQ - q0, TK_Q);
-  // lane l < 16 of wave w holds the state of row 16 w + l for the whole block: its threshold, its hits so far and, for
-  // the fill, where its slots of this chunk begin and how many they are
-  const int my_row = wave * kRows + lane;
-  const bool holder = lane < kRows && my_row < rows_live;
-  const float my_thr = holder ? a.thr[q0 + my_row] : __builtin_nanf("");
-  int my_cnt = 0, my_cap = 0;
-  int64_t my_base = 0;
-  if constexpr (FILL) {
-    if (holder) {
-      const int64_t q = q0 + my_row, off = a.offsets[q];
-      const int32_t* pre = a.ws + q * a.n_chunks + chunk;
-      my_base = off + pre[0];
-      const int64_t next = chunk + 1 < a.n_chunks ? off + pre[1] : a.offsets[q + 1];
-      const int64_t room = next - my_base;  // never beyond the row's next chunk, nor more than the chunk has items
-      my_cap = room < 0 ? 0 : room > g_end - g_begin ? g_end - g_begin : (int)room;
-    }
-    if (!__syncthreads_or(my_cap > 0)) return;  // block-uniform: no row of this block has a hit in this chunk
-  }
+  TkRange<FILL, false> rg;  // the rows' thresholds, hits so far and, for the fill, slots of this chunk
+  if (!rg.init(a.thr, nullptr, a.ws, a.offsets, q0, rows_live, chunk, a.n_chunks, g_end - g_begin, wave, lane))
+    return;  // block-uniform: no row of this block has a hit in this chunk
   tk_load_qw(sQw, a.qw, a.NQ, a.M, q0, tid);  // read after the barriers of the first K loop
   for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
     uint64_t m0 = ~0ull, m1 = ~0ull;
@@ -103,37 +87,9 @@ __global__ __launch_bounds__(256) void range_kernel(Args a) {
     tk_tile<BF16, false>(a, smem, sS, sQw, q0, [=](int r) { return g0 + r < g_end ? g0 + r : -1; }, tid, wq, wg, l31, h);
     const bool live0 = g0 + lane < g_end && (!MASKED || ((m0 >> lane) & 1ull));
     const bool live1 = g0 + 64 + lane < g_end && (!MASKED || ((m1 >> lane) & 1ull));
-    for (int rr = 0; rr < kRows; ++rr) {
-      const int row = wave * kRows + rr;
-      if (row >= rows_live) break;
-      const float s0 = sS[row * TK_SLD + lane], s1 = sS[row * TK_SLD + 64 + lane];
-      const float thr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_thr), rr));
-      const bool hit0 = live0 && s0 >= thr, hit1 = live1 && s1 >= thr;
-      const uint64_t b0 = __ballot(hit0), b1 = __ballot(hit1);
-      const int n0 = __popcll(b0), n1 = __popcll(b1);
-      if constexpr (FILL) {
-        if (b0 | b1) {  // wave-uniform
-          const int seen = __builtin_amdgcn_readlane(my_cnt, rr), cap = __builtin_amdgcn_readlane(my_cap, rr);
-          const int64_t base = (int64_t)(((uint64_t)(unsigned)__builtin_amdgcn_readlane((int)(my_base >> 32), rr) << 32) |
-                                         (unsigned)__builtin_amdgcn_readlane((int)my_base, rr));
-          const uint64_t below = (1ull << lane) - 1;
-          const int p0 = seen + __popcll(b0 & below), p1 = seen + n0 + __popcll(b1 & below);
-          if (hit0 && p0 < cap) {
-            a.indices[base + p0] = g0 + lane;
-            a.scores[base + p0] = s0;
-          }
-          if (hit1 && p1 < cap) {
-            a.indices[base + p1] = g0 + 64 + lane;
-            a.scores[base + p1] = s1;
-          }
-        }
-      }
-      if (lane == rr) my_cnt += n0 + n1;
-    }
+    rg.tile(sS, g0, live0, live1, rows_live, a.indices, a.scores, wave, lane);
   }
-  if constexpr (!FILL) {
-    if (holder) a.ws[(int64_t)(q0 + my_row) * a.n_chunks + chunk] = my_cnt;
-  }
+  if constexpr (!FILL) rg.flush(a.ws, a.n_chunks, chunk);
 }
 
 // One thread per query: the chunk counts become their exclusive prefix, in chunk order; the row total as int64.
@@ -149,6 +105,11 @@ __global__ __launch_bounds__(256) void range_offsets_kernel(int32_t* __restrict_
     run += n;
   }
   row_counts[q] = run;
+}
+
+int rg_offsets_launch(int32_t* ws, int R, int n_chunks, int64_t* row_counts, hipStream_t s) {
+  hipLaunchKernelGGL(range_offsets_kernel, dim3((R + 255) / 256), dim3(256), 0, s, ws, R, n_chunks, row_counts);
+  return (int)hipGetLastError();
 }
 
 namespace {
@@ -183,9 +144,7 @@ int rg_count(const MmtSearchScan& s, const float* thr, int32_t* ws, int64_t* row
   Args a = {};
   if (const int rc = rg_fill<BF16>(a, s, thr, ws, row_counts != nullptr)) return rc;
   rg_launch<BF16, false>(a, (hipStream_t)stream);
-  hipLaunchKernelGGL(range_offsets_kernel, dim3((s.NQ + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws, s.NQ, a.n_chunks,
-                     row_counts);
-  return (int)hipGetLastError();
+  return rg_offsets_launch(ws, s.NQ, a.n_chunks, row_counts, (hipStream_t)stream);
 }
 
 template <bool BF16, class Args>
@@ -200,8 +159,7 @@ int rg_fill_hits(const MmtSearchScan& s, const float* thr, const int32_t* ws, co
 }  // namespace
 
 extern "C" int64_t mmt_range_workspace_ints(int NQ, int NV) {
-  if (NQ <= 0 || NV <= 0) return MMT_ERR_ARG;
-  return (int64_t)NQ * tk_n_chunks(NQ, NV);
+  return tk_range_workspace_ints(NQ, NV);
 }
 
 // storage -> the body and its argument block.  The fp8 pair is named last: the kernels lie in the code object in the order

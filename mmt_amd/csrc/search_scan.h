@@ -1,16 +1,20 @@
 // The scoring tile of the gallery scans, shared by every kernel that scores a (query, item) pair: the top-k kernels
 // (search.hip: a running top-k per query), the count / threshold kernels (search_rank.hip: a counter per query and
 // target), the range kernels (search_range.hip: every hit) and the querybank column pass (search_norm.hip).  Block shape,
-// the two K loops (fp32 gallery on v_mfma_f32_32x32x2_f32, bf16 gallery on v_mfma_f32_32x32x16_bf16 -- an fp8 gallery is
+// the K loop (tk_scan: fp32 gallery on v_mfma_f32_32x32x2_f32, bf16 gallery on v_mfma_f32_32x32x16_bf16 -- an fp8 gallery is
 // widened to bf16 on its way into LDS and runs the bf16 loop), the gated-denominator epilogue (with an fp8 gallery: the
 // item's scale first) and the querybank rewrite are composed in ONE place, tk_tile, so a pair has the same score bits on
-// every path by construction.  The subset gate of a tile (tk_tile_mask), the chunk rule and launch geometry (tk_chunk, tk_geometry),
-// the shape gate and the per-device dynamic-LDS limit (tk_lds_limits) are here once as well, and so are the steps that
-// follow a tile on more than one path: the count step (tk_tile_count), the query-set pooling (tk_tile_pool) and the item-set
-// pooling (tk_tile_pool_items, with the unaligned subset window tk_tile_mask_window).
+// every path by construction.  The K loop is itself a composition -- slab stager, loop with its barriers, MFMA step -- and
+// the kernels that score two STORED rows (search_self.hip, search_diverse.hip) are made of the same three pieces and of ONE
+// definition of that similarity, tk_pair_sims.  The subset gate of a tile (tk_tile_mask), the chunk rule and launch
+// geometry (tk_chunk, tk_geometry), the shape gate and the per-device dynamic-LDS limit (tk_lds_limits) are here once as
+// well, and so are the steps that follow a tile on more than one path: the count step (tk_tile_count), the range step
+// (TkRange), the query-set pooling (tk_tile_pool) and the item-set pooling (tk_tile_pool_items, with the unaligned subset
+// window tk_tile_mask_window).
 //
-// Which gallery row a tile row / column holds is a functor `grow(r)`, r in 0 .. TK_G - 1 -> gallery row, or -1 for "none"
-// (zero-filled in registers, never read): g0 + r for a scan, a table lookup for the rank kernels' threshold pass.
+// Which row a slab row / tile column holds is a functor `row(r)` on both sides -> row number, or -1 for "none" (zero-filled
+// in registers, never read): g0 + r for a scan's gallery side, a table lookup for the rank kernels' threshold pass and the
+// stored-row kernels, q0 + r below NQ for a query.
 #pragma once
 #include <cmath>
 #include <initializer_list>
@@ -47,59 +51,6 @@ __device__ __forceinline__ void tk_load_qw(float* sQw, const float* qw, int NQ, 
   }
 }
 
-// fp32 K loop of one 64 x 128 tile: acc = Q'[q0 .. q0 + 63] . G'[grow(.)]^T.  The K dimension streams through LDS
-// (smem: TK_SLAB_BYTES) in 32-wide slabs, register-staged: the next slab's global loads are in flight during the
-// current slab's MFMAs.  Opens with a barrier (the previous tile's scores, which share smem, are consumed) and leaves
-// the last slab's reads unfenced: the caller syncs before it reuses smem.
-template <class GRow>
-__device__ __forceinline__ void tk_scan_f32(f32x16 (&acc)[2], unsigned char* smem, const float* q, const float* g, int NQ,
-                                            int K, int q0, GRow grow, int tid, int wq, int wg, int l31, int h) {
-  float* sA = (float*)smem;        // [TK_Q][TK_LD]   slab of Q'
-  float* sB = sA + TK_Q * TK_LD;   // [TK_G][TK_LD]   slab of G'
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  // staging: Q' slab = 64 rows x 8 f32x4 (2 per thread), G' slab = 128 rows x 8 f32x4 (4 per thread)
-  int gr[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) gr[j] = grow((tid + 256 * j) >> 3);
-  f32x4 ra[2], rb[4];
-  auto load = [&](int kb) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 4;
-      ra[j] = (q0 + r < NQ && c < K) ? *(const f32x4*)(q + (int64_t)(q0 + r) * K + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = kb + ((tid + 256 * j) & 7) * 4;
-      rb[j] = (gr[j] >= 0 && c < K) ? *(const f32x4*)(g + (int64_t)gr[j] * K + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  };
-  load(0);
-  for (int kb = 0; kb < K; kb += TK_BK) {
-    __syncthreads();  // previous slab (or the previous tile's scores) consumed
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { const int i = tid + 256 * j; *(f32x4*)(sA + (i >> 3) * TK_LD + (i & 7) * 4) = ra[j]; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const int i = tid + 256 * j; *(f32x4*)(sB + (i >> 3) * TK_LD + (i & 7) * 4) = rb[j]; }
-    __syncthreads();
-    if (kb + TK_BK < K) load(kb + TK_BK);
-    // 8 contraction values per step = 4 MFMAs per accumulator; lane half h feeds k = kk + 4h + u to MFMA u
-#pragma unroll
-    for (int kk = 0; kk < TK_BK; kk += 8) {
-      const f32x4 av = *(const f32x4*)(sA + (wq * 32 + l31) * TK_LD + kk + 4 * h);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const f32x4 bv = *(const f32x4*)(sB + (wg * 64 + t * 32 + l31) * TK_LD + kk + 4 * h);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc[t], 0, 0, 0);
-      }
-    }
-  }
-}
-
 // 16 fp8 values (OCP e4m3fn, one 16-byte load) -> 16 bf16 as two 16-byte halves, exactly: every e4m3fn value is a bf16
 // value (3 mantissa bits against 7, and the range fits), so the upper half of v_cvt_pk_f32_fp8's fp32 IS the bf16.
 __device__ __forceinline__ void tk_widen_fp8(const u32x4& v, u32x4& lo, u32x4& hi) {
@@ -115,106 +66,163 @@ __device__ __forceinline__ void tk_widen_fp8(const u32x4& v, u32x4& lo, u32x4& h
   hi = u32x4{o[4], o[5], o[6], o[7]};
 }
 
-// K loop of one tile over a gallery stored in 16 bits or fewer (smem: TKB_SLAB_BYTES): per 64-wide slab the block stages
-// hi(Q'), lo(Q') (64 rows each) and the gallery (128 rows) as bf16; a wave reads each gallery fragment ONCE and feeds it to
-// the hi and the lo MFMA.  Barriers as tk_scan_f32.  The gallery slab is 128 rows x 64 elements:
-//   bf16 (FP8 = false): 128 bytes of a row = 8 sixteen-byte loads, 4 per thread, stored to LDS as they are (K % 8 == 0);
-//   fp8  (FP8 = true) :  64 bytes of a row = 4 sixteen-byte loads, 2 per thread, each widened in registers to 16 bf16
-//                        (tk_widen_fp8) and stored as two 16-byte halves to the same place of the same slab (K % 16 == 0).
-// Either way a 16-byte load is inside the row or past its end as a whole, and LDS layout, pitch and MFMA loop are one.
-template <bool FP8, class GRow>
-__device__ __forceinline__ void tk_scan_b16(f32x16 (&acc)[2], unsigned char* smem, const bf16_t* q_hi, const bf16_t* q_lo,
-                                            const void* g, int NQ, int K, int q0, GRow grow, int tid, int wq, int wg, int l31,
-                                            int h) {
-  constexpr int NB = FP8 ? 2 : 4;    // gallery loads per thread and slab
-  constexpr int SH = FP8 ? 2 : 3;    // log2 of the loads per gallery row and slab
-  constexpr int EL = FP8 ? 16 : 8;   // elements per load
-  bf16_t* sAh = (bf16_t*)smem;          // [TK_Q][TKB_LD]  slab of hi(Q')
-  bf16_t* sAl = sAh + TK_Q * TKB_LD;    // [TK_Q][TKB_LD]  slab of lo(Q')
-  bf16_t* sB = sAl + TK_Q * TKB_LD;     // [TK_G][TKB_LD]  slab of the stored gallery, as bf16
-  const u32x4 zero = {0u, 0u, 0u, 0u};
+// The K loops.  Every contraction over the folded row -- a query against stored rows (tk_scan in tk_tile), stored rows
+// against stored rows (tk_scan in search_self.hip, the Gram of search_diverse.hip) -- is a composition of three pieces, so
+// the slab sequence (kb ascending) and the MFMA sequence inside a slab (kk ascending; then u ascending for fp32, hi before
+// lo for a query's two bf16 planes; ONE accumulator per output) are the same everywhere by construction.
+//
+// 1. The slab stager: ROWS (64 or 128) rows of one slab, staged through registers it owns, 16 bytes per load.  T is what a
+// row is stored as: float (32-wide slabs, pitch TK_LD), bf16_t = bf16 bits, or uint8_t = e4m3fn codes (64-wide slabs of
+// bf16, pitch TKB_LD; the codes are widened on their way into LDS, here and nowhere else).  K % EL == 0, so a load is
+// inside its row or past its end as a whole.  P planes of the same rows (a query's hi and lo) share one stager, so the
+// load predicate and the row offset are formed once for both.
+template <class T, int ROWS, int P = 1>
+struct TkStager {
+  static constexpr bool F32 = std::is_same_v<T, float>, FP8 = std::is_same_v<T, uint8_t>;
+  using S = std::conditional_t<F32, float, bf16_t>;   // what the slab holds in LDS
+  using V = std::conditional_t<F32, f32x4, u32x4>;    // one load
+  static constexpr int BK = F32 ? TK_BK : TKB_BK;     // contraction values per slab
+  static constexpr int LD = F32 ? TK_LD : TKB_LD;     // slab row pitch, in S
+  static constexpr int KK = F32 ? 8 : 16;             // contraction values per fragment step: lane half h holds kk + KK/2 * h ..
+  static constexpr int EL = 16 / sizeof(T);           // elements per load
+  static constexpr int SH = FP8 ? 2 : 3;              // log2 of the loads per row and slab
+  static constexpr int N = (ROWS << SH) / 256;        // loads per thread and slab
+  int at[N];
+  V reg[P][N];  // P planes of the same rows (a query's hi and lo), one behind the other in LDS
+
+  template <class Row>
+  __device__ __forceinline__ void rows(Row row, int tid) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) at[j] = row((tid + 256 * j) >> SH);
+  }
+  // slab kb of the planes base[p] [.][K] -> registers
+  __device__ __forceinline__ void load(const T* const (&base)[P], int K, int kb, int tid) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const int c = kb + ((tid + 256 * j) & ((1 << SH) - 1)) * EL;
+      const bool in = at[j] >= 0 && c < K;
+      const int64_t off = (int64_t)at[j] * K + c;
+#pragma unroll
+      for (int p = 0; p < P; ++p) reg[p][j] = in ? *(const V*)(base[p] + off) : V{};
+    }
+  }
+  // registers -> slabs [P][ROWS][LD]
+  __device__ __forceinline__ void store(S* slab, int tid) const {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const int i = tid + 256 * j, o = (i >> SH) * LD + (i & ((1 << SH) - 1)) * EL;
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        S* dst = slab + p * ROWS * LD + o;
+        if constexpr (FP8) {
+          u32x4 lo, hi;
+          tk_widen_fp8(reg[p][j], lo, hi);
+          *(u32x4*)dst = lo;
+          *(u32x4*)(dst + 8) = hi;
+        } else {
+          *(V*)dst = reg[p][j];
+        }
+      }
+    }
+  }
+};
+
+// 2. The loop and its barrier discipline, stated once: K streams through LDS slab by slab, the next slab's global loads
+// (`load(kb)`) in flight during the current slab's MFMAs (`step(kk)`, KK contraction values each).  It OPENS with a barrier
+// (what shared the slabs' LDS before, the previous tile's scores for one, is consumed) and leaves the last slab's reads
+// UNFENCED: the caller syncs before it reuses that LDS.
+template <int BK, int KK, class Load, class Store, class Step>
+__device__ __forceinline__ void tk_k_loop(int K, Load load, Store store, Step step) {
+  load(0);
+  for (int kb = 0; kb < K; kb += BK) {
+    __syncthreads();
+    store();
+    __syncthreads();
+    if (kb + BK < K) load(kb + BK);
+#pragma unroll
+    for (int kk = 0; kk < BK; kk += KK) step(kk);
+  }
+}
+
+// 3. The fragment step of a wave: S x T accumulators of 32 x 32 (acc[s * T + t]) take KK contraction values of slab rows
+// ar + 32 s (A) and br + 32 t (B), the lane's own row l31 included in ar / br.  `live(s, t)` is wave-uniform and stays
+// outside the arithmetic: a dead output is not multiplied.  fp32 rows: lane half h feeds k = kk + 4h + u to MFMA u.
+template <int P, int S, int T, class Live>
+__device__ __forceinline__ void tk_step(f32x16* acc, const float* a, int ar, const float* b, int br, int kk, int h, Live live) {
+  static_assert(P == 1, "fp32 rows are one plane");
+  f32x4 av[S], bv[T];
+#pragma unroll
+  for (int s = 0; s < S; ++s) av[s] = *(const f32x4*)(a + (ar + s * 32) * TK_LD + kk + 4 * h);
+#pragma unroll
+  for (int t = 0; t < T; ++t) bv[t] = *(const f32x4*)(b + (br + t * 32) * TK_LD + kk + 4 * h);
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+      if (live(s, t)) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          acc[s * T + t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][u], bv[t][u], acc[s * T + t], 0, 0, 0);
+      }
+}
+
+// bf16 slabs: lane half h holds k = kk + 8h .. + 7 of its row, one v_mfma_f32_32x32x16_bf16 per A plane.  The A side is P
+// planes [TK_Q][TKB_LD] one behind the other: a query's hi then lo (a B fragment is read once and feeds both), a stored
+// row's single plane of exact bf16 values.
+template <int P, int S, int T, class Live>
+__device__ __forceinline__ void tk_step(f32x16* acc, const bf16_t* a, int ar, const bf16_t* b, int br, int kk, int h, Live live) {
+  bf16x8_t av[P][S], bv[T];
+#pragma unroll
+  for (int p = 0; p < P; ++p)
+#pragma unroll
+    for (int s = 0; s < S; ++s) av[p][s] = *(const bf16x8_t*)(a + p * TK_Q * TKB_LD + (ar + s * 32) * TKB_LD + kk + 8 * h);
+#pragma unroll
+  for (int t = 0; t < T; ++t) bv[t] = *(const bf16x8_t*)(b + (br + t * 32) * TKB_LD + kk + 8 * h);
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+      if (live(s, t)) {
+#pragma unroll
+        for (int p = 0; p < P; ++p)
+          acc[s * T + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[p][s], bv[t], acc[s * T + t], 0, 0, 0);
+      }
+}
+
+// K loop of one 64 x 128 tile: acc = A[arow(.)] . G[grow(.)]^T, the block's 4 waves as 2 x 2 of 32 rows x 64 columns.
+// A is P planes of TA (a[p] [.][K]), G one of TB; smem holds the slabs [P][TK_Q][LD] then [TK_G][LD] (TK_SLAB_BYTES,
+// TKB_SLAB_BYTES with two planes).  Barriers: tk_k_loop's.
+template <int P, class TA, class TB, class ARow, class GRow>
+__device__ __forceinline__ void tk_scan(f32x16 (&acc)[2], unsigned char* smem, const TA* const (&a)[P], ARow arow, const TB* g,
+                                        GRow grow, int K, int tid, int wq, int wg, int l31, int h) {
+  using SA = TkStager<TA, TK_Q, P>;
+  using SB = TkStager<TB, TK_G>;
+  using S = typename SB::S;
+  static_assert(std::is_same_v<S, typename SA::S>, "both sides are staged into slabs of one kind");
+  constexpr int LD = SB::LD;
+  S* sA = (S*)smem;
+  S* sB = sA + P * TK_Q * LD;
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  // staging, 16 bytes per load: hi and lo slabs = 64 rows x 8 (2 per thread each), gallery slab = 128 rows x 8 (bf16) or
-  // x 4 (fp8)
-  int gr[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) gr[j] = grow((tid + 256 * j) >> SH);
-  u32x4 rh[2], rl[2], rb[NB];
-  auto load = [&](int kb) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int i = tid + 256 * j, r = i >> 3, c = kb + (i & 7) * 8;
-      const bool in = q0 + r < NQ && c < K;
-      const int64_t off = (int64_t)(q0 + r) * K + c;
-      rh[j] = in ? *(const u32x4*)(q_hi + off) : zero;
-      rl[j] = in ? *(const u32x4*)(q_lo + off) : zero;
-    }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int c = kb + ((tid + 256 * j) & ((1 << SH) - 1)) * EL;
-      const int64_t off = (int64_t)gr[j] * K + c;
-      if constexpr (FP8)
-        rb[j] = (gr[j] >= 0 && c < K) ? *(const u32x4*)((const uint8_t*)g + off) : zero;
-      else
-        rb[j] = (gr[j] >= 0 && c < K) ? *(const u32x4*)((const bf16_t*)g + off) : zero;
-    }
-  };
-  load(0);
-  for (int kb = 0; kb < K; kb += TKB_BK) {
-    __syncthreads();  // previous slab (or the previous tile's scores) consumed
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int i = tid + 256 * j, o = (i >> 3) * TKB_LD + (i & 7) * 8;
-      *(u32x4*)(sAh + o) = rh[j];
-      *(u32x4*)(sAl + o) = rl[j];
-    }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int i = tid + 256 * j;
-      bf16_t* dst = sB + (i >> SH) * TKB_LD + (i & ((1 << SH) - 1)) * EL;
-      if constexpr (FP8) {
-        u32x4 lo, hi;
-        tk_widen_fp8(rb[j], lo, hi);
-        *(u32x4*)dst = lo;
-        *(u32x4*)(dst + 8) = hi;
-      } else {
-        *(u32x4*)dst = rb[j];
-      }
-    }
-    __syncthreads();
-    if (kb + TKB_BK < K) load(kb + TKB_BK);
-    // 16 contraction values per MFMA; lane half h holds k = kk + 8h .. + 7 of its row (A) / column (B)
-#pragma unroll
-    for (int kk = 0; kk < TKB_BK; kk += 16) {
-      const int ao = (wq * 32 + l31) * TKB_LD + kk + 8 * h;
-      const bf16x8_t ah = *(const bf16x8_t*)(sAh + ao), al = *(const bf16x8_t*)(sAl + ao);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const bf16x8_t bv = *(const bf16x8_t*)(sB + (wg * 64 + t * 32 + l31) * TKB_LD + kk + 8 * h);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bv, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bv, acc[t], 0, 0, 0);
-      }
-    }
-  }
-}
-
-// bf16-gallery K loop of one tile: g [.][K] bf16 bits.
-template <class GRow>
-__device__ __forceinline__ void tk_scan_bf16(f32x16 (&acc)[2], unsigned char* smem, const bf16_t* q_hi, const bf16_t* q_lo,
-                                             const bf16_t* g, int NQ, int K, int q0, GRow grow, int tid, int wq, int wg,
-                                             int l31, int h) {
-  tk_scan_b16<false>(acc, smem, q_hi, q_lo, g, NQ, K, q0, grow, tid, wq, wg, l31, h);
-}
-
-// fp8-gallery K loop of one tile: g [.][K] e4m3fn codes, half the gallery bytes of tk_scan_bf16 and the same arithmetic.
-template <class GRow>
-__device__ __forceinline__ void tk_scan_fp8(f32x16 (&acc)[2], unsigned char* smem, const bf16_t* q_hi, const bf16_t* q_lo,
-                                            const uint8_t* g, int NQ, int K, int q0, GRow grow, int tid, int wq, int wg,
-                                            int l31, int h) {
-  tk_scan_b16<true>(acc, smem, q_hi, q_lo, g, NQ, K, q0, grow, tid, wq, wg, l31, h);
+  SA A;
+  SB B;
+  A.rows(arow, tid);
+  B.rows(grow, tid);
+  tk_k_loop<SB::BK, SB::KK>(
+      K,
+      [&](int kb) {
+        A.load(a, K, kb, tid);
+        B.load({g}, K, kb, tid);
+      },
+      [&] {
+        A.store(sA, tid);
+        B.store(sB, tid);
+      },
+      [&](int kk) {
+        tk_step<P, 1, 2>(acc, sA, wq * 32 + l31, sB, wg * 64 + l31, kk, h, [](int, int) { return true; });
+      });
 }
 
 // fl(a * b) as an instruction of its own: the optimiser cannot contract it with a following add or subtract into an fma
@@ -419,6 +427,110 @@ __device__ __forceinline__ void tk_count_flush(const int* sCnt, int32_t* cnt, in
   }
 }
 
+// The range step of one score tile (search_range.hip, search_self.hip), count and fill: lane l < 16 of wave w holds the
+// state of row 16 w + l for the whole block -- its threshold, with OWN the one item it never meets (left out by NUMBER, -1 =
+// none; without OWN that compare does not exist), its hits so far and, for the fill, where its slots of this chunk begin and
+// how many they are -- so there is no LDS and no barrier.  Per row and tile two ballots of `live && score >= thr` (a plain
+// float compare: a NaN threshold hits nothing, -inf every live item); the popcounts add up in the holder.  The fill writes a
+// hit to base + (hits of the row in the block's earlier tiles) + (hits in lower columns of this tile), clamped against the
+// start of the row's next chunk: a disagreement between the passes would show inside the row's own slots, never as a stray
+// write.
+template <bool FILL, bool OWN>
+struct TkRange {
+  static constexpr int kRows = TK_Q / 4;  // rows per wave
+  bool holder;
+  int64_t q, base;
+  float thr;
+  int own, cnt, cap;
+
+  // ws [.][n_chunks]: the count pass's counts (flush), for the fill their exclusive prefix (the offsets kernel).  False
+  // (FILL only, block-uniform): no row of this block has a hit in this chunk of `items` items.
+  __device__ __forceinline__ bool init(const float* thrs, const int64_t* self, const int32_t* ws, const int64_t* offsets, int q0,
+                                       int rows_live, int chunk, int n_chunks, int items, int wave, int lane) {
+    holder = lane < kRows && wave * kRows + lane < rows_live;
+    q = q0 + wave * kRows + lane;
+    thr = holder ? thrs[q] : __builtin_nanf("");
+    own = (OWN && holder && self) ? (int)self[q] : -1;
+    cnt = cap = 0;
+    base = 0;
+    if constexpr (FILL) {
+      if (holder) {
+        const int64_t off = offsets[q];
+        const int32_t* pre = ws + q * n_chunks + chunk;
+        base = off + pre[0];
+        const int64_t next = chunk + 1 < n_chunks ? off + pre[1] : offsets[q + 1];
+        const int64_t room = next - base;  // never beyond the row's next chunk, nor more than the chunk has items
+        cap = room < 0 ? 0 : room > items ? items : (int)room;
+      }
+      return __syncthreads_or(cap > 0);
+    }
+    return true;
+  }
+
+  // live0 / live1: column `lane` / 64 + `lane` of the tile at g0 holds an item that may be hit.
+  __device__ __forceinline__ void tile(const float* sS, int g0, bool live0, bool live1, int rows_live, int64_t* indices,
+                                       float* scores, int wave, int lane) {
+    const int c0 = g0 + lane, c1 = g0 + 64 + lane;
+#pragma nounroll
+    for (int rr = 0; rr < kRows; ++rr) {
+      const int row = wave * kRows + rr;
+      if (row >= rows_live) break;
+      const float s0 = sS[row * TK_SLD + lane], s1 = sS[row * TK_SLD + 64 + lane];
+      const float t = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(thr), rr));
+      const int o = OWN ? __builtin_amdgcn_readlane(own, rr) : -1;
+      const bool hit0 = live0 && (!OWN || c0 != o) && s0 >= t, hit1 = live1 && (!OWN || c1 != o) && s1 >= t;
+      const uint64_t b0 = __ballot(hit0), b1 = __ballot(hit1);
+      const int n0 = __popcll(b0), n1 = __popcll(b1);
+      if constexpr (FILL) {
+        if (b0 | b1) {  // wave-uniform
+          const int seen = __builtin_amdgcn_readlane(cnt, rr), room = __builtin_amdgcn_readlane(cap, rr);
+          const int64_t at = (int64_t)(((uint64_t)(unsigned)__builtin_amdgcn_readlane((int)(base >> 32), rr) << 32) |
+                                       (unsigned)__builtin_amdgcn_readlane((int)base, rr));
+          const uint64_t below = (1ull << lane) - 1;
+          const int p0 = seen + __popcll(b0 & below), p1 = seen + n0 + __popcll(b1 & below);
+          if (hit0 && p0 < room) {
+            indices[at + p0] = c0;
+            scores[at + p0] = s0;
+          }
+          if (hit1 && p1 < room) {
+            indices[at + p1] = c1;
+            scores[at + p1] = s1;
+          }
+        }
+      }
+      if (lane == rr) cnt += n0 + n1;
+    }
+  }
+
+  __device__ __forceinline__ void flush(int32_t* ws, int n_chunks, int chunk) const {
+    if (holder) ws[q * n_chunks + chunk] = cnt;
+  }
+};
+
+// THE similarity of two STORED items (search_diverse.hip: pair_scores_kernel; search_self.hip: sj_tile), N rows against one
+// column:  sim = <f_g, f_h> / sum_m gw_g[m] gw_h[m]  (0 -> 1e-5), the denominator an explicit fma chain over m ascending
+// (symmetric in its factors), with fp8 rows the numerator fl(acc * fl(scale_g * scale_h)): the product of two powers of two,
+// then one rounded multiply (tk_mul_rn).  acc[r] is row r's contraction, row_w(r, m) / row_scale(r) its weights and scale,
+// col_w(m) / col_scale the column's.  Not tk_tile_scores: a query's denominator is another, non-fma expression.
+template <bool FP8, int N, class Acc, class RowW, class ColW, class RowS>
+__device__ __forceinline__ void tk_pair_sims(float (&sim)[N], const Acc& acc, int M, RowW row_w, ColW col_w, RowS row_scale,
+                                             float col_scale) {
+  float den[N];
+#pragma unroll
+  for (int r = 0; r < N; ++r) den[r] = 0.f;
+  for (int m = 0; m < M; ++m) {
+    const float w = col_w(m);
+#pragma unroll
+    for (int r = 0; r < N; ++r) den[r] = __builtin_fmaf(row_w(r, m), w, den[r]);
+  }
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+    float num = acc[r];
+    if constexpr (FP8) num = tk_mul_rn(num, tk_mul_rn(row_scale(r), col_scale));
+    sim[r] = num / (den[r] == 0.f ? 1e-5f : den[r]);
+  }
+}
+
 // Column statistics of one score tile for the log-sum-exp over a bank of queries (search_norm.hip only): thread c < TK_G
 // takes column c and the tile's live rows 0 .. rows_live - 1 in ascending order: x = fl(beta * score), m = max x,
 // p = sum exp(x - m).  The order is fixed by the row number alone, so (m, p) is a function of the 64-row bank block, the
@@ -446,14 +558,13 @@ __device__ __forceinline__ void tk_tile(const Args& a, unsigned char* smem, floa
   constexpr bool FP8 = TkFp8<Args>::value;
   static_assert(!FP8 || BF16, "an fp8 gallery is scanned with the bf16 query pair");
   f32x16 acc[2];
-  if constexpr (FP8)
-    tk_scan_fp8(acc, smem, (const bf16_t*)a.q, (const bf16_t*)a.q_lo, (const uint8_t*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg,
-                l31, h);
-  else if constexpr (BF16)
-    tk_scan_bf16(acc, smem, (const bf16_t*)a.q, (const bf16_t*)a.q_lo, (const bf16_t*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg,
-                 l31, h);
+  const int NQ = a.NQ;
+  const auto qrow = [=](int r) { return q0 + r < NQ ? q0 + r : -1; };
+  if constexpr (BF16)  // the query as two bf16 planes, hi then lo
+    tk_scan(acc, smem, {(const bf16_t*)a.q, (const bf16_t*)a.q_lo}, qrow, (const std::conditional_t<FP8, uint8_t, bf16_t>*)a.g,
+            grow, a.K, tid, wq, wg, l31, h);
   else
-    tk_scan_f32(acc, smem, (const float*)a.q, (const float*)a.g, a.NQ, a.K, q0, grow, tid, wq, wg, l31, h);
+    tk_scan(acc, smem, {(const float*)a.q}, qrow, (const float*)a.g, grow, a.K, tid, wq, wg, l31, h);
   __syncthreads();  // the slabs become the score tile
   if constexpr (FP8)
     tk_tile_scores<true>(acc, sS, sQw, a.gw, a.M, grow, wq, wg, l31, h, a.gscale);
@@ -522,9 +633,18 @@ int tk_chunk(int NQ, int NV);
 // The chunk reduce of the count passes (search_rank.hip): cnt [n][n_chunks][2] summed in chunk order.
 int rk_reduce_launch(const int32_t* cnt, int64_t n, int n_chunks, int32_t* greater, int32_t* equal, hipStream_t s);
 
+// The offsets kernel between the count and the fill pass of a range scan (search_range.hip): one thread per row turns
+// ws [R][n_chunks] into the row's exclusive prefix in place, in chunk order, and writes the row total as int64.
+int rg_offsets_launch(int32_t* ws, int R, int n_chunks, int64_t* row_counts, hipStream_t s);
+
 inline int tk_n_chunks(int NQ, int NV) {
   const int chunk = tk_chunk(NQ, NV);
   return (NV + chunk - 1) / chunk;
+}
+
+// int32 words of a range scan's workspace [NQ][n_chunks].
+inline int64_t tk_range_workspace_ints(int NQ, int NV) {
+  return NQ < 1 || NV < 1 ? (int64_t)MMT_ERR_ARG : (int64_t)NQ * tk_n_chunks(NQ, NV);
 }
 
 // The launch geometry of a scan over a.NQ queries and a.NV items: grid = n_qt * n_chunks blocks.

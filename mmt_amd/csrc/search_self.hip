@@ -2,12 +2,11 @@
 // against the stored items, as a streaming scan -- per row item its k best stored items, or every stored item at or above
 // a threshold as a CSR -- without the NV x NV matrix.  The quantity is the one of search_diverse.hip,
 //   sim(g, h) = <f_g, f_h> / sum_m gw_g[m] gw_h[m]      (0 -> 1e-5)
-// f_g the dequantised stored row, and every score here has the bits pair_scores_kernel gives the pair: the K loops below
-// are written next to dv_gram_f32 / dv_gram_b16 and run their slab and MFMA sequence -- kb ascending in the slab widths
-// of search_scan.h, kk ascending, u ascending, ONE accumulator per output, fp32 rows on v_mfma_f32_32x32x2_f32, bf16 rows
-// and fp8 codes widened exactly (tk_widen_fp8) on one v_mfma_f32_32x32x16_bf16 per fragment, no hi / lo pair -- and the
-// epilogue is that kernel's: den = fma(gw_g[m], gw_h[m], den) for m ascending, fp8: num = fl(acc * fl(scale_g * scale_h))
-// (tk_mul_rn), sim = num / den.  search_scan.h, search_topk.h and every other .hip file are only read.
+// f_g the dequantised stored row, and every score here has the bits pair_scores_kernel gives the pair BY CONSTRUCTION: the K
+// loop is search_scan.h's tk_scan -- the scans' composition of TkStager, tk_k_loop and tk_step, with the A rows read
+// through a row table and ONE plane of the stored element (fp32 rows on v_mfma_f32_32x32x2_f32; bf16 rows, and fp8 codes
+// widened exactly in the stager, on one v_mfma_f32_32x32x16_bf16 per fragment, no hi / lo pair), the pieces the Gram of
+// search_diverse.hip is made of -- and the epilogue is the one definition of sim, tk_pair_sims.
 //
 // BOTH operands are stored rows, and they are two operands: the A side (a_rows, a_weights, a_scales: NA rows) read
 // through the row indirection items[r] (null = row r), 64 rows of the slab per block; the B side (g, gw, gscale: NV items)
@@ -19,11 +18,10 @@
 //                              consumes it unchanged: the row's own item is its single exclusion (E = 1), a subset bitmap
 //                              gates tiles and columns (tk_tile_mask).  tk_flush leaves the chunk's sorted k best per row
 //                              in the workspace [R][n_chunks][k]; tk_merge_launch merges it.
-//   self_kernel<ST, SJ_COUNT>, <ST, SJ_FILL> : the count and the fill step of range_kernel (search_range.hip) restated:
-//                              `live && item != self && score >= thr[row]`, two ballots per row and tile, the popcounts
-//                              summed in the lane that holds the row; self_offsets_kernel turns a row's chunk counts into
-//                              their exclusive prefix; the fill writes a hit to offsets[r] + prefix + hits before it, the
-//                              position clamped against the start of the row's next chunk.
+//   self_kernel<ST, SJ_COUNT>, <ST, SJ_FILL> : the count and the fill pass of a range scan: search_scan.h's range step
+//                              TkRange<FILL, true>, range_kernel's with the row's own item to skip (`live && item != self
+//                              && score >= thr[row]`); between the passes search_range.hip's offsets kernel
+//                              (rg_offsets_launch) turns a row's chunk counts into their exclusive prefix.
 // No atomics; every output slot has one writer; results are bit-reproducible.
 #include "search_topk.h"
 
@@ -54,163 +52,30 @@ struct SjArgs {
   int NA, NQ, NV, M, K, k, chunk, n_qt, n_chunks;  // NQ = R, named as tk_geometry reads it
 };
 
-// fp32 K loop of one 64 x 128 tile, both operands stored rows: acc = A[sRow[.]] . G[grow(.)]^T.  tk_scan_f32 with the A
-// slab read through the row table; the slab and MFMA sequence of dv_gram_f32.  Opens with a barrier, leaves the last
-// slab's reads unfenced.
-template <class GRow>
-__device__ __forceinline__ void sj_scan_f32(f32x16 (&acc)[2], unsigned char* smem, const float* a, const int* sRow,
-                                            const float* g, int K, GRow grow, int tid, int wq, int wg, int l31, int h) {
-  float* sA = (float*)smem;        // [TK_Q][TK_LD]
-  float* sB = sA + TK_Q * TK_LD;   // [TK_G][TK_LD]
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  int ar[2], gr[4];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) ar[j] = sRow[(tid + 256 * j) >> 3];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) gr[j] = grow((tid + 256 * j) >> 3);
-  f32x4 ra[2], rb[4];
-  auto load = [&](int kb) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int c = kb + ((tid + 256 * j) & 7) * 4;
-      ra[j] = (ar[j] >= 0 && c < K) ? *(const f32x4*)(a + (int64_t)ar[j] * K + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = kb + ((tid + 256 * j) & 7) * 4;
-      rb[j] = (gr[j] >= 0 && c < K) ? *(const f32x4*)(g + (int64_t)gr[j] * K + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  };
-  load(0);
-  for (int kb = 0; kb < K; kb += TK_BK) {
-    __syncthreads();  // previous slab (or the previous tile's scores) consumed
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { const int i = tid + 256 * j; *(f32x4*)(sA + (i >> 3) * TK_LD + (i & 7) * 4) = ra[j]; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const int i = tid + 256 * j; *(f32x4*)(sB + (i >> 3) * TK_LD + (i & 7) * 4) = rb[j]; }
-    __syncthreads();
-    if (kb + TK_BK < K) load(kb + TK_BK);
-    // 8 contraction values per step; lane half h feeds k = kk + 4h + u to MFMA u (as dv_gram_f32)
-#pragma unroll
-    for (int kk = 0; kk < TK_BK; kk += 8) {
-      const f32x4 av = *(const f32x4*)(sA + (wq * 32 + l31) * TK_LD + kk + 4 * h);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const f32x4 bv = *(const f32x4*)(sB + (wg * 64 + t * 32 + l31) * TK_LD + kk + 4 * h);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc[t], 0, 0, 0);
-      }
-    }
-  }
-}
-
-// The same over rows stored in 16 bits or fewer: bf16 as they are, fp8 widened exactly to bf16 on the way into LDS, on
-// BOTH sides; one MFMA per fragment (as dv_gram_b16).  A slab: 64 rows x 64 elements = 8 (bf16) or 4 (fp8) sixteen-byte
-// loads per row, 2 or 1 per thread; B slab: 128 rows, 4 or 2 per thread.
-template <bool FP8, class GRow>
-__device__ __forceinline__ void sj_scan_b16(f32x16 (&acc)[2], unsigned char* smem, const void* a, const int* sRow,
-                                            const void* g, int K, GRow grow, int tid, int wq, int wg, int l31, int h) {
-  constexpr int NA_ = FP8 ? 1 : 2;   // A loads per thread and slab
-  constexpr int NB = FP8 ? 2 : 4;    // B loads per thread and slab
-  constexpr int SH = FP8 ? 2 : 3;    // log2 of the loads per row and slab
-  constexpr int EL = FP8 ? 16 : 8;   // elements per load
-  bf16_t* sA = (bf16_t*)smem;           // [TK_Q][TKB_LD]
-  bf16_t* sB = sA + TK_Q * TKB_LD;      // [TK_G][TKB_LD]
-  const u32x4 zero = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  int ar[NA_], gr[NB];
-#pragma unroll
-  for (int j = 0; j < NA_; ++j) ar[j] = sRow[(tid + 256 * j) >> SH];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) gr[j] = grow((tid + 256 * j) >> SH);
-  u32x4 ra[NA_], rb[NB];
-  auto fetch = [&](const void* base, int row, int c) {
-    const int64_t off = (int64_t)row * K + c;
-    if (row < 0 || c >= K) return zero;
-    if constexpr (FP8)
-      return *(const u32x4*)((const uint8_t*)base + off);
-    else
-      return *(const u32x4*)((const bf16_t*)base + off);
-  };
-  auto load = [&](int kb) {
-#pragma unroll
-    for (int j = 0; j < NA_; ++j) ra[j] = fetch(a, ar[j], kb + ((tid + 256 * j) & ((1 << SH) - 1)) * EL);
-#pragma unroll
-    for (int j = 0; j < NB; ++j) rb[j] = fetch(g, gr[j], kb + ((tid + 256 * j) & ((1 << SH) - 1)) * EL);
-  };
-  auto stage = [&](bf16_t* slab, int i, const u32x4& v) {
-    bf16_t* dst = slab + (i >> SH) * TKB_LD + (i & ((1 << SH) - 1)) * EL;
-    if constexpr (FP8) {
-      u32x4 lo, hi;
-      tk_widen_fp8(v, lo, hi);
-      *(u32x4*)dst = lo;
-      *(u32x4*)(dst + 8) = hi;
-    } else {
-      *(u32x4*)dst = v;
-    }
-  };
-  load(0);
-  for (int kb = 0; kb < K; kb += TKB_BK) {
-    __syncthreads();  // previous slab (or the previous tile's scores) consumed
-#pragma unroll
-    for (int j = 0; j < NA_; ++j) stage(sA, tid + 256 * j, ra[j]);
-#pragma unroll
-    for (int j = 0; j < NB; ++j) stage(sB, tid + 256 * j, rb[j]);
-    __syncthreads();
-    if (kb + TKB_BK < K) load(kb + TKB_BK);
-    // 16 contraction values per MFMA; lane half h holds k = kk + 8h .. + 7 of its row (as dv_gram_b16)
-#pragma unroll
-    for (int kk = 0; kk < TKB_BK; kk += 16) {
-      const bf16x8_t av = *(const bf16x8_t*)(sA + (wq * 32 + l31) * TKB_LD + kk + 8 * h);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const bf16x8_t bv = *(const bf16x8_t*)(sB + (wg * 64 + t * 32 + l31) * TKB_LD + kk + 8 * h);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[t], 0, 0, 0);
-      }
-    }
-  }
-}
-
-// One 64 x 128 tile of sims in sS [TK_Q][TK_SLD]: the K loop and the epilogue of pair_scores_kernel -- the rows' weights
-// (sAw [TK_Q][MMT_MAX_EXPERTS], zero past M and for no row) and, fp8, scales (sAsc [TK_Q]) from LDS, the column's read
-// per lane.  Ends fenced.
+// One 64 x 128 tile of sims in sS [TK_Q][TK_SLD]: tk_scan with the A rows read through the row table -- one plane of
+// the stored element, widened if it is fp8 -- and the stored-pair epilogue tk_pair_sims: the rows' weights
+// (sAw [TK_Q][MMT_MAX_EXPERTS], zero past M and for no row) and, fp8, scales (sAsc [TK_Q]) from LDS, the column's read per
+// lane, once per m for its 16 rows.  Ends fenced.
 template <int ST, class GRow>
 __device__ __forceinline__ void sj_tile(const SjArgs& a, unsigned char* smem, float* sS, const float* sAw, const float* sAsc,
                                         const int* sRow, GRow grow, int tid, int wq, int wg, int l31, int h) {
+  using T = std::conditional_t<ST == MMT_SEARCH_FP32, float, std::conditional_t<ST == MMT_SEARCH_FP8, uint8_t, bf16_t>>;
   f32x16 acc[2];
-  if constexpr (ST == MMT_SEARCH_FP32)
-    sj_scan_f32(acc, smem, (const float*)a.a, sRow, (const float*)a.g, a.K, grow, tid, wq, wg, l31, h);
-  else
-    sj_scan_b16<ST == MMT_SEARCH_FP8>(acc, smem, a.a, sRow, a.g, a.K, grow, tid, wq, wg, l31, h);
+  tk_scan(acc, smem, {(const T*)a.a}, [=](int r) { return sRow[r]; }, (const T*)a.g, grow, a.K, tid, wq, wg, l31, h);
   __syncthreads();  // the slabs become the score tile
   const int M = a.M;
+  const float* gw = a.gw;
+  const auto row = [=](int r) { return wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h; };  // of accumulator element r
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const int col = wg * 64 + t * 32 + l31, g = grow(col);
-    float sc = 1.f;
+    float sc = 1.f, sim[16];
     if constexpr (ST == MMT_SEARCH_FP8) sc = g >= 0 ? a.gscale[g] : 1.f;
-    float den[16];
+    tk_pair_sims<ST == MMT_SEARCH_FP8>(
+        sim, acc[t], M, [=](int r, int m) { return sAw[row(r) * MMT_MAX_EXPERTS + m]; },
+        [=](int m) { return g >= 0 ? gw[(int64_t)g * M + m] : 0.f; }, [=](int r) { return sAsc[row(r)]; }, sc);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) den[r] = 0.f;
-    for (int m = 0; m < M; ++m) {
-      const float gwm = g >= 0 ? a.gw[(int64_t)g * M + m] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        den[r] = __builtin_fmaf(sAw[(wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * MMT_MAX_EXPERTS + m], gwm, den[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      float num = acc[t][r];
-      if constexpr (ST == MMT_SEARCH_FP8) num = tk_mul_rn(num, tk_mul_rn(sAsc[row], sc));
-      sS[row * TK_SLD + col] = num / (den[r] == 0.f ? 1e-5f : den[r]);
-    }
+    for (int r = 0; r < 16; ++r) sS[row(r) * TK_SLD + col] = sim[r];
   }
   __syncthreads();
 }
@@ -237,28 +102,11 @@ __global__ __launch_bounds__(256) void self_kernel(SjArgs a) {
   const int cap = a.k + 64;
   int* sEx = (int*)(sC + (MODE == SJ_TOPK ? TK_Q * cap : 0));  // [TK_Q]
 
-  // range only: lane l < 16 of wave w holds the state of row 16 w + l for the whole block (as range_kernel)
-  const int my_row = wave * kRows + lane;
-  const bool holder = lane < kRows && my_row < rows_live;
-  float my_thr = __builtin_nanf("");
-  int my_self = -1, my_cnt = 0, my_cap = 0;
-  int64_t my_base = 0;
+  // range only: the rows' thresholds, own items, hits so far and, for the fill, slots of this chunk
+  TkRange<MODE == SJ_FILL, true> rg;
   if constexpr (MODE != SJ_TOPK) {
-    if (holder) {
-      my_thr = a.thr[q0 + my_row];
-      if (a.self) my_self = (int)a.self[q0 + my_row];
-    }
-  }
-  if constexpr (MODE == SJ_FILL) {
-    if (holder) {
-      const int64_t q = q0 + my_row, off = a.offsets[q];
-      const int32_t* pre = a.cnt + q * a.n_chunks + chunk;
-      my_base = off + pre[0];
-      const int64_t next = chunk + 1 < a.n_chunks ? off + pre[1] : a.offsets[q + 1];
-      const int64_t room = next - my_base;  // never beyond the row's next chunk, nor more than the chunk has items
-      my_cap = room < 0 ? 0 : room > g_end - g_begin ? g_end - g_begin : (int)room;
-    }
-    if (!__syncthreads_or(my_cap > 0)) return;  // block-uniform: no row of this block has a hit in this chunk
+    if (!rg.init(a.thr, a.self, a.cnt, a.offsets, q0, rows_live, chunk, a.n_chunks, g_end - g_begin, wave, lane))
+      return;  // block-uniform: no row of this block has a hit in this chunk
   }
 
   if (tid < TK_Q) {
@@ -287,36 +135,8 @@ __global__ __launch_bounds__(256) void self_kernel(SjArgs a) {
     if constexpr (MODE == SJ_TOPK) {
       tk_tile_select<true>(sS, sC, sN, sT, a.k, rows_live, g0, g_end, wave, lane, m0, m1, sEx, 1);
     } else {
-      const int c0 = g0 + lane, c1 = g0 + 64 + lane;
-      const bool live0 = c0 < g_end && ((m0 >> lane) & 1ull), live1 = c1 < g_end && ((m1 >> lane) & 1ull);
-      for (int rr = 0; rr < kRows; ++rr) {
-        const int row = wave * kRows + rr;
-        if (row >= rows_live) break;
-        const float s0 = sS[row * TK_SLD + lane], s1 = sS[row * TK_SLD + 64 + lane];
-        const float thr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_thr), rr));
-        const int own = __builtin_amdgcn_readlane(my_self, rr);  // the self pair goes by item number, not by score
-        const bool hit0 = live0 && c0 != own && s0 >= thr, hit1 = live1 && c1 != own && s1 >= thr;
-        const uint64_t b0 = __ballot(hit0), b1 = __ballot(hit1);
-        const int n0 = __popcll(b0), n1 = __popcll(b1);
-        if constexpr (MODE == SJ_FILL) {
-          if (b0 | b1) {  // wave-uniform
-            const int seen = __builtin_amdgcn_readlane(my_cnt, rr), room = __builtin_amdgcn_readlane(my_cap, rr);
-            const int64_t base = (int64_t)(((uint64_t)(unsigned)__builtin_amdgcn_readlane((int)(my_base >> 32), rr) << 32) |
-                                           (unsigned)__builtin_amdgcn_readlane((int)my_base, rr));
-            const uint64_t below = (1ull << lane) - 1;
-            const int p0 = seen + __popcll(b0 & below), p1 = seen + n0 + __popcll(b1 & below);
-            if (hit0 && p0 < room) {
-              a.indices[base + p0] = c0;
-              a.scores[base + p0] = s0;
-            }
-            if (hit1 && p1 < room) {
-              a.indices[base + p1] = c1;
-              a.scores[base + p1] = s1;
-            }
-          }
-        }
-        if (lane == rr) my_cnt += n0 + n1;
-      }
+      const bool live0 = g0 + lane < g_end && ((m0 >> lane) & 1ull), live1 = g0 + 64 + lane < g_end && ((m1 >> lane) & 1ull);
+      rg.tile(sS, g0, live0, live1, rows_live, a.indices, a.scores, wave, lane);
     }
   }
   if constexpr (MODE == SJ_TOPK) {
@@ -329,24 +149,7 @@ __global__ __launch_bounds__(256) void self_kernel(SjArgs a) {
       tk_flush(sC + row * cap, sN[row], a.k, lane, ws + (q0 + row) * ws_row);
     }
   }
-  if constexpr (MODE == SJ_COUNT) {
-    if (holder) a.cnt[(int64_t)(q0 + my_row) * a.n_chunks + chunk] = my_cnt;
-  }
-}
-
-// One thread per row: the chunk counts become their exclusive prefix, in chunk order; the row total as int64.
-__global__ __launch_bounds__(256) void self_offsets_kernel(int32_t* __restrict__ cnt, int R, int n_chunks,
-                                                           int64_t* __restrict__ row_counts) {
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= R) return;
-  int32_t* row = cnt + (int64_t)q * n_chunks;
-  int run = 0;
-  for (int c = 0; c < n_chunks; ++c) {
-    const int n = row[c];
-    row[c] = run;
-    run += n;
-  }
-  row_counts[q] = run;
+  if constexpr (MODE == SJ_COUNT) rg.flush(a.cnt, a.n_chunks, chunk);
 }
 
 namespace {
@@ -399,8 +202,7 @@ extern "C" int64_t mmt_self_topk_workspace_keys(int R, int NV, int k) {
 }
 
 extern "C" int64_t mmt_self_range_workspace_ints(int R, int NV) {
-  if (R < 1 || NV < 1) return MMT_ERR_ARG;
-  return (int64_t)R * tk_n_chunks(R, NV);
+  return tk_range_workspace_ints(R, NV);
 }
 
 extern "C" int mmt_search_self_topk(const void* a_rows, const float* a_weights, const float* a_scales, int NA,
@@ -430,8 +232,7 @@ extern "C" int mmt_search_self_range_count(const void* a_rows, const float* a_we
   a.thr = thr; a.cnt = ws;
   const hipStream_t st = (hipStream_t)stream;
   sj_launch<SJ_COUNT>(a, storage, kRangeLds, st);
-  hipLaunchKernelGGL(self_offsets_kernel, dim3((R + 255) / 256), dim3(256), 0, st, ws, R, a.n_chunks, row_counts);
-  return (int)hipGetLastError();
+  return rg_offsets_launch(ws, R, a.n_chunks, row_counts, st);
 }
 
 extern "C" int mmt_search_self_range_fill(const void* a_rows, const float* a_weights, const float* a_scales, int NA,

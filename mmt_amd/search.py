@@ -291,20 +291,23 @@ re-uploads, crops and windows of one video, `search_groups` removes such copies 
 sim(g, h), reachable there only for lists of C <= 128 as a C x C matrix; searching with dequantised rows as queries is a
 different quantity (on a bfloat16 or float8_e4m3fn index it re-rounds one operand).  The self-join is a streaming scan
 with BOTH operands stored rows (search_self.hip): blocks of 64 row items x one gallery chunk score 64 x 128 tiles with the
-slab and MFMA sequence of the Gram kernel -- fp32 rows on v_mfma_f32_32x32x2_f32, bf16 rows and exactly widened fp8 codes on
-one v_mfma_f32_32x32x16_bf16 per fragment, the same fma chain for the denominator, the same rounded multiplies for the fp8
-scales -- so every score the three calls return has exactly the bits `pair_scores` gives the pair on the same index, on
+Gram kernel's own pieces (search_scan.h: one slab stager, one K loop, one MFMA step, and tk_pair_sims, the one
+definition of sim) -- fp32 rows on v_mfma_f32_32x32x2_f32, bf16 rows and exactly widened fp8 codes on one
+v_mfma_f32_32x32x16_bf16 per fragment -- so every score the three calls return has exactly the bits `pair_scores` gives
+the pair on the same index, on
 all three storage dtypes, whatever the row batching, the launch geometry, num_items, the position or the shard.  The order
 is `search`'s; the self pair (g, g) is left out by item NUMBER, not by score, so an exact copy of g stays in g's list.
 `neighbours` keeps a running top-k per row (the selection, workspace and merge of `search`); `neighbour_range` is the two
-scans of `range_search`, no atomics, the total known after the first; `duplicate_groups` turns the threshold graph's edges,
+scans of `range_search` (one range step on the device, one CSR assembly `_csr` and one pair of batch loops on the host),
+no atomics, the total known after the first; `duplicate_groups` turns the threshold graph's edges,
 taken from `neighbour_range` in row batches, into connected components by minimum-label propagation with pointer jumping
 (`connected_components`, torch ops), labels[g] = the smallest item number of g's component -- which `grouping` accepts
 unchanged, so `search_groups` de-duplicates without anybody's labels and `diversify` penalises with the same bits.
 source= takes another VideoIndex's items as the rows (an upload batch against the gallery before `add`; no self pair).
 ShardedVideoIndex has the three calls, bit-identical: per row batch the rows' stored bytes, weights and scales are staged
 on the primary and copied to every shard, which joins them against its own items; lists are merged
-(mmt_search_merge_lists), CSR rows assembled as `range_search` assembles them.  Out of scope: norm=, pooling=,
+(mmt_search_merge_lists), CSR rows assembled by the helper that assembles `range_search`'s
+(`_range_csr`).  Out of scope: norm=, pooling=,
 item_pooling=, grouping=, after= and exclude= raise ValueError naming the option.
 
     lse = index.query_lse(q, qw, beta=20.0, subset=None)          # QueryLse: .lse [NQ], .top_scores, .top_items, .sums, .bits
@@ -2071,46 +2074,75 @@ class VideoIndex(_Index):
                                      ops._p(outs[0][r0:r1]), ops._p(outs[1][r0:r1]), ops._stream()), 'mmt_search_self_topk')
 
   def _self_range_count(self, a, items, own, thr, subset):
-    """The count pass of `neighbour_range`, batch by batch: thr float32 [R] on this device -> (hits per row int64 [R], the
-    batches' workspaces as the fill pass wants them).  Nothing here waits for the device."""
+    """The count pass of `neighbour_range` (`_count_batches`): a, items, own as `_self_operands`."""
+    return self._count_batches('mmt_self_range_workspace_ints', 'mmt_search_self_range_count',
+                               lambda r0, r1: (self._self_operands(a, items, own, r0, r1, subset), None), thr)
+
+  def _self_range_fill(self, a, items, own, thr, subset, kept, offsets, indices, scores):
+    """The fill pass of `neighbour_range`: `kept` from `_self_range_count` of the same arguments (`_fill_batches`)."""
+    self._fill_batches('mmt_search_self_range_fill',
+                       lambda r0, r1: (self._self_operands(a, items, own, r0, r1, subset), None), thr, kept, offsets,
+                       indices, scores)
+
+  def _scan_lead(self, q, qw, subset):
+    """The leading argument of the range entries over queries: (r0, r1) -> ((the batch's descriptor,), what it points at)."""
+    scan = _Scan(subset)
+
+    def lead(r0, r1):
+      desc, _, _, keep = self._describe(scan, q, qw, r0, r1)
+      return (desc,), keep
+    return lead
+
+  def _count_batches(self, workspace, entry, lead, thr):
+    """The count pass of a range scan, batch by batch: thr float32 [R] on this device, one per row; lead(r0, r1) -> (the
+    entry's arguments before the thresholds, what keeps them alive) -> (hits per row int64 [R], the batches' workspaces as
+    the fill pass wants them).  Nothing here waits for the device."""
     r, nv, L = thr.shape[0], self.num_items, _lib.lib()
     counts = torch.empty(r, device=self.device, dtype=torch.int64)
     kept = []
     for r0, r1 in self._batches(r, 1):
-      ws = torch.empty(L.mmt_self_range_workspace_ints(r1 - r0, nv), device=self.device, dtype=torch.int32)
-      check(L.mmt_search_self_range_count(*self._self_operands(a, items, own, r0, r1, subset), ops._p(thr[r0:r1]), ops._p(ws),
-                                          ops._p(counts[r0:r1]), ops._stream()), 'mmt_search_self_range_count')
+      args, _keep = lead(r0, r1)
+      ws = torch.empty(getattr(L, workspace)(r1 - r0, nv), device=self.device, dtype=torch.int32)
+      check(getattr(L, entry)(*args, ops._p(thr[r0:r1]), ops._p(ws), ops._p(counts[r0:r1]), ops._stream()), entry)
       kept.append(ws)
     return counts, kept
 
-  def _self_range_fill(self, a, items, own, thr, subset, kept, offsets, indices, scores):
-    """The fill pass of `neighbour_range`: `kept` from `_self_range_count` of the same arguments, offsets int64 [R + 1]
-    into indices / scores."""
+  def _fill_batches(self, entry, lead, thr, kept, offsets, indices, scores):
+    """The fill pass of a range scan: `kept` from `_count_batches` of the same arguments, offsets int64 [R + 1] into
+    indices / scores."""
     L = _lib.lib()
     for (r0, r1), ws in zip(self._batches(thr.shape[0], 1), kept):
-      check(L.mmt_search_self_range_fill(*self._self_operands(a, items, own, r0, r1, subset), ops._p(thr[r0:r1]), ops._p(ws),
-                                         ops._p(offsets[r0:r1 + 1]), ops._p(indices), ops._p(scores), ops._stream()),
-            'mmt_search_self_range_fill')
+      args, _keep = lead(r0, r1)
+      check(getattr(L, entry)(*args, ops._p(thr[r0:r1]), ops._p(ws), ops._p(offsets[r0:r1 + 1]), ops._p(indices),
+                              ops._p(scores), ops._stream()), entry)
 
-  def _neighbour_range(self, rows, items, own, thr, subset, order, max_hits, who, spent=0):
-    """`neighbour_range` behind its checks: items int64 [R] of `rows`' numbers, own as `_self_operands`, thr float32 [R].
-    Every batch is counted first, then comes the one allocation, then the fills, as `range_search`.  spent: the hits an
-    enclosing call has already used of max_hits."""
-    a, r = rows._self_rows(), items.shape[0]
+  def _csr(self, r, count, fill, order, max_hits, who, spent=0):
+    """The CSR of a range scan of r rows, `range_search`'s and `neighbour_range`'s: count() -> (hits per row int64 [r], the
+    batches' workspaces) counts every batch first, the sum of the counts places the rows -- the total is the call's one
+    wait for the device, held against max_hits (spent: the hits an enclosing call has already used of it) before anything
+    of output size exists -- then comes the one allocation, then fill(workspaces, offsets, indices, scores)."""
     with torch.cuda.device(self.device):
       offsets = torch.zeros(r + 1, device=self.device, dtype=torch.int64)
       total = 0
       if r:
-        counted = self._self_range_count(a, items, own, thr, subset)
-        torch.cumsum(counted[0], 0, out=offsets[1:])
+        counts, kept = count()
+        torch.cumsum(counts, 0, out=offsets[1:])
         total = int(offsets[-1])
       if spent + total > max_hits:
         raise ValueError('%s: %d hits exceed max_hits = %d' % (who, spent + total, max_hits))
       indices = torch.empty(total, device=self.device, dtype=torch.int64)
       scores = torch.empty(total, device=self.device, dtype=torch.float32)
       if total:
-        self._self_range_fill(a, items, own, thr, subset, counted[1], offsets, indices, scores)
+        fill(kept, offsets, indices, scores)
       return _range_result(offsets, indices, scores, order)
+
+  def _neighbour_range(self, rows, items, own, thr, subset, order, max_hits, who, spent=0):
+    """`neighbour_range` behind its checks (`_csr`): items int64 [R] of `rows`' numbers, own as `_self_operands`, thr
+    float32 [R]."""
+    a = rows._self_rows()
+    return self._csr(items.shape[0], lambda: self._self_range_count(a, items, own, thr, subset),
+                     lambda *outs: self._self_range_fill(a, items, own, thr, subset, *outs), order, max_hits, who, spent)
+
 
   def _rank_counts(self, q, qw, tg, scan):
     """`rank_counts` behind its checks: tg int64 [NQ >= 1, T] on the index device (with a pooling [num_sets, T], with an
@@ -2235,43 +2267,17 @@ class VideoIndex(_Index):
     where a recount would be a third scan; the folded queries of a batch, which are large, are folded again instead.
     Exclusions per query are not part of this call: the caller applies them to the CSR."""
     q, qw, thr = self._range_args(embds, weights, threshold, subset, order, max_hits)
-    nq = q.shape[0]
-    with torch.cuda.device(self.device):
-      counted = self._range_count(q, qw, thr, subset)
-      offsets = torch.zeros(nq + 1, device=self.device, dtype=torch.int64)
-      if nq:
-        torch.cumsum(counted[0], 0, out=offsets[1:])
-      total = int(offsets[-1]) if nq else 0
-      if total > max_hits:
-        raise ValueError('range_search: %d hits exceed max_hits = %d' % (total, max_hits))
-      indices = torch.empty(total, device=self.device, dtype=torch.int64)
-      scores = torch.empty(total, device=self.device, dtype=torch.float32)
-      if total:
-        self._range_fill(q, qw, thr, subset, counted[1], offsets, indices, scores)
-      return _range_result(offsets, indices, scores, order)
+    return self._csr(q.shape[0], lambda: self._range_count(q, qw, thr, subset),
+                     lambda *outs: self._range_fill(q, qw, thr, subset, *outs), order, max_hits, 'range_search')
 
   def _range_count(self, q, qw, thr, subset):
-    """The count pass of `range_search` behind its checks, batch by batch -> (hits per query int64 [NQ], the batches'
-    workspaces as the fill pass wants them).  Nothing here waits for the device."""
-    nq, nv, L, scan = q.shape[0], self.num_items, _lib.lib(), _Scan(subset)
-    counts = torch.empty(nq, device=self.device, dtype=torch.int64)
-    kept = []
-    for r0, r1 in self._batches(nq, 1):
-      desc, _, _, _keep = self._describe(scan, q, qw, r0, r1)
-      ws = torch.empty(L.mmt_range_workspace_ints(r1 - r0, nv), device=self.device, dtype=torch.int32)
-      check(L.mmt_search_range_count(desc, ops._p(thr[r0:r1]), ops._p(ws), ops._p(counts[r0:r1]), ops._stream()),
-            'mmt_search_range_count')
-      kept.append(ws)
-    return counts, kept
+    """The count pass of `range_search` behind its checks (`_count_batches`)."""
+    return self._count_batches('mmt_range_workspace_ints', 'mmt_search_range_count', self._scan_lead(q, qw, subset), thr)
 
   def _range_fill(self, q, qw, thr, subset, kept, offsets, indices, scores):
-    """The fill pass of `range_search`: `kept` from `_range_count` of the same arguments, offsets int64 [NQ + 1] into
-    indices / scores."""
-    L, scan = _lib.lib(), _Scan(subset)
-    for (r0, r1), ws in zip(self._batches(q.shape[0], 1), kept):
-      desc, _, _, _keep = self._describe(scan, q, qw, r0, r1)
-      check(L.mmt_search_range_fill(desc, ops._p(thr[r0:r1]), ops._p(ws), ops._p(offsets[r0:r1 + 1]), ops._p(indices),
-                                    ops._p(scores), ops._stream()), 'mmt_search_range_fill')
+    """The fill pass of `range_search`: `kept` from `_range_count` of the same arguments (`_fill_batches`)."""
+    self._fill_batches('mmt_search_range_fill', self._scan_lead(q, qw, subset), thr, kept, offsets, indices, scores)
+
 
 
 MAX_SHARDS = 32  # lists per query of the merge kernel
@@ -2699,17 +2705,29 @@ class ShardedVideoIndex(_Index):
       self._merged(tuple(o[r0:r1] for o in outs), live, k, 'mmt_search_merge_lists', tables, lists)
 
   def _neighbour_range(self, rows, items, own, thr, subset, order, max_hits, who, spent=0):
-    """`neighbour_range` behind its checks, over all shards, assembled as `range_search` assembles its rows: per staging
-    batch every shard counts the hits among its own items; the totals are summed on the primary and held against max_hits
-    before any shard allocates its outputs; the batches are staged again, every shard fills a CSR of its own, whose local
-    numbers go through its table to global ones, and the primary orders the hits by (row, global item)."""
-    r = items.shape[0]
-    live, batches = self._live(subset), self._stage_batches(r)
+    """`neighbour_range` behind its checks, over all shards (`_range_csr`): a batch is a staging batch of the rows' stored
+    bytes, staged once for the count and again for the fill."""
+    live = self._live(subset)
+    return self._range_csr(items.shape[0], live, self._stage_batches(items.shape[0]),
+                           lambda r0, r1: self._staged(items, r0, r1, thr, subset, live),
+                           lambda sh, mine: sh.index._self_range_count(mine[0], None, *mine[1:]),
+                           lambda sh, mine, *outs: sh.index._self_range_fill(mine[0], None, *mine[1:], *outs),
+                           order, max_hits, who, spent)
+
+  def _range_csr(self, r, live, batches, stage, count, fill, order, max_hits, who, spent=0):
+    """The CSR of a range scan of r rows over all shards, assembled as VideoIndex._csr assembles one index's: per batch
+    (r0, r1) of `batches`, stage(r0, r1) -> {shard: its operands} and every shard counts the hits among its own items
+    (count(shard, operands) -> (hits per row, workspaces)); the totals are summed on the primary -- the call's one wait for
+    the devices -- and held against max_hits (spent: the hits an enclosing call has already used of it) before any shard
+    allocates its outputs; the batches are staged again, every shard fills a CSR of its own (fill(shard, operands,
+    workspaces, offsets, indices, scores)), whose local numbers go through its table to global ones, and the primary orders
+    the hits by (row, global item) with two stable torch sorts."""
     counted = {}
     for b, (r0, r1) in enumerate(batches):
-      for (s, sh), (a, local, t, part) in zip(live, self._staged(items, r0, r1, thr, subset, live).values()):
+      staged = stage(r0, r1)
+      for s, sh in live:
         with torch.cuda.device(sh.device):
-          counted[b, s] = sh.index._self_range_count(a, None, local, t, part)
+          counted[b, s] = count(sh, staged[s])
     with torch.cuda.device(self.device):
       per_shard = torch.zeros(len(live), r, device=self.device, dtype=torch.int64)
       for b, (r0, r1) in enumerate(batches):
@@ -2727,17 +2745,16 @@ class ShardedVideoIndex(_Index):
     for b, (r0, r1) in enumerate(batches):
       if not any(cells[b]):
         continue
-      staged = self._staged(items, r0, r1, thr, subset, live)
+      staged = stage(r0, r1)
       for i, (s, sh) in enumerate(live):
         if not cells[b][i]:
           continue
-        a, own_s, t, part = staged[s]
         with torch.cuda.device(sh.device):
           local = torch.zeros(r1 - r0 + 1, device=sh.device, dtype=torch.int64)
           torch.cumsum(counted[b, s][0], 0, out=local[1:])
           idx = torch.empty(cells[b][i], device=sh.device, dtype=torch.int64)
           sc = torch.empty(cells[b][i], device=sh.device, dtype=torch.float32)
-          sh.index._self_range_fill(a, None, own_s, t, part, counted[b, s][1], local, idx, sc)
+          fill(sh, staged[s], counted[b, s][1], local, idx, sc)
         at.append(_csr_rows(local.to(self.device)) + r0)
         hit.append(sh.ids[idx.to(self.device)])
         sims.append(sc.to(self.device))
@@ -2818,39 +2835,13 @@ class ShardedVideoIndex(_Index):
     to global ones; the primary concatenates the shards' hits and orders them by (query, global item) with two stable
     torch sorts.  order='score' as VideoIndex.range_search.  Exclusions are applied to the CSR by the caller."""
     q, qw, thr = self._range_args(embds, weights, threshold, subset, order, max_hits)
-    nq = q.shape[0]
-    scan, live = _Scan(subset), self._live(subset)
-    args, counted = {}, {}
-    for s, sh in live:
-      args[s] = (q.to(sh.device), qw.to(sh.device), thr.to(sh.device), scan.shard(s, self).subset)
-      with torch.cuda.device(sh.device):
-        counted[s] = sh.index._range_count(*args[s])
-    with torch.cuda.device(self.device):
-      per_shard = torch.stack([counted[s][0].to(self.device) for s, _ in live])   # [S, NQ]
-      totals = per_shard.sum(1).tolist()
-      if sum(totals) > max_hits:
-        raise ValueError('range_search: %d hits exceed max_hits = %d' % (sum(totals), max_hits))
-      offsets = torch.zeros(nq + 1, device=self.device, dtype=torch.int64)
-      if nq:
-        torch.cumsum(per_shard.sum(0), 0, out=offsets[1:])
-    rows, items, scores = [], [], []
-    for (s, sh), total in zip(live, totals):
-      if not total:
-        continue
-      with torch.cuda.device(sh.device):
-        local = torch.zeros(nq + 1, device=sh.device, dtype=torch.int64)
-        torch.cumsum(counted[s][0], 0, out=local[1:])
-        idx = torch.empty(total, device=sh.device, dtype=torch.int64)
-        sc = torch.empty(total, device=sh.device, dtype=torch.float32)
-        sh.index._range_fill(*args[s], counted[s][1], local, idx, sc)
-      rows.append(_csr_rows(local.to(self.device)))
-      items.append(sh.ids[idx.to(self.device)])
-      scores.append(sc.to(self.device))
-    with torch.cuda.device(self.device):
-      if not rows:
-        return RangeResult(offsets, torch.empty(0, device=self.device, dtype=torch.int64),
-                           torch.empty(0, device=self.device, dtype=torch.float32))
-      rows, items, scores = torch.cat(rows), torch.cat(items), torch.cat(scores)
-      by_item = torch.argsort(items, stable=True)
-      perm = by_item[torch.argsort(rows[by_item], stable=True)]
-      return _range_result(offsets, items[perm], scores[perm], order)
+    scan, live, args = _Scan(subset), self._live(subset), {}
+
+    def stage(r0, r1):  # one batch: the queries go to every shard once, for both passes
+      for s, sh in live:
+        if s not in args:
+          args[s] = (q.to(sh.device), qw.to(sh.device), thr.to(sh.device), scan.shard(s, self).subset)
+      return args
+    return self._range_csr(q.shape[0], live, [(0, q.shape[0])] if q.shape[0] else [], stage,
+                           lambda sh, mine: sh.index._range_count(*mine),
+                           lambda sh, mine, *outs: sh.index._range_fill(*mine, *outs), order, max_hits, 'range_search')

@@ -142,6 +142,59 @@ def test_row_batching_and_a_second_run_change_no_bit(dtype, monkeypatch):
     _same((again.offsets, again.indices, again.scores), (hits.offsets, hits.indices, hits.scores))
 
 
+@pytest.mark.parametrize('dtype', DTYPES, ids=IDS)
+def test_a_ragged_last_slab_of_the_stored_row_loops(dtype):
+  """Several slabs, then a partial one, in the K loops over two stored rows: 130 items (two column tiles, the second with
+  2 live columns; three row blocks, the last with 2 rows), M = 7, d = 16, so K = 112 = 3.5 fp32 slabs = 1.75 16-bit slabs.
+  Item 7 has all-zero weights (the 1e-5 denominator), item 129 is an exact copy of item 3 (another tile, another row block).
+  pair_scores over 128-wide lists of 64-item blocks is held to the fp64 definition on the stored values within
+  gamma_K sum |f_g f_h| / |den| + 2^-22 |value|, gamma_K = K u / (1 - K u) with K = 112 and u = 2^-24: the worst case of
+  an fp32 sum of K exact products in any order, plus the scale multiply and the division (test_index_diverse_gpu.
+  _definition's formula: derived, not tuned).  neighbours and neighbour_range (threshold: the matrix's median, one of its
+  own values) have that matrix's bits and order."""
+  import numpy as np
+  from mmt_amd.search import VideoIndex
+  nv, m, d = 130, 7, 16
+  gamma = m * d * 2.0 ** -24 / (1 - m * d * 2.0 ** -24)
+  gen = torch.Generator(device=DEV).manual_seed(nv)
+  g, gw = torch.randn(nv, m, d, device=DEV, generator=gen), torch.rand(nv, m, device=DEV, generator=gen)
+  g[129], gw[129] = g[3], gw[3]
+  gw[7] = 0
+  index = VideoIndex(g, gw, dtype=dtype)
+  blocks = [torch.arange(b, min(nv, b + 64), device=DEV) for b in range(0, nv, 64)]
+  lists = torch.full((len(blocks) ** 2, 128), -1, device=DEV, dtype=torch.int64)
+  for i, bi in enumerate(blocks):
+    for j, bj in enumerate(blocks):
+      lists[i * len(blocks) + j, :bi.numel()] = bi
+      lists[i * len(blocks) + j, 64:64 + bj.numel()] = bj
+  sims = index.pair_scores(lists)
+  s = torch.empty(nv, nv, device=DEV, dtype=torch.float32)
+  for i, bi in enumerate(blocks):
+    for j, bj in enumerate(blocks):
+      s[bi[0]:bi[-1] + 1, bj[0]:bj[-1] + 1] = sims[i * len(blocks) + j, :bi.numel(), 64:64 + bj.numel()]
+  s = s.cpu()
+  assert not torch.isnan(s).any()
+  f = index.folded[:nv].cpu().float().double().numpy()
+  if index.scales is not None:
+    f = f * index.scales[:nv].cpu().double().numpy()[:, None]
+  w = index.weights[:nv].cpu().double().numpy()
+  den = w @ w.T
+  den[den == 0] = float(np.float32(1e-5))
+  value = (f @ f.T) / den
+  tol = gamma * (np.abs(f) @ np.abs(f).T) / np.abs(den) + 2.0 ** -22 * np.abs(value)
+  err = np.abs(s.double().numpy() - value)
+  print('%s: max |error| %.3g, max error / bound %.3g over %d pairs' % (dtype, err.max(), (err / tol.clip(1e-300)).max(),
+                                                                        err.size))
+  assert f.shape == (nv, m * d) and (err <= tol).all()
+  assert torch.equal(_bits(s[3]), _bits(s[129])) and torch.equal(_bits(s[:, 3].contiguous()), _bits(s[:, 129].contiguous()))
+  own = torch.arange(nv)
+  _same(index.neighbours(k=128), brute_neighbours(s, own, 128))
+  thr = float(s.median())
+  hits = index.neighbour_range(thr)
+  _same((hits.offsets, hits.indices, hits.scores), brute_range(s, own, torch.full((nv,), thr)))
+  assert 0 < int(hits.offsets[-1]) < nv * (nv - 1)
+
+
 def _thresholds(s, own):
   """One threshold per row, taken from S itself -- the row's sim to item (7 row + 3) % 300, which must then be hit unless
   it is the row's own item -- with rows 10 .. 19 at -inf (every item but the row's own) and 20 .. 29 at NaN (nothing)."""
