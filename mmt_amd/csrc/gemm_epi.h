@@ -11,19 +11,22 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 // erf-form GELU (model/bert.py:37-53) of a bf16-ROUNDED pre-activation, by table: the epilogues apply the activation to
 // the value they store (backward differentiates exactly what was applied), so its argument is one of 65536 bf16 numbers
-// and Phi(|x|) / gelu'(|x|) for the 2304 magnitudes in [2^-15, 8) are EXACT table entries (gelu_lut.h, double precision
-// rounded to fp32; smaller / larger magnitudes clamp: relative error < 1.3e-5 / none).  Per element: and, med3, LDS read,
-// sign fix, multiply -- the Abramowitz-Stegun form it replaces (|erf error| 1.5e-7) cost one v_rcp + one v_exp + a dozen
-// fma: ~45 of the ~110 issue slots of a 4-element sweep step, and the sweep is VALU-bound (tools/gemm2_budget.py r04).
+// and Phi(-|x|) / gelu'(|x|) for the 2304 magnitudes in [2^-15, 8) are EXACT table entries (gelu_lut.h, double precision
+// rounded to fp32; smaller / larger magnitudes clamp: relative error < 1.3e-5 / none).  The forward table holds the lower
+// tail u = Phi(-|x|): a negative argument takes x u, whose relative error is the entry's, a positive one x (1 - u) -- the
+// subtraction is harmless there (1 - u >= 1/2: every positive bf16 argument gets the result x fp32(Phi(x)) would give).  Per element:
+// and, med3, LDS read, sign fix, multiply -- the Abramowitz-Stegun form it replaces (|erf error| 1.5e-7) cost one v_rcp +
+// one v_exp + a dozen fma: ~45 of the ~110 issue slots of a 4-element sweep step, and the sweep is VALU-bound
+// (tools/gemm2_budget.py r04).
 __device__ __forceinline__ float gelu_lut_abs(const float* __restrict__ lut, unsigned b) {
   const unsigned mag = b & 0x7fffu;
   const unsigned idx = min(max(mag, (unsigned)MMT_GELU_LUT_LO), (unsigned)(MMT_GELU_LUT_LO + MMT_GELU_LUT_N - 1)) - MMT_GELU_LUT_LO;
   return lut[idx];
 }
-// x Phi(x) for x = the bf16 number with bits b (lut = the Phi table in LDS)
+// x Phi(x) for x = the bf16 number with bits b (lut = the Phi(-|x|) table in LDS)
 __device__ __forceinline__ float gelu_lut(const float* __restrict__ lut, unsigned b) {
-  const float t = gelu_lut_abs(lut, b);
-  return bf2f((bf16_t)b) * ((b & 0x8000u) ? 1.0f - t : t);
+  const float u = gelu_lut_abs(lut, b);
+  return bf2f((bf16_t)b) * ((b & 0x8000u) ? u : 1.0f - u);
 }
 // d/dx [x Phi(x)] (lut = the derivative table): g'(-x) = 1 - g'(x)
 __device__ __forceinline__ float gelu_grad_lut(const float* __restrict__ lut, unsigned b) {
