@@ -767,6 +767,29 @@ int mmt_search_self_range_fill(const void* a_rows, const float* a_weights, const
 int64_t mmt_row_expsum_workspace_ints64(int NQ, int NV);
 int mmt_search_row_expsum(const MmtSearchScan* scan, float beta, const float* xmax, int F, int64_t* ws, void* stream);
 
+/* The streaming schedule of the plain top-k scan (search_stream.hip), additive: one entry and its size function, nothing
+ * that exists changes and mmt_abi_version() stays 6.  It serves search.py's `search` on an index whose schedule is 'stream': the search
+ * of a handful of queries (a service answering one caption, or a few), where the gallery is read once and its bytes are
+ * the cost -- the same similarity and the same order as mmt_search_topk (reference: utils/util.py:38-68
+ * compress_predictions, trainer/trainer.py:411-437, utils/visualizer.py:74-92; similarity of model/model.py:789-837).
+ * mmt_search_topk_stream (subset, exclude, after; fp32, bf16, fp8; no norm, no sets: MMT_ERR_ARG): outputs, k, gates and
+ *   the rule for which slots are written exactly as mmt_search_topk.  THE CONTRACT: scores and indices are those of
+ *   mmt_search_topk for the same descriptor, BIT FOR BIT.  A (query, item) accumulator goes through the same MFMA sequence
+ *   (bf16 / fp8: K ascending in steps of 16, lane half h feeding k = kk + 8h .. + 7, one v_mfma_f32_32x32x16_bf16 per query
+ *   plane, hi then lo; fp32: K ascending in steps of 8, four v_mfma_f32_32x32x2_f32 with k = kk + 4h + u) and the same
+ *   epilogue expression (the `den += qw[m] * gw[m]` chain, 0 -> 1e-5, fp8: the rounded multiply by the scale first, then
+ *   num / den); the keys and the running top-k are shared, and the merge of the chunk lists is by rank as well, over the
+ *   lists whose heads can reach the answer (a rank is unique, so the output is that merge's).  Only the schedule differs:
+ *   a block holds 32 query rows, the gallery goes from memory straight to the registers of the lane that multiplies it, a
+ *   slab ahead, and never through LDS.  Meant for NQ <= 32; any NQ is taken, in tiles of 32 rows.
+ * mmt_topk_stream_workspace_keys: uint64, NQ * n_chunks * k with n_chunks a function of (NQ, NV) only, non-decreasing in
+ *   NV: the 512-item sweeps of the gallery cut into min(sweeps, max(512 / ceil(NQ / 32), ceil(sweeps / 8))) runs.
+ *   MMT_ERR_ARG if a size is out of range; for both entries that includes NV > INT_MAX - 512 (a sweep's last tile numbers up
+ *   to 511 items past NV, and an item number is an int).  MMT_ERR_ALIGN: q, q_lo, g or subset off a 16-byte boundary.  All refused on
+ *   the host before any launch.  No atomics; one writer per slot. */
+int64_t mmt_topk_stream_workspace_keys(int NQ, int NV, int k);
+int mmt_search_topk_stream(const MmtSearchScan* scan, int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
+
 /* Beside the scans.
  * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> the subset words, padding included: one ballot per 64
  *   items, one writer per word.

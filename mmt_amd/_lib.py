@@ -274,6 +274,9 @@ SIGNATURES = {
     # softmax over the gallery, additive: the descriptor, beta, xmax, F, the int64 workspace, the stream
     'mmt_row_expsum_workspace_ints64': (c_i64, [c_int, c_int]),
     'mmt_search_row_expsum': (c_int, [_SCAN, c_f32, c_vp, c_int, c_vp, c_vp]),
+    # the streaming schedule of the plain top-k scan, additive: mmt_search_topk's arguments, its own workspace size
+    'mmt_topk_stream_workspace_keys': (c_i64, [c_int, c_int, c_int]),
+    'mmt_search_topk_stream': (c_int, [_SCAN, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

@@ -74,20 +74,21 @@ __device__ __forceinline__ void tk_flush(uint64_t* c, int n, int k, int lane, ui
   for (int j = lane; j < k; j += 64) dst[j] = j < have ? c[j] : 0ull;
 }
 
-// Selection over the score tile: wave w owns rows 16w .. 16w + 15; columns in increasing index order.  MASKED: only the
+// Selection over the score tile: wave w owns rows 16w .. 16w + 15 (ROWS / 4 of them); columns in increasing index order.  MASKED: only the
 // columns whose bit is set in m0 (columns 0 .. 63) / m1 (64 .. 127) are candidates, less the row's exclusions sEx[row][E]
 // (item numbers, -1 = none; lane e holds exclusion e, and the few that fall into this tile clear their bit).  The score
 // tile is the unmasked kernel's, so a returned score has the bits the unmasked search gives that item.  AFTER (the paged
 // search: the argument blocks with kAfter): sB [TK_Q] holds one bound per row, a position in the search's order, and only
 // keys strictly below it are candidates: 2^64 - 1 = no cursor (no score gives that key), 0 = the row is exhausted, and
-// tk_key(a, first) + 1 = everything that scores below a, and at score a the items from number `first` on.
-template <bool MASKED = false, bool AFTER = false>
+// tk_key(a, first) + 1 = everything that scores below a, and at score a the items from number `first` on.  ROWS: the rows of
+// the block's score tile, a quarter per wave (TK_Q, or the streaming schedule's 32: search_stream.hip).
+template <bool MASKED = false, bool AFTER = false, int ROWS = TK_Q>
 __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, int* sN, uint64_t* sT, int k, int rows_live,
                                                int g0, int g_end, int wave, int lane, uint64_t m0 = 0, uint64_t m1 = 0,
                                                const int* sEx = nullptr, int E = 0, const uint64_t* sB = nullptr) {
   const int cap = k + 64;
-  for (int rr = 0; rr < TK_Q / 4; ++rr) {
-    const int row = wave * (TK_Q / 4) + rr;
+  for (int rr = 0; rr < ROWS / 4; ++rr) {
+    const int row = wave * (ROWS / 4) + rr;
     if (row >= rows_live) break;
     int n = sN[row];
     uint64_t thr = sT[row];

@@ -226,6 +226,22 @@ taken without the cursor, so every page of a query makes the same choice); not w
 `search_groups` has no cursor.  `search_deep` is host code: ceil(w / page) pages of `search`, w = min(depth, candidates),
 each continuing from the last column of the one before, concatenated to [NQ, w].
 
+    index.schedule = 'stream'                                          # a property of the index: None, 'tile' or 'stream'
+    scores, indices = index.search(q, qw, k=10, subset=..., exclude=..., after=...)
+    coarse.schedule = 'stream'; scores, indices = fine.search_refined(q, qw, coarse, k=10)
+
+Not a further question but a second SCHEDULE of the first: the launches above are tuned for evaluation, thousands of queries
+at once; a service answers one caption, or a few, at a time, and then the scan is a matter of reading the gallery once.
+On an index whose `schedule` is 'stream', `search` sends its plain top-k pass to mmt_search_topk_stream: a block holds 32 query rows, a gallery row goes
+from memory straight into the registers of the lane that multiplies it, a whole slab ahead, and never through LDS; the
+queries go through LDS double-buffered, one barrier per slab.  Meant for NQ <= 32; any NQ is taken.  The results are
+`search`'s to the bit on all three storage dtypes and both index classes -- the same MFMA sequence per pair, the same
+epilogue expression, the same keys and running top-k, a merge by rank that looks at the lists' heads first -- so the
+schedule is a matter of speed alone (one query over 262 144 items in 0.44 ms on bf16, 0.28 ms on fp8).  It combines with
+subset=, exclude= and after=; norm=, dynamic=, pooling= and item_pooling= are refused by name.  Opt-in: an index starts
+with schedule None, None and 'tile' take exactly the calls they always took, and nothing chooses a schedule by NQ.  It
+is a setting of the index and not an argument of `search`, whose parameter list stays what it was.
+
     scores, rows = index.reverse_search(q, qw, k=10)                       # [num_items, k'], k' = min(k, NQ), k <= MAX_RK = 32
     norm = index.csls_norm(bank_embds, bank_weights, k=10, dynamic=False)  # HubNorm: kind='csls', .k, .beta == 2.0, .lse = r
     scores, indices = index.search(q, qw, k=10, norm=norm)                 # every norm= consumer, unchanged
@@ -800,12 +816,15 @@ class _Scan:
   [NQ, E] exclusions, checked), norm (a HubNorm / ShardedHubNorm: every query normalised), pooling (a QueryPooling) and
   item_pooling (an ItemPooling / ShardedItemPooling), each None unless given and already checked against the index, and
   after (the cursor of a paged `search`, checked: scores float32 [NQ] and first int64 [NQ], the lowest item number still
-  admitted at that score in the index's own numbers, -1 where the score is a sentinel: _limits).  A public call builds it
+  admitted at that score in the index's own numbers, -1 where the score is a sentinel: _limits), and stream: whether the
+  top-k pass takes the streaming schedule (`search` on an index whose schedule is 'stream'; every shard's view keeps it).  A public call builds it
   once and every internal call takes it whole; the sizes that depend on which options are there are answered here."""
 
-  def __init__(self, subset=None, ex=None, norm=None, pooling=None, item_pooling=None, after=None):
+  def __init__(self, subset=None, ex=None, norm=None, pooling=None, item_pooling=None, after=None, stream=False):
     self.subset, self.ex, self.norm, self.pooling, self.item_pooling = subset, ex, norm, pooling, item_pooling
     self.after = after
+    # `search` on an index set to 'stream': the top-k pass goes to mmt_search_topk_stream (checked: no norm, no sets)
+    self.stream = stream
     # MmtSearchScan.sets: whose rows come in sets
     self.sets = (_lib.SEARCH_SETS_ITEM if item_pooling is not None else
                  _lib.SEARCH_SETS_QUERY if pooling is not None else _lib.SEARCH_SETS_NONE)
@@ -821,7 +840,7 @@ class _Scan:
 
   def at(self, after):
     """The same scan from another cursor (None = from the top): the pages of `search_deep`."""
-    return _Scan(self.subset, self.ex, self.norm, self.pooling, self.item_pooling, after)
+    return _Scan(self.subset, self.ex, self.norm, self.pooling, self.item_pooling, after, self.stream)
 
   def rows(self, q):
     """The rows of the outputs: one per query, or with a pooling one per query set."""
@@ -852,7 +871,7 @@ class _Scan:
     device = index.shards[s].device
     ex = None if self.ex is None else index._local(self.ex, s).to(device)
     after = None if self.after is None else (self.after[0].to(device), index._first(self.after[1], s).to(device))
-    return _Scan(part(self.subset), ex, part(self.norm), self.pooling, part(self.item_pooling), after)
+    return _Scan(part(self.subset), ex, part(self.norm), self.pooling, part(self.item_pooling), after, self.stream)
 
 
 def _column_groups(src, outs, r0, r1):
@@ -1208,6 +1227,36 @@ class _Index:
       raise ValueError('search: after (scores [NQ], items [NQ]) expected, got %s and %s' % (
           tuple(after[0].shape), tuple(after[1].shape)))
 
+  _schedule = None   # a class default: an index made without a constructor call has the tile schedule too
+
+  @property
+  def schedule(self):
+    """Which schedule `search` gives its plain top-k pass: None or 'tile' -- the launches tuned for thousands of queries,
+    what every call has always taken -- or 'stream', the schedule for a handful of queries (`search`'s docstring; DESIGN
+    9.21).  A setting of the index, not an argument of the call: a service sets it once on the index it serves from.
+    It is plain state on a shared object: setting it is not synchronised with calls in flight on other threads, so a
+    process that serves online queries and runs evaluation batches from the same stored items at the same time should
+    not toggle it between calls -- the stored tensors are shared by a second index object made for the other schedule.
+    Assigning anything else is a ValueError, and the index keeps what it had."""
+    return self._schedule
+
+  @schedule.setter
+  def schedule(self, value):
+    if value is not None and (not isinstance(value, str) or value not in ('tile', 'stream')):
+      raise ValueError("schedule must be None, 'tile' or 'stream', got %r" % (value,))
+    self._schedule = value
+
+  def _streams(self, who, norm, dynamic, pooling, item_pooling):
+    """Whether a `search` with these options takes the streaming schedule: it has no kernels for the querybank
+    normalisation or for sets, and an index set to it says so by the argument's name instead of answering on the other
+    schedule."""
+    if self._schedule != 'stream':
+      return False
+    for name, given in (('norm', norm), ('dynamic', dynamic), ('pooling', pooling), ('item_pooling', item_pooling)):
+      if given is not None:
+        raise ValueError("%s: the index's schedule 'stream' does not combine with %s=" % (who, name))
+    return True
+
   def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None, pooling=None,
              item_pooling=None, after=None):
     """Queries (NQ, M, d) / (NQ, M), or the text layout (B, M, C, d) / (B, C, M) -> (scores [NQ, k'] float32,
@@ -1246,16 +1295,36 @@ class _Index:
     with subset=, exclude=, norm= and dynamic=; under the dynamic rule a query's plain top-1 is taken WITHOUT the cursor,
     so the choice is the same on every page.  after= with pooling= or item_pooling= is a ValueError; `search_groups` has
     no cursor (a group's representative may lie before a position while other members lie after it).  after=None takes
-    exactly the calls above."""
+    exactly the calls above.
+    The index's `schedule` (a property; None at first): None or 'tile' take exactly the calls above.  With
+    index.schedule = 'stream' this call sends the top-k pass through the streaming schedule
+    (mmt_search_topk_stream), built for a handful of queries -- a service answering one caption, or a few: it is MEANT FOR
+    NQ <= 32, where the scan is a matter of reading the gallery once, and takes any NQ, the rows going through in tiles of
+    32.  The results are `search`'s TO THE BIT, scores and indices, on all three storages: a pair's accumulator goes
+    through the same instruction sequence and the same epilogue expression, keys and running top-k are shared, and the
+    merge is by rank as well (measured over 262 144 items, k = 10: faster than 'tile' at every NQ from 1 to 64).
+    Combines with subset=, exclude= and after=; with norm= (and so dynamic=), pooling= or item_pooling= it is a ValueError
+    naming the argument, raised before anything is scored (any other value of the property is refused when it is
+    assigned).  It is the schedule of THIS call alone (and of the coarse search of `search_refined`): `search_deep`, `search_groups`,
+    the shortlist search of `search_diverse` and the searches inside `hub_norm`,
+    `query_lse` and their kin keep the tile schedule.  ShardedVideoIndex: the property of the sharded index decides and
+    every shard takes it; the shard merge is the same."""
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
       raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
+    return self._search_call(self._streams('search', norm, dynamic, pooling, item_pooling), embds, weights, k, subset,
+                             exclude, norm, dynamic, pooling, item_pooling, after)
+
+  def _search_call(self, stream, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None, pooling=None,
+                   item_pooling=None, after=None):
+    """`search` behind its check of k and of the schedule: stream = whether the top-k pass takes the streaming schedule.
+    Host code that builds on `search` without taking part in the schedule (`search_diverse`) calls this with False."""
     if self.num_items == 0:
       raise ValueError('search: the index holds no items')
     if after is not None:
       self._after(after, pooling, item_pooling)
     q, qw, dynamic = self._scan_args('search', embds, weights, norm, dynamic, subset, exclude, pooling, item_pooling)
     ex, cursor = _limits(exclude, after, q.shape[0], self.num_items)
-    scan = _Scan(subset, ex, norm, pooling, item_pooling, cursor)
+    scan = _Scan(subset, ex, norm, pooling, item_pooling, cursor, stream)
     return self._dynamic(dynamic, q, qw, scan, lambda scan: self._search(q, qw, k, scan))
 
   def search_deep(self, embds, weights, depth, page=DEEP_PAGE, subset=None, exclude=None, norm=None, dynamic=None):
@@ -1382,8 +1451,9 @@ class _Index:
     this one -> (scores, indices) [NQ, min(k, shortlist, the coarse list's width)], scores with this index's bits.
     coarse: a VideoIndex or ShardedVideoIndex with this index's num_items, num_experts and dim on this index's (primary)
     device; shortlist an int in 1 .. MAX_K; subset and exclude are `coarse`'s (a subset from ITS `subset`) and are checked
-    by it.  The two indexes are TAKEN to hold the same items under the same numbers: that cannot be checked here.  Host
-    code only."""
+    by it.  The two indexes are TAKEN to hold the same items under the same numbers: that cannot be checked here.
+    The coarse search takes `coarse`'s own schedule: with coarse.schedule = 'stream' this is the online pipeline, an fp8
+    shortlist streamed for a few queries and then re-scored, and the result is the same to the bit.  Host code only."""
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
       raise ValueError('search_refined: k must be an int in 1..%d, got %r' % (MAX_K, k))
     if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not 1 <= shortlist <= MAX_K:
@@ -1506,7 +1576,8 @@ class _Index:
     (scores, indices, values) [NQ, min(k, the list's width)].  shortlist an int in 1 .. MAX_K; coarse: None, or a
     VideoIndex / ShardedVideoIndex TAKEN to hold the same items under the same numbers (same num_items, num_experts, dim
     and device is all that can be checked) -- typically a float8_e4m3fn one; subset and exclude are the searching
-    index's and are checked by it.  Relevance and item-item similarity are this index's.  Out of scope as `diversify`."""
+    index's and are checked by it.  Relevance and item-item similarity are this index's.  The shortlist search keeps the
+    tile schedule whatever the searching index's `schedule` says.  Out of scope as `diversify`."""
     self._diverse_args('search_diverse', k, lam, unsupported)
     if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not 1 <= shortlist <= MAX_K:
       raise ValueError('search_diverse: shortlist must be an int in 1..%d, got %r' % (MAX_K, shortlist))
@@ -1520,7 +1591,8 @@ class _Index:
         raise ValueError('search_diverse: the coarse index is on %s, this one on %s' % (coarse.device, self.device))
     if self.num_items == 0:
       raise ValueError('search_diverse: the index holds no items')
-    _, shortlisted = (self if coarse is None else coarse).search(embds, weights, k=shortlist, subset=subset, exclude=exclude)
+    # `search` without the index's schedule: the diversified search is not one of the calls that take it
+    _, shortlisted = (self if coarse is None else coarse)._search_call(False, embds, weights, shortlist, subset, exclude)
     return self.diversify(embds, weights, shortlisted, k, lam)
 
   def _self_args(self, who, items, subset, source, unsupported, k=...):
@@ -1997,7 +2069,9 @@ class VideoIndex(_Index):
     outs = _lists(2 if grouping is None else 3, self.device, scan.rows(q), min(k, nv), vacant=scan.ex is not None or paged)
     if nq == 0:
       return outs
-    workspace = getattr(L, _WORKSPACES[scan.sets][0])
+    topk, workspace = L.mmt_search_topk, getattr(L, _WORKSPACES[scan.sets][0])
+    if scan.stream:   # behind `search`'s checks: no norm, no sets; with a grouping nobody asks for it
+      topk, workspace = L.mmt_search_topk_stream, L.mmt_topk_stream_workspace_keys
     bounds = None
     with torch.cuda.device(self.device):
       if paged:
@@ -2010,8 +2084,8 @@ class VideoIndex(_Index):
         desc, dims, (o0, o1), _keep = self._describe(scan, q, qw, r0, r1, bounds)
         ws = torch.empty(workspace(*dims, k), device=self.device, dtype=torch.int64)
         if grouping is None:
-          check(L.mmt_search_topk(desc, k, ops._p(ws), ops._p(outs[0][o0:o1]), ops._p(outs[1][o0:o1]), ops._stream()),
-                'mmt_search_topk')
+          check(topk(desc, k, ops._p(ws), ops._p(outs[0][o0:o1]), ops._p(outs[1][o0:o1]), ops._stream()),
+                'mmt_search_topk_stream' if scan.stream else 'mmt_search_topk')
         else:
           check(L.mmt_search_topk_groups(desc, k, ops._p(grouping.ids), ops._p(ws), ops._p(outs[0][o0:o1]),
                                          ops._p(outs[1][o0:o1]), ops._p(outs[2][o0:o1]), ops._stream()),

@@ -117,7 +117,13 @@ profiles/search_bench.json) under 'neighbours'.
 --lse times the softmax over 262 144 items (beta = 20) at NQ = 64 and 4 096 on a float32, a bf16 and an fp8 index: the sum
 pass alone (mmt_search_row_expsum with xmax given) and `query_lse` whole, beside search(k = 1) and search(k = 10) on the same
 index, and on float32 the route through the matrix (the similarity kernel + torch.logsumexp) with its peak memory.  --runs
-rounds, every variant once per round, interleaved; median and spread.  Default output profiles/search_lse_bench.json."""
+rounds, every variant once per round, interleaved; median and spread.  Default output profiles/search_lse_bench.json.
+
+--stream times `search` on an index whose schedule is 'stream' against the same index with 'tile' -- the same build's tile kernels, whose code this
+schedule leaves as it was -- with k = 10 over 262 144 items at NQ = 1, 8, 32 and 64 on a float32, a bf16 and an fp8 index:
+--runs rounds, the two schedules interleaved, on device events; median and spread, the index bytes over the time (TB/s),
+the device time of the scan and the merge kernel separately (one profiled call), at NQ = 1 the wall time of a call with its
+synchronisation, and whether the two results are the same bits.  Default output profiles/search_stream_bench.json."""
 import argparse
 import json
 import math
@@ -634,6 +640,77 @@ def fp8_mode(a, dev):
   return row
 
 
+def kernel_times(fn):
+  """Device time of every kernel of one call of fn, by kernel name (torch.profiler), in seconds."""
+  from torch.profiler import ProfilerActivity, profile
+  fn()
+  torch.cuda.synchronize()
+  with profile(activities=[ProfilerActivity.CUDA]) as prof:
+    fn()
+    torch.cuda.synchronize()
+  out = {}
+  for ev in prof.events():
+    if ev.device_type.name != 'CPU' and 'Memcpy' not in ev.name and 'Memset' not in ev.name:
+      out[ev.name] = out.get(ev.name, 0.0) + ev.device_time_total / 1e6
+  return out
+
+
+def stream_mode(a, dev):
+  """`search` with index.schedule = 'stream' against 'tile' in one session: k = 10 over NV = 262 144 items at NQ = 1, 8, 32 and
+  64 on a float32, a bf16 and an fp8 index of the same gallery."""
+  import time
+  nv, chunk = SHAPES['S3'][1], 8192
+  gen = torch.Generator(device=dev).manual_seed(0)
+  nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
+  dtypes = {'float32': torch.float32, 'bfloat16': torch.bfloat16, 'float8_e4m3fn': torch.float8_e4m3fn}
+  idx = {n: VideoIndex.empty(nv, M, D, dev, dtype=t) for n, t in dtypes.items()}
+  for at in range(0, nv, chunk):
+    g = nrm(torch.randn(chunk, M, D, device=dev, generator=gen))
+    gw = torch.softmax(torch.randn(chunk, M, device=dev, generator=gen), -1)
+    for index in idx.values():
+      index.add(g, gw)
+  q = nrm(torch.randn(64, M, D, device=dev, generator=gen) + 0.3 * g[:64])
+  qw = torch.softmax(torch.randn(64, M, device=dev, generator=gen), -1)
+  row = {'NV': nv, 'index_bytes': {n: idx[n].nbytes for n in idx}, 'cells': {}}
+  for n in dtypes:
+    for nq in (1, 8, 32, 64):
+      def call(n, nq, sched):
+        idx[n].schedule = sched          # a property of the index; a plain assignment, no device work
+        return idx[n].search(q[:nq], qw[:nq], k=K)
+      fns = {sched: (lambda n=n, nq=nq, sched=sched: call(n, nq, sched)) for sched in ('tile', 'stream')}
+      ts, out = {sched: [] for sched in fns}, {}
+      for _ in range(a.runs):          # interleaved: drift hits both alike
+        for sched, fn in fns.items():
+          t, _, _, out[sched] = timed(fn, a.min_seconds)
+          ts[sched].append(t)
+      cell = {'bit_identical': bool(torch.equal(out['tile'][1], out['stream'][1]) and
+                                    torch.equal(out['tile'][0].view(torch.int32), out['stream'][0].view(torch.int32)))}
+      for sched, fn in fns.items():
+        med = float(np.median(ts[sched]))
+        cell[sched] = dict(seconds_median=med, seconds_spread=max(ts[sched]) - min(ts[sched]), seconds_runs=ts[sched],
+                           gallery_tbytes_per_second=idx[n].nbytes / med / 1e12)
+        try:
+          cell[sched]['kernel_seconds'] = kernel_times(fn)
+        except Exception as e:  # the profiler is an instrument: a build without it still gives the timings above
+          cell[sched]['kernel_seconds'] = 'unavailable: %s' % type(e).__name__
+        if nq == 1:                    # a served query: the host's share is part of it
+          torch.cuda.synchronize()
+          t0 = time.perf_counter()
+          for _ in range(50):
+            fn()
+            torch.cuda.synchronize()
+          cell[sched]['wall_seconds_per_call'] = (time.perf_counter() - t0) / 50
+      t, st = cell['tile'], cell['stream']
+      cell['summary'] = dict(tile_over_stream=t['seconds_median'] / st['seconds_median'],
+                             spreads_combined=t['seconds_spread'] + st['seconds_spread'],
+                             stream_wins=t['seconds_median'] - st['seconds_median'] > t['seconds_spread'] + st['seconds_spread'])
+      row['cells']['%s/nq%d' % (n, nq)] = cell
+      print('%s nq=%d: tile %.3f ms, stream %.3f ms (%.2f TB/s), identical %s' % (
+          n, nq, 1e3 * t['seconds_median'], 1e3 * st['seconds_median'], st['gallery_tbytes_per_second'], cell['bit_identical']),
+          file=sys.stderr)
+  return row
+
+
 def composed_rescore(index, q, qw, cand, k):
   """What `rescore` replaces, from the public calls: `target_scores` of the candidates (MAX_T columns per launch), then
   `search`'s order in torch -- two stable sorts, by item and then by descending score with -0 as +0 and none last.
@@ -1024,6 +1101,8 @@ def main():
                   'search(k = 10) (no other mode flag)')
   ap.add_argument('--fp8', action='store_true', help='time the fp8-stored index against the bf16-stored one: search(k = 10) '
                   'at NQ = 64 and 4096 over 262 144 items, and add of 8 192 items (no other mode flag)')
+  ap.add_argument('--stream', action='store_true', help="time search with index.schedule = 'stream' against 'tile' (k = 10) at "
+                  'NQ = 1, 8, 32, 64 on a float32, a bf16 and an fp8 index of 262 144 items; no other mode')
   ap.add_argument('--shapes', default='S1,S2,S3')
   ap.add_argument('--out', default=None)
   ap.add_argument('--min-seconds', type=float, default=0.5)
@@ -1159,6 +1238,16 @@ def main():
     res.update(rescore_mode(a, dev))
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
                                 'search_rescore_bench.json')
+    with open(out, 'w') as f:
+      json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return
+  if a.stream:
+    res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'stream', 'runs': a.runs,
+           'min_seconds': a.min_seconds}
+    res.update(stream_mode(a, dev))
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                'search_stream_bench.json')
     with open(out, 'w') as f:
       json.dump(res, f, indent=1)
     print(json.dumps(res))
