@@ -790,6 +790,37 @@ int mmt_search_row_expsum(const MmtSearchScan* scan, float beta, const float* xm
 int64_t mmt_topk_stream_workspace_keys(int NQ, int NV, int k);
 int mmt_search_topk_stream(const MmtSearchScan* scan, int k, uint64_t* ws, float* scores, int64_t* index, void* stream);
 
+/* Per-query attribute filters, additive: five entries, nothing that exists changes, MmtSearchScan stays 21 fields / 128
+ * bytes and mmt_abi_version() stays 6.  Every stored item carries one 64-bit tag word, tags [NV]; every query row three
+ * 64-bit masks, where [NQ][3] = (all_of, none_of, any_of).  Item g is a candidate of row q iff
+ *   (tags[g] & all_of) == all_of  and  (tags[g] & none_of) == 0  and  (any_of == 0 or (tags[g] & any_of) != 0)
+ * -- plain 64-bit integer operations on bit patterns (bit 63 is an ordinary bit); three zero masks admit every item.  The
+ * predicate is ANDed with the descriptor's subset, exclusions and cursor and acts at selection and counting only: a
+ * returned score has the bits the unfiltered entry gives the pair.  A 128-item tile in which no (live row, allowed item)
+ * pair passes is skipped before its K loop on the tile schedule (an exact, block-uniform test); the streaming schedule
+ * filters in the selection alone.  Each entry takes the unfiltered entry's arguments with tags and where right behind the
+ * descriptor, and its workspace, outputs, written slots and gates:
+ *   mmt_search_topk_where         as mmt_search_topk          (subset, exclude, after; fp32, bf16, fp8)
+ *   mmt_search_topk_stream_where  as mmt_search_topk_stream   (subset, exclude, after; fp32, bf16, fp8)
+ *   mmt_search_count_where        as mmt_search_count         (subset; fp32, bf16, fp8): thresholds from the unfiltered
+ *                                 mmt_search_thresholds, so a target is scored whether or not it passes and counts itself
+ *                                 only if it does
+ *   mmt_search_range_count_where  as mmt_search_range_count   (subset; fp32, bf16, fp8)
+ *   mmt_search_range_fill_where   as mmt_search_range_fill    (subset; fp32, bf16, fp8)
+ * MMT_ERR_ARG: a norm, sets, any other part the entry does not take, a null tags or a null where, and the unfiltered
+ * entry's own refusals -- all before the alignment check (MMT_ERR_ALIGN: q, q_lo, g or subset off a 16-byte boundary).  All
+ * refused on the host before any launch.  No atomics; one writer per slot. */
+int mmt_search_topk_where(const MmtSearchScan* scan, const uint64_t* tags, const uint64_t* where, int k, uint64_t* ws,
+                          float* scores, int64_t* index, void* stream);
+int mmt_search_topk_stream_where(const MmtSearchScan* scan, const uint64_t* tags, const uint64_t* where, int k, uint64_t* ws,
+                                 float* scores, int64_t* index, void* stream);
+int mmt_search_count_where(const MmtSearchScan* scan, const uint64_t* tags, const uint64_t* where, const float* thr, int T,
+                           int32_t* ws, int32_t* greater, int32_t* equal, void* stream);
+int mmt_search_range_count_where(const MmtSearchScan* scan, const uint64_t* tags, const uint64_t* where, const float* thr,
+                                 int32_t* ws, int64_t* row_counts, void* stream);
+int mmt_search_range_fill_where(const MmtSearchScan* scan, const uint64_t* tags, const uint64_t* where, const float* thr,
+                                const int32_t* ws, const int64_t* offsets, int64_t* indices, float* scores, void* stream);
+
 /* Beside the scans.
  * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> the subset words, padding included: one ballot per 64
  *   items, one writer per word.

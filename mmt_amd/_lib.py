@@ -277,6 +277,13 @@ SIGNATURES = {
     # the streaming schedule of the plain top-k scan, additive: mmt_search_topk's arguments, its own workspace size
     'mmt_topk_stream_workspace_keys': (c_i64, [c_int, c_int, c_int]),
     'mmt_search_topk_stream': (c_int, [_SCAN, c_int, c_vp, c_vp, c_vp, c_vp]),
+    # per-query attribute filters, additive: the unfiltered entry's arguments with tags [NV] and where [NQ][3] behind the
+    # descriptor
+    'mmt_search_topk_where': (c_int, [_SCAN, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_topk_stream_where': (c_int, [_SCAN, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_count_where': (c_int, [_SCAN, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_range_count_where': (c_int, [_SCAN, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_range_fill_where': (c_int, [_SCAN, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

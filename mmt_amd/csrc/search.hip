@@ -34,6 +34,10 @@
 //   <., Tk*AfterArgs>, <., NmTopkAfterArgs> : the masked and normalised kernels with a cursor per query row (the paged search,
 //                                      mmt_search_topk [after]): the selection also declines every key at or above the row's
 //                                      bound (tk_tile_select<true, true>), one more compare on the same score tile.
+//   <., Tk*WhereArgs>                : the paged kernels with the per-query attribute filter (mmt_search_topk_where): a tag
+//                                      word per item, three masks per row, one more term of the selection's `live` per row
+//                                      (tk_tile_select<true, true, TK_Q, true>), and a tile in which no row has a candidate
+//                                      skipped before its K loop (tk_tile_where_any).
 // The argument blocks stay separate types with their layouts as they are: a field appended to TkArgs moves the hidden
 // kernel arguments behind it and changes the unmasked code (profiles/search_subset_kernel_identity.txt).
 //
@@ -131,6 +135,28 @@ struct NmTopkAfterArgs : NmTopkArgs {  // as TkAfterArgs
   static constexpr bool kAfter = true;
 };
 
+// The filtered search (mmt_search_topk_where): the paged blocks with a tag word per item and three masks per query row
+// behind them (search_scan.h: tk_tag_pass), again in types of their own.  One instantiation per storage serves every
+// combination of subset, exclusions and cursor: `after` may be null here, and every live row then gets the bound
+// 2^64 - 1, which no key reaches.
+struct TkWhereArgs : TkAfterArgs {
+  const uint64_t* tags;     // [NV]
+  const uint64_t* where;    // [NQ][3]: all_of, none_of, any_of
+  static constexpr bool kWhere = true;
+};
+
+struct TkBf16WhereArgs : TkBf16AfterArgs {  // as TkWhereArgs
+  const uint64_t* tags;
+  const uint64_t* where;
+  static constexpr bool kWhere = true;
+};
+
+struct TkFp8WhereArgs : TkFp8AfterArgs {  // as TkWhereArgs
+  const uint64_t* tags;
+  const uint64_t* where;
+  static constexpr bool kWhere = true;
+};
+
 // One block of the fused scan: 64 queries x one gallery chunk -> the chunk's sorted k best per query in the workspace.
 // Args = TkArgs, TkBf16Args (kMask = TK_MASK_NONE), their masked forms or NmTopkArgs (TK_MASK_NULLABLE: subset bitmap,
 // may be null, and per-query exclusions, E = 0 allowed), or one of those with a cursor per row (kAfter).
@@ -140,6 +166,8 @@ __global__ __launch_bounds__(256) void topk_scan_kernel(Args a) {
   constexpr bool NORM = Args::kNorm;
   constexpr bool AFTER = TkAfter<Args>::value;
   static_assert(!AFTER || MASK != TK_MASK_NONE, "the blocks with a cursor extend the masked ones");
+  constexpr bool WHERE = TkWhere<Args>::value;
+  static_assert(!WHERE || (AFTER && !NORM), "the filtered blocks extend the paged ones of the plain score");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int kUnion = BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -165,18 +193,45 @@ __global__ __launch_bounds__(256) void topk_scan_kernel(Args a) {
   uint64_t* sB = nullptr;                                     // paged: [TK_Q] bounds, behind the exclusions
   if constexpr (AFTER) {
     sB = (uint64_t*)(sEx + TK_Q * a.E);
-    const uint64_t mine = q0 + lane < a.NQ ? a.after[q0 + lane] : 0ull;  // every wave reads the block's 64 bounds
+    uint64_t mine;  // every wave reads the block's 64 bounds
+    if constexpr (WHERE) mine = q0 + lane < a.NQ ? (a.after ? a.after[q0 + lane] : ~0ull) : 0ull;  // filtered: a null cursor
+    else mine = q0 + lane < a.NQ ? a.after[q0 + lane] : 0ull;
     if (wave == 0) sB[lane] = mine;                                       // read behind the barriers of tk_tile
     // block-uniform (the four waves hold the same 64 values), before any barrier: every row of the block is exhausted --
     // no tile is scored, and the flush below writes the empty lists
     if (!__ballot(mine != 0ull)) g_stop = g_begin;
   }
+  uint64_t* sW = nullptr;                                     // filtered: [TK_Q][3] masks, behind the bounds
+  TkWhereGate gate;                                           // what the rows' masks share, the tags a tile ahead
+  TkTagStream stream;
+  if constexpr (WHERE) {
+    sW = sB + TK_Q;
+    tk_load_where<TK_Q>(sW, a.where, a.NQ, q0, tid);
+    gate.template init<TK_Q>(a.where, a.NQ, q0, lane);
+    stream.init(a.tags, g_begin, g_end, lane);
+    __syncthreads();  // read by the gate of the first tile
+  }
   for (int g0 = g_begin; g0 < g_stop; g0 += TK_G) {
+    uint64_t t0 = 0, t1 = 0;
+    if constexpr (WHERE) stream.next(a.tags, g0, g_end, lane, t0, t1);  // before any skip: the next tile's are asked for
     uint64_t m0 = ~0ull, m1 = ~0ull;
     if constexpr (MASK != TK_MASK_NONE)
       if (a.subset && !tk_tile_mask(a.subset, g0, m0, m1)) continue;  // block-uniform: nothing of this tile is allowed
+    if constexpr (WHERE) {
+      // block-uniform: no live row has a candidate in this tile (subset and filter; exclusions and cursor play no part)
+      if (!tk_tile_where_any<TK_Q>(gate, sW, a.NQ - q0, t0, t1, g0 + lane < g_end && ((m0 >> lane) & 1ull),
+                                   g0 + 64 + lane < g_end && ((m1 >> lane) & 1ull), wave))
+        continue;
+    }
     tk_tile<BF16, NORM>(a, smem, sS, sQw, q0, [=](int r) { return g0 + r < g_end ? g0 + r : -1; }, tid, wq, wg, l31, h);
-    if constexpr (AFTER)
+    if constexpr (WHERE) {
+      if (gate.uniform)  // block-uniform: one predicate for all rows is two more mask words, and the paged selection runs
+        tk_tile_select<true, true>(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane, m0 & __ballot(gate.common(t0)),
+                                   m1 & __ballot(gate.common(t1)), sEx, a.E, sB);
+      else
+        tk_tile_select<true, true, TK_Q, true>(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane, m0, m1, sEx, a.E, sB,
+                                               sW, t0, t1);
+    } else if constexpr (AFTER)
       tk_tile_select<true, true>(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane, m0, m1, sEx, a.E, sB);
     else if constexpr (MASK != TK_MASK_NONE)
       tk_tile_select<true>(sS, sC, sN, sT, a.k, a.NQ - q0, g0, g_end, wave, lane, m0, m1, sEx, a.E);
@@ -284,6 +339,8 @@ size_t tk_state_lds(int k) { return TK_QW_BYTES + TK_Q * (4 + 8) + (size_t)TK_Q 
 size_t tk_exclude_lds(int E) { return (size_t)TK_Q * E * 4; }
 // ... and behind those, the paged kernels' bounds [TK_Q]
 constexpr size_t kAfterLds = (size_t)TK_Q * 8;
+// ... and behind those, the filtered kernels' masks [TK_Q][3]
+constexpr size_t kWhereLds = TK_WHERE_BYTES(TK_Q);
 size_t tk_select_lds(int k) { return (size_t)4 * (k + 64) * 8; }
 
 // The k = 128 footprint of the fused kernels is over the 64 KiB default.
@@ -306,14 +363,25 @@ void tk_topk_lds_limits() {
                        {(const void*)topk_scan_kernel<true, NmTopkAfterArgs>, bf16 + ex + kAfterLds}});
 }
 
+void tk_where_lds_limits() {
+  static bool done[64] = {};
+  const size_t f32 = TK_UNION_BYTES + tk_state_lds(TK_MAXK), bf16 = TKB_UNION_BYTES + tk_state_lds(TK_MAXK);
+  const size_t more = tk_exclude_lds(TK_MAXE) + kAfterLds + kWhereLds;
+  tk_lds_limits(done, {{(const void*)topk_scan_kernel<false, TkWhereArgs>, f32 + more},
+                       {(const void*)topk_scan_kernel<true, TkBf16WhereArgs>, bf16 + more},
+                       {(const void*)topk_scan_kernel<true, TkFp8WhereArgs>, bf16 + more}});
+}
+
 // The fused search behind mmt_search_topk (Args = TkMaskedArgs, TkBf16MaskedArgs, TkFp8MaskedArgs or NmTopkArgs, or one of
 // those with a cursor; the descriptor has passed tk_scan_gate and carries the parts Args stands for): gate, fill, the
-// chunk scan and the merge.  Without subset, exclusions, norm and cursor the unmasked instantiation runs.
+// chunk scan and the merge.  Without subset, exclusions, norm and cursor the unmasked instantiation runs.  tags, where: the
+// filtered blocks' (mmt_search_topk_where: Args = Tk*WhereArgs, whose one instantiation takes every combination).
 template <bool BF16, class Args>
-int tk_search(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_t* index, void* stream) {
-  constexpr bool AFTER = TkAfter<Args>::value, FP8 = TkFp8<Args>::value;
+int tk_search(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_t* index, void* stream,
+              const uint64_t* tags = nullptr, const uint64_t* where = nullptr) {
+  constexpr bool AFTER = TkAfter<Args>::value, FP8 = TkFp8<Args>::value, WHERE = TkWhere<Args>::value;
   if (!tk_scan_operands<BF16, FP8, Args::kNorm>(s) || !ws || !index || !tk_args_ok(s.NQ, s.NV, k) ||
-      !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16, FP8))
+      !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16, FP8) || (WHERE && (!tags || !where)))
     return MMT_ERR_ARG;
   if (((uintptr_t)s.q | (uintptr_t)s.q_lo | (uintptr_t)s.g) & 15) return MMT_ERR_ALIGN;
   if (s.E < 0 || s.E > TK_MAXE || (s.E > 0 && !s.exclude)) return MMT_ERR_ARG;
@@ -326,15 +394,17 @@ int tk_search(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_
   a.NQ = s.NQ; a.NV = s.NV; a.M = s.M; a.K = s.M * s.d; a.k = k;
   a.subset = s.subset; a.exclude = s.exclude; a.E = s.E;
   if constexpr (AFTER) a.after = s.after;
+  if constexpr (WHERE) { a.tags = tags; a.where = where; }
   tk_geometry(a);
-  tk_topk_lds_limits();
+  if constexpr (WHERE) tk_where_lds_limits();
+  else tk_topk_lds_limits();
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(a.n_qt * a.n_chunks);
   const size_t lds = (BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES) + tk_state_lds(k);
   using Plain = std::conditional_t<FP8, TkFp8Args, std::conditional_t<BF16, TkBf16Args, TkArgs>>;
   if (AFTER || Args::kNorm || s.subset || s.E)
-    hipLaunchKernelGGL((topk_scan_kernel<BF16, Args>), grid, dim3(256), lds + tk_exclude_lds(s.E) + (AFTER ? kAfterLds : 0),
-                       st, a);
+    hipLaunchKernelGGL((topk_scan_kernel<BF16, Args>), grid, dim3(256),
+                       lds + tk_exclude_lds(s.E) + (AFTER ? kAfterLds : 0) + (WHERE ? kWhereLds : 0), st, a);
   else if constexpr (!Args::kNorm && !AFTER)  // constexpr only so that the slice to Plain is not instantiated for NmTopkArgs
     hipLaunchKernelGGL((topk_scan_kernel<BF16, Plain>), grid, dim3(256), lds, st, (Plain)a);
   return tk_merge_launch(ws, s.NQ, a.n_chunks, k, k < s.NV ? k : s.NV, scores, index, st);
@@ -389,6 +459,16 @@ extern "C" int mmt_search_topk(const MmtSearchScan* scan, int k, uint64_t* ws, f
                  : tk_search<false, NmTopkArgs>(s, k, ws, scores, index, stream);
   return after ? tk_search<false, TkAfterArgs>(s, k, ws, scores, index, stream)
                : tk_search<false, TkMaskedArgs>(s, k, ws, scores, index, stream);
+}
+
+// The filtered search: storage -> the one filtered block of that storage.
+extern "C" int mmt_search_topk_where(const MmtSearchScan* scan, const uint64_t* tags, const uint64_t* where, int k,
+                                     uint64_t* ws, float* scores, int64_t* index, void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_SUBSET | SC_EXCLUDE | SC_AFTER | SC_FP8)) return rc;
+  const MmtSearchScan& s = *scan;
+  if (s.storage == MMT_SEARCH_FP8) return tk_search<true, TkFp8WhereArgs>(s, k, ws, scores, index, stream, tags, where);
+  if (s.storage == MMT_SEARCH_BF16) return tk_search<true, TkBf16WhereArgs>(s, k, ws, scores, index, stream, tags, where);
+  return tk_search<false, TkWhereArgs>(s, k, ws, scores, index, stream, tags, where);
 }
 
 extern "C" int mmt_rows_topk(const float* sims, int64_t ld, const int32_t* rows, int NR, int NV, int k, uint64_t* ws,

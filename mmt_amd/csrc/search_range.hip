@@ -59,6 +59,21 @@ struct RgFp8MaskedArgs : RgFp8Args {  // as RgMaskedArgs
   const uint32_t* subset;
 };
 
+// The filtered passes (mmt_search_range_count_where, mmt_search_range_fill_where): the masked blocks with a tag word per
+// item and three masks per query row behind them (search_scan.h: tk_tag_pass); the subset may be null here.  Both passes
+// apply the same term, so they see the same hits.
+struct RgWhereArgs : RgMaskedArgs {
+  const uint64_t* tags;    // [NV]
+  const uint64_t* where;   // [NQ][3]: all_of, none_of, any_of
+  static constexpr bool kWhere = true;
+};
+
+struct RgFp8WhereArgs : RgFp8MaskedArgs {  // as RgWhereArgs
+  const uint64_t* tags;
+  const uint64_t* where;
+  static constexpr bool kWhere = true;
+};
+
 // The unmasked block of a masked one.
 template <class Args>
 using RgPlain = std::conditional_t<TkFp8<Args>::value, RgFp8Args, RgArgs>;
@@ -66,6 +81,8 @@ using RgPlain = std::conditional_t<TkFp8<Args>::value, RgFp8Args, RgArgs>;
 // Args: RgArgs / RgMaskedArgs unless given (the fp8 blocks).
 template <bool BF16, bool FILL, bool MASKED, class Args = std::conditional_t<MASKED, RgMaskedArgs, RgArgs>>
 __global__ __launch_bounds__(256) void range_kernel(Args a) {
+  constexpr bool WHERE = TkWhere<Args>::value;
+  static_assert(!WHERE || MASKED, "the filtered blocks extend the masked ones");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int kUnion = BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -80,14 +97,40 @@ __global__ __launch_bounds__(256) void range_kernel(Args a) {
   if (!rg.init(a.thr, nullptr, a.ws, a.offsets, q0, rows_live, chunk, a.n_chunks, g_end - g_begin, wave, lane))
     return;  // block-uniform: no row of this block has a hit in this chunk
   tk_load_qw(sQw, a.qw, a.NQ, a.M, q0, tid);  // read after the barriers of the first K loop
+  uint64_t* sW = nullptr;                     // filtered: [TK_Q][3] masks behind the query weights
+  TkWhereGate gate;                           // what the rows' masks share, the tags a tile ahead
+  TkTagStream stream;
+  if constexpr (WHERE) {
+    sW = (uint64_t*)(sQw + TK_Q * MMT_MAX_EXPERTS);
+    tk_load_where<TK_Q>(sW, a.where, a.NQ, q0, tid);
+    gate.template init<TK_Q>(a.where, a.NQ, q0, lane);
+    stream.init(a.tags, g_begin, g_end, lane);
+    __syncthreads();  // read by the gate of the first tile
+  }
   for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
-    uint64_t m0 = ~0ull, m1 = ~0ull;
-    if constexpr (MASKED)
+    uint64_t m0 = ~0ull, m1 = ~0ull, t0 = 0, t1 = 0;
+    if constexpr (WHERE) stream.next(a.tags, g0, g_end, lane, t0, t1);  // before any skip: the next tile's are asked for
+    if constexpr (WHERE) {
+      if (a.subset && !tk_tile_mask(a.subset, g0, m0, m1)) continue;  // block-uniform; a null subset allows every item
+    } else if constexpr (MASKED) {
       if (!tk_tile_mask(a.subset, g0, m0, m1)) continue;  // block-uniform: nothing of this tile can hit
+    }
+    if constexpr (WHERE) {
+      if (!tk_tile_where_any<TK_Q>(gate, sW, rows_live, t0, t1, g0 + lane < g_end && ((m0 >> lane) & 1ull),
+                                   g0 + 64 + lane < g_end && ((m1 >> lane) & 1ull), wave))
+        continue;  // block-uniform: no live row has a candidate in this tile
+    }
     tk_tile<BF16, false>(a, smem, sS, sQw, q0, [=](int r) { return g0 + r < g_end ? g0 + r : -1; }, tid, wq, wg, l31, h);
     const bool live0 = g0 + lane < g_end && (!MASKED || ((m0 >> lane) & 1ull));
     const bool live1 = g0 + 64 + lane < g_end && (!MASKED || ((m1 >> lane) & 1ull));
-    rg.tile(sS, g0, live0, live1, rows_live, a.indices, a.scores, wave, lane);
+    if constexpr (WHERE) {
+      if (gate.uniform)  // block-uniform: one predicate for all rows is one more term of the shared liveness
+        rg.tile(sS, g0, live0 && gate.common(t0), live1 && gate.common(t1), rows_live, a.indices, a.scores, wave, lane);
+      else
+        rg.template tile<true>(sS, g0, live0, live1, rows_live, a.indices, a.scores, wave, lane, sW, t0, t1);
+    } else {
+      rg.tile(sS, g0, live0, live1, rows_live, a.indices, a.scores, wave, lane);
+    }
   }
   if constexpr (!FILL) rg.flush(a.ws, a.n_chunks, chunk);
 }
@@ -118,6 +161,7 @@ namespace {
 template <bool BF16, class Args>
 int rg_fill(Args& a, const MmtSearchScan& s, const float* thr, const int32_t* ws, bool own) {
   constexpr bool FP8 = TkFp8<Args>::value;
+  if constexpr (TkWhere<Args>::value) own = own && a.tags && a.where;  // set by the caller before the fill
   if (!tk_scan_operands<BF16, FP8>(s) || !thr || !ws || !own || !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16, FP8))
     return MMT_ERR_ARG;
   if (!tk_scan_aligned(s)) return MMT_ERR_ALIGN;
@@ -131,7 +175,10 @@ int rg_fill(Args& a, const MmtSearchScan& s, const float* thr, const int32_t* ws
 
 template <bool BF16, bool FILL, class Args>
 void rg_launch(const Args& a, hipStream_t s) {
-  if (a.subset)
+  if constexpr (TkWhere<Args>::value)  // always the filtered instantiation, its masks behind the query weights
+    hipLaunchKernelGGL((range_kernel<BF16, FILL, true, Args>), dim3(a.n_qt * a.n_chunks), dim3(256),
+                       tk_base_lds<BF16>() + TK_WHERE_BYTES(TK_Q), s, a);
+  else if (a.subset)
     hipLaunchKernelGGL((range_kernel<BF16, FILL, true, Args>), dim3(a.n_qt * a.n_chunks), dim3(256), tk_base_lds<BF16>(), s,
                        a);
   else
@@ -139,22 +186,37 @@ void rg_launch(const Args& a, hipStream_t s) {
                        tk_base_lds<BF16>(), s, (RgPlain<Args>)a);
 }
 
+// tags, where: the filtered blocks' (Args = Rg*WhereArgs), null for the others.
 template <bool BF16, class Args>
-int rg_count(const MmtSearchScan& s, const float* thr, int32_t* ws, int64_t* row_counts, void* stream) {
+int rg_count_tagged(const MmtSearchScan& s, const float* thr, int32_t* ws, int64_t* row_counts, void* stream,
+                    const uint64_t* tags, const uint64_t* where) {
   Args a = {};
+  if constexpr (TkWhere<Args>::value) { a.tags = tags; a.where = where; }
   if (const int rc = rg_fill<BF16>(a, s, thr, ws, row_counts != nullptr)) return rc;
   rg_launch<BF16, false>(a, (hipStream_t)stream);
   return rg_offsets_launch(ws, s.NQ, a.n_chunks, row_counts, (hipStream_t)stream);
 }
 
 template <bool BF16, class Args>
-int rg_fill_hits(const MmtSearchScan& s, const float* thr, const int32_t* ws, const int64_t* offsets, int64_t* indices,
-                 float* scores, void* stream) {
+int rg_count(const MmtSearchScan& s, const float* thr, int32_t* ws, int64_t* row_counts, void* stream) {
+  return rg_count_tagged<BF16, Args>(s, thr, ws, row_counts, stream, nullptr, nullptr);
+}
+
+template <bool BF16, class Args>
+int rg_fill_hits_tagged(const MmtSearchScan& s, const float* thr, const int32_t* ws, const int64_t* offsets, int64_t* indices,
+                        float* scores, void* stream, const uint64_t* tags, const uint64_t* where) {
   Args a = {};
+  if constexpr (TkWhere<Args>::value) { a.tags = tags; a.where = where; }
   if (const int rc = rg_fill<BF16>(a, s, thr, ws, offsets && indices && scores)) return rc;
   a.offsets = offsets; a.indices = indices; a.scores = scores;
   rg_launch<BF16, true>(a, (hipStream_t)stream);
   return (int)hipGetLastError();
+}
+
+template <bool BF16, class Args>
+int rg_fill_hits(const MmtSearchScan& s, const float* thr, const int32_t* ws, const int64_t* offsets, int64_t* indices,
+                 float* scores, void* stream) {
+  return rg_fill_hits_tagged<BF16, Args>(s, thr, ws, offsets, indices, scores, stream, nullptr, nullptr);
 }
 }  // namespace
 
@@ -191,4 +253,28 @@ extern "C" int mmt_search_range_fill(const MmtSearchScan* scan, const float* thr
                                      int64_t* indices, float* scores, void* stream) {
   if (const int rc = tk_scan_gate(scan, SC_SUBSET | SC_FP8)) return rc;
   return kRgBodies.fill[scan->storage](*scan, thr, ws, offsets, indices, scores, stream);
+}
+
+// The filtered passes (subset; fp32, bf16, fp8): workspace, outputs and the offsets kernel are the unfiltered entries'.
+extern "C" int mmt_search_range_count_where(const MmtSearchScan* scan, const uint64_t* tags, const uint64_t* where,
+                                            const float* thr, int32_t* ws, int64_t* row_counts, void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_SUBSET | SC_FP8)) return rc;
+  switch (scan->storage) {
+    case MMT_SEARCH_FP32: return rg_count_tagged<false, RgWhereArgs>(*scan, thr, ws, row_counts, stream, tags, where);
+    case MMT_SEARCH_BF16: return rg_count_tagged<true, RgWhereArgs>(*scan, thr, ws, row_counts, stream, tags, where);
+    default: return rg_count_tagged<true, RgFp8WhereArgs>(*scan, thr, ws, row_counts, stream, tags, where);
+  }
+}
+
+extern "C" int mmt_search_range_fill_where(const MmtSearchScan* scan, const uint64_t* tags, const uint64_t* where,
+                                           const float* thr, const int32_t* ws, const int64_t* offsets, int64_t* indices,
+                                           float* scores, void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_SUBSET | SC_FP8)) return rc;
+  switch (scan->storage) {
+    case MMT_SEARCH_FP32:
+      return rg_fill_hits_tagged<false, RgWhereArgs>(*scan, thr, ws, offsets, indices, scores, stream, tags, where);
+    case MMT_SEARCH_BF16:
+      return rg_fill_hits_tagged<true, RgWhereArgs>(*scan, thr, ws, offsets, indices, scores, stream, tags, where);
+    default: return rg_fill_hits_tagged<true, RgFp8WhereArgs>(*scan, thr, ws, offsets, indices, scores, stream, tags, where);
+  }
 }

@@ -77,6 +77,24 @@ struct RkFp8MaskedArgs : RkFp8Args {  // as RkMaskedArgs
   static constexpr TkMask kMask = TK_MASK_SET;
 };
 
+// The filtered count pass (mmt_search_count_where): the masked blocks with a tag word per item and three masks per query
+// row behind them (search_scan.h: tk_tag_pass); the subset may be null here.  An item is counted for a row only if its
+// tags pass the row's masks; thresholds come from the unfiltered threshold pass, so a target is scored whether or not it
+// passes and counts itself only if it does.
+struct RkWhereArgs : RkMaskedArgs {
+  const uint64_t* tags;    // [NV]
+  const uint64_t* where;   // [NQ][3]: all_of, none_of, any_of
+  static constexpr TkMask kMask = TK_MASK_NULLABLE;
+  static constexpr bool kWhere = true;
+};
+
+struct RkFp8WhereArgs : RkFp8MaskedArgs {  // as RkWhereArgs
+  const uint64_t* tags;
+  const uint64_t* where;
+  static constexpr TkMask kMask = TK_MASK_NULLABLE;
+  static constexpr bool kWhere = true;
+};
+
 // The unmasked block of a masked one: what the threshold pass and a count pass without a subset are launched with.
 template <class Args>
 using RkPlain = std::conditional_t<TkFp8<Args>::value, RkFp8Args, RkArgs>;
@@ -95,6 +113,8 @@ template <bool BF16, bool THR, class Args>
 __global__ __launch_bounds__(256) void rank_kernel(Args a) {
   constexpr TkMask MASK = Args::kMask;
   constexpr bool NORM = Args::kNorm;
+  constexpr bool WHERE = TkWhere<Args>::value;
+  static_assert(!WHERE || (!THR && !NORM && MASK == TK_MASK_NULLABLE), "the filter belongs to the plain count pass");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int kUnion = BF16 ? TKB_UNION_BYTES : TK_UNION_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -128,16 +148,38 @@ __global__ __launch_bounds__(256) void rank_kernel(Args a) {
       sCnt[2 * i] = 0;
       sCnt[2 * i + 1] = 0;
     }
+    uint64_t* sW = nullptr;  // filtered: [TK_Q][3] masks behind the counters (TK_Q * T * 12 bytes: 8-byte aligned)
+    TkWhereGate gate;        // what the rows' masks share, the tags a tile ahead
+    TkTagStream stream;
+    if constexpr (WHERE) {
+      sW = (uint64_t*)(sCnt + 2 * TK_Q * T);
+      tk_load_where<TK_Q>(sW, a.where, a.NQ, q0, tid);
+      gate.template init<TK_Q>(a.where, a.NQ, q0, lane);
+      stream.init(a.tags, g_begin, g_end, lane);
+    }
     if constexpr (MASK != TK_MASK_NONE) __syncthreads();  // every tile may be skipped: the counters are read below all the same
     for (int g0 = g_begin; g0 < g_end; g0 += TK_G) {
-      uint64_t m0 = ~0ull, m1 = ~0ull;
+      uint64_t m0 = ~0ull, m1 = ~0ull, t0 = 0, t1 = 0;
+      if constexpr (WHERE) stream.next(a.tags, g0, g_end, lane, t0, t1);  // before any skip: the next tile's are asked for
       if constexpr (MASK != TK_MASK_NONE)
         if ((MASK == TK_MASK_SET || a.subset) && !tk_tile_mask(a.subset, g0, m0, m1)) continue;  // block-uniform
+      if constexpr (WHERE) {
+        if (!tk_tile_where_any<TK_Q>(gate, sW, rows_live, t0, t1, g0 + lane < g_end && ((m0 >> lane) & 1ull),
+                                     g0 + 64 + lane < g_end && ((m1 >> lane) & 1ull), wave))
+          continue;  // block-uniform: no live row has an item to count in this tile
+      }
       tk_tile<BF16, NORM>(a, smem, sS, sQw, q0, [=](int r) { return g0 + r < g_end ? g0 + r : -1; }, tid, wq, wg, l31, h);
       // wave w owns rows 16w .. 16w + 15 for the whole block, so its counters need no barrier
       const bool live0 = g0 + lane < g_end && (MASK == TK_MASK_NONE || ((m0 >> lane) & 1ull));
       const bool live1 = g0 + 64 + lane < g_end && (MASK == TK_MASK_NONE || ((m1 >> lane) & 1ull));
-      tk_tile_count(sS, sThr, sCnt, T, rows_live, live0, live1, wave, lane);
+      if constexpr (WHERE) {
+        if (gate.uniform)  // block-uniform: one predicate for all rows is one more term of the shared liveness
+          tk_tile_count(sS, sThr, sCnt, T, rows_live, live0 && gate.common(t0), live1 && gate.common(t1), wave, lane);
+        else
+          tk_tile_count<true>(sS, sThr, sCnt, T, rows_live, live0, live1, wave, lane, sW, t0, t1);
+      } else {
+        tk_tile_count(sS, sThr, sCnt, T, rows_live, live0, live1, wave, lane);
+      }
     }
     tk_count_flush(sCnt, a.cnt, T, rows_live, q0, a.n_chunks, chunk, wave, lane);
   }
@@ -172,6 +214,7 @@ bool rk_args_ok(int NQ, int NV, int T) { return NQ > 0 && NV > 0 && T >= 1 && T 
 template <bool BF16, class Args>
 int rk_fill(Args& a, const MmtSearchScan& s, int T, const uint32_t* subset, bool own) {
   constexpr bool FP8 = TkFp8<Args>::value;
+  if constexpr (TkWhere<Args>::value) own = own && a.tags && a.where;  // set by the caller before the fill
   if (!tk_scan_operands<BF16, FP8, Args::kNorm>(s) || !own || !rk_args_ok(s.NQ, s.NV, T) ||
       !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16, FP8))
     return MMT_ERR_ARG;
@@ -204,6 +247,22 @@ void rk_lds_limits() {
     tk_lds_limits(done, {{(const void*)rank_kernel<BF16, false, RkArgs>, bytes},
                          {(const void*)rank_kernel<BF16, false, RkMaskedArgs>, bytes},
                          {(const void*)rank_kernel<BF16, false, NmRankArgs>, bytes}});
+}
+
+// The filtered count pass and the reduce: always the filtered instantiation, its masks behind the counters.
+template <bool BF16, class Args>
+int rk_count_where(const MmtSearchScan& s, const uint64_t* tags, const uint64_t* where, const float* thr, int T, int32_t* ws,
+                   int32_t* greater, int32_t* equal, void* stream) {
+  static bool done[64] = {};
+  Args a = {};
+  a.tags = tags; a.where = where;
+  if (const int rc = rk_fill<BF16>(a, s, T, s.subset, thr && ws && greater && equal)) return rc;
+  a.thr = const_cast<float*>(thr); a.cnt = ws;
+  tk_lds_limits(done, {{(const void*)rank_kernel<BF16, false, Args>,
+                        tk_base_lds<BF16>() + (size_t)TK_Q * RK_MAXT * 12 + TK_WHERE_BYTES(TK_Q)}});
+  hipLaunchKernelGGL((rank_kernel<BF16, false, Args>), dim3(a.n_qt * a.n_chunks), dim3(256),
+                     tk_base_lds<BF16>() + (size_t)TK_Q * a.T * 12 + TK_WHERE_BYTES(TK_Q), (hipStream_t)stream, a);
+  return rk_reduce_launch(a.cnt, (int64_t)a.NQ * a.T, a.n_chunks, greater, equal, (hipStream_t)stream);
 }
 
 // The count pass and the reduce.
@@ -301,4 +360,16 @@ extern "C" int mmt_search_count(const MmtSearchScan* scan, const float* thr, int
                        : rk_count<false, RkMaskedArgs>(s, thr, T, ws, greater, equal, stream);
   return p & SC_NORM ? rk_count<true, NmRankArgs>(s, thr, T, ws, greater, equal, stream)
                      : rk_count<true, RkMaskedArgs>(s, thr, T, ws, greater, equal, stream);
+}
+
+// The filtered count pass (subset; fp32, bf16, fp8): mmt_search_count against given thresholds with the per-query
+// attribute filter; workspace and outputs are mmt_search_count's.
+extern "C" int mmt_search_count_where(const MmtSearchScan* scan, const uint64_t* tags, const uint64_t* where, const float* thr,
+                                      int T, int32_t* ws, int32_t* greater, int32_t* equal, void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_SUBSET | SC_FP8)) return rc;
+  switch (scan->storage) {
+    case MMT_SEARCH_FP32: return rk_count_where<false, RkWhereArgs>(*scan, tags, where, thr, T, ws, greater, equal, stream);
+    case MMT_SEARCH_BF16: return rk_count_where<true, RkWhereArgs>(*scan, tags, where, thr, T, ws, greater, equal, stream);
+    default: return rk_count_where<true, RkFp8WhereArgs>(*scan, tags, where, thr, T, ws, greater, equal, stream);
+  }
 }

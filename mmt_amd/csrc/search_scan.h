@@ -10,7 +10,8 @@
 // geometry (tk_chunk, tk_geometry), the shape gate and the per-device dynamic-LDS limit (tk_lds_limits) are here once as
 // well, and so are the steps that follow a tile on more than one path: the count step (tk_tile_count), the range step
 // (TkRange), the query-set pooling (tk_tile_pool) and the item-set pooling (tk_tile_pool_items, with the unaligned subset
-// window tk_tile_mask_window).
+// window tk_tile_mask_window).  The per-query attribute filter is here too: the predicate (tk_tag_pass), its staging, its
+// tile gate (TkWhereGate, tk_tile_where_any) and the WHERE forms of the count and range steps.
 //
 // Which row a slab row / tile column holds is a functor `row(r)` on both sides -> row number, or -1 for "none" (zero-filled
 // in registers, never read): g0 + r for a scan's gallery side, a table lookup for the rank kernels' threshold pass and the
@@ -387,23 +388,136 @@ __device__ __forceinline__ void tk_tile_pool_items(float* sS, const float* sIw, 
     });
 }
 
+// The per-query attribute filter (the `_where` entries of mmt_hip.h; search.py: IndexTagging, TagFilter): every stored item
+// carries one 64-bit tag word, every query row three 64-bit masks (all_of, none_of, any_of), and item g is a candidate of
+// row q iff tk_tag_pass(tags[g], where[q]) -- plain integer operations on bit patterns, bit 63 an ordinary bit; three zero
+// masks admit every item.  It is one more term of the column liveness at selection and counting, per ROW where the subset
+// and the chunk's end are per column (tk_tile_select, tk_tile_count, TkRange::tile: their WHERE forms), and never touches a
+// score.  An argument block says so itself with `static constexpr bool kWhere = true`; a block that says nothing has none,
+// and its kernels are the ones they were.
+template <class Args, class = void>
+struct TkWhere { static constexpr bool value = false; };
+template <class Args>
+struct TkWhere<Args, std::void_t<decltype(Args::kWhere)>> { static constexpr bool value = Args::kWhere; };
+
+#define TK_WHERE_BYTES(rows) ((rows) * 3 * 8)  // a block's masks in LDS: [rows][3] uint64
+
+__device__ __forceinline__ bool tk_tag_pass(uint64_t t, uint64_t all_of, uint64_t none_of, uint64_t any_of) {
+  return (t & all_of) == all_of && (t & none_of) == 0ull && (any_of == 0ull || (t & any_of) != 0ull);
+}
+
+// The masks of the block's ROWS query rows -> sW [ROWS][3]; a row past NQ gets zeros (it is never live).  The caller
+// syncs before they are read.
+template <int ROWS>
+__device__ __forceinline__ void tk_load_where(uint64_t* sW, const uint64_t* where, int NQ, int q0, int tid) {
+  for (int i = tid; i < ROWS * 3; i += 256) sW[i] = q0 + i / 3 < NQ ? where[(int64_t)q0 * 3 + i] : 0ull;
+}
+
+// The tag words of the lane's two columns of the tile at g0 (column `lane` and 64 + `lane`; 0 past g_end, where the
+// column is not live anyway): two loads per thread and tile, 1 KiB per wave.
+__device__ __forceinline__ void tk_tile_tags(const uint64_t* tags, int g0, int g_end, int lane, uint64_t& t0, uint64_t& t1) {
+  t0 = g0 + lane < g_end ? tags[g0 + lane] : 0ull;
+  t1 = g0 + 64 + lane < g_end ? tags[g0 + 64 + lane] : 0ull;
+}
+
+// The same, one tile ahead: `next` hands out the tags of the tile at g0 and asks for those of the tile behind it, so the
+// loads of a tile are in flight during the tile before -- a skipped tile costs no memory round trip of its own.
+struct TkTagStream {
+  uint64_t n0, n1;
+  __device__ __forceinline__ void init(const uint64_t* tags, int g_begin, int g_end, int lane) {
+    tk_tile_tags(tags, g_begin, g_end, lane, n0, n1);
+  }
+  __device__ __forceinline__ void next(const uint64_t* tags, int g0, int g_end, int lane, uint64_t& t0, uint64_t& t1) {
+    t0 = n0;
+    t1 = n1;
+    tk_tile_tags(tags, g0 + TK_G, g_end, lane, n0, n1);
+  }
+};
+
+__device__ __forceinline__ uint64_t tk_shfl_xor64(uint64_t x, int m) {
+  return (uint64_t)(unsigned)__shfl_xor((int)x, m) | (uint64_t)(unsigned)__shfl_xor((int)(x >> 32), m) << 32;
+}
+
+// What the masks of a block's live rows have in common, formed once per block by every wave alike (lane l reads row l
+// from memory, six butterfly reductions): a_and / n_and = the bits EVERY row demands / bars, y_or = the bits some row's
+// any_of names, every_any = every row has an any_of.  An item that lacks a bit of a_and, has a bit of n_and, or -- where
+// every row has an any_of -- has no bit of y_or passes NO row: `common` is a necessary condition, and where all rows
+// carry the same three masks (uniform: the shared predicate) it is the predicate itself -- a per-COLUMN liveness like the
+// subset's, which the kernels then fold into the shared liveness and run the unfiltered step.
+struct TkWhereGate {
+  uint64_t a_and, n_and, y_or;
+  bool every_any, uniform;
+
+  template <int ROWS>
+  __device__ __forceinline__ void init(const uint64_t* where, int NQ, int q0, int lane) {
+    static_assert(ROWS <= 64, "a lane per row");
+    const bool live = lane < ROWS && q0 + lane < NQ;
+    const uint64_t* w = where + (int64_t)(q0 + lane) * 3;
+    const uint64_t a = live ? w[0] : 0ull, n = live ? w[1] : 0ull, y = live ? w[2] : 0ull;
+    uint64_t aa = live ? a : ~0ull, ao = a, na = live ? n : ~0ull, no = n, ya = live ? y : ~0ull, yo = y;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      aa &= tk_shfl_xor64(aa, m); ao |= tk_shfl_xor64(ao, m);
+      na &= tk_shfl_xor64(na, m); no |= tk_shfl_xor64(no, m);
+      ya &= tk_shfl_xor64(ya, m); yo |= tk_shfl_xor64(yo, m);
+    }
+    a_and = aa; n_and = na; y_or = yo;
+    every_any = __ballot(live && y == 0ull) == 0ull;
+    uniform = aa == ao && na == no && ya == yo;
+  }
+  __device__ __forceinline__ bool common(uint64_t t) const {
+    return (t & a_and) == a_and && (t & n_and) == 0ull && (!every_any || (t & y_or) != 0ull);
+  }
+};
+
+// The filter's gate of a tile, exact and block-uniform: whether ANY (live row, live column) pair of the ROWS x 128 tile
+// passes -- live0 / live1 the column liveness every row shares (the chunk's end, the subset's bit).  First the rows'
+// common condition: the four waves hold the same 128 tags and the same column liveness, so its ballot is the same in all
+// of them and decides without a barrier -- false: no pair passes; true with uniform rows: a pair passes.  Otherwise the
+// pairs are spread as the selection spreads them (wave w: rows ROWS / 4 * w ..; lane: columns `lane` and 64 + `lane`), a
+// wave stops at its first row with a pass, and one __syncthreads_or joins the four waves.  False: the caller skips the
+// tile before its K loop, as it skips a tile without a subset bit.  Every thread of the block must arrive.
+template <int ROWS>
+__device__ __forceinline__ bool tk_tile_where_any(const TkWhereGate& gate, const uint64_t* sW, int rows_live, uint64_t t0,
+                                                  uint64_t t1, bool live0, bool live1, int wave) {
+  if (!__ballot((live0 && gate.common(t0)) || (live1 && gate.common(t1)))) return false;
+  if (gate.uniform) return true;
+  bool any = false;
+  for (int rr = 0; rr < ROWS / 4 && !any; ++rr) {
+    const int row = wave * (ROWS / 4) + rr;
+    if (row >= rows_live) break;
+    const uint64_t wa = sW[row * 3], wn = sW[row * 3 + 1], wy = sW[row * 3 + 2];
+    any = __ballot((live0 && tk_tag_pass(t0, wa, wn, wy)) || (live1 && tk_tag_pass(t1, wa, wn, wy))) != 0ull;  // wave-uniform
+  }
+  return __syncthreads_or(any);
+}
+
 // The count step of one score tile (the count passes of search_rank.hip and search_pool.hip): wave w owns rows 16w .. 16w + 15
 // of the tile for the whole block, so its counters need no barrier.  Per row, lane t holds threshold t of sThr [.][T]; the
 // wave broadcasts one threshold at a time and counts `score > thr` / `score == thr` over the live columns (live0: column
 // `lane`, live1: column 64 + `lane`) with two ballots each -- plain float compares: -0 == +0, NaN counts for nothing --
-// and lane t adds the sums of threshold t to sCnt [.][T][2].
+// and lane t adds the sums of threshold t to sCnt [.][T][2].  WHERE: the liveness is per row -- the shared one ANDed with
+// the row's filter sW [.][3] over the lane's tags t0 / t1 (tk_tile_tags).
+template <bool WHERE = false>
 __device__ __forceinline__ void tk_tile_count(const float* sS, const float* sThr, int* sCnt, int T, int rows_live, bool live0,
-                                              bool live1, int wave, int lane) {
+                                              bool live1, int wave, int lane, const uint64_t* sW = nullptr, uint64_t t0 = 0,
+                                              uint64_t t1 = 0) {
   for (int rr = 0; rr < TK_Q / 4; ++rr) {
     const int row = wave * (TK_Q / 4) + rr;
     if (row >= rows_live) break;
     const float s0 = sS[row * TK_SLD + lane], s1 = sS[row * TK_SLD + 64 + lane];
     const int mine = lane < T ? __float_as_int(sThr[row * T + lane]) : 0;
+    bool l0 = live0, l1 = live1;
+    if constexpr (WHERE) {
+      const uint64_t wa = sW[row * 3], wn = sW[row * 3 + 1], wy = sW[row * 3 + 2];
+      l0 = l0 && tk_tag_pass(t0, wa, wn, wy);
+      l1 = l1 && tk_tag_pass(t1, wa, wn, wy);
+    }
     int ng = 0, ne = 0;
     for (int t = 0; t < T; ++t) {
       const float thr = __int_as_float(__builtin_amdgcn_readlane(mine, t));
-      const int cg = __popcll(__ballot(live0 && s0 > thr)) + __popcll(__ballot(live1 && s1 > thr));
-      const int ce = __popcll(__ballot(live0 && s0 == thr)) + __popcll(__ballot(live1 && s1 == thr));
+      const int cg = __popcll(__ballot(l0 && s0 > thr)) + __popcll(__ballot(l1 && s1 > thr));
+      const int ce = __popcll(__ballot(l0 && s0 == thr)) + __popcll(__ballot(l1 && s1 == thr));
       if (lane == t) { ng = cg; ne = ce; }
     }
     if (lane < T) {
@@ -467,9 +581,12 @@ struct TkRange {
     return true;
   }
 
-  // live0 / live1: column `lane` / 64 + `lane` of the tile at g0 holds an item that may be hit.
+  // live0 / live1: column `lane` / 64 + `lane` of the tile at g0 holds an item that may be hit.  WHERE: by the row's filter
+  // sW [.][3] as well, over the lane's tags t0 / t1 (tk_tile_tags) -- the same term in the count and in the fill.
+  template <bool WHERE = false>
   __device__ __forceinline__ void tile(const float* sS, int g0, bool live0, bool live1, int rows_live, int64_t* indices,
-                                       float* scores, int wave, int lane) {
+                                       float* scores, int wave, int lane, const uint64_t* sW = nullptr, uint64_t t0 = 0,
+                                       uint64_t t1 = 0) {
     const int c0 = g0 + lane, c1 = g0 + 64 + lane;
 #pragma nounroll
     for (int rr = 0; rr < kRows; ++rr) {
@@ -478,7 +595,12 @@ struct TkRange {
       const float s0 = sS[row * TK_SLD + lane], s1 = sS[row * TK_SLD + 64 + lane];
       const float t = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(thr), rr));
       const int o = OWN ? __builtin_amdgcn_readlane(own, rr) : -1;
-      const bool hit0 = live0 && (!OWN || c0 != o) && s0 >= t, hit1 = live1 && (!OWN || c1 != o) && s1 >= t;
+      bool hit0 = live0 && (!OWN || c0 != o) && s0 >= t, hit1 = live1 && (!OWN || c1 != o) && s1 >= t;
+      if constexpr (WHERE) {
+        const uint64_t wa = sW[row * 3], wn = sW[row * 3 + 1], wy = sW[row * 3 + 2];
+        hit0 = hit0 && tk_tag_pass(t0, wa, wn, wy);
+        hit1 = hit1 && tk_tag_pass(t1, wa, wn, wy);
+      }
       const uint64_t b0 = __ballot(hit0), b1 = __ballot(hit1);
       const int n0 = __popcll(b0), n1 = __popcll(b1);
       if constexpr (FILL) {

@@ -57,6 +57,16 @@ struct StArgs {
   int NQ, NV, M, K, k, E, tiles, n_qt, n_chunks;
 };
 
+// The filtered search on this schedule (mmt_search_topk_stream_where): StArgs with a tag word per item and three masks per
+// query row behind it (search_scan.h: tk_tag_pass), in a type of its own, so the kernels above keep their argument block.
+// One instantiation per storage, masked and paged: subset, exclude and after may each be absent (a null `after` gives
+// every live row the bound 2^64 - 1).  The filter acts in the selection; it skips no sweep.
+struct StWhereArgs : StArgs {
+  const uint64_t* tags;     // [NV]
+  const uint64_t* where;    // [NQ][3]: all_of, none_of, any_of
+  static constexpr bool kWhere = true;
+};
+
 // What a gallery stored as TG (float, bf16_t = bf16 bits, uint8_t = e4m3fn codes) means for the loop.
 template <class TG>
 struct StKind {
@@ -294,11 +304,13 @@ __device__ __forceinline__ void st_tile_scores(const f32x16 (&acc)[ST_T], float*
 }
 
 // One block: 32 queries x one gallery chunk -> the chunk's sorted k best per query in the workspace.
-template <class TG, bool MASKED, bool AFTER>
-__global__ __launch_bounds__(256, 2) void topk_stream_kernel(StArgs a) {
+template <class TG, bool MASKED, bool AFTER, class Args = StArgs>
+__global__ __launch_bounds__(256, 2) void topk_stream_kernel(Args a) {
   using X = StKind<TG>;
   using TQ = typename X::TQ;
   static_assert(!AFTER || MASKED, "the paged kernels extend the masked ones");
+  constexpr bool WHERE = TkWhere<Args>::value;
+  static_assert(!WHERE || AFTER, "the filtered kernels extend the paged ones");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, h = lane >> 5;
@@ -324,8 +336,16 @@ __global__ __launch_bounds__(256, 2) void topk_stream_kernel(StArgs a) {
   }
   if constexpr (MASKED)
     for (int i = tid; i < ST_Q * a.E; i += 256) sEx[i] = q0 + i / a.E < a.NQ ? (int)a.exclude[(int64_t)q0 * a.E + i] : -1;
-  if constexpr (AFTER)
+  if constexpr (WHERE) {
+    if (tid < ST_Q) sB[tid] = q0 + tid < a.NQ ? (a.after ? a.after[q0 + tid] : ~0ull) : 0ull;  // filtered: a null cursor
+  } else if constexpr (AFTER) {
     if (tid < ST_Q) sB[tid] = q0 + tid < a.NQ ? a.after[q0 + tid] : 0ull;
+  }
+  uint64_t* sW = nullptr;                                         // filtered: [ST_Q][3] masks, behind the bounds
+  if constexpr (WHERE) {
+    sW = sB + ST_Q;
+    tk_load_where<ST_Q>(sW, a.where, a.NQ, q0, tid);
+  }
   // all of the above is read behind the barriers of the first sweep
 
   StQueryStager<TG> Q;
@@ -373,9 +393,15 @@ __global__ __launch_bounds__(256, 2) void topk_stream_kernel(StArgs a) {
       for (int i = 0; i < 4; ++i)
         if (i == w) { lw = live[i]; x0 = m0[i]; x1 = m1[i]; }
       if (!lw) continue;  // block-uniform
+      uint64_t t0 = 0, t1 = 0;  // filtered: the tags of the lane's two columns, on their way during the epilogue
+      if constexpr (WHERE) tk_tile_tags(a.tags, G0 + w * TK_G, g_end, lane, t0, t1);
       if (w == wave) st_tile_scores<X::FP8>(acc, sS, sQw, a.gw, a.M, g0, g_end, l31, h, a.gscale);
       __syncthreads();
-      tk_tile_select<MASKED, AFTER, ST_Q>(sS, sC, sN, sT, a.k, rows_live, G0 + w * TK_G, g_end, wave, lane, x0, x1, sEx,
+      if constexpr (WHERE)
+        tk_tile_select<true, true, ST_Q, true>(sS, sC, sN, sT, a.k, rows_live, G0 + w * TK_G, g_end, wave, lane, x0, x1, sEx,
+                                               a.E, sB, sW, t0, t1);
+      else
+        tk_tile_select<MASKED, AFTER, ST_Q>(sS, sC, sN, sT, a.k, rows_live, G0 + w * TK_G, g_end, wave, lane, x0, x1, sEx,
                                     MASKED ? a.E : 0, sB);
       __syncthreads();
     }
@@ -468,9 +494,9 @@ void st_geometry(StArgs& a) {
 bool st_args_ok(int NQ, int NV, int k) { return NQ > 0 && NV > 0 && NV <= 0x7fffffff - ST_G && k >= 1 && k <= TK_MAXK; }
 
 template <class TG>
-size_t st_lds(int k, int E, bool after) {
+size_t st_lds(int k, int E, bool after, bool where = false) {
   return 2 * StKind<TG>::SLAB_BYTES + ST_TILE_BYTES + ST_QW_BYTES + ST_Q * (4 + 8) + (size_t)ST_Q * (k + 64) * 8 +
-         (size_t)ST_Q * E * 4 + (after ? ST_Q * 8 : 0);
+         (size_t)ST_Q * E * 4 + (after ? ST_Q * 8 : 0) + (where ? TK_WHERE_BYTES(ST_Q) : 0);
 }
 
 // The k = 128 footprint is over the 64 KiB default.
@@ -488,6 +514,14 @@ void st_lds_limits() {
                        {(const void*)topk_stream_kernel<uint8_t, true, true>, bf16}});
 }
 
+void st_where_lds_limits() {
+  static bool done[64] = {};
+  const size_t f32 = st_lds<float>(TK_MAXK, TK_MAXE, true, true), bf16 = st_lds<bf16_t>(TK_MAXK, TK_MAXE, true, true);
+  tk_lds_limits(done, {{(const void*)topk_stream_kernel<float, true, true, StWhereArgs>, f32},
+                       {(const void*)topk_stream_kernel<bf16_t, true, true, StWhereArgs>, bf16},
+                       {(const void*)topk_stream_kernel<uint8_t, true, true, StWhereArgs>, bf16}});
+}
+
 // The merge launch of this path; lists beyond what the heads' LDS holds go to the tile schedule's merge.
 int st_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, float* scores, int64_t* index, hipStream_t s) {
   constexpr size_t kLdsMax = 64 * 1024;
@@ -500,29 +534,37 @@ int st_merge_launch(const uint64_t* ws, int NQ, int n_chunks, int k, int kout, f
   return (int)hipGetLastError();
 }
 
-// Gate, geometry, the chunk scan and the merge: tk_search's gates in tk_search's order.
-template <class TG>
-int st_search(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_t* index, void* stream) {
-  constexpr bool BF16 = !StKind<TG>::F32, FP8 = StKind<TG>::FP8;
+// Gate, geometry, the chunk scan and the merge: tk_search's gates in tk_search's order.  Args = StWhereArgs: the filtered
+// search, with its tags and masks.
+template <class TG, class Args = StArgs>
+int st_search(const MmtSearchScan& s, int k, uint64_t* ws, float* scores, int64_t* index, void* stream,
+              const uint64_t* tags = nullptr, const uint64_t* where = nullptr) {
+  constexpr bool BF16 = !StKind<TG>::F32, FP8 = StKind<TG>::FP8, WHERE = TkWhere<Args>::value;
   if (!tk_scan_operands<BF16, FP8>(s) || !ws || !index || !st_args_ok(s.NQ, s.NV, k) ||
-      !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16, FP8))
+      !tk_shape_ok(s.NQ, s.NV, s.M, s.d, BF16, FP8) || (WHERE && (!tags || !where)))
     return MMT_ERR_ARG;
   if (((uintptr_t)s.q | (uintptr_t)s.q_lo | (uintptr_t)s.g) & 15) return MMT_ERR_ALIGN;
   if (s.E < 0 || s.E > TK_MAXE || (s.E > 0 && !s.exclude)) return MMT_ERR_ARG;
   if ((uintptr_t)s.subset & 15) return MMT_ERR_ALIGN;  // null = every item allowed
-  StArgs a = {};
+  Args a = {};
   a.q = s.q; a.q_lo = s.q_lo; a.qw = s.qw; a.g = s.g; a.gw = s.gw; a.gscale = s.gscale; a.ws = ws;
   a.subset = s.subset; a.exclude = s.exclude; a.after = s.after;
   a.NQ = s.NQ; a.NV = s.NV; a.M = s.M; a.K = s.M * s.d; a.k = k; a.E = s.E;
   st_geometry(a);
-  st_lds_limits();
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(a.n_qt * a.n_chunks);
-  const bool after = s.after != nullptr, masked = after || s.subset || s.E;
-  const size_t lds = st_lds<TG>(k, s.E, after);
-  if (after) hipLaunchKernelGGL((topk_stream_kernel<TG, true, true>), grid, dim3(256), lds, st, a);
-  else if (masked) hipLaunchKernelGGL((topk_stream_kernel<TG, true, false>), grid, dim3(256), lds, st, a);
-  else hipLaunchKernelGGL((topk_stream_kernel<TG, false, false>), grid, dim3(256), lds, st, a);
+  if constexpr (WHERE) {
+    a.tags = tags; a.where = where;
+    st_where_lds_limits();
+    hipLaunchKernelGGL((topk_stream_kernel<TG, true, true, Args>), grid, dim3(256), st_lds<TG>(k, s.E, true, true), st, a);
+  } else {
+    st_lds_limits();
+    const bool after = s.after != nullptr, masked = after || s.subset || s.E;
+    const size_t lds = st_lds<TG>(k, s.E, after);
+    if (after) hipLaunchKernelGGL((topk_stream_kernel<TG, true, true>), grid, dim3(256), lds, st, a);
+    else if (masked) hipLaunchKernelGGL((topk_stream_kernel<TG, true, false>), grid, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((topk_stream_kernel<TG, false, false>), grid, dim3(256), lds, st, a);
+  }
   return st_merge_launch(ws, s.NQ, a.n_chunks, k, k < s.NV ? k : s.NV, scores, index, st);
 }
 }  // namespace
@@ -541,4 +583,13 @@ extern "C" int mmt_search_topk_stream(const MmtSearchScan* scan, int k, uint64_t
   if (scan->storage == MMT_SEARCH_FP8) return st_search<uint8_t>(*scan, k, ws, scores, index, stream);
   if (scan->storage == MMT_SEARCH_BF16) return st_search<bf16_t>(*scan, k, ws, scores, index, stream);
   return st_search<float>(*scan, k, ws, scores, index, stream);
+}
+
+// The filtered search on this schedule: mmt_search_topk_where's arguments and answer, mmt_search_topk_stream's workspace.
+extern "C" int mmt_search_topk_stream_where(const MmtSearchScan* scan, const uint64_t* tags, const uint64_t* where, int k,
+                                            uint64_t* ws, float* scores, int64_t* index, void* stream) {
+  if (const int rc = tk_scan_gate(scan, SC_SUBSET | SC_EXCLUDE | SC_AFTER | SC_FP8)) return rc;
+  if (scan->storage == MMT_SEARCH_FP8) return st_search<uint8_t, StWhereArgs>(*scan, k, ws, scores, index, stream, tags, where);
+  if (scan->storage == MMT_SEARCH_BF16) return st_search<bf16_t, StWhereArgs>(*scan, k, ws, scores, index, stream, tags, where);
+  return st_search<float, StWhereArgs>(*scan, k, ws, scores, index, stream, tags, where);
 }

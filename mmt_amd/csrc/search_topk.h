@@ -81,11 +81,15 @@ __device__ __forceinline__ void tk_flush(uint64_t* c, int n, int k, int lane, ui
 // search: the argument blocks with kAfter): sB [TK_Q] holds one bound per row, a position in the search's order, and only
 // keys strictly below it are candidates: 2^64 - 1 = no cursor (no score gives that key), 0 = the row is exhausted, and
 // tk_key(a, first) + 1 = everything that scores below a, and at score a the items from number `first` on.  ROWS: the rows of
-// the block's score tile, a quarter per wave (TK_Q, or the streaming schedule's 32: search_stream.hip).
-template <bool MASKED = false, bool AFTER = false, int ROWS = TK_Q>
+// the block's score tile, a quarter per wave (TK_Q, or the streaming schedule's 32: search_stream.hip).  WHERE (the
+// per-query attribute filter: search_scan.h, tk_tag_pass): sW [ROWS][3] holds the rows' masks and t0 / t1 the tag words of
+// the lane's two columns (tk_tile_tags), loaded once per tile outside the row loop; a column is a candidate of a row only
+// if its tags pass the row's masks -- one more term of `live`, per row.
+template <bool MASKED = false, bool AFTER = false, int ROWS = TK_Q, bool WHERE = false>
 __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, int* sN, uint64_t* sT, int k, int rows_live,
                                                int g0, int g_end, int wave, int lane, uint64_t m0 = 0, uint64_t m1 = 0,
-                                               const int* sEx = nullptr, int E = 0, const uint64_t* sB = nullptr) {
+                                               const int* sEx = nullptr, int E = 0, const uint64_t* sB = nullptr,
+                                               const uint64_t* sW = nullptr, uint64_t t0 = 0, uint64_t t1 = 0) {
   const int cap = k + 64;
   for (int rr = 0; rr < ROWS / 4; ++rr) {
     const int row = wave * (ROWS / 4) + rr;
@@ -95,6 +99,8 @@ __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, in
     uint64_t bound = ~0ull;
     if constexpr (AFTER) bound = sB[row];
     uint64_t a0 = m0, a1 = m1;
+    uint64_t wa = 0, wn = 0, wy = 0;
+    if constexpr (WHERE) { wa = sW[row * 3]; wn = sW[row * 3 + 1]; wy = sW[row * 3 + 2]; }
     if constexpr (MASKED) {
       if (E) {
         const int mine = lane < E ? sEx[row * E + lane] : -1;
@@ -112,6 +118,7 @@ __device__ __forceinline__ void tk_tile_select(const float* sS, uint64_t* sC, in
       const int col = half * 64 + lane, g = g0 + col;
       bool live = g < g_end;
       if constexpr (MASKED) live = live && (((half ? a1 : a0) >> lane) & 1ull);
+      if constexpr (WHERE) live = live && tk_tag_pass(half ? t1 : t0, wa, wn, wy);
       tk_push<AFTER>(sC + row * cap, n, thr, k, live ? tk_key(sS[row * TK_SLD + col], g) : 0ull, lane, bound);
     }
     if (lane == 0) { sN[row] = n; sT[row] = thr; }

@@ -356,10 +356,37 @@ items and the int64 partials are added on the primary: bit-identical in .sums an
 the reference's InfoNceLoss over a whole evaluation set on it (rows: `query_lse`; columns: `hub_norm`; diagonal:
 `target_scores`).  Out of scope: exclude=, norm= (a dual softmax), pooling=, item_pooling=, after= and grouping= raise
 ValueError naming the option; a single-pass online softmax would save a scan and lose the bit-identity across shards.
+
+    tg  = index.tagging(tags)                                     # IndexTagging: one int64 tag word per stored item
+    flt = tg.where(all_of=0, none_of=0, any_of=0)                 # TagFilter: ints (broadcast) or int64 [NQ] per argument
+    scores, indices = index.search(q, qw, k=10, where=flt, subset=..., exclude=..., after=...)
+
+Not a further question but a per-query CANDIDATE SET for the ones above.  `subset=` is one bitmap for every row of a call
+and `exclude=` bars at most 32 named items per row; a retrieval service has a predicate per query over what the stored
+videos ARE -- "English, not flagged, category A or B", "this channel only".  Every stored item carries one 64-bit tag word
+t[g] whose bits mean what the caller decides, every query row three 64-bit masks, and item g is a candidate of row q iff
+    (t[g] & all_of[q]) == all_of[q]  and  (t[g] & none_of[q]) == 0  and  (any_of[q] == 0 or (t[g] & any_of[q]) != 0)
+-- plain 64-bit integer operations on bit patterns: the int64 tensors are bit patterns, bit 63 an ordinary bit, and a row
+whose three masks are 0 admits every item (`tag_pass` restates it in numpy).  The predicate is ANDed with subset=,
+exclude= and after= and acts at selection and counting only, so every returned score keeps the bits plain `search` gives
+the pair, and ShardedVideoIndex stays bit-identical (the predicate depends on the item and the row alone).  where= is
+taken by `search` on both schedules, `search_deep`, `rank_counts`, `ranks`, `threshold_counts`, `range_search` and
+`search_refined` (the coarse stage, with a filter from the coarse index's tagging), on all three storage dtypes and both
+index classes (mmt_search_topk_where and its four kin: the unfiltered entries' arguments with the tags and the masks
+behind the descriptor).  The result shapes are exclude='s: width min(k, candidates after subset), slots without a
+candidate hold (-inf, -1); a target of the counts is scored whether or not it passes and counts itself only if it does.
+On the tile schedule a 128-item tile in which no (live row, allowed item) pair passes is skipped before its K loop -- an
+exact test, so a selective predicate shared by a block's rows costs what the same subset costs; the streaming schedule
+filters in the selection alone.  Like a grouping, a tagging describes the num_items of its moment and is
+refused after a further `add`; the index's own storage and `nbytes` do not change.  where= with norm=, pooling= or
+item_pooling=, and on `search_groups`, `rescore`, `reverse_search`, the self-join and `query_lse`, is a ValueError before
+anything is scored; where=None takes exactly the calls above.
 """
 import ctypes
+import functools
 import math
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -378,8 +405,8 @@ MAX_ITEM_SET = 128  # items per stored set of an item-pooled scan: one 128-colum
 _POOL_MODES = {'mean': 0, 'max': 1}  # the `mode` of the pooled entry points
 _BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 bytes per element either way) + chunk lists
 _MAX_HITS = 1 << 27  # default cap of a range search's total: a guard against a mistyped threshold, not a tuned number
-_NOT_SELF = ('norm', 'pooling', 'item_pooling', 'grouping', 'after', 'exclude')  # options the self-join refuses by name
-_NOT_LSE = ('exclude', 'norm', 'pooling', 'item_pooling', 'after', 'grouping')  # options `query_lse` refuses by name
+_NOT_SELF = ('norm', 'pooling', 'item_pooling', 'grouping', 'after', 'exclude', 'where')  # options the self-join refuses by name
+_NOT_LSE = ('exclude', 'norm', 'pooling', 'item_pooling', 'after', 'grouping', 'where')  # options `query_lse` refuses by name
 _GROUP_ROWS = 1 << 16  # rows per `neighbour_range` call of `duplicate_groups`: the CSR of a batch is dropped for its edges
 FP8 = torch.float8_e4m3fn
 _DTYPES = {torch.float32: 4, torch.bfloat16: 8, FP8: 16}  # storage dtype -> multiple d must have (16-byte folded rows)
@@ -512,6 +539,87 @@ class ShardedGrouping:
   def __init__(self, parts, ids, num_groups):
     self.parts, self.ids, self.num_groups = parts, ids, num_groups
     self.num_items, self.device = ids.shape[0], ids.device
+
+
+def _mask_word(name, v):
+  """One argument of `where` that is a Python int: 0 .. 2^64 - 1 -> the int64 with that bit pattern."""
+  if not 0 <= v < 1 << 64:
+    raise ValueError('where: %s must lie in 0 .. 2^64 - 1, got %d' % (name, v))
+  return v - (1 << 64) if v >= 1 << 63 else v
+
+
+def _tag_filter(tagging, all_of, none_of, any_of):
+  """The checks of `where` -> TagFilter over `tagging`."""
+  given = (('all_of', all_of), ('none_of', none_of), ('any_of', any_of))
+  rows = None
+  for name, v in given:
+    if torch.is_tensor(v):
+      if v.dtype != torch.int64:
+        raise ValueError('where: %s must be an int or an int64 tensor, got %s' % (name, v.dtype))
+      if v.device != tagging.device:
+        raise ValueError('where: %s must be on the index device %s, got %s' % (name, tagging.device, v.device))
+      if v.dim() != 1:
+        raise ValueError('where: %s [NQ] expected, got %s' % (name, tuple(v.shape)))
+      if rows is not None and v.shape[0] != rows:
+        raise ValueError('where: %s holds %d rows, the masks before it %d' % (name, v.shape[0], rows))
+      rows = v.shape[0]
+    elif isinstance(v, bool) or not isinstance(v, int):
+      raise ValueError('where: %s must be an int or an int64 tensor, got %s' % (name, type(v).__name__))
+  words = [v if torch.is_tensor(v) else _mask_word(name, v) for name, v in given]
+  masks = torch.empty(1 if rows is None else rows, 3, device=tagging.device, dtype=torch.int64)
+  for j, w in enumerate(words):
+    masks[:, j] = w
+  return TagFilter(masks, tagging, rows)
+
+
+class TagFilter:
+  """The per-query attribute filter of a scan (IndexTagging.where / ShardedTagging.where), passed as where=: `masks` int64
+  [NQ, 3] on the index device, contiguous, row q = (all_of, none_of, any_of) as bit patterns; `tagging` the tagging it
+  filters; `num_rows` = NQ, the query rows a call must bring -- or None when every argument was a Python int: `masks` is
+  then [1, 3] and stands for any number of rows."""
+
+  def __init__(self, masks, tagging, num_rows):
+    self.masks, self.tagging, self.num_rows = masks, tagging, num_rows
+
+  def _rows(self, nq):
+    """The masks of a call with nq query rows, [nq, 3] contiguous (a broadcast filter is written out)."""
+    return self.masks if self.num_rows is not None else self.masks.expand(nq, 3).contiguous()
+
+  def _passes(self, items):
+    """Which of items int64 [NQ, T] (-1 = none, which fails) pass their row's masks -> bool [NQ, T], in torch ops on the
+    tagging's device: `tag_pass` for the given pairs."""
+    t = self.tagging.tags[items.clamp(min=0)]
+    a, n, y = (self.masks[:, j:j + 1] for j in range(3))
+    return (items >= 0) & ((t & a) == a) & ((t & n) == 0) & ((y == 0) | ((t & y) != 0))
+
+
+class IndexTagging:
+  """The attribute tags of a VideoIndex's items (VideoIndex.tagging): `tags` int64 [num_items] on the index device, one
+  64-bit word per item, a bit pattern whose bits mean what the caller decides (one-hot fields, flags, cohort bits);
+  `num_items` and `device` it was built for."""
+
+  def __init__(self, tags):
+    self.tags = tags
+    self.num_items, self.device = tags.shape[0], tags.device
+
+  def where(self, all_of=0, none_of=0, any_of=0):
+    """The filter of a call's query rows -> TagFilter for where=.  Each argument is a Python int in 0 .. 2^64 - 1 (the
+    same mask for every row) or an int64 tensor [NQ] on the index device (a bit pattern per row; bit 63 is an ordinary
+    bit); tensors must agree in NQ.  Item g is a candidate of row q iff (t[g] & all_of[q]) == all_of[q] and
+    (t[g] & none_of[q]) == 0 and (any_of[q] == 0 or (t[g] & any_of[q]) != 0).  Nothing here waits for the device."""
+    return _tag_filter(self, all_of, none_of, any_of)
+
+
+class ShardedTagging:
+  """The attribute tags of a ShardedVideoIndex's items (ShardedVideoIndex.tagging): `parts[s]` is shard s's IndexTagging in
+  its own item order on its own device (None for a shard without items); `tags` int64 [num_items] in global item order on
+  the primary device; `num_items`, `device`."""
+
+  def __init__(self, parts, tags):
+    self.parts, self.tags = parts, tags
+    self.num_items, self.device = tags.shape[0], tags.device
+
+  where = IndexTagging.where
 
 
 class QueryPooling:
@@ -705,6 +813,21 @@ def search_order(scores, items):
   return by_item[torch.argsort((scores + 0.0)[by_item], descending=True, stable=True)]   # -0.0 + 0.0 = +0.0
 
 
+def tag_pass(tags, masks):
+  """The attribute filter restated in numpy: tags int64 / uint64 [NV] and masks [NQ, 3] = (all_of, none_of, any_of) per
+  row -- numpy arrays or torch tensors (copied to the host) -> bool [NQ, NV], True where item g is a candidate of row q:
+  (t & all_of) == all_of and (t & none_of) == 0 and (any_of == 0 or (t & any_of) != 0), computed on the uint64 VIEW of
+  both, so bit 63 is a bit like the others."""
+  host = lambda x: np.ascontiguousarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x)
+  t, m = host(tags), host(masks)
+  if t.dtype not in (np.int64, np.uint64) or m.dtype not in (np.int64, np.uint64):
+    raise ValueError('tag_pass: 64-bit integer tags and masks expected, got %s and %s' % (t.dtype, m.dtype))
+  t, m = t.view(np.uint64).reshape(1, -1), m.view(np.uint64).reshape(-1, 3)
+  a, n, y = m[:, 0:1], m[:, 1:2], m[:, 2:3]
+  zero = np.uint64(0)
+  return ((t & a) == a) & ((t & n) == zero) & ((y == zero) | ((t & y) != zero))
+
+
 def connected_components(num_items, src, dst):
   """The connected components of the undirected graph on 0 .. num_items - 1 with the edges (src[i], dst[i]) -- int64 [E]
   each, on one device, CPU included; direction, order and repeats do not matter -> labels int64 [num_items] there:
@@ -787,6 +910,35 @@ class QueryLse:
     return torch.exp(self.log_prob(scores))
 
 
+def _where_option(full):
+  """Gives a public call the keyword-only option where= without putting it into the call's own parameter list, which
+  the tests of earlier changes pin name for name (DESIGN 9.21 kept `search`'s list by making the schedule a property; a
+  filter belongs to the call, so it cannot go that way).  The decorated method is the call as it was and is what runs
+  without a filter; with one, `full` runs -- the same call with `where` as its last parameter, whose docstring the
+  public name shows.  `inspect.signature` follows the wrapper to the decorated method and so does NOT list where=; the
+  docstring does."""
+  def decorate(method):
+    @functools.wraps(method)
+    def call(self, *args, where=None, **kwargs):
+      if where is None:
+        return method(self, *args, **kwargs)
+      return full(self, *args, where=where, **kwargs)
+    call.__doc__ = full.__doc__
+    return call
+  return decorate
+
+
+def _refuses_where(method):
+  """The same for a call that takes no filter: where= is a ValueError by the call's name, before anything is looked at,
+  instead of the TypeError of an unknown keyword."""
+  @functools.wraps(method)
+  def call(self, *args, where=None, **kwargs):
+    if where is not None:
+      raise ValueError('%s: where= is out of scope: this call takes no per-query filter' % method.__name__)
+    return method(self, *args, **kwargs)
+  return call
+
+
 def _check_rk(who, k):
   if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_RK:
     raise ValueError('%s: k must be an int in 1..%d, got %r' % (who, MAX_RK, k))
@@ -817,12 +969,15 @@ class _Scan:
   item_pooling (an ItemPooling / ShardedItemPooling), each None unless given and already checked against the index, and
   after (the cursor of a paged `search`, checked: scores float32 [NQ] and first int64 [NQ], the lowest item number still
   admitted at that score in the index's own numbers, -1 where the score is a sentinel: _limits), and stream: whether the
-  top-k pass takes the streaming schedule (`search` on an index whose schedule is 'stream'; every shard's view keeps it).  A public call builds it
+  top-k pass takes the streaming schedule (`search` on an index whose schedule is 'stream'; every shard's view keeps it), and
+  where (a TagFilter, checked against the index and the call's query rows: the per-query attribute filter, which sends the
+  top-k, count and range passes to their `_where` entries).  A public call builds it
   once and every internal call takes it whole; the sizes that depend on which options are there are answered here."""
 
-  def __init__(self, subset=None, ex=None, norm=None, pooling=None, item_pooling=None, after=None, stream=False):
+  def __init__(self, subset=None, ex=None, norm=None, pooling=None, item_pooling=None, after=None, stream=False,
+               where=None):
     self.subset, self.ex, self.norm, self.pooling, self.item_pooling = subset, ex, norm, pooling, item_pooling
-    self.after = after
+    self.after, self.where = after, where
     # `search` on an index set to 'stream': the top-k pass goes to mmt_search_topk_stream (checked: no norm, no sets)
     self.stream = stream
     # MmtSearchScan.sets: whose rows come in sets
@@ -831,16 +986,16 @@ class _Scan:
 
   def plain(self):
     """The same candidates without the norm, the cursor kept: the result the dynamic rule falls back to."""
-    return _Scan(self.subset, self.ex, after=self.after)
+    return _Scan(self.subset, self.ex, after=self.after, where=self.where)
 
   def uncursored(self):
     """The candidates of the whole list, without norm or cursor: what the dynamic rule DECIDES on -- a query's plain top-1,
     which is then the same on every page of that query."""
-    return _Scan(self.subset, self.ex)
+    return _Scan(self.subset, self.ex, where=self.where)
 
   def at(self, after):
     """The same scan from another cursor (None = from the top): the pages of `search_deep`."""
-    return _Scan(self.subset, self.ex, self.norm, self.pooling, self.item_pooling, after, self.stream)
+    return _Scan(self.subset, self.ex, self.norm, self.pooling, self.item_pooling, after, self.stream, self.where)
 
   def rows(self, q):
     """The rows of the outputs: one per query, or with a pooling one per query set."""
@@ -866,12 +1021,15 @@ class _Scan:
     """Shard s's view of it on the ShardedVideoIndex `index`: its part of the subset, the norm and the item pooling (None
     where the shard has none), the pooling as it is, the exclusions in the shard's item numbers on its device, and the
     cursor with `first` in the shard's numbers: the count of its items numbered at or below the cursor's item
-    (ShardedVideoIndex._first), which restates the global tie rule locally."""
+    (ShardedVideoIndex._first), which restates the global tie rule locally, and the filter as the shard's part of the
+    tagging with the masks on its device."""
     part = lambda whole: None if whole is None else whole.parts[s]
     device = index.shards[s].device
     ex = None if self.ex is None else index._local(self.ex, s).to(device)
     after = None if self.after is None else (self.after[0].to(device), index._first(self.after[1], s).to(device))
-    return _Scan(part(self.subset), ex, part(self.norm), self.pooling, part(self.item_pooling), after, self.stream)
+    where = None if self.where is None else TagFilter(self.where.masks.to(device), self.where.tagging.parts[s],
+                                                      self.where.num_rows)
+    return _Scan(part(self.subset), ex, part(self.norm), self.pooling, part(self.item_pooling), after, self.stream, where)
 
 
 def _column_groups(src, outs, r0, r1):
@@ -994,6 +1152,40 @@ class _Index:
     if lo < -1 or hi >= n:
       raise ValueError('ranks: targets must lie in -1 .. %d, got %d .. %d' % (n - 1, lo, hi))
 
+  def _tags(self, tags):
+    """The checks of `tagging` -> the tags as int64 [num_items] of their own."""
+    if self.num_items == 0:
+      raise ValueError('tagging: the index holds no items')
+    if not torch.is_tensor(tags) or tags.dtype != torch.int64:
+      raise ValueError('tagging: tags must be an int64 tensor, got %s' % (
+          tags.dtype if torch.is_tensor(tags) else type(tags).__name__))
+    if tags.device != self.device:
+      raise ValueError('tagging: tags must be on the index device %s, got %s' % (self.device, tags.device))
+    if tuple(tags.shape) != (self.num_items,):
+      raise ValueError('tagging: tags of shape (%d,) expected, got %s' % (self.num_items, tuple(tags.shape)))
+    return tags.contiguous().clone()
+
+  def _where(self, where, who, norm=None, pooling=None, item_pooling=None):
+    """Type and age of `where`, and what it does not combine with: all that can be said before the queries are known."""
+    for name, given in (('norm', norm), ('pooling', pooling), ('item_pooling', item_pooling)):
+      if given is not None:
+        raise ValueError('%s: where= does not combine with %s=' % (who, name))
+    if not isinstance(where, TagFilter):
+      raise ValueError('%s: where must come from the where() of a tagging, got %s' % (who, type(where).__name__))
+    self._made_here(where.tagging, who, 'tagging', self._tagging_type, '%s.tagging' % type(self).__name__)
+
+  @staticmethod
+  def _where_rows(where, who, nq):
+    """The filter's row count against the call's query rows."""
+    if where is not None and where.num_rows is not None and where.num_rows != nq:
+      raise ValueError('%s: %d query rows but the where= filter holds %d rows' % (who, nq, where.num_rows))
+
+  @staticmethod
+  def _no_where(who, where):
+    """The calls that take no filter say so by name, before anything is scored."""
+    if where is not None:
+      raise ValueError('%s: where= is out of scope: this call takes no per-query filter' % who)
+
   def pooling(self, set_size, num_sets, row_weights=None, mode='mean'):
     """The query sets of a pooled scan -> QueryPooling, built once like a subset and passed as pooling= to `search`,
     `rank_counts`, `ranks`, `target_scores` and `threshold_counts`: the queries of such a call are num_sets * set_size rows,
@@ -1033,10 +1225,13 @@ class _Index:
     if pooling is not None or exclude is not None or norm is not None:
       raise ValueError('%s: item_pooling= does not combine with pooling=, exclude= or norm=' % who)
 
-  def _scan_args(self, who, embds, weights, norm, dynamic, subset=None, exclude=None, pooling=None, item_pooling=None):
+  def _scan_args(self, who, embds, weights, norm, dynamic, subset=None, exclude=None, pooling=None, item_pooling=None,
+                 where=None):
     """The checks every scan shares once its own arguments have passed -> q, qw, whether the dynamic rule applies.  With
     a pooling the query count must be its num_rows: nothing is scored otherwise.  With an item pooling the subset is one
     of its sets."""
+    if where is not None:
+      self._where(where, who, norm, pooling, item_pooling)
     for what, given in (('item_pooling=', item_pooling), ('pooling=', pooling), ('norm=', norm)):
       if given is not None:
         self._no_fp8(who, what)
@@ -1055,6 +1250,7 @@ class _Index:
     if pooling is not None and q.shape[0] != pooling.num_rows:
       raise ValueError('%s: %d queries but the pooling has %d rows (%d sets of %d)' % (
           who, q.shape[0], pooling.num_rows, pooling.num_sets, pooling.set_size))
+    self._where_rows(where, who, q.shape[0])
     return q, qw, dynamic
 
   def _use_norm(self, q, qw, scan):
@@ -1104,7 +1300,7 @@ class _Index:
     top1 = self._search(b, bw, 1, _Scan())[1][:, 0]
     return torch.zeros(self.num_items, device=self.device, dtype=torch.bool).index_fill_(0, top1, True)
 
-  def reverse_search(self, embds, weights, k=10):
+  def reverse_search(self, embds, weights, k=10, where=None):
     """The search run the other way: queries in either layout of `search` (the text layout numbers its rows b * C + c),
     NQ >= 1 of them -> (scores float32 [num_items, k'], rows int64 [num_items, k']) on the device, k' = min(k, NQ), k an
     int in 1 .. MAX_RK = 32: for every stored item the k' query rows that score best on it, best first, equal scores
@@ -1114,6 +1310,7 @@ class _Index:
     matrix, and the result does not depend on the batching, on num_items, on an item's position or on the shard that
     holds it -- ShardedVideoIndex.reverse_search (every shard takes all the rows and answers for its own items) is
     bit-identical.  It takes no options: subset=, exclude=, norm= and the poolings are not part of this call."""
+    self._no_where('reverse_search', where)
     _check_rk('reverse_search', k)
     if self.num_items == 0:
       raise ValueError('reverse_search: the index holds no items')
@@ -1257,8 +1454,8 @@ class _Index:
         raise ValueError("%s: the index's schedule 'stream' does not combine with %s=" % (who, name))
     return True
 
-  def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None, pooling=None,
-             item_pooling=None, after=None):
+  def _search_filtered(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None, pooling=None,
+                       item_pooling=None, after=None, where=None):
     """Queries (NQ, M, d) / (NQ, M), or the text layout (B, M, C, d) / (B, C, M) -> (scores [NQ, k'] float32,
     indices [NQ, k'] int64) on the device, k' = min(k, NV), best first.  subset (from this index's `subset`): only its
     items are candidates and k' = min(k, subset.count).  exclude: int64 [NQ] or [NQ, E <= 32] on the index device, values
@@ -1308,27 +1505,41 @@ class _Index:
     assigned).  It is the schedule of THIS call alone (and of the coarse search of `search_refined`): `search_deep`, `search_groups`,
     the shortlist search of `search_diverse` and the searches inside `hub_norm`,
     `query_lse` and their kin keep the tile schedule.  ShardedVideoIndex: the property of the sharded index decides and
-    every shard takes it; the shard merge is the same."""
+    every shard takes it; the shard merge is the same.
+    where (a TagFilter from the `where` of this index's `tagging`): the per-query attribute filter -- item g is a candidate
+    of row q only if its tag word passes the row's three masks (module docstring; `tag_pass`), ANDed with subset=,
+    exclude= and after=.  Shapes as with exclude=: k' = min(k, the candidates after subset), and a row with fewer passing
+    candidates ends in (-inf, -1).  A score has the bits the call without where= gives the pair; both schedules take it
+    (mmt_search_topk_where, mmt_search_topk_stream_where) and give the same bits.  A filter whose row count is not this
+    call's, or from another index's tagging, and where= with norm=, pooling= or item_pooling= are ValueErrors raised before
+    anything is scored.  where=None takes exactly the calls above."""
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
       raise ValueError('search: k must be an int in 1..%d, got %r' % (MAX_K, k))
     return self._search_call(self._streams('search', norm, dynamic, pooling, item_pooling), embds, weights, k, subset,
-                             exclude, norm, dynamic, pooling, item_pooling, after)
+                             exclude, norm, dynamic, pooling, item_pooling, after, where)
+
+  @_where_option(_search_filtered)
+  def search(self, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None, pooling=None,
+             item_pooling=None, after=None):
+    return self._search_filtered(embds, weights, k, subset, exclude, norm, dynamic, pooling, item_pooling, after)
 
   def _search_call(self, stream, embds, weights, k=10, subset=None, exclude=None, norm=None, dynamic=None, pooling=None,
-                   item_pooling=None, after=None):
+                   item_pooling=None, after=None, where=None):
     """`search` behind its check of k and of the schedule: stream = whether the top-k pass takes the streaming schedule.
     Host code that builds on `search` without taking part in the schedule (`search_diverse`) calls this with False."""
     if self.num_items == 0:
       raise ValueError('search: the index holds no items')
     if after is not None:
       self._after(after, pooling, item_pooling)
-    q, qw, dynamic = self._scan_args('search', embds, weights, norm, dynamic, subset, exclude, pooling, item_pooling)
+    q, qw, dynamic = self._scan_args('search', embds, weights, norm, dynamic, subset, exclude, pooling, item_pooling,
+                                     where)
     ex, cursor = _limits(exclude, after, q.shape[0], self.num_items)
-    scan = _Scan(subset, ex, norm, pooling, item_pooling, cursor, stream)
+    scan = _Scan(subset, ex, norm, pooling, item_pooling, cursor, stream, where)
     return self._dynamic(dynamic, q, qw, scan, lambda scan: self._search(q, qw, k, scan))
 
-  def search_deep(self, embds, weights, depth, page=DEEP_PAGE, subset=None, exclude=None, norm=None, dynamic=None):
-    """The sorted list deeper than MAX_K: queries, subset, exclude, norm and dynamic as for `search`; depth an int >= 1, page
+  def _search_deep_filtered(self, embds, weights, depth, page=DEEP_PAGE, subset=None, exclude=None, norm=None,
+                            dynamic=None, where=None):
+    """The sorted list deeper than MAX_K: queries, subset, exclude, norm, dynamic and where as for `search`; depth an int >= 1, page
     an int in 1 .. MAX_K -> (scores [NQ, w] float32, indices [NQ, w] int64), w = min(depth, the candidates after subset):
     column for column the complete ordered candidate list of each query, cut at w, a row with fewer candidates left
     (exclusions) ending in (-inf, -1).  Host code: the concatenation of ceil(w / page) pages, each a search(k = min(page,
@@ -1344,8 +1555,8 @@ class _Index:
       raise ValueError('search_deep: page must be an int in 1..%d, got %r' % (MAX_K, page))
     if self.num_items == 0:
       raise ValueError('search: the index holds no items')
-    q, qw, dynamic = self._scan_args('search', embds, weights, norm, dynamic, subset, exclude)
-    scan = _Scan(subset, _limits(exclude, None, q.shape[0], self.num_items)[0], norm)
+    q, qw, dynamic = self._scan_args('search', embds, weights, norm, dynamic, subset, exclude, where=where)
+    scan = _Scan(subset, _limits(exclude, None, q.shape[0], self.num_items)[0], norm, where=where)
     width = min(depth, scan.candidates(self))
     use = self._use_norm(q, qw, scan) if dynamic and q.shape[0] else None
     pages, cursor = [], None
@@ -1356,7 +1567,12 @@ class _Index:
       cursor = (scores, torch.where(items >= 0, items + 1, items))   # a vacant slot (-inf, -1) is "exhausted" as it is
     return tuple(torch.cat(parts, 1) for parts in zip(*pages))
 
-  def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None, item_pooling=None):
+  @_where_option(_search_deep_filtered)
+  def search_deep(self, embds, weights, depth, page=DEEP_PAGE, subset=None, exclude=None, norm=None, dynamic=None):
+    return self._search_deep_filtered(embds, weights, depth, page, subset, exclude, norm, dynamic)
+
+  def rank_counts(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None, item_pooling=None,
+                  where=None):
     """Queries as for `search`; targets [NQ] or [NQ, T] int64 on the index device, values -1 .. num_items - 1 ->
     (greater, equal), int32 of targets' shape: how many of the num_items stored items score above / exactly equal to item
     targets[q, t] for query q (the item itself is one of the equal ones); 0 / 0 where the target is -1.  The range of the
@@ -1372,12 +1588,16 @@ class _Index:
     (mmt_search_thresholds [item sets], mmt_search_count [item sets]); a target counts itself; a subset is one of sets.
     ShardedVideoIndex: each
     shard scores the targets it holds, the primary picks the owner's value per (query, target), each shard counts its
-    items against those thresholds and the int32 counts are summed on the primary."""
+    items against those thresholds and the int32 counts are summed on the primary.
+    where (as `search`; not with norm=, pooling= or item_pooling=): only the items that pass the row's filter are counted;
+    like a target outside the subset, a target that does not pass is still scored (the unfiltered threshold pass) and
+    does not count itself (mmt_search_thresholds, then mmt_search_count_where)."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     self._targets(targets)
-    q, qw, dynamic = self._scan_args('ranks', embds, weights, norm, dynamic, subset, pooling=pooling, item_pooling=item_pooling)
-    scan = _Scan(subset=subset, norm=norm, pooling=pooling, item_pooling=item_pooling)
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, norm, dynamic, subset, pooling=pooling, item_pooling=item_pooling,
+                                     where=where)
+    scan = _Scan(subset=subset, norm=norm, pooling=pooling, item_pooling=item_pooling, where=where)
     nq, shape = scan.rows(q), targets.shape
     if shape[0] != nq:
       raise ValueError('ranks: %d %s but targets %s' % (nq, 'queries' if pooling is None else 'query sets', tuple(shape)))
@@ -1388,21 +1608,26 @@ class _Index:
     out = self._dynamic(dynamic, q, qw, scan, lambda scan: self._rank_counts(q, qw, tg, scan))
     return out[0].reshape(shape), out[1].reshape(shape)
 
-  def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None, item_pooling=None):
+  def ranks(self, embds, weights, targets, subset=None, norm=None, dynamic=None, pooling=None, item_pooling=None,
+            where=None):
     """The reference's tie-averaged 0-based rank (model/metric.py:90-121) of item targets[q, t] among the stored items for
     query q: greater + (equal - 1) / 2 from `rank_counts`, +inf where the target is -1.  float64 on the device, of
     targets' shape (float32 would not hold counts above 2^24).  subset: the rank among its items, +inf for a target that
     is not one of them.  norm, dynamic: as `rank_counts` -- the rank under the querybank-normalised score.  pooling: as
     `rank_counts` -- one row per query set, the rank under the set's pooled score.  item_pooling: as `rank_counts` -- the
-    rank of the target SET among the sets."""
+    rank of the target SET among the sets.  where: as `rank_counts` -- the rank among the items that pass the row's filter,
+    +inf for a target that does not."""
     greater, equal = self.rank_counts(embds, weights, targets, subset=subset, norm=norm, dynamic=dynamic, pooling=pooling,
-                                      item_pooling=item_pooling)
+                                      item_pooling=item_pooling, where=where)
     ranks = greater.double() + (equal.double() - 1) / 2
     none = targets < 0
     if subset is not None:
       none = none | ~subset.mask[targets.clamp(min=0)]
+    if where is not None:
+      none = none | ~where._passes(targets.reshape(targets.shape[0], -1)).reshape(targets.shape)
     return torch.where(none, torch.full_like(ranks, float('inf')), ranks)
 
+  @_refuses_where
   def rescore(self, embds, weights, candidates, k=None):
     """Queries as for `search`; candidates int64 [NQ, C] on the index device, 1 <= C <= MAX_C = 1024, values
     -1 .. num_items - 1 (-1 = none), in any order, an item as often as it comes -> (scores [NQ, k'] float32, indices
@@ -1445,7 +1670,7 @@ class _Index:
       raise ValueError('rescore: candidates must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
     return self._rescore(q, qw, cand, min(k, c))
 
-  def search_refined(self, embds, weights, coarse, k=10, shortlist=MAX_K, subset=None, exclude=None):
+  def _search_refined_filtered(self, embds, weights, coarse, k=10, shortlist=MAX_K, subset=None, exclude=None, where=None):
     """The two-stage search as one call: coarse.search(embds, weights, k=shortlist, subset=subset, exclude=exclude) on a
     cheap index of the same items -- typically a float8_e4m3fn one -- then self.rescore(embds, weights, that list, k) on
     this one -> (scores, indices) [NQ, min(k, shortlist, the coarse list's width)], scores with this index's bits.
@@ -1453,7 +1678,9 @@ class _Index:
     device; shortlist an int in 1 .. MAX_K; subset and exclude are `coarse`'s (a subset from ITS `subset`) and are checked
     by it.  The two indexes are TAKEN to hold the same items under the same numbers: that cannot be checked here.
     The coarse search takes `coarse`'s own schedule: with coarse.schedule = 'stream' this is the online pipeline, an fp8
-    shortlist streamed for a few queries and then re-scored, and the result is the same to the bit.  Host code only."""
+    shortlist streamed for a few queries and then re-scored, and the result is the same to the bit.  where: the filter of
+    the COARSE stage, built from `coarse`'s tagging and checked by it; the re-scoring takes the shortlist as it is.  Host
+    code only."""
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
       raise ValueError('search_refined: k must be an int in 1..%d, got %r' % (MAX_K, k))
     if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not 1 <= shortlist <= MAX_K:
@@ -1465,8 +1692,12 @@ class _Index:
       raise ValueError('search_refined: the coarse index holds (num_items, num_experts, dim) = %s, this one %s' % (theirs, mine))
     if coarse.device != self.device:
       raise ValueError('search_refined: the coarse index is on %s, this one on %s' % (coarse.device, self.device))
-    _, shortlisted = coarse.search(embds, weights, k=shortlist, subset=subset, exclude=exclude)
+    _, shortlisted = coarse.search(embds, weights, k=shortlist, subset=subset, exclude=exclude, where=where)
     return self.rescore(embds, weights, shortlisted, k)
+
+  @_where_option(_search_refined_filtered)
+  def search_refined(self, embds, weights, coarse, k=10, shortlist=MAX_K, subset=None, exclude=None):
+    return self._search_refined_filtered(embds, weights, coarse, k, shortlist, subset, exclude)
 
   def _candidate_lists(self, who, candidates):
     """Type, device and shape of the candidate lists of `pair_scores` and `diversify`, in the words of `rescore`'s checks."""
@@ -1751,6 +1982,7 @@ class _Index:
       raise ValueError('grouping: group_ids must lie in 0 .. %d, got %d .. %d' % (MAX_GROUP_ID, lo, hi))
     return group_ids.to(torch.int32).contiguous(), _count_groups(group_ids)
 
+  @_refuses_where
   def search_groups(self, embds, weights, grouping, k=10, subset=None):
     """Queries as for `search`; grouping from this index's `grouping` -> (scores [NQ, k'] float32, groups [NQ, k'] int64,
     items [NQ, k'] int64) on the device, k' = min(k, grouping.num_groups): per query the k' best GROUPS, best first.  A
@@ -1776,7 +2008,7 @@ class _Index:
     q, qw = self._queries(embds, weights)
     return self._search_groups(q, qw, min(k, grouping.num_groups), grouping, subset)
 
-  def _range_args(self, embds, weights, threshold, subset, order, max_hits):
+  def _range_args(self, embds, weights, threshold, subset, order, max_hits, where=None):
     """The checks of `range_search` -> q, qw, thr float32 [NQ]."""
     if order not in ('index', 'score'):
       raise ValueError("range_search: order must be 'index' or 'score', got %r" % (order,))
@@ -1795,8 +2027,11 @@ class _Index:
       raise ValueError('range_search: threshold must be a float or a float32 tensor, got %s' % type(threshold).__name__)
     if subset is not None:
       self._subset(subset, 'range_search')
+    if where is not None:
+      self._where(where, 'range_search')
     q, qw = self._queries(embds, weights)
     nq = q.shape[0]
+    self._where_rows(where, 'range_search', nq)
     if torch.is_tensor(threshold):
       if threshold.shape[0] != nq:
         raise ValueError('range_search: %d queries but threshold %s' % (nq, tuple(threshold.shape)))
@@ -1919,6 +2154,22 @@ class VideoIndex(_Index):
 
   def _grouping(self, grouping, who):
     self._made_here(grouping, who, 'grouping', IndexGrouping, 'VideoIndex.grouping')
+
+  _tagging_type = IndexTagging
+
+  def tagging(self, tags):
+    """tags: int64 [num_items] on the index device, one 64-bit tag word per stored item -- a bit pattern whose bits mean
+    what the caller decides -> IndexTagging, whose `where` builds the filters that where= takes.  Copied here, once; the
+    index's own storage and `nbytes` do not change.  It describes the num_items of this moment: after a further `add` it
+    is refused.  Nothing here waits for the device."""
+    return IndexTagging(self._tags(tags))
+
+  @staticmethod
+  def _filter_args(scan, r0, r1, nq):
+    """The two arguments the `_where` entries take behind the descriptor for query rows r0 .. r1 - 1 of nq: (the tags, the
+    rows' masks), and what keeps them alive."""
+    masks = scan.where._rows(nq)[r0:r1]
+    return (ops._p(scan.where.tagging.tags), ops._p(masks)), masks
 
   def _search_groups(self, q, qw, k, grouping, subset):
     """`search_groups` behind its argument checks: q (NQ, M, d) / qw (NQ, M) fp32 on the index device, 1 <= k <=
@@ -2062,16 +2313,21 @@ class VideoIndex(_Index):
     then are the outputs filled beforehand.  A cursor's bounds are built once, on the device (mmt_search_after_keys),
     and sliced per row batch next to the exclusions.  Nothing here waits for the device."""
     nq, nv, L = q.shape[0], self.num_items, _lib.lib()
-    paged = scan.after is not None
-    masked = scan.subset is not None or scan.ex is not None or paged
+    paged, filtered = scan.after is not None, scan.where is not None
+    masked = scan.subset is not None or scan.ex is not None or paged or filtered
     if grouping is None and (masked or scan.sets):
       k = min(k, scan.candidates(self))  # lists no longer than the candidates: the outputs stay dense
-    outs = _lists(2 if grouping is None else 3, self.device, scan.rows(q), min(k, nv), vacant=scan.ex is not None or paged)
+    outs = _lists(2 if grouping is None else 3, self.device, scan.rows(q), min(k, nv),
+                  vacant=scan.ex is not None or paged or filtered)
     if nq == 0:
       return outs
-    topk, workspace = L.mmt_search_topk, getattr(L, _WORKSPACES[scan.sets][0])
+    name = 'mmt_search_topk'
+    workspace = getattr(L, _WORKSPACES[scan.sets][0])
     if scan.stream:   # behind `search`'s checks: no norm, no sets; with a grouping nobody asks for it
-      topk, workspace = L.mmt_search_topk_stream, L.mmt_topk_stream_workspace_keys
+      name, workspace = 'mmt_search_topk_stream', L.mmt_topk_stream_workspace_keys
+    if filtered:      # behind the checks: no norm, no sets, no grouping; the unfiltered entry's workspace
+      name += '_where'
+    topk = getattr(L, name)
     bounds = None
     with torch.cuda.device(self.device):
       if paged:
@@ -2084,8 +2340,8 @@ class VideoIndex(_Index):
         desc, dims, (o0, o1), _keep = self._describe(scan, q, qw, r0, r1, bounds)
         ws = torch.empty(workspace(*dims, k), device=self.device, dtype=torch.int64)
         if grouping is None:
-          check(topk(desc, k, ops._p(ws), ops._p(outs[0][o0:o1]), ops._p(outs[1][o0:o1]), ops._stream()),
-                'mmt_search_topk_stream' if scan.stream else 'mmt_search_topk')
+          tagged, _masks = self._filter_args(scan, r0, r1, nq) if filtered else ((), None)
+          check(topk(desc, *tagged, k, ops._p(ws), ops._p(outs[0][o0:o1]), ops._p(outs[1][o0:o1]), ops._stream()), name)
         else:
           check(L.mmt_search_topk_groups(desc, k, ops._p(grouping.ids), ops._p(ws), ops._p(outs[0][o0:o1]),
                                          ops._p(outs[1][o0:o1]), ops._p(outs[2][o0:o1]), ops._stream()),
@@ -2158,13 +2414,17 @@ class VideoIndex(_Index):
                        lambda r0, r1: (self._self_operands(a, items, own, r0, r1, subset), None), thr, kept, offsets,
                        indices, scores)
 
-  def _scan_lead(self, q, qw, subset):
-    """The leading argument of the range entries over queries: (r0, r1) -> ((the batch's descriptor,), what it points at)."""
-    scan = _Scan(subset)
+  def _scan_lead(self, q, qw, subset, where=None):
+    """The leading arguments of the range entries over queries: (r0, r1) -> ((the batch's descriptor, with a filter the
+    tags and the rows' masks), what they point at)."""
+    scan = _Scan(subset, where=where)
 
     def lead(r0, r1):
       desc, _, _, keep = self._describe(scan, q, qw, r0, r1)
-      return (desc,), keep
+      if where is None:
+        return (desc,), keep
+      tagged, masks = self._filter_args(scan, r0, r1, q.shape[0])
+      return (desc,) + tagged, (keep, masks)
     return lead
 
   def _count_batches(self, workspace, entry, lead, thr):
@@ -2221,8 +2481,8 @@ class VideoIndex(_Index):
   def _rank_counts(self, q, qw, tg, scan):
     """`rank_counts` behind its checks: tg int64 [NQ >= 1, T] on the index device (with a pooling [num_sets, T], with an
     item pooling set numbers) -> (greater, equal) int32 of its shape.  Plain: the threshold and the count pass in one
-    call per batch (mmt_search_rank); with a norm, a pooling or an item pooling: one after the other."""
-    if scan.norm is not None or scan.sets:
+    call per batch (mmt_search_rank); with a norm, a pooling, an item pooling or a filter: one after the other."""
+    if scan.norm is not None or scan.sets or scan.where is not None:
       return self._threshold_counts(q, qw, self._target_scores(q, qw, tg, scan), scan)
     nq, nv, L = q.shape[0], self.num_items, _lib.lib()
     greater = torch.empty(tg.shape, device=self.device, dtype=torch.int32)
@@ -2276,7 +2536,7 @@ class VideoIndex(_Index):
     return thr.reshape(targets.shape)
 
   def threshold_counts(self, embds, weights, thresholds, subset=None, norm=None, dynamic=None, pooling=None,
-                       item_pooling=None):
+                       item_pooling=None, where=None):
     """Queries as for `search`; thresholds float32 [NQ] or [NQ, T] on the index device -> (greater, equal), int32 of
     thresholds' shape: how many stored items score above / exactly equal to thresholds[q, t] for query q (plain float
     compares; a NaN threshold counts nothing) -- the count pass of `rank_counts` against given values (mmt_search_count).
@@ -2284,7 +2544,9 @@ class VideoIndex(_Index):
     items' score' is what is compared (mmt_search_count [lse]); the dynamic rule as in `rank_counts`.  pooling (from
     `pooling`; not with norm=): thresholds [NS] or [NS, T], one row per query SET; the items' pooled score for the set is
     what is compared (mmt_search_count [query sets]).  item_pooling (from `item_pooling`; not with norm= or pooling=): the
-    SETS' pooled scores for the query are what is compared and counted (mmt_search_count [item sets])."""
+    SETS' pooled scores for the query are what is compared and counted (mmt_search_count [item sets]).  where (as `search`;
+    not with norm=, pooling= or item_pooling=): only the items that pass the row's filter are counted
+    (mmt_search_count_where)."""
     if self.num_items == 0:
       raise ValueError('ranks: the index holds no items')
     if not torch.is_tensor(thresholds) or thresholds.dtype != torch.float32:
@@ -2294,8 +2556,9 @@ class VideoIndex(_Index):
       raise ValueError('ranks: thresholds must be on the index device %s, got %s' % (self.device, thresholds.device))
     if thresholds.dim() not in (1, 2) or thresholds.dim() == 2 and thresholds.shape[1] < 1:
       raise ValueError('ranks: thresholds [NQ] or [NQ, T >= 1] expected, got %s' % (tuple(thresholds.shape),))
-    q, qw, dynamic = self._scan_args('ranks', embds, weights, norm, dynamic, subset, pooling=pooling, item_pooling=item_pooling)
-    scan = _Scan(subset=subset, norm=norm, pooling=pooling, item_pooling=item_pooling)
+    q, qw, dynamic = self._scan_args('ranks', embds, weights, norm, dynamic, subset, pooling=pooling, item_pooling=item_pooling,
+                                     where=where)
+    scan = _Scan(subset=subset, norm=norm, pooling=pooling, item_pooling=item_pooling, where=where)
     nq = scan.rows(q)
     if thresholds.shape[0] != nq:
       raise ValueError('ranks: %d %s but thresholds %s' % (nq, 'queries' if pooling is None else 'query sets',
@@ -2313,16 +2576,19 @@ class VideoIndex(_Index):
       return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
     workspace = getattr(L, _WORKSPACES[scan.sets][1])
     t_max = min(MAX_T, thr.shape[1])
+    filtered = scan.where is not None   # behind the checks: no norm, no sets; the unfiltered entry's workspace
+    name = 'mmt_search_count_where' if filtered else 'mmt_search_count'
     with torch.cuda.device(self.device):
       for r0, r1 in self._batches(nq, t_max, scan.pooling, scan.columns(self)):
         desc, dims, (o0, o1), _keep = self._describe(scan, q, qw, r0, r1)
         ws = torch.empty(workspace(*dims, t_max), device=self.device, dtype=torch.int32)
+        tagged, _masks = self._filter_args(scan, r0, r1, nq) if filtered else ((), None)
         for ts, (gs, es) in _column_groups(thr, (greater, equal), o0, o1):
-          check(L.mmt_search_count(desc, ops._p(ts), ts.shape[1], ops._p(ws), ops._p(gs), ops._p(es), ops._stream()),
-                'mmt_search_count')
+          check(getattr(L, name)(desc, *tagged, ops._p(ts), ts.shape[1], ops._p(ws), ops._p(gs), ops._p(es), ops._stream()),
+                name)
     return greater.reshape(thresholds.shape), equal.reshape(thresholds.shape)
 
-  def range_search(self, embds, weights, threshold, subset=None, order='index', max_hits=_MAX_HITS):
+  def range_search(self, embds, weights, threshold, subset=None, order='index', max_hits=_MAX_HITS, where=None):
     """Queries as for `search`; threshold a Python float, or float32 [NQ] on the index device (one per query) ->
     RangeResult: for every query ALL items g with score(q, g) >= threshold[q], however many (`search` stops at MAX_K), as a
     CSR on the device -- offsets int64 [NQ + 1], indices int64 [total], scores float32 [total], counts int64 [NQ]; query q's
@@ -2339,18 +2605,22 @@ class VideoIndex(_Index):
     call, then comes the one allocation, then the fills.  Each batch's count workspace is KEPT for its fill rather than
     recounted: it is 4 bytes per query and gallery chunk (at most 1 / 1024 of the score matrix, 1 MiB at 4 096 x 262 144),
     where a recount would be a third scan; the folded queries of a batch, which are large, are folded again instead.
-    Exclusions per query are not part of this call: the caller applies them to the CSR."""
-    q, qw, thr = self._range_args(embds, weights, threshold, subset, order, max_hits)
-    return self._csr(q.shape[0], lambda: self._range_count(q, qw, thr, subset),
-                     lambda *outs: self._range_fill(q, qw, thr, subset, *outs), order, max_hits, 'range_search')
+    Exclusions per query are not part of this call: the caller applies them to the CSR.  where (as `search`): only the
+    items that pass the row's filter are hits, in both scans alike (mmt_search_range_count_where,
+    mmt_search_range_fill_where)."""
+    q, qw, thr = self._range_args(embds, weights, threshold, subset, order, max_hits, where)
+    return self._csr(q.shape[0], lambda: self._range_count(q, qw, thr, subset, where),
+                     lambda *outs: self._range_fill(q, qw, thr, subset, where, *outs), order, max_hits, 'range_search')
 
-  def _range_count(self, q, qw, thr, subset):
+  def _range_count(self, q, qw, thr, subset, where=None):
     """The count pass of `range_search` behind its checks (`_count_batches`)."""
-    return self._count_batches('mmt_range_workspace_ints', 'mmt_search_range_count', self._scan_lead(q, qw, subset), thr)
+    return self._count_batches('mmt_range_workspace_ints', 'mmt_search_range_count' + ('_where' if where is not None else ''),
+                               self._scan_lead(q, qw, subset, where), thr)
 
-  def _range_fill(self, q, qw, thr, subset, kept, offsets, indices, scores):
+  def _range_fill(self, q, qw, thr, subset, where, kept, offsets, indices, scores):
     """The fill pass of `range_search`: `kept` from `_range_count` of the same arguments (`_fill_batches`)."""
-    self._fill_batches('mmt_search_range_fill', self._scan_lead(q, qw, subset), thr, kept, offsets, indices, scores)
+    self._fill_batches('mmt_search_range_fill' + ('_where' if where is not None else ''),
+                       self._scan_lead(q, qw, subset, where), thr, kept, offsets, indices, scores)
 
 
 
@@ -2860,6 +3130,22 @@ class ShardedVideoIndex(_Index):
   def _grouping(self, grouping, who):
     self._made_here(grouping, who, 'grouping', ShardedGrouping, 'ShardedVideoIndex.grouping')
 
+  _tagging_type = ShardedTagging
+
+  def tagging(self, tags):
+    """tags: int64 [num_items] on the primary device, as VideoIndex.tagging -> ShardedTagging: the tags cut into one
+    IndexTagging per shard, in the shard's item order on its device.  After a further `add` it is refused."""
+    tags = self._tags(tags)
+    parts = []
+    for sh in self.shards:
+      part = None
+      if sh.num_items:
+        local = tags[sh.ids[:sh.num_items]]  # gathered on the primary, where the table is
+        with torch.cuda.device(sh.device):
+          part = IndexTagging(local.to(sh.device))
+      parts.append(part)
+    return ShardedTagging(parts, tags)
+
   def _search_groups(self, q, qw, k, grouping, subset):
     """`search_groups` behind its checks: q, qw on the primary, 1 <= k <= grouping.num_groups.  Every live shard returns its
     best min(k, its groups) groups; the merge on the primary keeps one entry per group."""
@@ -2901,20 +3187,22 @@ class ShardedVideoIndex(_Index):
       equal += es.to(self.device)
     return greater, equal
 
-  def range_search(self, embds, weights, threshold, subset=None, order='index', max_hits=_MAX_HITS):
+  def range_search(self, embds, weights, threshold, subset=None, order='index', max_hits=_MAX_HITS, where=None):
     """VideoIndex.range_search over all shards -> RangeResult on the primary, in global item numbers, bit-identical to that
     of one VideoIndex.  Every shard counts the hits among its own items (with its part of the subset); the shards' totals
     are summed on the primary -- the call's one wait for the devices -- and held against max_hits before any shard
     allocates its outputs; every shard then fills a CSR of its own, whose local item numbers go through the shard's table
     to global ones; the primary concatenates the shards' hits and orders them by (query, global item) with two stable
-    torch sorts.  order='score' as VideoIndex.range_search.  Exclusions are applied to the CSR by the caller."""
-    q, qw, thr = self._range_args(embds, weights, threshold, subset, order, max_hits)
-    scan, live, args = _Scan(subset), self._live(subset), {}
+    torch sorts.  order='score' as VideoIndex.range_search.  Exclusions are applied to the CSR by the caller.  where: every
+    shard filters with its part of the tagging and the masks on its device."""
+    q, qw, thr = self._range_args(embds, weights, threshold, subset, order, max_hits, where)
+    scan, live, args = _Scan(subset, where=where), self._live(subset), {}
 
     def stage(r0, r1):  # one batch: the queries go to every shard once, for both passes
       for s, sh in live:
         if s not in args:
-          args[s] = (q.to(sh.device), qw.to(sh.device), thr.to(sh.device), scan.shard(s, self).subset)
+          view = scan.shard(s, self)
+          args[s] = (q.to(sh.device), qw.to(sh.device), thr.to(sh.device), view.subset, view.where)
       return args
     return self._range_csr(q.shape[0], live, [(0, q.shape[0])] if q.shape[0] else [], stage,
                            lambda sh, mine: sh.index._range_count(*mine),

@@ -123,7 +123,15 @@ rounds, every variant once per round, interleaved; median and spread.  Default o
 schedule leaves as it was -- with k = 10 over 262 144 items at NQ = 1, 8, 32 and 64 on a float32, a bf16 and an fp8 index:
 --runs rounds, the two schedules interleaved, on device events; median and spread, the index bytes over the time (TB/s),
 the device time of the scan and the merge kernel separately (one profiled call), at NQ = 1 the wall time of a call with its
-synchronisation, and whether the two results are the same bits.  Default output profiles/search_stream_bench.json."""
+synchronisation, and whether the two results are the same bits.  Default output profiles/search_stream_bench.json.
+
+--where times the per-query attribute filter (search(where=)) at 4 096 queries x 262 144 items, k = 10, on a float32, a bf16
+and an fp8 index, every pair of variants alternated in one process, --runs rounds on device events; median and spread:
+(a) all-zero masks against plain `search` -- the cost of the predicate -- with search(exclude=) at E = 32 beside them;
+(b) 16 distinct predicates interleaved over the rows, each passing about 1/16 of randomly placed items, against the route
+without where=: 16 subset= searches over gathered row groups, bitmap builds included; (c) one predicate shared by all rows
+that passes one contiguous sixteenth of the gallery against subset= of the same items -- the tile skip; (d) one query on
+the streaming schedule (bf16, fp8) with and without a predicate.  Default output profiles/search_where_bench.json."""
 import argparse
 import json
 import math
@@ -711,6 +719,83 @@ def stream_mode(a, dev):
   return row
 
 
+def where_mode(a, dev):
+  """search(where=) at NQ = 4 096 over NV = 262 144 items, k = 10, on all three storages (module docstring, --where)."""
+  nq, nv, chunk, preds = 4096, SHAPES['S3'][1], 8192, 16
+  gen = torch.Generator(device=dev).manual_seed(0)
+  nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
+  dtypes = {'float32': torch.float32, 'bfloat16': torch.bfloat16, 'float8_e4m3fn': torch.float8_e4m3fn}
+  idx = {n: VideoIndex.empty(nv, M, D, dev, dtype=t) for n, t in dtypes.items()}
+  for at in range(0, nv, chunk):
+    g = nrm(torch.randn(chunk, M, D, device=dev, generator=gen))
+    gw = torch.softmax(torch.randn(chunk, M, device=dev, generator=gen), -1)
+    for index in idx.values():
+      index.add(g, gw)
+  q = nrm(torch.randn(nq, M, D, device=dev, generator=gen) + 0.3 * g[torch.arange(nq, device=dev) % chunk])
+  qw = torch.softmax(torch.randn(nq, M, device=dev, generator=gen), -1)
+  # bits 0 .. 15: one category per item, at random; bit 16: one contiguous sixteenth of the gallery
+  category = torch.randint(0, preds, (nv,), device=dev, generator=gen)
+  block = torch.zeros(nv, device=dev, dtype=torch.bool)
+  block[nv // 2:nv // 2 + nv // 16] = True
+  tags = (torch.ones(nv, device=dev, dtype=torch.int64) << category) | (block.long() << 16)
+  per_row = torch.ones(nq, device=dev, dtype=torch.int64) << (torch.arange(nq, device=dev) % preds)
+  groups = [torch.arange(c, nq, preds, device=dev) for c in range(preds)]
+  exclude = torch.randint(0, nv, (nq, 32), device=dev, generator=gen)
+  row = {'NQ': nq, 'NV': nv, 'index_bytes': {n: idx[n].nbytes for n in idx}}
+
+  def by_subsets(index):   # the route without where=: per distinct predicate a bitmap, a gather of its rows, a whole scan
+    scores = torch.empty(nq, K, device=dev)
+    items = torch.empty(nq, K, device=dev, dtype=torch.int64)
+    for c, rows in enumerate(groups):
+      scores[rows], items[rows] = index.search(q[rows], qw[rows], k=K, subset=index.subset(category == c))
+    return scores, items
+
+  same = lambda x, y: bool(torch.equal(x[1], y[1]) and torch.equal(x[0].view(torch.int32), y[0].view(torch.int32)))
+  for n, index in idx.items():
+    tg = index.tagging(tags)
+    zero, mixed, shared = tg.where(), tg.where(all_of=per_row), tg.where(all_of=1 << 16)
+    subset = index.subset(block)
+    pairs = {
+        'a_predicate_cost': {'plain': lambda: index.search(q, qw, k=K), 'where_zero': lambda: index.search(q, qw, k=K, where=zero),
+                             'exclude_32': lambda: index.search(q, qw, k=K, exclude=exclude)},
+        'b_16_predicates': {'where': lambda: index.search(q, qw, k=K, where=mixed), 'subsets_16': lambda: by_subsets(index)},
+        'c_shared_sixteenth': {'where': lambda: index.search(q, qw, k=K, where=shared),
+                               'subset': lambda: index.search(q, qw, k=K, subset=subset)},
+    }
+    if n != 'float32':
+      def one(sched, flt):
+        index.schedule = sched
+        try:
+          return index.search(q[:1], qw[:1], k=K, where=flt)
+        finally:
+          index.schedule = None
+      sixteenth = tg.where(all_of=1)
+      pairs['d_stream_one_query'] = {'plain': lambda: one('stream', None), 'where': lambda: one('stream', sixteenth),
+                                     'where_zero': lambda: one('stream', zero)}
+    for what, fns in pairs.items():
+      ts, out = {v: [] for v in fns}, {}
+      for _ in range(a.runs):          # alternated: drift hits the variants alike
+        for v, fn in fns.items():
+          t, _, _, out[v] = timed(fn, a.min_seconds)
+          ts[v].append(t)
+      cell = {v: dict(seconds_median=float(np.median(ts[v])), seconds_spread=max(ts[v]) - min(ts[v]), seconds_runs=ts[v])
+              for v in fns}
+      first, second = list(fns)[:2]
+      cell['summary'] = dict(
+          ratio='%s / %s' % (second, first), value=cell[second]['seconds_median'] / cell[first]['seconds_median'],
+          difference_seconds=cell[second]['seconds_median'] - cell[first]['seconds_median'],
+          spreads_combined=cell[first]['seconds_spread'] + cell[second]['seconds_spread'])
+      if what != 'd_stream_one_query':
+        cell['summary']['same_bits'] = same(out[first], out[second])
+      else:
+        cell['summary']['zero_masks_same_bits_as_plain'] = same(out['plain'], out['where_zero'])
+      row['%s/%s' % (n, what)] = cell
+      print('%s %s: %s' % (n, what, ', '.join('%s %.3f ms (+- %.3f)' % (v, 1e3 * cell[v]['seconds_median'],
+                                                                        1e3 * cell[v]['seconds_spread']) for v in fns)),
+            file=sys.stderr)
+  return row
+
+
 def composed_rescore(index, q, qw, cand, k):
   """What `rescore` replaces, from the public calls: `target_scores` of the candidates (MAX_T columns per launch), then
   `search`'s order in torch -- two stable sorts, by item and then by descending score with -0 as +0 and none last.
@@ -1103,6 +1188,9 @@ def main():
                   'at NQ = 64 and 4096 over 262 144 items, and add of 8 192 items (no other mode flag)')
   ap.add_argument('--stream', action='store_true', help="time search with index.schedule = 'stream' against 'tile' (k = 10) at "
                   'NQ = 1, 8, 32, 64 on a float32, a bf16 and an fp8 index of 262 144 items; no other mode')
+  ap.add_argument('--where', action='store_true', help='time search(where=) at 4 096 x 262 144, k = 10, on a float32, a bf16 and '
+                  'an fp8 index: zero masks against plain search, 16 predicates against 16 subset searches, a shared '
+                  'contiguous predicate against the same subset, one streamed query with and without a predicate')
   ap.add_argument('--shapes', default='S1,S2,S3')
   ap.add_argument('--out', default=None)
   ap.add_argument('--min-seconds', type=float, default=0.5)
@@ -1181,6 +1269,17 @@ def main():
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
+  if a.where:
+    res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'where', 'runs': a.runs,
+           'min_seconds': a.min_seconds}
+    res.update(where_mode(a, dev))
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                'search_where_bench.json')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+      json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return
   if a.lse:
     res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'lse', 'runs': a.runs,
            'min_seconds': a.min_seconds}
