@@ -821,6 +821,35 @@ int mmt_search_range_count_where(const MmtSearchScan* scan, const uint64_t* tags
 int mmt_search_range_fill_where(const MmtSearchScan* scan, const uint64_t* tags, const uint64_t* where, const float* thr,
                                 const int32_t* ws, const int64_t* offsets, int64_t* indices, float* scores, void* stream);
 
+/* The per-expert breakdown of a score (search_explain.hip), additive: one entry with plain arguments, nothing that exists
+ * changes and mmt_abi_version() stays 6.  It serves search.py's `expert_scores`, `search_explained` and
+ * `pair_expert_scores`: which expert produced a match, and with what share of the gate -- the score of the scans is a sum
+ * over experts of terms that share one denominator, so it decomposes exactly.
+ * mmt_search_expert_parts (fp32, bf16, fp8): qf fp32 [R][M * d], rows ALWAYS in fp32 (mmt_search_fold's; or dequantised
+ *   stored rows in a query's place), qw fp32 [R][M]; g [NV][M * d] in `storage` (MMT_SEARCH_FP32 / _BF16 / _FP8), gw fp32
+ *   [NV][M], gscale fp32 [NV] with fp8 and null otherwise -- not a descriptor entry: MmtSearchScan's q / q_lo mean the bf16
+ *   pair on a bf16 or fp8 gallery.  candidates int64 [R][C], 1 <= C <= MMT_SEARCH_MAX_C, any order, repeats allowed, a
+ *   value outside 0 .. NV - 1 is "none": checked on the device, never dereferenced -> parts, mix fp32 [R][C][M], NaN in all
+ *   M slots of a none.  With f_g the dequantised stored row and den = fma(qw[m], gw[g][m], den) over m ascending, 0 -> 1e-5:
+ *     dot_m  = sum_{j < d} qf[m d + j] * f_g[m d + j]
+ *     part_m = dot_m / den                        fp8: fl(fl(dot_m * gscale[g]) / den) on the codes, a rounded multiply
+ *     mix_m  = fl(qw[m] * gw[g][m]) / den         both quotients correctly rounded divisions
+ *   sum_m part_m is the score of the pair on the stored value, sum_m mix_m is 1 (0 where den was 0), part_m / mix_m the
+ *   similarity under expert m alone.  dot_m is one fp32 fma chain per lane -- lane l of a wave takes the 16-byte groups l,
+ *   l + 64, ... of the expert's d values, elements ascending -- then a fixed butterfly over the 64 lanes: an order that is a
+ *   function of (d, storage) and the element index alone, so a pair's values depend on the pair alone, bit for bit -- not
+ *   on its place in the list, the other candidates, C, R or the launch geometry -- and with stored rows as qf the values of
+ *   (g, h) have the bits of (h, g).  Within (d + M + 4) * 2^-24 * <|qf_m|, |f_g,m|> / |den| of the fp64 value.  One wave
+ *   per pair on the vector ALUs, 16-byte loads of the stored row; no workspace.
+ * MMT_ERR_ARG: a null qf, qw, g, gw, candidates, parts or mix, an unknown storage, gscale given without fp8 or missing with
+ *   it, C out of range, R / NV < 1, M outside 1 .. 16, d < 1 or off the storage's multiple, R * ceil(C / 16) beyond a grid;
+ *   then MMT_ERR_ALIGN: qf or g off a 16-byte boundary.  All refused on the host before any launch.  No atomics; one writer
+ *   per slot. */
+#define MMT_SEARCH_MAX_C 1024
+int mmt_search_expert_parts(const float* qf, const float* qw, const void* g, const float* gw, const float* gscale,
+                            int storage, int NV, int M, int d, const int64_t* candidates, int R, int C, float* parts,
+                            float* mix, void* stream);
+
 /* Beside the scans.
  * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> the subset words, padding included: one ballot per 64
  *   items, one writer per word.

@@ -284,6 +284,10 @@ SIGNATURES = {
     'mmt_search_count_where': (c_int, [_SCAN, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mmt_search_range_count_where': (c_int, [_SCAN, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mmt_search_range_fill_where': (c_int, [_SCAN, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # the per-expert breakdown of a score, additive and without a descriptor: fp32 rows and their weights, the stored
+    # operand (g, gw, gscale, storage, NV, M, d), candidates [R][C], parts and mix [R][C][M], the stream
+    'mmt_search_expert_parts': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp,
+                                        c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

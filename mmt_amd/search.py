@@ -381,6 +381,42 @@ filters in the selection alone.  Like a grouping, a tagging descri
 refused after a further `add`; the index's own storage and `nbytes` do not change.  where= with norm=, pooling= or
 item_pooling=, and on `search_groups`, `rescore`, `reverse_search`, the self-join and `query_lse`, is a ValueError before
 anything is scored; where=None takes exactly the calls above.
+
+    es = index.expert_scores(q, qw, candidates)            # ExpertScores: .parts, .mix float32 [NQ, C, M]; .expert_sims
+    scores, indices, es = index.search_explained(q, qw, k=10, subset=None, exclude=None, after=None, where=None)
+    es = index.pair_expert_scores(items, candidates)       # items int64 [R]: stored rows in the query's place
+
+The thirteenth question: WHICH EXPERT produced a match, and with what share of the gate.  The twelve above return the
+mixture as one number; what makes the model multi-modal -- "matched on speech 46 %, OCR 31 %", the reason for a wrong
+top-1, what the renormalisation of a missing modality (gw[g][m] = 0) did, whether two "duplicates" agree in the picture
+or only in the audio track -- is its decomposition, which is exact and additive: the score is a sum over experts of
+terms that share one denominator.  With qf = fold_fp32(Q, qw)[q], f_g the dequantised stored row (float32: the row;
+bfloat16: widened; float8_e4m3fn: code * scales[g]) and den = sum_m qw[q][m] gw[g][m] in fp32 in expert order (0 -> 1e-5):
+    dot_m  = sum_{j < d} qf[m d + j] * f_g[m d + j]
+    part_m = dot_m / den           float8_e4m3fn: fl(fl(dot_m * scales[g]) / den) on the codes, as the scans place the scale
+    mix_m  = fl(qw[q][m] * gw[g][m]) / den
+sum_m part_m is the score on the stored value -- what `search` returns on this index -- sum_m mix_m is 1 (0 where the
+denominator was 0) and expert_sims = part_m / mix_m is <Q_m[q], G_m[g]>, the pair's similarity under expert m alone (the
+cosine, for unit-norm experts).  candidates int64 [NQ, C <= MAX_C = 1024] as for `rescore` (-1 = none, any order, repeats);
+a none has NaN in all M slots.  Only the listed rows are touched: a gather of NQ * C stored rows at about 2 flops per
+byte, so it runs on the vector ALUs -- one wave per pair, 16-byte loads of the stored row, the query's fold in LDS
+(mmt_search_expert_parts, search_explain.hip) -- not on the 64 x 128 MFMA tile of `rescore`, which computes 64 rows to keep
+one; M one-hot-weight searches would cost M full scans and answer another question (another denominator), and
+index_select + dequantise + einsum materialises 7.5 GB for 4 096 x 128 hits and needs a dequantiser.  dot_m is one fp32
+fma chain per lane in an order fixed by (d, dtype) and the element index alone, then a fixed butterfly; both quotients are
+correctly rounded divisions.  Hence, deduced and not measured: the values of a pair depend on the pair alone, bit for bit
+-- not on its place in the list, the other candidates, C, NQ, the row batching, the query layout or the shard
+(ShardedVideoIndex: every shard explains the candidates it holds and the primary takes each pair from its owner) -- and
+every part is within (d + M + 4) * 2^-24 * <|qf_m|, |f_g,m|> / |den| of the fp64 value of the definition.  The fold is
+the fp32 one on every dtype: the entry takes plain arguments, not the descriptor, whose q / q_lo are the bf16 pair on a
+bfloat16 or float8_e4m3fn index.  `search_explained` is host code like `search_refined`: `search` with the given options
+under the index's schedule, then `expert_scores` of the returned indices; the list is `search`'s to the bit and a vacant
+slot has NaN parts.  `pair_expert_scores` explains the hits of `pair_scores`, `neighbours` and `duplicate_groups`: the R
+rows of `items` are gathered and dequantised to fp32 (exact), their stored weights serve as qw and the same kernel runs,
+so the parts sum to sim(g, h) and, every product commuting and the denominator being symmetric, (g, h) has the bits of
+(h, g).  4 096 x 128 pairs on 262 144 items x 7 x 512 take 1.40 ms on a float32 index, 0.79 ms on bfloat16 and 0.78 ms on
+float8_e4m3fn.  Out of scope: norm=, dynamic=, pooling= and item_pooling= raise ValueError naming the
+option -- the parts explain the plain score -- and there is no per-expert top-k over the whole gallery.
 """
 import ctypes
 import functools
@@ -406,6 +442,7 @@ _POOL_MODES = {'mean': 0, 'max': 1}  # the `mode` of the pooled entry points
 _BATCH_BYTES = 48 << 20  # folded queries (fp32, or the bf16 hi + lo pair: 4 bytes per element either way) + chunk lists
 _MAX_HITS = 1 << 27  # default cap of a range search's total: a guard against a mistyped threshold, not a tuned number
 _NOT_SELF = ('norm', 'pooling', 'item_pooling', 'grouping', 'after', 'exclude', 'where')  # options the self-join refuses by name
+_NOT_EXPLAINED = ('norm', 'dynamic', 'pooling', 'item_pooling')  # options `search_explained` refuses by name
 _NOT_LSE = ('exclude', 'norm', 'pooling', 'item_pooling', 'after', 'grouping', 'where')  # options `query_lse` refuses by name
 _GROUP_ROWS = 1 << 16  # rows per `neighbour_range` call of `duplicate_groups`: the CSR of a batch is dropped for its edges
 FP8 = torch.float8_e4m3fn
@@ -428,6 +465,13 @@ def _fold(x, w):
   out = torch.empty(n, m * d, device=x.device, dtype=torch.float32)
   check(_lib.lib().mmt_search_fold(ops._p(x), ops._p(w), n, m, d, ops._p(out), ops._stream()), 'mmt_search_fold')
   return out
+
+
+def _dequantised(stored, dtype, scales):
+  """Stored rows as bytes (uint8 [n, row bytes]) of an index of `dtype`, with their scales (float8_e4m3fn) or None -> the
+  rows in fp32 [n, M * d]: float32 as it is, bfloat16 widened, float8_e4m3fn code * scale -- a power of two.  All exact."""
+  rows = stored.view(dtype).to(torch.float32)
+  return rows if scales is None else rows * scales[:, None]
 
 
 def _limits(exclude, after, nq, nv):
@@ -517,6 +561,22 @@ class RangeResult:
   def __init__(self, offsets, indices, scores):
     self.offsets, self.indices, self.scores = offsets, indices, scores
     self.counts = offsets[1:] - offsets[:-1]
+
+
+class ExpertScores:
+  """The per-expert breakdown of scores (`expert_scores`, `search_explained`, `pair_expert_scores`) on the index device:
+  `parts` and `mix` float32 [R, C, M], slot m of pair (r, candidates[r, c]) -- part_m, expert m's share of the score (the
+  parts of a pair sum to its score), and mix_m, expert m's share of the gate (they sum to 1, or to 0 where the pair's
+  denominator was 0); NaN in all M slots of a candidate of -1.  `expert_sims` = parts / mix, the raw similarity
+  <Q_m, G_m> of the pair under expert m alone (the cosine, for unit-norm experts): torch's division, NaN where the
+  expert has no share of the gate (a missing modality: 0 / 0)."""
+
+  def __init__(self, parts, mix):
+    self.parts, self.mix = parts, mix
+
+  @property
+  def expert_sims(self):
+    return self.parts / self.mix
 
 
 MAX_GROUP_ID = 2 ** 31 - 2
@@ -1699,15 +1759,16 @@ class _Index:
   def search_refined(self, embds, weights, coarse, k=10, shortlist=MAX_K, subset=None, exclude=None):
     return self._search_refined_filtered(embds, weights, coarse, k, shortlist, subset, exclude)
 
-  def _candidate_lists(self, who, candidates):
-    """Type, device and shape of the candidate lists of `pair_scores` and `diversify`, in the words of `rescore`'s checks."""
+  def _candidate_lists(self, who, candidates, widest=MAX_DC, rows='R'):
+    """Type, device and shape of the candidate lists of `pair_scores` and `diversify` -- and, `widest` = MAX_C wide, of
+    `expert_scores` and `pair_expert_scores` -- in the words of `rescore`'s checks."""
     if not torch.is_tensor(candidates) or candidates.dtype != torch.int64:
       raise ValueError('%s: candidates must be an int64 tensor, got %s' % (
           who, candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__))
     if candidates.device != self.device:
       raise ValueError('%s: candidates must be on the index device %s, got %s' % (who, self.device, candidates.device))
-    if candidates.dim() != 2 or not 1 <= candidates.shape[1] <= MAX_DC:
-      raise ValueError('%s: candidates [R, 1 <= C <= %d] expected, got %s' % (who, MAX_DC, tuple(candidates.shape)))
+    if candidates.dim() != 2 or not 1 <= candidates.shape[1] <= widest:
+      raise ValueError('%s: candidates [%s, 1 <= C <= %d] expected, got %s' % (who, rows, widest, tuple(candidates.shape)))
 
   def _candidate_range(self, who, cand):
     """The values of the (non-empty) candidates against -1 .. num_items - 1: one small reduction and a host sync."""
@@ -1825,6 +1886,91 @@ class _Index:
     # `search` without the index's schedule: the diversified search is not one of the calls that take it
     _, shortlisted = (self if coarse is None else coarse)._search_call(False, embds, weights, shortlist, subset, exclude)
     return self.diversify(embds, weights, shortlisted, k, lam)
+
+  def _no_scores(self, rows, c):
+    return ExpertScores(*(torch.empty(rows, c, self.num_experts, device=self.device, dtype=torch.float32) for _ in range(2)))
+
+  def expert_scores(self, embds, weights, candidates):
+    """The thirteenth question: which expert produced a match, and with what share of the gate.  Queries as for `search`;
+    candidates int64 [NQ, C] on the index device, 1 <= C <= MAX_C = 1024, values -1 .. num_items - 1 (-1 = none), in any
+    order, an item as often as it comes -- the indices `search`, `rescore` or any other call returned -> ExpertScores:
+    .parts and .mix float32 [NQ, C, M] on the device, NaN in all M slots of a -1.  With qf = fold_fp32(Q, qw)[q], f_g the
+    dequantised stored row of item g (float32: the row; bfloat16: widened; float8_e4m3fn: code * scales[g]) and
+    den = sum_m qw[q][m] gw[g][m] in fp32 in expert order (0 -> 1e-5):
+        dot_m  = sum_{j < d} qf[m d + j] * f_g[m d + j]
+        part_m = dot_m / den          float8_e4m3fn: fl(fl(dot_m * scales[g]) / den) on the codes, as the scans place the scale
+        mix_m  = fl(qw[q][m] * gw[g][m]) / den
+    so that sum_m part_m is the score of the pair on THIS index -- the quantity `search` returns, defined on the stored
+    value -- sum_m mix_m is 1 (0 where the denominator was 0: all parts and mix are then 0) and .expert_sims = parts / mix
+    is <Q_m[q], G_m[g]>, the pair's similarity under expert m alone.  dot_m is an fp32 fma chain in an order fixed by
+    (d, dtype) and the element index alone and both quotients are correctly rounded divisions, so the values of a pair
+    depend on the pair alone, bit for bit -- not on its place in the list, the other candidates, C, NQ, the row batching
+    or the shard: ShardedVideoIndex.expert_scores is bit-identical -- and each part is within
+    (d + M + 4) * 2^-24 * <|qf_m|, |f_g,m|> / |den| of the fp64 value of the definition.  Only the listed rows are touched:
+    one wave per pair on the vector ALUs (mmt_search_expert_parts), no gathered copy of the rows, no dequantised gallery.
+    The type, device and shape of the candidates are checked before the queries are looked at, their range like
+    `rescore`'s (one small reduction and a host sync); nothing after that waits for the device.  The queries are folded in
+    fp32 on every dtype, in row batches whose folded rows and outputs stay within _BATCH_BYTES."""
+    self._candidate_lists('expert_scores', candidates, MAX_C, 'NQ')
+    if self.num_items == 0:
+      raise ValueError('expert_scores: the index holds no items')
+    q, qw = self._queries(embds, weights)
+    nq, c = q.shape[0], candidates.shape[1]
+    if candidates.shape[0] != nq:
+      raise ValueError('expert_scores: %d queries but candidates %s' % (nq, tuple(candidates.shape)))
+    if nq == 0:
+      return self._no_scores(0, c)
+    cand = candidates.contiguous()
+    self._candidate_range('expert_scores', cand)
+    return ExpertScores(*self._expert_parts(q, qw, cand))
+
+  def search_explained(self, embds, weights, k=10, subset=None, exclude=None, after=None, where=None, **unsupported):
+    """`search` with its answer explained, host code in the manner of `search_refined`: search(embds, weights, k, subset=,
+    exclude=, after=, where=) -- under the index's own `schedule` -- then `expert_scores` on the returned indices ->
+    (scores, indices, ExpertScores).  The list is `search`'s to the bit; slot j of the breakdown belongs to indices[:, j],
+    and a vacant slot (-inf, -1) has NaN parts.  Out of scope: norm=, dynamic=, pooling= and item_pooling= raise
+    ValueError naming the option -- the parts explain the plain score."""
+    for name in unsupported:
+      if name not in _NOT_EXPLAINED:
+        raise TypeError('search_explained() got an unexpected keyword argument %r' % name)
+      raise ValueError('search_explained: %s= is out of scope: the parts explain the plain score' % name)
+    scores, indices = self.search(embds, weights, k=k, subset=subset, exclude=exclude, after=after, where=where)
+    return scores, indices, self.expert_scores(embds, weights, indices)
+
+  def pair_expert_scores(self, items, candidates):
+    """`expert_scores` with STORED items in the queries' place: what explains a hit of `pair_scores`, `neighbours` or
+    `duplicate_groups` -- whether the picture or only the audio track of two videos agrees.  items int64 [R] on the index
+    device, values 0 .. num_items - 1, repeats allowed; candidates int64 [R, C] as for `expert_scores` -> ExpertScores
+    [R, C, M] of the pairs (items[r], candidates[r, c]).  The R rows of `items` are gathered and dequantised to fp32
+    (exact: float32 as it is, bfloat16 widened, float8_e4m3fn code * scale), their stored weights serve as qw and the
+    same kernel runs, so the parts sum to `pair_scores`' sim(g, h) = <f_g, f_h> / sum_m gw[g][m] gw[h][m] and mix_m is
+    fl(gw[g][m] * gw[h][m]) over that denominator.  The accumulation order depends on the element index alone, every
+    product commutes and the denominator is symmetric in its factors: the values of (g, h) have the bits of (h, g).
+    ShardedVideoIndex.pair_expert_scores gathers the rows from their shards onto the primary first and is bit-identical.
+    The ranges are checked with one small reduction and a host sync; nothing after that waits for the device."""
+    self._candidate_lists('pair_expert_scores', candidates, MAX_C, 'NQ')
+    if not torch.is_tensor(items) or items.dtype != torch.int64:
+      raise ValueError('pair_expert_scores: items must be an int64 tensor, got %s' % (
+          items.dtype if torch.is_tensor(items) else type(items).__name__))
+    if items.device != self.device:
+      raise ValueError('pair_expert_scores: items must be on the index device %s, got %s' % (self.device, items.device))
+    if items.dim() != 1:
+      raise ValueError('pair_expert_scores: items [R] expected, got %s' % (tuple(items.shape),))
+    if self.num_items == 0:
+      raise ValueError('pair_expert_scores: the index holds no items')
+    r, c = items.shape[0], candidates.shape[1]
+    if candidates.shape[0] != r:
+      raise ValueError('pair_expert_scores: %d items but candidates %s' % (r, tuple(candidates.shape)))
+    if r == 0:
+      return self._no_scores(0, c)
+    items, cand = items.contiguous(), candidates.contiguous()
+    lo, hi, clo, chi = (int(v) for v in torch.stack(torch.aminmax(items) + torch.aminmax(cand)).tolist())
+    if lo < 0 or hi >= self.num_items:
+      raise ValueError('pair_expert_scores: items must lie in 0 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
+    if clo < -1 or chi >= self.num_items:
+      raise ValueError('pair_expert_scores: candidates must lie in -1 .. %d, got %d .. %d' % (self.num_items - 1, clo, chi))
+    rows, rw = self._stored_rows(items)
+    return ExpertScores(*self._expert_parts(rows, rw, cand))
 
   def _self_args(self, who, items, subset, source, unsupported, k=...):
     """The checks of the self-join calls that look at no value, before anything touches the device -> the index whose
@@ -2371,6 +2517,31 @@ class VideoIndex(_Index):
       check(_lib.lib().mmt_search_pair_scores(ops._p(self.folded), ops._p(self.weights), ops._p(self.scales),
                                               _STORAGE[self.dtype], self.num_items, self.num_experts, self.dim, ops._p(cand),
                                               r, c, ops._p(sims), ops._stream()), 'mmt_search_pair_scores')
+
+  def _expert_parts(self, q, qw, cand):
+    """`expert_scores` and `pair_expert_scores` behind their checks: q (R >= 1, M, d) fp32 queries, folded here in fp32 batch
+    by batch whatever the index's dtype, or (R, M * d) fp32 rows that stand folded already (dequantised stored rows);
+    qw (R, M) and cand int64 [R, C] (contiguous, item numbers, one outside 0 .. num_items - 1 = none), all on the index
+    device -> (parts, mix) float32 [R, C, M].  One launch per row batch, no workspace: a row's outputs are 8 C M bytes.
+    Nothing here waits for the device."""
+    r, c, m, L = q.shape[0], cand.shape[1], self.num_experts, _lib.lib()
+    with torch.cuda.device(self.device):
+      parts, mix = (torch.empty(r, c, m, device=self.device, dtype=torch.float32) for _ in range(2))
+      for r0, r1 in self._row_batches(r, 8 * c * m):
+        wb = qw[r0:r1]
+        qf = _fold(q[r0:r1], wb) if q.dim() == 3 else q[r0:r1]
+        check(L.mmt_search_expert_parts(ops._p(qf), ops._p(wb), ops._p(self.folded), ops._p(self.weights),
+                                        ops._p(self.scales), _STORAGE[self.dtype], self.num_items, m, self.dim,
+                                        ops._p(cand[r0:r1]), r1 - r0, c, ops._p(parts[r0:r1]), ops._p(mix[r0:r1]),
+                                        ops._stream()), 'mmt_search_expert_parts')
+    return parts, mix
+
+  def _stored_rows(self, items):
+    """The stored rows of `items` (int64 [R], 0 .. num_items - 1, on the index device) dequantised to fp32 -- exact on every
+    dtype -- with their weights: (rows [R, M * d], weights [R, M]).  R rows only."""
+    with torch.cuda.device(self.device):
+      stored = self.folded.view(torch.uint8)[items]   # bytes: a gather, whatever the dtype
+      return _dequantised(stored, self.dtype, None if self.scales is None else self.scales[items]), self.weights[items]
 
   def _self_rows(self):
     """This index's stored operand as the A side of the self-join entries: (rows, weights, scales or None, NA)."""
@@ -2984,6 +3155,28 @@ class ShardedVideoIndex(_Index):
     staging.num_items = n
     renumbered = torch.where(live, torch.searchsorted(distinct, cand.clamp(min=0)), torch.full_like(cand, -1))
     staging._pair_scores(renumbered, sims)
+
+  def _expert_parts(self, q, qw, cand):
+    """`expert_scores` and `pair_expert_scores` behind their checks: q, qw and cand (global numbers) on the primary.  Every
+    shard that holds items gets the rows and the candidates in its own numbers -- what it does not hold is -1, none, and
+    comes back NaN -- and the primary takes each pair from the shard that owns it.  A pair's values depend on the pair
+    alone, so the bits are those of one VideoIndex."""
+    out = None
+    for s, sh in self._live():
+      local = self._local(cand, s)   # translated on the primary, where the item maps are
+      with torch.cuda.device(sh.device):
+        mine = sh.index._expert_parts(q.to(sh.device), qw.to(sh.device), local.to(sh.device))
+      mine = tuple(t.to(self.device) for t in mine)
+      own = (local >= 0).unsqueeze(-1)
+      out = mine if out is None else tuple(torch.where(own, a, b) for a, b in zip(mine, out))
+    return out
+
+  def _stored_rows(self, items):
+    """As VideoIndex._stored_rows, items in global numbers on the primary: the rows' stored bytes, weights and scales are
+    gathered from their shards onto the primary (`_stage`) and dequantised there."""
+    stored, weights, scales = self._stage(items)
+    with torch.cuda.device(self.device):
+      return _dequantised(stored, self.dtype, scales), weights
 
   def _stage_batches(self, r):
     """Row ranges of the self-join's staging blocks: whole 64-row blocks whose stored bytes, weights and scales stay
