@@ -850,6 +850,37 @@ int mmt_search_expert_parts(const float* qf, const float* qw, const void* g, con
                             int storage, int NV, int M, int d, const int64_t* candidates, int R, int C, float* parts,
                             float* mix, void* stream);
 
+/* Cell-probed search (search_cells.hip), additive: one entry over the descriptor and its size function, nothing that
+ * exists changes, MmtSearchScan stays 21 fields / 128 bytes and mmt_abi_version() stays 6.  It serves search.py's `cells`,
+ * `search_probed` and `search_cells`: the inverted file.  The stored items are partitioned into cells, every query row names
+ * a few cells (its probes) and gets the k best items of their union -- for that row mmt_search_topk with the union as its
+ * subset, bit for bit: the same K loop and score epilogue (tk_scan, tk_tile_scores), the same key, running top-k and merge.
+ * mmt_search_topk_cells (no options; fp32, bf16, fp8): the cell tables and the call's work list come behind the descriptor.
+ *   items int64 [n_items]: the item numbers cell after cell, a cell's items ascending; a value outside 0 .. NV - 1 is
+ *     "none": checked on the device, never dereferenced.  The stored rows are read through it and are not moved.
+ *   pair_row, pair_slot int32 [n_pairs]: the (row, probe) pairs the call keeps -- invalid, empty and repeated cells dropped --
+ *     ordered by (cell, row): the query row of a pair, 0 .. NQ - 1, and its probe slot, 0 .. P - 1, unique within the row.
+ *   work int32 [n_work][5] = (first pair, rows, first position in items, end position, piece): one block scores `rows`
+ *     (1 .. 64) consecutive pairs of one cell against positions [first, end) of items, at most MMT_SEARCH_CELL_PIECE of
+ *     them, piece (0 .. pieces - 1) numbering the cuts of a cell.  rows = 0 is "no work": n_work may be an upper bound
+ *     known without waiting for the device, the entries past the real count zero.  An entry outside these ranges is
+ *     dropped on the device.
+ *   1 <= P <= MMT_SEARCH_MAX_PROBES, pieces >= 1, 1 <= k <= 128.  ws uint64 [mmt_topk_cells_workspace_keys(NQ, P, pieces,
+ *     k)] = NQ * P * pieces * k: every (row, slot, piece) has a list of its own, zeroed by the entry, one writer each, and
+ *     the merge launch of mmt_search_topk joins a row's P * pieces lists.  scores fp32 / index int64 [NQ][k]: the best k
+ *     items of the row's probed cells in the search's order -- score descending, -0 tied with +0, equal scores by
+ *     ascending item number, across cells as within them -- then (-inf, -1); every slot is written.
+ * MMT_ERR_ARG: any part of the descriptor beyond its operands (subset, exclude, after, norm, sets), a null operand, table,
+ *   workspace or output, n_items / n_work / n_pairs < 1, P, pieces or k out of range, P * pieces * k >= 2^31, and the common
+ *   shape gates; MMT_ERR_ALIGN: q, q_lo or g off a 16-byte boundary.  All refused on the host before any launch.  No
+ *   atomics; one writer per slot. */
+#define MMT_SEARCH_MAX_PROBES 64
+#define MMT_SEARCH_CELL_PIECE 2048
+int64_t mmt_topk_cells_workspace_keys(int NQ, int P, int pieces, int k);
+int mmt_search_topk_cells(const MmtSearchScan* scan, const int64_t* items, int n_items, const int32_t* work, int n_work,
+                          const int32_t* pair_row, const int32_t* pair_slot, int n_pairs, int P, int pieces, int k,
+                          uint64_t* ws, float* scores, int64_t* index, void* stream);
+
 /* Beside the scans.
  * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> the subset words, padding included: one ballot per 64
  *   items, one writer per word.

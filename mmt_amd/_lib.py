@@ -288,6 +288,11 @@ SIGNATURES = {
     # operand (g, gw, gscale, storage, NV, M, d), candidates [R][C], parts and mix [R][C][M], the stream
     'mmt_search_expert_parts': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp,
                                         c_vp, c_vp]),
+    # cell-probed search, additive: the descriptor, then items, n_items, work, n_work, pair_row, pair_slot, n_pairs, P,
+    # pieces, k, the workspace, the outputs, the stream
+    'mmt_topk_cells_workspace_keys': (c_i64, [c_int, c_int, c_int, c_int]),
+    'mmt_search_topk_cells': (c_int, [_SCAN, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                      c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

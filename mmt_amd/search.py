@@ -417,6 +417,23 @@ so the parts sum to sim(g, h) and, every product commuting and the denominator b
 (h, g).  4 096 x 128 pairs on 262 144 items x 7 x 512 take 1.40 ms on a float32 index, 0.79 ms on bfloat16 and 0.78 ms on
 float8_e4m3fn.  Out of scope: norm=, dynamic=, pooling= and item_pooling= raise ValueError naming the
 option -- the parts explain the plain score -- and there is no per-expert top-k over the whole gallery.
+
+Cell-probed search (`cells`, `search_probed`; `cells_from_centres`, `cells.probes`, `search_cells`): the inverted file,
+the cut of a scan PER QUERY that `subset=` (one set for the whole call), `where=` (64 tag bits, a tile skipped only when no
+row of a 64-query block wants it) and `rescore` (1 024 candidates, 64 rows computed to keep one) do not give.  The items
+are partitioned into cells, `index.cells(cell_ids)`, once: a CSR of item numbers sorted by (cell, item); the stored rows
+stay where they are.  `search_probed(q, qw, cells, probes, k)` takes int64 [NQ, P <= MAX_PROBES = 64] cell numbers per row
+(-1 = none, a repeat counts once) and row q of the result is the k best items of the union of its cells in `search`'s
+order -- equal scores by ascending item number across cells too -- then (-inf, -1): search(subset = those items) for that
+row, with the score bits of `search`, `rescore` and `target_scores`, on all three dtypes.  Exact; the approximation of an
+inverted file is the choice of cells, and that is the caller's: a k-means of their own and a coarse index, or
+`cells_from_centres(centres)`, which assigns every item to its best centre with `neighbours` and whose `probes` are
+`search` over the centres.  The (row, probe) pairs are regrouped on the device -- sorted by (cell, row), cut into groups of
+at most 64 rows and pieces of at most CELL_PIECE = 2 048 items (`probe_plan` is the numpy restatement) -- and one block per
+(group, piece) scans 64 x 128 tiles through two row tables with the K loop, epilogue, running top-k and merge of the other
+scans (mmt_search_topk_cells, search_cells.hip).  A result depends on the row's probes as a set alone.  Timings, tile counts
+and recall: DESIGN 9.24.  Out of scope: subset=, exclude=, after=, where=, norm=, dynamic=, pooling=, item_pooling= and
+grouping= raise ValueError naming the option; no trainer, no product quantisation, no re-ordering of the stored rows.
 """
 import ctypes
 import functools
@@ -444,6 +461,9 @@ _MAX_HITS = 1 << 27  # default cap of a range search's total: a guard against a 
 _NOT_SELF = ('norm', 'pooling', 'item_pooling', 'grouping', 'after', 'exclude', 'where')  # options the self-join refuses by name
 _NOT_EXPLAINED = ('norm', 'dynamic', 'pooling', 'item_pooling')  # options `search_explained` refuses by name
 _NOT_LSE = ('exclude', 'norm', 'pooling', 'item_pooling', 'after', 'grouping', 'where')  # options `query_lse` refuses by name
+MAX_PROBES = 64  # cells per query row of `search_probed`: a row's lists in the merge are MAX_PROBES * pieces * k keys
+CELL_PIECE = 2048  # items of a cell one block of the probed scan walks (16 tiles); a larger cell is cut into pieces
+_NOT_PROBED = ('subset', 'exclude', 'after', 'where', 'norm', 'dynamic', 'pooling', 'item_pooling', 'grouping')  # refused by name
 _GROUP_ROWS = 1 << 16  # rows per `neighbour_range` call of `duplicate_groups`: the CSR of a batch is dropped for its edges
 FP8 = torch.float8_e4m3fn
 _DTYPES = {torch.float32: 4, torch.bfloat16: 8, FP8: 16}  # storage dtype -> multiple d must have (16-byte folded rows)
@@ -886,6 +906,130 @@ def tag_pass(tags, masks):
   a, n, y = m[:, 0:1], m[:, 1:2], m[:, 2:3]
   zero = np.uint64(0)
   return ((t & a) == a) & ((t & n) == zero) & ((y == zero) | ((t & y) != zero))
+
+
+def cell_lists(cell_ids, num_cells):
+  """The CSR of `cells` restated in numpy: cell_ids int64 [num_items], values -1 .. num_cells - 1 (-1 = in no cell; a numpy
+  array or a torch tensor, copied to the host) -> (offsets int64 [num_cells + 1], items int64 [offsets[-1]]): the item
+  numbers sorted by (cell, item), cell c at offsets[c] .. offsets[c + 1]."""
+  ids = np.asarray(cell_ids.detach().cpu().numpy() if torch.is_tensor(cell_ids) else cell_ids, dtype=np.int64)
+  items = np.flatnonzero(ids >= 0)
+  items = items[np.argsort(ids[items], kind='stable')]
+  offsets = np.concatenate([[0], np.cumsum(np.bincount(ids[ids >= 0], minlength=num_cells))])
+  return offsets.astype(np.int64), items.astype(np.int64)
+
+
+def probe_plan(probes, offsets, piece=CELL_PIECE):
+  """The regrouping of `search_probed` (`_probe_plan`, which runs on the device) restated in numpy: probes int64 [NQ, P]
+  and the cells' offsets int64 [num_cells + 1] (numpy arrays or torch tensors, copied to the host) -> (pair_row int32 [n],
+  pair_slot int32 [n], work int32 [w, 5]), the tables of mmt_search_topk_cells without the device plan's padding.  A probe
+  outside 0 .. num_cells - 1 (-1 = none), an empty cell and a cell listed again in its row are dropped.  Every row is sorted
+  by cell, a dropped probe behind the others, and a pair's SLOT is its place in that sorted row; the pairs that stay are
+  ordered by (cell, row).  Each cell's pairs are cut into row groups of at most 64 and its items into ceil(size / piece)
+  pieces of at most `piece`; the work items go cell by cell, group by group, piece by piece, each (first pair, rows, first
+  position in the item table, end position, piece).  A function of the probes and the offsets alone.  The number of 64 x
+  128 tile K loops the scan runs is the sum over the work items of ceil((end - first) / 128)."""
+  host = lambda x: np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=np.int64)
+  p, off = host(probes), host(offsets)
+  c, sizes = off.shape[0] - 1, np.diff(off)
+  ok = (p >= 0) & (p < c)
+  ok &= sizes[np.where(ok, p, 0)] > 0
+  s = np.sort(np.where(ok, p, c), axis=1)
+  live = s < c
+  live[:, 1:] &= s[:, 1:] != s[:, :-1]
+  rows, slots = np.nonzero(live)
+  cell = s[rows, slots]
+  order = np.lexsort((rows, cell))
+  rows, slots, cell = rows[order], slots[order], cell[order]
+  work, start = [], 0
+  for ci, count in zip(*np.unique(cell, return_counts=True)):
+    for g in range(0, count, 64):
+      for pc in range(-(-sizes[ci] // piece)):
+        first = off[ci] + pc * piece
+        work.append((start + g, min(64, count - g), first, min(first + piece, off[ci + 1]), pc))
+    start += count
+  return rows.astype(np.int32), slots.astype(np.int32), np.array(work, dtype=np.int32).reshape(-1, 5)
+
+
+def _probe_plan(probes, offsets, max_pieces, piece=CELL_PIECE):
+  """`probe_plan` in torch, where the probes are (the device; any device works): probes int64 [NQ, P], offsets int64
+  [num_cells + 1 >= 2], max_pieces >= the largest cell's piece count -> (pair_row int32 [NQ * P], pair_slot int32 [NQ * P],
+  work int32 [W, 5]).  Nothing here waits for the device, so the lengths are upper bounds: the kept pairs come first in the
+  pair tables (behind them what the sort leaves of the dropped ones, which no work item refers to), and W = max_pieces *
+  min(NQ * P, num_cells + NQ * P // 64) bounds the work items -- a cell's row groups number ceil(pairs / 64) <= 1 + pairs //
+  64 and no more than its pairs -- the entries past the real count being zero: rows = 0, no work.  Two stable sorts (every
+  row by cell; the pairs by cell * NQ + row, a key no two kept pairs share), two searchsorted and a prefix sum: the same
+  probes give the same tables."""
+  nq, width = probes.shape
+  c, dev = offsets.shape[0] - 1, probes.device
+  sizes = offsets[1:] - offsets[:-1]
+  ok = (probes >= 0) & (probes < c)
+  ok &= sizes[probes.clamp(0, c - 1)] > 0
+  s, _ = torch.sort(torch.where(ok, probes, torch.full_like(probes, c)), dim=1, stable=True)
+  live = s < c
+  live[:, 1:] &= s[:, 1:] != s[:, :-1]
+  row = torch.arange(nq, device=dev, dtype=torch.int64).unsqueeze(1)
+  key, order = torch.sort(torch.where(live, s * nq + row, torch.full_like(s, c * nq)).reshape(-1), stable=True)
+  pair_row, pair_slot = (key % nq).to(torch.int32), (order % width).to(torch.int32)
+  bounds = torch.searchsorted(key, torch.arange(c + 1, device=dev, dtype=torch.int64) * nq)
+  start, count = bounds[:-1], bounds[1:] - bounds[:-1]            # a cell's first pair, its pairs
+  pieces = (sizes + (piece - 1)) // piece
+  per_cell = (count + 63) // 64 * pieces                           # row groups x pieces
+  end = torch.cumsum(per_cell, 0)
+  w = torch.arange(max_pieces * min(nq * width, c + nq * width // 64), device=dev, dtype=torch.int64)
+  cell = torch.searchsorted(end, w, right=True)
+  none = (cell >= c).unsqueeze(1)
+  cell = cell.clamp(max=c - 1)
+  local = w - (end - per_cell)[cell]
+  pcs = pieces[cell].clamp(min=1)
+  group, pc = local // pcs, local % pcs
+  first = offsets[cell] + pc * piece
+  work = torch.stack([start[cell] + 64 * group, (count[cell] - 64 * group).clamp(max=64), first,
+                      torch.minimum(first + piece, offsets[cell + 1]), pc], 1)
+  return pair_row, pair_slot, torch.where(none, torch.zeros_like(work), work).to(torch.int32).contiguous()
+
+
+class IndexCells:
+  """A partition of a VideoIndex's items into cells (VideoIndex.cells, cells_from_centres): the inverted file that
+  `search_probed` reads.  `offsets` int64 [num_cells + 1] and `items` int64: the item numbers sorted by (cell, item), cell c
+  at offsets[c] .. offsets[c + 1], so a cell's items ascend; `sizes` int64 [num_cells]; `num_cells`, `num_items` (the index
+  size it was built for), `device`; `max_pieces`: the pieces of CELL_PIECE items the largest cell is cut into, known here so
+  that no call has to ask the device.  `centres`: int64 [num_cells], the centre items of cells made by `cells_from_centres`
+  -- cell c is the cell of item centres[c] -- else None; only such cells answer `probes`.  The stored rows are not moved or
+  copied: the scan reads them through `items`."""
+
+  def __init__(self, index, offsets, items, num_items):
+    self._index = index
+    self.offsets, self.items = offsets, items
+    self.sizes = offsets[1:] - offsets[:-1]
+    self.num_cells, self.num_items, self.device = offsets.shape[0] - 1, num_items, offsets.device
+    self.max_pieces = max(1, -(-int(self.sizes.max()) // CELL_PIECE))   # the one wait for the device of the build
+    self.centres = self._subset = self._cell_of = None
+
+  def probes(self, embds, weights, nprobe):
+    """Queries as for `search` -> probes int64 [NQ, min(nprobe, num_cells)] for `search_probed`: per row the cells of its
+    nprobe best centres, best first -- search(embds, weights, k=nprobe, subset=subset(centres)) on the cells' index, the
+    item numbers mapped to cell numbers through a table, a vacant slot staying -1.  nprobe an int in 1 .. MAX_PROBES.
+    Only on cells made by `cells_from_centres`; with a quantiser of their own a caller takes the probes from its
+    coarse_index.search(...)[1]."""
+    if self.centres is None:
+      raise ValueError('probes: these cells were not made from centres; take the probes from a coarse index of your own')
+    if isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 1 <= nprobe <= MAX_PROBES:
+      raise ValueError('probes: nprobe must be an int in 1..%d, got %r' % (MAX_PROBES, nprobe))
+    if self._index.num_items != self.num_items:
+      raise ValueError('probes: the cells were built for %d items, the index holds %d' % (self.num_items, self._index.num_items))
+    _, best = self._index.search(embds, weights, k=nprobe, subset=self._subset)
+    return torch.where(best >= 0, self._cell_of[best.clamp(min=0)], best)
+
+
+class ShardedCells(IndexCells):
+  """The cells of a ShardedVideoIndex: IndexCells in global item numbers on the primary device, and `parts[s]`: shard s's
+  IndexCells -- the restriction of every cell to the items the shard holds, in its own numbers on its own device (None for
+  a shard without items)."""
+
+  def __init__(self, index, offsets, items, num_items, parts):
+    super().__init__(index, offsets, items, num_items)
+    self.parts = parts
 
 
 def connected_components(num_items, src, dst):
@@ -1759,6 +1903,121 @@ class _Index:
   def search_refined(self, embds, weights, coarse, k=10, shortlist=MAX_K, subset=None, exclude=None):
     return self._search_refined_filtered(embds, weights, coarse, k, shortlist, subset, exclude)
 
+  def _cell_ids(self, cell_ids, num_cells):
+    """The checks of `cells` -> (the labels as they came, contiguous; the number of cells).  One small reduction and a host
+    sync."""
+    if self.num_items == 0:
+      raise ValueError('cells: the index holds no items')
+    if not torch.is_tensor(cell_ids) or cell_ids.dtype != torch.int64:
+      raise ValueError('cells: cell_ids must be an int64 tensor, got %s' % (
+          cell_ids.dtype if torch.is_tensor(cell_ids) else type(cell_ids).__name__))
+    if cell_ids.device != self.device:
+      raise ValueError('cells: cell_ids must be on the index device %s, got %s' % (self.device, cell_ids.device))
+    if tuple(cell_ids.shape) != (self.num_items,):
+      raise ValueError('cells: cell_ids of shape (%d,) expected, got %s' % (self.num_items, tuple(cell_ids.shape)))
+    if num_cells is not None and (isinstance(num_cells, bool) or not isinstance(num_cells, int) or
+                                  not 1 <= num_cells < 2 ** 31):
+      raise ValueError('cells: num_cells must be None or an int in 1 .. 2^31 - 1, got %r' % (num_cells,))
+    lo, hi = (int(v) for v in torch.aminmax(cell_ids))
+    if num_cells is None:
+      num_cells = max(hi + 1, 1)
+    if lo < -1 or hi >= num_cells:
+      raise ValueError('cells: cell_ids must lie in -1 .. %d, got %d .. %d' % (num_cells - 1, lo, hi))
+    return cell_ids.contiguous(), num_cells
+
+  @staticmethod
+  def _cell_csr(cell_ids, num_cells):
+    """`cell_lists` on the device of the labels: -> (offsets int64 [num_cells + 1], items int64).  The length of `items`,
+    the number of labelled items, is a wait for the device."""
+    ids = torch.where(cell_ids >= 0, cell_ids, torch.full_like(cell_ids, num_cells))
+    ids, items = torch.sort(ids, stable=True)
+    offsets = torch.searchsorted(ids, torch.arange(num_cells + 1, device=ids.device, dtype=torch.int64))
+    return offsets, items[:int(offsets[-1])].contiguous()
+
+  def _cells(self, cells, who):
+    """Type, origin and age of `cells`."""
+    if type(cells) is not self._cells_type or cells._index is not self:
+      raise ValueError('%s: cells must come from the cells() or cells_from_centres() of this index, got %s' % (
+          who, type(cells).__name__ + (' of another index' if isinstance(cells, IndexCells) else '')))
+    if cells.num_items != self.num_items:
+      raise ValueError('%s: the cells were built for %d items, the index holds %d' % (who, cells.num_items, self.num_items))
+
+  def cells_from_centres(self, centres):
+    """centres: int64 [C] of distinct item numbers on the index device -> the cells of the coarse quantiser that needs no
+    second index and no trainer: cell c is the cell of item centres[c], and item g joins the cell of the centre that is
+    g's best stored item among the centres in `neighbours`' order -- neighbours(k=1, subset=subset(centres)) -- while a
+    centre belongs to its own cell.  `.centres` keeps them, and `.probes` then finds a query's cells with `search` over
+    the same subset.  Host code over existing calls; the checks cost one small reduction and a host sync."""
+    if not torch.is_tensor(centres) or centres.dtype != torch.int64:
+      raise ValueError('cells_from_centres: centres must be an int64 tensor, got %s' % (
+          centres.dtype if torch.is_tensor(centres) else type(centres).__name__))
+    if centres.device != self.device:
+      raise ValueError('cells_from_centres: centres must be on the index device %s, got %s' % (self.device, centres.device))
+    if centres.dim() != 1 or centres.shape[0] < 1:
+      raise ValueError('cells_from_centres: centres [C >= 1] expected, got %s' % (tuple(centres.shape),))
+    if self.num_items == 0:
+      raise ValueError('cells_from_centres: the index holds no items')
+    centres = centres.contiguous().clone()
+    lo, hi = (int(v) for v in torch.aminmax(centres))
+    if lo < 0 or hi >= self.num_items:
+      raise ValueError('cells_from_centres: centres must lie in 0 .. %d, got %d .. %d' % (self.num_items - 1, lo, hi))
+    c = centres.shape[0]
+    cell_of = torch.full((self.num_items,), -1, device=self.device, dtype=torch.int64)
+    cell_of[centres] = torch.arange(c, device=self.device, dtype=torch.int64)
+    if int((cell_of >= 0).sum()) != c:
+      raise ValueError('cells_from_centres: the centres must be distinct items')
+    subset = self.subset(centres)
+    _, best = self.neighbours(k=1, subset=subset)      # an item's best centre other than itself; -1: none (C = 1)
+    best = best[:, 0]
+    ids = torch.where(cell_of >= 0, cell_of, torch.where(best >= 0, cell_of[best.clamp(min=0)], best))
+    cells = self.cells(ids, c)
+    cells.centres, cells._subset, cells._cell_of = centres, subset, cell_of
+    return cells
+
+  def search_probed(self, embds, weights, cells, probes, k=10, **unsupported):
+    """Queries as for `search`; cells from this index's `cells` or `cells_from_centres`; probes int64 [NQ, P] on the index
+    device, 1 <= P <= MAX_PROBES = 64: the cells row q looks into, in any order, -1 (or anything outside 0 .. num_cells - 1)
+    = none, a cell listed twice counting once -> (scores [NQ, k] float32, indices [NQ, k] int64) on the device, k an int
+    in 1 .. MAX_K.  Row q holds the k best items of the union of its probed cells under `search`'s order -- score
+    descending, -0 tied with +0, equal scores by ascending ITEM NUMBER, across cells as within one -- and (-inf, -1) in the
+    slots left: row q is search(q, k, subset=subset(the probed cells' items)), padded.  That is exact; what is approximate
+    about an inverted file is the choice of cells, which is the caller's (`search_cells` makes it with the centres).
+    Every score has the very bits `search`, `rescore` and `target_scores` give the pair on this index, whatever its
+    dtype.  The result depends on a row's probes as a SET: not on their order, the other rows of the call, the row
+    batching, the launch geometry, or on a ShardedVideoIndex the shard.  The (row, probe) pairs are regrouped on the
+    device into blocks of at most 64 rows that want the same cell (`probe_plan` restates it), one launch scans them
+    through the cells' item table (mmt_search_topk_cells) and the merge of `search` joins a row's lists; per row batch the
+    workspace is 8 k P max_pieces bytes a row.  Nothing here waits for the device.  index.schedule has no effect.  Out
+    of scope: subset=, exclude=, after=, where=, norm=, dynamic=, pooling=, item_pooling= and grouping= raise ValueError
+    naming the option."""
+    for name in unsupported:
+      if name not in _NOT_PROBED:
+        raise TypeError('search_probed() got an unexpected keyword argument %r' % name)
+      raise ValueError('search_probed: %s= is out of scope: the candidates are the probed cells and nothing else' % name)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+      raise ValueError('search_probed: k must be an int in 1..%d, got %r' % (MAX_K, k))
+    self._cells(cells, 'search_probed')
+    if not torch.is_tensor(probes) or probes.dtype != torch.int64:
+      raise ValueError('search_probed: probes must be an int64 tensor, got %s' % (
+          probes.dtype if torch.is_tensor(probes) else type(probes).__name__))
+    if probes.device != self.device:
+      raise ValueError('search_probed: probes must be on the index device %s, got %s' % (self.device, probes.device))
+    if probes.dim() != 2 or not 1 <= probes.shape[1] <= MAX_PROBES:
+      raise ValueError('search_probed: probes [NQ, 1 <= P <= %d] expected, got %s' % (MAX_PROBES, tuple(probes.shape)))
+    q, qw = self._queries(embds, weights)
+    if probes.shape[0] != q.shape[0]:
+      raise ValueError('search_probed: %d queries but probes %s' % (q.shape[0], tuple(probes.shape)))
+    if q.shape[0] == 0 or cells.items.shape[0] == 0:
+      return _lists(2, self.device, q.shape[0], k, vacant=True)
+    return self._search_probed(q, qw, cells, probes.contiguous(), k)
+
+  def search_cells(self, embds, weights, cells, nprobe=8, k=10):
+    """The inverted-file search as one call: cells.probes(embds, weights, nprobe), then search_probed(embds, weights,
+    cells, those probes, k) -> (scores, indices) [NQ, k].  cells from this index's `cells_from_centres`.  The probes follow
+    index.schedule, as any `search` does; the probed scan does not.  Host code only."""
+    self._cells(cells, 'search_cells')
+    return self.search_probed(embds, weights, cells, cells.probes(embds, weights, nprobe), k)
+
   def _candidate_lists(self, who, candidates, widest=MAX_DC, rows='R'):
     """Type, device and shape of the candidate lists of `pair_scores` and `diversify` -- and, `widest` = MAX_C wide, of
     `expert_scores` and `pair_expert_scores` -- in the words of `rescore`'s checks."""
@@ -2309,6 +2568,36 @@ class VideoIndex(_Index):
     index's own storage and `nbytes` do not change.  It describes the num_items of this moment: after a further `add` it
     is refused.  Nothing here waits for the device."""
     return IndexTagging(self._tags(tags))
+
+  _cells_type = IndexCells
+
+  def cells(self, cell_ids, num_cells=None):
+    """cell_ids: int64 [num_items] on the index device, the cell of every item, any labelling in 0 .. num_cells - 1, -1 =
+    in no cell (num_cells None = the largest label + 1; a cell may be empty) -> IndexCells for `search_probed`: the
+    inverted file, built here once like a grouping -- one stable sort and a searchsorted; the range check, the number of
+    labelled items and the largest cell's size are its waits for the device.  The stored rows are not moved or copied and
+    `nbytes` does not change: the scan reads them through the cells' item table.  It describes the num_items of this
+    moment: after a further `add` it is refused."""
+    ids, num_cells = self._cell_ids(cell_ids, num_cells)
+    return IndexCells(self, *self._cell_csr(ids, num_cells), self.num_items)
+
+  def _search_probed(self, q, qw, cells, probes, k):
+    """`search_probed` behind its checks: q (NQ >= 1, M, d) / qw (NQ, M) fp32 and probes int64 [NQ, P] (contiguous) on the
+    index device, cells this index's own with at least one item.  Per row batch the plan (torch, on the device), one
+    workspace of P * max_pieces lists of k keys per row and one call.  Nothing here waits for the device."""
+    nq, width, L, nothing = q.shape[0], probes.shape[1], _lib.lib(), _Scan()
+    outs = _lists(2, self.device, nq, k)
+    with torch.cuda.device(self.device):
+      for r0, r1 in self._row_batches(nq, 8 * k * width * cells.max_pieces):
+        pair_row, pair_slot, work = _probe_plan(probes[r0:r1], cells.offsets, cells.max_pieces)
+        desc, _, _, _keep = self._describe(nothing, q, qw, r0, r1)
+        ws = torch.empty(L.mmt_topk_cells_workspace_keys(r1 - r0, width, cells.max_pieces, k), device=self.device,
+                         dtype=torch.int64)
+        check(L.mmt_search_topk_cells(desc, ops._p(cells.items), cells.items.shape[0], ops._p(work), work.shape[0],
+                                      ops._p(pair_row), ops._p(pair_slot), pair_row.shape[0], width, cells.max_pieces, k,
+                                      ops._p(ws), ops._p(outs[0][r0:r1]), ops._p(outs[1][r0:r1]), ops._stream()),
+              'mmt_search_topk_cells')
+    return outs
 
   @staticmethod
   def _filter_args(scan, r0, r1, nq):
@@ -3338,6 +3627,33 @@ class ShardedVideoIndex(_Index):
           part = IndexTagging(local.to(sh.device))
       parts.append(part)
     return ShardedTagging(parts, tags)
+
+  _cells_type = ShardedCells
+
+  def cells(self, cell_ids, num_cells=None):
+    """cell_ids: int64 [num_items] on the primary device, as VideoIndex.cells -> ShardedCells: every shard gets the
+    restriction of each cell to the items it holds, in its own numbers (a shard's item table is increasing, so a cell's
+    items ascend there as they do globally).  After a further `add` it is refused."""
+    ids, num_cells = self._cell_ids(cell_ids, num_cells)
+    parts = []
+    for sh in self.shards:
+      part = None
+      if sh.num_items:
+        local = ids[sh.ids[:sh.num_items]]  # gathered on the primary, where the table is
+        with torch.cuda.device(sh.device):
+          part = IndexCells(sh.index, *self._cell_csr(local.to(sh.device), num_cells), sh.num_items)
+      parts.append(part)
+    return ShardedCells(self, *self._cell_csr(ids, num_cells), self.num_items, parts)
+
+  def _search_probed(self, q, qw, cells, probes, k):
+    """`search_probed` behind its checks: q, qw and probes on the primary.  Every shard that holds items of a cell answers
+    for the same probes over its part of the cells and returns its lists in its own numbers, the slots it cannot fill
+    vacant; an item lives on one shard, and the merge applies the global tie rule (mmt_search_merge_lists)."""
+    outs = _lists(2, self.device, q.shape[0], k)
+    live = [(s, sh) for s, sh in self._live() if cells.parts[s].items.shape[0]]
+    lists = lambda s, sh: sh.index._search_probed(q.to(sh.device), qw.to(sh.device), cells.parts[s],
+                                                  probes.to(sh.device), k)
+    return self._merged(outs, live, k, 'mmt_search_merge_lists', self._tables(tuple(s for s, _ in live)), lists)
 
   def _search_groups(self, q, qw, k, grouping, subset):
     """`search_groups` behind its checks: q, qw on the primary, 1 <= k <= grouping.num_groups.  Every live shard returns its

@@ -131,7 +131,16 @@ and an fp8 index, every pair of variants alternated in one process, --runs round
 (b) 16 distinct predicates interleaved over the rows, each passing about 1/16 of randomly placed items, against the route
 without where=: 16 subset= searches over gathered row groups, bitmap builds included; (c) one predicate shared by all rows
 that passes one contiguous sixteenth of the gallery against subset= of the same items -- the tile skip; (d) one query on
-the streaming schedule (bf16, fp8) with and without a predicate.  Default output profiles/search_where_bench.json."""
+the streaming schedule (bf16, fp8) with and without a predicate.  Default output profiles/search_where_bench.json.
+
+--cells times the cell-probed search (search_probed) over 262 144 items drawn from 1 024 planted clusters (a unit centre plus
+unit noise per expert: an inverted file on isotropic data says nothing), k = 10, with 1 024 cells from randomly sampled
+centres (cells_from_centres), at NQ = 1, 64 and 4 096 and nprobe = 1, 4, 16 and 64 on a float32, a bf16 and an fp8 index:
+`search_probed` against `search` on the same index and, where every row's probed union fits 1 024 items, against `rescore`
+on that union; --runs rounds on device events, every variant once per round, interleaved; median and spread.  Beside the
+times: the 64 x 128 tile K loops each route executes (the probed scan's from search.probe_plan), whose ratio is the derived
+expectation; the regrouping alone (the torch plan), timed on its own; recall@10 of `search_cells` against `search`, per
+nprobe -- a property of the quantiser, reported and never a test.  Default output profiles/search_cells_bench.json."""
 import argparse
 import json
 import math
@@ -796,6 +805,102 @@ def where_mode(a, dev):
   return row
 
 
+def cells_mode(a, dev):
+  """search_probed against search and rescore on planted clusters (module docstring, --cells)."""
+  from mmt_amd import search
+  nv, chunk, ncells, nq_all = SHAPES['S3'][1], 8192, 1024, 4096
+  gen = torch.Generator(device=dev).manual_seed(0)
+  nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
+  noise = lambda n: torch.randn(n, M, D, device=dev, generator=gen) / math.sqrt(D)
+  planted = nrm(torch.randn(ncells, M, D, device=dev, generator=gen))
+  dtypes = {'float32': torch.float32, 'bfloat16': torch.bfloat16, 'float8_e4m3fn': torch.float8_e4m3fn}
+  idx = {n: VideoIndex.empty(nv, M, D, dev, dtype=t) for n, t in dtypes.items()}
+  source = torch.randint(0, nv, (nq_all,), device=dev, generator=gen)       # a query is a noisy copy of a stored item
+  q = torch.empty(nq_all, M, D, device=dev)
+  for at in range(0, nv, chunk):
+    g = nrm(planted[torch.randint(0, ncells, (chunk,), device=dev, generator=gen)] + noise(chunk))
+    gw = torch.softmax(torch.randn(chunk, M, device=dev, generator=gen), -1)
+    for index in idx.values():
+      index.add(g, gw)
+    mine = (source >= at) & (source < at + chunk)
+    q[mine] = g[source[mine] - at]
+  q = nrm(q + noise(nq_all))
+  qw = torch.softmax(torch.randn(nq_all, M, device=dev, generator=gen), -1)
+  centres = torch.randperm(nv, device=dev, generator=gen)[:ncells]
+  row = {'NV': nv, 'num_cells': ncells, 'cell_piece': search.CELL_PIECE, 'index_bytes': {n: idx[n].nbytes for n in idx}}
+  same = lambda x, y: bool(torch.equal(x[1], y[1]) and torch.equal(x[0].view(torch.int32), y[0].view(torch.int32)))
+  for n, index in idx.items():
+    cells = index.cells_from_centres(centres)
+    sizes = cells.sizes.cpu().numpy()
+    offsets, items = cells.offsets.cpu().numpy(), cells.items.cpu().numpy()
+    row[n + '/cells'] = dict(size_min=int(sizes.min()), size_median=float(np.median(sizes)), size_max=int(sizes.max()),
+                             max_pieces=cells.max_pieces)
+    exact = index.search(q, qw, k=K)[1]
+    probes = {p: cells.probes(q, qw, p) for p in (1, 4, 16, 64)}
+    for p, pr in probes.items():                                            # recall@10 at 4 096 queries
+      got = index.search_probed(q, qw, cells, pr, k=K)[1]
+      hit = (got.unsqueeze(2) == exact.unsqueeze(1)).any(2).float().sum(1) / K
+      row['%s/recall_at_10/nprobe%d' % (n, p)] = float(hit.mean())
+    for nq in (1, 64, nq_all):
+      qq, ww = q[:nq], qw[:nq]
+      fns = {'search': lambda: index.search(qq, ww, k=K)}
+      tiles = {'search': -(-nq // 64) * -(-nv // 128)}
+      notes = {}
+      for p, pr in probes.items():
+        mine = pr[:nq].contiguous()
+        fns['probed_%d' % p] = lambda mine=mine: index.search_probed(qq, ww, cells, mine, k=K)
+        fns['plan_%d' % p] = lambda mine=mine: search._probe_plan(mine, cells.offsets, cells.max_pieces)
+        host = mine.cpu().numpy()
+        work = search.probe_plan(host, offsets)[2]
+        tiles['probed_%d' % p] = int((-(-(work[:, 3] - work[:, 2]) // 128)).sum())
+        union = [np.concatenate([items[offsets[c]:offsets[c + 1]] for c in np.unique(r[r >= 0])] or [items[:0]]) for r in host]
+        widest = max(len(u) for u in union)
+        if widest <= search.MAX_C:                                          # the route a caller has today for such rows
+          cand = np.full((nq, widest), -1, np.int64)
+          for r, u in enumerate(union):
+            cand[r, :len(u)] = u
+          cand = torch.from_numpy(cand).to(dev)
+          fns['rescore_%d' % p] = lambda cand=cand: index.rescore(qq, ww, cand, k=K)
+          tiles['rescore_%d' % p] = -(-nq // 64) * -(-64 * widest // 128)
+          notes['rescore_%d' % p] = 'C = %d' % widest
+        else:
+          notes['rescore_%d' % p] = 'not run: the widest probed union holds %d items' % widest
+      ts, out = {v: [] for v in fns}, {}
+      for _ in range(a.runs):          # interleaved: drift hits the variants alike
+        for v, fn in fns.items():
+          t, _, _, out[v] = timed(fn, a.min_seconds)
+          ts[v].append(t)
+      cell = {v: dict(seconds_median=float(np.median(ts[v])), seconds_spread=max(ts[v]) - min(ts[v]), seconds_runs=ts[v])
+              for v in fns}
+      for v, t in tiles.items():
+        cell[v]['tile_k_loops'] = t
+      base = cell['search']
+      summary = {'notes': notes}
+      for p in probes:
+        c = cell['probed_%d' % p]
+        s = dict(search_over_probed_seconds=base['seconds_median'] / c['seconds_median'],
+                 search_over_probed_tiles=base['tile_k_loops'] / max(1, c['tile_k_loops']),
+                 plan_share_of_probed=cell['plan_%d' % p]['seconds_median'] / c['seconds_median'],
+                 spreads_combined=base['seconds_spread'] + c['seconds_spread'],
+                 probed_faster_beyond_spread=bool(base['seconds_median'] - c['seconds_median'] >
+                                                  base['seconds_spread'] + c['seconds_spread']))
+        if 'rescore_%d' % p in cell:
+          r = cell['rescore_%d' % p]
+          padded = tuple(torch.cat([t, torch.full((nq, K - t.shape[1]), v, device=dev, dtype=t.dtype)], 1) if t.shape[1] < K else t
+                         for t, v in zip(out['rescore_%d' % p], (float('-inf'), -1)))
+          s.update(rescore_over_probed_seconds=r['seconds_median'] / c['seconds_median'],
+                   rescore_over_probed_tiles=r['tile_k_loops'] / max(1, c['tile_k_loops']),
+                   same_bits_as_rescore=same(out['probed_%d' % p], padded))
+        summary['nprobe%d' % p] = s
+      cell['summary'] = summary
+      row['%s/nq%d' % (n, nq)] = cell
+      print('%s nq=%d: search %.3f ms; %s' % (n, nq, 1e3 * base['seconds_median'], ', '.join(
+          'nprobe %d: %.3f ms (plan %.3f), tiles %d' % (p, 1e3 * cell['probed_%d' % p]['seconds_median'],
+                                                        1e3 * cell['plan_%d' % p]['seconds_median'],
+                                                        cell['probed_%d' % p]['tile_k_loops']) for p in probes)), file=sys.stderr)
+  return row
+
+
 def composed_rescore(index, q, qw, cand, k):
   """What `rescore` replaces, from the public calls: `target_scores` of the candidates (MAX_T columns per launch), then
   `search`'s order in torch -- two stable sorts, by item and then by descending score with -0 as +0 and none last.
@@ -1191,6 +1296,9 @@ def main():
   ap.add_argument('--where', action='store_true', help='time search(where=) at 4 096 x 262 144, k = 10, on a float32, a bf16 and '
                   'an fp8 index: zero masks against plain search, 16 predicates against 16 subset searches, a shared '
                   'contiguous predicate against the same subset, one streamed query with and without a predicate')
+  ap.add_argument('--cells', action='store_true', help='time search_probed at 1, 64 and 4 096 queries x 262 144 clustered items '
+                  'in 1 024 cells, nprobe = 1, 4, 16, 64, k = 10, on a float32, a bf16 and an fp8 index, against search and '
+                  'rescore; tile counts and recall@10 beside the times')
   ap.add_argument('--shapes', default='S1,S2,S3')
   ap.add_argument('--out', default=None)
   ap.add_argument('--min-seconds', type=float, default=0.5)
@@ -1269,6 +1377,17 @@ def main():
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
+  if a.cells:
+    res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'cells', 'runs': a.runs,
+           'min_seconds': a.min_seconds}
+    res.update(cells_mode(a, dev))
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                'search_cells_bench.json')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+      json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return
   if a.where:
     res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'where', 'runs': a.runs,
            'min_seconds': a.min_seconds}
