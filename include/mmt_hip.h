@@ -881,6 +881,38 @@ int mmt_search_topk_cells(const MmtSearchScan* scan, const int64_t* items, int n
                           const int32_t* pair_row, const int32_t* pair_slot, int n_pairs, int P, int pieces, int k,
                           uint64_t* ws, float* scores, int64_t* index, void* stream);
 
+/* The k-means update over the stored items (search_kmeans.hip), additive: three entries, nothing that exists changes,
+ * MmtSearchScan stays 21 fields / 128 bytes and mmt_abi_version() stays 6.  They serve search.py's `cell_sums`,
+ * `cell_centroids` and `train_cells`.  With f_g the dequantised stored row of item g (fp32 as it is, bf16 widened, fp8 code
+ * x the item's scale: exact), gw_g its weights and L a cell's slice of `items` (ascending, n = |L|):
+ *   S[m] = sum_{g in L} f_g[m], w[m] = sum_{g in L} gw_g[m]; G_c[m] = S[m] / |S[m]|_2 (zero S[m]: a zero row), gw_c[m] = w[m] / n.
+ * mmt_search_cell_sums (fp32, bf16, fp8): the partial sums of the pieces of the cells' lists.
+ *   g, gw, gscale, storage, NV, M, d: the stored operand as in mmt_search_expert_parts (gscale exactly when fp8).
+ *   items int64 [n_items]: the item numbers cell after cell; a value outside 0 .. NV - 1 contributes nothing: checked on
+ *     the device, never dereferenced.
+ *   work int32 [n_work][3] = (cell, first position in items, end position): one piece, at most MMT_SEARCH_SUM_PIECE
+ *     consecutive positions of one cell.  end <= first, positions outside 0 .. n_items or a longer piece mean "no work"
+ *     (a zero partial row): n_work may be an upper bound known without waiting for the device.
+ *   ws fp32 [mmt_cell_sums_workspace_floats(n_work, M, d)] = n_work * M * (d + 1): [n_work][M d] partial rows, then
+ *     [n_work][M] partial weights.  One block per (piece, slab of MMT_SEARCH_SUM_SLAB columns); a thread owns its columns
+ *     and adds the piece's rows in ascending position, one rounded fp32 add each, from +0.  One writer per slot.
+ * mmt_search_cell_centroids: one block per cell joins the partial rows piece_start[c] .. piece_start[c + 1] - 1 (int32
+ *   [C + 1]) in ascending order from +0 into sums fp32 [C][M d] and wsums [C][M] (always written, zero for a cell without
+ *   pieces); n = offsets[c + 1] - offsets[c] (int64 [C + 1]).  embds [C][M][d] / weights [C][M] fp32, both or neither, are
+ *   in/out: the centroid of a cell with n > 0 is written, the rows of an empty cell are left as they are.  A cell whose
+ *   piece range is not inside 0 .. n_work or whose offsets are not inside 0 .. n_items is treated as empty.
+ * The order of every sum is a function of a row's position in its cell's list and of the column alone; two calls are
+ * bit-identical.  MMT_ERR_ARG: a null operand, table, workspace or output (embds without weights), gscale on fp32 / bf16 or
+ * none on fp8, NV / n_items / n_work / C < 1, M outside 1 .. 16, d not a multiple of 4 (bf16: 8, fp8: 16), M d >= 2^27;
+ * MMT_ERR_ALIGN: g or ws off a 16-byte boundary.  All refused on the host before any launch.  No atomics, no scratch. */
+#define MMT_SEARCH_SUM_PIECE 256
+#define MMT_SEARCH_SUM_SLAB 1024
+int64_t mmt_cell_sums_workspace_floats(int n_work, int M, int d);
+int mmt_search_cell_sums(const void* g, const float* gw, const float* gscale, int storage, int NV, int M, int d,
+                         const int64_t* items, int n_items, const int32_t* work, int n_work, float* ws, void* stream);
+int mmt_search_cell_centroids(const float* ws, int n_work, const int32_t* piece_start, const int64_t* offsets, int n_items,
+                              int C, int M, int d, float* sums, float* wsums, float* embds, float* weights, void* stream);
+
 /* Beside the scans.
  * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> the subset words, padding included: one ballot per 64
  *   items, one writer per word.

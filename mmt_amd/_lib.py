@@ -293,6 +293,13 @@ SIGNATURES = {
     'mmt_topk_cells_workspace_keys': (c_i64, [c_int, c_int, c_int, c_int]),
     'mmt_search_topk_cells': (c_int, [_SCAN, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp,
                                       c_vp, c_vp]),
+    # the k-means update, additive: (n_work, M, d); the stored operand (g, gw, gscale, storage, NV, M, d), items, n_items,
+    # work, n_work, the workspace, the stream; the workspace, n_work, piece_start, offsets, n_items, C, M, d, sums, wsums,
+    # embds, weights, the stream
+    'mmt_cell_sums_workspace_floats': (c_i64, [c_int, c_int, c_int]),
+    'mmt_search_cell_sums': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp]),
+    'mmt_search_cell_centroids': (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

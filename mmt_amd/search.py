@@ -434,6 +434,23 @@ at most 64 rows and pieces of at most CELL_PIECE = 2 048 items (`probe_plan` is 
 scans (mmt_search_topk_cells, search_cells.hip).  A result depends on the row's probes as a set alone.  Timings, tile counts
 and recall: DESIGN 9.24.  Out of scope: subset=, exclude=, after=, where=, norm=, dynamic=, pooling=, item_pooling= and
 grouping= raise ValueError naming the option; no trainer, no product quantisation, no re-ordering of the stored rows.
+
+K-means cells (`train_cells`, `cell_sums`, `cell_centroids`; `CellQuantiser`): the trainer the inverted file lacked.  A
+stored item is its folded row f_g = gw_g (.) G_g and its weights gw_g; for a cell with member list L (its slice of
+`IndexCells.items`, ascending, n = |L|)
+    S[m] = sum_{g in L} f_g[m]      w[m] = sum_{g in L} gw_g[m]      G_c[m] = S[m] / |S[m]|_2      gw_c[m] = w[m] / n
+on the stored values dequantised exactly: spherical k-means per expert, weighted by the gate -- a member without a
+modality adds nothing to that expert, an expert missing in every member has weight 0 in the centroid and a zero row, and
+the centroid of a one-item cell is the item.  `cell_sums` and `cell_centroids` are the update step (search_kmeans.hip:
+a cell's list is cut into pieces of SUM_PIECE = 256 positions, a thread owns its columns and adds a piece's rows in
+ascending position, one block per cell joins the pieces in ascending order; no atomics, so two calls are bit-identical
+and a cell's sums do not depend on the other cells, num_items or the launch -- `cell_sums_ref` restates the order);
+the assignment step is `centroids.neighbours(k=1, source=index)` against a VideoIndex of the centroids in the gallery's
+dtype.  `train_cells(num_cells, iters)` is the Lloyd loop around them, deterministic, with empty cells re-seeded by the
+worst-served items (`reseed_ref`), and returns a `CellQuantiser`: `.assign(index)` gives that index's cells, whose
+`probes` and `search_cells` then work as on cells made from centres.  Timings and recall: DESIGN 9.25.  Out of scope:
+a ShardedVideoIndex (training on a sample held in one index is the usual practice), subset=, where=, norm=, pooling= and
+item_pooling=: ValueError naming the call or the option.
 """
 import ctypes
 import functools
@@ -464,6 +481,9 @@ _NOT_LSE = ('exclude', 'norm', 'pooling', 'item_pooling', 'after', 'grouping', '
 MAX_PROBES = 64  # cells per query row of `search_probed`: a row's lists in the merge are MAX_PROBES * pieces * k keys
 CELL_PIECE = 2048  # items of a cell one block of the probed scan walks (16 tiles); a larger cell is cut into pieces
 _NOT_PROBED = ('subset', 'exclude', 'after', 'where', 'norm', 'dynamic', 'pooling', 'item_pooling', 'grouping')  # refused by name
+SUM_PIECE = 256  # positions of a cell's list one block of `cell_sums` adds; a longer list is cut into pieces
+SUM_SLAB = 1024  # columns of the M * d one block of `cell_sums` takes
+_NOT_TRAINED = ('subset', 'where', 'norm', 'pooling', 'item_pooling')  # options the k-means calls refuse by name
 _GROUP_ROWS = 1 << 16  # rows per `neighbour_range` call of `duplicate_groups`: the CSR of a batch is dropped for its edges
 FP8 = torch.float8_e4m3fn
 _DTYPES = {torch.float32: 4, torch.bfloat16: 8, FP8: 16}  # storage dtype -> multiple d must have (16-byte folded rows)
@@ -989,14 +1009,116 @@ def _probe_plan(probes, offsets, max_pieces, piece=CELL_PIECE):
   return pair_row, pair_slot, torch.where(none, torch.zeros_like(work), work).to(torch.int32).contiguous()
 
 
+def cell_sums_ref(rows, weights, offsets, items, piece=SUM_PIECE):
+  """The order of `cell_sums` (mmt_search_cell_sums, mmt_search_cell_centroids) restated in numpy: rows float32
+  [num_items, M * d], the stored rows dequantised; weights float32 [num_items, M]; offsets and items the cells' CSR (numpy
+  arrays or torch tensors, copied to the host) -> (sums float32 [C, M * d], wsums float32 [C, M], counts int64 [C]).  A
+  cell's list is cut into pieces of at most `piece` positions; a piece's rows are added in ascending position, one fp32
+  add each from +0, and the pieces' partial rows in ascending order, again from +0.  Bit for bit what the kernels give."""
+  host = lambda x: np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x)
+  rows, weights = host(rows).astype(np.float32, copy=False), host(weights).astype(np.float32, copy=False)
+  off, items = host(offsets).astype(np.int64), host(items).astype(np.int64)
+  c = off.shape[0] - 1
+  sums, wsums = np.zeros((c, rows.shape[1]), np.float32), np.zeros((c, weights.shape[1]), np.float32)
+  for ci in range(c):
+    for first in range(off[ci], off[ci + 1], piece):
+      part, wpart = np.zeros(rows.shape[1], np.float32), np.zeros(weights.shape[1], np.float32)
+      for g in items[first:min(first + piece, off[ci + 1])]:
+        part, wpart = part + rows[g], wpart + weights[g]
+      sums[ci], wsums[ci] = sums[ci] + part, wsums[ci] + wpart
+  return sums, wsums, np.diff(off)
+
+
+def reseed_ref(ids, scores, items, num_cells):
+  """The re-seeding rule of `train_cells` restated in numpy: ids int64 [num_items], the labels after an assignment (-1 =
+  not in the sample); items int64 [T] ascending, the training sample; scores float32 [T], the score of items[i] under its
+  best centroid -> the labels with the empty cells filled.  The E cells without an item, in ascending cell number,
+  receive the E items of the sample with the lowest scores -- a stable sort by score over ascending item numbers, so equal
+  scores go to the smaller number -- and those items are relabelled.  A cell the relabelling empties stays empty."""
+  ids, items = np.array(ids, dtype=np.int64), np.asarray(items, dtype=np.int64)
+  empty = np.flatnonzero(np.bincount(ids[items], minlength=num_cells) == 0)
+  worst = items[np.argsort(np.asarray(scores, dtype=np.float32), kind='stable')[:len(empty)]]
+  ids[worst] = empty
+  return ids
+
+
+def _reseed(ids, scores, items, num_cells):
+  """`reseed_ref` in torch, where the labels are: nothing here waits for the device.  Cell c, when empty, is the e-th empty
+  cell and takes the e-th item of the stable sort; the cells that have items write to a slot behind the labels."""
+  n = ids.shape[0]
+  empty = torch.bincount(ids[items], minlength=num_cells) == 0
+  nth = (torch.cumsum(empty, 0) - 1).clamp(min=0, max=items.shape[0] - 1)
+  worst = items[torch.sort(scores, stable=True)[1]][nth]
+  out = torch.cat([ids, ids.new_zeros(1)])
+  out.scatter_(0, torch.where(empty, worst, torch.full_like(worst, n)), torch.arange(num_cells, device=ids.device))
+  return out[:n]
+
+
+def _sum_plan(offsets, n_work, piece=SUM_PIECE):
+  """The piece tables of `cell_sums`, in torch where the offsets are (the device; any device works): offsets int64
+  [num_cells + 1], n_work >= the number of pieces, a bound the host knows without waiting (ceil(labelled / piece) +
+  num_cells) -> (work int32 [n_work, 3] = (cell, first position, end position), cell by cell, piece by piece, the entries
+  past the real count zero: no work; piece_start int32 [num_cells + 1]: cell c's pieces are piece_start[c] ..
+  piece_start[c + 1] - 1)."""
+  c = offsets.shape[0] - 1
+  sizes = offsets[1:] - offsets[:-1]
+  pieces = (sizes + (piece - 1)) // piece
+  end = torch.cumsum(pieces, 0)
+  w = torch.arange(n_work, device=offsets.device, dtype=torch.int64)
+  cell = torch.searchsorted(end, w, right=True)
+  none = (cell >= c).unsqueeze(1)
+  cell = cell.clamp(max=c - 1)
+  first = offsets[cell] + (w - (end - pieces)[cell]) * piece
+  work = torch.stack([cell, first, torch.minimum(first + piece, offsets[cell + 1])], 1)
+  start = torch.cat([end.new_zeros(1), end])
+  return torch.where(none, torch.zeros_like(work), work).to(torch.int32).contiguous(), start.to(torch.int32)
+
+
+class CellQuantiser:
+  """A trained coarse quantiser (VideoIndex.train_cells).  `centroids`: a VideoIndex of num_cells items in the gallery's
+  dtype, M and d -- item c is the centroid of cell c, folded and rounded by `add`; `embds` [num_cells, M, d] and `weights`
+  [num_cells, M]: the unrounded fp32 values it was built from; `objective` and `moved`: device tensors [iterations], the
+  mean score of a training item under its best centroid at each assignment and the labels that changed against the
+  iteration before; `iterations`: the iterations run (fewer than asked when an assignment moved nothing); `num_cells`."""
+
+  def __init__(self, centroids, embds, weights, objective, moved):
+    self.centroids, self.embds, self.weights = centroids, embds, weights
+    self.objective, self.moved = objective, moved
+    self.iterations, self.num_cells = objective.shape[0], centroids.num_items
+
+  def assign(self, index, **unsupported):
+    """index: a VideoIndex with the centroids' dtype, num_experts and dim on their device -> its IndexCells over ALL its
+    items: item g joins the cell of its best centroid, centroids.neighbours(k=1, source=index), ties to the lower cell.
+    The cells carry `.quantiser`, so `cells.probes` and `index.search_cells` work on them.  Not on a ShardedVideoIndex."""
+    for name in unsupported:
+      if name not in _NOT_TRAINED:
+        raise TypeError('assign() got an unexpected keyword argument %r' % name)
+      raise ValueError('assign: %s= is out of scope: every item joins the cell of its best centroid' % name)
+    if hasattr(index, 'shards'):
+      raise ValueError('assign: not available on a ShardedVideoIndex; assign the items of one VideoIndex')
+    _, best = self.centroids.neighbours(k=1, source=index)
+    cells = index.cells(best[:, 0].contiguous(), self.num_cells)
+    cells.quantiser = self
+    return cells
+
+  def probes(self, embds, weights, nprobe):
+    """Queries as for `search` -> probes int64 [NQ, min(nprobe, num_cells)] for `search_probed`: per row the cells of its
+    nprobe best centroids, best first -- centroids.search(k=nprobe)[1]: the item numbers of the centroid index are the cell
+    numbers.  nprobe an int in 1 .. MAX_PROBES."""
+    if isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 1 <= nprobe <= MAX_PROBES:
+      raise ValueError('probes: nprobe must be an int in 1..%d, got %r' % (MAX_PROBES, nprobe))
+    return self.centroids.search(embds, weights, k=min(nprobe, self.num_cells))[1]
+
+
 class IndexCells:
   """A partition of a VideoIndex's items into cells (VideoIndex.cells, cells_from_centres): the inverted file that
   `search_probed` reads.  `offsets` int64 [num_cells + 1] and `items` int64: the item numbers sorted by (cell, item), cell c
   at offsets[c] .. offsets[c + 1], so a cell's items ascend; `sizes` int64 [num_cells]; `num_cells`, `num_items` (the index
   size it was built for), `device`; `max_pieces`: the pieces of CELL_PIECE items the largest cell is cut into, known here so
   that no call has to ask the device.  `centres`: int64 [num_cells], the centre items of cells made by `cells_from_centres`
-  -- cell c is the cell of item centres[c] -- else None; only such cells answer `probes`.  The stored rows are not moved or
-  copied: the scan reads them through `items`."""
+  -- cell c is the cell of item centres[c] -- else None; `quantiser`: the CellQuantiser of cells made by its `assign`, else
+  None; only cells with one of the two answer `probes`.  The stored rows are not moved or copied: the scan reads them
+  through `items`."""
 
   def __init__(self, index, offsets, items, num_items):
     self._index = index
@@ -1004,7 +1126,7 @@ class IndexCells:
     self.sizes = offsets[1:] - offsets[:-1]
     self.num_cells, self.num_items, self.device = offsets.shape[0] - 1, num_items, offsets.device
     self.max_pieces = max(1, -(-int(self.sizes.max()) // CELL_PIECE))   # the one wait for the device of the build
-    self.centres = self._subset = self._cell_of = None
+    self.centres = self._subset = self._cell_of = self.quantiser = None
 
   def probes(self, embds, weights, nprobe):
     """Queries as for `search` -> probes int64 [NQ, min(nprobe, num_cells)] for `search_probed`: per row the cells of its
@@ -1012,6 +1134,10 @@ class IndexCells:
     item numbers mapped to cell numbers through a table, a vacant slot staying -1.  nprobe an int in 1 .. MAX_PROBES.
     Only on cells made by `cells_from_centres`; with a quantiser of their own a caller takes the probes from its
     coarse_index.search(...)[1]."""
+    if self.quantiser is not None:
+      if self._index.num_items != self.num_items:
+        raise ValueError('probes: the cells were built for %d items, the index holds %d' % (self.num_items, self._index.num_items))
+      return self.quantiser.probes(embds, weights, nprobe)
     if self.centres is None:
       raise ValueError('probes: these cells were not made from centres; take the probes from a coarse index of your own')
     if isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 1 <= nprobe <= MAX_PROBES:
@@ -2600,6 +2726,144 @@ class VideoIndex(_Index):
     return outs
 
   @staticmethod
+  def _not_trained(who, unsupported):
+    for name in unsupported:
+      if name not in _NOT_TRAINED:
+        raise TypeError('%s() got an unexpected keyword argument %r' % (who, name))
+      raise ValueError('%s: %s= is out of scope: the cells hold stored items and their plain sim assigns them' % (who, name))
+
+  def cell_sums(self, cells, **unsupported):
+    """cells from this index's `cells` (or a quantiser's `assign`) -> (sums [C, M * d] float32, wsums [C, M] float32,
+    counts [C] int64) on the device: per cell the sum of its members' stored rows -- dequantised exactly: float32 as it
+    is, bfloat16 widened, float8_e4m3fn code x the item's scale -- and of their weights, and the number of members; zero
+    for an empty cell.  The update step of a k-means without an fp32 copy of the gallery and without atomics: a cell's
+    list is cut into pieces of SUM_PIECE positions, a piece's rows are added in ascending position and the pieces in
+    ascending order (`cell_sums_ref` restates it), so the sums of a cell depend on its member list alone -- not on the
+    other cells, num_cells, num_items or the launch -- and two calls are bit-identical.  Every labelled row is read once
+    (mmt_search_cell_sums, mmt_search_cell_centroids); nothing here waits for the device.  Not on a ShardedVideoIndex."""
+    self._not_trained('cell_sums', unsupported)
+    self._cells(cells, 'cell_sums')
+    sums, wsums = self._cell_update(cells, None, None)
+    return sums, wsums, cells.sizes.clone()
+
+  def cell_centroids(self, cells, out=None, **unsupported):
+    """cells as for `cell_sums` -> (embds [C, M, d], weights [C, M]) float32 on the device: the centroid of every cell as
+    an item, G_c[m] = S[m] / |S[m]|_2 (a zero S[m] gives a zero row) and gw_c[m] = w[m] / n from the cell's `cell_sums`;
+    the centroid of a one-item cell is the item.  out: a pair of contiguous float32 tensors of those shapes on the index
+    device, written in place and returned; the rows of an EMPTY cell are left as they are (None: zeros).  Not on a
+    ShardedVideoIndex."""
+    self._not_trained('cell_centroids', unsupported)
+    self._cells(cells, 'cell_centroids')
+    c, m, d = cells.num_cells, self.num_experts, self.dim
+    if out is None:
+      out = (torch.zeros(c, m, d, device=self.device), torch.zeros(c, m, device=self.device))
+    else:
+      if not isinstance(out, (tuple, list)) or len(out) != 2 or not all(torch.is_tensor(t) for t in out):
+        raise ValueError('cell_centroids: out must be a pair of tensors (embds, weights)')
+      for t, shape in zip(out, ((c, m, d), (c, m))):
+        if t.dtype != torch.float32 or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous():
+          raise ValueError('cell_centroids: out must hold contiguous float32 tensors %s and %s on the index device %s' % (
+              (c, m, d), (c, m), self.device))
+    self._cell_update(cells, out[0], out[1])
+    return out[0], out[1]
+
+  def _cell_update(self, cells, embds, weights):
+    """`cell_sums` and `cell_centroids` behind their checks -> (sums, wsums); embds / weights: the in/out centroid buffers
+    or None.  The piece tables (torch, on the device) for a bound the host knows, one workspace of a partial row per
+    piece and two calls.  Nothing here waits for the device."""
+    c, m, d, L = cells.num_cells, self.num_experts, self.dim, _lib.lib()
+    labelled = cells.items.shape[0]
+    if labelled == 0:
+      return torch.zeros(c, m * d, device=self.device), torch.zeros(c, m, device=self.device)
+    sums, wsums = torch.empty(c, m * d, device=self.device), torch.empty(c, m, device=self.device)
+    n_work = -(-labelled // SUM_PIECE) + c
+    with torch.cuda.device(self.device):
+      work, piece_start = _sum_plan(cells.offsets, n_work)
+      ws = torch.empty(L.mmt_cell_sums_workspace_floats(n_work, m, d), device=self.device, dtype=torch.float32)
+      check(L.mmt_search_cell_sums(ops._p(self.folded), ops._p(self.weights), ops._p(self.scales), _STORAGE[self.dtype],
+                                   self.num_items, m, d, ops._p(cells.items), labelled, ops._p(work), n_work, ops._p(ws),
+                                   ops._stream()), 'mmt_search_cell_sums')
+      check(L.mmt_search_cell_centroids(ops._p(ws), n_work, ops._p(piece_start), ops._p(cells.offsets), labelled, c, m, d,
+                                        ops._p(sums), ops._p(wsums), ops._p(embds), ops._p(weights), ops._stream()),
+            'mmt_search_cell_centroids')
+    return sums, wsums
+
+  def train_cells(self, num_cells, iters=10, init=None, seed=0, items=None, **unsupported):
+    """Spherical k-means over the stored items -> CellQuantiser with num_cells centroids.  num_cells an int in 1 .. the
+    number of training items; iters an int >= 1; items: int64 [T] on the index device, the training sample (repeats count
+    once; None = every stored item) -- the items outside it are labelled -1 during training; init: int64 [num_cells] of
+    distinct item numbers of the sample on the index device, checked as `cells_from_centres` checks its centres (None:
+    the first num_cells of a host permutation of the sample seeded with `seed`).  It starts from the cells {init[c]}.  An
+    iteration builds the VideoIndex of the centroids in this index's dtype, assigns every training item to its best
+    centroid -- centroids.neighbours(k=1, source=self, items=sample), ties to the lower cell -- re-seeds the cells left
+    empty with the sample's lowest-scoring items (`reseed_ref`), and takes the new centroids from `cell_centroids`; a cell
+    the re-seeding emptied keeps its previous centroid.  `objective[t]` is the mean score of that assignment, `moved[t]`
+    the labels it changed; it stops early after an assignment that moved none.  Deterministic: the same index, arguments
+    and seed give bit-identical centroids and labels.  Not on a ShardedVideoIndex; subset=, where=, norm=, pooling= and
+    item_pooling= raise ValueError naming the option."""
+    self._not_trained('train_cells', unsupported)
+    if isinstance(num_cells, bool) or not isinstance(num_cells, int) or not 1 <= num_cells < 2 ** 31:
+      raise ValueError('train_cells: num_cells must be an int in 1 .. 2^31 - 1, got %r' % (num_cells,))
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+      raise ValueError('train_cells: iters must be an int >= 1, got %r' % (iters,))
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+      raise ValueError('train_cells: seed must be an int in 0 .. 2^32 - 1, got %r' % (seed,))
+    for name, t, shape in (('items', items, '[T >= 1]'), ('init', init, '[num_cells]')):
+      if t is None:
+        continue
+      if not torch.is_tensor(t) or t.dtype != torch.int64:
+        raise ValueError('train_cells: %s must be an int64 tensor, got %s' % (
+            name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+      if t.device != self.device:
+        raise ValueError('train_cells: %s must be on the index device %s, got %s' % (name, self.device, t.device))
+      if t.dim() != 1 or t.shape[0] < 1 or (name == 'init' and t.shape[0] != num_cells):
+        raise ValueError('train_cells: %s %s expected, got %s' % (name, shape, tuple(t.shape)))
+    if self.num_items == 0:
+      raise ValueError('train_cells: the index holds no items')
+    n, dev = self.num_items, self.device
+    if items is None:
+      train = torch.arange(n, device=dev, dtype=torch.int64)
+    else:
+      lo, hi = (int(v) for v in torch.aminmax(items))
+      if lo < 0 or hi >= n:
+        raise ValueError('train_cells: items must lie in 0 .. %d, got %d .. %d' % (n - 1, lo, hi))
+      train = torch.unique(items)  # ascending
+    if num_cells > train.shape[0]:
+      raise ValueError('train_cells: %d cells but %d training items' % (num_cells, train.shape[0]))
+    if init is None:
+      init = train[torch.from_numpy(np.random.RandomState(seed).permutation(train.shape[0])[:num_cells]).to(dev)]
+    else:
+      lo, hi = (int(v) for v in torch.aminmax(init))
+      if lo < 0 or hi >= n:
+        raise ValueError('train_cells: init must lie in 0 .. %d, got %d .. %d' % (n - 1, lo, hi))
+    ids = torch.full((n,), -1, device=dev, dtype=torch.int64)
+    ids[init] = torch.arange(num_cells, device=dev, dtype=torch.int64)
+    in_sample = torch.zeros(n, device=dev, dtype=torch.bool)
+    in_sample[train] = True
+    distinct, sampled = (int(v) for v in torch.stack([(ids >= 0).sum(), in_sample[init].sum()]).tolist())
+    if distinct != num_cells:
+      raise ValueError('train_cells: the items of init must be distinct')
+    if sampled != num_cells:
+      raise ValueError('train_cells: the items of init must belong to the training items')
+    embds, weights = self.cell_centroids(self.cells(ids, num_cells))
+    objective, moved = [], []
+    for _ in range(iters):
+      centroids = VideoIndex(embds, weights, dtype=self.dtype)
+      s, best = centroids.neighbours(k=1, source=self, items=train)
+      new = torch.full_like(ids, -1)
+      new[train] = best[:, 0]
+      new = _reseed(new, s[:, 0], train, num_cells)
+      cells = self.cells(new, num_cells)
+      self.cell_centroids(cells, out=(embds, weights))
+      objective.append(s.mean())
+      moved.append((new != ids).sum())
+      ids = new
+      if int(moved[-1]) == 0:
+        break
+    return CellQuantiser(VideoIndex(embds, weights, dtype=self.dtype), embds, weights, torch.stack(objective),
+                         torch.stack(moved))
+
+  @staticmethod
   def _filter_args(scan, r0, r1, nq):
     """The two arguments the `_where` entries take behind the descriptor for query rows r0 .. r1 - 1 of nq: (the tags, the
     rows' masks), and what keeps them alive."""
@@ -3644,6 +3908,18 @@ class ShardedVideoIndex(_Index):
           part = IndexCells(sh.index, *self._cell_csr(local.to(sh.device), num_cells), sh.num_items)
       parts.append(part)
     return ShardedCells(self, *self._cell_csr(ids, num_cells), self.num_items, parts)
+
+  def _no_training(who):
+    def refuse(self, *args, **kwargs):
+      raise ValueError('%s: not available on a ShardedVideoIndex: sums across shards would need an order-independent '
+                       'accumulator to stay bit-identical; train on a sample held in one VideoIndex' % who)
+    refuse.__name__ = who
+    return refuse
+
+  train_cells = _no_training('train_cells')
+  cell_sums = _no_training('cell_sums')
+  cell_centroids = _no_training('cell_centroids')
+  del _no_training
 
   def _search_probed(self, q, qw, cells, probes, k):
     """`search_probed` behind its checks: q, qw and probes on the primary.  Every shard that holds items of a cell answers

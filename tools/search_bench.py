@@ -140,7 +140,18 @@ centres (cells_from_centres), at NQ = 1, 64 and 4 096 and nprobe = 1, 4, 16 and 
 on that union; --runs rounds on device events, every variant once per round, interleaved; median and spread.  Beside the
 times: the 64 x 128 tile K loops each route executes (the probed scan's from search.probe_plan), whose ratio is the derived
 expectation; the regrouping alone (the torch plan), timed on its own; recall@10 of `search_cells` against `search`, per
-nprobe -- a property of the quantiser, reported and never a test.  Default output profiles/search_cells_bench.json."""
+nprobe -- a property of the quantiser, reported and never a test.  Default output profiles/search_cells_bench.json.
+
+--kmeans times the k-means cells on the data of --cells (262 144 x 7 x 512 from 1 024 planted clusters, 1 024 cells) on a
+float32, a bf16 and an fp8 index: (a) the update step, cell_centroids (mmt_search_cell_sums + mmt_search_cell_centroids)
+over the cells of the sampled centres, in ms and as a fraction of the HBM peak from the bytes of the labelled rows, their
+weights and scales; (b) the same update from the public tensors -- the stored rows dequantised in chunks of 8 192 and
+summed with index_add_, whose atomics make two runs differ -- with the peak memory of both; (c) one Lloyd iteration split
+into its assignment (the centroid index and neighbours(k=1, source=index)) and its update (cells + cell_centroids);
+--runs rounds on device events, every variant once per round, interleaved; median and spread.  (d) train_cells(1 024,
+iters=10) once on a host clock, its objective and moved, and recall@10 of search_cells against search at nprobe 1, 4, 16
+and 64 with its cells beside the cells of the sampled centres on the same data and queries -- reported, never a test.
+Default output profiles/search_kmeans_bench.json."""
 import argparse
 import json
 import math
@@ -805,10 +816,10 @@ def where_mode(a, dev):
   return row
 
 
-def cells_mode(a, dev):
-  """search_probed against search and rescore on planted clusters (module docstring, --cells)."""
-  from mmt_amd import search
-  nv, chunk, ncells, nq_all = SHAPES['S3'][1], 8192, 1024, 4096
+def clustered_gallery(dev, nv, ncells, nq_all, chunk=8192):
+  """The data of --cells and --kmeans, from seed 0: nv items drawn from ncells planted clusters (a unit centre plus unit
+  noise per expert, renormalised; softmax weights) on a float32, a bf16 and an fp8 index, nq_all queries that are noisy
+  copies of stored items, and ncells randomly sampled centre items -> (indexes by dtype name, q, qw, centres)."""
   gen = torch.Generator(device=dev).manual_seed(0)
   nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
   noise = lambda n: torch.randn(n, M, D, device=dev, generator=gen) / math.sqrt(D)
@@ -827,6 +838,100 @@ def cells_mode(a, dev):
   q = nrm(q + noise(nq_all))
   qw = torch.softmax(torch.randn(nq_all, M, device=dev, generator=gen), -1)
   centres = torch.randperm(nv, device=dev, generator=gen)[:ncells]
+  return idx, q, qw, centres
+
+
+HBM_PEAK = 8.0e12  # bytes/s, HBM3E specification
+
+
+def kmeans_mode(a, dev):
+  """The k-means update, one Lloyd iteration and the recall of trained cells (module docstring, --kmeans)."""
+  import time
+  from mmt_amd import search
+  nv, ncells, nq_all, chunk = SHAPES['S3'][1], 1024, 4096, 8192
+  idx, q, qw, centres = clustered_gallery(dev, nv, ncells, nq_all)
+  row = {'NV': nv, 'num_cells': ncells, 'sum_piece': search.SUM_PIECE, 'sum_slab': search.SUM_SLAB,
+         'hbm_peak_bytes_per_second': HBM_PEAK, 'index_bytes': {n: idx[n].nbytes for n in idx},
+         'not_measured': ['kernel times from a profiler trace: the update is timed as one call on device events',
+                          'a training sample smaller than the gallery (items=)', 'num_cells other than 1 024']}
+
+  def recall(index, cells, exact):
+    out = {}
+    for p in (1, 4, 16, 64):
+      got = index.search_cells(q, qw, cells, nprobe=p, k=K)[1]
+      out['nprobe%d' % p] = float(((got.unsqueeze(2) == exact.unsqueeze(1)).any(2).float().sum(1) / K).mean())
+    return out
+
+  for n, index in idx.items():
+    sampled = index.cells_from_centres(centres)
+    ids = torch.empty(nv, device=dev, dtype=torch.int64)
+    ids[sampled.items] = torch.repeat_interleave(torch.arange(ncells, device=dev), sampled.sizes)
+    labelled = int(sampled.items.shape[0])
+    row_bytes = labelled * (M * D * index.folded.element_size() + M * 4 + (4 if index.scales is not None else 0))
+    out = (torch.zeros(ncells, M, D, device=dev), torch.zeros(ncells, M, device=dev))
+
+    def update_torch():
+      sums, wsums = torch.zeros(ncells, M * D, device=dev), torch.zeros(ncells, M, device=dev)
+      for at in range(0, nv, chunk):
+        rows = index.folded[at:at + chunk].to(torch.float32)
+        if index.scales is not None:
+          rows = rows * index.scales[at:at + chunk, None]
+        sums.index_add_(0, ids[at:at + chunk], rows)
+        wsums.index_add_(0, ids[at:at + chunk], index.weights[at:at + chunk])
+      counts = torch.bincount(ids, minlength=ncells).clamp(min=1)
+      return torch.nn.functional.normalize(sums.view(ncells, M, D), dim=-1), wsums / counts[:, None]
+
+    def assignment():
+      return VideoIndex(out[0], out[1], dtype=index.dtype).neighbours(k=1, source=index)
+
+    fns = {'update': lambda: index.cell_centroids(sampled, out=out), 'update_torch_index_add': update_torch,
+           'assignment': assignment, 'cells_build': lambda: index.cells(ids, ncells),
+           'cells_build_and_update': lambda: index.cell_centroids(index.cells(ids, ncells), out=out)}
+    ts, peaks, res = {v: [] for v in fns}, {v: 0 for v in fns}, {}
+    for _ in range(a.runs):            # interleaved: drift hits the variants alike
+      for v, fn in fns.items():
+        t, _, peak, res[v] = timed(fn, a.min_seconds)
+        ts[v].append(t)
+        peaks[v] = max(peaks[v], peak)
+    cell = {v: dict(seconds_median=float(np.median(ts[v])), seconds_spread=max(ts[v]) - min(ts[v]), seconds_runs=ts[v],
+                    peak_mem_growth_bytes=int(peaks[v])) for v in fns}
+    up, ref = cell['update'], cell['update_torch_index_add']
+    up.update(bytes_read=row_bytes, bytes_per_second=row_bytes / up['seconds_median'],
+              fraction_of_hbm_peak=row_bytes / up['seconds_median'] / HBM_PEAK)
+    again = index.cell_centroids(sampled)
+    diff = (res['update_torch_index_add'][0] - again[0]).abs().max()
+    cell['summary'] = dict(
+        torch_over_update_seconds=ref['seconds_median'] / up['seconds_median'],
+        torch_over_update_peak_bytes=ref['peak_mem_growth_bytes'] / max(1, up['peak_mem_growth_bytes']),
+        iteration_seconds=cell['assignment']['seconds_median'] + cell['cells_build_and_update']['seconds_median'],
+        update_share_of_iteration=cell['cells_build_and_update']['seconds_median'] /
+        (cell['assignment']['seconds_median'] + cell['cells_build_and_update']['seconds_median']),
+        update_is_bit_identical_across_calls=bool(torch.equal(again[0].view(torch.int32), res['update'][0].view(torch.int32))),
+        max_abs_difference_to_the_torch_route=float(diff))
+    row[n + '/times'] = cell
+    exact = index.search(q, qw, k=K)[1]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    quantiser = index.train_cells(ncells, iters=10)
+    trained = quantiser.assign(index)
+    torch.cuda.synchronize()
+    sizes = trained.sizes.cpu().numpy()
+    row[n + '/train_cells'] = dict(seconds_host_clock=time.perf_counter() - t0, iterations=quantiser.iterations,
+                                   objective=quantiser.objective.cpu().tolist(), moved=quantiser.moved.cpu().tolist(),
+                                   size_min=int(sizes.min()), size_median=float(np.median(sizes)), size_max=int(sizes.max()))
+    row[n + '/recall_at_10'] = {'trained': recall(index, trained, exact), 'sampled_centres': recall(index, sampled, exact)}
+    print('%s: update %.3f ms (%.0f%% of HBM peak), torch %.3f ms, assignment %.3f ms; recall trained %s sampled %s' % (
+        n, 1e3 * up['seconds_median'], 100 * up['fraction_of_hbm_peak'], 1e3 * ref['seconds_median'],
+        1e3 * cell['assignment']['seconds_median'], row[n + '/recall_at_10']['trained'],
+        row[n + '/recall_at_10']['sampled_centres']), file=sys.stderr)
+  return row
+
+
+def cells_mode(a, dev):
+  """search_probed against search and rescore on planted clusters (module docstring, --cells)."""
+  from mmt_amd import search
+  nv, ncells, nq_all = SHAPES['S3'][1], 1024, 4096
+  idx, q, qw, centres = clustered_gallery(dev, nv, ncells, nq_all)
   row = {'NV': nv, 'num_cells': ncells, 'cell_piece': search.CELL_PIECE, 'index_bytes': {n: idx[n].nbytes for n in idx}}
   same = lambda x, y: bool(torch.equal(x[1], y[1]) and torch.equal(x[0].view(torch.int32), y[0].view(torch.int32)))
   for n, index in idx.items():
@@ -1299,6 +1404,9 @@ def main():
   ap.add_argument('--cells', action='store_true', help='time search_probed at 1, 64 and 4 096 queries x 262 144 clustered items '
                   'in 1 024 cells, nprobe = 1, 4, 16, 64, k = 10, on a float32, a bf16 and an fp8 index, against search and '
                   'rescore; tile counts and recall@10 beside the times')
+  ap.add_argument('--kmeans', action='store_true', help='time the k-means update (cell_centroids) at 262 144 clustered items '
+                  'in 1 024 cells on a float32, a bf16 and an fp8 index against dequantise + index_add_, one Lloyd iteration '
+                  'split into assignment and update, and recall@10 of search_cells with train_cells(1 024, iters=10)')
   ap.add_argument('--shapes', default='S1,S2,S3')
   ap.add_argument('--out', default=None)
   ap.add_argument('--min-seconds', type=float, default=0.5)
@@ -1377,6 +1485,17 @@ def main():
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
+  if a.kmeans:
+    res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'kmeans', 'runs': a.runs,
+           'min_seconds': a.min_seconds}
+    res.update(kmeans_mode(a, dev))
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                'search_kmeans_bench.json')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+      json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return
   if a.cells:
     res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'cells', 'runs': a.runs,
            'min_seconds': a.min_seconds}
