@@ -1069,7 +1069,9 @@ int mmt_text_heads_fwd(const MmtTextHeads* h, const float* text, const float* te
                        const MmtTextHeadsOpts* opts, void* stream);
 /* gradients are WRITTEN through the g_* pointers; dtext [N, K] (nullable) receives the gradient for the text
  * tower; w1_all = the M fc.weight matrices contiguous as [M*d, K].  dtext_moe [N, K] (nullable): gradient wrt the MoE
- * branch's input (with the on-the-fly dropout: already masked, i.e. the gradient wrt text through that branch). */
+ * branch's input (with the on-the-fly dropout: already masked, i.e. the gradient wrt text through that branch); without
+ * it that gradient is added into dtext.  Every g_* pointer is nullable on its own, per expert and per parameter (a frozen
+ * parameter): a null one is skipped, on both kernel paths, and every other gradient is what it is with all of them set. */
 int mmt_text_heads_bwd(const MmtTextHeads* h, const float* text, const float* text_moe, const float* w1_all, int N,
                        int C, int M, int d, int K, int use_bn, int training, float* ws, const float* dtext_embds,
                        const float* text_weights, const float* dtext_weights, float* dtext, float* dtext_moe,

@@ -431,14 +431,19 @@ extern "C" int mmt_text_heads_bwd(const MmtTextHeads* h, const float* text, cons
   TRY(mmt_sgemm_batched(&g, stream));
   // g_w2[m] = dx1[m]^T . y[m]
   g.M = d; g.N = d; g.K = N; g.sai = 1; g.sak = (int64_t)M * d; g.sbj = 1; g.sbk = (int64_t)M * d; g.ldc = d; g.beta = 0.f;
-  bool any = false;
-  for (int m = 0; m < M; ++m) { g.A[m] = dz + (int64_t)m * d; g.B[m] = y + (int64_t)m * d; g.C[m] = h->g_w2[m]; any |= h->g_w2[m] != nullptr; }
-  if (any) TRY(mmt_sgemm_batched(&g, stream));
+  // every g_* pointer is nullable on its own: the batch holds the experts whose gradient is asked for, and only those
+  int nb = 0;
+  for (int m = 0; m < M; ++m)
+    if (h->g_w2[m]) { g.A[nb] = dz + (int64_t)m * d; g.B[nb] = y + (int64_t)m * d; g.C[nb] = h->g_w2[m]; ++nb; }
+  g.batch = nb;
+  if (nb) TRY(mmt_sgemm_batched(&g, stream));
   // g_w1[m] = dy[m]^T . text
   g.M = d; g.N = K; g.K = N; g.sai = 1; g.sak = (int64_t)M * d; g.sbj = 1; g.sbk = K; g.ldc = K;
-  any = false;
-  for (int m = 0; m < M; ++m) { g.A[m] = dyg + (int64_t)m * d; g.B[m] = text; g.C[m] = h->g_w1[m]; any |= h->g_w1[m] != nullptr; }
-  if (any) TRY(mmt_sgemm_batched(&g, stream));
+  nb = 0;
+  for (int m = 0; m < M; ++m)
+    if (h->g_w1[m]) { g.A[nb] = dyg + (int64_t)m * d; g.B[nb] = text; g.C[nb] = h->g_w1[m]; ++nb; }
+  g.batch = nb;
+  if (nb) TRY(mmt_sgemm_batched(&g, stream));
   hipLaunchKernelGGL(colsum_f32_kernel, dim3((M * d + 255) / 256), dim3(256), 0, s, dyg, N, M, d, *h);
   if (dtext) {  // dtext = dy_all [N, M*d] . W1_all [M*d, K]
     if (!w1_all) return MMT_ERR_ARG;
