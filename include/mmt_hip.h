@@ -913,6 +913,49 @@ int mmt_search_cell_sums(const void* g, const float* gw, const float* gscale, in
 int mmt_search_cell_centroids(const float* ws, int n_work, const int32_t* piece_start, const int64_t* offsets, int n_items,
                               int C, int M, int d, float* sums, float* wsums, float* embds, float* weights, void* stream);
 
+/* The exact k-means update (search_kmeans.hip), additive: four entries and a size function, nothing that exists changes,
+ * MmtSearchScan stays 21 fields / 128 bytes and mmt_abi_version() stays 6.  They serve search.py's `sum_scale`,
+ * `cell_sums_exact`, `cell_centroids(exact=True)` and `train_cells(exact=True)` on both index classes.
+ * THE DEFINITION.  f_g[k] is the dequantised stored value of item g, column k, as above; gw_g[m] its weights; the index
+ * holds num_items items.  bits B = 62 - ceil(log2(max(num_items, 2))) (the F of mmt_search_row_expsum).  exponent E = the
+ * least integer with max |f_g[k]| <= 2^E over the stored rows (0 when all are zero; a maximum of exactly 1.0 gives 0, the
+ * next float up 1); wexponent the same over |gw_g[m]|.  term(g, k) = rint(f_g[k] * 2^(B - E)), taken in fp64 where the
+ * scaling is exact, rounded to nearest, ties to even, converted to int64; |term| <= 2^B and a cell has at most num_items
+ * <= 2^(62 - B) members, so a sum stays within +-2^62; a value beyond 2^E (a stale or foreign scale) is clamped to +-2^B
+ * and never wraps.  sums[c][k] = sum over the cell's members of term(g, k) as int64, wsums likewise with wexponent:
+ * integer addition is associative, so they are functions of the cell's member SET -- not of the order of its list, the
+ * pieces, or how the items are spread over several indexes that share (B, E, wexponent), whose tensors simply add.
+ * Back to fp32: S = ldexp(float32(sum), E - B), float32(sum) being ONE int64 -> fp32 conversion, round to nearest even
+ * (never through fp64: that rounds twice).  |S - sum f| <= n_c 2^(E - B - 1) + ulp32(S) / 2 per column.  The centroid is
+ * mmt_search_cell_centroids' formula on these S and w, by the same device code: equal fp32 sums give equal centroid bits.
+ * mmt_search_absmax (fp32, bf16, fp8): one pass over the stored rows and the weights; out fp32 [2][n_blocks]: the maxima
+ *   of |f| and of |gw| of block b's grid-stride share at out[b] and out[n_blocks + b], every slot written, one writer per
+ *   slot.  The caller joins them with a maximum (order-independent) and derives E and wexponent.  1 <= n_blocks <= 65535.
+ * mmt_search_cell_sums_exact: the operands of mmt_search_cell_sums, the piece_start table of mmt_search_cell_centroids,
+ *   bits in 1 .. 61 and exponent / wexponent in -MMT_SEARCH_SUM_MAX_EXPONENT .. MMT_SEARCH_SUM_MAX_EXPONENT -> sums int64
+ *   [C][M d] and wsums int64 [C][M], always written, zero for a cell without pieces.  ws: int64
+ *   [mmt_cell_sums_exact_workspace_bytes(n_work, M, d) / 8], [n_work][M d] partial rows then [n_work][M] partial weights.
+ *   One block per (piece, column slab) with int64 accumulators in registers, then one block per cell joins its partial
+ *   rows.  The device-side range checks are those of mmt_search_cell_sums.
+ * mmt_search_cell_centroids_exact: sums int64 [C][M d] / wsums int64 [C][M] -- of one call, or the integer sum of several
+ *   indexes' -- offsets int64 [C + 1] (n = offsets[c + 1] - offsets[c]; outside 0 .. n_items: an empty cell) and the
+ *   scale -> fsums fp32 [C][M d], fwsums fp32 [C][M] (always written) and in/out embds / weights, both or neither, as
+ *   mmt_search_cell_centroids: the rows of an empty cell are left as they are.  One block per cell.
+ * MMT_ERR_ARG: what mmt_search_cell_sums / mmt_search_cell_centroids refuse, a null table or output, C < 1, bits or an
+ *   exponent out of range, n_blocks out of range; MMT_ERR_ALIGN: g or ws off a 16-byte boundary.  All refused on the host
+ *   before any launch.  No atomics, no scratch. */
+#define MMT_SEARCH_SUM_MAX_EXPONENT 160
+int mmt_search_absmax(const void* g, const float* gw, const float* gscale, int storage, int NV, int M, int d, float* out,
+                      int n_blocks, void* stream);
+int64_t mmt_cell_sums_exact_workspace_bytes(int n_work, int M, int d);
+int mmt_search_cell_sums_exact(const void* g, const float* gw, const float* gscale, int storage, int NV, int M, int d,
+                               const int64_t* items, int n_items, const int32_t* work, int n_work,
+                               const int32_t* piece_start, int C, int bits, int exponent, int wexponent, int64_t* ws,
+                               int64_t* sums, int64_t* wsums, void* stream);
+int mmt_search_cell_centroids_exact(const int64_t* sums, const int64_t* wsums, const int64_t* offsets, int n_items, int C,
+                                    int M, int d, int bits, int exponent, int wexponent, float* fsums, float* fwsums,
+                                    float* embds, float* weights, void* stream);
+
 /* Beside the scans.
  * mmt_search_subset_pack: mask [NV] bytes (nonzero = allowed) -> the subset words, padding included: one ballot per 64
  *   items, one writer per word.

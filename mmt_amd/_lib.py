@@ -300,6 +300,15 @@ SIGNATURES = {
     'mmt_search_cell_sums': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp]),
     'mmt_search_cell_centroids': (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
                                           c_vp]),
+    # the exact k-means update, additive: the stored operand, out, n_blocks, the stream; (n_work, M, d); the operands of
+    # mmt_search_cell_sums up to n_work, piece_start, C, bits, exponent, wexponent, the workspace, sums, wsums, the stream;
+    # sums, wsums, offsets, n_items, C, M, d, bits, exponent, wexponent, fsums, fwsums, embds, weights, the stream
+    'mmt_search_absmax': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp]),
+    'mmt_cell_sums_exact_workspace_bytes': (c_i64, [c_int, c_int, c_int]),
+    'mmt_search_cell_sums_exact': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp,
+                                           c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mmt_search_cell_centroids_exact': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                                c_vp, c_vp, c_vp, c_vp]),
     'mmt_ls_fold_bf16': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mmt_transpose_bf16': (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
     'mmt_ls_finish': (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

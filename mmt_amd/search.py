@@ -449,8 +449,37 @@ the assignment step is `centroids.neighbours(k=1, source=index)` against a Video
 dtype.  `train_cells(num_cells, iters)` is the Lloyd loop around them, deterministic, with empty cells re-seeded by the
 worst-served items (`reseed_ref`), and returns a `CellQuantiser`: `.assign(index)` gives that index's cells, whose
 `probes` and `search_cells` then work as on cells made from centres.  Timings and recall: DESIGN 9.25.  Out of scope:
-a ShardedVideoIndex (training on a sample held in one index is the usual practice), subset=, where=, norm=, pooling= and
-item_pooling=: ValueError naming the call or the option.
+these fp32 sums on a ShardedVideoIndex (they depend on the order of a cell's list; the exact sums below do not), subset=,
+where=, norm=, pooling= and item_pooling=: ValueError naming the call or the option.
+
+Exact cell sums (`sum_scale`, `cell_sums_exact`, `cell_centroids(exact=True)`, `train_cells(exact=True)`, `assign_cells`, on
+VideoIndex and ShardedVideoIndex): the update step with an accumulator whose result does not depend on the order of the
+additions, the idea of `query_lse`.  THE DEFINITION.  f_g[k] is the dequantised stored value of item g, column k, exactly
+as `cell_sums` forms it in fp32 (fp32 as stored, bf16 widened, fp8 code x the item's scale), gw_g[m] its weights, and the
+index holds num_items items.
+    bits B = lse_bits(num_items)
+    exponent E = the least integer with max |f_g[k]| <= 2^E over the stored rows (0 when all are zero; a maximum of
+                 exactly 1.0 gives 0, the next float up 1); wexponent the same over |gw_g[m]|
+    term(g, k) = (int64) rint(f_g[k] * 2^(B - E))     in fp64, where the scaling is exact; nearest, ties to even
+    sums[c][k] = sum_{g in cell c} term(g, k)         int64; wsums likewise with wexponent; counts as `cell_sums`
+    S = ldexp(float32(sum), E - B)                    float32(sum): ONE int64 -> fp32 conversion, nearest even
+|term| <= 2^B and a cell has at most num_items <= 2^(62 - B) members, so a sum stays within +-2^62; a value beyond 2^E (a
+stale or foreign scale) is clamped to +-2^B and never wraps.  Integer addition is associative, so the sums are functions
+of a cell's member SET: the same items inserted in another order, or spread over shards, give the same sums and the same
+centroids.  |S - sum f| <= n_c 2^(E - B - 1) + ulp32(S) / 2 per column.  The conversion back never goes through fp64, which
+would round twice (2^53 + 2^29 + 1).  The centroid is `cell_centroids`' formula on these S and w, by the same device code,
+so equal fp32 sums give equal centroid bits on both paths.  `sum_scale_ref`, `cell_sums_exact_ref` and `exact_sums_float`
+restate it in numpy.  `sum_scale()` -> SumScale(exponent, wexponent, bits, num_items): one pass over the stored rows
+(mmt_search_absmax) and the one host sync of the path, kept until the next `add`.  On a ShardedVideoIndex E and wexponent
+are the maxima over the shards and B comes from the global num_items; every shard sums its own part of the cells under
+those three numbers on its own device (mmt_search_cell_sums_exact), the int64 tensors are added on the primary, and the
+finish runs there (mmt_search_cell_centroids_exact).  Everything is opt-in by name: the fp32 accumulator stays the default
+on a VideoIndex, bit for bit, and plain `train_cells`, `cell_sums`, `cell_centroids` and `quantiser.assign` keep raising
+ValueError on a ShardedVideoIndex.  With exact=True its `train_cells` is the same Lloyd loop -- the assignment shard by
+shard against a copy of the centroids on the shard's device, labels and scores gathered on the primary -- and for any
+placement of the same items the sums, centroids, objective, moved, iterations and labels, and `assign_cells` and
+`search_cells` on the result, are bit-identical to one VideoIndex; checked, as everything in that class, with all shards
+on one device.  Timings: DESIGN 9.26.
 """
 import ctypes
 import functools
@@ -483,6 +512,8 @@ CELL_PIECE = 2048  # items of a cell one block of the probed scan walks (16 tile
 _NOT_PROBED = ('subset', 'exclude', 'after', 'where', 'norm', 'dynamic', 'pooling', 'item_pooling', 'grouping')  # refused by name
 SUM_PIECE = 256  # positions of a cell's list one block of `cell_sums` adds; a longer list is cut into pieces
 SUM_SLAB = 1024  # columns of the M * d one block of `cell_sums` takes
+MAX_SUM_EXPONENT = 160  # |exponent| of a SumScale: past every finite fp32 magnitude (MMT_SEARCH_SUM_MAX_EXPONENT)
+_ABSMAX_BLOCKS = 1024  # blocks of the `sum_scale` pass at most: 256 K threads grid-striding over the 16-byte groups
 _NOT_TRAINED = ('subset', 'where', 'norm', 'pooling', 'item_pooling')  # options the k-means calls refuse by name
 _GROUP_ROWS = 1 << 16  # rows per `neighbour_range` call of `duplicate_groups`: the CSR of a batch is dropped for its edges
 FP8 = torch.float8_e4m3fn
@@ -1029,6 +1060,118 @@ def cell_sums_ref(rows, weights, offsets, items, piece=SUM_PIECE):
   return sums, wsums, np.diff(off)
 
 
+def _exponent_of(largest):
+  """The least integer E with largest <= 2^E for a finite float largest >= 0; 0 for 0.  Exactly 1.0 gives 0, the next
+  float up 1."""
+  if not largest > 0:
+    return 0
+  mantissa, e = math.frexp(largest)   # largest = mantissa * 2^e, 0.5 <= mantissa < 1
+  return e - 1 if mantissa == 0.5 else e
+
+
+class SumScale:
+  """The fixed-point scale of the exact cell sums (module docstring; `sum_scale`): `exponent` E and `wexponent`, the least
+  integers with |stored value| <= 2^E and |weight| <= 2^wexponent over the index; `bits` B = lse_bits(num_items); and the
+  `num_items` it was made for.  A term is rint(value * 2^(B - E)) as int64.  Indexes whose sums are to be added share one
+  scale: a ShardedVideoIndex hands its own to every shard.  One made by hand (exponents at or above the index's own,
+  |exponent| <= MAX_SUM_EXPONENT) is accepted by the index whose num_items it names."""
+
+  def __init__(self, exponent, wexponent, bits, num_items):
+    for name, v in (('exponent', exponent), ('wexponent', wexponent)):
+      if isinstance(v, bool) or not isinstance(v, int) or abs(v) > MAX_SUM_EXPONENT:
+        raise ValueError('SumScale: %s must be an int in -%d .. %d, got %r' % (name, MAX_SUM_EXPONENT, MAX_SUM_EXPONENT, v))
+    if isinstance(bits, bool) or not isinstance(bits, int) or bits != lse_bits(num_items):
+      raise ValueError('SumScale: bits must be lse_bits(num_items) = %d, got %r' % (lse_bits(num_items), bits))
+    self.exponent, self.wexponent, self.bits, self.num_items = exponent, wexponent, bits, num_items
+    self._index = None   # the index whose `sum_scale` made it
+
+  def __eq__(self, other):
+    return isinstance(other, SumScale) and (self.exponent, self.wexponent, self.bits, self.num_items) == (
+        other.exponent, other.wexponent, other.bits, other.num_items)
+
+  __hash__ = None
+
+  def __repr__(self):
+    return 'SumScale(exponent=%d, wexponent=%d, bits=%d, num_items=%d)' % (
+        self.exponent, self.wexponent, self.bits, self.num_items)
+
+
+def _host(x):
+  return np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x)
+
+
+def sum_scale_ref(rows, weights):
+  """`sum_scale` restated in numpy: rows float32 [num_items, M * d], the stored rows dequantised; weights float32
+  [num_items, M] (numpy arrays or torch tensors, copied to the host) -> SumScale.  The exponents are those of the largest
+  magnitudes, and a maximum does not care how the rows are split: over the shards of a ShardedVideoIndex they are the
+  largest of the shards' exponents, and bits comes from the global num_items."""
+  rows, weights = _host(rows).astype(np.float32, copy=False), _host(weights).astype(np.float32, copy=False)
+  n = rows.shape[0]
+  return SumScale(_exponent_of(float(np.abs(rows).max(initial=0))), _exponent_of(float(np.abs(weights).max(initial=0))),
+                  lse_bits(n), n)
+
+
+def _exact_terms(values, exponent, bits):
+  """float32 values -> int64 rint(value * 2^(bits - exponent)): scaled in fp64 (exact), rounded to nearest even, clamped
+  to +-2^bits."""
+  scaled = np.ldexp(values.astype(np.float64), bits - exponent)
+  return np.clip(np.rint(scaled), -2.0 ** bits, 2.0 ** bits).astype(np.int64)
+
+
+def cell_sums_exact_ref(rows, weights, offsets, items, scale):
+  """The definition of `cell_sums_exact` (mmt_search_cell_sums_exact) restated in numpy: rows, weights, offsets and items
+  as `cell_sums_ref` takes them, scale a SumScale -> (sums int64 [C, M * d], wsums int64 [C, M], counts int64 [C]): per
+  cell the integer sum of its members' terms.  Integer addition is associative, so the order of a cell's list and any
+  split of the items into parts whose results are added give the same numbers."""
+  rows, weights = _host(rows).astype(np.float32, copy=False), _host(weights).astype(np.float32, copy=False)
+  off, items = _host(offsets).astype(np.int64), _host(items).astype(np.int64)
+  c = off.shape[0] - 1
+  sums, wsums = np.zeros((c, rows.shape[1]), np.int64), np.zeros((c, weights.shape[1]), np.int64)
+  for ci in range(c):
+    members = items[off[ci]:off[ci + 1]]
+    sums[ci] = _exact_terms(rows[members], scale.exponent, scale.bits).sum(0, dtype=np.int64)
+    wsums[ci] = _exact_terms(weights[members], scale.wexponent, scale.bits).sum(0, dtype=np.int64)
+  return sums, wsums, np.diff(off)
+
+
+def exact_sums_float(sums, exponent, bits):
+  """Exact sums back in fp32, restated in numpy: int64 sums (any shape) -> float32 ldexp(float32(sum), exponent - bits).
+  float32(sum) is the direct int64 -> fp32 conversion, rounded once to nearest even (__ll2float_rn on the device); a
+  detour through fp64 would round twice and give other bits (2^53 + 2^29 + 1)."""
+  return np.ldexp(_host(sums).astype(np.int64).astype(np.float32), np.int32(exponent - bits)).astype(np.float32)
+
+
+class ExactCellSums:
+  """What `cell_sums_exact` returns, on the index device (the primary of a sharded index): `sums` int64 [C, M * d] and
+  `wsums` int64 [C, M], the integer sums of the members' terms under `scale` (a SumScale); `counts` int64 [C].  `float()`
+  gives (sums, wsums, counts) with the sums in fp32, as `cell_sums` shapes them."""
+
+  def __init__(self, sums, wsums, counts, scale):
+    self.sums, self.wsums, self.counts, self.scale, self.device = sums, wsums, counts, scale, sums.device
+
+  def float(self):
+    """(sums float32 [C, M * d], wsums float32 [C, M], counts): ldexp(float32(sum), E - B) on the device, the conversion
+    rounded once (mmt_search_cell_centroids_exact without a centroid; `exact_sums_float` restates it)."""
+    offsets = torch.cat([self.counts.new_zeros(1), torch.cumsum(self.counts, 0)])
+    fsums, fwsums = _exact_finish(self.sums, self.wsums, offsets, self.scale, None, None)
+    return fsums, fwsums, self.counts.clone()
+
+
+def _exact_finish(sums, wsums, offsets, scale, embds, weights):
+  """int64 sums [C, M * d] / wsums [C, M] and the cells' offsets int64 [C + 1] on one device, a SumScale and the in/out
+  centroid buffers (embds [C, M, d], weights [C, M]) or None -> (sums, wsums) float32 there; the centroids of the cells
+  that have items are written (mmt_search_cell_centroids_exact).  Nothing here waits for the device."""
+  c, m = wsums.shape
+  d = sums.shape[1] // m
+  fsums, fwsums = torch.empty(c, m * d, device=sums.device), torch.empty(c, m, device=sums.device)
+  with torch.cuda.device(sums.device):
+    check(_lib.lib().mmt_search_cell_centroids_exact(
+        ops._p(sums), ops._p(wsums), ops._p(offsets), max(scale.num_items, 1), c, m, d, scale.bits, scale.exponent,
+        scale.wexponent, ops._p(fsums), ops._p(fwsums), ops._p(embds), ops._p(weights), ops._stream()),
+          'mmt_search_cell_centroids_exact')
+  return fsums, fwsums
+
+
 def reseed_ref(ids, scores, items, num_cells):
   """The re-seeding rule of `train_cells` restated in numpy: ids int64 [num_items], the labels after an assignment (-1 =
   not in the sample); items int64 [T] ascending, the training sample; scores float32 [T], the score of items[i] under its
@@ -1079,12 +1222,15 @@ class CellQuantiser:
   dtype, M and d -- item c is the centroid of cell c, folded and rounded by `add`; `embds` [num_cells, M, d] and `weights`
   [num_cells, M]: the unrounded fp32 values it was built from; `objective` and `moved`: device tensors [iterations], the
   mean score of a training item under its best centroid at each assignment and the labels that changed against the
-  iteration before; `iterations`: the iterations run (fewer than asked when an assignment moved nothing); `num_cells`."""
+  iteration before; `iterations`: the iterations run (fewer than asked when an assignment moved nothing); `num_cells`;
+  `exact`: whether the updates used the exact integer sums (train_cells(exact=True)), and then `scale`, their SumScale,
+  else None."""
 
-  def __init__(self, centroids, embds, weights, objective, moved):
+  def __init__(self, centroids, embds, weights, objective, moved, exact=False, scale=None):
     self.centroids, self.embds, self.weights = centroids, embds, weights
     self.objective, self.moved = objective, moved
     self.iterations, self.num_cells = objective.shape[0], centroids.num_items
+    self.exact, self.scale = exact, scale
 
   def assign(self, index, **unsupported):
     """index: a VideoIndex with the centroids' dtype, num_experts and dim on their device -> its IndexCells over ALL its
@@ -1095,7 +1241,7 @@ class CellQuantiser:
         raise TypeError('assign() got an unexpected keyword argument %r' % name)
       raise ValueError('assign: %s= is out of scope: every item joins the cell of its best centroid' % name)
     if hasattr(index, 'shards'):
-      raise ValueError('assign: not available on a ShardedVideoIndex; assign the items of one VideoIndex')
+      raise ValueError('assign: not available on a ShardedVideoIndex; call its assign_cells(quantiser)')
     _, best = self.centroids.neighbours(k=1, source=index)
     cells = index.cells(best[:, 0].contiguous(), self.num_cells)
     cells.quantiser = self
@@ -2068,6 +2214,165 @@ class _Index:
     if cells.num_items != self.num_items:
       raise ValueError('%s: the cells were built for %d items, the index holds %d' % (who, cells.num_items, self.num_items))
 
+  def sum_scale(self):
+    """The SumScale of the exact cell sums for the items held now: bits = lse_bits(num_items), exponent / wexponent from
+    the largest stored magnitude and the largest weight (mmt_search_absmax: one pass over the stored rows, per-block
+    maxima joined by torch.amax -- on a ShardedVideoIndex every shard's, joined on the primary: a maximum does not depend
+    on the order).  The one host sync of the exact path, taken once per index state: the result is kept until the next
+    `add`."""
+    if self.num_items == 0:
+      raise ValueError('sum_scale: the index holds no items')
+    cached = getattr(self, '_sum_scale', None)
+    if cached is None or cached.num_items != self.num_items:
+      largest, wlargest = self._absmax().tolist()
+      cached = SumScale(_exponent_of(largest), _exponent_of(wlargest), lse_bits(self.num_items), self.num_items)
+      cached._index = self
+      self._sum_scale = cached
+    return cached
+
+  def _scale(self, scale, who):
+    """scale=: None = this index's own `sum_scale`; else type, age and origin of the one given."""
+    if scale is None:
+      return self.sum_scale()
+    if not isinstance(scale, SumScale):
+      raise ValueError('%s: scale must be a SumScale (sum_scale() of this index), got %s' % (who, type(scale).__name__))
+    if scale.num_items != self.num_items:
+      raise ValueError('%s: the scale was built for %d items, the index holds %d' % (who, scale.num_items, self.num_items))
+    if scale._index is not None and scale._index is not self:
+      raise ValueError('%s: the scale belongs to another index' % who)
+    return scale
+
+  @staticmethod
+  def _exact_flag(who, exact, scale=None):
+    if not isinstance(exact, bool):
+      raise ValueError('%s: exact must be a bool, got %r' % (who, exact))
+    if scale is not None and not exact:
+      raise ValueError('%s: scale= goes with exact=True' % who)
+
+  def cell_sums_exact(self, cells, scale=None, **unsupported):
+    """cells as for `cell_sums` -> ExactCellSums: per cell the int64 sums of its members' terms rint(f * 2^(B - E)) (module
+    docstring, `cell_sums_exact_ref`) and of their weights' terms, and the counts.  scale: a SumScale, None = this index's
+    `sum_scale()`; one built for another num_items or by another index is refused.  Integer sums: a function of a cell's
+    member SET, so the same items inserted in another order, or spread over the shards of a ShardedVideoIndex in any way,
+    give the same numbers -- there every shard sums its own part under the global scale on its own device
+    (mmt_search_cell_sums_exact) and the int64 tensors are added on the primary.  `.float()` gives them in fp32."""
+    self._not_trained('cell_sums_exact', unsupported)
+    self._cells(cells, 'cell_sums_exact')
+    scale = self._scale(scale, 'cell_sums_exact')
+    sums, wsums = self._exact_sums(cells, scale)
+    return ExactCellSums(sums, wsums, cells.sizes.clone(), scale)
+
+  def _centroid_out(self, cells, out):
+    """out= of `cell_centroids`: None -> a pair of zeros; else the checks of the pair given."""
+    c, m, d = cells.num_cells, self.num_experts, self.dim
+    if out is None:
+      return torch.zeros(c, m, d, device=self.device), torch.zeros(c, m, device=self.device)
+    if not isinstance(out, (tuple, list)) or len(out) != 2 or not all(torch.is_tensor(t) for t in out):
+      raise ValueError('cell_centroids: out must be a pair of tensors (embds, weights)')
+    for t, shape in zip(out, ((c, m, d), (c, m))):
+      if t.dtype != torch.float32 or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError('cell_centroids: out must hold contiguous float32 tensors %s and %s on the index device %s' % (
+            (c, m, d), (c, m), self.device))
+    return out[0], out[1]
+
+  def _exact_centroids(self, cells, out, scale):
+    """`cell_centroids(exact=True)` behind its checks: the exact sums, then the finish on the index device (the primary)."""
+    sums, wsums = self._exact_sums(cells, scale)
+    _exact_finish(sums, wsums, cells.offsets, scale, out[0], out[1])
+    return out
+
+  @staticmethod
+  def _not_trained(who, unsupported):
+    for name in unsupported:
+      if name not in _NOT_TRAINED:
+        raise TypeError('%s() got an unexpected keyword argument %r' % (who, name))
+      raise ValueError('%s: %s= is out of scope: the cells hold stored items and their plain sim assigns them' % (who, name))
+
+  def assign_cells(self, quantiser):
+    """quantiser: a CellQuantiser trained either way, with this index's dtype, num_experts and dim -> this index's cells
+    over ALL its items, item g in the cell of its best centroid, ties to the lower cell, carrying `.quantiser`: on a
+    VideoIndex quantiser.assign(self); on a ShardedVideoIndex every shard's items are assigned on the shard's device
+    against a copy of the centroids there, and the labels are gathered into global order on the primary -- the same
+    cells, bit for bit, since a score does not depend on where the item is stored."""
+    if not isinstance(quantiser, CellQuantiser):
+      raise ValueError('assign_cells: quantiser must be a CellQuantiser, got %s' % type(quantiser).__name__)
+    if self.num_items == 0:
+      raise ValueError('assign_cells: the index holds no items')
+    held = quantiser.centroids
+    if (held.dtype, held.num_experts, held.dim) != (self.dtype, self.num_experts, self.dim):
+      raise ValueError('assign_cells: the quantiser holds (dtype, num_experts, dim) = (%s, %d, %d), this index (%s, %d, %d)'
+                       % (held.dtype, held.num_experts, held.dim, self.dtype, self.num_experts, self.dim))
+    _, best = self._assign(quantiser.embds, quantiser.weights, None)
+    cells = self.cells(best[:, 0].contiguous(), quantiser.num_cells)
+    cells.quantiser = quantiser
+    return cells
+
+  def _train_cells(self, num_cells, iters, init, seed, items, exact):
+    """`train_cells` behind the options refused by name: the argument checks and the Lloyd loop, on the index device (the
+    primary).  The class supplies the assignment (`_assign`) and the update (`cell_centroids`)."""
+    if isinstance(num_cells, bool) or not isinstance(num_cells, int) or not 1 <= num_cells < 2 ** 31:
+      raise ValueError('train_cells: num_cells must be an int in 1 .. 2^31 - 1, got %r' % (num_cells,))
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+      raise ValueError('train_cells: iters must be an int >= 1, got %r' % (iters,))
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+      raise ValueError('train_cells: seed must be an int in 0 .. 2^32 - 1, got %r' % (seed,))
+    for name, t, shape in (('items', items, '[T >= 1]'), ('init', init, '[num_cells]')):
+      if t is None:
+        continue
+      if not torch.is_tensor(t) or t.dtype != torch.int64:
+        raise ValueError('train_cells: %s must be an int64 tensor, got %s' % (
+            name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+      if t.device != self.device:
+        raise ValueError('train_cells: %s must be on the index device %s, got %s' % (name, self.device, t.device))
+      if t.dim() != 1 or t.shape[0] < 1 or (name == 'init' and t.shape[0] != num_cells):
+        raise ValueError('train_cells: %s %s expected, got %s' % (name, shape, tuple(t.shape)))
+    if self.num_items == 0:
+      raise ValueError('train_cells: the index holds no items')
+    n, dev = self.num_items, self.device
+    if items is None:
+      train = torch.arange(n, device=dev, dtype=torch.int64)
+    else:
+      lo, hi = (int(v) for v in torch.aminmax(items))
+      if lo < 0 or hi >= n:
+        raise ValueError('train_cells: items must lie in 0 .. %d, got %d .. %d' % (n - 1, lo, hi))
+      train = torch.unique(items)  # ascending
+    if num_cells > train.shape[0]:
+      raise ValueError('train_cells: %d cells but %d training items' % (num_cells, train.shape[0]))
+    if init is None:
+      init = train[torch.from_numpy(np.random.RandomState(seed).permutation(train.shape[0])[:num_cells]).to(dev)]
+    else:
+      lo, hi = (int(v) for v in torch.aminmax(init))
+      if lo < 0 or hi >= n:
+        raise ValueError('train_cells: init must lie in 0 .. %d, got %d .. %d' % (n - 1, lo, hi))
+    ids = torch.full((n,), -1, device=dev, dtype=torch.int64)
+    ids[init] = torch.arange(num_cells, device=dev, dtype=torch.int64)
+    in_sample = torch.zeros(n, device=dev, dtype=torch.bool)
+    in_sample[train] = True
+    distinct, sampled = (int(v) for v in torch.stack([(ids >= 0).sum(), in_sample[init].sum()]).tolist())
+    if distinct != num_cells:
+      raise ValueError('train_cells: the items of init must be distinct')
+    if sampled != num_cells:
+      raise ValueError('train_cells: the items of init must belong to the training items')
+    how = {'exact': True} if exact else {}
+    embds, weights = self.cell_centroids(self.cells(ids, num_cells), **how)
+    objective, moved = [], []
+    for _ in range(iters):
+      s, best = self._assign(embds, weights, train)
+      new = torch.full_like(ids, -1)
+      new[train] = best[:, 0]
+      new = _reseed(new, s[:, 0], train, num_cells)
+      cells = self.cells(new, num_cells)
+      self.cell_centroids(cells, out=(embds, weights), **how)
+      objective.append(s.mean())
+      moved.append((new != ids).sum())
+      ids = new
+      if int(moved[-1]) == 0:
+        break
+    with torch.cuda.device(dev):
+      centroids = VideoIndex(embds, weights, dtype=self.dtype)
+    return CellQuantiser(centroids, embds, weights, torch.stack(objective), torch.stack(moved), exact,
+                         self.sum_scale() if exact else None)
+
   def cells_from_centres(self, centres):
     """centres: int64 [C] of distinct item numbers on the index device -> the cells of the coarse quantiser that needs no
     second index and no trainer: cell c is the cell of item centres[c], and item g joins the cell of the centre that is
@@ -2725,13 +3030,6 @@ class VideoIndex(_Index):
               'mmt_search_topk_cells')
     return outs
 
-  @staticmethod
-  def _not_trained(who, unsupported):
-    for name in unsupported:
-      if name not in _NOT_TRAINED:
-        raise TypeError('%s() got an unexpected keyword argument %r' % (who, name))
-      raise ValueError('%s: %s= is out of scope: the cells hold stored items and their plain sim assigns them' % (who, name))
-
   def cell_sums(self, cells, **unsupported):
     """cells from this index's `cells` (or a quantiser's `assign`) -> (sums [C, M * d] float32, wsums [C, M] float32,
     counts [C] int64) on the device: per cell the sum of its members' stored rows -- dequantised exactly: float32 as it
@@ -2740,32 +3038,36 @@ class VideoIndex(_Index):
     list is cut into pieces of SUM_PIECE positions, a piece's rows are added in ascending position and the pieces in
     ascending order (`cell_sums_ref` restates it), so the sums of a cell depend on its member list alone -- not on the
     other cells, num_cells, num_items or the launch -- and two calls are bit-identical.  Every labelled row is read once
-    (mmt_search_cell_sums, mmt_search_cell_centroids); nothing here waits for the device.  Not on a ShardedVideoIndex."""
+    (mmt_search_cell_sums, mmt_search_cell_centroids); nothing here waits for the device.  Not on a ShardedVideoIndex:
+    `cell_sums_exact` is."""
     self._not_trained('cell_sums', unsupported)
     self._cells(cells, 'cell_sums')
     sums, wsums = self._cell_update(cells, None, None)
     return sums, wsums, cells.sizes.clone()
 
-  def cell_centroids(self, cells, out=None, **unsupported):
+  def cell_centroids(self, cells, out=None, exact=False, scale=None, **unsupported):
     """cells as for `cell_sums` -> (embds [C, M, d], weights [C, M]) float32 on the device: the centroid of every cell as
     an item, G_c[m] = S[m] / |S[m]|_2 (a zero S[m] gives a zero row) and gw_c[m] = w[m] / n from the cell's `cell_sums`;
     the centroid of a one-item cell is the item.  out: a pair of contiguous float32 tensors of those shapes on the index
-    device, written in place and returned; the rows of an EMPTY cell are left as they are (None: zeros).  Not on a
-    ShardedVideoIndex."""
+    device, written in place and returned; the rows of an EMPTY cell are left as they are (None: zeros).  exact=True
+    takes S and w from `cell_sums_exact(cells, scale).float()` instead -- the same formula by the same device code, on
+    sums that depend on a cell's member set alone; the default is untouched by it, bit for bit.  On a ShardedVideoIndex
+    only exact=True."""
     self._not_trained('cell_centroids', unsupported)
+    self._exact_flag('cell_centroids', exact, scale)
     self._cells(cells, 'cell_centroids')
-    c, m, d = cells.num_cells, self.num_experts, self.dim
-    if out is None:
-      out = (torch.zeros(c, m, d, device=self.device), torch.zeros(c, m, device=self.device))
-    else:
-      if not isinstance(out, (tuple, list)) or len(out) != 2 or not all(torch.is_tensor(t) for t in out):
-        raise ValueError('cell_centroids: out must be a pair of tensors (embds, weights)')
-      for t, shape in zip(out, ((c, m, d), (c, m))):
-        if t.dtype != torch.float32 or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous():
-          raise ValueError('cell_centroids: out must hold contiguous float32 tensors %s and %s on the index device %s' % (
-              (c, m, d), (c, m), self.device))
+    if exact:
+      scale = self._scale(scale, 'cell_centroids')
+      return self._exact_centroids(cells, self._centroid_out(cells, out), scale)
+    out = self._centroid_out(cells, out)
     self._cell_update(cells, out[0], out[1])
-    return out[0], out[1]
+    return out
+
+  def _sum_tables(self, cells):
+    """The piece tables of a sum over `cells` (torch, on the device) for a bound the host knows -> (n_work, work,
+    piece_start)."""
+    n_work = -(-cells.items.shape[0] // SUM_PIECE) + cells.num_cells
+    return (n_work,) + _sum_plan(cells.offsets, n_work)
 
   def _cell_update(self, cells, embds, weights):
     """`cell_sums` and `cell_centroids` behind their checks -> (sums, wsums); embds / weights: the in/out centroid buffers
@@ -2776,9 +3078,8 @@ class VideoIndex(_Index):
     if labelled == 0:
       return torch.zeros(c, m * d, device=self.device), torch.zeros(c, m, device=self.device)
     sums, wsums = torch.empty(c, m * d, device=self.device), torch.empty(c, m, device=self.device)
-    n_work = -(-labelled // SUM_PIECE) + c
     with torch.cuda.device(self.device):
-      work, piece_start = _sum_plan(cells.offsets, n_work)
+      n_work, work, piece_start = self._sum_tables(cells)
       ws = torch.empty(L.mmt_cell_sums_workspace_floats(n_work, m, d), device=self.device, dtype=torch.float32)
       check(L.mmt_search_cell_sums(ops._p(self.folded), ops._p(self.weights), ops._p(self.scales), _STORAGE[self.dtype],
                                    self.num_items, m, d, ops._p(cells.items), labelled, ops._p(work), n_work, ops._p(ws),
@@ -2788,7 +3089,45 @@ class VideoIndex(_Index):
             'mmt_search_cell_centroids')
     return sums, wsums
 
-  def train_cells(self, num_cells, iters=10, init=None, seed=0, items=None, **unsupported):
+  def _exact_sums(self, cells, scale):
+    """`cell_sums_exact` behind its checks -> (sums int64 [C, M * d], wsums int64 [C, M]) on the device; cells this
+    index's own, scale any SumScale (a shard is handed the global one).  The piece tables of `_cell_update`, one int64
+    workspace of a partial row per piece and one call.  Nothing here waits for the device."""
+    c, m, d, L = cells.num_cells, self.num_experts, self.dim, _lib.lib()
+    labelled = cells.items.shape[0]
+    if labelled == 0:
+      return (torch.zeros(c, m * d, device=self.device, dtype=torch.int64),
+              torch.zeros(c, m, device=self.device, dtype=torch.int64))
+    sums = torch.empty(c, m * d, device=self.device, dtype=torch.int64)
+    wsums = torch.empty(c, m, device=self.device, dtype=torch.int64)
+    with torch.cuda.device(self.device):
+      n_work, work, piece_start = self._sum_tables(cells)
+      ws = torch.empty(L.mmt_cell_sums_exact_workspace_bytes(n_work, m, d) // 8, device=self.device, dtype=torch.int64)
+      check(L.mmt_search_cell_sums_exact(ops._p(self.folded), ops._p(self.weights), ops._p(self.scales),
+                                         _STORAGE[self.dtype], self.num_items, m, d, ops._p(cells.items), labelled,
+                                         ops._p(work), n_work, ops._p(piece_start), c, scale.bits, scale.exponent,
+                                         scale.wexponent, ops._p(ws), ops._p(sums), ops._p(wsums), ops._stream()),
+            'mmt_search_cell_sums_exact')
+    return sums, wsums
+
+  def _absmax(self):
+    """float32 [2] on the device: the largest |stored value|, dequantised, and the largest |weight| of the items held
+    (mmt_search_absmax and a torch.amax over its per-block maxima).  Nothing here waits for the device."""
+    n, m, d = self.num_items, self.num_experts, self.dim
+    blocks = max(1, min(_ABSMAX_BLOCKS, -(-(n * m * d // _DTYPES[self.dtype]) // 256)))
+    with torch.cuda.device(self.device):
+      out = torch.empty(2, blocks, device=self.device, dtype=torch.float32)
+      check(_lib.lib().mmt_search_absmax(ops._p(self.folded), ops._p(self.weights), ops._p(self.scales),
+                                         _STORAGE[self.dtype], n, m, d, ops._p(out), blocks, ops._stream()),
+            'mmt_search_absmax')
+      return out.amax(1)
+
+  def _assign(self, embds, weights, train):
+    """The assignment step: centroids (embds [C, M, d], weights [C, M] fp32 on the device) and the training items (int64
+    ascending, None = every stored item) -> (scores [T, 1], cells [T, 1]) of each item's best centroid."""
+    return VideoIndex(embds, weights, dtype=self.dtype).neighbours(k=1, source=self, items=train)
+
+  def train_cells(self, num_cells, iters=10, init=None, seed=0, items=None, exact=False, **unsupported):
     """Spherical k-means over the stored items -> CellQuantiser with num_cells centroids.  num_cells an int in 1 .. the
     number of training items; iters an int >= 1; items: int64 [T] on the index device, the training sample (repeats count
     once; None = every stored item) -- the items outside it are labelled -1 during training; init: int64 [num_cells] of
@@ -2799,69 +3138,13 @@ class VideoIndex(_Index):
     empty with the sample's lowest-scoring items (`reseed_ref`), and takes the new centroids from `cell_centroids`; a cell
     the re-seeding emptied keeps its previous centroid.  `objective[t]` is the mean score of that assignment, `moved[t]`
     the labels it changed; it stops early after an assignment that moved none.  Deterministic: the same index, arguments
-    and seed give bit-identical centroids and labels.  Not on a ShardedVideoIndex; subset=, where=, norm=, pooling= and
-    item_pooling= raise ValueError naming the option."""
+    and seed give bit-identical centroids and labels.  exact=True takes every update from `cell_centroids(exact=True)`:
+    the result then depends on the items as a set per cell, not on their order in the index, and
+    ShardedVideoIndex.train_cells(exact=True) is bit-identical to it.  subset=, where=, norm=, pooling= and item_pooling=
+    raise ValueError naming the option."""
     self._not_trained('train_cells', unsupported)
-    if isinstance(num_cells, bool) or not isinstance(num_cells, int) or not 1 <= num_cells < 2 ** 31:
-      raise ValueError('train_cells: num_cells must be an int in 1 .. 2^31 - 1, got %r' % (num_cells,))
-    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
-      raise ValueError('train_cells: iters must be an int >= 1, got %r' % (iters,))
-    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
-      raise ValueError('train_cells: seed must be an int in 0 .. 2^32 - 1, got %r' % (seed,))
-    for name, t, shape in (('items', items, '[T >= 1]'), ('init', init, '[num_cells]')):
-      if t is None:
-        continue
-      if not torch.is_tensor(t) or t.dtype != torch.int64:
-        raise ValueError('train_cells: %s must be an int64 tensor, got %s' % (
-            name, t.dtype if torch.is_tensor(t) else type(t).__name__))
-      if t.device != self.device:
-        raise ValueError('train_cells: %s must be on the index device %s, got %s' % (name, self.device, t.device))
-      if t.dim() != 1 or t.shape[0] < 1 or (name == 'init' and t.shape[0] != num_cells):
-        raise ValueError('train_cells: %s %s expected, got %s' % (name, shape, tuple(t.shape)))
-    if self.num_items == 0:
-      raise ValueError('train_cells: the index holds no items')
-    n, dev = self.num_items, self.device
-    if items is None:
-      train = torch.arange(n, device=dev, dtype=torch.int64)
-    else:
-      lo, hi = (int(v) for v in torch.aminmax(items))
-      if lo < 0 or hi >= n:
-        raise ValueError('train_cells: items must lie in 0 .. %d, got %d .. %d' % (n - 1, lo, hi))
-      train = torch.unique(items)  # ascending
-    if num_cells > train.shape[0]:
-      raise ValueError('train_cells: %d cells but %d training items' % (num_cells, train.shape[0]))
-    if init is None:
-      init = train[torch.from_numpy(np.random.RandomState(seed).permutation(train.shape[0])[:num_cells]).to(dev)]
-    else:
-      lo, hi = (int(v) for v in torch.aminmax(init))
-      if lo < 0 or hi >= n:
-        raise ValueError('train_cells: init must lie in 0 .. %d, got %d .. %d' % (n - 1, lo, hi))
-    ids = torch.full((n,), -1, device=dev, dtype=torch.int64)
-    ids[init] = torch.arange(num_cells, device=dev, dtype=torch.int64)
-    in_sample = torch.zeros(n, device=dev, dtype=torch.bool)
-    in_sample[train] = True
-    distinct, sampled = (int(v) for v in torch.stack([(ids >= 0).sum(), in_sample[init].sum()]).tolist())
-    if distinct != num_cells:
-      raise ValueError('train_cells: the items of init must be distinct')
-    if sampled != num_cells:
-      raise ValueError('train_cells: the items of init must belong to the training items')
-    embds, weights = self.cell_centroids(self.cells(ids, num_cells))
-    objective, moved = [], []
-    for _ in range(iters):
-      centroids = VideoIndex(embds, weights, dtype=self.dtype)
-      s, best = centroids.neighbours(k=1, source=self, items=train)
-      new = torch.full_like(ids, -1)
-      new[train] = best[:, 0]
-      new = _reseed(new, s[:, 0], train, num_cells)
-      cells = self.cells(new, num_cells)
-      self.cell_centroids(cells, out=(embds, weights))
-      objective.append(s.mean())
-      moved.append((new != ids).sum())
-      ids = new
-      if int(moved[-1]) == 0:
-        break
-    return CellQuantiser(VideoIndex(embds, weights, dtype=self.dtype), embds, weights, torch.stack(objective),
-                         torch.stack(moved))
+    self._exact_flag('train_cells', exact)
+    return self._train_cells(num_cells, iters, init, seed, items, exact)
 
   @staticmethod
   def _filter_args(scan, r0, r1, nq):
@@ -3909,17 +4192,90 @@ class ShardedVideoIndex(_Index):
       parts.append(part)
     return ShardedCells(self, *self._cell_csr(ids, num_cells), self.num_items, parts)
 
-  def _no_training(who):
-    def refuse(self, *args, **kwargs):
-      raise ValueError('%s: not available on a ShardedVideoIndex: sums across shards would need an order-independent '
-                       'accumulator to stay bit-identical; train on a sample held in one VideoIndex' % who)
-    refuse.__name__ = who
-    return refuse
+  @staticmethod
+  def _float_sums_refused(who, instead):
+    """The fp32 sums depend on the order of a cell's list, which no placement of the items over shards preserves: only
+    the exact integer sums can be bit-identical to one VideoIndex, so here they have to be asked for by name."""
+    raise ValueError('%s: not available on a ShardedVideoIndex with the fp32 accumulator, whose sums depend on the order '
+                     'of the additions; %s' % (who, instead))
 
-  train_cells = _no_training('train_cells')
-  cell_sums = _no_training('cell_sums')
-  cell_centroids = _no_training('cell_centroids')
-  del _no_training
+  def cell_sums(self, *args, **kwargs):
+    """Refused: the fp32 sums are not order-independent.  `cell_sums_exact` is the sharded form."""
+    self._float_sums_refused('cell_sums', 'call cell_sums_exact(cells), whose integer sums add across shards')
+
+  def cell_centroids(self, cells=None, out=None, exact=False, scale=None, **unsupported):
+    """VideoIndex.cell_centroids(cells, out, exact=True, scale) on cells of this index, out on the primary -> bit-identical
+    to one VideoIndex over the same items, however they are placed: `cell_sums_exact`, then the finish on the primary
+    (mmt_search_cell_centroids_exact).  Without exact=True it raises ValueError."""
+    self._not_trained('cell_centroids', unsupported)
+    self._exact_flag('cell_centroids', exact, scale)
+    if not exact:
+      self._float_sums_refused('cell_centroids', 'pass exact=True for the integer sums, which add across shards')
+    self._cells(cells, 'cell_centroids')
+    scale = self._scale(scale, 'cell_centroids')
+    return self._exact_centroids(cells, self._centroid_out(cells, out), scale)
+
+  def train_cells(self, num_cells=None, iters=10, init=None, seed=0, items=None, exact=False, **unsupported):
+    """VideoIndex.train_cells(..., exact=True) over the shards -> a CellQuantiser on the primary, bit-identical to one
+    VideoIndex over the same items in every part: centroids, objective, moved, iterations.  init and items are global item
+    numbers on the primary.  The assignment runs shard by shard against a copy of the centroids on the shard's device
+    (`assign_cells` describes it), the update is `cell_centroids(exact=True)`.  Without exact=True it raises ValueError."""
+    self._not_trained('train_cells', unsupported)
+    self._exact_flag('train_cells', exact)
+    if not exact:
+      self._float_sums_refused('train_cells', 'pass exact=True for the integer sums, which add across shards')
+    return self._train_cells(num_cells, iters, init, seed, items, True)
+
+  def _absmax(self):
+    """The largest magnitudes over the shards, float32 [2] on the primary: a maximum of maxima."""
+    parts = [sh.index._absmax().to(self.device) for _, sh in self._live()]
+    with torch.cuda.device(self.device):
+      return torch.stack(parts).amax(0)
+
+  def _exact_sums(self, cells, scale):
+    """`cell_sums_exact` behind its checks: every shard that holds labelled items sums its part of the cells under the
+    GLOBAL scale on its own device; the int64 results are copied to the primary and added there -- integers, so neither
+    the placement nor the order of the shards matters."""
+    c, m, d = cells.num_cells, self.num_experts, self.dim
+    with torch.cuda.device(self.device):
+      sums = torch.zeros(c, m * d, device=self.device, dtype=torch.int64)
+      wsums = torch.zeros(c, m, device=self.device, dtype=torch.int64)
+    for s, sh in self._live():
+      if cells.parts[s].items.shape[0]:
+        mine, wmine = sh.index._exact_sums(cells.parts[s], scale)
+        with torch.cuda.device(self.device):
+          sums += mine.to(self.device)
+          wsums += wmine.to(self.device)
+    return sums, wsums
+
+  def _assign(self, embds, weights, train):
+    """The assignment step over the shards: centroids on the primary and the training items (global numbers, int64
+    ascending on the primary, None = every item) -> (scores [T, 1], cells [T, 1]) on the primary in the order of the
+    training items.  One VideoIndex of the centroids per distinct device, in the gallery's dtype; every shard's part of
+    the sample -- its local numbers, ascending as the global ones are -- is assigned by centroids.neighbours(k=1,
+    source=shard.index, items=...) and the rows are scattered to their places.  With a sample, finding a shard's part
+    waits for the device once per shard."""
+    total = self.num_items if train is None else train.shape[0]
+    with torch.cuda.device(self.device):
+      scores = torch.empty(total, 1, device=self.device, dtype=torch.float32)
+      best = torch.empty(total, 1, device=self.device, dtype=torch.int64)
+    centroids = {}
+    for s, sh in self._live():
+      if train is None:
+        at, local = sh.ids[:sh.num_items], None
+      else:
+        at = torch.nonzero(self._shard_of[train] == s)[:, 0]
+        if at.shape[0] == 0:
+          continue
+        local = self._local_of[train[at]].to(sh.device)
+      with torch.cuda.device(sh.device):
+        if sh.device not in centroids:
+          centroids[sh.device] = VideoIndex(embds.to(sh.device), weights.to(sh.device), dtype=self.dtype)
+        mine, cell = centroids[sh.device].neighbours(k=1, source=sh.index, items=local)
+      with torch.cuda.device(self.device):
+        scores[at] = mine.to(self.device)
+        best[at] = cell.to(self.device)
+    return scores, best
 
   def _search_probed(self, q, qw, cells, probes, k):
     """`search_probed` behind its checks: q, qw and probes on the primary.  Every shard that holds items of a cell answers

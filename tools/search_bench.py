@@ -151,7 +151,13 @@ into its assignment (the centroid index and neighbours(k=1, source=index)) and i
 --runs rounds on device events, every variant once per round, interleaved; median and spread.  (d) train_cells(1 024,
 iters=10) once on a host clock, its objective and moved, and recall@10 of search_cells against search at nprobe 1, 4, 16
 and 64 with its cells beside the cells of the sampled centres on the same data and queries -- reported, never a test.
-Default output profiles/search_kmeans_bench.json."""
+Default output profiles/search_kmeans_bench.json.
+
+--kmeans-exact times the exact (integer-sum) k-means update on the data of --kmeans, in one process and interleaved rounds:
+the sum_scale pass; cell_centroids with and without exact=True; one Lloyd iteration (assignment, cells, update) each way;
+the exact update and iteration on a 4-shard ShardedVideoIndex on the same device; and it checks once that a permuted
+re-insertion of the stored rows gives bit-identical exact centroids.  Default output
+profiles/search_kmeans_exact_bench.json."""
 import argparse
 import json
 import math
@@ -816,29 +822,31 @@ def where_mode(a, dev):
   return row
 
 
-def clustered_gallery(dev, nv, ncells, nq_all, chunk=8192):
+def clustered_gallery(dev, nv, ncells, nq_all, chunk=8192, shards=0):
   """The data of --cells and --kmeans, from seed 0: nv items drawn from ncells planted clusters (a unit centre plus unit
   noise per expert, renormalised; softmax weights) on a float32, a bf16 and an fp8 index, nq_all queries that are noisy
-  copies of stored items, and ncells randomly sampled centre items -> (indexes by dtype name, q, qw, centres)."""
+  copies of stored items, and ncells randomly sampled centre items -> (indexes by dtype name, q, qw, centres).  shards > 0:
+  the same chunks also go into a ShardedVideoIndex of that many shards on dev per dtype, returned as a fifth element."""
   gen = torch.Generator(device=dev).manual_seed(0)
   nrm = lambda x: torch.nn.functional.normalize(x, dim=-1)
   noise = lambda n: torch.randn(n, M, D, device=dev, generator=gen) / math.sqrt(D)
   planted = nrm(torch.randn(ncells, M, D, device=dev, generator=gen))
   dtypes = {'float32': torch.float32, 'bfloat16': torch.bfloat16, 'float8_e4m3fn': torch.float8_e4m3fn}
   idx = {n: VideoIndex.empty(nv, M, D, dev, dtype=t) for n, t in dtypes.items()}
+  sharded = {n: ShardedVideoIndex.empty(nv, M, D, [dev] * shards, dtype=t) for n, t in dtypes.items()} if shards else {}
   source = torch.randint(0, nv, (nq_all,), device=dev, generator=gen)       # a query is a noisy copy of a stored item
   q = torch.empty(nq_all, M, D, device=dev)
   for at in range(0, nv, chunk):
     g = nrm(planted[torch.randint(0, ncells, (chunk,), device=dev, generator=gen)] + noise(chunk))
     gw = torch.softmax(torch.randn(chunk, M, device=dev, generator=gen), -1)
-    for index in idx.values():
+    for index in list(idx.values()) + list(sharded.values()):
       index.add(g, gw)
     mine = (source >= at) & (source < at + chunk)
     q[mine] = g[source[mine] - at]
   q = nrm(q + noise(nq_all))
   qw = torch.softmax(torch.randn(nq_all, M, device=dev, generator=gen), -1)
   centres = torch.randperm(nv, device=dev, generator=gen)[:ncells]
-  return idx, q, qw, centres
+  return (idx, q, qw, centres, sharded) if shards else (idx, q, qw, centres)
 
 
 HBM_PEAK = 8.0e12  # bytes/s, HBM3E specification
@@ -924,6 +932,93 @@ def kmeans_mode(a, dev):
         n, 1e3 * up['seconds_median'], 100 * up['fraction_of_hbm_peak'], 1e3 * ref['seconds_median'],
         1e3 * cell['assignment']['seconds_median'], row[n + '/recall_at_10']['trained'],
         row[n + '/recall_at_10']['sampled_centres']), file=sys.stderr)
+  return row
+
+
+def kmeans_exact_mode(a, dev):
+  """The exact k-means update against the float update (module docstring, --kmeans-exact)."""
+  from mmt_amd import search
+  nv, ncells, shards = SHAPES['S3'][1], 1024, 4
+  idx, _, _, centres, sharded_idx = clustered_gallery(dev, nv, ncells, 64, shards=shards)
+  row = {'NV': nv, 'num_cells': ncells, 'shards': shards, 'sum_piece': search.SUM_PIECE, 'sum_slab': search.SUM_SLAB,
+         'hbm_peak_bytes_per_second': HBM_PEAK,
+         'not_measured': ['kernel times from a profiler trace: every variant is timed as calls on device events',
+                          'shards on more than one physical device', 'num_cells other than 1 024',
+                          'a training sample smaller than the gallery (items=)']}
+  same = lambda x, y: bool(all(torch.equal(u.view(torch.int32), v.view(torch.int32)) for u, v in zip(x, y)))
+  pair = lambda: (torch.zeros(ncells, M, D, device=dev), torch.zeros(ncells, M, device=dev))
+  for n, index in idx.items():
+    sharded = sharded_idx[n]
+    sampled = index.cells_from_centres(centres)
+    ids = torch.empty(nv, device=dev, dtype=torch.int64)
+    ids[sampled.items] = torch.repeat_interleave(torch.arange(ncells, device=dev), sampled.sizes)
+    scells = sharded.cells(ids, ncells)
+    labelled = int(sampled.items.shape[0])
+    row_bytes = labelled * (M * D * index.folded.element_size() + M * 4 + (4 if index.scales is not None else 0))
+    start, out, tmp = index.cell_centroids(sampled, exact=True), pair(), pair()
+
+    def forget(ix):
+      ix._sum_scale = None
+      return ix.sum_scale()
+
+    def iteration(ix, how):
+      if ix is index:
+        _, best = VideoIndex(start[0], start[1], dtype=index.dtype).neighbours(k=1, source=index)
+      else:
+        _, best = ix._assign(start[0], start[1], None)
+      return ix.cell_centroids(ix.cells(best[:, 0].contiguous(), ncells), out=tmp, **how)
+
+    fns = {'sum_scale': lambda: forget(index),
+           'update_float': lambda: index.cell_centroids(sampled, out=out),
+           'update_exact': lambda: index.cell_centroids(sampled, out=out, exact=True),
+           'iteration_float': lambda: iteration(index, {}),
+           'iteration_exact': lambda: iteration(index, {'exact': True}),
+           'sharded_sum_scale': lambda: forget(sharded),
+           'sharded_update_exact': lambda: sharded.cell_centroids(scells, out=out, exact=True),
+           'sharded_iteration_exact': lambda: iteration(sharded, {'exact': True})}
+    ts, peaks = {v: [] for v in fns}, {v: 0 for v in fns}
+    for _ in range(a.runs):            # interleaved: drift hits the variants alike
+      for v, fn in fns.items():
+        t, _, peak, _ = timed(fn, a.min_seconds)
+        ts[v].append(t)
+        peaks[v] = max(peaks[v], peak)
+    cell = {v: dict(seconds_median=float(np.median(ts[v])), seconds_spread=max(ts[v]) - min(ts[v]), seconds_runs=ts[v],
+                    peak_mem_growth_bytes=int(peaks[v])) for v in fns}
+    for v in ('update_float', 'update_exact', 'sharded_update_exact'):
+      cell[v].update(bytes_read=row_bytes, bytes_per_second=row_bytes / cell[v]['seconds_median'],
+                     fraction_of_hbm_peak=row_bytes / cell[v]['seconds_median'] / HBM_PEAK)
+    med = lambda v: cell[v]['seconds_median']
+    # a permuted re-insertion, once: the stored rows moved as they are, the labels alike
+    perm = torch.randperm(nv, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
+    again = VideoIndex.empty(nv, M, D, dev, dtype=index.dtype)
+    again.folded.view(torch.uint8).copy_(index.folded.view(torch.uint8)[perm])
+    again.weights.copy_(index.weights[perm])
+    if index.scales is not None:
+      again.scales.copy_(index.scales[perm])
+    again.num_items = nv
+    moved = again.cell_centroids(again.cells(ids[perm], ncells), exact=True)
+    moved_float = again.cell_centroids(again.cells(ids[perm], ncells))
+    del again
+    cell['summary'] = dict(
+        scale=repr(index.sum_scale()),
+        exact_over_float_update_seconds=med('update_exact') / med('update_float'),
+        exact_over_float_iteration_seconds=med('iteration_exact') / med('iteration_float'),
+        iteration_spreads_combined=cell['iteration_exact']['seconds_spread'] + cell['iteration_float']['seconds_spread'],
+        sharded_over_single_exact_update_seconds=med('sharded_update_exact') / med('update_exact'),
+        sharded_over_single_exact_iteration_seconds=med('sharded_iteration_exact') / med('iteration_exact'),
+        sum_scale_share_of_exact_iteration=med('sum_scale') / med('iteration_exact'),
+        sharded_centroids_same_bits_as_single=same(sharded.cell_centroids(scells, exact=True), start),
+        sharded_scale_equals_single=sharded.sum_scale() == index.sum_scale(),
+        permuted_reinsertion_same_bits_exact=same(moved, start),
+        permuted_reinsertion_same_bits_float=same(moved_float, index.cell_centroids(sampled)),
+        max_abs_difference_exact_to_float_centroids=float((start[0] - index.cell_centroids(sampled)[0]).abs().max()))
+    row[n + '/times'] = cell
+    print('%s: sum_scale %.3f ms; update float %.3f ms, exact %.3f ms (%.2f TB/s); iteration float %.3f ms, exact %.3f ms '
+          '(x %.3f); %d shards: update %.3f ms, iteration %.3f ms; permuted same bits: %s' % (
+              n, 1e3 * med('sum_scale'), 1e3 * med('update_float'), 1e3 * med('update_exact'),
+              cell['update_exact']['bytes_per_second'] / 1e12, 1e3 * med('iteration_float'), 1e3 * med('iteration_exact'),
+              cell['summary']['exact_over_float_iteration_seconds'], shards, 1e3 * med('sharded_update_exact'),
+              1e3 * med('sharded_iteration_exact'), cell['summary']['permuted_reinsertion_same_bits_exact']), file=sys.stderr)
   return row
 
 
@@ -1407,6 +1502,9 @@ def main():
   ap.add_argument('--kmeans', action='store_true', help='time the k-means update (cell_centroids) at 262 144 clustered items '
                   'in 1 024 cells on a float32, a bf16 and an fp8 index against dequantise + index_add_, one Lloyd iteration '
                   'split into assignment and update, and recall@10 of search_cells with train_cells(1 024, iters=10)')
+  ap.add_argument('--kmeans-exact', action='store_true', help='time the exact k-means update (cell_centroids(exact=True)) '
+                  'against the float update on the data of --kmeans: sum_scale, the update, one Lloyd iteration each way, '
+                  'the same on a 4-shard ShardedVideoIndex on one device, and a permuted re-insertion checked once')
   ap.add_argument('--shapes', default='S1,S2,S3')
   ap.add_argument('--out', default=None)
   ap.add_argument('--min-seconds', type=float, default=0.5)
@@ -1485,6 +1583,17 @@ def main():
   if not torch.cuda.is_available():
     raise SystemExit('search_bench needs the GPU')
   dev = torch.device('cuda', 0)
+  if a.kmeans_exact:
+    res = {'M': M, 'd': D, 'device': torch.cuda.get_device_name(0), 'mode': 'kmeans-exact', 'runs': a.runs,
+           'min_seconds': a.min_seconds}
+    res.update(kmeans_exact_mode(a, dev))
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                'search_kmeans_exact_bench.json')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+      json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return
   if a.kmeans:
     res = {'M': M, 'd': D, 'k': K, 'device': torch.cuda.get_device_name(0), 'mode': 'kmeans', 'runs': a.runs,
            'min_seconds': a.min_seconds}
